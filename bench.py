@@ -9,9 +9,15 @@ in HBM. With N > 1 (launched by `python -m torch.distributed.run`, one rank per 
 there is no data-path collective inside the timed region — the optional RCCL all-gather of
 deformed positions is timed separately and reported in `config`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` (HIP-event
-timing of the dominant kernel against the ~8 TB/s HBM peak) and `cpu_baseline` (the CPU oracle —
-all-core JavaScript skin when Node is available, else the threaded C port — on a bounded sample).
+Prints ONE JSON line on rank 0. A plain run does only what the headline (`value`, `ms_per_step`) needs: setup, the
+launch-shape search, warm-up, the K timed steps, and the line. `--full` adds everything else the line can carry: `roofline`
+(HIP-event timing of the dominant kernel against the ~8 TB/s HBM peak), `cpu_baseline` (the CPU oracle — all-core JavaScript
+skin when Node is available, else the threaded C port — on a bounded sample), the per-frame loops with pose upload, the
+second loop with two frames in flight and, at N > 1, the RCCL phase; without `--full` those fields are null (except `roofline`
+where two frames in flight were calibrated faster: the headline rule then needs the kernel's timing).
+`--dump-outputs DIR` writes what the last timed step computed (deformed positions and normals, float32, rows in global
+vertex order, instance-major for crowds; a fixed seeded sample of rows when the whole output exceeds 64 MB) as
+DIR/positions.npy and DIR/normals.npy.
 
 `--gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment) re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N`: a plain `python bench.py --gpus 8` IS an 8-rank run. A launcher whose
@@ -80,7 +86,29 @@ def parse_args():
     ap.add_argument("--no-sampled-loop", action="store_true", help="skip the secondary per-frame loop with the motion sampled on the GPU")
     ap.add_argument("--no-numa-bind", action="store_true", help="leave the process where the launcher put it instead of binding it to the cores of its GPU's NUMA node")
     ap.add_argument("--no-autotune", action="store_true", help="skip rz_autotune (setup-time search over launch shapes) and use the built-in heuristics")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (event-timed kernel), CPU baseline, per-frame loops, the second "
+                         "loop with two frames in flight, the RCCL phase at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the positions and normals of the last timed step as DIR/positions.npy and DIR/normals.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.allgather or args.rehearse_rccl):
+        ap.error("--allgather / --rehearse-rccl time the RCCL phase, which runs with --full only")
+    return args
+
+
+DUMP_BYTES = 64 << 20               # --dump-outputs: at most this much in all
+DUMP_SAMPLE_ROWS = 1 << 21          # rows of a seeded sample (2 x 24 MB of float32) when every row would not fit
+
+
+def dump_rows(rows_total):
+    """Global row indices (instance * verts + vertex) that --dump-outputs writes, ascending: every row when positions + normals
+    (24 B per row) fit DUMP_BYTES, else a fixed seeded sample that depends on rows_total only. None = every row."""
+    if rows_total * 24 <= DUMP_BYTES:
+        return None
+    return np.sort(np.random.default_rng(0x5EED).choice(rows_total, size=DUMP_SAMPLE_ROWS, replace=False))
 
 
 def cpu_baseline(args, mesh, deltas, mw, sparse=None):
@@ -428,7 +456,7 @@ def main():
     # what a WebGPU queue does with consecutive command buffers. The roofline below is always that of ONE kernel on one
     # stream (rz_time_frames); with --frames-in-flight 2 the timed steps themselves alternate.
     fork = None
-    if args.frames_in_flight != "1" or not args.no_pair_loop:
+    if args.frames_in_flight != "1" or (args.full and not args.no_pair_loop):
         try:
             fork = ctx.fork()
             put_pose(fork)
@@ -497,6 +525,28 @@ def main():
         sync_pair()
         return timed(lambda: ctx.time_span(args.steps, fork, lead=LEAD), sync_pair)
 
+    # --dump-outputs: the rows of the global output this rank holds (vertex shard [b, b + n), or instances [inst_begin, inst_begin + I)
+    # of the whole mesh), read from the context that ran the last step of a timed loop straight after it
+    rows_sel = dump_rows(I_total * V_total) if args.dump_outputs else None
+    rows_lo = inst_begin * V_total if crowd else b
+
+    def read_rows(c):
+        if rows_sel is not None:
+            mine = rows_sel[(rows_sel >= rows_lo) & (rows_sel < rows_lo + I * n)] - rows_lo
+        pos, nrm = [], []
+        for i in range(I):
+            if rows_sel is not None:
+                v = mine[np.searchsorted(mine, i * n):np.searchsorted(mine, (i + 1) * n)] - i * n
+                if len(v) == 0:
+                    continue
+            p, q = c.read(instance=i)
+            pos.append(p if rows_sel is None else p[v])
+            nrm.append(q if rows_sel is None else q[v])
+        if not pos:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        return np.concatenate(pos), np.concatenate(nrm)
+    last_out = {}
+
     kernel_reps = []
 
     def kernel_timing():
@@ -510,18 +560,25 @@ def main():
     # secondary number), then the kernel's own timing straight after them, in the same state of the GPU, then anything that
     # runs two kernels at once. A kernel cannot take longer than the step that contains it: if the event timing disagrees
     # with the one-stream step by more than 3 % it is measured again, once, and the line says so.
+    # A plain run times the kernel and the pair loop only when two frames in flight were calibrated faster: the headline rule below needs both.
     one_ms, pair_ms, pair_wall = None, None, None
     one_el, one_wall = one_stream()     # always: it is the headline whenever the overlapped step would be shorter than its own kernel
     one_ms = one_el / args.steps * 1e3
-    timing = kernel_timing()
-    kcheck = {"rule": "kernel_ms <= 1.03 x ms_per_step_one_stream", "remeasured": False}
-    if one_ms is not None and timing["deform_kernel_ms"] > 1.03 * one_ms:
+    if args.dump_outputs:
+        last_out[1] = read_rows(ctx)
+    timing, kcheck = None, None
+    if args.full or in_flight == 2:
         timing = kernel_timing()
-        kcheck["remeasured"] = True
-    kcheck["ok"] = one_ms is None or timing["deform_kernel_ms"] <= 1.03 * one_ms
-    if fork is not None and (in_flight == 2 or not args.no_pair_loop):
+        kcheck = {"rule": "kernel_ms <= 1.03 x ms_per_step_one_stream", "remeasured": False}
+        if one_ms is not None and timing["deform_kernel_ms"] > 1.03 * one_ms:
+            timing = kernel_timing()
+            kcheck["remeasured"] = True
+        kcheck["ok"] = one_ms is None or timing["deform_kernel_ms"] <= 1.03 * one_ms
+    if fork is not None and (in_flight == 2 or (args.full and not args.no_pair_loop)):
         pair_el, pair_wall = paired()
         pair_ms = pair_el / args.steps * 1e3
+        if args.dump_outputs:
+            last_out[2] = read_rows(fork if args.steps % 2 == 0 else ctx)      # rz_deform_pair: frame f runs on (ctx, fork)[f & 1]
     # Headline rule (round 5): a step cannot be shorter than the kernel it contains. When two frames in flight bring the step UNDER the
     # event-timed kernel (small frames: C3 4.4 us per step against a 6.4 us kernel) that number is throughput of two overlapped frames,
     # not the time of a frame: `value` / `ms_per_step` then stay the ONE-STREAM loop and the overlap is reported beside it
@@ -539,8 +596,10 @@ def main():
         fork.close()
         fork = None
 
-    kern_s = timing["deform_kernel_ms"] * 1e-3
-    achieved = timing["algorithmic_bytes_per_frame"] / kern_s / 1e9
+    tget = (timing or {}).get           # (null fields where the kernel was not timed)
+    if timing is not None:
+        kern_s = timing["deform_kernel_ms"] * 1e-3
+        achieved = timing["algorithmic_bytes_per_frame"] / kern_s / 1e9
     kernel_name = ctx.kernel_name()
     # HBM bytes per launch from the PMC counters are collected OFFLINE (rocprofv3 cannot run inside this process):
     # tools/gpu_profile.sh + tools/parse_prof.py store them per (workload shape, kernel); this line looks up the kernel the
@@ -606,17 +665,19 @@ def main():
             dt = None
         vals = gather(dt)
         return None if any(v is None for v in vals) else max(vals)
-    if frames is not None:
-        primary_call = ctx.frame_call("sampled", frame_table(frames))
-    elif quats is not None:
-        primary_call = ctx.frame_call("local", quats, mws)
-    else:
-        primary_call = ctx.frame_call("world", worlds, mws)
-    with_upload_ms = per_frame_loop(*primary_call)
+    with_upload_ms = None
+    if args.full:
+        if frames is not None:
+            primary_call = ctx.frame_call("sampled", frame_table(frames))
+        elif quats is not None:
+            primary_call = ctx.frame_call("local", quats, mws)
+        else:
+            primary_call = ctx.frame_call("world", worlds, mws)
+        with_upload_ms = per_frame_loop(*primary_call)
     # the same per-frame loop with two frames in flight: pose f + 1 is uploaded and its frame enqueued on the fork while frame f
     # still runs on the context (and the other way round)
     with_upload_pair_ms = None
-    if not args.no_pair_loop:
+    if args.full and not args.no_pair_loop:
         fk2, call_b = None, None
         try:
             fk2 = ctx.fork()
@@ -647,7 +708,7 @@ def main():
     # caller's pose solve: one memmove of the pre-packed rows into the slot (a solve writes them there in the first place);
     # _protocol_only writes nothing and is what the library itself costs per frame.
     mapped_ms, mapped_bare_ms, mapped_pair_ms = None, None, None
-    if crowd and quats is None and frames is None and hasattr(ctx, "mapped_frame_call"):
+    if args.full and crowd and quats is None and frames is None and hasattr(ctx, "mapped_frame_call"):
         import ctypes
         rows = np.ascontiguousarray(worlds.reshape(I, B, 4, 4)[:, :, :, :3], dtype=np.float32)
         src = rows.ctypes.data
@@ -680,7 +741,7 @@ def main():
     # ... and the same loop when the motion lives on the GPU (rz_set_pose_sampled: ONE float per instance per frame, bones
     # sampled + hierarchy solved by rz_fk_kernel): the per-frame loop that does not pay for the pose upload at any N
     sampled_ms = None
-    if not args.no_sampled_loop:
+    if args.full and not args.no_sampled_loop:
         sampled_call = None
         try:
             if frames is None:
@@ -699,16 +760,18 @@ def main():
     # one record per rank, so a slow or oddly planned GPU is visible in the scaling file — gathered BEFORE the RCCL phase below,
     # so that the line has them whatever happens there
     eff = {k: ctx.get_tuning(k) for k in ("effective_split", "effective_grid", "effective_inst_group", "effective_subsets", "effective_subset_bones", "effective_inst_lds")}
-    mine = {"rank": rank, "device": local_rank, "verts": n, "instances": I, "instance_begin": inst_begin, "kernel_ms": timing["deform_kernel_ms"], "frame_ms": timing["frame_ms"],
+    mine = {"rank": rank, "device": local_rank, "verts": n, "instances": I, "instance_begin": inst_begin, "kernel_ms": tget("deform_kernel_ms"), "frame_ms": tget("frame_ms"),
             "kernel": kernel_name, "grid": eff["effective_grid"], "morph_split": eff["effective_split"], "autotuned": tuned is not None, "rccl": None}
     per_rank = gather(mine)
+    # --dump-outputs: the last step of the loop the headline reports, every rank's rows gathered to rank 0 in rank order (= global order)
+    dumped = gather(last_out[headline_in_flight]) if args.dump_outputs else None
 
     # ---- RCCL: at N > 1 every rank joins a communicator made by the library's own entry points, says what the
     # communicator reports about itself, and the all-gather of deformed positions is timed — OUTSIDE `value`.
     # It runs LAST and under a watchdog: a multi-GPU collective is the one thing a 1-GPU box cannot rehearse, and a hang in it
     # must cost the line its RCCL fields, not the line itself. ----
     ag_ms, hard_exit = None, False
-    want_comm = not crowd and ((world_size > 1 and not args.no_allgather and (not args.share_gpu or args.rehearse_rccl)) or args.allgather)
+    want_comm = args.full and not crowd and ((world_size > 1 and not args.no_allgather and (not args.share_gpu or args.rehearse_rccl)) or args.allgather)
     if want_comm:
         import threading
         box = {"done": False, "ranks": None, "ag_ms": None}
@@ -763,12 +826,13 @@ def main():
             hard_exit = True            # a collective is stuck: no orderly shutdown is possible
     elif world_size > 1:
         why = ("a crowd is sharded along the instance axis: no exchange, no communicator (SURVEY 8e)" if crowd else
-               "--share-gpu: ranks share a GPU, RCCL needs one GPU per rank" if args.share_gpu else "--no-allgather")
+               "--share-gpu: ranks share a GPU, RCCL needs one GPU per rank" if args.share_gpu else
+               "--no-allgather" if args.no_allgather else "measured with --full only")
         for r in per_rank:
             r["rccl"] = {"skipped": why}
 
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
         try:
             if full_affinity is not None:
                 os.sched_setaffinity(0, full_affinity)      # the CPU baseline runs on ALL the host's cores, not on one node's
@@ -778,7 +842,7 @@ def main():
 
     if rank == 0:
         verts = V_total * I_total * args.steps
-        kms = [r["kernel_ms"] for r in per_rank]
+        kms = [r["kernel_ms"] for r in per_rank if r["kernel_ms"] is not None]
         names = {(1000000, 256, 64, 1): "C5", (30000, 200, 0, 256): "C4", (30000, 200, 64, 1): "C3", (30000, 200, 0, 1): "C2"}
         shard_how = "instance-sharded" if crowd else "vertex-sharded"
         if sparse_kind == "demo":
@@ -819,6 +883,7 @@ def main():
                 "autotune_rule": "heuristic plan (entry 0) unless a candidate's median-of-5-rounds time, MAX over ranks, is >= 2 % faster and its slowest round beats the heuristic's fastest; every rank adopts the same entry",
                 "autotune_pick": tune_pick,
                 "autotune_table": None if tune_table is None else [{k: (round(e[k], 6) if isinstance(e[k], float) else e[k]) for k in e} for e in tune_table],
+                "full": args.full,           # false: cpu_baseline, the per-frame loops, the RCCL phase (and roofline, unless the headline rule needed it) are null
                 "graph_replay": bool(args.graph),
                 "morph_split": eff["effective_split"],
                 "grid": eff["effective_grid"],
@@ -826,8 +891,8 @@ def main():
                 "inst_subsets": eff["effective_subsets"],
                 "inst_subset_bones": eff["effective_subset_bones"],
                 "inst_lds_bytes": eff["effective_inst_lds"],
-                "frame_ms_events": timing["frame_ms"],
-                "prep_kernel_ms": timing["prep_kernel_ms"],
+                "frame_ms_events": tget("frame_ms"),
+                "prep_kernel_ms": tget("prep_kernel_ms"),
                 "frame_ms_with_pose_upload": with_upload_ms,
                 "frame_ms_device_sampled_pose": sampled_ms,
                 "frame_ms_with_pose_upload_two_in_flight": with_upload_pair_ms,
@@ -853,10 +918,10 @@ def main():
                                    % ("_local" if args.device_fk else ""),
                 "allgather_ms": ag_ms,
                 "allgather_note": "ncclAllGather of the deformed positions over the library's own communicator, timed after and outside the K steps",
-                "kernel_ms_min_over_ranks": min(kms), "kernel_ms_max_over_ranks": max(kms),
+                "kernel_ms_min_over_ranks": min(kms, default=None), "kernel_ms_max_over_ranks": max(kms, default=None),
                 "ranks": per_rank,
             },
-            "roofline": {
+            "roofline": None if timing is None else {
                 "bound": "hbm",
                 "kernel": kernel_name,
                 "achieved": achieved,
@@ -876,6 +941,10 @@ def main():
             },
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "positions.npy"), np.concatenate([d[0] for d in dumped]))
+            np.save(os.path.join(args.dump_outputs, "normals.npy"), np.concatenate([d[1] for d in dumped]))
     else:
         out = None
     if not hard_exit:

@@ -52,7 +52,7 @@ def _check(d, n_gpus, steps, verts):
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--verts", "40000", "--bones", "64", "--morphs", "8",
-                                   "--steps", "20", "--warmup", "3", "--cpu-sample-verts", "20000", "--clock-warm-seconds", "0.2"], cwd=ROOT, timeout=600).decode()
+                                   "--steps", "20", "--warmup", "3", "--cpu-sample-verts", "20000", "--clock-warm-seconds", "0.2", "--full"], cwd=ROOT, timeout=600).decode()
     d = _last_json(out)
     _check(d, 1, 20, 40000)
     cb = d["cpu_baseline"]
@@ -64,7 +64,8 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-           "--verts", "50000", "--bones", "64", "--morphs", "8", "--share-gpu", "--dist-backend", "gloo", "--no-cpu-baseline", "--clock-warm-seconds", "0.2"]
+           "--verts", "50000", "--bones", "64", "--morphs", "8", "--share-gpu", "--dist-backend", "gloo", "--no-cpu-baseline", "--clock-warm-seconds", "0.2",
+           "--full"]
     out = subprocess.check_output(cmd, cwd=ROOT, env=env, timeout=900, stderr=subprocess.STDOUT).decode()
     d = _last_json(out)
     _check(d, 2, 20, 50000)
@@ -78,7 +79,7 @@ def test_bench_gpus_2_without_a_launcher_is_a_two_rank_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--verts", "50000", "--bones", "64",
-           "--morphs", "8", "--share-gpu", "--dist-backend", "gloo", "--no-cpu-baseline", "--clock-warm-seconds", "0.2"]
+           "--morphs", "8", "--share-gpu", "--dist-backend", "gloo", "--no-cpu-baseline", "--clock-warm-seconds", "0.2", "--full"]
     out = subprocess.check_output(cmd, cwd=ROOT, env=env, timeout=900, stderr=subprocess.STDOUT).decode()
     d = _last_json(out)
     _check(d, 2, 20, 50000)
@@ -113,15 +114,45 @@ def test_bench_single_rank_rccl_evidence_and_sparse_configs():
     """--allgather at N = 1 builds the RCCL communicator through rz_comm_init and reports what the communicator says
     (ncclCommCount / ncclCommUserRank); --config demo / sparse2 are the sparse real-shape lines of SURVEY 8d."""
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--verts", "40000", "--bones", "64", "--morphs", "8", "--steps", "20",
-                                   "--warmup", "3", "--no-cpu-baseline", "--clock-warm-seconds", "0.2", "--allgather"], cwd=ROOT, timeout=600).decode()
+                                   "--warmup", "3", "--no-cpu-baseline", "--clock-warm-seconds", "0.2", "--allgather", "--full"], cwd=ROOT, timeout=600).decode()
     d = _last_json(out)
     rc = d["config"]["ranks"][0]["rccl"]
     assert rc["comm_count"] == 1 and rc["comm_user_rank"] == 0 and rc["version"] > 0 and d["config"]["allgather_ms"] > 0
     for cfg, verts in (("demo", 28842), ("sparse2", 28842)):
         out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "50", "--warmup", "5",
-                                       "--clock-warm-seconds", "0.2", "--no-sampled-loop"], cwd=ROOT, timeout=600).decode()
+                                       "--clock-warm-seconds", "0.2", "--no-sampled-loop", "--full"], cwd=ROOT, timeout=600).decode()
         d = _last_json(out)
         assert d["n_gpus"] == 1 and d["config"]["verts_total"] == verts and d["config"]["morph_layout"] == "sparse CSR"
         assert "2, " in d["roofline"]["kernel"] or ", 2," in d["roofline"]["kernel"], d["roofline"]["kernel"]     # MODE 2 = sparse
         assert d["cpu_baseline"]["value"] > 0 and "sparse" in d["cpu_baseline"]["sample"]
         assert d["roofline"]["algorithmic_bytes_per_launch"] > verts * 60
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", ["mesh", "crowd"])
+def test_plain_bench_line_and_its_dumped_outputs_match_the_oracle(tmp_path, shape):
+    """A plain run (no --full) prints the headline without the fields that need runs of their own, and --dump-outputs writes the
+    last timed step: the whole deformed mesh (every instance of a crowd, instance-major), float32, equal to the CPU oracle."""
+    import numpy as np
+
+    import oracle
+    from helpers import assert_parity
+    from reze_engine_amd import synth
+    V, B, M, I = (40000, 64, 8, 1) if shape == "mesh" else (6000, 32, 0, 5)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--verts", str(V), "--bones", str(B), "--morphs", str(M),
+                                   "--instances", str(I), "--steps", "7", "--warmup", "3", "--clock-warm-seconds", "0.2",
+                                   "--dump-outputs", str(tmp_path)], cwd=ROOT, timeout=600).decode()
+    d = _last_json(out)
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and abs(d["value"] - V * I / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    c = d["config"]
+    assert c["full"] is False and d["cpu_baseline"] is None and c["frame_ms_with_pose_upload"] is None and c["allgather_ms"] is None
+    # the kernel is timed in a plain run only where the headline rule needs it: two frames in flight calibrated faster
+    assert (d["roofline"] is None) == (c["frames_in_flight_calibrated"] == 1), (c["frames_in_flight_calibrated"], d["roofline"])
+    pos, nrm = np.load(tmp_path / "positions.npy"), np.load(tmp_path / "normals.npy")
+    assert pos.dtype == nrm.dtype == np.float32 and pos.shape == nrm.shape == (V * I, 3)
+    mesh = synth.make_mesh_range(V, B, 0, V)
+    deltas, mw = synth.make_morphs_dense_range(V, M, 0, V) if M else (None, None)
+    for k in range(I):
+        world = mesh["world"] if I == 1 else synth.make_pose(mesh["parents"], mesh["bind"], B, seed=1000 + k)
+        pr, nr = oracle.deform(mesh["pos"], mesh["nrm"], mesh["joints"], mesh["weights"], world, mesh["inv_bind"], deltas, mw, threads=4)
+        assert_parity(pos[k * V:(k + 1) * V], nrm[k * V:(k + 1) * V], pr, nr, "dumped instance %d" % k)

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = textwrap.dedent('''
     """Stand-in for reze_engine_amd (tests/test_bench_rehearsal.py): the real synth / shard / capi modules, a DeformContext without a GPU."""
     import importlib.util, os, sys, time
+    import numpy as np
     _real = os.path.join(%(root)r, "reze-engine_amd")
     _spec = importlib.util.spec_from_file_location("reze_engine_amd_real", os.path.join(_real, "__init__.py"), submodule_search_locations=[_real])
     _pkg = importlib.util.module_from_spec(_spec)
@@ -29,20 +30,27 @@ STUB = textwrap.dedent('''
     US_PER_KVERT = 40.0                      # a frame of 1000 vertices "takes" 40 us
 
 
+    def _log(*what):
+        """REZE_STUB_LOG: one line per call of the measurements a plain run must not make"""
+        if os.environ.get("REZE_STUB_LOG"):
+            with open(os.environ["REZE_STUB_LOG"], "a") as f:
+                f.write(" ".join(str(w) for w in (os.environ.get("RANK", "0"),) + what) + "\\n")
+
+
     class DeformContext:
         def __init__(self, device=0, lib=None):
             self.V = 0; self.I = 1; self.busy_until = 0.0; self.tuning = {}
         def _frame_s(self): return self.V * self.I / 1000.0 * US_PER_KVERT * 1e-6
         def _enqueue(self, frames):
             self.busy_until = max(self.busy_until, time.perf_counter()) + frames * self._frame_s()
-        def upload_mesh(self, pos, nrm, j, w): self.V = len(pos)
-        def upload_skeleton(self, ib): pass
+        def upload_mesh(self, pos, nrm, j, w): self.V, self.pos, self.nrm = len(pos), np.asarray(pos, np.float32), np.asarray(nrm, np.float32)
+        def upload_skeleton(self, ib): self.B = len(ib)
         def upload_morphs_dense(self, d): pass
         def upload_morphs_sparse(self, *a): pass
         def upload_skeleton_topology(self, *a, **k): pass
         def upload_animation(self, *a, **k): pass
         def set_instances(self, n): self.I = n
-        def set_pose(self, *a): pass
+        def set_pose(self, world, *a): self.off = np.asarray(world, np.float64).reshape(-1, self.B * 16).sum(1)     # one number per instance
         def set_pose_local(self, *a, **k): pass
         def set_pose_sampled(self, *a): pass
         def set_tuning(self, **kw): self.tuning.update(kw)
@@ -56,6 +64,7 @@ STUB = textwrap.dedent('''
         def deform(self): self._enqueue(1)
         def deform_n(self, frames): self._enqueue(frames)
         def deform_pair(self, other, frames):
+            _log("deform_pair", frames)
             if os.environ.get("REZE_STUB_PAIR") == "fades":
                 # two frames in flight look a tenth faster during the calibration (its three calls) and run a tenth slower afterwards
                 self.pair_calls = getattr(self, "pair_calls", 0) + 1
@@ -67,6 +76,7 @@ STUB = textwrap.dedent('''
             if d > 0: time.sleep(d)
         def time_span(self, frames, other=None, lead=0):
             # the stand-in's "events": virtual GPU time from the first TIMED frame's start to the last frame's end
+            _log("time_span", frames, "pair" if other is not None else "one")
             if lead: self.deform_n(lead)
             t0 = max(self.busy_until, time.perf_counter())
             if other is None: self.deform_n(frames)
@@ -75,14 +85,21 @@ STUB = textwrap.dedent('''
             if other is not None: other.sync()
             return (max(self.busy_until, other.busy_until if other is not None else 0.0) - t0) * 1e3
         def fork(self):
-            f = DeformContext(); f.V = self.V; f.I = self.I; return f
+            _log("fork")
+            f = DeformContext(); f.V, f.I, f.B, f.pos, f.nrm = self.V, self.I, self.B, self.pos, self.nrm; return f
         def frame_call(self, kind, *a):
+            _log("frame_call", kind)
             return (lambda: self._enqueue(1)), (lambda: None)
+        def read(self, instance=0, v0=0, n=None):
+            # the stand-in's "deformed" vertices: the rest geometry moved by a number its instance's pose decides
+            return (self.pos + self.off[instance]).astype(np.float32), (self.nrm - self.off[instance]).astype(np.float32)
         def time_frames(self, frames):
+            _log("time_frames", frames)
             ms = self._frame_s() * 1e3
             return dict(frame_ms=ms, deform_kernel_ms=ms * 0.98, prep_kernel_ms=0.0, verts_per_frame=self.V, algorithmic_bytes_per_frame=self.V * 828, frames=frames)
         def kernel_name(self): return "rz_deform_dense_kernel<4, 8, true, false, false, true>"
         def comm_init(self, nranks, rank, uid, v_total):
+            _log("comm_init")
             if MODE == "fail": raise capi.RzError(-4, "ncclCommInitRank failed: unhandled system error (stand-in)")
             if MODE == "hang": time.sleep(3600)
             if MODE == "hang_rank3" and rank == 3: time.sleep(3600)
@@ -108,12 +125,21 @@ def _run(tmp_path, mode, extra=()):
     if "--pair-fades" in extra:
         env["REZE_STUB_PAIR"] = "fades"
         extra.remove("--pair-fades")
+    # what these tests check beyond the headline (RCCL phase, kernel timing, the pair loop) is measured with --full
+    full = ["--full", "--rehearse-rccl"]
+    if "--plain" in extra:
+        extra.remove("--plain")
+        full = []
+    env["REZE_STUB_LOG"] = str(tmp_path / "calls.log")
 
     shape = ["--verts", "65536", "--bones", "16", "--morphs", "2"]
     if "--crowd" in extra:
         extra.remove("--crowd")
         shape = ["--verts", "1024", "--bones", "16", "--morphs", "0", "--instances", "100"]
-    cmd = [sys.executable, str(work / "bench.py"), "--gpus", "8", "--share-gpu", "--rehearse-rccl", "--dist-backend", "gloo"] + shape + [
+    if "--big-crowd" in extra:              # 3 000 x 1 024 rows: more than --dump-outputs writes whole
+        extra.remove("--big-crowd")
+        shape = ["--verts", "1024", "--bones", "16", "--morphs", "0", "--instances", "3000"]
+    cmd = [sys.executable, str(work / "bench.py"), "--gpus", "8", "--share-gpu", "--dist-backend", "gloo"] + full + shape + [
            "--steps", "20", "--warmup", "2", "--no-cpu-baseline", "--no-sampled-loop", "--clock-warm-seconds", "0", "--rccl-timeout", "6"] + list(extra)
     p = subprocess.run(cmd, cwd=str(work), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     out = p.stdout.decode()
@@ -186,3 +212,51 @@ def test_bench_c4_is_sharded_along_the_instance_axis(tmp_path):
     # the slowest rank poses 13 of the 100 characters: 13 x 1024 vertices x 40 us per 1000 = 0.53 ms per step
     assert 0.4 < d["ms_per_step"] < 1.0 and abs(d["value"] - 1024 * 100 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
     assert p.returncode == 0
+
+
+def _calls(tmp_path):
+    return [ln.split()[1:] for ln in open(tmp_path / "calls.log").read().splitlines()]
+
+
+def test_plain_bench_runs_only_what_the_headline_needs_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing that needs runs of its own: no kernel timing, no pair loop, no
+    per-frame loops, no communicator. --dump-outputs writes the last timed step of every rank's shard, in global vertex order."""
+    dump = tmp_path / "out"
+    d, p = _run(tmp_path, "fail", extra=["--plain", "--frames-in-flight", "1", "--dump-outputs", str(dump)])
+    _scaling_intact(d)
+    c = d["config"]
+    assert p.returncode == 0 and c["full"] is False and d["roofline"] is None and d["cpu_baseline"] is None
+    assert c["frame_ms_with_pose_upload"] is None and c["ms_per_step_two_frames_in_flight"] is None and c["allgather_ms"] is None
+    assert all("skipped" in r["rccl"] and r["kernel_ms"] is None for r in c["ranks"])
+    calls = _calls(tmp_path)
+    assert sorted(calls) == [["time_span", "20", "one"]] * 8, calls
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import reze_engine_amd as rz
+    mesh = rz.synth.make_mesh_range(65536, 16, 0, 65536)
+    off = np.asarray(mesh["world"], np.float64).sum()
+    pos, nrm = np.load(dump / "positions.npy"), np.load(dump / "normals.npy")
+    assert pos.dtype == nrm.dtype == np.float32 and pos.shape == nrm.shape == (65536, 3)
+    assert np.array_equal(pos, (mesh["pos"] + off).astype(np.float32)) and np.array_equal(nrm, (mesh["nrm"] - off).astype(np.float32))
+
+
+def test_plain_bench_dumps_a_seeded_sample_of_a_crowd_too_large_to_write_whole(tmp_path):
+    """3 000 instances x 1 024 vertices over 8 ranks: positions + normals would exceed 64 MB, so --dump-outputs writes the rows
+    bench.dump_rows picks (fixed seed, ascending instance-major rows), gathered from the ranks that hold them."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import reze_engine_amd as rz
+    dump = tmp_path / "out"
+    d, p = _run(tmp_path, "ok", extra=["--plain", "--big-crowd", "--frames-in-flight", "1", "--dump-outputs", str(dump)])
+    assert p.returncode == 0 and d["config"]["instances"] == 3000
+    rows = bench.dump_rows(3000 * 1024)
+    assert len(rows) == bench.DUMP_SAMPLE_ROWS and np.all(np.diff(rows) > 0) and np.array_equal(rows, bench.dump_rows(3000 * 1024))
+    mesh = rz.synth.make_mesh_range(1024, 16, 0, 1024)
+    off = np.array([np.asarray(rz.synth.make_pose(mesh["parents"], mesh["bind"], 16, seed=1000 + k), np.float64).sum() for k in range(3000)])
+    pos, nrm = np.load(dump / "positions.npy"), np.load(dump / "normals.npy")
+    assert pos.dtype == np.float32 and pos.shape == nrm.shape == (len(rows), 3)
+    assert os.path.getsize(dump / "positions.npy") + os.path.getsize(dump / "normals.npy") <= bench.DUMP_BYTES
+    v, k = rows % 1024, rows // 1024
+    assert np.array_equal(pos, (mesh["pos"][v] + off[k][:, None]).astype(np.float32))
+    assert np.array_equal(nrm, (mesh["nrm"][v] - off[k][:, None]).astype(np.float32))

@@ -12,25 +12,25 @@ echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.txt
 fi
 echo "== bench"
-timeout 600 python bench.py 2>$O/bench.err | tail -1 > $O/bench_c5.json
-for c in c4 c3 c2; do timeout 600 python bench.py --config $c --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_$c.json; done
-for c in demo sparse2; do timeout 600 python bench.py --config $c 2>>$O/bench.err | tail -1 > $O/bench_$c.json; done
-timeout 600 python bench.py --verts 125184 --no-cpu-baseline --frames-in-flight 1 2>>$O/bench.err | tail -1 > $O/bench_shard8.json
-timeout 600 python bench.py --verts 125184 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard8_auto.json
-timeout 600 python bench.py --verts 250112 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard4.json
-timeout 600 python bench.py --verts 500224 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard2.json
+timeout 600 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench_c5.json
+for c in c4 c3 c2; do timeout 600 python bench.py --full --config $c --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_$c.json; done
+for c in demo sparse2; do timeout 600 python bench.py --full --config $c 2>>$O/bench.err | tail -1 > $O/bench_$c.json; done
+timeout 600 python bench.py --full --verts 125184 --no-cpu-baseline --frames-in-flight 1 2>>$O/bench.err | tail -1 > $O/bench_shard8.json
+timeout 600 python bench.py --full --verts 125184 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard8_auto.json
+timeout 600 python bench.py --full --verts 250112 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard4.json
+timeout 600 python bench.py --full --verts 500224 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard2.json
 # the driver's own flags, at every shard size of N = 1, 2, 4, 8 (round 6: the timed region is 20 steps; the step is an event span)
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c5_steps20.json
-for n in 2:500224 4:250112 8:125184; do timeout 600 python bench.py --verts ${n#*:} --steps 20 --warmup 5 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard${n%:*}_steps20.json; done
-timeout 600 python bench.py --config c4 --device-fk --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c4_devicefk.json
-timeout 600 python bench.py --config c4 --device-fk --device-sampling --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c4_sampled.json
-REZE_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python bench.py --allgather --steps 100 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c5_allgather1.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c5_steps20.json
+for n in 2:500224 4:250112 8:125184; do timeout 600 python bench.py --full --verts ${n#*:} --steps 20 --warmup 5 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_shard${n%:*}_steps20.json; done
+timeout 600 python bench.py --full --config c4 --device-fk --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c4_devicefk.json
+timeout 600 python bench.py --full --config c4 --device-fk --device-sampling --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c4_sampled.json
+REZE_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 python bench.py --full --allgather --steps 100 --no-cpu-baseline 2>>$O/bench.err | tail -1 > $O/bench_c5_allgather1.json
 echo "== 8 ranks on the one GPU (plumbing rehearsal; plain invocation: bench.py launches itself)"
-timeout 900 python bench.py --gpus 8 --share-gpu --dist-backend gloo --steps 50 --warmup 5 --no-cpu-baseline --no-sampled-loop --clock-warm-seconds 0.5 2>>$O/bench.err | grep '^{' | tail -1 > $O/bench_rehearse8.json
-timeout 900 python bench.py --config c4 --gpus 8 --share-gpu --dist-backend gloo --steps 20 --warmup 5 --no-cpu-baseline --no-sampled-loop --clock-warm-seconds 0.5 2>>$O/bench.err | grep '^{' | tail -1 > $O/bench_c4_rehearse8.json
+timeout 900 python bench.py --full --gpus 8 --share-gpu --dist-backend gloo --steps 50 --warmup 5 --no-cpu-baseline --no-sampled-loop --clock-warm-seconds 0.5 2>>$O/bench.err | grep '^{' | tail -1 > $O/bench_rehearse8.json
+timeout 900 python bench.py --full --config c4 --gpus 8 --share-gpu --dist-backend gloo --steps 20 --warmup 5 --no-cpu-baseline --no-sampled-loop --clock-warm-seconds 0.5 2>>$O/bench.err | grep '^{' | tail -1 > $O/bench_c4_rehearse8.json
 echo "== search stability: consecutive runs"
-for i in 1 2 3 4 5; do timeout 600 python bench.py --no-cpu-baseline --no-sampled-loop --no-pair-loop --frames-in-flight 1 2>>$O/bench.err | tail -1 > $O/stab_c5_$i.json; done
-for i in 1 2 3 4 5; do timeout 600 python bench.py --config c4 --no-cpu-baseline --no-sampled-loop --no-pair-loop --frames-in-flight 1 2>>$O/bench.err | tail -1 > $O/stab_c4_$i.json; done
+for i in 1 2 3 4 5; do timeout 600 python bench.py --full --no-cpu-baseline --no-sampled-loop --no-pair-loop --frames-in-flight 1 2>>$O/bench.err | tail -1 > $O/stab_c5_$i.json; done
+for i in 1 2 3 4 5; do timeout 600 python bench.py --full --config c4 --no-cpu-baseline --no-sampled-loop --no-pair-loop --frames-in-flight 1 2>>$O/bench.err | tail -1 > $O/stab_c4_$i.json; done
 python - <<'P'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/full/bench_*.json')) + sorted(glob.glob('gpurun_out/full/stab_*.json')):
