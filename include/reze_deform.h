@@ -34,8 +34,9 @@ extern "C" {
  *    gathered buffer changed; rz_gather_chunk exports it instead of making callers re-derive it.
  * 6 (round 5): + rz_device_numa_node.
  * 7 (round 6): + rz_map_pose / rz_commit_pose (caller-written poses), rz_time_span (event-timed K-step span), rz_instance_range
- *    (crowds sharded along the instance axis). Nothing removed or changed: a binding written against 5 or 6 keeps working. */
-#define RZ_ABI_VERSION 7
+ *    (crowds sharded along the instance axis). Nothing removed or changed: a binding written against 5 or 6 keeps working.
+ * 8: + rz_upload_sdef, nothing removed. */
+#define RZ_ABI_VERSION 8
 
 typedef struct rz_ctx rz_ctx;
 
@@ -114,6 +115,19 @@ int rz_upload_skeleton(rz_ctx *ctx, uint32_t B, const float *inverse_bind16);
 int rz_upload_morphs_dense(rz_ctx *ctx, uint32_t M, const float *deltas);
 int rz_upload_morphs_sparse(rz_ctx *ctx, uint32_t M, const uint32_t *morph_off,
                             const uint32_t *vert_idx, const float *delta3);
+
+/* SDEF skinning (PMX weight type 3) — opt-in; the reference folds SDEF vertices into BDEF2 and so does every frame without a table.
+ * The listed vertices of this shard are skinned as MMD does it (saba's PMXModel, PMX coordinates as they are): joints / weights of slots
+ * 0 and 1 (weights renormalised over those two; slots 2 and 3 are ignored — the loader writes zeros there), the morphed rest position
+ * rotated about C by the slerp of the two bones' palette rotations, plus the weighted palette transforms of the corrected centres
+ * C + (R0 - rw) / 2 and C + (R1 - rw) / 2 with rw = w0 R0 + w1 R1; normals by the slerped rotation. vert_idx[n] are relative to this shard
+ * (like sparse morph indices), strictly ascending and < V; c3 / r0_3 / r1_3 are [n][3] in model space. n = 0 / NULL removes the table.
+ * Every frame then runs one extra pass (rz_sdef_kernel) behind the deform / skin kernel for the listed vertices, writing positions,
+ * normals and, when on, the outline hull; rz_get_tuning("sdef_verts") says how many (0 = no pass). Crowd frames that keep their palettes
+ * in LDS only (the bone-subset skin kernel, the one-launch device-animated crowd) also run the palette kernel (rz_prep_kernel /
+ * rz_fk_kernel) in front of the pass. Like every static upload it is refused while forks exist (they borrow the table);
+ * rz_upload_mesh* drops it; it drops a captured graph. */
+int rz_upload_sdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx, const float *c3, const float *r0_3, const float *r1_3);
 
 /* Instancing — NEW (the reference draws one model): I poses of the same static mesh. Shrinking the crowd keeps the
  * resident pose (instances 0 .. I-1 of it); growing it beyond the count the pose was set for needs a new rz_set_pose*. */
@@ -258,7 +272,9 @@ int rz_read_palette(rz_ctx *ctx, uint32_t instance, float *rows3x4);
  * outline pipeline no longer re-skins; NULL turns it off. rz_read_hull reads it back.
  * rz_enable_aabb: every frame also reduces the axis-aligned bounding box of the deformed positions of each
  * instance inside the skin kernel (no extra pass over the mesh); rz_read_aabb returns min xyz, max xyz of the
- * most recent frame. */
+ * most recent frame. With an SDEF table (rz_upload_sdef) the SDEF pass extends that box by the SDEF vertices' final positions, so the
+ * box is that of all final positions together with the BDEF2 positions the skin kernel computed for the SDEF vertices first: a
+ * conservative bound (it contains every final position), not always the tightest one. */
 int rz_upload_edge_scale(rz_ctx *ctx, uint32_t V, const float *edge_size);
 int rz_read_hull(rz_ctx *ctx, uint32_t instance, uint32_t v0, uint32_t n, float *pos3);
 int rz_enable_aabb(rz_ctx *ctx, int enable);
@@ -314,7 +330,7 @@ int rz_time_span(rz_ctx *a, rz_ctx *b, uint32_t lead, uint32_t frames, double *s
  * "effective_subsets" / "effective_subset_bones" / "effective_inst_lds" / "effective_fk_kind" / "effective_variant" (the last template
  * argument of the single-mesh frame kernel: 0 everything compiled in, 3 without the fused consumers, 1 / 2 also with the specialised
  * hierarchy solve) and the counts
- * "verts" / "bones" / "morphs" / "instances". Unknown keys return RZ_ERR_INVALID.
+ * "verts" / "bones" / "morphs" / "instances" / "sdef_verts" (SDEF vertices the next frame fixes, 0 = no SDEF pass). Unknown keys return RZ_ERR_INVALID.
  * NOT a pure getter for crowds: an "effective_*" key describes the frame the NEXT rz_deform will launch, and a crowd's plan depends on
  * the per-run bone lists of its launch shape — when the shape, the mesh or the skeleton changed since the last frame the call brings
  * them up to date first, exactly as the next frame would (stream drained, one small kernel, one readback, a captured graph dropped).

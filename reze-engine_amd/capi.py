@@ -20,10 +20,11 @@ SYMBOLS = [
     "rz_read_palette", "rz_time_frames", "rz_set_tuning", "rz_get_tuning", "rz_autotune", "rz_autotune_measure", "rz_autotune_pick",
     "rz_autotune_apply", "rz_output_ptrs",
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
-    "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span",
+    "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
 ]
-# symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: the last four)
-OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span"}
+# symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
+# rz_time_span; 8: rz_upload_sdef)
+OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 
 
@@ -142,6 +143,8 @@ def load(path=None):
         L.rz_map_pose.argtypes = [vp, ctypes.c_int, ctypes.POINTER(fp), ctypes.POINTER(fp)]
         L.rz_commit_pose.argtypes = [vp]
         L.rz_time_span.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_double)]
+    if hasattr(L, "rz_upload_sdef"):           # (ABI 8)
+        L.rz_upload_sdef.argtypes = [vp, u32, ctypes.POINTER(u32), fp, fp, fp]
     for name in SYMBOLS:
         # (libraries older than the current ABI — tools/ab_inproc.py loads them side by side — lack the newer symbols: OPTIONAL_SYMBOLS)
         if name != "rz_last_error" and (name not in OPTIONAL_SYMBOLS or hasattr(L, name)):
@@ -480,6 +483,17 @@ class DeformContext:
             return
         e = _f32(edge).reshape(-1)
         self._chk(self._L.rz_upload_edge_scale(self._h, len(e), _fptr(e)))
+
+    def upload_sdef(self, idx, c, r0, r1):
+        """SDEF (PMX weight type 3) for the listed vertices of this shard: idx [n] shard-relative and strictly ascending, c / r0 / r1
+        [n][3] in model space. An empty `idx` removes the table."""
+        i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        if i.size == 0:
+            self._chk(self._L.rz_upload_sdef(self._h, 0, None, None, None, None))
+            return
+        cc, a, b = (_f32(x).reshape(-1) for x in (c, r0, r1))
+        assert cc.size == a.size == b.size == i.size * 3, (i.size, cc.size, a.size, b.size)
+        self._chk(self._L.rz_upload_sdef(self._h, int(i.size), i.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _fptr(cc), _fptr(a), _fptr(b)))
 
     def read_hull(self, instance=0, v0=0, n=None):
         n = self.V - v0 if n is None else n

@@ -204,6 +204,14 @@ void forget_search(rz_ctx *c)
     c->tuned_by_search = false;
 }
 
+void free_sdef(rz_ctx *c)
+{
+    drop_graph(c);
+    if (c->lender) c->sdef_tab = nullptr;     // a fork's table is its lender's
+    dfree(c->sdef_tab);
+    c->sdef_n = 0;
+}
+
 void free_morphs(rz_ctx *c)
 {
     forget_search(c);
@@ -310,6 +318,7 @@ int rz_destroy(rz_ctx *c)
         c->an_key_frame = c->an_key_pos = c->an_mkey_frame = c->an_mkey_weight = c->an_feed_ratio = nullptr; c->an_key_rot = nullptr; c->an_key_interp = nullptr;
         c->bm_off = c->bm_morph = nullptr; c->bm_rot = c->bm_tr = nullptr;
         c->dense = nullptr; c->sp_ptr = nullptr; c->sp_entries = nullptr; c->edge = nullptr;
+        c->sdef_tab = nullptr; c->sdef_n = 0;
         c->lender->n_forks--;
         c->lender = nullptr;
     }
@@ -327,6 +336,7 @@ int rz_destroy(rz_ctx *c)
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
     free_bone_morphs(c);
     free_morphs(c);
+    free_sdef(c);
     for (int k = 0; k < 2; ++k) {
         if (c->big_ev[k]) (void)hipEventDestroy(c->big_ev[k]);
     }
@@ -383,6 +393,7 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
     c->bm_off = parent->bm_off; c->bm_morph = parent->bm_morph; c->bm_rot = parent->bm_rot; c->bm_tr = parent->bm_tr; c->bm_count = parent->bm_count;
     c->morph_mode = parent->morph_mode; c->M = parent->M; c->Mpad = parent->Mpad; c->dense = parent->dense;
     c->sp_ptr = parent->sp_ptr; c->sp_entries = parent->sp_entries; c->sp_count = parent->sp_count;
+    c->sdef_tab = parent->sdef_tab; c->sdef_n = parent->sdef_n;
     c->edge = parent->edge; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on;
     c->I = parent->I;
     c->t_split = parent->t_split; c->t_unroll = parent->t_unroll; c->t_grid_cap = parent->t_grid_cap; c->t_nt = parent->t_nt; c->t_nts = parent->t_nts;

@@ -129,6 +129,9 @@ struct rz_ctx {
     uint32_t *bm_off = nullptr, *bm_morph = nullptr;
     float4 *bm_rot = nullptr, *bm_tr = nullptr;
     uint32_t bm_count = 0;
+    // SDEF vertices of this shard (rz_upload_sdef): [10][sdef_n] planes (kernels/sdef.hip); null = every vertex is skinned as the frame kernel skins it
+    uint32_t *sdef_tab = nullptr;
+    uint32_t sdef_n = 0;
 
     // morphs
     int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
@@ -338,6 +341,7 @@ int rebuild_fk_static(rz_ctx *c);      // upload.cpp: the device block behind fk
 void free_bone_morphs(rz_ctx *c);
 void forget_search(rz_ctx *c);
 void free_morphs(rz_ctx *c);
+void free_sdef(rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {
     *dst = nullptr;
@@ -379,6 +383,8 @@ int launch_deform(rz_ctx *c, const Plan &pl);
 bool want_overlap(const rz_ctx *c, const Plan &pl);
 int set_overlap(rz_ctx *c, bool on);
 int run_frame(rz_ctx *c, const Plan &pl);
+RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl);
+int launch_sdef(rz_ctx *c, const Plan &pl, const RzSdefParams &sp);
 hipStream_t front_stream(const rz_ctx *c);       // the stream per-frame inputs travel on and front kernels run on
 
 // ---- comm.cpp ----

@@ -172,6 +172,35 @@ struct RzMorphList {
     float w[kKargMorphs + kKargPad];
 };
 
+// rz_sdef_kernel (kernels/sdef.hip): SDEF skinning of the vertices listed by rz_upload_sdef, a pass of its own behind the frame kernel.
+// One lane per (table entry, instance); it reads what the frame kernel read and overwrites that kernel's output for the listed vertices.
+struct RzSdefParams {
+    const uint32_t *tab;        // [10][n] SoA planes, 40 B per entry: vertex index (ascending, < V) | C xyz | R0 xyz | R1 xyz
+    const float *geom;          // 6 planes of Vp floats
+    const uint32_t *joints01;   // [Vp] j0 | j1 << 16 (slots 2 / 3 of an SDEF vertex are ignored)
+    const uint32_t *weights;    // [Vp] 4 x unorm8
+    const float4 *palette;      // [I][B][3] this frame's palette rows
+    const float *dense;         // [M][3][Vp] (mode 1)
+    const uint32_t *sp_ptr;     // [Vp + 1]   (mode 2)
+    const float4 *sp_entries;
+    const float *morph_w;       // [I][M] this frame's weights (sparse targets; dense with wsrc 2): the device copy the frame read or left
+    const uint32_t *act_idx;    // [I][Mpad] the ring slot's ordered active list, written by rz_prep_kernel in front of the frame (wsrc 1)
+    const float *act_w;         // [I][Mpad]
+    const int *act_count;       // [I]
+    float *out_pos, *out_nrm;   // [I][Vp][3] where the frame kernel wrote (its own buffers or the gathered ones)
+    const float *edge;          // [Vp] or null: also the outline hull
+    float *out_hull;
+    uint32_t *aabb;             // [I][2][6] or null: extend slot `aabb_slot`, the one the frame kernel accumulated into
+    uint32_t n;                 // entries
+    int mode, M, Mpad;          // morph mode of the frame (0 when it has no weights to apply)
+    int wsrc;                   // mode 1: 0 = the one-launch frame's kernel-argument list (RzMorphList), 1 = act_*, 2 = morph_w compacted in the pass
+    int aabb_slot;
+    uint32_t Vp;
+    int B;
+};                              // (no padding: frame_signature() hashes the struct)
+struct RzMorphList;
+hipError_t rz_launch_sdef(const RzSdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st);
+
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).
 struct RzVariant {
     int mode;    // 0 none, 1 dense, 2 sparse

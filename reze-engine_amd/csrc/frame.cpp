@@ -80,6 +80,69 @@ int launch_deform(rz_ctx *c, const Plan &pl)
     return RZ_OK;
 }
 
+// The SDEF pass (kernels/sdef.hip) of a frame whose deform / skin kernel has just been enqueued. Its parameters are taken BEFORE that
+// launch (sdef_params): the bounding-box slot the frame accumulates into, and the morph weights where the frame read them.
+RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl)
+{
+    RzSdefParams s;
+    memset(&s, 0, sizeof s);
+    if (!c->sdef_tab || c->sdef_n == 0) return s;
+    s.tab = c->sdef_tab; s.n = c->sdef_n;
+    s.geom = c->geom; s.joints01 = c->j01; s.weights = c->wq; s.palette = c->palette;
+    if (c->morph_mode != 0 && c->M > 0) {
+        s.mode = c->morph_mode; s.M = (int)c->M; s.Mpad = (int)c->Mpad;
+        s.dense = c->dense; s.sp_ptr = c->sp_ptr; s.sp_entries = c->sp_entries;
+        // The weights where this frame's kernels leave or read them, never a pose block that a later upload may overwrite before the pass
+        // runs (under the overlapped-front protocol the next pose goes down the upload stream behind this frame's front):
+        //   dense, one-launch frame: its kernel-argument list (the weights may only sit in a pinned slot)
+        //   dense behind rz_prep_kernel (every crowd frame, the only frames that overlap): the ring slot's active list
+        //   otherwise (a single character's fused-hierarchy frame; sparse targets, which never overlap): the weights themselves — sampled
+        //   ones from the device block the front / workgroup 0 wrote, uploaded ones from the device copy workgroup 0 leaves, or where the
+        //   frame kernel reads them
+        if (s.mode == 1 && pl.v.fast && c->I == 1 && c->ml.count >= 0 && !c->pose_sampled) s.wsrc = 0;
+        else if (s.mode == 1 && pl.prep) {
+            s.wsrc = 1; s.act_idx = c->act_idx; s.act_w = c->act_w; s.act_count = c->act_count;
+        } else {
+            s.wsrc = 2;
+            const float *copy = deform_params(c, pl).morph_w_copy;
+            s.morph_w = c->pose_sampled ? c->morph_w : (copy ? copy : src_morph_w(c));
+        }
+    }
+    s.out_pos = c->ext_pos ? c->ext_pos : c->out_pos; s.out_nrm = c->ext_nrm ? c->ext_nrm : c->out_nrm;
+    if (c->edge) { s.edge = c->edge; s.out_hull = c->out_hull; }
+    if (c->aabb_on) { s.aabb = c->aabb; s.aabb_slot = c->aabb_slot; }
+    s.Vp = c->Vp; s.B = (int)c->B;
+    return s;
+}
+
+// Behind the deform / skin kernel on the frame's stream. Crowd forms that formed their palettes in LDS only (palette_stale: the bone-subset
+// skin kernel; fk_stale: the one-launch device-animated crowd) get them written first by the palette kernel those flags name — SDEF crowds
+// of those forms pay that kernel.
+int launch_sdef(rz_ctx *c, const Plan &pl, const RzSdefParams &sp)
+{
+    (void)pl;
+    if (sp.n == 0) return RZ_OK;
+    if (solve_on_demand(c) || c->palette_stale) {
+        // (never under the overlapped-front protocol: its frames have a front, which writes the ring slot's palettes, and the forms that
+        // keep palettes in LDS only have none; a palette kernel here would read the pose block on the wrong stream)
+        if (c->overlap_on) return fail(RZ_ERR_INVALID, "SDEF pass: an overlapped crowd frame left no palette in memory");
+        if (solve_on_demand(c)) {
+            if (int r = launch_fk(c, c->stream)) return r;
+        } else if (int r = launch_prep(c, c->stream)) return r;
+    }
+    HIP_TRY(rz_launch_sdef(sp, c->ml, c->I, c->stream));
+    return RZ_OK;
+}
+
+// the deform / skin kernel of a frame and, when the context has an SDEF table, the SDEF pass behind it
+static int launch_deform_sdef(rz_ctx *c, const Plan &pl)
+{
+    if (!c->sdef_n) return launch_deform(c, pl);
+    const RzSdefParams sp = sdef_params(c, pl);
+    if (int r = launch_deform(c, pl)) return r;
+    return launch_sdef(c, pl, sp);
+}
+
 // Crowds overlap the front kernels of a frame with the skin kernel of the frame before it. The protocol
 // needs a frame that HAS front kernels and a skin kernel that reads nothing of the pose slots themselves (sparse morph
 // frames read the uploaded weights directly), and plain stream capture (the graph key) stays single-stream.
@@ -115,13 +178,13 @@ int run_frame(rz_ctx *c, const Plan &pl)
         if (int r = launch_front(c, pl, c->up_stream)) return r;
         HIP_TRY(hipEventRecord(c->ev_front[s], c->up_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_front[s], 0));
-        if (int r = launch_deform(c, pl)) return r;
+        if (int r = launch_deform_sdef(c, pl)) return r;        // (the SDEF pass reads the slot's palettes and active lists too: ev_skin goes behind it)
         HIP_TRY(hipEventRecord(c->ev_skin[s], c->stream));
         c->skin_recorded[s] = true;
         return RZ_OK;
     }
     if (int r = launch_front(c, pl, c->stream)) return r;
-    return launch_deform(c, pl);
+    return launch_deform_sdef(c, pl);
 }
 
 // the stream per-frame inputs travel on and front kernels run on
@@ -167,6 +230,8 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     h = fnv(h, &fp, sizeof fp);
     const RzSubFk sf = subfk_params(c);
     h = fnv(h, &sf, sizeof sf);
+    const RzSdefParams sd = sdef_params(c, pl);
+    h = fnv(h, &sd, sizeof sd);
     const uint64_t misc[6] = { c->I, c->pose_local, c->pose_local_t, c->pose_sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }
@@ -201,7 +266,7 @@ int rz_deform_n(rz_ctx *c, uint32_t frames)
             int rc = RZ_OK;
             for (uint32_t k = 0; k < kGraphFrames && rc == RZ_OK; ++k) {
                 rc = launch_front(c, pl, c->stream);
-                if (rc == RZ_OK) rc = launch_deform(c, pl);
+                if (rc == RZ_OK) rc = launch_deform_sdef(c, pl);
             }
             hipError_t ce = hipStreamEndCapture(c->stream, &g);
             if (rc != RZ_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -360,10 +425,10 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
     HIP_TRY(hipEventSynchronize(c->ev1));
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     out->frame_ms = ms / frames;
-    // the deform / skin kernel alone (reads the ring slot the last frame left current)
+    // the deform / skin kernel alone (reads the ring slot the last frame left current), with the SDEF pass when there is a table
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     for (uint32_t f = 0; f < frames; ++f)
-        if (int r = launch_deform(c, pl)) return r;
+        if (int r = launch_deform_sdef(c, pl)) return r;
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     HIP_TRY(hipEventSynchronize(c->ev1));
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));

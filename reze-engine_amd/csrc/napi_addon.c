@@ -310,6 +310,23 @@ static napi_value fn_upload_morphs_sparse(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+/* uploadSdef(ctx, Uint32Array|null index, Float32Array c3, Float32Array r0_3, Float32Array r1_3): SDEF vertices of this shard (shard-relative,
+ * strictly ascending); an empty or null index removes the table */
+static napi_value fn_upload_sdef(napi_env env, napi_callback_info info)
+{
+    ARGS(5);
+    CTX(0);
+    void *idx, *cc, *a, *b;
+    size_t ni, nc, na, nb;
+    if (!get_ta(env, argv[1], napi_uint32_array, 1, &idx, &ni) || !get_ta(env, argv[2], napi_float32_array, 1, &cc, &nc) ||
+        !get_ta(env, argv[3], napi_float32_array, 1, &a, &na) || !get_ta(env, argv[4], napi_float32_array, 1, &b, &nb))
+        return throw_msg(env, "uploadSdef(ctx, Uint32Array index, Float32Array c3, Float32Array r0_3, Float32Array r1_3)");
+    if (ni > 0xffffffffu || nc < ni * 3 || na < ni * 3 || nb < ni * 3) return throw_msg(env, "uploadSdef: c3 / r0_3 / r1_3 need 3 floats per index");
+    int rc = ni ? rz_upload_sdef(ctx, (uint32_t)ni, (const uint32_t *)idx, (const float *)cc, (const float *)a, (const float *)b)
+                : rz_upload_sdef(ctx, 0, NULL, NULL, NULL, NULL);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
 static napi_value fn_set_instances(napi_env env, napi_callback_info info)
 {
     ARGS(2);
@@ -1003,6 +1020,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "readGathered", fn_read_gathered }, { "commInitAll", fn_comm_init_all }, { "allgatherAll", fn_allgather_all },
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
+        { "uploadSdef", fn_upload_sdef },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

@@ -47,6 +47,7 @@ int alloc_mesh(rz_ctx *c, uint32_t V)
     dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->edge);
     dfree(c->rj01); dfree(c->rj23); c->sub_valid = false;      // the run lists name this mesh's joints
     free_morphs(c);                       // morph targets are per-vertex: a new mesh invalidates them
+    free_sdef(c);                         // ... and so does the SDEF table: its indices name the old mesh's vertices
     c->V = V;
     c->Vp = round_up(V, kVertPad);
     const size_t Vp = c->Vp;
@@ -475,6 +476,35 @@ int rz_upload_edge_scale(rz_ctx *c, uint32_t V, const float *edge_size)
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->edge, edge_size, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
     return ensure_outputs(c);
+}
+
+int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float *c3, const float *r0_3, const float *r1_3)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_sdef")) return r;
+    if (n > 0) {
+        if (!vert_idx || !c3 || !r0_3 || !r1_3) return fail(RZ_ERR_INVALID, "rz_upload_sdef: null arrays for %u entries", n);
+        if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its SDEF table");
+        for (uint32_t k = 0; k < n; ++k) {
+            if (vert_idx[k] >= c->V) return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex index %u (entry %u) is outside the shard's %u vertices", vert_idx[k], k, c->V);
+            if (k > 0 && vert_idx[k] <= vert_idx[k - 1])
+                return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex indices must be strictly ascending (entry %u: %u after %u)", k, vert_idx[k], vert_idx[k - 1]);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_graph(c);
+    free_sdef(c);
+    if (n == 0) return RZ_OK;
+    // [10][n] planes: index | C xyz | R0 xyz | R1 xyz
+    std::vector<uint32_t> tab((size_t)n * 10);
+    memcpy(tab.data(), vert_idx, (size_t)n * 4);
+    const float *src[3] = { c3, r0_3, r1_3 };
+    for (int a = 0; a < 3; ++a)
+        for (int d = 0; d < 3; ++d)
+            for (uint32_t k = 0; k < n; ++k) memcpy(&tab[(size_t)(1 + 3 * a + d) * n + k], &src[a][(size_t)k * 3 + d], 4);
+    if (int r = to_device(&c->sdef_tab, tab.data(), tab.size())) return r;
+    c->sdef_n = n;
+    return RZ_OK;
 }
 
 int rz_enable_aabb(rz_ctx *c, int enable)

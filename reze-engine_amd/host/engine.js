@@ -45,6 +45,8 @@ class Engine {
     this.deviceFK = o.deviceFK === true // forward kinematics on the GPU: upload local rotations instead of world matrices
     this.outline = o.outline === true // also produce the outline pass's inverted hull (engine.ts:458-461) every frame
     this.bounds = o.bounds === true // also reduce the deformed mesh's bounding box every frame
+    // SDEF vertices (PMX weight type 3) skinned as MMD does; off (the default), they are skinned as BDEF2 like the reference does
+    this.sdef = o.sdef === true
     // gather: true = RCCL all-gather of the deformed mesh after every frame (needs distinct GPUs);
     // 'direct' = every shard's kernel stores straight into GPU devices[0]'s buffer over xGMI (no collective)
     this.gather = o.gather === 'direct' ? 'direct' : o.gather === true
@@ -234,6 +236,16 @@ class Engine {
         // PMX bone morphs: with the hierarchy solved on the GPU they are folded there (host FK: Model.posedLocals())
         const be = morphs.boneEntries
         if (this.deviceFK && be && be.morph.length > 0) n.uploadBoneMorphs(s.ctx, be.morph, be.bone, be.translation, be.rotation)
+      }
+      if (this.sdef) { // this shard's SDEF vertices, indices re-based to the shard (the table is sorted by vertex)
+        const t = model.getSdef()
+        let k0 = 0
+        while (k0 < t.index.length && t.index[k0] < b) k0++
+        let k1 = k0
+        while (k1 < t.index.length && t.index[k1] < e) k1++
+        const idx = new Uint32Array(k1 - k0)
+        for (let k = k0; k < k1; k++) idx[k - k0] = t.index[k] - b
+        n.uploadSdef(s.ctx, idx, t.c.slice(k0 * 3, k1 * 3), t.r0.slice(k0 * 3, k1 * 3), t.r1.slice(k0 * 3, k1 * 3))
       }
     }
     if (this.outline) {

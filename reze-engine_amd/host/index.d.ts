@@ -33,6 +33,7 @@ export interface EngineOptions {
   /** Solve the bone hierarchy on the GPU (uploads local rotations instead of world matrices). */ deviceFK?: boolean
   /** Also write the outline pass's inverted hull every frame. */ outline?: boolean
   /** Also reduce the deformed mesh's bounding box every frame. */ bounds?: boolean
+  /** Skin SDEF vertices (PMX weight type 3) as MMD does (default false: they are skinned as BDEF2, like the reference). */ sdef?: boolean
   /** One context per listed GPU; the mesh is vertex-sharded across them. */ devices?: number[]
   /** With deviceFK: seekFrame() samples the motion on the GPU (rz_upload_animation once, one float per frame). */ deviceSampling?: boolean
   /** Search launch shapes (morph split, workgroups per CU) once on the first rendered frame. */ autotune?: boolean

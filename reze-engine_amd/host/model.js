@@ -50,6 +50,8 @@ class Model {
     this.materials = materials || []
     this.skeleton = skeleton
     this.skinning = skinning
+    // SDEF vertices (PMX weight type 3): set by the PMX loader; skinned as BDEF2 unless the engine is asked for SDEF ({ sdef: true })
+    this.sdef = { index: new Uint32Array(0), c: new Float32Array(0), r0: new Float32Array(0), r1: new Float32Array(0) }
     this.rigidbodies = rigidbodies || []
     this.joints = joints || []
     this.clock = defaultClock
@@ -124,6 +126,7 @@ class Model {
   getIndices() { return this.indexData }
   getSkeleton() { return this.skeleton }
   getSkinning() { return this.skinning }
+  getSdef() { return this.sdef }
   getRigidbodies() { return this.rigidbodies }
   getJoints() { return this.joints }
   getBoneNames() { return this.skeleton.bones.map((b) => b.name) }

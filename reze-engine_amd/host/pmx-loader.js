@@ -117,6 +117,10 @@ class PmxLoader {
     const pos = new Float32Array(count * 3), nrm = new Float32Array(count * 3), uv = new Float32Array(count * 2)
     const joints = new Uint16Array(count * 4), weights = new Uint8Array(count * 4)
     const bone = () => { const j = c.index(h.boneIndexSize); return j >= 0 ? j : 0 }
+    const sdefIdx = []
+    const sdefC = []
+    const sdefR0 = []
+    const sdefR1 = []
     for (let v = 0; v < count; v++) {
       pos[v * 3] = c.f32(); pos[v * 3 + 1] = c.f32(); pos[v * 3 + 2] = c.f32()
       nrm[v * 3] = c.f32(); nrm[v * 3 + 1] = c.f32(); nrm[v * 3 + 2] = c.f32()
@@ -131,7 +135,10 @@ class PmxLoader {
         joints[o] = bone(); joints[o + 1] = bone()
         const w0 = clamp(Math.round(c.f32() * 255), 0, 255)
         weights[o] = w0; weights[o + 1] = clamp(255 - w0, 0, 255)
-        if (kind === 3) c.skip(36) // C, R0, R1
+        if (kind === 3) { // SDEF: C, R0, R1 (model space) go to Geometry.sdef; the engine applies them only when asked ({ sdef: true })
+          sdefIdx.push(v)
+          sdefC.push(c.f32(), c.f32(), c.f32()); sdefR0.push(c.f32(), c.f32(), c.f32()); sdefR1.push(c.f32(), c.f32(), c.f32())
+        }
       } else if (kind === 2 || kind === 4) { // BDEF4, QDEF treated as BDEF4
         for (let k = 0; k < 4; k++) joints[o + k] = bone()
         const q = [0, 0, 0, 0]
@@ -148,7 +155,8 @@ class PmxLoader {
       }
       c.skip(4) // edge scale
     }
-    return { count, pos, nrm, uv, joints, weights }
+    const sdef = { index: Uint32Array.from(sdefIdx), c: Float32Array.from(sdefC), r0: Float32Array.from(sdefR0), r1: Float32Array.from(sdefR1) }
+    return { count, pos, nrm, uv, joints, weights, sdef }
   }
 
   indices() {
@@ -422,7 +430,9 @@ class PmxLoader {
     PmxLoader.sanitizeSkinning(geo.joints, geo.weights, bones.length)
     const skeleton = { bones, inverseBindMatrices: PmxLoader.inverseBind(bones) }
     const skinning = { joints: geo.joints, weights: geo.weights }
-    return new Model(vertexData, indices, textures, materials, skeleton, skinning, rigidbodies, joints, morphs)
+    const model = new Model(vertexData, indices, textures, materials, skeleton, skinning, rigidbodies, joints, morphs)
+    model.sdef = geo.sdef
+    return model
   }
 }
 

@@ -16,7 +16,7 @@
  * (names, sparse targets, weights, group-morph flattening) feeding the fused GPU kernel.
  */
 import { Quat, easeInOut, kernels } from './math'
-import type { Bone, Material, MorphSet, NumArray, PosedLocals, RotTweenState, Skeleton, SkeletonRuntime, Skinning, Texture } from './types'
+import type { Bone, Material, MorphSet, NumArray, PosedLocals, RotTweenState, SdefTable, Skeleton, SkeletonRuntime, Skinning, Texture } from './types'
 import type { VMDSampler } from './vmd-sampler'
 const { slerpInto, mulInto, quatToMatInto, identityInto } = kernels
 
@@ -38,6 +38,7 @@ class Model {
   materials: Material[]
   skeleton: Skeleton
   skinning: Skinning
+  sdef: SdefTable
   rigidbodies: unknown[]
   joints: unknown[]
   clock: () => number
@@ -81,6 +82,8 @@ class Model {
     this.materials = materials || []
     this.skeleton = skeleton
     this.skinning = skinning
+    // SDEF vertices (PMX weight type 3): set by the PMX loader; skinned as BDEF2 unless the engine is asked for SDEF ({ sdef: true })
+    this.sdef = { index: new Uint32Array(0), c: new Float32Array(0), r0: new Float32Array(0), r1: new Float32Array(0) }
     this.rigidbodies = rigidbodies || []
     this.joints = joints || []
     this.clock = defaultClock
@@ -155,6 +158,7 @@ class Model {
   getIndices(): Uint32Array { return this.indexData }
   getSkeleton(): Skeleton { return this.skeleton }
   getSkinning(): Skinning { return this.skinning }
+  getSdef(): SdefTable { return this.sdef }
   getRigidbodies(): unknown[] { return this.rigidbodies }
   getJoints(): unknown[] { return this.joints }
   getBoneNames(): string[] { return this.skeleton.bones.map((b) => b.name) }

@@ -24,6 +24,8 @@ export interface Bone {
 /** model.ts:36-45 */
 export interface Skeleton { bones: Bone[]; inverseBindMatrices: Float32Array }
 export interface Skinning { joints: Uint16Array; weights: Uint8Array }
+// SDEF vertices (PMX weight type 3) of a model: ascending vertex indices and their C / R0 / R1 ([n][3], model space); empty without SDEF
+export interface SdefTable { index: Uint32Array; c: Float32Array; r0: Float32Array; r1: Float32Array }
 /** model.ts:52-59 */
 export interface SkeletonRuntime {
   nameIndex: Record<string, number>
@@ -94,6 +96,7 @@ export interface DeformAddon {
   uploadBoneMorphs(ctx: DeformContext, morph: Uint32Array | null, bone: Uint32Array | null, translation3: Float32Array | null, rotation4: Float32Array | null): void
   uploadAnimation(ctx: DeformContext, motion: FlatMotion): void
   uploadEdgeScale(ctx: DeformContext, edge: Float32Array | null): void
+  uploadSdef(ctx: DeformContext, index: Uint32Array | null, c3: Float32Array | null, r0_3: Float32Array | null, r1_3: Float32Array | null): void
   enableAabb(ctx: DeformContext, on: boolean): void
   setInstances(ctx: DeformContext, count: number): void
   setPose(ctx: DeformContext, world: Float32Array, morphWeights: Float32Array | null): void
@@ -129,7 +132,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }

@@ -303,3 +303,38 @@ def make_morphs_demo_shape(n_verts, n_morphs=60, total=36397, largest=1718, regi
     delta3 = ((rng.random((len(vert_idx), 3), dtype=np.float32) - np.float32(0.5)) * np.float32(0.1)).astype(np.float32)
     w = rng.random(n_morphs, dtype=np.float32)
     return offs, vert_idx, delta3, w
+
+
+def make_sdef(mesh, frac, seed=SEED + 7, cluster=0):
+    """SDEF table (PMX weight type 3) for round(frac x V) of the mesh's V vertices, all drawn from its BDEF2 vertices (two joints, slots 2
+    and 3 empty; fewer when the mesh has fewer of them):
+    C on the segment between the two bones' bind positions, R0 / R1 within 0.05 of C. cluster > 0 picks whole runs of `cluster`
+    consecutive vertices instead of scattered ones (real meshes keep SDEF to elbows, knees, shoulders). The mesh is not changed: an
+    SDEF vertex keeps its BDEF2 joints and weights, which is what a frame without the table skins. Returns dict(idx [n] uint32
+    ascending, c / r0 / r1 [n,3] float32)."""
+    rng = np.random.default_rng(seed)
+    w = mesh["weights"]
+    V = len(w)
+    bdef2 = np.flatnonzero((w[:, 1] > 0) & (w[:, 2] == 0) & (w[:, 3] == 0))
+    want = int(round(frac * V))
+    if cluster > 0:
+        starts = rng.permutation(max(V // cluster, 1))
+        picked = np.zeros(V, dtype=bool)
+        is2 = np.zeros(V, dtype=bool)
+        is2[bdef2] = True
+        for s in starts:
+            run = np.arange(s * cluster, min((s + 1) * cluster, V))
+            picked[run[is2[run]]] = True
+            if picked.sum() >= want:
+                break
+        idx = np.flatnonzero(picked)[:want] if picked.sum() > want else np.flatnonzero(picked)
+    else:
+        idx = np.sort(rng.choice(bdef2, size=min(want, len(bdef2)), replace=False))
+    idx = idx.astype(np.uint32)
+    bone_pos = -np.asarray(mesh["inv_bind"], dtype=np.float32).reshape(-1, 16)[:, 12:15]     # translation-only inverse binds
+    j = mesh["joints"][idx].astype(np.int64)
+    u = rng.uniform(0.2, 0.8, size=(len(idx), 1)).astype(np.float32)
+    c = (bone_pos[j[:, 0]] * (1 - u) + bone_pos[j[:, 1]] * u).astype(np.float32)
+    r0 = (c + rng.uniform(-0.05, 0.05, size=c.shape)).astype(np.float32)
+    r1 = (c + rng.uniform(-0.05, 0.05, size=c.shape)).astype(np.float32)
+    return dict(idx=idx, c=c, r0=r0, r1=r1)
