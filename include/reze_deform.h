@@ -35,7 +35,8 @@ extern "C" {
  * 6 (round 5): + rz_device_numa_node.
  * 7 (round 6): + rz_map_pose / rz_commit_pose (caller-written poses), rz_time_span (event-timed K-step span), rz_instance_range
  *    (crowds sharded along the instance axis). Nothing removed or changed: a binding written against 5 or 6 keeps working.
- * 8: + rz_upload_sdef, nothing removed. */
+ * 8: + rz_upload_sdef, nothing removed.
+ *    rz_upload_ik came later and is an addition too: the version stays 8, a binding detects the feature by the symbol. */
 #define RZ_ABI_VERSION 8
 
 typedef struct rz_ctx rz_ctx;
@@ -128,6 +129,30 @@ int rz_upload_morphs_sparse(rz_ctx *ctx, uint32_t M, const uint32_t *morph_off,
  * rz_fk_kernel) in front of the pass. Like every static upload it is refused while forks exist (they borrow the table);
  * rz_upload_mesh* drops it; it drops a captured graph. */
 int rz_upload_sdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx, const float *c3, const float *r0_3, const float *r1_3);
+
+/* PMX inverse kinematics — NEW (the reference's loader skips the IK block, engine/src/pmx-loader.ts). Opt-in: without a table every
+ * frame launches what it launched before. n_chains IK bones; chain k: goal[k] = the IK bone itself, effector[k] = the bone that is moved
+ * onto it (PMX: "target"), loops[k] iterations, limit_angle[k] radians per step, links link_off[k] .. link_off[k + 1] ordered from the
+ * effector outwards (knee, then leg); link e turns bone link_bone[e] and, if link_limited[e], is clamped to the Euler limits link_min3 /
+ * link_max3 (radians, three.js 'XYZ' order R = Rx * Ry * Rz; an axis with min > max is swapped). The solver is CCD in the clamp form
+ * (tests/ik_ref.py is the definition): chains in ascending order of the goal's bone index; per iteration, per link L in file order:
+ *     a = Rw[L]^T (pos[E] - pos[L]), b = Rw[L]^T (pos[G] - pos[L]), both normalised (a link with |a| or |b| < 1e-6 or |a x b| < 1e-7 is skipped)
+ *     q[L] = normalize(clamp(q[L] * quat(axis a x b, angle min(atan2(|a x b|, a . b), limit_angle))))        then the hierarchy is re-solved
+ * until |pos[G] - pos[E]| < 1e-4, no link turned, or `loops` iterations ran (0 = the chain does nothing). World matrices are those of the
+ * hierarchy solve after bone morphs; a chain sees what all earlier chains left. The final pose is the hierarchy solve of the solved local
+ * rotations, so append children of a link follow; rz_override_world lands after IK. Order of a frame: sample -> bone morphs -> hierarchy ->
+ * IK -> hierarchy of the solved locals -> overrides -> palette. It acts on device-solved poses only (rz_set_pose_local, rz_set_pose_sampled);
+ * with rz_set_pose the host owns the world matrices and has solved IK itself — the rule bone morphs follow.
+ * Valid: every index < B, effector != goal, every link a proper ancestor of the effector and of the link before it (bones between two
+ * links stay rigid), loops >= 0, at most 65535 chains with distinct goals and 255 links per chain. Refused with RZ_ERR_UNSUPPORTED: a bone
+ * on a chain's path that takes its append rotation from a link of any chain, or an ancestor of the effector or of the goal that takes it
+ * from a link of the same chain (either would force the whole solve into every step); a goal below one of its own chain's links; a path (outermost
+ * link ... effector) of more than 64 bones. With a table the solve runs as rz_fk_ik_kernel in front of the deform / skin kernel: the
+ * one-launch forms ("effective_fuse_fk") are not taken, and the skeleton must fit 156 B of LDS per bone. rz_get_tuning("ik_chains") = the
+ * count. n_chains = 0 removes the table. Needs rz_upload_skeleton_topology first; a new skeleton or topology drops it; refused while
+ * forks exist; drops a captured graph. */
+int rz_upload_ik(rz_ctx *ctx, uint32_t n_chains, const uint32_t *goal, const uint32_t *effector, const uint32_t *loops, const float *limit_angle,
+                 const uint32_t *link_off, const uint32_t *link_bone, const uint8_t *link_limited, const float *link_min3, const float *link_max3);
 
 /* Instancing — NEW (the reference draws one model): I poses of the same static mesh. Shrinking the crowd keeps the
  * resident pose (instances 0 .. I-1 of it); growing it beyond the count the pose was set for needs a new rz_set_pose*. */

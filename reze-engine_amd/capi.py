@@ -20,11 +20,12 @@ SYMBOLS = [
     "rz_read_palette", "rz_time_frames", "rz_set_tuning", "rz_get_tuning", "rz_autotune", "rz_autotune_measure", "rz_autotune_pick",
     "rz_autotune_apply", "rz_output_ptrs",
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
-    "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
+    "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
-# rz_time_span; 8: rz_upload_sdef)
-OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef"}
+# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik — detected by the symbol, the version stayed 8)
+OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
+                    "rz_upload_ik"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 
 
@@ -145,6 +146,9 @@ def load(path=None):
         L.rz_time_span.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_double)]
     if hasattr(L, "rz_upload_sdef"):           # (ABI 8)
         L.rz_upload_sdef.argtypes = [vp, u32, ctypes.POINTER(u32), fp, fp, fp]
+    if hasattr(L, "rz_upload_ik"):             # (ABI 8 still: the feature is detected by the symbol)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        L.rz_upload_ik.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32), fp, ctypes.POINTER(u32), ctypes.POINTER(u32), u8p, fp, fp]
     for name in SYMBOLS:
         # (libraries older than the current ABI — tools/ab_inproc.py loads them side by side — lack the newer symbols: OPTIONAL_SYMBOLS)
         if name != "rz_last_error" and (name not in OPTIONAL_SYMBOLS or hasattr(L, name)):
@@ -494,6 +498,40 @@ class DeformContext:
         cc, a, b = (_f32(x).reshape(-1) for x in (c, r0, r1))
         assert cc.size == a.size == b.size == i.size * 3, (i.size, cc.size, a.size, b.size)
         self._chk(self._L.rz_upload_sdef(self._h, int(i.size), i.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _fptr(cc), _fptr(a), _fptr(b)))
+
+    def upload_ik(self, chains):
+        """PMX inverse kinematics for device-solved poses: `chains` = [dict(goal, effector, loops, limit_angle, links=[dict(bone,
+        min=None | [3], max=None | [3])])], links ordered from the effector outwards, limits in radians (synth.make_ik /
+        synth.make_leg_rig build such lists; the loader's bone.ik has the same fields with `goal` = the bone's own index). An empty
+        list removes the table. Needs upload_skeleton_topology first."""
+        chains = list(chains)
+        if not hasattr(self._L, "rz_upload_ik"):
+            raise RzError(-6, "this build of the library has no rz_upload_ik")
+        if not chains:
+            self._chk(self._L.rz_upload_ik(self._h, 0, None, None, None, None, None, None, None, None, None))
+            return
+        u32p, u8p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint8)
+        goal = np.array([int(ch["goal"]) for ch in chains], dtype=np.uint32)
+        eff = np.array([int(ch["effector"]) for ch in chains], dtype=np.uint32)
+        loops = np.array([int(ch["loops"]) for ch in chains], dtype=np.uint32)
+        theta = _f32([float(ch["limit_angle"]) for ch in chains])
+        off = np.zeros(len(chains) + 1, dtype=np.uint32)
+        bone, limited, lo, hi = [], [], [], []
+        for k, ch in enumerate(chains):
+            for ln in ch["links"]:
+                has = ln.get("min") is not None and ln.get("max") is not None
+                bone.append(int(ln["bone"])); limited.append(1 if has else 0)
+                lo.append([float(x) for x in ln["min"]] if has else [0.0, 0.0, 0.0])
+                hi.append([float(x) for x in ln["max"]] if has else [0.0, 0.0, 0.0])
+            off[k + 1] = len(bone)
+        n = max(len(bone), 1)
+        bone_a = np.zeros(n, dtype=np.uint32); bone_a[:len(bone)] = bone
+        lim_a = np.zeros(n, dtype=np.uint8); lim_a[:len(limited)] = limited
+        lo_a = np.zeros((n, 3), dtype=np.float32); lo_a[:len(lo)] = np.asarray(lo, dtype=np.float32).reshape(-1, 3)
+        hi_a = np.zeros((n, 3), dtype=np.float32); hi_a[:len(hi)] = np.asarray(hi, dtype=np.float32).reshape(-1, 3)
+        self._chk(self._L.rz_upload_ik(self._h, len(chains), goal.ctypes.data_as(u32p), eff.ctypes.data_as(u32p), loops.ctypes.data_as(u32p),
+                                       _fptr(theta), off.ctypes.data_as(u32p), bone_a.ctypes.data_as(u32p), lim_a.ctypes.data_as(u8p),
+                                       _fptr(lo_a), _fptr(hi_a)))
 
     def read_hull(self, instance=0, v0=0, n=None):
         n = self.V - v0 if n is None else n

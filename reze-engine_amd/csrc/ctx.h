@@ -132,6 +132,11 @@ struct rz_ctx {
     // SDEF vertices of this shard (rz_upload_sdef): [10][sdef_n] planes (kernels/sdef.hip); null = every vertex is skinned as the frame kernel skins it
     uint32_t *sdef_tab = nullptr;
     uint32_t sdef_n = 0;
+    // PMX IK chains of this skeleton (rz_upload_ik), grouped into stages (deform_kernels.h: RzIkParams); ik_n = 0: no IK stage, rz_fk_kernel as ever
+    uint4 *ik_chain = nullptr;
+    uint32_t *ik_path = nullptr, *ik_stage_off = nullptr;
+    float4 *ik_link = nullptr;
+    uint32_t ik_n = 0, ik_stages = 0;
 
     // morphs
     int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
@@ -342,6 +347,8 @@ void free_bone_morphs(rz_ctx *c);
 void forget_search(rz_ctx *c);
 void free_morphs(rz_ctx *c);
 void free_sdef(rz_ctx *c);
+void free_ik(rz_ctx *c);
+RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {
     *dst = nullptr;

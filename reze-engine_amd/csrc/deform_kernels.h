@@ -83,6 +83,18 @@ struct RzFkParams {
     uint64_t st_expect;
 };
 
+// PMX inverse kinematics (rz_upload_ik; kernels/ik.hip.h): the stage rz_fk_ik_kernel runs between the doubling rounds and the override
+// pass. A block of its own, handed to that kernel only: RzFkParams — embedded in the fused kernels' arguments — does not change.
+struct RzIkParams {
+    const uint4 *chain;         // [n_chains][2], sorted by (stage, IK bone): (goal, first path entry, path length, parent of the path's first bone or -1)
+                                //                                            (loops, bits(per-step angle limit), first link, links)
+    const uint32_t *path;       // per chain its path, outermost link ... effector, parents first: bone | bit 31 = the bone is a link of the chain
+    const float4 *link;         // [links][2] in file order: (min xyz | position on the path), (max xyz | 1 = limited)
+    const uint32_t *stage_off;  // [n_stages + 1] chains of each stage: chains of one stage do not read what another one of it writes
+    int n_stages;
+    int n_chains;
+};
+
 // rz_deform_kernel: fused morph + 4-bone LBS (engine/src/engine.ts:253-272).
 struct RzDeformParams {
     const float *geom;          // 6 planes of Vp floats: x y z nx ny nz
@@ -216,9 +228,21 @@ struct RzVariant {
 // second matrix buffer of the doubling rounds) + 12 B (local translation), 16-byte rounded
 __host__ __device__ inline size_t rz_fk_scratch_bytes(int B) { return ((size_t)B * 60 + 15) & ~(size_t)15; }
 
+// rz_fk_ik_kernel: the pose's morph weights in LDS (bone morphs), rounded so that the matrix buffer behind them is 16-byte aligned
+__host__ __device__ inline size_t rz_fk_mw_bytes(const RzFkParams &p)
+{
+    if (!p.bm_off) return 0;
+    const int m = p.bm_M > p.sample.M ? p.bm_M : p.sample.M;
+    return ((size_t)(m > 1 ? m : 1) * 4 + 15) & ~(size_t)15;
+}
+
 hipError_t rz_launch_prep(const RzPrepParams &p, uint32_t instances, hipStream_t st);
 hipError_t rz_launch_fk(const RzFkParams &p, uint32_t instances, hipStream_t st);
 size_t rz_fk_lds_bytes(const RzFkParams &p);      // dynamic LDS of rz_fk_kernel (palette rows + solve scratch + the pose's morph weights)
+// the hierarchy solve with the IK stage (rz_fk_ik_kernel): region X of the solve stays alive across the doubling rounds, which get a
+// second matrix buffer of their own — 48 B per bone more
+hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t instances, hipStream_t st);
+size_t rz_fk_ik_lds_bytes(const RzFkParams &p);
 hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
                             uint32_t instances, hipStream_t st);
 size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v);

@@ -381,6 +381,8 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
     q2 = make_float4(r[2][0], r[2][1], r[2][2], r[2][3]);
 }
 
+#include "ik.hip.h"
+
 // The body of the hierarchy solve, shared by rz_fk_kernel (one workgroup per pose, results to global memory) and by the
 // FUSED single-character frame, where every workgroup of the deform kernels runs it as its prologue: `wl` is then the deform
 // kernel's LDS palette (it ends up holding rows 0..2 of W * inverseBind), `scr` aliases its wave scratch, the sampled morph
@@ -400,10 +402,14 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // executes every instruction once. KIND 1 = an uploaded pose, KIND 2 = a sampled pose, both PLAIN: no physics overrides,
 // at most 512 bones (two per thread), at most 256 vertex morphs (one per thread) — the host picks the variant when all of that holds
 // (RzDeformParams::fk_kind) and the generic form (KIND 0) otherwise. Same device functions, same bits.
-template <bool FUSED, int KIND = 0>
+// IK (rz_fk_ik_kernel only, generic form): the PMX IK stage (kernels/ik.hip.h) runs between the doubling rounds and the override pass. The
+// stage re-forms local matrices, so region X must survive the rounds: they get `ik_m2`, a second matrix buffer of their own.
+template <bool FUSED, int KIND = 0, bool IK = false>
 __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &early, const int inst, float4 *wl, unsigned char *scr, float *lds_mw,
-                                         const bool to_global, const uint64_t st_tagv = 0ull, unsigned long long *fs = nullptr)
+                                         const bool to_global, const uint64_t st_tagv = 0ull, unsigned long long *fs = nullptr,
+                                         const RzIkParams *ik = nullptr, float4 *ik_m2 = nullptr)
 {
+    static_assert(!IK || (!FUSED && KIND == 0), "the IK stage belongs to the generic solve of rz_fk_ik_kernel");
     constexpr bool PLAIN = KIND != 0;
 #ifdef RZ_ABLATE
 #define RZ_FSTAMP(k) do { if (fs) fs[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -415,7 +421,7 @@ __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &ear
     float4 *sq = reinterpret_cast<float4 *>(scr);                    // [B] local rotations of this pose
     uint4 *s_rec = reinterpret_cast<uint4 *>(sq + p.B);              // [B] (parent, append parent, bits(append ratio), flags)
     float4 *s_bind = reinterpret_cast<float4 *>(s_rec + p.B);        // [B] parent-relative bind translation
-    float4 *m2 = reinterpret_cast<float4 *>(scr);                    // [B][3] aliases the three arrays above
+    float4 *m2 = IK ? ik_m2 : reinterpret_cast<float4 *>(scr);       // [B][3] aliases the three arrays above (IK: a buffer of its own)
     float *s_lt = reinterpret_cast<float *>(scr + (size_t)p.B * 48);    // [B][3] local translations of this pose
     const int tid = threadIdx.x;
     const float4 *lq = p.local_q + (size_t)inst * p.B;
@@ -601,6 +607,14 @@ __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &ear
         float4 *t4 = src; src = dst; dst = t4;
     }
     RZ_FSTAMP(3);             // doubling rounds done
+    if constexpr (IK) {
+        src = ik_stage(p, *ik, src, wl, m2, sq, s_rec, s_bind, s_lt, has_t, tid);
+#pragma unroll
+        for (int k = 0; k < NBR; ++k) {         // the registers of the output pass: the solved rows
+            const int b = tid + k * kBlock;
+            if (b < p.B) { rm[k][0] = src[b * 3]; rm[k][1] = src[b * 3 + 1]; rm[k][2] = src[b * 3 + 2]; }
+        }
+    }
     const bool overrides = !PLAIN && p.ovr_off != nullptr;
     if (overrides) {
         // physics-driven bones: the supplied world matrix replaces the solved one (rows 0..2 of the column-major 4x4)

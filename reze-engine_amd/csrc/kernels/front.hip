@@ -50,6 +50,17 @@ __global__ void __launch_bounds__(kBlock) rz_fk_kernel(const uint4 *k_rec, const
     fk_solve<false>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(scr + rz_fk_scratch_bytes(p.B)), true);
 }
 
+// The same solve with the PMX IK stage (kernels/ik.hip.h), launched instead of rz_fk_kernel only while the context holds an IK table.
+// LDS: palette rows | solve scratch | the pose's morph weights (bone morphs) | the doubling rounds' own second matrix buffer.
+__global__ void __launch_bounds__(kBlock) rz_fk_ik_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
+    unsigned char *scr = smem + (size_t)p.B * 48;
+    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
+    fk_solve<false, 0, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
+                             reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)));
+}
 
 // ------------------------------------------------------------------------------------------------
 // rz_pull_pose_kernel: a crowd's per-frame pose (0.8 - 3.3 MB for 256 characters) comes down by a PULL. The host lays the pose out in
@@ -155,6 +166,23 @@ __global__ void rz_pack_skinning_kernel(const uint16_t *joints4, const uint8_t *
 hipError_t rz_launch_prep(const RzPrepParams &p, uint32_t instances, hipStream_t st)
 {
     hipLaunchKernelGGL(rz_prep_kernel, dim3(instances), dim3(kBlock), 0, st, p);
+    return hipGetLastError();
+}
+
+size_t rz_fk_ik_lds_bytes(const RzFkParams &p)
+{
+    return (size_t)p.B * 48 + rz_fk_scratch_bytes(p.B) + rz_fk_mw_bytes(p) + (size_t)p.B * 48;
+}
+
+hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t instances, hipStream_t st)
+{
+    const size_t lds = rz_fk_ik_lds_bytes(p);
+    if (lds > 160 * 1024 || !ik.chain || ik.n_stages <= 0) return hipErrorInvalidValue;      // (the host checks first and says why: launch_fk in frame.cpp)
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_fk_ik_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(rz_fk_ik_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, ik);
     return hipGetLastError();
 }
 

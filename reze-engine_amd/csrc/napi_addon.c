@@ -16,7 +16,7 @@
 
 #include "../../include/reze_deform.h"
 
-#define MAX_ARGS 8
+#define MAX_ARGS 10
 
 static napi_value throw_msg(napi_env env, const char *msg)
 {
@@ -324,6 +324,35 @@ static napi_value fn_upload_sdef(napi_env env, napi_callback_info info)
     if (ni > 0xffffffffu || nc < ni * 3 || na < ni * 3 || nb < ni * 3) return throw_msg(env, "uploadSdef: c3 / r0_3 / r1_3 need 3 floats per index");
     int rc = ni ? rz_upload_sdef(ctx, (uint32_t)ni, (const uint32_t *)idx, (const float *)cc, (const float *)a, (const float *)b)
                 : rz_upload_sdef(ctx, 0, NULL, NULL, NULL, NULL);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* uploadIK(ctx, Uint32Array|null goal, Uint32Array effector, Uint32Array loops, Float32Array limitAngle, Uint32Array linkOff [chains + 1],
+ * Uint32Array linkBone, Uint8Array linkLimited, Float32Array linkMin3, Float32Array linkMax3): the IK chains of the skeleton (rz_upload_ik);
+ * an empty or null goal removes the table */
+static napi_value fn_upload_ik(napi_env env, napi_callback_info info)
+{
+    ARGS(10);
+    CTX(0);
+    void *g, *e, *lp, *th, *off, *lb, *ll, *lo, *hi;
+    size_t ng, ne, nlp, nth, noff, nlb, nll, nlo, nhi;
+    if (!get_ta(env, argv[1], napi_uint32_array, 1, &g, &ng) || !get_ta(env, argv[2], napi_uint32_array, 1, &e, &ne) ||
+        !get_ta(env, argv[3], napi_uint32_array, 1, &lp, &nlp) || !get_ta(env, argv[4], napi_float32_array, 1, &th, &nth) ||
+        !get_ta(env, argv[5], napi_uint32_array, 1, &off, &noff) || !get_ta(env, argv[6], napi_uint32_array, 1, &lb, &nlb) ||
+        !get_ta(env, argv[7], napi_uint8_array, 1, &ll, &nll) || !get_ta(env, argv[8], napi_float32_array, 1, &lo, &nlo) ||
+        !get_ta(env, argv[9], napi_float32_array, 1, &hi, &nhi))
+        return throw_msg(env, "uploadIK(ctx, Uint32Array goal, Uint32Array effector, Uint32Array loops, Float32Array limitAngle, Uint32Array linkOff, Uint32Array linkBone, Uint8Array linkLimited, Float32Array linkMin3, Float32Array linkMax3)");
+    if (ng == 0) {
+        int rc0 = rz_upload_ik(ctx, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+        return rc0 ? throw_rz(env, rc0) : undef(env);
+    }
+    if (ng > 0xffffu || ne < ng || nlp < ng || nth < ng || noff < ng + 1) return throw_msg(env, "uploadIK: effector / loops / limitAngle need one entry per chain, linkOff one more");
+    const uint32_t *o = (const uint32_t *)off;
+    size_t nl = 0;
+    for (size_t k = 0; k <= ng; ++k) if (o[k] > nl) nl = o[k];
+    if (nlb < nl || nll < nl || nlo < nl * 3 || nhi < nl * 3) return throw_msg(env, "uploadIK: the link arrays are shorter than linkOff says");
+    int rc = rz_upload_ik(ctx, (uint32_t)ng, (const uint32_t *)g, (const uint32_t *)e, (const uint32_t *)lp, (const float *)th, o, (const uint32_t *)lb,
+                          (const uint8_t *)ll, (const float *)lo, (const float *)hi);
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
@@ -1020,7 +1049,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "readGathered", fn_read_gathered }, { "commInitAll", fn_comm_init_all }, { "allgatherAll", fn_allgather_all },
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
-        { "uploadSdef", fn_upload_sdef },
+        { "uploadSdef", fn_upload_sdef }, { "uploadIK", fn_upload_ik },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

@@ -194,7 +194,8 @@ Plan make_plan(const rz_ctx *c)
     // mode (and 27.7 -> 24.5 us on a 1/8 shard of C5); local poses 12.7-14.4 -> 9.8-12.8 us without dense morphs, no gain
     // with them (there the three-kernel frame keeps its kernel-argument morph list and streams from its first instruction).
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
-    pl.fuse_fk = c->I == 1 && c->pose_local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
+    // (an IK table keeps the solve in a kernel of its own, rz_fk_ik_kernel: the fused kernels carry no IK stage)
+    pl.fuse_fk = c->ik_n == 0 && c->I == 1 && c->pose_local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
                  (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pose_sampled || c->morph_mode != 1)));
     const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
@@ -398,11 +399,11 @@ int ensure_run_subsets(rz_ctx *c)
 // Plan of the next frame: the run lists first (the plan only takes the subset form when they match its shape).
 // Can the next crowd frame solve its hierarchy in the skin kernel's front? A device-animated crowd in the bone-subset form, nothing
 // acting on the solved pose between the solve and the palette (bone morphs fold weights in, physics overrides replace world matrices:
-// both stay with rz_fk_kernel), "fuse_fk" not switched off.
+// both stay with rz_fk_kernel; so does the IK stage of rz_fk_ik_kernel), "fuse_fk" not switched off.
 bool subfk_wanted(const rz_ctx *c)
 {
     return c->I > 1 && c->pose_local && c->has_topology && c->t_fusefk != 0 && c->t_subsets != 0 && c->sub_valid && c->sub_max < c->B &&
-           !(c->bm_count && c->M) && c->ovr_count == 0 && c->fk_host.size() == (size_t)c->B * 4;
+           !(c->bm_count && c->M) && c->ovr_count == 0 && c->ik_n == 0 && c->fk_host.size() == (size_t)c->B * 4;
 }
 
 // The closure records of the current run lists (see ctx.h). Host work + one readback of the lists, only when the lists or the
@@ -548,6 +549,16 @@ RzFkParams fk_params(const rz_ctx *c)
         q.feed_off = c->an_feed_off; q.feed_range = c->an_feed_range; q.feed_ratio = c->an_feed_ratio;
         q.morph_w = c->morph_w; q.M = (int)c->M;
     }
+    return p;
+}
+
+RzIkParams ik_params(const rz_ctx *c)
+{
+    RzIkParams p;
+    memset(&p, 0, sizeof p);
+    if (!c->ik_n) return p;
+    p.chain = c->ik_chain; p.path = c->ik_path; p.link = c->ik_link; p.stage_off = c->ik_stage_off;
+    p.n_stages = (int)c->ik_stages; p.n_chains = (int)c->ik_n;
     return p;
 }
 

@@ -256,6 +256,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "instances")) *value = (int)c->I;
     else if (!strcmp(key, "verts")) *value = (int)c->V;
     else if (!strcmp(key, "sdef_verts")) *value = (int)c->sdef_n;
+    else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
     else if (!strcmp(key, "nt_store")) *value = c->t_nts;
     else if (!strcmp(key, "fast")) *value = c->t_fast;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;

@@ -163,6 +163,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     c->fk_host.clear(); c->fk_rounds = 0; c->fk_gen++;
     c->fk_stale = false; c->subfk_valid = false;
     free_bone_morphs(c);                // ... as do bone morphs (their entries name its bones)
+    free_ik(c);                         // ... and the IK table (its chains name its bones)
     free_animation(c);                  // ... and so does an uploaded motion (its tracks name bones of that skeleton)
     return ensure_pose_buffers(c);
 }
@@ -325,6 +326,7 @@ int rz_upload_skeleton_topology(rz_ctx *c, uint32_t B, const int32_t *parents, c
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
+    free_ik(c);                         // its chains were checked against the old parents
     c->ovr_count = 0;
     c->fk_stale = false;                // (a crowd frame solved under the old topology: nothing of it can be formed on demand any more)
     dfree(c->fk_anc_more);
@@ -504,6 +506,148 @@ int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float 
             for (uint32_t k = 0; k < n; ++k) memcpy(&tab[(size_t)(1 + 3 * a + d) * n + k], &src[a][(size_t)k * 3 + d], 4);
     if (int r = to_device(&c->sdef_tab, tab.data(), tab.size())) return r;
     c->sdef_n = n;
+    return RZ_OK;
+}
+
+int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint32_t *effector, const uint32_t *loops, const float *limit_angle,
+                 const uint32_t *link_off, const uint32_t *link_bone, const uint8_t *link_limited, const float *link_min3, const float *link_max3)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_ik")) return r;
+    if (n_chains == 0) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        free_ik(c);
+        return RZ_OK;
+    }
+    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4) return fail(RZ_ERR_INVALID, "IK acts on device-solved poses: call rz_upload_skeleton_topology first");
+    if (n_chains > 65535) return fail(RZ_ERR_INVALID, "rz_upload_ik: %u chains (at most 65535)", n_chains);
+    if (!goal || !effector || !loops || !limit_angle || !link_off) return fail(RZ_ERR_INVALID, "rz_upload_ik: null chain arrays for %u chains", n_chains);
+    for (uint32_t k = 0; k < n_chains; ++k)
+        if (link_off[k] > link_off[k + 1]) return fail(RZ_ERR_INVALID, "rz_upload_ik: link offsets must be non-decreasing (chain %u)", k);
+    if (link_off[0] != 0) return fail(RZ_ERR_INVALID, "rz_upload_ik: link offsets start at %u, not 0", link_off[0]);
+    const uint32_t NL = link_off[n_chains];
+    if (NL && (!link_bone || !link_limited || !link_min3 || !link_max3)) return fail(RZ_ERR_INVALID, "rz_upload_ik: null link arrays for %u links", NL);
+    const uint32_t B = c->B;
+    auto parent_of = [&](uint32_t b) { return (int32_t)c->fk_host[4 * (size_t)b].x; };
+    auto append_of = [&](uint32_t b) -> int32_t {          // the bone whose local rotation b's local matrix reads, or -1 (fk_local_matrix)
+        const uint4 r = c->fk_host[4 * (size_t)b];
+        float ratio;
+        memcpy(&ratio, &r.z, 4);
+        return ((int32_t)r.y >= 0 && fabsf(fminf(1.0f, fmaxf(-1.0f, ratio))) > 1e-6f) ? (int32_t)r.y : -1;
+    };
+    // per chain: the path, outermost link ... effector (parents first), and the checks of "a valid table"
+    std::vector<std::vector<uint32_t>> path(n_chains);
+    std::vector<uint8_t> is_link((size_t)n_chains * B, 0), any_link(B, 0);
+    for (uint32_t k = 0; k < n_chains; ++k) {
+        const uint32_t nl = link_off[k + 1] - link_off[k];
+        if (goal[k] >= B || effector[k] >= B) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u names bone %u / %u of %u", k, goal[k], effector[k], B);
+        if (goal[k] == effector[k]) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u: the effector is the goal (bone %u)", k, goal[k]);
+        if (nl > 255) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u has %u links (at most 255)", k, nl);
+        if ((int32_t)loops[k] < 0) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u: loop count out of range", k);
+        if (!(limit_angle[k] == limit_angle[k]) || limit_angle[k] - limit_angle[k] != 0.0f) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u: the angle limit is not finite", k);
+        std::vector<uint32_t> rev{effector[k]};             // effector upwards
+        uint32_t cur = effector[k];
+        for (uint32_t e = link_off[k]; e < link_off[k + 1]; ++e) {
+            const uint32_t L = link_bone[e];
+            if (L >= B) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u: link %u names bone %u of %u", k, e - link_off[k], L, B);
+            for (int j = 0; j < 3; ++j) {
+                const float lo = link_min3[(size_t)e * 3 + j], hi = link_max3[(size_t)e * 3 + j];
+                if (link_limited[e] && (!(lo == lo) || lo - lo != 0.0f || !(hi == hi) || hi - hi != 0.0f))
+                    return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u: the limits of link %u are not finite", k, e - link_off[k]);
+            }
+            // every link is a proper ancestor of the one before it (the first: of the effector)
+            int32_t p = parent_of(cur);
+            while (p >= 0 && (uint32_t)p != L) { rev.push_back((uint32_t)p); p = parent_of((uint32_t)p); }
+            if (p < 0) return fail(RZ_ERR_INVALID, "rz_upload_ik: chain %u: link bone %u is not a proper ancestor of bone %u", k, L, cur);
+            rev.push_back(L);
+            is_link[(size_t)k * B + L] = 1; any_link[L] = 1;
+            cur = L;
+        }
+        path[k].assign(rev.rbegin(), rev.rend());
+    }
+    for (uint32_t k = 0; k < n_chains; ++k) {
+        if (path[k].size() > 64 && link_off[k + 1] > link_off[k])
+            return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: chain %u spans %zu bones from its outermost link to its effector: a chain is solved by one wave, one path bone per lane (at most 64)", k, path[k].size());
+        for (uint32_t b : path[k])
+            if (append_of(b) >= 0 && any_link[(uint32_t)append_of(b)])
+                return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: bone %u on the path of chain %u takes its append rotation from bone %d, a link of an IK chain: every step would need the whole solve", b, k, append_of(b));
+        // ... and so would a step when a bone ABOVE the path (an ancestor of the effector) copies the rotation of one of the chain's own links:
+        // turning the link would move the whole path under it
+        for (int32_t x = parent_of(path[k][0]); x >= 0; x = parent_of((uint32_t)x))
+            if (append_of((uint32_t)x) >= 0 && is_link[(size_t)k * B + (uint32_t)append_of((uint32_t)x)])
+                return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: bone %d, an ancestor of the effector of chain %u, takes its append rotation from bone %d, a link of that chain: every step would need the whole solve", x, k, append_of((uint32_t)x));
+        // the goal must hold still while its chain is solved
+        for (int32_t x = (int32_t)goal[k]; x >= 0; x = parent_of((uint32_t)x))
+            if (is_link[(size_t)k * B + (uint32_t)x] || (append_of((uint32_t)x) >= 0 && is_link[(size_t)k * B + (uint32_t)append_of((uint32_t)x)]))
+                return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: the goal of chain %u (bone %u) hangs below its own link %d: the goal would move with every step", k, goal[k], x);
+    }
+    // solve order: ascending IK bone (stable). Stages: a chain comes after every earlier chain whose links move a bone it reads (goal,
+    // effector — whose ancestors cover the path —, through parents or an append rotation), and not before an earlier chain that reads a
+    // bone ITS links move (that chain must not see it)
+    std::vector<uint32_t> ord(n_chains);
+    for (uint32_t k = 0; k < n_chains; ++k) ord[k] = k;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return goal[a] < goal[b]; });
+    for (uint32_t k = 1; k < n_chains; ++k)
+        if (goal[ord[k]] == goal[ord[k - 1]]) return fail(RZ_ERR_INVALID, "rz_upload_ik: two chains share the IK bone %u", goal[ord[k]]);
+    auto moves = [&](uint32_t mover, uint32_t reader) {      // do the links of `mover` change the world matrix of a bone `reader` reads?
+        const uint32_t reads[2] = { goal[reader], effector[reader] };
+        for (uint32_t s : reads)
+            for (int32_t x = (int32_t)s; x >= 0; x = parent_of((uint32_t)x)) {
+                if (is_link[(size_t)mover * B + (uint32_t)x]) return true;
+                const int32_t ap = append_of((uint32_t)x);
+                if (ap >= 0 && is_link[(size_t)mover * B + (uint32_t)ap]) return true;
+            }
+        return false;
+    };
+    std::vector<uint32_t> stage(n_chains, 0);
+    uint32_t n_stages = 0;
+    for (uint32_t i = 0; i < n_chains; ++i) {
+        uint32_t s = 0;
+        for (uint32_t j = 0; j < i; ++j) {
+            if (moves(ord[j], ord[i])) s = std::max(s, stage[j] + 1);
+            else if (moves(ord[i], ord[j])) s = std::max(s, stage[j]);
+        }
+        stage[i] = s;
+        n_stages = std::max(n_stages, s + 1);
+    }
+    std::vector<uint32_t> by_stage(n_chains);
+    for (uint32_t i = 0; i < n_chains; ++i) by_stage[i] = i;
+    std::stable_sort(by_stage.begin(), by_stage.end(), [&](uint32_t a, uint32_t b) { return stage[a] < stage[b]; });
+    std::vector<uint4> rec((size_t)n_chains * 2);
+    std::vector<uint32_t> pth, soff(n_stages + 1, 0);
+    std::vector<float4> lnk;
+    for (uint32_t i = 0; i < n_chains; ++i) {
+        const uint32_t k = ord[by_stage[i]];
+        soff[stage[by_stage[i]] + 1]++;
+        const uint32_t nl = link_off[k + 1] - link_off[k];
+        uint32_t tb;
+        memcpy(&tb, &limit_angle[k], 4);
+        rec[2 * (size_t)i] = make_uint4(goal[k], (uint32_t)pth.size(), (uint32_t)path[k].size(), (uint32_t)parent_of(path[k][0]));
+        rec[2 * (size_t)i + 1] = make_uint4(loops[k], tb, (uint32_t)lnk.size() / 2, nl);
+        for (uint32_t e = link_off[k]; e < link_off[k + 1]; ++e) {
+            uint32_t pos = 0;
+            while (path[k][pos] != link_bone[e]) ++pos;
+            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+            if (link_limited[e]) {
+                lo = make_float4(link_min3[(size_t)e * 3], link_min3[(size_t)e * 3 + 1], link_min3[(size_t)e * 3 + 2], 0.f);
+                hi = make_float4(link_max3[(size_t)e * 3], link_max3[(size_t)e * 3 + 1], link_max3[(size_t)e * 3 + 2], 0.f);
+            }
+            const uint32_t lim = link_limited[e] ? 1u : 0u;
+            memcpy(&lo.w, &pos, 4); memcpy(&hi.w, &lim, 4);
+            lnk.push_back(lo); lnk.push_back(hi);
+        }
+        for (uint32_t b : path[k]) pth.push_back(b | (is_link[(size_t)k * B + b] ? 0x80000000u : 0u));
+    }
+    for (uint32_t s = 0; s < n_stages; ++s) soff[s + 1] += soff[s];
+    if (lnk.empty()) { lnk.push_back(make_float4(0.f, 0.f, 0.f, 0.f)); lnk.push_back(make_float4(0.f, 0.f, 0.f, 0.f)); }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_ik(c);
+    drop_graph(c);
+    if (int r = to_device(&c->ik_chain, rec.data(), rec.size())) return r;
+    if (int r = to_device(&c->ik_path, pth.data(), pth.size())) return r;
+    if (int r = to_device(&c->ik_link, lnk.data(), lnk.size())) return r;
+    if (int r = to_device(&c->ik_stage_off, soff.data(), soff.size())) return r;
+    c->ik_n = n_chains; c->ik_stages = n_stages;
     return RZ_OK;
 }
 

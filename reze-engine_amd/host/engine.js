@@ -47,6 +47,7 @@ class Engine {
     this.bounds = o.bounds === true // also reduce the deformed mesh's bounding box every frame
     // SDEF vertices (PMX weight type 3) skinned as MMD does; off (the default), they are skinned as BDEF2 like the reference does
     this.sdef = o.sdef === true
+    this.ik = o.ik === true // PMX inverse kinematics: off unless asked for (device solve with deviceFK, else Model.solveIK on the host)
     // gather: true = RCCL all-gather of the deformed mesh after every frame (needs distinct GPUs);
     // 'direct' = every shard's kernel stores straight into GPU devices[0]'s buffer over xGMI (no collective)
     this.gather = o.gather === 'direct' ? 'direct' : o.gather === true
@@ -179,6 +180,7 @@ class Engine {
     this.overrides = null // they name bones of the previous model; the library drops its copy with the skeleton (rz_upload_skeleton)
     this.currentModel = model
     model.setClock(() => this.now())
+    model.setIK(this.ik && !this.deviceFK) // host solve: only without the device hierarchy (a model without IK bones: a no-op)
     const n = this.native, skinning = model.getSkinning(), skeleton = model.getSkeleton()
     const morphs = model.getMorphs()
     const V = model.getVertexCount()
@@ -206,6 +208,26 @@ class Engine {
           }
         })
         n.uploadSkeletonTopology(s.ctx, parents, bind, ap, ar, am)
+        // IK is per skeleton, not per vertex: every shard gets the same table, after the topology its chains are checked against
+        const chains = this.ik ? model.getIKChains() : []
+        if (chains.length > 0) {
+          let nl = 0
+          for (const ch of chains) nl += ch.links.length
+          const goal = new Uint32Array(chains.length), eff = new Uint32Array(chains.length), loops = new Uint32Array(chains.length)
+          const theta = new Float32Array(chains.length), off = new Uint32Array(chains.length + 1)
+          const lb = new Uint32Array(nl), ll = new Uint8Array(nl), lmin = new Float32Array(nl * 3), lmax = new Float32Array(nl * 3)
+          let e = 0
+          chains.forEach((ch, k) => {
+            goal[k] = ch.goal; eff[k] = ch.effector; loops[k] = ch.loops; theta[k] = ch.limitAngle
+            for (const l of ch.links) {
+              lb[e] = l.bone
+              if (l.min && l.max) { ll[e] = 1; lmin.set(l.min, e * 3); lmax.set(l.max, e * 3) }
+              e++
+            }
+            off[k + 1] = e
+          })
+          n.uploadIK(s.ctx, goal, eff, loops, theta, off, lb, ll, lmin, lmax)
+        }
       }
       if (morphs && morphs.names.length > 0) {
         const M = morphs.names.length

@@ -99,6 +99,14 @@ class Model {
     this.hasBoneMorphs = !!(this.morphs && this.morphs.boneEntries && this.morphs.boneEntries.morph.length > 0)
     this.poseRotations = new Float32Array(this.hasBoneMorphs ? n * 4 : 0)
     this.poseTranslations = new Float32Array(this.hasBoneMorphs ? n * 3 : 0)
+    // PMX inverse kinematics: off unless the engine is asked for it ({ ik: true }); the chains come from the loader's bone.ik
+    this.ikEnabled = false
+    this.ikChains = null
+    this.ikRotations = new Float32Array(0)
+    this.ikTranslations = new Float32Array(0)
+    this._ikR = new Float64Array(0)
+    this._ikP = new Float64Array(0)
+    this._ikDeps = {}
   }
 
   static parentFirstOrder(bones) {
@@ -242,7 +250,7 @@ class Model {
   computeWorldMatrices() {
     const bones = this.skeleton.bones
     const n = bones.length
-    const { rot, tra, moved } = this.posedLocals()
+    const { rot, tra, moved } = this.ikEnabled ? this.solveIK() : this.posedLocals()
     const useT = this.applyLocalTranslations || moved
     const world = this.runtimeSkeleton.worldMatrices
     const R = this._rot, A = this._app, T = this._tr, X = this._tmpA, L = this._tmpB
@@ -291,6 +299,147 @@ class Model {
       }
     }
     this.runtimeSkeleton.computedBones.fill(true)
+  }
+
+  /** The model's IK chains (bones the loader gave an `ik` block), ascending IK bone index: the solve order. `goal` is the IK bone itself. */
+  getIKChains() {
+    if (!this.ikChains) {
+      const out = []
+      const bones = this.skeleton.bones
+      for (let i = 0; i < bones.length; i++) {
+        const k = bones[i].ik
+        if (!k) continue
+        out.push({ goal: i, effector: k.effector, loops: k.loops, limitAngle: k.limitAngle, links: k.links.map((l) => ({ bone: l.bone, min: l.min, max: l.max })) })
+      }
+      this.ikChains = out
+    }
+    return this.ikChains
+  }
+
+  /** Switch the host IK solve on or off (a model without IK bones stays off). */
+  setIK(on) { this.ikEnabled = !!on && this.getIKChains().length > 0 }
+
+  /**
+   * PMX inverse kinematics on the host: CCD in the clamp form, the arithmetic of tests/ik_ref.py (the definition; GPU twin:
+   * csrc/kernels/ik.hip.h) in doubles, the solved rotations stored to a Float32Array pose copy like posedLocals() does for bone
+   * morphs - the runtime's tween and animation state is never overwritten. Chains in ascending order of the IK bone; per iteration and
+   * link L (file order: effector outwards): a, b = effector and goal in L's frame, q[L] = normalize(clamp(q[L] * quat(a x b,
+   * min(atan2(|a x b|, a . b), limitAngle)))), Euler limits in three.js 'XYZ' order; the bones that depend on q[L] are re-solved after
+   * every link. Returns the local pose computeWorldMatrices() then solves; called from there only when IK is on.
+   */
+  solveIK() {
+    const src = this.posedLocals()
+    const bones = this.skeleton.bones, n = bones.length
+    const useT = this.applyLocalTranslations || src.moved
+    if (this.ikRotations.length !== n * 4) {
+      this.ikRotations = new Float32Array(n * 4); this.ikTranslations = new Float32Array(n * 3)
+      this._ikR = new Float64Array(n * 9); this._ikP = new Float64Array(n * 3)
+    }
+    const rot = this.ikRotations, tra = this.ikTranslations, R = this._ikR, P = this._ikP
+    rot.set(src.rot)
+    if (useT) tra.set(src.tra); else tra.fill(0)
+    const sq = this._q
+    const M = new Float64Array(9), A = new Float64Array(9), X = new Float64Array(9)
+    const qmat = (o, x, y, z, w) => {
+      const x2 = x + x, y2 = y + y, z2 = z + z
+      const xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2, wx = w * x2, wy = w * y2, wz = w * z2
+      o[0] = 1 - (yy + zz); o[1] = xy - wz; o[2] = xz + wy
+      o[3] = xy + wz; o[4] = 1 - (xx + zz); o[5] = yz - wx
+      o[6] = xz - wy; o[7] = yz + wx; o[8] = 1 - (xx + yy)
+    }
+    const solveBone = (i) => {
+      const b = bones[i]
+      qmat(M, rot[i * 4], rot[i * 4 + 1], rot[i * 4 + 2], rot[i * 4 + 3])
+      let ax = 0, ay = 0, az = 0
+      const ap = b.appendParentIndex
+      if (b.appendRotate && ap !== undefined && ap !== null && ap >= 0 && ap < n) {
+        const ratio = b.appendRatio === undefined || b.appendRatio === null ? 1 : Math.max(-1, Math.min(1, b.appendRatio))
+        if (Math.abs(ratio) > 1e-6) {
+          let qx = rot[ap * 4], qy = rot[ap * 4 + 1], qz = rot[ap * 4 + 2]
+          if (ratio < 0) { qx = -qx; qy = -qy; qz = -qz }
+          slerpInto(sq, 0, 0, 0, 1, qx, qy, qz, rot[ap * 4 + 3], Math.abs(ratio))
+          qmat(A, sq[0], sq[1], sq[2], sq[3])
+          for (let r = 0; r < 3; r++) for (let c = 0; c < 3; c++) X[r * 3 + c] = A[r * 3] * M[c] + A[r * 3 + 1] * M[3 + c] + A[r * 3 + 2] * M[6 + c]
+          M.set(X)
+          if (b.appendMove) {
+            const rr = b.appendRatio === undefined || b.appendRatio === null ? 1 : b.appendRatio
+            ax = tra[ap * 3] * rr; ay = tra[ap * 3 + 1] * rr; az = tra[ap * 3 + 2] * rr
+          }
+        }
+      }
+      const tx = b.bindTranslation[0] + tra[i * 3] + (M[0] * ax + M[1] * ay + M[2] * az)
+      const ty = b.bindTranslation[1] + tra[i * 3 + 1] + (M[3] * ax + M[4] * ay + M[5] * az)
+      const tz = b.bindTranslation[2] + tra[i * 3 + 2] + (M[6] * ax + M[7] * ay + M[8] * az)
+      const p = b.parentIndex, o = i * 9
+      if (p >= 0 && p < n) {
+        const q = p * 9
+        for (let r = 0; r < 3; r++) {
+          for (let c = 0; c < 3; c++) X[r * 3 + c] = R[q + r * 3] * M[c] + R[q + r * 3 + 1] * M[3 + c] + R[q + r * 3 + 2] * M[6 + c]
+          P[i * 3 + r] = R[q + r * 3] * tx + R[q + r * 3 + 1] * ty + R[q + r * 3 + 2] * tz + P[p * 3 + r]
+        }
+        for (let k = 0; k < 9; k++) R[o + k] = X[k]
+      } else {
+        for (let k = 0; k < 9; k++) R[o + k] = M[k]
+        P[i * 3] = tx; P[i * 3 + 1] = ty; P[i * 3 + 2] = tz
+      }
+    }
+    const dependents = (L) => {
+      let d = this._ikDeps[L]
+      if (d) return d
+      const hit = new Uint8Array(n)
+      d = []
+      for (let k = 0; k < n; k++) {      // parent-first order: a bone depends on q[L] if it is L, appends from L, or its parent does
+        const i = this.solveOrder[k], b = bones[i]
+        const p = b.parentIndex
+        if (i === L || (b.appendRotate && b.appendParentIndex === L) || (p >= 0 && p < n && hit[p])) { hit[i] = 1; d.push(i) }
+      }
+      this._ikDeps[L] = d
+      return d
+    }
+    for (let k = 0; k < n; k++) solveBone(this.solveOrder[k])
+    const v = [0, 0, 0, 0, 0, 0]
+    for (const ch of this.getIKChains()) {
+      const G = ch.goal, E = ch.effector
+      for (let it = 0; it < ch.loops; it++) {
+        let rotated = false
+        for (const link of ch.links) {
+          const L = link.bone, o = L * 9
+          for (let s = 0; s < 2; s++) {          // v[0..2] = Rw^T (E - L), v[3..5] = Rw^T (G - L)
+            const T = s === 0 ? E : G
+            const dx = P[T * 3] - P[L * 3], dy = P[T * 3 + 1] - P[L * 3 + 1], dz = P[T * 3 + 2] - P[L * 3 + 2]
+            for (let c = 0; c < 3; c++) v[s * 3 + c] = R[o + c] * dx + R[o + 3 + c] * dy + R[o + 6 + c] * dz
+          }
+          const la = Math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), lb = Math.sqrt(v[3] * v[3] + v[4] * v[4] + v[5] * v[5])
+          if (la < 1e-6 || lb < 1e-6) continue
+          const ax = v[0] / la, ay = v[1] / la, az = v[2] / la, bx = v[3] / lb, by = v[4] / lb, bz = v[5] / lb
+          const cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx
+          const nn = Math.sqrt(cx * cx + cy * cy + cz * cz)
+          if (nn < 1e-7) continue
+          const ang = Math.min(Math.atan2(nn, ax * bx + ay * by + az * bz), ch.limitAngle)
+          const sn = Math.sin(ang * 0.5) / nn, rx = cx * sn, ry = cy * sn, rz = cz * sn, rw = Math.cos(ang * 0.5)
+          const x = rot[L * 4], y = rot[L * 4 + 1], z = rot[L * 4 + 2], w = rot[L * 4 + 3]      // Hamilton product q[L] * dq
+          let qx = w * rx + x * rw + y * rz - z * ry, qy = w * ry - x * rz + y * rw + z * rx
+          let qz = w * rz + x * ry - y * rx + z * rw, qw = w * rw - x * rx - y * ry - z * rz
+          if (link.min && link.max) {
+            qmat(M, qx, qy, qz, qw)
+            let e1 = Math.asin(Math.max(-1, Math.min(1, M[2]))), e0, e2
+            if (Math.abs(M[2]) < 0.9999999) { e0 = Math.atan2(-M[5], M[8]); e2 = Math.atan2(-M[1], M[0]) } else { e0 = Math.atan2(M[7], M[4]); e2 = 0 }
+            const cl = (e, a) => Math.min(Math.max(e, Math.min(link.min[a], link.max[a])), Math.max(link.min[a], link.max[a]))
+            e0 = cl(e0, 0); e1 = cl(e1, 1); e2 = cl(e2, 2)
+            const c1 = Math.cos(e0 / 2), c2 = Math.cos(e1 / 2), c3 = Math.cos(e2 / 2), s1 = Math.sin(e0 / 2), s2 = Math.sin(e1 / 2), s3 = Math.sin(e2 / 2)
+            qx = s1 * c2 * c3 + c1 * s2 * s3; qy = c1 * s2 * c3 - s1 * c2 * s3; qz = c1 * c2 * s3 + s1 * s2 * c3; qw = c1 * c2 * c3 - s1 * s2 * s3
+          }
+          const il = 1 / Math.sqrt(qx * qx + qy * qy + qz * qz + qw * qw)
+          rot[L * 4] = qx * il; rot[L * 4 + 1] = qy * il; rot[L * 4 + 2] = qz * il; rot[L * 4 + 3] = qw * il
+          rotated = true
+          const dep = dependents(L)
+          for (let k = 0; k < dep.length; k++) solveBone(dep[k])
+        }
+        const dx = P[G * 3] - P[E * 3], dy = P[G * 3 + 1] - P[E * 3 + 1], dz = P[G * 3 + 2] - P[E * 3 + 2]
+        if (Math.sqrt(dx * dx + dy * dy + dz * dz) < 1e-4 || !rotated) break
+      }
+    }
+    return { rot, tra, moved: true }
   }
 
   /** Pose every bone the sampler keys at `frame` (rotation + translation), and every morph it keys. Un-keyed bones keep their state. */

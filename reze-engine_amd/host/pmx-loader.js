@@ -227,22 +227,30 @@ class PmxLoader {
       if (flags & 0x0400) c.skip(12) // axis limit
       if (flags & 0x0800) c.skip(24) // local axes
       if (flags & 0x2000) c.i32() // external parent
-      if (flags & 0x0020) { // IK block (parsed to keep the cursor aligned; IK solving is out of scope)
-        c.index(bs); c.i32(); c.f32()
-        const links = c.i32()
-        for (let l = 0; l < links; l++) { c.index(bs); if (c.u8() === 1) c.skip(24) }
+      let ik // IK block: the bone is an IK goal (solved only on request: Engine { ik: true }, Model.solveIK / rz_upload_ik)
+      if (flags & 0x0020) {
+        const effector = c.index(bs), loops = c.i32(), limitAngle = c.f32()
+        const nl = c.i32(), links = []
+        for (let l = 0; l < nl; l++) {
+          const link = { bone: c.index(bs) }
+          if (c.u8() === 1) { link.min = c.vec3(); link.max = c.vec3() } // Euler limits, radians as stored
+          links.push(link)
+        }
+        ik = { effector, loops, limitAngle, links }
       }
-      raw[i] = { name, parent, p, appendParent, appendRatio, appendRotate, appendMove }
+      raw[i] = { name, parent, p, appendParent, appendRatio, appendRotate, appendMove, ik }
     }
     // absolute positions -> parent-relative bind translations (pmx-loader.ts:416-442)
     return raw.map((b) => {
       const hasParent = b.parent >= 0 && b.parent < n
       const pp = hasParent ? raw[b.parent].p : [0, 0, 0]
-      return {
+      const bone = {
         name: b.name, parentIndex: b.parent, bindTranslation: [b.p[0] - pp[0], b.p[1] - pp[1], b.p[2] - pp[2]],
         children: [], appendParentIndex: b.appendParent, appendRatio: b.appendRatio, appendRotate: b.appendRotate,
         appendMove: b.appendMove,
       }
+      if (b.ik) bone.ik = b.ik // only bones with flag 0x0020 carry the field: every other bone is the object it was
+      return bone
     })
   }
 

@@ -20,7 +20,12 @@ export interface Bone {
   appendRatio?: number
   appendRotate?: boolean
   appendMove?: boolean
+  /** PMX IK block (flag 0x0020): this bone is the goal. Links run from the effector outwards; limits are Euler angles in radians as stored. */
+  ik?: IKBlock
 }
+export interface IKLink { bone: number; min?: Triple; max?: Triple }
+export interface IKBlock { effector: number; loops: number; limitAngle: number; links: IKLink[] }
+export interface IKChain extends IKBlock { goal: number }
 /** model.ts:36-45 */
 export interface Skeleton { bones: Bone[]; inverseBindMatrices: Float32Array }
 export interface Skinning { joints: Uint16Array; weights: Uint8Array }
@@ -96,6 +101,7 @@ export interface DeformAddon {
   uploadBoneMorphs(ctx: DeformContext, morph: Uint32Array | null, bone: Uint32Array | null, translation3: Float32Array | null, rotation4: Float32Array | null): void
   uploadAnimation(ctx: DeformContext, motion: FlatMotion): void
   uploadEdgeScale(ctx: DeformContext, edge: Float32Array | null): void
+  uploadIK(ctx: DeformContext, goal: Uint32Array | null, effector: Uint32Array | null, loops: Uint32Array | null, limitAngle: Float32Array | null, linkOff: Uint32Array | null, linkBone: Uint32Array | null, linkLimited: Uint8Array | null, linkMin3: Float32Array | null, linkMax3: Float32Array | null): void
   uploadSdef(ctx: DeformContext, index: Uint32Array | null, c3: Float32Array | null, r0_3: Float32Array | null, r1_3: Float32Array | null): void
   enableAabb(ctx: DeformContext, on: boolean): void
   setInstances(ctx: DeformContext, count: number): void
@@ -132,7 +138,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; ik?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }

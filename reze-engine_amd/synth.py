@@ -338,3 +338,119 @@ def make_sdef(mesh, frac, seed=SEED + 7, cluster=0):
     r0 = (c + rng.uniform(-0.05, 0.05, size=c.shape)).astype(np.float32)
     r1 = (c + rng.uniform(-0.05, 0.05, size=c.shape)).astype(np.float32)
     return dict(idx=idx, c=c, r0=r0, r1=r1)
+
+
+def _ancestors(parents, b):
+    out, p = [], int(parents[b])
+    while p >= 0:
+        out.append(p)
+        p = int(parents[p])
+    return out
+
+
+def make_ik(mesh, n_chains=4, seed=SEED + 11, links=2, loops=12, limit_angle=1.0, limited=True, rigid=False):
+    """PMX IK chains on the mesh's synthetic skeleton, as `upload_ik` / tests/ik_ref.py take them: up to n_chains chains (fewer when the
+    tree runs out of places) of `links` links each — the effector's nearest ancestors, or every second one with rigid=True, which leaves a
+    rigid bone between two links. The goal of a chain is a bone outside the subtree of its outermost link (it holds still while the chain
+    is solved), goals are distinct; limited=True gives the first link of every chain Euler limits. The mesh is not changed. Returns a list
+    of dict(goal, effector, loops, limit_angle, links=[dict(bone, min, max)]) in ascending order of the goal."""
+    rng = np.random.default_rng(seed)
+    parents = np.asarray(mesh["parents"])
+    B = len(parents)
+    step = 2 if rigid else 1
+    anc = [_ancestors(parents, b) for b in range(B)]
+    chains, used_goal = [], set()
+    for e in rng.permutation(B):
+        if len(chains) >= n_chains:
+            break
+        e = int(e)
+        if len(anc[e]) < links * step + 1:
+            continue
+        lk = [anc[e][k * step + step - 1] for k in range(links)]
+        top = lk[-1]
+        cand = [g for g in rng.permutation(B) if int(g) != e and int(g) not in used_goal and top != int(g) and top not in anc[int(g)]]
+        if not cand:
+            continue
+        g = int(cand[0])
+        used_goal.add(g)
+        ll = []
+        for k, b in enumerate(lk):
+            if limited and k == 0:
+                lo = rng.uniform(-2.0, -0.2, size=3)
+                hi = rng.uniform(0.2, 2.0, size=3)
+                lo[1], hi[1] = max(lo[1], -1.2), min(hi[1], 1.2)
+                ll.append(dict(bone=int(b), min=[float(x) for x in lo.astype(np.float32)], max=[float(x) for x in hi.astype(np.float32)]))
+            else:
+                ll.append(dict(bone=int(b), min=None, max=None))
+        chains.append(dict(goal=g, effector=e, loops=int(loops), limit_angle=float(np.float32(limit_angle)), links=ll))
+    return sorted(chains, key=lambda ch: ch["goal"])
+
+
+LEG_RIG_NAMES = ["root", "centre", "leg_L", "knee_L", "ankle_L", "toe_L", "leg_R", "knee_R", "ankle_R", "toe_R",
+                 "leg_ik_L", "toe_ik_L", "leg_ik_R", "toe_ik_R"]
+
+
+def make_leg_rig(n_verts=0, seed=SEED + 12):
+    """The 14-bone two-leg rig of an MMD model's lower body: root, centre, 2 x (leg, knee, ankle, toe), 2 x leg-IK goal under the root and
+    2 x toe-IK goal under the leg-IK goal. Legs are 10 units long (thigh and shin 5 each), knees limited to X in [-180, -0.5] degrees; the
+    leg chains run 40 iterations at 2 rad per step over (knee, leg), the toe chains 3 iterations at 4 rad over (ankle). Returns a mesh dict
+    like make_mesh (n_verts vertices skinned to the rig's bones; quats = identity) plus names, chains, hips (leg bone of every leg chain),
+    l1 / l2 (thigh and shin length)."""
+    parents = np.array([-1, 0, 1, 2, 3, 4, 1, 6, 7, 8, 0, 10, 0, 12], dtype=np.int32)
+    bind = np.zeros((14, 3), dtype=np.float32)
+    bind[1] = (0.0, 12.0, 0.0)
+    for s, leg in ((1.0, 2), (-1.0, 6)):
+        bind[leg] = (s, -1.0, 0.0)
+        bind[leg + 1] = (0.0, -5.0, -0.1)        # the knee sits slightly forward, as in every MMD model: the leg bends one way
+        bind[leg + 2] = (0.0, -5.0, 0.1)
+        bind[leg + 3] = (0.0, -1.0, -1.5)
+    bind[10] = (1.0, 1.0, 0.0); bind[11] = (0.0, -1.0, -1.5)
+    bind[12] = (-1.0, 1.0, 0.0); bind[13] = (0.0, -1.0, -1.5)
+    knee_lo, knee_hi = [float(np.float32(-np.pi)), 0.0, 0.0], [float(np.float32(-0.5 * np.pi / 180.0)), 0.0, 0.0]
+    chains = []
+    for leg, goal in ((2, 10), (6, 12)):
+        chains.append(dict(goal=goal, effector=leg + 2, loops=40, limit_angle=2.0,
+                           links=[dict(bone=leg + 1, min=knee_lo, max=knee_hi), dict(bone=leg, min=None, max=None)]))
+        chains.append(dict(goal=goal + 1, effector=leg + 3, loops=3, limit_angle=4.0, links=[dict(bone=leg + 2, min=None, max=None)]))
+    chains.sort(key=lambda ch: ch["goal"])
+    quats = np.zeros((14, 4), dtype=np.float32)
+    quats[:, 3] = 1
+    out = dict(parents=parents, bind=bind, quats=quats, inv_bind=inverse_bind_translation_only(parents, bind),
+               world=fk_world(parents, bind, quats), names=list(LEG_RIG_NAMES), chains=chains, hips={10: 2, 12: 6},
+               l1=float(np.linalg.norm(bind[3])), l2=float(np.linalg.norm(bind[4])))
+    if n_verts:
+        rng = np.random.default_rng(seed)
+        lo, hi = np.array([-3.0, 0.0, -3.0], dtype=np.float32), np.array([3.0, 13.0, 3.0], dtype=np.float32)
+        out["pos"] = (lo + rng.random((n_verts, 3), dtype=np.float32) * (hi - lo)).astype(np.float32)
+        n = rng.standard_normal((n_verts, 3), dtype=np.float32)
+        out["nrm"] = (n / np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-12)).astype(np.float32)
+        out["joints"], out["weights"] = make_skinning(n_verts, 10, rng)        # the goal bones skin nothing
+    return out
+
+
+def leg_rig_pose(rig, seed, reach=(0.3, 0.9)):
+    """A random pose of the leg rig: the centre moved and turned, every leg goal put at reach[0] .. reach[1] of the leg's length from where
+    the hip ends up (so in reach for reach[1] < 1; above 1: out of reach), toes goals nudged. Returns (quats [14,4] f32, translations [14,3] f32)."""
+    rng = np.random.default_rng(seed)
+    q = np.zeros((14, 4), dtype=np.float32); q[:, 3] = 1
+    t = np.zeros((14, 3), dtype=np.float32)
+
+    def rq(max_angle):
+        ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+        a = rng.uniform(-max_angle, max_angle)
+        return np.concatenate([ax * np.sin(a / 2), [np.cos(a / 2)]]).astype(np.float32)
+    q[1] = rq(0.4)
+    t[1] = rng.uniform(-1.0, 1.0, size=3).astype(np.float32)
+    for b in (2, 4, 5, 6, 8, 9):           # the knees are left to the solver, as a motion leaves them
+        q[b] = rq(0.3)
+    w = fk_world(rig["parents"], rig["bind"] + t, q).reshape(14, 4, 4)
+    length = rig["l1"] + rig["l2"]
+    for goal, leg in rig["hips"].items():
+        hip = w[leg][3, :3].astype(np.float64)
+        d = np.array([rng.uniform(-0.6, 0.6), -1.0, rng.uniform(-0.8, 0.6)])
+        d /= np.linalg.norm(d)
+        p = hip + d * length * rng.uniform(*reach)
+        t[goal] = (p - np.asarray(rig["bind"][goal], dtype=np.float64)).astype(np.float32)      # the goal hangs under the root, which stays put
+        t[goal + 1] = rng.uniform(-0.3, 0.3, size=3).astype(np.float32)
+        q[goal] = rq(0.3)
+    return q, t
