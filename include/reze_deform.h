@@ -130,6 +130,27 @@ int rz_upload_morphs_sparse(rz_ctx *ctx, uint32_t M, const uint32_t *morph_off,
  * rz_upload_mesh* drops it; it drops a captured graph. */
 int rz_upload_sdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx, const float *c3, const float *r0_3, const float *r1_3);
 
+/* QDEF skinning (PMX 2.1 weight type 4, dual-quaternion blending) — opt-in; the reference folds QDEF vertices into BDEF4 and so does every
+ * frame without a table. For a listed vertex of this shard: joints j0..j3 (clamped to B - 1) and weights w_i = u8_i / isum exactly as
+ * the linear path decodes them (isum == 0: (1, 0, 0, 0)); slots of weight zero contribute nothing; p~ the morphed rest position (this
+ * frame's weights, ascending morph order, zero weights skipped), n the rest normal.
+ *   per bone j:  S_j = palette rows (world x inverseBind, 3 x 4); q_j = the unit quaternion of its upper 3 x 3 (Shepperd's method);
+ *                t_j = its fourth column; d_j = 1/2 (t_j, 0) (x) q_j:  d.xyz = 1/2 (q.w t + t x q.xyz),  d.w = -1/2 t . q.xyz.
+ *                A palette that is not rigid (scale, shear) loses its non-rigid part here. PMX poses are rigid.
+ *   blend (Kavan et al., dual-quaternion linear blending): pivot = the slot with the largest u8 weight, the lowest slot on ties;
+ *                s_i = -1 if dot(q_pivot, q_ji) < 0 else +1;  b_r = sum w_i s_i q_ji,  b_d = sum w_i s_i d_ji (slots ascending);
+ *                n_b = |b_r| (>= w_pivot >= 1/4);  c_r = b_r / n_b,  c_d = b_d / n_b
+ *   P' = R(c_r) p~ + 2 (c_r.w c_d.xyz - c_d.w c_r.xyz + c_r.xyz x c_d.xyz);  N' = normalize(R(c_r) n) (zero or non-finite: the rest
+ *   normal);  hull = P' + N' edge 0.01.   (tests/qdef_ref.py restates this in float64.)
+ * vert_idx[n] are relative to this shard, strictly ascending and < V; n = 0 / NULL removes the table. A vertex listed in the SDEF table
+ * too is refused (RZ_ERR_INVALID) by whichever of the two uploads comes second: a PMX vertex has one weight type. Every frame then runs
+ * one extra pass (rz_qdef_kernel) behind the deform / skin kernel (and behind the SDEF pass) for the listed vertices, writing positions,
+ * normals and, when on, the outline hull, and extending the bounding box as the SDEF pass does; rz_get_tuning("qdef_verts") says how
+ * many (0 = no pass). Crowd frames that keep their palettes in LDS only also run the palette kernel in front of the pass, once for both
+ * passes. Refused while forks exist (they borrow the table); rz_upload_mesh* drops it; it drops a captured graph. The ABI version stays
+ * 8: bindings detect the symbol. */
+int rz_upload_qdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx);
+
 /* PMX inverse kinematics — NEW (the reference's loader skips the IK block, engine/src/pmx-loader.ts). Opt-in: without a table every
  * frame launches what it launched before. n_chains IK bones; chain k: goal[k] = the IK bone itself, effector[k] = the bone that is moved
  * onto it (PMX: "target"), loops[k] iterations, limit_angle[k] radians per step, links link_off[k] .. link_off[k + 1] ordered from the
@@ -297,7 +318,7 @@ int rz_read_palette(rz_ctx *ctx, uint32_t instance, float *rows3x4);
  * outline pipeline no longer re-skins; NULL turns it off. rz_read_hull reads it back.
  * rz_enable_aabb: every frame also reduces the axis-aligned bounding box of the deformed positions of each
  * instance inside the skin kernel (no extra pass over the mesh); rz_read_aabb returns min xyz, max xyz of the
- * most recent frame. With an SDEF table (rz_upload_sdef) the SDEF pass extends that box by the SDEF vertices' final positions, so the
+ * most recent frame. With an SDEF table (rz_upload_sdef; the same holds for a QDEF table, rz_upload_qdef) the pass extends that box by the listed vertices' final positions, so the
  * box is that of all final positions together with the BDEF2 positions the skin kernel computed for the SDEF vertices first: a
  * conservative bound (it contains every final position), not always the tightest one. */
 int rz_upload_edge_scale(rz_ctx *ctx, uint32_t V, const float *edge_size);
@@ -347,6 +368,8 @@ int rz_time_span(rz_ctx *a, rz_ctx *b, uint32_t lead, uint32_t frames, double *s
  * rotations, a quarter of the bytes, stay with the copy engine, which does not disturb the frame they run under; 1: every such pose
  * is pulled; 0: the runtime copies every pose as it was handed over; rz_get_tuning("pose_pulled") / ("pose_rows") tell what the
  * last upload did),
+ * "qdef_chunks" (0 auto = 1, 1..64: how many 256-vertex chunks of the QDEF table one workgroup of rz_qdef_kernel takes behind one
+ * conversion of the skeleton to dual quaternions; same bits),
  * "overlap" (-1 / 0 off, 1: crowds run their front kernels on the upload stream under
  * the previous frame's skin kernel — measured slower on this runtime, kept for experiments). There is no key that makes a frame
  * emit anything but the deformed mesh: ablation switches exist only in a tools-only build and "dbg" is rejected here.
@@ -355,7 +378,7 @@ int rz_time_span(rz_ctx *a, rz_ctx *b, uint32_t lead, uint32_t frames, double *s
  * "effective_subsets" / "effective_subset_bones" / "effective_inst_lds" / "effective_fk_kind" / "effective_variant" (the last template
  * argument of the single-mesh frame kernel: 0 everything compiled in, 3 without the fused consumers, 1 / 2 also with the specialised
  * hierarchy solve) and the counts
- * "verts" / "bones" / "morphs" / "instances" / "sdef_verts" (SDEF vertices the next frame fixes, 0 = no SDEF pass). Unknown keys return RZ_ERR_INVALID.
+ * "verts" / "bones" / "morphs" / "instances" / "sdef_verts" (SDEF vertices the next frame fixes, 0 = no SDEF pass) / "qdef_verts" (likewise for QDEF). Unknown keys return RZ_ERR_INVALID.
  * NOT a pure getter for crowds: an "effective_*" key describes the frame the NEXT rz_deform will launch, and a crowd's plan depends on
  * the per-run bone lists of its launch shape — when the shape, the mesh or the skeleton changed since the last frame the call brings
  * them up to date first, exactly as the next frame would (stream drained, one small kernel, one readback, a captured graph dropped).

@@ -21,11 +21,12 @@ SYMBOLS = [
     "rz_autotune_apply", "rz_output_ptrs",
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
+    "rz_upload_qdef",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
-# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik — detected by the symbol, the version stayed 8)
+# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik and rz_upload_qdef — detected by the symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
-                    "rz_upload_ik"}
+                    "rz_upload_ik", "rz_upload_qdef"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 
 
@@ -146,6 +147,8 @@ def load(path=None):
         L.rz_time_span.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_double)]
     if hasattr(L, "rz_upload_sdef"):           # (ABI 8)
         L.rz_upload_sdef.argtypes = [vp, u32, ctypes.POINTER(u32), fp, fp, fp]
+    if hasattr(L, "rz_upload_qdef"):           # (ABI 8 still: the feature is detected by the symbol)
+        L.rz_upload_qdef.argtypes = [vp, u32, ctypes.POINTER(u32)]
     if hasattr(L, "rz_upload_ik"):             # (ABI 8 still: the feature is detected by the symbol)
         u8p = ctypes.POINTER(ctypes.c_uint8)
         L.rz_upload_ik.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32), fp, ctypes.POINTER(u32), ctypes.POINTER(u32), u8p, fp, fp]
@@ -498,6 +501,17 @@ class DeformContext:
         cc, a, b = (_f32(x).reshape(-1) for x in (c, r0, r1))
         assert cc.size == a.size == b.size == i.size * 3, (i.size, cc.size, a.size, b.size)
         self._chk(self._L.rz_upload_sdef(self._h, int(i.size), i.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _fptr(cc), _fptr(a), _fptr(b)))
+
+    def upload_qdef(self, idx):
+        """QDEF (PMX 2.1 weight type 4, dual-quaternion blending) for the listed vertices of this shard: idx [n] shard-relative and strictly
+        ascending, disjoint from the SDEF table. An empty `idx` removes the table."""
+        if not hasattr(self._L, "rz_upload_qdef"):
+            raise RzError(-6, "this build of the library has no rz_upload_qdef")
+        i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        if i.size == 0:
+            self._chk(self._L.rz_upload_qdef(self._h, 0, None))
+            return
+        self._chk(self._L.rz_upload_qdef(self._h, int(i.size), i.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
 
     def upload_ik(self, chains):
         """PMX inverse kinematics for device-solved poses: `chains` = [dict(goal, effector, loops, limit_angle, links=[dict(bone,

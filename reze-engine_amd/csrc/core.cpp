@@ -210,6 +210,16 @@ void free_sdef(rz_ctx *c)
     if (c->lender) c->sdef_tab = nullptr;     // a fork's table is its lender's
     dfree(c->sdef_tab);
     c->sdef_n = 0;
+    c->sdef_idx_host.clear();
+}
+
+void free_qdef(rz_ctx *c)
+{
+    drop_graph(c);
+    if (c->lender) c->qdef_tab = nullptr;     // a fork's table is its lender's
+    dfree(c->qdef_tab);
+    c->qdef_n = 0;
+    c->qdef_idx_host.clear();
 }
 
 void free_ik(rz_ctx *c)
@@ -328,6 +338,7 @@ int rz_destroy(rz_ctx *c)
         c->bm_off = c->bm_morph = nullptr; c->bm_rot = c->bm_tr = nullptr;
         c->dense = nullptr; c->sp_ptr = nullptr; c->sp_entries = nullptr; c->edge = nullptr;
         c->sdef_tab = nullptr; c->sdef_n = 0;
+        c->qdef_tab = nullptr; c->qdef_n = 0;
         c->ik_chain = nullptr; c->ik_path = c->ik_stage_off = nullptr; c->ik_link = nullptr; c->ik_n = c->ik_stages = 0;
         c->lender->n_forks--;
         c->lender = nullptr;
@@ -347,6 +358,7 @@ int rz_destroy(rz_ctx *c)
     free_bone_morphs(c);
     free_morphs(c);
     free_sdef(c);
+    free_qdef(c);
     free_ik(c);
     for (int k = 0; k < 2; ++k) {
         if (c->big_ev[k]) (void)hipEventDestroy(c->big_ev[k]);
@@ -405,6 +417,7 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
     c->morph_mode = parent->morph_mode; c->M = parent->M; c->Mpad = parent->Mpad; c->dense = parent->dense;
     c->sp_ptr = parent->sp_ptr; c->sp_entries = parent->sp_entries; c->sp_count = parent->sp_count;
     c->sdef_tab = parent->sdef_tab; c->sdef_n = parent->sdef_n;
+    c->qdef_tab = parent->qdef_tab; c->qdef_n = parent->qdef_n; c->t_qdefchunks = parent->t_qdefchunks;
     c->ik_chain = parent->ik_chain; c->ik_path = parent->ik_path; c->ik_stage_off = parent->ik_stage_off; c->ik_link = parent->ik_link;
     c->ik_n = parent->ik_n; c->ik_stages = parent->ik_stages;
     c->edge = parent->edge; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on;

@@ -132,6 +132,10 @@ struct rz_ctx {
     // SDEF vertices of this shard (rz_upload_sdef): [10][sdef_n] planes (kernels/sdef.hip); null = every vertex is skinned as the frame kernel skins it
     uint32_t *sdef_tab = nullptr;
     uint32_t sdef_n = 0;
+    // QDEF vertices of this shard (rz_upload_qdef): [qdef_n] indices (kernels/qdef.hip); null = every vertex is skinned as the frame kernel skins it
+    uint32_t *qdef_tab = nullptr;
+    uint32_t qdef_n = 0;
+    std::vector<uint32_t> sdef_idx_host, qdef_idx_host;     // the two tables' vertex lists (a vertex may be in one of them only); empty on a fork
     // PMX IK chains of this skeleton (rz_upload_ik), grouped into stages (deform_kernels.h: RzIkParams); ik_n = 0: no IK stage, rz_fk_kernel as ever
     uint4 *ik_chain = nullptr;
     uint32_t *ik_path = nullptr, *ik_stage_off = nullptr;
@@ -266,7 +270,7 @@ struct rz_ctx {
     RzMorphList ml;
 
     // tuning (0 / -1 = automatic)
-    int t_split = 0, t_unroll = 0, t_grid_cap = 0, t_nt = 1, t_nts = -1, t_geo = 0, t_fast = -1, t_instloop = -1, t_dbg = 0, t_outcap = -1, t_instblock = 0, t_instorder = 1, t_overlap = -1, t_zerocopy = -1, t_fusefk = -1;
+    int t_split = 0, t_unroll = 0, t_grid_cap = 0, t_nt = 1, t_nts = -1, t_geo = 0, t_fast = -1, t_instloop = -1, t_dbg = 0, t_outcap = -1, t_instblock = 0, t_instorder = 1, t_overlap = -1, t_zerocopy = -1, t_fusefk = -1, t_qdefchunks = 0;
     // Bone-subset crowd frames: per vertex run of the CURRENT launch shape, the ascending list of bones the run's
     // vertices name, and the joints rewritten as slots of that list. Derived from the static mesh, rebuilt (one small kernel +
     // one readback of the counts) whenever the shape (vertices per run, runs), the mesh or the skeleton changes.
@@ -347,6 +351,7 @@ void free_bone_morphs(rz_ctx *c);
 void forget_search(rz_ctx *c);
 void free_morphs(rz_ctx *c);
 void free_sdef(rz_ctx *c);
+void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
 RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
@@ -391,7 +396,8 @@ bool want_overlap(const rz_ctx *c, const Plan &pl);
 int set_overlap(rz_ctx *c, bool on);
 int run_frame(rz_ctx *c, const Plan &pl);
 RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl);
-int launch_sdef(rz_ctx *c, const Plan &pl, const RzSdefParams &sp);
+RzQdefParams qdef_params(const rz_ctx *c, const Plan &pl);
+int launch_passes(rz_ctx *c, const RzSdefParams &sp, const RzQdefParams &qp);
 hipStream_t front_stream(const rz_ctx *c);       // the stream per-frame inputs travel on and front kernels run on
 
 // ---- comm.cpp ----

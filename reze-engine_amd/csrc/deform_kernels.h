@@ -213,6 +213,38 @@ struct RzSdefParams {
 struct RzMorphList;
 hipError_t rz_launch_sdef(const RzSdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st);
 
+// rz_qdef_kernel (kernels/qdef.hip): dual-quaternion skinning of the vertices listed by rz_upload_qdef, the same kind of pass. The frame
+// fields carry the names they have in RzSdefParams (kernels/pass_parts.hip.h reads either struct).
+struct RzQdefParams {
+    const uint32_t *tab;        // [n] vertex indices (ascending, < V)
+    const float *geom;          // 6 planes of Vp floats
+    const uint32_t *joints01;   // [Vp] j0 | j1 << 16
+    const uint32_t *joints23;   // [Vp] j2 | j3 << 16
+    const uint32_t *weights;    // [Vp] 4 x unorm8
+    const float4 *palette;      // [I][B][3] this frame's palette rows
+    const float *dense;
+    const uint32_t *sp_ptr;
+    const float4 *sp_entries;
+    const float *morph_w;
+    const uint32_t *act_idx;
+    const float *act_w;
+    const int *act_count;
+    float *out_pos, *out_nrm;
+    const float *edge;
+    float *out_hull;
+    uint32_t *aabb;
+    uint32_t n;
+    int mode, M, Mpad;
+    int wsrc;
+    int aabb_slot;
+    uint32_t Vp;
+    int B;
+    int chunks;                 // 256-vertex chunks of the table one workgroup takes behind one conversion of the skeleton (>= 1)
+    int pad_;
+};                              // (no padding: frame_signature() hashes the struct)
+size_t rz_qdef_lds_bytes(int B);       // dynamic LDS of the pass: the skeleton's dual quaternions, 32 B per bone
+hipError_t rz_launch_qdef(const RzQdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st);
+
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).
 struct RzVariant {
     int mode;    // 0 none, 1 dense, 2 sparse

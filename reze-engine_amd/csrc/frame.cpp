@@ -88,14 +88,11 @@ int launch_deform(rz_ctx *c, const Plan &pl)
     return RZ_OK;
 }
 
-// The SDEF pass (kernels/sdef.hip) of a frame whose deform / skin kernel has just been enqueued. Its parameters are taken BEFORE that
-// launch (sdef_params): the bounding-box slot the frame accumulates into, and the morph weights where the frame read them.
-RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl)
+// The passes behind the deform / skin kernel of a frame: SDEF (kernels/sdef.hip) and QDEF (kernels/qdef.hip), each for the vertices its
+// table lists. Their parameters are taken BEFORE that launch (sdef_params / qdef_params): the bounding-box slot the frame accumulates
+// into, and the morph weights where the frame read them. S is RzSdefParams or RzQdefParams (the frame fields carry the same names).
+template <typename S> static void pass_frame_fields(const rz_ctx *c, const Plan &pl, S &s)
 {
-    RzSdefParams s;
-    memset(&s, 0, sizeof s);
-    if (!c->sdef_tab || c->sdef_n == 0) return s;
-    s.tab = c->sdef_tab; s.n = c->sdef_n;
     s.geom = c->geom; s.joints01 = c->j01; s.weights = c->wq; s.palette = c->palette;
     if (c->morph_mode != 0 && c->M > 0) {
         s.mode = c->morph_mode; s.M = (int)c->M; s.Mpad = (int)c->Mpad;
@@ -120,35 +117,56 @@ RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl)
     if (c->edge) { s.edge = c->edge; s.out_hull = c->out_hull; }
     if (c->aabb_on) { s.aabb = c->aabb; s.aabb_slot = c->aabb_slot; }
     s.Vp = c->Vp; s.B = (int)c->B;
+}
+
+RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl)
+{
+    RzSdefParams s;
+    memset(&s, 0, sizeof s);
+    if (!c->sdef_tab || c->sdef_n == 0) return s;
+    s.tab = c->sdef_tab; s.n = c->sdef_n;
+    pass_frame_fields(c, pl, s);
+    return s;
+}
+
+RzQdefParams qdef_params(const rz_ctx *c, const Plan &pl)
+{
+    RzQdefParams s;
+    memset(&s, 0, sizeof s);
+    if (!c->qdef_tab || c->qdef_n == 0) return s;
+    s.tab = c->qdef_tab; s.n = c->qdef_n; s.joints23 = c->j23;
+    pass_frame_fields(c, pl, s);
+    s.chunks = c->t_qdefchunks > 0 ? c->t_qdefchunks : 1;       // ("qdef_chunks"; the default is the measured one: NOTEBOOK.md, profiles/qdef_cost.txt)
     return s;
 }
 
 // Behind the deform / skin kernel on the frame's stream. Crowd forms that formed their palettes in LDS only (palette_stale: the bone-subset
-// skin kernel; fk_stale: the one-launch device-animated crowd) get them written first by the palette kernel those flags name — SDEF crowds
-// of those forms pay that kernel.
-int launch_sdef(rz_ctx *c, const Plan &pl, const RzSdefParams &sp)
+// skin kernel; fk_stale: the one-launch device-animated crowd) get them written first by the palette kernel those flags name, once for
+// both passes — crowds of those forms with a table pay that kernel.
+int launch_passes(rz_ctx *c, const RzSdefParams &sp, const RzQdefParams &qp)
 {
-    (void)pl;
-    if (sp.n == 0) return RZ_OK;
+    if (sp.n == 0 && qp.n == 0) return RZ_OK;
     if (solve_on_demand(c) || c->palette_stale) {
         // (never under the overlapped-front protocol: its frames have a front, which writes the ring slot's palettes, and the forms that
         // keep palettes in LDS only have none; a palette kernel here would read the pose block on the wrong stream)
-        if (c->overlap_on) return fail(RZ_ERR_INVALID, "SDEF pass: an overlapped crowd frame left no palette in memory");
+        if (c->overlap_on) return fail(RZ_ERR_INVALID, "SDEF / QDEF pass: an overlapped crowd frame left no palette in memory");
         if (solve_on_demand(c)) {
             if (int r = launch_fk(c, c->stream)) return r;
         } else if (int r = launch_prep(c, c->stream)) return r;
     }
-    HIP_TRY(rz_launch_sdef(sp, c->ml, c->I, c->stream));
+    if (sp.n) HIP_TRY(rz_launch_sdef(sp, c->ml, c->I, c->stream));
+    if (qp.n) HIP_TRY(rz_launch_qdef(qp, c->ml, c->I, c->stream));
     return RZ_OK;
 }
 
-// the deform / skin kernel of a frame and, when the context has an SDEF table, the SDEF pass behind it
-static int launch_deform_sdef(rz_ctx *c, const Plan &pl)
+// the deform / skin kernel of a frame and, when the context has an SDEF or a QDEF table, the passes behind it
+static int launch_deform_passes(rz_ctx *c, const Plan &pl)
 {
-    if (!c->sdef_n) return launch_deform(c, pl);
+    if (!c->sdef_n && !c->qdef_n) return launch_deform(c, pl);
     const RzSdefParams sp = sdef_params(c, pl);
+    const RzQdefParams qp = qdef_params(c, pl);
     if (int r = launch_deform(c, pl)) return r;
-    return launch_sdef(c, pl, sp);
+    return launch_passes(c, sp, qp);
 }
 
 // Crowds overlap the front kernels of a frame with the skin kernel of the frame before it. The protocol
@@ -186,13 +204,13 @@ int run_frame(rz_ctx *c, const Plan &pl)
         if (int r = launch_front(c, pl, c->up_stream)) return r;
         HIP_TRY(hipEventRecord(c->ev_front[s], c->up_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_front[s], 0));
-        if (int r = launch_deform_sdef(c, pl)) return r;        // (the SDEF pass reads the slot's palettes and active lists too: ev_skin goes behind it)
+        if (int r = launch_deform_passes(c, pl)) return r;        // (the SDEF / QDEF passes read the slot's palettes and active lists too: ev_skin goes behind them)
         HIP_TRY(hipEventRecord(c->ev_skin[s], c->stream));
         c->skin_recorded[s] = true;
         return RZ_OK;
     }
     if (int r = launch_front(c, pl, c->stream)) return r;
-    return launch_deform_sdef(c, pl);
+    return launch_deform_passes(c, pl);
 }
 
 // the stream per-frame inputs travel on and front kernels run on
@@ -240,6 +258,8 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     h = fnv(h, &sf, sizeof sf);
     const RzSdefParams sd = sdef_params(c, pl);
     h = fnv(h, &sd, sizeof sd);
+    const RzQdefParams qd = qdef_params(c, pl);
+    h = fnv(h, &qd, sizeof qd);
     if (c->ik_n) { const RzIkParams ik = ik_params(c); h = fnv(h, &ik, sizeof ik); }
     const uint64_t misc[6] = { c->I, c->pose_local, c->pose_local_t, c->pose_sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
@@ -275,7 +295,7 @@ int rz_deform_n(rz_ctx *c, uint32_t frames)
             int rc = RZ_OK;
             for (uint32_t k = 0; k < kGraphFrames && rc == RZ_OK; ++k) {
                 rc = launch_front(c, pl, c->stream);
-                if (rc == RZ_OK) rc = launch_deform_sdef(c, pl);
+                if (rc == RZ_OK) rc = launch_deform_passes(c, pl);
             }
             hipError_t ce = hipStreamEndCapture(c->stream, &g);
             if (rc != RZ_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -434,10 +454,10 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
     HIP_TRY(hipEventSynchronize(c->ev1));
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     out->frame_ms = ms / frames;
-    // the deform / skin kernel alone (reads the ring slot the last frame left current), with the SDEF pass when there is a table
+    // the deform / skin kernel alone (reads the ring slot the last frame left current), with the SDEF / QDEF passes when there is a table
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     for (uint32_t f = 0; f < frames; ++f)
-        if (int r = launch_deform_sdef(c, pl)) return r;
+        if (int r = launch_deform_passes(c, pl)) return r;
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     HIP_TRY(hipEventSynchronize(c->ev1));
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));

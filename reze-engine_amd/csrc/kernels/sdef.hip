@@ -12,37 +12,9 @@
 //   rw = w0 R0 + w1 R1; cr0 = (C + (C + R0 - rw)) / 2; cr1 = (C + (C + R1 - rw)) / 2
 //   P' = R (p~ - C) + w0 S0 (cr0, 1) + w1 S1 (cr1, 1);   N' = normalize(R n) (a zero-length result keeps the rest normal)
 // The float64 restatement the tests hold this to is tests/sdef_ref.py.
-#include "common.hip.h"
+#include "pass_parts.hip.h"
 
 namespace {
-
-struct Quatf { float x, y, z, w; };
-
-// unit quaternion of a rotation given as three matrix rows (Shepperd: branch on the trace, then on the largest diagonal)
-__device__ __forceinline__ Quatf quat_of_rows(const float4 r0, const float4 r1, const float4 r2)
-{
-    const float m00 = r0.x, m01 = r0.y, m02 = r0.z, m10 = r1.x, m11 = r1.y, m12 = r1.z, m20 = r2.x, m21 = r2.y, m22 = r2.z;
-    const float tr = m00 + m11 + m22;
-    Quatf q;
-    if (tr > 0.0f) {
-        const float s = sqrtf(tr + 1.0f) * 2.0f;
-        q.w = 0.25f * s; q.x = (m21 - m12) / s; q.y = (m02 - m20) / s; q.z = (m10 - m01) / s;
-    } else if (m00 > m11 && m00 > m22) {
-        const float s = sqrtf(1.0f + m00 - m11 - m22) * 2.0f;
-        q.w = (m21 - m12) / s; q.x = 0.25f * s; q.y = (m01 + m10) / s; q.z = (m02 + m20) / s;
-    } else if (m11 > m22) {
-        const float s = sqrtf(1.0f + m11 - m00 - m22) * 2.0f;
-        q.w = (m02 - m20) / s; q.x = (m01 + m10) / s; q.y = 0.25f * s; q.z = (m12 + m21) / s;
-    } else {
-        const float s = sqrtf(1.0f + m22 - m00 - m11) * 2.0f;
-        q.w = (m10 - m01) / s; q.x = (m02 + m20) / s; q.y = (m12 + m21) / s; q.z = 0.25f * s;
-    }
-    const float l = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    const float k = l > 0.0f ? 1.0f / l : 0.0f;
-    q.x *= k; q.y *= k; q.z *= k; q.w *= k;
-    if (l == 0.0f) q.w = 1.0f;
-    return q;
-}
 
 // math.ts slerpInto, with the hemisphere already chosen by the caller
 __device__ __forceinline__ Quatf slerp_q(const Quatf a, const Quatf b, const float t)
@@ -66,33 +38,6 @@ __device__ __forceinline__ float3 affine(const float4 r0, const float4 r1, const
 {
     return make_float3(fmaf(r0.z, z, fmaf(r0.y, y, fmaf(r0.x, x, r0.w))), fmaf(r1.z, z, fmaf(r1.y, y, fmaf(r1.x, x, r1.w))),
                        fmaf(r2.z, z, fmaf(r2.y, y, fmaf(r2.x, x, r2.w))));
-}
-
-constexpr int kChunk = 512;        // morph weights compacted into LDS at a time (frames whose active list is not in memory already)
-
-// this frame's deltas of vertex v for an ordered active list (idx[k] + base, w[k]), k < n. A lane's reads are gathers from scattered
-// vertices: a batch of them is issued before the first is used (the accumulation keeps ascending morph order), else the pass waits out one
-// memory latency per morph.
-__device__ __forceinline__ void add_dense(const uint32_t *idx, const float *w, const int n, const uint32_t base, const float *dense, const size_t Vp,
-                                          const uint32_t v, float &x, float &y, float &z)
-{
-    constexpr int U = 8;
-    int k = 0;
-    for (; k + U <= n; k += U) {
-        float ww[U], dx[U], dy[U], dz[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            ww[u] = w[k + u];
-            const float *d = dense + (size_t)(idx[k + u] + base) * 3 * Vp + v;
-            dx[u] = d[0]; dy[u] = d[Vp]; dz[u] = d[2 * Vp];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) { x = fmaf(ww[u], dx[u], x); y = fmaf(ww[u], dy[u], y); z = fmaf(ww[u], dz[u], z); }
-    }
-    for (; k < n; ++k) {
-        const float *d = dense + (size_t)(idx[k] + base) * 3 * Vp + v;
-        x = fmaf(w[k], d[0], x); y = fmaf(w[k], d[Vp], y); z = fmaf(w[k], d[2 * Vp], z);
-    }
 }
 
 // One lane per (SDEF vertex, instance): grid.x covers the table, grid.y = instance. The dense morph weights come from where the frame left

@@ -327,6 +327,20 @@ static napi_value fn_upload_sdef(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+/* uploadQdef(ctx, Uint32Array|null index): QDEF vertices of this shard (shard-relative, strictly ascending); an empty or null index removes
+ * the table */
+static napi_value fn_upload_qdef(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    void *idx;
+    size_t ni;
+    if (!get_ta(env, argv[1], napi_uint32_array, 1, &idx, &ni)) return throw_msg(env, "uploadQdef(ctx, Uint32Array index)");
+    if (ni > 0xffffffffu) return throw_msg(env, "uploadQdef: too many indices");
+    int rc = ni ? rz_upload_qdef(ctx, (uint32_t)ni, (const uint32_t *)idx) : rz_upload_qdef(ctx, 0, NULL);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
 /* uploadIK(ctx, Uint32Array|null goal, Uint32Array effector, Uint32Array loops, Float32Array limitAngle, Uint32Array linkOff [chains + 1],
  * Uint32Array linkBone, Uint8Array linkLimited, Float32Array linkMin3, Float32Array linkMax3): the IK chains of the skeleton (rz_upload_ik);
  * an empty or null goal removes the table */
@@ -1049,7 +1063,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "readGathered", fn_read_gathered }, { "commInitAll", fn_comm_init_all }, { "allgatherAll", fn_allgather_all },
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
-        { "uploadSdef", fn_upload_sdef }, { "uploadIK", fn_upload_ik },
+        { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

@@ -220,6 +220,9 @@ int rz_set_tuning(rz_ctx *c, const char *key, int value)
         if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(RZ_ERR_INVALID, "inst_block must be 0 (auto), 256, 512 or 1024 threads per workgroup");
         c->t_instblock = value;
         c->tuned_by_search = false;
+    } else if (!strcmp(key, "qdef_chunks")) {
+        if (value < 0 || value > 64) return fail(RZ_ERR_INVALID, "qdef_chunks must be 0 (auto) or 1..64 chunks of 256 QDEF vertices per workgroup");
+        c->t_qdefchunks = value;
     } else if (!strcmp(key, "fast")) {
         c->t_fast = value;        // -1 auto, 0 never (always prep kernel), 1 when possible
     } else {
@@ -256,6 +259,8 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "instances")) *value = (int)c->I;
     else if (!strcmp(key, "verts")) *value = (int)c->V;
     else if (!strcmp(key, "sdef_verts")) *value = (int)c->sdef_n;
+    else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef_n;
+    else if (!strcmp(key, "qdef_chunks")) *value = c->t_qdefchunks;
     else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
     else if (!strcmp(key, "nt_store")) *value = c->t_nts;
     else if (!strcmp(key, "fast")) *value = c->t_fast;

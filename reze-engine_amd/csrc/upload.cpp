@@ -48,6 +48,7 @@ int alloc_mesh(rz_ctx *c, uint32_t V)
     dfree(c->rj01); dfree(c->rj23); c->sub_valid = false;      // the run lists name this mesh's joints
     free_morphs(c);                       // morph targets are per-vertex: a new mesh invalidates them
     free_sdef(c);                         // ... and so does the SDEF table: its indices name the old mesh's vertices
+    free_qdef(c);                         // ... and the QDEF table
     c->V = V;
     c->Vp = round_up(V, kVertPad);
     const size_t Vp = c->Vp;
@@ -480,6 +481,17 @@ int rz_upload_edge_scale(rz_ctx *c, uint32_t V, const float *edge_size)
     return ensure_outputs(c);
 }
 
+// the first vertex two strictly ascending lists share, or -1 (a PMX vertex has one weight type: the SDEF and QDEF tables are disjoint)
+static int64_t first_shared(const uint32_t *a, size_t na, const std::vector<uint32_t> &b)
+{
+    size_t i = 0, k = 0;
+    while (i < na && k < b.size()) {
+        if (a[i] == b[k]) return (int64_t)a[i];
+        if (a[i] < b[k]) ++i; else ++k;
+    }
+    return -1;
+}
+
 int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float *c3, const float *r0_3, const float *r1_3)
 {
     if (int r = use(c)) return r;
@@ -492,6 +504,8 @@ int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float 
             if (k > 0 && vert_idx[k] <= vert_idx[k - 1])
                 return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex indices must be strictly ascending (entry %u: %u after %u)", k, vert_idx[k], vert_idx[k - 1]);
         }
+        const int64_t both = first_shared(vert_idx, n, c->qdef_idx_host);
+        if (both >= 0) return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex %lld is in the QDEF table already (a vertex has one weight type)", (long long)both);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
@@ -506,6 +520,32 @@ int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float 
             for (uint32_t k = 0; k < n; ++k) memcpy(&tab[(size_t)(1 + 3 * a + d) * n + k], &src[a][(size_t)k * 3 + d], 4);
     if (int r = to_device(&c->sdef_tab, tab.data(), tab.size())) return r;
     c->sdef_n = n;
+    c->sdef_idx_host.assign(vert_idx, vert_idx + n);
+    return RZ_OK;
+}
+
+int rz_upload_qdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_qdef")) return r;
+    if (n > 0) {
+        if (!vert_idx) return fail(RZ_ERR_INVALID, "rz_upload_qdef: null array for %u entries", n);
+        if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its QDEF table");
+        for (uint32_t k = 0; k < n; ++k) {
+            if (vert_idx[k] >= c->V) return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex index %u (entry %u) is outside the shard's %u vertices", vert_idx[k], k, c->V);
+            if (k > 0 && vert_idx[k] <= vert_idx[k - 1])
+                return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex indices must be strictly ascending (entry %u: %u after %u)", k, vert_idx[k], vert_idx[k - 1]);
+        }
+        const int64_t both = first_shared(vert_idx, n, c->sdef_idx_host);
+        if (both >= 0) return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex %lld is in the SDEF table already (a vertex has one weight type)", (long long)both);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_graph(c);
+    free_qdef(c);
+    if (n == 0) return RZ_OK;
+    if (int r = to_device(&c->qdef_tab, vert_idx, (size_t)n)) return r;
+    c->qdef_n = n;
+    c->qdef_idx_host.assign(vert_idx, vert_idx + n);
     return RZ_OK;
 }
 

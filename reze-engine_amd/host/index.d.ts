@@ -34,6 +34,7 @@ export interface EngineOptions {
   /** Also write the outline pass's inverted hull every frame. */ outline?: boolean
   /** Also reduce the deformed mesh's bounding box every frame. */ bounds?: boolean
   /** Skin SDEF vertices (PMX weight type 3) as MMD does (default false: they are skinned as BDEF2, like the reference). */ sdef?: boolean
+  /** Blend QDEF vertices (PMX 2.1 weight type 4) as dual quaternions (default false: they are skinned as BDEF4, like the reference). */ qdef?: boolean
   /** Solve PMX inverse kinematics (default false: the IK goal bones move, the legs do not follow, like the reference). With deviceFK the chains are uploaded once (rz_upload_ik) and solved on the GPU, else Model.solveIK() runs on the host. A bone with an IK block carries `ik: { effector, loops, limitAngle, links: [{ bone, min?, max? }] }` (Model.getIKChains() lists them). */ ik?: boolean
   /** One context per listed GPU; the mesh is vertex-sharded across them. */ devices?: number[]
   /** With deviceFK: seekFrame() samples the motion on the GPU (rz_upload_animation once, one float per frame). */ deviceSampling?: boolean

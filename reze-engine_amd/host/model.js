@@ -52,6 +52,8 @@ class Model {
     this.skinning = skinning
     // SDEF vertices (PMX weight type 3): set by the PMX loader; skinned as BDEF2 unless the engine is asked for SDEF ({ sdef: true })
     this.sdef = { index: new Uint32Array(0), c: new Float32Array(0), r0: new Float32Array(0), r1: new Float32Array(0) }
+    // QDEF vertices (PMX 2.1 weight type 4), ascending: set by the PMX loader; skinned as BDEF4 unless the engine is asked for QDEF ({ qdef: true })
+    this.qdef = new Uint32Array(0)
     this.rigidbodies = rigidbodies || []
     this.joints = joints || []
     this.clock = defaultClock
@@ -135,6 +137,7 @@ class Model {
   getSkeleton() { return this.skeleton }
   getSkinning() { return this.skinning }
   getSdef() { return this.sdef }
+  getQdef() { return this.qdef }
   getRigidbodies() { return this.rigidbodies }
   getJoints() { return this.joints }
   getBoneNames() { return this.skeleton.bones.map((b) => b.name) }

@@ -121,6 +121,7 @@ class PmxLoader {
     const sdefC = []
     const sdefR0 = []
     const sdefR1 = []
+    const qdefIdx = []
     for (let v = 0; v < count; v++) {
       pos[v * 3] = c.f32(); pos[v * 3 + 1] = c.f32(); pos[v * 3 + 2] = c.f32()
       nrm[v * 3] = c.f32(); nrm[v * 3 + 1] = c.f32(); nrm[v * 3 + 2] = c.f32()
@@ -139,7 +140,8 @@ class PmxLoader {
           sdefIdx.push(v)
           sdefC.push(c.f32(), c.f32(), c.f32()); sdefR0.push(c.f32(), c.f32(), c.f32()); sdefR1.push(c.f32(), c.f32(), c.f32())
         }
-      } else if (kind === 2 || kind === 4) { // BDEF4, QDEF treated as BDEF4
+      } else if (kind === 2 || kind === 4) { // BDEF4; QDEF (PMX 2.1) is encoded as BDEF4 and listed in Geometry.qdef: the engine blends it as dual quaternions only when asked ({ qdef: true })
+        if (kind === 4) qdefIdx.push(v)
         for (let k = 0; k < 4; k++) joints[o + k] = bone()
         const q = [0, 0, 0, 0]
         let sum = 0
@@ -156,7 +158,7 @@ class PmxLoader {
       c.skip(4) // edge scale
     }
     const sdef = { index: Uint32Array.from(sdefIdx), c: Float32Array.from(sdefC), r0: Float32Array.from(sdefR0), r1: Float32Array.from(sdefR1) }
-    return { count, pos, nrm, uv, joints, weights, sdef }
+    return { count, pos, nrm, uv, joints, weights, sdef, qdef: Uint32Array.from(qdefIdx) }
   }
 
   indices() {
@@ -440,6 +442,7 @@ class PmxLoader {
     const skinning = { joints: geo.joints, weights: geo.weights }
     const model = new Model(vertexData, indices, textures, materials, skeleton, skinning, rigidbodies, joints, morphs)
     model.sdef = geo.sdef
+    model.qdef = geo.qdef
     return model
   }
 }

@@ -44,6 +44,7 @@ class Engine {
   outline: boolean
   bounds: boolean
   sdef: boolean
+  qdef: boolean
   ik: boolean
   gather: boolean | 'direct'
   morphLayout: 'sparse' | 'dense'
@@ -102,6 +103,8 @@ class Engine {
     this.bounds = o.bounds === true // also reduce the deformed mesh's bounding box every frame
     // SDEF vertices (PMX weight type 3) skinned as MMD does; off (the default), they are skinned as BDEF2 like the reference does
     this.sdef = o.sdef === true
+    // QDEF vertices (PMX 2.1 weight type 4) blended as dual quaternions; off (the default), they are skinned as BDEF4 like the reference does
+    this.qdef = o.qdef === true
     this.ik = o.ik === true // PMX inverse kinematics: off unless asked for (device solve with deviceFK, else Model.solveIK on the host)
     // gather: true = RCCL all-gather of the deformed mesh after every frame (needs distinct GPUs);
     // 'direct' = every shard's kernel stores straight into GPU devices[0]'s buffer over xGMI (no collective)
@@ -323,6 +326,16 @@ class Engine {
         const idx = new Uint32Array(k1 - k0)
         for (let k = k0; k < k1; k++) idx[k - k0] = t.index[k] - b
         n.uploadSdef(s.ctx, idx, t.c.slice(k0 * 3, k1 * 3), t.r0.slice(k0 * 3, k1 * 3), t.r1.slice(k0 * 3, k1 * 3))
+      }
+      if (this.qdef) { // this shard's QDEF vertices, re-based to the shard (the list is ascending)
+        const q = model.getQdef()
+        let k0 = 0
+        while (k0 < q.length && q[k0] < b) k0++
+        let k1 = k0
+        while (k1 < q.length && q[k1] < e) k1++
+        const idx = new Uint32Array(k1 - k0)
+        for (let k = k0; k < k1; k++) idx[k - k0] = q[k] - b
+        n.uploadQdef(s.ctx, idx)
       }
     }
     if (this.outline) {

@@ -39,6 +39,7 @@ class Model {
   skeleton: Skeleton
   skinning: Skinning
   sdef: SdefTable
+  qdef: Uint32Array
   rigidbodies: unknown[]
   joints: unknown[]
   clock: () => number
@@ -91,6 +92,8 @@ class Model {
     this.skinning = skinning
     // SDEF vertices (PMX weight type 3): set by the PMX loader; skinned as BDEF2 unless the engine is asked for SDEF ({ sdef: true })
     this.sdef = { index: new Uint32Array(0), c: new Float32Array(0), r0: new Float32Array(0), r1: new Float32Array(0) }
+    // QDEF vertices (PMX 2.1 weight type 4), ascending: set by the PMX loader; skinned as BDEF4 unless the engine is asked for QDEF ({ qdef: true })
+    this.qdef = new Uint32Array(0)
     this.rigidbodies = rigidbodies || []
     this.joints = joints || []
     this.clock = defaultClock
@@ -174,6 +177,7 @@ class Model {
   getSkeleton(): Skeleton { return this.skeleton }
   getSkinning(): Skinning { return this.skinning }
   getSdef(): SdefTable { return this.sdef }
+  getQdef(): Uint32Array { return this.qdef }
   getRigidbodies(): unknown[] { return this.rigidbodies }
   getJoints(): unknown[] { return this.joints }
   getBoneNames(): string[] { return this.skeleton.bones.map((b) => b.name) }

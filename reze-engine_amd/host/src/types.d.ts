@@ -103,6 +103,7 @@ export interface DeformAddon {
   uploadEdgeScale(ctx: DeformContext, edge: Float32Array | null): void
   uploadIK(ctx: DeformContext, goal: Uint32Array | null, effector: Uint32Array | null, loops: Uint32Array | null, limitAngle: Float32Array | null, linkOff: Uint32Array | null, linkBone: Uint32Array | null, linkLimited: Uint8Array | null, linkMin3: Float32Array | null, linkMax3: Float32Array | null): void
   uploadSdef(ctx: DeformContext, index: Uint32Array | null, c3: Float32Array | null, r0_3: Float32Array | null, r1_3: Float32Array | null): void
+  uploadQdef(ctx: DeformContext, index: Uint32Array | null): void
   enableAabb(ctx: DeformContext, on: boolean): void
   setInstances(ctx: DeformContext, count: number): void
   setPose(ctx: DeformContext, world: Float32Array, morphWeights: Float32Array | null): void
@@ -138,7 +139,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; ik?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }

@@ -454,3 +454,29 @@ def leg_rig_pose(rig, seed, reach=(0.3, 0.9)):
         t[goal + 1] = rng.uniform(-0.3, 0.3, size=3).astype(np.float32)
         q[goal] = rq(0.3)
     return q, t
+
+
+def make_qdef(mesh, frac, seed=SEED + 8, cluster=0):
+    """QDEF list (PMX 2.1 weight type 4, dual-quaternion blending) of round(frac x V) of the mesh's V vertices, drawn from those with at
+    least two non-zero weights (fewer when the mesh has fewer of them) — two-, three- and four-influence vertices alike. cluster > 0
+    picks whole runs of `cluster` consecutive vertices instead of scattered ones (authors mark twisting forearms, shoulders, thighs).
+    The mesh is not changed: a QDEF vertex keeps its BDEF4 joints and weights, which is what a frame without the table skins.
+    Returns the ascending vertex indices [n] uint32."""
+    rng = np.random.default_rng(seed)
+    w = mesh["weights"]
+    V = len(w)
+    multi = np.flatnonzero((w > 0).sum(axis=1) >= 2)
+    want = int(round(frac * V))
+    if cluster > 0:
+        ok = np.zeros(V, dtype=bool)
+        ok[multi] = True
+        picked = np.zeros(V, dtype=bool)
+        for s in rng.permutation(max(V // cluster, 1)):
+            run = np.arange(s * cluster, min((s + 1) * cluster, V))
+            picked[run[ok[run]]] = True
+            if picked.sum() >= want:
+                break
+        idx = np.flatnonzero(picked)[:want]
+    else:
+        idx = np.sort(rng.choice(multi, size=min(want, len(multi)), replace=False))
+    return idx.astype(np.uint32)
