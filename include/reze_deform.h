@@ -264,6 +264,34 @@ typedef struct rz_animation {
 } rz_animation;
 int rz_upload_animation(rz_ctx *ctx, const rz_animation *anim);
 int rz_set_pose_sampled(rz_ctx *ctx, const float *frames);
+/* ---- a motion library on the device: per-instance clips and cross-fades — NEW (optional) ----
+ * rz_upload_animation holds ONE motion and rz_set_pose_sampled sends one frame number per instance, so a crowd dances one dance and a
+ * character can only hard-cut between motions. rz_upload_motions makes n_clips motions resident at once — each an rz_animation, checked
+ * exactly as rz_upload_animation checks it (offsets non-decreasing, key frames not descending, a bone driven by at most one track per
+ * clip, feed tracks in range; bones the model lacks are skipped), their keys concatenated on the device — and rz_set_pose_blended poses
+ * instance i from states[i] = (clip_a, frame_a, clip_b, frame_b, blend) (tests/motion_ref.py is the definition):
+ *     A = sample(clip_a, frame_a), B = sample(clip_b, frame_b)      what host/vmd-sampler.js defines, in f32 (rz_set_pose_sampled's sampler);
+ *                                                                   a bone / morph a clip does not key: identity, zero translation, weight 0
+ *     clip_b == RZ_NO_CLIP or blend == 0: exactly A (B is not evaluated, its fields are not read);  blend == 1: exactly B
+ *     otherwise per bone  q = Quat.slerp(qa, qb, blend)  (math.ts:156-189: qb negated when the dot product is negative, normalised lerp
+ *     above 0.9995, sine form otherwise),  t = ta + (tb - ta) * blend;  per vertex morph  w = wa + (wb - wa) * blend  on the effective
+ *     weights (own track, then group feeds). clip_a == clip_b is legal: two times of one motion.
+ * The result is a device-resident local pose with translations; from there the frame is an rz_set_pose_local frame: bone morphs ->
+ * hierarchy -> IK (with a table) -> overrides -> palette -> deform / skin -> the SDEF and QDEF passes. rz_motion_blend_kernel runs ONCE per
+ * call, in front of the frame, on the stream a copied pose of the same size would have travelled on, into the pose block that copy would
+ * have taken; rz_deform_n, graph replays and rz_time_span replay the resident pose. No host synchronisation; one character's state rides
+ * in the kernel arguments, a crowd's states go through a slot of the pinned ring.
+ * rz_upload_motions: independent of rz_upload_animation (both may be resident); n_clips = 0 removes the library; refused while forks exist
+ * (they borrow it); a new skeleton drops it; rz_get_tuning("motion_clips") = the count. rz_set_pose_blended needs the library and
+ * rz_upload_skeleton_topology; it refuses (RZ_ERR_INVALID, the resident pose untouched) a clip index >= n_clips (other than RZ_NO_CLIP in
+ * clip_b), a non-finite frame that would be sampled, a blend that is not in [0, 1], and a morph set of another size than the one the
+ * feeds were built for (upload the library again); a device error behind those checks leaves the context without a pose, as in
+ * rz_upload_pose. It cancels an outstanding rz_map_pose mapping. The ABI version stays 8: bindings
+ * detect the symbols. */
+#define RZ_NO_CLIP 0xffffffffu
+typedef struct rz_motion_state { uint32_t clip_a; float frame_a; uint32_t clip_b; float frame_b; float blend; } rz_motion_state;
+int rz_upload_motions(rz_ctx *ctx, uint32_t n_clips, const rz_animation *clips);
+int rz_set_pose_blended(rz_ctx *ctx, const rz_motion_state *states);
 /* ---- physics hand-off for device-solved poses ----
  * updateModelPose()  engine/src/engine.ts:2375-2381: between evaluatePose() and the world-matrix upload the reference
  * lets physics overwrite the world matrices of rigid-body-driven bones IN PLACE (physics.ts:715-751,
@@ -291,7 +319,7 @@ int rz_deform_n(rz_ctx *ctx, uint32_t frames);
  * buffer and the renderer reads frame f's output. A context has ONE compute stream and ONE set of output buffers, so its
  * frames run strictly one after the other and every frame pays its own launch ramp and tail — 1 us of a 16 us frame on a
  * 1/8 shard of C5, 2 us of a 6 us frame on a 30 k-vertex character. rz_fork makes a second context on the same GPU that
- * BORROWS every static device buffer of `ctx` (mesh, skeleton, topology, morph targets, bone morphs, motion, edge scale — no
+ * BORROWS every static device buffer of `ctx` (mesh, skeleton, topology, morph targets, bone morphs, motion, motion library, edge scale — no
  * copy, no extra HBM) and owns everything per-frame (streams, pose slots, palettes, outputs, tuning state copied from `ctx`
  * at fork time). Alternate frames between the two (rz_set_pose* + rz_deform on one while the other's frame is in flight, or
  * rz_deform_pair for a replay) and the tail of frame f overlaps the ramp of frame f + 1: measured 16.3 -> 15.2 us per frame

@@ -21,13 +21,15 @@ SYMBOLS = [
     "rz_autotune_apply", "rz_output_ptrs",
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
-    "rz_upload_qdef",
+    "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
-# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik and rz_upload_qdef — detected by the symbol, the version stayed 8)
+# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions and rz_set_pose_blended — detected by the symbol,
+# the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
-                    "rz_upload_ik", "rz_upload_qdef"}
+                    "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
+NO_CLIP = 0xffffffff
 
 
 class RzAnimation(ctypes.Structure):
@@ -38,6 +40,40 @@ class RzAnimation(ctypes.Structure):
                 ("mkey_off", ctypes.POINTER(ctypes.c_uint32)), ("mkey_frame", ctypes.POINTER(ctypes.c_float)),
                 ("mkey_weight", ctypes.POINTER(ctypes.c_float)), ("feed_off", ctypes.POINTER(ctypes.c_uint32)),
                 ("feed_track", ctypes.POINTER(ctypes.c_int32)), ("feed_ratio", ctypes.POINTER(ctypes.c_float))]
+
+
+class RzMotionState(ctypes.Structure):
+    _fields_ = [("clip_a", ctypes.c_uint32), ("frame_a", ctypes.c_float), ("clip_b", ctypes.c_uint32), ("frame_b", ctypes.c_float),
+                ("blend", ctypes.c_float)]
+
+
+# the same 20 bytes as a numpy record (set_pose_blended packs a crowd's states with it)
+MOTION_STATE_DTYPE = np.dtype([("clip_a", "<u4"), ("frame_a", "<f4"), ("clip_b", "<u4"), ("frame_b", "<f4"), ("blend", "<f4")])
+
+
+def _animation_struct(a, keep, track_bone, key_off, key_frame, key_rot, key_pos, key_interp=None,
+                      mkey_off=None, mkey_frame=None, mkey_weight=None, feed_off=None, feed_track=None, feed_ratio=None):
+    """Fill the rz_animation `a` from a flattened motion; the arrays it points at are appended to `keep`."""
+    def arr(x, dt, ct):
+        if x is None:
+            return None
+        v = np.ascontiguousarray(x, dtype=dt).reshape(-1)
+        keep.append(v)
+        return v.ctypes.data_as(ctypes.POINTER(ct))
+    a.n_bone_tracks = len(track_bone)
+    a.track_bone = arr(track_bone, np.int32, ctypes.c_int32)
+    a.key_off = arr(key_off, np.uint32, ctypes.c_uint32)
+    a.key_frame = arr(key_frame, np.float32, ctypes.c_float)
+    a.key_rot4 = arr(key_rot, np.float32, ctypes.c_float)
+    a.key_pos3 = arr(key_pos, np.float32, ctypes.c_float)
+    a.key_interp16 = arr(key_interp, np.uint8, ctypes.c_uint8)
+    a.n_morph_tracks = 0 if mkey_off is None else len(mkey_off) - 1
+    a.mkey_off = arr(mkey_off, np.uint32, ctypes.c_uint32)
+    a.mkey_frame = arr(mkey_frame, np.float32, ctypes.c_float)
+    a.mkey_weight = arr(mkey_weight, np.float32, ctypes.c_float)
+    a.feed_off = arr(feed_off, np.uint32, ctypes.c_uint32)
+    a.feed_track = arr(feed_track, np.int32, ctypes.c_int32)
+    a.feed_ratio = arr(feed_ratio, np.float32, ctypes.c_float)
 
 
 class RzTiming(ctypes.Structure):
@@ -149,6 +185,9 @@ def load(path=None):
         L.rz_upload_sdef.argtypes = [vp, u32, ctypes.POINTER(u32), fp, fp, fp]
     if hasattr(L, "rz_upload_qdef"):           # (ABI 8 still: the feature is detected by the symbol)
         L.rz_upload_qdef.argtypes = [vp, u32, ctypes.POINTER(u32)]
+    if hasattr(L, "rz_upload_motions"):        # (ABI 8 still: the feature is detected by the symbols)
+        L.rz_upload_motions.argtypes = [vp, u32, ctypes.POINTER(RzAnimation)]
+        L.rz_set_pose_blended.argtypes = [vp, ctypes.POINTER(RzMotionState)]
     if hasattr(L, "rz_upload_ik"):             # (ABI 8 still: the feature is detected by the symbol)
         u8p = ctypes.POINTER(ctypes.c_uint8)
         L.rz_upload_ik.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32), fp, ctypes.POINTER(u32), ctypes.POINTER(u32), u8p, fp, fp]
@@ -418,29 +457,50 @@ class DeformContext:
                          mkey_off=None, mkey_frame=None, mkey_weight=None, feed_off=None, feed_track=None, feed_ratio=None):
         """Flattened motion (rz_animation): bone tracks + optional morph tracks with their per-vertex-morph feeds."""
         keep = []
-
-        def arr(x, dt, ct):
-            if x is None:
-                return None
-            a = np.ascontiguousarray(x, dtype=dt).reshape(-1)
-            keep.append(a)
-            return a.ctypes.data_as(ctypes.POINTER(ct))
         a = RzAnimation()
-        a.n_bone_tracks = len(track_bone)
-        a.track_bone = arr(track_bone, np.int32, ctypes.c_int32)
-        a.key_off = arr(key_off, np.uint32, ctypes.c_uint32)
-        a.key_frame = arr(key_frame, np.float32, ctypes.c_float)
-        a.key_rot4 = arr(key_rot, np.float32, ctypes.c_float)
-        a.key_pos3 = arr(key_pos, np.float32, ctypes.c_float)
-        a.key_interp16 = arr(key_interp, np.uint8, ctypes.c_uint8)
-        a.n_morph_tracks = 0 if mkey_off is None else len(mkey_off) - 1
-        a.mkey_off = arr(mkey_off, np.uint32, ctypes.c_uint32)
-        a.mkey_frame = arr(mkey_frame, np.float32, ctypes.c_float)
-        a.mkey_weight = arr(mkey_weight, np.float32, ctypes.c_float)
-        a.feed_off = arr(feed_off, np.uint32, ctypes.c_uint32)
-        a.feed_track = arr(feed_track, np.int32, ctypes.c_int32)
-        a.feed_ratio = arr(feed_ratio, np.float32, ctypes.c_float)
+        _animation_struct(a, keep, track_bone, key_off, key_frame, key_rot, key_pos, key_interp, mkey_off, mkey_frame, mkey_weight,
+                          feed_off, feed_track, feed_ratio)
         self._chk(self._L.rz_upload_animation(self._h, ctypes.byref(a)))
+
+    def upload_motions(self, clips):
+        """The motion library (rz_upload_motions): `clips` = a list of flattened motions, each a dict with the keyword names of
+        upload_animation (track_bone, key_off, key_frame, key_rot, key_pos and optionally key_interp, mkey_off, mkey_frame, mkey_weight,
+        feed_off, feed_track, feed_ratio; synth.make_motion builds such dicts). An empty list removes the library."""
+        if not hasattr(self._L, "rz_upload_motions"):
+            raise RzError(-6, "this build of the library has no rz_upload_motions")
+        clips = list(clips)
+        if not clips:
+            self._chk(self._L.rz_upload_motions(self._h, 0, None))
+            return
+        keep = []
+        arr = (RzAnimation * len(clips))()
+        for k, clip in enumerate(clips):
+            _animation_struct(arr[k], keep, **clip)
+        self._chk(self._L.rz_upload_motions(self._h, len(clips), arr))
+
+    @staticmethod
+    def pack_motion_states(n, clip_a, frame_a, clip_b=None, frame_b=None, blend=None):
+        """[n] records of MOTION_STATE_DTYPE (the 20-byte rz_motion_state); scalars are broadcast, clip_b None or negative = NO_CLIP."""
+        st = np.zeros(n, dtype=MOTION_STATE_DTYPE)
+        st["clip_a"] = np.asarray(clip_a, dtype=np.int64).astype(np.uint32)
+        st["frame_a"] = np.asarray(frame_a, dtype=np.float32)
+        if clip_b is None:
+            st["clip_b"] = NO_CLIP
+        else:
+            cb = np.broadcast_to(np.asarray(clip_b, dtype=np.int64), (n,))
+            st["clip_b"] = np.where(cb < 0, NO_CLIP, cb).astype(np.uint32)
+        st["frame_b"] = 0.0 if frame_b is None else np.asarray(frame_b, dtype=np.float32)
+        st["blend"] = 0.0 if blend is None else np.asarray(blend, dtype=np.float32)
+        return st
+
+    def set_pose_blended(self, clip_a, frame_a, clip_b=None, frame_b=None, blend=None):
+        """One state per instance (scalars are broadcast): instance i is posed from clip_a[i] at frame_a[i], cross-faded by blend[i] into
+        clip_b[i] at frame_b[i] (clip_b None / negative / NO_CLIP or blend 0: clip_a alone). Sampled and blended on the GPU
+        (rz_set_pose_blended); needs upload_motions and upload_skeleton_topology."""
+        if not hasattr(self._L, "rz_set_pose_blended"):
+            raise RzError(-6, "this build of the library has no rz_set_pose_blended")
+        st = self.pack_motion_states(self.I, clip_a, frame_a, clip_b, frame_b, blend)
+        self._chk(self._L.rz_set_pose_blended(self._h, st.ctypes.data_as(ctypes.POINTER(RzMotionState))))
 
     def set_pose_sampled(self, frames):
         """One (fractional, 30 fps) frame per instance; bones, morph weights and the hierarchy are evaluated on the GPU."""
@@ -565,7 +625,8 @@ class DeformContext:
         """A zero-argument callable that does ONE per-frame upload + rz_deform through the raw C ABI with every array
         converted and every pointer built up front — for timing per-frame loops without numpy conversions in them
         (bench.py, tools/live_loop.py). kind: 'world' (rz_set_pose), 'local' (rz_set_pose_local), 'sampled'
-        (rz_set_pose_sampled; `primary` = a [T, I] table of frame numbers that is cycled through). Returns (call, check)."""
+        (rz_set_pose_sampled; `primary` = a [T, I] table of frame numbers that is cycled through), 'blended' (rz_set_pose_blended; a [T, I]
+        table of motion states). Returns (call, check)."""
         L, h = self._L, self._h
         keep = []
 
@@ -587,6 +648,17 @@ class DeformContext:
 
             def call():
                 if L.rz_set_pose_local(h, qp, tp, mp) or L.rz_deform(h):
+                    bad.append(1)
+        elif kind == "blended":
+            # `primary` = a [T, I] table of MOTION_STATE_DTYPE records (pack_motion_states) that is cycled through
+            rows = [np.ascontiguousarray(row, dtype=MOTION_STATE_DTYPE).reshape(-1) for row in np.atleast_2d(primary)]
+            keep.extend(rows)
+            table = [row.ctypes.data_as(ctypes.POINTER(RzMotionState)) for row in rows]
+            tick = [0]
+
+            def call():
+                tick[0] += 1
+                if L.rz_set_pose_blended(h, table[tick[0] % len(table)]) or L.rz_deform(h):
                     bad.append(1)
         else:
             table = [ptr(row) for row in np.atleast_2d(primary)]

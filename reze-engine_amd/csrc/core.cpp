@@ -188,6 +188,21 @@ void free_animation(rz_ctx *c)
     if (c->pose_sampled) { c->pose_sampled = false; c->pose_set = false; }
 }
 
+void free_motions(rz_ctx *c)
+{
+    if (c->mo_clips && !c->lender) {      // rz_motion_blend_kernel reads the library on whichever stream the pose travelled on
+        if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+    }
+    if (c->lender) {                      // a fork's library is its lender's
+        c->mo_bone_rec = nullptr; c->mo_feed_off = nullptr; c->mo_feed_range = c->mo_key_interp = nullptr;
+        c->mo_key_frame = c->mo_key_pos = c->mo_mkey_frame = c->mo_mkey_weight = c->mo_feed_ratio = nullptr; c->mo_key_rot = nullptr;
+    }
+    dfree(c->mo_bone_rec); dfree(c->mo_feed_off); dfree(c->mo_feed_range); dfree(c->mo_key_interp);
+    dfree(c->mo_key_frame); dfree(c->mo_key_pos); dfree(c->mo_mkey_frame); dfree(c->mo_mkey_weight); dfree(c->mo_feed_ratio); dfree(c->mo_key_rot);
+    c->mo_clips = 0; c->mo_M = 0;
+}
+
 void free_bone_morphs(rz_ctx *c)
 {
     if (!c->bm_off) return;
@@ -340,6 +355,7 @@ int rz_destroy(rz_ctx *c)
         c->sdef_tab = nullptr; c->sdef_n = 0;
         c->qdef_tab = nullptr; c->qdef_n = 0;
         c->ik_chain = nullptr; c->ik_path = c->ik_stage_off = nullptr; c->ik_link = nullptr; c->ik_n = c->ik_stages = 0;
+        free_motions(c);
         c->lender->n_forks--;
         c->lender = nullptr;
     }
@@ -352,6 +368,7 @@ int rz_destroy(rz_ctx *c)
     dfree(c->subfk_rec); dfree(c->subfk_count);
     dfree(c->fk_rec); dfree(c->fk_anc_more);
     free_animation(c); dfree(c->an_frames);
+    free_motions(c); dfree(c->mo_states);
     dfree(c->pose_blk[0]); dfree(c->pose_blk[1]);
     free_big_ring(c);
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
@@ -420,6 +437,9 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
     c->qdef_tab = parent->qdef_tab; c->qdef_n = parent->qdef_n; c->t_qdefchunks = parent->t_qdefchunks;
     c->ik_chain = parent->ik_chain; c->ik_path = parent->ik_path; c->ik_stage_off = parent->ik_stage_off; c->ik_link = parent->ik_link;
     c->ik_n = parent->ik_n; c->ik_stages = parent->ik_stages;
+    c->mo_clips = parent->mo_clips; c->mo_M = parent->mo_M; c->mo_bone_rec = parent->mo_bone_rec; c->mo_feed_off = parent->mo_feed_off;
+    c->mo_feed_range = parent->mo_feed_range; c->mo_key_interp = parent->mo_key_interp; c->mo_key_frame = parent->mo_key_frame; c->mo_key_pos = parent->mo_key_pos;
+    c->mo_mkey_frame = parent->mo_mkey_frame; c->mo_mkey_weight = parent->mo_mkey_weight; c->mo_feed_ratio = parent->mo_feed_ratio; c->mo_key_rot = parent->mo_key_rot;
     c->edge = parent->edge; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on;
     c->I = parent->I;
     c->t_split = parent->t_split; c->t_unroll = parent->t_unroll; c->t_grid_cap = parent->t_grid_cap; c->t_nt = parent->t_nt; c->t_nts = parent->t_nts;

@@ -117,6 +117,17 @@ struct rz_ctx {
     bool frames_inline = false;         // one character: the frame rides in the kernel arguments (frame0), nothing is uploaded
     float frame0 = 0.0f;
     size_t an_frames_alloc = 0;          // the current local pose carries translations (behind the rotations in its slot)
+    // the motion library (rz_upload_motions / rz_set_pose_blended; kernels/motion.hip): the keys of all clips concatenated, per clip one
+    // 16-byte track record per bone and M + 1 feed offsets. Independent of the single motion above; borrowed by forks.
+    uint32_t mo_clips = 0, mo_M = 0;    // clips resident (0 = no library) / vertex-morph count the feeds were built for
+    uint4 *mo_bone_rec = nullptr;       // [mo_clips][B]
+    uint32_t *mo_feed_off = nullptr;    // [mo_clips][mo_M + 1]
+    uint4 *mo_feed_range = nullptr, *mo_key_interp = nullptr;
+    float *mo_key_frame = nullptr, *mo_key_pos = nullptr, *mo_mkey_frame = nullptr, *mo_mkey_weight = nullptr, *mo_feed_ratio = nullptr;
+    float4 *mo_key_rot = nullptr;
+    RzMotionState *mo_states = nullptr; // [I] per-frame states of a crowd (this context's own, never borrowed)
+    size_t mo_states_alloc = 0;
+    hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states
     float4 *local_q = nullptr;          // I x B   (current pose slot)
 
     bool pose_local = false;            // the current pose came from rz_set_pose_local
@@ -346,6 +357,7 @@ void point_pose_at(rz_ctx *c, float *block);     // the current pose lives in `b
 void free_big_ring(rz_ctx *c);
 int ensure_pose_buffers(rz_ctx *c);
 void free_animation(rz_ctx *c);
+void free_motions(rz_ctx *c);
 int rebuild_fk_static(rz_ctx *c);      // upload.cpp: the device block behind fk_rec from the host copies
 void free_bone_morphs(rz_ctx *c);
 void forget_search(rz_ctx *c);

@@ -245,6 +245,29 @@ struct RzQdefParams {
 size_t rz_qdef_lds_bytes(int B);       // dynamic LDS of the pass: the skeleton's dual quaternions, 32 B per bone
 hipError_t rz_launch_qdef(const RzQdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st);
 
+// rz_motion_blend_kernel (kernels/motion.hip): the local pose of every instance from a library of resident motions, in front of the frame
+// (rz_upload_motions / rz_set_pose_blended). A kernel of its own: the frame kernels and rz_fk_kernel see a resident local pose.
+struct RzMotionState {          // = rz_motion_state of the C ABI (pose.cpp asserts the layout)
+    uint32_t clip_a; float frame_a;
+    uint32_t clip_b; float frame_b;     // clip_b = kRzNoClip: there is no second clip
+    float blend;                        // 0 = all of clip_a ... 1 = all of clip_b
+};
+constexpr uint32_t kRzNoClip = 0xffffffffu;
+struct RzMotionParams {
+    const RzMotionState *states;    // [I] on the device, or null: one character, the state rides in the kernel arguments (state0)
+    RzMotionState state0;
+    const uint4 *bone_rec;          // [n_clips][B] track of each bone in each clip: word 2 of the hierarchy's bone record (first key, end, bits(first
+                                    //              frame), bits(last frame)), key indices absolute in the concatenated key arrays
+    const uint32_t *feed_off;       // [n_clips][M + 1] per clip and vertex morph: its feeds in the concatenated feed arrays
+    RzSampleParams sample;          // the concatenated keys / morph keys / feeds of all clips (frames, feed_off, morph_w, M unused)
+    float4 *local_q;                // [I][B] out: the local-pose part of a pose block ...
+    float *local_t;                 // [I][B][3]
+    float *morph_w;                 // [I][M]
+    int B;
+    int M;
+};
+hipError_t rz_launch_motion_blend(const RzMotionParams &p, uint32_t instances, hipStream_t st);
+
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).
 struct RzVariant {
     int mode;    // 0 none, 1 dense, 2 sparse

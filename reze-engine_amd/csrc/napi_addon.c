@@ -534,44 +534,100 @@ static int get_prop_ta(napi_env env, napi_value obj, const char *name, napi_type
     return get_ta(env, v, want, optional, data, len);
 }
 
-static napi_value fn_upload_animation(napi_env env, napi_callback_info info)
+/* One flattened motion (host/vmd-sampler.js: VMDSampler.flatten) as an rz_animation over the object's typed arrays; M = the context's morph
+ * count. Returns NULL, or what is wrong with it (`who` names the caller in the message). */
+static const char *flat_to_animation(napi_env env, napi_value o, int M, const char *who, rz_animation *an)
 {
-    ARGS(2);
-    CTX(0);
+    static char msg[256];
     napi_valuetype vt;
-    if (napi_typeof(env, argv[1], &vt) != napi_ok || vt != napi_object)
-        return throw_msg(env, "uploadAnimation(ctx, { trackBone, keyOff, keyFrame, keyRot, keyPos, keyInterp?, mkeyOff?, mkeyFrame?, mkeyWeight?, feedOff?, feedTrack?, feedRatio? })");
+    if (napi_typeof(env, o, &vt) != napi_ok || vt != napi_object) {
+        snprintf(msg, sizeof msg, "%s(ctx, { trackBone, keyOff, keyFrame, keyRot, keyPos, keyInterp?, mkeyOff?, mkeyFrame?, mkeyWeight?, feedOff?, feedTrack?, feedRatio? })", who);
+        return msg;
+    }
     void *tb, *ko, *kf, *kr, *kp, *ki, *mo, *mf, *mw, *fo, *ft, *fr;
     size_t ntb, nko, nkf, nkr, nkp, nki, nmo, nmf, nmw, nfo, nft, nfr;
-    napi_value o = argv[1];
+    const char *bad = NULL;
     if (!get_prop_ta(env, o, "trackBone", napi_int32_array, 0, &tb, &ntb) || !get_prop_ta(env, o, "keyOff", napi_uint32_array, 0, &ko, &nko) ||
         !get_prop_ta(env, o, "keyFrame", napi_float32_array, 0, &kf, &nkf) || !get_prop_ta(env, o, "keyRot", napi_float32_array, 0, &kr, &nkr) ||
         !get_prop_ta(env, o, "keyPos", napi_float32_array, 0, &kp, &nkp) || !get_prop_ta(env, o, "keyInterp", napi_uint8_array, 1, &ki, &nki) ||
         !get_prop_ta(env, o, "mkeyOff", napi_uint32_array, 1, &mo, &nmo) || !get_prop_ta(env, o, "mkeyFrame", napi_float32_array, 1, &mf, &nmf) ||
         !get_prop_ta(env, o, "mkeyWeight", napi_float32_array, 1, &mw, &nmw) || !get_prop_ta(env, o, "feedOff", napi_uint32_array, 1, &fo, &nfo) ||
         !get_prop_ta(env, o, "feedTrack", napi_int32_array, 1, &ft, &nft) || !get_prop_ta(env, o, "feedRatio", napi_float32_array, 1, &fr, &nfr))
-        return throw_msg(env, "uploadAnimation: a field has the wrong typed-array type");
+        bad = "a field has the wrong typed-array type";
+    const size_t n = bad ? 0 : ntb;
+    if (!bad && nko != n + 1) bad = "keyOff must hold trackBone.length + 1 offsets";
+    const size_t K = (!bad && n) ? ((const uint32_t *)ko)[n] : 0;
+    if (!bad && (nkf < K || nkr < K * 4 || nkp < K * 3 || (ki && nki < K * 16))) bad = "key arrays are shorter than keyOff says";
+    const size_t mt = (!bad && mo) ? (nmo ? nmo - 1 : 0) : 0;
+    const size_t Km = mt ? ((const uint32_t *)mo)[mt] : 0;
+    if (!bad && mt && (!mf || !mw || nmf < Km || nmw < Km)) bad = "morph key arrays are shorter than mkeyOff says";
+    if (!bad && mt && M > 0) {
+        if (!fo || nfo != (size_t)M + 1) bad = "feedOff must hold morphs + 1 offsets";
+        else {
+            const size_t F = ((const uint32_t *)fo)[M];
+            if (F && (!ft || !fr || nft < F || nfr < F)) bad = "feed arrays are shorter than feedOff says";
+        }
+    }
+    if (bad) { snprintf(msg, sizeof msg, "%s: %s", who, bad); return msg; }
+    memset(an, 0, sizeof *an);
+    an->n_bone_tracks = (uint32_t)n; an->track_bone = (const int32_t *)tb; an->key_off = (const uint32_t *)ko; an->key_frame = (const float *)kf;
+    an->key_rot4 = (const float *)kr; an->key_pos3 = (const float *)kp; an->key_interp16 = (const uint8_t *)ki;
+    an->n_morph_tracks = (uint32_t)mt; an->mkey_off = (const uint32_t *)mo; an->mkey_frame = (const float *)mf; an->mkey_weight = (const float *)mw;
+    an->feed_off = (const uint32_t *)fo; an->feed_track = (const int32_t *)ft; an->feed_ratio = (const float *)fr;
+    return NULL;
+}
+
+static napi_value fn_upload_animation(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
     int M = 0;
     if (rz_get_tuning(ctx, "morphs", &M)) return throw_rz(env, RZ_ERR_INVALID);
-    const size_t n = ntb;
-    if (nko != n + 1) return throw_msg(env, "uploadAnimation: keyOff must hold trackBone.length + 1 offsets");
-    const size_t K = n ? ((const uint32_t *)ko)[n] : 0;
-    if (nkf < K || nkr < K * 4 || nkp < K * 3 || (ki && nki < K * 16)) return throw_msg(env, "uploadAnimation: key arrays are shorter than keyOff says");
-    const size_t mt = mo ? (nmo ? nmo - 1 : 0) : 0;
-    const size_t Km = mt ? ((const uint32_t *)mo)[mt] : 0;
-    if (mt && (!mf || !mw || nmf < Km || nmw < Km)) return throw_msg(env, "uploadAnimation: morph key arrays are shorter than mkeyOff says");
-    if (mt && M > 0) {
-        if (!fo || nfo != (size_t)M + 1) return throw_msg(env, "uploadAnimation: feedOff must hold morphs + 1 offsets");
-        const size_t F = ((const uint32_t *)fo)[M];
-        if (F && (!ft || !fr || nft < F || nfr < F)) return throw_msg(env, "uploadAnimation: feed arrays are shorter than feedOff says");
-    }
     rz_animation an;
-    memset(&an, 0, sizeof an);
-    an.n_bone_tracks = (uint32_t)n; an.track_bone = (const int32_t *)tb; an.key_off = (const uint32_t *)ko; an.key_frame = (const float *)kf;
-    an.key_rot4 = (const float *)kr; an.key_pos3 = (const float *)kp; an.key_interp16 = (const uint8_t *)ki;
-    an.n_morph_tracks = (uint32_t)mt; an.mkey_off = (const uint32_t *)mo; an.mkey_frame = (const float *)mf; an.mkey_weight = (const float *)mw;
-    an.feed_off = (const uint32_t *)fo; an.feed_track = (const int32_t *)ft; an.feed_ratio = (const float *)fr;
+    const char *bad = flat_to_animation(env, argv[1], M, "uploadAnimation", &an);
+    if (bad) return throw_msg(env, bad);
     int rc = rz_upload_animation(ctx, &an);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* uploadMotions(ctx, flats[]): the motion library (rz_upload_motions), one VMDSampler.flatten() result per clip; an empty array removes it */
+static napi_value fn_upload_motions(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    bool is_arr = false;
+    uint32_t n = 0;
+    if (napi_is_array(env, argv[1], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, argv[1], &n) != napi_ok)
+        return throw_msg(env, "uploadMotions(ctx, [flat motion, ...])");
+    if (n == 0) { int rc0 = rz_upload_motions(ctx, 0, NULL); return rc0 ? throw_rz(env, rc0) : undef(env); }
+    int M = 0;
+    if (rz_get_tuning(ctx, "morphs", &M)) return throw_rz(env, RZ_ERR_INVALID);
+    rz_animation *clips = (rz_animation *)calloc(n, sizeof *clips);
+    if (!clips) return throw_msg(env, "uploadMotions: out of memory");
+    for (uint32_t k = 0; k < n; ++k) {
+        napi_value o;
+        const char *bad = napi_get_element(env, argv[1], k, &o) != napi_ok ? "uploadMotions: cannot read a clip" : flat_to_animation(env, o, M, "uploadMotions", &clips[k]);
+        if (bad) { free(clips); return throw_msg(env, bad); }
+    }
+    int rc = rz_upload_motions(ctx, n, clips);
+    free(clips);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* setPoseBlended(ctx, ArrayBuffer states): one 20-byte rz_motion_state per instance — clipA u32 | frameA f32 | clipB u32 (0xffffffff = none) |
+ * frameB f32 | blend f32, little-endian (host/engine.js packs them with a DataView) */
+static napi_value fn_set_pose_blended(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    bool is_ab = false;
+    void *data = NULL;
+    size_t len = 0;
+    int I = 0;
+    if (napi_is_arraybuffer(env, argv[1], &is_ab) != napi_ok || !is_ab || napi_get_arraybuffer_info(env, argv[1], &data, &len) != napi_ok)
+        return throw_msg(env, "setPoseBlended(ctx, ArrayBuffer states /* 20 bytes per instance */)");
+    if (rz_get_tuning(ctx, "instances", &I) || len != (size_t)I * sizeof(rz_motion_state)) return throw_msg(env, "setPoseBlended: states must hold 20 bytes per instance");
+    int rc = rz_set_pose_blended(ctx, (const rz_motion_state *)data);
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
@@ -1061,7 +1117,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "timeFrames", fn_time_frames }, { "setTuning", fn_set_tuning }, { "getTuning", fn_get_tuning },
         { "commUniqueId", fn_comm_unique_id }, { "rcclInfo", fn_rccl_info }, { "commInit", fn_comm_init }, { "allgather", fn_allgather },
         { "readGathered", fn_read_gathered }, { "commInitAll", fn_comm_init_all }, { "allgatherAll", fn_allgather_all },
-        { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
+        { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
         { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
     };

@@ -600,6 +600,110 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
     return RZ_OK;
 }
 
+// A pose blended on the device out of the motion library (kernels/motion.hip). It takes the pose block a COPIED local pose of the same size
+// would take — the other block of pose_blk, or a block of the big-pose ring above 256 KB — and rz_motion_blend_kernel writes it there on the
+// stream that copy would have travelled on, followed by the event that copy would have recorded (copy_send). The context is left exactly as
+// after such a copy: a resident local pose with translations. A state that is refused is refused before anything of the resident pose is
+// touched; a device error after that (a staging slot, a block of the ring) leaves the context without a pose, as it does in rz_upload_pose.
+static_assert(sizeof(rz_motion_state) == sizeof(RzMotionState) && sizeof(RzMotionState) == 20, "rz_motion_state is RzMotionState");
+static bool finite_f(float x) { return x == x && x - x == 0.0f; }
+
+static int check_motion_states(const rz_ctx *c, const RzMotionState *sv)
+{
+    for (uint32_t i = 0; i < c->I; ++i) {
+        const RzMotionState &s = sv[i];
+        if (!finite_f(s.blend) || s.blend < 0.0f || s.blend > 1.0f) return fail(RZ_ERR_INVALID, "instance %u: blend %g is not in [0, 1]", i, (double)s.blend);
+        const bool has_b = s.clip_b != kRzNoClip && s.blend != 0.0f, use_a = !(has_b && s.blend == 1.0f);
+        if (s.clip_a >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u: clip_a %u of %u", i, s.clip_a, c->mo_clips);
+        if (s.clip_b != kRzNoClip && s.clip_b >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u: clip_b %u of %u", i, s.clip_b, c->mo_clips);
+        if ((use_a && !finite_f(s.frame_a)) || (has_b && !finite_f(s.frame_b))) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
+    }
+    return RZ_OK;
+}
+
+int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
+{
+    if (int r = use(c)) return r;
+    if (!c->mo_clips) return fail(RZ_ERR_INVALID, "rz_upload_motions has not been called");
+    if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
+    if (c->mo_M != c->M) return fail(RZ_ERR_INVALID, "the library's morph feeds were built for %u vertex morphs, the context holds %u: upload it again", c->mo_M, c->M);
+    if (!states) return fail(RZ_ERR_INVALID, "null motion states");
+    // The states are read once, so that what is checked is what travels: one character's onto the stack (it may ride in the kernel
+    // arguments), a crowd's straight into the pinned slot it travels in. A refusal hands that slot back.
+    RzMotionState one;
+    const RzMotionState *sv = &one;
+    int slot = -1;
+    if (c->I == 1) memcpy(&one, states, sizeof one);
+    else {
+        if (int r = stage_acquire(c, std::max<size_t>((size_t)c->I * sizeof(RzMotionState), 4096), &slot)) return r;
+        memcpy(c->stage[slot], states, (size_t)c->I * sizeof(RzMotionState));
+        sv = static_cast<const RzMotionState *>(c->stage[slot]);
+    }
+    if (int r = check_motion_states(c, sv)) {
+        if (slot >= 0) c->stage_next = slot;
+        return r;
+    }
+    if (int r = ensure_pose_buffers(c)) return r;
+    c->map_layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
+    c->pose_local_t = true;
+    if (int r = pose_kind_changes(c, true)) return r;
+    const size_t nq = (size_t)c->I * c->B;
+    const PoseParts pp = pose_parts(c, nullptr, nq * sizeof(float4), nullptr, nq * 3 * sizeof(float), true, nullptr);
+    const bool piped = pose_piped(c, pp);
+    hipStream_t us = (piped || c->overlap_on) ? c->up_stream : c->stream;
+    const bool inline_state = c->I == 1 && !piped && !c->overlap_on && c->t_zerocopy != 0;      // (the rule of frames_inline)
+    if (!inline_state) {
+        if (c->I > c->mo_states_alloc) {
+            HIP_TRY(hipStreamSynchronize(c->up_stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            dfree(c->mo_states);
+            HIP_TRY(hipMalloc(&c->mo_states, (size_t)c->I * sizeof(RzMotionState)));
+            c->mo_states_alloc = c->I;
+        }
+        if (c->mo_states_stream && c->mo_states_stream != us) HIP_TRY(hipStreamSynchronize(c->mo_states_stream));     // (the protocol changed: rare)
+        c->mo_states_stream = us;
+        if (slot < 0) {
+            if (int r = stage_acquire(c, 4096, &slot)) return r;
+            memcpy(c->stage[slot], &one, sizeof one);
+        }
+    }
+    float *block = nullptr;
+    if (piped)
+        if (int r = big_acquire(c, &block)) return r;
+    c->zc_cur = -1;
+    c->zc_seq_cur = 0;
+    c->zc_epoch++;        // the kernel overwrites a pose block a helper may have staged and tagged: no later zero-copy pose may match that tag
+    c->world_resident = c->mw_resident = c->local_resident = true;
+    if (piped) point_pose_at(c, block);
+    else point_pose_slot(c, (c->pose_slot & 1) ^ 1);
+    RzMotionParams mp;
+    memset(&mp, 0, sizeof mp);
+    if (inline_state) mp.state0 = one;
+    else {
+        HIP_TRY(hipMemcpyAsync(c->mo_states, c->stage[slot], (size_t)c->I * sizeof(RzMotionState), hipMemcpyHostToDevice, us));
+        mp.states = c->mo_states;
+    }
+    mp.bone_rec = c->mo_bone_rec; mp.feed_off = c->mo_feed_off;
+    mp.sample.key_frame = c->mo_key_frame; mp.sample.key_rot = c->mo_key_rot; mp.sample.key_pos = c->mo_key_pos; mp.sample.key_interp = c->mo_key_interp;
+    mp.sample.mkey_frame = c->mo_mkey_frame; mp.sample.mkey_weight = c->mo_mkey_weight;
+    mp.sample.feed_range = c->mo_feed_range; mp.sample.feed_ratio = c->mo_feed_ratio;
+    mp.local_q = c->local_q; mp.local_t = reinterpret_cast<float *>(c->local_q + nq); mp.morph_w = c->morph_w;
+    mp.B = (int)c->B; mp.M = (int)c->M;
+    HIP_TRY(rz_launch_motion_blend(mp, c->I, us));
+    c->last_upload_pulled = false; c->last_upload_rows = false;
+    if (slot >= 0) {
+        // one event says both "the ring slot may be written again" and "the pose has landed" (copy_send)
+        HIP_TRY(hipEventRecord(c->stage_ev[slot], us));
+        c->stage_used[slot] = true;
+        if (piped) HIP_TRY(hipStreamWaitEvent(c->stream, c->stage_ev[slot], 0));
+    }
+    memset(&c->ml, 0, sizeof c->ml);
+    if (c->M > 0) c->ml.count = -1;          // the weights only exist on the device: the prep kernel compacts them
+    c->pose_I = c->I;
+    c->pose_set = true;
+    return RZ_OK;
+}
+
 int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16)
 {
     if (int r = use(c)) return r;

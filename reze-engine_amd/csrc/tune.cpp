@@ -262,6 +262,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef_n;
     else if (!strcmp(key, "qdef_chunks")) *value = c->t_qdefchunks;
     else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
+    else if (!strcmp(key, "motion_clips")) *value = (int)c->mo_clips;
     else if (!strcmp(key, "nt_store")) *value = c->t_nts;
     else if (!strcmp(key, "fast")) *value = c->t_fast;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;

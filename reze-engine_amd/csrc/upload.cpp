@@ -166,6 +166,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     free_bone_morphs(c);                // ... as do bone morphs (their entries name its bones)
     free_ik(c);                         // ... and the IK table (its chains name its bones)
     free_animation(c);                  // ... and so does an uploaded motion (its tracks name bones of that skeleton)
+    free_motions(c);                    // ... and the motion library
     return ensure_pose_buffers(c);
 }
 
@@ -384,18 +385,17 @@ int rz_upload_bone_morphs(rz_ctx *c, uint32_t n, const uint32_t *morph, const ui
     return RZ_OK;
 }
 
-int rz_upload_animation(rz_ctx *c, const rz_animation *a)
+// What rz_upload_animation and rz_upload_motions check of one flattened motion, and what they derive from it: bone_track[b] = the track
+// that drives bone b or -1, feed_off[M + 1] / *F = the feeds of the context's vertex morphs (all zero without morph tracks).
+static int check_animation(const rz_ctx *c, const rz_animation *a, std::vector<int> &bone_track, std::vector<uint32_t> &feed_off, uint32_t *F_out)
 {
-    if (int r = use(c)) return r;
-    if (int r = static_unlocked(c, "rz_upload_animation")) return r;
     if (!a) return fail(RZ_ERR_INVALID, "null animation");
     if (c->B == 0) return fail(RZ_ERR_INVALID, "upload the skeleton before a motion");
     const uint32_t n = a->n_bone_tracks, mt = a->n_morph_tracks;
     if (n && (!a->track_bone || !a->key_off || !a->key_frame || !a->key_rot4 || !a->key_pos3)) return fail(RZ_ERR_INVALID, "null bone-track arrays");
     if (mt && (!a->mkey_off || !a->mkey_frame || !a->mkey_weight)) return fail(RZ_ERR_INVALID, "null morph-track arrays");
     if (c->M && mt && (!a->feed_off || (a->feed_off[c->M] && (!a->feed_track || !a->feed_ratio)))) return fail(RZ_ERR_INVALID, "null morph feeds");
-    std::vector<int> bone_track(c->B, -1);
-    const uint32_t K = n ? a->key_off[n] : 0;
+    bone_track.assign(c->B, -1);
     for (uint32_t t = 0; t < n; ++t) {
         if (a->key_off[t] > a->key_off[t + 1]) return fail(RZ_ERR_INVALID, "key offsets must be non-decreasing");
         const int32_t b = a->track_bone[t];
@@ -407,13 +407,12 @@ int rz_upload_animation(rz_ctx *c, const rz_animation *a)
             if (!(a->key_frame[k] >= a->key_frame[k - 1])) return fail(RZ_ERR_INVALID, "track %u: key frames must not descend", t);
         bone_track[b] = (int)t;
     }
-    const uint32_t Km = mt ? a->mkey_off[mt] : 0;
     for (uint32_t t = 0; t < mt; ++t) {
         if (a->mkey_off[t] > a->mkey_off[t + 1]) return fail(RZ_ERR_INVALID, "morph key offsets must be non-decreasing");
         for (uint32_t k = a->mkey_off[t] + 1; k < a->mkey_off[t + 1]; ++k)
             if (!(a->mkey_frame[k] >= a->mkey_frame[k - 1])) return fail(RZ_ERR_INVALID, "morph track %u: key frames must not descend", t);
     }
-    std::vector<uint32_t> feed_off(c->M + 1, 0);
+    feed_off.assign(c->M + 1, 0);
     uint32_t F = 0;
     if (c->M && mt) {
         for (uint32_t m = 0; m <= c->M; ++m) feed_off[m] = a->feed_off[m];
@@ -423,20 +422,37 @@ int rz_upload_animation(rz_ctx *c, const rz_animation *a)
         for (uint32_t f = 0; f < F; ++f)
             if (a->feed_track[f] < 0 || (uint32_t)a->feed_track[f] >= mt) return fail(RZ_ERR_INVALID, "feed %u names morph track %d of %u", f, a->feed_track[f], mt);
     }
+    *F_out = F;
+    return RZ_OK;
+}
+
+// (first key, one past the last key, bits(first key's frame), bits(last key's frame)) of track t, key indices shifted by `base`
+static uint4 track_record(const uint32_t *off, const float *kf, int t, uint32_t base)
+{
+    uint4 r; r.x = r.y = r.z = r.w = 0;
+    if (t < 0 || off[t + 1] == off[t]) return r;
+    r.x = base + off[t]; r.y = base + off[t + 1];
+    memcpy(&r.z, &kf[off[t]], 4);
+    memcpy(&r.w, &kf[off[t + 1] - 1], 4);
+    return r;
+}
+
+int rz_upload_animation(rz_ctx *c, const rz_animation *a)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_animation")) return r;
+    std::vector<int> bone_track;
+    std::vector<uint32_t> feed_off;
+    uint32_t F = 0;
+    if (int r = check_animation(c, a, bone_track, feed_off, &F)) return r;
+    const uint32_t n = a->n_bone_tracks, mt = a->n_morph_tracks;
+    const uint32_t K = n ? a->key_off[n] : 0, Km = mt ? a->mkey_off[mt] : 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_animation(c);
     // per bone / per morph feed: the key range itself, so the sampler's chain of dependent loads starts one level lower
     std::vector<uint4> bone_range(c->B), feed_range(F);
-    auto record = [](const uint32_t *off, const float *kf, int t) {
-        uint4 r; r.x = r.y = r.z = r.w = 0;
-        if (t < 0 || off[t + 1] == off[t]) return r;
-        r.x = off[t]; r.y = off[t + 1];
-        memcpy(&r.z, &kf[off[t]], 4);
-        memcpy(&r.w, &kf[off[t + 1] - 1], 4);
-        return r;
-    };
-    for (uint32_t b = 0; b < c->B; ++b) bone_range[b] = record(a->key_off, a->key_frame, bone_track[b]);
-    for (uint32_t f = 0; f < F; ++f) feed_range[f] = record(a->mkey_off, a->mkey_frame, a->feed_track[f]);
+    for (uint32_t b = 0; b < c->B; ++b) bone_range[b] = track_record(a->key_off, a->key_frame, bone_track[b], 0);
+    for (uint32_t f = 0; f < F; ++f) feed_range[f] = track_record(a->mkey_off, a->mkey_frame, a->feed_track[f], 0);
     if (int r = to_device(&c->an_key_frame, a->key_frame, K)) return r;
     if (int r = to_device(&c->an_key_rot, a->key_rot4, K)) return r;
     if (int r = to_device(&c->an_key_pos, a->key_pos3, (size_t)K * 3)) return r;
@@ -463,6 +479,73 @@ int rz_upload_animation(rz_ctx *c, const rz_animation *a)
     c->an_M = c->M;
     c->has_animation = true;
     return rebuild_fk_static(c);
+}
+
+int rz_upload_motions(rz_ctx *c, uint32_t n_clips, const rz_animation *clips)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_motions")) return r;
+    if (n_clips == 0) {
+        free_motions(c);
+        return RZ_OK;
+    }
+    if (!clips) return fail(RZ_ERR_INVALID, "rz_upload_motions: null clips");
+    if (n_clips == 0xffffffffu) return fail(RZ_ERR_INVALID, "rz_upload_motions: too many clips");
+    const uint32_t B = c->B, M = c->M;
+    // every clip is checked before anything is replaced; the keys of all clips are concatenated, the records carry absolute indices
+    std::vector<uint4> bone_rec, feed_range, interp;
+    std::vector<uint32_t> feed_off_all;
+    std::vector<float> key_frame, key_rot, key_pos, mkey_frame, mkey_weight, feed_ratio;
+    bool any_interp = false;
+    for (uint32_t k = 0; k < n_clips; ++k) any_interp = any_interp || (clips[k].key_interp16 != nullptr && clips[k].n_bone_tracks != 0);
+    // a clip without interpolation bytes beside one that has them: the default curve 20 20 107 107, which bezier_y answers with x itself
+    uint4 linear;
+    { const uint8_t d[16] = { 20, 20, 20, 20, 20, 20, 20, 20, 107, 107, 107, 107, 107, 107, 107, 107 }; memcpy(&linear, d, 16); }
+    for (uint32_t k = 0; k < n_clips; ++k) {
+        const rz_animation *a = &clips[k];
+        std::vector<int> bone_track;
+        std::vector<uint32_t> feed_off;
+        uint32_t F = 0;
+        if (int r = check_animation(c, a, bone_track, feed_off, &F)) {
+            const std::string why = last_error();
+            return fail(r, "rz_upload_motions: clip %u: %s", k, why.c_str());
+        }
+        const uint32_t n = a->n_bone_tracks, mt = a->n_morph_tracks;
+        const uint32_t K = n ? a->key_off[n] : 0, Km = mt ? a->mkey_off[mt] : 0;
+        const size_t key_base = key_frame.size(), mkey_base = mkey_frame.size(), feed_base = feed_range.size();
+        if (key_base + K > 0xfffffff0ull || mkey_base + Km > 0xfffffff0ull || feed_base + F > 0xfffffff0ull)
+            return fail(RZ_ERR_INVALID, "rz_upload_motions: the library's keys do not fit 32-bit indices");
+        for (uint32_t b = 0; b < B; ++b) bone_rec.push_back(track_record(a->key_off, a->key_frame, bone_track[b], (uint32_t)key_base));
+        for (uint32_t m = 0; m <= M; ++m) feed_off_all.push_back((uint32_t)feed_base + feed_off[m]);
+        for (uint32_t f = 0; f < F; ++f) {
+            feed_range.push_back(track_record(a->mkey_off, a->mkey_frame, a->feed_track[f], (uint32_t)mkey_base));
+            feed_ratio.push_back(a->feed_ratio[f]);
+        }
+        key_frame.insert(key_frame.end(), a->key_frame, a->key_frame + K);
+        key_rot.insert(key_rot.end(), a->key_rot4, a->key_rot4 + (size_t)K * 4);
+        key_pos.insert(key_pos.end(), a->key_pos3, a->key_pos3 + (size_t)K * 3);
+        if (any_interp) {
+            interp.resize(key_base + K, linear);
+            if (a->key_interp16 && K) memcpy(&interp[key_base], a->key_interp16, (size_t)K * 16);
+        }
+        mkey_frame.insert(mkey_frame.end(), a->mkey_frame, a->mkey_frame + Km);
+        mkey_weight.insert(mkey_weight.end(), a->mkey_weight, a->mkey_weight + Km);
+    }
+    free_motions(c);                    // (drains both streams first: a blend kernel may still be reading the old library)
+    if (int r = to_device(&c->mo_bone_rec, bone_rec.data(), bone_rec.size())) return r;
+    if (int r = to_device(&c->mo_feed_off, feed_off_all.data(), feed_off_all.size())) return r;
+    if (int r = to_device(&c->mo_feed_range, feed_range.data(), feed_range.size())) return r;
+    if (int r = to_device(&c->mo_feed_ratio, feed_ratio.data(), feed_ratio.size())) return r;
+    if (int r = to_device(&c->mo_key_frame, key_frame.data(), key_frame.size())) return r;
+    if (int r = to_device(&c->mo_key_rot, key_rot.data(), key_rot.size() / 4)) return r;
+    if (int r = to_device(&c->mo_key_pos, key_pos.data(), key_pos.size())) return r;
+    if (any_interp)
+        if (int r = to_device(&c->mo_key_interp, interp.data(), interp.size())) return r;
+    if (int r = to_device(&c->mo_mkey_frame, mkey_frame.data(), mkey_frame.size())) return r;
+    if (int r = to_device(&c->mo_mkey_weight, mkey_weight.data(), mkey_weight.size())) return r;
+    c->mo_M = M;
+    c->mo_clips = n_clips;
+    return RZ_OK;
 }
 
 int rz_upload_edge_scale(rz_ctx *c, uint32_t V, const float *edge_size)

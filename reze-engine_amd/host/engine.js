@@ -65,6 +65,11 @@ class Engine {
     this.deviceSampling = o.deviceSampling === true && o.deviceFK === true
     this.instances = 1
     this.animationOnDevice = null
+    // the motion library (loadMotion / seekMotions): name -> sampler; a clip's index on the device is its position in this map
+    this.motions = new Map()
+    this.motionsVersion = 0
+    this.motionsOnDevice = -1
+    this.motionsFor = null
     // framesInFlight: 2 = consecutive frames alternate between the context and a fork of it (rz_fork: the fork borrows the
     // static buffers, owns its stream, pose slots and outputs), so the tail of frame f overlaps the launch ramp of frame
     // f + 1 — what a WebGPU queue does with consecutive command buffers (engine.ts:2124-2136 submits one per frame).
@@ -491,6 +496,71 @@ class Engine {
       if (s.count === 0) continue
       const c = this.frameContext(s)
       this.native.setPoseSampled(c, f)
+      this.native.deform(c)
+    }
+    if (this.autotune && !this.tuned) { // as in render(): the first frame supplied a pose
+      for (const s of this.shards) if (s.count > 0) this.native.autotune(s.ctx, 0)
+      this.tuned = true
+    }
+    if (this.gather === 'direct' && this.shards.length > 1) this.native.gatherFence(this.ctx)
+    else if (this.gather && this.shards.length > 1) this.native.allgatherAll(this.shards.map((s) => s.ctx), true)
+    this.updateStats(wallClock() - t0)
+  }
+
+  /** Add or replace the motion `name` of the motion library. loadAnimation / seekFrame keep their single motion. */
+  async loadMotion(name, path) {
+    this.motions.set(name, new VMDSampler(await VMDLoader.load(path))) // (a replaced name keeps its place in the map: its clip index)
+    this.motionsVersion++
+  }
+
+  /**
+   * Pose from the motion library and deform one frame: per state, motion `a` at frameA cross-faded by `blend` into motion `b` at frameB
+   * (no `b`, or blend 0: `a` alone). With { deviceFK, deviceSampling } the library is uploaded once per (library, model) and every call is
+   * one rz_set_pose_blended — a crowd takes one state per instance, a single state poses every instance. Otherwise one character is
+   * posed on the host (Model.applyBlendedFrame) and rendered.
+   */
+  seekMotions(state) {
+    if (!this.currentModel) return
+    const states = Array.isArray(state) ? state : new Array(this.deviceSampling ? this.instances : 1).fill(state)
+    for (const st of states) {
+      if (!this.motions.has(st.a)) throw new Error('seekMotions: unknown motion "' + st.a + '"')
+      if (st.b !== undefined && st.b !== null && !this.motions.has(st.b)) throw new Error('seekMotions: unknown motion "' + st.b + '"')
+    }
+    if (this.deviceSampling) return this.seekMotionsOnDevice(states)
+    if (states.length !== 1) throw new Error('seekMotions: ' + states.length + ' states, but the host path poses one character (a crowd needs { deviceFK, deviceSampling })')
+    const st = states[0]
+    const hasB = st.b !== undefined && st.b !== null
+    this.currentModel.applyBlendedFrame(this.motions.get(st.a), st.frameA, hasB ? this.motions.get(st.b) : null, st.frameB, st.blend)
+    this.render()
+  }
+
+  /** seekMotions with { deviceFK, deviceSampling }: upload the flattened library once, then 20 bytes per instance and frame. */
+  seekMotionsOnDevice(states) {
+    const model = this.currentModel
+    if (states.length !== this.instances) throw new Error('seekMotions: ' + states.length + ' states for ' + this.instances + ' instances')
+    const names = Array.from(this.motions.keys())
+    if (this.motionsOnDevice !== this.motionsVersion || this.motionsFor !== model) {
+      const morphs = model.getMorphCount() > 0 ? model.getMorphs() : null
+      const flats = names.map((n) => this.motions.get(n).flatten(model.runtimeSkeleton.nameIndex, morphs))
+      this.dropForks() // the library is static data
+      for (const s of this.shards) if (s.count > 0) this.native.uploadMotions(s.ctx, flats)
+      this.motionsOnDevice = this.motionsVersion
+      this.motionsFor = model
+    }
+    const t0 = wallClock()
+    const buf = new ArrayBuffer(states.length * 20), dv = new DataView(buf)
+    states.forEach((st, i) => {
+      const hasB = st.b !== undefined && st.b !== null
+      dv.setUint32(i * 20, names.indexOf(st.a), true)
+      dv.setFloat32(i * 20 + 4, st.frameA, true)
+      dv.setUint32(i * 20 + 8, hasB ? names.indexOf(st.b) : 0xffffffff, true)
+      dv.setFloat32(i * 20 + 12, hasB && st.frameB !== undefined ? st.frameB : 0, true)
+      dv.setFloat32(i * 20 + 16, hasB && st.blend !== undefined ? st.blend : 0, true)
+    })
+    for (const s of this.shards) {
+      if (s.count === 0) continue
+      const c = this.frameContext(s)
+      this.native.setPoseBlended(c, buf)
       this.native.deform(c)
     }
     if (this.autotune && !this.tuned) { // as in render(): the first frame supplied a pose

@@ -47,6 +47,7 @@ export interface EngineOptions {
   /** Physics hand-off (engine.ts:2379-2381), host-FK frames: step() may overwrite world matrices in place before they are uploaded. */
   physics?: { step(dt: number, boneWorldMatrices: Float32Array, boneInverseBindMatrices: Float32Array): void }
 }
+export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
 export interface EngineStats {
   fps: number; frameTime: number; gpuMemory: number
   deformMs: number; vertsPerSec: number; hbmGBps: number
@@ -67,6 +68,10 @@ export class Engine {
   step(timeMs: number): void
   /** MMD-interpolated pose at a (fractional, 30 fps) frame; with a crowd (setInstanceCount) one frame per instance. */
   seekFrame(frame: number | ArrayLike<number>): void
+  /** Add or replace a named motion of the motion library (loadAnimation / seekFrame are untouched). */
+  loadMotion(name: string, path: string): Promise<void>
+  /** Pose from the motion library: motion `a` at frameA, cross-faded by `blend` (0 .. 1) into motion `b` at frameB — slerp for rotations, lerp for translations and morph weights. With { deviceFK, deviceSampling } the library is uploaded once (rz_upload_motions) and every frame is one rz_set_pose_blended; a crowd takes one state per instance. Otherwise one character is posed on the host (Model.applyBlendedFrame). */
+  seekMotions(state: MotionState | MotionState[]): void
   /** n independently posed copies of the model (needs { deviceFK, deviceSampling }, one GPU). */
   setInstanceCount(n: number): void
   /** Physics hand-off with { deviceFK }: world matrices (column-major 4x4 each) that replace the GPU-solved ones of the listed bones until the next call. */

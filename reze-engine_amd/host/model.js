@@ -463,6 +463,47 @@ class Model {
     }
   }
 
+  /**
+   * The host twin of rz_set_pose_blended (include/reze_deform.h; tests/motion_ref.py is the definition): A = samplerA at frameA and
+   * B = samplerB at frameB, cross-faded by `blend` — rotations by Quat.slerp (kernels.slerpInto), translations and morph weights linearly.
+   * A clip that does not key a bone or morph the other one keys counts as rest there (identity, zero translation, weight 0); a bone or
+   * morph keyed by neither clip is left alone, as applySampledFrame leaves it. No samplerB or blend 0: exactly A (B is not sampled);
+   * blend 1: exactly B. Group morphs are blended as raw weights: getEffectiveMorphWeights() is linear in them.
+   */
+  applyBlendedFrame(samplerA, frameA, samplerB, frameB, blend) {
+    const t = samplerB && blend !== undefined && blend !== null ? blend : 0
+    if (!(t >= 0 && t <= 1)) throw new Error('applyBlendedFrame: blend must be in [0, 1], got ' + blend)
+    const rot = this.runtimeSkeleton.localRotations, tra = this.runtimeSkeleton.localTranslations
+    this.applyLocalTranslations = true
+    const fb = frameB === undefined || frameB === null ? 0 : frameB
+    const bones = new Set(samplerA.boneNames())
+    if (samplerB) for (const name of samplerB.boneNames()) bones.add(name)
+    const rest = { rotation: [0, 0, 0, 1], position: [0, 0, 0] }
+    const q = [0, 0, 0, 1]
+    for (const name of bones) {
+      const idx = this.runtimeSkeleton.nameIndex[name]
+      if (idx === undefined) continue
+      const a = t < 1 ? samplerA.sampleBone(name, frameA) || rest : rest
+      const b = t > 0 ? samplerB.sampleBone(name, fb) || rest : rest
+      let r = a.rotation, p = a.position
+      if (t === 1) { r = b.rotation; p = b.position }
+      else if (t > 0) {
+        r = slerpInto(q, a.rotation[0], a.rotation[1], a.rotation[2], a.rotation[3], b.rotation[0], b.rotation[1], b.rotation[2], b.rotation[3], t)
+        p = [a.position[0] + (b.position[0] - a.position[0]) * t, a.position[1] + (b.position[1] - a.position[1]) * t, a.position[2] + (b.position[2] - a.position[2]) * t]
+      }
+      rot[idx * 4] = r[0]; rot[idx * 4 + 1] = r[1]; rot[idx * 4 + 2] = r[2]; rot[idx * 4 + 3] = r[3]
+      tra[idx * 3] = p[0]; tra[idx * 3 + 1] = p[1]; tra[idx * 3 + 2] = p[2]
+      this.rotTweenState.active[idx] = 0
+    }
+    const morphs = new Set(samplerA.morphNames())
+    if (samplerB) for (const name of samplerB.morphNames()) morphs.add(name)
+    for (const name of morphs) {
+      const wa = t < 1 ? samplerA.sampleMorph(name, frameA) || 0 : 0
+      const wb = t > 0 ? samplerB.sampleMorph(name, fb) || 0 : 0
+      this.setMorphWeights([name], [t === 0 ? wa : t === 1 ? wb : wa + (wb - wa) * t])
+    }
+  }
+
   // ---- morphs (no reference counterpart; PMX layout per pmx-loader.ts:471-488) ----
   getMorphNames() { return this.morphs ? this.morphs.names.slice() : [] }
   getMorphCount() { return this.morphs ? this.morphs.names.length : 0 }

@@ -79,6 +79,9 @@ export interface FlatMotion {
   feedOff?: Uint32Array; feedTrack?: Int32Array; feedRatio?: Float32Array
 }
 
+/** Engine.seekMotions(): instance i is posed from motion `a` at frameA, cross-faded by `blend` (0 .. 1) into motion `b` at frameB */
+export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
+
 /** opaque rz_ctx handle of the addon */
 export type DeformContext = unknown
 export interface Timing { frameMs: number; deformKernelMs: number; prepKernelMs: number; vertsPerFrame: number; algorithmicBytesPerFrame: number; frames: number }
@@ -100,6 +103,7 @@ export interface DeformAddon {
   uploadMorphsSparse(ctx: DeformContext, offsets: Uint32Array, vertexIndex: Uint32Array, deltas: Float32Array): void
   uploadBoneMorphs(ctx: DeformContext, morph: Uint32Array | null, bone: Uint32Array | null, translation3: Float32Array | null, rotation4: Float32Array | null): void
   uploadAnimation(ctx: DeformContext, motion: FlatMotion): void
+  uploadMotions(ctx: DeformContext, motions: FlatMotion[]): void
   uploadEdgeScale(ctx: DeformContext, edge: Float32Array | null): void
   uploadIK(ctx: DeformContext, goal: Uint32Array | null, effector: Uint32Array | null, loops: Uint32Array | null, limitAngle: Float32Array | null, linkOff: Uint32Array | null, linkBone: Uint32Array | null, linkLimited: Uint8Array | null, linkMin3: Float32Array | null, linkMax3: Float32Array | null): void
   uploadSdef(ctx: DeformContext, index: Uint32Array | null, c3: Float32Array | null, r0_3: Float32Array | null, r1_3: Float32Array | null): void
@@ -109,6 +113,8 @@ export interface DeformAddon {
   setPose(ctx: DeformContext, world: Float32Array, morphWeights: Float32Array | null): void
   setPoseLocal(ctx: DeformContext, localRotations: Float32Array, morphWeights: Float32Array | null, localTranslations?: Float32Array | null): void
   setPoseSampled(ctx: DeformContext, frames: Float32Array): void
+  /** 20 bytes per instance: clipA u32 | frameA f32 | clipB u32 (0xffffffff = none) | frameB f32 | blend f32, little-endian */
+  setPoseBlended(ctx: DeformContext, states: ArrayBuffer): void
   mapPose(ctx: DeformContext, layout?: 0 | 1): { matrices: Float32Array; morphWeights: Float32Array | null }
   commitPose(ctx: DeformContext): void
   overrideWorld(ctx: DeformContext, bones: Uint32Array, world16: Float32Array, instances: Uint32Array | null): void

@@ -480,3 +480,80 @@ def make_qdef(mesh, frac, seed=SEED + 8, cluster=0):
     else:
         idx = np.sort(rng.choice(multi, size=min(want, len(multi)), replace=False))
     return idx.astype(np.uint32)
+
+
+def _quat_mul(a, b):
+    """Hamilton product a * b of [..., 4] quaternions (x y z w)."""
+    ax, ay, az, aw = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bx, by, bz, bw = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], axis=-1)
+
+
+def make_motion_base(n_bones, seed=SEED + 20):
+    """Per-bone base rotations [B, 4] (unit, any angle) for make_motion: clips built around the same base keep every key of a bone within
+    `max_angle` of one rotation."""
+    q = np.random.default_rng(seed).normal(size=(n_bones, 4))
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def make_motion(n_bones, n_morphs=0, seed=SEED + 21, keyed=0.8, n_keys=6, base=None, max_angle=np.pi / 4, flip=0.0, uneven=True,
+                interp=True, span=8, trans=0.1, group_feed=None, morph_keyed=0.75):
+    """One flattened motion (a clip dict with the keyword names of DeformContext.upload_animation / upload_motions and of
+    tests/helpers.sample_reference) for a skeleton of n_bones bones and a morph set of n_morphs vertex morphs.
+      keyed        fraction of the bones that get a track, or a boolean mask [B] (a bone without a track is at rest in this clip)
+      base         [B, 4] per-bone base rotations (make_motion_base; default identity); every key of a bone is base * (a rotation of at
+                   most max_angle about a random axis) — so any two samples of that bone, in any clip built on the same base, are at most
+                   2 * max_angle apart: |dot| >= cos(max_angle) of the quaternions
+      flip         fraction of the keys stored with the opposite sign (the same rotation; a slerp must negate them back)
+      uneven       key frames are unevenly spaced (steps of 1 .. span frames) with ONE duplicate frame per track, so a span guessed by
+                   linear interpolation misses; False: one key every `span` frames
+      interp       random interpolation bytes 1 .. 126 (the four Bezier curves of every key); False: none (linear)
+      trans        key positions are uniform in [-trans, trans]
+      group_feed   (morph m, ratio): morph m is fed by one more track — a group morph's — behind its own
+      morph_keyed  fraction of the vertex morphs whose own track holds keys (the others have a track without keys, or — every fourth of
+                   them — no feed at all)."""
+    rng = np.random.default_rng(seed)
+    mask = np.asarray(keyed, dtype=bool) if np.ndim(keyed) else rng.random(n_bones) < keyed
+    tb = np.flatnonzero(mask).astype(np.int32)
+    n = len(tb)
+    bq = np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (n_bones, 1)) if base is None else np.asarray(base, dtype=np.float64)
+
+    def frames(k):
+        if not uneven:
+            return np.arange(k, dtype=np.float64) * span
+        f = np.cumsum(rng.integers(1, span + 1, size=k)).astype(np.float64)
+        if k >= 3:
+            d = int(rng.integers(1, k - 1))
+            f[d + 1:] -= f[d + 1] - f[d]            # key d + 1 repeats key d's frame
+        return f
+    kf = np.concatenate([frames(n_keys) for _ in range(n)]) if n else np.zeros(0)
+    ax = rng.normal(size=(n, n_keys, 3))
+    ax /= np.linalg.norm(ax, axis=2, keepdims=True)
+    ang = rng.uniform(-max_angle, max_angle, size=(n, n_keys, 1))
+    dq = np.concatenate([ax * np.sin(ang / 2), np.cos(ang / 2)], axis=2)
+    kq = _quat_mul(bq[tb][:, None, :], dq)
+    kq /= np.linalg.norm(kq, axis=2, keepdims=True)
+    kq[rng.random((n, n_keys)) < flip] *= -1.0
+    clip = dict(track_bone=tb, key_off=(np.arange(n + 1) * n_keys).astype(np.uint32), key_frame=kf.astype(np.float32),
+                key_rot=kq.reshape(-1, 4).astype(np.float32), key_pos=rng.uniform(-trans, trans, size=(n * n_keys, 3)).astype(np.float32),
+                key_interp=rng.integers(1, 127, size=(n * n_keys, 16)).astype(np.uint8) if interp else None)
+    if n_morphs:
+        has = rng.random(n_morphs) < morph_keyed
+        n_tracks = n_morphs + (1 if group_feed is not None else 0)
+        moff, mkf, mkw = [0], [], []
+        for t in range(n_tracks):
+            if t >= n_morphs or has[t]:
+                mkf.append(frames(n_keys)); mkw.append(rng.random(n_keys))
+            moff.append(moff[-1] + (n_keys if (t >= n_morphs or has[t]) else 0))
+        foff, ftr, fra = [0], [], []
+        for m in range(n_morphs):
+            if has[m] or m % 4 != 3:                        # its own track first (it may hold no key) ...
+                ftr.append(m); fra.append(1.0)
+            if group_feed is not None and int(group_feed[0]) == m:      # ... then the group tracks that include it
+                ftr.append(n_morphs); fra.append(float(group_feed[1]))
+            foff.append(len(ftr))
+        clip.update(mkey_off=np.array(moff, dtype=np.uint32), mkey_frame=(np.concatenate(mkf) if mkf else np.zeros(0)).astype(np.float32),
+                    mkey_weight=(np.concatenate(mkw) if mkw else np.zeros(0)).astype(np.float32), feed_off=np.array(foff, dtype=np.uint32),
+                    feed_track=np.array(ftr, dtype=np.int32), feed_ratio=np.array(fra, dtype=np.float32))
+    return clip
