@@ -303,6 +303,86 @@ int rz_set_pose_blended(rz_ctx *ctx, const rz_motion_state *states);
  * Several entries for one bone: the last wins (successive set() calls). Asynchronous H2D through pinned staging.
  * Physics itself (Bullet via @fred3d/ammo) stays out of scope: this only carries its result. */
 int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16);
+/* ---- rigid-body physics on the device for PMX bodies and joints — NEW (optional) ----
+ * The reference runs Bullet (Ammo, loaded at run time: engine/src/physics.ts) on the host around the seam above. rz_upload_physics /
+ * rz_physics_step keep the seam (physics.ts:534-569) and replace the solver by one of this build's own, defined in float64 by
+ * tests/physics_ref.py and run in float32 by rz_physics_kernel (kernels/physics.hip), which WRITES THE OVERRIDE TABLE on the device: no
+ * frame kernel changes, and without a table every frame launches what it launched before. The ABI version stays 8: bindings detect the symbols.
+ * One rz_physics_step(substeps):
+ *   1. the hierarchy solve of the resident pose runs without overrides (with IK when a table is resident); a body of type 0 or 2, or of mass
+ *      0, is placed at boneWorld x offset with zero velocity (physics.ts:663-667 treats types 0 and 2 alike); bone -1: at offset itself.
+ *      offset = inverseBind x T(shapePosition) R(shapeRotation) (physics.ts:572-596), computed by the caller, as position3 + quaternion4.
+ *   2. `substeps` fixed steps of h (default 1/75 s, the reference's fixedTimeStep; callers cap at 10 per call, its maxSubSteps). XPBD rigid
+ *      bodies (Mueller et al. 2020) in the smallest form that covers PMX joints. Per substep:
+ *        integrate the dynamic bodies (type 1, mass > 0):  v += h g  (g default (0, -98, 0), physics.ts:56);  v *= (1 - linear_damping)^h;
+ *          w *= (1 - angular_damping)^h;  keep x_prev, q_prev;  x += h v;  q = normalize(q + (h/2) [w, 0] (x) q)   (no gyroscopic term)
+ *        `iterations` passes (default 4) over the joints in colour order — colours assigned at upload, greedily in file order, so that no
+ *          two joints of a colour share a dynamic body; per joint, with p = x + q r the world anchors, Q_A = q_A j_A the joint frame carried
+ *          by body A (anchors r and frames j taken once in the bind pose: the body at T(sum of bind translations up its bone's chain) x offset,
+ *          the joint at position3 / Quat.fromEuler(rotation3)):
+ *            position         d = Q_A^-1 (p_B - p_A);  e = d - clamp(d, position_min, position_max);  c = Q_A e is removed as a rigid
+ *                             positional constraint (compliance 0) with the 3 x 3 generalised inverse mass of the anchor pair:
+ *                             K p = c,  K = (1/m_A + 1/m_B) 1 - [r_A]x I_A^-1 [r_A]x - [r_B]x I_B^-1 [r_B]x;  A gets +p at r_A, B -p
+ *                             at r_B. (The scalar split 1/m + (r x n)^T I^-1 (r x n) along n = c / |c| moves the anchor off n whenever
+ *                             the body is not a ball around it: its residual rose between iterations and the bodies jittered.)
+ *                             Skipped when |c| <= 1e-9 or det K <= 0
+ *            rotation limits  the Euler angles ('XYZ', R = Rx Ry Rz, the IK limits' convention) of q_rel = Q_A^-1 Q_B clamped to
+ *                             [rotation_min, rotation_max]; when any changed, the rotation Q_A q_clamped q_rel^-1 Q_A^-1 — angle
+ *                             theta = 2 atan2(|xyz|, w) about n — is removed as a rigid angular constraint with the 3 x 3 inverse inertia
+ *                             of the pair: K l = theta n, K = I_A^-1 + I_B^-1 in world space; A turns by -I_A^-1 l, B by +I_B^-1 l (the
+ *                             scalar split n^T I^-1 n turns a body about I^-1 n, not n: a welded joint then only converges linearly).
+ *                             Skipped when |xyz| <= 1e-9 or det K <= 0
+ *            angular springs  Euler angles (ex, ey, ez), Q_A and Q_B taken once, after the limits; per axis with spring_rotation k > 0:
+ *                             C = that angle, about its gimbal axis n (x: Q_A e_x, y: Q_A (0, cos ex, sin ex), z: Q_B e_z — a rotation
+ *                             about which changes that angle alone), alpha~ = 1 / (k h^2),
+ *                             d_lambda = (-C - alpha~ lambda) / (w_A + w_B + alpha~); lambda is accumulated over the iterations of a
+ *                             substep and zero at its start
+ *          a rotation correction d_phi is applied as q = normalize(q + (1/2) [d_phi, 0] (x) q); a min > max pair of limits is swapped
+ *        velocities from the pose change:  v = (x - x_prev) / h;  w = 2 (q (x) q_prev^-1).xyz / h, negated when .w < 0
+ *      Inverse inertia, diagonal in the body frame: sphere 2/5 m r^2 (r = size.x); box m/3 (b^2 + c^2) with half extents = size; capsule the
+ *      box of half extents (r, r + height/2, r) (r = size.x, height = size.y).
+ *   3. every dynamic body with a bone gives boneWorld = bodyWorld x offset^-1: that bone's override, in every following frame until the
+ *      next step. Children of an overridden bone keep the matrices solved from the un-overridden parent, as rz_override_world documents.
+ * NOT covered: collisions and friction of any kind, linear springs (spring_position), restitution. A welded joint (all limits equal) whose
+ * anchor is off the body's centre converges only linearly in `iterations` (the position and the rotation stage each undo part of the
+ * other): about 0.3 of a parent's jump is left at 4 iterations, 1e-5 of it at 32. Shapes feed the inertia only; group and
+ * mask are stored but unused — the signature carries shape, size, group, mask, friction, restitution and spring_position so that a contact
+ * stage needs no new one (those arrays may be NULL today). There is no host-side twin of the solver.
+ * rz_upload_physics: needs rz_upload_skeleton_topology first; NULL or n_bodies = 0 removes the table; gravity3 NULL, h = 0, iterations = 0 =
+ *   the defaults. RZ_ERR_INVALID (context untouched): a body, bone or joint index out of range, body_a == body_b, a value that is not finite,
+ *   mass < 0, a damping outside [0, 1], h < 0, a type or shape above 2, two dynamic bodies on one bone. RZ_ERR_UNSUPPORTED: a table whose state does not fit the
+ *   kernel's LDS (96 B per body, + 12 B per joint once the joints outnumber the 256 lanes; the limit is 160 KB). A new skeleton or
+ *   topology drops the table. With a table resident physics owns the override table — the dynamic bodies' bones of instance i at
+ *   [i nd, (i + 1) nd) — and rz_override_world is refused.
+ * rz_physics_step: enqueues on the frame's stream, no host synchronisation: the hierarchy solve, then rz_physics_kernel (one workgroup per
+ *   instance, state in LDS across all substeps). substeps = 0 only re-places the following bodies and re-emits the overrides; more than 1000 in one call is RZ_ERR_INVALID. Acts on
+ *   device-solved poses only (rz_set_pose_local / _sampled / _blended; with rz_set_pose the host owns the world matrices: refused). The
+ *   first step after an upload, after rz_physics_reset, or after rz_set_instances changed the count behaves as a reset followed by the step.
+ *   rz_deform_n, graph replays and rz_time_span replay the resident overrides and do not advance the simulation; the override buffers keep
+ *   their addresses across steps. The one-launch crowd form is not taken while overrides are resident (as with rz_override_world).
+ * rz_physics_reset: every body onto its bone's SOLVED (un-overridden) pose, zero velocities (without a device-solved pose: at the next step).
+ * All three are refused while forks exist. rz_read_physics: per body x3 q4 v3 w3 of one instance; blocking; for tests and tools.
+ * rz_get_tuning("physics_bodies") / ("physics_joints") / ("physics_colours") = the counts. */
+typedef struct rz_physics {
+    uint32_t n_bodies;
+    const int32_t *bone;                /* [n_bodies] -1 = none */
+    const uint8_t *type, *shape;        /* type 0 follows its bone, 1 dynamic, 2 dynamic + bone (treated as 0); shape 0 sphere, 1 box, 2 capsule */
+    const float *size3, *offset_pos3, *offset_rot4;
+    const float *mass, *linear_damping, *angular_damping, *restitution, *friction;
+    const uint8_t *group;
+    const uint16_t *mask;
+    uint32_t n_joints;
+    const uint32_t *body_a, *body_b;
+    const float *position3, *rotation3;                 /* model space, bind pose; rotation as the loader's Euler angles */
+    const float *position_min3, *position_max3, *rotation_min3, *rotation_max3, *spring_position3, *spring_rotation3;
+    const float *gravity3;              /* NULL = (0, -98, 0) */
+    float h;                            /* 0 = 1/75 s */
+    uint32_t iterations;                /* 0 = 4 */
+} rz_physics;
+int rz_upload_physics(rz_ctx *ctx, const rz_physics *tab);
+int rz_physics_step(rz_ctx *ctx, uint32_t substeps);
+int rz_physics_reset(rz_ctx *ctx);
+int rz_read_physics(rz_ctx *ctx, uint32_t instance, float *state13);
 /* Blocking readback of one instance's world matrices (B x 16, column-major) as the frame used them. */
 int rz_read_world(rz_ctx *ctx, uint32_t instance, float *world16);
 

@@ -22,12 +22,14 @@ SYMBOLS = [
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
+    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
-# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions and rz_set_pose_blended — detected by the symbol,
-# the version stayed 8)
+# rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended and the four physics entry
+# points — detected by the symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
-                    "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended"}
+                    "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
+                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
 
@@ -45,6 +47,16 @@ class RzAnimation(ctypes.Structure):
 class RzMotionState(ctypes.Structure):
     _fields_ = [("clip_a", ctypes.c_uint32), ("frame_a", ctypes.c_float), ("clip_b", ctypes.c_uint32), ("frame_b", ctypes.c_float),
                 ("blend", ctypes.c_float)]
+
+
+class RzPhysics(ctypes.Structure):
+    _f, _u8, _u32 = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    _fields_ = [("n_bodies", ctypes.c_uint32), ("bone", ctypes.POINTER(ctypes.c_int32)), ("type", _u8), ("shape", _u8),
+                ("size3", _f), ("offset_pos3", _f), ("offset_rot4", _f), ("mass", _f), ("linear_damping", _f), ("angular_damping", _f),
+                ("restitution", _f), ("friction", _f), ("group", _u8), ("mask", ctypes.POINTER(ctypes.c_uint16)),
+                ("n_joints", ctypes.c_uint32), ("body_a", _u32), ("body_b", _u32), ("position3", _f), ("rotation3", _f),
+                ("position_min3", _f), ("position_max3", _f), ("rotation_min3", _f), ("rotation_max3", _f),
+                ("spring_position3", _f), ("spring_rotation3", _f), ("gravity3", _f), ("h", ctypes.c_float), ("iterations", ctypes.c_uint32)]
 
 
 # the same 20 bytes as a numpy record (set_pose_blended packs a crowd's states with it)
@@ -191,6 +203,11 @@ def load(path=None):
     if hasattr(L, "rz_upload_ik"):             # (ABI 8 still: the feature is detected by the symbol)
         u8p = ctypes.POINTER(ctypes.c_uint8)
         L.rz_upload_ik.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32), fp, ctypes.POINTER(u32), ctypes.POINTER(u32), u8p, fp, fp]
+    if hasattr(L, "rz_upload_physics"):        # (ABI 8 still: the feature is detected by the symbols)
+        L.rz_upload_physics.argtypes = [vp, ctypes.POINTER(RzPhysics)]
+        L.rz_physics_step.argtypes = [vp, u32]
+        L.rz_physics_reset.argtypes = [vp]
+        L.rz_read_physics.argtypes = [vp, u32, fp]
     for name in SYMBOLS:
         # (libraries older than the current ABI — tools/ab_inproc.py loads them side by side — lack the newer symbols: OPTIONAL_SYMBOLS)
         if name != "rz_last_error" and (name not in OPTIONAL_SYMBOLS or hasattr(L, name)):
@@ -606,6 +623,53 @@ class DeformContext:
         self._chk(self._L.rz_upload_ik(self._h, len(chains), goal.ctypes.data_as(u32p), eff.ctypes.data_as(u32p), loops.ctypes.data_as(u32p),
                                        _fptr(theta), off.ctypes.data_as(u32p), bone_a.ctypes.data_as(u32p), lim_a.ctypes.data_as(u8p),
                                        _fptr(lo_a), _fptr(hi_a)))
+
+    def upload_physics(self, table):
+        """Rigid-body physics for device-solved poses: `table` = dict(n_bodies, bone, type, shape, size [n,3], offset_pos [n,3], offset_rot
+        [n,4], mass, linear_damping, angular_damping, restitution, friction, group, mask; n_joints, body_a, body_b, position, rotation,
+        position_min / _max, rotation_min / _max, spring_position, spring_rotation [m,3]; gravity [3] or None, h, iterations (0 = defaults))
+        — the arrays Model.physicsTables() produces on the Node side. None or n_bodies = 0 removes the table. Needs
+        upload_skeleton_topology first."""
+        if not hasattr(self._L, "rz_upload_physics"):
+            raise RzError(-6, "this build of the library has no rz_upload_physics")
+        if table is None or int(table["n_bodies"]) == 0:
+            self._chk(self._L.rz_upload_physics(self._h, None))
+            return
+        t, keep = RzPhysics(), []
+
+        def arr(key, dt, ct, count):
+            v = np.ascontiguousarray(table[key], dtype=dt).reshape(-1)
+            assert v.size == count, (key, v.size, count)
+            keep.append(v)
+            return v.ctypes.data_as(ctypes.POINTER(ct)) if v.size else None
+        nb, nj = int(table["n_bodies"]), int(table["n_joints"])
+        t.n_bodies, t.n_joints = nb, nj
+        t.bone = arr("bone", np.int32, ctypes.c_int32, nb)
+        t.type, t.shape, t.group = (arr(k, np.uint8, ctypes.c_uint8, nb) for k in ("type", "shape", "group"))
+        t.mask = arr("mask", np.uint16, ctypes.c_uint16, nb)
+        t.size3, t.offset_pos3, t.offset_rot4 = arr("size", np.float32, ctypes.c_float, nb * 3), arr("offset_pos", np.float32, ctypes.c_float, nb * 3), arr("offset_rot", np.float32, ctypes.c_float, nb * 4)
+        for k in ("mass", "linear_damping", "angular_damping", "restitution", "friction"):
+            setattr(t, k, arr(k, np.float32, ctypes.c_float, nb))
+        t.body_a, t.body_b = arr("body_a", np.uint32, ctypes.c_uint32, nj), arr("body_b", np.uint32, ctypes.c_uint32, nj)
+        for k in ("position", "rotation", "position_min", "position_max", "rotation_min", "rotation_max", "spring_position", "spring_rotation"):
+            setattr(t, k + "3", arr(k, np.float32, ctypes.c_float, nj * 3))
+        t.gravity3 = None if table.get("gravity") is None else arr("gravity", np.float32, ctypes.c_float, 3)
+        t.h, t.iterations = float(table.get("h", 0.0)), int(table.get("iterations", 0))
+        self._chk(self._L.rz_upload_physics(self._h, ctypes.byref(t)))
+
+    def physics_step(self, substeps):
+        """Advance the resident physics table by `substeps` fixed steps against the resident device-solved pose (0 = only re-place the
+        following bodies and re-emit the overrides). Enqueued on the frame's stream."""
+        self._chk(self._L.rz_physics_step(self._h, int(substeps)))
+
+    def physics_reset(self):
+        self._chk(self._L.rz_physics_reset(self._h))
+
+    def read_physics(self, instance=0):
+        """[n_bodies, 13] x3 q4 v3 w3 of one instance (blocking)."""
+        out = np.empty((self.get_tuning("physics_bodies"), 13), dtype=np.float32)
+        self._chk(self._L.rz_read_physics(self._h, int(instance), _fptr(out)))
+        return out
 
     def read_hull(self, instance=0, v0=0, n=None):
         n = self.V - v0 if n is None else n

@@ -377,6 +377,7 @@ int rz_destroy(rz_ctx *c)
     free_sdef(c);
     free_qdef(c);
     free_ik(c);
+    free_physics(c);
     for (int k = 0; k < 2; ++k) {
         if (c->big_ev[k]) (void)hipEventDestroy(c->big_ev[k]);
     }

@@ -7,6 +7,7 @@
 //   plan.cpp    launch shapes and the parameter blocks of the kernels                   (no exports)
 //   frame.cpp   launching frames, replay, timing, readbacks                             rz_deform* / rz_time_frames / rz_read*
 //   tune.cpp    launch-shape search and the tuning keys                                 rz_autotune* / rz_set_tuning / rz_get_tuning
+//   physics_host.cpp  rigid-body physics: table upload, stepping, reset, readback           rz_upload_physics / rz_physics_* / rz_read_physics
 //   comm.cpp    RCCL binding, all-gather, peer-direct gather                            rz_comm_* / rz_allgather* / rz_gather_*
 #pragma once
 #include "../../include/reze_deform.h"
@@ -153,6 +154,17 @@ struct rz_ctx {
     float4 *ik_link = nullptr;
     uint32_t ik_n = 0, ik_stages = 0;
 
+    // rigid-body physics (rz_upload_physics; physics_host.cpp, kernels/physics.hip): static records, per-instance state, and what the next step
+    // must do first. ph_nb = 0: no table. With a table the override table above is physics' own ([I][ph_nd] slots, fixed addresses).
+    float4 *ph_body = nullptr, *ph_joint = nullptr, *ph_state = nullptr;
+    int *ph_colour_off = nullptr;
+    uint32_t ph_nb = 0, ph_nj = 0, ph_ncol = 0, ph_nd = 0, ph_I = 0;
+    int ph_iterations = 0, ph_block = 64;
+    float ph_h = 0.0f, ph_g[3] = { 0.0f, 0.0f, 0.0f };
+    bool ph_reset = true;               // the next step places every body on its bone first
+    std::vector<int> ph_dyn_bone;       // [ph_nd] bones of the dynamic bodies
+    std::vector<uint8_t> ph_group;      // [ph_nb] collision group and mask as uploaded: kept for a contact stage, read by nothing yet
+    std::vector<uint16_t> ph_mask;
     // morphs
     int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
     uint32_t M = 0, Mpad = 12;
@@ -365,6 +377,7 @@ void free_morphs(rz_ctx *c);
 void free_sdef(rz_ctx *c);
 void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
+void free_physics(rz_ctx *c);          // physics_host.cpp
 RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {

@@ -268,6 +268,27 @@ struct RzMotionParams {
 };
 hipError_t rz_launch_motion_blend(const RzMotionParams &p, uint32_t instances, hipStream_t st);
 
+// rz_physics_kernel (kernels/physics.hip): rigid bodies and joints of every instance advanced by `substeps` fixed steps, one workgroup per
+// instance, in front of the frame (rz_upload_physics / rz_physics_step). It reads the world matrices the hierarchy solve left in memory and
+// writes the solve's override table; the frame kernels see overrides, nothing else.
+struct RzPhysicsParams {
+    const float4 *body;         // [nb][4]  offset position | inverse mass (0 = follows its bone);  offset rotation;  inverse inertia (body frame) |
+                                //          (1 - linear damping)^h;  (1 - angular damping)^h | bits(bone, -1 = none) | bits(override slot, -1 = none) | 0
+    const float4 *joint;        // [nj][8]  in solve order (colour, file index): anchor in A | bits(body A);  anchor in B | bits(body B);  joint frame in A;
+                                //          joint frame in B;  position min | alpha~ x;  position max | alpha~ y;  rotation min | alpha~ z;  rotation max | bits(spring axes)
+    const int *colour_off;      // [ncol + 1] joints of colour k: colour_off[k] .. colour_off[k + 1]
+    float4 *state;              // [I][nb][4] x | q | v | w
+    const float *world;         // [I][B][16] the un-overridden hierarchy solve (after IK)
+    float *ovr_world;           // [I][nd][16] out: the override table's matrices
+    int nb, nj, ncol, nd, B;
+    int iterations, substeps;
+    int reset;                  // every body (not only the following ones) is placed on its bone first
+    int block;                  // 64 or 256 lanes
+    float h, gx, gy, gz;
+};
+size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block);     // 96 B per body (+ 12 B per joint when the joints outnumber the lanes)
+hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st);
+
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).
 struct RzVariant {
     int mode;    // 0 none, 1 dense, 2 sparse

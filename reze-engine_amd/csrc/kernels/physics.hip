@@ -1,0 +1,344 @@
+// kernels/physics.hip — rz_physics_kernel: rigid-body physics for PMX bodies and joints on the device (rz_upload_physics / rz_physics_step).
+// XPBD rigid bodies in the form tests/physics_ref.py defines and include/reze_deform.h states; this file spells the same operations in the
+// same order in float32. One workgroup = one instance. Per call:
+//   load      a following body (type != 1 or mass 0; after a reset: every body) is placed at boneWorld x offset with zero velocity, from the
+//             world matrices the hierarchy solve (with IK) has just left in memory; a dynamic body's state x | q | v | w comes from its
+//             64-byte record. All of it lives in LDS from here on: 96 B per body (state + the substep's previous pose).
+//   substeps  integrate (lane per body) | barrier | iterations x colours x { joints of the colour, lane per joint | barrier } | velocities
+//             (lane per body: the lane that integrates the body next, so no barrier behind it)
+//   store     the state records, and per dynamic body with a bone boneWorld = bodyWorld x offset^-1 as four 16-byte stores into the
+//             hierarchy solve's override table (slot inst * nd + k, written by nobody else).
+// Joints of one colour share no dynamic body (the upload colours them), so their lanes read and write disjoint LDS records; a following body
+// may be shared and is only ever read. OWN: the table has no more joints than the block has lanes — lane t keeps joint t's constants (eight
+// float4) and its spring multipliers in registers for the whole kernel; otherwise lanes stride over a colour, reload the constants per
+// visit (they stay in L1 / L2) and keep the multipliers in LDS. The block is 64 lanes when the bodies and the widest colour fit a wave, else
+// 256. Every phase ends in __syncthreads() in the source of both; under __launch_bounds__(64) the workgroup is one wave and the compiler
+// emits no barrier instruction for it, only the wait for the wave's own LDS accesses (the 64-lane code objects hold no s_barrier, the
+// 256-lane ones three: DESIGN.md 9.7).
+#include "pass_parts.hip.h"
+
+namespace {
+
+#pragma clang fp contract(off)      // tests/physics_ref.py restates this arithmetic in float64, operation by operation
+
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 v3(const float x, const float y, const float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
+__device__ __forceinline__ V3 operator+(const V3 a, const V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 operator-(const V3 a, const V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 operator*(const V3 a, const float s) { return v3(a.x * s, a.y * s, a.z * s); }
+__device__ __forceinline__ V3 operator*(const V3 a, const V3 b) { return v3(a.x * b.x, a.y * b.y, a.z * b.z); }
+__device__ __forceinline__ V3 operator/(const V3 a, const float s) { return v3(a.x / s, a.y / s, a.z / s); }
+__device__ __forceinline__ V3 neg(const V3 a) { return v3(-a.x, -a.y, -a.z); }
+__device__ __forceinline__ float dot3(const V3 a, const V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 cross3(const V3 a, const V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+__device__ __forceinline__ V3 xyz(const float4 a) { return v3(a.x, a.y, a.z); }
+
+__device__ __forceinline__ float4 qmul(const float4 a, const float4 b)
+{
+    return make_float4(a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+                       a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
+                       a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w,
+                       a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z);
+}
+__device__ __forceinline__ float4 qconj(const float4 a) { return make_float4(-a.x, -a.y, -a.z, a.w); }
+// v turned by q:  v + w t + u x t,  t = 2 (u x v)
+__device__ __forceinline__ V3 qrot(const float4 q, const V3 v)
+{
+    const V3 u = xyz(q);
+    V3 t = cross3(u, v);
+    t = t + t;
+    return v + t * q.w + cross3(u, t);
+}
+__device__ __forceinline__ float4 qnormalize(const float4 q)
+{
+    const float l = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    return make_float4(q.x / l, q.y / l, q.z / l, q.w / l);
+}
+// q = normalize(q + 1/2 [dphi, 0] (x) q)
+__device__ __forceinline__ float4 rot_apply(const float4 q, const V3 d)
+{
+    const float4 m = qmul(make_float4(d.x, d.y, d.z, 0.0f), q);
+    return qnormalize(make_float4(q.x + 0.5f * m.x, q.y + 0.5f * m.y, q.z + 0.5f * m.z, q.w + 0.5f * m.w));
+}
+// I^-1 v in world space for a body at rotation q with the body-frame diagonal ii
+__device__ __forceinline__ V3 iinv(const float4 q, const V3 ii, const V3 v) { return qrot(q, ii * qrot(qconj(q), v)); }
+
+// Euler angles 'XYZ' (R = Rx Ry Rz) of the rotation q, through the matrix entries three.js reads (the convention of the IK limits)
+__device__ __forceinline__ V3 euler_xyz(const float4 q)
+{
+    const float x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
+    const float xx = q.x * x2, xy = q.x * y2, xz = q.x * z2, yy = q.y * y2, yz = q.y * z2, zz = q.z * z2;
+    const float wx = q.w * x2, wy = q.w * y2, wz = q.w * z2;
+    const float m00 = 1.0f - (yy + zz), m01 = xy - wz, m02 = xz + wy, m11 = 1.0f - (xx + zz), m12 = yz - wx, m21 = yz + wx, m22 = 1.0f - (xx + yy);
+    V3 e;
+    e.y = asinf(fminf(fmaxf(m02, -1.0f), 1.0f));
+    if (fabsf(m02) < 0.9999999f) { e.x = atan2f(-m12, m22); e.z = atan2f(-m01, m00); }
+    else { e.x = atan2f(m21, m11); e.z = 0.0f; }
+    return e;
+}
+__device__ __forceinline__ float4 from_euler_xyz(const V3 e)
+{
+    const float c1 = cosf(e.x * 0.5f), c2 = cosf(e.y * 0.5f), c3 = cosf(e.z * 0.5f);
+    const float s1 = sinf(e.x * 0.5f), s2 = sinf(e.y * 0.5f), s3 = sinf(e.z * 0.5f);
+    return make_float4(s1 * c2 * c3 + c1 * s2 * s3, c1 * s2 * c3 - s1 * c2 * s3, c1 * c2 * s3 + s1 * s2 * c3, c1 * c2 * c3 - s1 * s2 * s3);
+}
+__device__ __forceinline__ V3 clamp3(const V3 v, const V3 lo, const V3 hi)
+{
+    return v3(fminf(fmaxf(v.x, lo.x), hi.x), fminf(fmaxf(v.y, lo.y), hi.y), fminf(fmaxf(v.z, lo.z), hi.z));
+}
+
+constexpr float kEps = 1e-9f;
+
+// a joint's constants (deform_kernels.h: the eight float4 of a joint record)
+struct JointC {
+    V3 r_a, r_b, pmin, pmax, rmin, rmax, alpha;
+    float4 j_a, j_b;
+    int a, b;
+    uint32_t springs;
+};
+__device__ __forceinline__ JointC load_joint(const float4 *rec)
+{
+    const float4 w0 = rec[0], w1 = rec[1], w4 = rec[4], w5 = rec[5], w6 = rec[6], w7 = rec[7];
+    JointC c;
+    c.r_a = xyz(w0); c.a = (int)__float_as_uint(w0.w);
+    c.r_b = xyz(w1); c.b = (int)__float_as_uint(w1.w);
+    c.j_a = rec[2]; c.j_b = rec[3];
+    c.pmin = xyz(w4); c.pmax = xyz(w5); c.rmin = xyz(w6); c.rmax = xyz(w7);
+    c.alpha = v3(w4.w, w5.w, w6.w);
+    c.springs = __float_as_uint(w7.w);
+    return c;
+}
+
+// One joint, once: position, rotation limits, angular springs (tests/physics_ref.py: Sim._solve). sx / sq are the workgroup's body positions
+// and rotations in LDS, `body` the static body records (inverse mass in word 0's w, inverse inertia in word 2), lam the joint's three spring
+// multipliers.
+__device__ __forceinline__ void solve_joint(const JointC &c, const float4 *body, float4 *sx, float4 *sq, float &lam0, float &lam1, float &lam2)
+{
+    const float4 ba0 = body[4 * c.a], ba2 = body[4 * c.a + 2], bb0 = body[4 * c.b], bb2 = body[4 * c.b + 2];
+    const float ima = ba0.w, imb = bb0.w;
+    const V3 iia = xyz(ba2), iib = xyz(bb2);
+    V3 xa = xyz(sx[c.a]), xb = xyz(sx[c.b]);
+    float4 qa = sq[c.a], qb = sq[c.b];
+    // position
+    {
+        const V3 ra = qrot(qa, c.r_a), rb = qrot(qb, c.r_b);
+        const float4 QA = qmul(qa, c.j_a);
+        const V3 d = qrot(qconj(QA), (xb + rb) - (xa + ra));
+        const V3 e = d - clamp3(d, c.pmin, c.pmax);
+        const V3 cv = qrot(QA, e);
+        const float C = sqrtf(dot3(cv, cv));
+        if (C > kEps) {
+            // K p = c: the anchors' relative displacement for a correction p, K = (1/m_A + 1/m_B) 1 - [r_A]x I_A^-1 [r_A]x - [r_B]x I_B^-1 [r_B]x,
+            // column by column, solved by Cramer's rule
+            V3 k[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const V3 u = v3(ax == 0 ? 1.0f : 0.0f, ax == 1 ? 1.0f : 0.0f, ax == 2 ? 1.0f : 0.0f);
+                k[ax] = u * (ima + imb) + cross3(iinv(qa, iia, cross3(ra, u)), ra) + cross3(iinv(qb, iib, cross3(rb, u)), rb);
+            }
+            const float det = dot3(k[0], cross3(k[1], k[2]));
+            if (det > 0.0f) {
+                const V3 p = v3(dot3(cv, cross3(k[1], k[2])), dot3(k[0], cross3(cv, k[2])), dot3(k[0], cross3(k[1], cv))) / det;
+                const float4 qa_new = rot_apply(qa, iinv(qa, iia, cross3(ra, p)));
+                const float4 qb_new = rot_apply(qb, neg(iinv(qb, iib, cross3(rb, p))));
+                xa = xa + p * ima; xb = xb - p * imb;
+                qa = qa_new; qb = qb_new;
+            }
+        }
+    }
+    // rotation limits
+    {
+        const float4 QA = qmul(qa, c.j_a), QB = qmul(qb, c.j_b);
+        const float4 qrel = qmul(qconj(QA), QB);
+        const V3 eu = euler_xyz(qrel);
+        const V3 ec = clamp3(eu, c.rmin, c.rmax);
+        if (ec.x != eu.x || ec.y != eu.y || ec.z != eu.z) {
+            float4 dq = qmul(qmul(QA, qmul(from_euler_xyz(ec), qconj(qrel))), qconj(QA));
+            if (dq.w < 0.0f) dq = make_float4(-dq.x, -dq.y, -dq.z, -dq.w);
+            const float s = sqrtf(dot3(xyz(dq), xyz(dq)));
+            if (s > kEps) {
+                const V3 n = xyz(dq) / s;
+                const float theta = 2.0f * atan2f(s, dq.w);
+                // K l = theta n with K = I_A^-1 + I_B^-1 (world), column by column, Cramer's rule; A turns by -I_A^-1 l, B by +I_B^-1 l
+                V3 k[3];
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    const V3 u = v3(ax == 0 ? 1.0f : 0.0f, ax == 1 ? 1.0f : 0.0f, ax == 2 ? 1.0f : 0.0f);
+                    k[ax] = iinv(qa, iia, u) + iinv(qb, iib, u);
+                }
+                const float det = dot3(k[0], cross3(k[1], k[2]));
+                if (det > 0.0f) {
+                    const V3 rhs = n * theta;
+                    const V3 lm = v3(dot3(rhs, cross3(k[1], k[2])), dot3(k[0], cross3(rhs, k[2])), dot3(k[0], cross3(k[1], rhs))) / det;
+                    const float4 qa_new = rot_apply(qa, neg(iinv(qa, iia, lm)));
+                    const float4 qb_new = rot_apply(qb, iinv(qb, iib, lm));
+                    qa = qa_new; qb = qb_new;
+                }
+            }
+        }
+    }
+    // angular springs
+    if (c.springs) {
+        const float4 QA = qmul(qa, c.j_a), QB = qmul(qb, c.j_b);
+        const V3 eu = euler_xyz(qmul(qconj(QA), QB));
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            if (!(c.springs >> ax & 1u)) continue;
+            // the gimbal axis of that angle: x in A's joint frame, y turned by the x angle, z in B's joint frame
+            const V3 n = ax == 0 ? qrot(QA, v3(1.0f, 0.0f, 0.0f)) : ax == 1 ? qrot(QA, v3(0.0f, cosf(eu.x), sinf(eu.x))) : qrot(QB, v3(0.0f, 0.0f, 1.0f));
+            const V3 na = iinv(qa, iia, n), nb = iinv(qb, iib, n);
+            const float al = ax == 0 ? c.alpha.x : ax == 1 ? c.alpha.y : c.alpha.z;
+            const float ang = ax == 0 ? eu.x : ax == 1 ? eu.y : eu.z;
+            float &lam = ax == 0 ? lam0 : ax == 1 ? lam1 : lam2;
+            const float dl = (-ang - al * lam) / (dot3(n, na) + dot3(n, nb) + al);
+            lam = lam + dl;
+            qa = rot_apply(qa, neg(na * dl));
+            qb = rot_apply(qb, nb * dl);
+        }
+    }
+    // only dynamic bodies are written: a following body may be shared inside a colour and never moves
+    if (ima > 0.0f) { sx[c.a] = make_float4(xa.x, xa.y, xa.z, 0.0f); sq[c.a] = qa; }
+    if (imb > 0.0f) { sx[c.b] = make_float4(xb.x, xb.y, xb.z, 0.0f); sq[c.b] = qb; }
+}
+
+template <int BLOCK, bool OWN>
+__global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams p)
+{
+    extern __shared__ float4 ph_lds[];
+    const int tid = threadIdx.x, inst = blockIdx.x, nb = p.nb;
+    float4 *sx = ph_lds, *sq = sx + nb, *sv = sq + nb, *sw = sv + nb, *sxp = sw + nb, *sqp = sxp + nb;
+    float *slam = reinterpret_cast<float *>(sqp + nb);              // [nj][3], the striding form only
+    float4 *state = p.state + (size_t)inst * nb * 4;
+    const float *world = p.world + (size_t)inst * p.B * 16;
+
+    for (int b = tid; b < nb; b += BLOCK) {
+        const float4 b0 = p.body[4 * b], b1 = p.body[4 * b + 1], b3 = p.body[4 * b + 3];
+        const int bone = (int)__float_as_uint(b3.y);
+        const bool dyn = b0.w > 0.0f;
+        float4 x, q, v, w;
+        if (!dyn || p.reset) {
+            V3 px = xyz(b0);
+            q = b1;
+            if (bone >= 0) {
+                const float4 *m = reinterpret_cast<const float4 *>(world + (size_t)bone * 16);
+                const float4 c0 = m[0], c1 = m[1], c2 = m[2], c3 = m[3];
+                const float4 r0 = make_float4(c0.x, c1.x, c2.x, c3.x), r1 = make_float4(c0.y, c1.y, c2.y, c3.y), r2 = make_float4(c0.z, c1.z, c2.z, c3.z);
+                const Quatf qw = quat_of_rows(r0, r1, r2);
+                q = qmul(make_float4(qw.x, qw.y, qw.z, qw.w), b1);
+                const V3 o = px;
+                px = v3((r0.x * o.x + r0.y * o.y + r0.z * o.z) + r0.w, (r1.x * o.x + r1.y * o.y + r1.z * o.z) + r1.w, (r2.x * o.x + r2.y * o.y + r2.z * o.z) + r2.w);
+            }
+            x = make_float4(px.x, px.y, px.z, 0.0f);
+            v = w = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        } else {
+            x = state[4 * b]; q = state[4 * b + 1]; v = state[4 * b + 2]; w = state[4 * b + 3];
+        }
+        sx[b] = x; sq[b] = q; sv[b] = v; sw[b] = w;
+    }
+    JointC own;
+    float l0 = 0.0f, l1 = 0.0f, l2 = 0.0f;
+    if (OWN && tid < p.nj) own = load_joint(p.joint + (size_t)tid * 8);
+    __syncthreads();
+
+    const float h = p.h;
+    for (int s = 0; s < p.substeps; ++s) {
+        for (int b = tid; b < nb; b += BLOCK) {
+            const float4 b0 = p.body[4 * b], b2 = p.body[4 * b + 2], b3 = p.body[4 * b + 3];
+            if (b0.w > 0.0f) {
+                V3 v = xyz(sv[b]), w = xyz(sw[b]);
+                v = v + v3(h * p.gx, h * p.gy, h * p.gz);
+                v = v * b2.w; w = w * b3.x;
+                const float4 x = sx[b], q = sq[b];
+                sxp[b] = x; sqp[b] = q;
+                const V3 xn = xyz(x) + v * h;
+                const float4 m = qmul(make_float4(w.x, w.y, w.z, 0.0f), q);
+                const float hh = h * 0.5f;
+                sx[b] = make_float4(xn.x, xn.y, xn.z, 0.0f);
+                sq[b] = qnormalize(make_float4(q.x + hh * m.x, q.y + hh * m.y, q.z + hh * m.z, q.w + hh * m.w));
+                sv[b] = make_float4(v.x, v.y, v.z, 0.0f); sw[b] = make_float4(w.x, w.y, w.z, 0.0f);
+            }
+        }
+        if (OWN) { l0 = l1 = l2 = 0.0f; }
+        else for (int k = tid; k < 3 * p.nj; k += BLOCK) slam[k] = 0.0f;
+        __syncthreads();
+        for (int it = 0; it < p.iterations; ++it)
+            for (int col = 0; col < p.ncol; ++col) {
+                const int j0 = p.colour_off[col], j1 = p.colour_off[col + 1];
+                if (OWN) {
+                    if (tid >= j0 && tid < j1) solve_joint(own, p.body, sx, sq, l0, l1, l2);
+                } else {
+                    for (int j = j0 + tid; j < j1; j += BLOCK) {
+                        const JointC c = load_joint(p.joint + (size_t)j * 8);
+                        solve_joint(c, p.body, sx, sq, slam[3 * j], slam[3 * j + 1], slam[3 * j + 2]);
+                    }
+                }
+                __syncthreads();
+            }
+        for (int b = tid; b < nb; b += BLOCK) {
+            if (p.body[4 * b].w > 0.0f) {
+                const V3 v = (xyz(sx[b]) - xyz(sxp[b])) / h;
+                const float4 dq = qmul(sq[b], qconj(sqp[b]));
+                V3 om = (xyz(dq) * 2.0f) / h;
+                if (dq.w < 0.0f) om = neg(om);
+                sv[b] = make_float4(v.x, v.y, v.z, 0.0f); sw[b] = make_float4(om.x, om.y, om.z, 0.0f);
+            }
+        }
+        // (no barrier: the lane that wrote body b's velocities is the lane that integrates body b)
+    }
+
+    for (int b = tid; b < nb; b += BLOCK) {
+        const float4 x = sx[b], q = sq[b];
+        state[4 * b] = x; state[4 * b + 1] = q; state[4 * b + 2] = sv[b]; state[4 * b + 3] = sw[b];
+        const float4 b0 = p.body[4 * b], b1 = p.body[4 * b + 1], b3 = p.body[4 * b + 3];
+        const int slot = (int)__float_as_uint(b3.z);
+        if (slot >= 0) {
+            // boneWorld = bodyWorld x offset^-1: rotation q (x) offset_q^-1, translation x - R offset_p
+            const float4 qb = qmul(q, qconj(b1));
+            const float x2 = qb.x + qb.x, y2 = qb.y + qb.y, z2 = qb.z + qb.z;
+            const float xx = qb.x * x2, xy = qb.x * y2, xz = qb.x * z2, yy = qb.y * y2, yz = qb.y * z2, zz = qb.z * z2;
+            const float wx = qb.w * x2, wy = qb.w * y2, wz = qb.w * z2;
+            const float m00 = 1.0f - (yy + zz), m01 = xy - wz, m02 = xz + wy;
+            const float m10 = xy + wz, m11 = 1.0f - (xx + zz), m12 = yz - wx;
+            const float m20 = xz - wy, m21 = yz + wx, m22 = 1.0f - (xx + yy);
+            const float tx = x.x - (m00 * b0.x + m01 * b0.y + m02 * b0.z);
+            const float ty = x.y - (m10 * b0.x + m11 * b0.y + m12 * b0.z);
+            const float tz = x.z - (m20 * b0.x + m21 * b0.y + m22 * b0.z);
+            float4 *o = reinterpret_cast<float4 *>(p.ovr_world + ((size_t)inst * p.nd + slot) * 16);
+            o[0] = make_float4(m00, m10, m20, 0.0f);
+            o[1] = make_float4(m01, m11, m21, 0.0f);
+            o[2] = make_float4(m02, m12, m22, 0.0f);
+            o[3] = make_float4(tx, ty, tz, 1.0f);
+        }
+    }
+}
+
+#pragma clang fp contract(fast)
+
+template <int BLOCK, bool OWN>
+hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
+{
+    auto k = rz_physics_kernel<BLOCK, OWN>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k, dim3(instances), dim3(BLOCK), lds, st, p);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block)
+{
+    return (size_t)n_bodies * 96 + (n_joints > block ? (size_t)n_joints * 12 : 0);
+}
+
+hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st)
+{
+    if (p.nb <= 0 || instances == 0 || (p.block != 64 && p.block != 256)) return hipErrorInvalidValue;
+    const bool own = p.nj <= p.block;
+    const size_t lds = rz_physics_lds_bytes(p.nb, p.nj, p.block);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (p.block == 64) return own ? launch<64, true>(p, instances, lds, st) : launch<64, false>(p, instances, lds, st);
+    return own ? launch<256, true>(p, instances, lds, st) : launch<256, false>(p, instances, lds, st);
+}

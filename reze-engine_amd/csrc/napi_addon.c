@@ -370,6 +370,111 @@ static napi_value fn_upload_ik(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+static int get_prop_ta(napi_env env, napi_value obj, const char *name, napi_typedarray_type want, int optional, void **data, size_t *len);
+
+/* uploadPhysics(ctx, tables|null, { gravity?: Float32Array(3), h?: number, iterations?: number }?): the rigid bodies and joints of the skeleton
+ * (rz_upload_physics) as Model.physicsTables() lays them out — one entry per body in bone / type / shape / mass / ..., three per body in
+ * size / offsetPos, four in offsetRot, one per joint in bodyA / bodyB, three in the joint vectors. null or a table without bodies removes it. */
+static napi_value fn_upload_physics(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    static const char *usage = "uploadPhysics(ctx, { bone, type, shape, size, offsetPos, offsetRot, mass, linearDamping, angularDamping, restitution, friction, group, mask, bodyA, bodyB, position, rotation, positionMin, positionMax, rotationMin, rotationMax, springPosition, springRotation } | null, { gravity?, h?, iterations? }?)";
+    napi_value o = argv[1];
+    napi_valuetype vt;
+    if (napi_typeof(env, o, &vt) != napi_ok) return throw_msg(env, usage);
+    if (vt == napi_null || vt == napi_undefined) {
+        int rc0 = rz_upload_physics(ctx, NULL);
+        return rc0 ? throw_rz(env, rc0) : undef(env);
+    }
+    if (vt != napi_object) return throw_msg(env, usage);
+    void *bone, *type, *shape, *size, *op, *orot, *mass, *ld, *ad, *res, *fri, *grp, *mask, *ba, *bb, *jv[8], *grav = NULL;
+    size_t nb, nty, nsh, nsz, nop, nor, nm, nld, nad, nre, nfr, ngr, nma, nj, nbb, njv[8], ngrav = 0;
+    static const char *jname[8] = { "position", "rotation", "positionMin", "positionMax", "rotationMin", "rotationMax", "springPosition", "springRotation" };
+    if (!get_prop_ta(env, o, "bone", napi_int32_array, 0, &bone, &nb) || !get_prop_ta(env, o, "type", napi_uint8_array, 0, &type, &nty) ||
+        !get_prop_ta(env, o, "shape", napi_uint8_array, 0, &shape, &nsh) || !get_prop_ta(env, o, "size", napi_float32_array, 0, &size, &nsz) ||
+        !get_prop_ta(env, o, "offsetPos", napi_float32_array, 0, &op, &nop) || !get_prop_ta(env, o, "offsetRot", napi_float32_array, 0, &orot, &nor) ||
+        !get_prop_ta(env, o, "mass", napi_float32_array, 0, &mass, &nm) || !get_prop_ta(env, o, "linearDamping", napi_float32_array, 0, &ld, &nld) ||
+        !get_prop_ta(env, o, "angularDamping", napi_float32_array, 0, &ad, &nad) || !get_prop_ta(env, o, "restitution", napi_float32_array, 0, &res, &nre) ||
+        !get_prop_ta(env, o, "friction", napi_float32_array, 0, &fri, &nfr) || !get_prop_ta(env, o, "group", napi_uint8_array, 0, &grp, &ngr) ||
+        !get_prop_ta(env, o, "mask", napi_uint16_array, 0, &mask, &nma) || !get_prop_ta(env, o, "bodyA", napi_uint32_array, 0, &ba, &nj) ||
+        !get_prop_ta(env, o, "bodyB", napi_uint32_array, 0, &bb, &nbb))
+        return throw_msg(env, usage);
+    for (int k = 0; k < 8; ++k)
+        if (!get_prop_ta(env, o, jname[k], napi_float32_array, 0, &jv[k], &njv[k])) return throw_msg(env, usage);
+    if (nb > 0xffffffffu || nj > 0xffffffffu) return throw_msg(env, "uploadPhysics: too many bodies or joints");
+    if (nty < nb || nsh < nb || nsz < nb * 3 || nop < nb * 3 || nor < nb * 4 || nm < nb || nld < nb || nad < nb || nre < nb || nfr < nb || ngr < nb || nma < nb)
+        return throw_msg(env, "uploadPhysics: the body arrays need one entry per body (size / offsetPos three, offsetRot four)");
+    if (nbb < nj) return throw_msg(env, "uploadPhysics: bodyB is shorter than bodyA");
+    for (int k = 0; k < 8; ++k)
+        if (njv[k] < nj * 3) return throw_msg(env, "uploadPhysics: the joint arrays need three floats per joint");
+    rz_physics t;
+    memset(&t, 0, sizeof t);
+    if (argc > 2) {
+        napi_valuetype ot;
+        if (napi_typeof(env, argv[2], &ot) != napi_ok) return throw_msg(env, usage);
+        if (ot == napi_object) {
+            napi_value v;
+            bool has = false;
+            double d;
+            if (!get_prop_ta(env, argv[2], "gravity", napi_float32_array, 1, &grav, &ngrav) || (grav && ngrav < 3))
+                return throw_msg(env, "uploadPhysics: gravity must be a Float32Array of 3");
+            if (napi_has_named_property(env, argv[2], "h", &has) == napi_ok && has) {
+                if (napi_get_named_property(env, argv[2], "h", &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok) return throw_msg(env, "uploadPhysics: h must be a number");
+                t.h = (float)d;
+            }
+            if (napi_has_named_property(env, argv[2], "iterations", &has) == napi_ok && has) {
+                if (napi_get_named_property(env, argv[2], "iterations", &v) != napi_ok || !get_u32(env, v, &t.iterations)) return throw_msg(env, "uploadPhysics: iterations must be a count");
+            }
+        } else if (ot != napi_null && ot != napi_undefined) return throw_msg(env, usage);
+    }
+    t.n_bodies = (uint32_t)nb; t.bone = (const int32_t *)bone; t.type = (const uint8_t *)type; t.shape = (const uint8_t *)shape;
+    t.size3 = (const float *)size; t.offset_pos3 = (const float *)op; t.offset_rot4 = (const float *)orot; t.mass = (const float *)mass;
+    t.linear_damping = (const float *)ld; t.angular_damping = (const float *)ad; t.restitution = (const float *)res; t.friction = (const float *)fri;
+    t.group = (const uint8_t *)grp; t.mask = (const uint16_t *)mask;
+    t.n_joints = (uint32_t)nj; t.body_a = (const uint32_t *)ba; t.body_b = (const uint32_t *)bb;
+    t.position3 = (const float *)jv[0]; t.rotation3 = (const float *)jv[1]; t.position_min3 = (const float *)jv[2]; t.position_max3 = (const float *)jv[3];
+    t.rotation_min3 = (const float *)jv[4]; t.rotation_max3 = (const float *)jv[5]; t.spring_position3 = (const float *)jv[6]; t.spring_rotation3 = (const float *)jv[7];
+    t.gravity3 = (const float *)grav;
+    int rc = rz_upload_physics(ctx, &t);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* physicsStep(ctx, substeps): rz_physics_step — 0 only re-places the following bodies and re-emits the overrides */
+static napi_value fn_physics_step(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    uint32_t n;
+    if (!get_u32(env, argv[1], &n)) return throw_msg(env, "physicsStep(ctx, substeps)");
+    int rc = rz_physics_step(ctx, n);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+static napi_value fn_physics_reset(napi_env env, napi_callback_info info)
+{
+    ARGS(1);
+    CTX(0);
+    int rc = rz_physics_reset(ctx);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* readPhysics(ctx, instance, Float32Array state13): per body x3 q4 v3 w3 (rz_read_physics); blocking, for tests and tools */
+static napi_value fn_read_physics(napi_env env, napi_callback_info info)
+{
+    ARGS(3);
+    CTX(0);
+    uint32_t inst;
+    void *st;
+    size_t ns;
+    int nb = 0;
+    if (!get_u32(env, argv[1], &inst) || !get_ta(env, argv[2], napi_float32_array, 0, &st, &ns)) return throw_msg(env, "readPhysics(ctx, instance, Float32Array state13)");
+    if (rz_get_tuning(ctx, "physics_bodies", &nb)) return throw_rz(env, RZ_ERR_INVALID);
+    if (ns < (size_t)nb * 13) return throw_msg(env, "readPhysics: state13 must hold 13 floats per body");
+    int rc = rz_read_physics(ctx, inst, (float *)st);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
 static napi_value fn_set_instances(napi_env env, napi_callback_info info)
 {
     ARGS(2);
@@ -1120,6 +1225,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
         { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
+        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "readPhysics", fn_read_physics },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

@@ -1,0 +1,211 @@
+// physics_table.h — the host half of rz_upload_physics that needs no GPU: checking a table, colouring its joints and deriving the constants
+// rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams). Plain C++ on purpose, without HIP: tests/physics_table_main.cpp compiles it
+// alone and holds the colouring to tests/physics_ref.py. Everything is computed in double from the table's floats and rounded once, as
+// physics_ref.prepare does.
+#pragma once
+#include "../../include/reze_deform.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace rzphys {
+
+constexpr double kDefaultH = 1.0 / 75.0;
+constexpr int kDefaultIterations = 4;
+
+struct Built {
+    std::vector<float> body;            // [nb][16]
+    std::vector<float> joint;           // [nj][32], in solve order
+    std::vector<int> colour, order, colour_off;
+    std::vector<int> dyn_bone;          // bones of the dynamic bodies that have one, in body order: an instance's overrides
+    int nb = 0, nj = 0, ncol = 0, nd = 0, widest = 0, iterations = kDefaultIterations;
+    float h = (float)kDefaultH, g[3] = { 0.0f, -98.0f, 0.0f };
+};
+
+inline bool dynamic(const rz_physics *t, uint32_t b) { return t->type[b] == 1 && t->mass[b] > 0.0f; }
+
+inline bool finite_all(const float *p, size_t n)
+{
+    if (!p) return true;
+    for (size_t k = 0; k < n; ++k)
+        if (!std::isfinite(p[k])) return false;
+    return true;
+}
+
+// RZ_ERR_INVALID cases of rz_upload_physics; an empty string = the table is valid
+inline std::string validate(const rz_physics *t, uint32_t B)
+{
+    char m[200];
+    const uint32_t nb = t->n_bodies, nj = t->n_joints;
+    if (!t->bone || !t->type || !t->shape || !t->size3 || !t->offset_pos3 || !t->offset_rot4 || !t->mass || !t->linear_damping || !t->angular_damping)
+        return "physics table: null body arrays";
+    if (nj && (!t->body_a || !t->body_b || !t->position3 || !t->rotation3 || !t->position_min3 || !t->position_max3 || !t->rotation_min3 || !t->rotation_max3 || !t->spring_rotation3))
+        return "physics table: null joint arrays";
+    const struct { const char *name; const float *p; size_t n; } fl[] = {
+        { "size", t->size3, (size_t)nb * 3 }, { "offset_pos", t->offset_pos3, (size_t)nb * 3 }, { "offset_rot", t->offset_rot4, (size_t)nb * 4 },
+        { "mass", t->mass, nb }, { "linear_damping", t->linear_damping, nb }, { "angular_damping", t->angular_damping, nb },
+        { "restitution", t->restitution, nb }, { "friction", t->friction, nb },
+        { "position", t->position3, (size_t)nj * 3 }, { "rotation", t->rotation3, (size_t)nj * 3 },
+        { "position_min", t->position_min3, (size_t)nj * 3 }, { "position_max", t->position_max3, (size_t)nj * 3 },
+        { "rotation_min", t->rotation_min3, (size_t)nj * 3 }, { "rotation_max", t->rotation_max3, (size_t)nj * 3 },
+        { "spring_position", t->spring_position3, (size_t)nj * 3 }, { "spring_rotation", t->spring_rotation3, (size_t)nj * 3 },
+        { "gravity", t->gravity3, 3 }, { "h", &t->h, 1 } };
+    for (const auto &f : fl)
+        if (!finite_all(f.p, f.n)) { snprintf(m, sizeof m, "physics table: %s is not finite", f.name); return m; }
+    if (t->h < 0.0f) return "physics table: h must be > 0 (0 = the default 1/75 s)";
+    for (uint32_t b = 0; b < nb; ++b) {
+        if (t->bone[b] < -1 || t->bone[b] >= (int32_t)B) { snprintf(m, sizeof m, "physics table: body %u names bone %d (have %u)", b, t->bone[b], B); return m; }
+        if (t->type[b] > 2) { snprintf(m, sizeof m, "physics table: body %u has type %u (0 follows its bone, 1 dynamic, 2 dynamic + bone)", b, (unsigned)t->type[b]); return m; }
+        if (t->shape[b] > 2) { snprintf(m, sizeof m, "physics table: body %u has shape %u (0 sphere, 1 box, 2 capsule)", b, (unsigned)t->shape[b]); return m; }
+        if (t->mass[b] < 0.0f) { snprintf(m, sizeof m, "physics table: body %u has a negative mass", b); return m; }
+        if (t->linear_damping[b] < 0.0f || t->linear_damping[b] > 1.0f || t->angular_damping[b] < 0.0f || t->angular_damping[b] > 1.0f) {
+            snprintf(m, sizeof m, "physics table: body %u has a damping outside [0, 1]", b); return m;
+        }
+        const float *q = t->offset_rot4 + (size_t)b * 4;
+        if (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] <= 0.0f) { snprintf(m, sizeof m, "physics table: body %u has a zero offset rotation", b); return m; }
+    }
+    for (uint32_t j = 0; j < nj; ++j) {
+        if (t->body_a[j] >= nb || t->body_b[j] >= nb) { snprintf(m, sizeof m, "physics table: joint %u names bodies %u and %u (have %u)", j, t->body_a[j], t->body_b[j], nb); return m; }
+        if (t->body_a[j] == t->body_b[j]) { snprintf(m, sizeof m, "physics table: joint %u joins body %u to itself", j, t->body_a[j]); return m; }
+    }
+    std::vector<int> owner(B, -1);
+    for (uint32_t b = 0; b < nb; ++b)
+        if (dynamic(t, b) && t->bone[b] >= 0) {
+            if (owner[t->bone[b]] >= 0) { snprintf(m, sizeof m, "physics table: dynamic bodies %d and %u both drive bone %d", owner[t->bone[b]], b, t->bone[b]); return m; }
+            owner[t->bone[b]] = (int)b;
+        }
+    return "";
+}
+
+// Greedy, in file order: a joint takes the smallest colour in which no earlier joint shares a dynamic body with it
+inline void colour_joints(const rz_physics *t, std::vector<int> &colour, std::vector<int> &order, int &ncol)
+{
+    const uint32_t nb = t->n_bodies, nj = t->n_joints;
+    std::vector<std::vector<char>> used(nb);
+    colour.assign(nj, 0);
+    ncol = 0;
+    for (uint32_t j = 0; j < nj; ++j) {
+        const uint32_t ends[2] = { t->body_a[j], t->body_b[j] };
+        int c = 0;
+        for (;; ++c) {
+            bool taken = false;
+            for (uint32_t b : ends)
+                if (dynamic(t, b) && (size_t)c < used[b].size() && used[b][c]) taken = true;
+            if (!taken) break;
+        }
+        for (uint32_t b : ends)
+            if (dynamic(t, b)) { if (used[b].size() <= (size_t)c) used[b].resize(c + 1, 0); used[b][c] = 1; }
+        colour[j] = c;
+        ncol = std::max(ncol, c + 1);
+    }
+    order.resize(nj);
+    for (uint32_t j = 0; j < nj; ++j) order[j] = (int)j;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return colour[a] < colour[b]; });
+}
+
+struct D3 { double x, y, z; };
+struct D4 { double x, y, z, w; };
+inline D3 cross(D3 a, D3 b) { return { a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
+inline D4 qmul(D4 a, D4 b)
+{
+    return { a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
+             a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z };
+}
+inline D4 qconj(D4 a) { return { -a.x, -a.y, -a.z, a.w }; }
+inline D4 qnorm(D4 a) { const double l = std::sqrt(a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w); return { a.x / l, a.y / l, a.z / l, a.w / l }; }
+inline D3 qrot(D4 q, D3 v)
+{
+    const D3 u = { q.x, q.y, q.z };
+    D3 t = cross(u, v);
+    t = { t.x + t.x, t.y + t.y, t.z + t.z };
+    const D3 c = cross(u, t);
+    return { v.x + q.w * t.x + c.x, v.y + q.w * t.y + c.y, v.z + q.w * t.z + c.z };
+}
+// math.ts Quat.fromEuler: how the loader's Euler angles become quaternions
+inline D4 quat_from_pmx_euler(const float *r)
+{
+    const double cx = std::cos(r[0] * 0.5), sx = std::sin(r[0] * 0.5), cy = std::cos(r[1] * 0.5), sy = std::sin(r[1] * 0.5), cz = std::cos(r[2] * 0.5), sz = std::sin(r[2] * 0.5);
+    return qnorm({ cy * sx * cz + sy * cx * sz, sy * cx * cz - cy * sx * sz, cy * cx * sz - sy * sx * cz, cy * cx * cz + sy * sx * sz });
+}
+inline float bits_of(int32_t v) { float f; memcpy(&f, &v, 4); return f; }
+
+// parents[B] (-1 = root) and bind_translation3[B * 3]: the topology the hierarchy solve was given; the bind pose of a body is
+// T(sum of the bind translations up its bone's parent chain) x offset
+inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const float *bind3, Built &o)
+{
+    const uint32_t nb = t->n_bodies, nj = t->n_joints;
+    o.nb = (int)nb; o.nj = (int)nj;
+    const double h = t->h > 0.0f ? (double)t->h : kDefaultH;
+    o.h = (float)h;
+    o.iterations = t->iterations ? (int)t->iterations : kDefaultIterations;
+    if (t->gravity3) for (int k = 0; k < 3; ++k) o.g[k] = t->gravity3[k];
+    colour_joints(t, o.colour, o.order, o.ncol);
+    o.colour_off.assign(o.ncol + 1, 0);
+    for (uint32_t j = 0; j < nj; ++j) o.colour_off[o.colour[j] + 1]++;
+    o.widest = 0;
+    for (int c = 0; c < o.ncol; ++c) { o.widest = std::max(o.widest, o.colour_off[c + 1]); o.colour_off[c + 1] += o.colour_off[c]; }
+    std::vector<D3> bx(nb);
+    std::vector<D4> bq(nb);
+    o.body.assign((size_t)nb * 16, 0.0f);
+    o.dyn_bone.clear();
+    for (uint32_t b = 0; b < nb; ++b) {
+        D3 acc = { 0, 0, 0 };
+        uint32_t guard = 0;
+        for (int32_t p = t->bone[b]; p >= 0 && guard <= B; p = parents[p], ++guard) { acc.x += bind3[p * 3]; acc.y += bind3[p * 3 + 1]; acc.z += bind3[p * 3 + 2]; }
+        const float *op = t->offset_pos3 + (size_t)b * 3, *oq = t->offset_rot4 + (size_t)b * 4, *sz = t->size3 + (size_t)b * 3;
+        bx[b] = { acc.x + op[0], acc.y + op[1], acc.z + op[2] };
+        bq[b] = qnorm({ oq[0], oq[1], oq[2], oq[3] });
+        const bool dyn = dynamic(t, b);
+        const double m = t->mass[b];
+        double I[3] = { 0, 0, 0 };
+        if (dyn) {
+            if (t->shape[b] == 0) I[0] = I[1] = I[2] = 0.4 * m * sz[0] * sz[0];
+            else {
+                const double a = sz[0], bb = t->shape[b] == 1 ? sz[1] : sz[0] + 0.5 * sz[1], c = t->shape[b] == 1 ? sz[2] : sz[0];
+                I[0] = m / 3.0 * (bb * bb + c * c); I[1] = m / 3.0 * (a * a + c * c); I[2] = m / 3.0 * (a * a + bb * bb);
+            }
+        }
+        int slot = -1;
+        if (dyn && t->bone[b] >= 0) { slot = (int)o.dyn_bone.size(); o.dyn_bone.push_back(t->bone[b]); }
+        float *r = o.body.data() + (size_t)b * 16;
+        r[0] = op[0]; r[1] = op[1]; r[2] = op[2]; r[3] = dyn ? (float)(1.0 / m) : 0.0f;
+        r[4] = (float)bq[b].x; r[5] = (float)bq[b].y; r[6] = (float)bq[b].z; r[7] = (float)bq[b].w;
+        for (int k = 0; k < 3; ++k) r[8 + k] = I[k] > 0 ? (float)(1.0 / I[k]) : 0.0f;
+        r[11] = (float)std::pow(1.0 - (double)t->linear_damping[b], h);
+        r[12] = (float)std::pow(1.0 - (double)t->angular_damping[b], h);
+        r[13] = bits_of(t->bone[b]); r[14] = bits_of(slot); r[15] = 0.0f;
+    }
+    o.nd = (int)o.dyn_bone.size();
+    o.joint.assign((size_t)nj * 32, 0.0f);
+    for (uint32_t k = 0; k < nj; ++k) {
+        const uint32_t j = (uint32_t)o.order[k], a = t->body_a[j], b = t->body_b[j];
+        const D4 jq = quat_from_pmx_euler(t->rotation3 + (size_t)j * 3);
+        const float *jp = t->position3 + (size_t)j * 3;
+        const D3 ra = qrot(qconj(bq[a]), { jp[0] - bx[a].x, jp[1] - bx[a].y, jp[2] - bx[a].z });
+        const D3 rb = qrot(qconj(bq[b]), { jp[0] - bx[b].x, jp[1] - bx[b].y, jp[2] - bx[b].z });
+        const D4 ja = qmul(qconj(bq[a]), jq), jb = qmul(qconj(bq[b]), jq);
+        float *r = o.joint.data() + (size_t)k * 32;
+        r[0] = (float)ra.x; r[1] = (float)ra.y; r[2] = (float)ra.z; r[3] = bits_of((int32_t)a);
+        r[4] = (float)rb.x; r[5] = (float)rb.y; r[6] = (float)rb.z; r[7] = bits_of((int32_t)b);
+        r[8] = (float)ja.x; r[9] = (float)ja.y; r[10] = (float)ja.z; r[11] = (float)ja.w;
+        r[12] = (float)jb.x; r[13] = (float)jb.y; r[14] = (float)jb.z; r[15] = (float)jb.w;
+        int32_t springs = 0;
+        for (int ax = 0; ax < 3; ++ax) {
+            const float pl = t->position_min3[j * 3 + ax], ph = t->position_max3[j * 3 + ax], rl = t->rotation_min3[j * 3 + ax], rh = t->rotation_max3[j * 3 + ax];
+            r[16 + ax] = std::min(pl, ph); r[20 + ax] = std::max(pl, ph);
+            r[24 + ax] = std::min(rl, rh); r[28 + ax] = std::max(rl, rh);
+            const double ks = t->spring_rotation3[j * 3 + ax];
+            if (ks > 0) { springs |= 1 << ax; r[19 + 4 * ax] = (float)(1.0 / (ks * h * h)); }
+        }
+        r[31] = bits_of(springs);
+    }
+}
+
+}  // namespace rzphys
+#pragma GCC visibility pop

@@ -707,6 +707,7 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
 int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16)
 {
     if (int r = use(c)) return r;
+    if (c->ph_nb) return fail(RZ_ERR_INVALID, "rz_override_world while a physics table is resident: rz_physics_step writes the override table (remove the table with rz_upload_physics(ctx, NULL) first)");
     if (n == 0) { c->ovr_count = 0; return RZ_OK; }
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_override_world applies to device-solved poses: call rz_upload_skeleton_topology first");
     if (!bone || !world16) return fail(RZ_ERR_INVALID, "null override arrays");

@@ -263,6 +263,9 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "qdef_chunks")) *value = c->t_qdefchunks;
     else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
     else if (!strcmp(key, "motion_clips")) *value = (int)c->mo_clips;
+    else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph_nb;
+    else if (!strcmp(key, "physics_joints")) *value = (int)c->ph_nj;
+    else if (!strcmp(key, "physics_colours")) *value = (int)c->ph_ncol;
     else if (!strcmp(key, "nt_store")) *value = c->t_nts;
     else if (!strcmp(key, "fast")) *value = c->t_fast;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;

@@ -165,6 +165,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     c->fk_stale = false; c->subfk_valid = false;
     free_bone_morphs(c);                // ... as do bone morphs (their entries name its bones)
     free_ik(c);                         // ... and the IK table (its chains name its bones)
+    free_physics(c);                    // ... and the physics table (its bodies name its bones)
     free_animation(c);                  // ... and so does an uploaded motion (its tracks name bones of that skeleton)
     free_motions(c);                    // ... and the motion library
     return ensure_pose_buffers(c);
@@ -262,6 +263,7 @@ int rz_set_instances(rz_ctx *c, uint32_t I)
         drop_graph(c);
         c->aabb_rearm = true;
         c->ovr_count = 0;                 // overrides name (instance, bone) pairs of the old crowd
+        c->ph_reset = true;               // (a physics table rebuilds its per-instance state and the overrides at its next step)
         // The host-compacted active-morph list is only maintained while I == 1 (upload_pose). Coming back to one instance
         // from a crowd it is stale (zeroed): let the prep kernel compact instance 0's weights, which are still on the device.
         if (c->M > 0 && c->morph_mode == 1) c->ml.count = -1;
@@ -329,6 +331,7 @@ int rz_upload_skeleton_topology(rz_ctx *c, uint32_t B, const int32_t *parents, c
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
     free_ik(c);                         // its chains were checked against the old parents
+    free_physics(c);                    // its bind pose was taken from the old hierarchy
     c->ovr_count = 0;
     c->fk_stale = false;                // (a crowd frame solved under the old topology: nothing of it can be formed on demand any more)
     dfree(c->fk_anc_more);

@@ -28,6 +28,8 @@ try {
 } catch (e) {
   wallClock = () => Date.now()
 }
+// the reference's fixedTimeStep and maxSubSteps (physics.ts:534-569); h = 0 in the upload selects the same 1/75 s on the device
+const PHYSICS_H = 1 / 75, PHYSICS_MAX_SUBSTEPS = 10
 
 class Engine {
   constructor(canvas, options) {
@@ -60,6 +62,13 @@ class Engine {
     // itself (Bullet via @fred3d/ammo) is out of scope — this is only the seam it plugs into.
     this.physics = o.physics || null
     this.lastPhysicsTime = null
+    // devicePhysics: the model's PMX rigid bodies and joints simulated on the GPU (rz_upload_physics / rz_physics_step), which writes the
+    // override table there. It acts on device-solved poses only, and a host { physics } would fight it over the same bones.
+    this.devicePhysics = o.devicePhysics === true
+    if (this.devicePhysics && !this.deviceFK) throw new Error('devicePhysics needs new Engine(canvas, { deviceFK: true }); with host FK pass { physics }')
+    if (this.devicePhysics && this.physics) throw new Error('devicePhysics and { physics } are exclusive: both would write the physics-driven bones')
+    this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
+    this.physicsResident = false
     this.native = null
     // deviceSampling (needs deviceFK): seekFrame() sends one float — the frame — and the motion is sampled on the GPU
     this.deviceSampling = o.deviceSampling === true && o.deviceFK === true
@@ -107,6 +116,7 @@ class Engine {
   /** engine.ts:157-185: acquire the device. Throws when the addon or an MI355X is not available. */
   async init() {
     if (this.framesInFlight === 2 && (this.devices.length > 1 || this.gather)) throw new Error('framesInFlight: 2 needs a single GPU and no gather')
+    if (this.framesInFlight === 2 && this.devicePhysics) throw new Error('devicePhysics steps one context: it cannot run with framesInFlight: 2 (rz_physics_step is refused while forks exist)')
     this.native = requireAddon()
     this.shards = this.devices.map((d) => ({ ctx: this.native.create(d), begin: 0, count: 0, fork: null, last: null, flip: 0 }))
     this.ctx = this.shards[0].ctx
@@ -192,6 +202,8 @@ class Engine {
     const morphs = model.getMorphs()
     const V = model.getVertexCount()
     const G = this.shards.length
+    const tables = this.devicePhysics ? model.physicsTables() : null
+    this.physicsResident = false
     for (let r = 0; r < G; r++) {
       const s = this.shards[r]
       const range = n.shardRange(V, G, r)
@@ -235,6 +247,8 @@ class Engine {
           })
           n.uploadIK(s.ctx, goal, eff, loops, theta, off, lb, ll, lmin, lmax)
         }
+        // so is physics: every shard simulates the same bodies (the solve is deterministic), so no shard waits for another's overrides
+        if (tables && tables.nBodies > 0) { n.uploadPhysics(s.ctx, tables); this.physicsResident = true }
       }
       if (morphs && morphs.names.length > 0) {
         const M = morphs.names.length
@@ -305,6 +319,8 @@ class Engine {
     if (this.gather === 'direct' && G > 1) n.gatherDirect(this.shards.map((s) => s.ctx), V, 0)
     else if (this.gather && G > 1) n.commInitAll(this.shards.map((s) => s.ctx), V)
     this.tuned = false
+    this.physicsAccumulator = 0
+    this.lastPhysicsTime = this.physicsResident ? this.now() : null
     this.outPos = new Float32Array(V * 3)
     this.outNrm = new Float32Array(V * 3)
     this.stats.gpuMemory = Math.round(((V * 60 + skeleton.bones.length * 176 +
@@ -428,6 +444,30 @@ class Engine {
   }
 
   // ---- per frame ----
+  /**
+   * { devicePhysics }: the fixed substeps this frame owes (physics.ts:534-569 hands Bullet the frame's dt with fixedTimeStep 1/75 and
+   * maxSubSteps 10): the time the clock advanced since the last frame joins the accumulator, min(10, floor(acc / h)) substeps leave it.
+   * What the cap leaves over is dropped, as Bullet drops it, so a long stall does not come back as a burst. -1: no table resident.
+   */
+  physicsSubsteps() {
+    if (!this.physicsResident) return -1
+    const now = this.now()
+    if (this.lastPhysicsTime !== null && now > this.lastPhysicsTime) this.physicsAccumulator += (now - this.lastPhysicsTime) / 1000
+    this.lastPhysicsTime = now
+    const owed = Math.floor(this.physicsAccumulator / PHYSICS_H)
+    this.physicsAccumulator -= owed * PHYSICS_H
+    return Math.min(PHYSICS_MAX_SUBSTEPS, owed)
+  }
+
+  /** Every body back onto its bone's solved pose with zero velocities (rz_physics_reset); the accumulated time is dropped. */
+  resetPhysics() {
+    if (!this.devicePhysics) throw new Error('resetPhysics needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
+    if (!this.physicsResident) return
+    for (const s of this.shards) if (s.count > 0) this.native.physicsReset(s.ctx)
+    this.physicsAccumulator = 0
+    this.lastPhysicsTime = this.now()
+  }
+
   /** engine.ts:2124-2136 + 2375-2402 minus the draw calls: pose on the CPU, deformation on the GPU. */
   render() {
     if (!this.currentModel || !this.ctx) return
@@ -445,12 +485,14 @@ class Engine {
       this.physics.step(dt, model.getBoneWorldMatrices(), model.getBoneInverseBindMatrices())
     }
     const mw = model.getMorphCount() > 0 ? model.getEffectiveMorphWeights() : null
+    const substeps = this.physicsSubsteps()
     // per-frame inputs are replicated to every shard (16-22 KB); launches are asynchronous, so the GPUs run concurrently
     for (const s of this.shards) {
       if (s.count === 0) continue
       const c = this.frameContext(s)
       if (gpuFK) this.native.setPoseLocal(c, model.runtimeSkeleton.localRotations, mw, tra)
       else this.native.setPose(c, model.getBoneWorldMatrices(), mw)
+      if (substeps >= 0) this.native.physicsStep(c, substeps) // 0 still re-places the following bodies on the new pose
       this.native.deform(c)
     }
     if (this.autotune && !this.tuned) { // the first frame supplied a pose: time the candidate launch shapes once per shard
@@ -492,10 +534,12 @@ class Engine {
     // a crowd (setInstanceCount) takes one frame per instance; a single number poses every instance at that frame
     const f = typeof frame === 'number' ? new Float32Array(this.instances).fill(frame) : Float32Array.from(frame)
     if (f.length !== this.instances) throw new Error('seekFrame: ' + f.length + ' frames for ' + this.instances + ' instances')
+    const substeps = this.physicsSubsteps()
     for (const s of this.shards) {
       if (s.count === 0) continue
       const c = this.frameContext(s)
       this.native.setPoseSampled(c, f)
+      if (substeps >= 0) this.native.physicsStep(c, substeps)
       this.native.deform(c)
     }
     if (this.autotune && !this.tuned) { // as in render(): the first frame supplied a pose
@@ -557,10 +601,12 @@ class Engine {
       dv.setFloat32(i * 20 + 12, hasB && st.frameB !== undefined ? st.frameB : 0, true)
       dv.setFloat32(i * 20 + 16, hasB && st.blend !== undefined ? st.blend : 0, true)
     })
+    const substeps = this.physicsSubsteps()
     for (const s of this.shards) {
       if (s.count === 0) continue
       const c = this.frameContext(s)
       this.native.setPoseBlended(c, buf)
+      if (substeps >= 0) this.native.physicsStep(c, substeps)
       this.native.deform(c)
     }
     if (this.autotune && !this.tuned) { // as in render(): the first frame supplied a pose
@@ -582,6 +628,7 @@ class Engine {
   setBoneWorldOverrides(boneIndices, worldMatrices, instances) {
     if (!this.ctx) throw new Error('Engine.init() has not been called')
     if (!this.deviceFK) throw new Error('setBoneWorldOverrides needs new Engine(canvas, { deviceFK: true }); with host FK pass { physics }')
+    if (this.physicsResident) throw new Error('setBoneWorldOverrides: with { devicePhysics } the physics table owns the bone overrides')
     const b = boneIndices && boneIndices.length ? Uint32Array.from(boneIndices) : null
     const w = b ? (worldMatrices instanceof Float32Array ? worldMatrices : Float32Array.from(worldMatrices)) : null
     const i = b && instances ? Uint32Array.from(instances) : null

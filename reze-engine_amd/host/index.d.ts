@@ -46,6 +46,7 @@ export interface EngineOptions {
   /** false: time only advances through step(timeMs). */ realtime?: boolean
   /** Physics hand-off (engine.ts:2379-2381), host-FK frames: step() may overwrite world matrices in place before they are uploaded. */
   physics?: { step(dt: number, boneWorldMatrices: Float32Array, boneInverseBindMatrices: Float32Array): void }
+  /** Rigid-body physics on the GPU for the model's PMX bodies and joints (needs deviceFK; exclusive with `physics` and framesInFlight: 2). loadModel uploads Model.physicsTables() (rz_upload_physics); every frame turns the time the clock advanced since the last one into min(10, floor(accumulated / h)) fixed substeps of h = 1/75 s (rz_physics_step) before it deforms. No collisions, friction, linear springs or restitution. */ devicePhysics?: boolean
 }
 export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
 export interface EngineStats {
@@ -76,6 +77,8 @@ export class Engine {
   setInstanceCount(n: number): void
   /** Physics hand-off with { deviceFK }: world matrices (column-major 4x4 each) that replace the GPU-solved ones of the listed bones until the next call. */
   setBoneWorldOverrides(boneIndices: ArrayLike<number>, worldMatrices: ArrayLike<number>, instances?: ArrayLike<number>): void
+  /** With { devicePhysics }: every body back onto its bone's solved pose with zero velocities (rz_physics_reset); the accumulated time is dropped. */
+  resetPhysics(): void
   getDeformed(instance?: number): { positions: Float32Array; normals: Float32Array }
   getOutlineHull(): Float32Array
   getBounds(): { min: number[]; max: number[] }

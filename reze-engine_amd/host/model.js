@@ -140,6 +140,45 @@ class Model {
   getQdef() { return this.qdef }
   getRigidbodies() { return this.rigidbodies }
   getJoints() { return this.joints }
+
+  /*
+   * The flat arrays rz_upload_physics takes. A body's frame in its bone's space is offset = inverseBind x T(shapePosition) R(shapeRotation)
+   * (physics.ts:572-596), Euler angles -> quaternion with Quat.fromEuler as the reference does; the loader's inverse binds are pure
+   * translations, so the rotation of the offset is the shape's. A body without a bone (-1) keeps its model-space frame.
+   */
+  physicsTables() {
+    const rb = this.rigidbodies, jt = this.joints, nb = rb.length, nj = jt.length
+    const ib = this.skeleton.inverseBindMatrices, B = this.skeleton.bones.length
+    const t = {
+      nBodies: nb, bone: new Int32Array(nb), type: new Uint8Array(nb), shape: new Uint8Array(nb), size: new Float32Array(nb * 3),
+      offsetPos: new Float32Array(nb * 3), offsetRot: new Float32Array(nb * 4), mass: new Float32Array(nb), linearDamping: new Float32Array(nb),
+      angularDamping: new Float32Array(nb), restitution: new Float32Array(nb), friction: new Float32Array(nb), group: new Uint8Array(nb),
+      mask: new Uint16Array(nb), nJoints: nj, bodyA: new Uint32Array(nj), bodyB: new Uint32Array(nj), position: new Float32Array(nj * 3),
+      rotation: new Float32Array(nj * 3), positionMin: new Float32Array(nj * 3), positionMax: new Float32Array(nj * 3),
+      rotationMin: new Float32Array(nj * 3), rotationMax: new Float32Array(nj * 3), springPosition: new Float32Array(nj * 3),
+      springRotation: new Float32Array(nj * 3),
+    }
+    for (let i = 0; i < nb; i++) {
+      const b = rb[i]
+      const bone = b.boneIndex >= 0 && b.boneIndex < B ? b.boneIndex : -1
+      t.bone[i] = bone; t.type[i] = b.type; t.shape[i] = b.shape; t.group[i] = b.group; t.mask[i] = b.collisionMask
+      t.size.set([b.size.x, b.size.y, b.size.z], i * 3)
+      const o = bone >= 0 ? bone * 16 + 12 : -1
+      t.offsetPos.set([b.shapePosition.x + (o >= 0 ? ib[o] : 0), b.shapePosition.y + (o >= 0 ? ib[o + 1] : 0), b.shapePosition.z + (o >= 0 ? ib[o + 2] : 0)], i * 3)
+      const q = Quat.fromEuler(b.shapeRotation.x, b.shapeRotation.y, b.shapeRotation.z)
+      t.offsetRot.set([q.x, q.y, q.z, q.w], i * 4)
+      t.mass[i] = b.mass; t.linearDamping[i] = b.linearDamping; t.angularDamping[i] = b.angularDamping
+      t.restitution[i] = b.restitution; t.friction[i] = b.friction
+    }
+    for (let j = 0; j < nj; j++) {
+      const s = jt[j]
+      t.bodyA[j] = s.rigidbodyIndexA; t.bodyB[j] = s.rigidbodyIndexB
+      const src = [s.position, s.rotation, s.positionMin, s.positionMax, s.rotationMin, s.rotationMax, s.springPosition, s.springRotation]
+      const dst = [t.position, t.rotation, t.positionMin, t.positionMax, t.rotationMin, t.rotationMax, t.springPosition, t.springRotation]
+      for (let k = 0; k < 8; k++) dst[k].set([src[k].x, src[k].y, src[k].z], j * 3)
+    }
+    return t
+  }
   getBoneNames() { return this.skeleton.bones.map((b) => b.name) }
   getBoneWorldMatrices() { return this.runtimeSkeleton.worldMatrices }
   getBoneInverseBindMatrices() { return this.skeleton.inverseBindMatrices }

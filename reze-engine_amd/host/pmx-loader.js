@@ -79,7 +79,8 @@ class PmxLoader {
     const materials = this.guard('materials', () => this.materials(), [])
     const bones = this.guard('bones', () => this.bones(), [])
     const morphs = this.guard('morphs', () => this.morphs(geo.count, bones.length), null)
-    let rigidbodies = [], joints = []
+    let rigidbodies = []
+    let joints = []
     if (morphs !== null && this.guard('display frames', () => this.displayFrames(), false)) {
       rigidbodies = this.guard('rigidbodies', () => this.rigidbodies(), [])
       joints = this.guard('joints', () => this.joints(), [])

@@ -22,7 +22,7 @@ import { TextDecoder } from 'util'
 import { Model } from './model'
 import { Mat4, Vec3 } from './math'
 
-import type { Bone, IKLink, Material, MorphSet, SdefTable, Texture, Triple } from './types'
+import type { Bone, IKLink, Joint, Material, MorphSet, Rigidbody, SdefTable, Texture, Triple } from './types'
 interface PmxHeader { version: number; encoding: number; extraVec4: number; vertexIndexSize: number; textureIndexSize: number; materialIndexSize: number; boneIndexSize: number; morphIndexSize: number; rigidBodyIndexSize: number }
 interface Geometry { count: number; pos: Float32Array; nrm: Float32Array; uv: Float32Array; joints: Uint16Array; weights: Uint8Array; sdef: SdefTable; qdef: Uint32Array }
 class Cursor {
@@ -90,7 +90,8 @@ class PmxLoader {
     const materials = this.guard('materials', () => this.materials(), [])
     const bones = this.guard('bones', () => this.bones(), [])
     const morphs = this.guard('morphs', () => this.morphs(geo.count, bones.length), null)
-    let rigidbodies = [], joints = []
+    let rigidbodies: Rigidbody[] = []
+    let joints: Joint[] = []
     if (morphs !== null && this.guard('display frames', () => this.displayFrames(), false)) {
       rigidbodies = this.guard('rigidbodies', () => this.rigidbodies(), [])
       joints = this.guard('joints', () => this.joints(), [])
@@ -343,7 +344,7 @@ class PmxLoader {
     return true
   }
 
-  rigidbodies(): unknown[] {
+  rigidbodies(): Rigidbody[] {
     const c = this.cur
     const n = c.i32()
     if (n < 0 || n > 10000) throw new RangeError('Suspicious rigidbody count: ' + n)
@@ -364,7 +365,7 @@ class PmxLoader {
     return out
   }
 
-  joints(): unknown[] {
+  joints(): Joint[] {
     const c = this.cur, rs = this.h.rigidBodyIndexSize
     const n = c.i32()
     if (n < 0 || n > 10000) throw new RangeError('Suspicious joint count: ' + n)
@@ -439,7 +440,7 @@ class PmxLoader {
     }
   }
 
-  toModel(geo: Geometry, indices: Uint32Array, textures: Texture[], materials: Material[], bones: Bone[], morphs: MorphSet | null, rigidbodies: unknown[], joints: unknown[]): Model {
+  toModel(geo: Geometry, indices: Uint32Array, textures: Texture[], materials: Material[], bones: Bone[], morphs: MorphSet | null, rigidbodies: Rigidbody[], joints: Joint[]): Model {
     const n = geo.count
     const vertexData = new Float32Array(n * 8)
     for (let v = 0; v < n; v++) {

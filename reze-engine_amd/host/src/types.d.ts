@@ -4,7 +4,7 @@
  * (engine/src/model.ts:6-68, vmd-loader.ts:4-24) plus what this build adds: morph sets, the flattened motion of the device sampler and
  * the raw N-API addon (csrc/napi_addon.c over include/reze_deform.h).
  */
-import type { Quat, Vec3 } from './math'
+import type { Mat4, Quat, Vec3 } from './math'
 
 export type NumArray = Float32Array | number[]
 export type Quad = [number, number, number, number]
@@ -108,6 +108,10 @@ export interface DeformAddon {
   uploadIK(ctx: DeformContext, goal: Uint32Array | null, effector: Uint32Array | null, loops: Uint32Array | null, limitAngle: Float32Array | null, linkOff: Uint32Array | null, linkBone: Uint32Array | null, linkLimited: Uint8Array | null, linkMin3: Float32Array | null, linkMax3: Float32Array | null): void
   uploadSdef(ctx: DeformContext, index: Uint32Array | null, c3: Float32Array | null, r0_3: Float32Array | null, r1_3: Float32Array | null): void
   uploadQdef(ctx: DeformContext, index: Uint32Array | null): void
+  uploadPhysics(ctx: DeformContext, tables: PhysicsTables | null, options?: { gravity?: Float32Array; h?: number; iterations?: number } | null): void
+  physicsStep(ctx: DeformContext, substeps: number): void
+  physicsReset(ctx: DeformContext): void
+  readPhysics(ctx: DeformContext, instance: number, state13: Float32Array): void
   enableAabb(ctx: DeformContext, on: boolean): void
   setInstances(ctx: DeformContext, count: number): void
   setPose(ctx: DeformContext, world: Float32Array, morphWeights: Float32Array | null): void
@@ -139,13 +143,34 @@ export interface DeformAddon {
   gatherFence(root: DeformContext): void
 }
 
+// PMX rigid bodies and joints as the loader reads them (pmx-loader.ts: rigidbodies(), joints())
+export interface Rigidbody {
+  name: string; englishName: string; boneIndex: number; group: number; collisionMask: number; shape: number
+  size: Vec3; shapePosition: Vec3; shapeRotation: Vec3
+  mass: number; linearDamping: number; angularDamping: number; restitution: number; friction: number; type: number
+  bodyOffsetMatrixInverse: Mat4
+}
+export interface Joint {
+  name: string; englishName: string; type: number; rigidbodyIndexA: number; rigidbodyIndexB: number
+  position: Vec3; rotation: Vec3; positionMin: Vec3; positionMax: Vec3; rotationMin: Vec3; rotationMax: Vec3
+  springPosition: Vec3; springRotation: Vec3
+}
+// the flat arrays rz_upload_physics takes (Model.physicsTables()): offsets = inverseBind x T(shapePosition) R(shapeRotation)
+export interface PhysicsTables {
+  nBodies: number; bone: Int32Array; type: Uint8Array; shape: Uint8Array; size: Float32Array; offsetPos: Float32Array; offsetRot: Float32Array
+  mass: Float32Array; linearDamping: Float32Array; angularDamping: Float32Array; restitution: Float32Array; friction: Float32Array
+  group: Uint8Array; mask: Uint16Array
+  nJoints: number; bodyA: Uint32Array; bodyB: Uint32Array; position: Float32Array; rotation: Float32Array
+  positionMin: Float32Array; positionMax: Float32Array; rotationMin: Float32Array; rotationMax: Float32Array
+  springPosition: Float32Array; springRotation: Float32Array
+}
 /** the reference Physics' seam (engine.ts:2379-2381): may overwrite world matrices in place */
 export interface PhysicsLike { step(dt: number, worldMatrices: Float32Array, inverseBindMatrices: Float32Array): void }
 export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }

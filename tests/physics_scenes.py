@@ -1,0 +1,311 @@
+"""Synthetic skeletons with rigid-body tables for the physics tests (tests/test_physics_cpu.py, tests/test_gpu_physics.py): strands of
+dynamic bodies hanging from bodies that follow their bones, as hair, ribbons and skirts are rigged in PMX models. Every scene the GPU tests
+use is listed in SCENES and checked for conditioning on the CPU (test_physics_cpu.py: test_scenes_are_well_conditioned)."""
+import numpy as np
+
+import ik_ref
+import physics_ref
+
+PI = float(np.pi)
+FREE_MIN, FREE_MAX = (-PI, -PI / 2, -PI), (PI, PI / 2, PI)
+
+
+def _quat(axis, ang):
+    axis = np.asarray(axis, dtype=np.float64)
+    axis = axis / np.linalg.norm(axis)
+    return np.concatenate([axis * np.sin(ang / 2), [np.cos(ang / 2)]])
+
+
+def strands(n_strands, n_dyn, base=True, seed=1, n_verts=96, free_body=False, sprung=False, cross=False):
+    """A root bone carrying `n_strands` chains of `n_dyn` dynamic bones. base=True: every strand hangs from a bone of its own whose body
+    follows it; base=False: every strand hangs from ONE following body on the root (joints of one colour then share it). free_body: one more
+    dynamic body without joints on a bone of its own. sprung: every joint is limited and has a spring on every axis (a body on a free joint
+    without a spring about its own axis keeps whatever twist rounding gives it: its quaternion wanders at 1e-4 while its position holds).
+    cross: every dynamic body is also joined to the body at its height on the next strand, as the panels of a skirt are: a loose joint
+    (0.3 units of play per axis, rotation free), so a dynamic body sits in up to four joints and the joints outnumber the bodies."""
+    rng = np.random.default_rng(seed)
+    parents, bind, bodies, joints = [-1, 0], [[0.0, 0.0, 0.0], [0.0, 16.0, 0.0]], [], []        # a centre bone at the origin, a head at MMD height
+    level = []                      # [strand][k] = (body, model-space position of its bone)
+    root_body = None
+    if not base:
+        bodies.append(dict(bone=1, type=0, shape=1, size=[0.5, 0.2, 0.5], mass=0.0, offset_pos=[0, -0.1, 0]))
+        root_body = 0
+    pos = [np.array(bind[0]), np.array(bind[1])]
+    for s in range(n_strands):
+        ang = 2 * PI * s / max(n_strands, 1)
+        rad = 1.0 + 0.01 * s
+        at = np.array([rad * np.cos(ang), 0.0, rad * np.sin(ang)])
+        parent_bone, parent_body = 1, root_body
+        level.append([])
+        if base:
+            parents.append(1); bind.append(list(at)); pos.append(pos[1] + at)
+            parent_bone = len(parents) - 1
+            bodies.append(dict(bone=parent_bone, type=0 if s % 3 else 2, shape=0, size=[0.2, 0, 0], mass=1.0 if s % 3 == 0 else 0.0,
+                               offset_pos=[0, 0, 0], offset_rot=_quat(rng.normal(size=3), rng.uniform(-0.3, 0.3))))
+            parent_body = len(bodies) - 1
+            at = np.zeros(3)
+        for k in range(n_dyn):
+            step = at + (np.array([0.0, -1.0, 0.0]) if (k or base) else np.zeros(3))
+            parents.append(parent_bone); bind.append(list(step))
+            b = len(parents) - 1
+            pos.append(pos[parent_bone] + step)
+            shape = (s + k) % 3
+            size = [[0.5, 0, 0], [0.3, 0.5, 0.3], [0.3, 0.6, 0]][shape]
+            bodies.append(dict(bone=b, type=1, shape=shape, size=size, mass=float(rng.uniform(0.5, 2.0)),
+                               linear_damping=float(rng.uniform(0.98, 0.9995)), angular_damping=float(rng.uniform(0.98, 0.9995)),
+                               offset_pos=[0, -0.5, 0], offset_rot=_quat(rng.normal(size=3), rng.uniform(-0.4, 0.4))))
+            kind = 2 + s % 2 if sprung else (s + 2 * k) % 4
+            lim = float(rng.uniform(0.3, 0.8))
+            joints.append(dict(body_a=parent_body, body_b=len(bodies) - 1, position=list(pos[b]), rotation=list(rng.uniform(-0.5, 0.5, size=3)),
+                               rotation_min=FREE_MIN if kind == 0 else [-lim, -lim / 2, -lim], rotation_max=FREE_MAX if kind == 0 else [lim, lim / 2, lim],
+                               spring_rotation=[0, 0, 0] if kind == 1 else [float(rng.choice([50, 200] if sprung else [0, 50, 200])) for _ in range(3)],
+                               spring_position=[0, 0, 0]))
+            level[s].append((len(bodies) - 1, pos[b]))
+            parent_bone, parent_body, at = b, len(bodies) - 1, np.zeros(3)
+    if cross:
+        for s in range(n_strands):
+            for k in range(n_dyn):
+                (a, pa), (b, pb) = level[s][k], level[(s + 1) % n_strands][k]
+                joints.append(dict(body_a=a, body_b=b, position=list((pa + pb) / 2), rotation=[0, 0, 0], position_min=[-0.3] * 3, position_max=[0.3] * 3,
+                                   rotation_min=FREE_MIN, rotation_max=FREE_MAX, spring_rotation=[0, 0, 0], spring_position=[0, 0, 0]))
+    if free_body:
+        parents.append(1); bind.append([0.0, -3.0, 0.0]); pos.append(pos[1] + [0, -3.0, 0])
+        bodies.append(dict(bone=len(parents) - 1, type=1, shape=0, size=[0.5, 0, 0], mass=1.0, linear_damping=0.9, angular_damping=0.9))
+    return _scene(parents, bind, bodies, joints, rng, n_verts)
+
+
+def single_body(n_verts=64):
+    """one dynamic body on a bone of its own, no joints: it falls"""
+    rng = np.random.default_rng(5)
+    parents, bind = [-1, 0, 1], [[0.0, 0.0, 0.0], [0.0, 16.0, 0.0], [0.0, -1.0, 0.0]]
+    bodies = [dict(bone=2, type=1, shape=1, size=[0.3, 0.4, 0.5], mass=2.0, linear_damping=0.9, angular_damping=0.9, offset_pos=[0.1, -0.2, 0.0],
+                   offset_rot=_quat([1, 2, 3], 0.3))]
+    return _scene(parents, bind, bodies, [], rng, n_verts)
+
+
+def _scene(parents, bind, bodies, joints, rng, n_verts, gravity=None, h=0.0, iterations=0):
+    parents = np.array(parents, dtype=np.int32)
+    bind = np.array(bind, dtype=np.float32)
+    B = len(parents)
+    bp = ik_ref.bind_positions(parents, bind)
+    # a small mesh: every vertex near a bone, BDEF1 / BDEF2 on it and its parent
+    vb = (np.arange(n_verts) * B // n_verts) if n_verts >= B else rng.integers(0, B, size=n_verts)
+    vb = np.maximum(vb, 0)
+    pos = (bp[vb] + rng.uniform(-0.3, 0.3, size=(n_verts, 3)) + [0, -0.5, 0]).astype(np.float32)
+    nrm = rng.normal(size=(n_verts, 3))
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32)
+    jn = np.zeros((n_verts, 4), dtype=np.uint16)
+    wt = np.zeros((n_verts, 4), dtype=np.uint8)
+    jn[:, 0] = vb
+    jn[:, 1] = np.maximum(parents[vb], 0)
+    w0 = rng.integers(128, 256, size=n_verts)
+    w0[::3] = 255
+    wt[:, 0], wt[:, 1] = w0, 255 - w0
+    inv_bind = np.zeros((B, 16), dtype=np.float32)
+    inv_bind[:, 0] = inv_bind[:, 5] = inv_bind[:, 10] = inv_bind[:, 15] = 1
+    inv_bind[:, 12:15] = -bp.astype(np.float32)
+    mesh = dict(pos=pos, nrm=nrm, joints=jn, weights=wt, parents=parents, bind=bind, inv_bind=inv_bind)
+    table = physics_ref.make_table(bodies, joints, gravity=gravity, h=h, iterations=iterations)
+    return dict(mesh=mesh, table=table, parents=parents, bind=bind, B=B, extent=ik_ref.extent(bp), bodies=bodies, joints=joints)
+
+
+def pose(scene, seed, amount=1.0):
+    """A local pose (q [B,4], t [B,3]) that moves the centre, turns the head and bends every bone a little; the dynamic bones' own rotations are overridden
+    by physics but still steer the un-overridden matrices their children keep."""
+    rng = np.random.default_rng(1000 + seed)
+    B = scene["B"]
+    ax = rng.normal(size=(B, 3))
+    ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+    a = rng.uniform(-0.1, 0.1, size=B) * amount
+    a[0], a[1] = rng.uniform(-0.02, 0.02) * amount, rng.uniform(-0.08, 0.08) * amount     # (the head is 16 units above the centre)
+    q = np.concatenate([ax * np.sin(a / 2)[:, None], np.cos(a / 2)[:, None]], axis=1).astype(np.float32)
+    t = np.zeros((B, 3), dtype=np.float32)
+    t[0] = rng.uniform(-0.15, 0.15, size=3) * amount
+    return q, t
+
+
+def ik_scene(n_verts=96):
+    """An arm (upper, lower, effector) solved by IK towards a goal bone, a following body on the lower arm and a strand of three dynamic
+    bodies hanging from it: physics must read the pose AFTER IK."""
+    rng = np.random.default_rng(9)
+    parents = [-1, 0, 1, 2, 3, 0, 3, 6, 7]
+    bind = [[0, 0, 0], [0, 16, 0], [1, 0, 0], [2, 0, 0], [2, 0, 0], [4.2, 15.2, 0.8], [1, -0.2, 0], [0, -1, 0], [0, -1, 0]]
+    pos = ik_ref.bind_positions(parents, bind)
+    bodies = [dict(bone=3, type=0, shape=1, size=[1.0, 0.2, 0.2], mass=0.0, offset_pos=[1, 0, 0])]
+    joints = []
+    for k, b in enumerate((6, 7, 8)):
+        bodies.append(dict(bone=b, type=1, shape=2, size=[0.25, 0.5, 0], mass=1.0, linear_damping=0.99, angular_damping=0.99, offset_pos=[0, -0.5, 0],
+                           offset_rot=_quat([0, 0, 1], 0.1 * k)))
+        joints.append(dict(body_a=k, body_b=k + 1, position=list(pos[b]), rotation=[0.1, 0.2, -0.1], rotation_min=[-0.6, -0.3, -0.6], rotation_max=[0.6, 0.3, 0.6],
+                           spring_rotation=[50, 0, 50], spring_position=[0, 0, 0]))
+    sc = _scene(parents, bind, bodies, joints, rng, n_verts)
+    sc["chains"] = [dict(goal=5, effector=4, loops=8, limit_angle=1.0, links=[dict(bone=3, min=None, max=None), dict(bone=2, min=None, max=None)])]
+    return sc
+
+
+def ik_pose(scene, seed):
+    """the goal bone moves (so the arm does), everything else as pose()"""
+    q, t = pose(scene, seed)
+    t[5] = np.random.default_rng(50 + seed).uniform(-0.4, 0.4, size=3)
+    return q, t
+
+
+def motion(scene, seed, n_keys=6):
+    """A gentle motion (rz_animation fields): the centre drifts, the head and every bone without a dynamic body turn a little, a key every
+    3 frames."""
+    rng = np.random.default_rng(300 + seed)
+    t = scene["table"]
+    driven = set(int(b) for b in t["bone"][physics_ref.is_dynamic(t)] if b >= 0)
+    bones = np.array([b for b in range(scene["B"]) if b not in driven][:24], dtype=np.int32)
+    n = len(bones)
+    ax = rng.normal(size=(n, n_keys, 3))
+    ax /= np.linalg.norm(ax, axis=2, keepdims=True)
+    a = rng.uniform(-0.08, 0.08, size=(n, n_keys))
+    a[0] *= 0.25                    # (the head is 16 units above the centre)
+    kq = np.concatenate([ax * np.sin(a / 2)[..., None], np.cos(a / 2)[..., None]], axis=2).astype(np.float32)
+    kp = np.zeros((n, n_keys, 3), dtype=np.float32)
+    kp[0] = rng.uniform(-0.15, 0.15, size=(n_keys, 3))
+    return dict(track_bone=bones, key_off=(np.arange(n + 1) * n_keys).astype(np.uint32), key_frame=np.tile(np.arange(n_keys, dtype=np.float32) * 3, n),
+                key_rot=kq.reshape(-1, 4), key_pos=kp.reshape(-1, 3), key_interp=rng.integers(20, 107, size=(n * n_keys, 16)).astype(np.uint8))
+
+
+def write_pmx(scene, seed=0):
+    """A PMX 2.0 byte stream of the scene with its rigid-body and joint sections (tests/pmx_synth.py writes none): shapePosition = the bone's
+    bind position + the body's offset, shapeRotation = random Euler angles. Returns (bytes, the table a loader must derive from it:
+    offsets = inverseBind x T(shapePosition) R(Quat.fromEuler(shapeRotation)))."""
+    import struct
+    rng = np.random.default_rng(700 + seed)
+
+    def text(x):
+        b = x.encode("utf-16le")
+        return struct.pack("<i", len(b)) + b
+    m, t = scene["mesh"], scene["table"]
+    B, V = scene["B"], len(scene["mesh"]["pos"])
+    out = bytearray(b"PMX ") + struct.pack("<f", 2.0) + bytes([8, 0, 0, 4, 1, 1, 2, 2, 1])
+    out += text("physics scene") + text("") + text("") + text("")
+    out += struct.pack("<i", V)
+    for v in range(V):
+        out += m["pos"][v].tobytes() + m["nrm"][v].tobytes() + struct.pack("<2f", 0.5, 0.5)
+        out += bytes([1]) + struct.pack("<hhf", int(m["joints"][v, 0]), int(m["joints"][v, 1]), float(m["weights"][v, 0]) / 255.0) + struct.pack("<f", 1.0)
+    tri = (np.arange(3 * (V // 3)) % V).astype(np.int32)
+    out += struct.pack("<i", len(tri)) + tri.tobytes()
+    out += struct.pack("<i", 0)
+    out += struct.pack("<i", 1) + text("body") + text("") + struct.pack("<11f", *([0.5] * 11)) + bytes([0x10])
+    out += struct.pack("<5f", 0, 0, 0, 1, 1.25) + struct.pack("<bb", -1, -1) + bytes([0, 1, 0]) + text("") + struct.pack("<i", len(tri))
+    bp = ik_ref.bind_positions(scene["parents"], scene["bind"]).astype(np.float32)
+    out += struct.pack("<i", B)
+    for b in range(B):
+        out += text("bone%d" % b) + text("") + bp[b].tobytes() + struct.pack("<h", int(scene["parents"][b])) + struct.pack("<i", 0)
+        out += struct.pack("<H", 0) + struct.pack("<3f", 0, 1, 0)
+    out += struct.pack("<i", 0) + struct.pack("<i", 0)                   # morphs, display frames
+    nb, nj = t["n_bodies"], t["n_joints"]
+    want = {k: np.array(v, copy=True) if isinstance(v, np.ndarray) else v for k, v in t.items()}
+    out += struct.pack("<i", nb)
+    for b in range(nb):
+        bone = int(t["bone"][b])
+        sp = (t["offset_pos"][b] + (bp[bone] if bone >= 0 else 0)).astype(np.float32)
+        sr = rng.uniform(-0.6, 0.6, size=3).astype(np.float32)
+        out += text("body%d" % b) + text("") + struct.pack("<h", bone) + bytes([int(t["group"][b])]) + struct.pack("<H", int(t["mask"][b])) + bytes([int(t["shape"][b])])
+        out += t["size"][b].tobytes() + sp.tobytes() + sr.tobytes()
+        out += struct.pack("<5f", t["mass"][b], t["linear_damping"][b], t["angular_damping"][b], t["restitution"][b], t["friction"][b]) + bytes([int(t["type"][b])])
+        want["offset_pos"][b] = sp - (bp[bone] if bone >= 0 else np.float32(0))
+        want["offset_rot"][b] = physics_ref.quat_from_pmx_euler(sr).astype(np.float32)
+    out += struct.pack("<i", nj)
+    for j in range(nj):
+        out += text("joint%d" % j) + text("") + bytes([0]) + struct.pack("<bb", int(t["body_a"][j]), int(t["body_b"][j]))
+        for k in physics_ref.JOINT_F:
+            out += np.asarray(t[k][j], dtype=np.float32).tobytes()
+    return bytes(out), want
+
+
+SCENES = {
+    "one body": lambda: single_body(),
+    "63 bodies": lambda: strands(9, 6, base=True, seed=2, n_verts=128),
+    "65 bodies": lambda: strands(13, 4, base=True, seed=3, n_verts=130),
+    "wide colour": lambda: strands(260, 1, base=False, seed=4, n_verts=300, sprung=True),
+    "skirt": lambda: strands(8, 5, base=True, seed=8, n_verts=100, sprung=True, cross=True),     # 48 bodies, 80 joints: one wave, lanes stride
+    "one joint": lambda: strands(1, 1, base=True, seed=6, n_verts=64),
+    "crowd": lambda: strands(4, 5, base=True, seed=7, n_verts=96, free_body=True),
+    "ik": lambda: ik_scene(),
+}
+_memo = {}
+
+NODE_H, NODE_MAX_SUBSTEPS = 1 / 75, 10
+NODE_TIMES = tuple(16.7 * k for k in range(13))         # the engine clock (ms) of the Node end-to-end frames: step(0), step(16.7), ...
+
+
+def node_substeps(times=NODE_TIMES):
+    """what Engine { devicePhysics } owes per frame: the clock's advance joins the accumulator, min(10, floor(acc / h)) substeps leave it
+    (the same double arithmetic as host/src/engine.ts: physicsSubsteps())"""
+    import math
+    acc, last, out = 0.0, 0.0, []
+    for now in times:
+        if now > last:
+            acc += (now - last) / 1000
+        last = now
+        owed = math.floor(acc / NODE_H)
+        acc -= owed * NODE_H
+        out.append(min(NODE_MAX_SUBSTEPS, owed))
+    return tuple(out)
+
+
+def node_case():
+    """The Node end-to-end test's scene: the 'crowd' strands as a PMX file, run with the table its loader derives from the file, under one
+    fixed local pose (no translations: the engine sends none without a motion). Returns (scene, pmx bytes, q [B,4])."""
+    if "node" not in _memo:
+        sc = scene("crowd")
+        data, want = write_pmx(sc)
+        q, _ = pose(sc, 70, amount=2.0)
+        _memo["node"] = (dict(sc, table=want), data, q)
+    return _memo["node"]
+
+
+def bone_morph_case():
+    """The bone-morph GPU test's inputs: (scene, the morph, its weight, the un-morphed local poses); the morph moves body 0's bone, the
+    base of the first strand, whose body follows it."""
+    sc = scene("crowd")
+    base_bone = int(sc["table"]["bone"][0])
+    bm = dict(morph=np.array([0], dtype=np.uint32), bone=np.array([base_bone], dtype=np.uint32), t=np.array([[0.3, 0.1, -0.2]], dtype=np.float32),
+              q=np.array([[0.0, 0.0, np.sin(0.2), np.cos(0.2)]], dtype=np.float32))
+    return sc, bm, np.array([0.7], dtype=np.float32), [pose(sc, 20 + k) for k in range(3)]
+
+
+def scene(name):
+    if name not in _memo:
+        _memo[name] = SCENES[name]()
+    return _memo[name]
+
+
+CALLS = (1, 10, 10, 10, 10)        # substeps per call of the standard sequence: 1, 10, then 3 x 10, the pose changing between calls
+CROWD_CALLS = (1, 10, 10)
+
+
+def crowd_frames(instance, call):
+    """every instance at its own frame, one frame on per call"""
+    return 1.3 + 2.1 * instance + 1.0 * call
+
+
+def world_of(scene, q, t, chains=(), dtype=np.float64):
+    return ik_ref.solve(scene["parents"], scene["bind"], q, t, chains, dtype=dtype)[0]
+
+
+def run_reference(scene, poses, calls=CALLS, chains=(), dtype=np.float64, sim=None):
+    """The standard sequence on one instance: per call (float64 world with overrides applied [B,16], state [nb,13]). `poses` has one local
+    pose per call."""
+    sim = sim or physics_ref.Sim(scene["table"], scene["parents"], scene["bind"], dtype=dtype)
+    out = []
+    for (q, t), n in zip(poses, calls):
+        w = world_of(scene, q, t, chains, dtype=dtype)
+        ovr = sim.step(w, n)
+        out.append((physics_ref.apply_overrides(w, ovr), sim.state13().astype(np.float64)))
+    return out
+
+
+def conditioning(scene, poses, calls=CALLS, chains=()):
+    """largest float32-probe deviation from the float64 run over the whole horizon (positions and world-matrix entries), in units of extent"""
+    a = run_reference(scene, poses, calls, chains)
+    b = run_reference(scene, poses, calls, chains, dtype=np.float32)
+    worst = 0.0
+    for (wa, sa), (wb, sb) in zip(a, b):
+        worst = max(worst, float(np.abs(wa - wb).max()), float(np.abs(sa[:, :3] - sb[:, :3]).max()))
+    return worst / scene["extent"]
