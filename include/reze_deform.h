@@ -245,7 +245,12 @@ int rz_upload_bone_morphs(rz_ctx *ctx, uint32_t n, const uint32_t *morph, const 
  *                 interpolation bytes: X_x1 Y_x1 Z_x1 R_x1 | ..y1 | ..x2 | ..y2; NULL = linear)
  *   morph tracks: mkey_off[m+1], mkey_frame, mkey_weight; feeds per VERTEX MORPH of the uploaded morph set:
  *                 feed_off[M+1], feed_track, feed_ratio — its own track (ratio 1) first, then the group-morph
- *                 tracks that include it, ascending (the order Model.getEffectiveMorphWeights adds them in). */
+ *                 tracks that include it, ascending (the order Model.getEffectiveMorphWeights adds them in).
+ * Refused (RZ_ERR_INVALID, nothing resident changes): a key that is not finite — frame, rotation, position or morph weight — in a track
+ * that drives a bone or feeds a vertex morph of this model, with the track and the key named ("track 3 key 17: the rotation is not
+ * finite"; rz_upload_motions puts "clip k: " in front); keys of tracks that drive nothing of this model are not looked at.
+ * rz_set_pose_sampled refuses a frame that is NaN or infinite ("instance i: a frame that would be sampled is not finite", the wording of
+ * rz_set_pose_blended) and leaves the resident pose as it was. */
 typedef struct rz_animation {
     uint32_t n_bone_tracks;
     const int32_t *track_bone;

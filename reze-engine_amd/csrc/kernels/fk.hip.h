@@ -70,6 +70,10 @@ __device__ __forceinline__ float bezier_y(float x, float x1, float y1, float x2,
 // loaded speculatively together with their frames; only a wrong guess (uneven keys, duplicates) pays for a bisection of
 // what the guess left. Chain of dependent loads per bone: record -> keys, instead of bone -> track -> offsets -> ends ->
 // log2(n) probes -> keys.
+// A hand-keyed dance is the opposite of a baked motion — tracks of thousands of keys in bursts, gaps of hundreds of frames, runs of
+// equal frames — and there the guess misses nearly always, by thousands of keys. The repair path is held to the float64 sampler on such
+// tracks (70 000 keys, key indices beyond 65 536, frames beyond 100 000) by tests/test_gpu_sampler.py; tests/test_sampler_cpu.py
+// restates guess + repair in float32 and shows that one-off errors in it leave the bar.
 struct KeyRange { uint32_t b, e; float f0, f1; };
 __device__ __forceinline__ KeyRange key_range(const uint4 r) { return KeyRange{r.x, r.y, __uint_as_float(r.z), __uint_as_float(r.w)}; }
 

@@ -554,6 +554,8 @@ int rz_set_pose_local(rz_ctx *c, const float *local_rotations4, const float *loc
                        morph_weights);
 }
 
+static bool finite_f(float x) { return x == x && x - x == 0.0f; }
+
 int rz_set_pose_sampled(rz_ctx *c, const float *frames)
 {
     if (int r = use(c)) return r;
@@ -561,6 +563,10 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
     if (c->an_M != c->M) return fail(RZ_ERR_INVALID, "the motion's morph feeds were built for %u vertex morphs, the context holds %u", c->an_M, c->M);
     if (!frames) return fail(RZ_ERR_INVALID, "null frames");
+    // refused before anything of the resident pose is touched (the wording of rz_set_pose_blended): the span guess turns the frame into a
+    // key index, which is undefined for a NaN or an infinite frame
+    for (uint32_t i = 0; i < c->I; ++i)
+        if (!finite_f(frames[i])) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
     if (int r = ensure_pose_buffers(c)) return r;
     if (c->I > c->an_frames_alloc) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -606,8 +612,6 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
 // after such a copy: a resident local pose with translations. A state that is refused is refused before anything of the resident pose is
 // touched; a device error after that (a staging slot, a block of the ring) leaves the context without a pose, as it does in rz_upload_pose.
 static_assert(sizeof(rz_motion_state) == sizeof(RzMotionState) && sizeof(RzMotionState) == 20, "rz_motion_state is RzMotionState");
-static bool finite_f(float x) { return x == x && x - x == 0.0f; }
-
 static int check_motion_states(const rz_ctx *c, const RzMotionState *sv)
 {
     for (uint32_t i = 0; i < c->I; ++i) {

@@ -390,6 +390,9 @@ int rz_upload_bone_morphs(rz_ctx *c, uint32_t n, const uint32_t *morph, const ui
 
 // What rz_upload_animation and rz_upload_motions check of one flattened motion, and what they derive from it: bone_track[b] = the track
 // that drives bone b or -1, feed_off[M + 1] / *F = the feeds of the context's vertex morphs (all zero without morph tracks).
+// Keys of tracks that drive nothing of this model (a bone it lacks, a morph track no feed names) are never read by a kernel and are not looked at.
+static bool finite_key(float x) { return x == x && x - x == 0.0f; }
+
 static int check_animation(const rz_ctx *c, const rz_animation *a, std::vector<int> &bone_track, std::vector<uint32_t> &feed_off, uint32_t *F_out)
 {
     if (!a) return fail(RZ_ERR_INVALID, "null animation");
@@ -408,6 +411,15 @@ static int check_animation(const rz_ctx *c, const rz_animation *a, std::vector<i
             // equal frames are legal (real VMD files carry duplicate keys; host/vmd-sampler.js keeps them too): the span search
             // lands on the last key <= frame and the first key > frame, so a zero-length span is never divided by
             if (!(a->key_frame[k] >= a->key_frame[k - 1])) return fail(RZ_ERR_INVALID, "track %u: key frames must not descend", t);
+        // every key of a track that drives a bone of this model is finite: a NaN frame passes no comparison of the span search, an
+        // infinite one makes the guessed span's index undefined, and either in a rotation or a position is a NaN pose nothing explains
+        for (uint32_t k = a->key_off[t]; k < a->key_off[t + 1]; ++k) {
+            if (!finite_key(a->key_frame[k])) return fail(RZ_ERR_INVALID, "track %u key %u: the frame is not finite", t, k - a->key_off[t]);
+            for (int d = 0; d < 4; ++d)
+                if (!finite_key(a->key_rot4[(size_t)k * 4 + d])) return fail(RZ_ERR_INVALID, "track %u key %u: the rotation is not finite", t, k - a->key_off[t]);
+            for (int d = 0; d < 3; ++d)
+                if (!finite_key(a->key_pos3[(size_t)k * 3 + d])) return fail(RZ_ERR_INVALID, "track %u key %u: the position is not finite", t, k - a->key_off[t]);
+        }
         bone_track[b] = (int)t;
     }
     for (uint32_t t = 0; t < mt; ++t) {
@@ -424,6 +436,17 @@ static int check_animation(const rz_ctx *c, const rz_animation *a, std::vector<i
             if (feed_off[m] > feed_off[m + 1]) return fail(RZ_ERR_INVALID, "feed offsets must be non-decreasing");
         for (uint32_t f = 0; f < F; ++f)
             if (a->feed_track[f] < 0 || (uint32_t)a->feed_track[f] >= mt) return fail(RZ_ERR_INVALID, "feed %u names morph track %d of %u", f, a->feed_track[f], mt);
+        // ... and so is every key of a morph track that feeds a vertex morph of this model
+        std::vector<char> seen(mt, 0);
+        for (uint32_t f = 0; f < F; ++f) {
+            const uint32_t t = (uint32_t)a->feed_track[f];
+            if (seen[t]) continue;
+            seen[t] = 1;
+            for (uint32_t k = a->mkey_off[t]; k < a->mkey_off[t + 1]; ++k) {
+                if (!finite_key(a->mkey_frame[k])) return fail(RZ_ERR_INVALID, "morph track %u key %u: the frame is not finite", t, k - a->mkey_off[t]);
+                if (!finite_key(a->mkey_weight[k])) return fail(RZ_ERR_INVALID, "morph track %u key %u: the weight is not finite", t, k - a->mkey_off[t]);
+            }
+        }
     }
     *F_out = F;
     return RZ_OK;

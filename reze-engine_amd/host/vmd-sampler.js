@@ -20,10 +20,12 @@ function bezier(x, x1, y1, x2, y2) {
   if (x >= 1) return 1
   if (x1 === y1 && x2 === y2) return x // the default 20,20,107,107 curve is the identity
   let lo = 0, hi = 1, t = x
-  for (let i = 0; i < 32; i++) {
+  // the residual bound is on x(t): y is off by that times dy/dx, which reaches ~80 at x = 1/1000 on curves whose x(t) is flat at an end
+  // (control x of 0 or 127), so 1e-12 keeps y within 1e-10 there
+  for (let i = 0; i < 64; i++) {
     const s = 1 - t
     const fx = 3 * s * s * t * x1 + 3 * s * t * t * x2 + t * t * t - x
-    if (Math.abs(fx) < 1e-9) break
+    if (Math.abs(fx) < 1e-12) break
     if (fx > 0) hi = t; else lo = t
     const dfx = 3 * s * s * x1 + 6 * s * t * (x2 - x1) + 3 * t * t * (1 - x2)
     const tn = dfx !== 0 ? t - fx / dfx : (lo + hi) / 2

@@ -126,8 +126,11 @@ def bone_morph_reference(quats, trans, morph, bone, t3, q4, weights):
     return q, t
 
 
-def bezier_reference(x, x1, y1, x2, y2):
-    """host/vmd-sampler.js bezier() in float64: y(x) of the cubic (0,0) (x1,y1) (x2,y2) (1,1)."""
+def bezier_reference(x, x1, y1, x2, y2, dtype=np.float64):
+    """host/vmd-sampler.js bezier() in float64: y(x) of the cubic (0,0) (x1,y1) (x2,y2) (1,1). dtype=float32: the device's bezier_y
+    (kernels/fk.hip.h) restated operation by operation — float32 throughout, 24 iterations, break at |fx| < 1e-7."""
+    if np.dtype(dtype) == np.float32:
+        return _bezier_f32(x, x1, y1, x2, y2)
     if x <= 0:
         return 0.0
     if x >= 1:
@@ -151,10 +154,13 @@ def bezier_reference(x, x1, y1, x2, y2):
     return 3 * s * s * t * y1 + 3 * s * t * t * y2 + t ** 3
 
 
-def sample_reference(anim, frame, n_bones, n_morphs):
+def sample_reference(anim, frame, n_bones, n_morphs, dtype=np.float64, span_fn=None):
     """MMD motion sampling in float64 (the arithmetic of host/vmd-sampler.js): returns (quats [B,4], trans [B,3],
-    morph weights [M]) at `frame` for a flattened motion dict with the rz_animation field names."""
+    morph weights [M]) at `frame` for a flattened motion dict with the rz_animation field names. dtype=float32: the device's arithmetic
+    instead (sample_device_f32 below; span_fn replaces its span search)."""
     import numpy as np
+    if np.dtype(dtype) == np.float32:
+        return sample_device_f32(anim, frame, n_bones, n_morphs, span_fn)
 
     def span(kf, b, e, f):
         lo, hi = b, e - 1
@@ -209,4 +215,154 @@ def sample_reference(anim, frame, n_bones, n_morphs):
                     continue
                 i0, i1, x = span(mkf, lo, hi, frame)
                 w[m] += (mw[i0] + (mw[i1] - mw[i0]) * x) * float(anim["feed_ratio"][f])
+    return q, t, w
+
+
+# ---- the device sampler restated in float32 (kernels/fk.hip.h: bezier_y, span_guess, span_bisect, bone_finish, morph_finish) ----
+# Every operation is a float32 operation in the order the kernel spells it (contraction is off there). What differs from the device is
+# the last bit of acosf / sinf / sqrtf, so this is a model of the kernel's rounding, not of its bits. Test infrastructure.
+_F = np.float32
+
+
+def _bezier_f32(x, x1, y1, x2, y2):
+    F = _F
+    x, x1, y1, x2, y2 = F(x), F(x1), F(y1), F(x2), F(y2)
+    if x <= F(0):
+        return F(0)
+    if x >= F(1):
+        return F(1)
+    if x1 == y1 and x2 == y2:
+        return x
+    lo, hi, t = F(0), F(1), x
+    for _ in range(24):
+        s = F(1) - t
+        fx = F(3) * s * s * t * x1 + F(3) * s * t * t * x2 + t * t * t - x
+        if abs(fx) < F(1e-7):
+            break
+        if fx > F(0):
+            hi = t
+        else:
+            lo = t
+        d = F(3) * s * s * x1 + F(6) * s * t * (x2 - x1) + F(3) * t * t * (F(1) - x2)
+        tn = t - fx / d if d != F(0) else F(0.5) * (lo + hi)
+        t = tn if (tn > lo and tn < hi) else F(0.5) * (lo + hi)
+    s = F(1) - t
+    return F(3) * s * s * t * y1 + F(3) * s * t * t * y2 + t * t * t
+
+
+def span_guess_f32(kf, b, e, frame, clamp=2):
+    """span_guess: (0, key) when the frame clamps to one key, (1, g) with g the guessed first key of an interior span."""
+    F = _F
+    n = e - b
+    f0, f1 = kf[b], kf[e - 1]
+    if n == 1 or frame <= f0:
+        return 0, b
+    if frame >= f1:
+        return 0, e - 1
+    return 1, b + min(int((frame - f0) / (f1 - f0) * F(n - 1)), n - clamp)
+
+
+def span_bisect_f32(kf, b, e, frame, g, strict=False):
+    """span_bisect: the last key <= frame of [b, e) around the guess g; returns (key, probes)"""
+    lo, hi = b, e - 1
+    if kf[g] <= frame:
+        lo = g
+    else:
+        hi = g
+    steps = 0
+    while hi - lo > 1:
+        mid = (lo + hi) >> 1
+        steps += 1
+        if (kf[mid] < frame) if strict else (kf[mid] <= frame):
+            lo = mid
+        else:
+            hi = mid
+    return lo, steps
+
+
+SPAN_MUTANTS = ("no_repair", "strict_less", "first_of_run", "clamp_n_minus_1")
+
+
+def span_device_f32(kf, b, e, frame, stats=None, mutant=None):
+    """The device's span search — guess, check, repair — on a float32 key-frame array: (i0, i1), i1 == i0 for a clamped frame.
+    stats (a dict) receives guess (the guessed key), right (the check passed), steps (probes of the repair), beyond (a key outside
+    [b, e) was read). mutant: one of SPAN_MUTANTS, the same search with that one-off error."""
+    frame = _F(frame)
+    interior, g = span_guess_f32(kf, b, e, frame, clamp=1 if mutant == "clamp_n_minus_1" else 2)
+    if stats is not None:
+        stats.update(interior=bool(interior), guess=g, right=True, steps=0, beyond=False)
+    if not interior:
+        return g, g
+    if g + 1 >= e:                                   # (only the clamp mutant gets here: key e belongs to the next track, or to nobody)
+        if stats is not None:
+            stats["beyond"] = True
+        f_b = _F(np.inf)
+    else:
+        f_b = kf[g + 1]
+    i0 = g
+    if not (kf[g] <= frame and frame < f_b) and mutant != "no_repair":
+        i0, steps = span_bisect_f32(kf, b, e, frame, g, strict=(mutant == "strict_less"))
+        if stats is not None:
+            stats.update(right=False, steps=steps)
+    if mutant == "first_of_run":
+        while i0 > b and kf[i0 - 1] == kf[i0]:
+            i0 -= 1
+    return i0, i0 + 1
+
+
+def sample_device_f32(anim, frame, n_bones, n_morphs, span_fn=None):
+    """sample_reference in the device's float32 arithmetic: returns float32 (quats [B,4], trans [B,3], morph weights [M])."""
+    F = _F
+    span_fn = span_fn or span_device_f32
+    frame = F(frame)
+    q = np.tile(np.array([0, 0, 0, 1], dtype=F), (n_bones, 1))
+    t = np.zeros((n_bones, 3), dtype=F)
+    kf = np.asarray(anim["key_frame"], dtype=F)
+    rot = np.asarray(anim["key_rot"], dtype=F).reshape(-1, 4)
+    pos = np.asarray(anim["key_pos"], dtype=F).reshape(-1, 3)
+    ip = None if anim.get("key_interp") is None else np.asarray(anim["key_interp"], dtype=np.uint8).reshape(-1, 16)
+    inv127 = F(1) / F(127)
+    with np.errstate(all="ignore"):
+        for tr, b in enumerate(anim["track_bone"]):
+            lo, hi = int(anim["key_off"][tr]), int(anim["key_off"][tr + 1])
+            if b < 0 or b >= n_bones or hi == lo:
+                continue
+            i0, i1 = span_fn(kf, lo, hi, frame)
+            if i0 == i1:
+                q[b], t[b] = rot[i0], pos[i0]
+                continue
+            i1 = min(i1, len(kf) - 1)
+            x = (frame - kf[i0]) / (kf[i1] - kf[i0])
+            c = [x] * 4 if ip is None else [_bezier_f32(x, F(ip[i1][k]) * inv127, F(ip[i1][k + 4]) * inv127, F(ip[i1][k + 8]) * inv127,
+                                                        F(ip[i1][k + 12]) * inv127) for k in range(4)]
+            a, bq = rot[i0].copy(), rot[i1].copy()
+            d = a[0] * bq[0] + a[1] * bq[1] + a[2] * bq[2] + a[3] * bq[3]
+            if d < F(0):
+                d, bq = -d, -bq
+            if d > F(0.9995):
+                r = a + c[3] * (bq - a)
+                r = r * (F(1) / np.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]))
+            else:
+                th0 = np.arccos(d)
+                sn, th = np.sin(th0), th0 * c[3]
+                r = (np.sin(th0 - th) / sn) * a + (np.sin(th) / sn) * bq
+            q[b] = r
+            t[b] = pos[i0] + (pos[i1] - pos[i0]) * np.array(c[:3], dtype=F)
+        w = np.zeros(n_morphs, dtype=F)
+        if n_morphs and anim.get("mkey_off") is not None:
+            mkf = np.asarray(anim["mkey_frame"], dtype=F)
+            mw = np.asarray(anim["mkey_weight"], dtype=F)
+            for m in range(n_morphs):
+                for f in range(int(anim["feed_off"][m]), int(anim["feed_off"][m + 1])):
+                    tr = int(anim["feed_track"][f])
+                    lo, hi = int(anim["mkey_off"][tr]), int(anim["mkey_off"][tr + 1])
+                    if hi == lo:
+                        continue
+                    i0, i1 = span_fn(mkf, lo, hi, frame)
+                    if i0 == i1:
+                        wk = mw[i0]
+                    else:
+                        i1 = min(i1, len(mkf) - 1)
+                        wk = mw[i0] + (mw[i1] - mw[i0]) * ((frame - mkf[i0]) / (mkf[i1] - mkf[i0]))
+                    w[m] = w[m] + wk * F(anim["feed_ratio"][f])
     return q, t, w
