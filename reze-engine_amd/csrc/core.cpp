@@ -190,13 +190,9 @@ void free_animation(rz_ctx *c)
 
 void free_motions(rz_ctx *c)
 {
-    if (c->mo_clips && !c->lender) {      // rz_motion_blend_kernel reads the library on whichever stream the pose travelled on
+    if (c->mo_clips) {                    // rz_motion_blend_kernel reads the library on whichever stream the pose travelled on
         if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
-    }
-    if (c->lender) {                      // a fork's library is its lender's
-        c->mo_bone_rec = nullptr; c->mo_feed_off = nullptr; c->mo_feed_range = c->mo_key_interp = nullptr;
-        c->mo_key_frame = c->mo_key_pos = c->mo_mkey_frame = c->mo_mkey_weight = c->mo_feed_ratio = nullptr; c->mo_key_rot = nullptr;
     }
     dfree(c->mo_bone_rec); dfree(c->mo_feed_off); dfree(c->mo_feed_range); dfree(c->mo_key_interp);
     dfree(c->mo_key_frame); dfree(c->mo_key_pos); dfree(c->mo_mkey_frame); dfree(c->mo_mkey_weight); dfree(c->mo_feed_ratio); dfree(c->mo_key_rot);
@@ -222,7 +218,6 @@ void forget_search(rz_ctx *c)
 void free_sdef(rz_ctx *c)
 {
     drop_graph(c);
-    if (c->lender) c->sdef_tab = nullptr;     // a fork's table is its lender's
     dfree(c->sdef_tab);
     c->sdef_n = 0;
     c->sdef_idx_host.clear();
@@ -231,7 +226,6 @@ void free_sdef(rz_ctx *c)
 void free_qdef(rz_ctx *c)
 {
     drop_graph(c);
-    if (c->lender) c->qdef_tab = nullptr;     // a fork's table is its lender's
     dfree(c->qdef_tab);
     c->qdef_n = 0;
     c->qdef_idx_host.clear();
@@ -241,7 +235,6 @@ void free_ik(rz_ctx *c)
 {
     if (!c->ik_n) return;
     drop_graph(c);
-    if (c->lender) { c->ik_chain = nullptr; c->ik_path = c->ik_stage_off = nullptr; c->ik_link = nullptr; }     // a fork's table is its lender's
     dfree(c->ik_chain); dfree(c->ik_path); dfree(c->ik_stage_off); dfree(c->ik_link);
     c->ik_n = c->ik_stages = 0;
 }
@@ -345,17 +338,8 @@ int rz_destroy(rz_ctx *c)
 #endif
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
-    if (c->lender) {                      // a fork frees nothing it borrowed
-        c->geom = nullptr; c->j01 = c->j23 = c->wq = nullptr; c->inv_bind = nullptr;
-        c->fk_rec = nullptr; c->fk_anc_more = nullptr;
-        c->an_feed_range = nullptr; c->an_feed_off = nullptr;
-        c->an_key_frame = c->an_key_pos = c->an_mkey_frame = c->an_mkey_weight = c->an_feed_ratio = nullptr; c->an_key_rot = nullptr; c->an_key_interp = nullptr;
-        c->bm_off = c->bm_morph = nullptr; c->bm_rot = c->bm_tr = nullptr;
-        c->dense = nullptr; c->sp_ptr = nullptr; c->sp_entries = nullptr; c->edge = nullptr;
-        c->sdef_tab = nullptr; c->sdef_n = 0;
-        c->qdef_tab = nullptr; c->qdef_n = 0;
-        c->ik_chain = nullptr; c->ik_path = c->ik_stage_off = nullptr; c->ik_link = nullptr; c->ik_n = c->ik_stages = 0;
-        free_motions(c);
+    if (c->lender) {                      // a fork frees nothing it borrowed: the free_* calls below find an empty RzStatic
+        static_cast<RzStatic &>(*c) = RzStatic{};
         c->lender->n_forks--;
         c->lender = nullptr;
     }
@@ -363,20 +347,17 @@ int rz_destroy(rz_ctx *c)
     drop_graph(c);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->inv_bind);
+    // RzStatic ...
+    dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->inv_bind); dfree(c->edge);
+    dfree(c->fk_rec); dfree(c->fk_anc_more);
+    free_animation(c); free_motions(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c);
+    // ... and what the context owns
     dfree(c->rj01); dfree(c->rj23); dfree(c->sub_list); dfree(c->sub_count); dfree(c->zc_tag);
     dfree(c->subfk_rec); dfree(c->subfk_count);
-    dfree(c->fk_rec); dfree(c->fk_anc_more);
-    free_animation(c); dfree(c->an_frames);
-    free_motions(c); dfree(c->mo_states);
+    dfree(c->an_frames); dfree(c->mo_states);
     dfree(c->pose_blk[0]); dfree(c->pose_blk[1]);
     free_big_ring(c);
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
-    free_bone_morphs(c);
-    free_morphs(c);
-    free_sdef(c);
-    free_qdef(c);
-    free_ik(c);
     free_physics(c);
     for (int k = 0; k < 2; ++k) {
         if (c->big_ev[k]) (void)hipEventDestroy(c->big_ev[k]);
@@ -393,7 +374,7 @@ int rz_destroy(rz_ctx *c)
 #ifdef RZ_ALL_VARIANTS
     if (c->gate_host) { (void)hipHostFree(c->gate_host); c->gate_host = nullptr; }
 #endif
-    dfree(c->edge); dfree(c->out_hull); dfree(c->aabb);
+    dfree(c->out_hull); dfree(c->aabb);
     for (int i = 0; i < kStageSlots; ++i) {
         if (c->stage[i]) (void)hipHostFree(c->stage[i]);
         if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
@@ -421,32 +402,9 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
     HIP_TRY(hipStreamSynchronize(parent->stream));        // every static upload of the lender has landed (before anything is created: nothing to undo on failure)
     rz_ctx *c = nullptr;
     if (int r = rz_create(parent->device, &c)) return r;
-    c->V = parent->V; c->Vp = parent->Vp; c->geom = parent->geom; c->j01 = parent->j01; c->j23 = parent->j23; c->wq = parent->wq;
-    c->B = parent->B; c->inv_bind = parent->inv_bind;
-    c->has_topology = parent->has_topology; c->fk_rec = parent->fk_rec; c->fk_anc_more = parent->fk_anc_more; c->fk_rounds = parent->fk_rounds;
-    // ... and the host-side mirrors the plan reads (plan.cpp: subfk_wanted / ensure_subfk build a crowd's closure records from them): without
-    // them a fork of a device-animated crowd never took the one-launch frame and a context and its fork alternated two frame shapes
-    c->fk_host = parent->fk_host; c->an_host_range = parent->an_host_range; c->an_host_mrec = parent->an_host_mrec; c->fk_gen = parent->fk_gen;
-    c->has_animation = parent->has_animation; c->an_feed_range = parent->an_feed_range;
-    c->an_feed_off = parent->an_feed_off; c->an_key_frame = parent->an_key_frame; c->an_key_pos = parent->an_key_pos;
-    c->an_mkey_frame = parent->an_mkey_frame; c->an_mkey_weight = parent->an_mkey_weight; c->an_feed_ratio = parent->an_feed_ratio;
-    c->an_key_rot = parent->an_key_rot; c->an_key_interp = parent->an_key_interp; c->an_M = parent->an_M;
-    c->bm_off = parent->bm_off; c->bm_morph = parent->bm_morph; c->bm_rot = parent->bm_rot; c->bm_tr = parent->bm_tr; c->bm_count = parent->bm_count;
-    c->morph_mode = parent->morph_mode; c->M = parent->M; c->Mpad = parent->Mpad; c->dense = parent->dense;
-    c->sp_ptr = parent->sp_ptr; c->sp_entries = parent->sp_entries; c->sp_count = parent->sp_count;
-    c->sdef_tab = parent->sdef_tab; c->sdef_n = parent->sdef_n;
-    c->qdef_tab = parent->qdef_tab; c->qdef_n = parent->qdef_n; c->t_qdefchunks = parent->t_qdefchunks;
-    c->ik_chain = parent->ik_chain; c->ik_path = parent->ik_path; c->ik_stage_off = parent->ik_stage_off; c->ik_link = parent->ik_link;
-    c->ik_n = parent->ik_n; c->ik_stages = parent->ik_stages;
-    c->mo_clips = parent->mo_clips; c->mo_M = parent->mo_M; c->mo_bone_rec = parent->mo_bone_rec; c->mo_feed_off = parent->mo_feed_off;
-    c->mo_feed_range = parent->mo_feed_range; c->mo_key_interp = parent->mo_key_interp; c->mo_key_frame = parent->mo_key_frame; c->mo_key_pos = parent->mo_key_pos;
-    c->mo_mkey_frame = parent->mo_mkey_frame; c->mo_mkey_weight = parent->mo_mkey_weight; c->mo_feed_ratio = parent->mo_feed_ratio; c->mo_key_rot = parent->mo_key_rot;
-    c->edge = parent->edge; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on;
-    c->I = parent->I;
-    c->t_split = parent->t_split; c->t_unroll = parent->t_unroll; c->t_grid_cap = parent->t_grid_cap; c->t_nt = parent->t_nt; c->t_nts = parent->t_nts;
-    c->t_geo = parent->t_geo; c->t_fast = parent->t_fast; c->t_instloop = parent->t_instloop; c->t_outcap = parent->t_outcap; c->t_instblock = parent->t_instblock;
-    c->t_instorder = parent->t_instorder; c->t_overlap = parent->t_overlap; c->t_zerocopy = parent->t_zerocopy; c->t_pull = parent->t_pull; c->t_fkplain = parent->t_fkplain; c->t_fusefk = parent->t_fusefk;
-    c->t_graph = parent->t_graph; c->tuned_by_search = parent->tuned_by_search; c->t_subsets = parent->t_subsets; c->t_prefetch = parent->t_prefetch;
+    static_cast<RzStatic &>(*c) = *parent;      // borrowed: the lender's pointers, and copies of the host mirrors the plan reads (plan.cpp: ensure_subfk)
+    static_cast<RzTuning &>(*c) = *parent;      // inherited
+    c->I = parent->I; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on; c->tuned_by_search = parent->tuned_by_search;
     c->lender = parent;
     parent->n_forks++;
     int rc = ensure_pose_buffers(c);

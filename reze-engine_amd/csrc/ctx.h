@@ -1,6 +1,8 @@
 // ctx.h — what the translation units of libreze_deform.so's host side share: the context (struct rz_ctx), the error / HIP / RCCL
 // plumbing, the frame plan, and the internal entry points of each unit. Nothing here is part of the C ABI (include/reze_deform.h);
 // everything internal lives in namespace rzi with hidden visibility.
+// The context is three parts, and rz_fork follows them: a fork BORROWS RzStatic (a copy of the struct, the lender's pointers), INHERITS RzTuning
+// (by value), and OWNS everything else (streams, pose slots, palettes, outputs, physics).
 //   core.cpp    context life cycle, buffers every unit sizes, error state            rz_create / rz_destroy / rz_fork / rz_sync ...
 //   upload.cpp  static data: mesh, skeleton, topology, morph targets, motion            rz_upload_* / rz_set_instances / rz_shard_range
 //   pose.cpp    per-frame inputs: pinned ring, zero-copy slots, copies                  rz_set_pose* / rz_override_world / rz_read_world
@@ -82,12 +84,9 @@ int rccl_bind();
 }  // namespace rzi
 using rzi::kStageSlots;
 
-struct rz_ctx {
-    int device = 0;
-    int n_cu = 256;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-
+// Everything rz_upload_* writes and a frame only reads. A new static table goes here and nowhere else: rz_fork copies the struct as a whole and
+// rz_destroy resets a fork's copy as a whole before anything is freed, so a fork neither misses a table nor frees one.
+struct RzStatic {
     // static mesh shard
     uint32_t V = 0, Vp = 0;
     float *geom = nullptr;              // 6 x Vp
@@ -105,19 +104,14 @@ struct rz_ctx {
     int fk_rounds = 0;                  // radix-4 doubling rounds = ceil(log4(depth))
     std::vector<uint4> fk_host;         // host copy of the bone records (w2 is filled in from an_host_range)
     std::vector<uint4> an_host_range, an_host_mrec;     // the motion's per-bone track records / per-morph records (host copies)
-    bool pose_local_t = false;
     // device-side motion sampling (rz_upload_animation / rz_set_pose_sampled)
-    bool has_animation = false, pose_sampled = false;
+    bool has_animation = false;
     uint4 *an_feed_range = nullptr;     // (first key, end, first frame, last frame) per morph feed
     uint32_t *an_feed_off = nullptr;
     float *an_key_frame = nullptr, *an_key_pos = nullptr, *an_mkey_frame = nullptr, *an_mkey_weight = nullptr, *an_feed_ratio = nullptr;
     float4 *an_key_rot = nullptr;
     uint4 *an_key_interp = nullptr;
     uint32_t an_M = 0;                  // vertex-morph count the feeds were built for
-    float *an_frames = nullptr;         // [I]
-    bool frames_inline = false;         // one character: the frame rides in the kernel arguments (frame0), nothing is uploaded
-    float frame0 = 0.0f;
-    size_t an_frames_alloc = 0;          // the current local pose carries translations (behind the rotations in its slot)
     // the motion library (rz_upload_motions / rz_set_pose_blended; kernels/motion.hip): the keys of all clips concatenated, per clip one
     // 16-byte track record per bone and M + 1 feed offsets. Independent of the single motion above; borrowed by forks.
     uint32_t mo_clips = 0, mo_M = 0;    // clips resident (0 = no library) / vertex-morph count the feeds were built for
@@ -126,6 +120,55 @@ struct rz_ctx {
     uint4 *mo_feed_range = nullptr, *mo_key_interp = nullptr;
     float *mo_key_frame = nullptr, *mo_key_pos = nullptr, *mo_mkey_frame = nullptr, *mo_mkey_weight = nullptr, *mo_feed_ratio = nullptr;
     float4 *mo_key_rot = nullptr;
+    // PMX bone morphs (rz_upload_bone_morphs): entries grouped by bone, ascending morph index inside a bone
+    uint32_t *bm_off = nullptr, *bm_morph = nullptr;
+    float4 *bm_rot = nullptr, *bm_tr = nullptr;
+    uint32_t bm_count = 0;
+    // SDEF vertices of this shard (rz_upload_sdef): [10][sdef_n] planes (kernels/sdef.hip); null = every vertex is skinned as the frame kernel skins it
+    uint32_t *sdef_tab = nullptr;
+    uint32_t sdef_n = 0;
+    // QDEF vertices of this shard (rz_upload_qdef): [qdef_n] indices (kernels/qdef.hip); null = every vertex is skinned as the frame kernel skins it
+    uint32_t *qdef_tab = nullptr;
+    uint32_t qdef_n = 0;
+    std::vector<uint32_t> sdef_idx_host, qdef_idx_host;     // the two tables' vertex lists (a vertex may be in one of them only); read by the two uploads only, which a fork is refused
+    // PMX IK chains of this skeleton (rz_upload_ik), grouped into stages (deform_kernels.h: RzIkParams); ik_n = 0: no IK stage, rz_fk_kernel as ever
+    uint4 *ik_chain = nullptr;
+    uint32_t *ik_path = nullptr, *ik_stage_off = nullptr;
+    float4 *ik_link = nullptr;
+    uint32_t ik_n = 0, ik_stages = 0;
+    // morphs
+    int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
+    uint32_t M = 0, Mpad = 12;
+    float *dense = nullptr;             // M x 3 x Vp
+    uint32_t *sp_ptr = nullptr;         // Vp + 1
+    float4 *sp_entries = nullptr;
+    uint64_t sp_count = 0;
+    float *edge = nullptr;              // Vp: the fused hull consumer's edge scale
+    uint64_t fk_gen = 0;                // bumped when the hierarchy's static block is rebuilt
+};
+
+// The settable tuning keys (tune.cpp: kTuneKeys names each one; 0 / -1 = automatic). A fork starts with its lender's values.
+struct RzTuning {
+    int t_split = 0, t_unroll = 0, t_grid_cap = 0, t_nt = 1, t_nts = -1, t_geo = 0, t_fast = -1, t_instloop = -1, t_outcap = -1, t_instblock = 0, t_instorder = 1, t_overlap = -1, t_zerocopy = -1, t_fusefk = -1, t_qdefchunks = 0;
+    int t_fkplain = -1;                 // "fuse_fk_plain": -1 / 1 = the fused frame of a plain pose runs the specialised kernel variant, 0 = always the generic one
+    int t_pull = -1;                    // "pose_pull": -1 = world-matrix poses, 1 = every pose of more than 256 KB, 0 = hipMemcpyAsync of the pose as the host handed it over
+    int t_prefetch = -1;                // "pose_prefetch": -1 / 1 on, 0 off
+    int t_subsets = -1;                 // "inst_subsets": -1 / 1 = stage only the bones a vertex run names when that is a gain, 0 = always the whole palette
+    int t_graph = 0;                    // "graph" tuning key: rz_deform_n replays captured hipGraphs of kGraphFrames frames
+};
+
+struct rz_ctx : RzStatic, RzTuning {
+    int device = 0;
+    int n_cu = 256;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+
+    bool pose_local_t = false;          // the current local pose carries translations (behind the rotations in its slot)
+    bool pose_sampled = false;          // the current pose is sampled on the device from the uploaded motion (rz_set_pose_sampled)
+    float *an_frames = nullptr;         // [I]
+    bool frames_inline = false;         // one character: the frame rides in the kernel arguments (frame0), nothing is uploaded
+    float frame0 = 0.0f;
+    size_t an_frames_alloc = 0;
     RzMotionState *mo_states = nullptr; // [I] per-frame states of a crowd (this context's own, never borrowed)
     size_t mo_states_alloc = 0;
     hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states
@@ -137,22 +180,6 @@ struct rz_ctx {
     float *ovr_world = nullptr;
     uint32_t ovr_count = 0;
     size_t ovr_alloc = 0, ovr_off_alloc = 0;
-    // PMX bone morphs (rz_upload_bone_morphs): entries grouped by bone, ascending morph index inside a bone
-    uint32_t *bm_off = nullptr, *bm_morph = nullptr;
-    float4 *bm_rot = nullptr, *bm_tr = nullptr;
-    uint32_t bm_count = 0;
-    // SDEF vertices of this shard (rz_upload_sdef): [10][sdef_n] planes (kernels/sdef.hip); null = every vertex is skinned as the frame kernel skins it
-    uint32_t *sdef_tab = nullptr;
-    uint32_t sdef_n = 0;
-    // QDEF vertices of this shard (rz_upload_qdef): [qdef_n] indices (kernels/qdef.hip); null = every vertex is skinned as the frame kernel skins it
-    uint32_t *qdef_tab = nullptr;
-    uint32_t qdef_n = 0;
-    std::vector<uint32_t> sdef_idx_host, qdef_idx_host;     // the two tables' vertex lists (a vertex may be in one of them only); empty on a fork
-    // PMX IK chains of this skeleton (rz_upload_ik), grouped into stages (deform_kernels.h: RzIkParams); ik_n = 0: no IK stage, rz_fk_kernel as ever
-    uint4 *ik_chain = nullptr;
-    uint32_t *ik_path = nullptr, *ik_stage_off = nullptr;
-    float4 *ik_link = nullptr;
-    uint32_t ik_n = 0, ik_stages = 0;
 
     // rigid-body physics (rz_upload_physics; physics_host.cpp, kernels/physics.hip): static records, per-instance state, and what the next step
     // must do first. ph_nb = 0: no table. With a table the override table above is physics' own ([I][ph_nd] slots, fixed addresses).
@@ -165,13 +192,6 @@ struct rz_ctx {
     std::vector<int> ph_dyn_bone;       // [ph_nd] bones of the dynamic bodies
     std::vector<uint8_t> ph_group;      // [ph_nb] collision group and mask as uploaded: kept for a contact stage, read by nothing yet
     std::vector<uint16_t> ph_mask;
-    // morphs
-    int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
-    uint32_t M = 0, Mpad = 12;
-    float *dense = nullptr;             // M x 3 x Vp
-    uint32_t *sp_ptr = nullptr;         // Vp + 1
-    float4 *sp_entries = nullptr;
-    uint64_t sp_count = 0;
 
     // per-frame state
     uint32_t I = 1;
@@ -226,7 +246,6 @@ struct rz_ctx {
     float *out_pos = nullptr, *out_nrm = nullptr;
     size_t out_alloc_floats = 0;
     // fused consumers
-    float *edge = nullptr;              // Vp
     float *out_hull = nullptr;          // I x Vp x 3
     size_t hull_alloc_floats = 0;
     uint32_t *aabb = nullptr;           // I x 2 x 6 keys
@@ -241,8 +260,6 @@ struct rz_ctx {
     size_t stage_bytes = 0;
     // Crowd poses (more than 256 KB) are PULLED out of the ring slot by rz_pull_pose_kernel on the upload stream instead of copied by
     // hipMemcpyAsync, world matrices as their upper three rows (pose.cpp: upload_pose_copy)
-    int t_fkplain = -1;                 // "fuse_fk_plain": -1 / 1 = the fused frame of a plain pose runs the specialised kernel variant, 0 = always the generic one
-    int t_pull = -1;                    // "pose_pull": -1 = world-matrix poses, 1 = every pose of more than 256 KB, 0 = hipMemcpyAsync of the pose as the host handed it over
     bool last_upload_pulled = false, last_upload_rows = false;      // what the most recent copy upload did (rz_get_tuning: pose_pulled / pose_rows)
     hipEvent_t stage_ev[kStageSlots] = {};
     bool stage_used[kStageSlots] = {};
@@ -273,7 +290,6 @@ struct rz_ctx {
     uint32_t zc_epoch = 0;
     uint64_t zc_seq_cur = 0;            // sequence number of the current pose (0 = not prefetchable)
     uint64_t *zc_tag = nullptr;         // device: [2], one per pose block
-    int t_prefetch = -1;                // "pose_prefetch": -1 / 1 on, 0 off
     int zc_cur = -1;                    // slot of the current pose, -1 = the current pose came down as a copy
     bool zc_local = false;              // layout of that slot: [weights | rotations | translations] or [world | weights]
     int zc_kind = 0;                    // 0 world, 1 local rotations, 2 local rotations + translations (part of the sequence number)
@@ -292,8 +308,7 @@ struct rz_ctx {
     // count < 0 means "more than kKargMorphs active: use the prep kernel"
     RzMorphList ml;
 
-    // tuning (0 / -1 = automatic)
-    int t_split = 0, t_unroll = 0, t_grid_cap = 0, t_nt = 1, t_nts = -1, t_geo = 0, t_fast = -1, t_instloop = -1, t_dbg = 0, t_outcap = -1, t_instblock = 0, t_instorder = 1, t_overlap = -1, t_zerocopy = -1, t_fusefk = -1, t_qdefchunks = 0;
+    int t_dbg = 0;                      // "dbg": ablation switches of the tools-only build; not in RzTuning, a fork starts without them
     // Bone-subset crowd frames: per vertex run of the CURRENT launch shape, the ascending list of bones the run's
     // vertices name, and the joints rewritten as slots of that list. Derived from the static mesh, rebuilt (one small kernel +
     // one readback of the counts) whenever the shape (vertices per run, runs), the mesh or the skeleton changes.
@@ -303,7 +318,6 @@ struct rz_ctx {
     size_t sub_list_alloc = 0, sub_count_alloc = 0;
     uint32_t sub_per = 0, sub_runs = 0, sub_B = 0, sub_max = 0;
     bool sub_valid = false;
-    int t_subsets = -1;                 // "inst_subsets": -1 / 1 = stage only the bones a vertex run names when that is a gain, 0 = always the whole palette
     bool palette_stale = false;         // the last crowd frame formed its palettes in LDS only (subset form): rz_read_palette forms them on demand
     // Crowd frames of device-animated poses with the hierarchy solved in the skin kernel's front (kernels/crowd.hip:
     // rz_skin_instances_fk_kernel): per vertex run the closure of its named bones under "parent of", one 80-byte record per closure
@@ -314,9 +328,8 @@ struct rz_ctx {
     uint32_t subfk_stride = 0, subfk_rounds = 0;
     bool subfk_valid = false;
     uint64_t subfk_sub_gen = 0, subfk_fk_gen = 0;   // what it was built against
-    uint64_t sub_gen = 0, fk_gen = 0;               // bumped when the run lists / the hierarchy's static block are rebuilt
+    uint64_t sub_gen = 0;               // bumped when the run lists are rebuilt (RzStatic::fk_gen: the hierarchy's static block)
     bool fk_stale = false;              // the last crowd frame solved its hierarchy in LDS only: rz_read_world / rz_read_palette run rz_fk_kernel on demand
-    int t_graph = 0;                    // "graph" tuning key: rz_deform_n replays captured hipGraphs of kGraphFrames frames
     hipGraphExec_t graph_exec = nullptr;
     uint64_t graph_sig = 0;             // signature of everything the captured launches depend on
     bool tuned_by_search = false;       // rz_autotune set morph_split / grid_cap / inst_loop for the CURRENT mesh, morphs and instance count
@@ -329,9 +342,8 @@ struct rz_ctx {
     // peer-direct gather (rz_gather_direct): this context's kernels store straight into the root's gathered buffer
     float *ext_pos = nullptr, *ext_nrm = nullptr;
     rz_ctx *gather_root = nullptr;              // set on every contributor (the root contributes too)
-    // rz_fork: a fork borrows every STATIC device buffer of its lender (mesh, skeleton, topology, morph targets, bone morphs,
-    // motion, edge scale) and owns everything per-frame (streams, pose slots, palettes, outputs). While forks exist neither
-    // side may replace static data.
+    // rz_fork: a fork borrows RzStatic, inherits RzTuning, and owns everything else. While forks exist neither side may replace static
+    // data (static_unlocked), and physics, whose tables live in this struct and not in RzStatic, is refused on both (physics_usable).
     rz_ctx *lender = nullptr;
     int n_forks = 0;
 #ifdef RZ_ABLATE

@@ -3,6 +3,50 @@
 
 using namespace rzi;
 
+namespace {
+
+// The settable keys: name, member of RzTuning, and a check that leaves the value to store in v (normalised where the key says so) or
+// refuses it: RZ_ERR_INVALID with the row's message, RZ_ERR_UNSUPPORTED for a kernel variant only the tools-only build carries.
+// shape: the key is part of the launch shape rz_autotune searches, so setting it clears tuned_by_search.
+// kAlways clears it even when the value is then refused as invalid: deliberate, kept for compatibility, not an accident. kAccepted: only with the store.
+enum { kNo, kAlways, kAccepted };
+struct TuneKey { const char *name; int RzTuning::*field; int (*check)(int &v); const char *refusal; int shape; };
+int tools_only(bool selected) { return selected && !rz_has_all_variants() ? RZ_ERR_UNSUPPORTED : RZ_OK; }
+int need(bool ok) { return ok ? RZ_OK : RZ_ERR_INVALID; }
+template <int lo, int hi> int within(int &v) { return need(v >= lo && v <= hi); }
+const TuneKey kTuneKeys[] = {
+    { "morph_split", &RzTuning::t_split, [](int &v) { return need(v == 0 || v == 1 || v == 2 || v == 4 || v == 8); }, "morph_split must be 0 (auto),1,2,4,8", kAlways },
+    { "unroll", &RzTuning::t_unroll, [](int &v) { return v == 4 ? tools_only(true) : need(v == 0 || v == 8); }, "unroll must be 0 (auto), 4 or 8", kNo },
+    { "grid_cap", &RzTuning::t_grid_cap, [](int &v) { return need(v >= 0); }, "grid_cap must be >= 0", kAlways },
+    { "nontemporal", &RzTuning::t_nt, [](int &v) { v = v ? 1 : 0; return tools_only(v == 0); }, nullptr, kNo },
+    { "geo_lds", &RzTuning::t_geo, [](int &v) { v = v ? 1 : 0; return tools_only(v != 0); }, nullptr, kNo },
+    { "nt_store", &RzTuning::t_nts, [](int &v) { v = v < 0 ? -1 : (v ? 1 : 0); return (int)RZ_OK; }, nullptr, kNo },
+    { "out_cap", &RzTuning::t_outcap, within<-1, 2048>, "out_cap must be -1 (auto), 0 (off) or 64..2048 vertices per wave", kNo },
+    { "graph", &RzTuning::t_graph, within<0, 1>, "graph must be 0 or 1", kNo },
+    { "inst_loop", &RzTuning::t_instloop, [](int &v) { return v == 9 ? tools_only(true) : need(v >= -1 && v != 1 && v <= 64); },
+      "inst_loop must be -1 (auto), 0 (off), 2..8 / 10..64 (poses per workgroup, LDS form) or 9 (register form)", kAlways },
+    { "pose_prefetch", &RzTuning::t_prefetch, within<-1, 1>, "pose_prefetch must be -1 (auto = on), 0 (a zero-copy frame never stages the next pose) or 1", kNo },
+    { "inst_subsets", &RzTuning::t_subsets, within<-1, 1>, "inst_subsets must be -1 (auto = on), 0 (crowd frames always stage the whole palette) or 1", kNo },
+    { "fuse_fk", &RzTuning::t_fusefk, within<-1, 1>, "fuse_fk must be -1 (auto), 0 (always rz_fk_kernel in front) or 1 (every device-animated single character)", kNo },
+    { "zero_copy", &RzTuning::t_zerocopy, within<-1, 1>, "zero_copy must be -1 (auto = on for one character), 0 (every pose is copied to the device) or 1", kNo },
+    { "fuse_fk_plain", &RzTuning::t_fkplain, within<-1, 1>, "fuse_fk_plain must be -1 (auto = on), 0 (the fused frame always runs the generic hierarchy solve) or 1", kNo },
+    { "pose_pull", &RzTuning::t_pull, within<-1, 1>,
+      "pose_pull must be -1 (auto: a crowd's world matrices are pulled, local rotations copied), 0 (every pose is copied by hipMemcpyAsync as it was handed over) or 1 (every pose of more than 256 KB is pulled)", kNo },
+    { "overlap", &RzTuning::t_overlap, within<-1, 1>, "overlap must be -1 (auto = off), 0 (off) or 1 (crowds: front kernels on the upload stream)", kNo },
+    { "inst_order", &RzTuning::t_instorder, within<0, 1>, "inst_order must be 0 (an XCD takes one vertex run of every pose group) or 1 (every vertex run of its pose groups)", kNo },
+    { "inst_block", &RzTuning::t_instblock, [](int &v) { return need(v == 0 || v == 256 || v == 512 || v == 1024); }, "inst_block must be 0 (auto), 256, 512 or 1024 threads per workgroup", kAccepted },
+    { "qdef_chunks", &RzTuning::t_qdefchunks, within<0, 64>, "qdef_chunks must be 0 (auto) or 1..64 chunks of 256 QDEF vertices per workgroup", kNo },
+    { "fast", &RzTuning::t_fast, [](int &) { return (int)RZ_OK; }, nullptr, kNo },      // -1 auto, 0 never (always prep kernel), 1 when possible
+};
+const TuneKey *find_key(const char *key)
+{
+    for (const TuneKey &k : kTuneKeys)
+        if (!strcmp(key, k.name)) return &k;
+    return nullptr;
+}
+
+}  // namespace
+
 extern "C" {
 
 int rz_autotune_measure(rz_ctx *c, uint32_t frames, rz_tune_entry *table, int cap, int *count)
@@ -155,85 +199,31 @@ int rz_autotune(rz_ctx *c, uint32_t frames)
 int rz_set_tuning(rz_ctx *c, const char *key, int value)
 {
     if (!c || !key) return fail(RZ_ERR_INVALID, "null argument");
-    // variants that were measured slower everywhere are compiled into the tools-only build (make variants), not the product
-    if (!rz_has_all_variants() && ((!strcmp(key, "unroll") && value == 4) || (!strcmp(key, "geo_lds") && value != 0) ||
-                                   (!strcmp(key, "nontemporal") && value == 0) || (!strcmp(key, "inst_loop") && value == 9)))
-        return fail(RZ_ERR_UNSUPPORTED, "%s = %d selects a kernel variant the product library does not carry (tools-only build: make -C reze-engine_amd/csrc variants)", key, value);
-    if (!strcmp(key, "morph_split") || !strcmp(key, "grid_cap") || !strcmp(key, "inst_loop")) c->tuned_by_search = false;   // the caller owns the shape now
-    if (!strcmp(key, "morph_split")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-            return fail(RZ_ERR_INVALID, "morph_split must be 0 (auto),1,2,4,8");
-        c->t_split = value;
-    } else if (!strcmp(key, "unroll")) {
-        if (value != 0 && value != 4 && value != 8) return fail(RZ_ERR_INVALID, "unroll must be 0 (auto), 4 or 8");
-        c->t_unroll = value;
-    } else if (!strcmp(key, "grid_cap")) {
-        if (value < 0) return fail(RZ_ERR_INVALID, "grid_cap must be >= 0");
-        c->t_grid_cap = value;
-    } else if (!strcmp(key, "nontemporal")) {
-        c->t_nt = value ? 1 : 0;
-    } else if (!strcmp(key, "geo_lds")) {
-        c->t_geo = value ? 1 : 0;
-    } else if (!strcmp(key, "nt_store")) {
-        c->t_nts = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (!strcmp(key, "out_cap")) {
-        if (value < -1 || value > 2048) return fail(RZ_ERR_INVALID, "out_cap must be -1 (auto), 0 (off) or 64..2048 vertices per wave");
-        c->t_outcap = value;
-    } else if (!strcmp(key, "graph")) {
-        if (value < 0 || value > 1) return fail(RZ_ERR_INVALID, "graph must be 0 or 1");
-        c->t_graph = value;
-    } else if (!strcmp(key, "dbg")) {
+    if (!strcmp(key, "dbg")) {
 #ifdef RZ_ABLATE
         c->t_dbg = value;
+        return RZ_OK;
 #else
         // ablation modes (they make the kernels skip work, i.e. emit garbage) are compiled into the tools-only build only
         return fail(RZ_ERR_INVALID, "tuning key 'dbg' does not exist in the product library (tools-only build: make -C reze-engine_amd/csrc ablate)");
 #endif
-    } else if (!strcmp(key, "inst_loop")) {
-        if (value < -1 || value == 1 || value > 64) return fail(RZ_ERR_INVALID, "inst_loop must be -1 (auto), 0 (off), 2..8 / 10..64 (poses per workgroup, LDS form) or 9 (register form)");
-        c->t_instloop = value;
-    } else if (!strcmp(key, "pose_prefetch")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "pose_prefetch must be -1 (auto = on), 0 (a zero-copy frame never stages the next pose) or 1");
-        c->t_prefetch = value;
-    } else if (!strcmp(key, "inst_subsets")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "inst_subsets must be -1 (auto = on), 0 (crowd frames always stage the whole palette) or 1");
-        c->t_subsets = value;
-    } else if (!strcmp(key, "fuse_fk")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "fuse_fk must be -1 (auto), 0 (always rz_fk_kernel in front) or 1 (every device-animated single character)");
-        c->t_fusefk = value;
-    } else if (!strcmp(key, "zero_copy")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "zero_copy must be -1 (auto = on for one character), 0 (every pose is copied to the device) or 1");
-        c->t_zerocopy = value;
-    } else if (!strcmp(key, "fuse_fk_plain")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "fuse_fk_plain must be -1 (auto = on), 0 (the fused frame always runs the generic hierarchy solve) or 1");
-        c->t_fkplain = value;
-    } else if (!strcmp(key, "pose_pull")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "pose_pull must be -1 (auto: a crowd's world matrices are pulled, local rotations copied), 0 (every pose is copied by hipMemcpyAsync as it was handed over) or 1 (every pose of more than 256 KB is pulled)");
-        c->t_pull = value;
-    } else if (!strcmp(key, "overlap")) {
-        if (value < -1 || value > 1) return fail(RZ_ERR_INVALID, "overlap must be -1 (auto = off), 0 (off) or 1 (crowds: front kernels on the upload stream)");
-        c->t_overlap = value;
-    } else if (!strcmp(key, "inst_order")) {
-        if (value != 0 && value != 1) return fail(RZ_ERR_INVALID, "inst_order must be 0 (an XCD takes one vertex run of every pose group) or 1 (every vertex run of its pose groups)");
-        c->t_instorder = value;
-    } else if (!strcmp(key, "inst_block")) {
-        if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(RZ_ERR_INVALID, "inst_block must be 0 (auto), 256, 512 or 1024 threads per workgroup");
-        c->t_instblock = value;
-        c->tuned_by_search = false;
-    } else if (!strcmp(key, "qdef_chunks")) {
-        if (value < 0 || value > 64) return fail(RZ_ERR_INVALID, "qdef_chunks must be 0 (auto) or 1..64 chunks of 256 QDEF vertices per workgroup");
-        c->t_qdefchunks = value;
-    } else if (!strcmp(key, "fast")) {
-        c->t_fast = value;        // -1 auto, 0 never (always prep kernel), 1 when possible
-    } else {
-        return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
     }
+    const TuneKey *k = find_key(key);
+    if (!k) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
+    int v = value;
+    const int r = k->check(v);
+    // variants that were measured slower everywhere are compiled into the tools-only build (make variants), not the product
+    if (r == RZ_ERR_UNSUPPORTED) return fail(r, "%s = %d selects a kernel variant the product library does not carry (tools-only build: make -C reze-engine_amd/csrc variants)", key, value);
+    if (k->shape == kAlways || (k->shape == kAccepted && r == RZ_OK)) c->tuned_by_search = false;      // the caller owns the shape now
+    if (r != RZ_OK) return fail(r, "%s", k->refusal);
+    c->*k->field = v;
     return RZ_OK;
 }
 
 int rz_get_tuning(rz_ctx *c, const char *key, int *value)
 {
     if (!c || !key || !value) return fail(RZ_ERR_INVALID, "null argument");
+    if (const TuneKey *k = find_key(key)) { *value = c->*k->field; return RZ_OK; }
     if (!strncmp(key, "effective_", 10)) {
         // (an unknown key is refused BEFORE the work below: it drains the stream and may rebuild the run lists)
         static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones",
@@ -249,25 +239,17 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
             if (int r = ensure_subfk(c)) return r;
         }
     }
-    if (!strcmp(key, "morph_split")) *value = c->t_split;
-    else if (!strcmp(key, "unroll")) *value = c->t_unroll;
-    else if (!strcmp(key, "grid_cap")) *value = c->t_grid_cap;
-    else if (!strcmp(key, "nontemporal")) *value = c->t_nt;
-    else if (!strcmp(key, "geo_lds")) *value = c->t_geo;
-    else if (!strcmp(key, "bones")) *value = (int)c->B;
+    if (!strcmp(key, "bones")) *value = (int)c->B;
     else if (!strcmp(key, "morphs")) *value = (int)c->M;
     else if (!strcmp(key, "instances")) *value = (int)c->I;
     else if (!strcmp(key, "verts")) *value = (int)c->V;
     else if (!strcmp(key, "sdef_verts")) *value = (int)c->sdef_n;
     else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef_n;
-    else if (!strcmp(key, "qdef_chunks")) *value = c->t_qdefchunks;
     else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
     else if (!strcmp(key, "motion_clips")) *value = (int)c->mo_clips;
     else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph_nb;
     else if (!strcmp(key, "physics_joints")) *value = (int)c->ph_nj;
     else if (!strcmp(key, "physics_colours")) *value = (int)c->ph_ncol;
-    else if (!strcmp(key, "nt_store")) *value = c->t_nts;
-    else if (!strcmp(key, "fast")) *value = c->t_fast;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;
     else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;
@@ -276,13 +258,6 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "effective_split")) *value = make_plan(c).v.S;
     else if (!strcmp(key, "effective_unroll")) *value = make_plan(c).v.U;
     else if (!strcmp(key, "effective_fast")) *value = make_plan(c).v.fast ? 1 : 0;
-    else if (!strcmp(key, "inst_loop")) *value = c->t_instloop;
-    else if (!strcmp(key, "inst_block")) *value = c->t_instblock;
-    else if (!strcmp(key, "inst_order")) *value = c->t_instorder;
-    else if (!strcmp(key, "overlap")) *value = c->t_overlap;
-    else if (!strcmp(key, "zero_copy")) *value = c->t_zerocopy;
-    else if (!strcmp(key, "pose_pull")) *value = c->t_pull;
-    else if (!strcmp(key, "fuse_fk_plain")) *value = c->t_fkplain;
     else if (!strcmp(key, "effective_variant")) {
         // the last template argument of the single-mesh frame kernel the next frame launches (kernels/deform_small.hip / deform_dense.hip:
         // launch_one): 0 everything compiled in, 3 without the fused consumers, 1 / 2 without them and with the specialised solve
@@ -295,21 +270,16 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "effective_fk_kind")) { Plan pl; if (int r = frame_plan(c, &pl)) return r; *value = deform_params(c, pl).fk_kind; }
     else if (!strcmp(key, "pose_pulled")) *value = c->last_upload_pulled ? 1 : 0;      // the most recent copied pose came down by rz_pull_pose_kernel ...
     else if (!strcmp(key, "pose_rows")) *value = c->last_upload_rows ? 1 : 0;          // ... its world matrices as three rows per bone
-    else if (!strcmp(key, "fuse_fk")) *value = c->t_fusefk;
     else if (!strcmp(key, "effective_fuse_fk")) { const Plan pl = make_plan(c); *value = (pl.fuse_fk || pl.subfk) ? 1 : 0; }
     else if (!strcmp(key, "effective_closure_bones")) *value = make_plan(c).subfk ? (int)c->subfk_stride : 0;
     else if (!strcmp(key, "pose_resident")) *value = (c->zc_cur < 0 || (c->world_resident && c->mw_resident && c->local_resident)) ? 1 : 0;
     else if (!strcmp(key, "effective_overlap")) *value = want_overlap(c, make_plan(c)) ? 1 : 0;
     else if (!strcmp(key, "effective_inst_block")) *value = make_plan(c).inst_block;
-    else if (!strcmp(key, "out_cap")) *value = c->t_outcap;
-    else if (!strcmp(key, "graph")) *value = c->t_graph;
     else if (!strcmp(key, "effective_out_cap")) *value = (int)make_plan(c).out_cap;
     else if (!strcmp(key, "effective_inst_group")) *value = make_plan(c).inst_group;
     else if (!strcmp(key, "effective_poses_per_wg")) *value = make_plan(c).poses_per_wg;
     else if (!strcmp(key, "effective_grid")) *value = (int)make_plan(c).grid_x;
-    else if (!strcmp(key, "inst_subsets")) *value = c->t_subsets;
     else if (!strcmp(key, "all_variants")) *value = rz_has_all_variants() ? 1 : 0;
-    else if (!strcmp(key, "pose_prefetch")) *value = c->t_prefetch;
     else if (!strcmp(key, "pose_staged")) {
         // did the helper of an earlier frame stage the CURRENT pose in device memory? (synchronises; for tests and tools)
         *value = 0;
