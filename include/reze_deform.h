@@ -170,7 +170,7 @@ int rz_upload_qdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx);
  * from a link of the same chain (either would force the whole solve into every step); a goal below one of its own chain's links; a path (outermost
  * link ... effector) of more than 64 bones. With a table the solve runs as rz_fk_ik_kernel in front of the deform / skin kernel: the
  * one-launch forms ("effective_fuse_fk") are not taken, and the skeleton must fit 156 B of LDS per bone. rz_get_tuning("ik_chains") = the
- * count. n_chains = 0 removes the table. Needs rz_upload_skeleton_topology first; a new skeleton or topology drops it; refused while
+ * count, ("ik_stages") = the number of stages the chains were grouped into (the chains of a stage are solved at once). n_chains = 0 removes the table. Needs rz_upload_skeleton_topology first; a new skeleton or topology drops it; refused while
  * forks exist; drops a captured graph. */
 int rz_upload_ik(rz_ctx *ctx, uint32_t n_chains, const uint32_t *goal, const uint32_t *effector, const uint32_t *loops, const float *limit_angle,
                  const uint32_t *link_off, const uint32_t *link_bone, const uint8_t *link_limited, const float *link_min3, const float *link_max3);
@@ -367,7 +367,10 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *   their addresses across steps. The one-launch crowd form is not taken while overrides are resident (as with rz_override_world).
  * rz_physics_reset: every body onto its bone's SOLVED (un-overridden) pose, zero velocities (without a device-solved pose: at the next step).
  * All three are refused while forks exist. rz_read_physics: per body x3 q4 v3 w3 of one instance; blocking; for tests and tools.
- * rz_get_tuning("physics_bodies") / ("physics_joints") / ("physics_colours") = the counts. */
+ * rz_get_tuning("physics_bodies") / ("physics_joints") / ("physics_colours") = the counts; ("physics_block") = the lanes per workgroup the
+ * resident table is solved with (64 when the bodies and the widest colour fit one wave, else 256), ("physics_own") = 1 when every lane keeps
+ * its joint in registers (no more joints than lanes), 0 when lanes stride over a colour, ("physics_lds") = the bytes of LDS per workgroup;
+ * all read-only, 0 without a table. */
 typedef struct rz_physics {
     uint32_t n_bodies;
     const int32_t *bone;                /* [n_bodies] -1 = none */

@@ -250,6 +250,12 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph_nb;
     else if (!strcmp(key, "physics_joints")) *value = (int)c->ph_nj;
     else if (!strcmp(key, "physics_colours")) *value = (int)c->ph_ncol;
+    // the form rz_launch_physics takes for the resident table (kernels/physics.hip): lanes per workgroup, joints kept in registers (1) or
+    // strided over a colour (0), dynamic LDS per workgroup; all 0 without a table
+    else if (!strcmp(key, "physics_block")) *value = c->ph_nb ? c->ph_block : 0;
+    else if (!strcmp(key, "physics_own")) *value = (c->ph_nb && (int)c->ph_nj <= c->ph_block) ? 1 : 0;
+    else if (!strcmp(key, "physics_lds")) *value = c->ph_nb ? (int)rz_physics_lds_bytes((int)c->ph_nb, (int)c->ph_nj, c->ph_block) : 0;
+    else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;
     else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;

@@ -16,13 +16,17 @@ def _quat(axis, ang):
     return np.concatenate([axis * np.sin(ang / 2), [np.cos(ang / 2)]])
 
 
-def strands(n_strands, n_dyn, base=True, seed=1, n_verts=96, free_body=False, sprung=False, cross=False):
+def strands(n_strands, n_dyn, base=True, seed=1, n_verts=96, free_body=False, sprung=False, cross=False, tie=False, boned=None, gravity=None, h=0.0, iterations=0):
     """A root bone carrying `n_strands` chains of `n_dyn` dynamic bones. base=True: every strand hangs from a bone of its own whose body
     follows it; base=False: every strand hangs from ONE following body on the root (joints of one colour then share it). free_body: one more
     dynamic body without joints on a bone of its own. sprung: every joint is limited and has a spring on every axis (a body on a free joint
     without a spring about its own axis keeps whatever twist rounding gives it: its quaternion wanders at 1e-4 while its position holds).
     cross: every dynamic body is also joined to the body at its height on the next strand, as the panels of a skirt are: a loose joint
-    (0.3 units of play per axis, rotation free), so a dynamic body sits in up to four joints and the joints outnumber the bodies."""
+    (0.3 units of play per axis, rotation free), so a dynamic body sits in up to four joints and the joints outnumber the bodies. tie: one
+    more such joint, between the last bodies of the first and the third strand (an odd joint count). boned: only the dynamic bodies of the
+    first `boned` strands drive bones of their own; those of the other strands have bone = -1 and are placed by their offsets in model
+    space (a table may hold more bodies than the hierarchy solve takes bones). gravity, h, iterations: the table's parameters (None / 0 =
+    the defaults)."""
     rng = np.random.default_rng(seed)
     parents, bind, bodies, joints = [-1, 0], [[0.0, 0.0, 0.0], [0.0, 16.0, 0.0]], [], []        # a centre bone at the origin, a head at MMD height
     level = []                      # [strand][k] = (body, model-space position of its bone)
@@ -44,34 +48,43 @@ def strands(n_strands, n_dyn, base=True, seed=1, n_verts=96, free_body=False, sp
                                offset_pos=[0, 0, 0], offset_rot=_quat(rng.normal(size=3), rng.uniform(-0.3, 0.3))))
             parent_body = len(bodies) - 1
             at = np.zeros(3)
+        has_bone = boned is None or s < boned
+        parent_pos = pos[parent_bone]
         for k in range(n_dyn):
             step = at + (np.array([0.0, -1.0, 0.0]) if (k or base) else np.zeros(3))
-            parents.append(parent_bone); bind.append(list(step))
-            b = len(parents) - 1
-            pos.append(pos[parent_bone] + step)
+            here = parent_pos + step
+            b = -1
+            if has_bone:
+                parents.append(parent_bone); bind.append(list(step))
+                b = len(parents) - 1
+                pos.append(here)
             shape = (s + k) % 3
             size = [[0.5, 0, 0], [0.3, 0.5, 0.3], [0.3, 0.6, 0]][shape]
             bodies.append(dict(bone=b, type=1, shape=shape, size=size, mass=float(rng.uniform(0.5, 2.0)),
                                linear_damping=float(rng.uniform(0.98, 0.9995)), angular_damping=float(rng.uniform(0.98, 0.9995)),
-                               offset_pos=[0, -0.5, 0], offset_rot=_quat(rng.normal(size=3), rng.uniform(-0.4, 0.4))))
+                               offset_pos=[0, -0.5, 0] if has_bone else list(here + [0, -0.5, 0]), offset_rot=_quat(rng.normal(size=3), rng.uniform(-0.4, 0.4))))
             kind = 2 + s % 2 if sprung else (s + 2 * k) % 4
             lim = float(rng.uniform(0.3, 0.8))
-            joints.append(dict(body_a=parent_body, body_b=len(bodies) - 1, position=list(pos[b]), rotation=list(rng.uniform(-0.5, 0.5, size=3)),
+            joints.append(dict(body_a=parent_body, body_b=len(bodies) - 1, position=list(here), rotation=list(rng.uniform(-0.5, 0.5, size=3)),
                                rotation_min=FREE_MIN if kind == 0 else [-lim, -lim / 2, -lim], rotation_max=FREE_MAX if kind == 0 else [lim, lim / 2, lim],
                                spring_rotation=[0, 0, 0] if kind == 1 else [float(rng.choice([50, 200] if sprung else [0, 50, 200])) for _ in range(3)],
                                spring_position=[0, 0, 0]))
-            level[s].append((len(bodies) - 1, pos[b]))
-            parent_bone, parent_body, at = b, len(bodies) - 1, np.zeros(3)
+            level[s].append((len(bodies) - 1, here))
+            parent_bone, parent_body, at, parent_pos = (b if has_bone else parent_bone), len(bodies) - 1, np.zeros(3), here
     if cross:
         for s in range(n_strands):
             for k in range(n_dyn):
                 (a, pa), (b, pb) = level[s][k], level[(s + 1) % n_strands][k]
                 joints.append(dict(body_a=a, body_b=b, position=list((pa + pb) / 2), rotation=[0, 0, 0], position_min=[-0.3] * 3, position_max=[0.3] * 3,
                                    rotation_min=FREE_MIN, rotation_max=FREE_MAX, spring_rotation=[0, 0, 0], spring_position=[0, 0, 0]))
+    if tie:
+        (a, pa), (b, pb) = level[0][-1], level[2][-1]
+        joints.append(dict(body_a=a, body_b=b, position=list((pa + pb) / 2), rotation=[0, 0, 0], position_min=[-0.6] * 3, position_max=[0.6] * 3,
+                           rotation_min=FREE_MIN, rotation_max=FREE_MAX, spring_rotation=[0, 0, 0], spring_position=[0, 0, 0]))
     if free_body:
         parents.append(1); bind.append([0.0, -3.0, 0.0]); pos.append(pos[1] + [0, -3.0, 0])
         bodies.append(dict(bone=len(parents) - 1, type=1, shape=0, size=[0.5, 0, 0], mass=1.0, linear_damping=0.9, angular_damping=0.9))
-    return _scene(parents, bind, bodies, joints, rng, n_verts)
+    return _scene(parents, bind, bodies, joints, rng, n_verts, gravity=gravity, h=h, iterations=iterations)
 
 
 def single_body(n_verts=64):
@@ -81,6 +94,71 @@ def single_body(n_verts=64):
     bodies = [dict(bone=2, type=1, shape=1, size=[0.3, 0.4, 0.5], mass=2.0, linear_damping=0.9, angular_damping=0.9, offset_pos=[0.1, -0.2, 0.0],
                    offset_rot=_quat([1, 2, 3], 0.3))]
     return _scene(parents, bind, bodies, [], rng, n_verts)
+
+
+def falling_bodies(n_bodies, n_boned=100, seed=11, n_verts=300):
+    """`n_bodies` dynamic bodies and no joint: the first `n_boned` on bones of their own under the head (their bones fall with them), the
+    rest with bone = -1, placed by their offsets in model space. The largest table the LDS takes when no joint needs a multiplier."""
+    rng = np.random.default_rng(seed)
+    parents, bind, bodies = [-1, 0], [[0.0, 0.0, 0.0], [0.0, 16.0, 0.0]], []
+    for k in range(n_bodies):
+        at = [float(x) for x in rng.uniform(-4.0, 4.0, size=3)]
+        bone = -1
+        if k < n_boned:
+            parents.append(1); bind.append(at)
+            bone, at = len(parents) - 1, [0.0, -0.2, 0.0]
+        shape = k % 3
+        bodies.append(dict(bone=bone, type=1, shape=shape, size=[[0.4, 0, 0], [0.3, 0.4, 0.2], [0.2, 0.5, 0]][shape], mass=float(rng.uniform(0.5, 2.0)),
+                           linear_damping=float(rng.uniform(0.5, 0.99)), angular_damping=float(rng.uniform(0.5, 0.99)), offset_pos=at,
+                           offset_rot=_quat(rng.normal(size=3), rng.uniform(-0.5, 0.5))))
+    return _scene(parents, bind, bodies, [], rng, n_verts)
+
+
+def contents(n_verts=64, seed=12):
+    """What a table may hold beside strands, in 8 bodies and 6 joints:
+      body 0  follows nothing (bone = -1): an anchor fixed in model space            joint 0  0 - 1   the hanging body; sprung, limited
+      body 1  dynamic, bone = -1: hangs from the anchor, overrides no bone            joint 1  2 - 3   rotation limits given max first
+      body 2  follows bone 2                                                         joint 2  3 - 4   position play + rotation limits + springs
+      body 3  dynamic on bone 3, linear and angular damping 1.0                       joint 3  2 - 5   between two followers: nothing to move
+      body 4  dynamic on bone 4, damping 0.0                                          joint 4  5 - 6   the zero-inertia sphere under a follower, limits
+      body 5  type 2 on bone 5 (dynamic + bone: follows)                                       of 0.02 rad and springs: K = 0, det K = 0, skipped
+      body 6  dynamic on bone 6, a sphere of size 0 (no inertia: nothing turns it)    joint 5  6 - 7   a body under the sphere: K = its own inertia
+      body 7  dynamic on bone 7"""
+    rng = np.random.default_rng(seed)
+    parents = [-1, 0, 1, 2, 3, 1, 5, 6]
+    bind = [[0, 0, 0], [0, 16, 0], [1, 0, 0], [0, -1, 0], [0, -1, 0], [-1, 0, 0], [0, -1, 0], [0, -1, 0]]
+    bp = ik_ref.bind_positions(parents, bind)
+    dyn = dict(type=1, shape=1, size=[0.3, 0.5, 0.3], mass=1.0, linear_damping=0.99, angular_damping=0.99, offset_pos=[0, -0.5, 0])
+    bodies = [dict(bone=-1, type=0, shape=0, size=[0.2, 0, 0], mass=0.0, offset_pos=[0.0, 17.0, 1.0], offset_rot=_quat([0, 1, 0], 0.3)),
+              dict(dyn, bone=-1, offset_pos=[0.0, 16.0, 1.0], offset_rot=_quat([1, 0, 1], 0.2), mass=1.5),
+              dict(bone=2, type=0, shape=1, size=[0.2, 0.2, 0.2], mass=0.0, offset_rot=_quat([0, 0, 1], 0.2)),
+              dict(dyn, bone=3, linear_damping=1.0, angular_damping=1.0, offset_rot=_quat([1, 2, 0], 0.3)),
+              dict(dyn, bone=4, linear_damping=0.0, angular_damping=0.0, shape=2, size=[0.25, 0.6, 0], offset_rot=_quat([0, 1, 1], -0.2)),
+              dict(bone=5, type=2, shape=0, size=[0.3, 0, 0], mass=1.0, offset_rot=_quat([1, 0, 0], 0.25)),
+              dict(dyn, bone=6, shape=0, size=[0.0, 0, 0], mass=0.7, offset_pos=[0, -0.3, 0]),
+              dict(dyn, bone=7, mass=2.0, shape=0, size=[0.4, 0, 0])]
+    lim = dict(rotation_min=[-0.5, -0.25, -0.5], rotation_max=[0.5, 0.25, 0.5])
+    joints = [dict(lim, body_a=0, body_b=1, position=[0.0, 16.6, 1.0], rotation=[0.1, 0.0, -0.2], spring_rotation=[100, 100, 100]),
+              dict(body_a=2, body_b=3, position=list(bp[3]), rotation=[0.2, -0.1, 0.1], rotation_min=[0.6, 0.3, 0.6], rotation_max=[-0.6, -0.3, -0.6], spring_rotation=[50, 50, 50]),
+              dict(lim, body_a=3, body_b=4, position=list(bp[4]), rotation=[-0.1, 0.2, 0.3], position_min=[-0.1, -0.05, -0.1], position_max=[0.1, 0.05, 0.1],
+                   spring_rotation=[200, 50, 200]),
+              dict(lim, body_a=2, body_b=5, position=list((bp[2] + bp[5]) / 2), rotation=[0.3, 0.1, 0.0], spring_rotation=[50, 50, 50]),
+              dict(body_a=5, body_b=6, position=list(bp[6]), rotation=[0.0, 0.3, 0.1], rotation_min=[-0.02] * 3, rotation_max=[0.02] * 3, spring_rotation=[100, 50, 100]),
+              dict(lim, body_a=6, body_b=7, position=list(bp[7]), rotation=[0.1, 0.1, 0.1], spring_rotation=[50, 200, 50])]
+    return _scene(parents, bind, bodies, joints, rng, n_verts)
+
+
+def gimbal(n_verts=64, seed=13):
+    """two dynamic bodies under a following one; the first joint is locked at the gimbal angle (rotation_min.y = rotation_max.y = pi / 2),
+    where the Euler angles' x and z fall together and the branch euler_xyz takes turns on the last bit of one matrix entry"""
+    rng = np.random.default_rng(seed)
+    parents, bind = [-1, 0, 1, 2, 3], [[0, 0, 0], [0, 16, 0], [1, 0, 0], [0, -1, 0], [0, -1, 0]]
+    bp = ik_ref.bind_positions(parents, bind)
+    dyn = dict(type=1, shape=1, size=[0.3, 0.5, 0.3], mass=1.0, linear_damping=0.99, angular_damping=0.99, offset_pos=[0, -0.5, 0])
+    bodies = [dict(bone=2, type=0, shape=0, size=[0.2, 0, 0], mass=0.0), dict(dyn, bone=3, offset_rot=_quat([1, 1, 0], 0.2)), dict(dyn, bone=4, shape=2, size=[0.25, 0.6, 0])]
+    joints = [dict(body_a=0, body_b=1, position=list(bp[3]), rotation=[0.1, 0.2, 0.0], rotation_min=[-0.5, PI / 2, -0.5], rotation_max=[0.5, PI / 2, 0.5], spring_rotation=[50, 50, 50]),
+              dict(body_a=1, body_b=2, position=list(bp[4]), rotation=[0.0, 0.0, 0.1], rotation_min=[-0.5, -0.25, -0.5], rotation_max=[0.5, 0.25, 0.5], spring_rotation=[50, 0, 50])]
+    return _scene(parents, bind, bodies, joints, rng, n_verts)
 
 
 def _scene(parents, bind, bodies, joints, rng, n_verts, gravity=None, h=0.0, iterations=0):
@@ -218,6 +296,20 @@ def write_pmx(scene, seed=0):
     return bytes(out), want
 
 
+CROWD = dict(n_strands=4, n_dyn=5, base=True, seed=7, n_verts=96, free_body=True)
+PARAMS = dict(h=1 / 120, iterations=7, gravity=(3.0, -40.0, 25.0))        # every parameter of a table away from its default
+LDS_LIMIT, LDS_PER_BODY, LDS_PER_JOINT = 160 * 1024, 96, 12
+
+
+def lds_bytes(n_bodies, n_joints):
+    """include/reze_deform.h: 96 B per body, + 12 B per joint once the joints outnumber the lanes (64 when the table fits a wave, else 256);
+    with more than 64 bodies the block is 256"""
+    return n_bodies * LDS_PER_BODY + (n_joints * LDS_PER_JOINT if n_joints > (64 if n_bodies <= 64 else 256) else 0)
+
+
+MOST_STRANDS = (LDS_LIMIT - LDS_PER_BODY) // (LDS_PER_BODY + LDS_PER_JOINT)      # strands of one body under one shared base: 1516
+MOST_BODIES = LDS_LIMIT // LDS_PER_BODY                                           # 1706
+
 SCENES = {
     "one body": lambda: single_body(),
     "63 bodies": lambda: strands(9, 6, base=True, seed=2, n_verts=128),
@@ -225,9 +317,35 @@ SCENES = {
     "wide colour": lambda: strands(260, 1, base=False, seed=4, n_verts=300, sprung=True),
     "skirt": lambda: strands(8, 5, base=True, seed=8, n_verts=100, sprung=True, cross=True),     # 48 bodies, 80 joints: one wave, lanes stride
     "one joint": lambda: strands(1, 1, base=True, seed=6, n_verts=64),
-    "crowd": lambda: strands(4, 5, base=True, seed=7, n_verts=96, free_body=True),
+    "crowd": lambda: strands(**CROWD),
     "ik": lambda: ik_scene(),
+    # the table's parameters: all three set, and one at a time (the rest of the table is the "crowd" scene's)
+    "params": lambda: strands(**CROWD, **PARAMS),
+    "params h": lambda: strands(**CROWD, h=PARAMS["h"]),
+    "params iterations": lambda: strands(**CROWD, iterations=1),       # (1, not 7: 7 passes move these strands by 32 x the bar against 4, 1 pass by 208 x)
+    "params gravity": lambda: strands(**CROWD, gravity=PARAMS["gravity"]),
+    # the counts at which rz_launch_physics changes its form (FORMS below)
+    "64 bodies": lambda: strands(8, 7, base=True, seed=21, n_verts=128),
+    "64 bodies 63 joints": lambda: strands(9, 7, base=False, seed=22, n_verts=128, sprung=True),
+    "64 joints": lambda: strands(8, 4, base=True, seed=23, n_verts=96, sprung=True, cross=True),
+    "65 joints": lambda: strands(8, 4, base=True, seed=24, n_verts=96, sprung=True, cross=True, tie=True),
+    "65 bodies 64 joints": lambda: strands(16, 4, base=False, seed=25, n_verts=130, sprung=True),
+    "256 joints": lambda: strands(128, 2, base=True, seed=26, n_verts=400, sprung=True),
+    "257 joints": lambda: strands(257, 1, base=True, seed=27, n_verts=520, sprung=True),
+    # the largest tables the LDS takes
+    # (the hierarchy solve takes 1 412 bones, 116 B of LDS each: 1 000 strands drive bones, the bodies of the other 516 have none)
+    "most strands": lambda: strands(MOST_STRANDS, 1, base=False, seed=28, n_verts=600, sprung=True, boned=1000),
+    "most bodies": lambda: falling_bodies(MOST_BODIES),
+    "contents": lambda: contents(),
+    "gimbal": lambda: gimbal(),
 }
+# name: (bodies, joints, lanes per workgroup, joints in registers?) — what the upload must choose for the scene
+FORMS = {
+    "64 bodies": (64, 56, 64, 1), "64 bodies 63 joints": (64, 63, 64, 1), "64 joints": (40, 64, 64, 1), "65 joints": (40, 65, 64, 0),
+    "65 bodies 64 joints": (65, 64, 256, 1), "256 joints": (384, 256, 256, 1), "257 joints": (514, 257, 256, 0),
+    "most strands": (MOST_STRANDS + 1, MOST_STRANDS, 256, 0), "most bodies": (MOST_BODIES, 0, 256, 1),
+}
+EDGE_CALLS = (1, 10, 10)            # the largest tables run the crowd's shorter sequence
 _memo = {}
 
 NODE_H, NODE_MAX_SUBSTEPS = 1 / 75, 10
@@ -283,6 +401,11 @@ CROWD_CALLS = (1, 10, 10)
 def crowd_frames(instance, call):
     """every instance at its own frame, one frame on per call"""
     return 1.3 + 2.1 * instance + 1.0 * call
+
+
+def local_crowd_pose(scene, instance, call):
+    """the crowds fed through rz_set_pose_local: every instance at a pose of its own, a new one per call"""
+    return pose(scene, 200 + 10 * call + instance)
 
 
 def world_of(scene, q, t, chains=(), dtype=np.float64):

@@ -52,6 +52,7 @@ int main()
     rzphys::Built o;
     rzphys::build(&t, B, parents.data(), bind.data(), o);
     printf("counts %d %d %d %d %d %d %.9g\n", o.nb, o.nj, o.ncol, o.nd, o.widest, o.iterations, o.h);
+    printf("gravity %.9g %.9g %.9g\n", o.g[0], o.g[1], o.g[2]);
     printf("colour");
     for (int c : o.colour) printf(" %d", c);
     printf("\norder");

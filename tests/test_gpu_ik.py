@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import ik_ref
+import ik_scenes as iks
 from helpers import NRM_TOL, bone_morph_reference, sample_reference
 
 pytestmark = pytest.mark.gpu
@@ -418,6 +419,129 @@ def test_misuse_is_refused_with_a_message(rz, rig):
         bad(c, ch, -6, "ancestor of the effector")
 
 
+# ---- the edges of the launch shape: kernels/ik.hip.h solves a chain with one wave, one path bone per lane, and a stage with four waves ----
+
+def _edge(name):
+    """(mesh, skeleton, chains, poses) of a case of tests/ik_scenes.py, built once"""
+    if name not in _memo:
+        if name.startswith("path of 64"):
+            m = iks.long_chain(64, LONG_LINKS[name])
+            _memo[name] = (m, skel_of(m), m["chains"], iks.poses(m, 0))
+        elif name == "nine legs":
+            m = iks.nine_legs()
+            _memo[name] = (m, skel_of(m), m["chains"], iks.poses(m, 10))
+        elif name == "root link":
+            m = iks.root_link()
+            _memo[name] = (m, skel_of(m), m["chains"], iks.poses(m, 20))
+        elif name == "three stages":
+            m = iks.three_stages()
+            _memo[name] = (m, skel_of(m), m["chains"], iks.poses(m, 30))
+        else:
+            s = _rig()
+            chains = {"limits max first": lambda: iks.swapped(s["chains"], 0, 0), "limit_angle = 0": lambda: [dict(ch, limit_angle=0.0) for ch in s["chains"]],
+                      "limit_angle = 0, no limits": lambda: iks.unlimited(s["chains"], limit_angle=0.0)}[name]()
+            _memo[name] = (s["mesh"], s["sk"], chains, [s["synth"].leg_rig_pose(s["mesh"], 700 + k) for k in range(8)])
+    return _memo[name]
+
+
+LONG_LINKS = {"path of 64, links at 40 20 1": (40, 20, 1), "path of 64, links at 60 1": (60, 1), "path of 64, one link": (1,)}
+EDGES = tuple(LONG_LINKS) + ("nine legs", "root link", "three stages", "limits max first", "limit_angle = 0", "limit_angle = 0, no limits")
+
+
+def _run_edge(rz, oracle, name, I=8):
+    """the case's 8 poses as crowds of I; returns the world matrices of every pose"""
+    m, sk, chains, poses = _edge(name)
+    worlds, worst = [], 0.0
+    with make_ctx(rz, m, chains, instances=I) as c:
+        for k in range(0, len(poses), I):
+            set_local(c, poses[k:k + I])
+            c.deform()
+            worst = max(worst, check(c, oracle, m, sk, chains, poses[k:k + I], "%s, poses %d .. %d" % (name, k, k + I - 1)))
+            worlds += [c.read_world(i) for i in range(I)]
+        info = (c.get_tuning("ik_chains"), c.get_tuning("ik_stages"))
+    print("%s: %d chain(s) in %d stage(s), largest error %.2e x extent" % (name, info[0], info[1], worst))
+    return worlds, info
+
+
+@pytest.mark.parametrize("name", list(LONG_LINKS))
+def test_path_of_64_bones(rz, oracle, name):
+    """The longest path rz_upload_ik accepts: bones 1 .. 64 of a line, the effector in lane P - 1 = 63 (v_readlane of the wave's last lane
+    in every step), links at path bones 40 / 20 / 1, 60 / 1 or bone 1 alone with rigid bones between them, so a step re-solves up to 64
+    bones serially. The IK moves bones by 5 to 17 units. A path of 65 bones is refused."""
+    m, sk, chains, poses = _edge(name)
+    _, info = _run_edge(rz, oracle, name)
+    assert info == (1, 1)
+    plain = ik_ref.solve(sk["parents"], sk["bind"], *poses[0])[0]
+    assert np.abs(ik_ref.solve(sk["parents"], sk["bind"], *poses[0], chains)[0] - plain).max() > 1.0          # (the chain is not at rest)
+    if name == "path of 64, one link":
+        m65 = iks.long_chain(65, (1,))
+        with make_ctx(rz, m65, None) as c:
+            with pytest.raises(rz.RzError) as e:
+                c.upload_ik(m65["chains"])
+            assert e.value.code == -6 and "at most 64" in str(e.value) and "65 bones" in str(e.value), str(e.value)
+            assert c.get_tuning("ik_chains") == 0 and c.get_tuning("ik_stages") == 0
+
+
+def test_a_stage_wider_than_the_block(rz, oracle):
+    """Nine independent two-link legs under one root form ONE stage (ik_stages): the workgroup's four waves stride over it (c += kBlock / 64),
+    so wave 0 solves chains 0, 4 and 8 and every other wave two. As crowds of 4, every instance at its own pose."""
+    _, info = _run_edge(rz, oracle, "nine legs", I=4)
+    assert info == (9, 1)
+
+
+def test_outermost_link_is_a_root_bone(rz, oracle):
+    """par = -1: the chain's outermost link has no parent, the path is re-solved under the identity rows of ik_solve_chain; a limited knee
+    below it, the goal a root bone of its own."""
+    m, _, chains, _ = _edge("root link")
+    assert m["parents"][chains[0]["links"][-1]["bone"]] == -1
+    _, info = _run_edge(rz, oracle, "root link")
+    assert info == (1, 1)
+
+
+def test_limits_given_max_first_are_the_sorted_table(rz, oracle, rig):
+    """The left knee's limits with min and max exchanged: the kernel sorts them per axis (fminf / fmaxf) as the restatement does, so the
+    frame is the bits of the frame under the table as the rig gives it."""
+    m, sk, chains, poses = _edge("limits max first")
+    assert chains[0]["links"][0]["min"][0] > chains[0]["links"][0]["max"][0]
+    swapped, _ = _run_edge(rz, oracle, "limits max first")
+    with make_ctx(rz, m, rig["chains"], instances=len(poses)) as c:
+        set_local(c, poses)
+        c.deform()
+        for i in range(len(poses)):
+            assert np.array_equal(c.read_world(i).view(np.uint32), swapped[i].view(np.uint32)), "pose %d differs under limits given max first" % i
+        w = c.read_world(0)
+        c.upload_ik([])
+        c.deform()
+        assert np.abs(c.read_world(0) - w).max() > 0.1
+
+
+def test_limit_angle_zero(rz, oracle, rig):
+    """A per-step angle of 0: every step turns its link by nothing. Without limits the pose is the plain hierarchy within the bar although
+    all 40 iterations run (a step of angle 0 still counts as a rotation); with the rig's limits the restatement still clamps the straight
+    knee to its maximum of -0.5 degrees (0.05 units at the ankle), and the kernel is held to that."""
+    from helpers import fk_reference
+    m, sk, _, poses = _edge("limit_angle = 0, no limits")
+    worlds, _ = _run_edge(rz, oracle, "limit_angle = 0, no limits")
+    worst = 0.0
+    for (q, t), w in zip(poses, worlds):
+        worst = max(worst, float(np.abs(w - fk_reference(m["parents"], m["bind"], q, t).reshape(-1, 16)).max()) / sk["extent"])
+    print("limit_angle = 0 without limits against the plain hierarchy: %.2e x extent" % worst)
+    assert worst <= BAR
+    _run_edge(rz, oracle, "limit_angle = 0")
+
+
+def test_three_stages_each_on_the_pose_before(rz, oracle):
+    """leg chain, toe chain, and a chain below the toe: the upload orders them into three stages, and each stage starts from the whole
+    skeleton as the stage before left it (ik_resolve). The restatement without the earlier chains differs by far more than the bar."""
+    m, sk, chains, poses = _edge("three stages")
+    _, info = _run_edge(rz, oracle, "three stages")
+    assert info == (3, 3)
+    tip = chains[2]["effector"]
+    full = ik_ref.solve(sk["parents"], sk["bind"], *poses[0], chains)[0]
+    alone = ik_ref.solve(sk["parents"], sk["bind"], *poses[0], chains[2:])[0]
+    assert np.abs(full[tip] - alone[tip]).max() > 100 * BAR * sk["extent"]
+
+
 def _sampled_case(frames_of):
     s = _rig()
     anim = leg_motion(s["mesh"], np.random.default_rng(3))
@@ -435,6 +559,7 @@ CASES = {
     "random tree, rigid": lambda: (_tree()["sk"], tree_chains(_tree(), True), [tree_pose(_tree()["synth"], _tree()["mesh"], 70 + k) for k in range(8)]),
     "append children, 600 bones": lambda: (big_case()[1], big_case()[2], big_case()[5]),
 }
+CASES.update({name: (lambda name=name: _edge(name)[1:]) for name in EDGES})
 
 
 @pytest.mark.skipif(shutil.which("node") is None, reason="node is not installed")

@@ -389,6 +389,205 @@ def test_misuse(rz):
         assert c.get_tuning("physics_bodies") == 0
 
 
+# ---- the edges of the launch shape (kernels/physics.hip: rz_launch_physics) and of what a table may hold ----
+
+def form_of(c):
+    """(lanes per workgroup, joints in registers?, bytes of LDS) of the resident table"""
+    return c.get_tuning("physics_block"), c.get_tuning("physics_own"), c.get_tuning("physics_lds")
+
+
+def run_sequence(rz, oracle, name, calls=ps.CALLS):
+    """the standard sequence on one instance against the reference; returns (errors per call, counts, form, last state)"""
+    sc = ps.scene(name)
+    poses = [ps.pose(sc, k) for k in range(len(calls))]
+    ref = ps.run_reference(sc, poses, calls)
+    errs = []
+    with make_ctx(rz, sc) as c:
+        counts = (c.get_tuning("physics_bodies"), c.get_tuning("physics_joints"), c.get_tuning("physics_colours"))
+        form = form_of(c)
+        for (q, t), n, (rw, rs) in zip(poses, calls, ref):
+            set_local(c, [(q, t)])
+            c.physics_step(n)
+            c.deform()
+            errs.append(errors(c, oracle, sc, 0, rw, rs))
+        st = c.read_physics(0)
+    return errs, counts, form, st
+
+
+@pytest.mark.parametrize("name", ["params", "params h", "params iterations", "params gravity"])
+def test_table_parameters(rz, oracle, name):
+    """h, iterations and gravity3 away from their defaults (RzPhysicsParams h, iterations, gx / gy / gz): all three at once — 1 / 120 s, 7
+    passes, (3, -40, 25) — and one at a time. tests/test_physics_cpu.py: test_every_parameter_moves_the_reference shows that each of them,
+    and each component of gravity, moves the definition by more than 100 x this test's bar."""
+    errs, _, form, _ = run_sequence(rz, oracle, name)
+    assert form == (64, 1, ps.lds_bytes(25, 20))
+    assert_bar(errs, name)
+
+
+@pytest.mark.parametrize("name", [n for n in ps.FORMS if not n.startswith("most")])
+def test_switch_points(rz, oracle, name):
+    """The counts at which the launch changes its form, exactly: block = 64 iff nb <= 64 and the widest colour <= 64; joints in registers
+    iff nj <= block (64 / 65 joints in a wave: lane 63 owns a joint / <64, false>; 256 / 257 joints under 256 lanes); and above 48 KB of
+    LDS ("257 joints": 52 428 B) the launch first raises the kernel's dynamic shared memory limit."""
+    sc = ps.scene(name)
+    nb, nj, block, own = ps.FORMS[name]
+    _, _, ncol = physics_ref.colouring(sc["table"])
+    errs, counts, form, _ = run_sequence(rz, oracle, name)
+    print("%s: %d bodies %d joints %d colours -> %d lanes, joints %s, %d B of LDS" % ((name,) + counts + (form[0], "in registers" if form[1] else "strided", form[2])))
+    assert counts == (nb, nj, ncol) and (sc["table"]["n_bodies"], sc["table"]["n_joints"]) == (nb, nj)
+    assert form == (block, own, ps.lds_bytes(nb, nj))
+    if name == "257 joints":
+        assert form[2] > 48 * 1024
+    assert_bar(errs, name)
+
+
+@pytest.mark.parametrize("name", ["most strands", "most bodies"])
+def test_largest_tables(rz, oracle, name):
+    """The largest tables the upload accepts, from the documented formula — 96 B per body, + 12 B per joint once the joints outnumber the
+    lanes, at most 163 840 B: 1 516 strands of one body under one shared base (1 517 bodies, 1 516 joints in one colour, 163 824 B; 1 000
+    of the strands drive bones, the bodies of the rest have bone = -1, because the hierarchy solve takes 1 412 bones and no more) and
+    1 706 falling bodies without a joint (163 776 B), 100 of them on bones of their own, the rest with bone = -1. Both launch with the
+    raised dynamic shared memory limit. One strand or one body more is refused by the upload."""
+    sc = ps.scene(name)
+    nb, nj, block, own = ps.FORMS[name]
+    lds = ps.lds_bytes(nb, nj)
+    assert (nb, nj) == ((1517, 1516) if name == "most strands" else (1706, 0)) and lds == (163824 if name == "most strands" else 163776)
+    assert lds <= ps.LDS_LIMIT < ps.lds_bytes(nb + 1, nj + (1 if nj else 0))
+    errs, counts, form, st = run_sequence(rz, oracle, name, ps.EDGE_CALLS)
+    print("%s: %d bodies %d joints -> %d lanes, joints %s, %d B of LDS" % (name, counts[0], counts[1], form[0], "in registers" if form[1] else "strided", form[2]))
+    assert counts[:2] == (nb, nj) and form == (block, own, lds)
+    assert_bar(errs, name)
+    more = ps.strands(ps.MOST_STRANDS + 1, 1, base=False, seed=28, n_verts=64, sprung=True, boned=1000) if nj else ps.falling_bodies(ps.MOST_BODIES + 1, n_verts=64)
+    with make_ctx(rz, more, table=False) as c:
+        with pytest.raises(rz.capi.RzError) as e:
+            c.upload_physics(more["table"])
+        assert "too large" in str(e.value) and "%d B of LDS" % ps.lds_bytes(nb + 1, nj + (1 if nj else 0)) in str(e.value), str(e.value)
+        assert c.get_tuning("physics_bodies") == 0 and form_of(c) == (0, 0, 0)
+
+
+@pytest.mark.parametrize("name", ["65 bodies 64 joints", "257 joints"])
+def test_256_lane_forms_in_a_crowd(rz, oracle, name):
+    """<256, true> and <256, false> with inst > 0: three instances, each at a pose of its own through rz_set_pose_local, against the
+    reference per instance (the per-instance state, world and override addressing), and instance I - 2 bit for bit, state and overrides,
+    against the same sequence run alone."""
+    sc = ps.scene(name)
+    I, calls = 3, ps.CROWD_CALLS
+    dyn = physics_ref.prepare(sc["table"], sc["parents"], sc["bind"])["dyn_bodies"]
+    bones = [int(sc["table"]["bone"][b]) for b in dyn]
+    refs = [ps.run_reference(sc, [ps.local_crowd_pose(sc, i, k) for k in range(len(calls))], calls) for i in range(I)]
+    errs = []
+    with make_ctx(rz, sc, instances=I) as c:
+        assert form_of(c)[:2] == ps.FORMS[name][2:]
+        for call, n in enumerate(calls):
+            set_local(c, [ps.local_crowd_pose(sc, i, call) for i in range(I)])
+            c.physics_step(n)
+            c.deform()
+            for i in range(I):
+                errs.append(errors(c, oracle, sc, i, *refs[i][call]))
+        crowd = [(c.read_physics(i), c.read_world(i)) for i in range(I)]
+    assert_bar(errs, "%s, crowd of %d" % (name, I))
+    assert np.abs(crowd[0][0] - crowd[1][0]).max() > 0.01                  # (the instances are not copies of each other)
+    k = I - 2
+    with make_ctx(rz, sc) as c:
+        for call, n in enumerate(calls):
+            set_local(c, [ps.local_crowd_pose(sc, k, call)])
+            c.physics_step(n)
+            c.deform()
+        st, w = c.read_physics(0), c.read_world(0)
+    print("instance %d alone vs in the crowd: state differs by %.2e, overrides by %.2e" % (k, np.abs(st - crowd[k][0]).max(), np.abs(w[bones] - crowd[k][1][bones]).max()))
+    assert np.array_equal(st.view(np.uint32), crowd[k][0].view(np.uint32)) and np.array_equal(w[bones].view(np.uint32), crowd[k][1][bones].view(np.uint32)), \
+        "instance %d of the crowd is not bit-identical to the same sequence run alone" % k
+
+
+def test_table_contents(rz, oracle):
+    """What no strand scene holds (physics_scenes.contents): bone = -1 on a following and on a dynamic body, a type-2 follower, a joint
+    between two followers (det K = 0 in both stages: a no-op, and no NaN), a dynamic sphere of size 0 — zero inertia — under a follower in
+    a limited, sprung joint, dampings of exactly 0 and 1, rotation limits given max first, and position play with rotation limits and
+    springs in one joint. Held to the reference over the standard sequence; the followers' records are their placement."""
+    sc = ps.scene("contents")
+    t = sc["table"]
+    assert t["bone"][0] == -1 and t["bone"][1] == -1 and t["type"][5] == 2 and not physics_ref.is_dynamic(t)[[0, 2, 5]].any() and physics_ref.is_dynamic(t)[[1, 3, 4, 6, 7]].all()
+    assert (t["rotation_min"][1] > t["rotation_max"][1]).all() and t["size"][6][0] == 0 and t["linear_damping"][3] == 1 and t["linear_damping"][4] == 0
+    poses = [ps.pose(sc, k) for k in range(len(ps.CALLS))]
+    ref = ps.run_reference(sc, poses)
+    errs, place = [], 0.0
+    with make_ctx(rz, sc) as c:
+        assert c.get_tuning("physics_bodies") == 8 and c.get_tuning("physics_joints") == 6 and form_of(c) == (64, 1, 8 * 96)
+        for (q, tr), n, (rw, rs) in zip(poses, ps.CALLS, ref):
+            set_local(c, [(q, tr)])
+            c.physics_step(n)
+            c.deform()
+            errs.append(errors(c, oracle, sc, 0, rw, rs))
+            st = c.read_physics(0).astype(np.float64)
+            assert np.isfinite(st).all()
+            # a following body's record: boneWorld x offset (the offset itself without a bone), zero velocities
+            sim = physics_ref.Sim(t, sc["parents"], sc["bind"])
+            sim.reset(ps.world_of(sc, q, tr))
+            for b in (0, 2, 5):
+                place = max(place, float(np.abs(st[b, :3] - sim.x[b]).max()) / sc["extent"], float(np.minimum(np.abs(st[b, 3:7] - sim.q[b]).max(), np.abs(st[b, 3:7] + sim.q[b]).max())))
+                assert np.abs(st[b, 7:]).max() == 0.0
+        assert np.array_equal(c.read_physics(0)[0, :3], t["offset_pos"][0])         # (the anchor without a bone is its offset, bit for bit)
+    print("followers against their placement: %.2e" % place)
+    assert place <= BAR
+    assert_bar(errs, "table contents")
+
+
+@pytest.mark.parametrize("name", ["crowd", "wide colour"])
+def test_steps_add_up_bit_for_bit(rz, name):
+    """With one resident pose physics_step(30) is 30 x physics_step(1) and physics_step(1000) is 4 x physics_step(250), bit for bit in
+    the state and in the dynamic bones' world matrices: the state is stored and reloaded exactly, a following body is re-placed on the same
+    matrices, and the spring multipliers start at zero in every substep. One wave with its joints in registers ("crowd") and 256 lanes
+    striding with the multipliers in LDS ("wide colour"). No float64 bar applies over 1000 substeps (the float32 probe of the definition
+    itself drifts to 4e-3 x extent by then), which is why this is an identity and not a parity check. And physics_step(0) as the very first
+    call — a reset without a substep — leaves every body on the solved pose."""
+    sc = ps.scene(name)
+    q, t = ps.pose(sc, 30)
+    dyn = physics_ref.prepare(sc["table"], sc["parents"], sc["bind"])["dyn_bodies"]
+    bones = [int(sc["table"]["bone"][b]) for b in dyn]
+
+    def run(steps):
+        with make_ctx(rz, sc) as c:
+            set_local(c, [(q, t)])
+            for n in steps:
+                c.physics_step(n)
+            c.deform()
+            st, w = c.read_physics(0), c.read_world(0)
+        assert np.isfinite(st).all() and np.isfinite(w).all()
+        return st, w
+    for whole, parts in (((30,), (1,) * 30), ((1000,), (250,) * 4)):
+        (sa, wa), (sb, wb) = run(whole), run(parts)
+        print("%s, %d substeps in one call vs %d calls: state differs by %.2e, overrides by %.2e" % (name, whole[0], len(parts), np.abs(sa - sb).max(), np.abs(wa[bones] - wb[bones]).max()))
+        assert np.array_equal(sa.view(np.uint32), sb.view(np.uint32)) and np.array_equal(wa[bones].view(np.uint32), wb[bones].view(np.uint32))
+    assert np.abs(sa[dyn, 7:]).max() > 0                 # (something is still moving: the comparison is not of a scene at rest)
+    st, w = run((0,))
+    w0 = ps.world_of(sc, q, t)
+    sim = physics_ref.Sim(sc["table"], sc["parents"], sc["bind"])
+    sim.reset(w0)
+    e = max(float(np.abs(st[:, :3] - sim.x).max()), float(np.abs(w - w0).max())) / sc["extent"]
+    eq = float(np.minimum(np.abs(st[:, 3:7] - sim.q).max(axis=1), np.abs(st[:, 3:7] + sim.q).max(axis=1)).max())
+    print("%s, physics_step(0) as the first call: %.2e x extent from the solved pose, quaternions %.2e" % (name, e, eq))
+    assert e <= BAR and eq <= BAR and np.abs(st[:, 7:]).max() == 0.0
+
+
+def test_joint_locked_at_the_gimbal_angle(rz):
+    """rotation_min.y = rotation_max.y = pi / 2: the joint is held where euler_xyz changes its branch (|m02| < 0.9999999) on the last bits
+    of one matrix entry, so the float32 and the float64 run of the definition legitimately take different branches and part (the probe
+    deviates by 5.5e-3 x extent): there is NO parity bar here. What must hold in any branch: the state stays finite and the quaternions
+    stay unit to 1e-5 over the standard sequence."""
+    sc = ps.scene("gimbal")
+    worst = 0.0
+    with make_ctx(rz, sc) as c:
+        for k, n in enumerate(ps.CALLS):
+            set_local(c, [ps.pose(sc, k)])
+            c.physics_step(n)
+            c.deform()
+            st = c.read_physics(0).astype(np.float64)
+            assert np.isfinite(st).all() and np.isfinite(c.read_world(0)).all() and np.isfinite(c.read(0)[0]).all()
+            worst = max(worst, float(np.abs(np.linalg.norm(st[:, 3:7], axis=1) - 1).max()))
+    print("gimbal lock: quaternion norms off 1 by %.2e" % worst)
+    assert worst <= 1e-5
+
+
 @pytest.mark.skipif(shutil.which("node") is None, reason="node is not installed")
 def test_node_engine_end_to_end(rz, oracle, tmp_path):
     """new Engine(null, { deviceFK: true, devicePhysics: true }) on a PMX with a strand scene: loadModel uploads Model.physicsTables(), every
