@@ -493,7 +493,9 @@ int rz_time_span(rz_ctx *a, rz_ctx *b, uint32_t lead, uint32_t frames, double *s
  * "effective_inst_group" / "effective_inst_block" / "effective_fuse_fk" / "effective_overlap" / "pose_resident" /
  * "effective_subsets" / "effective_subset_bones" / "effective_inst_lds" / "effective_fk_kind" / "effective_variant" (the last template
  * argument of the single-mesh frame kernel: 0 everything compiled in, 3 without the fused consumers, 1 / 2 also with the specialised
- * hierarchy solve) and the counts
+ * hierarchy solve), "effective_closure_bones" / "effective_closure_rounds" (a device-animated crowd whose next frame solves the
+ * hierarchy in the front of the crowd kernel: closure records per vertex run — the longest run's, shorter ones are padded — and the
+ * radix-4 doubling rounds over them, 0 .. 3 for a longest chain of 1 / 2-4 / 5-16 / 17-64 bones; both 0 when rz_fk_kernel runs in front) and the counts
  * "verts" / "bones" / "morphs" / "instances" / "sdef_verts" (SDEF vertices the next frame fixes, 0 = no SDEF pass) / "qdef_verts" (likewise for QDEF). Unknown keys return RZ_ERR_INVALID.
  * NOT a pure getter for crowds: an "effective_*" key describes the frame the NEXT rz_deform will launch, and a crowd's plan depends on
  * the per-run bone lists of its launch shape — when the shape, the mesh or the skeleton changed since the last frame the call brings

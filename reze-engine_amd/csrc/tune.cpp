@@ -226,7 +226,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     if (const TuneKey *k = find_key(key)) { *value = c->*k->field; return RZ_OK; }
     if (!strncmp(key, "effective_", 10)) {
         // (an unknown key is refused BEFORE the work below: it drains the stream and may rebuild the run lists)
-        static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones",
+        static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones", "closure_rounds",
                                              "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds" };
         bool ok = false;
         for (const char *k : known) ok = ok || !strcmp(key + 10, k);
@@ -278,6 +278,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "pose_rows")) *value = c->last_upload_rows ? 1 : 0;          // ... its world matrices as three rows per bone
     else if (!strcmp(key, "effective_fuse_fk")) { const Plan pl = make_plan(c); *value = (pl.fuse_fk || pl.subfk) ? 1 : 0; }
     else if (!strcmp(key, "effective_closure_bones")) *value = make_plan(c).subfk ? (int)c->subfk_stride : 0;
+    else if (!strcmp(key, "effective_closure_rounds")) *value = make_plan(c).subfk ? (int)c->subfk_rounds : 0;      // radix-4 doubling rounds of that front (0 .. 3)
     else if (!strcmp(key, "pose_resident")) *value = (c->zc_cur < 0 || (c->world_resident && c->mw_resident && c->local_resident)) ? 1 : 0;
     else if (!strcmp(key, "effective_overlap")) *value = want_overlap(c, make_plan(c)) ? 1 : 0;
     else if (!strcmp(key, "effective_inst_block")) *value = make_plan(c).inst_block;
