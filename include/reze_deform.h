@@ -348,11 +348,12 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *      box of half extents (r, r + height/2, r) (r = size.x, height = size.y).
  *   3. every dynamic body with a bone gives boneWorld = bodyWorld x offset^-1: that bone's override, in every following frame until the
  *      next step. Children of an overridden bone keep the matrices solved from the un-overridden parent, as rz_override_world documents.
- * NOT covered: collisions and friction of any kind, linear springs (spring_position), restitution. A welded joint (all limits equal) whose
+ * NOT covered: contacts unless rz_physics_contacts enables them (below), and then none that involve a box; linear springs (spring_position),
+ * restitution. A welded joint (all limits equal) whose
  * anchor is off the body's centre converges only linearly in `iterations` (the position and the rotation stage each undo part of the
- * other): about 0.3 of a parent's jump is left at 4 iterations, 1e-5 of it at 32. Shapes feed the inertia only; group and
- * mask are stored but unused — the signature carries shape, size, group, mask, friction, restitution and spring_position so that a contact
- * stage needs no new one (those arrays may be NULL today). There is no host-side twin of the solver.
+ * other): about 0.3 of a parent's jump is left at 4 iterations, 1e-5 of it at 32. Without contacts shapes feed the inertia only; group, mask
+ * and friction are kept for the contact stage; restitution and spring_position are unused (group, mask, friction, restitution and
+ * spring_position may be NULL; contacts need the first three). There is no host-side twin of the solver.
  * rz_upload_physics: needs rz_upload_skeleton_topology first; NULL or n_bodies = 0 removes the table; gravity3 NULL, h = 0, iterations = 0 =
  *   the defaults. RZ_ERR_INVALID (context untouched): a body, bone or joint index out of range, body_a == body_b, a value that is not finite,
  *   mass < 0, a damping outside [0, 1], h < 0, a type or shape above 2, two dynamic bodies on one bone. RZ_ERR_UNSUPPORTED: a table whose state does not fit the
@@ -370,7 +371,42 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  * rz_get_tuning("physics_bodies") / ("physics_joints") / ("physics_colours") = the counts; ("physics_block") = the lanes per workgroup the
  * resident table is solved with (64 when the bodies and the widest colour fit one wave, else 256), ("physics_own") = 1 when every lane keeps
  * its joint in registers (no more joints than lanes), 0 when lanes stride over a colour, ("physics_lds") = the bytes of LDS per workgroup;
- * all read-only, 0 without a table. */
+ * all read-only, 0 without a table.
+ * ---- contacts between rigid bodies — NEW (optional, off by default) ----
+ * rz_physics_contacts(ctx, 1) adds a contact stage to rz_physics_kernel for the resident table (the reference registers every body with
+ * 1 << group and its mask, physics.ts:257-269, and joints do not exempt their bodies); 0 drops it. Defined in float64 by tests/contact_ref.py.
+ *   shapes      a sphere is the point x with radius size.x; a capsule the segment x +- q (0, size.y / 2, 0) with radius size.x (axis Y).
+ *   candidates  fixed when the stage is enabled: all a < b with at least one dynamic body, both spheres or capsules with radius > 0, both
+ *               masks nonzero, (1 << group[a]) & mask[b] and (1 << group[b]) & mask[a] both nonzero. follow pairs (one dynamic body):
+ *               per dynamic body the list of its following partners, ascending; dynamic pairs: coloured greedily in lexicographic (a, b)
+ *               order so that no two pairs of a colour share a body, solved in (colour, a, b) order.
+ *   where       in every iteration of a substep, after the last joint colour: pass F, every dynamic body on itself alone against its
+ *               following partners in list order; then pass D, the dynamic pairs colour by colour.
+ *   one contact (A the lower index)
+ *     1. closest points cA, cB of the segments P + s d, s in [0, 1], P = x - u, d = u + u, u = q (0, size.y / 2, 0): with r = P_A - P_B,
+ *        a = d_A.d_A, e = d_B.d_B, f = d_B.r, c = d_A.r, b = d_A.d_B and clamp to [0, 1]: a <= 1e-9 and e <= 1e-9: s = t = 0; a <= 1e-9:
+ *        s = 0, t = clamp(f / e); e <= 1e-9: t = 0, s = clamp(-c / a); else s = clamp((b f - c e) / (a e - b b)) when a e - b b > 1e-9, else 0;
+ *        t = (b s + f) / e; t < 0: t = 0, s = clamp(-c / a); t > 1: t = 1, s = clamp((b - c) / a)
+ *     2. d = cB - cA, dist = |d|, pen = (rA + rB) - dist; skipped unless pen > 0 and dist > 1e-9
+ *     3. n = d / dist; arms ra = (cA + n rA) - x_A, rb = (cB - n rB) - x_B
+ *     4. w = w_A + w_B, w_X = 1/m_X + (r_X x n)^T I_X^-1 (r_X x n), 0 for a following body; skipped unless w > 0
+ *     5. d_lambda = pen / w, p = n d_lambda: x_A -= p / m_A, q_A turned by -I_A^-1 (ra x p); x_B += p / m_B, q_B by +I_B^-1 (rb x p)
+ *     6. friction, mu = friction[A] friction[B] (Bullet's combination), when mu > 0: the arms are carried in the body frames from before 5
+ *        (la = q_A^-1 ra, lb likewise) and re-expressed in the corrected pose; the contact point's slip over this substep
+ *        D = [(x_A + ra) - (x_A,prev + q_A,prev la)] - [the same for B], its tangential part Dt = D - n (D.n); when |Dt| > 1e-9 an impulse
+ *        of min(|Dt| / w_t, mu d_lambda) along Dt / |Dt| (w_t the generalised inverse mass along it, skipped unless > 0), A -, B +. A
+ *        following body's previous pose is its current pose (it is placed once per call).
+ *     7. only dynamic bodies are corrected and written.
+ *   NOT covered: boxes (no contact involves one: counted in "physics_contact_boxes"), restitution, a velocity pass (a penetration removed
+ *   in one substep arrives as velocity, as in plain XPBD), a broad phase.
+ * rz_physics_contacts: on = 1 builds and uploads the lists for the resident table, on = 0 drops them; neither resets the simulation; both
+ *   drop a captured graph (replays still do not advance the simulation). A new rz_upload_physics, a table removal, a new skeleton or a
+ *   new topology turns contacts off. RZ_ERR_INVALID: no resident table; a table uploaded with group, mask, friction or size3 NULL; forks
+ *   exist. RZ_ERR_UNSUPPORTED (the context keeps its state): more than 65 536 candidates, follow entries + dynamic pairs — every pair of
+ *   the table is tested, a broad phase does not exist yet. The stage adds no LDS: "physics_lds" and the 160 KB limit are unchanged.
+ * rz_get_tuning("physics_contacts") = 0 / 1, ("physics_contact_follow") = the follow entries, ("physics_contact_pairs") = the dynamic
+ * pairs, ("physics_contact_colours") = their colours, ("physics_contact_boxes") = the boxes (with a nonzero mask) left out; all read-only,
+ * 0 without contacts. */
 typedef struct rz_physics {
     uint32_t n_bodies;
     const int32_t *bone;                /* [n_bodies] -1 = none */
@@ -390,6 +426,7 @@ typedef struct rz_physics {
 int rz_upload_physics(rz_ctx *ctx, const rz_physics *tab);
 int rz_physics_step(rz_ctx *ctx, uint32_t substeps);
 int rz_physics_reset(rz_ctx *ctx);
+int rz_physics_contacts(rz_ctx *ctx, uint32_t on);
 int rz_read_physics(rz_ctx *ctx, uint32_t instance, float *state13);
 /* Blocking readback of one instance's world matrices (B x 16, column-major) as the frame used them. */
 int rz_read_world(rz_ctx *ctx, uint32_t instance, float *world16);

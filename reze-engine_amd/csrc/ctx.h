@@ -190,8 +190,16 @@ struct rz_ctx : RzStatic, RzTuning {
     float ph_h = 0.0f, ph_g[3] = { 0.0f, 0.0f, 0.0f };
     bool ph_reset = true;               // the next step places every body on its bone first
     std::vector<int> ph_dyn_bone;       // [ph_nd] bones of the dynamic bodies
-    std::vector<uint8_t> ph_group;      // [ph_nb] collision group and mask as uploaded: kept for a contact stage, read by nothing yet
+    // what decides contacts, as uploaded (empty: the array was NULL): rz_physics_contacts derives its lists from these (contact_table.h)
+    std::vector<uint8_t> ph_group, ph_shape, ph_type;
     std::vector<uint16_t> ph_mask;
+    std::vector<float> ph_size, ph_friction, ph_mass;
+    // the contact stage (rz_physics_contacts): off unless ph_contacts; the lists are constants of the resident table
+    bool ph_contacts = false;
+    float4 *ph_c_shape = nullptr;
+    int *ph_c_follow_off = nullptr, *ph_c_follow_idx = nullptr, *ph_c_colour_off = nullptr;
+    int2 *ph_c_pair = nullptr;
+    uint32_t ph_c_follow = 0, ph_c_pairs = 0, ph_c_ncol = 0, ph_c_boxes = 0;
 
     // per-frame state
     uint32_t I = 1;
@@ -390,6 +398,7 @@ void free_sdef(rz_ctx *c);
 void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
 void free_physics(rz_ctx *c);          // physics_host.cpp
+void free_contacts(rz_ctx *c);
 RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {

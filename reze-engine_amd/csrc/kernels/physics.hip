@@ -15,6 +15,11 @@
 // 256. Every phase ends in __syncthreads() in the source of both; under __launch_bounds__(64) the workgroup is one wave and the compiler
 // emits no barrier instruction for it, only the wait for the wave's own LDS accesses (the 64-lane code objects hold no s_barrier, the
 // 256-lane ones three: DESIGN.md 9.7).
+// CONTACT (rz_physics_contacts; tests/contact_ref.py is its definition): in every iteration, behind the last joint colour, pass F — lane per
+// dynamic body (the integrate loop's mapping), the body in registers across its list of following partners, which are only read from LDS,
+// written back once | barrier — then pass D, the dynamic pairs colour by colour in the joints' striding form, a barrier per colour. The
+// lists and shape records stay in global memory (constants every workgroup reads); the stage adds no LDS. Without CONTACT the kernel is
+// the code it was.
 #include "pass_parts.hip.h"
 
 namespace {
@@ -201,7 +206,85 @@ __device__ __forceinline__ void solve_joint(const JointC &c, const float4 *body,
     if (imb > 0.0f) { sx[c.b] = make_float4(xb.x, xb.y, xb.z, 0.0f); sq[c.b] = qb; }
 }
 
-template <int BLOCK, bool OWN>
+// a body as the contact stage sees it. A following body: im = 0, ii = 0, previous pose = current pose (its sxp / sqp slots are never written)
+struct CBody {
+    V3 x, xp, ii;
+    float4 q, qp;
+    float im, r, hl, mu;
+};
+__device__ __forceinline__ CBody load_cbody(const int b, const float4 *body, const float4 *cshape, const float4 *sx, const float4 *sq, const float4 *sxp, const float4 *sqp)
+{
+    const float4 b0 = body[4 * b], b2 = body[4 * b + 2], sh = cshape[b];
+    CBody c;
+    c.im = b0.w; c.ii = xyz(b2);
+    c.r = sh.x; c.hl = sh.y; c.mu = sh.z;
+    c.x = xyz(sx[b]); c.q = sq[b];
+    if (c.im > 0.0f) { c.xp = xyz(sxp[b]); c.qp = sqp[b]; }
+    else { c.xp = c.x; c.qp = c.q; }
+    return c;
+}
+__device__ __forceinline__ float clamp01(const float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// One contact, once, A the lower index (tests/contact_ref.py: Sim._contact, the same operations in the same order). Only a dynamic body is
+// corrected; the caller writes back what it owns.
+__device__ __forceinline__ void solve_contact(CBody &A, CBody &B)
+{
+    // 1. closest points of the two segments
+    const V3 ua = qrot(A.q, v3(0.0f, A.hl, 0.0f)), ub = qrot(B.q, v3(0.0f, B.hl, 0.0f));
+    const V3 p1 = A.x - ua, p2 = B.x - ub, d1 = ua + ua, d2 = ub + ub;
+    const V3 r = p1 - p2;
+    const float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
+    float s, t;
+    if (a <= kEps) {
+        s = 0.0f;
+        t = e <= kEps ? 0.0f : clamp01(f / e);
+    } else if (e <= kEps) {
+        t = 0.0f;
+        s = clamp01(-c / a);
+    } else {
+        const float den = a * e - b * b;
+        s = den > kEps ? clamp01((b * f - c * e) / den) : 0.0f;
+        t = (b * s + f) / e;
+        if (t < 0.0f) { t = 0.0f; s = clamp01(-c / a); }
+        else if (t > 1.0f) { t = 1.0f; s = clamp01((b - c) / a); }
+    }
+    const V3 cA = p1 + d1 * s, cB = p2 + d2 * t;
+    // 2 - 4
+    const V3 d = cB - cA;
+    const float dist = sqrtf(dot3(d, d));
+    const float pen = (A.r + B.r) - dist;
+    if (!(pen > 0.0f && dist > kEps)) return;
+    const V3 n = d / dist;
+    const V3 ra = (cA + n * A.r) - A.x, rb = (cB - n * B.r) - B.x;
+    const V3 can = cross3(ra, n), cbn = cross3(rb, n);
+    const float w = (A.im + dot3(can, iinv(A.q, A.ii, can))) + (B.im + dot3(cbn, iinv(B.q, B.ii, cbn)));
+    if (!(w > 0.0f)) return;
+    // 5
+    const float dl = pen / w;
+    const V3 p = n * dl;
+    const float4 qa0 = A.q, qb0 = B.q;
+    if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra, p)))); A.x = A.x - p * A.im; A.q = qn; }
+    if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb, p))); B.x = B.x + p * B.im; B.q = qn; }
+    // 6. friction
+    const float mu = A.mu * B.mu;
+    if (!(mu > 0.0f)) return;
+    const V3 la = qrot(qconj(qa0), ra), lb = qrot(qconj(qb0), rb);
+    const V3 ra2 = qrot(A.q, la), rb2 = qrot(B.q, lb);
+    const V3 D = ((A.x + ra2) - (A.xp + qrot(A.qp, la))) - ((B.x + rb2) - (B.xp + qrot(B.qp, lb)));
+    const V3 Dt = D - n * dot3(D, n);
+    const float lt = sqrtf(dot3(Dt, Dt));
+    if (!(lt > kEps)) return;
+    const V3 td = Dt / lt;
+    const V3 cat = cross3(ra2, td), cbt = cross3(rb2, td);
+    const float wt = (A.im + dot3(cat, iinv(A.q, A.ii, cat))) + (B.im + dot3(cbt, iinv(B.q, B.ii, cbt)));
+    if (!(wt > 0.0f)) return;
+    const float sz = fminf(lt / wt, mu * dl);
+    const V3 pt = td * sz;
+    if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra2, pt)))); A.x = A.x - pt * A.im; A.q = qn; }
+    if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb2, pt))); B.x = B.x + pt * B.im; B.q = qn; }
+}
+
+template <int BLOCK, bool OWN, bool CONTACT>
 __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams p)
 {
     extern __shared__ float4 ph_lds[];
@@ -261,7 +344,7 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
         if (OWN) { l0 = l1 = l2 = 0.0f; }
         else for (int k = tid; k < 3 * p.nj; k += BLOCK) slam[k] = 0.0f;
         __syncthreads();
-        for (int it = 0; it < p.iterations; ++it)
+        for (int it = 0; it < p.iterations; ++it) {
             for (int col = 0; col < p.ncol; ++col) {
                 const int j0 = p.colour_off[col], j1 = p.colour_off[col + 1];
                 if (OWN) {
@@ -274,6 +357,35 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
                 }
                 __syncthreads();
             }
+            if (CONTACT) {
+                // pass F: a dynamic body against its following partners, in list order
+                for (int b = tid; b < nb; b += BLOCK) {
+                    if (!(p.body[4 * b].w > 0.0f)) continue;
+                    const int f0 = p.c_follow_off[b], f1 = p.c_follow_off[b + 1];
+                    if (f0 == f1) continue;
+                    CBody me = load_cbody(b, p.body, p.c_shape, sx, sq, sxp, sqp);
+                    for (int k = f0; k < f1; ++k) {
+                        const int o = p.c_follow_idx[k];
+                        CBody other = load_cbody(o, p.body, p.c_shape, sx, sq, sxp, sqp);
+                        if (b < o) solve_contact(me, other); else solve_contact(other, me);
+                    }
+                    sx[b] = make_float4(me.x.x, me.x.y, me.x.z, 0.0f); sq[b] = me.q;
+                }
+                __syncthreads();
+                // pass D: the dynamic pairs of a colour share no body
+                for (int col = 0; col < p.c_ncol; ++col) {
+                    const int j0 = p.c_colour_off[col], j1 = p.c_colour_off[col + 1];
+                    for (int j = j0 + tid; j < j1; j += BLOCK) {
+                        const int2 ab = p.c_pair[j];
+                        CBody A = load_cbody(ab.x, p.body, p.c_shape, sx, sq, sxp, sqp), B = load_cbody(ab.y, p.body, p.c_shape, sx, sq, sxp, sqp);
+                        solve_contact(A, B);
+                        sx[ab.x] = make_float4(A.x.x, A.x.y, A.x.z, 0.0f); sq[ab.x] = A.q;
+                        sx[ab.y] = make_float4(B.x.x, B.x.y, B.x.z, 0.0f); sq[ab.y] = B.q;
+                    }
+                    __syncthreads();
+                }
+            }
+        }
         for (int b = tid; b < nb; b += BLOCK) {
             if (p.body[4 * b].w > 0.0f) {
                 const V3 v = (xyz(sx[b]) - xyz(sxp[b])) / h;
@@ -314,10 +426,10 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
 
 #pragma clang fp contract(fast)
 
-template <int BLOCK, bool OWN>
+template <int BLOCK, bool OWN, bool CONTACT>
 hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
 {
-    auto k = rz_physics_kernel<BLOCK, OWN>;
+    auto k = rz_physics_kernel<BLOCK, OWN, CONTACT>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -339,6 +451,11 @@ hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipSt
     const bool own = p.nj <= p.block;
     const size_t lds = rz_physics_lds_bytes(p.nb, p.nj, p.block);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (p.block == 64) return own ? launch<64, true>(p, instances, lds, st) : launch<64, false>(p, instances, lds, st);
-    return own ? launch<256, true>(p, instances, lds, st) : launch<256, false>(p, instances, lds, st);
+    if (p.contacts) {
+        if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
+        if (p.block == 64) return own ? launch<64, true, true>(p, instances, lds, st) : launch<64, false, true>(p, instances, lds, st);
+        return own ? launch<256, true, true>(p, instances, lds, st) : launch<256, false, true>(p, instances, lds, st);
+    }
+    if (p.block == 64) return own ? launch<64, true, false>(p, instances, lds, st) : launch<64, false, false>(p, instances, lds, st);
+    return own ? launch<256, true, false>(p, instances, lds, st) : launch<256, false, false>(p, instances, lds, st);
 }

@@ -2,19 +2,29 @@
 // stepping, reset and readback. The solver itself is rz_physics_kernel (kernels/physics.hip); this unit owns the hierarchy solve's override
 // table while a physics table is resident.
 #include "ctx.h"
-#include "physics_table.h"
+#include "contact_table.h"
 
 using namespace rzi;
 
 namespace rzi {
 
+// the contact stage's lists: contacts are off afterwards
+void free_contacts(rz_ctx *c)
+{
+    dfree(c->ph_c_shape); dfree(c->ph_c_follow_off); dfree(c->ph_c_follow_idx); dfree(c->ph_c_pair); dfree(c->ph_c_colour_off);
+    c->ph_contacts = false;
+    c->ph_c_follow = c->ph_c_pairs = c->ph_c_ncol = c->ph_c_boxes = 0;
+}
+
 void free_physics(rz_ctx *c)
 {
     if (!c->ph_nb) return;
     drop_graph(c);
+    free_contacts(c);
     dfree(c->ph_body); dfree(c->ph_joint); dfree(c->ph_state); dfree(c->ph_colour_off);
     c->ph_nb = c->ph_nj = c->ph_ncol = c->ph_nd = c->ph_I = 0;
-    c->ph_dyn_bone.clear(); c->ph_group.clear(); c->ph_mask.clear();
+    c->ph_dyn_bone.clear(); c->ph_group.clear(); c->ph_mask.clear(); c->ph_shape.clear(); c->ph_type.clear();
+    c->ph_size.clear(); c->ph_friction.clear(); c->ph_mass.clear();
     c->ph_reset = true;
     c->ovr_count = 0;                   // the overrides were physics' own
 }
@@ -83,6 +93,10 @@ static int step(rz_ctx *c, uint32_t substeps, bool reset)
     p.nb = (int)c->ph_nb; p.nj = (int)c->ph_nj; p.ncol = (int)c->ph_ncol; p.nd = (int)c->ph_nd; p.B = (int)c->B;
     p.iterations = c->ph_iterations; p.substeps = (int)substeps; p.reset = (reset || c->ph_reset) ? 1 : 0; p.block = c->ph_block;
     p.h = c->ph_h; p.gx = c->ph_g[0]; p.gy = c->ph_g[1]; p.gz = c->ph_g[2];
+    if (c->ph_contacts) {
+        p.c_shape = c->ph_c_shape; p.c_follow_off = c->ph_c_follow_off; p.c_follow_idx = c->ph_c_follow_idx; p.c_pair = c->ph_c_pair;
+        p.c_colour_off = c->ph_c_colour_off; p.c_ncol = (int)c->ph_c_ncol; p.contacts = 1;
+    }
     HIP_TRY(rz_launch_physics(p, c->I, st));
     c->ph_reset = false;
     c->ovr_count = c->I * c->ph_nd;
@@ -141,6 +155,11 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
     c->ph_dyn_bone = o.dyn_bone;
     if (t->group) c->ph_group.assign(t->group, t->group + t->n_bodies);
     if (t->mask) c->ph_mask.assign(t->mask, t->mask + t->n_bodies);
+    if (t->friction) c->ph_friction.assign(t->friction, t->friction + t->n_bodies);
+    c->ph_shape.assign(t->shape, t->shape + t->n_bodies);
+    c->ph_type.assign(t->type, t->type + t->n_bodies);
+    c->ph_size.assign(t->size3, t->size3 + (size_t)t->n_bodies * 3);
+    c->ph_mass.assign(t->mass, t->mass + t->n_bodies);
     c->ph_I = 0;
     c->ph_reset = true;
     return RZ_OK;
@@ -152,6 +171,50 @@ int rz_physics_step(rz_ctx *c, uint32_t substeps)
     if (int r = physics_usable(c, "rz_physics_step")) return r;
     if (substeps > 1000) return fail(RZ_ERR_INVALID, "rz_physics_step: %u substeps in one call (at most 1000)", substeps);
     return step(c, substeps, false);
+}
+
+int rz_physics_contacts(rz_ctx *c, uint32_t on)
+{
+    if (int r = use(c)) return r;
+    if (int r = physics_usable(c, "rz_physics_contacts")) return r;
+    if (!on) {
+        if (!c->ph_contacts) return RZ_OK;
+        HIP_TRY(hipStreamSynchronize(c->up_stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drop_graph(c);
+        free_contacts(c);
+        return RZ_OK;
+    }
+    const size_t nb = c->ph_nb;
+    if (c->ph_group.size() != nb || c->ph_mask.size() != nb || c->ph_friction.size() != nb || c->ph_size.size() != nb * 3)
+        return fail(RZ_ERR_INVALID, "rz_physics_contacts: the resident table was uploaded without%s%s%s%s: contacts need group, mask, friction and size3",
+                    c->ph_group.size() != nb ? " group" : "", c->ph_mask.size() != nb ? " mask" : "", c->ph_friction.size() != nb ? " friction" : "",
+                    c->ph_size.size() != nb * 3 ? " size3" : "");
+    rz_physics t;
+    memset(&t, 0, sizeof t);
+    t.n_bodies = c->ph_nb; t.type = c->ph_type.data(); t.shape = c->ph_shape.data(); t.group = c->ph_group.data(); t.mask = c->ph_mask.data();
+    t.size3 = c->ph_size.data(); t.mass = c->ph_mass.data(); t.friction = c->ph_friction.data();
+    rzphys::Contacts o;
+    rzphys::build_contacts(&t, o);
+    if (o.too_many) return fail(RZ_ERR_UNSUPPORTED, "%s", rzphys::contacts_refusal(o).c_str());
+    // the new lists first: a failed allocation leaves the context as it was
+    float4 *shape = nullptr;
+    int *foff = nullptr, *fidx = nullptr, *coff = nullptr;
+    int2 *pair = nullptr;
+    int r = to_device(&shape, o.shape.data(), nb);
+    if (!r) r = to_device(&foff, o.follow_off.data(), o.follow_off.size());
+    if (!r) r = to_device(&fidx, o.follow_idx.data(), o.follow_idx.size());
+    if (!r) r = to_device(&pair, o.pair.data(), o.pair.size() / 2);
+    if (!r) r = to_device(&coff, o.colour_off.data(), o.colour_off.size());
+    if (r) { dfree(shape); dfree(foff); dfree(fidx); dfree(pair); dfree(coff); return r; }
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_graph(c);
+    free_contacts(c);
+    c->ph_c_shape = shape; c->ph_c_follow_off = foff; c->ph_c_follow_idx = fidx; c->ph_c_pair = pair; c->ph_c_colour_off = coff;
+    c->ph_c_follow = (uint32_t)o.n_follow; c->ph_c_pairs = (uint32_t)o.n_pairs; c->ph_c_ncol = (uint32_t)o.ncol; c->ph_c_boxes = (uint32_t)o.boxes;
+    c->ph_contacts = true;
+    return RZ_OK;
 }
 
 int rz_physics_reset(rz_ctx *c)

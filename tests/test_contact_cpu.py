@@ -1,0 +1,242 @@
+"""The contact stage without a GPU: what the definition (tests/contact_ref.py) promises, the host half of rz_physics_contacts
+(reze-engine_amd/csrc/contact_table.h, through tests/contact_table_main.cpp built with -fsanitize=address,undefined) against the definition's
+lists, the conditioning and contact activity of every case tests/test_gpu_contacts.py runs, and the Engine option against a recording addon."""
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import contact_ref as cr
+import contact_scenes as cs
+import physics_ref as pr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ILL = 2.5e-5
+IDENT = np.eye(4).T.reshape(1, 16)
+
+
+def one_bone(bodies, joints=(), **kw):
+    """a table on one bone at the origin; returns (Sim with contacts, world)"""
+    t = pr.make_table(list(bodies), list(joints), **kw)
+    return cr.Sim(t, [-1], [[0, 0, 0]]), IDENT.copy(), t
+
+
+def test_a_dropped_sphere_comes_to_rest_on_a_following_sphere():
+    """A sphere of radius 0.5 released 0.3 above a following sphere of radius 1: after 300 substeps it rests on it — the gap or penetration
+    is below 2 % of its radius (one substep of free fall from rest, g h^2 = 0.0174, is 3.5 % of the radius; the stage removes the whole
+    penetration it meets, so what is left is what gravity adds after the last solve, damped) — and it never passed through: its centre
+    stays above the contact height minus 10 % of the radius in every substep."""
+    R, r = 1.0, 0.5
+    sim, W, _ = one_bone([dict(bone=0, type=0, shape=0, size=[R, 0, 0], mass=0.0), dict(bone=-1, type=1, shape=0, size=[r, 0, 0], mass=1.0, offset_pos=[0, R + r + 0.3, 0],
+                                                                                     linear_damping=0.9, angular_damping=0.9)])
+    low = np.inf
+    for _ in range(300):
+        sim.step(W, 1)
+        low = min(low, sim.x[1, 1])
+    pen = (R + r) - np.linalg.norm(sim.x[1] - sim.x[0])
+    print("rest: penetration %.2e (%.2f %% of the radius), lowest centre %.4f (contact at %.1f), speed %.2e" % (pen, 100 * abs(pen) / r, low, R + r, np.linalg.norm(sim.v[1])))
+    assert abs(pen) < 0.02 * r and low > (R + r) - 0.1 * r
+    assert sum(a > 0 for a in sim.active) > 100
+
+
+def _slide(mu):
+    """a sphere on a capsule tilted by 0.5 rad (under 45 degrees): its drift along the capsule's axis over 30 substeps, its drift off the
+    surface, the substeps in contact and its final spin"""
+    tilt = cs._quat([0, 0, 1], np.pi / 2 - 0.5)                       # the Y axis turned towards -x, 0.5 rad off the horizontal
+    axis = pr.qrot(tilt, np.array([0.0, 1.0, 0.0]))
+    normal = np.array([axis[1], -axis[0], 0.0])
+    sim, W, _ = one_bone([dict(bone=0, type=0, shape=2, size=[0.5, 12.0, 0], mass=0.0, offset_rot=tilt, friction=1.0),
+                          dict(bone=-1, type=1, shape=0, size=[0.5, 0, 0], mass=1.0, offset_pos=list(normal * 1.0), friction=mu)])
+    sim.step(W, 0)
+    x0 = sim.x[1].copy()
+    sim.step(W, 30)
+    return float(np.dot(sim.x[1] - x0, -axis)), float(np.dot(sim.x[1] - x0, normal)), sum(a > 0 for a in sim.active), float(np.linalg.norm(sim.w[1]))
+
+
+def test_friction_holds_what_slides_without_it():
+    """mu = 0 (the sphere's friction; the product is 0): the sphere slides down the tilted capsule without turning, by g sin(0.5) t^2 / 2
+    within 5 %. mu = 1 with tan(0.5) = 0.55 < 1: the contact point sticks, so the sphere rolls — a ball rolling without slipping covers
+    5/7 = 0.714 of the sliding distance — and its drift is asserted below 0.8 of the frictionless one (the margin measured between the two
+    reference runs is printed), with a spin of about v / r."""
+    free, off0, n0, w0 = _slide(0.0)
+    held, off1, n1, w1 = _slide(1.0)
+    t = 30 * pr.DEFAULT_H
+    print("drift down the capsule over 30 substeps: %.4f without friction (g sin(0.5) t^2 / 2 = %.4f), %.4f with mu = 1 (ratio %.3f; 5/7 = 0.714); spin %.2e / %.2f; %d / %d substeps in contact"
+          % (free, 0.5 * 98 * np.sin(0.5) * t * t, held, held / free, w0, w1, n0, n1))
+    assert abs(free / (0.5 * 98 * np.sin(0.5) * t * t) - 1) < 0.05 and w0 < 1e-9
+    assert 0 < held < 0.8 * free and w1 > 1.0 and n0 >= 28 and n1 >= 28 and abs(off0) < 0.05 and abs(off1) < 0.05
+
+
+def _lists(bodies):
+    return cr.contact_lists(pr.make_table(bodies, []))
+
+
+def test_what_is_a_candidate():
+    """Bullet's rule in both directions, and what is left out: mask 0, radius 0, boxes (counted), two following bodies"""
+    dyn = dict(type=1, mass=1.0, shape=0, size=[0.3, 0, 0])
+    fol = dict(type=0, mass=0.0, shape=0, size=[0.3, 0, 0])
+    L = _lists([dict(dyn, group=1, mask=0xffff), dict(fol, group=2, mask=0xffff)])
+    assert (L["n_follow"], L["n_pairs"], list(L["follow_idx"]), list(L["follow_off"])) == (1, 0, [1], [0, 1, 1])
+    assert _lists([dict(dyn, group=1, mask=0xffff & ~4), dict(fol, group=2, mask=0xffff)])["n_follow"] == 0          # one-way masks exclude the pair
+    assert _lists([dict(dyn, group=1, mask=0xffff), dict(fol, group=2, mask=0xffff & ~2)])["n_follow"] == 0
+    assert _lists([dict(dyn, group=1, mask=0), dict(fol, group=2, mask=0xffff)])["n_follow"] == 0
+    assert _lists([dict(dyn, group=1, mask=0xffff, size=[0.0, 0, 0]), dict(fol, group=2, mask=0xffff)])["n_follow"] == 0
+    assert _lists([dict(fol, group=1, mask=0xffff), dict(fol, group=2, mask=0xffff)])["n_follow"] == 0
+    L = _lists([dict(dyn, group=1), dict(dyn, group=1, shape=1, size=[0.3, 0.3, 0.3]), dict(fol, shape=1, size=[1, 1, 1]), dict(fol, shape=1, size=[1, 1, 1], mask=0), dict(dyn, shape=2, size=[0.2, 0.5, 0])])
+    assert (L["boxes"], L["n_follow"], L["n_pairs"], L["pairs"].tolist()) == (2, 0, 1, [[0, 4]])
+    # a body in three dynamic pairs takes three colours; solve order is (colour, a, b)
+    L = _lists([dict(dyn)] * 4)
+    assert L["n_pairs"] == 6 and L["n_colours"] == 3 and L["pairs"].tolist() == [[0, 1], [2, 3], [0, 2], [1, 3], [0, 3], [1, 2]] and list(L["colour_off"]) == [0, 2, 4, 6]
+    # joined bodies are not exempt
+    t = pr.make_table([dict(dyn), dict(dyn)], [dict(body_a=0, body_b=1)])
+    assert cr.contact_lists(t)["n_pairs"] == 1
+
+
+def test_coincident_centres_are_skipped():
+    sim, W, _ = one_bone([dict(bone=0, type=0, shape=0, size=[1, 0, 0], mass=0.0), dict(bone=-1, type=1, shape=0, size=[0.5, 0, 0], mass=1.0)], gravity=(0, 0, 0))
+    sim.step(W, 5)
+    assert np.isfinite(sim.state13()).all() and np.array_equal(sim.x[1], [0, 0, 0]) and sum(sim.active) == 0
+
+
+def test_parallel_capsules_in_contact_stay_finite():
+    """the ill-conditioned closest-point case (a e - b b about 0): CPU only, finite and separated, in both precisions"""
+    for dt in (np.float64, np.float32):
+        t = pr.make_table([dict(bone=0, type=0, shape=2, size=[0.5, 2, 0], mass=0.0), dict(bone=-1, type=1, shape=2, size=[0.5, 2, 0], mass=1.0, offset_pos=[1.02, 0.2, 0], linear_damping=0.9, angular_damping=0.9)], [], gravity=(-98, 0, 0))
+        sim = cr.Sim(t, [-1], [[0, 0, 0]], dtype=dt)
+        sim.step(IDENT, 60)
+        assert np.isfinite(sim.state13()).all() and sim.x[1, 0] > 0.95 and sum(a > 0 for a in sim.active) > 10
+
+
+def test_contacts_that_never_touch_leave_the_run_identical():
+    """pairs exist and never come within reach: the float64 run with the stage is physics_ref.Sim's, bit for bit"""
+    sc = cs.apart()
+    poses = [cs.pose(sc, k) for k in range(3)]
+    sim = cr.Sim(sc["table"], sc["parents"], sc["bind"])
+    assert sim.lists["n_follow"] > 0 and sim.lists["n_pairs"] > 0
+    a = cs.run_reference(sc, poses, cs.SHORT, sim=sim)
+    b = cs.run_reference(sc, poses, cs.SHORT)
+    assert sum(sim.active) == 0
+    for (wa, sa), (wb, sb) in zip(a, b):
+        assert np.array_equal(wa, wb) and np.array_equal(sa, sb)
+
+
+def test_cases_are_well_conditioned_and_touch():
+    """every GPU case, none left out: the float32 probe of the definition stays within 2.5e-5 x extent of its float64 run over the whole
+    horizon, and at least one contact is active in at least a quarter of the substeps"""
+    rows, bad = [], {}
+    for name in cs._CASES:
+        c, act = cs.conditioning(name)
+        rows.append("%s %.1e / %.2f" % (name, c, act))
+        if c > ILL or act < 0.25:
+            bad[name] = (c, act)
+    print("float32 probe / extent, active fraction: " + ", ".join(rows))
+    assert not bad, "ill-conditioned or idle: %s" % bad
+    for name, (block, own) in cs.FORMS.items():
+        t = cs.case(name)[0]["table"]
+        _, _, ncol = pr.colouring(t)
+        widest = max(np.bincount(pr.colouring(t)[0])) if t["n_joints"] else 0
+        assert (64 if t["n_bodies"] <= 64 and widest <= 64 else 256) == block and int(t["n_joints"] <= block) == own, name
+    # the Node end-to-end case: the PMX's table under one pose, the engine's substeps
+    import physics_scenes as ps
+    sc, _, q = cs.node_case()
+    calls = ps.node_substeps()
+    poses = [(q, np.zeros((sc["B"], 3), dtype=np.float32))] * len(calls)
+    runs = {}
+    for dt in (np.float64, np.float32):
+        sim = cr.Sim(sc["table"], sc["parents"], sc["bind"], dtype=dt)
+        runs[dt] = (cs.run_reference(sc, poses, calls, dtype=dt, sim=sim), sim)
+    c = max(max(float(np.abs(a[0] - b[0]).max()), float(np.abs(a[1][:, :3] - b[1][:, :3]).max())) for a, b in zip(runs[np.float64][0], runs[np.float32][0])) / sc["extent"]
+    act = float((np.array(runs[np.float64][1].active) > 0).mean())
+    print("node case: %.1e / %.2f" % (c, act))
+    assert c <= ILL and act >= 0.25
+    # the strides the cases are there for
+    L = {n: cr.contact_lists(cs.case(n)[0]["table"]) for n in ("stride 256", "70 partners", "257 pairs", "three colours")}
+    d = np.diff(L["stride 256"]["follow_off"])
+    assert (d == 1).sum() >= 257 and d.max() == 1
+    d = np.diff(L["70 partners"]["follow_off"])
+    dyn = pr.is_dynamic(cs.case("70 partners")[0]["table"])
+    assert d.max() == 70 and (d[dyn] == 0).any()
+    assert np.diff(L["257 pairs"]["colour_off"])[0] == 257 and cs.case("257 pairs")[0]["table"]["n_bodies"] == 515
+    assert L["three colours"]["n_colours"] >= 3 and L["three colours"]["n_follow"] > 0
+
+
+# ---- the host half: contact_table.h against the definition's lists ----
+
+def dump(t):
+    rows = ["%d" % t["n_bodies"]]
+    for b in range(t["n_bodies"]):
+        rows.append("%d %d %d %d %r %r %r %r %r" % (t["type"][b], t["shape"][b], t["group"][b], t["mask"][b], float(t["size"][b][0]), float(t["size"][b][1]), float(t["size"][b][2]),
+                                                    float(t["mass"][b]), float(t["friction"][b])))
+    return "\n".join(rows) + "\n"
+
+
+def limit_table(n_follow):
+    """256 dynamic x n_follow following spheres, all in each other's masks: 256 n_follow follow entries (65 536 with 256, the limit)"""
+    dyn = dict(bone=-1, type=1, mass=1.0, shape=0, size=[0.1, 0, 0], group=1, mask=1 << 2)
+    fol = dict(bone=1, type=0, mass=0.0, shape=0, size=[0.1, 0, 0], group=2, mask=1 << 1)
+    return pr.make_table([dict(dyn, offset_pos=[3.0 * k, 0, 0]) for k in range(256)] + [dict(fol, offset_pos=[3.0 * k, 50.0, 0]) for k in range(n_follow)], [])
+
+
+@pytest.fixture(scope="module")
+def contact_tool(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("contact_table") / "contact_table_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(ROOT, "tests", "contact_table_main.cpp")])
+    return exe
+
+
+def run_tool(tool, t):
+    out = subprocess.run([tool], input=dump(t), capture_output=True, text=True, check=True).stdout
+    return {ln.split(" ", 1)[0]: ln.split(" ", 1)[1].split() if " " in ln else [] for ln in out.strip().split("\n")}, out
+
+
+@pytest.mark.parametrize("name", ["own 64", "stride 256", "70 partners", "257 pairs", "three colours", "capsule sphere df"])
+def test_host_lists_equal_the_definition(contact_tool, name):
+    """shape records, the follow CSR, the dynamic pairs in solve order, colour offsets and counts, entry for entry"""
+    t = cs.case(name)[0]["table"]
+    L = cr.contact_lists(t)
+    rows, out = run_tool(contact_tool, t)
+    assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and rows["refused"][0] == "0"
+    shape = np.array([float(v) for v in rows["shape"]], dtype=np.float32).reshape(-1, 4)          # (%.9g round-trips a float32)
+    assert np.array_equal(shape[:, 0], L["radius"]) and np.array_equal(shape[:, 1], L["half"]) and np.array_equal(shape[:, 2], L["friction"])
+    assert np.array_equal(shape[:, 3], L["takes"].astype(int))
+    assert [int(v) for v in rows["follow_off"]] == list(L["follow_off"]) and [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"])
+    assert [int(v) for v in rows["pair"]] == list(L["pairs"].reshape(-1)) and [int(v) for v in rows["colour_off"]] == list(L["colour_off"])
+
+
+def test_host_counts_boxes_and_applies_the_masks(contact_tool):
+    dyn = dict(type=1, mass=1.0, shape=0, size=[0.3, 0, 0])
+    fol = dict(type=0, mass=0.0, shape=0, size=[0.3, 0, 0])
+    t = pr.make_table([dict(dyn, group=1), dict(dyn, group=1, shape=1, size=[0.3, 0.3, 0.3]), dict(fol, shape=1, size=[1, 1, 1]), dict(fol, shape=1, size=[1, 1, 1], mask=0),
+                       dict(dyn, shape=2, size=[0.2, 0.5, 0]), dict(fol, group=3, mask=0xffff & ~2), dict(dyn, size=[0, 0, 0]), dict(fol, group=20), dict(fol, group=4)], [])
+    L = cr.contact_lists(t)
+    rows, _ = run_tool(contact_tool, t)
+    assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and L["boxes"] == 2
+    assert [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"]) == [8, 5, 8] and [int(v) for v in rows["pair"]] == [0, 4]
+
+
+def test_host_refuses_one_past_the_limit(contact_tool):
+    """256 dynamic x 256 following bodies = 65 536 candidates are taken, 256 x 257 are refused with both counts in the message"""
+    rows, _ = run_tool(contact_tool, limit_table(256))
+    assert rows["counts"][:2] == ["65536", "0"] and rows["refused"][0] == "0" and len(rows["follow_idx"]) == 65536
+    rows, out = run_tool(contact_tool, limit_table(257))
+    assert rows["counts"][:2] == ["65792", "0"] and rows["refused"][0] == "1" and rows.get("follow_idx", []) == []
+    assert "65792 follow entries and 0 dynamic pairs" in out and "broad phase" in out
+    assert cr.refusal(cr.contact_lists(limit_table(257))) and not cr.refusal(cr.contact_lists(limit_table(256)))
+
+
+@pytest.mark.skipif(shutil.which("node") is None, reason="node is not installed")
+def test_engine_physics_contacts_option_with_a_recording_addon(tmp_path):
+    """Engine { physicsContacts } against a stand-in for the addon: physicsContacts(ctx, 1) follows uploadPhysics on every shard at
+    loadModel; without the option the engine makes no such call; physicsContacts without devicePhysics throws"""
+    sc, data, _ = cs.node_case()
+    (tmp_path / "s.pmx").write_bytes(data)
+    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contacts_engine_mock.js"), str(tmp_path / "s.pmx")], timeout=60).decode().strip().splitlines()[-1])
+    assert r["needsDevicePhysics"] and r["needsDeviceFK"]
+    assert r["shards"] >= 2 and len(r["on"]) == r["shards"]
+    for calls in r["on"]:
+        assert calls.count("physicsContacts:1") == 1 and calls.index("physicsContacts:1") == calls.index("uploadPhysics") + 1
+    assert all("physicsContacts" not in " ".join(calls) for calls in r["off"]) and all("uploadPhysics" in calls for calls in r["off"])
