@@ -374,7 +374,8 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  * all read-only, 0 without a table.
  * ---- contacts between rigid bodies — NEW (optional, off by default) ----
  * rz_physics_contacts(ctx, 1) adds a contact stage to rz_physics_kernel for the resident table (the reference registers every body with
- * 1 << group and its mask, physics.ts:257-269, and joints do not exempt their bodies); 0 drops it. Defined in float64 by tests/contact_ref.py.
+ * 1 << group and its mask, physics.ts:257-269, and joints do not exempt their bodies); 2 adds it with the table's boxes taking part (`boxes`
+ * below); 0 drops it. Defined in float64 by tests/contact_ref.py.
  *   shapes      a sphere is the point x with radius size.x; a capsule the segment x +- q (0, size.y / 2, 0) with radius size.x (axis Y).
  *   candidates  fixed when the stage is enabled: all a < b with at least one dynamic body, both spheres or capsules with radius > 0, both
  *               masks nonzero, (1 << group[a]) & mask[b] and (1 << group[b]) & mask[a] both nonzero. follow pairs (one dynamic body):
@@ -397,16 +398,35 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *        of min(|Dt| / w_t, mu d_lambda) along Dt / |Dt| (w_t the generalised inverse mass along it, skipped unless > 0), A -, B +. A
  *        following body's previous pose is its current pose (it is placed once per call).
  *     7. only dynamic bodies are corrected and written.
- *   NOT covered: boxes (no contact involves one: counted in "physics_contact_boxes"), restitution, a velocity pass (a penetration removed
+ *   boxes       on = 1: no contact involves a box (those with a nonzero mask are counted in "physics_contact_boxes"). on = 2: a box (shape 1,
+ *               the set |y_i| <= e_i in its own frame, e = size3, the three half extents the inertia reads) takes part when all three are
+ *               > 0 and its mask is nonzero, against spheres and capsules in either index order, following or dynamic, as a shape of
+ *               radius 0. A pair of two boxes is no candidate; those the rule would pair are counted in "physics_contact_box_pairs".
+ *               Defined in float64 by tests/contact_box_ref.py. With a box X and a round shape R (segment P + s d, radius r; a sphere:
+ *               d = 0) step 1 becomes:
+ *     1a. the segment in the box frame: P' = q_X^-1 (P - x_X), d' = q_X^-1 d
+ *     1b. c(s) = P' + s d', g(s) = c - clamp(c, -e, e), f(s) = g(s).d' (half the derivative of the squared distance, monotone):
+ *         f(0) >= 0: s = 0; else f(1) <= 0: s = 1; else 24 bisection steps on [lo, hi] = [0, 1] — m = (lo + hi) / 2, f(m) > 0: hi = m,
+ *         else lo = m — and s = (lo + hi) / 2
+ *     1c. b' = clamp(c(s), -e, e); the round shape's point is P + s d in world space, the box's x_X + q_X b'
+ *     1d. shallow, |c(s) - b'| > 1e-9: steps 2 - 7 unchanged (A the lower index, n from cA to cB, the box's radius 0)
+ *     1e. deep, |c(s) - b'| <= 1e-9 (the centre line is inside the box): the axis i with the smallest e_i - |c_i| (the first of x, y, z
+ *         wins a tie), sg = +1 when c_i >= 0, else -1; outward normal N = sg q_X axis_i; the box's point is c with component i set to
+ *         sg e_i; pen = r + (e_i - |c_i|); n = N when the box is A, -N when it is B; steps 3 - 7 with this n and pen, without the
+ *         dist > 1e-9 test.
+ *         A pair without a box runs steps 1 - 7 as they are.
+ *   NOT covered: box against box (left out, counted in "physics_contact_box_pairs"), restitution, a velocity pass (a penetration removed
  *   in one substep arrives as velocity, as in plain XPBD), a broad phase.
- * rz_physics_contacts: on = 1 builds and uploads the lists for the resident table, on = 0 drops them; neither resets the simulation; both
+ * rz_physics_contacts: on = 1 (and every value but 0 and 2) builds and uploads the lists for the resident table, on = 2 the lists with
+ *   the boxes taking part, on = 0 drops them; switching between 1 and 2 rebuilds them; none resets the simulation; all
  *   drop a captured graph (replays still do not advance the simulation). A new rz_upload_physics, a table removal, a new skeleton or a
  *   new topology turns contacts off. RZ_ERR_INVALID: no resident table; a table uploaded with group, mask, friction or size3 NULL; forks
  *   exist. RZ_ERR_UNSUPPORTED (the context keeps its state): more than 65 536 candidates, follow entries + dynamic pairs — every pair of
  *   the table is tested, a broad phase does not exist yet. The stage adds no LDS: "physics_lds" and the 160 KB limit are unchanged.
- * rz_get_tuning("physics_contacts") = 0 / 1, ("physics_contact_follow") = the follow entries, ("physics_contact_pairs") = the dynamic
- * pairs, ("physics_contact_colours") = their colours, ("physics_contact_boxes") = the boxes (with a nonzero mask) left out; all read-only,
- * 0 without contacts. */
+ * rz_get_tuning("physics_contacts") = 0 / 1 / 2, ("physics_contact_follow") = the follow entries, ("physics_contact_pairs") = the dynamic
+ * pairs, ("physics_contact_colours") = their colours, ("physics_contact_boxes") = the boxes with a nonzero mask that take no part (on = 1:
+ * all of them; on = 2: those with an extent of 0), ("physics_contact_box_pairs") = the pairs of two boxes left out under on = 2 (a build
+ * without box contacts does not know this key: that is how a binding detects them); all read-only, 0 without contacts. */
 typedef struct rz_physics {
     uint32_t n_bodies;
     const int32_t *bone;                /* [n_bodies] -1 = none */

@@ -669,12 +669,15 @@ class DeformContext:
     def physics_reset(self):
         self._chk(self._L.rz_physics_reset(self._h))
 
-    def physics_contacts(self, on=True):
+    def physics_contacts(self, on=True, boxes=False):
         """Contacts between the spheres and capsules of the resident physics table (off by default; include/reze_deform.h states the stage).
-        A new table, skeleton or topology turns them off again. Does not reset the simulation."""
+        boxes=True: the table's boxes take part against them as well (a pair of two boxes is left out and counted in the tuning key
+        physics_contact_box_pairs). A new table, skeleton or topology turns contacts off again. Does not reset the simulation."""
         if not hasattr(self._L, "rz_physics_contacts"):
             raise RzError(-6, "this build of the library has no rz_physics_contacts")
-        self._chk(self._L.rz_physics_contacts(self._h, 1 if on else 0))
+        if on and boxes:
+            self.get_tuning("physics_contact_box_pairs")        # (a library without box contacts does not know the key: its error says so)
+        self._chk(self._L.rz_physics_contacts(self._h, (2 if boxes else 1) if on else 0))
 
     def read_physics(self, instance=0):
         """[n_bodies, 13] x3 q4 v3 w3 of one instance (blocking)."""

@@ -1,6 +1,7 @@
 // contact_table.h — the host half of rz_physics_contacts that needs no GPU: from the table as uploaded, the per-body shape records, the follow
 // lists and the coloured dynamic pairs the contact stage of rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams). Plain C++ without
 // HIP, beside physics_table.h: tests/contact_table_main.cpp compiles it alone and holds the lists to tests/contact_ref.py entry for entry.
+// The boxes mode (rz_physics_contacts(ctx, 2)) is held to tests/contact_box_ref.py by tests/contact_box_table_main.cpp.
 #pragma once
 #include "physics_table.h"
 
@@ -10,14 +11,16 @@ namespace rzphys {
 constexpr size_t kMaxContactCandidates = 65536;         // follow entries + dynamic pairs: every pair of the table is tested (no broad phase yet)
 
 struct Contacts {
-    std::vector<float> shape;           // [nb][4] radius | half length of the segment (0: a sphere) | friction | bits(1 = takes part)
+    std::vector<float> shape;           // [nb][4] radius | half length of the segment (0: a sphere) | friction | bits(1 = takes part, 4 = a box)
+    std::vector<float> box;             // [nb][4] boxes mode: a box's three half extents | 0; zeros for every other body
     std::vector<int> follow_off;        // [nb + 1] a dynamic body's following partners: follow_idx[follow_off[b] .. follow_off[b + 1]), ascending
     std::vector<int> follow_idx;
     std::vector<int> pair;              // [n_pairs][2] dynamic pairs (a < b) in solve order: (colour, a, b)
     std::vector<int> colour_off;        // [ncol + 1]
     size_t n_follow = 0, n_pairs = 0;   // counted in full even when the limit is passed (the lists are then empty)
-    int ncol = 0, boxes = 0;
+    int ncol = 0, boxes = 0;            // boxes: those with a nonzero mask that take no part (boxes mode: the ones with an extent of 0)
     bool too_many = false;
+    size_t box_pairs = 0;               // boxes mode: pairs of two boxes that the rule would pair; they are no candidates (left out, counted)
 };
 
 inline bool takes_part(const rz_physics *t, uint32_t b)
@@ -31,23 +34,33 @@ inline bool groups_meet(const rz_physics *t, uint32_t a, uint32_t b)
     return (ga & t->mask[b]) && (gb & t->mask[a]);
 }
 
-// t must carry group, mask, friction and size3
-inline void build_contacts(const rz_physics *t, Contacts &o)
+// a box takes part (boxes mode only) when its three half extents are positive
+inline bool box_takes_part(const rz_physics *t, uint32_t b)
+{
+    const float *sz = t->size3 + (size_t)b * 3;
+    return t->shape[b] == 1 && sz[0] > 0.0f && sz[1] > 0.0f && sz[2] > 0.0f && t->mask[b] != 0;
+}
+
+// t must carry group, mask, friction and size3. boxes: rz_physics_contacts(ctx, 2) — boxes take part against spheres and capsules
+inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
 {
     const uint32_t nb = t->n_bodies;
     o = Contacts();
     o.shape.assign((size_t)nb * 4, 0.0f);
+    if (boxes) o.box.assign((size_t)nb * 4, 0.0f);
     std::vector<uint32_t> in;           // the bodies that take part
     for (uint32_t b = 0; b < nb; ++b) {
         float *r = o.shape.data() + (size_t)b * 4;
         const float *sz = t->size3 + (size_t)b * 3;
-        const bool on = takes_part(t, b);
-        r[0] = sz[0];
+        const bool isbox = boxes && t->shape[b] == 1;
+        const bool on = takes_part(t, b) || (isbox && box_takes_part(t, b));
+        r[0] = isbox ? 0.0f : sz[0];      // a box counts as a shape of radius 0
         r[1] = t->shape[b] == 2 ? (float)((double)sz[1] * 0.5) : 0.0f;
         r[2] = t->friction[b];
-        r[3] = bits_of(on ? 1 : 0);
+        r[3] = bits_of((on ? 1 : 0) | (isbox ? 4 : 0));
+        if (isbox) for (int k = 0; k < 3; ++k) o.box[(size_t)b * 4 + k] = sz[k];
         if (on) in.push_back(b);
-        if (t->shape[b] == 1 && t->mask[b] != 0) o.boxes++;
+        if (t->shape[b] == 1 && t->mask[b] != 0 && !on) o.boxes++;
     }
     // count first: the limit is checked before any list is built
     std::vector<int> nfol(nb, 0);
@@ -56,6 +69,7 @@ inline void build_contacts(const rz_physics *t, Contacts &o)
             const uint32_t a = in[i], b = in[k];
             const bool da = dynamic(t, a), db = dynamic(t, b);
             if (!(da || db) || !groups_meet(t, a, b)) continue;
+            if (t->shape[a] == 1 && t->shape[b] == 1) { o.box_pairs++; continue; }
             if (da && db) o.n_pairs++;
             else { nfol[da ? a : b]++; o.n_follow++; }
         }
@@ -71,7 +85,7 @@ inline void build_contacts(const rz_physics *t, Contacts &o)
         for (size_t k = i + 1; k < in.size(); ++k) {
             const uint32_t a = in[i], b = in[k];
             const bool da = dynamic(t, a), db = dynamic(t, b);
-            if (!(da || db) || !groups_meet(t, a, b)) continue;
+            if (!(da || db) || !groups_meet(t, a, b) || (t->shape[a] == 1 && t->shape[b] == 1)) continue;
             if (!(da && db)) {
                 // (a, b) ascends lexicographically, so a dynamic body meets its partners in ascending order whichever side it is on
                 if (da) o.follow_idx[fill[a]++] = (int)b; else o.follow_idx[fill[b]++] = (int)a;

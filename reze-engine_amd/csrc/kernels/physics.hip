@@ -19,7 +19,9 @@
 // dynamic body (the integrate loop's mapping), the body in registers across its list of following partners, which are only read from LDS,
 // written back once | barrier — then pass D, the dynamic pairs colour by colour in the joints' striding form, a barrier per colour. The
 // lists and shape records stay in global memory (constants every workgroup reads); the stage adds no LDS. Without CONTACT the kernel is
-// the code it was.
+// the code it was. CONTACT = 2 (tests/contact_box_ref.py): boxes take part against spheres and capsules — the body's record carries a box
+// bit, its half extents come from c_box, and solve_contact_boxes finds the closest points by a fixed 24-step bisection in the box frame
+// before the same correction and friction; CONTACT = 0 and 1 are the code they were.
 #include "pass_parts.hip.h"
 
 namespace {
@@ -284,7 +286,135 @@ __device__ __forceinline__ void solve_contact(CBody &A, CBody &B)
     if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb2, pt))); B.x = B.x + pt * B.im; B.q = qn; }
 }
 
-template <int BLOCK, bool OWN, bool CONTACT>
+// CONTACT = 2: a body with its half extents (a box: r = 0, hl = 0; every other body: box = false, e unread)
+struct CBox : CBody {
+    V3 e;
+    bool box;
+};
+__device__ __forceinline__ CBox load_cbox(const int b, const float4 *body, const float4 *cshape, const float4 *cbox, const float4 *sx, const float4 *sq, const float4 *sxp, const float4 *sqp)
+{
+    CBox c;
+    static_cast<CBody &>(c) = load_cbody(b, body, cshape, sx, sq, sxp, sqp);
+    c.box = (__float_as_uint(cshape[b].w) & 4u) != 0;
+    c.e = v3(0.0f, 0.0f, 0.0f);
+    if (c.box) c.e = xyz(cbox[b]);
+    return c;
+}
+
+// f(s) of the definition: half the derivative of the squared distance between P + s d and the box |y_i| <= e_i
+__device__ __forceinline__ float box_slope(const V3 P, const V3 d, const V3 e, const float s)
+{
+    const V3 c = P + d * s;
+    return dot3(c - clamp3(c, neg(e), e), d);
+}
+// the parameter s in [0, 1] at which the segment P + s d (box frame) is closest to the box: a fixed trip count with selects, so lanes
+// that meet a box do not diverge among themselves whatever their geometry
+__device__ __forceinline__ float box_closest(const V3 P, const V3 d, const V3 e)
+{
+    const float f0 = box_slope(P, d, e, 0.0f), f1 = box_slope(P, d, e, 1.0f);
+    float lo = 0.0f, hi = 1.0f;
+#pragma unroll 1
+    for (int k = 0; k < 24; ++k) {
+        const float m = (lo + hi) * 0.5f;
+        const bool up = box_slope(P, d, e, m) > 0.0f;
+        hi = up ? m : hi;
+        lo = up ? lo : m;
+    }
+    return f0 >= 0.0f ? 0.0f : f1 <= 0.0f ? 1.0f : (lo + hi) * 0.5f;
+}
+
+// One contact under CONTACT = 2 (tests/contact_box_ref.py: Sim._box_contact, the same operations in the same order). A pair without a box
+// is solve_contact's; a pair of two boxes does not occur (contact_table.h leaves them out).
+__device__ __forceinline__ void solve_contact_boxes(CBox &A, CBox &B)
+{
+    if (!(A.box || B.box)) { solve_contact(A, B); return; }
+    // 1. X the box, R the round shape
+    const bool ax = A.box;
+    const V3 xX = ax ? A.x : B.x, xR = ax ? B.x : A.x, e = ax ? A.e : B.e;
+    const float4 qX = ax ? A.q : B.q, qR = ax ? B.q : A.q;
+    const float r = ax ? B.r : A.r, hl = ax ? B.hl : A.hl;
+    const V3 u = qrot(qR, v3(0.0f, hl, 0.0f));
+    const V3 P = xR - u, d = u + u;
+    const float4 qi = qconj(qX);
+    const V3 Pl = qrot(qi, P - xX), dl_ = qrot(qi, d);
+    const float s = box_closest(Pl, dl_, e);
+    const V3 cl = Pl + dl_ * s;
+    const V3 bl = clamp3(cl, neg(e), e);
+    const V3 cR = P + d * s;
+    const V3 gap = cl - bl;
+    const bool deep = !(sqrtf(dot3(gap, gap)) > kEps);
+    V3 n, cX;
+    float pen;
+    if (deep) {
+        // the face the centre line is nearest to; the first of x, y, z wins a tie
+        const float mx = e.x - fabsf(cl.x), my = e.y - fabsf(cl.y), mz = e.z - fabsf(cl.z);
+        const int i = (mx <= my && mx <= mz) ? 0 : (my <= mz ? 1 : 2);
+        const float ci = i == 0 ? cl.x : i == 1 ? cl.y : cl.z, ei = i == 0 ? e.x : i == 1 ? e.y : e.z, mi = i == 0 ? mx : i == 1 ? my : mz;
+        const float sg = ci >= 0.0f ? 1.0f : -1.0f;
+        const V3 face = v3(i == 0 ? sg * ei : cl.x, i == 1 ? sg * ei : cl.y, i == 2 ? sg * ei : cl.z);
+        const V3 N = qrot(qX, v3(i == 0 ? sg : 0.0f, i == 1 ? sg : 0.0f, i == 2 ? sg : 0.0f));
+        cX = xX + qrot(qX, face);
+        pen = r + mi;
+        n = ax ? N : neg(N);
+    } else {
+        cX = xX + qrot(qX, bl);
+    }
+    const V3 cA = ax ? cX : cR, cB = ax ? cR : cX;
+    if (!deep) {
+        // 2
+        const V3 dv = cB - cA;
+        const float dist = sqrtf(dot3(dv, dv));
+        pen = (A.r + B.r) - dist;
+        if (!(pen > 0.0f && dist > kEps)) return;
+        n = dv / dist;
+    }
+    // 3 - 7: solve_contact from here on
+    const V3 ra = (cA + n * A.r) - A.x, rb = (cB - n * B.r) - B.x;
+    const V3 can = cross3(ra, n), cbn = cross3(rb, n);
+    const float w = (A.im + dot3(can, iinv(A.q, A.ii, can))) + (B.im + dot3(cbn, iinv(B.q, B.ii, cbn)));
+    if (!(w > 0.0f)) return;
+    const float dl = pen / w;
+    const V3 p = n * dl;
+    const float4 qa0 = A.q, qb0 = B.q;
+    if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra, p)))); A.x = A.x - p * A.im; A.q = qn; }
+    if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb, p))); B.x = B.x + p * B.im; B.q = qn; }
+    const float mu = A.mu * B.mu;
+    if (!(mu > 0.0f)) return;
+    const V3 la = qrot(qconj(qa0), ra), lb = qrot(qconj(qb0), rb);
+    const V3 ra2 = qrot(A.q, la), rb2 = qrot(B.q, lb);
+    const V3 D = ((A.x + ra2) - (A.xp + qrot(A.qp, la))) - ((B.x + rb2) - (B.xp + qrot(B.qp, lb)));
+    const V3 Dt = D - n * dot3(D, n);
+    const float lt = sqrtf(dot3(Dt, Dt));
+    if (!(lt > kEps)) return;
+    const V3 td = Dt / lt;
+    const V3 cat = cross3(ra2, td), cbt = cross3(rb2, td);
+    const float wt = (A.im + dot3(cat, iinv(A.q, A.ii, cat))) + (B.im + dot3(cbt, iinv(B.q, B.ii, cbt)));
+    if (!(wt > 0.0f)) return;
+    const float sz = fminf(lt / wt, mu * dl);
+    const V3 pt = td * sz;
+    if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra2, pt)))); A.x = A.x - pt * A.im; A.q = qn; }
+    if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb2, pt))); B.x = B.x + pt * B.im; B.q = qn; }
+}
+
+// the contact stage's body and solve by mode
+template <int CONTACT> struct ContactOps {
+    using Body = CBody;
+    static __device__ __forceinline__ Body load(const int b, const float4 *body, const float4 *cshape, const float4 *, const float4 *sx, const float4 *sq, const float4 *sxp, const float4 *sqp)
+    {
+        return load_cbody(b, body, cshape, sx, sq, sxp, sqp);
+    }
+    static __device__ __forceinline__ void solve(Body &A, Body &B) { solve_contact(A, B); }
+};
+template <> struct ContactOps<2> {
+    using Body = CBox;
+    static __device__ __forceinline__ Body load(const int b, const float4 *body, const float4 *cshape, const float4 *cbox, const float4 *sx, const float4 *sq, const float4 *sxp, const float4 *sqp)
+    {
+        return load_cbox(b, body, cshape, cbox, sx, sq, sxp, sqp);
+    }
+    static __device__ __forceinline__ void solve(Body &A, Body &B) { solve_contact_boxes(A, B); }
+};
+
+template <int BLOCK, bool OWN, int CONTACT>
 __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams p)
 {
     extern __shared__ float4 ph_lds[];
@@ -358,16 +488,17 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
                 __syncthreads();
             }
             if (CONTACT) {
+                using Ops = ContactOps<CONTACT>;
                 // pass F: a dynamic body against its following partners, in list order
                 for (int b = tid; b < nb; b += BLOCK) {
                     if (!(p.body[4 * b].w > 0.0f)) continue;
                     const int f0 = p.c_follow_off[b], f1 = p.c_follow_off[b + 1];
                     if (f0 == f1) continue;
-                    CBody me = load_cbody(b, p.body, p.c_shape, sx, sq, sxp, sqp);
+                    typename Ops::Body me = Ops::load(b, p.body, p.c_shape, p.c_box, sx, sq, sxp, sqp);
                     for (int k = f0; k < f1; ++k) {
                         const int o = p.c_follow_idx[k];
-                        CBody other = load_cbody(o, p.body, p.c_shape, sx, sq, sxp, sqp);
-                        if (b < o) solve_contact(me, other); else solve_contact(other, me);
+                        typename Ops::Body other = Ops::load(o, p.body, p.c_shape, p.c_box, sx, sq, sxp, sqp);
+                        if (b < o) Ops::solve(me, other); else Ops::solve(other, me);
                     }
                     sx[b] = make_float4(me.x.x, me.x.y, me.x.z, 0.0f); sq[b] = me.q;
                 }
@@ -377,8 +508,8 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
                     const int j0 = p.c_colour_off[col], j1 = p.c_colour_off[col + 1];
                     for (int j = j0 + tid; j < j1; j += BLOCK) {
                         const int2 ab = p.c_pair[j];
-                        CBody A = load_cbody(ab.x, p.body, p.c_shape, sx, sq, sxp, sqp), B = load_cbody(ab.y, p.body, p.c_shape, sx, sq, sxp, sqp);
-                        solve_contact(A, B);
+                        typename Ops::Body A = Ops::load(ab.x, p.body, p.c_shape, p.c_box, sx, sq, sxp, sqp), B = Ops::load(ab.y, p.body, p.c_shape, p.c_box, sx, sq, sxp, sqp);
+                        Ops::solve(A, B);
                         sx[ab.x] = make_float4(A.x.x, A.x.y, A.x.z, 0.0f); sq[ab.x] = A.q;
                         sx[ab.y] = make_float4(B.x.x, B.x.y, B.x.z, 0.0f); sq[ab.y] = B.q;
                     }
@@ -426,7 +557,7 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
 
 #pragma clang fp contract(fast)
 
-template <int BLOCK, bool OWN, bool CONTACT>
+template <int BLOCK, bool OWN, int CONTACT>
 hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
 {
     auto k = rz_physics_kernel<BLOCK, OWN, CONTACT>;
@@ -453,9 +584,15 @@ hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipSt
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (p.contacts) {
         if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
-        if (p.block == 64) return own ? launch<64, true, true>(p, instances, lds, st) : launch<64, false, true>(p, instances, lds, st);
-        return own ? launch<256, true, true>(p, instances, lds, st) : launch<256, false, true>(p, instances, lds, st);
+        if (p.contacts == 2) {
+            if (!p.c_box) return hipErrorInvalidValue;
+            if (p.block == 64) return own ? launch<64, true, 2>(p, instances, lds, st) : launch<64, false, 2>(p, instances, lds, st);
+            return own ? launch<256, true, 2>(p, instances, lds, st) : launch<256, false, 2>(p, instances, lds, st);
+        }
+        if (p.contacts != 1) return hipErrorInvalidValue;
+        if (p.block == 64) return own ? launch<64, true, 1>(p, instances, lds, st) : launch<64, false, 1>(p, instances, lds, st);
+        return own ? launch<256, true, 1>(p, instances, lds, st) : launch<256, false, 1>(p, instances, lds, st);
     }
-    if (p.block == 64) return own ? launch<64, true, false>(p, instances, lds, st) : launch<64, false, false>(p, instances, lds, st);
-    return own ? launch<256, true, false>(p, instances, lds, st) : launch<256, false, false>(p, instances, lds, st);
+    if (p.block == 64) return own ? launch<64, true, 0>(p, instances, lds, st) : launch<64, false, 0>(p, instances, lds, st);
+    return own ? launch<256, true, 0>(p, instances, lds, st) : launch<256, false, 0>(p, instances, lds, st);
 }

@@ -254,11 +254,12 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     // strided over a colour (0), dynamic LDS per workgroup; all 0 without a table
     else if (!strcmp(key, "physics_block")) *value = c->ph_nb ? c->ph_block : 0;
     else if (!strcmp(key, "physics_own")) *value = (c->ph_nb && (int)c->ph_nj <= c->ph_block) ? 1 : 0;
-    else if (!strcmp(key, "physics_contacts")) *value = c->ph_contacts ? 1 : 0;
+    else if (!strcmp(key, "physics_contacts")) *value = c->ph_contacts;
     else if (!strcmp(key, "physics_contact_follow")) *value = (int)c->ph_c_follow;
     else if (!strcmp(key, "physics_contact_pairs")) *value = (int)c->ph_c_pairs;
     else if (!strcmp(key, "physics_contact_colours")) *value = (int)c->ph_c_ncol;
     else if (!strcmp(key, "physics_contact_boxes")) *value = (int)c->ph_c_boxes;
+    else if (!strcmp(key, "physics_contact_box_pairs")) *value = (int)c->ph_c_box_pairs;
     else if (!strcmp(key, "physics_lds")) *value = c->ph_nb ? (int)rz_physics_lds_bytes((int)c->ph_nb, (int)c->ph_nj, c->ph_block) : 0;
     else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;

@@ -67,8 +67,9 @@ class Engine {
     this.devicePhysics = o.devicePhysics === true
     if (this.devicePhysics && !this.deviceFK) throw new Error('devicePhysics needs new Engine(canvas, { deviceFK: true }); with host FK pass { physics }')
     if (this.devicePhysics && this.physics) throw new Error('devicePhysics and { physics } are exclusive: both would write the physics-driven bones')
-    // physicsContacts: contacts between the table's spheres and capsules (rz_physics_contacts), enabled on every shard behind the upload
-    this.physicsContacts = o.physicsContacts === true
+    // physicsContacts: contacts between the table's spheres and capsules (rz_physics_contacts), enabled on every shard behind the upload;
+    // 'boxes': its boxes take part as well
+    this.physicsContacts = o.physicsContacts === 'boxes' ? 'boxes' : o.physicsContacts === true
     if (this.physicsContacts && !this.devicePhysics) throw new Error('physicsContacts needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
     this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
     this.physicsResident = false
@@ -253,7 +254,7 @@ class Engine {
         // so is physics: every shard simulates the same bodies (the solve is deterministic), so no shard waits for another's overrides
         if (tables && tables.nBodies > 0) {
           n.uploadPhysics(s.ctx, tables)
-          if (this.physicsContacts) n.physicsContacts(s.ctx, 1)
+          if (this.physicsContacts) n.physicsContacts(s.ctx, this.physicsContacts === 'boxes' ? 2 : 1)
           this.physicsResident = true
         }
       }
