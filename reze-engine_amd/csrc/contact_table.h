@@ -1,7 +1,7 @@
 // contact_table.h — the host half of rz_physics_contacts that needs no GPU: from the table as uploaded, the per-body shape records, the follow
 // lists and the coloured dynamic pairs the contact stage of rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams). Plain C++ without
-// HIP, beside physics_table.h: tests/contact_table_main.cpp compiles it alone and holds the lists to tests/contact_ref.py entry for entry.
-// The boxes mode (rz_physics_contacts(ctx, 2)) is held to tests/contact_box_ref.py by tests/contact_box_table_main.cpp.
+// HIP, beside physics_table.h: tests/contact_table_main.cpp compiles it alone, and the CPU tests hold the lists it prints to
+// tests/contact_ref.py entry for entry, and those of the boxes mode (rz_physics_contacts(ctx, 2)) to tests/contact_box_ref.py.
 #pragma once
 #include "physics_table.h"
 
@@ -62,14 +62,17 @@ inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
         if (on) in.push_back(b);
         if (t->shape[b] == 1 && t->mask[b] != 0 && !on) o.boxes++;
     }
+    // the rule, for a < b that both take part; a pair of two boxes passes it and is left out by both walks
+    const auto pairs_up = [t](uint32_t a, uint32_t b) { return (dynamic(t, a) || dynamic(t, b)) && groups_meet(t, a, b); };
+    const auto two_boxes = [t](uint32_t a, uint32_t b) { return t->shape[a] == 1 && t->shape[b] == 1; };
     // count first: the limit is checked before any list is built
     std::vector<int> nfol(nb, 0);
     for (size_t i = 0; i < in.size(); ++i)
         for (size_t k = i + 1; k < in.size(); ++k) {
             const uint32_t a = in[i], b = in[k];
+            if (!pairs_up(a, b)) continue;
+            if (two_boxes(a, b)) { o.box_pairs++; continue; }
             const bool da = dynamic(t, a), db = dynamic(t, b);
-            if (!(da || db) || !groups_meet(t, a, b)) continue;
-            if (t->shape[a] == 1 && t->shape[b] == 1) { o.box_pairs++; continue; }
             if (da && db) o.n_pairs++;
             else { nfol[da ? a : b]++; o.n_follow++; }
         }
@@ -84,8 +87,8 @@ inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
     for (size_t i = 0; i < in.size(); ++i)
         for (size_t k = i + 1; k < in.size(); ++k) {
             const uint32_t a = in[i], b = in[k];
+            if (!pairs_up(a, b) || two_boxes(a, b)) continue;
             const bool da = dynamic(t, a), db = dynamic(t, b);
-            if (!(da || db) || !groups_meet(t, a, b) || (t->shape[a] == 1 && t->shape[b] == 1)) continue;
             if (!(da && db)) {
                 // (a, b) ascends lexicographically, so a dynamic body meets its partners in ascending order whichever side it is on
                 if (da) o.follow_idx[fill[a]++] = (int)b; else o.follow_idx[fill[b]++] = (int)a;

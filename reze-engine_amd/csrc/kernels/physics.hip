@@ -19,9 +19,10 @@
 // dynamic body (the integrate loop's mapping), the body in registers across its list of following partners, which are only read from LDS,
 // written back once | barrier — then pass D, the dynamic pairs colour by colour in the joints' striding form, a barrier per colour. The
 // lists and shape records stay in global memory (constants every workgroup reads); the stage adds no LDS. Without CONTACT the kernel is
-// the code it was. CONTACT = 2 (tests/contact_box_ref.py): boxes take part against spheres and capsules — the body's record carries a box
-// bit, its half extents come from c_box, and solve_contact_boxes finds the closest points by a fixed 24-step bisection in the box frame
-// before the same correction and friction; CONTACT = 0 and 1 are the code they were.
+// the code it was. One solver: a front end finds the contact points, the normal and the penetration (steps 1 and 2), resolve_contact
+// corrects and applies friction (steps 3 - 7). solve_contact is the front end for two segments. CONTACT = 2 (tests/contact_box_ref.py):
+// boxes take part against spheres and capsules — the body's record carries a box bit, its half extents come from c_box, and
+// solve_contact_boxes is the box front end, a fixed 24-step bisection in the box frame, ahead of the same resolve_contact.
 #include "pass_parts.hip.h"
 
 namespace {
@@ -227,36 +228,12 @@ __device__ __forceinline__ CBody load_cbody(const int b, const float4 *body, con
 }
 __device__ __forceinline__ float clamp01(const float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
-// One contact, once, A the lower index (tests/contact_ref.py: Sim._contact, the same operations in the same order). Only a dynamic body is
-// corrected; the caller writes back what it owns.
-__device__ __forceinline__ void solve_contact(CBody &A, CBody &B)
+// Steps 3 - 7 of one contact, whichever front end found it (tests/contact_ref.py: Sim._resolve, the same operations in the same order):
+// from the contact points cA and cB, the normal n from A to B and the penetration pen, the arms, the generalised inverse mass, the
+// correction and the friction. Only a dynamic body is corrected; the caller writes back what it owns.
+__device__ __forceinline__ void resolve_contact(CBody &A, CBody &B, const V3 cA, const V3 cB, const V3 n, const float pen)
 {
-    // 1. closest points of the two segments
-    const V3 ua = qrot(A.q, v3(0.0f, A.hl, 0.0f)), ub = qrot(B.q, v3(0.0f, B.hl, 0.0f));
-    const V3 p1 = A.x - ua, p2 = B.x - ub, d1 = ua + ua, d2 = ub + ub;
-    const V3 r = p1 - p2;
-    const float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
-    float s, t;
-    if (a <= kEps) {
-        s = 0.0f;
-        t = e <= kEps ? 0.0f : clamp01(f / e);
-    } else if (e <= kEps) {
-        t = 0.0f;
-        s = clamp01(-c / a);
-    } else {
-        const float den = a * e - b * b;
-        s = den > kEps ? clamp01((b * f - c * e) / den) : 0.0f;
-        t = (b * s + f) / e;
-        if (t < 0.0f) { t = 0.0f; s = clamp01(-c / a); }
-        else if (t > 1.0f) { t = 1.0f; s = clamp01((b - c) / a); }
-    }
-    const V3 cA = p1 + d1 * s, cB = p2 + d2 * t;
-    // 2 - 4
-    const V3 d = cB - cA;
-    const float dist = sqrtf(dot3(d, d));
-    const float pen = (A.r + B.r) - dist;
-    if (!(pen > 0.0f && dist > kEps)) return;
-    const V3 n = d / dist;
+    // 3, 4
     const V3 ra = (cA + n * A.r) - A.x, rb = (cB - n * B.r) - B.x;
     const V3 can = cross3(ra, n), cbn = cross3(rb, n);
     const float w = (A.im + dot3(can, iinv(A.q, A.ii, can))) + (B.im + dot3(cbn, iinv(B.q, B.ii, cbn)));
@@ -284,6 +261,38 @@ __device__ __forceinline__ void solve_contact(CBody &A, CBody &B)
     const V3 pt = td * sz;
     if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra2, pt)))); A.x = A.x - pt * A.im; A.q = qn; }
     if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb2, pt))); B.x = B.x + pt * B.im; B.q = qn; }
+}
+
+// One contact, once, A the lower index: steps 1 and 2 for two segments (tests/contact_ref.py: Sim._contact, the same operations in the
+// same order), then resolve_contact.
+__device__ __forceinline__ void solve_contact(CBody &A, CBody &B)
+{
+    // 1. closest points of the two segments
+    const V3 ua = qrot(A.q, v3(0.0f, A.hl, 0.0f)), ub = qrot(B.q, v3(0.0f, B.hl, 0.0f));
+    const V3 p1 = A.x - ua, p2 = B.x - ub, d1 = ua + ua, d2 = ub + ub;
+    const V3 r = p1 - p2;
+    const float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
+    float s, t;
+    if (a <= kEps) {
+        s = 0.0f;
+        t = e <= kEps ? 0.0f : clamp01(f / e);
+    } else if (e <= kEps) {
+        t = 0.0f;
+        s = clamp01(-c / a);
+    } else {
+        const float den = a * e - b * b;
+        s = den > kEps ? clamp01((b * f - c * e) / den) : 0.0f;
+        t = (b * s + f) / e;
+        if (t < 0.0f) { t = 0.0f; s = clamp01(-c / a); }
+        else if (t > 1.0f) { t = 1.0f; s = clamp01((b - c) / a); }
+    }
+    const V3 cA = p1 + d1 * s, cB = p2 + d2 * t;
+    // 2
+    const V3 d = cB - cA;
+    const float dist = sqrtf(dot3(d, d));
+    const float pen = (A.r + B.r) - dist;
+    if (!(pen > 0.0f && dist > kEps)) return;
+    resolve_contact(A, B, cA, cB, d / dist, pen);
 }
 
 // CONTACT = 2: a body with its half extents (a box: r = 0, hl = 0; every other body: box = false, e unread)
@@ -323,8 +332,8 @@ __device__ __forceinline__ float box_closest(const V3 P, const V3 d, const V3 e)
     return f0 >= 0.0f ? 0.0f : f1 <= 0.0f ? 1.0f : (lo + hi) * 0.5f;
 }
 
-// One contact under CONTACT = 2 (tests/contact_box_ref.py: Sim._box_contact, the same operations in the same order). A pair without a box
-// is solve_contact's; a pair of two boxes does not occur (contact_table.h leaves them out).
+// One contact under CONTACT = 2: the box front end (tests/contact_box_ref.py: Sim._box_contact, the same operations in the same order),
+// then resolve_contact. A pair without a box is solve_contact's; a pair of two boxes does not occur (contact_table.h leaves them out).
 __device__ __forceinline__ void solve_contact_boxes(CBox &A, CBox &B)
 {
     if (!(A.box || B.box)) { solve_contact(A, B); return; }
@@ -368,35 +377,11 @@ __device__ __forceinline__ void solve_contact_boxes(CBox &A, CBox &B)
         if (!(pen > 0.0f && dist > kEps)) return;
         n = dv / dist;
     }
-    // 3 - 7: solve_contact from here on
-    const V3 ra = (cA + n * A.r) - A.x, rb = (cB - n * B.r) - B.x;
-    const V3 can = cross3(ra, n), cbn = cross3(rb, n);
-    const float w = (A.im + dot3(can, iinv(A.q, A.ii, can))) + (B.im + dot3(cbn, iinv(B.q, B.ii, cbn)));
-    if (!(w > 0.0f)) return;
-    const float dl = pen / w;
-    const V3 p = n * dl;
-    const float4 qa0 = A.q, qb0 = B.q;
-    if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra, p)))); A.x = A.x - p * A.im; A.q = qn; }
-    if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb, p))); B.x = B.x + p * B.im; B.q = qn; }
-    const float mu = A.mu * B.mu;
-    if (!(mu > 0.0f)) return;
-    const V3 la = qrot(qconj(qa0), ra), lb = qrot(qconj(qb0), rb);
-    const V3 ra2 = qrot(A.q, la), rb2 = qrot(B.q, lb);
-    const V3 D = ((A.x + ra2) - (A.xp + qrot(A.qp, la))) - ((B.x + rb2) - (B.xp + qrot(B.qp, lb)));
-    const V3 Dt = D - n * dot3(D, n);
-    const float lt = sqrtf(dot3(Dt, Dt));
-    if (!(lt > kEps)) return;
-    const V3 td = Dt / lt;
-    const V3 cat = cross3(ra2, td), cbt = cross3(rb2, td);
-    const float wt = (A.im + dot3(cat, iinv(A.q, A.ii, cat))) + (B.im + dot3(cbt, iinv(B.q, B.ii, cbt)));
-    if (!(wt > 0.0f)) return;
-    const float sz = fminf(lt / wt, mu * dl);
-    const V3 pt = td * sz;
-    if (A.im > 0.0f) { const float4 qn = rot_apply(A.q, neg(iinv(A.q, A.ii, cross3(ra2, pt)))); A.x = A.x - pt * A.im; A.q = qn; }
-    if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb2, pt))); B.x = B.x + pt * B.im; B.q = qn; }
+    resolve_contact(A, B, cA, cB, n, pen);
 }
 
-// the contact stage's body and solve by mode
+// the contact stage's body and solve by mode. Two body types, not one with the box fields always there: CBody is small enough to come
+// back from its loader in registers, and growing it changes the code of CONTACT = 1 (profiles/contact_fold_identity.txt)
 template <int CONTACT> struct ContactOps {
     using Body = CBody;
     static __device__ __forceinline__ Body load(const int b, const float4 *body, const float4 *cshape, const float4 *, const float4 *sx, const float4 *sq, const float4 *sxp, const float4 *sqp)
@@ -584,15 +569,12 @@ hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipSt
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (p.contacts) {
         if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
-        if (p.contacts == 2) {
-            if (!p.c_box) return hipErrorInvalidValue;
-            if (p.block == 64) return own ? launch<64, true, 2>(p, instances, lds, st) : launch<64, false, 2>(p, instances, lds, st);
-            return own ? launch<256, true, 2>(p, instances, lds, st) : launch<256, false, 2>(p, instances, lds, st);
-        }
-        if (p.contacts != 1) return hipErrorInvalidValue;
-        if (p.block == 64) return own ? launch<64, true, 1>(p, instances, lds, st) : launch<64, false, 1>(p, instances, lds, st);
-        return own ? launch<256, true, 1>(p, instances, lds, st) : launch<256, false, 1>(p, instances, lds, st);
+        if (p.contacts == 2 ? !p.c_box : p.contacts != 1) return hipErrorInvalidValue;
     }
-    if (p.block == 64) return own ? launch<64, true, 0>(p, instances, lds, st) : launch<64, false, 0>(p, instances, lds, st);
-    return own ? launch<256, true, 0>(p, instances, lds, st) : launch<256, false, 0>(p, instances, lds, st);
+    // one instantiation per (block, OWN, CONTACT)
+    using Launch = hipError_t (*)(const RzPhysicsParams &, uint32_t, size_t, hipStream_t);
+    static const Launch table[2][2][3] = {
+        {{launch<64, false, 0>, launch<64, false, 1>, launch<64, false, 2>}, {launch<64, true, 0>, launch<64, true, 1>, launch<64, true, 2>}},
+        {{launch<256, false, 0>, launch<256, false, 1>, launch<256, false, 2>}, {launch<256, true, 0>, launch<256, true, 1>, launch<256, true, 2>}}};
+    return table[p.block == 256][own][p.contacts](p, instances, lds, st);
 }

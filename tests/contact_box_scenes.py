@@ -6,7 +6,7 @@ import numpy as np
 
 import contact_box_ref
 import contact_scenes as cs
-from contact_scenes import ALL, G_CHAIN, G_COLLIDER, PARAMS, SHORT, Builder, pose, ring, run_reference, write_pmx  # noqa: F401
+from contact_scenes import ALL, FORMS, G_CHAIN, G_COLLIDER, PARAMS, SHORT, Builder, pose, ring, run_reference, write_pmx  # noqa: F401
 from physics_scenes import _quat
 
 PI = float(np.pi)
@@ -166,7 +166,6 @@ _CASES = {
     "box pair": (lambda: with_box_pair(), 0.3, SHORT),
     "params": (lambda: strands(6, 3, 76, **PARAMS), 0.5, SHORT),
 }
-FORMS = {"own 64": (64, 1), "stride 64": (64, 0), "own 256": (256, 1), "stride 256": (256, 0)}
 # the region a case is there for: (clamped coordinates of the closest point, whether the bisection decides s)
 REGIONS = {"sphere face": (1, False), "sphere edge": (2, False), "sphere corner": (3, False), "capsule end on": (1, False),
            "capsule across edge": (2, True), "capsule tilted": (1, False), "deep": (0, False)}

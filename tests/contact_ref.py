@@ -39,21 +39,28 @@ from physics_ref import EPS, cross, dot, qconj, qrot, rot_apply
 MAX_CANDIDATES = 65536
 
 
-def contact_lists(t):
-    """What enabling contacts derives from a table: per-body shape records, the follow CSR, the coloured dynamic pairs."""
+def contact_lists(t, boxes=False):
+    """What enabling contacts derives from a table: per-body shape records, the follow CSR, the coloured dynamic pairs. boxes=True
+    (contact_box_ref.py): boxes take part, and the keys `box` (the record's box bit), `ext` (half extents, zeros for non-boxes) and
+    `box_pairs` (candidate pairs of two boxes, left out) come with the rest."""
     nb = t["n_bodies"]
     dyn = physics_ref.is_dynamic(t)
     shape = np.asarray(t["shape"]).astype(np.int64)
     size = np.asarray(t["size"], dtype=np.float32).reshape(nb, 3)
     mask = np.asarray(t["mask"]).astype(np.int64)
     group = np.asarray(t["group"]).astype(np.int64)
-    radius = size[:, 0].copy()
+    box = (shape == 1) & boxes
+    radius = np.where(box, np.float32(0), size[:, 0]).astype(np.float32)
     half = np.where(shape == 2, size[:, 1].astype(np.float64) * 0.5, 0.0).astype(np.float32)
-    takes = ((shape == 0) | (shape == 2)) & (radius > 0) & (mask != 0)
+    takes_box = box & (size > 0).all(axis=1) & (mask != 0)
+    takes = (((shape == 0) | (shape == 2)) & (size[:, 0] > 0) & (mask != 0)) | takes_box
     bit = np.where(group < 16, np.left_shift(1, np.minimum(group, 15)), 0)
     hit = (bit[:, None] & mask[None, :]) != 0                     # hit[a, b]: a's group is in b's mask
     cand = takes[:, None] & takes[None, :] & hit & hit.T & (dyn[:, None] | dyn[None, :])
     cand &= np.triu(np.ones((nb, nb), dtype=bool), 1)
+    two = takes_box[:, None] & takes_box[None, :]
+    box_pairs = int((cand & two).sum())
+    cand &= ~two
     a, b = np.nonzero(cand)                                       # lexicographic (a, b)
     both = dyn[a] & dyn[b]
     follow_off = np.zeros(nb + 1, dtype=np.int64)
@@ -76,10 +83,13 @@ def contact_lists(t):
         colour[k] = c
     order = np.argsort(colour, kind="stable")
     ncol = int(colour.max()) + 1 if len(pa) else 0
-    return dict(radius=radius, half=half, friction=np.asarray(t["friction"], dtype=np.float32).reshape(nb), takes=takes,
-                follow_off=follow_off, follow_idx=partner.astype(np.int64), pairs=np.stack([pa[order], pb[order]], axis=1).reshape(-1, 2),
-                colour_off=np.searchsorted(colour[order], np.arange(ncol + 1)).astype(np.int64), n_colours=ncol,
-                n_follow=int(len(partner)), n_pairs=int(len(pa)), boxes=int(((shape == 1) & (mask != 0)).sum()))
+    L = dict(radius=radius, half=half, friction=np.asarray(t["friction"], dtype=np.float32).reshape(nb), takes=takes,
+             follow_off=follow_off, follow_idx=partner.astype(np.int64), pairs=np.stack([pa[order], pb[order]], axis=1).reshape(-1, 2),
+             colour_off=np.searchsorted(colour[order], np.arange(ncol + 1)).astype(np.int64), n_colours=ncol,
+             n_follow=int(len(partner)), n_pairs=int(len(pa)), boxes=int(((shape == 1) & (mask != 0) & ~takes_box).sum()))
+    if boxes:
+        L.update(box=box, ext=np.where(box[:, None], size, np.float32(0)).astype(np.float32), box_pairs=box_pairs)
+    return L
 
 
 def refusal(lists):
@@ -93,10 +103,10 @@ class Sim(physics_ref.Sim):
     """physics_ref.Sim with the contact stage. contacts=False steps exactly as physics_ref.Sim does. `active` gets, per substep, the number
     of contact solves that passed steps 2 and 4."""
 
-    def __init__(self, table, parents, bind, dtype=np.float64, contacts=True):
+    def __init__(self, table, parents, bind, dtype=np.float64, contacts=True, boxes=False):
         super().__init__(table, parents, bind, dtype=dtype)
         self.contacts = contacts
-        self.lists = L = contact_lists(table)
+        self.lists = L = contact_lists(table, boxes=boxes)
         self.cr, self.chl, self.cmu = L["radius"].astype(self.dt), L["half"].astype(self.dt), L["friction"].astype(self.dt)
         self.active = []
         # pass F by partner rank: rank k = the k-th partner of every dynamic body that has one
@@ -112,12 +122,9 @@ class Sim(physics_ref.Sim):
         return np.minimum(np.maximum(v, dt(0)), dt(1))
 
     def _contact(self, a, b, xp, qp):
-        c, dt = self.c, self.dt.type
+        dt = self.dt.type
         eps, one, zero = dt(EPS), dt(1), dt(0)
         xa, qa, xb, qb = self.x[a], self.q[a], self.x[b], self.q[b]
-        ima, imb, iia, iib = c["inv_mass"][a], c["inv_mass"][b], c["inv_inertia"][a], c["inv_inertia"][b]
-        da, db = c["dyn"][a], c["dyn"][b]
-        rA, rB = self.cr[a], self.cr[b]
 
         def axis(q, hl):
             u = np.zeros((len(hl), 3), dtype=self.dt)
@@ -141,12 +148,24 @@ class Sim(physics_ref.Sim):
         s = np.where(dega, zero, np.where(dege, s_lo, s_g))
         t = np.where(dega, np.where(dege, zero, self._clamp01(F / se_)), np.where(dege, zero, t_g))
         cA, cB = p1 + d1 * s[:, None], p2 + d2 * t[:, None]
-        # 2 - 4
+        # 2, and n of 3
         d = cB - cA
         dist = np.sqrt(dot(d, d))
-        pen = (rA + rB) - dist
+        pen = (self.cr[a] + self.cr[b]) - dist
         ok = (pen > zero) & (dist > eps)
         n = d / np.where(ok, dist, one)[:, None]
+        return int(self._resolve(a, b, cA, cB, n, pen, ok, xp, qp).sum())
+
+    def _resolve(self, a, b, cA, cB, n, pen, ok, xp, qp):
+        """Steps 3 - 7 for the pairs (a, b) whose front end found the points cA and cB, the normal n from A to B and the penetration pen;
+        `ok` marks the rows that passed step 2. Returns the rows that passed step 4 as well (the active contacts)."""
+        c, dt = self.c, self.dt.type
+        eps, one, zero = dt(EPS), dt(1), dt(0)
+        xa, qa, xb, qb = self.x[a], self.q[a], self.x[b], self.q[b]
+        ima, imb, iia, iib = c["inv_mass"][a], c["inv_mass"][b], c["inv_inertia"][a], c["inv_inertia"][b]
+        da, db = c["dyn"][a], c["dyn"][b]
+        rA, rB = self.cr[a], self.cr[b]
+        # 3, 4
         ra, rb = (cA + n * rA[:, None]) - xa, (cB - n * rB[:, None]) - xb
         can, cbn = cross(ra, n), cross(rb, n)
         w = (ima + dot(can, self._iinv(qa, iia, can))) + (imb + dot(cbn, self._iinv(qb, iib, cbn)))
@@ -181,7 +200,7 @@ class Sim(physics_ref.Sim):
         # 7
         self.x[a[da]], self.q[a[da]] = xa2[da], qa2[da]
         self.x[b[db]], self.q[b[db]] = xb2[db], qb2[db]
-        return int(ok.sum())
+        return ok
 
     def substep(self):
         if not self.contacts:

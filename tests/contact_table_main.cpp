@@ -1,13 +1,16 @@
 // A stand-alone program around reze-engine_amd/csrc/contact_table.h (the GPU-free half of rz_physics_contacts): it reads the columns of a
 // table that decide contacts as text and prints the lists the call would upload, for tests/test_contact_cpu.py to compare with
-// tests/contact_ref.py. Also the program to build under -fsanitize=address,undefined.
+// tests/contact_ref.py and tests/test_contact_box_cpu.py with tests/contact_box_ref.py. Also the program to build under
+// -fsanitize=address,undefined.
+//   usage:  contact_table_main [boxes: 0 | 1]     (with the argument the same lines, 1: in the boxes mode, then `box_pairs` and `box`)
 //   input:  nb; then per body: type shape group mask size3 mass friction
 #include "../reze-engine_amd/csrc/contact_table.h"
 
 #include <iostream>
 
-int main()
+int main(int argc, char **argv)
 {
+    const bool boxes = argc > 1 && argv[1][0] == '1';
     uint32_t nb;
     std::cin >> nb;
     if (!std::cin || nb > (1u << 20)) { std::cerr << "bad count\n"; return 2; }
@@ -27,7 +30,7 @@ int main()
     t.n_bodies = nb; t.type = type.data(); t.shape = shape.data(); t.group = group.data(); t.mask = mask.data(); t.size3 = size.data();
     t.mass = mass.data(); t.friction = friction.data();
     rzphys::Contacts o;
-    rzphys::build_contacts(&t, o);
+    rzphys::build_contacts(&t, o, boxes);
     printf("counts %zu %zu %d %d\n", o.n_follow, o.n_pairs, o.ncol, o.boxes);
     printf("refused %d %s\n", o.too_many ? 1 : 0, o.too_many ? rzphys::contacts_refusal(o).c_str() : "");
     printf("shape");
@@ -44,6 +47,11 @@ int main()
     for (int v : o.pair) printf(" %d", v);
     printf("\ncolour_off");
     for (int v : o.colour_off) printf(" %d", v);
+    if (argc > 1) {
+        printf("\nbox_pairs %zu", o.box_pairs);
+        printf("\nbox");
+        for (float v : o.box) printf(" %.9g", v);
+    }
     printf("\n");
     return 0;
 }

@@ -1,5 +1,5 @@
 """Box contacts without a GPU: what the definition (tests/contact_box_ref.py) promises, its closest-point routine alone against a dense scan,
-the host half of rz_physics_contacts(ctx, 2) (reze-engine_amd/csrc/contact_table.h, through tests/contact_box_table_main.cpp built with
+the host half of rz_physics_contacts(ctx, 2) (reze-engine_amd/csrc/contact_table.h, through tests/contact_table_main.cpp built with
 -fsanitize=address,undefined) against the definition's lists, the conditioning and contact activity of every case
 tests/test_gpu_contact_boxes.py runs, and the Engine option 'boxes' against a recording addon."""
 import json
@@ -245,16 +245,12 @@ def dump(t):
 
 
 @pytest.fixture(scope="module")
-def tools(tmp_path_factory):
-    """(the boxes program, its sibling that calls the two-argument build_contacts), both under ASan and UBSan"""
-    d = tmp_path_factory.mktemp("contact_box_table")
-    out = []
-    for src in ("contact_box_table_main", "contact_table_main"):
-        exe = str(d / src)
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
-                               os.path.join(ROOT, "tests", src + ".cpp")])
-        out.append(exe)
-    return out
+def tool(tmp_path_factory):
+    """the table program under ASan and UBSan: with an argument (0 | 1) it prints the box lines too, without one what it always printed"""
+    exe = str(tmp_path_factory.mktemp("contact_box_table") / "contact_table_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(ROOT, "tests", "contact_table_main.cpp")])
+    return exe
 
 
 def run_tool(tool, t, *args):
@@ -272,12 +268,12 @@ def mixed_table():
 
 
 @pytest.mark.parametrize("name", ["own 64", "stride 256", "capsule box dd", "box pair", "mixed"])
-def test_host_lists_equal_the_definition(tools, name):
+def test_host_lists_equal_the_definition(tool, name):
     """shape records with the box bit, c_box, the follow CSR, the dynamic pairs in solve order, colour offsets and all counts, entry for
-    entry, with boxes taking part; without, the program prints what its sibling (the two-argument call) prints"""
+    entry, with boxes taking part; without, the program prints what it prints without the argument"""
     t = mixed_table() if name == "mixed" else bs.case(name)[0]["table"]
     L = br.contact_lists(t, boxes=True)
-    rows, _ = run_tool(tools[0], t, "1")
+    rows, _ = run_tool(tool, t, "1")
     assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and rows["refused"][0] == "0"
     assert int(rows["box_pairs"][0]) == L["box_pairs"]
     shape = np.array([float(v) for v in rows["shape"]], dtype=np.float32).reshape(-1, 4)
@@ -288,19 +284,19 @@ def test_host_lists_equal_the_definition(tools, name):
     assert [int(v) for v in rows["follow_off"]] == list(L["follow_off"]) and [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"])
     assert [int(v) for v in rows["pair"]] == list(L["pairs"].reshape(-1)) and [int(v) for v in rows["colour_off"]] == list(L["colour_off"])
     # boxes off
-    _, off = run_tool(tools[0], t, "0")
-    _, old = run_tool(tools[1], t)
+    _, off = run_tool(tool, t, "0")
+    _, old = run_tool(tool, t)
     assert off == old + "box_pairs 0\nbox\n"
     O = cr.contact_lists(t)
-    rows, _ = run_tool(tools[0], t, "0")
+    rows, _ = run_tool(tool, t, "0")
     assert [int(v) for v in rows["counts"]] == [O["n_follow"], O["n_pairs"], O["n_colours"], O["boxes"]]
 
 
-def test_host_refuses_one_past_the_limit_with_boxes(tools):
+def test_host_refuses_one_past_the_limit_with_boxes(tool):
     """256 dynamic spheres x 256 following boxes = 65 536 candidates are taken, 256 x 257 are refused with both counts in the message"""
-    rows, _ = run_tool(tools[0], limit_table(256), "1")
+    rows, _ = run_tool(tool, limit_table(256), "1")
     assert rows["counts"][:2] == ["65536", "0"] and rows["refused"][0] == "0" and len(rows["follow_idx"]) == 65536
-    rows, out = run_tool(tools[0], limit_table(257), "1")
+    rows, out = run_tool(tool, limit_table(257), "1")
     assert rows["counts"][:2] == ["65792", "0"] and rows["refused"][0] == "1" and rows.get("follow_idx", []) == []
     assert "65792 follow entries and 0 dynamic pairs" in out and "broad phase" in out
     assert br.refusal(br.contact_lists(limit_table(257), boxes=True)) and not br.refusal(br.contact_lists(limit_table(256), boxes=True))

@@ -17,12 +17,10 @@ import pytest
 import contact_box_ref
 import contact_box_scenes as bs
 import contact_ref
-import physics_ref
 import physics_scenes as ps
-from helpers import NRM_TOL
+from physics_gpu import BAR, assert_bar, bits, dyn_bones, errors, make_ctx, same, set_local, set_mode
 
 pytestmark = pytest.mark.gpu
-BAR = 1e-4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("physics_contacts", "physics_contact_follow", "physics_contact_pairs", "physics_contact_colours", "physics_contact_boxes", "physics_contact_box_pairs")
 PARITY = os.path.join(ROOT, "profiles", "contact_box_edges_parity.txt")
@@ -46,71 +44,10 @@ def parity_file():
             f.write(HEAD + "\n" + "".join(_rows[name] + "\n" for name in bs._CASES))
 
 
-def make_ctx(rz, sc, instances=1, mode=2):
-    m = sc["mesh"]
-    c = rz.DeformContext(0)
-    c.upload_mesh(m["pos"], m["nrm"], m["joints"], m["weights"])
-    c.upload_skeleton(m["inv_bind"])
-    c.upload_skeleton_topology(m["parents"], m["bind"])
-    if instances > 1:
-        c.set_instances(instances)
-    c.upload_physics(sc["table"])
-    set_mode(c, mode)
-    return c
-
-
-def set_mode(c, mode):
-    if mode == 2:
-        c.physics_contacts(True, boxes=True)
-    else:
-        c.physics_contacts(bool(mode))
-
-
-def set_local(c, poses):
-    c.set_pose_local(np.stack([p[0] for p in poses]), None, np.stack([p[1] for p in poses]))
-
-
-def errors(c, oracle, sc, i, ref_world, ref_state):
-    """(position, quaternion, world, deformed position [all but the quaternion in units of extent], normal) errors of instance i against
-    the reference's (world [B,16] with overrides, state [nb,13]); the frame has run"""
-    m, ext = sc["mesh"], sc["extent"]
-    st = c.read_physics(i).astype(np.float64)
-    assert np.isfinite(st).all()
-    ex = float(np.abs(st[:, :3] - ref_state[:, :3]).max()) / ext
-    eq = float(np.minimum(np.abs(st[:, 3:7] - ref_state[:, 3:7]).max(axis=1), np.abs(st[:, 3:7] + ref_state[:, 3:7]).max(axis=1)).max())
-    wg = c.read_world(i).astype(np.float64)
-    ew = float(np.abs(wg - ref_world).max()) / ext
-    pg, ng = c.read(i)
-    pr, nr = oracle.deform(m["pos"], m["nrm"], m["joints"], m["weights"], ref_world.astype(np.float32), m["inv_bind"])
-    ep = float(np.abs(pg.astype(np.float64) - pr).max()) / ext
-    en = float(np.linalg.norm(ng.astype(np.float64) - nr, axis=1).max())
-    return ex, eq, ew, ep, en
-
-
-def assert_bar(e, what):
-    e = np.array(e).reshape(-1, 5)
-    worst = e.max(axis=0)
-    line = "%s: body position %.2e quaternion %.2e world %.2e deformed %.2e (x extent), normals %.2e" % ((what,) + tuple(worst))
-    print(line)
-    assert worst[0] <= BAR and worst[2] <= BAR and worst[3] <= BAR, "%s: position %.3e world %.3e deformed %.3e x extent" % (what, worst[0], worst[2], worst[3])
-    assert worst[1] <= BAR, "%s: quaternion %.3e" % (what, worst[1])
-    assert worst[4] <= NRM_TOL, "%s: normals %.3e" % (what, worst[4])
-    return line
-
-
-def dyn_bones(sc):
-    dyn = physics_ref.prepare(sc["table"], sc["parents"], sc["bind"])["dyn_bodies"]
-    return [int(sc["table"]["bone"][b]) for b in dyn]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def run(rz, sc, poses, calls, mode=2, split=False, detour=()):
     """one instance through the calls; (state, world) after the last frame. split: every call of n substeps as n calls of one. detour: the
     modes to pass through (ending in `mode` again) behind the first call"""
-    with make_ctx(rz, sc, mode=mode) as c:
+    with make_ctx(rz, sc, contacts=mode) as c:
         for k, ((q, t), n) in enumerate(zip(poses, calls)):
             set_local(c, [(q, t)])
             for part in ([1] * n if split else [n]):
@@ -125,11 +62,6 @@ def run(rz, sc, poses, calls, mode=2, split=False, detour=()):
         return c.read_physics(0), c.read_world(0)
 
 
-def same(a, b, bones):
-    (sa, wa), (sb, wb) = a, b
-    return np.isfinite(sa).all() and np.array_equal(bits(sa), bits(sb)) and np.array_equal(bits(wa[bones]), bits(wb[bones]))
-
-
 @pytest.mark.parametrize("name", list(bs._CASES))
 def test_case_against_the_definition(rz, oracle, name):
     """every case of contact_box_scenes (the four instantiations, the shape pairs in both index orders and three roles, the regions of the
@@ -140,7 +72,7 @@ def test_case_against_the_definition(rz, oracle, name):
     ref, _ = bs.reference(name)
     L = contact_box_ref.contact_lists(sc["table"], boxes=True)
     errs = []
-    with make_ctx(rz, sc) as c:
+    with make_ctx(rz, sc, contacts=2) as c:
         assert [c.get_tuning(k) for k in KEYS] == [2, L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"], L["box_pairs"]]
         if name in bs.FORMS:
             assert (c.get_tuning("physics_block"), c.get_tuning("physics_own")) == bs.FORMS[name]
@@ -167,7 +99,7 @@ def test_crowd_instances_equal_the_sequence_run_alone(rz, oracle):
     poses = [[bs.pose(sc, k, amounts[i], turn=0.05 + 0.02 * i) for k in range(len(calls))] for i in range(I)]
     refs = [bs.run_reference(sc, poses[i], calls, sim=bs.sim_of(sc)) for i in range(I)]
     errs = []
-    with make_ctx(rz, sc, instances=I) as c:
+    with make_ctx(rz, sc, instances=I, contacts=2) as c:
         for call, n in enumerate(calls):
             set_local(c, [poses[i][call] for i in range(I)])
             c.physics_step(n)
@@ -209,7 +141,7 @@ def test_the_old_paths_are_what_they_were(rz, kind):
     a, b = run(rz, a_sc, poses, calls, mode=a_mode), run(rz, b_sc, poses, calls, mode=b_mode)
     print("%s: state differs by %.2e" % (kind, np.abs(a[0] - b[0]).max()))
     assert same(a, b, dyn_bones(sc))
-    with make_ctx(rz, a_sc, mode=a_mode) as c:
+    with make_ctx(rz, a_sc, contacts=a_mode) as c:
         L = contact_ref.contact_lists(a_sc["table"])
         assert [c.get_tuning(k) for k in KEYS] == [a_mode, L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"], 0]
 
@@ -220,7 +152,7 @@ def test_a_pair_of_two_boxes_is_counted_and_changes_nothing(rz):
     _, poses, calls = bs.case("box pair")
     La, Lb = (contact_box_ref.contact_lists(s["table"], boxes=True) for s in (a_sc, b_sc))
     assert (La["box_pairs"], Lb["box_pairs"]) == (1, 0) and La["n_follow"] == Lb["n_follow"] > 0
-    with make_ctx(rz, b_sc) as c:
+    with make_ctx(rz, b_sc, contacts=2) as c:
         assert c.get_tuning("physics_contact_box_pairs") == 0 and c.get_tuning("physics_contact_follow") == Lb["n_follow"]
     a, b = run(rz, a_sc, poses, calls), run(rz, b_sc, poses, calls)
     print("box pair counted vs masked apart: state differs by %.2e" % np.abs(a[0] - b[0]).max())
@@ -231,7 +163,7 @@ def test_switching_between_the_modes(rz):
     """2 -> 0 zeroes every key; 1 -> 2 -> 1 (a substep under 2 in between) leaves the state bit-identical to never having left 1 when the
     boxes are out of reach; the simulation is not reset by any switch"""
     sc, poses, _ = bs.case("own 64")
-    with make_ctx(rz, sc) as c:
+    with make_ctx(rz, sc, contacts=2) as c:
         set_local(c, [poses[1]])
         c.physics_step(3)
         before = c.read_physics(0)
@@ -267,7 +199,7 @@ def test_refusals(rz):
         assert word in str(e.value), str(e.value)
         if code is not None:
             assert e.value.code == code, e.value.code
-    with make_ctx(rz, sc) as c:
+    with make_ctx(rz, sc, contacts=2) as c:
         before = [c.get_tuning(k) for k in KEYS]
         f = c.fork()
         try:

@@ -14,73 +14,18 @@ import pytest
 
 import contact_ref
 import contact_scenes as cs
-import physics_ref
 import physics_scenes as ps
-from helpers import NRM_TOL
+from physics_gpu import BAR, assert_bar, bits, dyn_bones, errors, make_ctx, set_local
 
 pytestmark = pytest.mark.gpu
-BAR = 1e-4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("physics_contacts", "physics_contact_follow", "physics_contact_pairs", "physics_contact_colours", "physics_contact_boxes")
-
-
-def make_ctx(rz, sc, instances=1, contacts=True):
-    m = sc["mesh"]
-    c = rz.DeformContext(0)
-    c.upload_mesh(m["pos"], m["nrm"], m["joints"], m["weights"])
-    c.upload_skeleton(m["inv_bind"])
-    c.upload_skeleton_topology(m["parents"], m["bind"])
-    if instances > 1:
-        c.set_instances(instances)
-    c.upload_physics(sc["table"])
-    if contacts:
-        c.physics_contacts(True)
-    return c
-
-
-def set_local(c, poses):
-    c.set_pose_local(np.stack([p[0] for p in poses]), None, np.stack([p[1] for p in poses]))
-
-
-def errors(c, oracle, sc, i, ref_world, ref_state):
-    """(position, quaternion, world, deformed position [all but the quaternion in units of extent], normal) errors of instance i against
-    the reference's (world [B,16] with overrides, state [nb,13]); the frame has run"""
-    m, ext = sc["mesh"], sc["extent"]
-    st = c.read_physics(i).astype(np.float64)
-    assert np.isfinite(st).all()
-    ex = float(np.abs(st[:, :3] - ref_state[:, :3]).max()) / ext
-    eq = float(np.minimum(np.abs(st[:, 3:7] - ref_state[:, 3:7]).max(axis=1), np.abs(st[:, 3:7] + ref_state[:, 3:7]).max(axis=1)).max())
-    wg = c.read_world(i).astype(np.float64)
-    ew = float(np.abs(wg - ref_world).max()) / ext
-    pg, ng = c.read(i)
-    pr, nr = oracle.deform(m["pos"], m["nrm"], m["joints"], m["weights"], ref_world.astype(np.float32), m["inv_bind"])
-    ep = float(np.abs(pg.astype(np.float64) - pr).max()) / ext
-    en = float(np.linalg.norm(ng.astype(np.float64) - nr, axis=1).max())
-    return ex, eq, ew, ep, en
-
-
-def assert_bar(e, what):
-    e = np.array(e).reshape(-1, 5)
-    worst = e.max(axis=0)
-    print("%s: body position %.2e quaternion %.2e world %.2e deformed %.2e (x extent), normals %.2e" % ((what,) + tuple(worst)))
-    assert worst[0] <= BAR and worst[2] <= BAR and worst[3] <= BAR, "%s: position %.3e world %.3e deformed %.3e x extent" % (what, worst[0], worst[2], worst[3])
-    assert worst[1] <= BAR, "%s: quaternion %.3e" % (what, worst[1])
-    assert worst[4] <= NRM_TOL, "%s: normals %.3e" % (what, worst[4])
-
-
-def dyn_bones(sc):
-    dyn = physics_ref.prepare(sc["table"], sc["parents"], sc["bind"])["dyn_bodies"]
-    return [int(sc["table"]["bone"][b]) for b in dyn]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def run(rz, sc, poses, calls, contacts=True, toggle=False, split=False):
     """one instance through the calls; (state, world) after the last frame. toggle: contacts on and off again before the first step.
     split: every call of n substeps as n calls of one"""
-    with make_ctx(rz, sc, contacts=contacts) as c:
+    with make_ctx(rz, sc, contacts=int(contacts)) as c:
         if toggle:
             c.physics_contacts(True)
             assert c.get_tuning("physics_contacts") == 1
@@ -103,7 +48,7 @@ def test_case_against_the_definition(rz, oracle, name):
     ref, _ = cs.reference(name)
     L = contact_ref.contact_lists(sc["table"])
     errs = []
-    with make_ctx(rz, sc) as c:
+    with make_ctx(rz, sc, contacts=1) as c:
         assert [c.get_tuning(k) for k in KEYS] == [1, L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]]
         if name in cs.FORMS:
             assert (c.get_tuning("physics_block"), c.get_tuning("physics_own")) == cs.FORMS[name]
@@ -129,7 +74,7 @@ def test_crowd_instances_equal_the_sequence_run_alone(rz, oracle):
     poses = [[cs.pose(sc, k, amounts[i], turn=0.05 + 0.02 * i) for k in range(len(calls))] for i in range(I)]
     refs = [cs.run_reference(sc, poses[i], calls, sim=contact_ref.Sim(sc["table"], sc["parents"], sc["bind"])) for i in range(I)]
     errs = []
-    with make_ctx(rz, sc, instances=I) as c:
+    with make_ctx(rz, sc, instances=I, contacts=1) as c:
         for call, n in enumerate(calls):
             set_local(c, [poses[i][call] for i in range(I)])
             c.physics_step(n)
@@ -182,7 +127,7 @@ def test_replays_do_not_advance(rz):
     """rz_deform_n replays the resident overrides with contacts on: the state and the frame stay where the step left them; enabling and
     disabling between replays changes no frame either (the overrides are resident, the simulation is not reset)"""
     sc, poses, _ = cs.case("own 64")
-    with make_ctx(rz, sc) as c:
+    with make_ctx(rz, sc, contacts=1) as c:
         for k, n in enumerate(cs.SHORT):
             set_local(c, [poses[k]])
             c.physics_step(n)
@@ -210,7 +155,7 @@ def test_misuse(rz):
         assert word in str(e.value), str(e.value)
         if code is not None:
             assert e.value.code == code, e.value.code
-    with make_ctx(rz, sc, contacts=False) as c:
+    with make_ctx(rz, sc) as c:
         # no table
         c.upload_physics(None)
         refused(lambda: c.physics_contacts(True), "no physics table", code=-1)

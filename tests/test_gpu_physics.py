@@ -16,55 +16,10 @@ import motion_ref
 import physics_ref
 import physics_scenes as ps
 from helpers import NRM_TOL, sample_reference
+from physics_gpu import BAR, assert_bar, errors, make_ctx, set_local
 
 pytestmark = pytest.mark.gpu
-BAR = 1e-4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def make_ctx(rz, sc, instances=1, table=True, chains=None):
-    m = sc["mesh"]
-    c = rz.DeformContext(0)
-    c.upload_mesh(m["pos"], m["nrm"], m["joints"], m["weights"])
-    c.upload_skeleton(m["inv_bind"])
-    c.upload_skeleton_topology(m["parents"], m["bind"])
-    if instances > 1:
-        c.set_instances(instances)
-    if chains:
-        c.upload_ik(chains)
-    if table:
-        c.upload_physics(sc["table"])
-    return c
-
-
-def set_local(c, poses):
-    c.set_pose_local(np.stack([p[0] for p in poses]), None, np.stack([p[1] for p in poses]))
-
-
-def errors(c, oracle, sc, i, ref_world, ref_state):
-    """(position, quaternion, world, deformed position [all but the quaternion in units of extent], normal) errors of instance i against
-    the reference's (world [B,16] with overrides, state [nb,13]); the frame has run"""
-    m, ext = sc["mesh"], sc["extent"]
-    st = c.read_physics(i).astype(np.float64)
-    assert np.isfinite(st).all()
-    ex = float(np.abs(st[:, :3] - ref_state[:, :3]).max()) / ext
-    eq = float(np.minimum(np.abs(st[:, 3:7] - ref_state[:, 3:7]).max(axis=1), np.abs(st[:, 3:7] + ref_state[:, 3:7]).max(axis=1)).max())
-    wg = c.read_world(i).astype(np.float64)
-    ew = float(np.abs(wg - ref_world).max()) / ext
-    pg, ng = c.read(i)
-    pr, nr = oracle.deform(m["pos"], m["nrm"], m["joints"], m["weights"], ref_world.astype(np.float32), m["inv_bind"])
-    ep = float(np.abs(pg.astype(np.float64) - pr).max()) / ext
-    en = float(np.linalg.norm(ng.astype(np.float64) - nr, axis=1).max())
-    return ex, eq, ew, ep, en
-
-
-def assert_bar(e, what):
-    e = np.array(e).reshape(-1, 5)
-    worst = e.max(axis=0)
-    print("%s: body position %.2e quaternion %.2e world %.2e deformed %.2e (x extent), normals %.2e" % ((what,) + tuple(worst)))
-    assert worst[0] <= BAR and worst[2] <= BAR and worst[3] <= BAR, "%s: position %.3e world %.3e deformed %.3e x extent" % (what, worst[0], worst[2], worst[3])
-    assert worst[1] <= BAR, "%s: quaternion %.3e" % (what, worst[1])
-    assert worst[4] <= NRM_TOL, "%s: normals %.3e" % (what, worst[4])
 
 
 @pytest.mark.parametrize("name", ["one body", "63 bodies", "65 bodies", "wide colour", "skirt", "one joint"])
