@@ -348,7 +348,7 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *      box of half extents (r, r + height/2, r) (r = size.x, height = size.y).
  *   3. every dynamic body with a bone gives boneWorld = bodyWorld x offset^-1: that bone's override, in every following frame until the
  *      next step. Children of an overridden bone keep the matrices solved from the un-overridden parent, as rz_override_world documents.
- * NOT covered: contacts unless rz_physics_contacts enables them (below), and then none that involve a box; linear springs (spring_position),
+ * NOT covered: contacts unless rz_physics_contacts enables them (below; boxes only under on = 2 and 3); linear springs (spring_position),
  * restitution. A welded joint (all limits equal) whose
  * anchor is off the body's centre converges only linearly in `iterations` (the position and the rotation stage each undo part of the
  * other): about 0.3 of a parent's jump is left at 4 iterations, 1e-5 of it at 32. Without contacts shapes feed the inertia only; group, mask
@@ -375,7 +375,7 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  * ---- contacts between rigid bodies — NEW (optional, off by default) ----
  * rz_physics_contacts(ctx, 1) adds a contact stage to rz_physics_kernel for the resident table (the reference registers every body with
  * 1 << group and its mask, physics.ts:257-269, and joints do not exempt their bodies); 2 adds it with the table's boxes taking part (`boxes`
- * below); 0 drops it. Defined in float64 by tests/contact_ref.py.
+ * below); 3 with pairs of two boxes as well (`box pairs` below); 0 drops it. Defined in float64 by tests/contact_ref.py.
  *   shapes      a sphere is the point x with radius size.x; a capsule the segment x +- q (0, size.y / 2, 0) with radius size.x (axis Y).
  *   candidates  fixed when the stage is enabled: all a < b with at least one dynamic body, both spheres or capsules with radius > 0, both
  *               masks nonzero, (1 << group[a]) & mask[b] and (1 << group[b]) & mask[a] both nonzero. follow pairs (one dynamic body):
@@ -415,18 +415,43 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *         sg e_i; pen = r + (e_i - |c_i|); n = N when the box is A, -N when it is B; steps 3 - 7 with this n and pen, without the
  *         dist > 1e-9 test.
  *         A pair without a box runs steps 1 - 7 as they are.
- *   NOT covered: box against box (left out, counted in "physics_contact_box_pairs"), restitution, a velocity pass (a penetration removed
- *   in one substep arrives as velocity, as in plain XPBD), a broad phase.
- * rz_physics_contacts: on = 1 (and every value but 0 and 2) builds and uploads the lists for the resident table, on = 2 the lists with
- *   the boxes taking part, on = 0 drops them; switching between 1 and 2 rebuilds them; none resets the simulation; all
+ *   box pairs   on = 3: everything on = 2 does, and a pair of two boxes that the rule pairs is a candidate like any other — it enters the
+ *               follow lists and the coloured dynamic pairs, counts toward the 65 536 candidates and is counted in
+ *               "physics_contact_box_box"; "physics_contact_box_pairs" is then 0. Defined in float64 by tests/contact_boxbox_ref.py. For
+ *               two boxes, A the lower index, with a_i = q_A axis_i, b_j = q_B axis_j, half extents eA and eB, t = x_B - x_A,
+ *               C_ij = a_i.b_j, tA_i = a_i.t, tB_j = b_j.t, step 1 becomes:
+ *     1a. the overlaps of the 15 axes. Face A_i: o = eA_i + sum_j eB_j |C_ij| - |tA_i|. Face B_j: o = sum_i eA_i |C_ij| + eB_j - |tB_j|.
+ *         Edge (i, j), with i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1, j2 likewise and l2 = 1 - C_ij^2, considered only when l2 > 1e-6:
+ *         o = (eA_i1 |C_i2,j| + eA_i2 |C_i1,j| + eB_j1 |C_i,j2| + eB_j2 |C_i,j1| - |tA_i2 C_i1,j - tA_i1 C_i2,j|) / sqrt(l2).
+ *         Any considered o <= 0: no contact.
+ *     1b. the face axis is the first smallest in the order A0 A1 A2 B0 B1 B2, the edge axis the first smallest in the order (0,0), (0,1)
+ *         .. (2,2); the edge wins only when o_edge < 0.95 o_face; pen is the chosen o.
+ *     1c. a face axis i of the reference box X, the other box Y incident: sg = +1 when the component along the axis of the vector from
+ *         x_X to x_Y is >= 0, else -1; N = sg axis. Y's point p = x_Y - sum_k clamp((N.y_k) / 0.05, -1, 1) eY_k y_k: a vertex, sliding
+ *         continuously to an edge midpoint or the face centre as Y's face becomes parallel to X's. p' = q_X^-1 (p - x_X) clamped to
+ *         [-eX, eX], its component i then set to sg eX_i; cX = x_X + q_X p', cY = cX - N pen; n = N when X is A, else -N.
+ *     1d. an edge axis (i, j): L = (a_i x b_j) / |a_i x b_j|, n = L when t.L >= 0, else -L. A's edge has its centre at
+ *         x_A + sum_{k != i} s_k eA_k a_k, s_k = +1 when a_k.n >= 0, else -1, and half length eA_i along a_i; B's at
+ *         x_B - sum_{k != j} s'_k eB_k b_k, s'_k from b_k.n likewise, half length eB_j along b_j. cA, cB are the closest points of the
+ *         two segments by the clamped solve of step 1 above.
+ *         Then steps 3 - 7 with both radii 0, without the dist > 1e-9 test. One point per pair and iteration: no manifold.
+ *         At rest a face on a face is the tie of 1b between A_i and B_i; the first in the order wins it. A thin plate lying flat is
+ *         turned back by about 60 g h^2 / e times its tilt per contact (e its larger half extent): at the default step and gravity
+ *         a plate with e of 0.6 and less rattles at rest by some 0.007 rad, one of 0.8 rests.
+ *   NOT covered: restitution, a velocity pass (a penetration removed in one substep arrives as velocity, as in plain XPBD), a broad
+ *   phase, a manifold of several points; under on = 2 box against box (left out, counted in "physics_contact_box_pairs").
+ * rz_physics_contacts: on = 1 (and every value but 0, 2 and 3) builds and uploads the lists for the resident table, on = 2 the lists with
+ *   the boxes taking part, on = 3 those with pairs of two boxes as well, on = 0 drops them; switching among 1, 2 and 3 rebuilds them; none resets the simulation; all
  *   drop a captured graph (replays still do not advance the simulation). A new rz_upload_physics, a table removal, a new skeleton or a
  *   new topology turns contacts off. RZ_ERR_INVALID: no resident table; a table uploaded with group, mask, friction or size3 NULL; forks
  *   exist. RZ_ERR_UNSUPPORTED (the context keeps its state): more than 65 536 candidates, follow entries + dynamic pairs — every pair of
  *   the table is tested, a broad phase does not exist yet. The stage adds no LDS: "physics_lds" and the 160 KB limit are unchanged.
- * rz_get_tuning("physics_contacts") = 0 / 1 / 2, ("physics_contact_follow") = the follow entries, ("physics_contact_pairs") = the dynamic
+ * rz_get_tuning("physics_contacts") = 0 / 1 / 2 / 3, ("physics_contact_follow") = the follow entries, ("physics_contact_pairs") = the dynamic
  * pairs, ("physics_contact_colours") = their colours, ("physics_contact_boxes") = the boxes with a nonzero mask that take no part (on = 1:
- * all of them; on = 2: those with an extent of 0), ("physics_contact_box_pairs") = the pairs of two boxes left out under on = 2 (a build
- * without box contacts does not know this key: that is how a binding detects them); all read-only, 0 without contacts. */
+ * all of them; on = 2 and 3: those with an extent of 0), ("physics_contact_box_pairs") = the pairs of two boxes left out under on = 2 (a build
+ * without box contacts does not know this key: that is how a binding detects them), ("physics_contact_box_box") = the pairs of two boxes
+ * taking part under on = 3, 0 in every other mode (a build without on = 3 does not know this key, the ABI version stayed 8: that is how a
+ * binding detects it); all read-only, 0 without contacts. */
 typedef struct rz_physics {
     uint32_t n_bodies;
     const int32_t *bone;                /* [n_bodies] -1 = none */

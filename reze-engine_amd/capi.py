@@ -669,15 +669,18 @@ class DeformContext:
     def physics_reset(self):
         self._chk(self._L.rz_physics_reset(self._h))
 
-    def physics_contacts(self, on=True, boxes=False):
+    def physics_contacts(self, on=True, boxes=False, box_pairs=False):
         """Contacts between the spheres and capsules of the resident physics table (off by default; include/reze_deform.h states the stage).
         boxes=True: the table's boxes take part against them as well (a pair of two boxes is left out and counted in the tuning key
-        physics_contact_box_pairs). A new table, skeleton or topology turns contacts off again. Does not reset the simulation."""
+        physics_contact_box_pairs). box_pairs=True (implies boxes): pairs of two boxes are candidates too, counted in the tuning key
+        physics_contact_box_box. A new table, skeleton or topology turns contacts off again. Does not reset the simulation."""
         if not hasattr(self._L, "rz_physics_contacts"):
             raise RzError(-6, "this build of the library has no rz_physics_contacts")
-        if on and boxes:
+        if on and box_pairs:
+            self.get_tuning("physics_contact_box_box")          # (a library without box - box contacts does not know the key: its error says so)
+        elif on and boxes:
             self.get_tuning("physics_contact_box_pairs")        # (a library without box contacts does not know the key: its error says so)
-        self._chk(self._L.rz_physics_contacts(self._h, (2 if boxes else 1) if on else 0))
+        self._chk(self._L.rz_physics_contacts(self._h, (3 if box_pairs else 2 if boxes else 1) if on else 0))
 
     def read_physics(self, instance=0):
         """[n_bodies, 13] x3 q4 v3 w3 of one instance (blocking)."""

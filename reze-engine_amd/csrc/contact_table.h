@@ -1,7 +1,8 @@
 // contact_table.h — the host half of rz_physics_contacts that needs no GPU: from the table as uploaded, the per-body shape records, the follow
 // lists and the coloured dynamic pairs the contact stage of rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams). Plain C++ without
 // HIP, beside physics_table.h: tests/contact_table_main.cpp compiles it alone, and the CPU tests hold the lists it prints to
-// tests/contact_ref.py entry for entry, and those of the boxes mode (rz_physics_contacts(ctx, 2)) to tests/contact_box_ref.py.
+// tests/contact_ref.py entry for entry, those of the boxes mode (rz_physics_contacts(ctx, 2)) to tests/contact_box_ref.py, and those with
+// pairs of two boxes kept (rz_physics_contacts(ctx, 3)) to tests/contact_boxbox_ref.py.
 #pragma once
 #include "physics_table.h"
 
@@ -21,6 +22,7 @@ struct Contacts {
     int ncol = 0, boxes = 0;            // boxes: those with a nonzero mask that take no part (boxes mode: the ones with an extent of 0)
     bool too_many = false;
     size_t box_pairs = 0;               // boxes mode: pairs of two boxes that the rule would pair; they are no candidates (left out, counted)
+    size_t n_box_box = 0;               // box_pairs kept: the pairs of two boxes among the candidates (box_pairs is then 0)
 };
 
 inline bool takes_part(const rz_physics *t, uint32_t b)
@@ -41,8 +43,9 @@ inline bool box_takes_part(const rz_physics *t, uint32_t b)
     return t->shape[b] == 1 && sz[0] > 0.0f && sz[1] > 0.0f && sz[2] > 0.0f && t->mask[b] != 0;
 }
 
-// t must carry group, mask, friction and size3. boxes: rz_physics_contacts(ctx, 2) — boxes take part against spheres and capsules
-inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
+// t must carry group, mask, friction and size3. boxes: rz_physics_contacts(ctx, 2) — boxes take part against spheres and capsules.
+// keep_box_pairs (with boxes): rz_physics_contacts(ctx, 3) — a pair of two boxes is a candidate like any other
+inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false, bool keep_box_pairs = false)
 {
     const uint32_t nb = t->n_bodies;
     o = Contacts();
@@ -62,16 +65,20 @@ inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
         if (on) in.push_back(b);
         if (t->shape[b] == 1 && t->mask[b] != 0 && !on) o.boxes++;
     }
-    // the rule, for a < b that both take part; a pair of two boxes passes it and is left out by both walks
+    // the rule, for a < b that both take part; a pair of two boxes passes it and is left out by both walks unless keep_box_pairs
     const auto pairs_up = [t](uint32_t a, uint32_t b) { return (dynamic(t, a) || dynamic(t, b)) && groups_meet(t, a, b); };
     const auto two_boxes = [t](uint32_t a, uint32_t b) { return t->shape[a] == 1 && t->shape[b] == 1; };
+    const bool keep = boxes && keep_box_pairs;
     // count first: the limit is checked before any list is built
     std::vector<int> nfol(nb, 0);
     for (size_t i = 0; i < in.size(); ++i)
         for (size_t k = i + 1; k < in.size(); ++k) {
             const uint32_t a = in[i], b = in[k];
             if (!pairs_up(a, b)) continue;
-            if (two_boxes(a, b)) { o.box_pairs++; continue; }
+            if (two_boxes(a, b)) {
+                if (!keep) { o.box_pairs++; continue; }
+                o.n_box_box++;
+            }
             const bool da = dynamic(t, a), db = dynamic(t, b);
             if (da && db) o.n_pairs++;
             else { nfol[da ? a : b]++; o.n_follow++; }
@@ -87,7 +94,7 @@ inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
     for (size_t i = 0; i < in.size(); ++i)
         for (size_t k = i + 1; k < in.size(); ++k) {
             const uint32_t a = in[i], b = in[k];
-            if (!pairs_up(a, b) || two_boxes(a, b)) continue;
+            if (!pairs_up(a, b) || (!keep && two_boxes(a, b))) continue;
             const bool da = dynamic(t, a), db = dynamic(t, b);
             if (!(da && db)) {
                 // (a, b) ascends lexicographically, so a dynamic body meets its partners in ascending order whichever side it is on
@@ -117,9 +124,10 @@ inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false)
 
 inline std::string contacts_refusal(const Contacts &o)
 {
-    char m[240];
-    snprintf(m, sizeof m, "rz_physics_contacts: %zu follow entries and %zu dynamic pairs are more than %zu candidates: every pair of the table is tested, a broad phase does not exist yet",
-             o.n_follow, o.n_pairs, kMaxContactCandidates);
+    char m[280], of_boxes[64] = "";
+    if (o.n_box_box) snprintf(of_boxes, sizeof of_boxes, " (%zu of them pairs of two boxes)", o.n_box_box);
+    snprintf(m, sizeof m, "rz_physics_contacts: %zu follow entries and %zu dynamic pairs%s are more than %zu candidates: every pair of the table is tested, a broad phase does not exist yet",
+             o.n_follow, o.n_pairs, of_boxes, kMaxContactCandidates);
     return m;
 }
 

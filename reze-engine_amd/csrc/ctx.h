@@ -195,11 +195,11 @@ struct rz_ctx : RzStatic, RzTuning {
     std::vector<uint16_t> ph_mask;
     std::vector<float> ph_size, ph_friction, ph_mass;
     // the contact stage (rz_physics_contacts): off unless ph_contacts; the lists are constants of the resident table
-    int ph_contacts = 0;                // 0 off | 1 spheres and capsules | 2 boxes take part as well
+    int ph_contacts = 0;                // 0 off | 1 spheres and capsules | 2 boxes take part as well | 3 and box against box
     float4 *ph_c_shape = nullptr, *ph_c_box = nullptr;
     int *ph_c_follow_off = nullptr, *ph_c_follow_idx = nullptr, *ph_c_colour_off = nullptr;
     int2 *ph_c_pair = nullptr;
-    uint32_t ph_c_follow = 0, ph_c_pairs = 0, ph_c_ncol = 0, ph_c_boxes = 0, ph_c_box_pairs = 0;
+    uint32_t ph_c_follow = 0, ph_c_pairs = 0, ph_c_ncol = 0, ph_c_boxes = 0, ph_c_box_pairs = 0, ph_c_box_box = 0;
 
     // per-frame state
     uint32_t I = 1;

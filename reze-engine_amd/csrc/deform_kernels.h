@@ -285,15 +285,15 @@ struct RzPhysicsParams {
     int reset;                  // every body (not only the following ones) is placed on its bone first
     int block;                  // 64 or 256 lanes
     float h, gx, gy, gz;
-    // the contact stage (rz_physics_contacts; contact_table.h derives the lists): null / 0 unless contacts is 1 or 2
+    // the contact stage (rz_physics_contacts; contact_table.h derives the lists): null / 0 unless contacts is 1, 2 or 3
     const float4 *c_shape;      // [nb]     radius | half length of the segment (0: a sphere) | friction | bits(1 = takes part, 4 = a box)
     const int *c_follow_off;    // [nb + 1] a dynamic body's following partners: c_follow_idx[c_follow_off[b] .. c_follow_off[b + 1]), ascending
     const int *c_follow_idx;
     const int2 *c_pair;         // [pairs]  dynamic pairs (a < b) in solve order (colour, a, b)
     const int *c_colour_off;    // [c_ncol + 1]
     int c_ncol;
-    int contacts;               // the CONTACT instantiations: 1 spheres and capsules | 2 boxes take part as well
-    const float4 *c_box;        // [nb]     contacts = 2 only: a box's half extents | 0, zeros for every other body (behind the rest:
+    int contacts;               // the CONTACT instantiations: 1 spheres and capsules | 2 boxes take part as well | 3 and box against box
+    const float4 *c_box;        // [nb]     contacts = 2 and 3 only: a box's half extents | 0, zeros for every other body (behind the rest:
                                 //          the arguments of the other instantiations stay where they were)
 };
 size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block);     // 96 B per body (+ 12 B per joint when the joints outnumber the lanes)

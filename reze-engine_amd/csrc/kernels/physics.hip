@@ -22,7 +22,9 @@
 // the code it was. One solver: a front end finds the contact points, the normal and the penetration (steps 1 and 2), resolve_contact
 // corrects and applies friction (steps 3 - 7). solve_contact is the front end for two segments. CONTACT = 2 (tests/contact_box_ref.py):
 // boxes take part against spheres and capsules — the body's record carries a box bit, its half extents come from c_box, and
-// solve_contact_boxes is the box front end, a fixed 24-step bisection in the box frame, ahead of the same resolve_contact.
+// solve_contact_boxes is the box front end, a fixed 24-step bisection in the box frame, ahead of the same resolve_contact. CONTACT = 3
+// (tests/contact_boxbox_ref.py): pairs of two boxes are candidates too — solve_contact_box_box is their front end, a separating-axis
+// search over the 15 axes and one contact point on the axis of least overlap, ahead of the same resolve_contact.
 #include "pass_parts.hip.h"
 
 namespace {
@@ -263,6 +265,30 @@ __device__ __forceinline__ void resolve_contact(CBody &A, CBody &B, const V3 cA,
     if (B.im > 0.0f) { const float4 qn = rot_apply(B.q, iinv(B.q, B.ii, cross3(rb2, pt))); B.x = B.x + pt * B.im; B.q = qn; }
 }
 
+// Step 1 of tests/contact_ref.py on its own, for the edges of two boxes: the closest points cA, cB of the segments p1 + s d1 and p2 + t d2,
+// s and t in [0, 1]. solve_contact below keeps its own spelling of the same solve: calling this one from there changes the instruction
+// streams of the CONTACT = 1 and 2 instantiations (four instructions fewer each), and those stay what they were.
+__device__ __forceinline__ void closest_on_segments(const V3 p1, const V3 d1, const V3 p2, const V3 d2, V3 &cA, V3 &cB)
+{
+    const V3 r = p1 - p2;
+    const float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r), c = dot3(d1, r), b = dot3(d1, d2);
+    float s, t;
+    if (a <= kEps) {
+        s = 0.0f;
+        t = e <= kEps ? 0.0f : clamp01(f / e);
+    } else if (e <= kEps) {
+        t = 0.0f;
+        s = clamp01(-c / a);
+    } else {
+        const float den = a * e - b * b;
+        s = den > kEps ? clamp01((b * f - c * e) / den) : 0.0f;
+        t = (b * s + f) / e;
+        if (t < 0.0f) { t = 0.0f; s = clamp01(-c / a); }
+        else if (t > 1.0f) { t = 1.0f; s = clamp01((b - c) / a); }
+    }
+    cA = p1 + d1 * s; cB = p2 + d2 * t;
+}
+
 // One contact, once, A the lower index: steps 1 and 2 for two segments (tests/contact_ref.py: Sim._contact, the same operations in the
 // same order), then resolve_contact.
 __device__ __forceinline__ void solve_contact(CBody &A, CBody &B)
@@ -380,6 +406,104 @@ __device__ __forceinline__ void solve_contact_boxes(CBox &A, CBox &B)
     resolve_contact(A, B, cA, cB, n, pen);
 }
 
+// component i of v, and the members of a triple rotated by i — (v_i, v_i+1, v_i+2) —, by selects: the box - box front end indexes nothing at
+// run time (a register array indexed by a variable would go to scratch)
+__device__ __forceinline__ float pick(const V3 v, const int i) { return i == 0 ? v.x : i == 1 ? v.y : v.z; }
+__device__ __forceinline__ float pick(const int i, const float a, const float b, const float c) { return i == 0 ? a : i == 1 ? b : c; }
+__device__ __forceinline__ V3 pick(const int i, const V3 a, const V3 b, const V3 c)
+{
+    return v3(pick(i, a.x, b.x, c.x), pick(i, a.y, b.y, c.y), pick(i, a.z, b.z, c.z));
+}
+__device__ __forceinline__ float clamp11(const float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
+__device__ __forceinline__ float sign_of(const float v) { return v >= 0.0f ? 1.0f : -1.0f; }
+
+// CONTACT = 3, one contact of two boxes, A the lower index: step 1 of tests/contact_boxbox_ref.py (Sim._boxbox_contact, the same operations
+// in the same order) — the overlaps of the 15 axes, the choice between the best face and the best edge axis, the face's or the edges'
+// contact points — then resolve_contact. The 15 axes are walked with compile-time indices; "the first smallest" is a chain of strict <.
+__device__ __forceinline__ void solve_contact_box_box(CBox &A, CBox &B)
+{
+    const V3 a0 = qrot(A.q, v3(1.0f, 0.0f, 0.0f)), a1 = qrot(A.q, v3(0.0f, 1.0f, 0.0f)), a2 = qrot(A.q, v3(0.0f, 0.0f, 1.0f));
+    const V3 b0 = qrot(B.q, v3(1.0f, 0.0f, 0.0f)), b1 = qrot(B.q, v3(0.0f, 1.0f, 0.0f)), b2 = qrot(B.q, v3(0.0f, 0.0f, 1.0f));
+    const V3 t = B.x - A.x;
+    const V3 c0 = v3(dot3(a0, b0), dot3(a0, b1), dot3(a0, b2)), c1 = v3(dot3(a1, b0), dot3(a1, b1), dot3(a1, b2)), c2 = v3(dot3(a2, b0), dot3(a2, b1), dot3(a2, b2));
+    const V3 tA = v3(dot3(a0, t), dot3(a1, t), dot3(a2, t)), tB = v3(dot3(b0, t), dot3(b1, t), dot3(b2, t));
+    const V3 eA = A.e, eB = B.e;
+    // 1a, 1b: the faces in the order A0 A1 A2 B0 B1 B2
+    float of = 0.0f, oe = 0.0f;
+    int kf = 0, ke = -1;
+    bool apart = false;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int i = k % 3;
+        float o;
+        if (k < 3) {
+            const V3 c = pick(i, c0, c1, c2);
+            o = (pick(eA, i) + ((eB.x * fabsf(c.x) + eB.y * fabsf(c.y)) + eB.z * fabsf(c.z))) - fabsf(pick(tA, i));
+        } else {
+            o = (((eA.x * fabsf(pick(c0, i)) + eA.y * fabsf(pick(c1, i))) + eA.z * fabsf(pick(c2, i))) + pick(eB, i)) - fabsf(pick(tB, i));
+        }
+        apart = apart || o <= 0.0f;
+        if (k == 0 || o < of) { of = o; kf = k; }
+    }
+    // the edges in the order (0,0), (0,1) .. (2,2); a near-parallel pair is not considered
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int i = k / 3, j = k % 3, i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+        const V3 ci = pick(i, c0, c1, c2), ci1 = pick(i1, c0, c1, c2), ci2 = pick(i2, c0, c1, c2);
+        const float cij = pick(ci, j);
+        const float l2 = 1.0f - cij * cij;
+        const bool considered = l2 > 1e-6f;
+        const float r = ((pick(eA, i1) * fabsf(pick(ci2, j)) + pick(eA, i2) * fabsf(pick(ci1, j))) + pick(eB, j1) * fabsf(pick(ci, j2))) + pick(eB, j2) * fabsf(pick(ci, j1));
+        const float o = (r - fabsf(pick(tA, i2) * pick(ci1, j) - pick(tA, i1) * pick(ci2, j))) / sqrtf(considered ? l2 : 1.0f);
+        apart = apart || (considered && o <= 0.0f);
+        if (considered && (ke < 0 || o < oe)) { oe = o; ke = k; }
+    }
+    if (apart) return;
+    const bool edge = ke >= 0 && oe < 0.95f * of;
+    const float pen = edge ? oe : of;
+    V3 cA, cB, n;
+    if (!edge) {
+        // 1c. X the reference box, Y the incident one
+        const bool xa = kf < 3;
+        const int i = xa ? kf : kf - 3;
+        const V3 xX = xa ? A.x : B.x, xY = xa ? B.x : A.x, eX = xa ? eA : eB, eY = xa ? eB : eA;
+        const float4 qX = xa ? A.q : B.q;
+        const V3 y0 = xa ? b0 : a0, y1 = xa ? b1 : a1, y2 = xa ? b2 : a2;
+        const V3 axis = xa ? pick(i, a0, a1, a2) : pick(i, b0, b1, b2);
+        const float sg = sign_of(xa ? pick(tA, i) : -pick(tB, i));
+        const V3 N = axis * sg;
+        V3 p = xY - y0 * (clamp11(dot3(N, y0) / 0.05f) * eY.x);
+        p = p - y1 * (clamp11(dot3(N, y1) / 0.05f) * eY.y);
+        p = p - y2 * (clamp11(dot3(N, y2) / 0.05f) * eY.z);
+        const V3 pl = clamp3(qrot(qconj(qX), p - xX), neg(eX), eX);
+        const float on = sg * pick(eX, i);
+        const V3 cX = xX + qrot(qX, v3(i == 0 ? on : pl.x, i == 1 ? on : pl.y, i == 2 ? on : pl.z));
+        const V3 cY = cX - N * pen;
+        n = xa ? N : neg(N);
+        cA = xa ? cX : cY; cB = xa ? cY : cX;
+    } else {
+        // 1d. the two edges
+        const int i = ke / 3, j = ke - 3 * i;
+        const V3 ai = pick(i, a0, a1, a2), ai1 = pick(i, a1, a2, a0), ai2 = pick(i, a2, a0, a1);
+        const V3 bj = pick(j, b0, b1, b2), bj1 = pick(j, b1, b2, b0), bj2 = pick(j, b2, b0, b1);
+        const V3 c = cross3(ai, bj);
+        const V3 L = c / sqrtf(dot3(c, c));
+        n = dot3(t, L) >= 0.0f ? L : neg(L);
+        const V3 ctrA = (A.x + ai1 * (sign_of(dot3(ai1, n)) * pick(i, eA.y, eA.z, eA.x))) + ai2 * (sign_of(dot3(ai2, n)) * pick(i, eA.z, eA.x, eA.y));
+        const V3 ctrB = (B.x - bj1 * (sign_of(dot3(bj1, n)) * pick(j, eB.y, eB.z, eB.x))) - bj2 * (sign_of(dot3(bj2, n)) * pick(j, eB.z, eB.x, eB.y));
+        const V3 ua = ai * pick(eA, i), ub = bj * pick(eB, j);
+        closest_on_segments(ctrA - ua, ua + ua, ctrB - ub, ub + ub, cA, cB);
+    }
+    resolve_contact(A, B, cA, cB, n, pen);
+}
+
+// One contact under CONTACT = 3: no box — solve_contact; one box — the box front end; two boxes — solve_contact_box_box
+__device__ __forceinline__ void solve_contact_all(CBox &A, CBox &B)
+{
+    if (A.box && B.box) solve_contact_box_box(A, B);
+    else solve_contact_boxes(A, B);
+}
+
 // the contact stage's body and solve by mode. Two body types, not one with the box fields always there: CBody is small enough to come
 // back from its loader in registers, and growing it changes the code of CONTACT = 1 (profiles/contact_fold_identity.txt)
 template <int CONTACT> struct ContactOps {
@@ -397,6 +521,9 @@ template <> struct ContactOps<2> {
         return load_cbox(b, body, cshape, cbox, sx, sq, sxp, sqp);
     }
     static __device__ __forceinline__ void solve(Body &A, Body &B) { solve_contact_boxes(A, B); }
+};
+template <> struct ContactOps<3> : ContactOps<2> {
+    static __device__ __forceinline__ void solve(Body &A, Body &B) { solve_contact_all(A, B); }
 };
 
 template <int BLOCK, bool OWN, int CONTACT>
@@ -569,12 +696,14 @@ hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipSt
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (p.contacts) {
         if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
-        if (p.contacts == 2 ? !p.c_box : p.contacts != 1) return hipErrorInvalidValue;
+        if (p.contacts == 2 || p.contacts == 3 ? !p.c_box : p.contacts != 1) return hipErrorInvalidValue;
     }
     // one instantiation per (block, OWN, CONTACT)
     using Launch = hipError_t (*)(const RzPhysicsParams &, uint32_t, size_t, hipStream_t);
-    static const Launch table[2][2][3] = {
-        {{launch<64, false, 0>, launch<64, false, 1>, launch<64, false, 2>}, {launch<64, true, 0>, launch<64, true, 1>, launch<64, true, 2>}},
-        {{launch<256, false, 0>, launch<256, false, 1>, launch<256, false, 2>}, {launch<256, true, 0>, launch<256, true, 1>, launch<256, true, 2>}}};
+    static const Launch table[2][2][4] = {
+        {{launch<64, false, 0>, launch<64, false, 1>, launch<64, false, 2>, launch<64, false, 3>},
+         {launch<64, true, 0>, launch<64, true, 1>, launch<64, true, 2>, launch<64, true, 3>}},
+        {{launch<256, false, 0>, launch<256, false, 1>, launch<256, false, 2>, launch<256, false, 3>},
+         {launch<256, true, 0>, launch<256, true, 1>, launch<256, true, 2>, launch<256, true, 3>}}};
     return table[p.block == 256][own][p.contacts](p, instances, lds, st);
 }

@@ -460,13 +460,13 @@ static napi_value fn_physics_reset(napi_env env, napi_callback_info info)
 }
 
 /* physicsContacts(ctx, on): rz_physics_contacts — contacts between the spheres and capsules of the resident table, 1 on / 0 off / 2 on with
- * the boxes taking part */
+ * the boxes taking part / 3 on with the boxes taking part against each other as well */
 static napi_value fn_physics_contacts(napi_env env, napi_callback_info info)
 {
     ARGS(2);
     CTX(0);
     uint32_t on;
-    if (!get_u32(env, argv[1], &on) || on > 2) return throw_msg(env, "physicsContacts(ctx, on): on is 0, 1 or 2");
+    if (!get_u32(env, argv[1], &on) || on > 3) return throw_msg(env, "physicsContacts(ctx, on): on is 0, 1, 2 or 3");
     int rc = rz_physics_contacts(ctx, on);
     return rc ? throw_rz(env, rc) : undef(env);
 }

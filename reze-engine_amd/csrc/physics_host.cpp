@@ -13,7 +13,7 @@ void free_contacts(rz_ctx *c)
 {
     dfree(c->ph_c_shape); dfree(c->ph_c_box); dfree(c->ph_c_follow_off); dfree(c->ph_c_follow_idx); dfree(c->ph_c_pair); dfree(c->ph_c_colour_off);
     c->ph_contacts = 0;
-    c->ph_c_follow = c->ph_c_pairs = c->ph_c_ncol = c->ph_c_boxes = c->ph_c_box_pairs = 0;
+    c->ph_c_follow = c->ph_c_pairs = c->ph_c_ncol = c->ph_c_boxes = c->ph_c_box_pairs = c->ph_c_box_box = 0;
 }
 
 void free_physics(rz_ctx *c)
@@ -185,7 +185,7 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
         free_contacts(c);
         return RZ_OK;
     }
-    const int mode = on == 2 ? 2 : 1;    // (every other nonzero value is 1, as it always was)
+    const int mode = on == 2 || on == 3 ? (int)on : 1;    // (every other nonzero value is 1, as it always was)
     const size_t nb = c->ph_nb;
     if (c->ph_group.size() != nb || c->ph_mask.size() != nb || c->ph_friction.size() != nb || c->ph_size.size() != nb * 3)
         return fail(RZ_ERR_INVALID, "rz_physics_contacts: the resident table was uploaded without%s%s%s%s: contacts need group, mask, friction and size3",
@@ -196,14 +196,14 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
     t.n_bodies = c->ph_nb; t.type = c->ph_type.data(); t.shape = c->ph_shape.data(); t.group = c->ph_group.data(); t.mask = c->ph_mask.data();
     t.size3 = c->ph_size.data(); t.mass = c->ph_mass.data(); t.friction = c->ph_friction.data();
     rzphys::Contacts o;
-    rzphys::build_contacts(&t, o, mode == 2);
+    rzphys::build_contacts(&t, o, mode >= 2, mode == 3);
     if (o.too_many) return fail(RZ_ERR_UNSUPPORTED, "%s", rzphys::contacts_refusal(o).c_str());
     // the new lists first: a failed allocation leaves the context as it was
     float4 *shape = nullptr, *box = nullptr;
     int *foff = nullptr, *fidx = nullptr, *coff = nullptr;
     int2 *pair = nullptr;
     int r = to_device(&shape, o.shape.data(), nb);
-    if (!r && mode == 2) r = to_device(&box, o.box.data(), nb);
+    if (!r && mode >= 2) r = to_device(&box, o.box.data(), nb);
     if (!r) r = to_device(&foff, o.follow_off.data(), o.follow_off.size());
     if (!r) r = to_device(&fidx, o.follow_idx.data(), o.follow_idx.size());
     if (!r) r = to_device(&pair, o.pair.data(), o.pair.size() / 2);
@@ -215,7 +215,7 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
     free_contacts(c);
     c->ph_c_shape = shape; c->ph_c_box = box; c->ph_c_follow_off = foff; c->ph_c_follow_idx = fidx; c->ph_c_pair = pair; c->ph_c_colour_off = coff;
     c->ph_c_follow = (uint32_t)o.n_follow; c->ph_c_pairs = (uint32_t)o.n_pairs; c->ph_c_ncol = (uint32_t)o.ncol; c->ph_c_boxes = (uint32_t)o.boxes;
-    c->ph_c_box_pairs = (uint32_t)o.box_pairs;
+    c->ph_c_box_pairs = (uint32_t)o.box_pairs; c->ph_c_box_box = (uint32_t)o.n_box_box;
     c->ph_contacts = mode;
     return RZ_OK;
 }

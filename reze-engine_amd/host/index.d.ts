@@ -47,7 +47,7 @@ export interface EngineOptions {
   /** Physics hand-off (engine.ts:2379-2381), host-FK frames: step() may overwrite world matrices in place before they are uploaded. */
   physics?: { step(dt: number, boneWorldMatrices: Float32Array, boneInverseBindMatrices: Float32Array): void }
   /** Rigid-body physics on the GPU for the model's PMX bodies and joints (needs deviceFK; exclusive with `physics` and framesInFlight: 2). loadModel uploads Model.physicsTables() (rz_upload_physics); every frame turns the time the clock advanced since the last one into min(10, floor(accumulated / h)) fixed substeps of h = 1/75 s (rz_physics_step) before it deforms. No linear springs or restitution; contacts are opt-in (physicsContacts). */ devicePhysics?: boolean
-  /** With devicePhysics: contacts and friction between the model's sphere and capsule bodies by their PMX groups and masks (rz_physics_contacts, called on every shard right after the table's upload at loadModel). Off by default; without devicePhysics it throws. true: boxes take no part. 'boxes': the model's box bodies collide with its spheres and capsules as well (rz_physics_contacts(ctx, 2)); a pair of two boxes is still left out. */ physicsContacts?: boolean | 'boxes'
+  /** With devicePhysics: contacts and friction between the model's sphere and capsule bodies by their PMX groups and masks (rz_physics_contacts, called on every shard right after the table's upload at loadModel). Off by default; without devicePhysics it throws. true: boxes take no part. 'boxes': the model's box bodies collide with its spheres and capsules as well (rz_physics_contacts(ctx, 2)); a pair of two boxes is still left out. 'all': pairs of two boxes collide too (rz_physics_contacts(ctx, 3)). */ physicsContacts?: boolean | 'boxes' | 'all'
 }
 export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
 export interface EngineStats {

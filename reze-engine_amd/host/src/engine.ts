@@ -54,7 +54,7 @@ class Engine {
   physics: PhysicsLike | null
   lastPhysicsTime: number | null
   devicePhysics: boolean
-  physicsContacts: boolean | 'boxes'
+  physicsContacts: boolean | 'boxes' | 'all'
   physicsAccumulator: number
   physicsResident: boolean
   native: DeformAddon | null
@@ -132,8 +132,8 @@ class Engine {
     if (this.devicePhysics && !this.deviceFK) throw new Error('devicePhysics needs new Engine(canvas, { deviceFK: true }); with host FK pass { physics }')
     if (this.devicePhysics && this.physics) throw new Error('devicePhysics and { physics } are exclusive: both would write the physics-driven bones')
     // physicsContacts: contacts between the table's spheres and capsules (rz_physics_contacts), enabled on every shard behind the upload;
-    // 'boxes': its boxes take part as well
-    this.physicsContacts = o.physicsContacts === 'boxes' ? 'boxes' : o.physicsContacts === true
+    // 'boxes': its boxes take part as well; 'all': and its boxes meet each other
+    this.physicsContacts = o.physicsContacts === 'boxes' || o.physicsContacts === 'all' ? o.physicsContacts : o.physicsContacts === true
     if (this.physicsContacts && !this.devicePhysics) throw new Error('physicsContacts needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
     this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
     this.physicsResident = false
@@ -318,7 +318,7 @@ class Engine {
         // so is physics: every shard simulates the same bodies (the solve is deterministic), so no shard waits for another's overrides
         if (tables && tables.nBodies > 0) {
           n.uploadPhysics(s.ctx, tables)
-          if (this.physicsContacts) n.physicsContacts(s.ctx, this.physicsContacts === 'boxes' ? 2 : 1)
+          if (this.physicsContacts) n.physicsContacts(s.ctx, this.physicsContacts === 'all' ? 3 : this.physicsContacts === 'boxes' ? 2 : 1)
           this.physicsResident = true
         }
       }
