@@ -1,8 +1,8 @@
 // contact_table.h — the host half of rz_physics_contacts that needs no GPU: from the table as uploaded, the per-body shape records, the follow
 // lists and the coloured dynamic pairs the contact stage of rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams). Plain C++ without
-// HIP, beside physics_table.h: tests/contact_table_main.cpp compiles it alone, and the CPU tests hold the lists it prints to
-// tests/contact_ref.py entry for entry, those of the boxes mode (rz_physics_contacts(ctx, 2)) to tests/contact_box_ref.py, and those with
-// pairs of two boxes kept (rz_physics_contacts(ctx, 3)) to tests/contact_boxbox_ref.py.
+// HIP, beside physics_table.h: tests/contact_table_main.cpp compiles it alone, and the CPU tests hold the lists it prints under every mode
+// of rz_physics_contacts (1; 2, boxes take part; 3, pairs of two boxes kept) to contact_lists(table, mode) of tests/contact_ref.py entry
+// for entry.
 #pragma once
 #include "physics_table.h"
 
@@ -43,10 +43,11 @@ inline bool box_takes_part(const rz_physics *t, uint32_t b)
     return t->shape[b] == 1 && sz[0] > 0.0f && sz[1] > 0.0f && sz[2] > 0.0f && t->mask[b] != 0;
 }
 
-// t must carry group, mask, friction and size3. boxes: rz_physics_contacts(ctx, 2) — boxes take part against spheres and capsules.
-// keep_box_pairs (with boxes): rz_physics_contacts(ctx, 3) — a pair of two boxes is a candidate like any other
-inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false, bool keep_box_pairs = false)
+// t must carry group, mask, friction and size3. mode as rz_physics_contacts takes it: 1 — spheres and capsules; 2 — boxes take part against
+// them; 3 — a pair of two boxes is a candidate like any other
+inline void build_contacts(const rz_physics *t, Contacts &o, int mode)
 {
+    const bool boxes = mode >= 2, keep = mode == 3;
     const uint32_t nb = t->n_bodies;
     o = Contacts();
     o.shape.assign((size_t)nb * 4, 0.0f);
@@ -65,10 +66,9 @@ inline void build_contacts(const rz_physics *t, Contacts &o, bool boxes = false,
         if (on) in.push_back(b);
         if (t->shape[b] == 1 && t->mask[b] != 0 && !on) o.boxes++;
     }
-    // the rule, for a < b that both take part; a pair of two boxes passes it and is left out by both walks unless keep_box_pairs
+    // the rule, for a < b that both take part; a pair of two boxes passes it and is left out by both walks unless mode 3
     const auto pairs_up = [t](uint32_t a, uint32_t b) { return (dynamic(t, a) || dynamic(t, b)) && groups_meet(t, a, b); };
     const auto two_boxes = [t](uint32_t a, uint32_t b) { return t->shape[a] == 1 && t->shape[b] == 1; };
-    const bool keep = boxes && keep_box_pairs;
     // count first: the limit is checked before any list is built
     std::vector<int> nfol(nb, 0);
     for (size_t i = 0; i < in.size(); ++i)

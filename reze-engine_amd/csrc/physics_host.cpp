@@ -196,7 +196,7 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
     t.n_bodies = c->ph_nb; t.type = c->ph_type.data(); t.shape = c->ph_shape.data(); t.group = c->ph_group.data(); t.mask = c->ph_mask.data();
     t.size3 = c->ph_size.data(); t.mass = c->ph_mass.data(); t.friction = c->ph_friction.data();
     rzphys::Contacts o;
-    rzphys::build_contacts(&t, o, mode >= 2, mode == 3);
+    rzphys::build_contacts(&t, o, mode);
     if (o.too_many) return fail(RZ_ERR_UNSUPPORTED, "%s", rzphys::contacts_refusal(o).c_str());
     // the new lists first: a failed allocation leaves the context as it was
     float4 *shape = nullptr, *box = nullptr;

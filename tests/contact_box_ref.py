@@ -1,5 +1,6 @@
 """Contacts with PMX box bodies restated in NumPy: the definition rz_physics_contacts(ctx, 2) (kernels/physics.hip, CONTACT = 2) is held to.
-A subclass of contact_ref.Sim; include/reze_deform.h states the same in words. Everything contact_ref.py says holds; what changes:
+The front end contact_ref.Sim runs under modes 2 and 3 for a pair of a box and a round shape (Sim._box_contact); include/reze_deform.h
+states the same in words. Everything contact_ref.py says holds; what changes:
 
 Shapes    a box is shape 1: the set |y_i| <= e_i in its own frame, e = size (three half extents, as the inertia reads them). It takes part
           when all three are > 0 and its mask is nonzero, and counts as a shape of radius 0 with no segment. A box with a nonzero mask that
@@ -21,17 +22,9 @@ Pairs without a box run contact_ref.Sim._contact itself.
 """
 import numpy as np
 
-import contact_ref
-from contact_ref import MAX_CANDIDATES, refusal  # noqa: F401
 from physics_ref import EPS, dot, qconj, qrot
 
 BISECTIONS = 24
-
-
-def contact_lists(t, boxes=False):
-    """contact_ref.contact_lists, always with the keys `box`, `ext` and `box_pairs` (zeros unless boxes=True: boxes take part)"""
-    nb = t["n_bodies"]
-    return dict(dict(box=np.zeros(nb, dtype=bool), ext=np.zeros((nb, 3), dtype=np.float32), box_pairs=0), **contact_ref.contact_lists(t, boxes=boxes))
 
 
 def closest_on_segment(P, d, e, dt=np.float64):
@@ -56,68 +49,37 @@ def closest_on_segment(P, d, e, dt=np.float64):
     return s, c, np.minimum(np.maximum(c, -e), e)
 
 
-class Sim(contact_ref.Sim):
-    """contact_ref.Sim; boxes=True: with boxes taking part (rz_physics_contacts(ctx, 2)). `regions` counts the active box contacts by
-    (coordinates of the closest point that the clamp moved — 0 in the deep case —, whether s lies strictly inside (0, 1))."""
-
-    def __init__(self, table, parents, bind, dtype=np.float64, contacts=True, boxes=True):
-        super().__init__(table, parents, bind, dtype=dtype, contacts=contacts, boxes=boxes)
-        self.boxes = boxes
-        self.regions = {}
-        self.lists = L = contact_lists(table, boxes=boxes)
-        self.cbox, self.cext = L["box"] & L["takes"], L["ext"].astype(self.dt)
-
-    def _contact(self, a, b, xp, qp):
-        a, b = np.asarray(a), np.asarray(b)
-        wb = self.cbox[a] | self.cbox[b]
-        n = 0
-        if (~wb).any():
-            n += super()._contact(a[~wb], b[~wb], xp, qp)
-        if wb.any():
-            n += self._box_contact(a[wb], b[wb], xp, qp)
-        return n
-
-    def _box_contact(self, a, b, xp, qp):
-        dt = self.dt.type
-        eps, one, zero = dt(EPS), dt(1), dt(0)
-        rA, rB = self.cr[a], self.cr[b]
-        # 1. the box X = A or B, the round shape R the other
-        ax = self.cbox[a]
-        X, R = np.where(ax, a, b), np.where(ax, b, a)
-        xX, qX, xR, qR, e, r = self.x[X], self.q[X], self.x[R], self.q[R], self.cext[X], self.cr[R]
-        u = np.zeros((len(a), 3), dtype=self.dt)
-        u[:, 1] = self.chl[R]
-        u = qrot(qR, u)
-        P, d = xR - u, u + u
-        qi = qconj(qX)
-        Pl, dl_ = qrot(qi, P - xX), qrot(qi, d)
-        s, cl, bl = closest_on_segment(Pl, dl_, e, dt=dt)
-        cR = P + d * s[:, None]
-        gap = cl - bl
-        deep = ~(np.sqrt(dot(gap, gap)) > eps)
-        m = e - np.abs(cl)
-        i = np.argmin(m, axis=1)                                      # the first smallest
-        rows = np.arange(len(a))
-        sg = np.where(cl[rows, i] >= zero, one, -one)
-        face = cl.copy()
-        face[rows, i] = sg * e[rows, i]
-        unit = np.zeros((len(a), 3), dtype=self.dt)
-        unit[rows, i] = sg
-        N = qrot(qX, unit)
-        cX = xX + qrot(qX, np.where(deep[:, None], face, bl))
-        cA, cB = np.where(ax[:, None], cX, cR), np.where(ax[:, None], cR, cX)
-        # 2
-        dv = cB - cA
-        dist = np.sqrt(dot(dv, dv))
-        pen_s = (rA + rB) - dist
-        ok_s = (pen_s > zero) & (dist > eps)
-        n_s = dv / np.where(ok_s, dist, one)[:, None]
-        pen = np.where(deep, r + m[rows, i], pen_s)
-        n = np.where(deep[:, None], np.where(ax[:, None], N, -N), n_s)
-        ok = deep | ok_s
-        # 3 - 7
-        ok = self._resolve(a, b, cA, cB, n, pen, ok, xp, qp)
-        for k in np.nonzero(ok)[0]:
-            key = (int((cl[k] != bl[k]).sum()), bool(zero < s[k] < one))
-            self.regions[key] = self.regions.get(key, 0) + 1
-        return int(ok.sum())
+def front_end(box_is_a, xX, qX, e, P, d, r):
+    """Steps 1 and 2 for rows of pairs of a box X (half extents e) and a round shape R (segment P + s d in world space, radius r);
+    box_is_a: the box has the lower index. A dict with `ok` (step 2 passed), the contact points `cA` and `cB`, the normal `n` from A to B
+    and `pen`; and, for the tests: `moved` (coordinates of the closest point that the clamp moved, 0 in the deep case) and `inside` (s lies
+    strictly inside (0, 1))"""
+    dt = xX.dtype.type
+    eps, one, zero = dt(EPS), dt(1), dt(0)
+    ax = box_is_a[:, None]
+    rows = np.arange(len(xX))
+    # 1. a - c
+    qi = qconj(qX)
+    s, cl, bl = closest_on_segment(qrot(qi, P - xX), qrot(qi, d), e, dt=dt)
+    cR = P + d * s[:, None]
+    gap = cl - bl
+    deep = ~(np.sqrt(dot(gap, gap)) > eps)
+    # 1e
+    m = e - np.abs(cl)
+    i = np.argmin(m, axis=1)                                      # the first smallest
+    sg = np.where(cl[rows, i] >= zero, one, -one)
+    face = cl.copy()
+    face[rows, i] = sg * e[rows, i]
+    unit = np.zeros((len(xX), 3), dtype=xX.dtype)
+    unit[rows, i] = sg
+    N = qrot(qX, unit)
+    cX = xX + qrot(qX, np.where(deep[:, None], face, bl))
+    cA, cB = np.where(ax, cX, cR), np.where(ax, cR, cX)
+    # 2 (the box's radius is 0)
+    dv = cB - cA
+    dist = np.sqrt(dot(dv, dv))
+    pen_s = r - dist
+    ok_s = (pen_s > zero) & (dist > eps)
+    n_s = dv / np.where(ok_s, dist, one)[:, None]
+    return dict(ok=deep | ok_s, cA=cA, cB=cB, n=np.where(deep[:, None], np.where(ax, N, -N), n_s), pen=np.where(deep, r + m[rows, i], pen_s),
+                moved=(cl != bl).sum(axis=1), inside=(zero < s) & (s < one))

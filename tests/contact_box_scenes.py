@@ -4,7 +4,6 @@ move. Every case the GPU tests run is listed in _CASES and checked for condition
 (test_contact_box_cpu.py: test_cases_are_well_conditioned_and_touch)."""
 import numpy as np
 
-import contact_box_ref
 import contact_scenes as cs
 from contact_scenes import ALL, FORMS, G_CHAIN, G_COLLIDER, PARAMS, SHORT, Builder, pose, ring, run_reference, write_pmx  # noqa: F401
 from physics_scenes import _quat
@@ -170,52 +169,10 @@ _CASES = {
 REGIONS = {"sphere face": (1, False), "sphere edge": (2, False), "sphere corner": (3, False), "capsule end on": (1, False),
            "capsule across edge": (2, True), "capsule tilted": (1, False), "deep": (0, False)}
 CROWD = "own 64"
-_memo = {}
+_cases = cs.Cases(_CASES, 2)
+case, reference, conditioning, node_case, node_conditioning, sim_of = _cases.case, _cases.reference, _cases.conditioning, _cases.node_case, _cases.node_conditioning, _cases.sim_of
 
 
-def case(name):
-    """(scene, poses, calls)"""
-    if name not in _memo:
-        make, amount, calls = _CASES[name]
-        sc = make()
-        _memo[name] = (sc, [pose(sc, k, amount) for k in range(len(calls))], calls)
-    return _memo[name]
-
-
-def sim_of(sc, dtype=np.float64, boxes=True):
-    return contact_box_ref.Sim(sc["table"], sc["parents"], sc["bind"], dtype=dtype, boxes=boxes)
-
-
-def reference(name, dtype=np.float64):
-    """the case's run_reference with boxes taking part (memoised): per call (world [B,16], state [nb,13]); also the Sim"""
-    key = (name, np.dtype(dtype).name)
-    if key not in _memo:
-        sc, poses, calls = case(name)
-        sim = sim_of(sc, dtype)
-        _memo[key] = (run_reference(sc, poses, calls, dtype=dtype, sim=sim), sim)
-    return _memo[key]
-
-
-def conditioning(name):
-    """(largest float32-probe deviation from the float64 run in units of extent, the fraction of substeps with an active contact, the
-    probe's largest quaternion deviation up to sign)"""
-    sc, _, _ = case(name)
-    a, sim = reference(name)
-    b, _ = reference(name, dtype=np.float32)
-    worst = turn = 0.0
-    for (wa, sa), (wb, sb) in zip(a, b):
-        worst = max(worst, float(np.abs(wa - wb).max()), float(np.abs(sa[:, :3] - sb[:, :3]).max()))
-        turn = max(turn, float(np.minimum(np.abs(sa[:, 3:7] - sb[:, 3:7]).max(axis=1), np.abs(sa[:, 3:7] + sb[:, 3:7]).max(axis=1)).max()))
-    act = np.array(sim.active)
-    return worst / sc["extent"], float((act > 0).mean()), turn
-
-
-def node_case():
-    """The Node end-to-end test's scene: the 'own 64' chains as a PMX file, run with the table its loader derives from the file, under one
-    fixed local pose of the carrier. Returns (scene, pmx bytes, q [B,4])."""
-    if "node" not in _memo:
-        sc, _, _ = case("own 64")
-        data, want = write_pmx(sc)
-        q, _ = pose(sc, 3, turn=0.5)
-        _memo["node"] = (dict(sc, table=want), data, q)
-    return _memo["node"]
+def limit_table(n_follow):
+    """256 dynamic spheres x n_follow following boxes, all in each other's masks: 256 n_follow follow entries against boxes"""
+    return cs.limit_table(n_follow, fol_shape=1)

@@ -1,6 +1,6 @@
 """Contacts between two PMX box bodies restated in NumPy: the definition rz_physics_contacts(ctx, 3) (kernels/physics.hip, CONTACT = 3) is
-held to. A subclass of contact_box_ref.Sim; include/reze_deform.h states the same in words. Everything contact_box_ref.py says holds; what
-changes:
+held to. The front end contact_ref.Sim runs under mode 3 for a pair of two boxes (Sim._boxbox_contact); include/reze_deform.h states the
+same in words. Everything contact_box_ref.py says holds; what changes:
 
 Pairs     a pair of two boxes that the rule pairs is a candidate like any other: it enters the follow lists and the coloured dynamic pairs,
           counts toward the 65 536-candidate limit and is counted in `n_box_box`; `box_pairs`, the pairs left out, is 0.
@@ -25,70 +25,16 @@ C_ij = a_i.b_j, tA_i = a_i.t, tB_j = b_j.t:
        B's edge: centre (x_B - b_j1 (s'_j1 eB_j1)) - b_j2 (s'_j2 eB_j2), s'_k from b_k.n in the same way; u_B = b_j eB_j
        cA, cB: the closest points of the segments P = centre - u, d = u + u by the clamped solve of contact_ref.py's step 1
   then steps 3 - 7 of contact_ref.py with both radii 0 and this n and pen, without the dist > EPS test.
-Pairs with fewer than two boxes run contact_box_ref.Sim._contact itself.
+Pairs with fewer than two boxes run contact_ref.Sim._box_contact and Sim._contact themselves.
 """
 import numpy as np
 
-import contact_box_ref
-import physics_ref
-from contact_box_ref import MAX_CANDIDATES  # noqa: F401
-from physics_ref import EPS, cross, dot, qconj, qrot
+import contact_ref
+from physics_ref import cross, dot, qconj, qrot
 
 SLIDE = 0.05            # 1c: the width, in N.y_k, over which Y's point slides from a vertex to an edge midpoint or the face centre
 EDGE_BIAS = 0.95        # 1b: an edge axis must beat the best face axis by this factor
 PARALLEL = 1e-6         # 1a: an edge pair with 1 - C_ij^2 at or below this is skipped
-
-
-def contact_lists(t, box_pairs=True):
-    """contact_box_ref.contact_lists(t, boxes=True) with `n_box_box`. box_pairs=True: the rule of contact_ref.contact_lists with boxes
-    taking part and pairs of two boxes not removed — follow lists and colouring over the larger pair set, `box_pairs` 0."""
-    L = contact_box_ref.contact_lists(t, boxes=True)
-    if not box_pairs:
-        return dict(L, n_box_box=0)
-    nb = t["n_bodies"]
-    dyn = physics_ref.is_dynamic(t)
-    mask = np.asarray(t["mask"]).astype(np.int64)
-    group = np.asarray(t["group"]).astype(np.int64)
-    takes = L["takes"]
-    takes_box = takes & L["box"]
-    bit = np.where(group < 16, np.left_shift(1, np.minimum(group, 15)), 0)
-    hit = (bit[:, None] & mask[None, :]) != 0                     # hit[a, b]: a's group is in b's mask
-    cand = takes[:, None] & takes[None, :] & hit & hit.T & (dyn[:, None] | dyn[None, :])
-    cand &= np.triu(np.ones((nb, nb), dtype=bool), 1)
-    n_box_box = int((cand & takes_box[:, None] & takes_box[None, :]).sum())
-    a, b = np.nonzero(cand)                                       # lexicographic (a, b)
-    both = dyn[a] & dyn[b]
-    follow_off = np.zeros(nb + 1, dtype=np.int64)
-    fa, fb = a[~both], b[~both]
-    owner = np.where(dyn[fa], fa, fb)
-    partner = np.where(dyn[fa], fb, fa)
-    o = np.lexsort((partner, owner))
-    owner, partner = owner[o], partner[o]
-    np.add.at(follow_off, owner + 1, 1)
-    follow_off = np.cumsum(follow_off)
-    pa, pb = a[both], b[both]
-    used = [set() for _ in range(nb)]
-    colour = np.zeros(len(pa), dtype=np.int64)
-    for k in range(len(pa)):
-        c = 0
-        ua, ub = used[pa[k]], used[pb[k]]
-        while c in ua or c in ub:
-            c += 1
-        ua.add(c); ub.add(c)
-        colour[k] = c
-    order = np.argsort(colour, kind="stable")
-    ncol = int(colour.max()) + 1 if len(pa) else 0
-    return dict(L, follow_off=follow_off, follow_idx=partner.astype(np.int64), pairs=np.stack([pa[order], pb[order]], axis=1).reshape(-1, 2),
-                colour_off=np.searchsorted(colour[order], np.arange(ncol + 1)).astype(np.int64), n_colours=ncol,
-                n_follow=int(len(partner)), n_pairs=int(len(pa)), box_pairs=0, n_box_box=n_box_box)
-
-
-def refusal(lists):
-    """What rz_physics_contacts refuses with RZ_ERR_UNSUPPORTED, or None: the counts as its message gives them"""
-    if lists["n_follow"] + lists["n_pairs"] > MAX_CANDIDATES:
-        of_boxes = " (%d of them pairs of two boxes)" % lists["n_box_box"] if lists.get("n_box_box") else ""
-        return "%d follow entries and %d dynamic pairs%s" % (lists["n_follow"], lists["n_pairs"], of_boxes)
-    return None
 
 
 def axes_of(q):
@@ -138,27 +84,6 @@ def choose(face, edge, considered):
     oe = edge[np.arange(len(edge)), ke]
     wins = considered.any(axis=1) & (oe < face.dtype.type(EDGE_BIAS) * of)
     return ~sep, kf, ke, wins, np.where(wins, oe, of)
-
-
-def closest_on_segments(p1, d1, p2, d2):
-    """the clamped solve of contact_ref.Sim._contact's step 1: the closest points of rows of segments p1 + s d1 and p2 + t d2"""
-    dt = p1.dtype.type
-    eps, one, zero = dt(EPS), dt(1), dt(0)
-    clamp01 = lambda v: np.minimum(np.maximum(v, zero), one)
-    r = p1 - p2
-    A, E, F, C, Bq = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
-    dega, dege = A <= eps, E <= eps
-    sa_, se_ = np.where(dega, one, A), np.where(dege, one, E)
-    den = A * E - Bq * Bq
-    s_gen = np.where(den > eps, clamp01((Bq * F - C * E) / np.where(den > eps, den, one)), zero)
-    t_gen = (Bq * s_gen + F) / se_
-    s_lo = clamp01(-C / sa_)
-    s_hi = clamp01((Bq - C) / sa_)
-    s_g = np.where(t_gen < zero, s_lo, np.where(t_gen > one, s_hi, s_gen))
-    t_g = np.where(t_gen < zero, zero, np.where(t_gen > one, one, t_gen))
-    s = np.where(dega, zero, np.where(dege, s_lo, s_g))
-    t = np.where(dega, np.where(dege, zero, clamp01(F / se_)), np.where(dege, zero, t_g))
-    return p1 + d1 * s[:, None], p2 + d2 * t[:, None]
 
 
 def front_end(xA, qA, eA, xB, qB, eB):
@@ -211,52 +136,7 @@ def front_end(xA, qA, eA, xB, qB, eB):
         ctr_a = ctr_a + ak * (sa * eA[rows, ka])[:, None]
         ctr_b = ctr_b - bk * (sb * eB[rows, kb])[:, None]
     ua, ub = ai * eA[rows, ie][:, None], bj * eB[rows, je][:, None]
-    cA_e, cB_e = closest_on_segments(ctr_a - ua, ua + ua, ctr_b - ub, ub + ub)
+    cA_e, cB_e = contact_ref.closest_on_segments(ctr_a - ua, ua + ua, ctr_b - ub, ub + ub)
     w3 = wins[:, None]
     return dict(ok=ok, cA=np.where(w3, cA_e, cA_f), cB=np.where(w3, cB_e, cB_f), n=np.where(w3, n_e, n_f), pen=pen, edge=wins,
                 axis=np.where(wins, ke, kf), moved=np.where(wins, 0, moved.sum(axis=1)), considered=considered, face=face, edges=edge)
-
-
-class Sim(contact_box_ref.Sim):
-    """contact_box_ref.Sim with boxes taking part; box_pairs=True: pairs of two boxes are candidates too (rz_physics_contacts(ctx, 3)).
-    `kinds` counts the active box - box contacts by ("A" | "B" | "edge", axis | (i, j), coordinates of p' that the clamp of 1c moved —
-    0 for an edge); `n_boxbox` is their number, `n_skipped` that of those among them with an edge axis not considered (1a); `apart` counts
-    the pairs found separated by the axes (0 .. 5 the faces, 6 .. 14 the edges) whose overlap was not positive."""
-
-    def __init__(self, table, parents, bind, dtype=np.float64, contacts=True, box_pairs=True):
-        super().__init__(table, parents, bind, dtype=dtype, contacts=contacts, boxes=True)
-        self.box_pairs = box_pairs
-        self.kinds, self.apart = {}, {}
-        self.n_boxbox = self.n_skipped = 0
-        self.lists = L = contact_lists(table, box_pairs=box_pairs)
-        n = np.diff(L["follow_off"])
-        self.ranks = []
-        for k in range(int(n.max()) if len(n) else 0):
-            me = np.nonzero(n > k)[0]
-            other = L["follow_idx"][L["follow_off"][me] + k]
-            self.ranks.append((np.minimum(me, other), np.maximum(me, other)))
-
-    def _contact(self, a, b, xp, qp):
-        a, b = np.asarray(a), np.asarray(b)
-        two = self.cbox[a] & self.cbox[b]
-        n = 0
-        if (~two).any():
-            n += super()._contact(a[~two], b[~two], xp, qp)
-        if two.any():
-            n += self._boxbox_contact(a[two], b[two], xp, qp)
-        return n
-
-    def _boxbox_contact(self, a, b, xp, qp):
-        f = front_end(self.x[a], self.q[a], self.cext[a], self.x[b], self.q[b], self.cext[b])
-        # 3 - 7
-        ok = self._resolve(a, b, f["cA"], f["cB"], f["n"], f["pen"], f["ok"], xp, qp)
-        for k in np.nonzero(ok)[0]:
-            ax = int(f["axis"][k])
-            key = ("edge", (ax // 3, ax % 3), 0) if f["edge"][k] else ("AB"[ax // 3], ax % 3, int(f["moved"][k]))
-            self.kinds[key] = self.kinds.get(key, 0) + 1
-        for k in np.nonzero(~f["ok"])[0]:
-            key = tuple(np.nonzero(np.concatenate([f["face"][k] <= 0, f["considered"][k] & (f["edges"][k] <= 0)]))[0].tolist())
-            self.apart[key] = self.apart.get(key, 0) + 1
-        self.n_boxbox += int(ok.sum())
-        self.n_skipped += int((ok & ~f["considered"].all(axis=1)).sum())
-        return int(ok.sum())

@@ -5,7 +5,7 @@ on the CPU (test_contact_boxbox_cpu.py: test_cases_are_well_conditioned_and_touc
 import numpy as np
 
 import contact_box_scenes as bs
-import contact_boxbox_ref
+import contact_scenes as cs
 from contact_box_scenes import BOX, FORMS, FREE, PARAMS, SHORT, Builder, pose, run_reference, turn_to_x, write_pmx  # noqa: F401
 from contact_scenes import G_COLLIDER
 from physics_scenes import _quat
@@ -106,56 +106,11 @@ KINDS = {
     "near parallel": lambda k: k[0] in "AB",
 }
 CROWD = "own 64"
-_memo = {}
+_cases = cs.Cases(_CASES, 3)
+case, reference, conditioning, node_conditioning, sim_of = _cases.case, _cases.reference, _cases.conditioning, _cases.node_conditioning, _cases.sim_of
+node_case = bs.node_case                    # (the same scene under either Cases: 'own 64' of the same builder)
 
 
-def case(name):
-    """(scene, poses, calls)"""
-    if name not in _memo:
-        make, amount, calls = _CASES[name][:3]
-        sc = make()
-        _memo[name] = (sc, [pose(sc, k, amount, *_CASES[name][3:]) for k in range(len(calls))], calls)
-    return _memo[name]
-
-
-def sim_of(sc, dtype=np.float64, box_pairs=True):
-    return contact_boxbox_ref.Sim(sc["table"], sc["parents"], sc["bind"], dtype=dtype, box_pairs=box_pairs)
-
-
-def reference(name, dtype=np.float64):
-    """the case's run_reference with pairs of two boxes taking part (memoised): per call (world [B,16], state [nb,13]); also the Sim"""
-    key = (name, np.dtype(dtype).name)
-    if key not in _memo:
-        sc, poses, calls = case(name)
-        sim = sim_of(sc, dtype)
-        _memo[key] = (run_reference(sc, poses, calls, dtype=dtype, sim=sim), sim)
-    return _memo[key]
-
-
-def mode2(name):
-    """the case under the definition of mode 2 (box pairs left out), memoised: per call (world, state)"""
-    key = (name, "mode 2")
-    if key not in _memo:
-        sc, poses, calls = case(name)
-        _memo[key] = run_reference(sc, poses, calls, sim=sim_of(sc, box_pairs=False))
-    return _memo[key]
-
-
-def conditioning(name):
-    """(largest float32-probe deviation from the float64 run in units of extent, the fraction of substeps with an active contact, the
-    probe's largest quaternion deviation up to sign)"""
-    sc, _, _ = case(name)
-    a, sim = reference(name)
-    b, _ = reference(name, dtype=np.float32)
-    worst = turn = 0.0
-    for (wa, sa), (wb, sb) in zip(a, b):
-        worst = max(worst, float(np.abs(wa - wb).max()), float(np.abs(sa[:, :3] - sb[:, :3]).max()))
-        turn = max(turn, float(np.minimum(np.abs(sa[:, 3:7] - sb[:, 3:7]).max(axis=1), np.abs(sa[:, 3:7] + sb[:, 3:7]).max(axis=1)).max()))
-    act = np.array(sim.active)
-    return worst / sc["extent"], float((act > 0).mean()), turn
-
-
-def node_case():
-    """The Node end-to-end test's scene: the 'own 64' chains as a PMX file, run with the table its loader derives from the file, under one
-    fixed local pose of the carrier. Returns (scene, pmx bytes, q [B,4])."""
-    return bs.node_case()
+def limit_table(n_follow):
+    """256 dynamic boxes x n_follow following boxes, all in each other's masks: 256 n_follow follow entries, every one a pair of two boxes"""
+    return cs.limit_table(n_follow, dyn_shape=1, fol_shape=1)

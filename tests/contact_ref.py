@@ -1,5 +1,8 @@
 """Contacts between PMX rigid bodies restated in NumPy: the definition the device stage (kernels/physics.hip with CONTACT, rz_physics_contacts)
-is held to. A subclass of physics_ref.Sim; include/reze_deform.h states the same stage in words.
+is held to. A subclass of physics_ref.Sim; include/reze_deform.h states the same stage in words. The mode is rz_physics_contacts': 0 off,
+1 what this file states, 2 with boxes against round shapes (contact_box_ref.py states what changes), 3 with pairs of two boxes as well
+(contact_boxbox_ref.py). One Sim for all of them: per batch of pairs, by the pairs' shapes, one of three front ends finds the contact
+(steps 1 and 2) and the one _resolve applies it (steps 3 - 7).
 
 Shapes    a sphere is the point x with radius size.x; a capsule the segment x +- q (0, size.y / 2, 0) with radius size.x (the axis is Y, as
           the inertia assumes). Boxes take no part (counted in `boxes`).
@@ -33,23 +36,26 @@ No restitution and no velocity pass: a penetration removed in one substep arrive
 """
 import numpy as np
 
+import contact_box_ref
+import contact_boxbox_ref
 import physics_ref
 from physics_ref import EPS, cross, dot, qconj, qrot, rot_apply
 
 MAX_CANDIDATES = 65536
 
 
-def contact_lists(t, boxes=False):
-    """What enabling contacts derives from a table: per-body shape records, the follow CSR, the coloured dynamic pairs. boxes=True
-    (contact_box_ref.py): boxes take part, and the keys `box` (the record's box bit), `ext` (half extents, zeros for non-boxes) and
-    `box_pairs` (candidate pairs of two boxes, left out) come with the rest."""
+def contact_lists(t, mode=1):
+    """What enabling contacts in `mode` (1, 2 or 3) derives from a table: per-body shape records, the follow CSR, the coloured dynamic
+    pairs. From mode 2 boxes take part: `box` is the record's box bit, `ext` the half extents (zeros for non-boxes). A candidate pair of two
+    boxes is left out and counted in `box_pairs` under mode 2, kept and counted in `n_box_box` under mode 3; all four are zeros where the
+    mode has none."""
     nb = t["n_bodies"]
     dyn = physics_ref.is_dynamic(t)
     shape = np.asarray(t["shape"]).astype(np.int64)
     size = np.asarray(t["size"], dtype=np.float32).reshape(nb, 3)
     mask = np.asarray(t["mask"]).astype(np.int64)
     group = np.asarray(t["group"]).astype(np.int64)
-    box = (shape == 1) & boxes
+    box = (shape == 1) & (mode >= 2)
     radius = np.where(box, np.float32(0), size[:, 0]).astype(np.float32)
     half = np.where(shape == 2, size[:, 1].astype(np.float64) * 0.5, 0.0).astype(np.float32)
     takes_box = box & (size > 0).all(axis=1) & (mask != 0)
@@ -59,8 +65,9 @@ def contact_lists(t, boxes=False):
     cand = takes[:, None] & takes[None, :] & hit & hit.T & (dyn[:, None] | dyn[None, :])
     cand &= np.triu(np.ones((nb, nb), dtype=bool), 1)
     two = takes_box[:, None] & takes_box[None, :]
-    box_pairs = int((cand & two).sum())
-    cand &= ~two
+    n_two = int((cand & two).sum())
+    if mode < 3:
+        cand &= ~two
     a, b = np.nonzero(cand)                                       # lexicographic (a, b)
     both = dyn[a] & dyn[b]
     follow_off = np.zeros(nb + 1, dtype=np.int64)
@@ -83,32 +90,69 @@ def contact_lists(t, boxes=False):
         colour[k] = c
     order = np.argsort(colour, kind="stable")
     ncol = int(colour.max()) + 1 if len(pa) else 0
-    L = dict(radius=radius, half=half, friction=np.asarray(t["friction"], dtype=np.float32).reshape(nb), takes=takes,
-             follow_off=follow_off, follow_idx=partner.astype(np.int64), pairs=np.stack([pa[order], pb[order]], axis=1).reshape(-1, 2),
-             colour_off=np.searchsorted(colour[order], np.arange(ncol + 1)).astype(np.int64), n_colours=ncol,
-             n_follow=int(len(partner)), n_pairs=int(len(pa)), boxes=int(((shape == 1) & (mask != 0) & ~takes_box).sum()))
-    if boxes:
-        L.update(box=box, ext=np.where(box[:, None], size, np.float32(0)).astype(np.float32), box_pairs=box_pairs)
-    return L
+    return {"radius": radius, "half": half, "friction": np.asarray(t["friction"], dtype=np.float32).reshape(nb), "takes": takes,
+            "follow_off": follow_off, "follow_idx": partner.astype(np.int64), "pairs": np.stack([pa[order], pb[order]], axis=1).reshape(-1, 2),
+            "colour_off": np.searchsorted(colour[order], np.arange(ncol + 1)).astype(np.int64), "n_colours": ncol,
+            "n_follow": int(len(partner)), "n_pairs": int(len(pa)), "boxes": int(((shape == 1) & (mask != 0) & ~takes_box).sum()),
+            "box": box, "ext": np.where(box[:, None], size, np.float32(0)).astype(np.float32),
+            "box_pairs": n_two if mode == 2 else 0, "n_box_box": n_two if mode == 3 else 0}
 
 
 def refusal(lists):
-    """What rz_physics_contacts refuses with RZ_ERR_UNSUPPORTED, or None"""
+    """What rz_physics_contacts refuses with RZ_ERR_UNSUPPORTED, or None: the counts as its message gives them"""
     if lists["n_follow"] + lists["n_pairs"] > MAX_CANDIDATES:
-        return "%d follow entries and %d dynamic pairs" % (lists["n_follow"], lists["n_pairs"])
+        of_boxes = " (%d of them pairs of two boxes)" % lists["n_box_box"] if lists["n_box_box"] else ""
+        return "%d follow entries and %d dynamic pairs%s" % (lists["n_follow"], lists["n_pairs"], of_boxes)
     return None
 
 
-class Sim(physics_ref.Sim):
-    """physics_ref.Sim with the contact stage. contacts=False steps exactly as physics_ref.Sim does. `active` gets, per substep, the number
-    of contact solves that passed steps 2 and 4."""
+def closest_on_segments(p1, d1, p2, d2):
+    """Step 1 on its own: the closest points of rows of segments p1 + s d1 and p2 + t d2, s and t in [0, 1]"""
+    dt = p1.dtype.type
+    eps, one, zero = dt(EPS), dt(1), dt(0)
+    clamp01 = lambda v: np.minimum(np.maximum(v, zero), one)
+    r = p1 - p2
+    A, E, F, C, Bq = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
+    dega, dege = A <= eps, E <= eps
+    sa_, se_ = np.where(dega, one, A), np.where(dege, one, E)
+    den = A * E - Bq * Bq
+    s_gen = np.where(den > eps, clamp01((Bq * F - C * E) / np.where(den > eps, den, one)), zero)
+    t_gen = (Bq * s_gen + F) / se_
+    s_lo = clamp01(-C / sa_)
+    s_hi = clamp01((Bq - C) / sa_)
+    s_g = np.where(t_gen < zero, s_lo, np.where(t_gen > one, s_hi, s_gen))
+    t_g = np.where(t_gen < zero, zero, np.where(t_gen > one, one, t_gen))
+    s = np.where(dega, zero, np.where(dege, s_lo, s_g))
+    t = np.where(dega, np.where(dege, zero, clamp01(F / se_)), np.where(dege, zero, t_g))
+    return p1 + d1 * s[:, None], p2 + d2 * t[:, None]
 
-    def __init__(self, table, parents, bind, dtype=np.float64, contacts=True, boxes=False):
+
+def segment_of(x, q, hl):
+    """a round shape's segment P + s d, s in [0, 1] (a sphere: d = 0): (P, d)"""
+    u = np.zeros((len(hl), 3), dtype=x.dtype)
+    u[:, 1] = hl
+    u = qrot(q, u)
+    return x - u, u + u
+
+
+class Sim(physics_ref.Sim):
+    """physics_ref.Sim with the contact stage in `mode`; mode=0 steps exactly as physics_ref.Sim does. `active` gets, per substep, the number
+    of contact solves that passed steps 2 and 4.
+    `regions` counts the active contacts of a box and a round shape by (coordinates of the closest point that the clamp moved — 0 in the
+    deep case —, whether s lies strictly inside (0, 1)).
+    `kinds` counts the active box - box contacts by ("A" | "B" | "edge", axis | (i, j), coordinates of p' that the clamp of 1c moved —
+    0 for an edge); `n_boxbox` is their number, `n_skipped` that of those among them with an edge axis not considered (1a); `apart` counts
+    the pairs found separated by the axes (0 .. 5 the faces, 6 .. 14 the edges) whose overlap was not positive."""
+
+    def __init__(self, table, parents, bind, dtype=np.float64, mode=1):
         super().__init__(table, parents, bind, dtype=dtype)
-        self.contacts = contacts
-        self.lists = L = contact_lists(table, boxes=boxes)
+        self.mode = mode
+        self.lists = L = contact_lists(table, mode or 1)
         self.cr, self.chl, self.cmu = L["radius"].astype(self.dt), L["half"].astype(self.dt), L["friction"].astype(self.dt)
+        self.cbox, self.cext = L["box"] & L["takes"], L["ext"].astype(self.dt)
         self.active = []
+        self.regions, self.kinds, self.apart = {}, {}, {}
+        self.n_boxbox = self.n_skipped = 0
         # pass F by partner rank: rank k = the k-th partner of every dynamic body that has one
         n = np.diff(L["follow_off"])
         self.ranks = []
@@ -117,37 +161,19 @@ class Sim(physics_ref.Sim):
             other = L["follow_idx"][L["follow_off"][me] + k]
             self.ranks.append((np.minimum(me, other), np.maximum(me, other)))
 
-    def _clamp01(self, v):
-        dt = self.dt.type
-        return np.minimum(np.maximum(v, dt(0)), dt(1))
+    def _contacts(self, a, b, xp, qp):
+        """the pairs (a, b) of one rank or colour, each through the front end of its shapes; returns the number of active contacts"""
+        a, b = np.asarray(a), np.asarray(b)
+        n_box = self.cbox[a].astype(int) + self.cbox[b]
+        return sum(front(a[n_box == k], b[n_box == k], xp, qp)
+                   for k, front in enumerate((self._contact, self._box_contact, self._boxbox_contact)) if (n_box == k).any())
 
     def _contact(self, a, b, xp, qp):
+        """two segments: steps 1 and 2 above"""
         dt = self.dt.type
         eps, one, zero = dt(EPS), dt(1), dt(0)
-        xa, qa, xb, qb = self.x[a], self.q[a], self.x[b], self.q[b]
-
-        def axis(q, hl):
-            u = np.zeros((len(hl), 3), dtype=self.dt)
-            u[:, 1] = hl
-            return qrot(q, u)
         # 1. closest points
-        ua, ub = axis(qa, self.chl[a]), axis(qb, self.chl[b])
-        p1, p2 = xa - ua, xb - ub
-        d1, d2 = ua + ua, ub + ub
-        r = p1 - p2
-        A, E, F, C, Bq = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
-        dega, dege = A <= eps, E <= eps
-        sa_, se_ = np.where(dega, one, A), np.where(dege, one, E)
-        den = A * E - Bq * Bq
-        s_gen = np.where(den > eps, self._clamp01((Bq * F - C * E) / np.where(den > eps, den, one)), zero)
-        t_gen = (Bq * s_gen + F) / se_
-        s_lo = self._clamp01(-C / sa_)
-        s_hi = self._clamp01((Bq - C) / sa_)
-        s_g = np.where(t_gen < zero, s_lo, np.where(t_gen > one, s_hi, s_gen))
-        t_g = np.where(t_gen < zero, zero, np.where(t_gen > one, one, t_gen))
-        s = np.where(dega, zero, np.where(dege, s_lo, s_g))
-        t = np.where(dega, np.where(dege, zero, self._clamp01(F / se_)), np.where(dege, zero, t_g))
-        cA, cB = p1 + d1 * s[:, None], p2 + d2 * t[:, None]
+        cA, cB = closest_on_segments(*segment_of(self.x[a], self.q[a], self.chl[a]), *segment_of(self.x[b], self.q[b], self.chl[b]))
         # 2, and n of 3
         d = cB - cA
         dist = np.sqrt(dot(d, d))
@@ -155,6 +181,32 @@ class Sim(physics_ref.Sim):
         ok = (pen > zero) & (dist > eps)
         n = d / np.where(ok, dist, one)[:, None]
         return int(self._resolve(a, b, cA, cB, n, pen, ok, xp, qp).sum())
+
+    def _box_contact(self, a, b, xp, qp):
+        """a box and a round shape: contact_box_ref.front_end"""
+        ax = self.cbox[a]
+        X, R = np.where(ax, a, b), np.where(ax, b, a)
+        f = contact_box_ref.front_end(ax, self.x[X], self.q[X], self.cext[X], *segment_of(self.x[R], self.q[R], self.chl[R]), self.cr[R])
+        ok = self._resolve(a, b, f["cA"], f["cB"], f["n"], f["pen"], f["ok"], xp, qp)
+        for k in np.nonzero(ok)[0]:
+            key = (int(f["moved"][k]), bool(f["inside"][k]))
+            self.regions[key] = self.regions.get(key, 0) + 1
+        return int(ok.sum())
+
+    def _boxbox_contact(self, a, b, xp, qp):
+        """two boxes: contact_boxbox_ref.front_end"""
+        f = contact_boxbox_ref.front_end(self.x[a], self.q[a], self.cext[a], self.x[b], self.q[b], self.cext[b])
+        ok = self._resolve(a, b, f["cA"], f["cB"], f["n"], f["pen"], f["ok"], xp, qp)
+        for k in np.nonzero(ok)[0]:
+            ax = int(f["axis"][k])
+            key = ("edge", (ax // 3, ax % 3), 0) if f["edge"][k] else ("AB"[ax // 3], ax % 3, int(f["moved"][k]))
+            self.kinds[key] = self.kinds.get(key, 0) + 1
+        for k in np.nonzero(~f["ok"])[0]:
+            key = tuple(np.nonzero(np.concatenate([f["face"][k] <= 0, f["considered"][k] & (f["edges"][k] <= 0)]))[0].tolist())
+            self.apart[key] = self.apart.get(key, 0) + 1
+        self.n_boxbox += int(ok.sum())
+        self.n_skipped += int((ok & ~f["considered"].all(axis=1)).sum())
+        return int(ok.sum())
 
     def _resolve(self, a, b, cA, cB, n, pen, ok, xp, qp):
         """Steps 3 - 7 for the pairs (a, b) whose front end found the points cA and cB, the normal n from A to B and the penetration pen;
@@ -203,7 +255,7 @@ class Sim(physics_ref.Sim):
         return ok
 
     def substep(self):
-        if not self.contacts:
+        if not self.mode:
             return super().substep()
         c, dt = self.c, self.dt.type
         L = self.lists
@@ -225,10 +277,10 @@ class Sim(physics_ref.Sim):
             if res is not None:
                 self.residuals[-1].append(max(res) if res else 0.0)
             for a, b in self.ranks:                                                 # pass F
-                active += self._contact(a, b, xp, qp)
+                active += self._contacts(a, b, xp, qp)
             for k in range(L["n_colours"]):                                         # pass D
                 P = L["pairs"][L["colour_off"][k]:L["colour_off"][k + 1]]
-                active += self._contact(P[:, 0], P[:, 1], xp, qp)
+                active += self._contacts(P[:, 0], P[:, 1], xp, qp)
         self.active.append(active)
         self.v = np.where(d, (self.x - xp) / h, self.v)
         dq = physics_ref.qmul(self.q, qconj(qp))

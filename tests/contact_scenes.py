@@ -2,6 +2,9 @@
 hanging from one following body on a carrier bone the poses move, around following collider bodies on a bone the poses leave alone, so
 contacts arise from motion. Every case the GPU tests run is listed in CASES and checked for conditioning and for contact activity on the
 CPU (test_contact_cpu.py: test_cases_are_well_conditioned_and_touch)."""
+import os
+import subprocess
+
 import numpy as np
 
 import contact_ref
@@ -254,46 +257,116 @@ _CASES = {
 # name: (lanes per workgroup, joints in registers?) — the form the launch must take
 FORMS = {"own 64": (64, 1), "stride 64": (64, 0), "own 256": (256, 1), "stride 256": (256, 0)}
 CROWD = "own 64"
-_memo = {}
 
 
-def case(name):
-    """(scene, poses, calls)"""
-    if name not in _memo:
-        make, amount, calls = _CASES[name]
-        sc = make()
-        _memo[name] = (sc, [pose(sc, k, amount) for k in range(len(calls))], calls)
-    return _memo[name]
+def limit_table(n_follow, dyn_shape=0, fol_shape=0):
+    """256 dynamic x n_follow following bodies (spheres, or boxes where the shape is 1), all in each other's masks: 256 n_follow follow
+    entries (65 536 with 256, the limit) under the modes that pair the two shapes"""
+    size = lambda shape: [0.1, 0.1, 0.1] if shape == 1 else [0.1, 0, 0]
+    dyn = dict(bone=-1, type=1, mass=1.0, shape=dyn_shape, size=size(dyn_shape), group=1, mask=1 << 2)
+    fol = dict(bone=1, type=0, mass=0.0, shape=fol_shape, size=size(fol_shape), group=2, mask=1 << 1)
+    return physics_ref.make_table([dict(dyn, offset_pos=[3.0 * k, 0, 0]) for k in range(256)] + [dict(fol, offset_pos=[3.0 * k, 50.0, 0]) for k in range(n_follow)], [])
 
 
-def reference(name, dtype=np.float64, contacts=True):
-    """the case's run_reference with contacts on (memoised in float64): per call (world [B,16], state [nb,13]); also the Sim"""
-    key = (name, np.dtype(dtype).name, contacts)
-    if key not in _memo:
-        sc, poses, calls = case(name)
-        sim = contact_ref.Sim(sc["table"], sc["parents"], sc["bind"], dtype=dtype, contacts=contacts)
-        _memo[key] = (run_reference(sc, poses, calls, dtype=dtype, sim=sim), sim)
-    return _memo[key]
+# ---- the host half's stand-alone program (tests/contact_table_main.cpp around reze-engine_amd/csrc/contact_table.h) ----
+
+def build_table_tool(folder):
+    """the table program under ASan and UBSan"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(folder / "contact_table_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(root, "tests", "contact_table_main.cpp")])
+    return exe
 
 
-def conditioning(name):
-    """(largest float32-probe deviation from the float64 run in units of extent, the fraction of substeps with an active contact)"""
-    sc, _, _ = case(name)
-    a, sim = reference(name)
-    b, _ = reference(name, dtype=np.float32)
-    worst = 0.0
-    for (wa, sa), (wb, sb) in zip(a, b):
-        worst = max(worst, float(np.abs(wa - wb).max()), float(np.abs(sa[:, :3] - sb[:, :3]).max()))
-    act = np.array(sim.active)
-    return worst / sc["extent"], float((act > 0).mean())
+def run_table_tool(tool, t, mode=1):
+    """the program's lines for table t under the mode, as {first word: the rest, split}, and its whole output"""
+    rows = ["%d" % t["n_bodies"]]
+    for b in range(t["n_bodies"]):
+        rows.append("%d %d %d %d %r %r %r %r %r" % (t["type"][b], t["shape"][b], t["group"][b], t["mask"][b], float(t["size"][b][0]), float(t["size"][b][1]), float(t["size"][b][2]),
+                                                    float(t["mass"][b]), float(t["friction"][b])))
+    out = subprocess.run([tool, "%d" % mode], input="\n".join(rows) + "\n", capture_output=True, text=True, check=True).stdout
+    return {ln.split(" ", 1)[0]: ln.split(" ", 1)[1].split() if " " in ln else [] for ln in out.strip().split("\n")}, out
 
 
-def node_case():
-    """The Node end-to-end test's scene: the 'own 64' chains as a PMX file, run with the table its loader derives from the file, under one
-    fixed local pose of the carrier. Returns (scene, pmx bytes, q [B,4])."""
-    if "node" not in _memo:
-        sc, _, _ = case("own 64")
-        data, want = write_pmx(sc)
-        q, _ = pose(sc, 3, turn=0.5)
-        _memo["node"] = (dict(sc, table=want), data, q)
-    return _memo["node"]
+def assert_host_lists(rows, L):
+    """the program's lines against the definition's lists of the same mode, entry for entry: counts, shape records with the box bit, c_box,
+    the follow CSR, the dynamic pairs in solve order and the colour offsets"""
+    assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and rows["refused"][0] == "0"
+    assert int(rows["box_pairs"][0]) == L["box_pairs"] and int(rows["box_box"][0]) == L["n_box_box"]
+    shape = np.array([float(v) for v in rows["shape"]], dtype=np.float32).reshape(-1, 4)          # (%.9g round-trips a float32)
+    assert np.array_equal(shape[:, 0], L["radius"]) and np.array_equal(shape[:, 1], L["half"]) and np.array_equal(shape[:, 2], L["friction"])
+    assert np.array_equal(shape[:, 3], L["takes"].astype(int) + 4 * L["box"].astype(int))
+    box = np.array([float(v) for v in rows["box"]], dtype=np.float32).reshape(-1, 4)
+    if len(box):
+        assert np.array_equal(box[:, :3], L["ext"]) and not box[:, 3].any()
+    else:                                                                                         # (mode 1 uploads no c_box)
+        assert not L["box"].any() and not L["ext"].any()
+    assert [int(v) for v in rows["follow_off"]] == list(L["follow_off"]) and [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"])
+    assert [int(v) for v in rows["pair"]] == list(L["pairs"].reshape(-1)) and [int(v) for v in rows["colour_off"]] == list(L["colour_off"])
+
+
+class Cases:
+    """What the tests ask of a table of cases — name: (scene, pose amount, calls[, how far the carrier turns: pose's `turn`, 0.05 unless
+    given]) — under the contact mode they are there for. Scenes and float64 references are built once."""
+
+    def __init__(self, cases, mode):
+        self.cases, self.mode, self.memo = cases, mode, {}
+
+    def sim_of(self, sc, dtype=np.float64, mode=None):
+        return contact_ref.Sim(sc["table"], sc["parents"], sc["bind"], dtype=dtype, mode=self.mode if mode is None else mode)
+
+    def case(self, name):
+        """(scene, poses, calls)"""
+        if name not in self.memo:
+            make, amount, calls = self.cases[name][:3]
+            sc = make()
+            self.memo[name] = (sc, [pose(sc, k, amount, *self.cases[name][3:]) for k in range(len(calls))], calls)
+        return self.memo[name]
+
+    def reference(self, name, dtype=np.float64, mode=None):
+        """the case's run_reference under the mode (memoised): per call (world [B,16], state [nb,13]); also the Sim"""
+        key = (name, np.dtype(dtype).name, self.mode if mode is None else mode)
+        if key not in self.memo:
+            sc, poses, calls = self.case(name)
+            sim = self.sim_of(sc, dtype, mode)
+            self.memo[key] = (run_reference(sc, poses, calls, dtype=dtype, sim=sim), sim)
+        return self.memo[key]
+
+    def conditioning(self, name):
+        """(largest float32-probe deviation from the float64 run in units of extent, the fraction of substeps with an active contact, the
+        probe's largest quaternion deviation up to sign)"""
+        sc, _, _ = self.case(name)
+        a, sim = self.reference(name)
+        b, _ = self.reference(name, dtype=np.float32)
+        worst = turn = 0.0
+        for (wa, sa), (wb, sb) in zip(a, b):
+            worst = max(worst, float(np.abs(wa - wb).max()), float(np.abs(sa[:, :3] - sb[:, :3]).max()))
+            turn = max(turn, float(np.minimum(np.abs(sa[:, 3:7] - sb[:, 3:7]).max(axis=1), np.abs(sa[:, 3:7] + sb[:, 3:7]).max(axis=1)).max()))
+        act = np.array(sim.active)
+        return worst / sc["extent"], float((act > 0).mean()), turn
+
+    def node_case(self):
+        """The Node end-to-end test's scene: the 'own 64' chains as a PMX file, run with the table its loader derives from the file, under
+        one fixed local pose of the carrier. Returns (scene, pmx bytes, q [B,4])."""
+        if "node" not in self.memo:
+            sc, _, _ = self.case("own 64")
+            data, want = write_pmx(sc)
+            q, _ = pose(sc, 3, turn=0.5)
+            self.memo["node"] = (dict(sc, table=want), data, q)
+        return self.memo["node"]
+
+    def node_conditioning(self):
+        """the Node case under the engine's substeps: (largest float32-probe deviation from the float64 run in units of extent, the
+        fraction of substeps with an active contact, the float64 Sim)"""
+        sc, _, q = self.node_case()
+        calls = ps.node_substeps()
+        poses = [(q, np.zeros((sc["B"], 3), dtype=np.float32))] * len(calls)
+        sims = [self.sim_of(sc, dt) for dt in (np.float64, np.float32)]
+        a, b = (run_reference(sc, poses, calls, dtype=dt, sim=sim) for dt, sim in zip((np.float64, np.float32), sims))
+        c = max(max(float(np.abs(x[0] - y[0]).max()), float(np.abs(x[1][:, :3] - y[1][:, :3]).max())) for x, y in zip(a, b)) / sc["extent"]
+        return c, float((np.array(sims[0].active) > 0).mean()), sims[0]
+
+
+_cases = Cases(_CASES, 1)
+case, reference, conditioning, node_case, node_conditioning, sim_of = _cases.case, _cases.reference, _cases.conditioning, _cases.node_case, _cases.node_conditioning, _cases.sim_of

@@ -1,8 +1,8 @@
 // A stand-alone program around reze-engine_amd/csrc/contact_table.h (the GPU-free half of rz_physics_contacts): it reads the columns of a
-// table that decide contacts as text and prints the lists the call would upload, for tests/test_contact_cpu.py to compare with
-// tests/contact_ref.py and tests/test_contact_box_cpu.py with tests/contact_box_ref.py. Also the program to build under
-// -fsanitize=address,undefined.
-//   usage:  contact_table_main [boxes: 0 | 1]     (with the argument the same lines, 1: in the boxes mode, then `box_pairs` and `box`)
+// table that decide contacts as text and prints the lists rz_physics_contacts(ctx, mode) would upload, for tests/test_contact_cpu.py,
+// tests/test_contact_box_cpu.py and tests/test_contact_boxbox_cpu.py to compare with tests/contact_ref.py's contact_lists(table, mode).
+// Also the program to build under -fsanitize=address,undefined.
+//   usage:  contact_table_main [mode: 1 | 2 | 3]  (1 without the argument; the same lines under every mode)
 //   input:  nb; then per body: type shape group mask size3 mass friction
 #include "../reze-engine_amd/csrc/contact_table.h"
 
@@ -10,7 +10,8 @@
 
 int main(int argc, char **argv)
 {
-    const bool boxes = argc > 1 && argv[1][0] == '1';
+    const int mode = argc > 1 ? argv[1][0] - '0' : 1;
+    if (argc > 2 || mode < 1 || mode > 3 || (argc > 1 && argv[1][1])) { std::cerr << "usage: contact_table_main [1 | 2 | 3]\n"; return 2; }
     uint32_t nb;
     std::cin >> nb;
     if (!std::cin || nb > (1u << 20)) { std::cerr << "bad count\n"; return 2; }
@@ -30,7 +31,7 @@ int main(int argc, char **argv)
     t.n_bodies = nb; t.type = type.data(); t.shape = shape.data(); t.group = group.data(); t.mask = mask.data(); t.size3 = size.data();
     t.mass = mass.data(); t.friction = friction.data();
     rzphys::Contacts o;
-    rzphys::build_contacts(&t, o, boxes);
+    rzphys::build_contacts(&t, o, mode);
     printf("counts %zu %zu %d %d\n", o.n_follow, o.n_pairs, o.ncol, o.boxes);
     printf("refused %d %s\n", o.too_many ? 1 : 0, o.too_many ? rzphys::contacts_refusal(o).c_str() : "");
     printf("shape");
@@ -47,11 +48,10 @@ int main(int argc, char **argv)
     for (int v : o.pair) printf(" %d", v);
     printf("\ncolour_off");
     for (int v : o.colour_off) printf(" %d", v);
-    if (argc > 1) {
-        printf("\nbox_pairs %zu", o.box_pairs);
-        printf("\nbox");
-        for (float v : o.box) printf(" %.9g", v);
-    }
+    printf("\nbox_pairs %zu", o.box_pairs);
+    printf("\nbox_box %zu", o.n_box_box);
+    printf("\nbox");
+    for (float v : o.box) printf(" %.9g", v);
     printf("\n");
     return 0;
 }

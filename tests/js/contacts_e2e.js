@@ -1,13 +1,14 @@
 'use strict'
-/* End-to-end contacts through the N-API boundary on a PMX whose rigid bodies carry group, mask and friction, under one fixed local pose:
- *   on:   new Engine(null, { deviceFK: true, devicePhysics: true, physicsContacts: true })   rz_physics_contacts behind the table's upload
- *   off:  new Engine(null, { deviceFK: true, devicePhysics: true })                          the same table without contacts
- * usage: node contacts_e2e.js <model.pmx> <localRotations.f32> <outdir> <time ms>...
- * Dumps per engine the deformed positions, world matrices and body state of every frame (pos_ / world_ / state_<tag>.f32). Prints the
- * substeps every frame asked for and the contact tuning keys. */
+/* End-to-end contacts through the N-API boundary on a PMX whose rigid bodies carry group, mask and friction, under one fixed local pose.
+ * One engine per option of the comma-separated list, new Engine(null, { deviceFK: true, devicePhysics: true, physicsContacts: <option> }):
+ *   true:   rz_physics_contacts(ctx, 1) behind the table's upload      boxes:  (ctx, 2)      all:  (ctx, 3)
+ *   off:    no physicsContacts at all: the same table without contacts
+ * usage: node contacts_e2e.js <options> <tuning keys> <model.pmx> <localRotations.f32> <outdir> <time ms>...
+ * Dumps per option the deformed positions, world matrices and body state of every frame (pos_ / world_ / state_<option>.f32). Prints per
+ * option the substeps every frame asked for and the comma-separated tuning keys asked for. */
 const fs = require('fs'), path = require('path')
 const { Engine } = require(path.join(__dirname, '..', '..', 'reze-engine_amd', 'host'))
-const [pmx, rot, out, ...ts] = process.argv.slice(2)
+const [options, keys, pmx, rot, out, ...ts] = process.argv.slice(2)
 const cat = (parts) => {
   const all = new Float32Array(parts.reduce((n, p) => n + p.length, 0))
   let o = 0
@@ -20,8 +21,9 @@ const cat = (parts) => {
   const raw = fs.readFileSync(rot)
   const q = new Float32Array(raw.buffer.slice(raw.byteOffset, raw.byteOffset + raw.byteLength))
   const res = { times }
-  for (const [tag, opts] of [['on', { deviceFK: true, devicePhysics: true, physicsContacts: true }], ['off', { deviceFK: true, devicePhysics: true }]]) {
-    const e = new Engine(null, Object.assign({ realtime: false }, opts))
+  for (const tag of options.split(',')) {
+    const opts = tag === 'off' ? {} : { physicsContacts: tag === 'true' ? true : tag }
+    const e = new Engine(null, Object.assign({ realtime: false, deviceFK: true, devicePhysics: true }, opts))
     await e.init(); await e.loadModel(pmx)
     const substeps = [], step = e.native.physicsStep
     e.native = Object.assign({}, e.native, { physicsStep: (c, n) => { substeps.push(n); step(c, n) } })
@@ -38,8 +40,7 @@ const cat = (parts) => {
     fs.writeFileSync(path.join(out, 'pos_' + tag + '.f32'), cat(pos))
     fs.writeFileSync(path.join(out, 'world_' + tag + '.f32'), cat(world))
     fs.writeFileSync(path.join(out, 'state_' + tag + '.f32'), cat(state))
-    res[tag] = substeps.slice()
-    res[tag + 'Keys'] = ['physics_contacts', 'physics_contact_follow', 'physics_contact_pairs', 'physics_contact_colours', 'physics_contact_boxes'].map((k) => e.native.getTuning(e.ctx, k))
+    res[tag] = { substeps: substeps.slice(), keys: keys.split(',').map((k) => e.native.getTuning(e.ctx, k)) }
     e.dispose()
   }
   console.log(JSON.stringify(res))

@@ -24,7 +24,7 @@ IDENT = np.eye(4).T.reshape(1, 16)
 def one_bone(bodies, joints=(), dtype=np.float64, **kw):
     """a table on one bone at the origin; returns (Sim with boxes taking part, world, table)"""
     t = pr.make_table(list(bodies), list(joints), **kw)
-    return br.Sim(t, [-1], [[0, 0, 0]], dtype=dtype), IDENT.copy(), t
+    return cr.Sim(t, [-1], [[0, 0, 0]], dtype=dtype, mode=2), IDENT.copy(), t
 
 
 def test_a_dropped_sphere_comes_to_rest_on_a_following_box():
@@ -97,13 +97,13 @@ def test_a_centre_inside_the_box_leaves_through_the_nearest_face():
     assert np.allclose(sim.x[1], [0.75, 0, 0], atol=1e-12), sim.x[1]
 
 
-def _lists(bodies, boxes=True):
-    return br.contact_lists(pr.make_table(bodies, []), boxes=boxes)
+def _lists(bodies, mode=2):
+    return cr.contact_lists(pr.make_table(bodies, []), mode)
 
 
 def test_what_is_a_candidate_with_boxes():
     """boxes against round shapes in either order and role; two boxes are counted, not paired; a zero extent or a zero mask keeps a box out;
-    boxes=False is contact_ref's lists"""
+    mode 1 leaves every box out"""
     dyn = dict(type=1, mass=1.0, shape=0, size=[0.3, 0, 0])
     fol = dict(type=0, mass=0.0, shape=0, size=[0.3, 0, 0])
     bx = dict(shape=1, size=[0.3, 0.2, 0.1])
@@ -118,18 +118,19 @@ def test_what_is_a_candidate_with_boxes():
     # a zero extent: the box takes no part and is counted; a zero mask: neither
     L = _lists([dict(dyn), dict(fol, shape=1, size=[0.3, 0.0, 0.1]), dict(fol, mask=0, **bx), dict(dyn, **bx)])
     assert (L["boxes"], L["n_follow"], L["n_pairs"], L["box_pairs"]) == (1, 0, 1, 0) and L["takes"].tolist() == [True, False, False, True]
-    # boxes off: today's lists
+    # mode 1: the boxes are counted and leave no trace in the lists (those of the same table with the boxes' masks 0, but for the count)
     t = pr.make_table([dict(fol, **bx), dict(dyn), dict(dyn, **bx)], [])
-    off, old = br.contact_lists(t, boxes=False), cr.contact_lists(t)
-    assert off["box_pairs"] == 0 and off["boxes"] == old["boxes"] == 2 and all(np.array_equal(off[k], old[k]) for k in old)
+    off, old = cr.contact_lists(t, 1), cr.contact_lists(bs.masked_boxes(dict(table=t))["table"], 1)
+    assert off["box_pairs"] == 0 and off["boxes"] == 2 and old["boxes"] == 0 and not off["box"].any() and not off["ext"].any()
+    assert all(np.array_equal(off[k], old[k]) for k in old if k != "boxes")
 
 
 def test_without_boxes_the_definition_is_contact_ref():
-    """a table without a box: the run with boxes=True is contact_ref.Sim's, bit for bit (pairs without a box go through the inherited code)"""
+    """a table without a box: the run under mode 2 is that under mode 1, bit for bit (pairs without a box go through the segment front end)"""
     sc = bs.no_boxes()
     poses = [bs.pose(sc, k) for k in range(3)]
     a = bs.run_reference(sc, poses, bs.SHORT, sim=bs.sim_of(sc))
-    b = bs.run_reference(sc, poses, bs.SHORT, sim=cr.Sim(sc["table"], sc["parents"], sc["bind"]))
+    b = bs.run_reference(sc, poses, bs.SHORT, sim=bs.sim_of(sc, mode=1))
     for (wa, sa), (wb, sb) in zip(a, b):
         assert np.array_equal(wa, wb) and np.array_equal(sa, sb)
 
@@ -213,49 +214,19 @@ def test_cases_are_well_conditioned_and_touch():
             assert [bool(dyn[b]) for b in pair] == {"fd": [False, True], "df": [True, False], "dd": [True, True]}[order], name
             assert sum(sim.regions.values()) >= 10 and (L["n_pairs"] == 1) == (order == "dd"), name
     # the Node end-to-end case: the PMX's table under one pose, the engine's substeps
-    import physics_scenes as ps
-    sc, _, q = bs.node_case()
-    calls = ps.node_substeps()
-    poses = [(q, np.zeros((sc["B"], 3), dtype=np.float32))] * len(calls)
-    runs = {}
-    for dt in (np.float64, np.float32):
-        sim = bs.sim_of(sc, dt)
-        runs[dt] = (bs.run_reference(sc, poses, calls, dtype=dt, sim=sim), sim)
-    c = max(max(float(np.abs(a[0] - b[0]).max()), float(np.abs(a[1][:, :3] - b[1][:, :3]).max())) for a, b in zip(runs[np.float64][0], runs[np.float32][0])) / sc["extent"]
-    act = float((np.array(runs[np.float64][1].active) > 0).mean())
+    c, act, sim = bs.node_conditioning()
     print("node case: %.1e / %.2f" % (c, act))
-    assert c <= ILL and act >= 0.25 and sum(runs[np.float64][1].regions.values()) > 0
+    assert c <= ILL and act >= 0.25 and sum(sim.regions.values()) > 0
 
 
 # ---- the host half: contact_table.h in its boxes mode against the definition's lists ----
 
-def limit_table(n_follow):
-    """256 dynamic spheres x n_follow following boxes, all in each other's masks: 256 n_follow follow entries against boxes"""
-    dyn = dict(bone=-1, type=1, mass=1.0, shape=0, size=[0.1, 0, 0], group=1, mask=1 << 2)
-    fol = dict(bone=1, type=0, mass=0.0, shape=1, size=[0.1, 0.1, 0.1], group=2, mask=1 << 1)
-    return pr.make_table([dict(dyn, offset_pos=[3.0 * k, 0, 0]) for k in range(256)] + [dict(fol, offset_pos=[3.0 * k, 50.0, 0]) for k in range(n_follow)], [])
-
-
-def dump(t):
-    rows = ["%d" % t["n_bodies"]]
-    for b in range(t["n_bodies"]):
-        rows.append("%d %d %d %d %r %r %r %r %r" % (t["type"][b], t["shape"][b], t["group"][b], t["mask"][b], float(t["size"][b][0]), float(t["size"][b][1]), float(t["size"][b][2]),
-                                                    float(t["mass"][b]), float(t["friction"][b])))
-    return "\n".join(rows) + "\n"
-
-
 @pytest.fixture(scope="module")
 def tool(tmp_path_factory):
-    """the table program under ASan and UBSan: with an argument (0 | 1) it prints the box lines too, without one what it always printed"""
-    exe = str(tmp_path_factory.mktemp("contact_box_table") / "contact_table_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
-                           os.path.join(ROOT, "tests", "contact_table_main.cpp")])
-    return exe
+    return cs.build_table_tool(tmp_path_factory.mktemp("contact_box_table"))
 
 
-def run_tool(tool, t, *args):
-    out = subprocess.run([tool] + list(args), input=dump(t), capture_output=True, text=True, check=True).stdout
-    return {ln.split(" ", 1)[0]: ln.split(" ", 1)[1].split() if " " in ln else [] for ln in out.strip().split("\n")}, out
+run_tool, limit_table = cs.run_table_tool, bs.limit_table
 
 
 def mixed_table():
@@ -270,37 +241,26 @@ def mixed_table():
 @pytest.mark.parametrize("name", ["own 64", "stride 256", "capsule box dd", "box pair", "mixed"])
 def test_host_lists_equal_the_definition(tool, name):
     """shape records with the box bit, c_box, the follow CSR, the dynamic pairs in solve order, colour offsets and all counts, entry for
-    entry, with boxes taking part; without, the program prints what it prints without the argument"""
+    entry, with boxes taking part; and without, under mode 1"""
     t = mixed_table() if name == "mixed" else bs.case(name)[0]["table"]
-    L = br.contact_lists(t, boxes=True)
-    rows, _ = run_tool(tool, t, "1")
-    assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and rows["refused"][0] == "0"
-    assert int(rows["box_pairs"][0]) == L["box_pairs"]
-    shape = np.array([float(v) for v in rows["shape"]], dtype=np.float32).reshape(-1, 4)
-    assert np.array_equal(shape[:, 0], L["radius"]) and np.array_equal(shape[:, 1], L["half"]) and np.array_equal(shape[:, 2], L["friction"])
-    assert np.array_equal(shape[:, 3], L["takes"].astype(int) + 4 * L["box"].astype(int))
-    box = np.array([float(v) for v in rows["box"]], dtype=np.float32).reshape(-1, 4)
-    assert np.array_equal(box[:, :3], L["ext"]) and not box[:, 3].any() and L["box"].any()
-    assert [int(v) for v in rows["follow_off"]] == list(L["follow_off"]) and [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"])
-    assert [int(v) for v in rows["pair"]] == list(L["pairs"].reshape(-1)) and [int(v) for v in rows["colour_off"]] == list(L["colour_off"])
+    L = cr.contact_lists(t, 2)
+    rows, _ = run_tool(tool, t, 2)
+    cs.assert_host_lists(rows, L)
+    assert L["box"].any()
     # boxes off
-    _, off = run_tool(tool, t, "0")
-    _, old = run_tool(tool, t)
-    assert off == old + "box_pairs 0\nbox\n"
-    O = cr.contact_lists(t)
-    rows, _ = run_tool(tool, t, "0")
-    assert [int(v) for v in rows["counts"]] == [O["n_follow"], O["n_pairs"], O["n_colours"], O["boxes"]]
+    rows, _ = run_tool(tool, t, 1)
+    cs.assert_host_lists(rows, cr.contact_lists(t, 1))
 
 
 def test_host_refuses_one_past_the_limit_with_boxes(tool):
     """256 dynamic spheres x 256 following boxes = 65 536 candidates are taken, 256 x 257 are refused with both counts in the message"""
-    rows, _ = run_tool(tool, limit_table(256), "1")
+    rows, _ = run_tool(tool, limit_table(256), 2)
     assert rows["counts"][:2] == ["65536", "0"] and rows["refused"][0] == "0" and len(rows["follow_idx"]) == 65536
-    rows, out = run_tool(tool, limit_table(257), "1")
+    rows, out = run_tool(tool, limit_table(257), 2)
     assert rows["counts"][:2] == ["65792", "0"] and rows["refused"][0] == "1" and rows.get("follow_idx", []) == []
     assert "65792 follow entries and 0 dynamic pairs" in out and "broad phase" in out
-    assert br.refusal(br.contact_lists(limit_table(257), boxes=True)) and not br.refusal(br.contact_lists(limit_table(256), boxes=True))
-    assert br.contact_lists(limit_table(257), boxes=False)["n_follow"] == 0
+    assert cr.refusal(cr.contact_lists(limit_table(257), 2)) and not cr.refusal(cr.contact_lists(limit_table(256), 2))
+    assert cr.contact_lists(limit_table(257), 1)["n_follow"] == 0
 
 
 @pytest.mark.skipif(shutil.which("node") is None, reason="node is not installed")
@@ -309,9 +269,9 @@ def test_engine_boxes_option_with_a_recording_addon(tmp_path):
     loadModel; true passes 1; any other string turns nothing on; 'boxes' without devicePhysics throws"""
     sc, data, _ = bs.node_case()
     (tmp_path / "s.pmx").write_bytes(data)
-    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contact_boxes_engine_mock.js"), str(tmp_path / "s.pmx")], timeout=60).decode().strip().splitlines()[-1])
+    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contacts_engine_mock.js"), str(tmp_path / "s.pmx"), "boxes", "true", "everything"], timeout=60).decode().strip().splitlines()[-1])
     assert r["needsDevicePhysics"] and r["shards"] >= 2 and len(r["boxes"]) == r["shards"]
-    for tag, want in (("boxes", "physicsContacts:2"), ("plain", "physicsContacts:1")):
+    for tag, want in (("boxes", "physicsContacts:2"), ("true", "physicsContacts:1")):
         for calls in r[tag]:
             assert [c for c in calls if c.startswith("physicsContacts")] == [want] and calls.index(want) == calls.index("uploadPhysics") + 1
-    assert all("physicsContacts" not in " ".join(calls) for calls in r["other"]) and all("uploadPhysics" in calls for calls in r["other"])
+    assert all("physicsContacts" not in " ".join(calls) for calls in r["everything"]) and all("uploadPhysics" in calls for calls in r["everything"])

@@ -1,6 +1,6 @@
 """Contacts between two boxes without a GPU: what the definition (tests/contact_boxbox_ref.py) promises, its separating-axis search alone
 against a dense scan, the host half of rz_physics_contacts(ctx, 3) (reze-engine_amd/csrc/contact_table.h, through
-tests/contact_boxbox_table_main.cpp built with -fsanitize=address,undefined) against the definition's lists, the conditioning and contact
+tests/contact_table_main.cpp built with -fsanitize=address,undefined) against the definition's lists, the conditioning and contact
 activity of every case tests/test_gpu_contact_boxbox.py runs, and the Engine option 'all' against a recording addon."""
 import json
 import os
@@ -10,23 +10,16 @@ import subprocess
 import numpy as np
 import pytest
 
-import contact_box_ref as br
 import contact_box_scenes as bs
 import contact_boxbox_ref as xr
 import contact_boxbox_scenes as xs
+import contact_ref as cr
 import contact_scenes as cs
 import physics_ref as pr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ILL = 2.5e-5                            # the conditioning bar of tests/test_contact_cpu.py
 IDENT = np.eye(4).T.reshape(1, 16)
-
-
-def limit_table(n_follow):
-    """256 dynamic boxes x n_follow following boxes, all in each other's masks: 256 n_follow follow entries, every one a pair of two boxes"""
-    dyn = dict(bone=-1, type=1, mass=1.0, shape=1, size=[0.1, 0.1, 0.1], group=1, mask=1 << 2)
-    fol = dict(bone=1, type=0, mass=0.0, shape=1, size=[0.1, 0.1, 0.1], group=2, mask=1 << 1)
-    return pr.make_table([dict(dyn, offset_pos=[3.0 * k, 0, 0]) for k in range(256)] + [dict(fol, offset_pos=[3.0 * k, 50.0, 0]) for k in range(n_follow)], [])
 
 
 def surface(e, n=7):
@@ -73,7 +66,7 @@ def drop_sim(e, rot, base, dtype=np.float64):
     t = pr.make_table([dict(bone=0, type=0, shape=1, size=list(base), mass=0.0, friction=0.5),
                        dict(bone=-1, type=1, shape=1, size=list(e), mass=1.0, offset_pos=[0.1, base[1] + 1.8 * max(e), -0.05], offset_rot=rot,
                             linear_damping=0.5, angular_damping=0.5, friction=0.5)], [])
-    return xr.Sim(t, [-1], [[0, 0, 0]], dtype=dtype), IDENT.copy()
+    return cr.Sim(t, [-1], [[0, 0, 0]], dtype=dtype, mode=3), IDENT.copy()
 
 
 @pytest.mark.parametrize("name", list(DROPS))
@@ -107,7 +100,7 @@ def test_crossed_bars_are_held_by_their_edges():
     top = 0.2 * np.sqrt(2)
     dyn = dict(bone=-1, type=1, shape=1, size=[0.2, 0.2, 2.0], mass=1.0, offset_pos=[0.05, 2 * top + 0.02, 0.03], offset_rot=cs._quat([0, 0, 1], np.pi / 4 + 0.02),
                linear_damping=0.5, angular_damping=0.5, friction=0.5)
-    sim = xr.Sim(pr.make_table([fol, dyn], []), [-1], [[0, 0, 0]])
+    sim = cr.Sim(pr.make_table([fol, dyn], []), [-1], [[0, 0, 0]], mode=3)
     W = IDENT.copy()
     worst, low, first = 0.0, np.inf, None
     for k in range(200):
@@ -129,8 +122,8 @@ def _slide(mu):
     drift off the face, the substeps in contact"""
     tilt = cs._quat([0, 0, 1], -0.5)
     down, normal = pr.qrot(tilt, np.array([1.0, 0.0, 0.0])), pr.qrot(tilt, np.array([0.0, 1.0, 0.0]))
-    sim = xr.Sim(pr.make_table([dict(bone=0, type=0, shape=1, size=[12.0, 0.5, 2.0], mass=0.0, offset_rot=tilt, friction=1.0),
-                                dict(bone=-1, type=1, shape=1, size=[0.6, 0.3, 0.5], mass=1.0, offset_pos=list(normal * 0.8), offset_rot=tilt, friction=mu)], []), [-1], [[0, 0, 0]])
+    sim = cr.Sim(pr.make_table([dict(bone=0, type=0, shape=1, size=[12.0, 0.5, 2.0], mass=0.0, offset_rot=tilt, friction=1.0),
+                                dict(bone=-1, type=1, shape=1, size=[0.6, 0.3, 0.5], mass=1.0, offset_pos=list(normal * 0.8), offset_rot=tilt, friction=mu)], []), [-1], [[0, 0, 0]], mode=3)
     W = IDENT.copy()
     sim.step(W, 0)
     x0 = sim.x[1].copy()
@@ -192,32 +185,34 @@ def test_the_search_alone_against_a_dense_scan():
 
 
 def test_what_is_a_candidate_with_box_pairs():
-    """two boxes pair like any two shapes, in either role; box_pairs=False is contact_box_ref's lists; a table without a pair of two boxes
-    has the same lists either way"""
+    """two boxes pair like any two shapes, in either role; mode 2 counts the same pairs and leaves them out; a table without a pair of two
+    boxes has the same lists either way"""
     dyn = dict(type=1, mass=1.0, shape=0, size=[0.3, 0, 0])
     fol = dict(type=0, mass=0.0, shape=0, size=[0.3, 0, 0])
     bx = dict(shape=1, size=[0.3, 0.2, 0.1])
     t = pr.make_table([dict(fol, **bx), dict(dyn), dict(dyn, **bx), dict(fol, shape=2, size=[0.2, 0.5, 0]), dict(dyn, **bx), dict(fol, **bx)], [])
-    L = xr.contact_lists(t)
+    L = cr.contact_lists(t, 3)
     assert (L["n_follow"], L["n_pairs"], L["box_pairs"], L["n_box_box"], L["boxes"]) == (9, 3, 0, 5, 0)
     assert L["follow_off"].tolist() == [0, 0, 3, 6, 6, 9, 9] and L["follow_idx"].tolist() == [0, 3, 5, 0, 3, 5, 0, 3, 5]
     assert L["pairs"].tolist() == [[1, 2], [1, 4], [2, 4]] and L["colour_off"].tolist() == [0, 1, 2, 3]
-    off, old = xr.contact_lists(t, box_pairs=False), br.contact_lists(t, boxes=True)
-    assert off["n_box_box"] == 0 and off["box_pairs"] == old["box_pairs"] == 5 and all(np.array_equal(off[k], old[k]) for k in old)
+    off = cr.contact_lists(t, 2)
+    assert off["n_box_box"] == 0 and off["box_pairs"] == L["n_box_box"] == 5 and off["n_follow"] + off["n_pairs"] == L["n_follow"] + L["n_pairs"] - 5
+    assert off["follow_idx"].tolist() == [0, 3, 5, 3, 3] and off["pairs"].tolist() == [[1, 2], [1, 4]]
+    assert all(np.array_equal(off[k], L[k]) for k in ("radius", "half", "friction", "takes", "box", "ext", "boxes"))
     # two following boxes are no pair; a zero extent keeps a box out
-    assert xr.contact_lists(pr.make_table([dict(fol, **bx), dict(fol, **bx)], []))["n_box_box"] == 0
-    assert xr.contact_lists(pr.make_table([dict(dyn, **bx), dict(fol, shape=1, size=[0.3, 0.0, 0.1])], []))["n_box_box"] == 0
+    assert cr.contact_lists(pr.make_table([dict(fol, **bx), dict(fol, **bx)], []), 3)["n_box_box"] == 0
+    assert cr.contact_lists(pr.make_table([dict(dyn, **bx), dict(fol, shape=1, size=[0.3, 0.0, 0.1])], []), 3)["n_box_box"] == 0
     t = bs.with_box_pair(apart=True)["table"]
-    a, b = xr.contact_lists(t), xr.contact_lists(t, box_pairs=False)
+    a, b = cr.contact_lists(t, 3), cr.contact_lists(t, 2)
     assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_without_box_pairs_the_definition_is_contact_box_ref():
-    """box_pairs=False on a table with pairs of two boxes, and box_pairs=True on a table without one: the runs are contact_box_ref.Sim's,
-    bit for bit"""
-    for sc, box_pairs in ((bs.case("box pair")[0], False), (bs.with_box_pair(apart=True), True)):
+    """mode 2 on a table with pairs of two boxes, and mode 3 on a table without one: the runs are those of contact_box_scenes' Sim (mode
+    2), bit for bit"""
+    for sc, mode in ((bs.case("box pair")[0], 2), (bs.with_box_pair(apart=True), 3)):
         poses = [bs.pose(sc, k, 0.3) for k in range(3)]
-        a = bs.run_reference(sc, poses, bs.SHORT, sim=xs.sim_of(sc, box_pairs=box_pairs))
+        a = bs.run_reference(sc, poses, bs.SHORT, sim=xs.sim_of(sc, mode=mode))
         b = bs.run_reference(sc, poses, bs.SHORT, sim=bs.sim_of(sc))
         for (wa, sa), (wb, sb) in zip(a, b):
             assert np.array_equal(wa, wb) and np.array_equal(sa, sb)
@@ -232,7 +227,7 @@ def test_cases_are_well_conditioned_and_touch():
     for name in xs._CASES:
         c, act, turn = xs.conditioning(name)
         ref, sim = xs.reference(name)
-        moved = float(np.abs(xs.mode2(name)[-1][1][:, :3] - ref[-1][1][:, :3]).max())
+        moved = float(np.abs(xs.reference(name, mode=2)[0][-1][1][:, :3] - ref[-1][1][:, :3]).max())
         rows.append("%s %.1e / %.2f / %.1e / %d / %.3f" % (name, c, act, turn, sim.n_boxbox, moved))
         if c > ILL or act < 0.25 or turn > ILL or sim.n_boxbox < 10 or moved <= 0.01:
             bad[name] = (c, act, turn, sim.n_boxbox, moved)
@@ -265,49 +260,22 @@ def test_cases_are_well_conditioned_and_touch():
         (key,) = sim.apart
         assert len(key) == 1 and key[0] in axes and sum(a > 0 for a in sim.active) >= 10, (kind, key)
     sc, poses, calls = bs.case("box pair")
-    a, b = bs.run_reference(sc, poses, calls, sim=xs.sim_of(sc)), bs.run_reference(sc, poses, calls, sim=xs.sim_of(sc, box_pairs=False))
+    a, b = bs.run_reference(sc, poses, calls, sim=xs.sim_of(sc)), bs.run_reference(sc, poses, calls, sim=xs.sim_of(sc, mode=2))
     assert np.abs(a[-1][1][:, :3] - b[-1][1][:, :3]).max() > 0.01
     # the Node end-to-end case: the PMX's table under one pose, the engine's substeps
-    import physics_scenes as ps
-    sc, _, q = xs.node_case()
-    calls = ps.node_substeps()
-    poses = [(q, np.zeros((sc["B"], 3), dtype=np.float32))] * len(calls)
-    runs = {}
-    for dt in (np.float64, np.float32):
-        sim = xs.sim_of(sc, dt)
-        runs[dt] = (xs.run_reference(sc, poses, calls, dtype=dt, sim=sim), sim)
-    c = max(max(float(np.abs(a[0] - b[0]).max()), float(np.abs(a[1][:, :3] - b[1][:, :3]).max())) for a, b in zip(runs[np.float64][0], runs[np.float32][0])) / sc["extent"]
-    act = float((np.array(runs[np.float64][1].active) > 0).mean())
-    print("node case: %.1e / %.2f / %d" % (c, act, runs[np.float64][1].n_boxbox))
-    assert c <= ILL and act >= 0.25 and runs[np.float64][1].n_boxbox > 0
+    c, act, sim = xs.node_conditioning()
+    print("node case: %.1e / %.2f / %d" % (c, act, sim.n_boxbox))
+    assert c <= ILL and act >= 0.25 and sim.n_boxbox > 0
 
 
 # ---- the host half: contact_table.h with pairs of two boxes kept against the definition's lists ----
 
-def dump(t):
-    rows = ["%d" % t["n_bodies"]]
-    for b in range(t["n_bodies"]):
-        rows.append("%d %d %d %d %r %r %r %r %r" % (t["type"][b], t["shape"][b], t["group"][b], t["mask"][b], float(t["size"][b][0]), float(t["size"][b][1]), float(t["size"][b][2]),
-                                                    float(t["mass"][b]), float(t["friction"][b])))
-    return "\n".join(rows) + "\n"
-
-
 @pytest.fixture(scope="module")
 def tools(tmp_path_factory):
-    """the two table programs under ASan and UBSan: the new one (mode 2 | 3) and the one the boxes mode is held to (contact_table_main)"""
-    d = tmp_path_factory.mktemp("contact_boxbox_table")
-    out = []
-    for name in ("contact_boxbox_table_main", "contact_table_main"):
-        exe = str(d / name)
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
-                               os.path.join(ROOT, "tests", name + ".cpp")])
-        out.append(exe)
-    return out
+    return cs.build_table_tool(tmp_path_factory.mktemp("contact_boxbox_table"))
 
 
-def run_tool(tool, t, *args):
-    out = subprocess.run([tool] + list(args), input=dump(t), capture_output=True, text=True, check=True).stdout
-    return {ln.split(" ", 1)[0]: ln.split(" ", 1)[1].split() if " " in ln else [] for ln in out.strip().split("\n")}, out
+run_tool, limit_table = cs.run_table_tool, xs.limit_table
 
 
 def mixed_table():
@@ -322,47 +290,41 @@ def mixed_table():
 @pytest.mark.parametrize("name", ["own 64", "stride 256", "box box dd", "box pair", "mixed"])
 def test_host_lists_equal_the_definition(tools, name):
     """shape records with the box bit, c_box, the follow CSR, the dynamic pairs in solve order, colour offsets and all counts, entry for
-    entry, with pairs of two boxes kept; without them the program prints what the boxes mode's program prints, and `box_box 0`"""
-    tool, old_tool = tools
+    entry, with pairs of two boxes kept; and with them left out, under mode 2"""
+    tool = tools
     t = mixed_table() if name == "mixed" else bs.case("box pair")[0]["table"] if name == "box pair" else xs.case(name)[0]["table"]
-    L = xr.contact_lists(t)
-    rows, _ = run_tool(tool, t, "3")
-    assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and rows["refused"][0] == "0"
-    assert int(rows["box_pairs"][0]) == L["box_pairs"] == 0 and int(rows["box_box"][0]) == L["n_box_box"] > 0
-    shape = np.array([float(v) for v in rows["shape"]], dtype=np.float32).reshape(-1, 4)
-    assert np.array_equal(shape[:, 0], L["radius"]) and np.array_equal(shape[:, 1], L["half"]) and np.array_equal(shape[:, 2], L["friction"])
-    assert np.array_equal(shape[:, 3], L["takes"].astype(int) + 4 * L["box"].astype(int))
-    box = np.array([float(v) for v in rows["box"]], dtype=np.float32).reshape(-1, 4)
-    assert np.array_equal(box[:, :3], L["ext"]) and not box[:, 3].any()
-    assert [int(v) for v in rows["follow_off"]] == list(L["follow_off"]) and [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"])
-    assert [int(v) for v in rows["pair"]] == list(L["pairs"].reshape(-1)) and [int(v) for v in rows["colour_off"]] == list(L["colour_off"])
+    L = cr.contact_lists(t, 3)
+    rows, _ = run_tool(tool, t, 3)
+    cs.assert_host_lists(rows, L)
+    assert L["box_pairs"] == 0 and L["n_box_box"] > 0
     # pairs of two boxes left out: the boxes mode
-    _, off = run_tool(tool, t, "2")
-    _, old = run_tool(old_tool, t, "1")
-    assert off == old + "box_box 0\n" and "box_pairs %d\n" % br.contact_lists(t, boxes=True)["box_pairs"] in old
+    L2 = cr.contact_lists(t, 2)
+    rows, _ = run_tool(tool, t, 2)
+    cs.assert_host_lists(rows, L2)
+    assert L2["n_box_box"] == 0 and L2["box_pairs"] == L["n_box_box"]
 
 
 def test_host_refuses_one_past_the_limit_with_box_pairs(tools):
     """256 dynamic boxes x 256 following boxes = 65 536 candidates, every one a pair of two boxes, are taken; 256 x 257 are refused with
     the counts in the message; a table of spheres, boxes and box pairs one past the limit is refused with its box pairs counted; with the
     pairs of two boxes left out both are taken"""
-    tool, _ = tools
-    rows, _ = run_tool(tool, limit_table(256), "3")
+    tool = tools
+    rows, _ = run_tool(tool, limit_table(256), 3)
     assert rows["counts"][:2] == ["65536", "0"] and rows["refused"][0] == "0" and len(rows["follow_idx"]) == 65536 and rows["box_box"] == ["65536"]
-    rows, out = run_tool(tool, limit_table(257), "3")
+    rows, out = run_tool(tool, limit_table(257), 3)
     assert rows["counts"][:2] == ["65792", "0"] and rows["refused"][0] == "1" and rows.get("follow_idx", []) == [] and rows["box_box"] == ["65792"]
-    assert xr.refusal(xr.contact_lists(limit_table(257))) in out and "(65792 of them pairs of two boxes)" in out and "broad phase" in out
-    assert not xr.refusal(xr.contact_lists(limit_table(256))) and not xr.refusal(xr.contact_lists(limit_table(257), box_pairs=False))
-    rows, _ = run_tool(tool, limit_table(257), "2")
+    assert cr.refusal(cr.contact_lists(limit_table(257), 3)) in out and "(65792 of them pairs of two boxes)" in out and "broad phase" in out
+    assert not cr.refusal(cr.contact_lists(limit_table(256), 3)) and not cr.refusal(cr.contact_lists(limit_table(257), 2))
+    rows, _ = run_tool(tool, limit_table(257), 2)
     assert rows["counts"][:2] == ["0", "0"] and rows["refused"][0] == "0" and rows["box_pairs"] == ["65792"] and rows["box_box"] == ["0"]
     # mixed: 255 dynamic spheres and one dynamic box against 257 following boxes: 65 535 sphere - box entries and 257 box - box ones
     t = limit_table(257)
     t["shape"][:255] = 0
-    L = xr.contact_lists(t)
-    assert (L["n_follow"], L["n_box_box"]) == (65792, 257) and xr.refusal(L) == "65792 follow entries and 0 dynamic pairs (257 of them pairs of two boxes)"
-    rows, out = run_tool(tool, t, "3")
-    assert rows["refused"][0] == "1" and xr.refusal(L) in out
-    rows, _ = run_tool(tool, t, "2")
+    L = cr.contact_lists(t, 3)
+    assert (L["n_follow"], L["n_box_box"]) == (65792, 257) and cr.refusal(L) == "65792 follow entries and 0 dynamic pairs (257 of them pairs of two boxes)"
+    rows, out = run_tool(tool, t, 3)
+    assert rows["refused"][0] == "1" and cr.refusal(L) in out
+    rows, _ = run_tool(tool, t, 2)
     assert rows["counts"][:2] == ["65535", "0"] and rows["refused"][0] == "0" and rows["box_pairs"] == ["257"]
 
 
@@ -372,9 +334,9 @@ def test_engine_all_option_with_a_recording_addon(tmp_path):
     loadModel; 'boxes' still passes 2 and true 1; any other string turns nothing on; 'all' without devicePhysics throws"""
     sc, data, _ = xs.node_case()
     (tmp_path / "s.pmx").write_bytes(data)
-    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contact_boxbox_engine_mock.js"), str(tmp_path / "s.pmx")], timeout=60).decode().strip().splitlines()[-1])
+    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contacts_engine_mock.js"), str(tmp_path / "s.pmx"), "all", "boxes", "true", "everything"], timeout=60).decode().strip().splitlines()[-1])
     assert r["needsDevicePhysics"] and r["shards"] >= 2 and len(r["all"]) == r["shards"]
-    for tag, want in (("all", "physicsContacts:3"), ("boxes", "physicsContacts:2"), ("plain", "physicsContacts:1")):
+    for tag, want in (("all", "physicsContacts:3"), ("boxes", "physicsContacts:2"), ("true", "physicsContacts:1")):
         for calls in r[tag]:
             assert [c for c in calls if c.startswith("physicsContacts")] == [want] and calls.index(want) == calls.index("uploadPhysics") + 1
-    assert all("physicsContacts" not in " ".join(calls) for calls in r["other"]) and all("uploadPhysics" in calls for calls in r["other"])
+    assert all("physicsContacts" not in " ".join(calls) for calls in r["everything"]) and all("uploadPhysics" in calls for calls in r["everything"])

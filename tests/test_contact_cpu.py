@@ -128,7 +128,7 @@ def test_cases_are_well_conditioned_and_touch():
     horizon, and at least one contact is active in at least a quarter of the substeps"""
     rows, bad = [], {}
     for name in cs._CASES:
-        c, act = cs.conditioning(name)
+        c, act, _ = cs.conditioning(name)
         rows.append("%s %.1e / %.2f" % (name, c, act))
         if c > ILL or act < 0.25:
             bad[name] = (c, act)
@@ -140,16 +140,7 @@ def test_cases_are_well_conditioned_and_touch():
         widest = max(np.bincount(pr.colouring(t)[0])) if t["n_joints"] else 0
         assert (64 if t["n_bodies"] <= 64 and widest <= 64 else 256) == block and int(t["n_joints"] <= block) == own, name
     # the Node end-to-end case: the PMX's table under one pose, the engine's substeps
-    import physics_scenes as ps
-    sc, _, q = cs.node_case()
-    calls = ps.node_substeps()
-    poses = [(q, np.zeros((sc["B"], 3), dtype=np.float32))] * len(calls)
-    runs = {}
-    for dt in (np.float64, np.float32):
-        sim = cr.Sim(sc["table"], sc["parents"], sc["bind"], dtype=dt)
-        runs[dt] = (cs.run_reference(sc, poses, calls, dtype=dt, sim=sim), sim)
-    c = max(max(float(np.abs(a[0] - b[0]).max()), float(np.abs(a[1][:, :3] - b[1][:, :3]).max())) for a, b in zip(runs[np.float64][0], runs[np.float32][0])) / sc["extent"]
-    act = float((np.array(runs[np.float64][1].active) > 0).mean())
+    c, act, _ = cs.node_conditioning()
     print("node case: %.1e / %.2f" % (c, act))
     assert c <= ILL and act >= 0.25
     # the strides the cases are there for
@@ -165,32 +156,12 @@ def test_cases_are_well_conditioned_and_touch():
 
 # ---- the host half: contact_table.h against the definition's lists ----
 
-def dump(t):
-    rows = ["%d" % t["n_bodies"]]
-    for b in range(t["n_bodies"]):
-        rows.append("%d %d %d %d %r %r %r %r %r" % (t["type"][b], t["shape"][b], t["group"][b], t["mask"][b], float(t["size"][b][0]), float(t["size"][b][1]), float(t["size"][b][2]),
-                                                    float(t["mass"][b]), float(t["friction"][b])))
-    return "\n".join(rows) + "\n"
-
-
-def limit_table(n_follow):
-    """256 dynamic x n_follow following spheres, all in each other's masks: 256 n_follow follow entries (65 536 with 256, the limit)"""
-    dyn = dict(bone=-1, type=1, mass=1.0, shape=0, size=[0.1, 0, 0], group=1, mask=1 << 2)
-    fol = dict(bone=1, type=0, mass=0.0, shape=0, size=[0.1, 0, 0], group=2, mask=1 << 1)
-    return pr.make_table([dict(dyn, offset_pos=[3.0 * k, 0, 0]) for k in range(256)] + [dict(fol, offset_pos=[3.0 * k, 50.0, 0]) for k in range(n_follow)], [])
-
-
 @pytest.fixture(scope="module")
 def contact_tool(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("contact_table") / "contact_table_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
-                           os.path.join(ROOT, "tests", "contact_table_main.cpp")])
-    return exe
+    return cs.build_table_tool(tmp_path_factory.mktemp("contact_table"))
 
 
-def run_tool(tool, t):
-    out = subprocess.run([tool], input=dump(t), capture_output=True, text=True, check=True).stdout
-    return {ln.split(" ", 1)[0]: ln.split(" ", 1)[1].split() if " " in ln else [] for ln in out.strip().split("\n")}, out
+run_tool, limit_table = cs.run_table_tool, cs.limit_table
 
 
 @pytest.mark.parametrize("name", ["own 64", "stride 256", "70 partners", "257 pairs", "three colours", "capsule sphere df"])
@@ -199,12 +170,7 @@ def test_host_lists_equal_the_definition(contact_tool, name):
     t = cs.case(name)[0]["table"]
     L = cr.contact_lists(t)
     rows, out = run_tool(contact_tool, t)
-    assert [int(v) for v in rows["counts"]] == [L["n_follow"], L["n_pairs"], L["n_colours"], L["boxes"]] and rows["refused"][0] == "0"
-    shape = np.array([float(v) for v in rows["shape"]], dtype=np.float32).reshape(-1, 4)          # (%.9g round-trips a float32)
-    assert np.array_equal(shape[:, 0], L["radius"]) and np.array_equal(shape[:, 1], L["half"]) and np.array_equal(shape[:, 2], L["friction"])
-    assert np.array_equal(shape[:, 3], L["takes"].astype(int))
-    assert [int(v) for v in rows["follow_off"]] == list(L["follow_off"]) and [int(v) for v in rows["follow_idx"]] == list(L["follow_idx"])
-    assert [int(v) for v in rows["pair"]] == list(L["pairs"].reshape(-1)) and [int(v) for v in rows["colour_off"]] == list(L["colour_off"])
+    cs.assert_host_lists(rows, L)
 
 
 def test_host_counts_boxes_and_applies_the_masks(contact_tool):
@@ -234,9 +200,9 @@ def test_engine_physics_contacts_option_with_a_recording_addon(tmp_path):
     loadModel; without the option the engine makes no such call; physicsContacts without devicePhysics throws"""
     sc, data, _ = cs.node_case()
     (tmp_path / "s.pmx").write_bytes(data)
-    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contacts_engine_mock.js"), str(tmp_path / "s.pmx")], timeout=60).decode().strip().splitlines()[-1])
+    r = json.loads(subprocess.check_output(["node", os.path.join(ROOT, "tests", "js", "contacts_engine_mock.js"), str(tmp_path / "s.pmx"), "true", "off"], timeout=60).decode().strip().splitlines()[-1])
     assert r["needsDevicePhysics"] and r["needsDeviceFK"]
-    assert r["shards"] >= 2 and len(r["on"]) == r["shards"]
-    for calls in r["on"]:
+    assert r["shards"] >= 2 and len(r["true"]) == r["shards"]
+    for calls in r["true"]:
         assert calls.count("physicsContacts:1") == 1 and calls.index("physicsContacts:1") == calls.index("uploadPhysics") + 1
     assert all("physicsContacts" not in " ".join(calls) for calls in r["off"]) and all("uploadPhysics" in calls for calls in r["off"])
