@@ -342,18 +342,19 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *                             about which changes that angle alone), alpha~ = 1 / (k h^2),
  *                             d_lambda = (-C - alpha~ lambda) / (w_A + w_B + alpha~); lambda is accumulated over the iterations of a
  *                             substep and zero at its start
+ *            linear springs   only under rz_physics_springs (below): the last stage of the joint, per axis with spring_position k > 0
  *          a rotation correction d_phi is applied as q = normalize(q + (1/2) [d_phi, 0] (x) q); a min > max pair of limits is swapped
  *        velocities from the pose change:  v = (x - x_prev) / h;  w = 2 (q (x) q_prev^-1).xyz / h, negated when .w < 0
  *      Inverse inertia, diagonal in the body frame: sphere 2/5 m r^2 (r = size.x); box m/3 (b^2 + c^2) with half extents = size; capsule the
  *      box of half extents (r, r + height/2, r) (r = size.x, height = size.y).
  *   3. every dynamic body with a bone gives boneWorld = bodyWorld x offset^-1: that bone's override, in every following frame until the
  *      next step. Children of an overridden bone keep the matrices solved from the un-overridden parent, as rz_override_world documents.
- * NOT covered: contacts unless rz_physics_contacts enables them (below; boxes only under on = 2 and 3); linear springs (spring_position),
- * restitution. A welded joint (all limits equal) whose
+ * NOT covered: contacts unless rz_physics_contacts enables them (below; boxes only under on = 2 and 3); linear springs (spring_position)
+ * unless rz_physics_springs enables them (below); restitution. A welded joint (all limits equal) whose
  * anchor is off the body's centre converges only linearly in `iterations` (the position and the rotation stage each undo part of the
  * other): about 0.3 of a parent's jump is left at 4 iterations, 1e-5 of it at 32. Without contacts shapes feed the inertia only; group, mask
- * and friction are kept for the contact stage; restitution and spring_position are unused (group, mask, friction, restitution and
- * spring_position may be NULL; contacts need the first three). There is no host-side twin of the solver.
+ * and friction are kept for the contact stage and spring_position for the linear springs; restitution is unused (group, mask, friction,
+ * restitution and spring_position may be NULL; contacts need the first three, the linear springs the last). There is no host-side twin of the solver.
  * rz_upload_physics: needs rz_upload_skeleton_topology first; NULL or n_bodies = 0 removes the table; gravity3 NULL, h = 0, iterations = 0 =
  *   the defaults. RZ_ERR_INVALID (context untouched): a body, bone or joint index out of range, body_a == body_b, a value that is not finite,
  *   mass < 0, a damping outside [0, 1], h < 0, a type or shape above 2, two dynamic bodies on one bone. RZ_ERR_UNSUPPORTED: a table whose state does not fit the
@@ -451,7 +452,30 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  * all of them; on = 2 and 3: those with an extent of 0), ("physics_contact_box_pairs") = the pairs of two boxes left out under on = 2 (a build
  * without box contacts does not know this key: that is how a binding detects them), ("physics_contact_box_box") = the pairs of two boxes
  * taking part under on = 3, 0 in every other mode (a build without on = 3 does not know this key, the ABI version stayed 8: that is how a
- * binding detects it); all read-only, 0 without contacts. */
+ * binding detects it); all read-only, 0 without contacts.
+ * ---- linear joint springs — NEW (optional, off by default) ----
+ * rz_physics_springs(ctx, 1) adds the linear springs of the resident table's joints (PMX spring_position: a joint with play along an axis
+ * and a spring on it then swings about its rest point instead of hanging at the end of its play); 0 drops them. Defined in float64 by
+ * tests/spring_ref.py. The stage is the last of a joint's solve, behind the angular springs, in every iteration; per axis ax = x, y, z in
+ * that order with spring_position[ax] = k > 0, each axis from the pose the one before left:
+ *     r_A = q_A r_a, r_B = q_B r_b, n = Q_A e_ax (Q_A = q_A j_A; n is taken as fixed for this correction)
+ *     C = n . ((x_B + r_B) - (x_A + r_A)) — the component of d the position stage computes; the rest point is 0
+ *     w = 1/m_A + 1/m_B + (r_A x n)^T I_A^-1 (r_A x n) + (r_B x n)^T I_B^-1 (r_B x n)
+ *     alpha~ = 1 / (k h^2), d_lambda = (-C - alpha~ lambda) / (w + alpha~), lambda += d_lambda (three more multipliers per joint, zero at
+ *     the start of a substep);  x_A -= n d_lambda / m_A, q_A turned by -I_A^-1 (r_A x n) d_lambda;  x_B += n d_lambda / m_B, q_B by
+ *     +I_B^-1 (r_B x n) d_lambda. Only dynamic bodies are written; k <= 0: no spring on that axis.
+ *   One body on one spring is backward Euler's oscillator: period 2 pi h / atan(omega h) with omega^2 = k / m, amplitude falling by
+ *   (1 + (omega h)^2)^(-1/2) per substep, whatever `iterations` is. The rest point is always 0 (the joint's own position).
+ * rz_physics_springs: on != 0 derives one record per joint (alpha~ per axis in double, rounded once, and the axes' bits) from the
+ *   spring_position3 kept at upload and selects the LSPRING instantiations of rz_physics_kernel; a table without any k > 0 is taken and
+ *   goes on through the kernels and the LDS it had. Neither value resets or touches the simulation; both drop a captured graph. A new
+ *   rz_upload_physics, a table removal, a new skeleton or a new topology turns the springs off. Without the call a table steps through
+ *   exactly the kernels, and to exactly the bits, it did before this entry point existed. RZ_ERR_INVALID: no resident table; forks exist;
+ *   a table with joints uploaded with spring_position3 NULL. RZ_ERR_UNSUPPORTED: in the striding form (more joints than lanes) the
+ *   multipliers in LDS cost 24 B per joint instead of 12, and 96 B per body + 24 B per joint exceeds 160 KB. The context keeps its state
+ *   in every case. The block size chosen at upload does not change.
+ * rz_get_tuning("physics_springs") = 0 / 1, ("physics_spring_axes") = the (joint, axis) pairs with k > 0 while enabled, else 0;
+ * ("physics_lds") reports the size actually launched. A build without the symbol has no linear springs (the ABI version stayed 8). */
 typedef struct rz_physics {
     uint32_t n_bodies;
     const int32_t *bone;                /* [n_bodies] -1 = none */
@@ -472,6 +496,7 @@ int rz_upload_physics(rz_ctx *ctx, const rz_physics *tab);
 int rz_physics_step(rz_ctx *ctx, uint32_t substeps);
 int rz_physics_reset(rz_ctx *ctx);
 int rz_physics_contacts(rz_ctx *ctx, uint32_t on);
+int rz_physics_springs(rz_ctx *ctx, uint32_t on);
 int rz_read_physics(rz_ctx *ctx, uint32_t instance, float *state13);
 /* Blocking readback of one instance's world matrices (B x 16, column-major) as the frame used them. */
 int rz_read_world(rz_ctx *ctx, uint32_t instance, float *world16);

@@ -22,14 +22,14 @@ SYMBOLS = [
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
-    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts",
+    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
-# points and rz_physics_contacts — detected by the symbol, the version stayed 8)
+# points, rz_physics_contacts and rz_physics_springs — detected by the symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
                     "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
-                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts"}
+                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
 
@@ -210,6 +210,8 @@ def load(path=None):
         L.rz_read_physics.argtypes = [vp, u32, fp]
     if hasattr(L, "rz_physics_contacts"):
         L.rz_physics_contacts.argtypes = [vp, u32]
+    if hasattr(L, "rz_physics_springs"):
+        L.rz_physics_springs.argtypes = [vp, u32]
     for name in SYMBOLS:
         # (libraries older than the current ABI — tools/ab_inproc.py loads them side by side — lack the newer symbols: OPTIONAL_SYMBOLS)
         if name != "rz_last_error" and (name not in OPTIONAL_SYMBOLS or hasattr(L, name)):
@@ -681,6 +683,14 @@ class DeformContext:
         elif on and boxes:
             self.get_tuning("physics_contact_box_pairs")        # (a library without box contacts does not know the key: its error says so)
         self._chk(self._L.rz_physics_contacts(self._h, (3 if box_pairs else 2 if boxes else 1) if on else 0))
+
+    def physics_springs(self, on=True):
+        """The linear springs of the resident physics table's joints (PMX spring_position; off by default; include/reze_deform.h states the
+        stage): a joint with play along an axis and a spring on it swings about its rest point. The table must have been uploaded with
+        spring_position. A new table, skeleton or topology turns the springs off again. Does not reset the simulation."""
+        if not hasattr(self._L, "rz_physics_springs"):
+            raise RzError(-6, "this build of the library has no rz_physics_springs")
+        self._chk(self._L.rz_physics_springs(self._h, 1 if on else 0))
 
     def read_physics(self, instance=0):
         """[n_bodies, 13] x3 q4 v3 w3 of one instance (blocking)."""

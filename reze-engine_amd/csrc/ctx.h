@@ -194,6 +194,15 @@ struct rz_ctx : RzStatic, RzTuning {
     std::vector<uint8_t> ph_group, ph_shape, ph_type;
     std::vector<uint16_t> ph_mask;
     std::vector<float> ph_size, ph_friction, ph_mass;
+    // what decides the linear springs, as uploaded (ph_spring_pos empty: the column was NULL): rz_physics_springs derives its records from
+    // these (physics_table.h)
+    std::vector<float> ph_spring_pos;   // [ph_nj * 3] spring_position3, file order
+    std::vector<int> ph_order;          // [ph_nj] the joints' solve order
+    double ph_hd = 0.0;                 // h as derived at upload, before its rounding to ph_h
+    // the linear springs (rz_physics_springs): off unless ph_springs; ph_lin is null while no axis of the table has a spring
+    int ph_springs = 0;
+    uint32_t ph_spring_axes = 0;
+    float4 *ph_lin = nullptr;           // [ph_nj] in solve order (deform_kernels.h: RzPhysicsParams::lin)
     // the contact stage (rz_physics_contacts): off unless ph_contacts; the lists are constants of the resident table
     int ph_contacts = 0;                // 0 off | 1 spheres and capsules | 2 boxes take part as well | 3 and box against box
     float4 *ph_c_shape = nullptr, *ph_c_box = nullptr;
@@ -399,6 +408,7 @@ void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
 void free_physics(rz_ctx *c);          // physics_host.cpp
 void free_contacts(rz_ctx *c);
+void free_springs(rz_ctx *c);
 RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {

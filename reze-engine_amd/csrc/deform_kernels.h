@@ -295,8 +295,11 @@ struct RzPhysicsParams {
     int contacts;               // the CONTACT instantiations: 1 spheres and capsules | 2 boxes take part as well | 3 and box against box
     const float4 *c_box;        // [nb]     contacts = 2 and 3 only: a box's half extents | 0, zeros for every other body (behind the rest:
                                 //          the arguments of the other instantiations stay where they were)
+    // the linear springs (rz_physics_springs; physics_table.h derives the records): null = off, the LSPRING instantiations otherwise
+    const float4 *lin;          // [nj]     in solve order: alpha~ x | alpha~ y | alpha~ z | bits(axes with spring_position > 0) (behind the rest, as c_box is)
 };
-size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block);     // 96 B per body (+ 12 B per joint when the joints outnumber the lanes)
+// 96 B per body (+ 12 B per joint when the joints outnumber the lanes, 24 B with the linear springs' multipliers)
+size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block, int springs);
 hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st);
 
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).

@@ -25,7 +25,12 @@
 // solve_contact_boxes is the box front end, a fixed 24-step bisection in the box frame, ahead of the same resolve_contact. CONTACT = 3
 // (tests/contact_boxbox_ref.py): pairs of two boxes are candidates too — solve_contact_box_box is their front end, a separating-axis
 // search over the 15 axes and one contact point on the axis of least overlap, ahead of the same resolve_contact.
+// LSPRING (rz_physics_springs; tests/spring_ref.py is its definition): the linear springs of a joint, the tail of solve_joint behind the
+// angular springs — per axis with spring_position > 0 a compliant constraint on that component of the anchors' offset in A's joint frame.
+// A joint's linear constants are one more float4 (alpha~ x, y, z | bits(axes)) from p.lin and three more multipliers: in registers with
+// the rest under OWN, loaded per visit and kept in LDS ([nj][6] then) otherwise. Without LSPRING the kernel is the code it was.
 #include "pass_parts.hip.h"
+#include "../physics_table.h"       // rzphys::lds_bytes: the LDS arithmetic, where the host half's own test program reaches it
 
 namespace {
 
@@ -121,8 +126,10 @@ __device__ __forceinline__ JointC load_joint(const float4 *rec)
 
 // One joint, once: position, rotation limits, angular springs (tests/physics_ref.py: Sim._solve). sx / sq are the workgroup's body positions
 // and rotations in LDS, `body` the static body records (inverse mass in word 0's w, inverse inertia in word 2), lam the joint's three spring
-// multipliers.
-__device__ __forceinline__ void solve_joint(const JointC &c, const float4 *body, float4 *sx, float4 *sq, float &lam0, float &lam1, float &lam2)
+// multipliers. LSPRING: then the linear springs (tests/spring_ref.py: Sim._solve) with the joint's linear record lin and their multipliers ll.
+template <bool LSPRING>
+__device__ __forceinline__ void solve_joint(const JointC &c, const float4 *body, float4 *sx, float4 *sq, float &lam0, float &lam1, float &lam2,
+                                            const float4 lin, float &ll0, float &ll1, float &ll2)
 {
     const float4 ba0 = body[4 * c.a], ba2 = body[4 * c.a + 2], bb0 = body[4 * c.b], bb2 = body[4 * c.b + 2];
     const float ima = ba0.w, imb = bb0.w;
@@ -204,6 +211,29 @@ __device__ __forceinline__ void solve_joint(const JointC &c, const float4 *body,
             lam = lam + dl;
             qa = rot_apply(qa, neg(na * dl));
             qb = rot_apply(qb, nb * dl);
+        }
+    }
+    // linear springs: per axis, from the pose the axis before left, the anchors' offset along that axis of A's joint frame
+    if constexpr (LSPRING) {
+        const uint32_t axes = __float_as_uint(lin.w);
+        if (axes) {
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                if (!(axes >> ax & 1u)) continue;
+                const V3 ra = qrot(qa, c.r_a), rb = qrot(qb, c.r_b);
+                const V3 n = qrot(qmul(qa, c.j_a), v3(ax == 0 ? 1.0f : 0.0f, ax == 1 ? 1.0f : 0.0f, ax == 2 ? 1.0f : 0.0f));
+                const float C = dot3(n, (xb + rb) - (xa + ra));
+                const V3 can = cross3(ra, n), cbn = cross3(rb, n);
+                const V3 na = iinv(qa, iia, can), nb = iinv(qb, iib, cbn);
+                const float w = ((ima + imb) + dot3(can, na)) + dot3(cbn, nb);
+                const float al = ax == 0 ? lin.x : ax == 1 ? lin.y : lin.z;
+                float &lam = ax == 0 ? ll0 : ax == 1 ? ll1 : ll2;
+                const float dl = (-C - al * lam) / (w + al);
+                lam = lam + dl;
+                const V3 p = n * dl;
+                xa = xa - p * ima; qa = rot_apply(qa, neg(na * dl));
+                xb = xb + p * imb; qb = rot_apply(qb, nb * dl);
+            }
         }
     }
     // only dynamic bodies are written: a following body may be shared inside a colour and never moves
@@ -526,13 +556,14 @@ template <> struct ContactOps<3> : ContactOps<2> {
     static __device__ __forceinline__ void solve(Body &A, Body &B) { solve_contact_all(A, B); }
 };
 
-template <int BLOCK, bool OWN, int CONTACT>
+template <int BLOCK, bool OWN, int CONTACT, bool LSPRING>
 __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams p)
 {
     extern __shared__ float4 ph_lds[];
     const int tid = threadIdx.x, inst = blockIdx.x, nb = p.nb;
     float4 *sx = ph_lds, *sq = sx + nb, *sv = sq + nb, *sw = sv + nb, *sxp = sw + nb, *sqp = sxp + nb;
-    float *slam = reinterpret_cast<float *>(sqp + nb);              // [nj][3], the striding form only
+    constexpr int NLAM = LSPRING ? 6 : 3;
+    float *slam = reinterpret_cast<float *>(sqp + nb);              // [nj][NLAM], the striding form only
     float4 *state = p.state + (size_t)inst * nb * 4;
     const float *world = p.world + (size_t)inst * p.B * 16;
 
@@ -562,7 +593,10 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
     }
     JointC own;
     float l0 = 0.0f, l1 = 0.0f, l2 = 0.0f;
+    float4 own_lin = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
     if (OWN && tid < p.nj) own = load_joint(p.joint + (size_t)tid * 8);
+    if constexpr (LSPRING && OWN) { if (tid < p.nj) own_lin = p.lin[tid]; }
     __syncthreads();
 
     const float h = p.h;
@@ -583,18 +617,20 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
                 sv[b] = make_float4(v.x, v.y, v.z, 0.0f); sw[b] = make_float4(w.x, w.y, w.z, 0.0f);
             }
         }
-        if (OWN) { l0 = l1 = l2 = 0.0f; }
-        else for (int k = tid; k < 3 * p.nj; k += BLOCK) slam[k] = 0.0f;
+        if (OWN) { l0 = l1 = l2 = 0.0f; m0 = m1 = m2 = 0.0f; }
+        else for (int k = tid; k < NLAM * p.nj; k += BLOCK) slam[k] = 0.0f;
         __syncthreads();
         for (int it = 0; it < p.iterations; ++it) {
             for (int col = 0; col < p.ncol; ++col) {
                 const int j0 = p.colour_off[col], j1 = p.colour_off[col + 1];
                 if (OWN) {
-                    if (tid >= j0 && tid < j1) solve_joint(own, p.body, sx, sq, l0, l1, l2);
+                    if (tid >= j0 && tid < j1) solve_joint<LSPRING>(own, p.body, sx, sq, l0, l1, l2, own_lin, m0, m1, m2);
                 } else {
                     for (int j = j0 + tid; j < j1; j += BLOCK) {
                         const JointC c = load_joint(p.joint + (size_t)j * 8);
-                        solve_joint(c, p.body, sx, sq, slam[3 * j], slam[3 * j + 1], slam[3 * j + 2]);
+                        float *lj = slam + NLAM * j;
+                        if constexpr (LSPRING) solve_joint<true>(c, p.body, sx, sq, lj[0], lj[1], lj[2], p.lin[j], lj[3], lj[4], lj[5]);
+                        else solve_joint<false>(c, p.body, sx, sq, lj[0], lj[1], lj[2], own_lin, m0, m1, m2);
                     }
                 }
                 __syncthreads();
@@ -669,10 +705,10 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
 
 #pragma clang fp contract(fast)
 
-template <int BLOCK, bool OWN, int CONTACT>
+template <int BLOCK, bool OWN, int CONTACT, bool LSPRING>
 hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
 {
-    auto k = rz_physics_kernel<BLOCK, OWN, CONTACT>;
+    auto k = rz_physics_kernel<BLOCK, OWN, CONTACT, LSPRING>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -683,27 +719,27 @@ hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipS
 
 }  // namespace
 
-size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block)
+size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block, int springs)
 {
-    return (size_t)n_bodies * 96 + (n_joints > block ? (size_t)n_joints * 12 : 0);
+    return rzphys::lds_bytes(n_bodies, n_joints, block, springs != 0);
 }
 
 hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st)
 {
     if (p.nb <= 0 || instances == 0 || (p.block != 64 && p.block != 256)) return hipErrorInvalidValue;
-    const bool own = p.nj <= p.block;
-    const size_t lds = rz_physics_lds_bytes(p.nb, p.nj, p.block);
+    const bool own = p.nj <= p.block, springs = p.lin != nullptr;
+    const size_t lds = rz_physics_lds_bytes(p.nb, p.nj, p.block, springs);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (p.contacts) {
         if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
         if (p.contacts == 2 || p.contacts == 3 ? !p.c_box : p.contacts != 1) return hipErrorInvalidValue;
     }
-    // one instantiation per (block, OWN, CONTACT)
+    // one instantiation per (block, OWN, CONTACT, LSPRING)
     using Launch = hipError_t (*)(const RzPhysicsParams &, uint32_t, size_t, hipStream_t);
-    static const Launch table[2][2][4] = {
-        {{launch<64, false, 0>, launch<64, false, 1>, launch<64, false, 2>, launch<64, false, 3>},
-         {launch<64, true, 0>, launch<64, true, 1>, launch<64, true, 2>, launch<64, true, 3>}},
-        {{launch<256, false, 0>, launch<256, false, 1>, launch<256, false, 2>, launch<256, false, 3>},
-         {launch<256, true, 0>, launch<256, true, 1>, launch<256, true, 2>, launch<256, true, 3>}}};
-    return table[p.block == 256][own][p.contacts](p, instances, lds, st);
+#define RZ_PH_ROW(B, O, L) { launch<B, O, 0, L>, launch<B, O, 1, L>, launch<B, O, 2, L>, launch<B, O, 3, L> }
+    static const Launch table[2][2][2][4] = {
+        {{RZ_PH_ROW(64, false, false), RZ_PH_ROW(64, true, false)}, {RZ_PH_ROW(256, false, false), RZ_PH_ROW(256, true, false)}},
+        {{RZ_PH_ROW(64, false, true), RZ_PH_ROW(64, true, true)}, {RZ_PH_ROW(256, false, true), RZ_PH_ROW(256, true, true)}}};
+#undef RZ_PH_ROW
+    return table[springs][p.block == 256][own][p.contacts](p, instances, lds, st);
 }

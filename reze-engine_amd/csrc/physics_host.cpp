@@ -16,15 +16,24 @@ void free_contacts(rz_ctx *c)
     c->ph_c_follow = c->ph_c_pairs = c->ph_c_ncol = c->ph_c_boxes = c->ph_c_box_pairs = c->ph_c_box_box = 0;
 }
 
+// the linear springs' records: the stage is off afterwards
+void free_springs(rz_ctx *c)
+{
+    dfree(c->ph_lin);
+    c->ph_springs = 0;
+    c->ph_spring_axes = 0;
+}
+
 void free_physics(rz_ctx *c)
 {
     if (!c->ph_nb) return;
     drop_graph(c);
     free_contacts(c);
+    free_springs(c);
     dfree(c->ph_body); dfree(c->ph_joint); dfree(c->ph_state); dfree(c->ph_colour_off);
     c->ph_nb = c->ph_nj = c->ph_ncol = c->ph_nd = c->ph_I = 0;
     c->ph_dyn_bone.clear(); c->ph_group.clear(); c->ph_mask.clear(); c->ph_shape.clear(); c->ph_type.clear();
-    c->ph_size.clear(); c->ph_friction.clear(); c->ph_mass.clear();
+    c->ph_size.clear(); c->ph_friction.clear(); c->ph_mass.clear(); c->ph_spring_pos.clear(); c->ph_order.clear();
     c->ph_reset = true;
     c->ovr_count = 0;                   // the overrides were physics' own
 }
@@ -97,6 +106,7 @@ static int step(rz_ctx *c, uint32_t substeps, bool reset)
         p.c_shape = c->ph_c_shape; p.c_follow_off = c->ph_c_follow_off; p.c_follow_idx = c->ph_c_follow_idx; p.c_pair = c->ph_c_pair;
         p.c_colour_off = c->ph_c_colour_off; p.c_ncol = (int)c->ph_c_ncol; p.contacts = c->ph_contacts; p.c_box = c->ph_c_box;
     }
+    p.lin = c->ph_lin;
     HIP_TRY(rz_launch_physics(p, c->I, st));
     c->ph_reset = false;
     c->ovr_count = c->I * c->ph_nd;
@@ -134,9 +144,8 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
     }
     rzphys::Built o;
     rzphys::build(t, c->B, parents.data(), bind.data(), o);
-    // 64 lanes when the bodies and the widest colour fit one wave, else 256 (unmeasured: DESIGN.md 9.7)
-    const int block = o.nb <= 64 && o.widest <= 64 ? 64 : 256;
-    const size_t lds = rz_physics_lds_bytes(o.nb, o.nj, block);
+    const int block = rzphys::block_for(o.nb, o.widest);
+    const size_t lds = rz_physics_lds_bytes(o.nb, o.nj, block, 0);
     if (lds > 160 * 1024)
         return fail(RZ_ERR_UNSUPPORTED, "physics table too large for the device solver: %u bodies and %u joints need %zu B of LDS (96 B per body, + 12 B per joint once the joints outnumber the %d lanes; the limit is 160 KB)",
                     t->n_bodies, t->n_joints, lds, block);
@@ -160,6 +169,9 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
     c->ph_type.assign(t->type, t->type + t->n_bodies);
     c->ph_size.assign(t->size3, t->size3 + (size_t)t->n_bodies * 3);
     c->ph_mass.assign(t->mass, t->mass + t->n_bodies);
+    if (t->spring_position3) c->ph_spring_pos.assign(t->spring_position3, t->spring_position3 + (size_t)t->n_joints * 3);
+    c->ph_order = o.order;
+    c->ph_hd = o.hd;
     c->ph_I = 0;
     c->ph_reset = true;
     return RZ_OK;
@@ -217,6 +229,39 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
     c->ph_c_follow = (uint32_t)o.n_follow; c->ph_c_pairs = (uint32_t)o.n_pairs; c->ph_c_ncol = (uint32_t)o.ncol; c->ph_c_boxes = (uint32_t)o.boxes;
     c->ph_c_box_pairs = (uint32_t)o.box_pairs; c->ph_c_box_box = (uint32_t)o.n_box_box;
     c->ph_contacts = mode;
+    return RZ_OK;
+}
+
+int rz_physics_springs(rz_ctx *c, uint32_t on)
+{
+    if (int r = use(c)) return r;
+    if (int r = physics_usable(c, "rz_physics_springs")) return r;
+    if (!on) {
+        if (!c->ph_springs) return RZ_OK;
+        HIP_TRY(hipStreamSynchronize(c->up_stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drop_graph(c);
+        free_springs(c);
+        return RZ_OK;
+    }
+    const size_t nj = c->ph_nj;
+    const bool have = c->ph_spring_pos.size() == nj * 3;          // (empty: the column was NULL)
+    rzphys::Linear o;
+    if (have) rzphys::build_linear(c->ph_spring_pos.data(), c->ph_order, c->ph_hd, o);
+    bool invalid = false;
+    const std::string bad = rzphys::springs_refusal((int)c->ph_nb, (int)nj, c->ph_block, have, o.axes, invalid);
+    if (!bad.empty()) return fail(invalid ? RZ_ERR_INVALID : RZ_ERR_UNSUPPORTED, "%s", bad.c_str());
+    // the new records first: a failed allocation leaves the context as it was. A table without a spring axis keeps the old kernels
+    float4 *lin = nullptr;
+    if (o.axes)
+        if (int r = to_device(&lin, o.rec.data(), nj)) return r;
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_graph(c);
+    free_springs(c);
+    c->ph_lin = lin;
+    c->ph_spring_axes = (uint32_t)o.axes;
+    c->ph_springs = 1;
     return RZ_OK;
 }
 

@@ -26,6 +26,7 @@ struct Built {
     std::vector<int> dyn_bone;          // bones of the dynamic bodies that have one, in body order: an instance's overrides
     int nb = 0, nj = 0, ncol = 0, nd = 0, widest = 0, iterations = kDefaultIterations;
     float h = (float)kDefaultH, g[3] = { 0.0f, -98.0f, 0.0f };
+    double hd = kDefaultH;              // h before its rounding: what the spring constants are derived from
 };
 
 inline bool dynamic(const rz_physics *t, uint32_t b) { return t->type[b] == 1 && t->mass[b] > 0.0f; }
@@ -142,7 +143,7 @@ inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const
     const uint32_t nb = t->n_bodies, nj = t->n_joints;
     o.nb = (int)nb; o.nj = (int)nj;
     const double h = t->h > 0.0f ? (double)t->h : kDefaultH;
-    o.h = (float)h;
+    o.h = (float)h; o.hd = h;
     o.iterations = t->iterations ? (int)t->iterations : kDefaultIterations;
     if (t->gravity3) for (int k = 0; k < 3; ++k) o.g[k] = t->gravity3[k];
     colour_joints(t, o.colour, o.order, o.ncol);
@@ -205,6 +206,59 @@ inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const
         }
         r[31] = bits_of(springs);
     }
+}
+
+// ---- the linear springs (rz_physics_springs; tests/spring_ref.py) ----
+
+constexpr size_t kLdsLimit = 160 * 1024;
+// lanes per workgroup, chosen at upload: 64 when the bodies and the widest colour fit one wave, else 256 (unmeasured: DESIGN.md 9.7)
+inline int block_for(int n_bodies, int widest) { return n_bodies <= 64 && widest <= 64 ? 64 : 256; }
+// LDS of one workgroup: 96 B per body; once the joints outnumber the lanes their multipliers live there too, 12 B per joint, 24 B with the
+// linear springs' three more
+inline size_t lds_bytes(int n_bodies, int n_joints, int block, bool springs)
+{
+    return (size_t)n_bodies * 96 + (n_joints > block ? (size_t)n_joints * (springs ? 24 : 12) : 0);
+}
+
+struct Linear {
+    std::vector<float> rec;             // [nj][4] in solve order: alpha~ x | alpha~ y | alpha~ z | bits(axes with spring_position > 0)
+    int axes = 0;                       // (joint, axis) pairs with a spring
+};
+// spring_position3 as uploaded ([nj * 3], file order), the solve order and the h rz_upload_physics derived; alpha~ = 1 / (k h^2) in double,
+// rounded once, as build does for the angular ones
+inline void build_linear(const float *spring_position3, const std::vector<int> &order, double h, Linear &o)
+{
+    const size_t nj = order.size();
+    o.rec.assign(nj * 4, 0.0f);
+    o.axes = 0;
+    for (size_t k = 0; k < nj; ++k) {
+        const size_t j = (size_t)order[k];
+        int32_t bits = 0;
+        for (int ax = 0; ax < 3; ++ax) {
+            const double ks = spring_position3[j * 3 + ax];
+            if (ks > 0) { bits |= 1 << ax; o.rec[k * 4 + ax] = (float)(1.0 / (ks * h * h)); ++o.axes; }
+        }
+        o.rec[k * 4 + 3] = bits_of(bits);
+    }
+}
+
+// What rz_physics_springs(ctx, 1) refuses for a resident table, "" = nothing. invalid: RZ_ERR_INVALID (the column is missing), otherwise
+// RZ_ERR_UNSUPPORTED (the doubled multipliers no longer fit). A table without a spring axis launches the old kernels at the old size.
+inline std::string springs_refusal(int n_bodies, int n_joints, int block, bool have_column, int axes, bool &invalid)
+{
+    char m[320];
+    invalid = false;
+    if (n_joints && !have_column) {
+        invalid = true;
+        return "rz_physics_springs: the resident table was uploaded without spring_position: linear springs need spring_position3";
+    }
+    const size_t lds = lds_bytes(n_bodies, n_joints, block, true);
+    if (axes && lds > kLdsLimit) {
+        snprintf(m, sizeof m, "rz_physics_springs: %d bodies and %d joints need %zu B of LDS with linear springs (96 B per body, + 24 B per joint instead of 12 once the joints outnumber the %d lanes; the limit is 160 KB)",
+                 n_bodies, n_joints, lds, block);
+        return m;
+    }
+    return "";
 }
 
 }  // namespace rzphys

@@ -261,7 +261,9 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "physics_contact_boxes")) *value = (int)c->ph_c_boxes;
     else if (!strcmp(key, "physics_contact_box_pairs")) *value = (int)c->ph_c_box_pairs;
     else if (!strcmp(key, "physics_contact_box_box")) *value = (int)c->ph_c_box_box;
-    else if (!strcmp(key, "physics_lds")) *value = c->ph_nb ? (int)rz_physics_lds_bytes((int)c->ph_nb, (int)c->ph_nj, c->ph_block) : 0;
+    else if (!strcmp(key, "physics_springs")) *value = c->ph_springs;
+    else if (!strcmp(key, "physics_spring_axes")) *value = (int)c->ph_spring_axes;
+    else if (!strcmp(key, "physics_lds")) *value = c->ph_nb ? (int)rz_physics_lds_bytes((int)c->ph_nb, (int)c->ph_nj, c->ph_block, c->ph_lin != nullptr) : 0;
     else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;

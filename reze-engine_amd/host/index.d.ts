@@ -46,8 +46,9 @@ export interface EngineOptions {
   /** false: time only advances through step(timeMs). */ realtime?: boolean
   /** Physics hand-off (engine.ts:2379-2381), host-FK frames: step() may overwrite world matrices in place before they are uploaded. */
   physics?: { step(dt: number, boneWorldMatrices: Float32Array, boneInverseBindMatrices: Float32Array): void }
-  /** Rigid-body physics on the GPU for the model's PMX bodies and joints (needs deviceFK; exclusive with `physics` and framesInFlight: 2). loadModel uploads Model.physicsTables() (rz_upload_physics); every frame turns the time the clock advanced since the last one into min(10, floor(accumulated / h)) fixed substeps of h = 1/75 s (rz_physics_step) before it deforms. No linear springs or restitution; contacts are opt-in (physicsContacts). */ devicePhysics?: boolean
+  /** Rigid-body physics on the GPU for the model's PMX bodies and joints (needs deviceFK; exclusive with `physics` and framesInFlight: 2). loadModel uploads Model.physicsTables() (rz_upload_physics); every frame turns the time the clock advanced since the last one into min(10, floor(accumulated / h)) fixed substeps of h = 1/75 s (rz_physics_step) before it deforms. No restitution; contacts (physicsContacts) and the joints' linear springs (physicsSprings) are opt-in. */ devicePhysics?: boolean
   /** With devicePhysics: contacts and friction between the model's sphere and capsule bodies by their PMX groups and masks (rz_physics_contacts, called on every shard right after the table's upload at loadModel). Off by default; without devicePhysics it throws. true: boxes take no part. 'boxes': the model's box bodies collide with its spheres and capsules as well (rz_physics_contacts(ctx, 2)); a pair of two boxes is still left out. 'all': pairs of two boxes collide too (rz_physics_contacts(ctx, 3)). */ physicsContacts?: boolean | 'boxes' | 'all'
+  /** With devicePhysics: the linear springs of the model's joints (PMX spring_position; rz_physics_springs, called on every shard right after the table's upload at loadModel, ahead of physicsContacts): a joint with play along an axis and a spring on it swings about its rest point instead of hanging at the end of its play. Off by default; without devicePhysics it throws. */ physicsSprings?: boolean
 }
 export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
 export interface EngineStats {

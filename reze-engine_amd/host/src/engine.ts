@@ -55,6 +55,7 @@ class Engine {
   lastPhysicsTime: number | null
   devicePhysics: boolean
   physicsContacts: boolean | 'boxes' | 'all'
+  physicsSprings: boolean
   physicsAccumulator: number
   physicsResident: boolean
   native: DeformAddon | null
@@ -135,6 +136,10 @@ class Engine {
     // 'boxes': its boxes take part as well; 'all': and its boxes meet each other
     this.physicsContacts = o.physicsContacts === 'boxes' || o.physicsContacts === 'all' ? o.physicsContacts : o.physicsContacts === true
     if (this.physicsContacts && !this.devicePhysics) throw new Error('physicsContacts needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
+    // physicsSprings: the linear springs of the table's joints (PMX spring_position; rz_physics_springs), enabled on every shard behind the
+    // upload and ahead of the contacts
+    this.physicsSprings = o.physicsSprings === true
+    if (this.physicsSprings && !this.devicePhysics) throw new Error('physicsSprings needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
     this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
     this.physicsResident = false
     this.native = null
@@ -318,6 +323,7 @@ class Engine {
         // so is physics: every shard simulates the same bodies (the solve is deterministic), so no shard waits for another's overrides
         if (tables && tables.nBodies > 0) {
           n.uploadPhysics(s.ctx, tables)
+          if (this.physicsSprings) n.physicsSprings(s.ctx, 1)
           if (this.physicsContacts) n.physicsContacts(s.ctx, this.physicsContacts === 'all' ? 3 : this.physicsContacts === 'boxes' ? 2 : 1)
           this.physicsResident = true
         }

@@ -1,0 +1,74 @@
+// A stand-alone program around reze-engine_amd/csrc/physics_table.h for the host half of rz_physics_springs: it reads a table as text and
+// prints what the call would derive from it — the linear records in solve order, the number of spring axes, the LDS of both forms and
+// the refusal — for tests/test_spring_cpu.py to compare with tests/spring_ref.py. Also the program to build under
+// -fsanitize=address,undefined.
+//   input:  B nb nj h iterations has_gravity has_column [gx gy gz]; parents[B]; bind[B*3]; then per body: bone type shape size3 offset_pos3
+//           offset_rot4 mass linear_damping angular_damping; per joint: body_a body_b position3 rotation3 position_min3 position_max3
+//           rotation_min3 rotation_max3 spring_rotation3 spring_position3 (has_column = 0: read, and handed on as NULL)
+#include "../reze-engine_amd/csrc/physics_table.h"
+
+#include <iostream>
+
+int main()
+{
+    uint32_t B, nb, nj, iterations;
+    int has_g, has_column;
+    float h, g[3] = { 0, 0, 0 };
+    std::cin >> B >> nb >> nj >> h >> iterations >> has_g >> has_column;
+    if (has_g) std::cin >> g[0] >> g[1] >> g[2];
+    std::vector<int32_t> parents(B), bone(nb);
+    std::vector<float> bind(B * 3), size(nb * 3), op(nb * 3), oq(nb * 4), mass(nb), ld(nb), ad(nb);
+    std::vector<uint8_t> type(nb), shape(nb);
+    std::vector<uint32_t> ja(nj), jb(nj);
+    std::vector<float> jf[8];
+    for (auto &v : jf) v.resize(nj * 3);
+    for (auto &p : parents) std::cin >> p;
+    for (auto &x : bind) std::cin >> x;
+    for (uint32_t b = 0; b < nb; ++b) {
+        int ty, sh;
+        std::cin >> bone[b] >> ty >> sh;
+        type[b] = (uint8_t)ty; shape[b] = (uint8_t)sh;
+        for (int k = 0; k < 3; ++k) std::cin >> size[b * 3 + k];
+        for (int k = 0; k < 3; ++k) std::cin >> op[b * 3 + k];
+        for (int k = 0; k < 4; ++k) std::cin >> oq[b * 4 + k];
+        std::cin >> mass[b] >> ld[b] >> ad[b];
+    }
+    for (uint32_t j = 0; j < nj; ++j) {
+        std::cin >> ja[j] >> jb[j];
+        for (auto &v : jf)
+            for (int k = 0; k < 3; ++k) std::cin >> v[j * 3 + k];
+    }
+    if (!std::cin) { std::cerr << "short input\n"; return 2; }
+    rz_physics t;
+    memset(&t, 0, sizeof t);
+    t.n_bodies = nb; t.bone = bone.data(); t.type = type.data(); t.shape = shape.data(); t.size3 = size.data(); t.offset_pos3 = op.data();
+    t.offset_rot4 = oq.data(); t.mass = mass.data(); t.linear_damping = ld.data(); t.angular_damping = ad.data();
+    t.n_joints = nj; t.body_a = ja.data(); t.body_b = jb.data();
+    t.position3 = jf[0].data(); t.rotation3 = jf[1].data(); t.position_min3 = jf[2].data(); t.position_max3 = jf[3].data();
+    t.rotation_min3 = jf[4].data(); t.rotation_max3 = jf[5].data(); t.spring_rotation3 = jf[6].data();
+    t.spring_position3 = has_column ? jf[7].data() : nullptr;
+    t.gravity3 = has_g ? g : nullptr; t.h = h; t.iterations = iterations;
+    const std::string bad = rzphys::validate(&t, B);
+    printf("valid %d %s\n", bad.empty() ? 1 : 0, bad.c_str());
+    if (!bad.empty()) return 0;
+    rzphys::Built o;
+    rzphys::build(&t, B, parents.data(), bind.data(), o);
+    const int block = rzphys::block_for(o.nb, o.widest);
+    rzphys::Linear lin;
+    if (t.spring_position3) rzphys::build_linear(t.spring_position3, o.order, o.hd, lin);
+    bool invalid = false;
+    const std::string no = rzphys::springs_refusal(o.nb, o.nj, block, t.spring_position3 != nullptr, lin.axes, invalid);
+    printf("form %d %d\n", block, o.nj <= block ? 1 : 0);
+    printf("lds %zu %zu\n", rzphys::lds_bytes(o.nb, o.nj, block, false), rzphys::lds_bytes(o.nb, o.nj, block, true));
+    printf("refused %d %s\n", no.empty() ? 0 : invalid ? RZ_ERR_INVALID : RZ_ERR_UNSUPPORTED, no.c_str());
+    printf("axes %d\n", lin.axes);
+    printf("order");
+    for (int c : o.order) printf(" %d", c);
+    printf("\nalpha");
+    for (size_t k = 0; k < lin.rec.size(); ++k)
+        if (k % 4 != 3) printf(" %.9g", lin.rec[k]);
+    printf("\nbits");
+    for (size_t k = 3; k < lin.rec.size(); k += 4) { int32_t v; memcpy(&v, &lin.rec[k], 4); printf(" %d", v); }
+    printf("\n");
+    return 0;
+}
