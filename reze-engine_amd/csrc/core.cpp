@@ -64,6 +64,14 @@ void drop_graph(rz_ctx *c)
     c->graph_sig = 0;
 }
 
+// nothing this context enqueued is still running: per-frame inputs and front kernels travel on the upload stream, the frame on the compute stream
+int drain(rz_ctx *c)
+{
+    HIP_TRY(hipStreamSynchronize(c->up_stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RZ_OK;
+}
+
 int ensure_outputs(rz_ctx *c)
 {
     // one instance: room for a whole all-gather chunk; instances are strided by Vp
@@ -417,9 +425,7 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
 int rz_sync(rz_ctx *c)
 {
     if (int r = use(c)) return r;
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RZ_OK;
+    return drain(c);
 }
 
 int rz_output_ptrs(rz_ctx *c, void **pos, void **nrm, uint32_t *v_padded)

@@ -2,7 +2,7 @@
 // plumbing, the frame plan, and the internal entry points of each unit. Nothing here is part of the C ABI (include/reze_deform.h);
 // everything internal lives in namespace rzi with hidden visibility.
 // The context is three parts, and rz_fork follows them: a fork BORROWS RzStatic (a copy of the struct, the lender's pointers), INHERITS RzTuning
-// (by value), and OWNS everything else (streams, pose slots, palettes, outputs, physics).
+// (by value), and OWNS everything else (streams, pose slots, palettes, outputs, and physics: one member, RzPhysics ph, empty in a fresh fork).
 //   core.cpp    context life cycle, buffers every unit sizes, error state            rz_create / rz_destroy / rz_fork / rz_sync ...
 //   upload.cpp  static data: mesh, skeleton, topology, morph targets, motion            rz_upload_* / rz_set_instances / rz_shard_range
 //   pose.cpp    per-frame inputs: pinned ring, zero-copy slots, copies                  rz_set_pose* / rz_override_world / rz_read_world
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "deform_kernels.h"
+#include "physics_table.h"
 
 #pragma GCC visibility push(hidden)
 namespace rzi {
@@ -47,6 +48,18 @@ const char *last_error();
 
 
 inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
+
+// Device memory with one owner. As a local it is upload-time scratch, or a replacement under construction, released on every exit path
+// (HIP_TRY returns early on failure); as a member it is released when its owner is reset or assigned (`owner = {}`).
+template <class T> struct Scratch {
+    T *p = nullptr;
+    Scratch() = default;
+    Scratch(Scratch &&o) noexcept : p(o.p) { o.p = nullptr; }
+    Scratch &operator=(Scratch &&o) noexcept { std::swap(p, o.p); return *this; }       // (o goes out of scope with what this one held)
+    ~Scratch() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
+    operator T *() const { return p; }
+};
 
 constexpr uint32_t kVertPad = 1024;   // planes are padded to a whole S=1 tile (256 quads)
 // Shards of one mesh are equal-sized except the last; their size is a multiple of 256 vertices (whole quads, whole S = 1 wave
@@ -157,6 +170,37 @@ struct RzTuning {
     int t_graph = 0;                    // "graph" tuning key: rz_deform_n replays captured hipGraphs of kGraphFrames frames
 };
 
+// Rigid-body physics (rz_upload_physics; physics_host.cpp, kernels/physics.hip): static records, per-instance state, and what the next step must
+// do first. nb = 0: no table. A fork's own, and empty from the start (physics is refused while forks exist). Every device array has its owner
+// here, so a stage is released by resetting its part as a whole (`part = {}`) and the table by resetting the struct: a new member cannot be
+// forgotten.
+struct RzPhysics {
+    rzi::Scratch<float4> body, joint, state;
+    rzi::Scratch<int> colour_off;
+    uint32_t nb = 0, nj = 0, ncol = 0, nd = 0, I = 0;
+    int iterations = 0, block = 64;
+    float h = 0.0f, g[3] = { 0.0f, 0.0f, 0.0f };
+    bool reset = true;                  // the next step places every body on its bone first
+    std::vector<int> dyn_bone;          // [nd] bones of the dynamic bodies
+    rzphys::Kept kept;                  // the columns as uploaded: rz_physics_contacts and rz_physics_springs derive their records from its view()
+    std::vector<int> order;             // [nj] the joints' solve order
+    double hd = 0.0;                    // h as derived at upload, before its rounding to h
+    // the contact stage (rz_physics_contacts): off unless mode; the lists are constants of the resident table
+    struct Contacts {
+        int mode = 0;                   // 0 off | 1 spheres and capsules | 2 boxes take part as well | 3 and box against box
+        rzi::Scratch<float4> shape, box;
+        rzi::Scratch<int> follow_off, follow_idx, colour_off;
+        rzi::Scratch<int2> pair;
+        uint32_t follow = 0, pairs = 0, ncol = 0, boxes = 0, box_pairs = 0, box_box = 0;
+    } contacts;
+    // the linear springs (rz_physics_springs): off unless on; lin is null while no axis of the table has a spring
+    struct Springs {
+        int on = 0;
+        uint32_t axes = 0;
+        rzi::Scratch<float4> lin;       // [nj] in solve order (deform_kernels.h: RzPhysicsParams::lin)
+    } springs;
+};
+
 struct rz_ctx : RzStatic, RzTuning {
     int device = 0;
     int n_cu = 256;
@@ -181,34 +225,7 @@ struct rz_ctx : RzStatic, RzTuning {
     uint32_t ovr_count = 0;
     size_t ovr_alloc = 0, ovr_off_alloc = 0;
 
-    // rigid-body physics (rz_upload_physics; physics_host.cpp, kernels/physics.hip): static records, per-instance state, and what the next step
-    // must do first. ph_nb = 0: no table. With a table the override table above is physics' own ([I][ph_nd] slots, fixed addresses).
-    float4 *ph_body = nullptr, *ph_joint = nullptr, *ph_state = nullptr;
-    int *ph_colour_off = nullptr;
-    uint32_t ph_nb = 0, ph_nj = 0, ph_ncol = 0, ph_nd = 0, ph_I = 0;
-    int ph_iterations = 0, ph_block = 64;
-    float ph_h = 0.0f, ph_g[3] = { 0.0f, 0.0f, 0.0f };
-    bool ph_reset = true;               // the next step places every body on its bone first
-    std::vector<int> ph_dyn_bone;       // [ph_nd] bones of the dynamic bodies
-    // what decides contacts, as uploaded (empty: the array was NULL): rz_physics_contacts derives its lists from these (contact_table.h)
-    std::vector<uint8_t> ph_group, ph_shape, ph_type;
-    std::vector<uint16_t> ph_mask;
-    std::vector<float> ph_size, ph_friction, ph_mass;
-    // what decides the linear springs, as uploaded (ph_spring_pos empty: the column was NULL): rz_physics_springs derives its records from
-    // these (physics_table.h)
-    std::vector<float> ph_spring_pos;   // [ph_nj * 3] spring_position3, file order
-    std::vector<int> ph_order;          // [ph_nj] the joints' solve order
-    double ph_hd = 0.0;                 // h as derived at upload, before its rounding to ph_h
-    // the linear springs (rz_physics_springs): off unless ph_springs; ph_lin is null while no axis of the table has a spring
-    int ph_springs = 0;
-    uint32_t ph_spring_axes = 0;
-    float4 *ph_lin = nullptr;           // [ph_nj] in solve order (deform_kernels.h: RzPhysicsParams::lin)
-    // the contact stage (rz_physics_contacts): off unless ph_contacts; the lists are constants of the resident table
-    int ph_contacts = 0;                // 0 off | 1 spheres and capsules | 2 boxes take part as well | 3 and box against box
-    float4 *ph_c_shape = nullptr, *ph_c_box = nullptr;
-    int *ph_c_follow_off = nullptr, *ph_c_follow_idx = nullptr, *ph_c_colour_off = nullptr;
-    int2 *ph_c_pair = nullptr;
-    uint32_t ph_c_follow = 0, ph_c_pairs = 0, ph_c_ncol = 0, ph_c_boxes = 0, ph_c_box_pairs = 0, ph_c_box_box = 0;
+    RzPhysics ph;                       // rigid-body physics; with a table the override table above is physics' own ([I][ph.nd] slots, fixed addresses)
 
     // per-frame state
     uint32_t I = 1;
@@ -385,12 +402,7 @@ template <class T> void dfree(T *&p)
 }
 int poll_event(hipEvent_t ev, const char *what);
 void drop_graph(rz_ctx *c);
-// upload-time scratch that is released on every exit path (HIP_TRY returns early on failure)
-template <class T> struct Scratch {
-    T *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
-};
+int drain(rz_ctx *c);                  // the upload stream, then the compute stream
 int ensure_outputs(rz_ctx *c);
 void set_ring(rz_ctx *c, int slot);
 void point_pose_slot(rz_ctx *c, int k);
@@ -407,8 +419,6 @@ void free_sdef(rz_ctx *c);
 void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
 void free_physics(rz_ctx *c);          // physics_host.cpp
-void free_contacts(rz_ctx *c);
-void free_springs(rz_ctx *c);
 RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {

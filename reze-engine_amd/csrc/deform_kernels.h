@@ -298,8 +298,7 @@ struct RzPhysicsParams {
     // the linear springs (rz_physics_springs; physics_table.h derives the records): null = off, the LSPRING instantiations otherwise
     const float4 *lin;          // [nj]     in solve order: alpha~ x | alpha~ y | alpha~ z | bits(axes with spring_position > 0) (behind the rest, as c_box is)
 };
-// 96 B per body (+ 12 B per joint when the joints outnumber the lanes, 24 B with the linear springs' multipliers)
-size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block, int springs);
+// (its LDS: physics_table.h, rzphys::lds_bytes and kLdsLimit)
 hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st);
 
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).

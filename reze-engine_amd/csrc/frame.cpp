@@ -184,8 +184,7 @@ bool want_overlap(const rz_ctx *c, const Plan &pl)
 int set_overlap(rz_ctx *c, bool on)
 {
     if (c->overlap_on == on) return RZ_OK;
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int r = drain(c)) return r;
     c->overlap_on = on;
     c->skin_recorded[0] = c->skin_recorded[1] = false;
     return RZ_OK;
@@ -445,8 +444,7 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
     // issues them — for crowds that is the overlapped protocol: fronts on the upload stream, skin kernels on the
     // context's stream (the events below sit on the context's stream; the last skin kernel waits for the last front)
     if (int r = run_frame(c, pl)) return r;       // the deform-only loop below needs a palette
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int r = drain(c)) return r;
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     for (uint32_t f = 0; f < frames; ++f)
         if (int r = run_frame(c, pl)) return r;

@@ -719,17 +719,12 @@ hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipS
 
 }  // namespace
 
-size_t rz_physics_lds_bytes(int n_bodies, int n_joints, int block, int springs)
-{
-    return rzphys::lds_bytes(n_bodies, n_joints, block, springs != 0);
-}
-
 hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st)
 {
     if (p.nb <= 0 || instances == 0 || (p.block != 64 && p.block != 256)) return hipErrorInvalidValue;
     const bool own = p.nj <= p.block, springs = p.lin != nullptr;
-    const size_t lds = rz_physics_lds_bytes(p.nb, p.nj, p.block, springs);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = rzphys::lds_bytes(p.nb, p.nj, p.block, springs);
+    if (lds > rzphys::kLdsLimit) return hipErrorInvalidValue;
     if (p.contacts) {
         if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
         if (p.contacts == 2 || p.contacts == 3 ? !p.c_box : p.contacts != 1) return hipErrorInvalidValue;

@@ -1,6 +1,8 @@
-// physics_host.cpp — rigid-body physics for PMX bodies and joints (ctx.h): the table's upload (physics_table.h checks, colours and derives it),
-// stepping, reset and readback. The solver itself is rz_physics_kernel (kernels/physics.hip); this unit owns the hierarchy solve's override
-// table while a physics table is resident.
+// physics_host.cpp — rigid-body physics for PMX bodies and joints: the table's upload (physics_table.h checks, colours and derives it, and keeps
+// the columns the contact stage and the linear springs derive from later), the two stages' switches, stepping, reset and readback. All of its
+// state is one member of the context, RzPhysics ph (ctx.h), whose device arrays free themselves: a stage is released by resetting its part,
+// the table by resetting ph, and a replacement is built in a local part that takes the old one's place only after drain(). The solver itself
+// is rz_physics_kernel (kernels/physics.hip); this unit owns the hierarchy solve's override table while a physics table is resident.
 #include "ctx.h"
 #include "contact_table.h"
 
@@ -8,33 +10,11 @@ using namespace rzi;
 
 namespace rzi {
 
-// the contact stage's lists: contacts are off afterwards
-void free_contacts(rz_ctx *c)
-{
-    dfree(c->ph_c_shape); dfree(c->ph_c_box); dfree(c->ph_c_follow_off); dfree(c->ph_c_follow_idx); dfree(c->ph_c_pair); dfree(c->ph_c_colour_off);
-    c->ph_contacts = 0;
-    c->ph_c_follow = c->ph_c_pairs = c->ph_c_ncol = c->ph_c_boxes = c->ph_c_box_pairs = c->ph_c_box_box = 0;
-}
-
-// the linear springs' records: the stage is off afterwards
-void free_springs(rz_ctx *c)
-{
-    dfree(c->ph_lin);
-    c->ph_springs = 0;
-    c->ph_spring_axes = 0;
-}
-
 void free_physics(rz_ctx *c)
 {
-    if (!c->ph_nb) return;
+    if (!c->ph.nb) return;
     drop_graph(c);
-    free_contacts(c);
-    free_springs(c);
-    dfree(c->ph_body); dfree(c->ph_joint); dfree(c->ph_state); dfree(c->ph_colour_off);
-    c->ph_nb = c->ph_nj = c->ph_ncol = c->ph_nd = c->ph_I = 0;
-    c->ph_dyn_bone.clear(); c->ph_group.clear(); c->ph_mask.clear(); c->ph_shape.clear(); c->ph_type.clear();
-    c->ph_size.clear(); c->ph_friction.clear(); c->ph_mass.clear(); c->ph_spring_pos.clear(); c->ph_order.clear();
-    c->ph_reset = true;
+    c->ph = {};                         // every array, list and record with its counts and flags; the next table starts from a reset
     c->ovr_count = 0;                   // the overrides were physics' own
 }
 
@@ -42,16 +22,16 @@ void free_physics(rz_ctx *c)
 // the kernel's). The table's buffers only ever grow, and only here: across steps they keep their addresses.
 static int ensure_instances(rz_ctx *c)
 {
-    if (c->ph_I == c->I && c->ph_state) return RZ_OK;
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RzPhysics &ph = c->ph;
+    if (ph.I == c->I && ph.state) return RZ_OK;
+    if (int r = drain(c)) return r;
     drop_graph(c);
     c->ovr_count = 0;
-    c->ph_I = 0;
-    dfree(c->ph_state);
-    const size_t I = c->I, nd = c->ph_nd, n = I * nd;
-    HIP_TRY(hipMalloc(&c->ph_state, I * c->ph_nb * 4 * sizeof(float4)));
-    HIP_TRY(hipMemset(c->ph_state, 0, I * c->ph_nb * 4 * sizeof(float4)));
+    ph.I = 0;
+    ph.state = {};
+    const size_t I = c->I, nd = ph.nd, n = I * nd;
+    HIP_TRY(ph.state.alloc(I * ph.nb * 4));
+    HIP_TRY(hipMemset(ph.state, 0, I * ph.nb * 4 * sizeof(float4)));
     if (n > c->ovr_alloc || I + 1 > c->ovr_off_alloc) {
         dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
         c->ovr_alloc = c->ovr_off_alloc = 0;
@@ -64,19 +44,37 @@ static int ensure_instances(rz_ctx *c)
     std::vector<int> off(I + 1), bones(std::max<size_t>(n, 1));
     for (size_t i = 0; i <= I; ++i) off[i] = (int)(i * nd);
     for (size_t i = 0; i < I; ++i)
-        for (size_t k = 0; k < nd; ++k) bones[i * nd + k] = c->ph_dyn_bone[k];
+        for (size_t k = 0; k < nd; ++k) bones[i * nd + k] = ph.dyn_bone[k];
     HIP_TRY(hipMemcpy(c->ovr_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
     if (n) HIP_TRY(hipMemcpy(c->ovr_bone, bones.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    c->ph_I = c->I;
-    c->ph_reset = true;
+    ph.I = c->I;
+    ph.reset = true;
     return RZ_OK;
 }
 
 static int physics_usable(rz_ctx *c, const char *what)
 {
-    if (!c->ph_nb) return fail(RZ_ERR_INVALID, "%s: no physics table is resident (rz_upload_physics)", what);
+    if (!c->ph.nb) return fail(RZ_ERR_INVALID, "%s: no physics table is resident (rz_upload_physics)", what);
     if (c->lender || c->n_forks) return fail(RZ_ERR_INVALID, "%s while forks exist: physics owns the override table of one context", what);
     return RZ_OK;
+}
+
+// the solver's arguments for the resident table; a stage that is off has left its part empty, so its pointers and counts are null and 0
+static RzPhysicsParams physics_params(const rz_ctx *c, uint32_t substeps, bool reset)
+{
+    const RzPhysics &ph = c->ph;
+    const RzPhysics::Contacts &k = ph.contacts;
+    RzPhysicsParams p;
+    memset(&p, 0, sizeof p);
+    p.body = ph.body; p.joint = ph.joint; p.colour_off = ph.colour_off; p.state = ph.state;
+    p.world = c->world; p.ovr_world = c->ovr_world;
+    p.nb = (int)ph.nb; p.nj = (int)ph.nj; p.ncol = (int)ph.ncol; p.nd = (int)ph.nd; p.B = (int)c->B;
+    p.iterations = ph.iterations; p.substeps = (int)substeps; p.reset = (reset || ph.reset) ? 1 : 0; p.block = ph.block;
+    p.h = ph.h; p.gx = ph.g[0]; p.gy = ph.g[1]; p.gz = ph.g[2];
+    p.c_shape = k.shape; p.c_follow_off = k.follow_off; p.c_follow_idx = k.follow_idx; p.c_pair = k.pair;
+    p.c_colour_off = k.colour_off; p.c_ncol = (int)k.ncol; p.contacts = k.mode; p.c_box = k.box;
+    p.lin = ph.springs.lin;
+    return p;
 }
 
 // the hierarchy solve of the resident pose without overrides, then the solver: both on the stream the frame's front runs on
@@ -95,21 +93,9 @@ static int step(rz_ctx *c, uint32_t substeps, bool reset)
     const int r = launch_fk(c, st);
     c->ovr_count = saved;
     if (r) return r;
-    RzPhysicsParams p;
-    memset(&p, 0, sizeof p);
-    p.body = c->ph_body; p.joint = c->ph_joint; p.colour_off = c->ph_colour_off; p.state = c->ph_state;
-    p.world = c->world; p.ovr_world = c->ovr_world;
-    p.nb = (int)c->ph_nb; p.nj = (int)c->ph_nj; p.ncol = (int)c->ph_ncol; p.nd = (int)c->ph_nd; p.B = (int)c->B;
-    p.iterations = c->ph_iterations; p.substeps = (int)substeps; p.reset = (reset || c->ph_reset) ? 1 : 0; p.block = c->ph_block;
-    p.h = c->ph_h; p.gx = c->ph_g[0]; p.gy = c->ph_g[1]; p.gz = c->ph_g[2];
-    if (c->ph_contacts) {
-        p.c_shape = c->ph_c_shape; p.c_follow_off = c->ph_c_follow_off; p.c_follow_idx = c->ph_c_follow_idx; p.c_pair = c->ph_c_pair;
-        p.c_colour_off = c->ph_c_colour_off; p.c_ncol = (int)c->ph_c_ncol; p.contacts = c->ph_contacts; p.c_box = c->ph_c_box;
-    }
-    p.lin = c->ph_lin;
-    HIP_TRY(rz_launch_physics(p, c->I, st));
-    c->ph_reset = false;
-    c->ovr_count = c->I * c->ph_nd;
+    HIP_TRY(rz_launch_physics(physics_params(c, substeps, reset), c->I, st));
+    c->ph.reset = false;
+    c->ovr_count = c->I * c->ph.nd;
     if (c->ovr_count) c->fk_stale = true;       // world matrices and palettes in memory are the un-overridden solve's: rz_read_world / rz_read_palette solve again
     return RZ_OK;
 }
@@ -123,19 +109,17 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_physics")) return r;
     if (!t || t->n_bodies == 0) {
-        if (c->ph_nb) {
-            HIP_TRY(hipStreamSynchronize(c->up_stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
+        if (c->ph.nb)
+            if (int r = drain(c)) return r;
         free_physics(c);
         return RZ_OK;
     }
     if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
         return fail(RZ_ERR_INVALID, "rz_upload_physics needs the hierarchy: call rz_upload_skeleton_topology first");
-    const std::string bad = rzphys::validate(t, c->B);
+    std::string bad = rzphys::validate(t, c->B);
     if (!bad.empty()) return fail(RZ_ERR_INVALID, "%s", bad.c_str());
-    if (t->n_bodies > (1u << 20) || t->n_joints > (1u << 20))
-        return fail(RZ_ERR_UNSUPPORTED, "physics table too large for the device solver: %u bodies and %u joints (96 B of LDS per body, + 12 B per joint once the joints outnumber the lanes; the limit is 160 KB)", t->n_bodies, t->n_joints);
+    bad = rzphys::upload_refusal(t->n_bodies, t->n_joints, nullptr);
+    if (!bad.empty()) return fail(RZ_ERR_UNSUPPORTED, "%s", bad.c_str());
     std::vector<int32_t> parents(c->B);
     std::vector<float> bind((size_t)c->B * 3);
     for (uint32_t b = 0; b < c->B; ++b) {
@@ -144,36 +128,25 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
     }
     rzphys::Built o;
     rzphys::build(t, c->B, parents.data(), bind.data(), o);
-    const int block = rzphys::block_for(o.nb, o.widest);
-    const size_t lds = rz_physics_lds_bytes(o.nb, o.nj, block, 0);
-    if (lds > 160 * 1024)
-        return fail(RZ_ERR_UNSUPPORTED, "physics table too large for the device solver: %u bodies and %u joints need %zu B of LDS (96 B per body, + 12 B per joint once the joints outnumber the %d lanes; the limit is 160 KB)",
-                    t->n_bodies, t->n_joints, lds, block);
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    bad = rzphys::upload_refusal(t->n_bodies, t->n_joints, &o);
+    if (!bad.empty()) return fail(RZ_ERR_UNSUPPORTED, "%s", bad.c_str());
+    if (int r = drain(c)) return r;
     free_physics(c);
     drop_graph(c);
     c->ovr_count = 0;                   // hand-fed overrides end here: the table is physics' own from now on
-    if (int r = to_device(&c->ph_body, o.body.data(), (size_t)o.nb * 4)) return r;
-    if (int r = to_device(&c->ph_joint, o.joint.data(), (size_t)o.nj * 8)) { dfree(c->ph_body); return r; }
-    if (int r = to_device(&c->ph_colour_off, o.colour_off.data(), o.colour_off.size())) { dfree(c->ph_body); dfree(c->ph_joint); return r; }
-    c->ph_nb = (uint32_t)o.nb; c->ph_nj = (uint32_t)o.nj; c->ph_ncol = (uint32_t)o.ncol; c->ph_nd = (uint32_t)o.nd;
-    c->ph_iterations = o.iterations; c->ph_h = o.h;
-    for (int k = 0; k < 3; ++k) c->ph_g[k] = o.g[k];
-    c->ph_block = block;
-    c->ph_dyn_bone = o.dyn_bone;
-    if (t->group) c->ph_group.assign(t->group, t->group + t->n_bodies);
-    if (t->mask) c->ph_mask.assign(t->mask, t->mask + t->n_bodies);
-    if (t->friction) c->ph_friction.assign(t->friction, t->friction + t->n_bodies);
-    c->ph_shape.assign(t->shape, t->shape + t->n_bodies);
-    c->ph_type.assign(t->type, t->type + t->n_bodies);
-    c->ph_size.assign(t->size3, t->size3 + (size_t)t->n_bodies * 3);
-    c->ph_mass.assign(t->mass, t->mass + t->n_bodies);
-    if (t->spring_position3) c->ph_spring_pos.assign(t->spring_position3, t->spring_position3 + (size_t)t->n_joints * 3);
-    c->ph_order = o.order;
-    c->ph_hd = o.hd;
-    c->ph_I = 0;
-    c->ph_reset = true;
+    // (the old table has gone, as it always had by here: a failed allocation leaves the context without one)
+    RzPhysics ph;
+    if (int r = to_device(&ph.body.p, o.body.data(), (size_t)o.nb * 4)) return r;
+    if (int r = to_device(&ph.joint.p, o.joint.data(), (size_t)o.nj * 8)) return r;
+    if (int r = to_device(&ph.colour_off.p, o.colour_off.data(), o.colour_off.size())) return r;
+    ph.nb = (uint32_t)o.nb; ph.nj = (uint32_t)o.nj; ph.ncol = (uint32_t)o.ncol; ph.nd = (uint32_t)o.nd;
+    ph.iterations = o.iterations; ph.h = o.h; ph.hd = o.hd;
+    for (int k = 0; k < 3; ++k) ph.g[k] = o.g[k];
+    ph.block = rzphys::block_for(o.nb, o.widest);
+    ph.dyn_bone = o.dyn_bone;
+    ph.order = o.order;
+    ph.kept.keep(t);
+    c->ph = std::move(ph);
     return RZ_OK;
 }
 
@@ -190,45 +163,35 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
     if (int r = use(c)) return r;
     if (int r = physics_usable(c, "rz_physics_contacts")) return r;
     if (!on) {
-        if (!c->ph_contacts) return RZ_OK;
-        HIP_TRY(hipStreamSynchronize(c->up_stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!c->ph.contacts.mode) return RZ_OK;
+        if (int r = drain(c)) return r;
         drop_graph(c);
-        free_contacts(c);
+        c->ph.contacts = {};
         return RZ_OK;
     }
     const int mode = on == 2 || on == 3 ? (int)on : 1;    // (every other nonzero value is 1, as it always was)
-    const size_t nb = c->ph_nb;
-    if (c->ph_group.size() != nb || c->ph_mask.size() != nb || c->ph_friction.size() != nb || c->ph_size.size() != nb * 3)
+    const rz_physics t = c->ph.kept.view();
+    if (!t.group || !t.mask || !t.friction || !t.size3)
         return fail(RZ_ERR_INVALID, "rz_physics_contacts: the resident table was uploaded without%s%s%s%s: contacts need group, mask, friction and size3",
-                    c->ph_group.size() != nb ? " group" : "", c->ph_mask.size() != nb ? " mask" : "", c->ph_friction.size() != nb ? " friction" : "",
-                    c->ph_size.size() != nb * 3 ? " size3" : "");
-    rz_physics t;
-    memset(&t, 0, sizeof t);
-    t.n_bodies = c->ph_nb; t.type = c->ph_type.data(); t.shape = c->ph_shape.data(); t.group = c->ph_group.data(); t.mask = c->ph_mask.data();
-    t.size3 = c->ph_size.data(); t.mass = c->ph_mass.data(); t.friction = c->ph_friction.data();
+                    !t.group ? " group" : "", !t.mask ? " mask" : "", !t.friction ? " friction" : "", !t.size3 ? " size3" : "");
     rzphys::Contacts o;
     rzphys::build_contacts(&t, o, mode);
     if (o.too_many) return fail(RZ_ERR_UNSUPPORTED, "%s", rzphys::contacts_refusal(o).c_str());
-    // the new lists first: a failed allocation leaves the context as it was
-    float4 *shape = nullptr, *box = nullptr;
-    int *foff = nullptr, *fidx = nullptr, *coff = nullptr;
-    int2 *pair = nullptr;
-    int r = to_device(&shape, o.shape.data(), nb);
-    if (!r && mode >= 2) r = to_device(&box, o.box.data(), nb);
-    if (!r) r = to_device(&foff, o.follow_off.data(), o.follow_off.size());
-    if (!r) r = to_device(&fidx, o.follow_idx.data(), o.follow_idx.size());
-    if (!r) r = to_device(&pair, o.pair.data(), o.pair.size() / 2);
-    if (!r) r = to_device(&coff, o.colour_off.data(), o.colour_off.size());
-    if (r) { dfree(shape); dfree(box); dfree(foff); dfree(fidx); dfree(pair); dfree(coff); return r; }
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    // the new lists first, in a part of their own: a failed allocation leaves the context as it was
+    RzPhysics::Contacts k;
+    if (int r = to_device(&k.shape.p, o.shape.data(), t.n_bodies)) return r;
+    if (mode >= 2)
+        if (int r = to_device(&k.box.p, o.box.data(), t.n_bodies)) return r;
+    if (int r = to_device(&k.follow_off.p, o.follow_off.data(), o.follow_off.size())) return r;
+    if (int r = to_device(&k.follow_idx.p, o.follow_idx.data(), o.follow_idx.size())) return r;
+    if (int r = to_device(&k.pair.p, o.pair.data(), o.pair.size() / 2)) return r;
+    if (int r = to_device(&k.colour_off.p, o.colour_off.data(), o.colour_off.size())) return r;
+    k.follow = (uint32_t)o.n_follow; k.pairs = (uint32_t)o.n_pairs; k.ncol = (uint32_t)o.ncol; k.boxes = (uint32_t)o.boxes;
+    k.box_pairs = (uint32_t)o.box_pairs; k.box_box = (uint32_t)o.n_box_box;
+    k.mode = mode;
+    if (int r = drain(c)) return r;
     drop_graph(c);
-    free_contacts(c);
-    c->ph_c_shape = shape; c->ph_c_box = box; c->ph_c_follow_off = foff; c->ph_c_follow_idx = fidx; c->ph_c_pair = pair; c->ph_c_colour_off = coff;
-    c->ph_c_follow = (uint32_t)o.n_follow; c->ph_c_pairs = (uint32_t)o.n_pairs; c->ph_c_ncol = (uint32_t)o.ncol; c->ph_c_boxes = (uint32_t)o.boxes;
-    c->ph_c_box_pairs = (uint32_t)o.box_pairs; c->ph_c_box_box = (uint32_t)o.n_box_box;
-    c->ph_contacts = mode;
+    c->ph.contacts = std::move(k);      // (k leaves with the old lists)
     return RZ_OK;
 }
 
@@ -237,31 +200,28 @@ int rz_physics_springs(rz_ctx *c, uint32_t on)
     if (int r = use(c)) return r;
     if (int r = physics_usable(c, "rz_physics_springs")) return r;
     if (!on) {
-        if (!c->ph_springs) return RZ_OK;
-        HIP_TRY(hipStreamSynchronize(c->up_stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!c->ph.springs.on) return RZ_OK;
+        if (int r = drain(c)) return r;
         drop_graph(c);
-        free_springs(c);
+        c->ph.springs = {};
         return RZ_OK;
     }
-    const size_t nj = c->ph_nj;
-    const bool have = c->ph_spring_pos.size() == nj * 3;          // (empty: the column was NULL)
+    const float *column = c->ph.kept.view().spring_position3;
     rzphys::Linear o;
-    if (have) rzphys::build_linear(c->ph_spring_pos.data(), c->ph_order, c->ph_hd, o);
+    if (column) rzphys::build_linear(column, c->ph.order, c->ph.hd, o);
     bool invalid = false;
-    const std::string bad = rzphys::springs_refusal((int)c->ph_nb, (int)nj, c->ph_block, have, o.axes, invalid);
+    const std::string bad = rzphys::springs_refusal((int)c->ph.nb, (int)c->ph.nj, c->ph.block, column != nullptr, o.axes, invalid);
     if (!bad.empty()) return fail(invalid ? RZ_ERR_INVALID : RZ_ERR_UNSUPPORTED, "%s", bad.c_str());
-    // the new records first: a failed allocation leaves the context as it was. A table without a spring axis keeps the old kernels
-    float4 *lin = nullptr;
+    // the new records first, in a part of their own: a failed allocation leaves the context as it was. A table without a spring axis keeps
+    // the old kernels
+    RzPhysics::Springs s;
     if (o.axes)
-        if (int r = to_device(&lin, o.rec.data(), nj)) return r;
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int r = to_device(&s.lin.p, o.rec.data(), c->ph.nj)) return r;
+    s.axes = (uint32_t)o.axes;
+    s.on = 1;
+    if (int r = drain(c)) return r;
     drop_graph(c);
-    free_springs(c);
-    c->ph_lin = lin;
-    c->ph_spring_axes = (uint32_t)o.axes;
-    c->ph_springs = 1;
+    c->ph.springs = std::move(s);
     return RZ_OK;
 }
 
@@ -270,7 +230,7 @@ int rz_physics_reset(rz_ctx *c)
     if (int r = use(c)) return r;
     if (int r = physics_usable(c, "rz_physics_reset")) return r;
     if (!c->pose_set || !c->pose_local || !c->has_topology) {       // nothing to stand the bodies on yet: the next step does it
-        c->ph_reset = true;
+        c->ph.reset = true;
         c->ovr_count = 0;
         return RZ_OK;
     }
@@ -280,15 +240,15 @@ int rz_physics_reset(rz_ctx *c)
 int rz_read_physics(rz_ctx *c, uint32_t instance, float *state13)
 {
     if (int r = use(c)) return r;
-    if (!c->ph_nb) return fail(RZ_ERR_INVALID, "rz_read_physics: no physics table is resident (rz_upload_physics)");
+    const RzPhysics &ph = c->ph;
+    if (!ph.nb) return fail(RZ_ERR_INVALID, "rz_read_physics: no physics table is resident (rz_upload_physics)");
     if (!state13) return fail(RZ_ERR_INVALID, "rz_read_physics: null output");
-    if (!c->ph_state || c->ph_reset || instance >= c->ph_I)
-        return fail(RZ_ERR_INVALID, "rz_read_physics: instance %u has no state (%u instance(s) stepped; rz_physics_step or rz_physics_reset first)", instance, c->ph_reset ? 0u : c->ph_I);
-    HIP_TRY(hipStreamSynchronize(c->up_stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::vector<float> rec((size_t)c->ph_nb * 16);
-    HIP_TRY(hipMemcpy(rec.data(), c->ph_state + (size_t)instance * c->ph_nb * 4, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (uint32_t b = 0; b < c->ph_nb; ++b) {
+    if (!ph.state || ph.reset || instance >= ph.I)
+        return fail(RZ_ERR_INVALID, "rz_read_physics: instance %u has no state (%u instance(s) stepped; rz_physics_step or rz_physics_reset first)", instance, ph.reset ? 0u : ph.I);
+    if (int r = drain(c)) return r;
+    std::vector<float> rec((size_t)ph.nb * 16);
+    HIP_TRY(hipMemcpy(rec.data(), ph.state.p + (size_t)instance * ph.nb * 4, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (uint32_t b = 0; b < ph.nb; ++b) {
         const float *r = rec.data() + (size_t)b * 16;
         float *o = state13 + (size_t)b * 13;
         o[0] = r[0]; o[1] = r[1]; o[2] = r[2];

@@ -1,7 +1,9 @@
 // physics_table.h — the host half of rz_upload_physics that needs no GPU: checking a table, colouring its joints and deriving the constants
-// rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams). Plain C++ on purpose, without HIP: tests/physics_table_main.cpp compiles it
-// alone and holds the colouring to tests/physics_ref.py. Everything is computed in double from the table's floats and rounded once, as
-// physics_ref.prepare does.
+// rz_physics_kernel runs on (deform_kernels.h: RzPhysicsParams); the owned copy of the columns later stages derive from (Kept); the solver's
+// LDS arithmetic with its one limit (kLdsLimit, lds_bytes: host and launcher both read them here) and what is refused over it
+// (upload_refusal, springs_refusal); the linear springs' records. Plain C++ on purpose, without HIP: tests/physics_table_main.cpp compiles it
+// alone and holds it to tests/physics_ref.py and tests/spring_ref.py. Everything is computed in double from the table's floats and rounded
+// once, as physics_ref.prepare does.
 #pragma once
 #include "../../include/reze_deform.h"
 
@@ -208,9 +210,38 @@ inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const
     }
 }
 
-// ---- the linear springs (rz_physics_springs; tests/spring_ref.py) ----
+// The columns of an uploaded table that later stages derive from (rz_physics_contacts: contact_table.h; rz_physics_springs: build_linear),
+// owned. view() is that table again: its pointers are these vectors, or null where the column was not uploaded (or has no element).
+struct Kept {
+    uint32_t n_bodies = 0, n_joints = 0;
+    std::vector<uint8_t> type, shape, group;
+    std::vector<uint16_t> mask;
+    std::vector<float> size3, mass, friction, spring_position3;
 
-constexpr size_t kLdsLimit = 160 * 1024;
+    void keep(const rz_physics *t)
+    {
+        const size_t nb = n_bodies = t->n_bodies, nj = n_joints = t->n_joints;
+        copy(type, t->type, nb); copy(shape, t->shape, nb); copy(group, t->group, nb); copy(mask, t->mask, nb);
+        copy(size3, t->size3, nb * 3); copy(mass, t->mass, nb); copy(friction, t->friction, nb); copy(spring_position3, t->spring_position3, nj * 3);
+    }
+    rz_physics view() const
+    {
+        rz_physics t;
+        memset(&t, 0, sizeof t);
+        t.n_bodies = n_bodies; t.n_joints = n_joints;
+        t.type = ptr(type); t.shape = ptr(shape); t.group = ptr(group); t.mask = ptr(mask);
+        t.size3 = ptr(size3); t.mass = ptr(mass); t.friction = ptr(friction); t.spring_position3 = ptr(spring_position3);
+        return t;
+    }
+
+private:
+    template <class T> static void copy(std::vector<T> &to, const T *from, size_t n) { if (from) to.assign(from, from + n); else to.clear(); }
+    template <class T> static const T *ptr(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+};
+
+// ---- the solver's LDS, and the linear springs (rz_physics_springs; tests/spring_ref.py) ----
+
+constexpr size_t kLdsLimit = 160 * 1024;   // what one workgroup of rz_physics_kernel may take: the only spelling of it
 // lanes per workgroup, chosen at upload: 64 when the bodies and the widest colour fit one wave, else 256 (unmeasured: DESIGN.md 9.7)
 inline int block_for(int n_bodies, int widest) { return n_bodies <= 64 && widest <= 64 ? 64 : 256; }
 // LDS of one workgroup: 96 B per body; once the joints outnumber the lanes their multipliers live there too, 12 B per joint, 24 B with the
@@ -259,6 +290,25 @@ inline std::string springs_refusal(int n_bodies, int n_joints, int block, bool h
         return m;
     }
     return "";
+}
+
+// What rz_upload_physics refuses of a valid table as too large (RZ_ERR_UNSUPPORTED), "" = nothing. o null: before the table is built, the cap on
+// the counts alone (nothing of that size is coloured first); otherwise the LDS its launch form takes.
+inline std::string upload_refusal(uint32_t n_bodies, uint32_t n_joints, const Built *o)
+{
+    char m[320];
+    if (!o) {
+        if (n_bodies <= (1u << 20) && n_joints <= (1u << 20)) return "";
+        snprintf(m, sizeof m, "physics table too large for the device solver: %u bodies and %u joints (96 B of LDS per body, + 12 B per joint once the joints outnumber the lanes; the limit is 160 KB)",
+                 n_bodies, n_joints);
+        return m;
+    }
+    const int block = block_for(o->nb, o->widest);
+    const size_t lds = lds_bytes(o->nb, o->nj, block, false);
+    if (lds <= kLdsLimit) return "";
+    snprintf(m, sizeof m, "physics table too large for the device solver: %u bodies and %u joints need %zu B of LDS (96 B per body, + 12 B per joint once the joints outnumber the %d lanes; the limit is 160 KB)",
+             n_bodies, n_joints, lds, block);
+    return m;
 }
 
 }  // namespace rzphys

@@ -54,8 +54,7 @@ extern "C" {
 static int stage_acquire(rz_ctx *c, size_t need, int *slot_out)
 {
     if (need > c->stage_bytes || !c->stage[0]) {
-        HIP_TRY(hipStreamSynchronize(c->up_stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int r = drain(c)) return r;
         need = (need + 4095) / 4096 * 4096;
         for (int i = 0; i < kStageSlots; ++i) {
             if (c->stage[i]) { (void)hipHostFree(c->stage[i]); c->stage[i] = nullptr; c->stage_dev[i] = nullptr; }
@@ -90,8 +89,7 @@ static int stage_acquire(rz_ctx *c, size_t need, int *slot_out)
 static int zc_acquire(rz_ctx *c, size_t need, int *slot_out)
 {
     if (need > c->zc_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->up_stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int r = drain(c)) return r;
         drop_graph(c);
         const size_t hdr_off = (need + 63) / 64 * 64;
         for (int i = 0; i < rz_ctx::kZcSlots; ++i) {
@@ -258,8 +256,7 @@ static int big_acquire(rz_ctx *c, float **block)
     const size_t need = (size_t)c->pose_alloc_I * c->pose_alloc_B * 16 + (((size_t)c->pose_alloc_I * std::max<size_t>(c->pose_alloc_M, Mq) + 3) / 4 * 4) +
                         (size_t)c->pose_alloc_I * c->pose_alloc_B * 7 + 4;
     if (!c->big_blk[0] || c->big_floats < need) {
-        HIP_TRY(hipStreamSynchronize(c->up_stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int r = drain(c)) return r;
         drop_graph(c);
         free_big_ring(c);
         for (uint64_t k = 0; k < N; ++k) {
@@ -658,8 +655,7 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
     const bool inline_state = c->I == 1 && !piped && !c->overlap_on && c->t_zerocopy != 0;      // (the rule of frames_inline)
     if (!inline_state) {
         if (c->I > c->mo_states_alloc) {
-            HIP_TRY(hipStreamSynchronize(c->up_stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (int r = drain(c)) return r;
             dfree(c->mo_states);
             HIP_TRY(hipMalloc(&c->mo_states, (size_t)c->I * sizeof(RzMotionState)));
             c->mo_states_alloc = c->I;
@@ -711,7 +707,7 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
 int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16)
 {
     if (int r = use(c)) return r;
-    if (c->ph_nb) return fail(RZ_ERR_INVALID, "rz_override_world while a physics table is resident: rz_physics_step writes the override table (remove the table with rz_upload_physics(ctx, NULL) first)");
+    if (c->ph.nb) return fail(RZ_ERR_INVALID, "rz_override_world while a physics table is resident: rz_physics_step writes the override table (remove the table with rz_upload_physics(ctx, NULL) first)");
     if (n == 0) { c->ovr_count = 0; return RZ_OK; }
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_override_world applies to device-solved poses: call rz_upload_skeleton_topology first");
     if (!bone || !world16) return fail(RZ_ERR_INVALID, "null override arrays");
@@ -740,8 +736,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
     for (uint32_t i = 0; i < c->I; ++i) off[i + 1] += off[i];
     const size_t m = bones.size();
     if (m > c->ovr_alloc || off.size() > c->ovr_off_alloc) {
-        HIP_TRY(hipStreamSynchronize(c->up_stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int r = drain(c)) return r;
         drop_graph(c);
         dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
         c->ovr_alloc = std::max<size_t>(m, 64); c->ovr_off_alloc = off.size();
@@ -779,8 +774,7 @@ int rz_read_world(rz_ctx *c, uint32_t instance, float *world16)
     if (solve_on_demand(c)) {                           // a crowd frame that solved its hierarchy in LDS only: the solve as a kernel of its own, now
         if (int r = launch_fk(c, c->stream)) return r;
     }
-    HIP_TRY(hipStreamSynchronize(c->up_stream));        // rz_fk_kernel may have written them on the front stream
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int r = drain(c)) return r;        // rz_fk_kernel may have written them on the front stream
     HIP_TRY(hipMemcpy(world16, c->world + (size_t)instance * c->B * 16, (size_t)c->B * 16 * sizeof(float), hipMemcpyDeviceToHost));
     return RZ_OK;
 }

@@ -247,23 +247,23 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef_n;
     else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
     else if (!strcmp(key, "motion_clips")) *value = (int)c->mo_clips;
-    else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph_nb;
-    else if (!strcmp(key, "physics_joints")) *value = (int)c->ph_nj;
-    else if (!strcmp(key, "physics_colours")) *value = (int)c->ph_ncol;
+    else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph.nb;
+    else if (!strcmp(key, "physics_joints")) *value = (int)c->ph.nj;
+    else if (!strcmp(key, "physics_colours")) *value = (int)c->ph.ncol;
     // the form rz_launch_physics takes for the resident table (kernels/physics.hip): lanes per workgroup, joints kept in registers (1) or
     // strided over a colour (0), dynamic LDS per workgroup; all 0 without a table
-    else if (!strcmp(key, "physics_block")) *value = c->ph_nb ? c->ph_block : 0;
-    else if (!strcmp(key, "physics_own")) *value = (c->ph_nb && (int)c->ph_nj <= c->ph_block) ? 1 : 0;
-    else if (!strcmp(key, "physics_contacts")) *value = c->ph_contacts;
-    else if (!strcmp(key, "physics_contact_follow")) *value = (int)c->ph_c_follow;
-    else if (!strcmp(key, "physics_contact_pairs")) *value = (int)c->ph_c_pairs;
-    else if (!strcmp(key, "physics_contact_colours")) *value = (int)c->ph_c_ncol;
-    else if (!strcmp(key, "physics_contact_boxes")) *value = (int)c->ph_c_boxes;
-    else if (!strcmp(key, "physics_contact_box_pairs")) *value = (int)c->ph_c_box_pairs;
-    else if (!strcmp(key, "physics_contact_box_box")) *value = (int)c->ph_c_box_box;
-    else if (!strcmp(key, "physics_springs")) *value = c->ph_springs;
-    else if (!strcmp(key, "physics_spring_axes")) *value = (int)c->ph_spring_axes;
-    else if (!strcmp(key, "physics_lds")) *value = c->ph_nb ? (int)rz_physics_lds_bytes((int)c->ph_nb, (int)c->ph_nj, c->ph_block, c->ph_lin != nullptr) : 0;
+    else if (!strcmp(key, "physics_block")) *value = c->ph.nb ? c->ph.block : 0;
+    else if (!strcmp(key, "physics_own")) *value = (c->ph.nb && (int)c->ph.nj <= c->ph.block) ? 1 : 0;
+    else if (!strcmp(key, "physics_contacts")) *value = c->ph.contacts.mode;
+    else if (!strcmp(key, "physics_contact_follow")) *value = (int)c->ph.contacts.follow;
+    else if (!strcmp(key, "physics_contact_pairs")) *value = (int)c->ph.contacts.pairs;
+    else if (!strcmp(key, "physics_contact_colours")) *value = (int)c->ph.contacts.ncol;
+    else if (!strcmp(key, "physics_contact_boxes")) *value = (int)c->ph.contacts.boxes;
+    else if (!strcmp(key, "physics_contact_box_pairs")) *value = (int)c->ph.contacts.box_pairs;
+    else if (!strcmp(key, "physics_contact_box_box")) *value = (int)c->ph.contacts.box_box;
+    else if (!strcmp(key, "physics_springs")) *value = c->ph.springs.on;
+    else if (!strcmp(key, "physics_spring_axes")) *value = (int)c->ph.springs.axes;
+    else if (!strcmp(key, "physics_lds")) *value = c->ph.nb ? (int)rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0;
     else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;

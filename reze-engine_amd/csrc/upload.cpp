@@ -263,7 +263,7 @@ int rz_set_instances(rz_ctx *c, uint32_t I)
         drop_graph(c);
         c->aabb_rearm = true;
         c->ovr_count = 0;                 // overrides name (instance, bone) pairs of the old crowd
-        c->ph_reset = true;               // (a physics table rebuilds its per-instance state and the overrides at its next step)
+        c->ph.reset = true;               // (a physics table rebuilds its per-instance state and the overrides at its next step)
         // The host-compacted active-morph list is only maintained while I == 1 (upload_pose). Coming back to one instance
         // from a crowd it is stale (zeroed): let the prep kernel compact instance 0's weights, which are still on the device.
         if (c->M > 0 && c->morph_mode == 1) c->ml.count = -1;

@@ -1,6 +1,9 @@
 """Synthetic skeletons with rigid-body tables for the physics tests (tests/test_physics_cpu.py, tests/test_gpu_physics.py): strands of
 dynamic bodies hanging from bodies that follow their bones, as hair, ribbons and skirts are rigged in PMX models. Every scene the GPU tests
 use is listed in SCENES and checked for conditioning on the CPU (test_physics_cpu.py: test_scenes_are_well_conditioned)."""
+import os
+import subprocess
+
 import numpy as np
 
 import ik_ref
@@ -432,3 +435,30 @@ def conditioning(scene, poses, calls=CALLS, chains=()):
     for (wa, sa), (wb, sb) in zip(a, b):
         worst = max(worst, float(np.abs(wa - wb).max()), float(np.abs(sa[:, :3] - sb[:, :3]).max()))
     return worst / scene["extent"]
+
+
+# ---- the host half's stand-alone program (tests/physics_table_main.cpp around reze-engine_amd/csrc/physics_table.h) ----
+
+def build_table_tool(folder):
+    """the table program under ASan and UBSan"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(folder / "physics_table_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           os.path.join(root, "tests", "physics_table_main.cpp")])
+    return exe
+
+
+def dump_table(t, parents, bind, column=True):
+    """the program's input for table t; column=False: spring_position is written, and handed on as NULL"""
+    rows = ["%d %d %d %.9g %d %d %d" % (len(parents), t["n_bodies"], t["n_joints"], float(t["h"]), t["iterations"], 0 if t["gravity"] is None else 1, 1 if column else 0)]
+    if t["gravity"] is not None:
+        rows.append(" ".join("%.9g" % x for x in t["gravity"]))
+    rows.append(" ".join(str(int(p)) for p in parents))
+    rows.append(" ".join("%.9g" % x for x in np.asarray(bind, dtype=np.float32).reshape(-1)))
+    for b in range(t["n_bodies"]):
+        rows.append(" ".join([str(int(t["bone"][b])), str(int(t["type"][b])), str(int(t["shape"][b]))] + ["%.9g" % x for x in
+                    list(t["size"][b]) + list(t["offset_pos"][b]) + list(t["offset_rot"][b]) + [t["mass"][b], t["linear_damping"][b], t["angular_damping"][b]]]))
+    for j in range(t["n_joints"]):
+        rows.append(" ".join([str(int(t["body_a"][j])), str(int(t["body_b"][j]))] + ["%.9g" % x for k in
+                    ("position", "rotation", "position_min", "position_max", "rotation_min", "rotation_max", "spring_rotation", "spring_position") for x in t[k][j]]))
+    return "\n".join(rows) + "\n"

@@ -314,26 +314,9 @@ def test_engine_device_physics_option_with_a_recording_addon(tmp_path):
     assert r["plain"] == ["topology", "setPoseLocal", "deform", "setPoseLocal", "deform"]
 
 
-def dump_table(t, parents, bind):
-    rows = ["%d %d %d %.9g %d %d" % (len(parents), t["n_bodies"], t["n_joints"], float(t["h"]), t["iterations"], 0 if t["gravity"] is None else 1)]
-    if t["gravity"] is not None:
-        rows.append(" ".join("%.9g" % x for x in t["gravity"]))
-    rows.append(" ".join(str(int(p)) for p in parents))
-    rows.append(" ".join("%.9g" % x for x in np.asarray(bind, dtype=np.float32).reshape(-1)))
-    for b in range(t["n_bodies"]):
-        rows.append(" ".join([str(int(t["bone"][b])), str(int(t["type"][b])), str(int(t["shape"][b]))] + ["%.9g" % x for x in
-                    list(t["size"][b]) + list(t["offset_pos"][b]) + list(t["offset_rot"][b]) + [t["mass"][b], t["linear_damping"][b], t["angular_damping"][b]]]))
-    for j in range(t["n_joints"]):
-        rows.append(" ".join([str(int(t["body_a"][j])), str(int(t["body_b"][j]))] + ["%.9g" % x for k in
-                    ("position", "rotation", "position_min", "position_max", "rotation_min", "rotation_max", "spring_rotation") for x in t[k][j]]))
-    return "\n".join(rows) + "\n"
-
-
 @pytest.fixture(scope="module")
 def table_tool(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("physics_table") / "physics_table_main")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "physics_table_main.cpp")])
-    return exe
+    return ps.build_table_tool(tmp_path_factory.mktemp("physics_table"))
 
 
 @pytest.mark.parametrize("name", ["crowd", "63 bodies", "wide colour", "one body", "ik", "params", "params gravity", "contents", "gimbal", "64 joints", "65 joints",
@@ -343,7 +326,7 @@ def test_upload_colours_and_derives_what_the_reference_does(table_tool, name):
     records; with "contents": bone = -1, a zero inertia, dampings of 0 and 1 and limits given max first"""
     sc = ps.scene(name)
     t = sc["table"]
-    out = subprocess.run([table_tool], input=dump_table(t, sc["parents"], sc["bind"]), capture_output=True, text=True, check=True).stdout
+    out = subprocess.run([table_tool], input=ps.dump_table(t, sc["parents"], sc["bind"]), capture_output=True, text=True, check=True).stdout
     rows = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1].split() if " " in ln else [] for ln in out.strip().split("\n")}
     assert rows["valid"][0] == "1", out[:200]
     colour, order, ncol = pr.colouring(t)
@@ -383,5 +366,5 @@ def test_upload_validation_messages(table_tool):
         t = copy.deepcopy(sc["table"])
         t[key][idx] = val
         assert pr.validate(t, sc["B"]) is not None
-        out = subprocess.run([table_tool], input=dump_table(t, sc["parents"], sc["bind"]), capture_output=True, text=True, check=True).stdout
+        out = subprocess.run([table_tool], input=ps.dump_table(t, sc["parents"], sc["bind"]), capture_output=True, text=True, check=True).stdout
         assert out.startswith("valid 0") and word in out, out[:200]
