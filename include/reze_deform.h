@@ -297,6 +297,38 @@ int rz_set_pose_sampled(rz_ctx *ctx, const float *frames);
 typedef struct rz_motion_state { uint32_t clip_a; float frame_a; uint32_t clip_b; float frame_b; float blend; } rz_motion_state;
 int rz_upload_motions(rz_ctx *ctx, uint32_t n_clips, const rz_animation *clips);
 int rz_set_pose_blended(rz_ctx *ctx, const rz_motion_state *states);
+/* ---- layers on top of the cross-fade: bone / morph masks, additive clips — NEW (optional) ----
+ * rz_set_pose_layered poses instance i from base[i] exactly as rz_set_pose_blended does, then applies layers[i][0 .. n_layers) in order
+ * (n_layers <= RZ_MAX_MOTION_LAYERS), each one clip of the library at its own frame with a weight, an optional mask and a mode
+ * (tests/layer_ref.py is the definition):
+ *   1. (q, t, w) is what rz_set_pose_blended defines for base[i].
+ *   2. A layer with clip == RZ_NO_CLIP or weight == 0 is skipped as a whole: its other fields are not read (a non-finite frame is legal).
+ *   3. Otherwise L = sample(clip, frame), the library's sampler. The layer acts on bone b only when the clip keys b (a track with at least
+ *      one key) AND the mask includes b (RZ_NO_MASK includes everything):
+ *        RZ_LAYER_OVERRIDE   q = Quat.slerp(q, qL, weight),  t = t + (tL - t) * weight;  at weight == 1 q and t ARE qL and tL
+ *        RZ_LAYER_ADDITIVE   q = Quat.multiply(q, Quat.slerp(identity, qL, weight)),  t = t + tL * weight   (the forms bone morphs use;
+ *                            nothing is renormalised beyond what those forms do)
+ *   4. The layer acts on vertex morph m only when at least one of m's feeds in that clip holds a key AND the mask includes m (masks
+ *      uploaded without morph masks include every morph); wL = the effective weight (own track, then group feeds):
+ *        OVERRIDE   w = w + (wL - w) * weight, at weight == 1 w IS wL;   ADDITIVE   w = w + wL * weight
+ *   5. n_layers == 0, or every layer skipped, gives the bits of rz_set_pose_blended(base).
+ * The result is written where rz_set_pose_blended writes it (rz_motion_layer_kernel, once per call, same pose block, stream and event);
+ * every frame behind it is an rz_set_pose_local frame and replays do not sample again. One character's state and layers ride in the
+ * kernel arguments (100 bytes), a crowd's I x (20 + 20 n_layers) bytes go through a slot of the pinned ring.
+ * rz_upload_motion_masks: n_masks masks, one byte per bone (non-zero = included), and optionally one byte per vertex morph; static data
+ * like the library (forks see it; refused while forks exist; a new skeleton drops it; n_masks = 0 removes it;
+ * rz_get_tuning("motion_masks") = the count). The masks are built for the morph set resident at upload: with a set of another size
+ * rz_set_pose_layered refuses masked layers until they are uploaded again.
+ * rz_set_pose_layered refuses (RZ_ERR_INVALID, the resident pose untouched, instance and layer named) whatever rz_set_pose_blended refuses
+ * of base, n_layers > RZ_MAX_MOTION_LAYERS, layers == NULL with n_layers > 0, and a layer that is not skipped with a clip >= n_clips, a
+ * mask >= n_masks (other than RZ_NO_MASK), a mode > 1, a weight that is not finite or not in [0, 1], or a non-finite frame. It cancels an
+ * outstanding rz_map_pose mapping. The ABI version stays 8: bindings detect the symbols. */
+#define RZ_MAX_MOTION_LAYERS 4
+#define RZ_NO_MASK 0xffffffffu
+enum { RZ_LAYER_OVERRIDE = 0, RZ_LAYER_ADDITIVE = 1 };
+typedef struct rz_motion_layer { uint32_t clip; float frame; float weight; uint32_t mask; uint32_t mode; } rz_motion_layer; /* 20 B */
+int rz_upload_motion_masks(rz_ctx *ctx, uint32_t n_masks, const uint8_t *bone_mask /* [n_masks][B] */, const uint8_t *morph_mask /* [n_masks][M] or NULL */);
+int rz_set_pose_layered(rz_ctx *ctx, const rz_motion_state *base /* [I] */, uint32_t n_layers, const rz_motion_layer *layers /* [I][n_layers] */);
 /* ---- physics hand-off for device-solved poses ----
  * updateModelPose()  engine/src/engine.ts:2375-2381: between evaluatePose() and the world-matrix upload the reference
  * lets physics overwrite the world matrices of rigid-body-driven bones IN PLACE (physics.ts:715-751,

@@ -21,17 +21,21 @@ SYMBOLS = [
     "rz_autotune_apply", "rz_output_ptrs",
     "rz_comm_unique_id", "rz_rccl_info", "rz_comm_info", "rz_comm_init", "rz_allgather", "rz_read_gathered", "rz_comm_init_all", "rz_allgather_all", "rz_gather_direct", "rz_gather_fence", "rz_upload_edge_scale", "rz_read_hull", "rz_enable_aabb", "rz_read_aabb",
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
-    "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
+    "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
-# points, rz_physics_contacts and rz_physics_springs — detected by the symbol, the version stayed 8)
+# points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks and rz_set_pose_layered — detected by the symbol, the version
+# stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
-                    "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended",
+                    "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
                     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
+NO_MASK = 0xffffffff
+MAX_MOTION_LAYERS = 4
+LAYER_OVERRIDE, LAYER_ADDITIVE = 0, 1
 
 
 class RzAnimation(ctypes.Structure):
@@ -49,6 +53,11 @@ class RzMotionState(ctypes.Structure):
                 ("blend", ctypes.c_float)]
 
 
+class RzMotionLayer(ctypes.Structure):
+    _fields_ = [("clip", ctypes.c_uint32), ("frame", ctypes.c_float), ("weight", ctypes.c_float), ("mask", ctypes.c_uint32),
+                ("mode", ctypes.c_uint32)]
+
+
 class RzPhysics(ctypes.Structure):
     _f, _u8, _u32 = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
     _fields_ = [("n_bodies", ctypes.c_uint32), ("bone", ctypes.POINTER(ctypes.c_int32)), ("type", _u8), ("shape", _u8),
@@ -61,6 +70,9 @@ class RzPhysics(ctypes.Structure):
 
 # the same 20 bytes as a numpy record (set_pose_blended packs a crowd's states with it)
 MOTION_STATE_DTYPE = np.dtype([("clip_a", "<u4"), ("frame_a", "<f4"), ("clip_b", "<u4"), ("frame_b", "<f4"), ("blend", "<f4")])
+
+# the 20-byte rz_motion_layer as a numpy record (set_pose_layered packs [I, n_layers] of them)
+MOTION_LAYER_DTYPE = np.dtype([("clip", "<u4"), ("frame", "<f4"), ("weight", "<f4"), ("mask", "<u4"), ("mode", "<u4")])
 
 
 def _animation_struct(a, keep, track_bone, key_off, key_frame, key_rot, key_pos, key_interp=None,
@@ -200,6 +212,9 @@ def load(path=None):
     if hasattr(L, "rz_upload_motions"):        # (ABI 8 still: the feature is detected by the symbols)
         L.rz_upload_motions.argtypes = [vp, u32, ctypes.POINTER(RzAnimation)]
         L.rz_set_pose_blended.argtypes = [vp, ctypes.POINTER(RzMotionState)]
+    if hasattr(L, "rz_set_pose_layered"):      # (ABI 8 still: the feature is detected by the symbols)
+        L.rz_upload_motion_masks.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)]
+        L.rz_set_pose_layered.argtypes = [vp, ctypes.POINTER(RzMotionState), u32, ctypes.POINTER(RzMotionLayer)]
     if hasattr(L, "rz_upload_ik"):             # (ABI 8 still: the feature is detected by the symbol)
         u8p = ctypes.POINTER(ctypes.c_uint8)
         L.rz_upload_ik.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32), fp, ctypes.POINTER(u32), ctypes.POINTER(u32), u8p, fp, fp]
@@ -523,6 +538,55 @@ class DeformContext:
         st = self.pack_motion_states(self.I, clip_a, frame_a, clip_b, frame_b, blend)
         self._chk(self._L.rz_set_pose_blended(self._h, st.ctypes.data_as(ctypes.POINTER(RzMotionState))))
 
+    def upload_motion_masks(self, bone_masks, morph_masks=None):
+        """The masks of layered poses (rz_upload_motion_masks): bone_masks [n_masks, B], non-zero = the mask includes the bone; optionally
+        morph_masks [n_masks, M] for the vertex morphs (None: every mask includes every morph). No masks removes them."""
+        if not hasattr(self._L, "rz_upload_motion_masks"):
+            raise RzError(-6, "this build of the library has no rz_upload_motion_masks")
+        bm = np.ascontiguousarray(np.asarray(bone_masks) != 0, dtype=np.uint8)
+        if bm.size == 0:
+            self._chk(self._L.rz_upload_motion_masks(self._h, 0, None, None))
+            return
+        bm = np.atleast_2d(bm)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        mm = None
+        if morph_masks is not None:
+            mm = np.ascontiguousarray(np.atleast_2d(np.asarray(morph_masks) != 0), dtype=np.uint8)
+            assert mm.shape[0] == bm.shape[0], "one morph mask per bone mask"
+        self._chk(self._L.rz_upload_motion_masks(self._h, bm.shape[0], bm.ctypes.data_as(u8p), None if mm is None or mm.size == 0 else mm.ctypes.data_as(u8p)))
+
+    @staticmethod
+    def pack_motion_layers(n, layers):
+        """[n, n_layers] records of MOTION_LAYER_DTYPE from a record array of that shape, or from a list of n per-instance lists of dicts
+        (clip, frame, weight = 1, mask = None, mode = 0 or additive = False; shorter lists are padded with skipped layers)."""
+        if isinstance(layers, np.ndarray) and layers.dtype == MOTION_LAYER_DTYPE:
+            out = np.ascontiguousarray(layers)
+            return out.reshape(n, -1) if out.size else out.reshape(n, 0)
+        rows = [list(r) for r in layers]
+        assert len(rows) == n, "%d layer lists for %d instances" % (len(rows), n)
+        out = np.zeros((n, max([len(r) for r in rows] + [0])), dtype=MOTION_LAYER_DTYPE)
+        out["clip"] = NO_CLIP
+        for i, r in enumerate(rows):
+            for l, d in enumerate(r):
+                clip, mask = d.get("clip"), d.get("mask")
+                mode = d.get("mode", LAYER_ADDITIVE if d.get("additive") else LAYER_OVERRIDE)
+                out[i, l] = (NO_CLIP if clip is None or clip < 0 else clip, d.get("frame", 0.0), d.get("weight", 1.0),
+                             NO_MASK if mask is None or mask < 0 else mask, mode)
+        return out
+
+    def set_pose_layered(self, base, layers):
+        """base: [I] records of MOTION_STATE_DTYPE (pack_motion_states); layers: [I, n_layers] records of MOTION_LAYER_DTYPE or a list of
+        per-instance lists of dicts (pack_motion_layers). Instance i is posed from base[i] as set_pose_blended poses it, then its layers
+        are applied in order on the GPU (rz_set_pose_layered)."""
+        if not hasattr(self._L, "rz_set_pose_layered"):
+            raise RzError(-6, "this build of the library has no rz_set_pose_layered")
+        st = np.ascontiguousarray(base, dtype=MOTION_STATE_DTYPE).reshape(-1)
+        assert st.size == self.I, "%d states for %d instances" % (st.size, self.I)
+        ly = self.pack_motion_layers(self.I, layers)
+        n = ly.shape[1]
+        self._chk(self._L.rz_set_pose_layered(self._h, st.ctypes.data_as(ctypes.POINTER(RzMotionState)), n,
+                                              ly.ctypes.data_as(ctypes.POINTER(RzMotionLayer)) if n else None))
+
     def set_pose_sampled(self, frames):
         """One (fractional, 30 fps) frame per instance; bones, morph weights and the hierarchy are evaluated on the GPU."""
         f = _f32(np.atleast_1d(frames)).reshape(-1)
@@ -717,7 +781,8 @@ class DeformContext:
         converted and every pointer built up front — for timing per-frame loops without numpy conversions in them
         (bench.py, tools/live_loop.py). kind: 'world' (rz_set_pose), 'local' (rz_set_pose_local), 'sampled'
         (rz_set_pose_sampled; `primary` = a [T, I] table of frame numbers that is cycled through), 'blended' (rz_set_pose_blended; a [T, I]
-        table of motion states). Returns (call, check)."""
+        table of motion states), 'layered' (rz_set_pose_layered; a pair of tables, states [T, I] and layers [T, I, n_layers]). Returns
+        (call, check)."""
         L, h = self._L, self._h
         keep = []
 
@@ -750,6 +815,21 @@ class DeformContext:
             def call():
                 tick[0] += 1
                 if L.rz_set_pose_blended(h, table[tick[0] % len(table)]) or L.rz_deform(h):
+                    bad.append(1)
+        elif kind == "layered":
+            # `primary` = (a [T, I] table of MOTION_STATE_DTYPE records, a [T, I, n_layers] table of MOTION_LAYER_DTYPE records), cycled through
+            srows = [np.ascontiguousarray(row, dtype=MOTION_STATE_DTYPE).reshape(-1) for row in np.atleast_2d(primary[0])]
+            lrows = [np.ascontiguousarray(row, dtype=MOTION_LAYER_DTYPE).reshape(self.I, -1) for row in primary[1]]
+            keep.extend(srows + lrows)
+            n_layers = lrows[0].shape[1]
+            table = [(s.ctypes.data_as(ctypes.POINTER(RzMotionState)), l.ctypes.data_as(ctypes.POINTER(RzMotionLayer)) if n_layers else None)
+                     for s, l in zip(srows, lrows)]
+            tick = [0]
+
+            def call():
+                tick[0] += 1
+                sp, lp = table[tick[0] % len(table)]
+                if L.rz_set_pose_layered(h, sp, n_layers, lp) or L.rz_deform(h):
                     bad.append(1)
         else:
             table = [ptr(row) for row in np.atleast_2d(primary)]

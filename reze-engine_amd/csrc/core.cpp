@@ -207,6 +207,16 @@ void free_motions(rz_ctx *c)
     c->mo_clips = 0; c->mo_M = 0;
 }
 
+void free_motion_masks(rz_ctx *c)
+{
+    if (c->mk_count) {                    // rz_motion_layer_kernel reads the masks on whichever stream the pose travelled on
+        if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+    }
+    dfree(c->mk_bone_bits); dfree(c->mk_morph_bits);
+    c->mk_count = 0; c->mk_M = 0; c->mk_bone_words = 0; c->mk_morph_words = 0;
+}
+
 void free_bone_morphs(rz_ctx *c)
 {
     if (!c->bm_off) return;
@@ -358,11 +368,11 @@ int rz_destroy(rz_ctx *c)
     // RzStatic ...
     dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->inv_bind); dfree(c->edge);
     dfree(c->fk_rec); dfree(c->fk_anc_more);
-    free_animation(c); free_motions(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c);
+    free_animation(c); free_motions(c); free_motion_masks(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c);
     // ... and what the context owns
     dfree(c->rj01); dfree(c->rj23); dfree(c->sub_list); dfree(c->sub_count); dfree(c->zc_tag);
     dfree(c->subfk_rec); dfree(c->subfk_count);
-    dfree(c->an_frames); dfree(c->mo_states);
+    dfree(c->an_frames); dfree(c->mo_states); dfree(c->mo_layers);
     dfree(c->pose_blk[0]); dfree(c->pose_blk[1]);
     free_big_ring(c);
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);

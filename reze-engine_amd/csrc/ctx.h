@@ -133,6 +133,11 @@ struct RzStatic {
     uint4 *mo_feed_range = nullptr, *mo_key_interp = nullptr;
     float *mo_key_frame = nullptr, *mo_key_pos = nullptr, *mo_mkey_frame = nullptr, *mo_mkey_weight = nullptr, *mo_feed_ratio = nullptr;
     float4 *mo_key_rot = nullptr;
+    // the masks of layered poses (rz_upload_motion_masks / rz_set_pose_layered; kernels/motion_layers.hip): bit sets, one 32-bit word per 32
+    // bones / vertex morphs, mk_bone_words / mk_morph_words words per mask. mk_morph_bits null: every mask includes every morph.
+    uint32_t mk_count = 0, mk_M = 0;    // masks resident (0 = none) / vertex-morph count the morph masks were built for
+    uint32_t *mk_bone_bits = nullptr, *mk_morph_bits = nullptr;
+    uint32_t mk_bone_words = 0, mk_morph_words = 0;
     // PMX bone morphs (rz_upload_bone_morphs): entries grouped by bone, ascending morph index inside a bone
     uint32_t *bm_off = nullptr, *bm_morph = nullptr;
     float4 *bm_rot = nullptr, *bm_tr = nullptr;
@@ -215,7 +220,9 @@ struct rz_ctx : RzStatic, RzTuning {
     size_t an_frames_alloc = 0;
     RzMotionState *mo_states = nullptr; // [I] per-frame states of a crowd (this context's own, never borrowed)
     size_t mo_states_alloc = 0;
-    hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states
+    hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states (and mo_layers)
+    RzMotionLayer *mo_layers = nullptr; // [I][n_layers] per-frame layers of a crowd, behind their states on the same stream (this context's own)
+    size_t mo_layers_alloc = 0;
     float4 *local_q = nullptr;          // I x B   (current pose slot)
 
     bool pose_local = false;            // the current pose came from rz_set_pose_local
@@ -411,6 +418,7 @@ void free_big_ring(rz_ctx *c);
 int ensure_pose_buffers(rz_ctx *c);
 void free_animation(rz_ctx *c);
 void free_motions(rz_ctx *c);
+void free_motion_masks(rz_ctx *c);
 int rebuild_fk_static(rz_ctx *c);      // upload.cpp: the device block behind fk_rec from the host copies
 void free_bone_morphs(rz_ctx *c);
 void forget_search(rz_ctx *c);

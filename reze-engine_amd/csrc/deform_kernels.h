@@ -268,6 +268,28 @@ struct RzMotionParams {
 };
 hipError_t rz_launch_motion_blend(const RzMotionParams &p, uint32_t instances, hipStream_t st);
 
+// rz_motion_layer_kernel (kernels/motion_layers.hip): the cross-fade above, then up to kRzMaxLayers layers per instance — one clip each at its
+// own frame with a weight, an optional bone / morph mask and a mode (rz_upload_motion_masks / rz_set_pose_layered). It writes what
+// rz_motion_blend_kernel writes, where it writes it; rz_set_pose_blended keeps launching that kernel.
+constexpr int kRzMaxLayers = 4;
+constexpr uint32_t kRzNoMask = 0xffffffffu;
+struct RzMotionLayer {          // = rz_motion_layer of the C ABI (pose.cpp asserts the layout)
+    uint32_t clip; float frame;         // clip = kRzNoClip or weight = 0: the layer is skipped, nothing else of it is read
+    float weight;
+    uint32_t mask;                      // kRzNoMask: every bone and morph
+    uint32_t mode;                      // 0 override, 1 additive
+};
+struct RzLayerParams {
+    RzMotionParams m;               // the library, the base states ([I] or state0) and the output, as the blend kernel takes them
+    const RzMotionLayer *layers;    // [I][n_layers] on the device, or null: one character, the layers ride in the kernel arguments (layers0)
+    RzMotionLayer layers0[kRzMaxLayers];
+    int n_layers;
+    const uint32_t *bone_bits;      // [n_masks][bone_words] bit sets: bit (b & 31) of word b >> 5 = the mask includes bone b
+    const uint32_t *morph_bits;     // [n_masks][morph_words], or null: every mask includes every morph
+    int bone_words, morph_words;
+};
+hipError_t rz_launch_motion_layers(const RzLayerParams &p, uint32_t instances, hipStream_t st);
+
 // rz_physics_kernel (kernels/physics.hip): rigid bodies and joints of every instance advanced by `substeps` fixed steps, one workgroup per
 // instance, in front of the frame (rz_upload_physics / rz_physics_step). It reads the world matrices the hierarchy solve left in memory and
 // writes the solve's override table; the frame kernels see overrides, nothing else.

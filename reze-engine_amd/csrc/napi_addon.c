@@ -759,6 +759,48 @@ static napi_value fn_set_pose_blended(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+/* uploadMotionMasks(ctx, n, Uint8Array bones, Uint8Array | null morphs): the masks of layered poses (rz_upload_motion_masks), n x B bytes
+ * for the bones and, optionally, n x M for the vertex morphs (non-zero = included); n = 0 removes them */
+static napi_value fn_upload_motion_masks(napi_env env, napi_callback_info info)
+{
+    ARGS(4);
+    CTX(0);
+    uint32_t n = 0;
+    void *bones = NULL, *morphs = NULL;
+    size_t nb = 0, nm = 0;
+    int B = 0, M = 0;
+    if (!get_u32(env, argv[1], &n) || !get_ta(env, argv[2], napi_uint8_array, 1, &bones, &nb) || !get_ta(env, argv[3], napi_uint8_array, 1, &morphs, &nm))
+        return throw_msg(env, "uploadMotionMasks(ctx, n, Uint8Array bones /* n x bones */, Uint8Array | null morphs /* n x morphs */)");
+    if (n == 0) { int rc0 = rz_upload_motion_masks(ctx, 0, NULL, NULL); return rc0 ? throw_rz(env, rc0) : undef(env); }
+    if (rz_get_tuning(ctx, "bones", &B) || rz_get_tuning(ctx, "morphs", &M)) return throw_rz(env, RZ_ERR_INVALID);
+    if (!bones || nb != (size_t)n * (size_t)B) return throw_msg(env, "uploadMotionMasks: bones must hold one byte per mask and bone");
+    if (morphs && nm != (size_t)n * (size_t)M) return throw_msg(env, "uploadMotionMasks: morphs must hold one byte per mask and morph");
+    int rc = rz_upload_motion_masks(ctx, n, (const uint8_t *)bones, M > 0 ? (const uint8_t *)morphs : NULL);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* setPoseLayered(ctx, ArrayBuffer states, nLayers, ArrayBuffer layers): one 20-byte rz_motion_state per instance (setPoseBlended's) and
+ * nLayers 20-byte rz_motion_layer per instance — clip u32 (0xffffffff = none) | frame f32 | weight f32 | mask u32 (0xffffffff = none) |
+ * mode u32 (0 override, 1 additive), little-endian */
+static napi_value fn_set_pose_layered(napi_env env, napi_callback_info info)
+{
+    ARGS(4);
+    CTX(0);
+    bool is_ab = false, is_lb = false;
+    void *data = NULL, *ldata = NULL;
+    size_t len = 0, llen = 0;
+    uint32_t nl = 0;
+    int I = 0;
+    if (napi_is_arraybuffer(env, argv[1], &is_ab) != napi_ok || !is_ab || napi_get_arraybuffer_info(env, argv[1], &data, &len) != napi_ok || !get_u32(env, argv[2], &nl)
+        || napi_is_arraybuffer(env, argv[3], &is_lb) != napi_ok || !is_lb || napi_get_arraybuffer_info(env, argv[3], &ldata, &llen) != napi_ok)
+        return throw_msg(env, "setPoseLayered(ctx, ArrayBuffer states /* 20 bytes per instance */, nLayers, ArrayBuffer layers /* 20 bytes per instance and layer */)");
+    if (rz_get_tuning(ctx, "instances", &I) || len != (size_t)I * sizeof(rz_motion_state)) return throw_msg(env, "setPoseLayered: states must hold 20 bytes per instance");
+    if (nl > RZ_MAX_MOTION_LAYERS) return throw_msg(env, "setPoseLayered: at most 4 layers");
+    if (llen != (size_t)I * nl * sizeof(rz_motion_layer)) return throw_msg(env, "setPoseLayered: layers must hold 20 bytes per instance and layer");
+    int rc = rz_set_pose_layered(ctx, (const rz_motion_state *)data, nl, nl ? (const rz_motion_layer *)ldata : NULL);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
 static napi_value fn_set_pose_sampled(napi_env env, napi_callback_info info)
 {
     ARGS(2);
@@ -1245,7 +1287,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "timeFrames", fn_time_frames }, { "setTuning", fn_set_tuning }, { "getTuning", fn_get_tuning },
         { "commUniqueId", fn_comm_unique_id }, { "rcclInfo", fn_rccl_info }, { "commInit", fn_comm_init }, { "allgather", fn_allgather },
         { "readGathered", fn_read_gathered }, { "commInitAll", fn_comm_init_all }, { "allgatherAll", fn_allgather_all },
-        { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
+        { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "uploadMotionMasks", fn_upload_motion_masks }, { "setPoseLayered", fn_set_pose_layered }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
         { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
         { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "readPhysics", fn_read_physics },

@@ -622,27 +622,66 @@ static int check_motion_states(const rz_ctx *c, const RzMotionState *sv)
     return RZ_OK;
 }
 
-int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
+// What rz_set_pose_layered checks of the layers, before anything of the resident pose is touched. A skipped layer (no clip, or weight 0) is not
+// looked at beyond those two fields.
+static_assert(sizeof(rz_motion_layer) == sizeof(RzMotionLayer) && sizeof(RzMotionLayer) == 20, "rz_motion_layer is RzMotionLayer");
+static_assert(RZ_MAX_MOTION_LAYERS == kRzMaxLayers && RZ_NO_MASK == kRzNoMask, "the layer constants of the C ABI are the kernel's");
+static int check_motion_layers(const rz_ctx *c, uint32_t n_layers, const RzMotionLayer *lv)
+{
+    for (uint32_t i = 0; i < c->I; ++i)
+        for (uint32_t l = 0; l < n_layers; ++l) {
+            const RzMotionLayer &y = lv[(size_t)i * n_layers + l];
+            if (y.clip == kRzNoClip || y.weight == 0.0f) continue;
+            if (!finite_f(y.weight) || y.weight < 0.0f || y.weight > 1.0f) return fail(RZ_ERR_INVALID, "instance %u layer %u: weight %g is not in [0, 1]", i, l, (double)y.weight);
+            if (y.clip >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u layer %u: clip %u of %u", i, l, y.clip, c->mo_clips);
+            if (y.mode > 1u) return fail(RZ_ERR_INVALID, "instance %u layer %u: mode %u is neither RZ_LAYER_OVERRIDE nor RZ_LAYER_ADDITIVE", i, l, y.mode);
+            if (!finite_f(y.frame)) return fail(RZ_ERR_INVALID, "instance %u layer %u: the frame is not finite", i, l);
+            if (y.mask != kRzNoMask) {
+                if (y.mask >= c->mk_count) return fail(RZ_ERR_INVALID, "instance %u layer %u: mask %u of %u", i, l, y.mask, c->mk_count);
+                if (c->mk_M != c->M)
+                    return fail(RZ_ERR_INVALID, "instance %u layer %u: the masks were built for %u vertex morphs, the context holds %u: upload them again", i, l, c->mk_M, c->M);
+            }
+        }
+    return RZ_OK;
+}
+
+// rz_set_pose_blended and rz_set_pose_layered: one path. `layered` picks the kernel (rz_set_pose_blended launches rz_motion_blend_kernel, as
+// ever) and what travels: the states alone into mo_states, or the states with the layers behind them — I x 20 x (1 + n_layers) bytes, one
+// ring slot, one copy — into mo_layers.
+static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, uint32_t n_layers, const rz_motion_layer *layers)
 {
     if (int r = use(c)) return r;
     if (!c->mo_clips) return fail(RZ_ERR_INVALID, "rz_upload_motions has not been called");
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
     if (c->mo_M != c->M) return fail(RZ_ERR_INVALID, "the library's morph feeds were built for %u vertex morphs, the context holds %u: upload it again", c->mo_M, c->M);
     if (!states) return fail(RZ_ERR_INVALID, "null motion states");
-    // The states are read once, so that what is checked is what travels: one character's onto the stack (it may ride in the kernel
-    // arguments), a crowd's straight into the pinned slot it travels in. A refusal hands that slot back.
-    RzMotionState one;
-    const RzMotionState *sv = &one;
+    if (n_layers > (uint32_t)kRzMaxLayers) return fail(RZ_ERR_INVALID, "%u layers: at most %d", n_layers, kRzMaxLayers);
+    if (n_layers && !layers) return fail(RZ_ERR_INVALID, "null motion layers");
+    // The states (and layers) are read once, so that what is checked is what travels: one character's onto the stack (they may ride in the
+    // kernel arguments), a crowd's straight into the pinned slot they travel in. A refusal hands that slot back.
+    struct { RzMotionState st; RzMotionLayer ly[kRzMaxLayers]; } one;
+    const size_t n_rec = (size_t)c->I * (1 + n_layers), n_bytes = n_rec * sizeof(RzMotionState);
+    const RzMotionState *sv = &one.st;
+    const RzMotionLayer *lv = one.ly;
     int slot = -1;
-    if (c->I == 1) memcpy(&one, states, sizeof one);
-    else {
-        if (int r = stage_acquire(c, std::max<size_t>((size_t)c->I * sizeof(RzMotionState), 4096), &slot)) return r;
-        memcpy(c->stage[slot], states, (size_t)c->I * sizeof(RzMotionState));
+    auto fill = [&](void *dst) {        // [I] states, then [I][n_layers] layers: records of 20 bytes both
+        memcpy(dst, states, (size_t)c->I * sizeof(RzMotionState));
+        if (n_layers) memcpy(static_cast<RzMotionState *>(dst) + c->I, layers, (size_t)c->I * n_layers * sizeof(RzMotionLayer));
+    };
+    if (c->I == 1) {
+        memset(&one, 0, sizeof one);
+        fill(&one);
+    } else {
+        if (int r = stage_acquire(c, std::max<size_t>(n_bytes, 4096), &slot)) return r;
+        fill(c->stage[slot]);
         sv = static_cast<const RzMotionState *>(c->stage[slot]);
+        lv = reinterpret_cast<const RzMotionLayer *>(sv + c->I);
     }
-    if (int r = check_motion_states(c, sv)) {
+    int bad = check_motion_states(c, sv);
+    if (!bad && n_layers) bad = check_motion_layers(c, n_layers, lv);
+    if (bad) {
         if (slot >= 0) c->stage_next = slot;
-        return r;
+        return bad;
     }
     if (int r = ensure_pose_buffers(c)) return r;
     c->map_layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
@@ -654,17 +693,24 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
     hipStream_t us = (piped || c->overlap_on) ? c->up_stream : c->stream;
     const bool inline_state = c->I == 1 && !piped && !c->overlap_on && c->t_zerocopy != 0;      // (the rule of frames_inline)
     if (!inline_state) {
-        if (c->I > c->mo_states_alloc) {
+        if (!layered && c->I > c->mo_states_alloc) {
             if (int r = drain(c)) return r;
             dfree(c->mo_states);
             HIP_TRY(hipMalloc(&c->mo_states, (size_t)c->I * sizeof(RzMotionState)));
             c->mo_states_alloc = c->I;
         }
+        if (layered && n_rec > c->mo_layers_alloc) {
+            if (int r = drain(c)) return r;
+            dfree(c->mo_layers);
+            c->mo_layers_alloc = 0;
+            HIP_TRY(hipMalloc(&c->mo_layers, (size_t)c->I * (1 + kRzMaxLayers) * sizeof(RzMotionLayer)));
+            c->mo_layers_alloc = (size_t)c->I * (1 + kRzMaxLayers);
+        }
         if (c->mo_states_stream && c->mo_states_stream != us) HIP_TRY(hipStreamSynchronize(c->mo_states_stream));     // (the protocol changed: rare)
         c->mo_states_stream = us;
         if (slot < 0) {
             if (int r = stage_acquire(c, 4096, &slot)) return r;
-            memcpy(c->stage[slot], &one, sizeof one);
+            memcpy(c->stage[slot], &one, n_bytes);
         }
     }
     float *block = nullptr;
@@ -676,10 +722,17 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
     c->world_resident = c->mw_resident = c->local_resident = true;
     if (piped) point_pose_at(c, block);
     else point_pose_slot(c, (c->pose_slot & 1) ^ 1);
-    RzMotionParams mp;
-    memset(&mp, 0, sizeof mp);
-    if (inline_state) mp.state0 = one;
-    else {
+    RzLayerParams lp;
+    memset(&lp, 0, sizeof lp);
+    RzMotionParams &mp = lp.m;
+    if (inline_state) {
+        mp.state0 = one.st;
+        memcpy(lp.layers0, one.ly, sizeof one.ly);
+    } else if (layered) {
+        HIP_TRY(hipMemcpyAsync(c->mo_layers, c->stage[slot], n_bytes, hipMemcpyHostToDevice, us));
+        mp.states = reinterpret_cast<const RzMotionState *>(c->mo_layers);
+        lp.layers = c->mo_layers + c->I;
+    } else {
         HIP_TRY(hipMemcpyAsync(c->mo_states, c->stage[slot], (size_t)c->I * sizeof(RzMotionState), hipMemcpyHostToDevice, us));
         mp.states = c->mo_states;
     }
@@ -689,7 +742,14 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
     mp.sample.feed_range = c->mo_feed_range; mp.sample.feed_ratio = c->mo_feed_ratio;
     mp.local_q = c->local_q; mp.local_t = reinterpret_cast<float *>(c->local_q + nq); mp.morph_w = c->morph_w;
     mp.B = (int)c->B; mp.M = (int)c->M;
-    HIP_TRY(rz_launch_motion_blend(mp, c->I, us));
+    if (layered) {
+        lp.n_layers = (int)n_layers;
+        lp.bone_bits = c->mk_bone_bits; lp.bone_words = (int)c->mk_bone_words;
+        lp.morph_bits = c->mk_M == c->M ? c->mk_morph_bits : nullptr; lp.morph_words = (int)c->mk_morph_words;      // (masks of another morph set: no layer names one)
+        HIP_TRY(rz_launch_motion_layers(lp, c->I, us));
+    } else {
+        HIP_TRY(rz_launch_motion_blend(mp, c->I, us));
+    }
     c->last_upload_pulled = false; c->last_upload_rows = false;
     if (slot >= 0) {
         // one event says both "the ring slot may be written again" and "the pose has landed" (copy_send)
@@ -702,6 +762,16 @@ int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
     c->pose_I = c->I;
     c->pose_set = true;
     return RZ_OK;
+}
+
+int rz_set_pose_blended(rz_ctx *c, const rz_motion_state *states)
+{
+    return library_pose(c, states, false, 0, nullptr);
+}
+
+int rz_set_pose_layered(rz_ctx *c, const rz_motion_state *base, uint32_t n_layers, const rz_motion_layer *layers)
+{
+    return library_pose(c, base, true, n_layers, layers);
 }
 
 int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16)

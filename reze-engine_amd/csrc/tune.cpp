@@ -247,6 +247,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef_n;
     else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
     else if (!strcmp(key, "motion_clips")) *value = (int)c->mo_clips;
+    else if (!strcmp(key, "motion_masks")) *value = (int)c->mk_count;
     else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph.nb;
     else if (!strcmp(key, "physics_joints")) *value = (int)c->ph.nj;
     else if (!strcmp(key, "physics_colours")) *value = (int)c->ph.ncol;

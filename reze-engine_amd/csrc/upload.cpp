@@ -168,6 +168,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     free_physics(c);                    // ... and the physics table (its bodies name its bones)
     free_animation(c);                  // ... and so does an uploaded motion (its tracks name bones of that skeleton)
     free_motions(c);                    // ... and the motion library
+    free_motion_masks(c);               // ... and the masks of layered poses (one bit per bone of that skeleton)
     return ensure_pose_buffers(c);
 }
 
@@ -571,6 +572,41 @@ int rz_upload_motions(rz_ctx *c, uint32_t n_clips, const rz_animation *clips)
     if (int r = to_device(&c->mo_mkey_weight, mkey_weight.data(), mkey_weight.size())) return r;
     c->mo_M = M;
     c->mo_clips = n_clips;
+    return RZ_OK;
+}
+
+// The masks of layered poses, packed into bit sets on the way to the device: one 32-bit word per 32 bones (vertex morphs), whole words per
+// mask, so a wave reads two words of a mask where it would read 64 bytes.
+int rz_upload_motion_masks(rz_ctx *c, uint32_t n_masks, const uint8_t *bone_mask, const uint8_t *morph_mask)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_motion_masks")) return r;
+    if (n_masks == 0) {
+        free_motion_masks(c);
+        return RZ_OK;
+    }
+    if (c->B == 0) return fail(RZ_ERR_INVALID, "upload the skeleton before the motion masks");
+    if (!bone_mask) return fail(RZ_ERR_INVALID, "rz_upload_motion_masks: null bone masks");
+    if (n_masks == 0xffffffffu) return fail(RZ_ERR_INVALID, "rz_upload_motion_masks: too many masks");
+    const uint32_t B = c->B, M = c->M, wb = (B + 31) / 32, wm = (M + 31) / 32;
+    auto pack = [n_masks](const uint8_t *bytes, uint32_t n, uint32_t words) {
+        std::vector<uint32_t> bits((size_t)n_masks * words, 0u);
+        for (uint32_t k = 0; k < n_masks; ++k)
+            for (uint32_t i = 0; i < n; ++i)
+                if (bytes[(size_t)k * n + i]) bits[(size_t)k * words + (i >> 5)] |= 1u << (i & 31);
+        return bits;
+    };
+    const std::vector<uint32_t> bone_bits = pack(bone_mask, B, wb);
+    const bool morphs = morph_mask != nullptr && M > 0;
+    const std::vector<uint32_t> morph_bits = morphs ? pack(morph_mask, M, wm) : std::vector<uint32_t>();
+    free_motion_masks(c);               // (drains both streams first: a layer kernel may still be reading the old masks)
+    if (int r = to_device(&c->mk_bone_bits, bone_bits.data(), bone_bits.size())) return r;
+    if (morphs)
+        if (int r = to_device(&c->mk_morph_bits, morph_bits.data(), morph_bits.size())) { free_motion_masks(c); return r; }
+    c->mk_bone_words = wb;
+    c->mk_morph_words = morphs ? wm : 0;
+    c->mk_M = M;
+    c->mk_count = n_masks;
     return RZ_OK;
 }
 

@@ -50,7 +50,10 @@ export interface EngineOptions {
   /** With devicePhysics: contacts and friction between the model's sphere and capsule bodies by their PMX groups and masks (rz_physics_contacts, called on every shard right after the table's upload at loadModel). Off by default; without devicePhysics it throws. true: boxes take no part. 'boxes': the model's box bodies collide with its spheres and capsules as well (rz_physics_contacts(ctx, 2)); a pair of two boxes is still left out. 'all': pairs of two boxes collide too (rz_physics_contacts(ctx, 3)). */ physicsContacts?: boolean | 'boxes' | 'all'
   /** With devicePhysics: the linear springs of the model's joints (PMX spring_position; rz_physics_springs, called on every shard right after the table's upload at loadModel, ahead of physicsContacts): a joint with play along an axis and a spring on it swings about its rest point instead of hanging at the end of its play. Off by default; without devicePhysics it throws. */ physicsSprings?: boolean
 }
-export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
+export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number; layers?: MotionLayer[] }
+/** one layer of a MotionState: motion `motion` at `frame`, applied with `weight` (default 1) where the mask `mask` (Engine.setMotionMask; none: everywhere) includes the bone or morph and the motion keys it — override (slerp / lerp towards it) or `additive` (q * slerp(identity, qL, weight), t + tL * weight, w + wL * weight). At most 4 per state. */
+export interface MotionLayer { motion: string; frame: number; weight?: number; mask?: string | null; additive?: boolean }
+export interface MotionMaskSpec { bones: string[]; withDescendants?: boolean; morphs?: string[] | 'all' | 'none' }
 export interface EngineStats {
   fps: number; frameTime: number; gpuMemory: number
   deformMs: number; vertsPerSec: number; hbmGBps: number
@@ -75,6 +78,8 @@ export class Engine {
   loadMotion(name: string, path: string): Promise<void>
   /** Pose from the motion library: motion `a` at frameA, cross-faded by `blend` (0 .. 1) into motion `b` at frameB — slerp for rotations, lerp for translations and morph weights. With { deviceFK, deviceSampling } the library is uploaded once (rz_upload_motions) and every frame is one rz_set_pose_blended; a crowd takes one state per instance. Otherwise one character is posed on the host (Model.applyBlendedFrame). */
   seekMotions(state: MotionState | MotionState[]): void
+  /** Add or replace the mask `name` for MotionState.layers: the named bones (`withDescendants`: and every bone below them in the skeleton) and morphs (names, 'all' — the default — or 'none'). With { deviceFK, deviceSampling } the masks are uploaded once per (mask set, model) (rz_upload_motion_masks) and a state with layers is one rz_set_pose_layered; otherwise one character is posed on the host (Model.applyLayeredFrame). */
+  setMotionMask(name: string, spec: MotionMaskSpec): void
   /** n independently posed copies of the model (needs { deviceFK, deviceSampling }, one GPU). */
   setInstanceCount(n: number): void
   /** Physics hand-off with { deviceFK }: world matrices (column-major 4x4 each) that replace the GPU-solved ones of the listed bones until the next call. */

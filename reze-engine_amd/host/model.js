@@ -543,6 +543,127 @@ class Model {
     }
   }
 
+  /** effective weights (own track, then the group tracks that list the morph) of one sampler at `frame` into w, driven[i] = 1 where a feed of morph i holds a key: what VMDSampler.flatten() lays out for the device */
+  _sampleEffective(sampler, frame, w, driven) {
+    w.fill(0); driven.fill(0)
+    if (!this.morphs) return
+    const { names, types, groups } = this.morphs
+    for (let i = 0; i < names.length; i++) {
+      if (types[i] !== 1 && types[i] !== 2) continue
+      const own = sampler.sampleMorph(names[i], frame)
+      if (own !== null) { w[i] += own; driven[i] = 1 }
+    }
+    for (let g = 0; g < names.length; g++) {
+      if (types[g] !== 0 || !groups[g]) continue
+      const wg = sampler.sampleMorph(names[g], frame)
+      if (wg === null) continue
+      for (const [child, ratio] of groups[g]) if (types[child] === 1 || types[child] === 2) { w[child] += wg * ratio; driven[child] = 1 }
+    }
+  }
+
+  /**
+   * The host twin of rz_set_pose_layered (include/reze_deform.h; tests/layer_ref.py is the definition). `base` is applyBlendedFrame's state
+   * { a, frameA, b?, frameB?, blend? } with samplers for a and b; `layers` are { sampler, frame, weight = 1, mask = null, additive = false }
+   * applied in order, `mask` a key of `masks` (name -> { bones: Uint8Array[B], morphs: Uint8Array[M] | null }). A layer without a sampler or
+   * with weight 0 is skipped. A layer acts on a bone only where its clip keys the bone and the mask includes it — override: slerp / lerp
+   * towards the layer's sample (the sample itself at weight 1); additive: q * slerp(identity, qL, weight), t + tL * weight — and on a
+   * vertex or bone morph only where the clip keys the morph or a group morph that lists it and the mask includes it, on the EFFECTIVE
+   * weights. A clip that does not key a bone or morph another one keys counts as rest there; a bone or morph that no clip keys is left
+   * alone, as applyBlendedFrame leaves it. Morphs are written back as own weights: a group morph some clip keys is set to 0 and what it
+   * fed is carried by the morphs it lists, so that getEffectiveMorphWeights() gives the layered weights.
+   */
+  applyLayeredFrame(base, layers, masks) {
+    const t = base.b && base.blend !== undefined && base.blend !== null ? base.blend : 0
+    if (!(t >= 0 && t <= 1)) throw new Error('applyLayeredFrame: blend must be in [0, 1], got ' + base.blend)
+    if (layers.length > 4) throw new Error('applyLayeredFrame: ' + layers.length + ' layers, at most 4')
+    const live = []
+    layers.forEach((l, k) => {
+      if (!l.sampler || l.weight === 0) return
+      const w = l.weight === undefined || l.weight === null ? 1 : l.weight
+      if (!(w >= 0 && w <= 1)) throw new Error('applyLayeredFrame: layer ' + k + ': weight must be in [0, 1], got ' + l.weight)
+      if (!Number.isFinite(l.frame)) throw new Error('applyLayeredFrame: layer ' + k + ': the frame is not finite')
+      let mask = null
+      if (l.mask !== undefined && l.mask !== null) {
+        mask = masks ? masks[l.mask] : undefined
+        if (!mask) throw new Error('applyLayeredFrame: layer ' + k + ': unknown mask "' + l.mask + '"')
+      }
+      live.push({ sampler: l.sampler, frame: l.frame, weight: w, mask, additive: !!l.additive })
+    })
+    const rot = this.runtimeSkeleton.localRotations, tra = this.runtimeSkeleton.localTranslations
+    this.applyLocalTranslations = true
+    const fb = base.frameB === undefined || base.frameB === null ? 0 : base.frameB
+    const useA = t < 1, useB = t > 0
+    const bones = new Set(base.a.boneNames())
+    if (base.b) for (const name of base.b.boneNames()) bones.add(name)
+    for (const l of live) for (const name of l.sampler.boneNames()) bones.add(name)
+    const rest = { rotation: [0, 0, 0, 1], position: [0, 0, 0] }
+    const q = [0, 0, 0, 1], s = [0, 0, 0, 1]
+    for (const name of bones) {
+      const idx = this.runtimeSkeleton.nameIndex[name]
+      if (idx === undefined) continue
+      const a = useA ? base.a.sampleBone(name, base.frameA) || rest : rest
+      const b = useB ? base.b.sampleBone(name, fb) || rest : rest
+      let r = a.rotation.slice(), p = a.position.slice()
+      if (t === 1) { r = b.rotation.slice(); p = b.position.slice() }
+      else if (t > 0) {
+        r = Array.from(slerpInto(q, a.rotation[0], a.rotation[1], a.rotation[2], a.rotation[3], b.rotation[0], b.rotation[1], b.rotation[2], b.rotation[3], t))
+        p = [a.position[0] + (b.position[0] - a.position[0]) * t, a.position[1] + (b.position[1] - a.position[1]) * t, a.position[2] + (b.position[2] - a.position[2]) * t]
+      }
+      for (const l of live) {
+        if (l.mask && !l.mask.bones[idx]) continue
+        const o = l.sampler.sampleBone(name, l.frame)
+        if (!o) continue
+        const w = l.weight, lr = o.rotation, lp = o.position
+        if (l.additive) {
+          slerpInto(s, 0, 0, 0, 1, lr[0], lr[1], lr[2], lr[3], w)
+          const x = r[0], y = r[1], z = r[2], ww = r[3]      // Hamilton product r * s (Quat.multiply)
+          r = [ww * s[0] + x * s[3] + y * s[2] - z * s[1], ww * s[1] - x * s[2] + y * s[3] + z * s[0], ww * s[2] + x * s[1] - y * s[0] + z * s[3], ww * s[3] - x * s[0] - y * s[1] - z * s[2]]
+          p = [p[0] + lp[0] * w, p[1] + lp[1] * w, p[2] + lp[2] * w]
+        } else if (w === 1) {
+          r = lr.slice(); p = lp.slice()
+        } else {
+          r = Array.from(slerpInto(q, r[0], r[1], r[2], r[3], lr[0], lr[1], lr[2], lr[3], w))
+          p = [p[0] + (lp[0] - p[0]) * w, p[1] + (lp[1] - p[1]) * w, p[2] + (lp[2] - p[2]) * w]
+        }
+      }
+      rot[idx * 4] = r[0]; rot[idx * 4 + 1] = r[1]; rot[idx * 4 + 2] = r[2]; rot[idx * 4 + 3] = r[3]
+      tra[idx * 3] = p[0]; tra[idx * 3 + 1] = p[1]; tra[idx * 3 + 2] = p[2]
+      this.rotTweenState.active[idx] = 0
+    }
+    if (!this.morphs) return
+    const M = this.morphs.names.length, types = this.morphs.types
+    const w = new Float64Array(M), wl = new Float64Array(M), any = new Uint8Array(M), dl = new Uint8Array(M)
+    if (useA) { this._sampleEffective(base.a, base.frameA, wl, dl); for (let i = 0; i < M; i++) { w[i] = wl[i]; any[i] |= dl[i] } }
+    if (useB) {
+      this._sampleEffective(base.b, fb, wl, dl)
+      for (let i = 0; i < M; i++) { w[i] = t === 1 ? wl[i] : w[i] + (wl[i] - w[i]) * t; any[i] |= dl[i] }
+    }
+    // (a base clip that is not sampled still keys its morphs: they are at rest, not left alone — as in applyBlendedFrame)
+    const keyedBy = (smp) => {
+      const names = new Set(smp.morphNames())
+      for (let i = 0; i < M; i++) {
+        if (!names.has(this.morphs.names[i])) continue
+        if (types[i] === 1 || types[i] === 2) any[i] = 1
+        else if (types[i] === 0 && this.morphs.groups[i]) for (const [child] of this.morphs.groups[i]) if (types[child] === 1 || types[child] === 2) any[child] = 1
+      }
+      return names
+    }
+    const groupsKeyed = new Set()
+    const samplers = [base.a].concat(base.b ? [base.b] : [], live.map((l) => l.sampler))
+    for (const smp of samplers) for (const name of keyedBy(smp)) { const g = this.morphNameIndex[name]; if (g !== undefined && types[g] === 0) groupsKeyed.add(g) }
+    for (const l of live) {
+      this._sampleEffective(l.sampler, l.frame, wl, dl)
+      for (let i = 0; i < M; i++) {
+        if (!dl[i] || (l.mask && l.mask.morphs && !l.mask.morphs[i])) continue
+        if (l.additive) w[i] = w[i] + wl[i] * l.weight
+        else w[i] = l.weight === 1 ? wl[i] : w[i] + (wl[i] - w[i]) * l.weight
+      }
+    }
+    for (const g of groupsKeyed) this.morphWeights[g] = 0
+    const now = Float64Array.from(this.getEffectiveMorphWeights())      // what the group morphs no clip keys still feed
+    for (let i = 0; i < M; i++) if (any[i]) this.morphWeights[i] += w[i] - now[i]
+  }
+
   // ---- morphs (no reference counterpart; PMX layout per pmx-loader.ts:471-488) ----
   getMorphNames() { return this.morphs ? this.morphs.names.slice() : [] }
   getMorphCount() { return this.morphs ? this.morphs.names.length : 0 }

@@ -21,7 +21,7 @@ import { VMDLoader } from './vmd-loader'
 import { VMDSampler } from './vmd-sampler'
 import { requireAddon } from './addon'
 
-import type { Bounds, DeformAddon, DeformContext, DeformedMesh, EngineOptions, EngineStats, MotionState, PhysicsLike, Shard, Timer, Timing, VMDKeyFrames } from './types'
+import type { Bounds, DeformAddon, DeformContext, DeformedMesh, EngineOptions, EngineStats, HostMask, MotionMaskSpec, MotionState, PhysicsLike, Shard, Timer, Timing, VMDKeyFrames } from './types'
 import type { Model } from './model'
 let wallClock: () => number
 try {
@@ -97,6 +97,10 @@ class Engine {
   motionsVersion: number
   motionsOnDevice: number
   motionsFor: Model | null
+  motionMasks: Map<string, MotionMaskSpec>
+  masksVersion: number
+  masksOnDevice: number
+  masksFor: Model | null
   constructor(canvas: unknown, options?: EngineOptions) {
     this.canvas = canvas || null // accepted for signature compatibility; nothing is drawn
     const o = options || {}
@@ -152,6 +156,11 @@ class Engine {
     this.motionsVersion = 0
     this.motionsOnDevice = -1
     this.motionsFor = null
+    // the masks of layered motion states (setMotionMask): name -> spec; a mask's index on the device is its position in this map
+    this.motionMasks = new Map()
+    this.masksVersion = 0
+    this.masksOnDevice = -1
+    this.masksFor = null
     // framesInFlight: 2 = consecutive frames alternate between the context and a fork of it (rz_fork: the fork borrows the
     // static buffers, owns its stream, pose slots and outputs), so the tail of frame f overlaps the launch ramp of frame
     // f + 1 — what a WebGPU queue does with consecutive command buffers (engine.ts:2124-2136 submits one per frame).
@@ -639,7 +648,9 @@ class Engine {
    * Pose from the motion library and deform one frame: per state, motion `a` at frameA cross-faded by `blend` into motion `b` at frameB
    * (no `b`, or blend 0: `a` alone). With { deviceFK, deviceSampling } the library is uploaded once per (library, model) and every call is
    * one rz_set_pose_blended — a crowd takes one state per instance, a single state poses every instance. Otherwise one character is
-   * posed on the host (Model.applyBlendedFrame) and rendered.
+   * posed on the host (Model.applyBlendedFrame) and rendered. A state may carry up to four `layers` ({ motion, frame, weight?, mask?,
+   * additive? }; masks from setMotionMask): on the device the call becomes one rz_set_pose_layered (the masks are uploaded once per
+   * (mask set, model)), on the host Model.applyLayeredFrame. Without layers nothing changes.
    */
   seekMotions(state: MotionState | MotionState[]): void {
     if (!this.currentModel) return
@@ -647,13 +658,63 @@ class Engine {
     for (const st of states) {
       if (!this.motions.has(st.a)) throw new Error('seekMotions: unknown motion "' + st.a + '"')
       if (st.b !== undefined && st.b !== null && !this.motions.has(st.b)) throw new Error('seekMotions: unknown motion "' + st.b + '"')
+      if (!st.layers) continue
+      if (st.layers.length > 4) throw new Error('seekMotions: ' + st.layers.length + ' layers, at most 4')
+      for (const l of st.layers) {
+        if (!this.motions.has(l.motion)) throw new Error('seekMotions: unknown motion "' + l.motion + '"')
+        if (l.mask !== undefined && l.mask !== null && !this.motionMasks.has(l.mask)) throw new Error('seekMotions: unknown mask "' + l.mask + '"')
+      }
     }
     if (this.deviceSampling) return this.seekMotionsOnDevice(states)
     if (states.length !== 1) throw new Error('seekMotions: ' + states.length + ' states, but the host path poses one character (a crowd needs { deviceFK, deviceSampling })')
     const st = states[0]
     const hasB = st.b !== undefined && st.b !== null
-    this.currentModel.applyBlendedFrame(this.motions.get(st.a), st.frameA, hasB ? this.motions.get(st.b) : null, st.frameB, st.blend)
+    if (st.layers && st.layers.length) {
+      const masks = this.resolveMotionMasks(this.currentModel)
+      const resolved = {}
+      Array.from(this.motionMasks.keys()).forEach((name, k) => { resolved[name] = masks[k] })
+      this.currentModel.applyLayeredFrame({ a: this.motions.get(st.a), frameA: st.frameA, b: hasB ? this.motions.get(st.b) : null, frameB: st.frameB, blend: st.blend },
+        st.layers.map((l) => ({ sampler: this.motions.get(l.motion), frame: l.frame, weight: l.weight, mask: l.mask, additive: l.additive })), resolved)
+    } else this.currentModel.applyBlendedFrame(this.motions.get(st.a), st.frameA, hasB ? this.motions.get(st.b) : null, st.frameB, st.blend)
     this.render()
+  }
+
+  /**
+   * Add or replace the mask `name` that the layers of a MotionState may name: the bones `spec.bones` (with `withDescendants`, every bone
+   * below them in the skeleton's parent table as well) and the morphs `spec.morphs` (names, 'all' — the default — or 'none'). Names are
+   * resolved against the model when the mask is first used; a bone the model lacks throws there.
+   */
+  setMotionMask(name: string, spec: MotionMaskSpec): void {
+    if (!spec || !Array.isArray(spec.bones)) throw new Error('setMotionMask(name, { bones: string[], withDescendants?, morphs? })')
+    this.motionMasks.set(name, { bones: spec.bones.slice(), withDescendants: !!spec.withDescendants, morphs: Array.isArray(spec.morphs) ? spec.morphs.slice() : spec.morphs || 'all' }) // (a replaced name keeps its place in the map: its mask index)
+    this.masksVersion++
+  }
+
+  /** every mask of setMotionMask resolved for `model`, in the map's order: one byte per bone and one per morph */
+  resolveMotionMasks(model: Model): HostMask[] {
+    const bones = model.getSkeleton().bones, B = bones.length, M = model.getMorphCount()
+    const out = []
+    for (const [name, spec] of this.motionMasks) {
+      const bm = new Uint8Array(B), mm = new Uint8Array(M)
+      for (const bn of spec.bones) {
+        const i = model.runtimeSkeleton.nameIndex[bn]
+        if (i === undefined) throw new Error('setMotionMask "' + name + '": unknown bone "' + bn + '"')
+        bm[i] = 1
+      }
+      if (spec.withDescendants) {
+        for (let i = 0; i < B; i++) { // a bone is in when an ancestor is (parents may come after their children in a PMX: walk up)
+          for (let p = bones[i].parentIndex, n = 0; p >= 0 && p < B && n < B; p = bones[p].parentIndex, n++) if (bm[p] === 1) { bm[i] = 2; break }
+        }
+        for (let i = 0; i < B; i++) if (bm[i]) bm[i] = 1
+      }
+      if (spec.morphs === 'all' || spec.morphs === undefined) mm.fill(1)
+      else if (spec.morphs !== 'none') {
+        const names = model.getMorphNames()
+        for (const mn of spec.morphs) { const i = names.indexOf(mn); if (i >= 0) mm[i] = 1 }
+      }
+      out.push({ bones: bm, morphs: mm })
+    }
+    return out
   }
 
   /** seekMotions with { deviceFK, deviceSampling }: upload the flattened library once, then 20 bytes per instance and frame. */
@@ -679,11 +740,40 @@ class Engine {
       dv.setFloat32(i * 20 + 12, hasB && st.frameB !== undefined ? st.frameB : 0, true)
       dv.setFloat32(i * 20 + 16, hasB && st.blend !== undefined ? st.blend : 0, true)
     })
+    // layers: the longest list decides the count, shorter ones are padded with skipped layers; no layers at all is a blended pose, as ever
+    const nLayers = states.reduce((n, st) => Math.max(n, st.layers ? st.layers.length : 0), 0)
+    let lbuf = null
+    if (nLayers > 0) {
+      const maskNames = Array.from(this.motionMasks.keys())
+      if (maskNames.length > 0 && (this.masksOnDevice !== this.masksVersion || this.masksFor !== model)) {
+        const masks = this.resolveMotionMasks(model)
+        const B = masks[0].bones.length, M = masks[0].morphs.length
+        const bm = new Uint8Array(masks.length * B), mm = M > 0 ? new Uint8Array(masks.length * M) : null
+        masks.forEach((m, k) => { bm.set(m.bones, k * B); if (mm) mm.set(m.morphs, k * M) })
+        this.dropForks() // the masks are static data
+        for (const s of this.shards) if (s.count > 0) this.native.uploadMotionMasks(s.ctx, masks.length, bm, mm)
+        this.masksOnDevice = this.masksVersion
+        this.masksFor = model
+      }
+      lbuf = new ArrayBuffer(states.length * nLayers * 20)
+      const lv = new DataView(lbuf)
+      states.forEach((st, i) => {
+        for (let k = 0; k < nLayers; k++) {
+          const l = st.layers && k < st.layers.length ? st.layers[k] : null, o = (i * nLayers + k) * 20
+          lv.setUint32(o, l ? names.indexOf(l.motion) : 0xffffffff, true)
+          lv.setFloat32(o + 4, l ? l.frame : 0, true)
+          lv.setFloat32(o + 8, l ? (l.weight === undefined || l.weight === null ? 1 : l.weight) : 0, true)
+          lv.setUint32(o + 12, l && l.mask !== undefined && l.mask !== null ? maskNames.indexOf(l.mask) : 0xffffffff, true)
+          lv.setUint32(o + 16, l && l.additive ? 1 : 0, true)
+        }
+      })
+    }
     const substeps = this.physicsSubsteps()
     for (const s of this.shards) {
       if (s.count === 0) continue
       const c = this.frameContext(s)
-      this.native.setPoseBlended(c, buf)
+      if (lbuf) this.native.setPoseLayered(c, buf, nLayers, lbuf)
+      else this.native.setPoseBlended(c, buf)
       if (substeps >= 0) this.native.physicsStep(c, substeps)
       this.native.deform(c)
     }

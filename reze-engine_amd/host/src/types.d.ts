@@ -80,7 +80,21 @@ export interface FlatMotion {
 }
 
 /** Engine.seekMotions(): instance i is posed from motion `a` at frameA, cross-faded by `blend` (0 .. 1) into motion `b` at frameB */
-export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number }
+export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number; layers?: MotionLayer[] }
+/** one layer of a MotionState: motion `motion` at `frame`, applied with `weight` (default 1) where the mask `mask` (Engine.setMotionMask; none: everywhere) includes the bone or morph and the motion keys it — override (slerp / lerp towards it) or `additive` */
+export interface MotionLayer { motion: string; frame: number; weight?: number; mask?: string | null; additive?: boolean }
+/** Engine.setMotionMask(): the bones a layer may act on (`withDescendants`: and every bone below them) and the morphs (names, 'all' — the default — or 'none') */
+export interface MotionMaskSpec { bones: string[]; withDescendants?: boolean; morphs?: string[] | 'all' | 'none' }
+/** Model.applyLayeredFrame(): a mask resolved for one model, one byte per bone and per morph (morphs null: all) */
+export interface HostMask { bones: Uint8Array; morphs: Uint8Array | null }
+export interface LayeredBase { a: VMDSamplerLike; frameA: number; b?: VMDSamplerLike | null; frameB?: number; blend?: number }
+export interface HostLayer { sampler: VMDSamplerLike | null; frame: number; weight?: number; mask?: string | null; additive?: boolean }
+/** what Model.applyLayeredFrame needs of a VMDSampler */
+export interface VMDSamplerLike {
+  boneNames(): string[]; morphNames(): string[]
+  sampleBone(name: string, frame: number): { rotation: number[]; position: number[] } | null
+  sampleMorph(name: string, frame: number): number | null
+}
 
 /** opaque rz_ctx handle of the addon */
 export type DeformContext = unknown
@@ -121,6 +135,10 @@ export interface DeformAddon {
   setPoseSampled(ctx: DeformContext, frames: Float32Array): void
   /** 20 bytes per instance: clipA u32 | frameA f32 | clipB u32 (0xffffffff = none) | frameB f32 | blend f32, little-endian */
   setPoseBlended(ctx: DeformContext, states: ArrayBuffer): void
+  /** n masks of one byte per bone and, optionally, per morph (non-zero = included); n = 0 removes them (rz_upload_motion_masks) */
+  uploadMotionMasks(ctx: DeformContext, n: number, bones: Uint8Array | null, morphs: Uint8Array | null): void
+  /** setPoseBlended's states and nLayers x 20 bytes per instance: clip u32 (0xffffffff = none) | frame f32 | weight f32 | mask u32 (0xffffffff = none) | mode u32 (0 override, 1 additive), little-endian (rz_set_pose_layered) */
+  setPoseLayered(ctx: DeformContext, states: ArrayBuffer, nLayers: number, layers: ArrayBuffer): void
   mapPose(ctx: DeformContext, layout?: 0 | 1): { matrices: Float32Array; morphWeights: Float32Array | null }
   commitPose(ctx: DeformContext): void
   overrideWorld(ctx: DeformContext, bones: Uint32Array, world16: Float32Array, instances: Uint32Array | null): void
