@@ -338,8 +338,33 @@ int rz_set_pose_layered(rz_ctx *ctx, const rz_motion_state *base /* [I] */, uint
  * (column-major 4x4, affine) replace the solved ones of (instance[k], bone[k]) after the hierarchy solve and before
  * the palette product, in every following frame until the next call; n = 0 clears. instance = NULL means instance 0.
  * Several entries for one bone: the last wins (successive set() calls). Asynchronous H2D through pinned staging.
- * Physics itself (Bullet via @fred3d/ammo) stays out of scope: this only carries its result. */
+ * Physics itself (Bullet via @fred3d/ammo) stays out of scope: this only carries its result.
+ * ---- bones below an overridden bone follow it — NEW (optional, off by default) ----
+ * The seam above leaves every bone BELOW an overridden one where the un-overridden solve put it: a strand's tip bone without a body,
+ * an ornament hanging off a hair bone, the sub-bone of a skirt plate stay with the animation while the physics bone swings away.
+ * rz_override_follow(ctx, 1) adds one stage to the device hierarchy solve, defined by tests/follow_ref.py:
+ *   S   the solved world matrices of an instance — hierarchy, bone morphs and IK, exactly what is solved without the flag;
+ *   O   the set of that instance's overridden bones, with matrices O_a (hand-fed here, or written by rz_physics_step);
+ *   every bone b outside O with an ancestor in O takes, with a = the NEAREST such ancestor along `parents`,
+ *       W_b = O_a (S_a^-1 S_b),   S_a^-1 the rigid inverse (R^T, -R^T p: world matrices carry no scale);
+ *   bones of O take O_a, all others keep S_b. So an override below another override is absolute: the bones between the two follow the
+ *   upper one, the bones below the lower one the lower one.
+ * Order of a frame: sample -> bone morphs -> hierarchy -> IK -> followers -> overrides -> palette. NOT covered — nothing is evaluated again
+ * on the followed pose: append rotation / move whose append parent is overridden or follows; IK chains below an overridden bone; following
+ * (type 0 / 2) bodies on follower bones (the first solve of rz_physics_step runs without overrides as before, so bodies are placed on the
+ * un-followed pose); PMX after-physics bones / transform levels, which stay unparsed.
+ * A flag of the context, off by default. It needs a resident topology (RZ_ERR_INVALID without), persists across rz_override_world calls,
+ * physics uploads / removals and rz_set_instances, and is cleared by a new skeleton or topology. A fork inherits it at rz_fork and may set
+ * it like its lender. A change drops the captured graph. on > 1: RZ_ERR_INVALID, context untouched. The follower lists — per instance the
+ * followers ascending by bone, each with its ancestor's entry in the override table — are built on the host from `parents` wherever the
+ * override set is built: here (they travel in the same pinned slot down the same stream), with a physics table's per-instance buffers,
+ * and when the flag flips while a set is resident. With the flag off, or with a set nothing hangs below, nothing is built, uploaded or
+ * passed and every frame launches what it launched before; with follower entries resident the solve is rz_fk_follow_kernel /
+ * rz_fk_ik_follow_kernel, and a single character's frame keeps the solve in that kernel instead of its own prologue.
+ * rz_get_tuning("override_follow") = 0 / 1, ("override_followers") = the follower entries resident over all instances (0 while off).
+ * The ABI version stays 8: bindings detect the symbol. Host twin for host-solved poses: Model.followOverrides (host/model.js). */
 int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16);
+int rz_override_follow(rz_ctx *ctx, uint32_t on);
 /* ---- rigid-body physics on the device for PMX bodies and joints — NEW (optional) ----
  * The reference runs Bullet (Ammo, loaded at run time: engine/src/physics.ts) on the host around the seam above. rz_upload_physics /
  * rz_physics_step keep the seam (physics.ts:534-569) and replace the solver by one of this build's own, defined in float64 by
@@ -380,7 +405,8 @@ int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const u
  *      Inverse inertia, diagonal in the body frame: sphere 2/5 m r^2 (r = size.x); box m/3 (b^2 + c^2) with half extents = size; capsule the
  *      box of half extents (r, r + height/2, r) (r = size.x, height = size.y).
  *   3. every dynamic body with a bone gives boneWorld = bodyWorld x offset^-1: that bone's override, in every following frame until the
- *      next step. Children of an overridden bone keep the matrices solved from the un-overridden parent, as rz_override_world documents.
+ *      next step. Children of an overridden bone keep the matrices solved from the un-overridden parent, as rz_override_world documents
+ *      (unless rz_override_follow is on: then they follow it, as stated there).
  * NOT covered: contacts unless rz_physics_contacts enables them (below; boxes only under on = 2 and 3); linear springs (spring_position)
  * unless rz_physics_springs enables them (below); restitution. A welded joint (all limits equal) whose
  * anchor is off the body's centre converges only linearly in `iterations` (the position and the rotation stage each undo part of the

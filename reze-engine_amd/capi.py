@@ -23,14 +23,15 @@ SYMBOLS = [
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
+    "rz_override_follow",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
-# points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks and rz_set_pose_layered — detected by the symbol, the version
-# stayed 8)
+# points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks, rz_set_pose_layered and rz_override_follow — detected by the
+# symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
                     "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
-                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs"}
+                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs", "rz_override_follow"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
 NO_MASK = 0xffffffff
@@ -227,6 +228,8 @@ def load(path=None):
         L.rz_physics_contacts.argtypes = [vp, u32]
     if hasattr(L, "rz_physics_springs"):
         L.rz_physics_springs.argtypes = [vp, u32]
+    if hasattr(L, "rz_override_follow"):
+        L.rz_override_follow.argtypes = [vp, u32]
     for name in SYMBOLS:
         # (libraries older than the current ABI — tools/ab_inproc.py loads them side by side — lack the newer symbols: OPTIONAL_SYMBOLS)
         if name != "rz_last_error" and (name not in OPTIONAL_SYMBOLS or hasattr(L, name)):
@@ -623,6 +626,14 @@ class DeformContext:
             assert i.size == b.size
             ip = i.ctypes.data_as(u32p)
         self._chk(self._L.rz_override_world(self._h, int(b.size), ip, b.ctypes.data_as(u32p), _fptr(w)))
+
+    def override_follow(self, on=True):
+        """Bones below an overridden bone follow it (off by default; include/reze_deform.h and tests/follow_ref.py state the stage):
+        W_b = O_a (S_a^-1 S_b) with a the nearest overridden ancestor of b, for hand-fed overrides and for those rz_physics_step writes.
+        Needs the topology; a new skeleton or topology clears it. `on` is passed as given: values other than 0 / 1 are refused."""
+        if not hasattr(self._L, "rz_override_follow"):
+            raise RzError(-6, "this build of the library has no rz_override_follow")
+        self._chk(self._L.rz_override_follow(self._h, int(on)))
 
     def read_world(self, instance=0):
         out = np.empty((self.B, 16), dtype=np.float32)

@@ -376,6 +376,7 @@ int rz_destroy(rz_ctx *c)
     dfree(c->pose_blk[0]); dfree(c->pose_blk[1]);
     free_big_ring(c);
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
+    dfree(c->fol_off); dfree(c->fol_ent);
     free_physics(c);
     for (int k = 0; k < 2; ++k) {
         if (c->big_ev[k]) (void)hipEventDestroy(c->big_ev[k]);
@@ -423,6 +424,7 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
     static_cast<RzStatic &>(*c) = *parent;      // borrowed: the lender's pointers, and copies of the host mirrors the plan reads (plan.cpp: ensure_subfk)
     static_cast<RzTuning &>(*c) = *parent;      // inherited
     c->I = parent->I; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on; c->tuned_by_search = parent->tuned_by_search;
+    c->ovr_follow = parent->ovr_follow;         // rz_override_follow: a flag of the context, inherited here; the override set and its followers are each context's own
     c->lender = parent;
     parent->n_forks++;
     int rc = ensure_pose_buffers(c);

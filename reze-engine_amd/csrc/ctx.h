@@ -231,6 +231,15 @@ struct rz_ctx : RzStatic, RzTuning {
     float *ovr_world = nullptr;
     uint32_t ovr_count = 0;
     size_t ovr_alloc = 0, ovr_off_alloc = 0;
+    // rz_override_follow: bones below an overridden bone follow it (kernels/fk.hip.h: FOLLOW). A flag of the context (a fork starts with its
+    // lender's value); the lists exist only while it is on and are valid whenever ovr_count != 0 — built wherever the override set is
+    // built (rz_override_world, the physics table's per-instance buffers, and the flag's own flip while overrides are resident)
+    int ovr_follow = 0;
+    int *fol_off = nullptr;             // [I + 1]
+    uint2 *fol_ent = nullptr;           // [fol_count] (follower bone, entry of its nearest overridden ancestor in the override table)
+    uint32_t fol_count = 0;
+    size_t fol_alloc = 0, fol_off_alloc = 0;
+    std::vector<int> ovr_off_host, ovr_bone_host;       // the hand-fed override set as uploaded (rz_override_world), for a later flip of the flag
 
     RzPhysics ph;                       // rigid-body physics; with a table the override table above is physics' own ([I][ph.nd] slots, fixed addresses)
 
@@ -450,6 +459,13 @@ int frame_plan(rz_ctx *c, Plan *pl);
 RzDeformParams deform_params(const rz_ctx *c, const Plan &pl);
 RzPrepParams prep_params(const rz_ctx *c);
 RzFkParams fk_params(const rz_ctx *c);
+// rz_override_follow: null pointers unless the flag is on, overrides are resident and at least one bone follows one
+RzFollowParams follow_params(const rz_ctx *c);
+// the follower lists of an override set (off [I + 1], bones ascending inside an instance) from the resident parents: fol_off [I + 1] and per
+// entry (follower bone, index of its nearest overridden ancestor's entry), ascending by bone inside an instance
+void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent);
+int reserve_followers(rz_ctx *c, size_t entries, size_t offsets);       // grows fol_off / fol_ent (drains and drops the graph when it must)
+int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones);       // build + blocking upload; the caller has drained
 uint64_t algorithmic_bytes(const rz_ctx *c);
 
 // ---- pose.cpp ----

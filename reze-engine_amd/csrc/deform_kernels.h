@@ -60,7 +60,8 @@ struct RzFkParams {
     int n_rounds;               // radix-4 doubling rounds = ceil(log4(depth of the hierarchy)); 0 = roots only
     // physics hand-off (engine.ts:2379-2381, physics.ts:715-751): world matrices that replace the solved ones AFTER the
     // hierarchy solve — children keep the matrices solved from the un-overridden parent, exactly like the reference's
-    // in-place boneWorldMatrices.set(). Entries sorted by instance; ovr_off[i]..ovr_off[i+1] are instance i's.
+    // in-place boneWorldMatrices.set() (the entry points with the follow stage let them follow it: RzFollowParams). Entries sorted by
+    // instance; ovr_off[i]..ovr_off[i+1] are instance i's.
     const int *ovr_off;         // [I + 1] or nullptr
     const int *ovr_bone;        // [n]
     const float *ovr_world;     // [n][16] column-major
@@ -93,6 +94,15 @@ struct RzIkParams {
     const uint32_t *stage_off;  // [n_stages + 1] chains of each stage: chains of one stage do not read what another one of it writes
     int n_stages;
     int n_chains;
+};
+
+// Followers of overridden bones (rz_override_follow; kernels/fk.hip.h: FOLLOW): per instance the bones below an overridden bone, each with
+// the entry of its NEAREST overridden ancestor in the override table, ascending by bone. A block of its own like RzIkParams, handed to the
+// rz_fk_*follow_kernel entries only, which are launched only while entries exist: RzFkParams — embedded in the fused kernels' arguments —
+// does not change, and with the flag off (or nothing to follow) both pointers are null and every frame launches what it launched before.
+struct RzFollowParams {
+    const int *off;             // [I + 1] or nullptr
+    const uint2 *ent;           // [n] (follower bone, index into ovr_bone / ovr_world)
 };
 
 // rz_deform_kernel: fused morph + 4-bone LBS (engine/src/engine.ts:253-272).
@@ -353,6 +363,8 @@ size_t rz_fk_lds_bytes(const RzFkParams &p);      // dynamic LDS of rz_fk_kernel
 // second matrix buffer of their own — 48 B per bone more
 hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t instances, hipStream_t st);
 size_t rz_fk_ik_lds_bytes(const RzFkParams &p);
+// the same two solves with the follow stage (rz_fk_follow_kernel / rz_fk_ik_follow_kernel; `ik` null = no IK table): same LDS as their twins
+hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const RzFollowParams &fo, uint32_t instances, hipStream_t st);
 hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
                             uint32_t instances, hipStream_t st);
 size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v);

@@ -16,18 +16,22 @@ int check_ready(rz_ctx *c)
 int launch_fk(rz_ctx *c, hipStream_t st)
 {
     const RzFkParams fp = fk_params(c);
+    const RzFollowParams fo = follow_params(c);         // entries resident (rz_override_follow): the same solves with the follow stage
     if (c->ik_n) {              // the solve with the IK stage: a kernel of its own, launched only while a table is present
         const size_t lds = rz_fk_ik_lds_bytes(fp);
         if (lds > 160 * 1024)
             return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve with IK on the device: %u bones need %zu B of LDS (156 B per bone + the pose's morph weights: the IK stage keeps the local pose alive beside both matrix buffers; the limit is 160 KB)", c->B, lds);
-        HIP_TRY(rz_launch_fk_ik(fp, ik_params(c), c->I, st));
+        const RzIkParams ik = ik_params(c);
+        if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, &ik, fo, c->I, st));
+        else HIP_TRY(rz_launch_fk_ik(fp, ik, c->I, st));
         c->palette_stale = false; c->fk_stale = false;
         return RZ_OK;
     }
     const size_t lds = rz_fk_lds_bytes(fp);
     if (lds > 160 * 1024)
         return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve on the device: %u bones need %zu B of LDS (116 B per bone + the pose's morph weights; the limit is 160 KB)", c->B, lds);
-    HIP_TRY(rz_launch_fk(fp, c->I, st));
+    if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, nullptr, fo, c->I, st));
+    else HIP_TRY(rz_launch_fk(fp, c->I, st));
     c->palette_stale = false; c->fk_stale = false;
     return RZ_OK;
 }
@@ -260,6 +264,7 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     const RzQdefParams qd = qdef_params(c, pl);
     h = fnv(h, &qd, sizeof qd);
     if (c->ik_n) { const RzIkParams ik = ik_params(c); h = fnv(h, &ik, sizeof ik); }
+    if (c->ovr_follow) { const RzFollowParams fo = follow_params(c); h = fnv(h, &fo, sizeof fo); }
     const uint64_t misc[6] = { c->I, c->pose_local, c->pose_local_t, c->pose_sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }

@@ -408,12 +408,26 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // (RzDeformParams::fk_kind) and the generic form (KIND 0) otherwise. Same device functions, same bits.
 // IK (rz_fk_ik_kernel only, generic form): the PMX IK stage (kernels/ik.hip.h) runs between the doubling rounds and the override pass. The
 // stage re-forms local matrices, so region X must survive the rounds: they get `ik_m2`, a second matrix buffer of their own.
-template <bool FUSED, int KIND = 0, bool IK = false>
+// FOLLOW (rz_fk_follow_kernel / rz_fk_ik_follow_kernel only, generic form; rz_override_follow, defined by tests/follow_ref.py): bones below an
+// overridden bone follow it. With S the solved world matrices (hierarchy, bone morphs, IK), O the instance's overridden bones and O_a their
+// matrices, every bone b outside O with an ancestor in O takes  W_b = O_a * (S_a^-1 * S_b),  a = the NEAREST such ancestor along the
+// parents, S_a^-1 the rigid inverse (R^T, -R^T p: world matrices carry no scale); bones of O take O_a, all others keep S_b. So an override
+// below another override is absolute, the bones between the two follow the upper one and the bones below the lower one the lower one.
+// Nothing is re-evaluated: append rotation / move from an overridden or following append parent, IK chains below an overridden bone and
+// following bodies on follower bones see the solved pose. The host builds the (follower, override entry) list per instance from the
+// parents (plan.cpp: build_followers); the stage runs between the IK stage and the override write, while the solved rows in LDS are still
+// un-overridden: a lane reads S_a and S_b from LDS, O_a from the override table, and writes W_b over its own row. No follower reads a row
+// another follower writes (a is overridden, never a follower), so the stage needs no LDS of its own and one barrier: behind it, before
+// the override write replaces the S_a it read. Entries ascend by bone inside an
+// instance: consecutive lanes read rows 48 B apart, which a 16-lane group of a 16-byte LDS read spreads over all sixteen 16-byte slots of
+// a bank row (3 l mod 16 is a permutation), and lanes of one strand read the same S_a, which is a broadcast.
+template <bool FUSED, int KIND = 0, bool IK = false, bool FOLLOW = false>
 __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &early, const int inst, float4 *wl, unsigned char *scr, float *lds_mw,
                                          const bool to_global, const uint64_t st_tagv = 0ull, unsigned long long *fs = nullptr,
-                                         const RzIkParams *ik = nullptr, float4 *ik_m2 = nullptr)
+                                         const RzIkParams *ik = nullptr, float4 *ik_m2 = nullptr, const RzFollowParams *fol = nullptr)
 {
     static_assert(!IK || (!FUSED && KIND == 0), "the IK stage belongs to the generic solve of rz_fk_ik_kernel");
+    static_assert(!FOLLOW || (!FUSED && KIND == 0), "the follow stage belongs to the generic solve of the rz_fk_*follow_kernel entries");
     constexpr bool PLAIN = KIND != 0;
 #ifdef RZ_ABLATE
 #define RZ_FSTAMP(k) do { if (fs) fs[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -620,6 +634,30 @@ __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &ear
         }
     }
     const bool overrides = !PLAIN && p.ovr_off != nullptr;
+    if constexpr (FOLLOW) {
+        // followers of this instance's overridden bones: W_b = O_a * (S_a^-1 * S_b) over the follower's own row (the host launches this
+        // form only with an override table and follower entries resident)
+        for (int k = fol->off[inst] + tid; k < fol->off[inst + 1]; k += kBlock) {
+            const uint2 e = fol->ent[k];                    // (follower bone, entry of its nearest overridden ancestor in the override table)
+            const int b = (int)e.x, a = p.ovr_bone[e.y];
+            const float4 *m = reinterpret_cast<const float4 *>(p.ovr_world + (size_t)e.y * 16);
+            const float4 c0 = m[0], c1 = m[1], c2 = m[2], c3 = m[3];
+            const float4 a0 = src[a * 3], a1 = src[a * 3 + 1], a2 = src[a * 3 + 2];
+            const float4 s0 = src[b * 3], s1 = src[b * 3 + 1], s2 = src[b * 3 + 2];
+            // S_a^-1 * S_b: rotation R_a^T R_b, translation R_a^T (p_b - p_a)
+            const float dx = s0.w - a0.w, dy = s1.w - a1.w, dz = s2.w - a2.w;
+            const float4 r0 = make_float4(fmaf(a2.x, s2.x, fmaf(a1.x, s1.x, a0.x * s0.x)), fmaf(a2.x, s2.y, fmaf(a1.x, s1.y, a0.x * s0.y)),
+                                          fmaf(a2.x, s2.z, fmaf(a1.x, s1.z, a0.x * s0.z)), fmaf(a2.x, dz, fmaf(a1.x, dy, a0.x * dx)));
+            const float4 r1 = make_float4(fmaf(a2.y, s2.x, fmaf(a1.y, s1.x, a0.y * s0.x)), fmaf(a2.y, s2.y, fmaf(a1.y, s1.y, a0.y * s0.y)),
+                                          fmaf(a2.y, s2.z, fmaf(a1.y, s1.z, a0.y * s0.z)), fmaf(a2.y, dz, fmaf(a1.y, dy, a0.y * dx)));
+            const float4 r2 = make_float4(fmaf(a2.z, s2.x, fmaf(a1.z, s1.x, a0.z * s0.x)), fmaf(a2.z, s2.y, fmaf(a1.z, s1.y, a0.z * s0.y)),
+                                          fmaf(a2.z, s2.z, fmaf(a1.z, s1.z, a0.z * s0.z)), fmaf(a2.z, dz, fmaf(a1.z, dy, a0.z * dx)));
+            float4 w0, w1, w2;
+            affine_mul(make_float4(c0.x, c1.x, c2.x, c3.x), make_float4(c0.y, c1.y, c2.y, c3.y), make_float4(c0.z, c1.z, c2.z, c3.z), r0, r1, r2, w0, w1, w2);
+            src[b * 3] = w0; src[b * 3 + 1] = w1; src[b * 3 + 2] = w2;
+        }
+        __syncthreads();        // every S_a has been read: the override write below may replace it
+    }
     if (overrides) {
         // physics-driven bones: the supplied world matrix replaces the solved one (rows 0..2 of the column-major 4x4)
         for (int k = p.ovr_off[inst] + tid; k < p.ovr_off[inst + 1]; k += kBlock) {

@@ -62,6 +62,28 @@ __global__ void __launch_bounds__(kBlock) rz_fk_ik_kernel(const uint4 *k_rec, co
                              reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)));
 }
 
+// The two solves above with the follow stage (kernels/fk.hip.h: FOLLOW; rz_override_follow), launched instead of them only while an
+// override table AND follower entries are resident. Same LDS as their twins.
+__global__ void __launch_bounds__(kBlock) rz_fk_follow_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzFollowParams fo)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
+    unsigned char *scr = smem + (size_t)p.B * 48;
+    fk_solve<false, 0, false, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(scr + rz_fk_scratch_bytes(p.B)), true,
+                                    0ull, nullptr, nullptr, nullptr, &fo);
+}
+
+__global__ void __launch_bounds__(kBlock) rz_fk_ik_follow_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik,
+                                                                 const RzFollowParams fo)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
+    unsigned char *scr = smem + (size_t)p.B * 48;
+    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
+    fk_solve<false, 0, true, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
+                                   reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), &fo);
+}
+
 // ------------------------------------------------------------------------------------------------
 // rz_pull_pose_kernel: a crowd's per-frame pose (0.8 - 3.3 MB for 256 characters) comes down by a PULL. The host lays the pose out in
 // a pinned, device-mapped ring slot; 16 workgroups read it over the host link with 16-byte loads (1 KiB contiguous per wave
@@ -202,6 +224,21 @@ hipError_t rz_launch_fk(const RzFkParams &p, uint32_t instances, hipStream_t st)
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(rz_fk_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p);
+    return hipGetLastError();
+}
+
+hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const RzFollowParams &fo, uint32_t instances, hipStream_t st)
+{
+    const size_t lds = ik ? rz_fk_ik_lds_bytes(p) : rz_fk_lds_bytes(p);
+    // (the host checks the LDS first and says why: launch_fk in frame.cpp; the stage reads the override table through every entry)
+    if (lds > 160 * 1024 || !fo.off || !fo.ent || !p.ovr_off || (ik && (!ik->chain || ik->n_stages <= 0))) return hipErrorInvalidValue;
+    const void *fn = ik ? reinterpret_cast<const void *>(rz_fk_ik_follow_kernel) : reinterpret_cast<const void *>(rz_fk_follow_kernel);
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    if (ik) hipLaunchKernelGGL(rz_fk_ik_follow_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, *ik, fo);
+    else hipLaunchKernelGGL(rz_fk_follow_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, fo);
     return hipGetLastError();
 }
 

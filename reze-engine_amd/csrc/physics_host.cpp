@@ -47,6 +47,11 @@ static int ensure_instances(rz_ctx *c)
         for (size_t k = 0; k < nd; ++k) bones[i * nd + k] = ph.dyn_bone[k];
     HIP_TRY(hipMemcpy(c->ovr_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
     if (n) HIP_TRY(hipMemcpy(c->ovr_bone, bones.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    c->fol_count = 0;
+    if (c->ovr_follow) {                // rz_override_follow: the bones below the dynamic bodies' bones, with the set they follow
+        bones.resize(n);
+        if (int r = upload_followers(c, off, bones)) return r;
+    }
     ph.I = c->I;
     ph.reset = true;
     return RZ_OK;

@@ -194,8 +194,9 @@ Plan make_plan(const rz_ctx *c)
     // mode (and 27.7 -> 24.5 us on a 1/8 shard of C5); local poses 12.7-14.4 -> 9.8-12.8 us without dense morphs, no gain
     // with them (there the three-kernel frame keeps its kernel-argument morph list and streams from its first instruction).
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
-    // (an IK table keeps the solve in a kernel of its own, rz_fk_ik_kernel: the fused kernels carry no IK stage)
-    pl.fuse_fk = c->ik_n == 0 && c->I == 1 && c->pose_local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
+    // (an IK table keeps the solve in a kernel of its own, rz_fk_ik_kernel: the fused kernels carry no IK stage; nor the follow stage of
+    // rz_override_follow, so resident follower entries keep the solve with rz_fk_follow_kernel)
+    pl.fuse_fk = c->ik_n == 0 && !follow_params(c).off && c->I == 1 && c->pose_local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
                  (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pose_sampled || c->morph_mode != 1)));
     const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
@@ -550,6 +551,70 @@ RzFkParams fk_params(const rz_ctx *c)
         q.morph_w = c->morph_w; q.M = (int)c->M;
     }
     return p;
+}
+
+RzFollowParams follow_params(const rz_ctx *c)
+{
+    RzFollowParams p;
+    memset(&p, 0, sizeof p);
+    if (c->ovr_follow && c->ovr_count && c->fol_count) { p.off = c->fol_off; p.ent = c->fol_ent; }
+    return p;
+}
+
+void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent)
+{
+    const size_t I = off.empty() ? 0 : off.size() - 1;
+    const int B = (int)c->B;
+    fol_off.assign(I + 1, 0);
+    ent.clear();
+    // near[b]: the override entry bone b takes its matrix from — its own when it is overridden, else its nearest overridden ancestor's
+    // (-1 = none above it). Parents may come in any order, so a bone's chain is walked up to the first bone already known.
+    constexpr int kUnknown = -2;
+    std::vector<int> near(B), chain;
+    for (size_t i = 0; i < I; ++i) {
+        fol_off[i] = (int)ent.size();
+        if (off[i] == off[i + 1]) continue;
+        std::fill(near.begin(), near.end(), kUnknown);
+        for (int k = off[i]; k < off[i + 1]; ++k) near[bones[k]] = k;
+        for (int b = 0; b < B; ++b) {
+            chain.clear();
+            int cur = b;
+            while (cur >= 0 && near[cur] == kUnknown) { chain.push_back(cur); cur = (int32_t)c->fk_host[4 * (size_t)cur].x; }
+            const int found = cur < 0 ? -1 : near[cur];
+            for (int x : chain) near[x] = found;
+        }
+        for (int b = 0; b < B; ++b)
+            if (near[b] >= 0 && bones[near[b]] != b) ent.push_back(make_uint2((uint32_t)b, (uint32_t)near[b]));
+    }
+    fol_off[I] = (int)ent.size();
+}
+
+int reserve_followers(rz_ctx *c, size_t entries, size_t offsets)
+{
+    if (entries <= c->fol_alloc && offsets <= c->fol_off_alloc) return RZ_OK;
+    if (int r = drain(c)) return r;
+    drop_graph(c);
+    dfree(c->fol_off); dfree(c->fol_ent);
+    c->fol_alloc = c->fol_off_alloc = 0;
+    c->fol_count = 0;
+    const size_t cap = std::max<size_t>(entries, 64), ocap = std::max(offsets, c->ovr_off_alloc);
+    HIP_TRY(hipMalloc(&c->fol_off, ocap * sizeof(int)));
+    HIP_TRY(hipMalloc(&c->fol_ent, cap * sizeof(uint2)));
+    c->fol_alloc = cap; c->fol_off_alloc = ocap;
+    return RZ_OK;
+}
+
+int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones)
+{
+    std::vector<int> fol_off;
+    std::vector<uint2> ent;
+    build_followers(c, off, bones, fol_off, ent);
+    c->fol_count = 0;
+    if (int r = reserve_followers(c, ent.size(), fol_off.size())) return r;
+    HIP_TRY(hipMemcpy(c->fol_off, fol_off.data(), fol_off.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!ent.empty()) HIP_TRY(hipMemcpy(c->fol_ent, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    c->fol_count = (uint32_t)ent.size();
+    return RZ_OK;
 }
 
 RzIkParams ik_params(const rz_ctx *c)

@@ -778,7 +778,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
 {
     if (int r = use(c)) return r;
     if (c->ph.nb) return fail(RZ_ERR_INVALID, "rz_override_world while a physics table is resident: rz_physics_step writes the override table (remove the table with rz_upload_physics(ctx, NULL) first)");
-    if (n == 0) { c->ovr_count = 0; return RZ_OK; }
+    if (n == 0) { c->ovr_count = 0; c->ovr_off_host.clear(); c->ovr_bone_host.clear(); return RZ_OK; }
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_override_world applies to device-solved poses: call rz_upload_skeleton_topology first");
     if (!bone || !world16) return fail(RZ_ERR_INVALID, "null override arrays");
     // sort by (instance, bone); of several entries for one bone the LAST wins, like successive boneWorldMatrices.set() calls
@@ -815,10 +815,20 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
         HIP_TRY(hipMalloc(&c->ovr_bone, c->ovr_alloc * sizeof(int)));
         HIP_TRY(hipMalloc(&c->ovr_world, c->ovr_alloc * 16 * sizeof(float)));
     }
-    // one pinned ring slot carries offsets | bones | matrices down the compute stream, in order with the frames
+    // rz_override_follow: per-instance sets differ, so the follower lists are rebuilt with every set and travel with it
+    std::vector<int> fol_off;
+    std::vector<uint2> fol_ent;
+    if (c->ovr_follow) {
+        build_followers(c, off, bones, fol_off, fol_ent);
+        c->fol_count = 0;
+        if (int r = reserve_followers(c, fol_ent.size(), fol_off.size())) return r;
+    }
+    // one pinned ring slot carries offsets | bones | matrices (| follower offsets | follower entries) down the compute stream, in order
+    // with the frames
     const size_t b_off = off.size() * sizeof(int), b_bone = m * sizeof(int), b_mat = m * 16 * sizeof(float);
+    const size_t b_pad = (b_off + b_bone + b_mat + 7) & ~(size_t)7, b_foff = fol_off.size() * sizeof(int), b_fent = fol_ent.size() * sizeof(uint2);
     int slot = 0;
-    if (int r = stage_acquire(c, std::max<size_t>(b_off + b_bone + b_mat, 4096), &slot)) return r;
+    if (int r = stage_acquire(c, std::max<size_t>(b_pad + b_foff + b_fent, 4096), &slot)) return r;
     char *st = static_cast<char *>(c->stage[slot]);
     memcpy(st, off.data(), b_off);
     memcpy(st + b_off, bones.data(), b_bone);
@@ -827,9 +837,48 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
     HIP_TRY(hipMemcpyAsync(c->ovr_off, st, b_off, hipMemcpyHostToDevice, us));
     HIP_TRY(hipMemcpyAsync(c->ovr_bone, st + b_off, b_bone, hipMemcpyHostToDevice, us));
     HIP_TRY(hipMemcpyAsync(c->ovr_world, st + b_off + b_bone, b_mat, hipMemcpyHostToDevice, us));
+    if (c->ovr_follow) {
+        memcpy(st + b_pad + b_fent, fol_off.data(), b_foff);        // (the 8-byte entries first: aligned)
+        HIP_TRY(hipMemcpyAsync(c->fol_off, st + b_pad + b_fent, b_foff, hipMemcpyHostToDevice, us));
+        if (b_fent) {
+            memcpy(st + b_pad, fol_ent.data(), b_fent);
+            HIP_TRY(hipMemcpyAsync(c->fol_ent, st + b_pad, b_fent, hipMemcpyHostToDevice, us));
+        }
+    }
     HIP_TRY(hipEventRecord(c->stage_ev[slot], us));
     c->stage_used[slot] = true;
     c->ovr_count = (uint32_t)m;
+    if (c->ovr_follow) c->fol_count = (uint32_t)fol_ent.size();
+    c->ovr_off_host = std::move(off); c->ovr_bone_host = std::move(bones);
+    return RZ_OK;
+}
+
+int rz_override_follow(rz_ctx *c, uint32_t on)
+{
+    if (int r = use(c)) return r;
+    if (on > 1) return fail(RZ_ERR_INVALID, "rz_override_follow: on must be 0 or 1 (got %u)", on);
+    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+        return fail(RZ_ERR_INVALID, "rz_override_follow needs the hierarchy: call rz_upload_skeleton_topology first");
+    if ((int)on == c->ovr_follow) return RZ_OK;
+    if (int r = drain(c)) return r;
+    drop_graph(c);
+    c->fol_count = 0;
+    if (on) {
+        // an override set is resident: its follower lists now (a later set brings its own). A physics table's set is laid out with its
+        // per-instance buffers and outlives a reset, so it counts as resident once those exist for the current crowd.
+        if (c->ph.nb && c->ph.state && c->ph.I == c->I) {
+            const size_t I = c->I, nd = c->ph.nd;
+            std::vector<int> off(I + 1), bones(I * nd);
+            for (size_t i = 0; i <= I; ++i) off[i] = (int)(i * nd);
+            for (size_t i = 0; i < I; ++i)
+                for (size_t k = 0; k < nd; ++k) bones[i * nd + k] = c->ph.dyn_bone[k];
+            if (int r = upload_followers(c, off, bones)) return r;
+        } else if (!c->ph.nb && c->ovr_count) {
+            if (int r = upload_followers(c, c->ovr_off_host, c->ovr_bone_host)) return r;
+        }
+    }
+    c->ovr_follow = (int)on;
+    if (c->ovr_count) c->fk_stale = true;       // world matrices and palettes in memory are the other setting's: rz_read_world / rz_read_palette solve again
     return RZ_OK;
 }
 

@@ -265,6 +265,8 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "physics_springs")) *value = c->ph.springs.on;
     else if (!strcmp(key, "physics_spring_axes")) *value = (int)c->ph.springs.axes;
     else if (!strcmp(key, "physics_lds")) *value = c->ph.nb ? (int)rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0;
+    else if (!strcmp(key, "override_follow")) *value = c->ovr_follow;
+    else if (!strcmp(key, "override_followers")) *value = follow_params(c).off ? (int)c->fol_count : 0;     // entries resident over all instances
     else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;

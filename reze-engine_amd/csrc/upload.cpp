@@ -151,6 +151,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
     c->ovr_count = 0;
+    c->ovr_follow = 0; c->fol_count = 0;        // rz_override_follow goes with the hierarchy it was set for
     dfree(c->inv_bind);
     HIP_TRY(hipMalloc(&c->inv_bind, (size_t)B * 16 * sizeof(float)));
     HIP_TRY(hipMemcpy(c->inv_bind, inverse_bind16, (size_t)B * 16 * sizeof(float), hipMemcpyHostToDevice));
@@ -334,6 +335,7 @@ int rz_upload_skeleton_topology(rz_ctx *c, uint32_t B, const int32_t *parents, c
     free_ik(c);                         // its chains were checked against the old parents
     free_physics(c);                    // its bind pose was taken from the old hierarchy
     c->ovr_count = 0;
+    c->ovr_follow = 0; c->fol_count = 0;        // rz_override_follow: the follower lists were built from the old parents
     c->fk_stale = false;                // (a crowd frame solved under the old topology: nothing of it can be formed on demand any more)
     dfree(c->fk_anc_more);
     if (!more.empty())

@@ -75,6 +75,11 @@ class Engine {
     // upload and ahead of the contacts
     this.physicsSprings = o.physicsSprings === true
     if (this.physicsSprings && !this.devicePhysics) throw new Error('physicsSprings needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
+    // followOverrides: bones below an overridden bone follow it (rz_override_follow; the definition is tests/follow_ref.py), for the
+    // overrides devicePhysics writes and for those fed through setBoneWorldOverrides; set on every shard behind the topology upload, and
+    // on every fork. The stage is the device hierarchy solve's: host FK users call Model.followOverrides from their { physics } hook.
+    this.followOverrides = o.followOverrides === true
+    if (this.followOverrides && !this.deviceFK) throw new Error('followOverrides needs new Engine(canvas, { deviceFK: true }); with host FK call Model.followOverrides from the { physics } hook')
     this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
     this.physicsResident = false
     this.native = null
@@ -161,6 +166,7 @@ class Engine {
     if (this.framesInFlight !== 2 || (this.autotune && !this.tuned)) { s.last = s.ctx; return s.ctx }
     if (!s.fork) { // made after the launch-shape search, so that it inherits the tuned plan
       s.fork = this.native.fork(s.ctx)
+      if (this.followOverrides) this.native.overrideFollow(s.fork, 1) // (rz_fork hands the flag down already: said again, so a fork never depends on when its lender was set)
       if (this.overrides) this.native.overrideWorld(s.fork, this.overrides[0], this.overrides[1], this.overrides[2])
     }
     s.flip ^= 1
@@ -240,6 +246,7 @@ class Engine {
           }
         })
         n.uploadSkeletonTopology(s.ctx, parents, bind, ap, ar, am)
+        if (this.followOverrides) n.overrideFollow(s.ctx, 1) // a new topology cleared it
         // IK is per skeleton, not per vertex: every shard gets the same table, after the topology its chains are checked against
         const chains = this.ik ? model.getIKChains() : []
         if (chains.length > 0) {

@@ -84,6 +84,7 @@ class Model {
     this._app = new Float32Array(16)
     this._tmpA = new Float32Array(16)
     this._tmpB = new Float32Array(16)
+    this._follow = new Float64Array(12) // followOverrides(): S_a^-1 S_b, rows
     this._tr = new Float32Array(16)
     this._q = [0, 0, 0, 1]
 
@@ -360,6 +361,62 @@ class Model {
 
   /** Switch the host IK solve on or off (a model without IK bones stays off). */
   setIK(on) { this.ikEnabled = !!on && this.getIKChains().length > 0 }
+
+  /**
+   * Bones below an overridden bone follow it: the host twin of the device stage rz_override_follow (csrc/kernels/fk.hip.h: FOLLOW), the
+   * definition of tests/follow_ref.py in doubles with f32 stores. `world` holds the SOLVED world matrices S (n x 16, column-major: what
+   * computeWorldMatrices() left, before a physics hook wrote into it) and is rewritten in place; `bones` / `matrices` (16 floats each)
+   * are the override set O, of several entries for one bone the last. Every bone b outside O with an ancestor in O takes
+   * W_b = O_a (S_a^-1 S_b), a the NEAREST such ancestor along the parents and S_a^-1 the rigid inverse (R^T, -R^T p); bones of O take
+   * O_a; all others keep S_b. An override below another override is absolute. Nothing is evaluated again on the followed pose (append
+   * transforms, IK). For host-FK users of the { physics } hook: call it from the hook with a copy of the matrices taken on entry.
+   */
+  followOverrides(world, bones, matrices) {
+    const sk = this.skeleton.bones, n = sk.length
+    if (matrices.length !== bones.length * 16) throw new Error('followOverrides: ' + bones.length + ' bones need ' + bones.length * 16 + ' matrix floats')
+    if (world.length !== n * 16) throw new Error('followOverrides: world holds ' + world.length + ' floats, the skeleton has ' + n + ' bones')
+    const own = new Int32Array(n).fill(-1)
+    for (let k = 0; k < bones.length; k++) {
+      if (!(bones[k] >= 0 && bones[k] < n)) throw new Error('followOverrides: bone ' + bones[k] + ' out of range')
+      own[bones[k]] = k
+    }
+    // near[b]: the entry bone b takes its matrix from (-1 = no bone above it is overridden, -2 = not known yet); parents may come in any order
+    const near = new Int32Array(n).fill(-2)
+    const chain = []
+    for (let b = 0; b < n; b++) {
+      chain.length = 0
+      let cur = b
+      while (cur >= 0 && near[cur] === -2 && own[cur] < 0) { chain.push(cur); cur = sk[cur].parentIndex }
+      const found = cur < 0 ? -1 : own[cur] >= 0 ? own[cur] : near[cur]
+      if (cur >= 0 && own[cur] >= 0) near[cur] = own[cur]
+      for (const x of chain) near[x] = found
+    }
+    const S = Float64Array.from(world) // followers read S_a after bone a itself has been rewritten
+    for (let b = 0; b < n; b++) {
+      const k = near[b]
+      if (k < 0) continue
+      const o = k * 16, wb = b * 16
+      if (own[b] >= 0) {
+        for (let c = 0; c < 4; c++) { world[wb + c * 4] = matrices[o + c * 4]; world[wb + c * 4 + 1] = matrices[o + c * 4 + 1]; world[wb + c * 4 + 2] = matrices[o + c * 4 + 2]; world[wb + c * 4 + 3] = c === 3 ? 1 : 0 }
+        continue
+      }
+      const a = bones[k] * 16
+      // rel = S_a^-1 S_b: rows i of R_a^T are columns i of S_a
+      const dx = S[wb + 12] - S[a + 12], dy = S[wb + 13] - S[a + 13], dz = S[wb + 14] - S[a + 14]
+      const rel = this._follow
+      for (let i = 0; i < 3; i++) {
+        const ax = S[a + i * 4], ay = S[a + i * 4 + 1], az = S[a + i * 4 + 2]
+        for (let j = 0; j < 3; j++) rel[i * 4 + j] = ax * S[wb + j * 4] + ay * S[wb + j * 4 + 1] + az * S[wb + j * 4 + 2]
+        rel[i * 4 + 3] = ax * dx + ay * dy + az * dz
+      }
+      // W_b = O_a rel, upper three rows
+      for (let i = 0; i < 3; i++) {
+        const o0 = matrices[o + i], o1 = matrices[o + 4 + i], o2 = matrices[o + 8 + i]
+        for (let j = 0; j < 4; j++) world[wb + j * 4 + i] = o0 * rel[j] + o1 * rel[4 + j] + o2 * rel[8 + j] + (j === 3 ? matrices[o + 12 + i] : 0)
+      }
+      world[wb + 3] = 0; world[wb + 7] = 0; world[wb + 11] = 0; world[wb + 15] = 1
+    }
+  }
 
   /**
    * PMX inverse kinematics on the host: CCD in the clamp form, the arithmetic of tests/ik_ref.py (the definition; GPU twin:

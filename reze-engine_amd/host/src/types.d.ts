@@ -127,6 +127,7 @@ export interface DeformAddon {
   physicsReset(ctx: DeformContext): void
   physicsContacts(ctx: DeformContext, on: 0 | 1 | 2 | 3): void
   physicsSprings(ctx: DeformContext, on: 0 | 1): void
+  overrideFollow(ctx: DeformContext, on: 0 | 1): void
   readPhysics(ctx: DeformContext, instance: number, state13: Float32Array): void
   enableAabb(ctx: DeformContext, on: boolean): void
   setInstances(ctx: DeformContext, count: number): void
@@ -190,7 +191,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; followOverrides?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }
