@@ -131,28 +131,19 @@ void point_pose_at(rz_ctx *c, float *block)
 
 void point_pose_slot(rz_ctx *c, int k)
 {
-    c->pose_slot = k;
-    point_pose_at(c, c->pose_blk[k]);
-}
-
-// (callers have drained both streams)
-void free_big_ring(rz_ctx *c)
-{
-    for (int k = 0; k < rz_ctx::kBigBlocks; ++k) dfree(c->big_blk[k]);
-    c->big_floats = 0;
-    c->big_uploads = 0;
-    c->big_ev_seq[0] = c->big_ev_seq[1] = ~0ull;
+    c->pl.pose_slot = k;
+    point_pose_at(c, c->pl.pose_blk[k]);
 }
 
 int ensure_pose_buffers(rz_ctx *c)
 {
     if (c->B == 0) return RZ_OK;
     const uint32_t Mq = std::max<uint32_t>(c->M, 1);
-    if (c->I <= c->pose_alloc_I && c->B <= c->pose_alloc_B && Mq <= c->pose_alloc_M && c->world) return RZ_OK;
+    if (c->I <= c->pl.alloc_I && c->B <= c->pl.alloc_B && Mq <= c->pl.alloc_M && c->world) return RZ_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
-    for (int k = 0; k < 2; ++k) dfree(c->pose_blk[k]);
-    free_big_ring(c);
+    for (int k = 0; k < 2; ++k) c->pl.pose_blk[k] = {};
+    c->pl.big = {};
     c->world = nullptr; c->morph_w = nullptr; c->local_q = nullptr;
     for (int k = 0; k < 2; ++k) { dfree(c->palette_ring[k]); dfree(c->act_idx_ring[k]); dfree(c->act_w_ring[k]); dfree(c->act_count_ring[k]); c->skin_recorded[k] = false; }
     c->palette = nullptr; c->act_idx = nullptr; c->act_w = nullptr; c->act_count = nullptr;
@@ -160,8 +151,8 @@ int ensure_pose_buffers(rz_ctx *c)
     const size_t Mpad = round_up(Mq + 8, 4);
     const size_t blk_floats = I * B * 16 + ((I * Mq + 3) / 4 * 4) + I * B * 7 + 4;      // + 4: the prefetch helper copies whole 16-byte cells
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipMalloc(&c->pose_blk[k], blk_floats * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(c->pose_blk[k], 0, blk_floats * sizeof(float), c->stream));
+        HIP_TRY(c->pl.pose_blk[k].alloc(blk_floats));
+        HIP_TRY(hipMemsetAsync(c->pl.pose_blk[k], 0, blk_floats * sizeof(float), c->stream));
     }
     point_pose_slot(c, 0);
     for (int k = 0; k < 2; ++k) {
@@ -175,13 +166,12 @@ int ensure_pose_buffers(rz_ctx *c)
         HIP_TRY(hipMemsetAsync(c->act_count_ring[k], 0, I * sizeof(int), c->stream));
     }
     set_ring(c, 0);
-    if (!c->zc_tag) HIP_TRY(hipMalloc(&c->zc_tag, 2 * sizeof(uint64_t)));
-    HIP_TRY(hipMemsetAsync(c->zc_tag, 0, 2 * sizeof(uint64_t), c->stream));
-    c->zc_epoch++;                      // poses staged under the old layout must never match again
-    c->zc_seq_cur = 0;
+    if (!c->pl.tag) HIP_TRY(c->pl.tag.alloc(2));
+    HIP_TRY(hipMemsetAsync(c->pl.tag, 0, 2 * sizeof(uint64_t), c->stream));
+    retire_pose_tags(c);                // poses staged under the old layout must never match again
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->pose_alloc_I = I; c->pose_alloc_B = B; c->pose_alloc_M = Mq;
-    c->pose_set = false;
+    c->pl.alloc_I = I; c->pl.alloc_B = B; c->pl.alloc_M = Mq;
+    c->pl.cur.set = false;
     return RZ_OK;
 }
 
@@ -193,7 +183,7 @@ void free_animation(rz_ctx *c)
     dfree(c->an_key_frame); dfree(c->an_key_pos); dfree(c->an_mkey_frame); dfree(c->an_mkey_weight); dfree(c->an_feed_ratio);
     dfree(c->an_key_rot); dfree(c->an_key_interp);
     c->has_animation = false;
-    if (c->pose_sampled) { c->pose_sampled = false; c->pose_set = false; }
+    if (c->pl.cur.sampled) { c->pl.cur.sampled = false; c->pl.cur.set = false; }
 }
 
 void free_motions(rz_ctx *c)
@@ -264,8 +254,8 @@ void free_morphs(rz_ctx *c)
     dfree(c->dense); dfree(c->sp_ptr); dfree(c->sp_entries);
     free_bone_morphs(c);                  // their entries name morphs of the old set
     c->morph_mode = 0; c->M = 0; c->Mpad = 12; c->sp_count = 0;
-    c->zc_epoch++; c->zc_seq_cur = 0;     // ... and so does a pose staged ahead of its frame
-    c->pose_set = false;                  // morph weights belong to the old target set
+    retire_pose_tags(c);                  // ... and so does a pose staged ahead of its frame
+    c->pl.cur.set = false;                // morph weights belong to the old target set
 }
 
 }  // namespace rzi
@@ -324,20 +314,17 @@ int rz_create(int device, rz_ctx **out)
         return fail(RZ_ERR_NO_DEVICE, "device %d is %s; this library carries gfx950 (MI355X) code only", device,
                     prop.gcnArchName);
     rz_ctx *c = new rz_ctx();
-    memset(&c->ml, 0, sizeof c->ml);
+    memset(&c->pl.cur.ml, 0, sizeof c->pl.cur.ml);
     c->device = device;
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (se == hipSuccess) se = hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking);
     for (int k = 0; k < 2 && se == hipSuccess; ++k) {
-        se = hipEventCreateWithFlags(&c->big_ev[k], hipEventDisableTiming);
-        if (se == hipSuccess) se = hipEventCreateWithFlags(&c->ev_front[k], hipEventDisableTiming);
+        se = hipEventCreateWithFlags(&c->ev_front[k], hipEventDisableTiming);
         if (se == hipSuccess) se = hipEventCreateWithFlags(&c->ev_skin[k], hipEventDisableTiming);
     }
     if (se == hipSuccess) se = hipEventCreate(&c->ev0);
     if (se == hipSuccess) se = hipEventCreate(&c->ev1);
-    for (int i = 0; i < kStageSlots && se == hipSuccess; ++i)
-        se = hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming);
     if (se != hipSuccess) {
         rz_destroy(c);
         return fail(RZ_ERR_HIP, "context setup failed: %s", hipGetErrorString(se));
@@ -370,17 +357,12 @@ int rz_destroy(rz_ctx *c)
     dfree(c->fk_rec); dfree(c->fk_anc_more);
     free_animation(c); free_motions(c); free_motion_masks(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c);
     // ... and what the context owns
-    dfree(c->rj01); dfree(c->rj23); dfree(c->sub_list); dfree(c->sub_count); dfree(c->zc_tag);
+    dfree(c->rj01); dfree(c->rj23); dfree(c->sub_list); dfree(c->sub_count);
     dfree(c->subfk_rec); dfree(c->subfk_count);
-    dfree(c->an_frames); dfree(c->mo_states); dfree(c->mo_layers);
-    dfree(c->pose_blk[0]); dfree(c->pose_blk[1]);
-    free_big_ring(c);
+    c->pl = {};                           // the pose transport: blocks, rings, events
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
     dfree(c->fol_off); dfree(c->fol_ent);
     free_physics(c);
-    for (int k = 0; k < 2; ++k) {
-        if (c->big_ev[k]) (void)hipEventDestroy(c->big_ev[k]);
-    }
     for (int k = 0; k < 2; ++k) {
         dfree(c->palette_ring[k]); dfree(c->act_idx_ring[k]); dfree(c->act_w_ring[k]); dfree(c->act_count_ring[k]);
         if (c->ev_front[k]) (void)hipEventDestroy(c->ev_front[k]);
@@ -394,14 +376,6 @@ int rz_destroy(rz_ctx *c)
     if (c->gate_host) { (void)hipHostFree(c->gate_host); c->gate_host = nullptr; }
 #endif
     dfree(c->out_hull); dfree(c->aabb);
-    for (int i = 0; i < kStageSlots; ++i) {
-        if (c->stage[i]) (void)hipHostFree(c->stage[i]);
-        if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
-    }
-    for (int i = 0; i < rz_ctx::kZcSlots; ++i)
-        if (c->zc_host[i]) (void)hipHostFree(c->zc_host[i]);
-    for (int e = 0; e < 2; ++e)
-        if (c->zc_ev[e]) (void)hipEventDestroy(c->zc_ev[e]);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->up_stream) (void)hipStreamDestroy(c->up_stream);

@@ -2,10 +2,12 @@
 // plumbing, the frame plan, and the internal entry points of each unit. Nothing here is part of the C ABI (include/reze_deform.h);
 // everything internal lives in namespace rzi with hidden visibility.
 // The context is three parts, and rz_fork follows them: a fork BORROWS RzStatic (a copy of the struct, the lender's pointers), INHERITS RzTuning
-// (by value), and OWNS everything else (streams, pose slots, palettes, outputs, and physics: one member, RzPhysics ph, empty in a fresh fork).
+// (by value), and OWNS everything else: streams, palettes, outputs, and two members that are empty in a fresh fork — the per-frame pose
+// transport (RzPoseLink pl: its rings, and where the current pose is) and physics (RzPhysics ph).
 //   core.cpp    context life cycle, buffers every unit sizes, error state            rz_create / rz_destroy / rz_fork / rz_sync ...
 //   upload.cpp  static data: mesh, skeleton, topology, morph targets, motion            rz_upload_* / rz_set_instances / rz_shard_range
-//   pose.cpp    per-frame inputs: pinned ring, zero-copy slots, copies                  rz_set_pose* / rz_override_world / rz_read_world
+//   pose.cpp    per-frame inputs: RzPoseLink's rings and transitions, copies            rz_set_pose* / rz_override_world / rz_read_world
+//   pose_ring.h the reuse proof of the zero-copy and big-pose rings (no HIP)            (no exports)
 //   plan.cpp    launch shapes and the parameter blocks of the kernels                   (no exports)
 //   frame.cpp   launching frames, replay, timing, readbacks                             rz_deform* / rz_time_frames / rz_read*
 //   tune.cpp    launch-shape search and the tuning keys                                 rz_autotune* / rz_set_tuning / rz_get_tuning
@@ -29,6 +31,7 @@
 
 #include "deform_kernels.h"
 #include "physics_table.h"
+#include "pose_ring.h"
 
 #pragma GCC visibility push(hidden)
 namespace rzi {
@@ -59,6 +62,38 @@ template <class T> struct Scratch {
     ~Scratch() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
     operator T *() const { return p; }
+};
+
+// Pinned host memory with one owner, in Scratch's way, and its device address where the device can read it in place.
+struct Pinned {
+    void *host = nullptr, *dev = nullptr;
+    Pinned &operator=(Pinned &&o) noexcept { std::swap(host, o.host); std::swap(dev, o.dev); return *this; }
+    ~Pinned() { if (host) (void)hipHostFree(host); }
+    // device-mapped where that can be had; `must_map` = false: memory that cannot be mapped is still good for copies (dev stays null)
+    hipError_t alloc(size_t bytes, bool must_map)
+    {
+        hipError_t e = hipHostMalloc(&host, bytes, hipHostMallocMapped);
+        if (e != hipSuccess) host = nullptr;
+        else if ((e = hipHostGetDevicePointer(&dev, host, 0)) == hipSuccess) return e;
+        (void)hipGetLastError();
+        dev = nullptr;
+        if (must_map || host) return must_map ? e : hipSuccess;
+        return hipHostMalloc(&host, bytes, hipHostMallocDefault);
+    }
+};
+
+// N events without timing, one owner. A ring's events are made when the ring is built (a drain, rare), never on a per-frame path.
+template <int N> struct Events {
+    hipEvent_t e[N] = {};
+    Events &operator=(Events &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipError_t create()
+    {
+        hipError_t r = hipSuccess;
+        for (int i = 0; i < N && r == hipSuccess; ++i) r = hipEventCreateWithFlags(&e[i], hipEventDisableTiming);
+        return r;
+    }
+    hipEvent_t operator[](int i) const { return e[i]; }
 };
 
 constexpr uint32_t kVertPad = 1024;   // planes are padded to a whole S=1 tile (256 quads)
@@ -206,26 +241,113 @@ struct RzPhysics {
     } springs;
 };
 
+// The per-frame pose transport (pose.cpp): where the current pose is, how it got there, and which slot of which ring may be written next. A
+// fork's own, and empty from the start. Pinned slots, device blocks and events have their owners here: a ring is re-allocated by building its
+// replacement, draining and assigning it, and the whole transport is released by resetting this struct.
+struct RzPoseLink {
+    // Two device blocks per context, and a ring of them for big poses: [world I*B*16 | morph weights pad4(I*max(M,1)) | local rotations I*B*4 | local
+    // translations I*B*3] floats. A world-matrix pose fills [world | weights], a local pose [weights | rotations (| translations)] — each a
+    // CONTIGUOUS range, so every upload is one copy (measured: a small H2D copy is a 4.5 us blit kernel on this runtime, and a second one for 256
+    // bytes of morph weights cost as much as the first). The offsets are those of the instance / bone / morph counts AT UPLOAD TIME
+    // (point_pose_slot): shrinking the crowd afterwards leaves the resident pose where it is.
+    rzi::Scratch<float> pose_blk[2];
+    int pose_slot = 0;
+    size_t alloc_I = 0, alloc_B = 0, alloc_M = 0;       // what the blocks (and the context's palette ring) were sized for
+
+    // The pinned staging ring: everything per-frame that is copied or pulled to the device goes through a slot of it — poses, the frames of a sampled
+    // pose, motion states and layers, override sets and their follower lists. ev[slot] = what was sent out of the slot has landed: the host polls it
+    // before the slot's next use, kStageSlots uploads later, and the compute stream waits for it where the pose travelled on the upload stream
+    // (staged_sent).
+    struct Stage {
+        rzi::Pinned slot[kStageSlots];  // (dev null: this ring can only be copied from)
+        size_t bytes = 0;
+        rzi::Events<kStageSlots> ev;
+        bool used[kStageSlots] = {};
+        int next = 0;
+    } stage;
+
+    // Zero-copy poses (one character, <= 256 KB): rz_set_pose* only writes the pose into a slot of this pinned, device-mapped ring — no copy is
+    // enqueued at all. The first frame's kernels read it over the host link (rz_fk_kernel the local pose; the one-launch deform kernel the world
+    // matrices, whose workgroup 0 also leaves them in the device pose block for the frames that replay the pose); anything that needs a
+    // device-resident pose first (rz_prep_kernel) gets it through make_resident(). Measured on MI355X (tools/archive/uploadbench): a 16.6 KB
+    // hipMemcpyAsync in front of a frame costs 18 us, two of <= 16 KB 9.5 us, reading the pinned slot from the kernel 7 us with the loads fully
+    // exposed. A slot is reused kSlots uploads later; that its readers are done is `proof`'s to say (pose_ring.h), so there is no per-frame marker.
+    // One hipEventRecord per kSlots / 2 uploads, and a record costs ~1.4 us of stream time: measured on a 1/8 shard of C5
+    // (tools/archive/live_shard.py, per-frame-pose loop over the resident replay): 8 slots +0.86 us per frame, 16 slots +0.50 us, 32 slots +0.37 us.
+    // 32 x <= 256 KB of pinned memory per context. Pose prefetch (deform_kernels.h: pf_*): every slot carries a header behind its payload — the
+    // sequence number of the pose it holds, written LAST — and the device keeps one tag per pose block: the sequence number a frame's helper
+    // workgroup staged there. Sequence numbers are (ring epoch << 32 | upload index + 1): a re-allocated ring never matches old tags.
+    struct ZeroCopy {
+        static constexpr int kSlots = 32;
+        rzi::Pinned slot[kSlots];
+        size_t bytes = 0, hdr_off = 0;  // payload bytes a slot holds / byte offset of the header inside it
+        rzring::ReuseProof<kSlots> proof;
+        rzi::Events<2> ev;
+    } zc;
+    uint32_t epoch = 0;                 // the ring epoch of the sequence numbers (pose.cpp: retire_pose_tags bumps it, nothing else)
+    rzi::Scratch<uint64_t> tag;         // device: [2], one per pose block
+
+    // Poses of more than 256 KB (crowds) travel on the upload stream into a ring of kBlocks device blocks of their own (the layout of pose_blk), so
+    // the upload of pose f+1 runs under the frame of pose f. A block is overwritten kBlocks uploads after it was filled; the same proof says its
+    // readers are done — no per-frame "slot is free" hand-off between the streams (round 4 had one: a record on the compute stream + a wait on the
+    // upload stream per frame, measured at 5 - 8 us per frame: tools/archive/overlapbench, profiles/r5_overlapbench.txt). 8 x 3.3 MB for C4.
+    struct Big {
+        static constexpr int kBlocks = 8;
+        rzi::Scratch<float> blk[kBlocks];
+        size_t floats = 0;
+        rzring::ReuseProof<kBlocks> proof;
+        rzi::Events<2> ev;
+    } big;
+
+    // rz_map_pose / rz_commit_pose: the slot handed out to the caller (layout < 0 = nothing mapped), and what it was sized for
+    struct Map {
+        int layout = -1;
+        bool zc = false;                // a slot of the zero-copy ring (one character) or of the staging ring (crowds)
+        int slot = 0;
+        uint64_t upload = 0;            // zero-copy: the upload index (1-based) zc_open gave the slot
+        uint32_t I = 0, B = 0, M = 0;
+        char *ptr = nullptr;
+    } map;
+
+    struct Current {                    // the current pose
+        bool set = false;
+        uint32_t I = 0;                 // instance count the pose was uploaded for
+        bool local = false;             // it is a local pose (rz_set_pose_local, or produced on the device), not world matrices
+        bool local_t = false;           // ... that carries translations (behind the rotations in its slot)
+        bool sampled = false;           // ... sampled on the device from the uploaded motion (rz_set_pose_sampled)
+        bool frames_inline = false;     // one character: the frame rides in the kernel arguments (frame0), nothing is uploaded
+        float frame0 = 0.0f;
+        int zc_slot = -1;               // its slot of the zero-copy ring, -1 = it came down as a copy or was produced on the device
+        bool zc_local = false;          // layout of that slot: [weights | rotations | translations] or [world | weights]
+        int zc_kind = 0;                // 0 world, 1 local rotations, 2 local rotations + translations (part of the sequence number)
+        size_t zc_total = 0, zc_mw_off = 0, zc_lq_off = 0;      // bytes in the slot, and where the weights / rotations sit in it
+        uint64_t seq = 0;               // its sequence number (0 = not prefetchable)
+        bool world_resident = true, mw_resident = true, local_resident = true;   // which parts the device pose block holds
+        bool resident() const { return zc_slot < 0 || (world_resident && mw_resident && local_resident); }
+        // host-compacted active-morph list (single-instance FAST path); count < 0 means "more than kKargMorphs active: use the prep kernel"
+        RzMorphList ml = {};
+    } cur;
+
+    // what device-produced poses are made from: [I] frames (sampled), [I] states or [I] states + [I][n_layers] layers of a crowd (blended / layered)
+    rzi::Scratch<float> an_frames;
+    rzi::Scratch<RzMotionState> mo_states;
+    rzi::Scratch<RzMotionLayer> mo_layers;
+    size_t an_frames_alloc = 0, mo_states_alloc = 0, mo_layers_alloc = 0;
+    hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states (and mo_layers)
+    // what the most recent copy upload did (rz_get_tuning: pose_pulled / pose_rows): a crowd's pose (more than 256 KB) is PULLED out of the ring
+    // slot by rz_pull_pose_kernel on the upload stream instead of copied, world matrices as their upper three rows (pose.cpp: upload_pose_copy)
+    bool last_pulled = false, last_rows = false;
+};
+
 struct rz_ctx : RzStatic, RzTuning {
     int device = 0;
     int n_cu = 256;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
-    bool pose_local_t = false;          // the current local pose carries translations (behind the rotations in its slot)
-    bool pose_sampled = false;          // the current pose is sampled on the device from the uploaded motion (rz_set_pose_sampled)
-    float *an_frames = nullptr;         // [I]
-    bool frames_inline = false;         // one character: the frame rides in the kernel arguments (frame0), nothing is uploaded
-    float frame0 = 0.0f;
-    size_t an_frames_alloc = 0;
-    RzMotionState *mo_states = nullptr; // [I] per-frame states of a crowd (this context's own, never borrowed)
-    size_t mo_states_alloc = 0;
-    hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states (and mo_layers)
-    RzMotionLayer *mo_layers = nullptr; // [I][n_layers] per-frame layers of a crowd, behind their states on the same stream (this context's own)
-    size_t mo_layers_alloc = 0;
+    RzPoseLink pl;                      // the per-frame pose transport; world / morph_w / local_q below point into its current block
     float4 *local_q = nullptr;          // I x B   (current pose slot)
 
-    bool pose_local = false;            // the current pose came from rz_set_pose_local
     // physics hand-off for device-solved frames (rz_override_world)
     int *ovr_off = nullptr, *ovr_bone = nullptr;
     float *ovr_world = nullptr;
@@ -246,32 +368,9 @@ struct rz_ctx : RzStatic, RzTuning {
     // per-frame state
     uint32_t I = 1;
     float *world = nullptr;             // I x B x 16   (current pose slot)
-    // Per-frame INPUTS are double-buffered and uploaded on their own stream, so the upload of pose f+1 overlaps the
-    // kernels of pose f: stage_ev[ring slot] = the pose has landed (the compute stream waits for it), ev_free[k] = everything
-    // that reads slot k has been enqueued up to here (the upload stream waits for it before overwriting the slot).
-    // One device block per pose slot: [world I*B*16 | morph weights pad4(I*max(M,1)) | local rotations I*B*4 | local
-    // translations I*B*3] floats. A world-matrix pose fills [world | weights], a local pose [weights | rotations (|
-    // translations)] — each a CONTIGUOUS range, so every upload is one copy (measured: a small H2D copy is a 4.5 us blit
-    // kernel on this runtime, and a second one for 256 bytes of morph weights cost as much as the first).
-    // The offsets are those of the instance / bone / morph counts AT UPLOAD TIME (point_pose_slot): shrinking the crowd
-    // afterwards leaves the resident pose where it is.
-    float *pose_blk[2] = {nullptr, nullptr};
     size_t mw_pad = 0;                              // floats reserved for the morph weights in the current layout (multiple of 4)
-    int pose_slot = 0;
-    hipStream_t up_stream = nullptr;
-    // Poses of more than 256 KB (crowds) travel on the upload stream into a ring of kBigBlocks device blocks of their own (same
-    // layout as pose_blk), so the upload of pose f+1 runs under the frame of pose f. A block is overwritten kBigBlocks uploads after
-    // it was filled; that its readers are done is proven like a zero-copy slot's: ONE event per kBigBlocks / 2 uploads, recorded on
-    // the compute stream at upload time and polled by the host before the block's next tenant is enqueued — no per-frame "slot is
-    // free" hand-off between the streams (round 4 had one: a record on the compute stream + a wait on the upload stream per frame,
-    // measured at 5 - 8 us per frame: tools/archive/overlapbench, profiles/r5_overlapbench.txt). 8 x 3.3 MB for C4.
-    static constexpr int kBigBlocks = 8;
-    float *big_blk[kBigBlocks] = {};
-    size_t big_floats = 0;
-    uint64_t big_uploads = 0;
-    hipEvent_t big_ev[2] = {nullptr, nullptr};
-    uint64_t big_ev_seq[2] = {~0ull, ~0ull};
-    float4 *palette = nullptr;          // I x B x 3   (current ring slot)
+    hipStream_t up_stream = nullptr;    // per-frame inputs travel here where that is a gain (pose.cpp: pose_stream): the upload of pose f+1 overlaps the kernels of pose f
+    float4 *palette = nullptr;         // I x B x 3   (current ring slot)
     float *morph_w = nullptr;           // I x M   (current pose slot)
     uint32_t *act_idx = nullptr;        // I x Mpad    (current ring slot)
     float *act_w = nullptr;             // I x Mpad    (current ring slot)
@@ -288,9 +387,6 @@ struct rz_ctx : RzStatic, RzTuning {
     hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_skin[2] = {nullptr, nullptr};
     bool skin_recorded[2] = {false, false};
     bool overlap_on = false;            // the two streams currently follow the overlapped-front protocol
-    bool pose_set = false;
-    uint32_t pose_I = 0;                // instance count the current pose was uploaded for
-    size_t pose_alloc_I = 0, pose_alloc_B = 0, pose_alloc_M = 0;
 
     // outputs
     float *out_pos = nullptr, *out_nrm = nullptr;
@@ -303,60 +399,6 @@ struct rz_ctx : RzStatic, RzTuning {
     bool aabb_on = false;
     int aabb_slot = 0;                  // slot the NEXT frame accumulates into
     bool aabb_rearm = false;            // both slots must be armed again before the next frame
-
-    // pinned staging ring for rz_set_pose
-    void *stage[kStageSlots] = {};
-    void *stage_dev[kStageSlots] = {};  // the slots' device addresses (device-mapped ring), or null: this ring can only be copied from
-    size_t stage_bytes = 0;
-    // Crowd poses (more than 256 KB) are PULLED out of the ring slot by rz_pull_pose_kernel on the upload stream instead of copied by
-    // hipMemcpyAsync, world matrices as their upper three rows (pose.cpp: upload_pose_copy)
-    bool last_upload_pulled = false, last_upload_rows = false;      // what the most recent copy upload did (rz_get_tuning: pose_pulled / pose_rows)
-    hipEvent_t stage_ev[kStageSlots] = {};
-    bool stage_used[kStageSlots] = {};
-    int stage_next = 0;
-
-    // Zero-copy poses (one character, <= 256 KB): rz_set_pose* only writes the pose into a slot of this pinned,
-    // device-mapped ring — no copy is enqueued at all. The first frame's kernels read it over the host link (rz_fk_kernel
-    // the local pose; the one-launch deform kernel the world matrices, whose workgroup 0 also leaves them in the device
-    // pose block for the frames that replay the pose); anything that needs a device-resident pose first (rz_prep_kernel)
-    // gets it through make_resident(). Measured on MI355X (tools/archive/uploadbench): a 16.6 KB hipMemcpyAsync in front of a
-    // frame costs 18 us, two of <= 16 KB 9.5 us, reading the pinned slot from the kernel 7 us with the loads fully exposed.
-    // A slot is reused kZcSlots (32) uploads later; one event per kZcSlots / 2 uploads (recorded on the compute stream at upload time) proves
-    // its readers are done, so there is no per-frame marker either.
-    // Slots of the ring: one hipEventRecord per kZcSlots / 2 uploads guards slot reuse, and a record costs ~1.4 us of stream time: measured
-    // on a 1/8 shard of C5 (tools/archive/live_shard.py, per-frame-pose loop over the resident replay): 8 slots +0.86 us per frame, 16 slots
-    // +0.50 us, 32 slots +0.37 us. 32 x <= 256 KB of pinned memory per context.
-    static constexpr int kZcSlots = 32;
-    void *zc_host[kZcSlots] = {};
-    void *zc_dev[kZcSlots] = {};
-    size_t zc_bytes = 0;
-    uint64_t zc_uploads = 0;
-    hipEvent_t zc_ev[2] = {nullptr, nullptr};
-    uint64_t zc_ev_seq[2] = {~0ull, ~0ull};
-    // Pose prefetch (deform_kernels.h: pf_*): every slot carries a header behind its payload — the sequence number of the pose
-    // it holds, written LAST — and the device keeps one tag per pose block: the sequence number a frame's helper workgroup
-    // staged there. Sequence numbers are (ring epoch << 32 | upload index + 1): a re-allocated ring never matches old tags.
-    size_t zc_hdr_off = 0;              // byte offset of the header inside a slot
-    uint32_t zc_epoch = 0;
-    uint64_t zc_seq_cur = 0;            // sequence number of the current pose (0 = not prefetchable)
-    uint64_t *zc_tag = nullptr;         // device: [2], one per pose block
-    int zc_cur = -1;                    // slot of the current pose, -1 = the current pose came down as a copy
-    bool zc_local = false;              // layout of that slot: [weights | rotations | translations] or [world | weights]
-    int zc_kind = 0;                    // 0 world, 1 local rotations, 2 local rotations + translations (part of the sequence number)
-    size_t zc_total = 0, zc_mw_off = 0, zc_lq_off = 0;     // bytes in the slot, and where the weights / rotations sit in it
-    bool world_resident = true, mw_resident = true, local_resident = true;   // which parts the device pose block holds
-
-    // rz_map_pose / rz_commit_pose: the slot handed out to the caller (map_layout < 0 = nothing mapped), and what it was sized for
-    int map_layout = -1;
-    bool map_zc = false;                // a slot of the zero-copy ring (one character) or of the staging ring (crowds)
-    int map_slot = 0;
-    uint64_t map_upload = 0;            // zero-copy: the upload index (1-based) zc_open gave the slot
-    uint32_t map_I = 0, map_B = 0, map_M = 0;
-    char *map_ptr = nullptr;
-
-    // host-compacted active-morph list of the current pose (single-instance FAST path);
-    // count < 0 means "more than kKargMorphs active: use the prep kernel"
-    RzMorphList ml;
 
     int t_dbg = 0;                      // "dbg": ablation switches of the tools-only build; not in RzTuning, a fork starts without them
     // Bone-subset crowd frames: per vertex run of the CURRENT launch shape, the ascending list of bones the run's
@@ -423,7 +465,6 @@ int ensure_outputs(rz_ctx *c);
 void set_ring(rz_ctx *c, int slot);
 void point_pose_slot(rz_ctx *c, int k);
 void point_pose_at(rz_ctx *c, float *block);     // the current pose lives in `block` (pose_blk[k] or a block of the big-pose ring)
-void free_big_ring(rz_ctx *c);
 int ensure_pose_buffers(rz_ctx *c);
 void free_animation(rz_ctx *c);
 void free_motions(rz_ctx *c);
@@ -474,6 +515,7 @@ const float *src_morph_w(const rz_ctx *c);
 const float4 *src_local_q(const rz_ctx *c);
 int make_resident(rz_ctx *c);
 uint64_t zc_seq(const rz_ctx *c, uint64_t upload_index_1, int kind);
+void retire_pose_tags(rz_ctx *c);     // nothing a helper workgroup staged and tagged so far, or a slot header published so far, may match a later pose
 
 // ---- frame.cpp ----
 int check_ready(rz_ctx *c);

@@ -9,7 +9,7 @@ int check_ready(rz_ctx *c)
 {
     if (c->V == 0 || !c->geom) return fail(RZ_ERR_INVALID, "no mesh uploaded (rz_upload_mesh)");
     if (c->B == 0 || !c->inv_bind) return fail(RZ_ERR_INVALID, "no skeleton uploaded (rz_upload_skeleton)");
-    if (!c->pose_set) return fail(RZ_ERR_INVALID, "no pose set (rz_set_pose)");
+    if (!c->pl.cur.set) return fail(RZ_ERR_INVALID, "no pose set (rz_set_pose)");
     return RZ_OK;
 }
 
@@ -47,14 +47,14 @@ int launch_prep(rz_ctx *c, hipStream_t st)
 // own — but only while the device-animated pose that frame deformed is still the current one. A new pose, skeleton or topology clears the
 // flag where it goes away (upload_pose, rz_set_pose_sampled, rz_upload_skeleton*); this is the second lock on the same door: rz_fk_kernel
 // on a pose block that holds world matrices, or on the records of a replaced skeleton, would overwrite the resident pose.
-bool solve_on_demand(const rz_ctx *c) { return c->fk_stale && c->pose_local && c->has_topology && c->pose_set && c->fk_rec; }
+bool solve_on_demand(const rz_ctx *c) { return c->fk_stale && c->pl.cur.local && c->has_topology && c->pl.cur.set && c->fk_rec; }
 
 // Everything a frame launches in front of the deform kernel: on-device FK (local-rotation poses) and/or the prep
 // kernel. The FK kernel already writes the palette, so prep is only still needed for its morph compaction.
 int launch_front(rz_ctx *c, const Plan &pl, hipStream_t st)
 {
     if (pl.fuse_fk || pl.subfk) return RZ_OK;       // the deform / crowd kernel solves the hierarchy itself
-    if (c->pose_local) {
+    if (c->pl.cur.local) {
         if (int r = launch_fk(c, st)) return r;
         if (pl.prep && c->morph_mode == 1)
             if (int r = launch_prep(c, st)) return r;
@@ -83,11 +83,11 @@ int launch_deform(rz_ctx *c, const Plan &pl)
     }
     size_t lds = rz_deform_lds_bytes(p, pl.v);
     if (lds > 160 * 1024) return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the LDS palette (%zu B)", lds);
-    HIP_TRY(rz_launch_deform(p, c->ml, pl.v, pl.grid_x + (p.pf_src ? 1u : 0u), c->I, c->stream));
+    HIP_TRY(rz_launch_deform(p, c->pl.cur.ml, pl.v, pl.grid_x + (p.pf_src ? 1u : 0u), c->I, c->stream));
     c->palette_stale = false;                          // this frame's palette is in memory: written by its front kernels or by workgroup 0
-    if (p.world_copy) c->world_resident = true;        // workgroup 0 of that launch left the pose in the device block
-    if (p.morph_w_copy) c->mw_resident = true;
-    if (p.fk.copy_q) c->local_resident = c->mw_resident = true;
+    if (p.world_copy) c->pl.cur.world_resident = true;        // workgroup 0 of that launch left the pose in the device block
+    if (p.morph_w_copy) c->pl.cur.mw_resident = true;
+    if (p.fk.copy_q) c->pl.cur.local_resident = c->pl.cur.mw_resident = true;
     if (c->aabb_on) c->aabb_slot ^= 1;     // this launch re-armed the other slot for the next frame
     return RZ_OK;
 }
@@ -108,13 +108,13 @@ template <typename S> static void pass_frame_fields(const rz_ctx *c, const Plan 
         //   otherwise (a single character's fused-hierarchy frame; sparse targets, which never overlap): the weights themselves — sampled
         //   ones from the device block the front / workgroup 0 wrote, uploaded ones from the device copy workgroup 0 leaves, or where the
         //   frame kernel reads them
-        if (s.mode == 1 && pl.v.fast && c->I == 1 && c->ml.count >= 0 && !c->pose_sampled) s.wsrc = 0;
+        if (s.mode == 1 && pl.v.fast && c->I == 1 && c->pl.cur.ml.count >= 0 && !c->pl.cur.sampled) s.wsrc = 0;
         else if (s.mode == 1 && pl.prep) {
             s.wsrc = 1; s.act_idx = c->act_idx; s.act_w = c->act_w; s.act_count = c->act_count;
         } else {
             s.wsrc = 2;
             const float *copy = deform_params(c, pl).morph_w_copy;
-            s.morph_w = c->pose_sampled ? c->morph_w : (copy ? copy : src_morph_w(c));
+            s.morph_w = c->pl.cur.sampled ? c->morph_w : (copy ? copy : src_morph_w(c));
         }
     }
     s.out_pos = c->ext_pos ? c->ext_pos : c->out_pos; s.out_nrm = c->ext_nrm ? c->ext_nrm : c->out_nrm;
@@ -158,8 +158,8 @@ int launch_passes(rz_ctx *c, const RzSdefParams &sp, const RzQdefParams &qp)
             if (int r = launch_fk(c, c->stream)) return r;
         } else if (int r = launch_prep(c, c->stream)) return r;
     }
-    if (sp.n) HIP_TRY(rz_launch_sdef(sp, c->ml, c->I, c->stream));
-    if (qp.n) HIP_TRY(rz_launch_qdef(qp, c->ml, c->I, c->stream));
+    if (sp.n) HIP_TRY(rz_launch_sdef(sp, c->pl.cur.ml, c->I, c->stream));
+    if (qp.n) HIP_TRY(rz_launch_qdef(qp, c->pl.cur.ml, c->I, c->stream));
     return RZ_OK;
 }
 
@@ -180,7 +180,7 @@ bool want_overlap(const rz_ctx *c, const Plan &pl)
 {
     // OPT-IN (overlap = 1): measured on MI355X / ROCm 7.2 the two cross-stream hand-offs per frame cost more than the front
     // kernels they hide — C4 39.0 -> 44.8 us with rz_prep_kernel in front, 43.4 -> 62.1 us with rz_fk_kernel
-    return c->t_overlap == 1 && c->I > 1 && c->morph_mode != 2 && !c->t_graph && (pl.prep || c->pose_local) && !pl.subfk;
+    return c->t_overlap == 1 && c->I > 1 && c->morph_mode != 2 && !c->t_graph && (pl.prep || c->pl.cur.local) && !pl.subfk;
 }
 
 // Switching protocols is rare (instance count, tuning keys): drain both streams so that nothing enqueued under the old
@@ -198,7 +198,7 @@ int set_overlap(rz_ctx *c, bool on)
 int run_frame(rz_ctx *c, const Plan &pl)
 {
     // rz_prep_kernel (and a skin kernel that is not the one-launch form) reads a device-resident pose
-    if (c->zc_cur >= 0 && (pl.prep || (!pl.v.fast && !c->pose_local)))
+    if (c->pl.cur.zc_slot >= 0 && (pl.prep || (!pl.v.fast && !c->pl.cur.local)))
         if (int r = make_resident(c)) return r;
     if (c->overlap_on) {
         const int s = c->ring_slot ^ 1;                       // the slot the skin kernel of two frames ago read
@@ -251,7 +251,7 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     uint64_t h = 1469598103934665603ull;
     const RzDeformParams dp = deform_params(c, pl);
     h = fnv(h, &dp, sizeof dp);
-    h = fnv(h, &c->ml, sizeof c->ml);
+    h = fnv(h, &c->pl.cur.ml, sizeof c->pl.cur.ml);
     h = fnv(h, &pl, sizeof pl);
     const RzPrepParams pp = prep_params(c);
     h = fnv(h, &pp, sizeof pp);
@@ -265,7 +265,7 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     h = fnv(h, &qd, sizeof qd);
     if (c->ik_n) { const RzIkParams ik = ik_params(c); h = fnv(h, &ik, sizeof ik); }
     if (c->ovr_follow) { const RzFollowParams fo = follow_params(c); h = fnv(h, &fo, sizeof fo); }
-    const uint64_t misc[6] = { c->I, c->pose_local, c->pose_local_t, c->pose_sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
+    const uint64_t misc[6] = { c->I, c->pl.cur.local, c->pl.cur.local_t, c->pl.cur.sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }
 
@@ -467,7 +467,7 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
     out->deform_kernel_ms = ms / frames;
     // the front kernels alone (only part of the frame when the plan is not the one-launch FAST form); everything has
     // drained at this point, so they may run on the context's stream whatever the protocol
-    if ((pl.prep || c->pose_local) && !pl.fuse_fk && !pl.subfk) {
+    if ((pl.prep || c->pl.cur.local) && !pl.fuse_fk && !pl.subfk) {
         HIP_TRY(hipStreamSynchronize(c->up_stream));
         HIP_TRY(hipEventRecord(c->ev0, c->stream));
         for (uint32_t f = 0; f < frames; ++f)

@@ -85,8 +85,8 @@ static RzPhysicsParams physics_params(const rz_ctx *c, uint32_t substeps, bool r
 // the hierarchy solve of the resident pose without overrides, then the solver: both on the stream the frame's front runs on
 static int step(rz_ctx *c, uint32_t substeps, bool reset)
 {
-    if (!c->pose_set) return fail(RZ_ERR_INVALID, "rz_physics_step: no pose set");
-    if (!c->pose_local || !c->has_topology)
+    if (!c->pl.cur.set) return fail(RZ_ERR_INVALID, "rz_physics_step: no pose set");
+    if (!c->pl.cur.local || !c->has_topology)
         return fail(RZ_ERR_INVALID, "rz_physics_step acts on device-solved poses (rz_set_pose_local, rz_set_pose_sampled, rz_set_pose_blended): with rz_set_pose the host owns the world matrices");
     if (int r = ensure_instances(c)) return r;
     hipStream_t st = front_stream(c);
@@ -234,7 +234,7 @@ int rz_physics_reset(rz_ctx *c)
 {
     if (int r = use(c)) return r;
     if (int r = physics_usable(c, "rz_physics_reset")) return r;
-    if (!c->pose_set || !c->pose_local || !c->has_topology) {       // nothing to stand the bodies on yet: the next step does it
+    if (!c->pl.cur.set || !c->pl.cur.local || !c->has_topology) {       // nothing to stand the bodies on yet: the next step does it
         c->ph.reset = true;
         c->ovr_count = 0;
         return RZ_OK;

@@ -76,6 +76,21 @@ void inst_runs(const rz_ctx *c, int G, int blk, bool for_subsets, uint32_t *per,
     }
 }
 
+// Pose prefetch, first frame of a zero-copy pose only (deform_kernels.h: st_*, pf_*). This frame: was the pose staged by the previous frame's
+// helper? Next frame: a helper looks at the slot the next upload will use. `dst_off`: the pose's range in the other block; the caller adds the st_* parts.
+void prefetch_params(const rz_ctx *c, RzDeformParams &p, size_t dst_off)
+{
+    const RzPoseLink &pl = c->pl;
+    const char *nxt = static_cast<const char *>(pl.zc.slot[(pl.cur.zc_slot + 1) % RzPoseLink::ZeroCopy::kSlots].dev);
+    p.st_tag = pl.tag.p + pl.pose_slot; p.st_expect = pl.cur.seq;
+    p.pf_src = reinterpret_cast<const float *>(nxt);
+    p.pf_src_seq = reinterpret_cast<const uint64_t *>(nxt + pl.zc.hdr_off);
+    p.pf_dst = pl.pose_blk[pl.pose_slot ^ 1].p + dst_off;
+    p.pf_tag = pl.tag.p + (pl.pose_slot ^ 1);
+    p.pf_expect = zc_seq(c, pl.zc.proof.uploads + 1, pl.cur.zc_kind);
+    p.pf_bytes = (uint32_t)((pl.cur.zc_total + 15) / 16 * 16);
+}
+
 }  // namespace
 
 RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
@@ -85,21 +100,12 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
     p.geom = c->geom; p.joints01 = c->j01; p.joints23 = c->j23; p.weights = c->wq;
     p.palette = c->palette; p.world = src_world(c); p.inv_bind = c->inv_bind; p.dense = c->dense;
     p.act_idx = c->act_idx; p.act_w = c->act_w; p.act_count = c->act_count; p.morph_w = src_morph_w(c);
-    if (pl.v.fast && c->zc_cur >= 0) {            // the one-launch kernel's workgroup 0 makes the pose resident
-        if (!c->world_resident && !c->zc_local) p.world_copy = c->world;
-        if (!c->mw_resident && pl.v.mode == 2) p.morph_w_copy = c->morph_w;
-        // Pose prefetch, first frame of a zero-copy world pose only. This frame: was the pose staged by the previous frame's
-        // helper? Next frame: a helper workgroup looks at the slot the next upload will use (deform_kernels.h: pf_*).
-        if (pl.pf && p.world_copy && c->zc_tag && c->zc_seq_cur) {
-            p.st_tag = c->zc_tag + c->pose_slot; p.st_expect = c->zc_seq_cur;
+    if (pl.v.fast && c->pl.cur.zc_slot >= 0) {            // the one-launch kernel's workgroup 0 makes the pose resident
+        if (!c->pl.cur.world_resident && !c->pl.cur.zc_local) p.world_copy = c->world;
+        if (!c->pl.cur.mw_resident && pl.v.mode == 2) p.morph_w_copy = c->morph_w;
+        if (pl.pf && p.world_copy && c->pl.tag && c->pl.cur.seq) {
+            prefetch_params(c, p, 0);
             p.st_world = c->world; p.st_morph_w = (pl.v.mode == 2 && c->M > 0) ? c->morph_w : nullptr;
-            const int nxt = (c->zc_cur + 1) % rz_ctx::kZcSlots;
-            p.pf_src = static_cast<const float *>(c->zc_dev[nxt]);
-            p.pf_src_seq = reinterpret_cast<const uint64_t *>(static_cast<const char *>(c->zc_dev[nxt]) + c->zc_hdr_off);
-            p.pf_dst = c->pose_blk[c->pose_slot ^ 1];
-            p.pf_tag = c->zc_tag + (c->pose_slot ^ 1);
-            p.pf_expect = zc_seq(c, c->zc_uploads + 1, c->zc_kind);
-            p.pf_bytes = (uint32_t)((c->zc_total + 15) / 16 * 16);
         }
     }
     p.sp_ptr = c->sp_ptr; p.sp_entries = c->sp_entries;
@@ -121,25 +127,19 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
         p.fk = fk_params(c); p.fk_on = 1;
         // the specialised variants (fk_solve<true, KIND>): no physics overrides, two bones per thread, one morph per thread;
         // "fuse_fk_plain" = 0 keeps the generic kernel (A/B, tests)
-        const bool plain = c->t_fkplain != 0 && !p.fk.ovr_off && c->B <= 512 && c->M <= 256 && (!c->pose_sampled || c->an_M <= 256);
-        p.fk_kind = plain ? (c->pose_sampled ? 2 : 1) : 0;
-        if (c->zc_cur >= 0 && c->zc_local && !c->pose_sampled && (!c->local_resident || !c->mw_resident)) {
+        const bool plain = c->t_fkplain != 0 && !p.fk.ovr_off && c->B <= 512 && c->M <= 256 && (!c->pl.cur.sampled || c->an_M <= 256);
+        p.fk_kind = plain ? (c->pl.cur.sampled ? 2 : 1) : 0;
+        if (c->pl.cur.zc_slot >= 0 && c->pl.cur.zc_local && !c->pl.cur.sampled && (!c->pl.cur.local_resident || !c->pl.cur.mw_resident)) {
             // zero-copy local pose, first frame: workgroup 0 makes it resident (every later frame of this pose reads the device
             // block instead of pulling the pose over the host link in every workgroup), and — like the one-launch frame of a
             // world pose — the frame looks for a copy the previous frame's helper staged and carries a helper for the next upload
-            float *blk_t = c->pose_local_t ? reinterpret_cast<float *>(c->local_q + c->B) : nullptr;
+            float *blk_t = c->pl.cur.local_t ? reinterpret_cast<float *>(c->local_q + c->B) : nullptr;
             p.fk.copy_q = c->local_q; p.fk.copy_t = blk_t;
             if (c->M > 0) p.morph_w_copy = c->morph_w;
-            if (pl.pf && c->zc_tag && c->zc_seq_cur) {
-                p.st_tag = c->zc_tag + c->pose_slot; p.st_expect = c->zc_seq_cur; p.fk.st_expect = c->zc_seq_cur;
+            if (pl.pf && c->pl.tag && c->pl.cur.seq) {
+                prefetch_params(c, p, c->morph_w - c->pl.pose_blk[c->pl.pose_slot].p);     // the local range of the other block
+                p.fk.st_expect = c->pl.cur.seq;
                 p.fk.st_local_q = c->local_q; p.fk.st_local_t = blk_t; p.st_morph_w = c->morph_w;
-                const int nxt = (c->zc_cur + 1) % rz_ctx::kZcSlots;
-                p.pf_src = static_cast<const float *>(c->zc_dev[nxt]);
-                p.pf_src_seq = reinterpret_cast<const uint64_t *>(static_cast<const char *>(c->zc_dev[nxt]) + c->zc_hdr_off);
-                p.pf_dst = c->pose_blk[c->pose_slot ^ 1] + (c->morph_w - c->pose_blk[c->pose_slot]);     // the local range of the other block
-                p.pf_tag = c->zc_tag + (c->pose_slot ^ 1);
-                p.pf_expect = zc_seq(c, c->zc_uploads + 1, c->zc_kind);
-                p.pf_bytes = (uint32_t)((c->zc_total + 15) / 16 * 16);
             }
         }
     }
@@ -152,7 +152,7 @@ bool inst_shape(const rz_ctx *c, InstShape *s)
 {
     const bool epilogues = c->edge != nullptr || c->aabb_on;   // only the generic kernel carries the fused consumers
     if (!(c->morph_mode == 0 && c->I > 1 && c->t_instloop != 0 && c->t_instloop != 9 && !epilogues) || c->B == 0 || c->V == 0) return false;
-    s->want_in_kernel = c->t_fast != 0 && !c->pose_local;
+    s->want_in_kernel = c->t_fast != 0 && !c->pl.cur.local;
     // workgroup size. Whole palettes: 512 threads for the one-launch frame (one workgroup of 8 waves per CU shares the 102 KB
     // group), 256 behind rz_prep_kernel / rz_fk_kernel (two workgroups of 80 KB each: measured best in round 2). Bone subsets
     // (30 KB): 512 threads in both forms — with finished rows staged the 512-thread kernel runs C4 in 32.1 us against 34.5 us
@@ -196,9 +196,9 @@ Plan make_plan(const rz_ctx *c)
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
     // (an IK table keeps the solve in a kernel of its own, rz_fk_ik_kernel: the fused kernels carry no IK stage; nor the follow stage of
     // rz_override_follow, so resident follower entries keep the solve with rz_fk_follow_kernel)
-    pl.fuse_fk = c->ik_n == 0 && !follow_params(c).off && c->I == 1 && c->pose_local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
-                 (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pose_sampled || c->morph_mode != 1)));
-    const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->ml.count >= 0);
+    pl.fuse_fk = c->ik_n == 0 && !follow_params(c).off && c->I == 1 && c->pl.cur.local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
+                 (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pl.cur.sampled || c->morph_mode != 1)));
+    const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->pl.cur.ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
     pl.dma = false;
     pl.inst_group = 0;
@@ -218,9 +218,9 @@ Plan make_plan(const rz_ctx *c)
     if (v.mode == 1 && v.S == 8 && c->t_grid_cap <= 0 && c->I == 1) cap = std::max(cap, 4u * (uint32_t)c->n_cu);
     // Pose prefetch: the first frame of a zero-copy world pose carries one helper workgroup that stages the NEXT pose (if the
     // host has written it already) — it takes one of the grid's slots, the workers share the mesh among cap - 1.
-    pl.pf = c->I == 1 && c->t_prefetch != 0 && c->zc_cur >= 0 && c->zc_seq_cur != 0 && c->zc_tag &&
-            ((v.fast && !c->zc_local && !c->world_resident) ||
-             (pl.fuse_fk && c->zc_local && !c->pose_sampled && (!c->local_resident || !c->mw_resident)));
+    pl.pf = c->I == 1 && c->t_prefetch != 0 && c->pl.cur.zc_slot >= 0 && c->pl.cur.seq != 0 && c->pl.tag &&
+            ((v.fast && !c->pl.cur.zc_local && !c->pl.cur.world_resident) ||
+             (pl.fuse_fk && c->pl.cur.zc_local && !c->pl.cur.sampled && (!c->pl.cur.local_resident || !c->pl.cur.mw_resident)));
     if (pl.pf && cap > 1) cap -= 1;
     const bool dense_rules = v.mode == 1 && c->t_grid_cap <= 0, one_mesh = c->I == 1;
     const uint32_t cap_i = std::max<uint32_t>(1, cap / std::max<uint32_t>(1, c->I));
@@ -350,7 +350,7 @@ extern "C" __attribute__((visibility("default"))) int rz_debug_plan_dense(uint32
     if (V == 0 || M == 0 || n_cu <= 0 || !split || !grid || !quads_per_wave) return RZ_ERR_INVALID;
     rz_ctx c;
     c.n_cu = n_cu; c.V = V; c.Vp = rzi::round_up(V, rzi::kVertPad); c.B = B; c.M = M; c.I = 1; c.morph_mode = 1;
-    c.ml.count = M <= (uint32_t)kKargMorphs ? (int)M : -1;
+    c.pl.cur.ml.count = M <= (uint32_t)kKargMorphs ? (int)M : -1;
     const rzi::Plan pl = rzi::make_plan(&c);
     *split = pl.v.S; *grid = (int)pl.grid_x; *quads_per_wave = (int)pl.quads_per_wave;
     if (out_cap) *out_cap = (int)pl.out_cap;
@@ -403,7 +403,7 @@ int ensure_run_subsets(rz_ctx *c)
 // both stay with rz_fk_kernel; so does the IK stage of rz_fk_ik_kernel), "fuse_fk" not switched off.
 bool subfk_wanted(const rz_ctx *c)
 {
-    return c->I > 1 && c->pose_local && c->has_topology && c->t_fusefk != 0 && c->t_subsets != 0 && c->sub_valid && c->sub_max < c->B &&
+    return c->I > 1 && c->pl.cur.local && c->has_topology && c->t_fusefk != 0 && c->t_subsets != 0 && c->sub_valid && c->sub_max < c->B &&
            !(c->bm_count && c->M) && c->ovr_count == 0 && c->ik_n == 0 && c->fk_host.size() == (size_t)c->B * 4;
 }
 
@@ -533,7 +533,7 @@ RzFkParams fk_params(const rz_ctx *c)
     RzFkParams p;
     memset(&p, 0, sizeof p);            // padding too: frame_signature() hashes the struct
     p.local_q = src_local_q(c);
-    p.local_t = c->pose_local_t ? reinterpret_cast<const float *>(p.local_q + (size_t)c->I * c->B) : nullptr;
+    p.local_t = c->pl.cur.local_t ? reinterpret_cast<const float *>(p.local_q + (size_t)c->I * c->B) : nullptr;
     p.bone_rec = c->fk_rec; p.anc_more = c->fk_anc_more; p.inv_bind = c->inv_bind;
     p.world = c->world; p.palette = c->palette; p.B = (int)c->B; p.n_rounds = c->fk_rounds;
     if (c->ovr_count) { p.ovr_off = c->ovr_off; p.ovr_bone = c->ovr_bone; p.ovr_world = c->ovr_world; }
@@ -541,9 +541,9 @@ RzFkParams fk_params(const rz_ctx *c)
         p.bm_off = c->bm_off; p.bm_morph = c->bm_morph; p.bm_rot = c->bm_rot; p.bm_tr = c->bm_tr;
         p.bm_w = src_morph_w(c); p.bm_M = (int)c->M;
     }
-    if (c->pose_sampled) {
+    if (c->pl.cur.sampled) {
         RzSampleParams &q = p.sample;
-        q.frames = c->frames_inline ? nullptr : c->an_frames; q.frames_inline = c->frames_inline ? 1 : 0; q.frame0 = c->frame0;
+        q.frames = c->pl.cur.frames_inline ? nullptr : c->pl.an_frames.p; q.frames_inline = c->pl.cur.frames_inline ? 1 : 0; q.frame0 = c->pl.cur.frame0;
         q.key_frame = c->an_key_frame;
         q.key_rot = c->an_key_rot; q.key_pos = c->an_key_pos; q.key_interp = c->an_key_interp;
         q.mkey_frame = c->an_mkey_frame; q.mkey_weight = c->an_mkey_weight;

@@ -1,4 +1,5 @@
-// pose.cpp — per-frame inputs: the pinned staging ring, zero-copy slots and their prefetch protocol, copies (ctx.h).
+// pose.cpp — per-frame inputs: the pose transport (ctx.h: RzPoseLink) — its pinned staging ring, zero-copy slots and their prefetch protocol,
+// big-pose ring, the transitions of the current pose — and the copies.
 #include "ctx.h"
 
 #include <immintrin.h>
@@ -8,31 +9,34 @@ using namespace rzi;
 namespace rzi {
 
 // Where the kernels read the current pose from: the device pose block, or (zero-copy, not yet resident) the pinned slot.
+static const char *cur_slot_dev(const rz_ctx *c) { return static_cast<const char *>(c->pl.zc.slot[c->pl.cur.zc_slot].dev); }
+
 const float *src_world(const rz_ctx *c)
 {
-    return (c->zc_cur >= 0 && !c->world_resident && !c->zc_local) ? static_cast<const float *>(c->zc_dev[c->zc_cur]) : c->world;
+    const RzPoseLink::Current &p = c->pl.cur;
+    return (p.zc_slot >= 0 && !p.world_resident && !p.zc_local) ? reinterpret_cast<const float *>(cur_slot_dev(c)) : c->world;
 }
 
 const float *src_morph_w(const rz_ctx *c)
 {
-    if (c->zc_cur < 0 || c->mw_resident) return c->morph_w;
-    const char *base = static_cast<const char *>(c->zc_dev[c->zc_cur]);
-    return reinterpret_cast<const float *>(base + c->zc_mw_off);
+    const RzPoseLink::Current &p = c->pl.cur;
+    return (p.zc_slot < 0 || p.mw_resident) ? c->morph_w : reinterpret_cast<const float *>(cur_slot_dev(c) + p.zc_mw_off);
 }
 
 const float4 *src_local_q(const rz_ctx *c)
 {
-    if (c->zc_cur < 0 || c->local_resident || !c->zc_local) return c->local_q;
-    return reinterpret_cast<const float4 *>(static_cast<const char *>(c->zc_dev[c->zc_cur]) + c->zc_lq_off);
+    const RzPoseLink::Current &p = c->pl.cur;
+    return (p.zc_slot < 0 || p.local_resident || !p.zc_local) ? c->local_q : reinterpret_cast<const float4 *>(cur_slot_dev(c) + p.zc_lq_off);
 }
 
 // Bring every part of a zero-copy pose into the device pose block (one copy out of the pinned slot, stream-ordered).
 int make_resident(rz_ctx *c)
 {
-    if (c->zc_cur < 0 || (c->world_resident && c->mw_resident && c->local_resident)) return RZ_OK;
-    void *dst = c->zc_local ? static_cast<void *>(c->morph_w) : static_cast<void *>(c->world);
-    HIP_TRY(hipMemcpyAsync(dst, c->zc_host[c->zc_cur], c->zc_total, hipMemcpyHostToDevice, c->stream));
-    c->world_resident = c->mw_resident = c->local_resident = true;
+    RzPoseLink::Current &p = c->pl.cur;
+    if (p.resident()) return RZ_OK;
+    void *dst = p.zc_local ? static_cast<void *>(c->morph_w) : static_cast<void *>(c->world);
+    HIP_TRY(hipMemcpyAsync(dst, c->pl.zc.slot[p.zc_slot].host, p.zc_total, hipMemcpyHostToDevice, c->stream));
+    p.world_resident = p.mw_resident = p.local_resident = true;
     return RZ_OK;
 }
 
@@ -43,7 +47,45 @@ int make_resident(rz_ctx *c)
 // only change with the skeleton / morph set / instance count, which start a new epoch.
 uint64_t zc_seq(const rz_ctx *c, uint64_t upload_index_1, int kind)
 {
-    return ((uint64_t)c->zc_epoch << 32) | ((uint64_t)(kind & 3) << 30) | (upload_index_1 & 0x3fffffffull);
+    return ((uint64_t)c->pl.epoch << 32) | ((uint64_t)(kind & 3) << 30) | (upload_index_1 & 0x3fffffffull);
+}
+
+// A new ring epoch: no slot header published so far and no tag a helper workgroup left in a pose block can match a later pose. For whatever changes
+// what a staged pose would mean: the skeleton, the morph set, the crowd, the blocks' layout, a re-built ring, a block overwritten from the device side.
+void retire_pose_tags(rz_ctx *c)
+{
+    c->pl.epoch++;
+    c->pl.cur.seq = 0;
+}
+
+// The HIP side of the reuse proof (pose_ring.h), for both rings: record the event that is due in front of this upload on the compute stream —
+// everything launched before upload u, i.e. every reader of uploads < u (a zero-copy slot is also read, speculatively, by the helper workgroup of
+// the frame before its own: launched earlier still) — poll the one that covers the readers of the slot's previous tenant, and take the slot.
+template <int N>
+static int ring_take(rz_ctx *c, rzring::ReuseProof<N> &proof, const Events<2> &ev, const char *ring, const char *polled, int *slot_out)
+{
+    const int rec = proof.record_event();
+    if (rec >= 0) {
+        HIP_TRY(hipEventRecord(ev[rec], c->stream));
+        proof.recorded(rec);
+    }
+    if (proof.reuses()) {
+        if (!proof.held()) return fail(RZ_ERR_HIP, "%s ring bookkeeping is inconsistent (upload %llu)", ring, (unsigned long long)proof.uploads);
+        if (int r = poll_event(ev[proof.poll_event()], polled)) return r;
+    }
+    *slot_out = proof.take();
+    return RZ_OK;
+}
+
+// A device array of the transport outgrown: build the replacement, drain, assign.
+template <class T> static int grow(rz_ctx *c, Scratch<T> &a, size_t &have, size_t want)
+{
+    Scratch<T> fresh;
+    HIP_TRY(fresh.alloc(want));
+    if (int r = drain(c)) return r;
+    a = std::move(fresh);
+    have = want;
+    return RZ_OK;
 }
 
 }  // namespace rzi
@@ -53,85 +95,35 @@ extern "C" {
 // Pinned staging ring for per-frame inputs: a slot is reused only after the copy that read it has completed.
 static int stage_acquire(rz_ctx *c, size_t need, int *slot_out)
 {
-    if (need > c->stage_bytes || !c->stage[0]) {
+    RzPoseLink::Stage &sg = c->pl.stage;
+    if (need > sg.bytes || !sg.slot[0].host) {
+        RzPoseLink::Stage fresh;
+        fresh.bytes = (need + 4095) / 4096 * 4096;
+        fresh.next = sg.next;
+        // device-mapped, so that a crowd's pose can be pulled out of the slot by a kernel; a slot that cannot be mapped is still good for copies
+        for (Pinned &s : fresh.slot) HIP_TRY(s.alloc(fresh.bytes, false));
+        HIP_TRY(fresh.ev.create());
         if (int r = drain(c)) return r;
-        need = (need + 4095) / 4096 * 4096;
-        for (int i = 0; i < kStageSlots; ++i) {
-            if (c->stage[i]) { (void)hipHostFree(c->stage[i]); c->stage[i] = nullptr; c->stage_dev[i] = nullptr; }
-            c->stage_used[i] = false;
-        }
-        c->stage_bytes = 0;
-        for (int i = 0; i < kStageSlots; ++i) {
-            // device-mapped, so that a crowd's pose can be pulled out of the slot by a kernel; a slot that cannot be mapped is still good for copies
-            if (hipHostMalloc(&c->stage[i], need, hipHostMallocMapped) != hipSuccess) {
-                (void)hipGetLastError();
-                c->stage[i] = nullptr;
-                HIP_TRY(hipHostMalloc(&c->stage[i], need, hipHostMallocDefault));
-            } else if (hipHostGetDevicePointer(&c->stage_dev[i], c->stage[i], 0) != hipSuccess) {
-                (void)hipGetLastError();
-                c->stage_dev[i] = nullptr;
-            }
-        }
-        c->stage_bytes = need;
+        sg = std::move(fresh);
     }
-    const int slot = c->stage_next;
-    c->stage_next = (slot + 1) % kStageSlots;
-    if (c->stage_used[slot]) {
+    const int slot = sg.next;
+    sg.next = (slot + 1) % kStageSlots;
+    if (sg.used[slot]) {
         // the copy that read this slot kStageSlots uploads ago: normally long done
-        if (int r = poll_event(c->stage_ev[slot], "pinned staging slot")) return r;
+        if (int r = poll_event(sg.ev[slot], "pinned staging slot")) return r;
     }
     *slot_out = slot;
     return RZ_OK;
 }
 
-// A slot of the zero-copy ring for the next upload: (re)allocate the ring when the pose outgrew it, record the 1-in-4 event,
-// and make sure the readers of the slot's previous tenant (8 uploads ago) are done.
-static int zc_acquire(rz_ctx *c, size_t need, int *slot_out)
+// What sits in staging slot `slot` has been enqueued on `us`. One event says both "the ring slot may be written again" (the host polls it
+// eight uploads later) and, for a pose that travelled on the upload stream, "the pose has landed" (the compute stream waits for it): a record
+// is ~1.4 us of stream time, and the upload stream is what a host-animated crowd is bound by.
+static int staged_sent(rz_ctx *c, int slot, hipStream_t us, bool piped)
 {
-    if (need > c->zc_bytes) {
-        if (int r = drain(c)) return r;
-        drop_graph(c);
-        const size_t hdr_off = (need + 63) / 64 * 64;
-        for (int i = 0; i < rz_ctx::kZcSlots; ++i) {
-            if (c->zc_host[i]) { (void)hipHostFree(c->zc_host[i]); c->zc_host[i] = nullptr; c->zc_dev[i] = nullptr; }
-            // no pinned, device-mapped memory to be had (locked-memory limits ...): not an error, the caller copies instead
-            if (hipHostMalloc(&c->zc_host[i], hdr_off + 64, hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer(&c->zc_dev[i], c->zc_host[i], 0) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int j = 0; j <= i; ++j)
-                    if (c->zc_host[j]) { (void)hipHostFree(c->zc_host[j]); c->zc_host[j] = nullptr; c->zc_dev[j] = nullptr; }
-                c->zc_bytes = 0; c->zc_cur = -1;
-                return RZ_ERR_UNSUPPORTED;
-            }
-        }
-        for (int i = 0; i < rz_ctx::kZcSlots; ++i) memset(static_cast<char *>(c->zc_host[i]) + hdr_off, 0, 64);
-        c->zc_bytes = need;
-        c->zc_hdr_off = hdr_off;
-        c->zc_epoch++;
-        c->zc_seq_cur = 0;
-        c->zc_uploads = 0;
-        c->zc_ev_seq[0] = c->zc_ev_seq[1] = ~0ull;
-        c->zc_cur = -1;
-    }
-    const uint64_t u = c->zc_uploads;
-    constexpr uint64_t P = rz_ctx::kZcSlots / 2;        // event period
-    if (u % P == 0) {
-        const int e = (int)((u / P) & 1);
-        if (!c->zc_ev[e]) HIP_TRY(hipEventCreateWithFlags(&c->zc_ev[e], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->zc_ev[e], c->stream));      // everything launched before upload u, i.e. every reader of uploads < u
-        c->zc_ev_seq[e] = u;
-    }
-    if (u >= (uint64_t)rz_ctx::kZcSlots) {
-        // previous tenant = upload u - 2P, read by frames launched before upload u - 2P + 1 (and, speculatively, by the helper
-        // workgroup of the frame before it): covered by the event of the first multiple of P that is >= u - 2P + 1 — it is
-        // <= u - P, so it was recorded at least P uploads ago, and it is the older of the two events kept
-        const uint64_t cand = (u - (2 * P - 1) + (P - 1)) / P * P;
-        const int e = (int)((cand / P) & 1);
-        if (c->zc_ev_seq[e] != cand) return fail(RZ_ERR_HIP, "zero-copy ring bookkeeping is inconsistent (upload %llu)", (unsigned long long)u);
-        if (int r = poll_event(c->zc_ev[e], "zero-copy pose ring")) return r;
-    }
-    *slot_out = (int)(u % rz_ctx::kZcSlots);
-    c->zc_uploads = u + 1;
+    HIP_TRY(hipEventRecord(c->pl.stage.ev[slot], us));
+    c->pl.stage.used[slot] = true;
+    if (piped) HIP_TRY(hipStreamWaitEvent(c->stream, c->pl.stage.ev[slot], 0));
     return RZ_OK;
 }
 
@@ -194,16 +186,19 @@ static bool can_pack_rows()
     return ok;
 }
 
+// the morph weights' place in a slot: the weights handed over (none: zeros), then zeros up to their padded size
+static void lay_out_weights(const PoseParts &pp, char *st_mw)
+{
+    if (pp.morph_weights && pp.mb) memcpy(st_mw, pp.morph_weights, pp.mb); else memset(st_mw, 0, pp.mb);
+    if (pp.mwb > pp.mb) memset(st_mw + pp.mb, 0, pp.mwb - pp.mb);
+}
+
 static void lay_out_pose(const rz_ctx *c, const PoseParts &pp, char *st)
 {
-    char *st_mw = pp.local ? st : st + pp.pbytes;
     char *st_pr = pp.local ? st + pp.mwb : st;
     memcpy(st_pr, pp.primary, pp.pbytes);
     if (pp.sbytes) memcpy(st_pr + pp.pbytes, pp.secondary, pp.sbytes);
-    if (pp.local || c->M > 0) {
-        if (pp.morph_weights && pp.mb) memcpy(st_mw, pp.morph_weights, pp.mb); else memset(st_mw, 0, pp.mb);
-        if (pp.mwb > pp.mb) memset(st_mw + pp.mb, 0, pp.mwb - pp.mb);
-    }
+    if (pp.local || c->M > 0) lay_out_weights(pp, pp.local ? st : st + pp.pbytes);
 }
 
 // One character: no copy at all. The pose is laid out in a pinned, device-mapped slot; the frame's own kernels read it.
@@ -214,74 +209,82 @@ static void lay_out_pose(const rz_ctx *c, const PoseParts &pp, char *st)
 // caller of rz_map_pose); zc_publish writes the number and makes the slot the current pose.
 static int zc_open(rz_ctx *c, const PoseParts &pp, int *zs)
 {
-    if (int r = zc_acquire(c, std::max<size_t>(std::max<size_t>((size_t)c->B * 64 + pp.mwb, pp.mwb + (size_t)c->B * 28), 4096), zs)) return r;
-    char *slot = static_cast<char *>(c->zc_host[*zs]);
-    *reinterpret_cast<volatile uint64_t *>(slot + c->zc_hdr_off) = 0;
+    const size_t need = std::max<size_t>(std::max<size_t>((size_t)c->B * 64 + pp.mwb, pp.mwb + (size_t)c->B * 28), 4096);
+    if (need > c->pl.zc.bytes) {        // the ring is (re)built when the pose outgrew it
+        RzPoseLink::ZeroCopy fresh;
+        fresh.bytes = need; fresh.hdr_off = (need + 63) / 64 * 64;
+        for (Pinned &s : fresh.slot) {
+            // no pinned, device-mapped memory to be had (locked-memory limits ...): not an error, the caller copies instead
+            if (s.alloc(fresh.hdr_off + 64, true) != hipSuccess) return RZ_ERR_UNSUPPORTED;
+            memset(static_cast<char *>(s.host) + fresh.hdr_off, 0, 64);
+        }
+        HIP_TRY(fresh.ev.create());
+        if (int r = drain(c)) return r;
+        drop_graph(c);
+        c->pl.zc = std::move(fresh);
+        c->pl.cur.zc_slot = -1;
+        retire_pose_tags(c);            // (before zc_publish forms this upload's sequence number: a re-built ring never matches old tags)
+    }
+    if (int r = ring_take(c, c->pl.zc.proof, c->pl.zc.ev, "zero-copy", "zero-copy pose ring", zs)) return r;
+    *reinterpret_cast<volatile uint64_t *>(static_cast<char *>(c->pl.zc.slot[*zs].host) + c->pl.zc.hdr_off) = 0;
     std::atomic_thread_fence(std::memory_order_seq_cst);
     return RZ_OK;
 }
 
 static void zc_publish(rz_ctx *c, const PoseParts &pp, int zs, uint64_t upload_index_1)
 {
-    char *slot = static_cast<char *>(c->zc_host[zs]);
-    volatile uint64_t *hdr = reinterpret_cast<volatile uint64_t *>(slot + c->zc_hdr_off);
+    RzPoseLink::Current &p = c->pl.cur;
+    volatile uint64_t *hdr = reinterpret_cast<volatile uint64_t *>(static_cast<char *>(c->pl.zc.slot[zs].host) + c->pl.zc.hdr_off);
     std::atomic_thread_fence(std::memory_order_seq_cst);
     const int kind = pp.local ? (pp.sbytes ? 2 : 1) : 0;
-    const uint64_t seq = zc_seq(c, upload_index_1, kind);
-    *hdr = seq;
-    c->zc_seq_cur = seq;
-    point_pose_slot(c, c->pose_slot ^ 1);   // where the pose will live once something makes it resident
-    c->zc_cur = zs; c->zc_local = pp.local; c->zc_kind = kind; c->zc_total = pp.total;
-    c->zc_mw_off = pp.local ? 0 : pp.pbytes; c->zc_lq_off = pp.mwb;
-    c->world_resident = pp.local;           // a local pose has no world matrices to bring over: rz_fk_kernel writes them
-    c->mw_resident = false;
-    c->local_resident = !pp.local;
+    p.seq = zc_seq(c, upload_index_1, kind);
+    *hdr = p.seq;
+    point_pose_slot(c, c->pl.pose_slot ^ 1);   // where the pose will live once something makes it resident
+    p.zc_slot = zs; p.zc_local = pp.local; p.zc_kind = kind; p.zc_total = pp.total;
+    p.zc_mw_off = pp.local ? 0 : pp.pbytes; p.zc_lq_off = pp.mwb;
+    p.world_resident = pp.local;            // a local pose has no world matrices to bring over: rz_fk_kernel writes them
+    p.mw_resident = false;
+    p.local_resident = !pp.local;
 }
 
-static int upload_pose_zero_copy(rz_ctx *c, const PoseParts &pp)
+// The pose block is about to be written from the device side — a copy, a pull, a kernel that produces the pose there: nothing of the
+// current pose sits in a pinned slot any more, and a block a helper workgroup may have staged and tagged is overwritten, so no later
+// zero-copy pose may match that tag.
+static void pose_leaves_pinned_slots(rz_ctx *c)
 {
-    int zs = 0;
-    if (int r = zc_open(c, pp, &zs)) return r;
-    lay_out_pose(c, pp, static_cast<char *>(c->zc_host[zs]));
-    zc_publish(c, pp, zs, c->zc_uploads);       // zc_uploads is already this upload's index + 1
-    return RZ_OK;
+    RzPoseLink::Current &p = c->pl.cur;
+    p.zc_slot = -1;
+    retire_pose_tags(c);
+    p.world_resident = p.mw_resident = p.local_resident = true;
 }
 
-// A block of the big-pose ring for the next upload of more than 256 KB (ctx.h): (re)allocate the ring when the layout grew, record
-// the one-in-four event, make sure the readers of the block's previous tenant (kBigBlocks uploads ago) are done.
-static int big_acquire(rz_ctx *c, float **block)
+// ... and the block it is written into: the other of the two pose blocks, or for a piped pose (more than 256 KB) the next block of the
+// big-pose ring (ctx.h), (re)built when the layout grew. c->world / c->morph_w / c->local_q name it under the current counts afterwards.
+static int take_pose_block(rz_ctx *c, bool piped)
 {
-    constexpr uint64_t N = rz_ctx::kBigBlocks, P = N / 2;
+    pose_leaves_pinned_slots(c);
+    if (!piped) {
+        point_pose_slot(c, (c->pl.pose_slot & 1) ^ 1);
+        return RZ_OK;
+    }
+    const RzPoseLink &pl = c->pl;
     const size_t Mq = std::max<uint32_t>(c->M, 1);
-    const size_t need = (size_t)c->pose_alloc_I * c->pose_alloc_B * 16 + (((size_t)c->pose_alloc_I * std::max<size_t>(c->pose_alloc_M, Mq) + 3) / 4 * 4) +
-                        (size_t)c->pose_alloc_I * c->pose_alloc_B * 7 + 4;
-    if (!c->big_blk[0] || c->big_floats < need) {
-        if (int r = drain(c)) return r;
-        drop_graph(c);
-        free_big_ring(c);
-        for (uint64_t k = 0; k < N; ++k) {
-            HIP_TRY(hipMalloc(&c->big_blk[k], need * sizeof(float)));
-            HIP_TRY(hipMemsetAsync(c->big_blk[k], 0, need * sizeof(float), c->stream));
+    const size_t need = pl.alloc_I * pl.alloc_B * 16 + ((pl.alloc_I * std::max<size_t>(pl.alloc_M, Mq) + 3) / 4 * 4) + pl.alloc_I * pl.alloc_B * 7 + 4;
+    if (!pl.big.blk[0] || pl.big.floats < need) {
+        RzPoseLink::Big fresh;
+        fresh.floats = need;
+        for (Scratch<float> &b : fresh.blk) {
+            HIP_TRY(b.alloc(need));
+            HIP_TRY(hipMemsetAsync(b, 0, need * sizeof(float), c->stream));
         }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->big_floats = need;
+        HIP_TRY(fresh.ev.create());
+        if (int r = drain(c)) return r;         // (the memsets with it)
+        drop_graph(c);
+        c->pl.big = std::move(fresh);
     }
-    const uint64_t u = c->big_uploads;
-    if (u % P == 0) {
-        const int e = (int)((u / P) & 1);
-        HIP_TRY(hipEventRecord(c->big_ev[e], c->stream));     // everything launched before upload u, i.e. every reader of uploads < u
-        c->big_ev_seq[e] = u;
-    }
-    if (u >= N) {
-        // previous tenant = upload u - N, read by frames launched before upload u - N + 1: covered by the event of the first multiple
-        // of P that is >= u - N + 1 — it is <= u - P, the older of the two events kept (the arithmetic of zc_acquire)
-        const uint64_t cand = (u - (N - 1) + (P - 1)) / P * P;
-        const int e = (int)((cand / P) & 1);
-        if (c->big_ev_seq[e] != cand) return fail(RZ_ERR_HIP, "big-pose ring bookkeeping is inconsistent (upload %llu)", (unsigned long long)u);
-        if (int r = poll_event(c->big_ev[e], "big-pose ring")) return r;
-    }
-    *block = c->big_blk[u % N];
-    c->big_uploads = u + 1;
+    int k = 0;
+    if (int r = ring_take(c, c->pl.big.proof, c->pl.big.ev, "big-pose", "big-pose ring", &k)) return r;
+    point_pose_at(c, c->pl.big.blk[k]);
     return RZ_OK;
 }
 
@@ -289,9 +292,9 @@ static int big_acquire(rz_ctx *c, float **block)
 // — on the upload stream for big poses, so the upload overlaps whatever the compute stream is still running; the compute stream then
 // waits for it. Three steps, shared by rz_set_pose* (the library fills the slot: upload_pose_copy) and rz_map_pose / rz_commit_pose (the
 // caller does): copy_begin takes the slot, the slot is filled, copy_send enqueues everything.
-static size_t stage_need(const rz_ctx *c, const PoseParts &pp)
+static int copy_begin(rz_ctx *c, const PoseParts &pp, int *slot)
 {
-    return std::max<size_t>((size_t)c->I * c->B * 64 + pp.mwb, pp.mwb + (size_t)c->I * c->B * 28);
+    return stage_acquire(c, std::max<size_t>((size_t)c->I * c->B * 64 + pp.mwb, pp.mwb + (size_t)c->I * c->B * 28), slot);
 }
 
 // Large poses (instanced crowds: MBs) take the upload stream and a block of the big-pose ring (ctx.h): nothing enqueued so far
@@ -301,6 +304,11 @@ static size_t stage_need(const rz_ctx *c, const PoseParts &pp)
 // Overlapped-front protocol (crowds, opt-in): EVERY per-frame input travels on the upload stream and is consumed there,
 // by the front kernels — stream order is the only ordering needed, no event at all.
 static bool pose_piped(const rz_ctx *c, const PoseParts &pp) { return !c->overlap_on && pp.total > (256u << 10); }
+// the stream a pose travels on ...
+static hipStream_t pose_stream(const rz_ctx *c, bool piped) { return (piped || c->overlap_on) ? c->up_stream : c->stream; }
+// ... and whether what a device-produced pose of one character is made from (a frame number, a motion state with its layers) rides in the
+// kernel arguments instead: nothing is uploaded at all
+static bool rides_in_arguments(const rz_ctx *c, bool piped) { return c->I == 1 && !piped && !c->overlap_on && c->t_zerocopy != 0; }
 
 // How it crosses the host link (tools/archive/overlapbench, tools/pullbench: profiles/r5_overlapbench.txt, r5_pullbench.txt):
 //  * world matrices of a crowd are PULLED out of the slot by rz_pull_pose_kernel (kernels/front.hip), three rows per bone: the
@@ -310,71 +318,47 @@ static bool pose_piped(const rz_ctx *c, const PoseParts &pp) { return !c->overla
 //    (27.7 us per frame with the copy running, 35.5 us with the pull), so they stay with hipMemcpyAsync ("pose_pull" = 1 pulls them too).
 static bool pose_pullable(const rz_ctx *c, const PoseParts &pp, int slot)
 {
-    return (pose_piped(c, pp) || c->overlap_on) && c->stage_dev[slot] && (pp.total & 3u) == 0;
-}
-
-static int copy_begin(rz_ctx *c, const PoseParts &pp, int *slot)
-{
-    return stage_acquire(c, stage_need(c, pp), slot);
+    return (pose_piped(c, pp) || c->overlap_on) && c->pl.stage.slot[slot].dev && (pp.total & 3u) == 0;
 }
 
 // `rows`: the slot holds the world matrices as 48 B per bone (pack_rows_avx512's layout) followed by the weights; otherwise the pose in
 // lay_out_pose's layout. `pull`: rz_pull_pose_kernel instead of hipMemcpyAsync (always with `rows`).
 static int copy_send(rz_ctx *c, const PoseParts &pp, int slot, bool pull, bool rows)
 {
-    c->zc_cur = -1;
-    c->zc_seq_cur = 0;
-    c->zc_epoch++;        // this copy overwrites a pose block a helper may have staged and tagged: no later zero-copy pose may match that tag
-    c->world_resident = c->mw_resident = c->local_resident = true;
     const bool piped = pose_piped(c, pp);
-    hipStream_t us = (piped || c->overlap_on) ? c->up_stream : c->stream;
-    float *block = nullptr;
-    if (piped) {
-        if (int r = big_acquire(c, &block)) return r;
-    }
-    // c->world / c->morph_w / c->local_q now name the pose's block under the current counts
-    if (piped) point_pose_at(c, block);
-    else point_pose_slot(c, (c->pose_slot & 1) ^ 1);
+    hipStream_t us = pose_stream(c, piped);
+    if (int r = take_pose_block(c, piped)) return r;
     void *dst = pp.local ? static_cast<void *>(c->morph_w) : static_cast<void *>(c->world);
     const size_t bones = (size_t)c->I * c->B;
-    if (pull) HIP_TRY(rz_launch_pull_pose(c->stage_dev[slot], dst, rows ? (uint32_t)bones : 0u, rows ? pp.total - pp.pbytes : pp.total, us));
-    else HIP_TRY(hipMemcpyAsync(dst, c->stage[slot], pp.total, hipMemcpyHostToDevice, us));
-    c->last_upload_pulled = pull; c->last_upload_rows = rows;
-    // one event says both "the ring slot may be written again" (the host polls it eight uploads later) and "the pose has landed" (the
-    // compute stream waits for it): a record is ~1.4 us of stream time, and the upload stream is what a host-animated crowd is bound by
-    HIP_TRY(hipEventRecord(c->stage_ev[slot], us));
-    c->stage_used[slot] = true;
-    if (piped) HIP_TRY(hipStreamWaitEvent(c->stream, c->stage_ev[slot], 0));
-    return RZ_OK;
+    if (pull) HIP_TRY(rz_launch_pull_pose(c->pl.stage.slot[slot].dev, dst, rows ? (uint32_t)bones : 0u, rows ? pp.total - pp.pbytes : pp.total, us));
+    else HIP_TRY(hipMemcpyAsync(dst, c->pl.stage.slot[slot].host, pp.total, hipMemcpyHostToDevice, us));
+    c->pl.last_pulled = pull; c->pl.last_rows = rows;
+    return staged_sent(c, slot, us, piped);
 }
 
 static int upload_pose_copy(rz_ctx *c, const PoseParts &pp)
 {
     int slot = 0;
     if (int r = copy_begin(c, pp, &slot)) return r;
-    char *st = static_cast<char *>(c->stage[slot]);
+    char *st = static_cast<char *>(c->pl.stage.slot[slot].host);
     const bool pull = pose_pullable(c, pp, slot) && (c->t_pull == 1 || (c->t_pull < 0 && !pp.local));
     const size_t bones = (size_t)c->I * c->B;
     bool rows = false;
     if (pull && !pp.local && can_pack_rows()) {
         rows = pack_rows_avx512(static_cast<const float *>(pp.primary), bones, reinterpret_cast<float *>(st));
-        if (rows && c->M > 0) {
-            char *st_mw = st + bones * 48;
-            if (pp.morph_weights && pp.mb) memcpy(st_mw, pp.morph_weights, pp.mb); else memset(st_mw, 0, pp.mb);
-            if (pp.mwb > pp.mb) memset(st_mw + pp.mb, 0, pp.mwb - pp.mb);
-        }
+        if (rows && c->M > 0) lay_out_weights(pp, st + bones * 48);
     }
     if (!rows) lay_out_pose(c, pp, st);     // (a matrix that is not affine: the whole pose as it was handed over)
     return copy_send(c, pp, slot, pull, rows);
 }
 
-// What a new pose does to the context BEFORE its bytes move: the pose kind decides the plan, the plan decides which stream protocol the
-// frame (and therefore this upload) follows.
-static int pose_kind_changes(rz_ctx *c, bool local)
+// A pose of another kind is about to replace the current one — what that does to the context BEFORE its bytes move: the pose kind decides
+// the plan, the plan decides which stream protocol the frame (and therefore this upload) follows.
+static int pose_begins(rz_ctx *c, bool local, bool local_t = false, bool sampled = false)
 {
-    c->pose_set = false;
-    c->pose_local = local;
-    c->pose_sampled = false;
+    RzPoseLink::Current &p = c->pl.cur;
+    p.set = false;
+    p.local = local; p.local_t = local_t; p.sampled = sampled;
     c->fk_stale = false;                // (it spoke of the pose this one replaces: rz_read_world / rz_read_palette must not solve THAT on demand any more)
     Plan upl;
     if (int r = frame_plan(c, &upl)) return r;          // the plan frames will use (run lists first), not the whole-palette fallback
@@ -393,39 +377,46 @@ static PoseParts pose_parts(const rz_ctx *c, const void *primary, size_t pbytes,
 
 static bool pose_zero_copy(const rz_ctx *c, const PoseParts &pp) { return !c->overlap_on && c->I == 1 && pp.total <= (256u << 10) && c->t_zerocopy != 0; }
 
-// ordered compaction of the non-zero weights for the one-launch path (instance 0)
-static void compact_morph_list(rz_ctx *c, const float *morph_weights)
+// The pose is in place. `morph_weights`: the weight vector the host handed over (null: all zero) — the non-zero weights of instance 0 are
+// compacted, in order, for the one-launch path; `on_device`: the weights only exist on the device — the prep kernel compacts them.
+static void pose_in_place(rz_ctx *c, const float *morph_weights, bool on_device = false)
 {
-    memset(&c->ml, 0, sizeof c->ml);
+    RzMorphList &ml = c->pl.cur.ml;
+    memset(&ml, 0, sizeof ml);
     if (c->M > 0 && morph_weights && c->I == 1) {
         int n = 0;
         for (uint32_t m = 0; m < c->M; ++m) {
             const float w = morph_weights[m];
             if (w == 0.0f) continue;
-            if (n < kKargMorphs) { c->ml.idx[n] = m; c->ml.w[n] = w; }
+            if (n < kKargMorphs) { ml.idx[n] = m; ml.w[n] = w; }
             ++n;
         }
-        c->ml.count = n <= kKargMorphs ? n : -1;
+        ml.count = n <= kKargMorphs ? n : -1;
     }
+    if (on_device && c->M > 0) ml.count = -1;
+    c->pl.cur.I = c->I;
+    c->pl.cur.set = true;
 }
 
 // Shared tail of rz_set_pose / rz_set_pose_local.
 static int upload_pose(rz_ctx *c, const void *primary, size_t pbytes, const void *secondary, size_t sbytes, bool local,
                        const float *morph_weights)
 {
-    c->map_layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
-    if (int r = pose_kind_changes(c, local)) return r;
+    c->pl.map.layout = -1;              // a pose handed over whole cancels a mapping that was never committed
+    if (int r = pose_begins(c, local, sbytes != 0)) return r;
     const PoseParts pp = pose_parts(c, primary, pbytes, secondary, sbytes, local, morph_weights);
-    int rc = RZ_ERR_UNSUPPORTED;
+    int rc = RZ_ERR_UNSUPPORTED, zs = 0;
     if (pose_zero_copy(c, pp)) {
-        rc = upload_pose_zero_copy(c, pp);
+        rc = zc_open(c, pp, &zs);
         if (rc == RZ_ERR_UNSUPPORTED) c->t_zerocopy = 0;      // no pinned device-mapped memory: from now on every pose is copied
+        if (rc == RZ_OK) {
+            lay_out_pose(c, pp, static_cast<char *>(c->pl.zc.slot[zs].host));
+            zc_publish(c, pp, zs, c->pl.zc.proof.uploads);      // (already this upload's index + 1)
+        }
     }
     if (rc == RZ_ERR_UNSUPPORTED) rc = upload_pose_copy(c, pp);
     if (rc) return rc;
-    c->pose_I = c->I;
-    compact_morph_list(c, morph_weights);
-    c->pose_set = true;
+    pose_in_place(c, morph_weights);
     return RZ_OK;
 }
 
@@ -465,7 +456,8 @@ int rz_map_pose(rz_ctx *c, int layout, float **matrices, float **morph_weights)
     if (layout != RZ_POSE_WORLD16 && layout != RZ_POSE_ROWS12) return fail(RZ_ERR_INVALID, "rz_map_pose: layout must be RZ_POSE_WORLD16 or RZ_POSE_ROWS12");
     if (c->B == 0) return fail(RZ_ERR_INVALID, "no skeleton uploaded");
     if (int r = ensure_pose_buffers(c)) return r;
-    c->map_layout = -1;
+    RzPoseLink::Map &map = c->pl.map;
+    map.layout = -1;
     const size_t bones = (size_t)c->I * c->B;
     // (the opt-in overlapped-front protocol moves every per-frame input onto the upload stream and decides that per pose KIND at upload
     // time: such a context hands its poses over with rz_set_pose)
@@ -475,14 +467,14 @@ int rz_map_pose(rz_ctx *c, int layout, float **matrices, float **morph_weights)
     if (pose_zero_copy(c, pp)) {
         if (layout == RZ_POSE_ROWS12)
             return fail(RZ_ERR_UNSUPPORTED, "rz_map_pose: a pose of %zu bytes is read in place by its frame, which wants whole 4 x 4 matrices: map it as RZ_POSE_WORLD16 (rows are for poses of more than 256 KB)", pp.total);
-        // Frames of the RESIDENT pose may be launched between this call and the commit. The ring's reuse proof (zc_acquire) counts every
+        // Frames of the RESIDENT pose may be launched between this call and the commit. The ring's reuse proof (pose_ring.h) counts every
         // reader of an earlier upload as launched before this upload's slot was taken — so such a frame must not be the first one of a
         // zero-copy pose, which reads its pinned slot: bring that pose into its device block now (one stream-ordered copy, rare).
-        if (c->pose_set)
+        if (c->pl.cur.set)
             if (int r = make_resident(c)) return r;
         int zs = 0;
         const int rc = zc_open(c, pp, &zs);
-        if (rc == RZ_OK) { c->map_zc = true; c->map_slot = zs; c->map_upload = c->zc_uploads; st = static_cast<char *>(c->zc_host[zs]); }
+        if (rc == RZ_OK) { map.zc = true; map.slot = zs; map.upload = c->pl.zc.proof.uploads; st = static_cast<char *>(c->pl.zc.slot[zs].host); }
         else if (rc == RZ_ERR_UNSUPPORTED) c->t_zerocopy = 0;       // no pinned device-mapped memory: from now on every pose is copied
         else return rc;
     }
@@ -491,29 +483,29 @@ int rz_map_pose(rz_ctx *c, int layout, float **matrices, float **morph_weights)
         if (int r = copy_begin(c, pp, &slot)) return r;
         if (layout == RZ_POSE_ROWS12 && !(pose_pullable(c, pp, slot) && c->t_pull != 0))
             return fail(RZ_ERR_UNSUPPORTED, "rz_map_pose: rows need the pull kernel (a pose of more than 256 KB, a device-mapped ring, \"pose_pull\" != 0): map this pose as RZ_POSE_WORLD16");
-        c->map_zc = false; c->map_slot = slot;
-        st = static_cast<char *>(c->stage[slot]);
+        map.zc = false; map.slot = slot;
+        st = static_cast<char *>(c->pl.stage.slot[slot].host);
     }
     const size_t mat_bytes = bones * (layout == RZ_POSE_ROWS12 ? 48 : 64);
     if (c->M > 0) {
-        memset(st + mat_bytes, 0, pp.mwb);          // weights the caller does not write are zero
+        lay_out_weights(pp, st + mat_bytes);        // weights the caller does not write are zero
         if (morph_weights) *morph_weights = reinterpret_cast<float *>(st + mat_bytes);
     }
     *matrices = reinterpret_cast<float *>(st);
-    c->map_layout = layout; c->map_I = c->I; c->map_B = c->B; c->map_M = c->M; c->map_ptr = st;
+    map.layout = layout; map.I = c->I; map.B = c->B; map.M = c->M; map.ptr = st;
     return RZ_OK;
 }
 
 int rz_commit_pose(rz_ctx *c)
 {
     if (int r = use(c)) return r;
-    if (c->map_layout < 0) return fail(RZ_ERR_INVALID, "rz_commit_pose without rz_map_pose (a pose call in between cancels a mapping)");
-    const int layout = c->map_layout;
-    const bool rows = layout == RZ_POSE_ROWS12;
-    c->map_layout = -1;
-    if (c->map_I != c->I || c->map_B != c->B || c->map_M != c->M) return fail(RZ_ERR_INVALID, "rz_commit_pose: the crowd, skeleton or morph set changed since rz_map_pose");
+    RzPoseLink::Map &map = c->pl.map;
+    if (map.layout < 0) return fail(RZ_ERR_INVALID, "rz_commit_pose without rz_map_pose (a pose call in between cancels a mapping)");
+    const bool rows = map.layout == RZ_POSE_ROWS12;
+    map.layout = -1;
+    if (map.I != c->I || map.B != c->B || map.M != c->M) return fail(RZ_ERR_INVALID, "rz_commit_pose: the crowd, skeleton or morph set changed since rz_map_pose");
     const size_t bones = (size_t)c->I * c->B;
-    char *st = c->map_ptr;
+    char *st = map.ptr;
     const float *mw = c->M > 0 ? reinterpret_cast<const float *>(st + bones * (rows ? 48 : 64)) : nullptr;
     const PoseParts pp = pose_parts(c, nullptr, bones * 64, nullptr, 0, false, nullptr);
     // the same decisions as at map time, on the state as it is NOW (a context under the overlapped-front protocol was refused at map time
@@ -521,21 +513,19 @@ int rz_commit_pose(rz_ctx *c)
     // resident pose as it was
     if (c->t_overlap == 1 || c->overlap_on) return fail(RZ_ERR_UNSUPPORTED, "rz_commit_pose: the overlapped-front protocol was switched on since rz_map_pose; hand the pose over with rz_set_pose");
     const bool zc_now = pose_zero_copy(c, pp);
-    bool same = c->map_zc ? (zc_now && c->zc_host[c->map_slot] == static_cast<void *>(st) && c->zc_uploads == c->map_upload)
-                          : (!zc_now && c->stage[c->map_slot] == static_cast<void *>(st));
-    const bool pull = !c->map_zc && same && pose_pullable(c, pp, c->map_slot) && c->t_pull != 0;       // ("pose_pull" = 0 since the map: rows are refused below)
+    bool same = map.zc ? (zc_now && c->pl.zc.slot[map.slot].host == static_cast<void *>(st) && c->pl.zc.proof.uploads == map.upload)
+                       : (!zc_now && c->pl.stage.slot[map.slot].host == static_cast<void *>(st));
+    const bool pull = !map.zc && same && pose_pullable(c, pp, map.slot) && c->t_pull != 0;       // ("pose_pull" = 0 since the map: rows are refused below)
     if (rows && !pull) same = false;
     if (!same) {
         if (rows) return fail(RZ_ERR_UNSUPPORTED, "rz_commit_pose: the context changed since rz_map_pose and this pose can no longer be pulled as rows: map it again");
         // a plain rz_set_pose out of the mapped memory (the slot it takes is the NEXT one of its ring, never the source)
         return upload_pose(c, st, bones * 64, nullptr, 0, false, mw);
     }
-    if (int r = pose_kind_changes(c, false)) return r;
-    if (c->map_zc) zc_publish(c, pp, c->map_slot, c->map_upload);
-    else if (int r = copy_send(c, pp, c->map_slot, pull, rows)) return r;
-    c->pose_I = c->I;
-    compact_morph_list(c, mw);
-    c->pose_set = true;
+    if (int r = pose_begins(c, false)) return r;
+    if (map.zc) zc_publish(c, pp, map.slot, map.upload);
+    else if (int r = copy_send(c, pp, map.slot, pull, rows)) return r;
+    pose_in_place(c, mw);
     return RZ_OK;
 }
 
@@ -546,7 +536,6 @@ int rz_set_pose_local(rz_ctx *c, const float *local_rotations4, const float *loc
     if (!local_rotations4) return fail(RZ_ERR_INVALID, "null local rotations");
     if (int r = ensure_pose_buffers(c)) return r;
     const size_t nq = (size_t)c->I * c->B;
-    c->pose_local_t = local_translations3 != nullptr;
     return upload_pose(c, local_rotations4, nq * sizeof(float4), local_translations3, local_translations3 ? nq * 3 * sizeof(float) : 0, true,
                        morph_weights);
 }
@@ -565,41 +554,24 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
     for (uint32_t i = 0; i < c->I; ++i)
         if (!finite_f(frames[i])) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
     if (int r = ensure_pose_buffers(c)) return r;
-    if (c->I > c->an_frames_alloc) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        dfree(c->an_frames);
-        HIP_TRY(hipMalloc(&c->an_frames, (size_t)c->I * sizeof(float)));
-        c->an_frames_alloc = c->I;
-    }
-    c->pose_set = false;
-    c->fk_stale = false;
-    c->pose_sampled = true;
-    c->pose_local = true;
-    c->pose_local_t = true;
-    Plan upl;
-    if (int r = frame_plan(c, &upl)) return r;
-    if (int r = set_overlap(c, want_overlap(c, upl))) return r;
-    c->zc_cur = -1;                         // the pose is produced on the device: nothing of it sits in a pinned slot
-    c->zc_seq_cur = 0;
-    c->zc_epoch++;                          // its frame writes world matrices / weights into the pose block: tags staged before never match again
-    c->world_resident = c->mw_resident = c->local_resident = true;
-    c->frames_inline = c->I == 1 && !c->overlap_on && c->t_zerocopy != 0;
-    if (c->frames_inline) {
-        c->frame0 = frames[0];              // one character: the frame number rides in rz_fk_kernel's arguments
+    RzPoseLink &pl = c->pl;
+    if (c->I > pl.an_frames_alloc)
+        if (int r = grow(c, pl.an_frames, pl.an_frames_alloc, c->I)) return r;
+    if (int r = pose_begins(c, true, true, true)) return r;
+    pose_leaves_pinned_slots(c);            // the pose is produced on the device: its frame writes world matrices / weights into the pose block
+    pl.cur.frames_inline = rides_in_arguments(c, false);
+    if (pl.cur.frames_inline) {
+        pl.cur.frame0 = frames[0];          // one character: the frame number rides in rz_fk_kernel's arguments
     } else {
         int slot = 0;
         if (int r = stage_acquire(c, std::max<size_t>((size_t)c->I * sizeof(float), 4096), &slot)) return r;
-        memcpy(c->stage[slot], frames, (size_t)c->I * sizeof(float));
+        memcpy(pl.stage.slot[slot].host, frames, (size_t)c->I * sizeof(float));
         hipStream_t us = front_stream(c);   // consumed by rz_fk_kernel, which runs on this stream
-        HIP_TRY(hipMemcpyAsync(c->an_frames, c->stage[slot], (size_t)c->I * sizeof(float), hipMemcpyHostToDevice, us));
-        HIP_TRY(hipEventRecord(c->stage_ev[slot], us));
-        c->stage_used[slot] = true;
+        HIP_TRY(hipMemcpyAsync(pl.an_frames, pl.stage.slot[slot].host, (size_t)c->I * sizeof(float), hipMemcpyHostToDevice, us));
+        if (int r = staged_sent(c, slot, us, false)) return r;
     }
-    point_pose_slot(c, c->pose_slot);       // the sampled pose is written by rz_fk_kernel under the current counts
-    memset(&c->ml, 0, sizeof c->ml);
-    if (c->M > 0) c->ml.count = -1;          // the weights only exist on the device: the prep kernel compacts them
-    c->pose_I = c->I;
-    c->pose_set = true;
+    point_pose_slot(c, pl.pose_slot);       // the sampled pose is written by rz_fk_kernel under the current counts
+    pose_in_place(c, nullptr, true);
     return RZ_OK;
 }
 
@@ -673,55 +645,38 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
         fill(&one);
     } else {
         if (int r = stage_acquire(c, std::max<size_t>(n_bytes, 4096), &slot)) return r;
-        fill(c->stage[slot]);
-        sv = static_cast<const RzMotionState *>(c->stage[slot]);
+        fill(c->pl.stage.slot[slot].host);
+        sv = static_cast<const RzMotionState *>(c->pl.stage.slot[slot].host);
         lv = reinterpret_cast<const RzMotionLayer *>(sv + c->I);
     }
     int bad = check_motion_states(c, sv);
     if (!bad && n_layers) bad = check_motion_layers(c, n_layers, lv);
     if (bad) {
-        if (slot >= 0) c->stage_next = slot;
+        if (slot >= 0) c->pl.stage.next = slot;
         return bad;
     }
     if (int r = ensure_pose_buffers(c)) return r;
-    c->map_layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
-    c->pose_local_t = true;
-    if (int r = pose_kind_changes(c, true)) return r;
+    RzPoseLink &pl = c->pl;
+    pl.map.layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
+    if (int r = pose_begins(c, true, true)) return r;
     const size_t nq = (size_t)c->I * c->B;
     const PoseParts pp = pose_parts(c, nullptr, nq * sizeof(float4), nullptr, nq * 3 * sizeof(float), true, nullptr);
     const bool piped = pose_piped(c, pp);
-    hipStream_t us = (piped || c->overlap_on) ? c->up_stream : c->stream;
-    const bool inline_state = c->I == 1 && !piped && !c->overlap_on && c->t_zerocopy != 0;      // (the rule of frames_inline)
+    hipStream_t us = pose_stream(c, piped);
+    const bool inline_state = rides_in_arguments(c, piped);
     if (!inline_state) {
-        if (!layered && c->I > c->mo_states_alloc) {
-            if (int r = drain(c)) return r;
-            dfree(c->mo_states);
-            HIP_TRY(hipMalloc(&c->mo_states, (size_t)c->I * sizeof(RzMotionState)));
-            c->mo_states_alloc = c->I;
-        }
-        if (layered && n_rec > c->mo_layers_alloc) {
-            if (int r = drain(c)) return r;
-            dfree(c->mo_layers);
-            c->mo_layers_alloc = 0;
-            HIP_TRY(hipMalloc(&c->mo_layers, (size_t)c->I * (1 + kRzMaxLayers) * sizeof(RzMotionLayer)));
-            c->mo_layers_alloc = (size_t)c->I * (1 + kRzMaxLayers);
-        }
-        if (c->mo_states_stream && c->mo_states_stream != us) HIP_TRY(hipStreamSynchronize(c->mo_states_stream));     // (the protocol changed: rare)
-        c->mo_states_stream = us;
+        if (!layered && c->I > pl.mo_states_alloc)
+            if (int r = grow(c, pl.mo_states, pl.mo_states_alloc, c->I)) return r;
+        if (layered && n_rec > pl.mo_layers_alloc)
+            if (int r = grow(c, pl.mo_layers, pl.mo_layers_alloc, (size_t)c->I * (1 + kRzMaxLayers))) return r;
+        if (pl.mo_states_stream && pl.mo_states_stream != us) HIP_TRY(hipStreamSynchronize(pl.mo_states_stream));     // (the protocol changed: rare)
+        pl.mo_states_stream = us;
         if (slot < 0) {
             if (int r = stage_acquire(c, 4096, &slot)) return r;
-            memcpy(c->stage[slot], &one, n_bytes);
+            memcpy(pl.stage.slot[slot].host, &one, n_bytes);
         }
     }
-    float *block = nullptr;
-    if (piped)
-        if (int r = big_acquire(c, &block)) return r;
-    c->zc_cur = -1;
-    c->zc_seq_cur = 0;
-    c->zc_epoch++;        // the kernel overwrites a pose block a helper may have staged and tagged: no later zero-copy pose may match that tag
-    c->world_resident = c->mw_resident = c->local_resident = true;
-    if (piped) point_pose_at(c, block);
-    else point_pose_slot(c, (c->pose_slot & 1) ^ 1);
+    if (int r = take_pose_block(c, piped)) return r;
     RzLayerParams lp;
     memset(&lp, 0, sizeof lp);
     RzMotionParams &mp = lp.m;
@@ -729,12 +684,12 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
         mp.state0 = one.st;
         memcpy(lp.layers0, one.ly, sizeof one.ly);
     } else if (layered) {
-        HIP_TRY(hipMemcpyAsync(c->mo_layers, c->stage[slot], n_bytes, hipMemcpyHostToDevice, us));
-        mp.states = reinterpret_cast<const RzMotionState *>(c->mo_layers);
-        lp.layers = c->mo_layers + c->I;
+        HIP_TRY(hipMemcpyAsync(pl.mo_layers, pl.stage.slot[slot].host, n_bytes, hipMemcpyHostToDevice, us));
+        mp.states = reinterpret_cast<const RzMotionState *>(pl.mo_layers.p);
+        lp.layers = pl.mo_layers + c->I;
     } else {
-        HIP_TRY(hipMemcpyAsync(c->mo_states, c->stage[slot], (size_t)c->I * sizeof(RzMotionState), hipMemcpyHostToDevice, us));
-        mp.states = c->mo_states;
+        HIP_TRY(hipMemcpyAsync(pl.mo_states, pl.stage.slot[slot].host, (size_t)c->I * sizeof(RzMotionState), hipMemcpyHostToDevice, us));
+        mp.states = pl.mo_states;
     }
     mp.bone_rec = c->mo_bone_rec; mp.feed_off = c->mo_feed_off;
     mp.sample.key_frame = c->mo_key_frame; mp.sample.key_rot = c->mo_key_rot; mp.sample.key_pos = c->mo_key_pos; mp.sample.key_interp = c->mo_key_interp;
@@ -750,17 +705,10 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
     } else {
         HIP_TRY(rz_launch_motion_blend(mp, c->I, us));
     }
-    c->last_upload_pulled = false; c->last_upload_rows = false;
-    if (slot >= 0) {
-        // one event says both "the ring slot may be written again" and "the pose has landed" (copy_send)
-        HIP_TRY(hipEventRecord(c->stage_ev[slot], us));
-        c->stage_used[slot] = true;
-        if (piped) HIP_TRY(hipStreamWaitEvent(c->stream, c->stage_ev[slot], 0));
-    }
-    memset(&c->ml, 0, sizeof c->ml);
-    if (c->M > 0) c->ml.count = -1;          // the weights only exist on the device: the prep kernel compacts them
-    c->pose_I = c->I;
-    c->pose_set = true;
+    pl.last_pulled = false; pl.last_rows = false;
+    if (slot >= 0)
+        if (int r = staged_sent(c, slot, us, piped)) return r;
+    pose_in_place(c, nullptr, true);
     return RZ_OK;
 }
 
@@ -787,8 +735,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
         const uint32_t i = instance ? instance[k] : 0;
         if (i >= c->I || bone[k] >= c->B) return fail(RZ_ERR_INVALID, "override %u names instance %u bone %u (have %u x %u)", k, i, bone[k], c->I, c->B);
         for (int e = 0; e < 16; ++e) {
-            const float x = world16[(size_t)k * 16 + e];
-            if (!(x == x) || x - x != 0.0f) return fail(RZ_ERR_INVALID, "override %u is not finite", k);
+            if (!finite_f(world16[(size_t)k * 16 + e])) return fail(RZ_ERR_INVALID, "override %u is not finite", k);
         }
         order[k] = k;
     }
@@ -829,7 +776,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
     const size_t b_pad = (b_off + b_bone + b_mat + 7) & ~(size_t)7, b_foff = fol_off.size() * sizeof(int), b_fent = fol_ent.size() * sizeof(uint2);
     int slot = 0;
     if (int r = stage_acquire(c, std::max<size_t>(b_pad + b_foff + b_fent, 4096), &slot)) return r;
-    char *st = static_cast<char *>(c->stage[slot]);
+    char *st = static_cast<char *>(c->pl.stage.slot[slot].host);
     memcpy(st, off.data(), b_off);
     memcpy(st + b_off, bones.data(), b_bone);
     memcpy(st + b_off + b_bone, mats.data(), b_mat);
@@ -845,8 +792,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
             HIP_TRY(hipMemcpyAsync(c->fol_ent, st + b_pad, b_fent, hipMemcpyHostToDevice, us));
         }
     }
-    HIP_TRY(hipEventRecord(c->stage_ev[slot], us));
-    c->stage_used[slot] = true;
+    if (int r = staged_sent(c, slot, us, false)) return r;
     c->ovr_count = (uint32_t)m;
     if (c->ovr_follow) c->fol_count = (uint32_t)fol_ent.size();
     c->ovr_off_host = std::move(off); c->ovr_bone_host = std::move(bones);
@@ -886,8 +832,9 @@ int rz_read_world(rz_ctx *c, uint32_t instance, float *world16)
 {
     if (int r = use(c)) return r;
     if (instance >= c->I || !world16 || !c->world) return fail(RZ_ERR_INVALID, "bad world read");
-    if (c->zc_cur >= 0 && !c->zc_local && !c->world_resident) {     // a zero-copy pose no frame has consumed yet: still in its pinned slot
-        memcpy(world16, c->zc_host[c->zc_cur], (size_t)c->B * 16 * sizeof(float));
+    const RzPoseLink::Current &p = c->pl.cur;
+    if (p.zc_slot >= 0 && !p.zc_local && !p.world_resident) {     // a zero-copy pose no frame has consumed yet: still in its pinned slot
+        memcpy(world16, c->pl.zc.slot[p.zc_slot].host, (size_t)c->B * 16 * sizeof(float));
         return RZ_OK;
     }
     if (solve_on_demand(c)) {                           // a crowd frame that solved its hierarchy in LDS only: the solve as a kernel of its own, now

@@ -272,7 +272,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;
     else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;
     else if (!strcmp(key, "effective_geo")) *value = make_plan(c).v.geo ? 1 : 0;
-    else if (!strcmp(key, "effective_prep")) { const Plan pl = make_plan(c); *value = ((pl.prep || c->pose_local) && !pl.fuse_fk && !pl.subfk) ? 1 : 0; }
+    else if (!strcmp(key, "effective_prep")) { const Plan pl = make_plan(c); *value = ((pl.prep || c->pl.cur.local) && !pl.fuse_fk && !pl.subfk) ? 1 : 0; }
     else if (!strcmp(key, "effective_split")) *value = make_plan(c).v.S;
     else if (!strcmp(key, "effective_unroll")) *value = make_plan(c).v.U;
     else if (!strcmp(key, "effective_fast")) *value = make_plan(c).v.fast ? 1 : 0;
@@ -286,12 +286,12 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
         *value = (!shapes || dp.edge || dp.aabb) ? 0 : ((!pl.v.fast && dp.fk_on && (dp.fk_kind == 1 || dp.fk_kind == 2)) ? dp.fk_kind : 3);
     }
     else if (!strcmp(key, "effective_fk_kind")) { Plan pl; if (int r = frame_plan(c, &pl)) return r; *value = deform_params(c, pl).fk_kind; }
-    else if (!strcmp(key, "pose_pulled")) *value = c->last_upload_pulled ? 1 : 0;      // the most recent copied pose came down by rz_pull_pose_kernel ...
-    else if (!strcmp(key, "pose_rows")) *value = c->last_upload_rows ? 1 : 0;          // ... its world matrices as three rows per bone
+    else if (!strcmp(key, "pose_pulled")) *value = c->pl.last_pulled ? 1 : 0;      // the most recent copied pose came down by rz_pull_pose_kernel ...
+    else if (!strcmp(key, "pose_rows")) *value = c->pl.last_rows ? 1 : 0;          // ... its world matrices as three rows per bone
     else if (!strcmp(key, "effective_fuse_fk")) { const Plan pl = make_plan(c); *value = (pl.fuse_fk || pl.subfk) ? 1 : 0; }
     else if (!strcmp(key, "effective_closure_bones")) *value = make_plan(c).subfk ? (int)c->subfk_stride : 0;
     else if (!strcmp(key, "effective_closure_rounds")) *value = make_plan(c).subfk ? (int)c->subfk_rounds : 0;      // radix-4 doubling rounds of that front (0 .. 3)
-    else if (!strcmp(key, "pose_resident")) *value = (c->zc_cur < 0 || (c->world_resident && c->mw_resident && c->local_resident)) ? 1 : 0;
+    else if (!strcmp(key, "pose_resident")) *value = c->pl.cur.resident() ? 1 : 0;
     else if (!strcmp(key, "effective_overlap")) *value = want_overlap(c, make_plan(c)) ? 1 : 0;
     else if (!strcmp(key, "effective_inst_block")) *value = make_plan(c).inst_block;
     else if (!strcmp(key, "effective_out_cap")) *value = (int)make_plan(c).out_cap;
@@ -302,12 +302,12 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "pose_staged")) {
         // did the helper of an earlier frame stage the CURRENT pose in device memory? (synchronises; for tests and tools)
         *value = 0;
-        if (c->zc_tag && c->zc_seq_cur) {
+        if (c->pl.tag && c->pl.cur.seq) {
             uint64_t tags[2] = {0, 0};
             HIP_TRY(hipSetDevice(c->device));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipMemcpy(tags, c->zc_tag, sizeof tags, hipMemcpyDeviceToHost));
-            *value = tags[c->pose_slot] == c->zc_seq_cur ? 1 : 0;
+            HIP_TRY(hipMemcpy(tags, c->pl.tag, sizeof tags, hipMemcpyDeviceToHost));
+            *value = tags[c->pl.pose_slot] == c->pl.cur.seq ? 1 : 0;
         }
     }
     else if (!strncmp(key, "addr_", 5)) {

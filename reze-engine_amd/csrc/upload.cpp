@@ -156,10 +156,10 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     HIP_TRY(hipMalloc(&c->inv_bind, (size_t)B * 16 * sizeof(float)));
     HIP_TRY(hipMemcpy(c->inv_bind, inverse_bind16, (size_t)B * 16 * sizeof(float), hipMemcpyHostToDevice));
     c->B = B;
-    c->zc_epoch++; c->zc_seq_cur = 0;   // a pose staged for the old skeleton must never match
+    retire_pose_tags(c);                // a pose staged for the old skeleton must never match
     c->sub_valid = false;               // joints are clamped to the bone count when the run lists are built
     c->palette_stale = false;
-    c->pose_set = false;
+    c->pl.cur.set = false;
     c->has_topology = false;            // belongs to the previous skeleton ...
     dfree(c->fk_rec); dfree(c->fk_anc_more);        // ... and so do its records (sized for the old bone count: nothing may read them for the new one)
     c->fk_host.clear(); c->fk_rounds = 0; c->fk_gen++;
@@ -268,11 +268,11 @@ int rz_set_instances(rz_ctx *c, uint32_t I)
         c->ph.reset = true;               // (a physics table rebuilds its per-instance state and the overrides at its next step)
         // The host-compacted active-morph list is only maintained while I == 1 (upload_pose). Coming back to one instance
         // from a crowd it is stale (zeroed): let the prep kernel compact instance 0's weights, which are still on the device.
-        if (c->M > 0 && c->morph_mode == 1) c->ml.count = -1;
+        if (c->M > 0 && c->morph_mode == 1) c->pl.cur.ml.count = -1;
         // A crowd larger than the one the resident pose was uploaded for has no pose for its new members (and a
         // single-character pose may still sit in its pinned slot, which holds exactly one instance): ask for a new one.
-        if (I > c->pose_I) c->pose_set = false;
-        c->zc_epoch++; c->zc_seq_cur = 0;
+        if (I > c->pl.cur.I) c->pl.cur.set = false;
+        retire_pose_tags(c);
     }
     c->I = I;
     if (int r = ensure_pose_buffers(c)) return r;
