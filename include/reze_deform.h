@@ -175,6 +175,43 @@ int rz_upload_qdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx);
 int rz_upload_ik(rz_ctx *ctx, uint32_t n_chains, const uint32_t *goal, const uint32_t *effector, const uint32_t *loops, const float *limit_angle,
                  const uint32_t *link_off, const uint32_t *link_bone, const uint8_t *link_limited, const float *link_min3, const float *link_max3);
 
+/* Chain switches of the IK stage — the VMD show / IK keys, which turn single chains off and on over a motion (a motion traced from motion
+ * capture keys the legs by FK and switches leg and toe IK off at frame 0). An addition: the version stays 8, a binding detects it by these
+ * symbols. Opt-in: without a call below every frame launches what it launched before. tests/ik_switch_ref.py is the definition:
+ *   state_at(keys, frame)   the row of the LAST key with key_frame <= frame, compared as floats (among keys on one frame the last wins);
+ *                           before the first key the first key's row; no keys: every chain on. A pure comparison: matched exactly.
+ *   choose(state)           clip A's row at frame_a when clip_b == RZ_NO_CLIP or blend < 0.5, else clip B's row at frame_b; a chosen clip
+ *                           without keys is all on. A switch does not cross-fade, and layers never switch IK.
+ *   solve                   the IK stage over the chains whose switch is on, in the same order; a chain that is off does nothing: its links
+ *                           keep the sampled or uploaded rotations, as a chain with loops == 0 does.
+ * The context holds one mask, [I][n_chains] in rz_upload_ik's chain order, all on at first. The last writer wins:
+ *   rz_set_ik_enabled                              writes it (non-zero = on; NULL = all on)
+ *   rz_set_pose_sampled                            while keys for RZ_NO_CLIP are resident: mask[i] = state_at(keys, frames[i])
+ *   rz_set_pose_blended / rz_set_pose_layered      while any clip of the library holds keys: mask[i] = choose(states[i])
+ *   rz_set_pose_local, rz_set_pose, and a sampling call without keys for its source, leave it alone.
+ * The switches are evaluated on the host, which is handed every frame and state anyway; only bits travel — one character's in the kernel
+ * arguments, a crowd's in one small copy, and only when they differ from the bits the device holds. While at least one bit is off
+ * (rz_get_tuning("ik_switched") = their number) the solve runs as rz_fk_ik_sw_kernel, whose waves skip the chains that are off, whose
+ * workgroup skips the whole-skeleton re-solve of a stage with no chain on, and the stage loop of an instance with none; a mask of all
+ * ones launches rz_fk_ik_kernel as ever. rz_physics_step's first solve uses the same mask.
+ * Keys (rz_get_tuning("ik_key_sets") = resident sets): key_enabled is [n_keys][n_chains] in rz_upload_ik's order, a chain a VMD key does
+ * not name already filled in by the caller (tests/ik_switch_ref.py: flatten). clip = RZ_NO_CLIP: the motion of rz_upload_animation; else a
+ * clip of the library. keys == NULL removes the set; a set of 0 keys is resident and says "all on". Static data: refused while forks exist,
+ * and forks see them. The mask is pose state: a fork owns its own. rz_upload_ik (a new table or none) resets the mask and drops every key
+ * set; rz_upload_animation drops the RZ_NO_CLIP keys, rz_upload_motions the library's; a new skeleton or topology drops everything.
+ * rz_set_instances: shrinking keeps the mask, members that appear are all on. rz_read_ik_enabled: what the next frame's solve uses (the
+ * host's mirror: no synchronisation). Refused with RZ_ERR_INVALID, nothing resident changed: no IK table; a clip index >= the library's
+ * count; a key frame that is not finite; descending key frames; null arrays with n_keys > 0.
+ * Not covered: the keys' `show` flag; switches inside the one-launch forms (with a table they are not taken); a cross-faded switch. */
+typedef struct rz_ik_keys {
+    uint32_t n_keys;
+    const float *key_frame;             /* [n_keys] non-descending */
+    const uint8_t *key_enabled;         /* [n_keys][n_chains] */
+} rz_ik_keys;
+int rz_set_ik_enabled(rz_ctx *ctx, const uint8_t *enabled);
+int rz_upload_ik_keys(rz_ctx *ctx, uint32_t clip, const rz_ik_keys *keys);
+int rz_read_ik_enabled(rz_ctx *ctx, uint8_t *out);
+
 /* Instancing — NEW (the reference draws one model): I poses of the same static mesh. Shrinking the crowd keeps the
  * resident pose (instances 0 .. I-1 of it); growing it beyond the count the pose was set for needs a new rz_set_pose*. */
 int rz_set_instances(rz_ctx *ctx, uint32_t I);

@@ -23,15 +23,16 @@ SYMBOLS = [
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
-    "rz_override_follow",
+    "rz_override_follow", "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
-# points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks, rz_set_pose_layered and rz_override_follow — detected by the
-# symbol, the version stayed 8)
+# points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks, rz_set_pose_layered, rz_override_follow and the three chain-switch entry
+# points (rz_set_ik_enabled ..) — detected by the symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
                     "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
-                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs", "rz_override_follow"}
+                    "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs", "rz_override_follow",
+                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
 NO_MASK = 0xffffffff
@@ -57,6 +58,10 @@ class RzMotionState(ctypes.Structure):
 class RzMotionLayer(ctypes.Structure):
     _fields_ = [("clip", ctypes.c_uint32), ("frame", ctypes.c_float), ("weight", ctypes.c_float), ("mask", ctypes.c_uint32),
                 ("mode", ctypes.c_uint32)]
+
+
+class RzIkKeys(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_uint32), ("key_frame", ctypes.POINTER(ctypes.c_float)), ("key_enabled", ctypes.POINTER(ctypes.c_uint8))]
 
 
 class RzPhysics(ctypes.Structure):
@@ -230,6 +235,10 @@ def load(path=None):
         L.rz_physics_springs.argtypes = [vp, u32]
     if hasattr(L, "rz_override_follow"):
         L.rz_override_follow.argtypes = [vp, u32]
+    if hasattr(L, "rz_upload_ik_keys"):
+        L.rz_set_ik_enabled.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
+        L.rz_upload_ik_keys.argtypes = [vp, u32, ctypes.POINTER(RzIkKeys)]
+        L.rz_read_ik_enabled.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
     for name in SYMBOLS:
         # (libraries older than the current ABI — tools/ab_inproc.py loads them side by side — lack the newer symbols: OPTIONAL_SYMBOLS)
         if name != "rz_last_error" and (name not in OPTIONAL_SYMBOLS or hasattr(L, name)):
@@ -702,6 +711,47 @@ class DeformContext:
         self._chk(self._L.rz_upload_ik(self._h, len(chains), goal.ctypes.data_as(u32p), eff.ctypes.data_as(u32p), loops.ctypes.data_as(u32p),
                                        _fptr(theta), off.ctypes.data_as(u32p), bone_a.ctypes.data_as(u32p), lim_a.ctypes.data_as(u8p),
                                        _fptr(lo_a), _fptr(hi_a)))
+
+    def _ik_chains(self):
+        if not hasattr(self._L, "rz_upload_ik_keys"):
+            raise RzError(-6, "this build of the library has no rz_upload_ik_keys")
+        return self.get_tuning("ik_chains")
+
+    def upload_ik_keys(self, keys, clip=None):
+        """VMD IK on / off keys of a motion: `keys` = (key_frame [n], key_enabled [n][n_chains]) in upload_ik's chain order, frames
+        non-descending (tests/ik_switch_ref.py: flatten makes them from a loader's ikFrames), or None to remove the set. clip = None: the
+        motion of upload_animation; else a clip of the library. While a set is resident the sampling pose calls write the chain switches."""
+        n_chains = self._ik_chains()
+        c = NO_CLIP if clip is None else int(clip)
+        if keys is None:
+            self._chk(self._L.rz_upload_ik_keys(self._h, c, None))
+            return
+        kf = np.ascontiguousarray(keys[0], dtype=np.float32).reshape(-1)
+        en = np.ascontiguousarray(np.asarray(keys[1]) != 0, dtype=np.uint8).reshape(-1)
+        assert en.size == kf.size * n_chains, "%d switch bytes for %d keys of %d chains" % (en.size, kf.size, n_chains)
+        k = RzIkKeys(kf.size, _fptr(kf) if kf.size else None, en.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if en.size else None)
+        self._chk(self._L.rz_upload_ik_keys(self._h, c, ctypes.byref(k)))
+
+    def set_ik_enabled(self, mask=None):
+        """The chain switches of the IK stage, [I][n_chains] in upload_ik's order (non-zero = on; one row is given to every instance), or
+        None = all on. The last writer wins: a sampling pose call with keys resident for its source writes them too."""
+        n_chains = self._ik_chains()
+        if mask is None:
+            self._chk(self._L.rz_set_ik_enabled(self._h, None))
+            return
+        m = np.asarray(mask) != 0
+        if m.size == n_chains and self.I > 1:
+            m = np.broadcast_to(m.reshape(1, n_chains), (self.I, n_chains))
+        m = np.ascontiguousarray(m, dtype=np.uint8).reshape(-1)
+        assert m.size == self.I * n_chains, "%d switches for %d instances of %d chains" % (m.size, self.I, n_chains)
+        self._chk(self._L.rz_set_ik_enabled(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+
+    def read_ik_enabled(self):
+        """[I][n_chains] uint8: the chain switches the next frame's solve uses (the host's mirror; nothing is synchronised)."""
+        n_chains = self._ik_chains()
+        out = np.empty((self.I, max(n_chains, 1)), dtype=np.uint8)
+        self._chk(self._L.rz_read_ik_enabled(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out[:, :n_chains]
 
     def upload_physics(self, table):
         """Rigid-body physics for device-solved poses: `table` = dict(n_bodies, bone, type, shape, size [n,3], offset_pos [n,3], offset_rot

@@ -183,6 +183,7 @@ void free_animation(rz_ctx *c)
     dfree(c->an_key_frame); dfree(c->an_key_pos); dfree(c->an_mkey_frame); dfree(c->an_mkey_weight); dfree(c->an_feed_ratio);
     dfree(c->an_key_rot); dfree(c->an_key_interp);
     c->has_animation = false;
+    c->ik_keys_an = {};                 // rz_upload_ik_keys(RZ_NO_CLIP): the keys of this motion
     if (c->pl.cur.sampled) { c->pl.cur.sampled = false; c->pl.cur.set = false; }
 }
 
@@ -195,6 +196,7 @@ void free_motions(rz_ctx *c)
     dfree(c->mo_bone_rec); dfree(c->mo_feed_off); dfree(c->mo_feed_range); dfree(c->mo_key_interp);
     dfree(c->mo_key_frame); dfree(c->mo_key_pos); dfree(c->mo_mkey_frame); dfree(c->mo_mkey_weight); dfree(c->mo_feed_ratio); dfree(c->mo_key_rot);
     c->mo_clips = 0; c->mo_M = 0;
+    c->ik_keys_mo.clear();              // rz_upload_ik_keys(clip): the keys of this library's clips
 }
 
 void free_motion_masks(rz_ctx *c)
@@ -241,6 +243,10 @@ void free_qdef(rz_ctx *c)
 
 void free_ik(rz_ctx *c)
 {
+    // chain switches name chains of this table: the mask is all on again and every key set goes (a fork holds no table of its own — its
+    // RzStatic is emptied before this runs — and its mask goes with its context)
+    c->ik_dev_pos.clear(); c->ik_keys_an = {}; c->ik_keys_mo.clear();
+    c->iksw.words.clear(); c->iksw.off = 0;
     if (!c->ik_n) return;
     drop_graph(c);
     dfree(c->ik_chain); dfree(c->ik_path); dfree(c->ik_stage_off); dfree(c->ik_link);
@@ -362,6 +368,7 @@ int rz_destroy(rz_ctx *c)
     c->pl = {};                           // the pose transport: blocks, rings, events
     dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
     dfree(c->fol_off); dfree(c->fol_ent);
+    c->iksw = {};
     free_physics(c);
     for (int k = 0; k < 2; ++k) {
         dfree(c->palette_ring[k]); dfree(c->act_idx_ring[k]); dfree(c->act_w_ring[k]); dfree(c->act_count_ring[k]);

@@ -132,6 +132,14 @@ int rccl_bind();
 }  // namespace rzi
 using rzi::kStageSlots;
 
+// One set of VMD IK on/off keys (rz_upload_ik_keys): the frames, non-descending, and per key one bit per chain in the DEVICE's chain order
+// (RzIkSwitchParams), [n][words]. Host data only: the step function is evaluated where the frames and states are handed over (pose.cpp).
+struct RzIkKeySet {
+    std::vector<float> frame;
+    std::vector<uint32_t> bits;
+    bool resident = false;              // (a set of no keys is resident too: it says "all on")
+};
+
 // Everything rz_upload_* writes and a frame only reads. A new static table goes here and nowhere else: rz_fork copies the struct as a whole and
 // rz_destroy resets a fork's copy as a whole before anything is freed, so a fork neither misses a table nor frees one.
 struct RzStatic {
@@ -189,6 +197,12 @@ struct RzStatic {
     uint32_t *ik_path = nullptr, *ik_stage_off = nullptr;
     float4 *ik_link = nullptr;
     uint32_t ik_n = 0, ik_stages = 0;
+    // chain switches (rz_set_ik_enabled / rz_upload_ik_keys): where chain k of rz_upload_ik's order sits in the device's order, rebuilt
+    // with every table, and the key sets — of the single motion, and one per clip of the library (empty: no clip holds keys). They go
+    // with the table (free_ik), the motion (free_animation) and the library (free_motions). The MASK is pose state: rz_ctx::iksw.
+    std::vector<uint32_t> ik_dev_pos;
+    RzIkKeySet ik_keys_an;
+    std::vector<RzIkKeySet> ik_keys_mo;
     // morphs
     int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
     uint32_t M = 0, Mpad = 12;
@@ -363,6 +377,17 @@ struct rz_ctx : RzStatic, RzTuning {
     size_t fol_alloc = 0, fol_off_alloc = 0;
     std::vector<int> ovr_off_host, ovr_bone_host;       // the hand-fed override set as uploaded (rz_override_world), for a later flip of the flag
 
+    // The per-instance chain switches the next solve uses: [I][words] in the device's chain order, set = on, padding bits clear; EMPTY =
+    // every chain of every instance is on (the only form `off` == 0 takes), and then rz_fk_ik_kernel is launched as ever. One character's
+    // words ride in the kernel arguments; a crowd's are copied into `dev` when they CHANGE (a switch flips a few times per motion, so a
+    // frame whose bits did not change sends nothing). A fork's own, all on from the start.
+    struct IkSwitch {
+        std::vector<uint32_t> words;
+        uint32_t off = 0;               // (instance, chain) bits clear
+        rzi::Scratch<uint32_t> dev;
+        size_t dev_alloc = 0;
+    } iksw;
+
     RzPhysics ph;                       // rigid-body physics; with a table the override table above is physics' own ([I][ph.nd] slots, fixed addresses)
 
     // per-frame state
@@ -507,6 +532,8 @@ RzFollowParams follow_params(const rz_ctx *c);
 void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent);
 int reserve_followers(rz_ctx *c, size_t entries, size_t offsets);       // grows fol_off / fol_ent (drains and drops the graph when it must)
 int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones);       // build + blocking upload; the caller has drained
+// chain switches: null mask and words 0 unless at least one bit is clear (then launch_fk takes the rz_fk_ik_sw*_kernel entries)
+RzIkSwitchParams ik_switch_params(const rz_ctx *c);
 uint64_t algorithmic_bytes(const rz_ctx *c);
 
 // ---- pose.cpp ----
@@ -516,6 +543,15 @@ const float4 *src_local_q(const rz_ctx *c);
 int make_resident(rz_ctx *c);
 uint64_t zc_seq(const rz_ctx *c, uint64_t upload_index_1, int kind);
 void retire_pose_tags(rz_ctx *c);     // nothing a helper workgroup staged and tagged so far, or a slot header published so far, may match a later pose
+// The chain switches become `words` ([I][ceil(ik_n / 32)], device order, padding bits clear; empty = all on) in two halves, so that a caller
+// can do everything that may fail before it changes anything else: plan (allocates, waits for a staging slot, fills it; `I` = the instance
+// count the words are for), then commit (enqueues a crowd's changed bits and takes the words into the mirror; if the enqueue fails the
+// mask is all on, which reads no device array). set_ik_words is both at once.
+struct IkWordsPlan { std::vector<uint32_t> w; uint32_t off = 0; int slot = -1; bool change = false, inline_words = false; };
+int plan_ik_words(rz_ctx *c, uint32_t I, std::vector<uint32_t> &&words, IkWordsPlan *pl);
+int commit_ik_words(rz_ctx *c, IkWordsPlan &pl);
+int set_ik_words(rz_ctx *c, std::vector<uint32_t> &&words);
+int plan_ik_resize(rz_ctx *c, uint32_t I, IkWordsPlan *pl);      // rz_set_instances, before the count changes: shrinking keeps the mask, members that appear are all on
 
 // ---- frame.cpp ----
 int check_ready(rz_ctx *c);

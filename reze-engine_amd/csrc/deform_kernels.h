@@ -105,6 +105,18 @@ struct RzFollowParams {
     const uint2 *ent;           // [n] (follower bone, index into ovr_bone / ovr_world)
 };
 
+// Per-instance switches of the IK chains (rz_set_ik_enabled / rz_upload_ik_keys; kernels/ik.hip.h: SW; defined by tests/ik_switch_ref.py):
+// one bit per chain in the DEVICE's chain order (RzIkParams::chain: sorted by stage, so a stage is a contiguous bit range), bit c of word
+// c / 32, set = the chain is solved. The host evaluates the switches (it knows every frame and state it hands over) and only the bits
+// travel: one character's few words in the kernel arguments, a crowd's in a device array. A block of its own like RzFollowParams, handed to
+// the rz_fk_ik_sw*_kernel entries only, which are launched only while at least one bit is clear: RzFkParams and RzIkParams do not change.
+constexpr int kRzIkSwInline = 4;
+struct RzIkSwitchParams {
+    const uint32_t *mask;       // [I][words], or nullptr: one instance, its words are w0 below
+    uint32_t w0[kRzIkSwInline];
+    int words;                  // words per instance = ceil(n_chains / 32)
+};
+
 // rz_deform_kernel: fused morph + 4-bone LBS (engine/src/engine.ts:253-272).
 struct RzDeformParams {
     const float *geom;          // 6 planes of Vp floats: x y z nx ny nz
@@ -365,6 +377,8 @@ hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t i
 size_t rz_fk_ik_lds_bytes(const RzFkParams &p);
 // the same two solves with the follow stage (rz_fk_follow_kernel / rz_fk_ik_follow_kernel; `ik` null = no IK table): same LDS as their twins
 hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const RzFollowParams &fo, uint32_t instances, hipStream_t st);
+// the IK solve with per-instance chain switches (rz_fk_ik_sw_kernel / rz_fk_ik_sw_follow_kernel; `fo` null = no follower entries): same LDS as rz_fk_ik_kernel
+hipError_t rz_launch_fk_ik_sw(const RzFkParams &p, const RzIkParams &ik, const RzIkSwitchParams &sw, const RzFollowParams *fo, uint32_t instances, hipStream_t st);
 hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
                             uint32_t instances, hipStream_t st);
 size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v);

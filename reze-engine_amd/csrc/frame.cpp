@@ -22,7 +22,9 @@ int launch_fk(rz_ctx *c, hipStream_t st)
         if (lds > 160 * 1024)
             return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve with IK on the device: %u bones need %zu B of LDS (156 B per bone + the pose's morph weights: the IK stage keeps the local pose alive beside both matrix buffers; the limit is 160 KB)", c->B, lds);
         const RzIkParams ik = ik_params(c);
-        if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, &ik, fo, c->I, st));
+        const RzIkSwitchParams sw = ik_switch_params(c);     // at least one chain of one instance is switched off: the entries that look
+        if (sw.words) HIP_TRY(rz_launch_fk_ik_sw(fp, ik, sw, fo.off ? &fo : nullptr, c->I, st));
+        else if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, &ik, fo, c->I, st));
         else HIP_TRY(rz_launch_fk_ik(fp, ik, c->I, st));
         c->palette_stale = false; c->fk_stale = false;
         return RZ_OK;
@@ -265,6 +267,7 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     h = fnv(h, &qd, sizeof qd);
     if (c->ik_n) { const RzIkParams ik = ik_params(c); h = fnv(h, &ik, sizeof ik); }
     if (c->ovr_follow) { const RzFollowParams fo = follow_params(c); h = fnv(h, &fo, sizeof fo); }
+    if (c->ik_n) { const RzIkSwitchParams sw = ik_switch_params(c); h = fnv(h, &sw, sizeof sw); }
     const uint64_t misc[6] = { c->I, c->pl.cur.local, c->pl.cur.local_t, c->pl.cur.sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }

@@ -421,11 +421,15 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // the override write replaces the S_a it read. Entries ascend by bone inside an
 // instance: consecutive lanes read rows 48 B apart, which a 16-lane group of a 16-byte LDS read spreads over all sixteen 16-byte slots of
 // a bank row (3 l mod 16 is a permutation), and lanes of one strand read the same S_a, which is a broadcast.
-template <bool FUSED, int KIND = 0, bool IK = false, bool FOLLOW = false>
+// SW (rz_fk_ik_sw_kernel / rz_fk_ik_sw_follow_kernel only; rz_set_ik_enabled / rz_upload_ik_keys): the IK stage honours the instance's chain
+// switches (kernels/ik.hip.h: ik_stage<SW>).
+template <bool FUSED, int KIND = 0, bool IK = false, bool FOLLOW = false, bool SW = false>
 __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &early, const int inst, float4 *wl, unsigned char *scr, float *lds_mw,
                                          const bool to_global, const uint64_t st_tagv = 0ull, unsigned long long *fs = nullptr,
-                                         const RzIkParams *ik = nullptr, float4 *ik_m2 = nullptr, const RzFollowParams *fol = nullptr)
+                                         const RzIkParams *ik = nullptr, float4 *ik_m2 = nullptr, const RzFollowParams *fol = nullptr,
+                                         const RzIkSwitchParams *iksw = nullptr)
 {
+    static_assert(!SW || IK, "chain switches belong to the IK stage");
     static_assert(!IK || (!FUSED && KIND == 0), "the IK stage belongs to the generic solve of rz_fk_ik_kernel");
     static_assert(!FOLLOW || (!FUSED && KIND == 0), "the follow stage belongs to the generic solve of the rz_fk_*follow_kernel entries");
     constexpr bool PLAIN = KIND != 0;
@@ -626,7 +630,8 @@ __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &ear
     }
     RZ_FSTAMP(3);             // doubling rounds done
     if constexpr (IK) {
-        src = ik_stage(p, *ik, src, wl, m2, sq, s_rec, s_bind, s_lt, has_t, tid);
+        if constexpr (SW) src = ik_stage<true>(p, *ik, src, wl, m2, sq, s_rec, s_bind, s_lt, has_t, tid, iksw, inst);
+        else src = ik_stage(p, *ik, src, wl, m2, sq, s_rec, s_bind, s_lt, has_t, tid);
 #pragma unroll
         for (int k = 0; k < NBR; ++k) {         // the registers of the output pass: the solved rows
             const int b = tid + k * kBlock;

@@ -84,6 +84,30 @@ __global__ void __launch_bounds__(kBlock) rz_fk_ik_follow_kernel(const uint4 *k_
                                    reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), &fo);
 }
 
+// The two IK solves with per-instance chain switches (kernels/ik.hip.h: SW; rz_set_ik_enabled / rz_upload_ik_keys), launched instead of
+// them only while at least one (instance, chain) bit is clear. Same LDS as their twins.
+__global__ void __launch_bounds__(kBlock) rz_fk_ik_sw_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik,
+                                                             const RzIkSwitchParams sw)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
+    unsigned char *scr = smem + (size_t)p.B * 48;
+    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
+    fk_solve<false, 0, true, false, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
+                                          reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), nullptr, &sw);
+}
+
+__global__ void __launch_bounds__(kBlock) rz_fk_ik_sw_follow_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik,
+                                                                    const RzFollowParams fo, const RzIkSwitchParams sw)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
+    unsigned char *scr = smem + (size_t)p.B * 48;
+    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
+    fk_solve<false, 0, true, true, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
+                                         reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), &fo, &sw);
+}
+
 // ------------------------------------------------------------------------------------------------
 // rz_pull_pose_kernel: a crowd's per-frame pose (0.8 - 3.3 MB for 256 characters) comes down by a PULL. The host lays the pose out in
 // a pinned, device-mapped ring slot; 16 workgroups read it over the host link with 16-byte loads (1 KiB contiguous per wave
@@ -242,6 +266,22 @@ hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const 
     return hipGetLastError();
 }
 
+hipError_t rz_launch_fk_ik_sw(const RzFkParams &p, const RzIkParams &ik, const RzIkSwitchParams &sw, const RzFollowParams *fo, uint32_t instances, hipStream_t st)
+{
+    const size_t lds = rz_fk_ik_lds_bytes(p);
+    // (the host checks the LDS first and says why: launch_fk in frame.cpp; words in the arguments serve one instance only)
+    if (lds > 160 * 1024 || !ik.chain || ik.n_stages <= 0 || sw.words != (ik.n_chains + 31) / 32) return hipErrorInvalidValue;
+    if (!sw.mask && (instances != 1 || sw.words > kRzIkSwInline)) return hipErrorInvalidValue;
+    if (fo && (!fo->off || !fo->ent || !p.ovr_off)) return hipErrorInvalidValue;
+    const void *fn = fo ? reinterpret_cast<const void *>(rz_fk_ik_sw_follow_kernel) : reinterpret_cast<const void *>(rz_fk_ik_sw_kernel);
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    if (fo) hipLaunchKernelGGL(rz_fk_ik_sw_follow_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, ik, *fo, sw);
+    else hipLaunchKernelGGL(rz_fk_ik_sw_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, ik, sw);
+    return hipGetLastError();
+}
 
 // `src` = device address of the pinned slot: [bones x 48 B of packed matrix columns | raw_bytes carried as they are]; `dst` = the
 // device pose block, where the matrices arrive as 4 x 4 and the rest behind them. raw_bytes is a multiple of 4.

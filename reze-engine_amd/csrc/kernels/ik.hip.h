@@ -147,16 +147,54 @@ __device__ __forceinline__ float4 *ik_resolve(const RzFkParams &p, float4 *wl, f
     return src;
 }
 
+// Word `i` of an instance's chain switches (RzIkSwitchParams): wave-uniform, so a scalar load or a select between kernel arguments
+__device__ __forceinline__ uint32_t ik_sw_word(const RzIkSwitchParams &sw, const int inst, const uint32_t i)
+{
+    if (sw.mask) return sw.mask[(size_t)inst * (size_t)sw.words + i];
+    return i == 0u ? sw.w0[0] : i == 1u ? sw.w0[1] : i == 2u ? sw.w0[2] : sw.w0[3];
+}
+
+// is any chain of [c0, c1) switched on?
+__device__ __forceinline__ bool ik_sw_any(const RzIkSwitchParams &sw, const int inst, const uint32_t c0, const uint32_t c1)
+{
+    if (c0 >= c1) return false;
+    const uint32_t wa = c0 >> 5, wb = (c1 - 1u) >> 5;
+    for (uint32_t i = wa; i <= wb; ++i) {
+        uint32_t m = ik_sw_word(sw, inst, i);
+        if (i == wa) m &= 0xffffffffu << (c0 & 31u);
+        if (i == wb) m &= 0xffffffffu >> (31u - ((c1 - 1u) & 31u));
+        if (m) return true;
+    }
+    return false;
+}
+
 // The IK stage of one pose (its workgroup): `src` holds the world rows of the plain solve; returns the buffer with the solved ones.
+// SW (the rz_fk_ik_sw*_kernel entries; tests/ik_switch_ref.py): the instance's chain switches. A wave skips a chain whose bit is clear (its
+// links keep the staged rotations, as a chain with no loops does); a stage none of whose chains is on changes no rotation, so its
+// whole-skeleton solve is skipped as well and `src` stays what the last live stage left; an instance with every bit clear does not enter
+// the loop. The bits are read through wave-uniform addresses and the two stage-level decisions depend on the instance alone: every
+// barrier is reached by the whole workgroup or by none of it.
+template <bool SW = false>
 __device__ __forceinline__ float4 *ik_stage(const RzFkParams &p, const RzIkParams &ik, float4 *src, float4 *wl, float4 *m2, float4 *sq, const uint4 *s_rec,
-                                            const float4 *s_bind, const float *s_lt, const bool has_t, const int tid)
+                                            const float4 *s_bind, const float *s_lt, const bool has_t, const int tid, const RzIkSwitchParams *sw = nullptr,
+                                            const int inst = 0)
 {
     const int lane = tid & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+    if constexpr (SW) {
+        if (!ik_sw_any(*sw, inst, 0u, (uint32_t)ik.n_chains)) return src;
+    }
     for (int s = 0; s < ik.n_stages; ++s) {
         const uint32_t c1 = ik.stage_off[s + 1];
-        for (uint32_t c = ik.stage_off[s] + wave; c < c1; c += kBlock / 64)
+        if constexpr (SW) {
+            if (!ik_sw_any(*sw, inst, ik.stage_off[s], c1)) continue;
+        }
+        for (uint32_t c = ik.stage_off[s] + wave; c < c1; c += kBlock / 64) {
+            if constexpr (SW) {
+                if (!((ik_sw_word(*sw, inst, c >> 5) >> (c & 31u)) & 1u)) continue;
+            }
             ik_solve_chain(ik, c, src, sq, s_rec, s_bind, s_lt, has_t, lane);
+        }
         __syncthreads();            // every chain of the stage has left its rotations; nobody reads `src` any more
         src = ik_resolve(p, wl, m2, sq, s_rec, s_bind, s_lt, has_t, tid);
     }

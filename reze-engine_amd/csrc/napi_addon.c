@@ -825,6 +825,67 @@ static napi_value fn_set_pose_sampled(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+/* uploadIKKeys(ctx, clip | null, Float32Array frames [n] | null, Uint8Array enabled [n][chains] | null): the IK on / off keys of a motion
+ * (rz_upload_ik_keys; VMDSampler.flatten().ikKeys). clip null: the motion of uploadAnimation, else a clip of uploadMotions. frames null removes the set. */
+static napi_value fn_upload_ik_keys(napi_env env, napi_callback_info info)
+{
+    ARGS(3);
+    CTX(0);
+    static const char *usage = "uploadIKKeys(ctx, clip | null, Float32Array frames | null, Uint8Array enabled)";
+    uint32_t clip = RZ_NO_CLIP;
+    napi_valuetype vt;
+    if (napi_typeof(env, argv[1], &vt) != napi_ok) return throw_msg(env, usage);
+    if (vt != napi_null && vt != napi_undefined && (!get_u32(env, argv[1], &clip) || clip == RZ_NO_CLIP)) return throw_msg(env, usage);
+    void *f, *e = NULL;
+    size_t nf, ne = 0;
+    if (!get_ta(env, argv[2], napi_float32_array, 1, &f, &nf)) return throw_msg(env, usage);
+    if (argc > 3 && !get_ta(env, argv[3], napi_uint8_array, 1, &e, &ne)) return throw_msg(env, usage);
+    if (napi_typeof(env, argv[2], &vt) != napi_ok) return throw_msg(env, usage);
+    if (vt == napi_null || vt == napi_undefined) {
+        int rc0 = rz_upload_ik_keys(ctx, clip, NULL);
+        return rc0 ? throw_rz(env, rc0) : undef(env);
+    }
+    int chains = 0;
+    if (rz_get_tuning(ctx, "ik_chains", &chains)) return throw_rz(env, RZ_ERR_INVALID);
+    if (nf > 0xffffffffu || ne != nf * (size_t)chains) return throw_msg(env, "uploadIKKeys: enabled must hold one byte per key and chain");
+    rz_ik_keys k = { (uint32_t)nf, (const float *)f, (const uint8_t *)e };
+    int rc = rz_upload_ik_keys(ctx, clip, &k);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* setIKEnabled(ctx, Uint8Array mask [instances][chains] | null): the chain switches of the IK stage (rz_set_ik_enabled); null = all on */
+static napi_value fn_set_ik_enabled(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    void *m;
+    size_t nm;
+    if (!get_ta(env, argv[1], napi_uint8_array, 1, &m, &nm)) return throw_msg(env, "setIKEnabled(ctx, Uint8Array mask | null)");
+    if (m) {
+        int I = 0, chains = 0;
+        if (rz_get_tuning(ctx, "instances", &I) || rz_get_tuning(ctx, "ik_chains", &chains) || nm != (size_t)I * (size_t)chains)
+            return throw_msg(env, "setIKEnabled: the mask must hold one byte per instance and chain");
+    }
+    int rc = rz_set_ik_enabled(ctx, (const uint8_t *)m);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
+/* readIKEnabled(ctx) -> Uint8Array [instances][chains]: the switches the next frame's solve uses (rz_read_ik_enabled) */
+static napi_value fn_read_ik_enabled(napi_env env, napi_callback_info info)
+{
+    ARGS(1);
+    CTX(0);
+    int I = 0, chains = 0;
+    if (rz_get_tuning(ctx, "instances", &I) || rz_get_tuning(ctx, "ik_chains", &chains)) return throw_rz(env, RZ_ERR_INVALID);
+    napi_value ab, ta;
+    void *data = NULL;
+    const size_t n = (size_t)I * (size_t)chains;
+    if (napi_create_arraybuffer(env, n, &data, &ab) != napi_ok || napi_create_typedarray(env, napi_uint8_array, n, ab, 0, &ta) != napi_ok)
+        return throw_msg(env, "readIKEnabled: out of memory");
+    int rc = rz_read_ik_enabled(ctx, n ? (uint8_t *)data : NULL);
+    return rc ? throw_rz(env, rc) : ta;
+}
+
 static napi_value fn_override_world(napi_env env, napi_callback_info info)
 {
     ARGS(4);
@@ -1301,7 +1362,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "uploadMotionMasks", fn_upload_motion_masks }, { "setPoseLayered", fn_set_pose_layered }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
         { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
-        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "overrideFollow", fn_override_follow },{ "readPhysics", fn_read_physics },
+        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "overrideFollow", fn_override_follow }, { "uploadIKKeys", fn_upload_ik_keys }, { "setIKEnabled", fn_set_ik_enabled }, { "readIKEnabled", fn_read_ik_enabled },{ "readPhysics", fn_read_physics },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

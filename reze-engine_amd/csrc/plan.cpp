@@ -627,6 +627,18 @@ RzIkParams ik_params(const rz_ctx *c)
     return p;
 }
 
+RzIkSwitchParams ik_switch_params(const rz_ctx *c)
+{
+    RzIkSwitchParams p;
+    memset(&p, 0, sizeof p);
+    const rz_ctx::IkSwitch &s = c->iksw;
+    if (!c->ik_n || !s.off || s.words.empty()) return p;
+    p.words = (int)((c->ik_n + 31) / 32);
+    if (c->I == 1 && p.words <= kRzIkSwInline) memcpy(p.w0, s.words.data(), (size_t)p.words * sizeof(uint32_t));
+    else p.mask = s.dev;
+    return p;
+}
+
 uint64_t algorithmic_bytes(const rz_ctx *c)
 {
     // 36 B read + 24 B written per vertex, 12*M B of dense morph targets per vertex,

@@ -127,6 +127,96 @@ static int staged_sent(rz_ctx *c, int slot, hipStream_t us, bool piped)
     return RZ_OK;
 }
 
+}  // extern "C"
+
+namespace rzi {
+
+// ---- chain switches of the IK stage (rz_set_ik_enabled / rz_upload_ik_keys; tests/ik_switch_ref.py is the definition) ----
+static uint32_t ik_sw_words(const rz_ctx *c) { return (c->ik_n + 31) / 32; }
+
+// A change of the mask in two halves, so that a pose call can do everything that may fail BEFORE it touches the resident pose:
+// plan_ik_words allocates, waits and fills the pinned slot; commit_ik_words enqueues the copy and takes the words into the mirror.
+int plan_ik_words(rz_ctx *c, uint32_t I, std::vector<uint32_t> &&w, IkWordsPlan *pl)
+{
+    rz_ctx::IkSwitch &s = c->iksw;
+    uint64_t on = 0;
+    for (uint32_t x : w) on += (uint64_t)__builtin_popcount(x);
+    pl->off = w.empty() ? 0u : (uint32_t)((uint64_t)I * c->ik_n - on);
+    if (pl->off == 0) w.clear();
+    pl->w = std::move(w);
+    pl->slot = -1;
+    pl->inline_words = I == 1 && ik_sw_words(c) <= (uint32_t)kRzIkSwInline;
+    pl->change = pl->w != s.words || pl->inline_words != (c->I == 1 && ik_sw_words(c) <= (uint32_t)kRzIkSwInline);
+    if (!pl->change || pl->w.empty() || pl->inline_words) return RZ_OK;
+    // a crowd's bits: one pinned slot, one copy on the stream the hierarchy solve runs on, in order with the frames
+    if (pl->w.size() > s.dev_alloc) {
+        if (int r = grow(c, s.dev, s.dev_alloc, std::max<size_t>(pl->w.size(), 64))) return r;
+        // (the array moved, drained: until the commit the mirror's words are what a frame must find in it)
+        if (s.off && !(c->I == 1 && ik_sw_words(c) <= (uint32_t)kRzIkSwInline))
+            HIP_TRY(hipMemcpy(s.dev, s.words.data(), s.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (int r = stage_acquire(c, std::max<size_t>(pl->w.size() * sizeof(uint32_t), 4096), &pl->slot)) return r;
+    memcpy(c->pl.stage.slot[pl->slot].host, pl->w.data(), pl->w.size() * sizeof(uint32_t));
+    return RZ_OK;
+}
+
+int commit_ik_words(rz_ctx *c, IkWordsPlan &pl)
+{
+    if (!pl.change) return RZ_OK;
+    rz_ctx::IkSwitch &s = c->iksw;
+    int rc = RZ_OK;
+    if (pl.slot >= 0) {
+        hipStream_t us = front_stream(c);
+        hipError_t e = hipMemcpyAsync(s.dev, c->pl.stage.slot[pl.slot].host, pl.w.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us);
+        if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(RZ_ERR_HIP, "the copy of the IK chain switches failed: %s", hipGetErrorString(e)); }
+        else rc = staged_sent(c, pl.slot, us, false);
+    }
+    if (rc) { s.words.clear(); s.off = 0; return rc; }      // the array holds nobody knows what: all on, which never reads it
+    s.words = std::move(pl.w);
+    s.off = pl.off;
+    pl.change = false;
+    return RZ_OK;
+}
+
+int set_ik_words(rz_ctx *c, std::vector<uint32_t> &&w)
+{
+    IkWordsPlan pl;
+    if (int r = plan_ik_words(c, c->I, std::move(w), &pl)) return r;
+    return commit_ik_words(c, pl);
+}
+
+int plan_ik_resize(rz_ctx *c, uint32_t I, IkWordsPlan *pl)
+{
+    pl->change = false;
+    if (c->iksw.words.empty() || I == c->I) return RZ_OK;
+    const uint32_t W = ik_sw_words(c), n = c->ik_n;
+    std::vector<uint32_t> w((size_t)I * W);
+    for (uint32_t i = 0; i < I; ++i)
+        for (uint32_t k = 0; k < W; ++k)
+            w[(size_t)i * W + k] = i < c->I ? c->iksw.words[(size_t)i * W + k] : (k + 1 < W || (n & 31u) == 0 ? 0xffffffffu : (1u << (n & 31u)) - 1u);
+    // (one character's words ride in the arguments, a crowd's lie in the device array: a change of the count may move them)
+    return plan_ik_words(c, I, std::move(w), pl);
+}
+
+// the row of the LAST key whose frame is <= `frame` (before the first key: the first key's row); nullptr = the set holds no key: all on
+static const uint32_t *ik_state_at(const RzIkKeySet &ks, uint32_t W, float frame)
+{
+    const size_t n = ks.frame.size();
+    if (!n) return nullptr;
+    const size_t k = (size_t)(std::upper_bound(ks.frame.begin(), ks.frame.end(), frame) - ks.frame.begin());
+    return &ks.bits[(k ? k - 1 : 0) * W];
+}
+
+static void ik_row_into(const rz_ctx *c, const uint32_t *row, uint32_t *dst)
+{
+    const uint32_t W = ik_sw_words(c), n = c->ik_n;
+    for (uint32_t k = 0; k < W; ++k) dst[k] = row ? row[k] : (k + 1 < W || (n & 31u) == 0 ? 0xffffffffu : (1u << (n & 31u)) - 1u);
+}
+
+}  // namespace rzi
+
+extern "C" {
+
 // One per-frame pose as the host handed it over, and where its parts go inside a slot (pinned slot and device pose block share
 // the layout):   world pose [world | weights]     local pose [weights | rotations | translations]
 struct PoseParts {
@@ -553,6 +643,13 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
     // key index, which is undefined for a NaN or an infinite frame
     for (uint32_t i = 0; i < c->I; ++i)
         if (!finite_f(frames[i])) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
+    IkWordsPlan sw;
+    if (c->ik_n && c->ik_keys_an.resident) {        // the motion's IK on/off keys: every instance's switches at its frame
+        const uint32_t W = ik_sw_words(c);
+        std::vector<uint32_t> w((size_t)c->I * W);
+        for (uint32_t i = 0; i < c->I; ++i) ik_row_into(c, ik_state_at(c->ik_keys_an, W, frames[i]), &w[(size_t)i * W]);
+        if (int r = plan_ik_words(c, c->I, std::move(w), &sw)) return r;
+    }
     if (int r = ensure_pose_buffers(c)) return r;
     RzPoseLink &pl = c->pl;
     if (c->I > pl.an_frames_alloc)
@@ -571,6 +668,7 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
         if (int r = staged_sent(c, slot, us, false)) return r;
     }
     point_pose_slot(c, pl.pose_slot);       // the sampled pose is written by rz_fk_kernel under the current counts
+    if (int r = commit_ik_words(c, sw)) return r;
     pose_in_place(c, nullptr, true);
     return RZ_OK;
 }
@@ -655,6 +753,20 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
         if (slot >= 0) c->pl.stage.next = slot;
         return bad;
     }
+    IkWordsPlan sw;
+    if (c->ik_n && !c->ik_keys_mo.empty()) {
+        // the library's IK on/off keys: clip A's row at frame_a, or from blend 0.5 on clip B's at frame_b (a switch does not cross-fade;
+        // layers never switch IK); a chosen clip without keys is all on. Planned here, before the resident pose is touched.
+        const uint32_t W = ik_sw_words(c);
+        std::vector<uint32_t> w((size_t)c->I * W);
+        for (uint32_t i = 0; i < c->I; ++i) {
+            const RzMotionState &s = sv[i];
+            const bool use_b = s.clip_b != kRzNoClip && !(s.blend < 0.5f);
+            const RzIkKeySet &ks = c->ik_keys_mo[use_b ? s.clip_b : s.clip_a];
+            ik_row_into(c, ks.resident ? ik_state_at(ks, W, use_b ? s.frame_b : s.frame_a) : nullptr, &w[(size_t)i * W]);
+        }
+        if (int r = plan_ik_words(c, c->I, std::move(w), &sw)) return r;
+    }
     if (int r = ensure_pose_buffers(c)) return r;
     RzPoseLink &pl = c->pl;
     pl.map.layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
@@ -708,6 +820,7 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
     pl.last_pulled = false; pl.last_rows = false;
     if (slot >= 0)
         if (int r = staged_sent(c, slot, us, piped)) return r;
+    if (int r = commit_ik_words(c, sw)) return r;
     pose_in_place(c, nullptr, true);
     return RZ_OK;
 }
@@ -825,6 +938,35 @@ int rz_override_follow(rz_ctx *c, uint32_t on)
     }
     c->ovr_follow = (int)on;
     if (c->ovr_count) c->fk_stale = true;       // world matrices and palettes in memory are the other setting's: rz_read_world / rz_read_palette solve again
+    return RZ_OK;
+}
+
+int rz_set_ik_enabled(rz_ctx *c, const uint8_t *enabled)
+{
+    if (int r = use(c)) return r;
+    if (!c->ik_n) return fail(RZ_ERR_INVALID, "rz_set_ik_enabled: no IK table is resident (rz_upload_ik)");
+    std::vector<uint32_t> w;
+    if (enabled) {
+        const uint32_t W = ik_sw_words(c), n = c->ik_n;
+        w.assign((size_t)c->I * W, 0u);
+        for (uint32_t i = 0; i < c->I; ++i)
+            for (uint32_t k = 0; k < n; ++k)
+                if (enabled[(size_t)i * n + k]) { const uint32_t d = c->ik_dev_pos[k]; w[(size_t)i * W + (d >> 5)] |= 1u << (d & 31u); }
+    }
+    return set_ik_words(c, std::move(w));
+}
+
+int rz_read_ik_enabled(rz_ctx *c, uint8_t *out)
+{
+    if (int r = use(c)) return r;
+    if (!c->ik_n) return fail(RZ_ERR_INVALID, "rz_read_ik_enabled: no IK table is resident (rz_upload_ik)");
+    if (!out) return fail(RZ_ERR_INVALID, "rz_read_ik_enabled: null out");
+    const uint32_t W = ik_sw_words(c), n = c->ik_n;
+    for (uint32_t i = 0; i < c->I; ++i)
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t d = c->ik_dev_pos[k];
+            out[(size_t)i * n + k] = c->iksw.words.empty() ? 1 : (uint8_t)((c->iksw.words[(size_t)i * W + (d >> 5)] >> (d & 31u)) & 1u);
+        }
     return RZ_OK;
 }
 

@@ -268,6 +268,12 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "override_follow")) *value = c->ovr_follow;
     else if (!strcmp(key, "override_followers")) *value = follow_params(c).off ? (int)c->fol_count : 0;     // entries resident over all instances
     else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
+    else if (!strcmp(key, "ik_switched")) *value = (int)c->iksw.off;       // (instance, chain) bits currently off
+    else if (!strcmp(key, "ik_key_sets")) {
+        int n = c->ik_keys_an.resident ? 1 : 0;
+        for (const RzIkKeySet &s : c->ik_keys_mo) n += s.resident ? 1 : 0;
+        *value = n;
+    }
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;
     else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;

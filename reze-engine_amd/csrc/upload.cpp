@@ -260,6 +260,10 @@ int rz_set_instances(rz_ctx *c, uint32_t I)
     if (int r = use(c)) return r;
     if (I == 0 || I > 65535) return fail(RZ_ERR_INVALID, "instance count must be 1..65535");
     if (I > 1 && (c->comm || c->gather_root)) return fail(RZ_ERR_UNSUPPORTED, "instancing and vertex sharding are exclusive");
+    // the chain switches follow the count: planned under the old count (nothing is changed if that fails), committed with the new one before
+    // anything else can fail, so the mirror is never sized for another count than c->I
+    IkWordsPlan sw;
+    if (int r = plan_ik_resize(c, I, &sw)) return r;
     if (I != c->I) {
         forget_search(c);
         drop_graph(c);
@@ -275,6 +279,7 @@ int rz_set_instances(rz_ctx *c, uint32_t I)
         retire_pose_tags(c);
     }
     c->I = I;
+    if (int r = commit_ik_words(c, sw)) return r;
     if (int r = ensure_pose_buffers(c)) return r;
     return ensure_outputs(c);
 }
@@ -835,6 +840,41 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
     if (int r = to_device(&c->ik_link, lnk.data(), lnk.size())) return r;
     if (int r = to_device(&c->ik_stage_off, soff.data(), soff.size())) return r;
     c->ik_n = n_chains; c->ik_stages = n_stages;
+    // chain switches arrive in this call's chain order and travel in the device's: where each chain went
+    c->ik_dev_pos.assign(n_chains, 0u);
+    for (uint32_t i = 0; i < n_chains; ++i) c->ik_dev_pos[ord[by_stage[i]]] = i;
+    return RZ_OK;
+}
+
+int rz_upload_ik_keys(rz_ctx *c, uint32_t clip, const rz_ik_keys *keys)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_ik_keys")) return r;
+    if (!c->ik_n) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: no IK table is resident (rz_upload_ik names the chains the keys switch)");
+    if (clip != RZ_NO_CLIP && clip >= c->mo_clips) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: clip %u of %u", clip, c->mo_clips);
+    const uint32_t n = keys ? keys->n_keys : 0, nc = c->ik_n, W = (nc + 31) / 32;
+    if (keys && n && (!keys->key_frame || !keys->key_enabled)) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: null key arrays for %u keys", n);
+    for (uint32_t k = 0; k < n; ++k) {
+        const float f = keys->key_frame[k];
+        if (!(f == f) || f - f != 0.0f) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: the frame of key %u is not finite", k);
+        if (k && f < keys->key_frame[k - 1]) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: key frames must not descend (key %u)", k);
+    }
+    RzIkKeySet set;
+    set.resident = keys != nullptr;     // NULL removes the set
+    if (n) {
+        set.frame.assign(keys->key_frame, keys->key_frame + n);
+        set.bits.assign((size_t)n * W, 0u);
+        for (uint32_t k = 0; k < n; ++k)
+            for (uint32_t ch = 0; ch < nc; ++ch)
+                if (keys->key_enabled[(size_t)k * nc + ch]) { const uint32_t d = c->ik_dev_pos[ch]; set.bits[(size_t)k * W + (d >> 5)] |= 1u << (d & 31u); }
+    }
+    // host data of the pose calls alone: no frame in flight reads it, nothing to drain
+    if (clip == RZ_NO_CLIP) { c->ik_keys_an = std::move(set); return RZ_OK; }
+    if (c->ik_keys_mo.empty()) { if (!set.resident) return RZ_OK; c->ik_keys_mo.resize(c->mo_clips); }
+    c->ik_keys_mo[clip] = std::move(set);
+    bool any = false;
+    for (const RzIkKeySet &s : c->ik_keys_mo) any = any || s.resident;
+    if (!any) c->ik_keys_mo.clear();
     return RZ_OK;
 }
 

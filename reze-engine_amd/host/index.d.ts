@@ -50,6 +50,7 @@ export interface EngineOptions {
   /** With devicePhysics: contacts and friction between the model's sphere and capsule bodies by their PMX groups and masks (rz_physics_contacts, called on every shard right after the table's upload at loadModel). Off by default; without devicePhysics it throws. true: boxes take no part. 'boxes': the model's box bodies collide with its spheres and capsules as well (rz_physics_contacts(ctx, 2)); a pair of two boxes is still left out. 'all': pairs of two boxes collide too (rz_physics_contacts(ctx, 3)). */ physicsContacts?: boolean | 'boxes' | 'all'
   /** With devicePhysics: the linear springs of the model's joints (PMX spring_position; rz_physics_springs, called on every shard right after the table's upload at loadModel, ahead of physicsContacts): a joint with play along an axis and a spring on it swings about its rest point instead of hanging at the end of its play. Off by default; without devicePhysics it throws. */ physicsSprings?: boolean
   /** With deviceFK: bones below an overridden bone follow it (rz_override_follow, called on every shard and fork behind the topology upload) — W_b = O_a (S_a^-1 S_b) with a the nearest overridden ancestor of b, S the solved pose; for the overrides devicePhysics writes and for those of setBoneWorldOverrides. A strand's tip bone without a body, an ornament on a hair bone, the sub-bone of a skirt plate then ride the physics bone instead of staying with the animation. Not re-evaluated on the followed pose: append transforms, IK chains, following bodies. Off by default; without deviceFK it throws (host FK: call Model.followOverrides(world, bones, matrices) from the { physics } hook). */ followOverrides?: boolean
+  /** With ik: honour the motion's VMD show / IK keys, which switch single IK chains off and on over time (a motion traced from motion capture switches leg and toe IK off at frame 0). Host path: seekFrame, playAnimation and seekMotions set the model's chain switches (Model.setIKChainEnabled) before the pose solve; a cross-fade takes clip `a`'s switches below blend 0.5 and clip `b`'s from there on, layers never switch. With { deviceFK, deviceSampling } the keys are uploaded behind the motion (rz_upload_ik_keys) and evaluated by the pose calls; host-sampled deviceFK frames send the switches with the pose (rz_set_ik_enabled). The keys' `show` flag is returned by the loader and not used. Off by default: a motion with such keys plays as before; without ik it throws. */ ikKeys?: boolean
 }
 export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number; layers?: MotionLayer[] }
 /** one layer of a MotionState: motion `motion` at `frame`, applied with `weight` (default 1) where the mask `mask` (Engine.setMotionMask; none: everywhere) includes the bone or morph and the motion keys it — override (slerp / lerp towards it) or `additive` (q * slerp(identity, qL, weight), t + tL * weight, w + wL * weight). At most 4 per state. */
@@ -85,6 +86,8 @@ export class Engine {
   setInstanceCount(n: number): void
   /** Physics hand-off with { deviceFK }: world matrices (column-major 4x4 each) that replace the GPU-solved ones of the listed bones until the next call. */
   setBoneWorldOverrides(boneIndices: ArrayLike<number>, worldMatrices: ArrayLike<number>, instances?: ArrayLike<number>): void
+  /** With { ik }: hold one IK chain (the name of its IK bone, or its index in Model.getIKChains()) off or on by hand, for one crowd member or all; `on` null hands it back to the motion. A chain that is off does nothing: its links keep the sampled or uploaded rotations. On the device path the held switches are laid over the state the motion's keys give (all on without ikKeys) and sent behind every pose call (rz_set_ik_enabled): only the named switch changes, as on the host path. */
+  setIKEnabled(nameOrIndex: string | number, on: boolean | null, instance?: number): void
   /** With { devicePhysics }: every body back onto its bone's solved pose with zero velocities (rz_physics_reset); the accumulated time is dropped. */
   resetPhysics(): void
   getDeformed(instance?: number): { positions: Float32Array; normals: Float32Array }
@@ -106,5 +109,8 @@ export class VMDSampler {
   sampleBone(name: string, frame: number): { rotation: number[]; position: number[] } | null
   sampleMorph(name: string, frame: number): number | null
   boneNames(): string[]; morphNames(): string[]
-  flatten(boneNameIndex: Record<string, number>, morphs: { names: string[]; types: ArrayLike<number>; groups: Array<Array<[number, number]> | null> } | null): Record<string, Int32Array | Uint32Array | Float32Array | Uint8Array>
+  /** the IK switches at `frame`, name of the IK bone -> on, for every chain the motion's show / IK keys name: the state the last key with key.frame <= frame left (before the first key: the first key's); empty without such keys */
+  ikStateAt(frame: number): Map<string, boolean>
+  /** `ikChainNames` (Model.getIKChainNames()): a motion with show / IK keys also returns ikKeys: { frames, enabled [n][chains] } for rz_upload_ik_keys */
+  flatten(boneNameIndex: Record<string, number>, morphs: { names: string[]; types: ArrayLike<number>; groups: Array<Array<[number, number]> | null> } | null, ikChainNames?: string[] | null): Record<string, Int32Array | Uint32Array | Float32Array | Uint8Array | { frames: Float32Array; enabled: Uint8Array }>
 }

@@ -21,7 +21,7 @@ import { VMDLoader } from './vmd-loader'
 import { VMDSampler } from './vmd-sampler'
 import { requireAddon } from './addon'
 
-import type { Bounds, DeformAddon, DeformContext, DeformedMesh, EngineOptions, EngineStats, HostMask, MotionMaskSpec, MotionState, PhysicsLike, Shard, Timer, Timing, VMDKeyFrames } from './types'
+import type { Bounds, DeformAddon, DeformContext, DeformedMesh, EngineOptions, EngineStats, FlatMotion, HostMask, MotionMaskSpec, MotionState, PhysicsLike, Shard, Timer, Timing, VMDKeyFrames } from './types'
 import type { Model } from './model'
 let wallClock: () => number
 try {
@@ -57,6 +57,9 @@ class Engine {
   physicsContacts: boolean | 'boxes' | 'all'
   physicsSprings: boolean
   followOverrides: boolean
+  ikKeys: boolean
+  ikManual: Int8Array | null
+  ikManualSent: WeakSet<object>
   physicsAccumulator: number
   physicsResident: boolean
   native: DeformAddon | null
@@ -150,6 +153,14 @@ class Engine {
     // on every fork. The stage is the device hierarchy solve's: host FK users call Model.followOverrides from their { physics } hook.
     this.followOverrides = o.followOverrides === true
     if (this.followOverrides && !this.deviceFK) throw new Error('followOverrides needs new Engine(canvas, { deviceFK: true }); with host FK call Model.followOverrides from the { physics } hook')
+    // ikKeys: honour the motion's VMD show / IK keys, which switch single IK chains off and on over time (tests/ik_switch_ref.py is the
+    // definition). Host path: seekFrame / playAnimation / seekMotions set the model's chain switches before the pose solve. Device path:
+    // the keys are uploaded behind the motion (rz_upload_ik_keys) and the sampling pose calls evaluate them; host-sampled frames of
+    // { deviceFK } send the model's switches with the pose (rz_set_ik_enabled). Off by default: a motion with such keys plays as before.
+    this.ikKeys = o.ikKeys === true
+    if (this.ikKeys && !this.ik) throw new Error('ikKeys needs new Engine(canvas, { ik: true }): the keys switch chains of the IK solve')
+    this.ikManual = null // setIKEnabled(): [instances][chains], 1 / 0 = held on / off by hand, -1 = left to the motion
+    this.ikManualSent = new WeakSet() // the contexts whose mask carries switches set by hand
     this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
     this.physicsResident = false
     this.native = null
@@ -286,6 +297,8 @@ class Engine {
     this.overrides = null // they name bones of the previous model; the library drops its copy with the skeleton (rz_upload_skeleton)
     this.currentModel = model
     model.setClock(() => this.now())
+    model.setIKKeys(this.ikKeys)
+    this.ikManual = null
     model.setIK(this.ik && !this.deviceFK) // host solve: only without the device hierarchy (a model without IK bones: a no-op)
     const n = this.native, skinning = model.getSkinning(), skeleton = model.getSkeleton()
     const morphs = model.getMorphs()
@@ -495,6 +508,16 @@ class Engine {
       if (f.time <= 0) apply(); else this.animationTimers.push(this.setTimer(apply, f.time * 1000))
     }
 
+    // show / IK keys ({ ikKeys }): step every chain a key names at the key's time
+    if (this.ikKeys && this.currentModel) {
+      const model = this.currentModel, names = model.getIKChainNames()
+      names.forEach((_, k) => model.setIKChainEnabled(k, true)) // a chain is on until a key of THIS motion names it: nothing of the playback before stays
+      for (const f of this.animationFrames.ikFrames || []) {
+        const apply = () => { for (const e of f.ik) if (names.indexOf(e.name) >= 0) model.setIKChainEnabled(e.name, e.enabled) }
+        if (f.time <= 0) apply(); else this.animationTimers.push(this.setTimer(apply, f.time * 1000))
+      }
+    }
+
     if (enableBreath && this.currentModel) {
       let maxTime = 0
       for (const kf of this.animationFrames) if (kf.time > maxTime) maxTime = kf.time
@@ -587,6 +610,7 @@ class Engine {
       const c = this.frameContext(s)
       if (gpuFK) this.native.setPoseLocal(c, model.runtimeSkeleton.localRotations, mw, tra)
       else this.native.setPose(c, model.getBoneWorldMatrices(), mw)
+      if (gpuFK) this.sendIKSwitches(c, true)
       if (substeps >= 0) this.native.physicsStep(c, substeps) // 0 still re-places the following bodies on the new pose
       this.native.deform(c)
     }
@@ -619,9 +643,13 @@ class Engine {
   seekFrameOnDevice(frame: number | ArrayLike<number>): void {
     const model = this.currentModel
     if (this.animationOnDevice !== this.animationFrames || this.animationFor !== model) {
-      const flat = this.sampler.flatten(model.runtimeSkeleton.nameIndex, model.getMorphCount() > 0 ? model.getMorphs() : null)
+      const flat = this.sampler.flatten(model.runtimeSkeleton.nameIndex, model.getMorphCount() > 0 ? model.getMorphs() : null, this.ikKeys ? model.getIKChainNames() : null)
       this.dropForks() // the motion is static data
-      for (const s of this.shards) if (s.count > 0) this.native.uploadAnimation(s.ctx, flat)
+      for (const s of this.shards) {
+        if (s.count === 0) continue
+        this.native.uploadAnimation(s.ctx, flat)
+        this.uploadIKKeysOf(s.ctx, null, flat, model)
+      }
       this.animationOnDevice = this.animationFrames
       this.animationFor = model
     }
@@ -634,6 +662,7 @@ class Engine {
       if (s.count === 0) continue
       const c = this.frameContext(s)
       this.native.setPoseSampled(c, f)
+      this.sendIKSwitches(c, false)
       if (substeps >= 0) this.native.physicsStep(c, substeps)
       this.native.deform(c)
     }
@@ -732,9 +761,14 @@ class Engine {
     const names = Array.from(this.motions.keys())
     if (this.motionsOnDevice !== this.motionsVersion || this.motionsFor !== model) {
       const morphs = model.getMorphCount() > 0 ? model.getMorphs() : null
-      const flats = names.map((n) => this.motions.get(n).flatten(model.runtimeSkeleton.nameIndex, morphs))
+      const chainNames = this.ikKeys ? model.getIKChainNames() : null
+      const flats = names.map((n) => this.motions.get(n).flatten(model.runtimeSkeleton.nameIndex, morphs, chainNames))
       this.dropForks() // the library is static data
-      for (const s of this.shards) if (s.count > 0) this.native.uploadMotions(s.ctx, flats)
+      for (const s of this.shards) {
+        if (s.count === 0) continue
+        this.native.uploadMotions(s.ctx, flats)
+        flats.forEach((f, k) => this.uploadIKKeysOf(s.ctx, k, f, model))
+      }
       this.motionsOnDevice = this.motionsVersion
       this.motionsFor = model
     }
@@ -782,6 +816,7 @@ class Engine {
       const c = this.frameContext(s)
       if (lbuf) this.native.setPoseLayered(c, buf, nLayers, lbuf)
       else this.native.setPoseBlended(c, buf)
+      this.sendIKSwitches(c, false)
       if (substeps >= 0) this.native.physicsStep(c, substeps)
       this.native.deform(c)
     }
@@ -792,6 +827,59 @@ class Engine {
     if (this.gather === 'direct' && this.shards.length > 1) this.native.gatherFence(this.ctx)
     else if (this.gather && this.shards.length > 1) this.native.allgatherAll(this.shards.map((s) => s.ctx), true)
     this.updateStats(wallClock() - t0)
+  }
+
+  /**
+   * { ikKeys }: the IK on / off keys of a motion (clip null) or of clip `clip` of the library, right behind its upload, which dropped the
+   * keys of the motion before it. A motion WITHOUT such keys uploads a set of no keys, which is resident and says "all on": the pose calls
+   * then write an all-on mask, as the host path does, instead of leaving the switches of the motion before in place.
+   */
+  uploadIKKeysOf(ctx: DeformContext, clip: number | null, flat: FlatMotion, model: Model): void {
+    const chains = model.getIKChains().length
+    if (!this.ikKeys || chains === 0) return
+    if (flat.ikKeys) this.native.uploadIKKeys(ctx, clip, flat.ikKeys.frames, flat.ikKeys.enabled)
+    else this.native.uploadIKKeys(ctx, clip, new Float32Array(0), new Uint8Array(0))
+  }
+
+  /**
+   * What follows a pose call on the device path. With { ikKeys }, a host-sampled frame (`hostPose`: rz_set_pose_local) carries the model's
+   * chain switches, which seekFrame / playAnimation / seekMotions set from the motion; device-sampled frames need nothing: their pose call
+   * evaluates the uploaded keys. Switches held by hand (setIKEnabled) are laid over that state, switch by switch, and the result is sent;
+   * once none is held any more, a context that carried some gets its own state back. Without either: no call.
+   */
+  sendIKSwitches(c: DeformContext, hostPose: boolean): void {
+    const on = this.currentModel.getIKChainEnabled(), n = on.length
+    if (n === 0) return
+    if (this.ikManual && this.ikManual.length !== this.instances * n) this.ikManual = null // (the crowd changed)
+    const held = this.ikManual !== null && this.ikManual.some((v) => v >= 0)
+    const fromKeys = this.ikKeys && !hostPose // the pose call has just written the mask
+    if (!held && !(this.ikKeys && hostPose)) {
+      if (this.ikManualSent.has(c)) { this.ikManualSent.delete(c); if (!fromKeys) this.native.setIKEnabled(c, null) }
+      return
+    }
+    const mask = fromKeys ? Uint8Array.from(this.native.readIKEnabled(c)) : new Uint8Array(this.instances * n).fill(1)
+    if (this.ikKeys && hostPose) for (let i = 0; i < this.instances; i++) on.forEach((v, k) => { mask[i * n + k] = v ? 1 : 0 })
+    if (held) { this.ikManual.forEach((v, j) => { if (v >= 0) mask[j] = v }); this.ikManualSent.add(c) } else this.ikManualSent.delete(c)
+    this.native.setIKEnabled(c, mask)
+  }
+
+  /**
+   * Hold one IK chain off or on by hand ({ ik: true }): `nameOrIndex` is the name of the chain's IK bone or its index in
+   * Model.getIKChains(); `instance` names one crowd member (default: all); `on` null hands the switch back to the motion. Host path: the
+   * model's switch. Device path: from the next pose call on the held switches are laid over the state the motion's keys give (all on
+   * without { ikKeys }) - only the named switch changes, as on the host path.
+   */
+  setIKEnabled(nameOrIndex: string | number, on: boolean | null, instance?: number): void {
+    if (!this.ik) throw new Error('setIKEnabled needs new Engine(canvas, { ik: true })')
+    const model = this.currentModel
+    if (!model) return
+    const names = model.getIKChainNames()
+    const k = typeof nameOrIndex === 'number' ? nameOrIndex : names.indexOf(nameOrIndex)
+    if (!(k >= 0 && k < names.length)) throw new Error('setIKEnabled: no IK chain ' + JSON.stringify(nameOrIndex))
+    if (!this.deviceFK) { model.setIKChainEnabled(k, on === null || on === undefined ? true : on); return }
+    if (instance !== undefined && !(instance >= 0 && instance < this.instances)) throw new Error('setIKEnabled: instance ' + instance + ' of ' + this.instances)
+    if (!this.ikManual || this.ikManual.length !== this.instances * names.length) this.ikManual = new Int8Array(this.instances * names.length).fill(-1)
+    for (let i = 0; i < this.instances; i++) if (instance === undefined || instance === i) this.ikManual[i * names.length + k] = on === null || on === undefined ? -1 : on ? 1 : 0
   }
 
   /**

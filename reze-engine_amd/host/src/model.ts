@@ -65,6 +65,8 @@ class Model {
   _uvWeights?: Float32Array
   ikEnabled: boolean
   ikChains: IKChain[] | null
+  ikChainOn: Uint8Array | null
+  ikKeys: boolean
   ikRotations: Float32Array
   ikTranslations: Float32Array
   _ikR: Float64Array
@@ -146,6 +148,8 @@ class Model {
     // PMX inverse kinematics: off unless the engine is asked for it ({ ik: true }); the chains come from the loader's bone.ik
     this.ikEnabled = false
     this.ikChains = null
+    this.ikChainOn = null // per-chain switches of solveIK(), in getIKChains() order; null = every chain on
+    this.ikKeys = false // setIKKeys(): the pose calls that sample a motion also set the switches from its show / IK keys
     this.ikRotations = new Float32Array(0)
     this.ikTranslations = new Float32Array(0)
     this._ikR = new Float64Array(0)
@@ -404,6 +408,33 @@ class Model {
   setIK(on: boolean): void { this.ikEnabled = !!on && this.getIKChains().length > 0 }
 
   /**
+   * Switch one IK chain of solveIK() off or on: `nameOrIndex` is the name of the chain's IK bone or its index in getIKChains(). A chain
+   * that is off does nothing: its links keep the posed rotations (tests/ik_switch_ref.py; device twin: rz_set_ik_enabled).
+   */
+  setIKChainEnabled(nameOrIndex: string | number, on: boolean): void {
+    const chains = this.getIKChains()
+    const k = typeof nameOrIndex === 'number' ? nameOrIndex : chains.findIndex((ch) => this.skeleton.bones[ch.goal].name === nameOrIndex)
+    if (!(k >= 0 && k < chains.length) || k !== Math.floor(k)) throw new Error('setIKChainEnabled: no IK chain ' + JSON.stringify(nameOrIndex))
+    if (!this.ikChainOn) this.ikChainOn = new Uint8Array(chains.length).fill(1)
+    this.ikChainOn[k] = on ? 1 : 0
+  }
+
+  /** the switches of getIKChains(), in that order */
+  getIKChainEnabled(): boolean[] { return this.getIKChains().map((_, k) => !this.ikChainOn || this.ikChainOn[k] !== 0) }
+
+  /** the names of the chains' IK bones, in getIKChains() order: what a VMD's show / IK keys name */
+  getIKChainNames(): string[] { return this.getIKChains().map((ch) => this.skeleton.bones[ch.goal].name) }
+
+  /** With it on, applySampledFrame / applyBlendedFrame / applyLayeredFrame also set the chain switches from the motion's show / IK keys. Off by default. */
+  setIKKeys(on: boolean): void { this.ikKeys = !!on }
+
+  /** every chain's switch from a sampler's IK state at `frame` (VMDSampler.ikStateAt); a chain the motion never names is on, and so is every chain without a sampler */
+  applyIKState(sampler: { ikStateAt?(frame: number): Map<string, boolean> } | null, frame: number): void {
+    const state = sampler && sampler.ikStateAt ? sampler.ikStateAt(frame) : new Map()
+    this.getIKChainNames().forEach((name, k) => this.setIKChainEnabled(k, state.get(name) !== false))
+  }
+
+  /**
    * Bones below an overridden bone follow it: the host twin of the device stage rz_override_follow (csrc/kernels/fk.hip.h: FOLLOW), the
    * definition of tests/follow_ref.py in doubles with f32 stores. `world` holds the SOLVED world matrices S (n x 16, column-major: what
    * computeWorldMatrices() left, before a physics hook wrote into it) and is rewritten in place; `bones` / `matrices` (16 floats each)
@@ -538,7 +569,10 @@ class Model {
     }
     for (let k = 0; k < n; k++) solveBone(this.solveOrder[k])
     const v = [0, 0, 0, 0, 0, 0]
-    for (const ch of this.getIKChains()) {
+    const chains = this.getIKChains()
+    for (let ci = 0; ci < chains.length; ci++) {
+      if (this.ikChainOn && !this.ikChainOn[ci]) continue      // switched off: its links keep the posed rotations
+      const ch = chains[ci]
       const G = ch.goal, E = ch.effector
       for (let it = 0; it < ch.loops; it++) {
         let rotated = false
@@ -584,6 +618,7 @@ class Model {
 
   /** Pose every bone the sampler keys at `frame` (rotation + translation), and every morph it keys. Un-keyed bones keep their state. */
   applySampledFrame(sampler: VMDSampler, frame: number): void {
+    if (this.ikKeys) this.applyIKState(sampler, frame)
     const rot = this.runtimeSkeleton.localRotations, tra = this.runtimeSkeleton.localTranslations
     this.applyLocalTranslations = true
     for (const name of sampler.boneNames()) {
@@ -610,6 +645,8 @@ class Model {
   applyBlendedFrame(samplerA: VMDSampler, frameA: number, samplerB?: VMDSampler | null, frameB?: number, blend?: number): void {
     const t = samplerB && blend !== undefined && blend !== null ? blend : 0
     if (!(t >= 0 && t <= 1)) throw new Error('applyBlendedFrame: blend must be in [0, 1], got ' + blend)
+    // IK switches do not cross-fade: clip A's at frameA below blend 0.5 (as float32, what the device is handed), clip B's at frameB from there on
+    if (this.ikKeys) { if (samplerB && !(Math.fround(t) < 0.5)) this.applyIKState(samplerB, frameB === undefined || frameB === null ? 0 : frameB); else this.applyIKState(samplerA, frameA) }
     const rot = this.runtimeSkeleton.localRotations, tra = this.runtimeSkeleton.localTranslations
     this.applyLocalTranslations = true
     const fb = frameB === undefined || frameB === null ? 0 : frameB
@@ -674,6 +711,8 @@ class Model {
     const t = base.b && base.blend !== undefined && base.blend !== null ? base.blend : 0
     if (!(t >= 0 && t <= 1)) throw new Error('applyLayeredFrame: blend must be in [0, 1], got ' + base.blend)
     if (layers.length > 4) throw new Error('applyLayeredFrame: ' + layers.length + ' layers, at most 4')
+    // (layers never switch IK: the base state chooses, as in applyBlendedFrame)
+    if (this.ikKeys) { if (base.b && !(Math.fround(t) < 0.5)) this.applyIKState(base.b, base.frameB === undefined || base.frameB === null ? 0 : base.frameB); else this.applyIKState(base.a, base.frameA) }
     const live = []
     layers.forEach((l, k) => {
       if (!l.sampler || l.weight === 0) return

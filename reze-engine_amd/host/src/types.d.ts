@@ -70,13 +70,17 @@ export interface Texture { path: string; name: string }
 export interface BoneFrame { boneName: string; frame: number; rotation: Quat; position: Vec3; interpolation: Uint8Array }
 export interface MorphFrame { morphName: string; frame: number; time: number; weight: number }
 export interface VMDKeyFrame { time: number; boneFrames: BoneFrame[] }
-export type VMDKeyFrames = VMDKeyFrame[] & { morphFrames?: MorphFrame[] }
+/** one key of a VMD's show / IK block: the chains it names are switched; a chain it does not name keeps its state */
+export interface IKFrame { frame: number; time: number; show: boolean; ik: Array<{ name: string; enabled: boolean }> }
+export type VMDKeyFrames = VMDKeyFrame[] & { morphFrames?: MorphFrame[]; ikFrames?: IKFrame[] }
 export interface BoneSample { rotation: Quad; position: Triple }
 /** VMDSampler.flatten(): the arrays of rz_animation (include/reze_deform.h) */
 export interface FlatMotion {
   trackBone: Int32Array; keyOff: Uint32Array; keyFrame: Float32Array; keyRot: Float32Array; keyPos: Float32Array; keyInterp: Uint8Array
   mkeyOff?: Uint32Array; mkeyFrame?: Float32Array; mkeyWeight?: Float32Array
   feedOff?: Uint32Array; feedTrack?: Int32Array; feedRatio?: Float32Array
+  /** the motion's IK on / off keys for the model's chains (rz_ik_keys): frames [n] non-descending, enabled [n][chains] */
+  ikKeys?: { frames: Float32Array; enabled: Uint8Array }
 }
 
 /** Engine.seekMotions(): instance i is posed from motion `a` at frameA, cross-faded by `blend` (0 .. 1) into motion `b` at frameB */
@@ -94,6 +98,7 @@ export interface VMDSamplerLike {
   boneNames(): string[]; morphNames(): string[]
   sampleBone(name: string, frame: number): { rotation: number[]; position: number[] } | null
   sampleMorph(name: string, frame: number): number | null
+  ikStateAt?(frame: number): Map<string, boolean>
 }
 
 /** opaque rz_ctx handle of the addon */
@@ -128,6 +133,9 @@ export interface DeformAddon {
   physicsContacts(ctx: DeformContext, on: 0 | 1 | 2 | 3): void
   physicsSprings(ctx: DeformContext, on: 0 | 1): void
   overrideFollow(ctx: DeformContext, on: 0 | 1): void
+  uploadIKKeys(ctx: DeformContext, clip: number | null, frames: Float32Array | null, enabled?: Uint8Array | null): void
+  setIKEnabled(ctx: DeformContext, mask: Uint8Array | null): void
+  readIKEnabled(ctx: DeformContext): Uint8Array
   readPhysics(ctx: DeformContext, instance: number, state13: Float32Array): void
   enableAabb(ctx: DeformContext, on: boolean): void
   setInstances(ctx: DeformContext, count: number): void
@@ -191,7 +199,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; followOverrides?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; followOverrides?: boolean; ikKeys?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }

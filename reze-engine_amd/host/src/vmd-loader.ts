@@ -12,13 +12,18 @@
  * (:129-140) and never reads the morph block; here they are kept (`position`, `interpolation`
  * on each bone frame) and the morph-frame block that follows (u32 count, then 15-byte Shift-JIS
  * name + u32 frame + f32 weight) is returned as `result.morphFrames` — the source of the morph
- * weights the fused kernel consumes (SURVEY §8f rank 2).
+ * weights the fused kernel consumes (SURVEY §8f rank 2). Behind it the camera, light and self-shadow
+ * blocks (u32 count + fixed records of 61, 28 and 9 bytes) are skipped and the show / IK block (u32
+ * count; per key u32 frame, u8 show, u32 n, n x (20-byte Shift-JIS name, u8 enabled)) is returned as
+ * `result.ikFrames` = [{ frame, time, show, ik: [{ name, enabled }] }] sorted by frame: the keys that
+ * switch single IK chains off and on over the motion (VMDSampler.ikStateAt, Engine { ikKeys }).
+ * A file that ends before or inside any of these blocks has no IK keys: `ikFrames` is [].
  */
 import * as fs from 'fs'
 import { TextDecoder } from 'util'
 import { Quat, Vec3 } from './math'
 
-import type { VMDKeyFrames } from './types'
+import type { IKFrame, VMDKeyFrames } from './types'
 const FRAME_RATE = 30.0
 
 function makeDecoder(): TextDecoder {
@@ -49,13 +54,13 @@ class VMDLoader {
   u32(): number { this.need(4); const v = this.view.getUint32(this.pos, true); this.pos += 4; return v }
   f32(): number { this.need(4); const v = this.view.getFloat32(this.pos, true); this.pos += 4; return v }
 
-  // fixed 15-byte, NUL-terminated Shift-JIS name
-  name15(): string {
-    this.need(15)
+  // fixed-size (15 bytes; 20 in the IK block), NUL-terminated Shift-JIS name
+  name15(size: number = 15): string {
+    this.need(size)
     let n = 0
-    while (n < 15 && this.bytes[this.pos + n] !== 0) n++
+    while (n < size && this.bytes[this.pos + n] !== 0) n++
     const raw = this.bytes.subarray(this.pos, this.pos + n)
-    this.pos += 15
+    this.pos += size
     try { return this.decoder.decode(raw) } catch (e) { return String.fromCharCode.apply(null, raw) }
   }
 
@@ -105,7 +110,39 @@ class VMDLoader {
       morphFrames.sort((a, b) => a.frame - b.frame)
     }
     keyFrames.morphFrames = morphFrames // array-with-extras keeps the reference's return type
+    keyFrames.ikFrames = this.parseIKFrames()
     return keyFrames
+  }
+
+  // camera, light and self-shadow blocks skipped, then the show / IK keys; [] when the file ends anywhere before or inside them
+  parseIKFrames(): IKFrame[] {
+    const end = this.view.byteLength
+    for (const size of [61, 28, 9]) {
+      if (this.pos + 4 > end) return []
+      const n = this.u32()
+      if (this.pos + n * size > end) return []
+      this.pos += n * size
+    }
+    if (this.pos + 4 > end) return []
+    const nKeys = this.u32()
+    const out: IKFrame[] = []
+    for (let i = 0; i < nKeys; i++) {
+      if (this.pos + 9 > end) return []
+      const frame = this.u32()
+      const show = this.bytes[this.pos] !== 0
+      this.pos += 1
+      const n = this.u32()
+      if (this.pos + n * 21 > end) return []
+      const ik = []
+      for (let k = 0; k < n; k++) {
+        const name = this.name15(20)
+        ik.push({ name, enabled: this.bytes[this.pos] !== 0 })
+        this.pos += 1
+      }
+      out.push({ frame, time: frame / FRAME_RATE, show, ik })
+    }
+    out.sort((a, b) => a.frame - b.frame) // (stable: keys on one frame keep their file order, the last one wins)
+    return out
   }
 }
 

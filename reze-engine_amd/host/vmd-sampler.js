@@ -8,6 +8,7 @@
  *   rotation   slerp between the surrounding keys, parameter warped by the key's R Bezier curve
  *   position   per-axis lerp, each axis warped by its own X / Y / Z Bezier curve
  *   morph      linear between the surrounding morph keys
+ *   IK on/off  a step function per chain (ikStateAt): the state the LAST key with key.frame <= frame left (tests/ik_switch_ref.py)
  * Interpolation block layout (first 16 of the 64 bytes; values / 127):
  *   [X_x1, Y_x1, Z_x1, R_x1,  X_y1, Y_y1, Z_y1, R_y1,  X_x2, Y_x2, Z_x2, R_x2,  X_y2, Y_y2, Z_y2, R_y2]
  * i.e. curve c in {X,Y,Z,R} = cubic Bezier through (0,0), (x1,y1), (x2,y2), (1,1), stored on the LATER key.
@@ -56,6 +57,29 @@ class VMDSampler {
     for (const keys of this.bones.values()) this.lastFrame = Math.max(this.lastFrame, keys[keys.length - 1].frame)
     for (const keys of this.morphs.values()) this.lastFrame = Math.max(this.lastFrame, keys[keys.length - 1].frame)
     this._q = [0, 0, 0, 1]
+    // the show / IK keys, stably sorted by frame, and behind every key the state of every chain the motion names: a chain is on until a
+    // key names it, and a key that does not name it leaves it as it is
+    this.ikFrames = (keyFrames.ikFrames || []).slice().sort((a, b) => a.frame - b.frame)
+    this.ikRows = []
+    const state = new Map()
+    for (const key of this.ikFrames) for (const e of key.ik) state.set(e.name, true)
+    for (const key of this.ikFrames) {
+      for (const e of key.ik) state.set(e.name, !!e.enabled)
+      this.ikRows.push(new Map(state))
+    }
+  }
+
+  /**
+   * The IK switches at `frame`: name -> on, for every chain the motion's show / IK keys name (a chain they never name is on). The state
+   * the LAST key with key.frame <= frame left, frames compared as float32 values (what the device is handed); before the first key the
+   * first key's state; an empty Map when the motion has no such keys.
+   */
+  ikStateAt(frame) {
+    const keys = this.ikFrames, f = Math.fround(frame)
+    if (keys.length === 0) return new Map()
+    let lo = 0, hi = keys.length // first key with frame > f
+    while (lo < hi) { const mid = (lo + hi) >> 1; if (Math.fround(keys[mid].frame) <= f) lo = mid + 1; else hi = mid }
+    return new Map(this.ikRows[lo > 0 ? lo - 1 : 0])
   }
 
   static span(keys, frame) { // index i with keys[i].frame <= frame < keys[i+1].frame (clamped)
@@ -96,9 +120,24 @@ class VMDSampler {
    * Flatten the motion for the device sampler (rz_upload_animation): one track per bone of `boneNameIndex` the motion
    * keys, one track per keyed morph, and for every morph of the model the tracks that feed its GPU weight in the order
    * Model.getEffectiveMorphWeights adds them — its own track (vertex morphs only), then the group morphs that list it,
-   * ascending. `morphs` is Model.getMorphs() ({ names, types, groups }) or null.
+   * ascending. `morphs` is Model.getMorphs() ({ names, types, groups }) or null. `ikChainNames` (the names of the IK bones of
+   * Model.getIKChains(), in that order): when the motion has show / IK keys they are returned as `ikKeys` for rz_upload_ik_keys.
    */
-  flatten(boneNameIndex, morphs) {
+  flatten(boneNameIndex, morphs, ikChainNames) {
+    const out = this.flattenTracks(boneNameIndex, morphs)
+    if (ikChainNames && this.ikFrames.length > 0) {
+      const n = this.ikFrames.length, C = ikChainNames.length
+      const frames = new Float32Array(n), enabled = new Uint8Array(n * C)
+      this.ikFrames.forEach((key, k) => {
+        frames[k] = key.frame
+        ikChainNames.forEach((name, c) => { enabled[k * C + c] = this.ikRows[k].get(name) === false ? 0 : 1 })
+      })
+      out.ikKeys = { frames, enabled }
+    }
+    return out
+  }
+
+  flattenTracks(boneNameIndex, morphs) {
     const tracks = []
     for (const [name, keys] of this.bones) {
       const b = boneNameIndex[name]
