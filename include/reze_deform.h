@@ -389,7 +389,9 @@ int rz_set_pose_layered(rz_ctx *ctx, const rz_motion_state *base /* [I] */, uint
  * Order of a frame: sample -> bone morphs -> hierarchy -> IK -> followers -> overrides -> palette. NOT covered — nothing is evaluated again
  * on the followed pose: append rotation / move whose append parent is overridden or follows; IK chains below an overridden bone; following
  * (type 0 / 2) bodies on follower bones (the first solve of rz_physics_step runs without overrides as before, so bodies are placed on the
- * un-followed pose); PMX after-physics bones / transform levels, which stay unparsed.
+ * un-followed pose). PMX after-physics bones are a stage of their own behind the overrides (rz_upload_after_physics below), which
+ * re-evaluates the listed bones; transform levels among before-physics bones stay unread (the first solve reads pose quaternions, which
+ * adds no ordering dependency).
  * A flag of the context, off by default. It needs a resident topology (RZ_ERR_INVALID without), persists across rz_override_world calls,
  * physics uploads / removals and rz_set_instances, and is cleared by a new skeleton or topology. A fork inherits it at rz_fork and may set
  * it like its lender. A change drops the captured graph. on > 1: RZ_ERR_INVALID, context untouched. The follower lists — per instance the
@@ -402,6 +404,41 @@ int rz_set_pose_layered(rz_ctx *ctx, const rz_motion_state *base /* [I] */, uint
  * The ABI version stays 8: bindings detect the symbol. Host twin for host-solved poses: Model.followOverrides (host/model.js). */
 int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16);
 int rz_override_follow(rz_ctx *ctx, uint32_t on);
+/* ---- PMX after-physics bones: solved again behind the overrides — NEW (optional) ----
+ * PMX flag 0x1000 ("deform after physics") marks helper bones that must see the simulated pose: a skirt or sleeve aid that takes half the
+ * rotation of the physics bone beside it, a chest support that appends from a sprung body's bone, a twist bone under a physics-driven arm.
+ * Solved once before the physics step, such a bone stays with the animation while the bone it copies swings away. rz_upload_after_physics
+ * hands over the ordered list A of those bones (ascending transform level, then index: Model.afterPhysicsOrder in host/model.js); a
+ * frame then runs sample -> bone morphs -> hierarchy -> IK -> followers -> overrides -> AFTER-PHYSICS BONES -> palette. The stage is defined
+ * by tests/after_ref.py. With F the world matrices as the frame leaves them today and O the instance's overridden bones, for b in A, in
+ * list order:
+ *   b in O: skipped — an overridden bone is never re-evaluated;
+ *   P = F[parent(b)] (identity for a root); with an append parent a in effect, a's local transform AS FINALLY POSED is read from F:
+ *   R_a = rot(F[parent(a)])^T rot(F[a]), t_a = rot(F[parent(a)])^T (pos(F[a]) - pos(F[parent(a)])) - bind_a (a root a: F[a] itself),
+ *   q_a = quat(R_a) by the branch on the largest of trace, m00, m11, m22, normalised; then the local matrix exactly as the first solve forms
+ *   it from q_a and t_a (ratio clamped to [-1, 1] for the rotation, conjugate for a negative ratio, the shorter arc, |ratio| <= 1e-6 = no
+ *   append, the unclamped ratio for append move): L = T(bind_b + t_b) R(A) R(q_b) T(add), with q_b, t_b the local pose after bone morphs;
+ *   F[b] = P L, and later entries read the new F[b].
+ * So a listed bone below an overridden bone follows it through its own local transform, not rigidly, and a helper that appends from an
+ * overridden bone, a follower, an IK link or an earlier listed bone sees where that bone really is. Where the append parent itself takes
+ * append, this stage sees its full local rotation, while the first solve, like the reference, leaves the parent's own append out: the one
+ * place where the two passes differ by more than rounding. The stage runs only while the override table holds at least one entry (hand-fed
+ * or physics'); without overrides the first solve is the answer already and every frame launches what it launched before, bit for bit.
+ * NOT covered: non-listed bones below a listed bone keep their matrices (as in MMD); IK chains whose bones are listed are not solved again;
+ * following bodies on listed bones are placed on the first solve; transform levels among before-physics bones; an append parent whose
+ * final local rotation lies near 180 degrees (the shorter-arc choice flips there, exactly as in the first solve).
+ * `bones` [n] is in evaluation order; n = 0 removes the list. RZ_ERR_INVALID, naming the bone: no topology resident, an index >= B, a bone
+ * listed twice, a listed bone whose parent, append parent or append parent's parent is listed LATER (the authoring error PMX editors warn
+ * about; level-parallel evaluation would not reproduce MMD's one-frame lag). RZ_ERR_UNSUPPORTED: a listed bone that is a link or the
+ * effector of a resident IK chain or lies on its path (outermost link ... effector) — in whichever order the two tables arrive:
+ * rz_upload_ik checks the resident list too; a goal may be listed — and a skeleton whose 48 B per bone + 1 B per entry exceed 160 KB of LDS.
+ * Static data: a new skeleton or topology clears the list, rz_fork lends it, and it is refused while forks exist like every static upload.
+ * The host derives dependency levels (level = 1 + the largest level over EARLIER entries that are the bone's parent, append parent or append
+ * parent's parent) and rz_fk_after_kernel (kernels/after.hip), a kernel of its own behind whichever hierarchy kernel ran, evaluates a
+ * level in parallel. A single character's frame keeps its solve out of the deform kernel's prologue while the stage runs.
+ * rz_get_tuning("after_physics") = entries resident, ("after_physics_levels") = their levels. ABI stays 8: bindings detect the symbol.
+ * Host twin for host-solved poses: Model.solveAfterPhysics (host/model.js). */
+int rz_upload_after_physics(rz_ctx *ctx, uint32_t n, const uint32_t *bones);
 /* ---- rigid-body physics on the device for PMX bodies and joints — NEW (optional) ----
  * The reference runs Bullet (Ammo, loaded at run time: engine/src/physics.ts) on the host around the seam above. rz_upload_physics /
  * rz_physics_step keep the seam (physics.ts:534-569) and replace the solver by one of this build's own, defined in float64 by

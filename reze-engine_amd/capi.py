@@ -23,16 +23,16 @@ SYMBOLS = [
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
-    "rz_override_follow", "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled",
+    "rz_override_follow", "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
 # points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks, rz_set_pose_layered, rz_override_follow and the three chain-switch entry
-# points (rz_set_ik_enabled ..) — detected by the symbol, the version stayed 8)
+# points (rz_set_ik_enabled ..), then rz_upload_after_physics — detected by the symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
                     "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
                     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs", "rz_override_follow",
-                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled"}
+                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
 NO_MASK = 0xffffffff
@@ -235,6 +235,8 @@ def load(path=None):
         L.rz_physics_springs.argtypes = [vp, u32]
     if hasattr(L, "rz_override_follow"):
         L.rz_override_follow.argtypes = [vp, u32]
+    if hasattr(L, "rz_upload_after_physics"):
+        L.rz_upload_after_physics.argtypes = [vp, u32, ctypes.POINTER(u32)]
     if hasattr(L, "rz_upload_ik_keys"):
         L.rz_set_ik_enabled.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
         L.rz_upload_ik_keys.argtypes = [vp, u32, ctypes.POINTER(RzIkKeys)]
@@ -643,6 +645,15 @@ class DeformContext:
         if not hasattr(self._L, "rz_override_follow"):
             raise RzError(-6, "this build of the library has no rz_override_follow")
         self._chk(self._L.rz_override_follow(self._h, int(on)))
+
+    def upload_after_physics(self, bones):
+        """PMX after-physics bones (flag 0x1000), in evaluation order — ascending transform level, then index: the listed bones are solved
+        again behind the overrides, from the final pose of the bones they read (include/reze_deform.h and tests/after_ref.py state the
+        stage). An empty list removes it. Needs the topology; a new skeleton or topology clears it."""
+        if not hasattr(self._L, "rz_upload_after_physics"):
+            raise RzError(-6, "this build of the library has no rz_upload_after_physics")
+        b = np.ascontiguousarray(bones, dtype=np.uint32).reshape(-1)
+        self._chk(self._L.rz_upload_after_physics(self._h, int(b.size), b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if b.size else None))
 
     def read_world(self, instance=0):
         out = np.empty((self.B, 16), dtype=np.float32)

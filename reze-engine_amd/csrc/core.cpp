@@ -245,12 +245,21 @@ void free_ik(rz_ctx *c)
 {
     // chain switches name chains of this table: the mask is all on again and every key set goes (a fork holds no table of its own — its
     // RzStatic is emptied before this runs — and its mask goes with its context)
-    c->ik_dev_pos.clear(); c->ik_keys_an = {}; c->ik_keys_mo.clear();
+    c->ik_dev_pos.clear(); c->ik_keys_an = {}; c->ik_keys_mo.clear(); c->ik_on_path.clear();
     c->iksw.words.clear(); c->iksw.off = 0;
     if (!c->ik_n) return;
     drop_graph(c);
     dfree(c->ik_chain); dfree(c->ik_path); dfree(c->ik_stage_off); dfree(c->ik_link);
     c->ik_n = c->ik_stages = 0;
+}
+
+void free_after(rz_ctx *c)
+{
+    c->af_bones.clear();
+    if (!c->af_n) return;
+    drop_graph(c);
+    dfree(c->af_rec); dfree(c->af_level_off); dfree(c->af_index);
+    c->af_n = c->af_levels = 0;
 }
 
 void free_morphs(rz_ctx *c)
@@ -361,7 +370,7 @@ int rz_destroy(rz_ctx *c)
     // RzStatic ...
     dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->inv_bind); dfree(c->edge);
     dfree(c->fk_rec); dfree(c->fk_anc_more);
-    free_animation(c); free_motions(c); free_motion_masks(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c);
+    free_animation(c); free_motions(c); free_motion_masks(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c); free_after(c);
     // ... and what the context owns
     dfree(c->rj01); dfree(c->rj23); dfree(c->sub_list); dfree(c->sub_count);
     dfree(c->subfk_rec); dfree(c->subfk_count);

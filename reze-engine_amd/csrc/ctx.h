@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "deform_kernels.h"
+#include "after_table.h"
 #include "physics_table.h"
 #include "pose_ring.h"
 
@@ -201,6 +202,14 @@ struct RzStatic {
     // with every table, and the key sets — of the single motion, and one per clip of the library (empty: no clip holds keys). They go
     // with the table (free_ik), the motion (free_animation) and the library (free_motions). The MASK is pose state: rz_ctx::iksw.
     std::vector<uint32_t> ik_dev_pos;
+    std::vector<uint8_t> ik_on_path;    // [B] 1 = the bone lies on a chain's path (outermost link ... effector): what rz_upload_after_physics refuses
+    // PMX after-physics bones (rz_upload_after_physics; after_table.h, kernels/after.hip): the list in evaluation order as uploaded, and
+    // its device tables (deform_kernels.h: RzAfterParams). af_n = 0: no list, no frame launches rz_fk_after_kernel. Static data: a fork
+    // borrows it; a new skeleton or topology clears it (free_after).
+    std::vector<uint32_t> af_bones;
+    uint4 *af_rec = nullptr;
+    int *af_level_off = nullptr, *af_index = nullptr;
+    uint32_t af_n = 0, af_levels = 0;
     RzIkKeySet ik_keys_an;
     std::vector<RzIkKeySet> ik_keys_mo;
     // morphs
@@ -501,6 +510,7 @@ void free_morphs(rz_ctx *c);
 void free_sdef(rz_ctx *c);
 void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
+void free_after(rz_ctx *c);
 void free_physics(rz_ctx *c);          // physics_host.cpp
 RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
@@ -532,6 +542,9 @@ RzFollowParams follow_params(const rz_ctx *c);
 void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent);
 int reserve_followers(rz_ctx *c, size_t entries, size_t offsets);       // grows fol_off / fol_ent (drains and drops the graph when it must)
 int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones);       // build + blocking upload; the caller has drained
+// rz_upload_after_physics: null pointers and n = 0 unless the list is resident AND the override table holds at least one entry (then
+// launch_fk launches rz_fk_after_kernel behind the solve)
+RzAfterParams after_params(const rz_ctx *c);
 // chain switches: null mask and words 0 unless at least one bit is clear (then launch_fk takes the rz_fk_ik_sw*_kernel entries)
 RzIkSwitchParams ik_switch_params(const rz_ctx *c);
 uint64_t algorithmic_bytes(const rz_ctx *c);

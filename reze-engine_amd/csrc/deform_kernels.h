@@ -105,6 +105,19 @@ struct RzFollowParams {
     const uint2 *ent;           // [n] (follower bone, index into ovr_bone / ovr_world)
 };
 
+// PMX after-physics bones (rz_upload_after_physics; kernels/after.hip: rz_fk_after_kernel; defined by tests/after_ref.py): the listed bones
+// are evaluated again behind the override write, level by level, on the world matrices the solve left in memory. Static data built on the
+// host (after_table.h). A block of its own, handed to a kernel of its own that is launched only while the list AND a non-empty override
+// table are resident: RzFkParams — embedded in the fused kernels' arguments — does not change.
+struct RzAfterParams {
+    const uint4 *rec;           // [n][3], sorted by (level, bone): (parent, append parent or -1, bits(append ratio), flags) — the bone record's word 0 —
+                                //         (bits(bind translation) x y z, the bone), (bits(the append parent's bind translation) x y z, its parent or -1)
+    const int *level_off;       // [n_levels + 1] entries of each level
+    const int *index;           // [B] entry of a bone, -1 = not listed
+    int n;
+    int n_levels;
+};
+
 // Per-instance switches of the IK chains (rz_set_ik_enabled / rz_upload_ik_keys; kernels/ik.hip.h: SW; defined by tests/ik_switch_ref.py):
 // one bit per chain in the DEVICE's chain order (RzIkParams::chain: sorted by stage, so a stage is a contiguous bit range), bit c of word
 // c / 32, set = the chain is solved. The host evaluates the switches (it knows every frame and state it hands over) and only the bits
@@ -377,6 +390,10 @@ hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t i
 size_t rz_fk_ik_lds_bytes(const RzFkParams &p);
 // the same two solves with the follow stage (rz_fk_follow_kernel / rz_fk_ik_follow_kernel; `ik` null = no IK table): same LDS as their twins
 hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const RzFollowParams &fo, uint32_t instances, hipStream_t st);
+// the after-physics stage behind whichever of the solves above ran, on the same stream (kernels/after.hip: rz_fk_after_kernel): reads the
+// world matrices that solve left in memory and writes the listed bones' world matrices and palette rows again
+hipError_t rz_launch_fk_after(const RzFkParams &p, const RzAfterParams &a, uint32_t instances, hipStream_t st);
+size_t rz_fk_after_lds_bytes(const RzFkParams &p, const RzAfterParams &a);
 // the IK solve with per-instance chain switches (rz_fk_ik_sw_kernel / rz_fk_ik_sw_follow_kernel; `fo` null = no follower entries): same LDS as rz_fk_ik_kernel
 hipError_t rz_launch_fk_ik_sw(const RzFkParams &p, const RzIkParams &ik, const RzIkSwitchParams &sw, const RzFollowParams *fo, uint32_t instances, hipStream_t st);
 hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,

@@ -13,6 +13,19 @@ int check_ready(rz_ctx *c)
     return RZ_OK;
 }
 
+// the after-physics stage (rz_upload_after_physics) behind whichever hierarchy kernel ran, on its stream: only while the list and a
+// non-empty override table are resident
+static int launch_fk_after(rz_ctx *c, const RzFkParams &fp, hipStream_t st)
+{
+    const RzAfterParams af = after_params(c);
+    if (!af.n) return RZ_OK;
+    const size_t lds = rz_fk_after_lds_bytes(fp, af);
+    if (lds > 160 * 1024)
+        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %d entries x 1 B = %zu B of LDS (the limit is 160 KB)", c->B, af.n, lds);
+    HIP_TRY(rz_launch_fk_after(fp, af, c->I, st));
+    return RZ_OK;
+}
+
 int launch_fk(rz_ctx *c, hipStream_t st)
 {
     const RzFkParams fp = fk_params(c);
@@ -26,6 +39,7 @@ int launch_fk(rz_ctx *c, hipStream_t st)
         if (sw.words) HIP_TRY(rz_launch_fk_ik_sw(fp, ik, sw, fo.off ? &fo : nullptr, c->I, st));
         else if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, &ik, fo, c->I, st));
         else HIP_TRY(rz_launch_fk_ik(fp, ik, c->I, st));
+        if (int r = launch_fk_after(c, fp, st)) return r;
         c->palette_stale = false; c->fk_stale = false;
         return RZ_OK;
     }
@@ -34,6 +48,7 @@ int launch_fk(rz_ctx *c, hipStream_t st)
         return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve on the device: %u bones need %zu B of LDS (116 B per bone + the pose's morph weights; the limit is 160 KB)", c->B, lds);
     if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, nullptr, fo, c->I, st));
     else HIP_TRY(rz_launch_fk(fp, c->I, st));
+    if (int r = launch_fk_after(c, fp, st)) return r;
     c->palette_stale = false; c->fk_stale = false;
     return RZ_OK;
 }
@@ -268,6 +283,7 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     if (c->ik_n) { const RzIkParams ik = ik_params(c); h = fnv(h, &ik, sizeof ik); }
     if (c->ovr_follow) { const RzFollowParams fo = follow_params(c); h = fnv(h, &fo, sizeof fo); }
     if (c->ik_n) { const RzIkSwitchParams sw = ik_switch_params(c); h = fnv(h, &sw, sizeof sw); }
+    if (c->af_n) { const RzAfterParams af = after_params(c); h = fnv(h, &af, sizeof af); }
     const uint64_t misc[6] = { c->I, c->pl.cur.local, c->pl.cur.local_t, c->pl.cur.sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }

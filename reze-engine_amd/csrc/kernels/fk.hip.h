@@ -413,8 +413,9 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // matrices, every bone b outside O with an ancestor in O takes  W_b = O_a * (S_a^-1 * S_b),  a = the NEAREST such ancestor along the
 // parents, S_a^-1 the rigid inverse (R^T, -R^T p: world matrices carry no scale); bones of O take O_a, all others keep S_b. So an override
 // below another override is absolute, the bones between the two follow the upper one and the bones below the lower one the lower one.
-// Nothing is re-evaluated: append rotation / move from an overridden or following append parent, IK chains below an overridden bone and
-// following bodies on follower bones see the solved pose. The host builds the (follower, override entry) list per instance from the
+// Nothing is re-evaluated HERE: append rotation / move from an overridden or following append parent, IK chains below an overridden bone and
+// following bodies on follower bones see the solved pose. (PMX after-physics bones are re-evaluated behind the override write by a kernel
+// of its own, kernels/after.hip: rz_fk_after_kernel, for the bones rz_upload_after_physics lists; this template is not part of it.) The host builds the (follower, override entry) list per instance from the
 // parents (plan.cpp: build_followers); the stage runs between the IK stage and the override write, while the solved rows in LDS are still
 // un-overridden: a lane reads S_a and S_b from LDS, O_a from the override table, and writes W_b over its own row. No follower reads a row
 // another follower writes (a is overridden, never a follower), so the stage needs no LDS of its own and one barrier: behind it, before

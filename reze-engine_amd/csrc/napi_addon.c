@@ -493,6 +493,19 @@ static napi_value fn_override_follow(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+/* uploadAfterPhysics(ctx, Uint32Array bones): rz_upload_after_physics — the PMX after-physics bones in evaluation order (Model.afterPhysicsOrder);
+ * an empty array removes the list */
+static napi_value fn_upload_after_physics(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    void *b;
+    size_t n;
+    if (!get_ta(env, argv[1], napi_uint32_array, 0, &b, &n) || n > 0xffffffffu) return throw_msg(env, "uploadAfterPhysics(ctx, Uint32Array bones)");
+    int rc = rz_upload_after_physics(ctx, (uint32_t)n, n ? (const uint32_t *)b : NULL);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
 /* readPhysics(ctx, instance, Float32Array state13): per body x3 q4 v3 w3 (rz_read_physics); blocking, for tests and tools */
 static napi_value fn_read_physics(napi_env env, napi_callback_info info)
 {
@@ -1362,7 +1375,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "uploadMotionMasks", fn_upload_motion_masks }, { "setPoseLayered", fn_set_pose_layered }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
         { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
-        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "overrideFollow", fn_override_follow }, { "uploadIKKeys", fn_upload_ik_keys }, { "setIKEnabled", fn_set_ik_enabled }, { "readIKEnabled", fn_read_ik_enabled },{ "readPhysics", fn_read_physics },
+        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "overrideFollow", fn_override_follow }, { "uploadAfterPhysics", fn_upload_after_physics }, { "uploadIKKeys", fn_upload_ik_keys }, { "setIKEnabled", fn_set_ik_enabled }, { "readIKEnabled", fn_read_ik_enabled },{ "readPhysics", fn_read_physics },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

@@ -196,7 +196,7 @@ Plan make_plan(const rz_ctx *c)
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
     // (an IK table keeps the solve in a kernel of its own, rz_fk_ik_kernel: the fused kernels carry no IK stage; nor the follow stage of
     // rz_override_follow, so resident follower entries keep the solve with rz_fk_follow_kernel)
-    pl.fuse_fk = c->ik_n == 0 && !follow_params(c).off && c->I == 1 && c->pl.cur.local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
+    pl.fuse_fk = c->ik_n == 0 && !follow_params(c).off && !after_params(c).n && c->I == 1 && c->pl.cur.local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
                  (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pl.cur.sampled || c->morph_mode != 1)));
     const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->pl.cur.ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
@@ -558,6 +558,14 @@ RzFollowParams follow_params(const rz_ctx *c)
     RzFollowParams p;
     memset(&p, 0, sizeof p);
     if (c->ovr_follow && c->ovr_count && c->fol_count) { p.off = c->fol_off; p.ent = c->fol_ent; }
+    return p;
+}
+
+RzAfterParams after_params(const rz_ctx *c)
+{
+    RzAfterParams p;
+    memset(&p, 0, sizeof p);
+    if (c->af_n && c->ovr_count) { p.rec = c->af_rec; p.level_off = c->af_level_off; p.index = c->af_index; p.n = (int)c->af_n; p.n_levels = (int)c->af_levels; }
     return p;
 }
 

@@ -166,6 +166,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     c->fk_stale = false; c->subfk_valid = false;
     free_bone_morphs(c);                // ... as do bone morphs (their entries name its bones)
     free_ik(c);                         // ... and the IK table (its chains name its bones)
+    free_after(c);                      // ... and the after-physics list (it names its bones)
     free_physics(c);                    // ... and the physics table (its bodies name its bones)
     free_animation(c);                  // ... and so does an uploaded motion (its tracks name bones of that skeleton)
     free_motions(c);                    // ... and the motion library
@@ -338,6 +339,7 @@ int rz_upload_skeleton_topology(rz_ctx *c, uint32_t B, const int32_t *parents, c
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
     free_ik(c);                         // its chains were checked against the old parents
+    free_after(c);                      // rz_upload_after_physics: its levels were derived from the old parents and append parents
     free_physics(c);                    // its bind pose was taken from the old hierarchy
     c->ovr_count = 0;
     c->ovr_follow = 0; c->fol_count = 0;        // rz_override_follow: the follower lists were built from the old parents
@@ -773,6 +775,12 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
             if (is_link[(size_t)k * B + (uint32_t)x] || (append_of((uint32_t)x) >= 0 && is_link[(size_t)k * B + (uint32_t)append_of((uint32_t)x)]))
                 return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: the goal of chain %u (bone %u) hangs below its own link %d: the goal would move with every step", k, goal[k], x);
     }
+    // rz_upload_after_physics: a listed bone on a chain's path would be posed twice — by the chain, and again from its pose quaternion behind
+    // the overrides, which undoes the chain (IK chains whose bones are listed are not re-solved after physics). A goal may be listed.
+    for (uint32_t k = 0; k < n_chains; ++k)
+        for (uint32_t b : path[k])
+            if (std::find(c->af_bones.begin(), c->af_bones.end(), b) != c->af_bones.end())
+                return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: bone %u on the path of chain %u is an after-physics bone (rz_upload_after_physics): the stage does not solve IK again", b, k);
     // solve order: ascending IK bone (stable). Stages: a chain comes after every earlier chain whose links move a bone it reads (goal,
     // effector — whose ancestors cover the path —, through parents or an append rotation), and not before an earlier chain that reads a
     // bone ITS links move (that chain must not see it)
@@ -841,8 +849,46 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
     if (int r = to_device(&c->ik_stage_off, soff.data(), soff.size())) return r;
     c->ik_n = n_chains; c->ik_stages = n_stages;
     // chain switches arrive in this call's chain order and travel in the device's: where each chain went
+    c->ik_on_path.assign(B, 0);
+    for (uint32_t k = 0; k < n_chains; ++k)
+        for (uint32_t b : path[k]) c->ik_on_path[b] = 1;
     c->ik_dev_pos.assign(n_chains, 0u);
     for (uint32_t i = 0; i < n_chains; ++i) c->ik_dev_pos[ord[by_stage[i]]] = i;
+    return RZ_OK;
+}
+
+int rz_upload_after_physics(rz_ctx *c, uint32_t n, const uint32_t *bones)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_after_physics")) return r;
+    if (n == 0) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->af_n) c->fk_stale = c->fk_stale || c->ovr_count != 0;       // world matrices in memory carry the stage: rz_read_world solves again
+        free_after(c);
+        return RZ_OK;
+    }
+    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+        return fail(RZ_ERR_INVALID, "rz_upload_after_physics acts on device-solved poses: call rz_upload_skeleton_topology first");
+    if (!bones) return fail(RZ_ERR_INVALID, "rz_upload_after_physics: null list of %u bones", n);
+    rzafter::Table t;
+    std::string err;
+    if (rzafter::build(c->B, reinterpret_cast<const uint32_t *>(c->fk_host.data()), n, bones, t, err)) return fail(RZ_ERR_INVALID, "%s", err.c_str());
+    if (c->ik_n)
+        for (uint32_t k = 0; k < n; ++k)
+            if (c->ik_on_path[bones[k]])
+                return fail(RZ_ERR_UNSUPPORTED, "rz_upload_after_physics: bone %u (entry %u) is a link or the effector of a resident IK chain, or lies on its path: the stage does not solve IK again", bones[k], k);
+    const size_t lds = rzafter::lds_bytes(c->B, n);
+    if (lds > 160 * 1024)
+        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %u entries x 1 B = %zu B of LDS (the limit is 160 KB = %d B)", c->B, n, lds, 160 * 1024);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_after(c);
+    drop_graph(c);
+    if (int r = to_device(&c->af_rec, t.rec.data(), (size_t)n * 3)) return r;
+    if (int r = to_device(&c->af_level_off, t.level_off.data(), t.level_off.size())) return r;
+    if (int r = to_device(&c->af_index, t.index.data(), t.index.size())) return r;
+    c->af_bones.assign(bones, bones + n);
+    c->af_n = n; c->af_levels = (uint32_t)t.levels;
+    if (c->ovr_count) c->fk_stale = true;       // world matrices and palettes in memory are the frame's without the stage: rz_read_world / rz_read_palette solve again
     return RZ_OK;
 }
 

@@ -80,6 +80,12 @@ class Engine {
     // on every fork. The stage is the device hierarchy solve's: host FK users call Model.followOverrides from their { physics } hook.
     this.followOverrides = o.followOverrides === true
     if (this.followOverrides && !this.deviceFK) throw new Error('followOverrides needs new Engine(canvas, { deviceFK: true }); with host FK call Model.followOverrides from the { physics } hook')
+    // afterPhysics: the model's PMX after-physics bones (flag 0x1000) are solved again behind the overrides, from the final pose of the bones
+    // they read (rz_upload_after_physics; the definition is tests/after_ref.py): Model.afterPhysicsOrder() goes up on every shard behind
+    // the topology upload — behind the IK table when both are on — and forks borrow it with the rest of the static data. The stage is the
+    // device frame's: host FK users call Model.solveAfterPhysics at the end of their { physics } hook.
+    this.afterPhysics = o.afterPhysics === true
+    if (this.afterPhysics && !this.deviceFK) throw new Error('afterPhysics needs new Engine(canvas, { deviceFK: true }); with host FK call Model.solveAfterPhysics(world, overriddenBones) from the { physics } hook')
     // ikKeys: honour the motion's VMD show / IK keys, which switch single IK chains off and on over time (tests/ik_switch_ref.py is the
     // definition). Host path: seekFrame / playAnimation / seekMotions set the model's chain switches before the pose solve. Device path:
     // the keys are uploaded behind the motion (rz_upload_ik_keys) and the sampling pose calls evaluate them; host-sampled frames of
@@ -276,6 +282,11 @@ class Engine {
             off[k + 1] = e
           })
           n.uploadIK(s.ctx, goal, eff, loops, theta, off, lb, ll, lmin, lmax)
+        }
+        // the after-physics bones in evaluation order: checked against the topology and the IK table just uploaded (a new topology cleared the list)
+        if (this.afterPhysics) {
+          const order = model.afterPhysicsOrder()
+          if (order.length > 0) n.uploadAfterPhysics(s.ctx, Uint32Array.from(order))
         }
         // so is physics: every shard simulates the same bodies (the solve is deterministic), so no shard waits for another's overrides
         if (tables && tables.nBodies > 0) {

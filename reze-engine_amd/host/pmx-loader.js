@@ -221,7 +221,7 @@ class PmxLoader {
       this.text()
       const p = c.vec3()
       const parent = c.index(bs)
-      c.i32() // transform order
+      const transformLevel = c.i32() // the PMX transform order ("deform layer"): after-physics bones are evaluated by (level, index)
       const flags = c.u16()
       if (flags & 0x0001) c.index(bs); else c.skip(12) // tail: bone index or offset
       let appendParent, appendRatio
@@ -241,7 +241,7 @@ class PmxLoader {
         }
         ik = { effector, loops, limitAngle, links }
       }
-      raw[i] = { name, parent, p, appendParent, appendRatio, appendRotate, appendMove, ik }
+      raw[i] = { name, parent, p, appendParent, appendRatio, appendRotate, appendMove, ik, transformLevel, afterPhysics: (flags & 0x1000) !== 0 }
     }
     // absolute positions -> parent-relative bind translations (pmx-loader.ts:416-442)
     return raw.map((b) => {
@@ -253,6 +253,9 @@ class PmxLoader {
         appendMove: b.appendMove,
       }
       if (b.ik) bone.ik = b.ik // only bones with flag 0x0020 carry the field: every other bone is the object it was
+      // the same pattern: only bones with flag 0x1000 ("deform after physics") / a non-zero transform level carry these (Model.afterPhysicsOrder)
+      if (b.afterPhysics) bone.afterPhysics = true
+      if (b.transformLevel) bone.transformLevel = b.transformLevel
       return bone
     })
   }

@@ -491,6 +491,156 @@ class Model {
   }
 
   /**
+   * The PMX after-physics bones (flag 0x1000, "deform after physics") in evaluation order: ascending (transform level, index) — the list
+   * rz_upload_after_physics takes and solveAfterPhysics() walks. Throws, naming the bone, when a listed bone's parent, append parent or
+   * append parent's parent is listed LATER: the authoring error PMX editors warn about (MMD then shows a one-frame lag, which neither
+   * twin reproduces).
+   */
+  afterPhysicsOrder(): number[] {
+    const bones = this.skeleton.bones, n = bones.length
+    const order = []
+    for (let i = 0; i < n; i++) if (bones[i].afterPhysics) order.push(i)
+    order.sort((a, b) => ((bones[a].transformLevel || 0) - (bones[b].transformLevel || 0)) || (a - b))
+    const pos = new Int32Array(n).fill(-1)
+    order.forEach((b, k) => { pos[b] = k })
+    for (let k = 0; k < order.length; k++) {
+      const b = order[k], ap = this._appendInEffect(b)
+      const reads = [bones[b].parentIndex, ap, ap >= 0 ? bones[ap].parentIndex : -1]
+      const what = ['parent', 'append parent', "append parent's parent"]
+      for (let j = 0; j < 3; j++) {
+        const r = reads[j]
+        if (r >= 0 && r < n && r !== b && pos[r] > k) {
+          throw new Error('afterPhysicsOrder: bone ' + b + ' (' + bones[b].name + ') is evaluated before its ' + what[j] + ', bone ' + r + ' (' + bones[r].name +
+            '): an after-physics bone must come after the after-physics bones it reads (transform level, then index)')
+        }
+      }
+    }
+    return order
+  }
+
+  /** the append parent bone b's local matrix reads, or -1: none, or a ratio that leaves none in effect (computeWorldMatrices) */
+  _appendInEffect(b: number): number {
+    const bone = this.skeleton.bones[b], n = this.skeleton.bones.length
+    const ap = bone.appendParentIndex
+    if (!bone.appendRotate || ap === undefined || ap === null || ap < 0 || ap >= n) return -1
+    const ratio = bone.appendRatio === undefined || bone.appendRatio === null ? 1 : Math.max(-1, Math.min(1, Math.fround(bone.appendRatio)))
+    return Math.abs(ratio) > 1e-6 ? ap : -1
+  }
+
+  /**
+   * The after-physics bones solved again on the final pose: the host twin of the device stage rz_upload_after_physics
+   * (csrc/kernels/after.hip), the definition of tests/after_ref.py in doubles with f32 stores. `world` holds the world matrices as the
+   * frame leaves them (n x 16, column-major: computeWorldMatrices(), then the physics hook's overrides, then followOverrides() if used)
+   * and is rewritten in place; `overriddenBones` is the override set O. For b in afterPhysicsOrder(), unless b is in O:
+   * P = world[parent(b)]; with an append parent a in effect, a's local transform as finally posed is read from `world`
+   * (R_a = rot(W[parent(a)])^T rot(W[a]), t_a = rot(W[parent(a)])^T (pos(W[a]) - pos(W[parent(a)])) - bind_a; a root a: W[a] itself),
+   * q_a = quat(R_a) by the branch on the largest of trace, m00, m11, m22, normalised, and the local matrix is formed as
+   * computeWorldMatrices() forms it with q_a and t_a in the place of a's pose; world[b] = P L, and later entries read it. Non-listed bones
+   * below a listed bone keep their matrices; IK is not solved again. For host-FK users of the { physics } hook: call it at the hook's end.
+   */
+  solveAfterPhysics(world: Float32Array, overriddenBones: ArrayLike<number>): void {
+    const bones = this.skeleton.bones, n = bones.length
+    if (world.length !== n * 16) throw new Error('solveAfterPhysics: world holds ' + world.length + ' floats, the skeleton has ' + n + ' bones')
+    const skip = new Uint8Array(n)
+    for (let k = 0; k < overriddenBones.length; k++) {
+      if (!(overriddenBones[k] >= 0 && overriddenBones[k] < n)) throw new Error('solveAfterPhysics: bone ' + overriddenBones[k] + ' out of range')
+      skip[overriddenBones[k]] = 1
+    }
+    const order = this.afterPhysicsOrder()
+    const { rot, tra, moved } = this.posedLocals()
+    const useT = this.applyLocalTranslations || moved
+    // row-major 3 x 3 of a quaternion (math.ts: fromQuat)
+    const qmat = (x, y, z, w) => {
+      const x2 = x + x, y2 = y + y, z2 = z + z
+      const xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2, wx = w * x2, wy = w * y2, wz = w * z2
+      return [1 - (yy + zz), xy - wz, xz + wy, xy + wz, 1 - (xx + zz), yz - wx, xz - wy, yz + wx, 1 - (xx + yy)]
+    }
+    const mul3 = (a, b) => {
+      const o = new Array(9)
+      for (let i = 0; i < 3; i++) for (let j = 0; j < 3; j++) o[i * 3 + j] = a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j] + a[i * 3 + 2] * b[6 + j]
+      return o
+    }
+    // rows (R row-major, p) of a column-major 4 x 4 in `world`
+    const rows = (b) => {
+      const o = b * 16
+      return { R: [world[o], world[o + 4], world[o + 8], world[o + 1], world[o + 5], world[o + 9], world[o + 2], world[o + 6], world[o + 10]], p: [world[o + 12], world[o + 13], world[o + 14]] }
+    }
+    for (const b of order) {
+      if (skip[b]) continue
+      const bone = bones[b]
+      let R = qmat(rot[b * 4], rot[b * 4 + 1], rot[b * 4 + 2], rot[b * 4 + 3])
+      let ax = 0, ay = 0, az = 0
+      const a = this._appendInEffect(b)
+      if (a >= 0) {
+        const A = rows(a)
+        let Ra = A.R, pa = A.p
+        const g = bones[a].parentIndex
+        if (g >= 0) {
+          const G = rows(g)
+          const Gt = [G.R[0], G.R[3], G.R[6], G.R[1], G.R[4], G.R[7], G.R[2], G.R[5], G.R[8]]
+          const d = [pa[0] - G.p[0], pa[1] - G.p[1], pa[2] - G.p[2]]
+          Ra = mul3(Gt, Ra)
+          pa = [Gt[0] * d[0] + Gt[1] * d[1] + Gt[2] * d[2], Gt[3] * d[0] + Gt[4] * d[1] + Gt[5] * d[2], Gt[6] * d[0] + Gt[7] * d[1] + Gt[8] * d[2]]
+        }
+        const ba = bones[a].bindTranslation
+        const ta = [pa[0] - ba[0], pa[1] - ba[1], pa[2] - ba[2]]
+        // q_a = quat(R_a): the branch on the largest of trace, m00, m11, m22, then normalised
+        const m = Ra, tr = m[0] + m[4] + m[8]
+        let qx, qy, qz, qw
+        if (tr >= m[0] && tr >= m[4] && tr >= m[8]) {
+          const s = Math.sqrt(tr + 1) * 2
+          qw = 0.25 * s; qx = (m[7] - m[5]) / s; qy = (m[2] - m[6]) / s; qz = (m[3] - m[1]) / s
+        } else if (m[0] >= m[4] && m[0] >= m[8]) {
+          const s = Math.sqrt(1 + m[0] - m[4] - m[8]) * 2
+          qw = (m[7] - m[5]) / s; qx = 0.25 * s; qy = (m[1] + m[3]) / s; qz = (m[2] + m[6]) / s
+        } else if (m[4] >= m[8]) {
+          const s = Math.sqrt(1 + m[4] - m[0] - m[8]) * 2
+          qw = (m[2] - m[6]) / s; qx = (m[1] + m[3]) / s; qy = 0.25 * s; qz = (m[5] + m[7]) / s
+        } else {
+          const s = Math.sqrt(1 + m[8] - m[0] - m[4]) * 2
+          qw = (m[3] - m[1]) / s; qx = (m[2] + m[6]) / s; qy = (m[5] + m[7]) / s; qz = 0.25 * s
+        }
+        const il = 1 / Math.sqrt(qx * qx + qy * qy + qz * qz + qw * qw)
+        qx *= il; qy *= il; qz *= il; qw *= il
+        const raw = bone.appendRatio === undefined || bone.appendRatio === null ? 1 : Math.fround(bone.appendRatio)
+        const ratio = Math.max(-1, Math.min(1, raw))
+        if (bone.appendMove) { ax = ta[0] * raw; ay = ta[1] * raw; az = ta[2] * raw }
+        if (ratio < 0) { qx = -qx; qy = -qy; qz = -qz }
+        // Quat.slerp(identity, q_a, |ratio|): the shorter arc
+        const t = Math.abs(ratio)
+        let c = qw
+        if (c < 0) { c = -c; qx = -qx; qy = -qy; qz = -qz; qw = -qw }
+        let sx, sy, sz, sw
+        if (c > 0.9995) {
+          sx = t * qx; sy = t * qy; sz = t * qz; sw = 1 + t * (qw - 1)
+          const l = 1 / Math.sqrt(sx * sx + sy * sy + sz * sz + sw * sw)
+          sx *= l; sy *= l; sz *= l; sw *= l
+        } else {
+          const th0 = Math.acos(c), sn = Math.sin(th0), th = th0 * t
+          const s0 = Math.sin(th0 - th) / sn, s1 = Math.sin(th) / sn
+          sx = s1 * qx; sy = s1 * qy; sz = s1 * qz; sw = s0 + s1 * qw
+        }
+        R = mul3(qmat(sx, sy, sz, sw), R)
+      }
+      const bt = bone.bindTranslation
+      let tx = bt[0], ty = bt[1], tz = bt[2]
+      if (useT) { tx += tra[b * 3]; ty += tra[b * 3 + 1]; tz += tra[b * 3 + 2] }
+      tx += R[0] * ax + R[1] * ay + R[2] * az; ty += R[3] * ax + R[4] * ay + R[5] * az; tz += R[6] * ax + R[7] * ay + R[8] * az
+      let W = R, px = tx, py = ty, pz = tz
+      if (bone.parentIndex >= 0) {
+        const P = rows(bone.parentIndex)
+        W = mul3(P.R, R)
+        px = P.R[0] * tx + P.R[1] * ty + P.R[2] * tz + P.p[0]; py = P.R[3] * tx + P.R[4] * ty + P.R[5] * tz + P.p[1]; pz = P.R[6] * tx + P.R[7] * ty + P.R[8] * tz + P.p[2]
+      }
+      const o = b * 16
+      world[o] = W[0]; world[o + 1] = W[3]; world[o + 2] = W[6]; world[o + 3] = 0
+      world[o + 4] = W[1]; world[o + 5] = W[4]; world[o + 6] = W[7]; world[o + 7] = 0
+      world[o + 8] = W[2]; world[o + 9] = W[5]; world[o + 10] = W[8]; world[o + 11] = 0
+      world[o + 12] = px; world[o + 13] = py; world[o + 14] = pz; world[o + 15] = 1
+    }
+  }
+
+  /**
    * PMX inverse kinematics on the host: CCD in the clamp form, the arithmetic of tests/ik_ref.py (the definition; GPU twin:
    * csrc/kernels/ik.hip.h) in doubles, the solved rotations stored to a Float32Array pose copy like posedLocals() does for bone
    * morphs - the runtime's tween and animation state is never overwritten. Chains in ascending order of the IK bone; per iteration and

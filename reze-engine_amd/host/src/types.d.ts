@@ -22,6 +22,10 @@ export interface Bone {
   appendMove?: boolean
   /** PMX IK block (flag 0x0020): this bone is the goal. Links run from the effector outwards; limits are Euler angles in radians as stored. */
   ik?: IKBlock
+  /** PMX flag 0x1000, "deform after physics": present (true) only on bones that carry it (Model.afterPhysicsOrder, Engine { afterPhysics }) */
+  afterPhysics?: boolean
+  /** the PMX transform order ("deform layer"): present only when it is not 0 */
+  transformLevel?: number
 }
 export interface IKLink { bone: number; min?: Triple; max?: Triple }
 export interface IKBlock { effector: number; loops: number; limitAngle: number; links: IKLink[] }
@@ -133,6 +137,7 @@ export interface DeformAddon {
   physicsContacts(ctx: DeformContext, on: 0 | 1 | 2 | 3): void
   physicsSprings(ctx: DeformContext, on: 0 | 1): void
   overrideFollow(ctx: DeformContext, on: 0 | 1): void
+  uploadAfterPhysics(ctx: DeformContext, bones: Uint32Array): void
   uploadIKKeys(ctx: DeformContext, clip: number | null, frames: Float32Array | null, enabled?: Uint8Array | null): void
   setIKEnabled(ctx: DeformContext, mask: Uint8Array | null): void
   readIKEnabled(ctx: DeformContext): Uint8Array
@@ -199,7 +204,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; followOverrides?: boolean; ikKeys?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; followOverrides?: boolean; afterPhysics?: boolean; ikKeys?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }
