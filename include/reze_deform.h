@@ -607,11 +607,37 @@ int rz_upload_after_physics(rz_ctx *ctx, uint32_t n, const uint32_t *bones);
  *   multipliers in LDS cost 24 B per joint instead of 12, and 96 B per body + 24 B per joint exceeds 160 KB. The context keeps its state
  *   in every case. The block size chosen at upload does not change.
  * rz_get_tuning("physics_springs") = 0 / 1, ("physics_spring_axes") = the (joint, axis) pairs with k > 0 while enabled, else 0;
- * ("physics_lds") reports the size actually launched. A build without the symbol has no linear springs (the ABI version stayed 8). */
+ * ("physics_lds") reports the size actually launched. A build without the symbol has no linear springs (the ABI version stayed 8).
+ * ---- PMX type-2 bodies, "physics + bone position alignment" — NEW (optional, off by default) ----
+ * Without rz_physics_aligned a body of type 2 follows its bone, as in the engine this one was modelled on. MMD simulates it like a dynamic
+ * body and gives its bone the rotation only; rz_physics_aligned(ctx, 1) does the same. Defined in float64 by tests/align_ref.py. A body is
+ * ALIGNED when the feature is on, its type is 2, its mass is > 0 and it has a bone. A type-2 body with a mass and no bone becomes a plain
+ * dynamic body; a type-2 body of mass 0 keeps following its bone. The table is then the same table with those bodies' type read as 1 —
+ * integration, joints in colour order, every spring, every contact mode, velocities, all as stated above — and two rules:
+ *   1. at the start of every rz_physics_step call — once per call, not per substep — an aligned body keeps q, v and w and is put back onto
+ *      its bone: x = p_bone + rot(q (x) offset_q^-1) offset_p, p_bone the translation of the bone's matrix in the un-overridden solve the
+ *      call has just run. On a reset (the implicit one of the first step too) every body is placed on its bone as ever, which satisfies it.
+ *   2. the override of an aligned body's bone takes its rotation from the body, q (x) offset_q^-1, and its translation column is the solved
+ *      matrix's own, the same float32 bits. The state (rz_read_physics) keeps the simulated x.
+ *   There is no pin inside the solve: joints hold the body, as in MMD; an aligned body without a joint drifts during a call and is back on
+ *   its bone at the next. substeps = 0 re-pins and re-emits with the new bone position. rz_physics_step(n) is therefore NOT n calls of
+ *   rz_physics_step(1) for a table with aligned bodies; it stays so, bit for bit, for every other table.
+ * rz_physics_aligned: on != 0 derives again, from the table kept at upload, everything rz_upload_physics derives — validation, the joints'
+ *   colours and order, inverse mass and inertia, the overridden bones and their slots, the block size — with those bodies dynamic, and
+ *   flags the aligned ones; 0 derives it as uploaded. Like a new upload both values turn contacts and linear springs off, reset the
+ *   simulation, drop a captured graph and rebuild rz_override_follow's lists: call it right behind rz_upload_physics, ahead of
+ *   rz_physics_springs and rz_physics_contacts. A new rz_upload_physics, a table removal, a new skeleton or a new topology turns it off.
+ *   With on = 1 and no aligned body the table steps through the kernels, and to the bits, of a plain upload; the ALIGN instantiations of
+ *   rz_physics_kernel run only for a table that has one. RZ_ERR_INVALID: no resident table; forks exist; two bodies that are dynamic now
+ *   drive one bone (the message names both). RZ_ERR_UNSUPPORTED: the LDS of the launch form the new colouring selects exceeds 160 KB —
+ *   the upload's own check on the new block size; with 96 B per body and 12 B per joint it cannot fail for a table the upload took (the
+ *   block differs only below 65 bodies, where both forms fit). The context keeps its state in every one of them.
+ * rz_get_tuning("physics_aligned") = 0 / 1, ("physics_aligned_bodies") = the aligned bodies while on, else 0. A build without the symbol
+ * has no aligned bodies (the ABI version stayed 8). */
 typedef struct rz_physics {
     uint32_t n_bodies;
     const int32_t *bone;                /* [n_bodies] -1 = none */
-    const uint8_t *type, *shape;        /* type 0 follows its bone, 1 dynamic, 2 dynamic + bone (treated as 0); shape 0 sphere, 1 box, 2 capsule */
+    const uint8_t *type, *shape;        /* type 0 follows its bone, 1 dynamic, 2 dynamic + bone (follows like 0 unless rz_physics_aligned); shape 0 sphere, 1 box, 2 capsule */
     const float *size3, *offset_pos3, *offset_rot4;
     const float *mass, *linear_damping, *angular_damping, *restitution, *friction;
     const uint8_t *group;
@@ -629,6 +655,7 @@ int rz_physics_step(rz_ctx *ctx, uint32_t substeps);
 int rz_physics_reset(rz_ctx *ctx);
 int rz_physics_contacts(rz_ctx *ctx, uint32_t on);
 int rz_physics_springs(rz_ctx *ctx, uint32_t on);
+int rz_physics_aligned(rz_ctx *ctx, uint32_t on);
 int rz_read_physics(rz_ctx *ctx, uint32_t instance, float *state13);
 /* Blocking readback of one instance's world matrices (B x 16, column-major) as the frame used them. */
 int rz_read_world(rz_ctx *ctx, uint32_t instance, float *world16);

@@ -23,16 +23,16 @@ SYMBOLS = [
     "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef", "rz_upload_ik",
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
-    "rz_override_follow", "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics",
+    "rz_override_follow", "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics", "rz_physics_aligned",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
 # points, rz_physics_contacts, rz_physics_springs, rz_upload_motion_masks, rz_set_pose_layered, rz_override_follow and the three chain-switch entry
-# points (rz_set_ik_enabled ..), then rz_upload_after_physics — detected by the symbol, the version stayed 8)
+# points (rz_set_ik_enabled ..), then rz_upload_after_physics and rz_physics_aligned — detected by the symbol, the version stayed 8)
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
                     "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
                     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs", "rz_override_follow",
-                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics"}
+                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics", "rz_physics_aligned"}
 POSE_WORLD16, POSE_ROWS12 = 0, 1
 NO_CLIP = 0xffffffff
 NO_MASK = 0xffffffff
@@ -233,6 +233,8 @@ def load(path=None):
         L.rz_physics_contacts.argtypes = [vp, u32]
     if hasattr(L, "rz_physics_springs"):
         L.rz_physics_springs.argtypes = [vp, u32]
+    if hasattr(L, "rz_physics_aligned"):
+        L.rz_physics_aligned.argtypes = [vp, u32]
     if hasattr(L, "rz_override_follow"):
         L.rz_override_follow.argtypes = [vp, u32]
     if hasattr(L, "rz_upload_after_physics"):
@@ -827,6 +829,16 @@ class DeformContext:
         if not hasattr(self._L, "rz_physics_springs"):
             raise RzError(-6, "this build of the library has no rz_physics_springs")
         self._chk(self._L.rz_physics_springs(self._h, 1 if on else 0))
+
+    def physics_aligned(self, on=True):
+        """PMX type-2 bodies ("physics + bone position alignment") of the resident table are simulated (off by default: they follow their
+        bones; include/reze_deform.h states the rules): such a body with a mass and a bone swings like a dynamic one, is put back onto its
+        bone at the start of every physics_step call, and its bone takes the body's rotation and keeps its own animated position. Rebuilds
+        what the upload derived, so like a new upload it turns contacts and linear springs off and resets the simulation: call it right
+        behind upload_physics, ahead of physics_springs and physics_contacts. A new table, skeleton or topology turns it off."""
+        if not hasattr(self._L, "rz_physics_aligned"):
+            raise RzError(-6, "this build of the library has no rz_physics_aligned")
+        self._chk(self._L.rz_physics_aligned(self._h, 1 if on else 0))
 
     def read_physics(self, instance=0):
         """[n_bodies, 13] x3 q4 v3 w3 of one instance (blocking)."""

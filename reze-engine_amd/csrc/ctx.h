@@ -248,6 +248,13 @@ struct RzPhysics {
     rzphys::Kept kept;                  // the columns as uploaded: rz_physics_contacts and rz_physics_springs derive their records from its view()
     std::vector<int> order;             // [nj] the joints' solve order
     double hd = 0.0;                    // h as derived at upload, before its rounding to h
+    // rz_physics_aligned: on = the resident records were derived with the table's type-2 bodies read as dynamic (kept stays the caller's
+    // table); types = the type column as the solver reads it then (what the contact lists derive from), n = the aligned bodies
+    struct Aligned {
+        int on = 0;
+        uint32_t n = 0;
+        std::vector<uint8_t> types;
+    } aligned;
     // the contact stage (rz_physics_contacts): off unless mode; the lists are constants of the resident table
     struct Contacts {
         int mode = 0;                   // 0 off | 1 spheres and capsules | 2 boxes take part as well | 3 and box against box

@@ -356,7 +356,7 @@ struct RzPhysicsParams {
     const float4 *lin;          // [nj]     in solve order: alpha~ x | alpha~ y | alpha~ z | bits(axes with spring_position > 0) (behind the rest, as c_box is)
 };
 // (its LDS: physics_table.h, rzphys::lds_bytes and kLdsLimit)
-hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st);
+hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st, bool aligned = false);   // aligned: the ALIGN instantiations (rz_physics_aligned)
 
 // Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).
 struct RzVariant {

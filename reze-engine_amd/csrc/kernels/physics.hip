@@ -29,8 +29,19 @@
 // angular springs — per axis with spring_position > 0 a compliant constraint on that component of the anchors' offset in A's joint frame.
 // A joint's linear constants are one more float4 (alpha~ x, y, z | bits(axes)) from p.lin and three more multipliers: in registers with
 // the rest under OWN, loaded per visit and kept in LDS ([nj][6] then) otherwise. Without LSPRING the kernel is the code it was.
+// ALIGN (rz_physics_aligned; tests/align_ref.py is its definition): the table has bodies of PMX type 2 that are simulated. Such a body's
+// record carries a flag in word 3's w. load: it takes the state path and is then pinned, once per call — x = the translation of its bone's
+// solved matrix + rot(q (x) offset_q^-1) offset_p, with q, v and w as the state has them. store: its override takes the rotation from the
+// body as every other does, and its translation column is the solved matrix's, copied as one float4. Nothing between the two changes.
+// Without ALIGN the kernel is the code it was. The instantiations are split over two translation units by ALIGN, so that the two halves
+// compile side by side: this file is the ALIGN = false half and rz_launch_physics; kernels/physics_align.hip compiles it again with
+// RZ_PHYSICS_ALIGN defined true and gives rz_launch_physics_aligned_half.
 #include "pass_parts.hip.h"
 #include "../physics_table.h"       // rzphys::lds_bytes: the LDS arithmetic, where the host half's own test program reaches it
+
+#ifndef RZ_PHYSICS_ALIGN
+#define RZ_PHYSICS_ALIGN false
+#endif
 
 namespace {
 
@@ -556,7 +567,22 @@ template <> struct ContactOps<3> : ContactOps<2> {
     static __device__ __forceinline__ void solve(Body &A, Body &B) { solve_contact_all(A, B); }
 };
 
-template <int BLOCK, bool OWN, int CONTACT, bool LSPRING>
+// the rotation of the unit quaternion q, row by row: the arithmetic of the store loop's override, for the re-pin of ALIGN (the store loop keeps
+// its own spelling, as solve_contact keeps its closest-point solve: the existing instantiations stay the instruction streams they were)
+struct M3 { float m00, m01, m02, m10, m11, m12, m20, m21, m22; };
+[[maybe_unused]] __device__ __forceinline__ M3 mat_of(const float4 qb)
+{
+    const float x2 = qb.x + qb.x, y2 = qb.y + qb.y, z2 = qb.z + qb.z;
+    const float xx = qb.x * x2, xy = qb.x * y2, xz = qb.x * z2, yy = qb.y * y2, yz = qb.y * z2, zz = qb.z * z2;
+    const float wx = qb.w * x2, wy = qb.w * y2, wz = qb.w * z2;
+    M3 m;
+    m.m00 = 1.0f - (yy + zz); m.m01 = xy - wz; m.m02 = xz + wy;
+    m.m10 = xy + wz; m.m11 = 1.0f - (xx + zz); m.m12 = yz - wx;
+    m.m20 = xz - wy; m.m21 = yz + wx; m.m22 = 1.0f - (xx + yy);
+    return m;
+}
+
+template <int BLOCK, bool OWN, int CONTACT, bool LSPRING, bool ALIGN>
 __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams p)
 {
     extern __shared__ float4 ph_lds[];
@@ -588,6 +614,15 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
             v = w = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         } else {
             x = state[4 * b]; q = state[4 * b + 1]; v = state[4 * b + 2]; w = state[4 * b + 3];
+            if constexpr (ALIGN) {
+                // an aligned body (it has a bone: physics_table.h) goes back onto its bone, once per call: the solved bone position + R offset_p
+                if (b3.w != 0.0f) {
+                    const float4 c3 = reinterpret_cast<const float4 *>(world + (size_t)bone * 16)[3];
+                    const M3 m = mat_of(qmul(q, qconj(b1)));
+                    x = make_float4(c3.x + (m.m00 * b0.x + m.m01 * b0.y + m.m02 * b0.z), c3.y + (m.m10 * b0.x + m.m11 * b0.y + m.m12 * b0.z),
+                                    c3.z + (m.m20 * b0.x + m.m21 * b0.y + m.m22 * b0.z), 0.0f);
+                }
+            }
         }
         sx[b] = x; sq[b] = q; sv[b] = v; sw[b] = w;
     }
@@ -698,17 +733,23 @@ __global__ void __launch_bounds__(BLOCK) rz_physics_kernel(const RzPhysicsParams
             o[0] = make_float4(m00, m10, m20, 0.0f);
             o[1] = make_float4(m01, m11, m21, 0.0f);
             o[2] = make_float4(m02, m12, m22, 0.0f);
-            o[3] = make_float4(tx, ty, tz, 1.0f);
+            if constexpr (ALIGN) {
+                // an aligned body's bone stays where the hierarchy solve put it: that matrix's own translation column, bit for bit
+                if (b3.w != 0.0f) o[3] = reinterpret_cast<const float4 *>(world + (size_t)__float_as_uint(b3.y) * 16)[3];
+                else o[3] = make_float4(tx, ty, tz, 1.0f);
+            } else {
+                o[3] = make_float4(tx, ty, tz, 1.0f);
+            }
         }
     }
 }
 
 #pragma clang fp contract(fast)
 
-template <int BLOCK, bool OWN, int CONTACT, bool LSPRING>
+template <int BLOCK, bool OWN, int CONTACT, bool LSPRING, bool ALIGN>
 hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
 {
-    auto k = rz_physics_kernel<BLOCK, OWN, CONTACT, LSPRING>;
+    auto k = rz_physics_kernel<BLOCK, OWN, CONTACT, LSPRING, ALIGN>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -717,24 +758,37 @@ hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipS
     return hipGetLastError();
 }
 
+// this unit's half of the launcher table: one instantiation per (LSPRING, block, OWN, CONTACT) with ALIGN = RZ_PHYSICS_ALIGN
+hipError_t launch_half(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
+{
+    using Launch = hipError_t (*)(const RzPhysicsParams &, uint32_t, size_t, hipStream_t);
+#define RZ_PH_ROW(B, O, L) { launch<B, O, 0, L, RZ_PHYSICS_ALIGN>, launch<B, O, 1, L, RZ_PHYSICS_ALIGN>, launch<B, O, 2, L, RZ_PHYSICS_ALIGN>, launch<B, O, 3, L, RZ_PHYSICS_ALIGN> }
+    static const Launch table[2][2][2][4] = {
+        {{RZ_PH_ROW(64, false, false), RZ_PH_ROW(64, true, false)}, {RZ_PH_ROW(256, false, false), RZ_PH_ROW(256, true, false)}},
+        {{RZ_PH_ROW(64, false, true), RZ_PH_ROW(64, true, true)}, {RZ_PH_ROW(256, false, true), RZ_PH_ROW(256, true, true)}}};
+#undef RZ_PH_ROW
+    return table[p.lin != nullptr][p.block == 256][p.nj <= p.block][p.contacts](p, instances, lds, st);
+}
+
 }  // namespace
 
-hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st)
+#if RZ_PHYSICS_ALIGN
+// the ALIGN = true half, for rz_launch_physics in the other unit, which has checked p
+hipError_t rz_launch_physics_aligned_half(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st) { return launch_half(p, instances, lds, st); }
+#else
+hipError_t rz_launch_physics_aligned_half(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st);      // kernels/physics_align.hip
+
+hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st, bool aligned)
 {
     if (p.nb <= 0 || instances == 0 || (p.block != 64 && p.block != 256)) return hipErrorInvalidValue;
-    const bool own = p.nj <= p.block, springs = p.lin != nullptr;
-    const size_t lds = rzphys::lds_bytes(p.nb, p.nj, p.block, springs);
+    const size_t lds = rzphys::lds_bytes(p.nb, p.nj, p.block, p.lin != nullptr);
     if (lds > rzphys::kLdsLimit) return hipErrorInvalidValue;
     if (p.contacts) {
         if (!p.c_shape || !p.c_follow_off || !p.c_follow_idx || !p.c_pair || !p.c_colour_off || p.c_ncol < 0) return hipErrorInvalidValue;
         if (p.contacts == 2 || p.contacts == 3 ? !p.c_box : p.contacts != 1) return hipErrorInvalidValue;
     }
-    // one instantiation per (block, OWN, CONTACT, LSPRING)
-    using Launch = hipError_t (*)(const RzPhysicsParams &, uint32_t, size_t, hipStream_t);
-#define RZ_PH_ROW(B, O, L) { launch<B, O, 0, L>, launch<B, O, 1, L>, launch<B, O, 2, L>, launch<B, O, 3, L> }
-    static const Launch table[2][2][2][4] = {
-        {{RZ_PH_ROW(64, false, false), RZ_PH_ROW(64, true, false)}, {RZ_PH_ROW(256, false, false), RZ_PH_ROW(256, true, false)}},
-        {{RZ_PH_ROW(64, false, true), RZ_PH_ROW(64, true, true)}, {RZ_PH_ROW(256, false, true), RZ_PH_ROW(256, true, true)}}};
-#undef RZ_PH_ROW
-    return table[springs][p.block == 256][own][p.contacts](p, instances, lds, st);
+    // aligned: the table has at least one aligned body
+    if (aligned && !p.world) return hipErrorInvalidValue;
+    return aligned ? rz_launch_physics_aligned_half(p, instances, lds, st) : launch_half(p, instances, lds, st);
 }
+#endif

@@ -482,6 +482,18 @@ static napi_value fn_physics_springs(napi_env env, napi_callback_info info)
     return rc ? throw_rz(env, rc) : undef(env);
 }
 
+/* physicsAligned(ctx, on): rz_physics_aligned — the resident table's PMX type-2 bodies are simulated and their bones keep their animated
+ * positions, 1 on / 0 off; like a new upload it turns springs and contacts off and resets the simulation */
+static napi_value fn_physics_aligned(napi_env env, napi_callback_info info)
+{
+    ARGS(2);
+    CTX(0);
+    uint32_t on;
+    if (!get_u32(env, argv[1], &on) || on > 1) return throw_msg(env, "physicsAligned(ctx, on): on is 0 or 1");
+    int rc = rz_physics_aligned(ctx, on);
+    return rc ? throw_rz(env, rc) : undef(env);
+}
+
 /* overrideFollow(ctx, on): rz_override_follow — bones below an overridden bone follow it (overrideWorld's sets and the physics table's), 1 on / 0 off */
 static napi_value fn_override_follow(napi_env env, napi_callback_info info)
 {
@@ -1375,7 +1387,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "autotune", fn_autotune }, { "autotuneMeasure", fn_autotune_measure }, { "autotunePick", fn_autotune_pick }, { "autotuneApply", fn_autotune_apply }, { "commInfo", fn_comm_info }, { "uploadAnimation", fn_upload_animation }, { "setPoseSampled", fn_set_pose_sampled }, { "uploadMotions", fn_upload_motions }, { "setPoseBlended", fn_set_pose_blended }, { "uploadMotionMasks", fn_upload_motion_masks }, { "setPoseLayered", fn_set_pose_layered }, { "overrideWorld", fn_override_world }, { "uploadBoneMorphs", fn_upload_bone_morphs }, { "fork", fn_fork }, { "deformPair", fn_deform_pair }, { "gatherDirect", fn_gather_direct }, { "gatherFence", fn_gather_fence },
         { "instanceRange", fn_instance_range }, { "mapPose", fn_map_pose }, { "commitPose", fn_commit_pose }, { "timeSpan", fn_time_span },
         { "uploadSdef", fn_upload_sdef }, { "uploadQdef", fn_upload_qdef }, { "uploadIK", fn_upload_ik },
-        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "overrideFollow", fn_override_follow }, { "uploadAfterPhysics", fn_upload_after_physics }, { "uploadIKKeys", fn_upload_ik_keys }, { "setIKEnabled", fn_set_ik_enabled }, { "readIKEnabled", fn_read_ik_enabled },{ "readPhysics", fn_read_physics },
+        { "uploadPhysics", fn_upload_physics }, { "physicsStep", fn_physics_step }, { "physicsReset", fn_physics_reset }, { "physicsContacts", fn_physics_contacts }, { "physicsSprings", fn_physics_springs }, { "physicsAligned", fn_physics_aligned }, { "overrideFollow", fn_override_follow }, { "uploadAfterPhysics", fn_upload_after_physics }, { "uploadIKKeys", fn_upload_ik_keys }, { "setIKEnabled", fn_set_ik_enabled }, { "readIKEnabled", fn_read_ik_enabled },{ "readPhysics", fn_read_physics },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value f;

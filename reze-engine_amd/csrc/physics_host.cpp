@@ -98,10 +98,53 @@ static int step(rz_ctx *c, uint32_t substeps, bool reset)
     const int r = launch_fk(c, st);
     c->ovr_count = saved;
     if (r) return r;
-    HIP_TRY(rz_launch_physics(physics_params(c, substeps, reset), c->I, st));
+    HIP_TRY(rz_launch_physics(physics_params(c, substeps, reset), c->I, st, c->ph.aligned.n != 0));
     c->ph.reset = false;
     c->ovr_count = c->I * c->ph.nd;
     if (c->ovr_count) c->fk_stale = true;       // world matrices and palettes in memory are the un-overridden solve's: rz_read_world / rz_read_palette solve again
+    return RZ_OK;
+}
+
+// A table's way into the context, for rz_upload_physics and rz_physics_aligned alike: checked, coloured and built first (physics_table.h:
+// derive) — a refusal leaves the context as it was — then the old table goes and the new one moves in with contacts and linear springs off
+// and a reset pending. aligned: the table's type-2 bodies with a mass are read as dynamic, those with a bone flagged; `kept` stays the
+// table as the caller gave it. `given` may point into c->ph.kept: it is copied before the old table goes.
+static int install(rz_ctx *c, const rz_physics *given, bool aligned)
+{
+    std::vector<int32_t> parents(c->B);
+    std::vector<float> bind((size_t)c->B * 3);
+    for (uint32_t b = 0; b < c->B; ++b) {
+        parents[b] = (int32_t)c->fk_host[4 * b].x;
+        memcpy(&bind[(size_t)b * 3], &c->fk_host[4 * b + 1], 12);
+    }
+    rzphys::Derived d;
+    std::string bad;
+    if (int r = rzphys::derive(given, c->B, parents.data(), bind.data(), aligned, d, bad)) return fail(r, "%s", bad.c_str());
+    const rzphys::Built &o = d.built;
+    RzPhysics::Aligned al;
+    al.on = aligned ? 1 : 0;
+    al.n = d.n_aligned;
+    al.types = std::move(d.types);
+    rzphys::Kept kept;
+    kept.keep(given);
+    if (int r = drain(c)) return r;
+    free_physics(c);
+    drop_graph(c);
+    c->ovr_count = 0;                   // hand-fed overrides end here: the table is physics' own from now on
+    // (the old table has gone, as it always had by here: a failed allocation leaves the context without one)
+    RzPhysics ph;
+    if (int r = to_device(&ph.body.p, o.body.data(), (size_t)o.nb * 4)) return r;
+    if (int r = to_device(&ph.joint.p, o.joint.data(), (size_t)o.nj * 8)) return r;
+    if (int r = to_device(&ph.colour_off.p, o.colour_off.data(), o.colour_off.size())) return r;
+    ph.nb = (uint32_t)o.nb; ph.nj = (uint32_t)o.nj; ph.ncol = (uint32_t)o.ncol; ph.nd = (uint32_t)o.nd;
+    ph.iterations = o.iterations; ph.h = o.h; ph.hd = o.hd;
+    for (int k = 0; k < 3; ++k) ph.g[k] = o.g[k];
+    ph.block = rzphys::block_for(o.nb, o.widest);
+    ph.dyn_bone = o.dyn_bone;
+    ph.order = o.order;
+    ph.kept = std::move(kept);
+    ph.aligned = std::move(al);
+    c->ph = std::move(ph);
     return RZ_OK;
 }
 
@@ -121,38 +164,18 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
     }
     if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
         return fail(RZ_ERR_INVALID, "rz_upload_physics needs the hierarchy: call rz_upload_skeleton_topology first");
-    std::string bad = rzphys::validate(t, c->B);
-    if (!bad.empty()) return fail(RZ_ERR_INVALID, "%s", bad.c_str());
-    bad = rzphys::upload_refusal(t->n_bodies, t->n_joints, nullptr);
-    if (!bad.empty()) return fail(RZ_ERR_UNSUPPORTED, "%s", bad.c_str());
-    std::vector<int32_t> parents(c->B);
-    std::vector<float> bind((size_t)c->B * 3);
-    for (uint32_t b = 0; b < c->B; ++b) {
-        parents[b] = (int32_t)c->fk_host[4 * b].x;
-        memcpy(&bind[(size_t)b * 3], &c->fk_host[4 * b + 1], 12);
-    }
-    rzphys::Built o;
-    rzphys::build(t, c->B, parents.data(), bind.data(), o);
-    bad = rzphys::upload_refusal(t->n_bodies, t->n_joints, &o);
-    if (!bad.empty()) return fail(RZ_ERR_UNSUPPORTED, "%s", bad.c_str());
-    if (int r = drain(c)) return r;
-    free_physics(c);
-    drop_graph(c);
-    c->ovr_count = 0;                   // hand-fed overrides end here: the table is physics' own from now on
-    // (the old table has gone, as it always had by here: a failed allocation leaves the context without one)
-    RzPhysics ph;
-    if (int r = to_device(&ph.body.p, o.body.data(), (size_t)o.nb * 4)) return r;
-    if (int r = to_device(&ph.joint.p, o.joint.data(), (size_t)o.nj * 8)) return r;
-    if (int r = to_device(&ph.colour_off.p, o.colour_off.data(), o.colour_off.size())) return r;
-    ph.nb = (uint32_t)o.nb; ph.nj = (uint32_t)o.nj; ph.ncol = (uint32_t)o.ncol; ph.nd = (uint32_t)o.nd;
-    ph.iterations = o.iterations; ph.h = o.h; ph.hd = o.hd;
-    for (int k = 0; k < 3; ++k) ph.g[k] = o.g[k];
-    ph.block = rzphys::block_for(o.nb, o.widest);
-    ph.dyn_bone = o.dyn_bone;
-    ph.order = o.order;
-    ph.kept.keep(t);
-    c->ph = std::move(ph);
-    return RZ_OK;
+    return install(c, t, false);
+}
+
+int rz_physics_aligned(rz_ctx *c, uint32_t on)
+{
+    if (int r = use(c)) return r;
+    if (int r = physics_usable(c, "rz_physics_aligned")) return r;
+    if (int r = static_unlocked(c, "rz_physics_aligned")) return r;
+    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+        return fail(RZ_ERR_INVALID, "rz_physics_aligned needs the hierarchy: call rz_upload_skeleton_topology first");
+    const rz_physics t = c->ph.kept.view();
+    return install(c, &t, on != 0);
 }
 
 int rz_physics_step(rz_ctx *c, uint32_t substeps)
@@ -175,7 +198,8 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
         return RZ_OK;
     }
     const int mode = on == 2 || on == 3 ? (int)on : 1;    // (every other nonzero value is 1, as it always was)
-    const rz_physics t = c->ph.kept.view();
+    rz_physics t = c->ph.kept.view();
+    if (c->ph.aligned.on) t.type = c->ph.aligned.types.data();       // rz_physics_aligned: the aligned bodies are dynamic to the lists too
     if (!t.group || !t.mask || !t.friction || !t.size3)
         return fail(RZ_ERR_INVALID, "rz_physics_contacts: the resident table was uploaded without%s%s%s%s: contacts need group, mask, friction and size3",
                     !t.group ? " group" : "", !t.mask ? " mask" : "", !t.friction ? " friction" : "", !t.size3 ? " size3" : "");

@@ -33,6 +33,24 @@ struct Built {
 
 inline bool dynamic(const rz_physics *t, uint32_t b) { return t->type[b] == 1 && t->mass[b] > 0.0f; }
 
+// rz_physics_aligned (tests/align_ref.py): with the feature on, a type-2 body with mass > 0 is simulated — read as type 1 —, and ALIGNED when
+// it has a bone as well: its bone takes the body's rotation and keeps its own solved position. `types` becomes the table's type column as
+// the solver reads it, `aligned` the per-body flag; the count of aligned bodies is returned. Off: the column as it is, no flag, 0.
+inline uint32_t read_types(const rz_physics *t, bool on, std::vector<uint8_t> &types, std::vector<uint8_t> &aligned)
+{
+    const uint32_t nb = t->n_bodies;
+    types.assign(t->type, t->type + nb);
+    aligned.assign(nb, 0);
+    uint32_t n = 0;
+    if (on)
+        for (uint32_t b = 0; b < nb; ++b)
+            if (t->type[b] == 2 && t->mass[b] > 0.0f) {
+                types[b] = 1;
+                if (t->bone[b] >= 0) { aligned[b] = 1; ++n; }
+            }
+    return n;
+}
+
 inline bool finite_all(const float *p, size_t n)
 {
     if (!p) return true;
@@ -139,8 +157,9 @@ inline D4 quat_from_pmx_euler(const float *r)
 inline float bits_of(int32_t v) { float f; memcpy(&f, &v, 4); return f; }
 
 // parents[B] (-1 = root) and bind_translation3[B * 3]: the topology the hierarchy solve was given; the bind pose of a body is
-// T(sum of the bind translations up its bone's parent chain) x offset
-inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const float *bind3, Built &o)
+// T(sum of the bind translations up its bone's parent chain) x offset. aligned (read_types; null = none): the bodies whose record carries
+// the flag in its 16th float, 1.0f; t's type column is then the one read_types made.
+inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const float *bind3, Built &o, const uint8_t *aligned = nullptr)
 {
     const uint32_t nb = t->n_bodies, nj = t->n_joints;
     o.nb = (int)nb; o.nj = (int)nj;
@@ -182,7 +201,7 @@ inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const
         for (int k = 0; k < 3; ++k) r[8 + k] = I[k] > 0 ? (float)(1.0 / I[k]) : 0.0f;
         r[11] = (float)std::pow(1.0 - (double)t->linear_damping[b], h);
         r[12] = (float)std::pow(1.0 - (double)t->angular_damping[b], h);
-        r[13] = bits_of(t->bone[b]); r[14] = bits_of(slot); r[15] = 0.0f;
+        r[13] = bits_of(t->bone[b]); r[14] = bits_of(slot); r[15] = aligned && aligned[b] ? 1.0f : 0.0f;
     }
     o.nd = (int)o.dyn_bone.size();
     o.joint.assign((size_t)nj * 32, 0.0f);
@@ -210,27 +229,45 @@ inline void build(const rz_physics *t, uint32_t B, const int32_t *parents, const
     }
 }
 
-// The columns of an uploaded table that later stages derive from (rz_physics_contacts: contact_table.h; rz_physics_springs: build_linear),
-// owned. view() is that table again: its pointers are these vectors, or null where the column was not uploaded (or has no element).
+// An uploaded table, owned: what later stages derive from (rz_physics_contacts: contact_table.h; rz_physics_springs: build_linear;
+// rz_physics_aligned: the whole of build again). view() is that table again: its pointers are these vectors, or null where the column was
+// not uploaded (or has no element).
 struct Kept {
-    uint32_t n_bodies = 0, n_joints = 0;
+    uint32_t n_bodies = 0, n_joints = 0, iterations = 0;
+    float h = 0.0f;
     std::vector<uint8_t> type, shape, group;
     std::vector<uint16_t> mask;
+    std::vector<int32_t> bone;
+    std::vector<uint32_t> body_a, body_b;
     std::vector<float> size3, mass, friction, spring_position3;
+    std::vector<float> offset_pos3, offset_rot4, linear_damping, angular_damping, restitution, gravity3;
+    std::vector<float> position3, rotation3, position_min3, position_max3, rotation_min3, rotation_max3, spring_rotation3;
 
     void keep(const rz_physics *t)
     {
         const size_t nb = n_bodies = t->n_bodies, nj = n_joints = t->n_joints;
+        h = t->h; iterations = t->iterations;
         copy(type, t->type, nb); copy(shape, t->shape, nb); copy(group, t->group, nb); copy(mask, t->mask, nb);
         copy(size3, t->size3, nb * 3); copy(mass, t->mass, nb); copy(friction, t->friction, nb); copy(spring_position3, t->spring_position3, nj * 3);
+        copy(bone, t->bone, nb); copy(offset_pos3, t->offset_pos3, nb * 3); copy(offset_rot4, t->offset_rot4, nb * 4);
+        copy(linear_damping, t->linear_damping, nb); copy(angular_damping, t->angular_damping, nb); copy(restitution, t->restitution, nb);
+        copy(gravity3, t->gravity3, 3);
+        copy(body_a, t->body_a, nj); copy(body_b, t->body_b, nj); copy(position3, t->position3, nj * 3); copy(rotation3, t->rotation3, nj * 3);
+        copy(position_min3, t->position_min3, nj * 3); copy(position_max3, t->position_max3, nj * 3);
+        copy(rotation_min3, t->rotation_min3, nj * 3); copy(rotation_max3, t->rotation_max3, nj * 3); copy(spring_rotation3, t->spring_rotation3, nj * 3);
     }
     rz_physics view() const
     {
         rz_physics t;
         memset(&t, 0, sizeof t);
-        t.n_bodies = n_bodies; t.n_joints = n_joints;
+        t.n_bodies = n_bodies; t.n_joints = n_joints; t.h = h; t.iterations = iterations;
         t.type = ptr(type); t.shape = ptr(shape); t.group = ptr(group); t.mask = ptr(mask);
         t.size3 = ptr(size3); t.mass = ptr(mass); t.friction = ptr(friction); t.spring_position3 = ptr(spring_position3);
+        t.bone = ptr(bone); t.offset_pos3 = ptr(offset_pos3); t.offset_rot4 = ptr(offset_rot4);
+        t.linear_damping = ptr(linear_damping); t.angular_damping = ptr(angular_damping); t.restitution = ptr(restitution); t.gravity3 = ptr(gravity3);
+        t.body_a = ptr(body_a); t.body_b = ptr(body_b); t.position3 = ptr(position3); t.rotation3 = ptr(rotation3);
+        t.position_min3 = ptr(position_min3); t.position_max3 = ptr(position_max3);
+        t.rotation_min3 = ptr(rotation_min3); t.rotation_max3 = ptr(rotation_max3); t.spring_rotation3 = ptr(spring_rotation3);
         return t;
     }
 
@@ -309,6 +346,35 @@ inline std::string upload_refusal(uint32_t n_bodies, uint32_t n_joints, const Bu
     snprintf(m, sizeof m, "physics table too large for the device solver: %u bodies and %u joints need %zu B of LDS (96 B per body, + 12 B per joint once the joints outnumber the %d lanes; the limit is 160 KB)",
              n_bodies, n_joints, lds, block);
     return m;
+}
+
+// Everything rz_upload_physics (aligned = false) and rz_physics_aligned derive from a table without the GPU, in the order the host owes:
+// the table as given is checked, its types are read (read_types), with the feature on the table as read is checked again — two bodies that
+// are dynamic now may drive one bone —, it is coloured and built, and the launch form the new colouring selects is held to the LDS limit.
+// 0, or RZ_ERR_INVALID / RZ_ERR_UNSUPPORTED with `bad` the message; nothing of `o` is to be used then.
+struct Derived {
+    Built built;
+    std::vector<uint8_t> types;         // the type column as the solver reads it
+    std::vector<uint8_t> flags;         // per body: aligned
+    uint32_t n_aligned = 0;
+};
+inline int derive(const rz_physics *given, uint32_t B, const int32_t *parents, const float *bind3, bool aligned, Derived &o, std::string &bad)
+{
+    bad = validate(given, B);
+    if (!bad.empty()) return RZ_ERR_INVALID;
+    bad = upload_refusal(given->n_bodies, given->n_joints, nullptr);
+    if (!bad.empty()) return RZ_ERR_UNSUPPORTED;
+    o.n_aligned = read_types(given, aligned, o.types, o.flags);
+    rz_physics read = *given;
+    read.type = o.types.data();
+    if (aligned) {
+        bad = validate(&read, B);
+        if (!bad.empty()) { bad = "rz_physics_aligned: " + bad; return RZ_ERR_INVALID; }
+    }
+    build(&read, B, parents, bind3, o.built, o.n_aligned ? o.flags.data() : nullptr);
+    bad = upload_refusal(given->n_bodies, given->n_joints, &o.built);
+    if (!bad.empty()) { if (aligned) bad = "rz_physics_aligned: " + bad; return RZ_ERR_UNSUPPORTED; }
+    return 0;
 }
 
 }  // namespace rzphys

@@ -264,6 +264,8 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "physics_contact_box_box")) *value = (int)c->ph.contacts.box_box;
     else if (!strcmp(key, "physics_springs")) *value = c->ph.springs.on;
     else if (!strcmp(key, "physics_spring_axes")) *value = (int)c->ph.springs.axes;
+    else if (!strcmp(key, "physics_aligned")) *value = c->ph.aligned.on;
+    else if (!strcmp(key, "physics_aligned_bodies")) *value = (int)c->ph.aligned.n;
     else if (!strcmp(key, "physics_lds")) *value = c->ph.nb ? (int)rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0;
     else if (!strcmp(key, "override_follow")) *value = c->ovr_follow;
     else if (!strcmp(key, "override_followers")) *value = follow_params(c).off ? (int)c->fol_count : 0;     // entries resident over all instances

@@ -75,6 +75,10 @@ class Engine {
     // upload and ahead of the contacts
     this.physicsSprings = o.physicsSprings === true
     if (this.physicsSprings && !this.devicePhysics) throw new Error('physicsSprings needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
+    // physicsAligned: the table's PMX type-2 bodies are simulated and their bones keep their animated positions (rz_physics_aligned), enabled
+    // on every shard right behind the table's upload, ahead of the springs and the contacts (it rebuilds what the upload derived)
+    this.physicsAligned = o.physicsAligned === true
+    if (this.physicsAligned && !this.devicePhysics) throw new Error('physicsAligned needs new Engine(canvas, { deviceFK: true, devicePhysics: true })')
     // followOverrides: bones below an overridden bone follow it (rz_override_follow; the definition is tests/follow_ref.py), for the
     // overrides devicePhysics writes and for those fed through setBoneWorldOverrides; set on every shard behind the topology upload, and
     // on every fork. The stage is the device hierarchy solve's: host FK users call Model.followOverrides from their { physics } hook.
@@ -291,6 +295,7 @@ class Engine {
         // so is physics: every shard simulates the same bodies (the solve is deterministic), so no shard waits for another's overrides
         if (tables && tables.nBodies > 0) {
           n.uploadPhysics(s.ctx, tables)
+          if (this.physicsAligned) n.physicsAligned(s.ctx, 1)
           if (this.physicsSprings) n.physicsSprings(s.ctx, 1)
           if (this.physicsContacts) n.physicsContacts(s.ctx, this.physicsContacts === 'all' ? 3 : this.physicsContacts === 'boxes' ? 2 : 1)
           this.physicsResident = true

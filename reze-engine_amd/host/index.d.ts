@@ -48,6 +48,7 @@ export interface EngineOptions {
   physics?: { step(dt: number, boneWorldMatrices: Float32Array, boneInverseBindMatrices: Float32Array): void }
   /** Rigid-body physics on the GPU for the model's PMX bodies and joints (needs deviceFK; exclusive with `physics` and framesInFlight: 2). loadModel uploads Model.physicsTables() (rz_upload_physics); every frame turns the time the clock advanced since the last one into min(10, floor(accumulated / h)) fixed substeps of h = 1/75 s (rz_physics_step) before it deforms. No restitution; contacts (physicsContacts) and the joints' linear springs (physicsSprings) are opt-in. */ devicePhysics?: boolean
   /** With devicePhysics: contacts and friction between the model's sphere and capsule bodies by their PMX groups and masks (rz_physics_contacts, called on every shard right after the table's upload at loadModel). Off by default; without devicePhysics it throws. true: boxes take no part. 'boxes': the model's box bodies collide with its spheres and capsules as well (rz_physics_contacts(ctx, 2)); a pair of two boxes is still left out. 'all': pairs of two boxes collide too (rz_physics_contacts(ctx, 3)). */ physicsContacts?: boolean | 'boxes' | 'all'
+  /** With devicePhysics: the model's PMX type-2 bodies ("physics + bone position alignment") are simulated instead of following their bones (rz_physics_aligned, called on every shard right after the table's upload at loadModel, ahead of physicsSprings and physicsContacts): such a body swings like a dynamic one, and its bone takes the rotation and keeps its animated position. Off by default; without devicePhysics it throws. */ physicsAligned?: boolean
   /** With devicePhysics: the linear springs of the model's joints (PMX spring_position; rz_physics_springs, called on every shard right after the table's upload at loadModel, ahead of physicsContacts): a joint with play along an axis and a spring on it swings about its rest point instead of hanging at the end of its play. Off by default; without devicePhysics it throws. */ physicsSprings?: boolean
   /** With deviceFK: bones below an overridden bone follow it (rz_override_follow, called on every shard and fork behind the topology upload) — W_b = O_a (S_a^-1 S_b) with a the nearest overridden ancestor of b, S the solved pose; for the overrides devicePhysics writes and for those of setBoneWorldOverrides. A strand's tip bone without a body, an ornament on a hair bone, the sub-bone of a skirt plate then ride the physics bone instead of staying with the animation. Not re-evaluated on the followed pose: append transforms, IK chains, following bodies. Off by default; without deviceFK it throws (host FK: call Model.followOverrides(world, bones, matrices) from the { physics } hook). */ followOverrides?: boolean
   /** With deviceFK: the model's PMX after-physics bones (flag 0x1000) are solved again behind the overrides, from the final pose of the bones they read (rz_upload_after_physics, called on every shard behind the topology upload and behind the IK table; forks borrow the list) — a skirt aid that takes half the rotation of a physics bone, a support bone that appends from a sprung body's bone then see the simulated pose. Evaluation order: Model.afterPhysicsOrder() (transform level, then index; it throws on a bone listed before a bone it reads). Off by default; without deviceFK it throws (host FK: call Model.solveAfterPhysics(world, overriddenBones) at the end of the { physics } hook). */ afterPhysics?: boolean

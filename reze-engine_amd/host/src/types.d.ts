@@ -136,6 +136,7 @@ export interface DeformAddon {
   physicsReset(ctx: DeformContext): void
   physicsContacts(ctx: DeformContext, on: 0 | 1 | 2 | 3): void
   physicsSprings(ctx: DeformContext, on: 0 | 1): void
+  physicsAligned(ctx: DeformContext, on: 0 | 1): void
   overrideFollow(ctx: DeformContext, on: 0 | 1): void
   uploadAfterPhysics(ctx: DeformContext, bones: Uint32Array): void
   uploadIKKeys(ctx: DeformContext, clip: number | null, frames: Float32Array | null, enabled?: Uint8Array | null): void
@@ -204,7 +205,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; followOverrides?: boolean; afterPhysics?: boolean; ikKeys?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; physicsAligned?: boolean; followOverrides?: boolean; afterPhysics?: boolean; ikKeys?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }
