@@ -112,8 +112,23 @@ int rz_upload_skeleton(rz_ctx *ctx, uint32_t B, const float *inverse_bind16);
  * morph section, engine/src/pmx-loader.ts:450-553). Dense: deltas[M][V][3] for this shard.
  * Sparse: PMX on-disk form (pmx-loader.ts:483-488) — morph m owns entries
  * [morph_off[m], morph_off[m+1]) of (vert_idx relative to this shard, delta xyz).
- * Passing M = 0 removes morphs. */
+ * Passing M = 0 removes morphs.
+ * Dense STORAGE: by default each delta is kept as a signed 24-bit integer times one power-of-two scale per morph (9 B per vertex and
+ * morph instead of 12 — the dense frame is bound by exactly this stream). Per morph E = the binary exponent of its largest |delta| over
+ * this shard, s = 2^(E - 22), q = rint(d / s) (E + 1 when the maximum would round to 2^23; an all-zero morph: s = 1): the stored value
+ * q * s differs from d by at most 2^(E - 23), that is max|d| * 2^-23 (a hair more, 1 + 2^-24 of it, for a raised E), below what one fmaf into the position rounds away. Four values take three
+ * dwords (d0 = q0 | q1[7:0] << 24, d1 = q1[23:8] | q2[15:0] << 16, d2 = q2[23:16] | q3 << 8). The scale belongs to the context: two
+ * shards may scale one morph differently, which is harmless — a vertex lives in one shard. A set with a non-finite delta, or an exponent
+ * outside [-64, 64], is stored as fp32 planes, whole. rz_upload_morphs_dense_ex(.., RZ_MORPH_F32) asks for fp32 planes: the frames then
+ * compute what they computed before 24-bit storage existed, bit for bit. rz_get_tuning("effective_morph_storage") = 24 or 32.
+ * rz_read_morph_dense: the resident (decoded) deltas of morph m as three planes [3][V] — for tests.
+ * rz_morph_encode24: the encoder alone, on the host, no device involved: scales[M] and, when packed is not NULL, the planes
+ * [M][3][ceil(V / 4) * 12 bytes]; *storage = 24, or 32 when the set would stay fp32 (nothing else is written then). */
+#define RZ_MORPH_F32 1u
 int rz_upload_morphs_dense(rz_ctx *ctx, uint32_t M, const float *deltas);
+int rz_upload_morphs_dense_ex(rz_ctx *ctx, uint32_t M, const float *deltas, uint32_t flags);
+int rz_read_morph_dense(rz_ctx *ctx, uint32_t m, float *planes3);
+int rz_morph_encode24(const float *deltas, uint32_t M, uint32_t V, uint8_t *packed, float *scales, int *storage);
 int rz_upload_morphs_sparse(rz_ctx *ctx, uint32_t M, const uint32_t *morph_off,
                             const uint32_t *vert_idx, const float *delta3);
 

@@ -24,6 +24,7 @@ SYMBOLS = [
     "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs",
     "rz_override_follow", "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics", "rz_physics_aligned",
+    "rz_upload_morphs_dense_ex", "rz_read_morph_dense", "rz_morph_encode24",
 ]
 # symbols a library older than the current ABI lacks (ABI 5: rz_gather_chunk; 6: rz_device_numa_node; 7: rz_instance_range ..
 # rz_time_span; 8: rz_upload_sdef, later rz_upload_ik, rz_upload_qdef, rz_upload_motions, rz_set_pose_blended, the four physics entry
@@ -32,8 +33,25 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = {"rz_gather_chunk", "rz_device_numa_node", "rz_instance_range", "rz_map_pose", "rz_commit_pose", "rz_time_span", "rz_upload_sdef",
                     "rz_upload_ik", "rz_upload_qdef", "rz_upload_motions", "rz_set_pose_blended", "rz_upload_motion_masks", "rz_set_pose_layered",
                     "rz_upload_physics", "rz_physics_step", "rz_physics_reset", "rz_read_physics", "rz_physics_contacts", "rz_physics_springs", "rz_override_follow",
-                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics", "rz_physics_aligned"}
+                    "rz_set_ik_enabled", "rz_upload_ik_keys", "rz_read_ik_enabled", "rz_upload_after_physics", "rz_physics_aligned",
+                    "rz_upload_morphs_dense_ex", "rz_read_morph_dense", "rz_morph_encode24"}       # (24-bit dense morph storage)
 POSE_WORLD16, POSE_ROWS12 = 0, 1
+MORPH_F32 = 1       # upload_morphs_dense(storage=): fp32 planes instead of the default 24-bit storage
+
+
+def morph_encode24(deltas):
+    """The library's 24-bit dense morph encoder on the host (no device): (storage, scales[M], packed[M, 3, ceil(V / 4) * 12] uint8 or None)."""
+    d = _f32(deltas)
+    assert d.ndim == 3 and d.shape[2] == 3, d.shape
+    M, V = d.shape[0], d.shape[1]
+    L = load()
+    packed = np.zeros((M, 3, (V + 3) // 4 * 12), dtype=np.uint8)
+    scales = np.zeros(M, dtype=np.float32)
+    storage = ctypes.c_int(0)
+    rc = L.rz_morph_encode24(_fptr(d), M, V, packed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _fptr(scales), ctypes.byref(storage))
+    if rc != 0:
+        raise RzError(rc, (L.rz_last_error() or b"").decode())
+    return storage.value, (scales if storage.value == 24 else None), (packed if storage.value == 24 else None)
 NO_CLIP = 0xffffffff
 NO_MASK = 0xffffffff
 MAX_MOTION_LAYERS = 4
@@ -237,6 +255,10 @@ def load(path=None):
         L.rz_physics_aligned.argtypes = [vp, u32]
     if hasattr(L, "rz_override_follow"):
         L.rz_override_follow.argtypes = [vp, u32]
+    if hasattr(L, "rz_upload_morphs_dense_ex"):
+        L.rz_upload_morphs_dense_ex.argtypes = [vp, u32, fp, u32]
+        L.rz_read_morph_dense.argtypes = [vp, u32, fp]
+        L.rz_morph_encode24.argtypes = [fp, u32, u32, ctypes.POINTER(ctypes.c_uint8), fp, ctypes.POINTER(ctypes.c_int)]
     if hasattr(L, "rz_upload_after_physics"):
         L.rz_upload_after_physics.argtypes = [vp, u32, ctypes.POINTER(u32)]
     if hasattr(L, "rz_upload_ik_keys"):
@@ -446,15 +468,27 @@ class DeformContext:
         self._chk(self._L.rz_upload_skeleton(self._h, len(ib), _fptr(ib)))
         self.B = len(ib)
 
-    def upload_morphs_dense(self, deltas):
+    def upload_morphs_dense(self, deltas, storage=None):
+        """storage: None = the library's default (24-bit integers with one scale per morph), MORPH_F32 = fp32 planes."""
         if deltas is None or len(deltas) == 0:
             self._chk(self._L.rz_upload_morphs_dense(self._h, 0, None))
             self.M = 0
             return
         d = _f32(deltas)
         assert d.ndim == 3 and d.shape[1] == self.V and d.shape[2] == 3, d.shape
-        self._chk(self._L.rz_upload_morphs_dense(self._h, d.shape[0], _fptr(d)))
+        if storage is None:
+            self._chk(self._L.rz_upload_morphs_dense(self._h, d.shape[0], _fptr(d)))
+        else:
+            if not hasattr(self._L, "rz_upload_morphs_dense_ex"):
+                raise RzError(-6, "this build of the library has no rz_upload_morphs_dense_ex")
+            self._chk(self._L.rz_upload_morphs_dense_ex(self._h, d.shape[0], _fptr(d), int(storage)))
         self.M = d.shape[0]
+
+    def read_morph_dense(self, m):
+        """The resident (decoded) deltas of dense morph m, [3, V] planes."""
+        out = np.empty((3, self.V), dtype=np.float32)
+        self._chk(self._L.rz_read_morph_dense(self._h, int(m), _fptr(out)))
+        return out
 
     def upload_morphs_sparse(self, morph_off, vert_idx, delta3):
         mo = np.ascontiguousarray(morph_off, dtype=np.uint32)

@@ -267,6 +267,7 @@ void free_morphs(rz_ctx *c)
     forget_search(c);
     drop_graph(c);
     dfree(c->dense); dfree(c->sp_ptr); dfree(c->sp_entries);
+    dfree(c->dense_fold); c->dense_fold_host.clear(); c->morph_storage = 32;
     free_bone_morphs(c);                  // their entries name morphs of the old set
     c->morph_mode = 0; c->M = 0; c->Mpad = 12; c->sp_count = 0;
     retire_pose_tags(c);                  // ... and so does a pose staged ahead of its frame

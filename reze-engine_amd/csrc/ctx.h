@@ -215,7 +215,12 @@ struct RzStatic {
     // morphs
     int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
     uint32_t M = 0, Mpad = 12;
-    float *dense = nullptr;             // M x 3 x Vp
+    float *dense = nullptr;             // M x 3 x Vp: fp32 planes, or (morph_storage 24) 24-bit integers, 3 * Vp bytes a plane
+    // 24-bit dense storage (upload.cpp: rz_upload_morphs_dense; kernels/common.hip.h): per morph s_m * 2^-8, s_m = the power of two its
+    // integers are multiples of — folded into the weights of every active list. Empty / null with fp32 planes.
+    int morph_storage = 32;             // bits per stored delta of the resident dense set: 24 or 32
+    float *dense_fold = nullptr;        // [M] device
+    std::vector<float> dense_fold_host; // [M] host mirror (the one-launch frame's list is compacted on the host)
     uint32_t *sp_ptr = nullptr;         // Vp + 1
     float4 *sp_entries = nullptr;
     uint64_t sp_count = 0;

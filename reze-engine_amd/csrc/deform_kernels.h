@@ -11,6 +11,7 @@ struct RzPrepParams {
     const float *inv_bind;   // [B][16]
     float4 *palette;         // [I][B][3]  row-major 3x4
     const float *morph_w;    // [I][M]
+    const float *dense_fold; // [M] 24-bit dense storage: the factor folded into every listed weight (RzDeformParams); null = none
     uint32_t *act_idx;       // [I][Mpad]
     float *act_w;            // [I][Mpad]
     int *act_count;          // [I]
@@ -139,7 +140,8 @@ struct RzDeformParams {
     float4 *palette;            // [I][B][3]  (read by !FAST, written once per frame by FAST)
     const float *world;         // [I][B][16] (FAST)
     const float *inv_bind;      // [B][16]    (FAST)
-    const float *dense;         // [M][3][Vp] planes (MODE 1)
+    const float *dense;         // [M][3][Vp] planes (MODE 1): fp32, or 24-bit integers, 3 * Vp bytes a plane (dense_fold != null)
+    const float *dense_fold;    // [M] 24-bit storage: s_m * 2^-8 per morph, folded into the weights of the active list; null = fp32 planes
     const uint32_t *act_idx;    // [I][Mpad]
     const float *act_w;         // [I][Mpad]
     const int *act_count;       // [I]
@@ -228,6 +230,7 @@ struct RzSdefParams {
     const uint32_t *weights;    // [Vp] 4 x unorm8
     const float4 *palette;      // [I][B][3] this frame's palette rows
     const float *dense;         // [M][3][Vp] (mode 1)
+    const float *dense_fold;    // [M] or null: as in RzDeformParams
     const uint32_t *sp_ptr;     // [Vp + 1]   (mode 2)
     const float4 *sp_entries;
     const float *morph_w;       // [I][M] this frame's weights (sparse targets; dense with wsrc 2): the device copy the frame read or left
@@ -258,6 +261,7 @@ struct RzQdefParams {
     const uint32_t *weights;    // [Vp] 4 x unorm8
     const float4 *palette;      // [I][B][3] this frame's palette rows
     const float *dense;
+    const float *dense_fold;
     const uint32_t *sp_ptr;
     const float4 *sp_entries;
     const float *morph_w;

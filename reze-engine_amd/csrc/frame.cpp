@@ -117,7 +117,7 @@ template <typename S> static void pass_frame_fields(const rz_ctx *c, const Plan 
     s.geom = c->geom; s.joints01 = c->j01; s.weights = c->wq; s.palette = c->palette;
     if (c->morph_mode != 0 && c->M > 0) {
         s.mode = c->morph_mode; s.M = (int)c->M; s.Mpad = (int)c->Mpad;
-        s.dense = c->dense; s.sp_ptr = c->sp_ptr; s.sp_entries = c->sp_entries;
+        s.dense = c->dense; s.dense_fold = s.mode == 1 ? c->dense_fold : nullptr; s.sp_ptr = c->sp_ptr; s.sp_entries = c->sp_entries;
         // The weights where this frame's kernels leave or read them, never a pose block that a later upload may overwrite before the pass
         // runs (under the overlapped-front protocol the next pose goes down the upload stream behind this frame's front):
         //   dense, one-launch frame: its kernel-argument list (the weights may only sit in a pinned slot)

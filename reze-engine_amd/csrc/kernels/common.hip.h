@@ -73,10 +73,50 @@ __device__ __forceinline__ float4 ld_stream(const float4 *p, bool nt)
     return *p;
 }
 
+// ---- 24-bit dense morph storage ("Dense morph storage") ----
+// A plane holds Vp signed 24-bit integers q, four to three dwords (d0 = q0 | q1[7:0] << 24, d1 = q1[23:8] | q2[15:0] << 16,
+// d2 = q2[23:16] | q3 << 8), and a delta is q * s_m with one power-of-two scale per morph. The decode leaves q << 8 (the value's three
+// bytes in the high 24 bits of a dword, low byte zero: no sign extension) as a float — exact, |q| < 2^23 — and the factor s_m * 2^-8
+// is folded into the morph's WEIGHT where the active list is built (compact_active, pose.cpp), which is exact too: a power of two. So
+// fmaf(w', float(q << 8), acc) is fmaf(w, q * s_m, acc) to the bit, and the loops multiply nothing.
+typedef uint32_t u3v __attribute__((ext_vector_type(3)));
+
+// the three dwords of a quad (4-byte aligned: a plane is 3 * Vp bytes, Vp % 4 == 0)
+// (NT is a template argument: with a run-time flag the two forms' loads are hoisted into one and lose the hint)
+template <bool NT> __device__ __forceinline__ u3v ld_stream3(const uint32_t *p)
+{
+    u3v v;
+    if constexpr (NT) { v.x = __builtin_nontemporal_load(p); v.y = __builtin_nontemporal_load(p + 1); v.z = __builtin_nontemporal_load(p + 2); }
+    else { v.x = p[0]; v.y = p[1]; v.z = p[2]; }
+    return v;
+}
+
+// one quad: q0..q3 << 8 as floats
+__device__ __forceinline__ float4 decode24_quad(const u3v d)
+{
+    const int v0 = (int)(d.x << 8);
+    const int v1 = (int)__builtin_amdgcn_perm(d.y, d.x, 0x0504030cu);     // [0, d0.b3, d1.b0, d1.b1]
+    const int v2 = (int)__builtin_amdgcn_perm(d.z, d.y, 0x0403020cu);     // [0, d1.b2, d1.b3, d2.b0]
+    const int v3 = (int)(d.z & 0xffffff00u);
+    return make_float4((float)v0, (float)v1, (float)v2, (float)v3);
+}
+
+// one vertex of a plane (`plane` = its first dword): two cached dword loads and a byte permute. The value's bytes start at byte 3 * v;
+// its last vertex-in-quad needs the first dword only (the second load then repeats it: nothing past the quad is read).
+__device__ __forceinline__ float decode24_at(const uint32_t *plane, const uint32_t v)
+{
+    const uint32_t b = 3u * v, i = b >> 2, r = b & 3u;
+    const uint32_t lo = plane[i], hi = plane[i + (r > 1u ? 1u : 0u)];
+    return (float)(int)__builtin_amdgcn_perm(hi, lo, 0x0201000cu + r * 0x01010100u);
+}
+
 // Ordered compaction of the non-zero morph weights of one pose (whole workgroup of kBlock threads; `mw` may be LDS or global,
 // `aidx` / `aw` likewise): entries keep ascending morph order = the oracle's accumulation order; the tail up to Mpad is
 // zero-padded so unrolled readers may over-read harmlessly. Returns the number of active morphs (workgroup-uniform).
-__device__ __forceinline__ int compact_active(const float *mw, const int M, const int Mpad, uint32_t *aidx, float *aw, int *wave_cnt)
+// `fold` (24-bit dense storage; null = fp32 planes): the per-morph factor s_m * 2^-8 of morph `fold_base + m`, multiplied into the listed
+// weight (exact); the zero test is on the weight as it came.
+__device__ __forceinline__ int compact_active(const float *mw, const int M, const int Mpad, uint32_t *aidx, float *aw, int *wave_cnt,
+                                              const float *fold = nullptr, const int fold_base = 0)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int base = 0;
@@ -97,7 +137,7 @@ __device__ __forceinline__ int compact_active(const float *mw, const int M, cons
         }
         if (on) {
             aidx[base + before + rank] = (uint32_t)m;
-            aw[base + before + rank] = w;
+            aw[base + before + rank] = fold ? w * fold[fold_base + m] : w;
         }
         base += total;
         __syncthreads();

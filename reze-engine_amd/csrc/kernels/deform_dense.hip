@@ -4,7 +4,9 @@
 //         a = s, s+S, ... and the partial sums are combined with a __shfl_xor butterfly. S > 1 multiplies the number of waves in flight
 //         when the per-GPU shard is small (8-GPU strong scaling); even the 1 M-vertex mesh streams 3 % faster with two lanes per quad.
 //   U     morphs in flight per lane-slice iteration (3*U 16-byte loads issued back to back)
-//   NT    nontemporal loads on the morph stream (read once per frame: do not keep it in cache)
+//   Q24   the morph planes are 24-bit integers (common.hip.h): 3*U 12-byte loads, a byte permute and a convert per value, the same
+//         twelve FMAs in the same order with weights that carry the morphs' scales. Not part of the name a plan reports.
+//   NT    nontemporal loads on the morph stream (read once per frame: do not keep it in cache; 24-bit planes at S >= 4 excepted, see NT3)
 //   NTS   nontemporal stores of the outputs
 //   GEO   1 = rest geometry is read with 16-byte loads by the quad owner and transposed through the wave's LDS scratch (tools-only
 //             build); 0 = only the morphed position goes through LDS and the vertex-per-lane phase reads normal / joints / weights
@@ -30,7 +32,7 @@ namespace {
 
 // __launch_bounds__(256, 2): the persistent grid is two workgroups per CU (2 waves per SIMD), so the register allocator may use up
 // to 256 VGPRs but not one more (a 257th would halve residency).
-template <int S, int U, bool NT, bool NTS, bool GEO, bool FAST, int FKV = 0>
+template <int S, int U, bool NT, bool NTS, bool GEO, bool FAST, int FKV = 0, bool Q24 = false>
 __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float *k_geom, const float *k_world, const float *k_inv_bind, const uint32_t k_bf,
                                                                     const uint32_t k_Vp, const uint32_t k_nq, const uint32_t k_qpw, const uint32_t *k_j01,
                                                                     const uint32_t *k_j23, const uint32_t *k_wq, const RzDeformParams p, const RzMorphList ml)
@@ -51,6 +53,11 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
     constexpr int NPL = GEO ? 9 : 3;         // scratch planes per wave
     constexpr int ROUNDS = (VW + 63) / 64;
     constexpr bool LDS_LIST = !FAST;
+    // 24-bit planes: a slice's segment of a wave-load is QPW * 12 B — 768 / 384 B at S = 1 / 2, whole 128-byte lines, read once: nontemporal
+    // like the fp32 stream. At S = 4 / 8 it is 192 / 96 B and shares its lines with the wave's neighbours and its own next step: there the
+    // plain (cached) load is the faster one (profiles/morph24_ab.txt: 1/8 and 1/4 shards 5-6 %, C3 18 % against nontemporal), while at
+    // S = 2 it is the slower one (C5: 123.8 against 115.0 us).
+    constexpr bool NT3 = NT && S <= 2;
 
     const int tid = threadIdx.x;
     const int inst = blockIdx.y;
@@ -142,7 +149,7 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
         // plain uploaded / sampled pose, kernels/fk.hip.h), then the ordered compaction of the pose's morph weights into the LDS list
         __shared__ int fz_cnt[kBlock / 64];
         float *lds_mw = fused_hierarchy_prologue<true, (FKV == 1 || FKV == 2) ? FKV : 0>(p.fk, fke, p.st_tag, p.st_expect, p.st_morph_w, p.morph_w, p.morph_w_copy, p.M, pal, scratch_all, wid, RZ_TL_FK);
-        fused_count = compact_active(lds_mw, p.M, p.Mpad, s_idx, s_w, fz_cnt);
+        fused_count = compact_active(lds_mw, p.M, p.Mpad, s_idx, s_w, fz_cnt, Q24 ? p.dense_fold : nullptr);
         __syncthreads();
     } else if (!FAST && FKV != 1 && FKV != 2) {
         const float4 *gpal = p.palette + (size_t)inst * p.B * 3;
@@ -216,6 +223,8 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
 
         if (live) {
             const float4 *D = reinterpret_cast<const float4 *>(p.dense) + q;
+            const uint32_t *DQ = reinterpret_cast<const uint32_t *>(p.dense) + q * 3;     // Q24: 3 dwords per quad, 3 * plane4 per plane
+            const size_t plane3 = 3 * plane4;
             // slice s of S accumulates the active morphs a = s, s+S, s+2S, ... in ascending order.
             // The loop counter a0 is wave-uniform, so on the FAST path the list entries are fetched with
             // scalar loads straight from the kernel arguments and each lane picks its slice's entry with
@@ -240,16 +249,23 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
             int a0 = 0;
             // full groups of U morphs per slice: 3*U independent 16-byte loads in flight per lane
             for (; a0 + U * S <= count; a0 += U * S) {
-                float4 dx[U], dy[U], dz[U];
+                std::conditional_t<Q24, u3v, float4> dx[U], dy[U], dz[U];
                 float w[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     uint32_t m;
                     entry(a0 + u * S, m, w[u]);
-                    const float4 *d = D + (size_t)m * 3 * plane4;
-                    dx[u] = ld_stream(d, NT);
-                    dy[u] = ld_stream(d + plane4, NT);
-                    dz[u] = ld_stream(d + 2 * plane4, NT);
+                    if constexpr (Q24) {
+                        const uint32_t *d = DQ + (size_t)m * 3 * plane3;
+                        dx[u] = ld_stream3<NT3>(d);
+                        dy[u] = ld_stream3<NT3>(d + plane3);
+                        dz[u] = ld_stream3<NT3>(d + 2 * plane3);
+                    } else {
+                        const float4 *d = D + (size_t)m * 3 * plane4;
+                        dx[u] = ld_stream(d, NT);
+                        dy[u] = ld_stream(d + plane4, NT);
+                        dz[u] = ld_stream(d + 2 * plane4, NT);
+                    }
                 }
                 if (FAST && FIRST && world_pending) load_world();     // zero-copy frame: behind the first group's loads
                 // first group of the first step: the palette math overlaps the 3*U loads just issued. On a zero-copy frame the
@@ -258,12 +274,15 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
                 if (FAST && FIRST && need_palette && (!from_host || a0 + 2 * U * S > count)) form_palette();
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    ax.x = fmaf(w[u], dx[u].x, ax.x); ax.y = fmaf(w[u], dx[u].y, ax.y);
-                    ax.z = fmaf(w[u], dx[u].z, ax.z); ax.w = fmaf(w[u], dx[u].w, ax.w);
-                    ay.x = fmaf(w[u], dy[u].x, ay.x); ay.y = fmaf(w[u], dy[u].y, ay.y);
-                    ay.z = fmaf(w[u], dy[u].z, ay.z); ay.w = fmaf(w[u], dy[u].w, ay.w);
-                    az.x = fmaf(w[u], dz[u].x, az.x); az.y = fmaf(w[u], dz[u].y, az.y);
-                    az.z = fmaf(w[u], dz[u].z, az.z); az.w = fmaf(w[u], dz[u].w, az.w);
+                    float4 fx, fy, fz;
+                    if constexpr (Q24) { fx = decode24_quad(dx[u]); fy = decode24_quad(dy[u]); fz = decode24_quad(dz[u]); }
+                    else { fx = dx[u]; fy = dy[u]; fz = dz[u]; }
+                    ax.x = fmaf(w[u], fx.x, ax.x); ax.y = fmaf(w[u], fx.y, ax.y);
+                    ax.z = fmaf(w[u], fx.z, ax.z); ax.w = fmaf(w[u], fx.w, ax.w);
+                    ay.x = fmaf(w[u], fy.x, ay.x); ay.y = fmaf(w[u], fy.y, ay.y);
+                    ay.z = fmaf(w[u], fy.z, ay.z); ay.w = fmaf(w[u], fy.w, ay.w);
+                    az.x = fmaf(w[u], fz.x, az.x); az.y = fmaf(w[u], fz.y, az.y);
+                    az.z = fmaf(w[u], fz.z, az.z); az.w = fmaf(w[u], fz.w, az.w);
                 }
             }
             for (; a0 < count; a0 += S) {     // remainder, one morph per slice at a time (list is zero-padded)
@@ -271,8 +290,15 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
                 float w;
                 entry(a0, m, w);
                 if (a0 + s < count) {
-                    const float4 *d = D + (size_t)m * 3 * plane4;
-                    float4 dx = ld_stream(d, NT), dy = ld_stream(d + plane4, NT), dz = ld_stream(d + 2 * plane4, NT);
+                    float4 dx, dy, dz;
+                    if constexpr (Q24) {
+                        const uint32_t *d = DQ + (size_t)m * 3 * plane3;
+                        const u3v qx = ld_stream3<NT3>(d), qy = ld_stream3<NT3>(d + plane3), qz = ld_stream3<NT3>(d + 2 * plane3);
+                        dx = decode24_quad(qx); dy = decode24_quad(qy); dz = decode24_quad(qz);
+                    } else {
+                        const float4 *d = D + (size_t)m * 3 * plane4;
+                        dx = ld_stream(d, NT); dy = ld_stream(d + plane4, NT); dz = ld_stream(d + 2 * plane4, NT);
+                    }
                     ax.x = fmaf(w, dx.x, ax.x); ax.y = fmaf(w, dx.y, ax.y); ax.z = fmaf(w, dx.z, ax.z); ax.w = fmaf(w, dx.w, ax.w);
                     ay.x = fmaf(w, dy.x, ay.x); ay.y = fmaf(w, dy.y, ay.y); ay.z = fmaf(w, dy.z, ay.z); ay.w = fmaf(w, dy.w, ay.w);
                     az.x = fmaf(w, dz.x, az.x); az.y = fmaf(w, dz.y, az.y); az.z = fmaf(w, dz.z, az.z); az.w = fmaf(w, dz.w, az.w);
@@ -371,21 +397,25 @@ constexpr bool kAllVariants = true;
 constexpr bool kAllVariants = false;
 #endif
 
-template <int S, int U, bool NT, bool NTS, bool GEO, bool FAST, int FKV = 0>
+template <int S, int U, bool NT, bool NTS, bool GEO, bool FAST, int FKV = 0, bool Q24 = false>
 static hipError_t launch_one(const RzDeformParams &p, const RzMorphList &ml, dim3 grid, size_t lds, hipStream_t st)
 {
     // FKV — which variant of the kernel (the shapes a plan selects only): 0 = everything compiled in (the fused consumers: outline hull,
     // bounding box); 3 = without them; 1 / 2 = without them AND the hierarchy solve specialised for a plain uploaded / sampled pose
+    // 24-bit morph planes (a property of the resident targets, not of the plan): the same variant, reading them
+    if constexpr (!Q24) {
+        if (p.dense_fold) return launch_one<S, U, NT, NTS, GEO, FAST, FKV, true>(p, ml, grid, lds, st);
+    }
     if constexpr (!GEO && NT && U == 8 && FKV == 0) {
         if (!p.edge && !p.aabb) {
             if constexpr (!FAST) {
-                if (p.fk_on && p.fk_kind == 1) return launch_one<S, U, NT, NTS, GEO, FAST, 1>(p, ml, grid, lds, st);
-                if (p.fk_on && p.fk_kind == 2) return launch_one<S, U, NT, NTS, GEO, FAST, 2>(p, ml, grid, lds, st);
+                if (p.fk_on && p.fk_kind == 1) return launch_one<S, U, NT, NTS, GEO, FAST, 1, Q24>(p, ml, grid, lds, st);
+                if (p.fk_on && p.fk_kind == 2) return launch_one<S, U, NT, NTS, GEO, FAST, 2, Q24>(p, ml, grid, lds, st);
             }
-            return launch_one<S, U, NT, NTS, GEO, FAST, 3>(p, ml, grid, lds, st);
+            return launch_one<S, U, NT, NTS, GEO, FAST, 3, Q24>(p, ml, grid, lds, st);
         }
     }
-    auto k = rz_deform_dense_kernel<S, U, NT, NTS, GEO, FAST, FKV>;
+    auto k = rz_deform_dense_kernel<S, U, NT, NTS, GEO, FAST, FKV, Q24>;
     if (p.B > 0xffff) return hipErrorInvalidValue;      // k_bf carries the bone count in 16 bits (the 48 B per bone LDS palette keeps it far below today)
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(kBlock) rz_prep_kernel(RzPrepParams p)
 
     if (p.M > 0) {
         __shared__ int wave_cnt[kBlock / 64];
-        const int n = compact_active(p.morph_w + (size_t)inst * p.M, p.M, p.Mpad, p.act_idx + (size_t)inst * p.Mpad, p.act_w + (size_t)inst * p.Mpad, wave_cnt);
+        const int n = compact_active(p.morph_w + (size_t)inst * p.M, p.M, p.Mpad, p.act_idx + (size_t)inst * p.Mpad, p.act_w + (size_t)inst * p.Mpad, wave_cnt, p.dense_fold);
         if (tid == 0) p.act_count[inst] = n;
     }
 }

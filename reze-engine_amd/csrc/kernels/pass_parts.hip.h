@@ -42,12 +42,32 @@ constexpr int kChunk = 512;        // morph weights compacted into LDS at a time
 
 // this frame's deltas of vertex v for an ordered active list (idx[k] + base, w[k]), k < n. A lane's reads are gathers from scattered
 // vertices: a batch of them is issued before the first is used (the accumulation keeps ascending morph order), else the pass waits out one
-// memory latency per morph.
+// memory latency per morph. `q24`: the planes are 24-bit integers and the weights carry the morphs' scales (common.hip.h).
 __device__ __forceinline__ void add_dense(const uint32_t *idx, const float *w, const int n, const uint32_t base, const float *dense, const size_t Vp,
-                                          const uint32_t v, float &x, float &y, float &z)
+                                          const uint32_t v, float &x, float &y, float &z, const bool q24 = false)
 {
     constexpr int U = 8;
     int k = 0;
+    if (q24) {
+        const uint32_t *dq = reinterpret_cast<const uint32_t *>(dense);
+        const size_t pd = Vp / 4 * 3;                   // dwords per plane
+        for (; k + U <= n; k += U) {
+            float ww[U], dx[U], dy[U], dz[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                ww[u] = w[k + u];
+                const uint32_t *d = dq + (size_t)(idx[k + u] + base) * 3 * pd;
+                dx[u] = decode24_at(d, v); dy[u] = decode24_at(d + pd, v); dz[u] = decode24_at(d + 2 * pd, v);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) { x = fmaf(ww[u], dx[u], x); y = fmaf(ww[u], dy[u], y); z = fmaf(ww[u], dz[u], z); }
+        }
+        for (; k < n; ++k) {
+            const uint32_t *d = dq + (size_t)(idx[k] + base) * 3 * pd;
+            x = fmaf(w[k], decode24_at(d, v), x); y = fmaf(w[k], decode24_at(d + pd, v), y); z = fmaf(w[k], decode24_at(d + 2 * pd, v), z);
+        }
+        return;
+    }
     for (; k + U <= n; k += U) {
         float ww[U], dx[U], dy[U], dz[U];
 #pragma unroll
@@ -75,15 +95,16 @@ __device__ __forceinline__ void add_morphs(const P &p, const RzMorphList &ml, co
                                            uint32_t *s_idx, float *s_w, int *wave_cnt, float &x, float &y, float &z)
 {
     if (p.mode == 1 && p.M > 0) {
+        const bool q24 = p.dense_fold != nullptr;
         if (p.wsrc == 0) {
-            if (live) add_dense(ml.idx, ml.w, ml.count, 0u, p.dense, Vp, v, x, y, z);
+            if (live) add_dense(ml.idx, ml.w, ml.count, 0u, p.dense, Vp, v, x, y, z, q24);
         } else if (p.wsrc == 1) {
-            if (live) add_dense(p.act_idx + (size_t)inst * p.Mpad, p.act_w + (size_t)inst * p.Mpad, p.act_count[inst], 0u, p.dense, Vp, v, x, y, z);
+            if (live) add_dense(p.act_idx + (size_t)inst * p.Mpad, p.act_w + (size_t)inst * p.Mpad, p.act_count[inst], 0u, p.dense, Vp, v, x, y, z, q24);
         } else {
             const float *mw = p.morph_w + (size_t)inst * p.M;
             for (int m0 = 0; m0 < p.M; m0 += kChunk) {          // (workgroup-uniform: compact_active synchronises the workgroup)
-                const int cnt = compact_active(mw + m0, min(kChunk, p.M - m0), kChunk, s_idx, s_w, wave_cnt);
-                if (live) add_dense(s_idx, s_w, cnt, (uint32_t)m0, p.dense, Vp, v, x, y, z);
+                const int cnt = compact_active(mw + m0, min(kChunk, p.M - m0), kChunk, s_idx, s_w, wave_cnt, p.dense_fold, m0);
+                if (live) add_dense(s_idx, s_w, cnt, (uint32_t)m0, p.dense, Vp, v, x, y, z, q24);
                 __syncthreads();
             }
         }

@@ -56,15 +56,16 @@ __global__ void __launch_bounds__(kBlock) rz_sdef_kernel(const RzSdefParams p, c
     float x = p.geom[v], y = p.geom[Vp + v], z = p.geom[2 * Vp + v];
 
     if (p.mode == 1 && p.M > 0) {
+        const bool q24 = p.dense_fold != nullptr;       // 24-bit planes: the listed weights carry the morphs' scales (common.hip.h)
         if (p.wsrc == 0) {
-            if (live) add_dense(ml.idx, ml.w, ml.count, 0u, p.dense, Vp, v, x, y, z);
+            if (live) add_dense(ml.idx, ml.w, ml.count, 0u, p.dense, Vp, v, x, y, z, q24);
         } else if (p.wsrc == 1) {
-            if (live) add_dense(p.act_idx + (size_t)inst * p.Mpad, p.act_w + (size_t)inst * p.Mpad, p.act_count[inst], 0u, p.dense, Vp, v, x, y, z);
+            if (live) add_dense(p.act_idx + (size_t)inst * p.Mpad, p.act_w + (size_t)inst * p.Mpad, p.act_count[inst], 0u, p.dense, Vp, v, x, y, z, q24);
         } else {
             const float *mw = p.morph_w + (size_t)inst * p.M;
             for (int m0 = 0; m0 < p.M; m0 += kChunk) {          // (workgroup-uniform: compact_active synchronises the workgroup)
-                const int cnt = compact_active(mw + m0, min(kChunk, p.M - m0), kChunk, s_idx, s_w, wave_cnt);
-                if (live) add_dense(s_idx, s_w, cnt, (uint32_t)m0, p.dense, Vp, v, x, y, z);
+                const int cnt = compact_active(mw + m0, min(kChunk, p.M - m0), kChunk, s_idx, s_w, wave_cnt, p.dense_fold, m0);
+                if (live) add_dense(s_idx, s_w, cnt, (uint32_t)m0, p.dense, Vp, v, x, y, z, q24);
                 __syncthreads();
             }
         }

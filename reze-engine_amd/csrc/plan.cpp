@@ -98,7 +98,7 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
     RzDeformParams p;
     memset(&p, 0, sizeof p);
     p.geom = c->geom; p.joints01 = c->j01; p.joints23 = c->j23; p.weights = c->wq;
-    p.palette = c->palette; p.world = src_world(c); p.inv_bind = c->inv_bind; p.dense = c->dense;
+    p.palette = c->palette; p.world = src_world(c); p.inv_bind = c->inv_bind; p.dense = c->dense; p.dense_fold = c->dense_fold;
     p.act_idx = c->act_idx; p.act_w = c->act_w; p.act_count = c->act_count; p.morph_w = src_morph_w(c);
     if (pl.v.fast && c->pl.cur.zc_slot >= 0) {            // the one-launch kernel's workgroup 0 makes the pose resident
         if (!c->pl.cur.world_resident && !c->pl.cur.zc_local) p.world_copy = c->world;
@@ -233,6 +233,11 @@ Plan make_plan(const rz_ctx *c)
         v.S = 4;
         per_wave = run_per_wave(pl.n_quads, cap_i, v.S, false, true);
     }
+    // 24-bit dense planes (12 B per quad) read with nontemporal loads (S <= 2, kernels/deform_dense.hip): a run longer than 32 quads is a
+    // multiple of 32 quads = 384 B, so it starts on a 128-byte line of every plane. Applied AFTER the split is chosen: the heuristic
+    // plans above are what they are for fp32 planes (an S = 2 run that survives them is a multiple of 32 already, or a single short
+    // step), so this only moves forced shapes (morph_split / grid_cap). S = 4 / 8 read through the cache and keep the 8-quad grain.
+    if (v.mode == 1 && c->morph_storage == 24 && v.S <= 2 && per_wave > 32) per_wave = round_up(per_wave, 32);
     pl.quads_per_wave = per_wave;
     pl.grid_x = std::max<uint32_t>(1, (pl.n_quads + per_wave * waves_per_wg - 1) / (per_wave * waves_per_wg));
     // LDS write batching. Measured (tools/archive/ablate_c5.py): parking a wave's WHOLE run and writing it once at the end
@@ -524,6 +529,7 @@ RzPrepParams prep_params(const rz_ctx *c)
     memset(&p, 0, sizeof p);
     p.world = c->world; p.inv_bind = c->inv_bind; p.palette = c->palette; p.morph_w = c->morph_w;
     p.act_idx = c->act_idx; p.act_w = c->act_w; p.act_count = c->act_count;
+    p.dense_fold = c->morph_mode == 1 ? c->dense_fold : nullptr;
     p.B = (int)c->B; p.M = (int)c->M; p.Mpad = (int)c->Mpad;
     return p;
 }
@@ -649,11 +655,11 @@ RzIkSwitchParams ik_switch_params(const rz_ctx *c)
 
 uint64_t algorithmic_bytes(const rz_ctx *c)
 {
-    // 36 B read + 24 B written per vertex, 12*M B of dense morph targets per vertex,
+    // 36 B read + 24 B written per vertex, 12*M B of dense morph targets per vertex (9*M B in 24-bit storage),
     // world + inverse-bind matrices, morph weights. The static mesh is counted once for instances.
     const uint64_t V = c->V, I = c->I, B = c->B, M = c->M;
     uint64_t bytes = V * 36 + I * (V * 24 + B * 64) + B * 64;
-    if (c->morph_mode == 1) bytes += I * (V * 12 * M + M * 4);
+    if (c->morph_mode == 1) bytes += I * (V * (c->morph_storage == 24 ? 9 : 12) * M + M * 4);
     if (c->morph_mode == 2) bytes += V * 4 + I * (c->sp_count * 16 + M * 4);
     return bytes;
 }

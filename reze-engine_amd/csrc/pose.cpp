@@ -478,7 +478,8 @@ static void pose_in_place(rz_ctx *c, const float *morph_weights, bool on_device 
         for (uint32_t m = 0; m < c->M; ++m) {
             const float w = morph_weights[m];
             if (w == 0.0f) continue;
-            if (n < kKargMorphs) { ml.idx[n] = m; ml.w[n] = w; }
+            // (24-bit dense planes: the listed weight carries the morph's scale — exact, a power of two; kernels/common.hip.h)
+            if (n < kKargMorphs) { ml.idx[n] = m; ml.w[n] = c->dense_fold_host.empty() ? w : w * c->dense_fold_host[m]; }
             ++n;
         }
         ml.count = n <= kKargMorphs ? n : -1;

@@ -227,7 +227,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     if (!strncmp(key, "effective_", 10)) {
         // (an unknown key is refused BEFORE the work below: it drains the stream and may rebuild the run lists)
         static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones", "closure_rounds",
-                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds" };
+                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds", "morph_storage" };
         bool ok = false;
         for (const char *k : known) ok = ok || !strcmp(key + 10, k);
         if (!ok) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
@@ -279,6 +279,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
         *value = n;
     }
     else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
+    else if (!strcmp(key, "effective_morph_storage")) *value = c->morph_mode == 1 ? c->morph_storage : 0;
     else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;
     else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;
     else if (!strcmp(key, "effective_geo")) *value = make_plan(c).v.geo ? 1 : 0;

@@ -174,15 +174,60 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     return ensure_pose_buffers(c);
 }
 
-int rz_upload_morphs_dense(rz_ctx *c, uint32_t M, const float *deltas)
+// ---- 24-bit dense morph storage: the encoder (kernels/common.hip.h reads what it writes; DESIGN.md "Dense morph storage") ----
+// Per morph: E = the binary exponent of its largest finite |delta| over the three planes, s = 2^(E - 22), q = rint(d / s); a maximum
+// that rounds to 2^23 takes E + 1. An all-zero morph gets s = 1. |q * s - d| <= s / 2 = 2^(E - 23), about max|d| * 2^-23.
+// The whole SET stays fp32 (returns false) when a delta is not finite or an exponent leaves [-64, 64], which keeps weight * scale away
+// from underflow and overflow.
+static bool morph_scales24(uint32_t M, uint32_t V, const float *deltas, float *scales)
 {
-    if (int r = use(c)) return r;
-    if (int r = static_unlocked(c, "rz_upload_morphs_dense")) return r;
-    if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its morph targets");
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_morphs(c);
-    if (M == 0) return ensure_pose_buffers(c);
-    if (!deltas) return fail(RZ_ERR_INVALID, "null morph deltas");
+    for (uint32_t m = 0; m < M; ++m) {
+        const uint32_t *bits = reinterpret_cast<const uint32_t *>(deltas + (size_t)m * V * 3);
+        uint32_t top = 0;
+        for (size_t i = 0, n = (size_t)V * 3; i < n; ++i) top = std::max(top, bits[i] & 0x7fffffffu);
+        if (top >= 0x7f800000u) return false;                   // Inf / NaN
+        if (top == 0) { scales[m] = 1.0f; continue; }
+        float mx;
+        memcpy(&mx, &top, 4);
+        int e;
+        (void)frexpf(mx, &e);                                   // mx = f * 2^e, 0.5 <= f < 1: the binary exponent is e - 1
+        int E = e - 1;
+        if (E < -126 || lrintf(ldexpf(mx, 22 - E)) >= (1 << 23)) E += 1;
+        if (E < -64 || E > 64) return false;
+        scales[m] = ldexpf(1.0f, E - 22);
+    }
+    return true;
+}
+
+// one plane (component `comp` of one morph's [V][3] deltas) as 12-byte quads; dst holds ceil(V / 4) * 12 bytes, the last quad zero-padded
+static void encode_plane24(const float *d3, uint32_t V, int comp, float inv_scale, uint32_t *dst)
+{
+    for (uint32_t v0 = 0; v0 < V; v0 += 4) {
+        uint32_t q[4] = { 0u, 0u, 0u, 0u };
+        for (uint32_t k = 0; k < 4 && v0 + k < V; ++k) q[k] = (uint32_t)(int32_t)lrintf(d3[(size_t)(v0 + k) * 3 + comp] * inv_scale) & 0xffffffu;
+        uint32_t *o = dst + (size_t)(v0 / 4) * 3;
+        o[0] = q[0] | q[1] << 24;
+        o[1] = q[1] >> 8 | q[2] << 16;
+        o[2] = q[2] >> 16 | q[3] << 8;
+    }
+}
+
+int rz_morph_encode24(const float *deltas, uint32_t M, uint32_t V, uint8_t *packed, float *scales, int *storage)
+{
+    if (!deltas || !scales || !storage || M == 0 || V == 0) return fail(RZ_ERR_INVALID, "rz_morph_encode24: null array or empty set");
+    *storage = 32;
+    if (!morph_scales24(M, V, deltas, scales)) return RZ_OK;
+    *storage = 24;
+    if (!packed) return RZ_OK;
+    const size_t plane = (size_t)(V + 3) / 4 * 12;
+    for (uint32_t m = 0; m < M; ++m)
+        for (int comp = 0; comp < 3; ++comp)
+            encode_plane24(deltas + (size_t)m * V * 3, V, comp, 1.0f / scales[m], reinterpret_cast<uint32_t *>(packed + ((size_t)m * 3 + comp) * plane));
+    return RZ_OK;
+}
+
+static int upload_dense_f32(rz_ctx *c, uint32_t M, const float *deltas)
+{
     const size_t Vp = c->Vp, V = c->V;
     size_t dense_off = 0;
 #ifdef RZ_ALL_VARIANTS
@@ -207,10 +252,77 @@ int rz_upload_morphs_dense(rz_ctx *c, uint32_t M, const float *deltas)
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    c->morph_storage = 32;
+    return RZ_OK;
+}
+
+// 24-bit planes: encoded on the host a batch of morphs at a time (at most 64 MB of packed planes), each batch one copy
+static int upload_dense_q24(rz_ctx *c, uint32_t M, const float *deltas, const std::vector<float> &scales)
+{
+    const size_t Vp = c->Vp, V = c->V, plane = Vp * 3, per_morph = plane * 3;      // bytes
+    HIP_TRY(hipMalloc(&c->dense, (size_t)M * per_morph));
+    HIP_TRY(hipMalloc(&c->dense_fold, (size_t)M * sizeof(float)));
+    const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(M, (64u << 20) / per_morph));
+    std::vector<uint32_t> stage((size_t)batch * per_morph / 4, 0u);               // (the pad past V stays zero: every batch writes the same quads)
+    char *dst = reinterpret_cast<char *>(c->dense);
+    for (uint32_t m0 = 0; m0 < M; m0 += batch) {
+        const uint32_t nb = std::min(batch, M - m0);
+        for (uint32_t k = 0; k < nb; ++k)
+            for (int comp = 0; comp < 3; ++comp)
+                encode_plane24(deltas + (size_t)(m0 + k) * V * 3, (uint32_t)V, comp, 1.0f / scales[m0 + k], stage.data() + ((size_t)k * 3 + comp) * (plane / 4));
+        HIP_TRY(hipMemcpy(dst + (size_t)m0 * per_morph, stage.data(), (size_t)nb * per_morph, hipMemcpyHostToDevice));
+    }
+    c->dense_fold_host.resize(M);
+    for (uint32_t m = 0; m < M; ++m) c->dense_fold_host[m] = scales[m] * (1.0f / 256.0f);
+    HIP_TRY(hipMemcpy(c->dense_fold, c->dense_fold_host.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice));
+    c->morph_storage = 24;
+    return RZ_OK;
+}
+
+int rz_upload_morphs_dense_ex(rz_ctx *c, uint32_t M, const float *deltas, uint32_t flags)
+{
+    if (int r = use(c)) return r;
+    if (int r = static_unlocked(c, "rz_upload_morphs_dense")) return r;
+    if (flags & ~(uint32_t)RZ_MORPH_F32) return fail(RZ_ERR_INVALID, "rz_upload_morphs_dense_ex: unknown flags 0x%x", flags);
+    if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its morph targets");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_morphs(c);
+    if (M == 0) return ensure_pose_buffers(c);
+    if (!deltas) return fail(RZ_ERR_INVALID, "null morph deltas");
+    std::vector<float> scales(M);
+    bool q24 = !(flags & RZ_MORPH_F32);
+    if (q24) q24 = morph_scales24(M, c->V, deltas, scales.data());
+    if (int r = q24 ? upload_dense_q24(c, M, deltas, scales) : upload_dense_f32(c, M, deltas)) { free_morphs(c); return r; }
     c->morph_mode = 1;
     c->M = M;
     c->Mpad = round_up(M + 8, 4);
     return ensure_pose_buffers(c);
+}
+
+int rz_upload_morphs_dense(rz_ctx *c, uint32_t M, const float *deltas) { return rz_upload_morphs_dense_ex(c, M, deltas, 0u); }
+
+int rz_read_morph_dense(rz_ctx *c, uint32_t m, float *planes3)
+{
+    if (int r = use(c)) return r;
+    if (c->morph_mode != 1 || !c->dense) return fail(RZ_ERR_INVALID, "rz_read_morph_dense: no dense morph targets resident");
+    if (m >= c->M || !planes3) return fail(RZ_ERR_INVALID, "rz_read_morph_dense: morph %u of %u, or null output", m, c->M);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t Vp = c->Vp, V = c->V;
+    if (c->morph_storage != 24) {
+        for (int comp = 0; comp < 3; ++comp)
+            HIP_TRY(hipMemcpy(planes3 + comp * V, c->dense + ((size_t)m * 3 + comp) * Vp, V * sizeof(float), hipMemcpyDeviceToHost));
+        return RZ_OK;
+    }
+    std::vector<uint8_t> raw(Vp * 9);
+    HIP_TRY(hipMemcpy(raw.data(), reinterpret_cast<const char *>(c->dense) + (size_t)m * Vp * 9, raw.size(), hipMemcpyDeviceToHost));
+    const float fold = c->dense_fold_host[m];
+    for (int comp = 0; comp < 3; ++comp)
+        for (size_t v = 0; v < V; ++v) {
+            const uint8_t *b = raw.data() + (size_t)comp * Vp * 3 + v * 3;
+            const int32_t q8 = (int32_t)((uint32_t)b[0] << 8 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 24);       // q << 8, as the kernels decode it
+            planes3[comp * V + v] = (float)q8 * fold;
+        }
+    return RZ_OK;
 }
 
 int rz_upload_morphs_sparse(rz_ctx *c, uint32_t M, const uint32_t *morph_off, const uint32_t *vert_idx, const float *delta3)

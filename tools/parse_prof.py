@@ -90,7 +90,16 @@ f_read_plain = known_kib / find(cal_f, "k_read<false, 4>", "FETCH_SIZE")
 f_write3 = (known_kib * 1024 // 12 * 12 / 1024.0) / find(cal_w, "k_fill3<true>", "WRITE_SIZE")   # NT 12 B/lane stores
 f_write3_plain = (known_kib * 1024 // 12 * 12 / 1024.0) / find(cal_w, "k_fill3<false>", "WRITE_SIZE")
 f_write4 = known_kib / find(cal_w, "k_fill<false>", "WRITE_SIZE")
+# 24-bit dense morph planes are read with 12 B/lane loads: calibrated on `membench quick3` (636 MiB read per launch) when that pass ran
+cal3_path = os.path.join(P, "cal_fetch3", "mb_counter_collection.csv")
+f_read3 = None
+if os.path.exists(cal3_path):
+    f_read3 = (636 * 1024.0 * 1024 // 12 * 12 / 1024.0) / find(counters(cal3_path), "k_read3<true, 8>", "FETCH_SIZE")
+# a partial run (only some workloads profiled) replaces the records of the shapes it measured and keeps the others
 rec = {}
+tj = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+if os.path.exists(tj):
+    rec = {k: v for k, v in json.load(open(tj)).items() if k != "_calibration"}
 for name, (title, V, B, M, I) in WORK.items():
     st = os.path.join(P, "trace_" + name, "bench_kernel_stats.csv")
     if os.path.exists(st):
@@ -106,6 +115,8 @@ for name, (title, V, B, M, I) in WORK.items():
     # one record per (workload shape, kernel): every deform / skin kernel variant the run launched often enough to average
     # (the launch-shape search tries several; bench.py looks up the one its plan ends up with, and only that one)
     shape = "V%d_B%d_M%d_I%d%s" % (V, B, M, I, "_demo" if name == "demo" else "")
+    for k in [k for k in rec if k.startswith(shape + "|")]:
+        del rec[k]
     for kf in sorted(fe):
         if not ("rz_deform_" in kf or "rz_skin_instances" in kf) or "FETCH_SIZE" not in fe[kf] or kf not in wr or "WRITE_SIZE" not in wr[kf]:
             continue
@@ -114,9 +125,15 @@ for name, (title, V, B, M, I) in WORK.items():
         fetch_kib, write_kib = fe[kf]["FETCH_SIZE"][0], wr[kf]["WRITE_SIZE"][0]
         kname = kf.replace("void (anonymous namespace)::", "").split("(")[0]
         targs = kname.split("<")[1].split(",")
+        # the dense kernel's eighth template argument (24-bit morph planes) is not part of the name a plan reports (capi.py: kernel_name;
+        # bench.py's key into this file): the record is filed under the seven-argument name and says which storage it measured
+        q24 = False
+        if "rz_deform_dense" in kname and len(targs) == 8:
+            q24 = "true" in targs[7]
+            kname = kname.rsplit(",", 1)[0] + ">"
         # position of NTS (nontemporal output stores) in the template list: dense <S, U, NT, NTS, ...>, small <S, MODE, NTS, ...>, crowd <BLOCK, NTS, ...>
         nts = "true" in targs[3 if "rz_deform_dense" in kname else (2 if "rz_deform_small" in kname else 1)]
-        read_b = fetch_kib * 1024 * f_read
+        read_b = fetch_kib * 1024 * (f_read3 if (q24 and f_read3) else f_read)
         write_b = write_kib * 1024 * (f_write3 if nts else f_write3_plain)
         if I > 1:
             alg_read = V * 36 + I * B * 64 + B * 64  # mesh once, world matrices per instance, inverse bind
@@ -125,10 +142,11 @@ for name, (title, V, B, M, I) in WORK.items():
             alg_read = V * (36 + 4) + 36397 * 16 + B * 128 + M * 4      # sparse: + 4 B of row pointer per vertex and the demo shape's 36 397 entries of 16 B
             alg_write = V * 24
         else:
-            alg_read = V * (36 + 12 * M) + B * 128 + M * 4
+            alg_read = V * (36 + (9 if q24 else 12) * M) + B * 128 + M * 4
             alg_write = V * 24
         r = {
             "kernel": kname,
+            "morph_storage_bits": (24 if q24 else 32) if "rz_deform_dense" in kname else None,
             "launches_counted": fe[kf]["FETCH_SIZE"][1],
             "hbm_bytes_per_launch": read_b + write_b, "read_bytes": read_b, "write_bytes": write_b,
             "raw_FETCH_SIZE_KiB": fetch_kib, "raw_WRITE_SIZE_KiB": write_kib,
@@ -145,7 +163,8 @@ for name, (title, V, B, M, I) in WORK.items():
         rec[shape + "|" + kname] = r
 rec["_calibration"] = {"FETCH_SIZE_factor_nt_16B_reads": f_read, "FETCH_SIZE_factor_plain_16B_reads": f_read_plain,
                        "WRITE_SIZE_factor_nt_12B_stores": f_write3, "WRITE_SIZE_factor_plain_12B_stores": f_write3_plain,
-                       "WRITE_SIZE_factor_16B_stores": f_write4, "known_bytes": "tools/membench quick: 828 MiB read / filled per launch"}
+                       "WRITE_SIZE_factor_16B_stores": f_write4, "known_bytes": "tools/membench quick: 828 MiB read / filled per launch",
+                       "FETCH_SIZE_factor_nt_12B_reads": f_read3, "known_bytes_12B": "tools/membench quick3: 636 MiB read per launch"}
 json.dump(rec, open(os.path.join(ROOT, "profiles", "pmc_traffic.json"), "w"), indent=1)
 with open(os.path.join(ROOT, "profiles", "%s_pmc_hbm_traffic.txt" % tag), "w") as f:
     f.write(json.dumps(rec, indent=1) + "\n")
