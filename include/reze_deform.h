@@ -183,7 +183,7 @@ int rz_upload_qdef(rz_ctx *ctx, uint32_t n, const uint32_t *vert_idx);
  * links stay rigid), loops >= 0, at most 65535 chains with distinct goals and 255 links per chain. Refused with RZ_ERR_UNSUPPORTED: a bone
  * on a chain's path that takes its append rotation from a link of any chain, or an ancestor of the effector or of the goal that takes it
  * from a link of the same chain (either would force the whole solve into every step); a goal below one of its own chain's links; a path (outermost
- * link ... effector) of more than 64 bones. With a table the solve runs as rz_fk_ik_kernel in front of the deform / skin kernel: the
+ * link ... effector) of more than 64 bones. With a table the solve runs as rz_fk_kernel<RzIkParams> in front of the deform / skin kernel: the
  * one-launch forms ("effective_fuse_fk") are not taken, and the skeleton must fit 156 B of LDS per bone. rz_get_tuning("ik_chains") = the
  * count, ("ik_stages") = the number of stages the chains were grouped into (the chains of a stage are solved at once). n_chains = 0 removes the table. Needs rz_upload_skeleton_topology first; a new skeleton or topology drops it; refused while
  * forks exist; drops a captured graph. */
@@ -206,9 +206,9 @@ int rz_upload_ik(rz_ctx *ctx, uint32_t n_chains, const uint32_t *goal, const uin
  *   rz_set_pose_local, rz_set_pose, and a sampling call without keys for its source, leave it alone.
  * The switches are evaluated on the host, which is handed every frame and state anyway; only bits travel — one character's in the kernel
  * arguments, a crowd's in one small copy, and only when they differ from the bits the device holds. While at least one bit is off
- * (rz_get_tuning("ik_switched") = their number) the solve runs as rz_fk_ik_sw_kernel, whose waves skip the chains that are off, whose
+ * (rz_get_tuning("ik_switched") = their number) the solve runs as rz_fk_kernel<RzIkParams, RzIkSwitchParams>, whose waves skip the chains that are off, whose
  * workgroup skips the whole-skeleton re-solve of a stage with no chain on, and the stage loop of an instance with none; a mask of all
- * ones launches rz_fk_ik_kernel as ever. rz_physics_step's first solve uses the same mask.
+ * ones launches rz_fk_kernel<RzIkParams> as ever. rz_physics_step's first solve uses the same mask.
  * Keys (rz_get_tuning("ik_key_sets") = resident sets): key_enabled is [n_keys][n_chains] in rz_upload_ik's order, a chain a VMD key does
  * not name already filled in by the caller (tests/ik_switch_ref.py: flatten). clip = RZ_NO_CLIP: the motion of rz_upload_animation; else a
  * clip of the library. keys == NULL removes the set; a set of 0 keys is resident and says "all on". Static data: refused while forks exist,
@@ -413,8 +413,8 @@ int rz_set_pose_layered(rz_ctx *ctx, const rz_motion_state *base /* [I] */, uint
  * followers ascending by bone, each with its ancestor's entry in the override table — are built on the host from `parents` wherever the
  * override set is built: here (they travel in the same pinned slot down the same stream), with a physics table's per-instance buffers,
  * and when the flag flips while a set is resident. With the flag off, or with a set nothing hangs below, nothing is built, uploaded or
- * passed and every frame launches what it launched before; with follower entries resident the solve is rz_fk_follow_kernel /
- * rz_fk_ik_follow_kernel, and a single character's frame keeps the solve in that kernel instead of its own prologue.
+ * passed and every frame launches what it launched before; with follower entries resident the solve is rz_fk_kernel<RzFollowParams> /
+ * rz_fk_kernel<RzIkParams, RzFollowParams>, and a single character's frame keeps the solve in that kernel instead of its own prologue.
  * rz_get_tuning("override_follow") = 0 / 1, ("override_followers") = the follower entries resident over all instances (0 while off).
  * The ABI version stays 8: bindings detect the symbol. Host twin for host-solved poses: Model.followOverrides (host/model.js). */
 int rz_override_world(rz_ctx *ctx, uint32_t n, const uint32_t *instance, const uint32_t *bone, const float *world16);

@@ -399,7 +399,7 @@ struct rz_ctx : RzStatic, RzTuning {
     std::vector<int> ovr_off_host, ovr_bone_host;       // the hand-fed override set as uploaded (rz_override_world), for a later flip of the flag
 
     // The per-instance chain switches the next solve uses: [I][words] in the device's chain order, set = on, padding bits clear; EMPTY =
-    // every chain of every instance is on (the only form `off` == 0 takes), and then rz_fk_ik_kernel is launched as ever. One character's
+    // every chain of every instance is on (the only form `off` == 0 takes), and then the solve is launched without the switch stage, as ever. One character's
     // words ride in the kernel arguments; a crowd's are copied into `dev` when they CHANGE (a switch flips a few times per motion, so a
     // frame whose bits did not change sends nothing). A fork's own, all on from the start.
     struct IkSwitch {
@@ -524,7 +524,6 @@ void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
 void free_after(rz_ctx *c);
 void free_physics(rz_ctx *c);          // physics_host.cpp
-RzIkParams ik_params(const rz_ctx *c);
 template <typename T> int to_device(T **dst, const void *src, size_t count)
 {
     *dst = nullptr;
@@ -546,19 +545,17 @@ RzSubFk subfk_params(const rz_ctx *c);
 int frame_plan(rz_ctx *c, Plan *pl);
 RzDeformParams deform_params(const rz_ctx *c, const Plan &pl);
 RzPrepParams prep_params(const rz_ctx *c);
-RzFkParams fk_params(const rz_ctx *c);
-// rz_override_follow: null pointers unless the flag is on, overrides are resident and at least one bone follows one
-RzFollowParams follow_params(const rz_ctx *c);
+RzFkParams fk_params(const rz_ctx *c, bool overrides = true);      // overrides = false: without the override table (rz_physics_step's solve)
+// Which stages the next hierarchy solve runs (deform_kernels.h: RzFkStages), the one owner of that decision: IK while a table is resident,
+// chain switches while at least one bit is clear, the follow stage while rz_override_follow is on, overrides are resident and a bone follows
+// one, the after-physics launch while its list and a non-empty override table are resident. A stage that is off leaves its block empty.
+// overrides = false as in fk_params: no follow and no after stage either.
+RzFkStages solve_stages(const rz_ctx *c, bool overrides = true);
 // the follower lists of an override set (off [I + 1], bones ascending inside an instance) from the resident parents: fol_off [I + 1] and per
 // entry (follower bone, index of its nearest overridden ancestor's entry), ascending by bone inside an instance
 void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent);
 int reserve_followers(rz_ctx *c, size_t entries, size_t offsets);       // grows fol_off / fol_ent (drains and drops the graph when it must)
 int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones);       // build + blocking upload; the caller has drained
-// rz_upload_after_physics: null pointers and n = 0 unless the list is resident AND the override table holds at least one entry (then
-// launch_fk launches rz_fk_after_kernel behind the solve)
-RzAfterParams after_params(const rz_ctx *c);
-// chain switches: null mask and words 0 unless at least one bit is clear (then launch_fk takes the rz_fk_ik_sw*_kernel entries)
-RzIkSwitchParams ik_switch_params(const rz_ctx *c);
 uint64_t algorithmic_bytes(const rz_ctx *c);
 
 // ---- pose.cpp ----
@@ -580,7 +577,7 @@ int plan_ik_resize(rz_ctx *c, uint32_t I, IkWordsPlan *pl);      // rz_set_insta
 
 // ---- frame.cpp ----
 int check_ready(rz_ctx *c);
-int launch_fk(rz_ctx *c, hipStream_t st);
+int launch_fk(rz_ctx *c, hipStream_t st, bool overrides = true);       // the solve + the after launch solve_stages(c, overrides) lists
 bool solve_on_demand(const rz_ctx *c);
 int launch_prep(rz_ctx *c, hipStream_t st);
 int launch_front(rz_ctx *c, const Plan &pl, hipStream_t st);

@@ -85,8 +85,9 @@ struct RzFkParams {
     uint64_t st_expect;
 };
 
-// PMX inverse kinematics (rz_upload_ik; kernels/ik.hip.h): the stage rz_fk_ik_kernel runs between the doubling rounds and the override
-// pass. A block of its own, handed to that kernel only: RzFkParams — embedded in the fused kernels' arguments — does not change.
+// PMX inverse kinematics (rz_upload_ik; kernels/ik.hip.h): the stage the solve runs between the doubling rounds and the override pass.
+// A block of its own, an argument of the rz_fk_kernel instantiations with the stage only (RzFkStages below): RzFkParams — embedded in
+// the fused kernels' arguments — does not change.
 struct RzIkParams {
     const uint4 *chain;         // [n_chains][2], sorted by (stage, IK bone): (goal, first path entry, path length, parent of the path's first bone or -1)
                                 //                                            (loops, bits(per-step angle limit), first link, links)
@@ -98,9 +99,9 @@ struct RzIkParams {
 };
 
 // Followers of overridden bones (rz_override_follow; kernels/fk.hip.h: FOLLOW): per instance the bones below an overridden bone, each with
-// the entry of its NEAREST overridden ancestor in the override table, ascending by bone. A block of its own like RzIkParams, handed to the
-// rz_fk_*follow_kernel entries only, which are launched only while entries exist: RzFkParams — embedded in the fused kernels' arguments —
-// does not change, and with the flag off (or nothing to follow) both pointers are null and every frame launches what it launched before.
+// the entry of its NEAREST overridden ancestor in the override table, ascending by bone. A block of its own like RzIkParams, an argument of the
+// rz_fk_kernel instantiations with the stage only, which are launched only while entries exist: RzFkParams — embedded in the fused kernels'
+// arguments — does not change, and with the flag off (or nothing to follow) both pointers are null and every frame launches what it launched before.
 struct RzFollowParams {
     const int *off;             // [I + 1] or nullptr
     const uint2 *ent;           // [n] (follower bone, index into ovr_bone / ovr_world)
@@ -122,13 +123,24 @@ struct RzAfterParams {
 // Per-instance switches of the IK chains (rz_set_ik_enabled / rz_upload_ik_keys; kernels/ik.hip.h: SW; defined by tests/ik_switch_ref.py):
 // one bit per chain in the DEVICE's chain order (RzIkParams::chain: sorted by stage, so a stage is a contiguous bit range), bit c of word
 // c / 32, set = the chain is solved. The host evaluates the switches (it knows every frame and state it hands over) and only the bits
-// travel: one character's few words in the kernel arguments, a crowd's in a device array. A block of its own like RzFollowParams, handed to
-// the rz_fk_ik_sw*_kernel entries only, which are launched only while at least one bit is clear: RzFkParams and RzIkParams do not change.
+// travel: one character's few words in the kernel arguments, a crowd's in a device array. A block of its own like RzFollowParams, an argument of
+// the rz_fk_kernel instantiations with the switches only, which are launched only while at least one bit is clear: RzFkParams and RzIkParams do not change.
 constexpr int kRzIkSwInline = 4;
 struct RzIkSwitchParams {
     const uint32_t *mask;       // [I][words], or nullptr: one instance, its words are w0 below
     uint32_t w0[kRzIkSwInline];
     int words;                  // words per instance = ceil(n_chains / 32)
+};
+
+// Which stages the next hierarchy solve runs: the four blocks above, each the empty one its builder returns (null pointers, n_chains == 0,
+// words == 0, n == 0) while its stage is off. The one description rz_launch_fk picks its instantiation from, rz_fk_lds_bytes sizes the
+// LDS from and the host asks (plan.cpp: solve_stages). ik / fo / sw are arguments of the solve; af is the launch behind it.
+struct RzFkStages {
+    RzIkParams ik;
+    RzIkSwitchParams sw;
+    RzFollowParams fo;
+    RzAfterParams af;
+    bool plain() const { return !ik.n_chains && !sw.words && !fo.off && !af.n; }       // no stage: what the fused kernels' embedded solve can stand in for
 };
 
 // rz_deform_kernel: fused morph + 4-bone LBS (engine/src/engine.ts:253-272).
@@ -377,7 +389,7 @@ struct RzVariant {
 // second matrix buffer of the doubling rounds) + 12 B (local translation), 16-byte rounded
 __host__ __device__ inline size_t rz_fk_scratch_bytes(int B) { return ((size_t)B * 60 + 15) & ~(size_t)15; }
 
-// rz_fk_ik_kernel: the pose's morph weights in LDS (bone morphs), rounded so that the matrix buffer behind them is 16-byte aligned
+// the solve with the IK stage: the pose's morph weights in LDS (bone morphs), rounded so that the matrix buffer behind them is 16-byte aligned
 __host__ __device__ inline size_t rz_fk_mw_bytes(const RzFkParams &p)
 {
     if (!p.bm_off) return 0;
@@ -386,20 +398,16 @@ __host__ __device__ inline size_t rz_fk_mw_bytes(const RzFkParams &p)
 }
 
 hipError_t rz_launch_prep(const RzPrepParams &p, uint32_t instances, hipStream_t st);
-hipError_t rz_launch_fk(const RzFkParams &p, uint32_t instances, hipStream_t st);
-size_t rz_fk_lds_bytes(const RzFkParams &p);      // dynamic LDS of rz_fk_kernel (palette rows + solve scratch + the pose's morph weights)
-// the hierarchy solve with the IK stage (rz_fk_ik_kernel): region X of the solve stays alive across the doubling rounds, which get a
-// second matrix buffer of their own — 48 B per bone more
-hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t instances, hipStream_t st);
-size_t rz_fk_ik_lds_bytes(const RzFkParams &p);
-// the same two solves with the follow stage (rz_fk_follow_kernel / rz_fk_ik_follow_kernel; `ik` null = no IK table): same LDS as their twins
-hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const RzFollowParams &fo, uint32_t instances, hipStream_t st);
-// the after-physics stage behind whichever of the solves above ran, on the same stream (kernels/after.hip: rz_fk_after_kernel): reads the
-// world matrices that solve left in memory and writes the listed bones' world matrices and palette rows again
+// The hierarchy solve (kernels/front.hip: rz_fk_kernel<Stage...>) with the stages `s` lists: one launcher picks the instantiation, whose
+// kernel arguments carry the blocks of the stages that are on and nothing else.
+hipError_t rz_launch_fk(const RzFkParams &p, const RzFkStages &s, uint32_t instances, hipStream_t st);
+// its dynamic LDS: palette rows + solve scratch + the pose's morph weights; with the IK stage region X of the solve stays alive across
+// the doubling rounds, which get a second matrix buffer of their own: 48 B per bone more
+size_t rz_fk_lds_bytes(const RzFkParams &p, const RzFkStages &s);
+// the after-physics stage (s.af) behind the solve, on the same stream (kernels/after.hip: rz_fk_after_kernel): reads the world matrices
+// the solve left in memory and writes the listed bones' world matrices and palette rows again
 hipError_t rz_launch_fk_after(const RzFkParams &p, const RzAfterParams &a, uint32_t instances, hipStream_t st);
 size_t rz_fk_after_lds_bytes(const RzFkParams &p, const RzAfterParams &a);
-// the IK solve with per-instance chain switches (rz_fk_ik_sw_kernel / rz_fk_ik_sw_follow_kernel; `fo` null = no follower entries): same LDS as rz_fk_ik_kernel
-hipError_t rz_launch_fk_ik_sw(const RzFkParams &p, const RzIkParams &ik, const RzIkSwitchParams &sw, const RzFollowParams *fo, uint32_t instances, hipStream_t st);
 hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
                             uint32_t instances, hipStream_t st);
 size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v);

@@ -13,42 +13,23 @@ int check_ready(rz_ctx *c)
     return RZ_OK;
 }
 
-// the after-physics stage (rz_upload_after_physics) behind whichever hierarchy kernel ran, on its stream: only while the list and a
-// non-empty override table are resident
-static int launch_fk_after(rz_ctx *c, const RzFkParams &fp, hipStream_t st)
+// The hierarchy solve of the resident pose with the stages solve_stages lists (plan.cpp), then the after-physics launch behind it on the
+// same stream if listed. The launchers refuse what does not fit; the LDS refusals are made here first, where they can say why.
+int launch_fk(rz_ctx *c, hipStream_t st, bool overrides)
 {
-    const RzAfterParams af = after_params(c);
-    if (!af.n) return RZ_OK;
-    const size_t lds = rz_fk_after_lds_bytes(fp, af);
+    const RzFkParams fp = fk_params(c, overrides);
+    const RzFkStages ss = solve_stages(c, overrides);
+    const size_t lds = rz_fk_lds_bytes(fp, ss);
     if (lds > 160 * 1024)
-        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %d entries x 1 B = %zu B of LDS (the limit is 160 KB)", c->B, af.n, lds);
-    HIP_TRY(rz_launch_fk_after(fp, af, c->I, st));
-    return RZ_OK;
-}
-
-int launch_fk(rz_ctx *c, hipStream_t st)
-{
-    const RzFkParams fp = fk_params(c);
-    const RzFollowParams fo = follow_params(c);         // entries resident (rz_override_follow): the same solves with the follow stage
-    if (c->ik_n) {              // the solve with the IK stage: a kernel of its own, launched only while a table is present
-        const size_t lds = rz_fk_ik_lds_bytes(fp);
-        if (lds > 160 * 1024)
-            return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve with IK on the device: %u bones need %zu B of LDS (156 B per bone + the pose's morph weights: the IK stage keeps the local pose alive beside both matrix buffers; the limit is 160 KB)", c->B, lds);
-        const RzIkParams ik = ik_params(c);
-        const RzIkSwitchParams sw = ik_switch_params(c);     // at least one chain of one instance is switched off: the entries that look
-        if (sw.words) HIP_TRY(rz_launch_fk_ik_sw(fp, ik, sw, fo.off ? &fo : nullptr, c->I, st));
-        else if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, &ik, fo, c->I, st));
-        else HIP_TRY(rz_launch_fk_ik(fp, ik, c->I, st));
-        if (int r = launch_fk_after(c, fp, st)) return r;
-        c->palette_stale = false; c->fk_stale = false;
-        return RZ_OK;
+        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve%s on the device: %u bones need %zu B of LDS (%s; the limit is 160 KB)", ss.ik.n_chains ? " with IK" : "", c->B, lds,
+                    ss.ik.n_chains ? "156 B per bone + the pose's morph weights: the IK stage keeps the local pose alive beside both matrix buffers" : "108 B per bone + the pose's morph weights");
+    HIP_TRY(rz_launch_fk(fp, ss, c->I, st));
+    if (ss.af.n) {
+        const size_t after_lds = rz_fk_after_lds_bytes(fp, ss.af);
+        if (after_lds > 160 * 1024)
+            return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %d entries x 1 B = %zu B of LDS (the limit is 160 KB)", c->B, ss.af.n, after_lds);
+        HIP_TRY(rz_launch_fk_after(fp, ss.af, c->I, st));
     }
-    const size_t lds = rz_fk_lds_bytes(fp);
-    if (lds > 160 * 1024)
-        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve on the device: %u bones need %zu B of LDS (116 B per bone + the pose's morph weights; the limit is 160 KB)", c->B, lds);
-    if (fo.off) HIP_TRY(rz_launch_fk_follow(fp, nullptr, fo, c->I, st));
-    else HIP_TRY(rz_launch_fk(fp, c->I, st));
-    if (int r = launch_fk_after(c, fp, st)) return r;
     c->palette_stale = false; c->fk_stale = false;
     return RZ_OK;
 }
@@ -280,10 +261,8 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     h = fnv(h, &sd, sizeof sd);
     const RzQdefParams qd = qdef_params(c, pl);
     h = fnv(h, &qd, sizeof qd);
-    if (c->ik_n) { const RzIkParams ik = ik_params(c); h = fnv(h, &ik, sizeof ik); }
-    if (c->ovr_follow) { const RzFollowParams fo = follow_params(c); h = fnv(h, &fo, sizeof fo); }
-    if (c->ik_n) { const RzIkSwitchParams sw = ik_switch_params(c); h = fnv(h, &sw, sizeof sw); }
-    if (c->af_n) { const RzAfterParams af = after_params(c); h = fnv(h, &af, sizeof af); }
+    const RzFkStages ss = solve_stages(c);     // whole and unconditionally: a stage that is off is the same zeros in every frame
+    h = fnv(h, &ss, sizeof ss);
     const uint64_t misc[6] = { c->I, c->pl.cur.local, c->pl.cur.local_t, c->pl.cur.sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }

@@ -406,9 +406,11 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // executes every instruction once. KIND 1 = an uploaded pose, KIND 2 = a sampled pose, both PLAIN: no physics overrides,
 // at most 512 bones (two per thread), at most 256 vertex morphs (one per thread) — the host picks the variant when all of that holds
 // (RzDeformParams::fk_kind) and the generic form (KIND 0) otherwise. Same device functions, same bits.
-// IK (rz_fk_ik_kernel only, generic form): the PMX IK stage (kernels/ik.hip.h) runs between the doubling rounds and the override pass. The
+// IK, FOLLOW and SW are the stages of the stand-alone solve: rz_fk_kernel<Stage...> (front.hip) sets each flag when its instantiation
+// receives the stage's block, and rz_launch_fk picks the instantiation from the one stage description (deform_kernels.h: RzFkStages).
+// IK (generic form): the PMX IK stage (kernels/ik.hip.h) runs between the doubling rounds and the override pass. The
 // stage re-forms local matrices, so region X must survive the rounds: they get `ik_m2`, a second matrix buffer of their own.
-// FOLLOW (rz_fk_follow_kernel / rz_fk_ik_follow_kernel only, generic form; rz_override_follow, defined by tests/follow_ref.py): bones below an
+// FOLLOW (generic form; rz_override_follow, defined by tests/follow_ref.py): bones below an
 // overridden bone follow it. With S the solved world matrices (hierarchy, bone morphs, IK), O the instance's overridden bones and O_a their
 // matrices, every bone b outside O with an ancestor in O takes  W_b = O_a * (S_a^-1 * S_b),  a = the NEAREST such ancestor along the
 // parents, S_a^-1 the rigid inverse (R^T, -R^T p: world matrices carry no scale); bones of O take O_a, all others keep S_b. So an override
@@ -422,7 +424,7 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // the override write replaces the S_a it read. Entries ascend by bone inside an
 // instance: consecutive lanes read rows 48 B apart, which a 16-lane group of a 16-byte LDS read spreads over all sixteen 16-byte slots of
 // a bank row (3 l mod 16 is a permutation), and lanes of one strand read the same S_a, which is a broadcast.
-// SW (rz_fk_ik_sw_kernel / rz_fk_ik_sw_follow_kernel only; rz_set_ik_enabled / rz_upload_ik_keys): the IK stage honours the instance's chain
+// SW (with IK only; rz_set_ik_enabled / rz_upload_ik_keys): the IK stage honours the instance's chain
 // switches (kernels/ik.hip.h: ik_stage<SW>).
 template <bool FUSED, int KIND = 0, bool IK = false, bool FOLLOW = false, bool SW = false>
 __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &early, const int inst, float4 *wl, unsigned char *scr, float *lds_mw,
@@ -431,8 +433,8 @@ __device__ __forceinline__ void fk_solve(const RzFkParams &p, const FkEarly &ear
                                          const RzIkSwitchParams *iksw = nullptr)
 {
     static_assert(!SW || IK, "chain switches belong to the IK stage");
-    static_assert(!IK || (!FUSED && KIND == 0), "the IK stage belongs to the generic solve of rz_fk_ik_kernel");
-    static_assert(!FOLLOW || (!FUSED && KIND == 0), "the follow stage belongs to the generic solve of the rz_fk_*follow_kernel entries");
+    static_assert(!IK || (!FUSED && KIND == 0), "the IK stage belongs to the generic solve of rz_fk_kernel");
+    static_assert(!FOLLOW || (!FUSED && KIND == 0), "the follow stage belongs to the generic solve of rz_fk_kernel");
     constexpr bool PLAIN = KIND != 0;
 #ifdef RZ_ABLATE
 #define RZ_FSTAMP(k) do { if (fs) fs[k] = __builtin_amdgcn_s_memrealtime(); } while (0)

@@ -40,72 +40,31 @@ __global__ void __launch_bounds__(kBlock) rz_prep_kernel(RzPrepParams p)
     }
 }
 
-// One workgroup per pose. The leading arguments are preloaded into SGPRs (kernels/deform_parts.hip.h): the static block and the two
-// counts a thread needs to ask for its records before `p` has arrived.
-__global__ void __launch_bounds__(kBlock) rz_fk_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p)
+// The hierarchy solve's one entry. One workgroup per pose. The leading arguments are preloaded into SGPRs (kernels/deform_parts.hip.h):
+// the static block and the two counts a thread needs to ask for its records before `p` has arrived. `Stage...` are the blocks of the
+// stages this instantiation runs, in the order RzIkParams, RzFollowParams, RzIkSwitchParams (kernels/fk.hip.h: IK, FOLLOW, SW): an
+// instantiation receives exactly the blocks it reads, so its kernel arguments hold nothing for a stage that is off. rz_launch_fk below
+// picks one of the six that exist: <>, <ik>, <fo>, <ik, fo>, <ik, sw>, <ik, fo, sw>.
+// LDS: palette rows | solve scratch | the pose's morph weights (bone morphs) | IK: the doubling rounds' own second matrix buffer.
+template <class T> __device__ __forceinline__ const T *fk_stage_arg() { return nullptr; }
+template <class T, class S0, class... S> __device__ __forceinline__ const T *fk_stage_arg(const S0 &s0, const S &...s)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
-    unsigned char *scr = smem + (size_t)p.B * 48;
-    fk_solve<false>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(scr + rz_fk_scratch_bytes(p.B)), true);
+    if constexpr (std::is_same<T, S0>::value) return &s0;
+    else return fk_stage_arg<T>(s...);
 }
 
-// The same solve with the PMX IK stage (kernels/ik.hip.h), launched instead of rz_fk_kernel only while the context holds an IK table.
-// LDS: palette rows | solve scratch | the pose's morph weights (bone morphs) | the doubling rounds' own second matrix buffer.
-__global__ void __launch_bounds__(kBlock) rz_fk_ik_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik)
+template <class... Stage>
+__global__ void __launch_bounds__(kBlock) rz_fk_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const Stage... stage)
 {
+    constexpr bool IK = (std::is_same<Stage, RzIkParams>::value || ...), FOLLOW = (std::is_same<Stage, RzFollowParams>::value || ...),
+                   SW = (std::is_same<Stage, RzIkSwitchParams>::value || ...);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
     unsigned char *scr = smem + (size_t)p.B * 48;
     unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
-    fk_solve<false, 0, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
-                             reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)));
-}
-
-// The two solves above with the follow stage (kernels/fk.hip.h: FOLLOW; rz_override_follow), launched instead of them only while an
-// override table AND follower entries are resident. Same LDS as their twins.
-__global__ void __launch_bounds__(kBlock) rz_fk_follow_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzFollowParams fo)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
-    unsigned char *scr = smem + (size_t)p.B * 48;
-    fk_solve<false, 0, false, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(scr + rz_fk_scratch_bytes(p.B)), true,
-                                    0ull, nullptr, nullptr, nullptr, &fo);
-}
-
-__global__ void __launch_bounds__(kBlock) rz_fk_ik_follow_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik,
-                                                                 const RzFollowParams fo)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
-    unsigned char *scr = smem + (size_t)p.B * 48;
-    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
-    fk_solve<false, 0, true, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
-                                   reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), &fo);
-}
-
-// The two IK solves with per-instance chain switches (kernels/ik.hip.h: SW; rz_set_ik_enabled / rz_upload_ik_keys), launched instead of
-// them only while at least one (instance, chain) bit is clear. Same LDS as their twins.
-__global__ void __launch_bounds__(kBlock) rz_fk_ik_sw_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik,
-                                                             const RzIkSwitchParams sw)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
-    unsigned char *scr = smem + (size_t)p.B * 48;
-    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
-    fk_solve<false, 0, true, false, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
-                                          reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), nullptr, &sw);
-}
-
-__global__ void __launch_bounds__(kBlock) rz_fk_ik_sw_follow_kernel(const uint4 *k_rec, const uint32_t k_B, const uint32_t k_M, const RzFkParams p, const RzIkParams ik,
-                                                                    const RzFollowParams fo, const RzIkSwitchParams sw)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
-    unsigned char *scr = smem + (size_t)p.B * 48;
-    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
-    fk_solve<false, 0, true, true, true>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr, &ik,
-                                         reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)), &fo, &sw);
+    fk_solve<false, 0, IK, FOLLOW, SW>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr,
+                                       fk_stage_arg<RzIkParams>(stage...), IK ? reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)) : nullptr,
+                                       fk_stage_arg<RzFollowParams>(stage...), fk_stage_arg<RzIkSwitchParams>(stage...));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -215,72 +174,40 @@ hipError_t rz_launch_prep(const RzPrepParams &p, uint32_t instances, hipStream_t
     return hipGetLastError();
 }
 
-size_t rz_fk_ik_lds_bytes(const RzFkParams &p)
-{
-    return (size_t)p.B * 48 + rz_fk_scratch_bytes(p.B) + rz_fk_mw_bytes(p) + (size_t)p.B * 48;
-}
-
-hipError_t rz_launch_fk_ik(const RzFkParams &p, const RzIkParams &ik, uint32_t instances, hipStream_t st)
-{
-    const size_t lds = rz_fk_ik_lds_bytes(p);
-    if (lds > 160 * 1024 || !ik.chain || ik.n_stages <= 0) return hipErrorInvalidValue;      // (the host checks first and says why: launch_fk in frame.cpp)
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_fk_ik_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(rz_fk_ik_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, ik);
-    return hipGetLastError();
-}
-
-size_t rz_fk_lds_bytes(const RzFkParams &p)
+// Dynamic LDS of the solve. Without IK: palette rows + solve scratch + the pose's morph weights as they are. With IK region X of the solve
+// stays alive across the doubling rounds, which get a second matrix buffer of their own, 48 B per bone more, behind the ROUNDED weights.
+size_t rz_fk_lds_bytes(const RzFkParams &p, const RzFkStages &s)
 {
     size_t lds = (size_t)p.B * 48 + rz_fk_scratch_bytes(p.B);
+    if (s.ik.n_chains) return lds + rz_fk_mw_bytes(p) + (size_t)p.B * 48;
     if (p.bm_off) lds += (size_t)std::max(std::max(p.bm_M, p.sample.M), 1) * 4;      // the pose's morph weights, for the bone morphs
     return lds;
 }
 
-hipError_t rz_launch_fk(const RzFkParams &p, uint32_t instances, hipStream_t st)
+template <class... Stage> static hipError_t fk_launch(const RzFkParams &p, size_t lds, uint32_t instances, hipStream_t st, const Stage &...stage)
 {
-    const size_t lds = rz_fk_lds_bytes(p);
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_fk_kernel<Stage...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(rz_fk_kernel<Stage...>, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, stage...);
+    return hipGetLastError();
+}
+
+// The hierarchy solve with the stages `s` lists (the after stage is a launch of its own behind it: rz_launch_fk_after). A stage is on
+// when its block is not the empty one its builder returns (plan.cpp: solve_stages); each check applies exactly when its stage is on.
+hipError_t rz_launch_fk(const RzFkParams &p, const RzFkStages &s, uint32_t instances, hipStream_t st)
+{
+    const bool ik = s.ik.n_chains != 0, fo = s.fo.off != nullptr, sw = s.sw.words != 0;
+    const size_t lds = rz_fk_lds_bytes(p, s);
     if (lds > 160 * 1024) return hipErrorInvalidValue;      // (the host checks first and says why: launch_fk in frame.cpp)
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_fk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(rz_fk_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p);
-    return hipGetLastError();
-}
-
-hipError_t rz_launch_fk_follow(const RzFkParams &p, const RzIkParams *ik, const RzFollowParams &fo, uint32_t instances, hipStream_t st)
-{
-    const size_t lds = ik ? rz_fk_ik_lds_bytes(p) : rz_fk_lds_bytes(p);
-    // (the host checks the LDS first and says why: launch_fk in frame.cpp; the stage reads the override table through every entry)
-    if (lds > 160 * 1024 || !fo.off || !fo.ent || !p.ovr_off || (ik && (!ik->chain || ik->n_stages <= 0))) return hipErrorInvalidValue;
-    const void *fn = ik ? reinterpret_cast<const void *>(rz_fk_ik_follow_kernel) : reinterpret_cast<const void *>(rz_fk_follow_kernel);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    if (ik) hipLaunchKernelGGL(rz_fk_ik_follow_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, *ik, fo);
-    else hipLaunchKernelGGL(rz_fk_follow_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, fo);
-    return hipGetLastError();
-}
-
-hipError_t rz_launch_fk_ik_sw(const RzFkParams &p, const RzIkParams &ik, const RzIkSwitchParams &sw, const RzFollowParams *fo, uint32_t instances, hipStream_t st)
-{
-    const size_t lds = rz_fk_ik_lds_bytes(p);
-    // (the host checks the LDS first and says why: launch_fk in frame.cpp; words in the arguments serve one instance only)
-    if (lds > 160 * 1024 || !ik.chain || ik.n_stages <= 0 || sw.words != (ik.n_chains + 31) / 32) return hipErrorInvalidValue;
-    if (!sw.mask && (instances != 1 || sw.words > kRzIkSwInline)) return hipErrorInvalidValue;
-    if (fo && (!fo->off || !fo->ent || !p.ovr_off)) return hipErrorInvalidValue;
-    const void *fn = fo ? reinterpret_cast<const void *>(rz_fk_ik_sw_follow_kernel) : reinterpret_cast<const void *>(rz_fk_ik_sw_kernel);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    if (fo) hipLaunchKernelGGL(rz_fk_ik_sw_follow_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, ik, *fo, sw);
-    else hipLaunchKernelGGL(rz_fk_ik_sw_kernel, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, ik, sw);
-    return hipGetLastError();
+    if (ik && (!s.ik.chain || s.ik.n_stages <= 0)) return hipErrorInvalidValue;
+    // switches belong to an IK table; words in the arguments serve one instance only
+    if (sw && (!ik || s.sw.words != (s.ik.n_chains + 31) / 32 || (!s.sw.mask && (instances != 1 || s.sw.words > kRzIkSwInline)))) return hipErrorInvalidValue;
+    if (fo && (!s.fo.ent || !p.ovr_off)) return hipErrorInvalidValue;       // the stage reads the override table through every entry
+    if (sw) return fo ? fk_launch(p, lds, instances, st, s.ik, s.fo, s.sw) : fk_launch(p, lds, instances, st, s.ik, s.sw);
+    if (ik) return fo ? fk_launch(p, lds, instances, st, s.ik, s.fo) : fk_launch(p, lds, instances, st, s.ik);
+    return fo ? fk_launch(p, lds, instances, st, s.fo) : fk_launch(p, lds, instances, st);
 }
 
 // `src` = device address of the pinned slot: [bones x 48 B of packed matrix columns | raw_bytes carried as they are]; `dst` = the

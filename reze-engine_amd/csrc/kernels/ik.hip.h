@@ -1,4 +1,4 @@
-// kernels/ik.hip.h — PMX inverse kinematics on the device: the stage of rz_fk_ik_kernel (front.hip) between the doubling rounds and the
+// kernels/ik.hip.h — PMX inverse kinematics on the device: the IK stage of rz_fk_kernel (front.hip: the instantiations that receive RzIkParams) between the doubling rounds and the
 // override pass of fk_solve. Included by fk.hip.h in front of fk_solve (inside its namespace and under its contraction pragma: every
 // FMA is spelled out); tests/ik_ref.py is the definition of what it computes.
 //
@@ -169,7 +169,7 @@ __device__ __forceinline__ bool ik_sw_any(const RzIkSwitchParams &sw, const int 
 }
 
 // The IK stage of one pose (its workgroup): `src` holds the world rows of the plain solve; returns the buffer with the solved ones.
-// SW (the rz_fk_ik_sw*_kernel entries; tests/ik_switch_ref.py): the instance's chain switches. A wave skips a chain whose bit is clear (its
+// SW (the instantiations that receive RzIkSwitchParams; tests/ik_switch_ref.py): the instance's chain switches. A wave skips a chain whose bit is clear (its
 // links keep the staged rotations, as a chain with no loops does); a stage none of whose chains is on changes no rotation, so its
 // whole-skeleton solve is skipped as well and `src` stays what the last live stage left; an instance with every bit clear does not enter
 // the loop. The bits are read through wave-uniform addresses and the two stage-level decisions depend on the instance alone: every

@@ -93,11 +93,7 @@ static int step(rz_ctx *c, uint32_t substeps, bool reset)
     // overlapped crowd frames: the hierarchy solve below rewrites the current ring slot's palettes, which the last frame's skin kernel and
     // SDEF / QDEF passes may still be reading on the compute stream (run_frame moves on to the other slot; this solve does not)
     if (c->overlap_on && c->skin_recorded[c->ring_slot]) HIP_TRY(hipStreamWaitEvent(c->up_stream, c->ev_skin[c->ring_slot], 0));
-    const uint32_t saved = c->ovr_count;
-    c->ovr_count = 0;                   // bodies follow (and are reset onto) the SOLVED pose
-    const int r = launch_fk(c, st);
-    c->ovr_count = saved;
-    if (r) return r;
+    if (int r = launch_fk(c, st, false)) return r;      // without overrides: bodies follow (and are reset onto) the SOLVED pose
     HIP_TRY(rz_launch_physics(physics_params(c, substeps, reset), c->I, st, c->ph.aligned.n != 0));
     c->ph.reset = false;
     c->ovr_count = c->I * c->ph.nd;

@@ -194,9 +194,9 @@ Plan make_plan(const rz_ctx *c)
     // mode (and 27.7 -> 24.5 us on a 1/8 shard of C5); local poses 12.7-14.4 -> 9.8-12.8 us without dense morphs, no gain
     // with them (there the three-kernel frame keeps its kernel-argument morph list and streams from its first instruction).
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
-    // (an IK table keeps the solve in a kernel of its own, rz_fk_ik_kernel: the fused kernels carry no IK stage; nor the follow stage of
-    // rz_override_follow, so resident follower entries keep the solve with rz_fk_follow_kernel)
-    pl.fuse_fk = c->ik_n == 0 && !follow_params(c).off && !after_params(c).n && c->I == 1 && c->pl.cur.local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
+    // (the fused kernels' embedded solve carries no stage: any stage of solve_stages — an IK table, resident follower entries, after-physics
+    // bones behind overrides — keeps the solve in rz_fk_kernel, whose instantiations do)
+    pl.fuse_fk = solve_stages(c).plain() && c->I == 1 && c->pl.cur.local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
                  (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pl.cur.sampled || c->morph_mode != 1)));
     const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->pl.cur.ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
@@ -405,7 +405,9 @@ int ensure_run_subsets(rz_ctx *c)
 // Plan of the next frame: the run lists first (the plan only takes the subset form when they match its shape).
 // Can the next crowd frame solve its hierarchy in the skin kernel's front? A device-animated crowd in the bone-subset form, nothing
 // acting on the solved pose between the solve and the palette (bone morphs fold weights in, physics overrides replace world matrices:
-// both stay with rz_fk_kernel; so does the IK stage of rz_fk_ik_kernel), "fuse_fk" not switched off.
+// both stay with rz_fk_kernel; so does its IK stage), "fuse_fk" not switched off. These conditions are its own and stronger than
+// solve_stages(c).plain(): it vetoes on ovr_count and ik_n themselves, before any stage exists (an override table without followers or
+// after-physics bones is no stage, yet the crowd kernel's front has no override write).
 bool subfk_wanted(const rz_ctx *c)
 {
     return c->I > 1 && c->pl.cur.local && c->has_topology && c->t_fusefk != 0 && c->t_subsets != 0 && c->sub_valid && c->sub_max < c->B &&
@@ -534,7 +536,8 @@ RzPrepParams prep_params(const rz_ctx *c)
     return p;
 }
 
-RzFkParams fk_params(const rz_ctx *c)
+// overrides = false: the solve of the pose as it is, without the override table (rz_physics_step: bodies follow the SOLVED pose)
+RzFkParams fk_params(const rz_ctx *c, bool overrides)
 {
     RzFkParams p;
     memset(&p, 0, sizeof p);            // padding too: frame_signature() hashes the struct
@@ -542,7 +545,7 @@ RzFkParams fk_params(const rz_ctx *c)
     p.local_t = c->pl.cur.local_t ? reinterpret_cast<const float *>(p.local_q + (size_t)c->I * c->B) : nullptr;
     p.bone_rec = c->fk_rec; p.anc_more = c->fk_anc_more; p.inv_bind = c->inv_bind;
     p.world = c->world; p.palette = c->palette; p.B = (int)c->B; p.n_rounds = c->fk_rounds;
-    if (c->ovr_count) { p.ovr_off = c->ovr_off; p.ovr_bone = c->ovr_bone; p.ovr_world = c->ovr_world; }
+    if (overrides && c->ovr_count) { p.ovr_off = c->ovr_off; p.ovr_bone = c->ovr_bone; p.ovr_world = c->ovr_world; }
     if (c->bm_count && c->M) {
         p.bm_off = c->bm_off; p.bm_morph = c->bm_morph; p.bm_rot = c->bm_rot; p.bm_tr = c->bm_tr;
         p.bm_w = src_morph_w(c); p.bm_M = (int)c->M;
@@ -559,7 +562,8 @@ RzFkParams fk_params(const rz_ctx *c)
     return p;
 }
 
-RzFollowParams follow_params(const rz_ctx *c)
+// rz_override_follow: null pointers unless the flag is on, overrides are resident and at least one bone follows one
+static RzFollowParams follow_params(const rz_ctx *c)
 {
     RzFollowParams p;
     memset(&p, 0, sizeof p);
@@ -567,7 +571,8 @@ RzFollowParams follow_params(const rz_ctx *c)
     return p;
 }
 
-RzAfterParams after_params(const rz_ctx *c)
+// rz_upload_after_physics: null pointers and n = 0 unless the list is resident AND the override table holds at least one entry
+static RzAfterParams after_params(const rz_ctx *c)
 {
     RzAfterParams p;
     memset(&p, 0, sizeof p);
@@ -631,7 +636,7 @@ int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<i
     return RZ_OK;
 }
 
-RzIkParams ik_params(const rz_ctx *c)
+static RzIkParams ik_params(const rz_ctx *c)
 {
     RzIkParams p;
     memset(&p, 0, sizeof p);
@@ -641,7 +646,8 @@ RzIkParams ik_params(const rz_ctx *c)
     return p;
 }
 
-RzIkSwitchParams ik_switch_params(const rz_ctx *c)
+// chain switches: null mask and words 0 unless at least one bit is clear
+static RzIkSwitchParams ik_switch_params(const rz_ctx *c)
 {
     RzIkSwitchParams p;
     memset(&p, 0, sizeof p);
@@ -651,6 +657,19 @@ RzIkSwitchParams ik_switch_params(const rz_ctx *c)
     if (c->I == 1 && p.words <= kRzIkSwInline) memcpy(p.w0, s.words.data(), (size_t)p.words * sizeof(uint32_t));
     else p.mask = s.dev;
     return p;
+}
+
+// The single statement of which stages the next hierarchy solve runs, made of the builders above: what launch_fk launches, what vetoes
+// the fused frame (make_plan), what keys a captured graph (frame_signature) and what rz_get_tuning("override_followers") reports all
+// read it. overrides = false (see fk_params): no override table, therefore no follow and no after stage; IK and its switches stay.
+RzFkStages solve_stages(const rz_ctx *c, bool overrides)
+{
+    RzFkStages s;
+    memset(&s, 0, sizeof s);            // padding too: frame_signature() hashes the struct
+    s.ik = ik_params(c);
+    s.sw = ik_switch_params(c);
+    if (overrides) { s.fo = follow_params(c); s.af = after_params(c); }
+    return s;
 }
 
 uint64_t algorithmic_bytes(const rz_ctx *c)

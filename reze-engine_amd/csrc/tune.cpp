@@ -268,7 +268,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "physics_aligned_bodies")) *value = (int)c->ph.aligned.n;
     else if (!strcmp(key, "physics_lds")) *value = c->ph.nb ? (int)rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0;
     else if (!strcmp(key, "override_follow")) *value = c->ovr_follow;
-    else if (!strcmp(key, "override_followers")) *value = follow_params(c).off ? (int)c->fol_count : 0;     // entries resident over all instances
+    else if (!strcmp(key, "override_followers")) *value = solve_stages(c).fo.off ? (int)c->fol_count : 0;     // entries resident over all instances
     else if (!strcmp(key, "after_physics")) *value = (int)c->af_n;         // entries resident (rz_upload_after_physics)
     else if (!strcmp(key, "after_physics_levels")) *value = (int)c->af_levels;
     else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;

@@ -1,6 +1,6 @@
 'use strict'
 /* End-to-end IK through the N-API boundary on a PMX + VMD that keys only the centre and the IK goals:
- *   device: new Engine(null, { deviceFK: true, deviceSampling: true, ik: true })   rz_upload_ik, solved by rz_fk_ik_kernel
+ *   device: new Engine(null, { deviceFK: true, deviceSampling: true, ik: true })   rz_upload_ik, solved by rz_fk_kernel<RzIkParams>
  *   host:   new Engine(null, { ik: true })                                         Model.solveIK()
  *   off:    new Engine(null, {})                                                   no IK: the legs do not follow
  * usage: node ik_e2e.js <model.pmx> <motion.vmd> <outdir>. Dumps the deformed positions of every frame, one file per engine. */

@@ -336,7 +336,7 @@ SCENES = {
     "256 joints": lambda: strands(128, 2, base=True, seed=26, n_verts=400, sprung=True),
     "257 joints": lambda: strands(257, 1, base=True, seed=27, n_verts=520, sprung=True),
     # the largest tables the LDS takes
-    # (the hierarchy solve takes 1 412 bones, 116 B of LDS each: 1 000 strands drive bones, the bodies of the other 516 have none)
+    # (the hierarchy solve takes 1 517 bones, 108 B of LDS each: 1 000 strands drive bones, the bodies of the other 516 have none)
     "most strands": lambda: strands(MOST_STRANDS, 1, base=False, seed=28, n_verts=600, sprung=True, boned=1000),
     "most bodies": lambda: falling_bodies(MOST_BODIES),
     "contents": lambda: contents(),

@@ -1,5 +1,5 @@
-"""Bones below an overridden bone follow it on the device (rz_override_follow; kernels/fk.hip.h: FOLLOW, rz_fk_follow_kernel and
-rz_fk_ik_follow_kernel) against the float64 definition tests/follow_ref.py, on the hand-laid scenes of tests/follow_scenes.py.
+"""Bones below an overridden bone follow it on the device (rz_override_follow; kernels/fk.hip.h: FOLLOW, rz_fk_kernel<RzFollowParams> and
+rz_fk_kernel<RzIkParams, RzFollowParams>) against the float64 definition tests/follow_ref.py, on the hand-laid scenes of tests/follow_scenes.py.
 
 Bars: world matrices within 5e-5 x max(1, |ref|) of the definition in float64 — the project's bar for world matrices
 (tests/test_gpu_layers.py, tests/test_gpu_fuzz.py); positions and normals of the scene's mesh, which has vertices on every follower

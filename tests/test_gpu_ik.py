@@ -1,4 +1,4 @@
-"""PMX inverse kinematics on the device (rz_upload_ik, kernels/ik.hip.h: the IK stage of rz_fk_ik_kernel) against the float64 restatement
+"""PMX inverse kinematics on the device (rz_upload_ik, kernels/ik.hip.h: the IK stage of rz_fk_kernel<RzIkParams>) against the float64 restatement
 tests/ik_ref.py, through every pose source and frame form that can carry it.
 
 The bar: world-matrix entries and deformed positions within 1e-4 x the skeleton's extent of the float64 restatement (1e-4 is the project's

@@ -1,5 +1,5 @@
 """Per-instance switches of the IK chains on the device (rz_set_ik_enabled / rz_upload_ik_keys / rz_read_ik_enabled; kernels/ik.hip.h:
-ik_stage<SW>, rz_fk_ik_sw_kernel and rz_fk_ik_sw_follow_kernel) against the float64 definition tests/ik_switch_ref.py, on the scenes and
+ik_stage<SW>, rz_fk_kernel<RzIkParams, RzIkSwitchParams> and <RzIkParams, RzFollowParams, RzIkSwitchParams>) against the float64 definition tests/ik_switch_ref.py, on the scenes and
 key tracks of tests/ik_switch_scenes.py.
 
 Bars, the IK suite's own (tests/test_gpu_ik.py): world-matrix entries and positions within 1e-4 x the skeleton's extent of the definition,
@@ -236,7 +236,7 @@ def same(a, b):
 
 
 def test_bit_identities(rz):
-    """an all-on instance inside a crowd that runs the switched entry is the pose run alone under rz_fk_ik_kernel; an all-off instance is, in
+    """an all-on instance inside a crowd that runs the switched instantiation is the pose run alone under rz_fk_kernel<RzIkParams>; an all-off instance is, in
     world matrices, the pose on a context whose table was removed; a mask of all ones leaves ik_switched at 0 and is the parent path's bits"""
     s = sc.scene("leg rig, crowd of 3")
     m, chains, poses = s["mesh"], s["chains"], s["poses"][:3]
@@ -303,7 +303,7 @@ def test_composition_follow_bone_morphs_replays_fork(rz, oracle):
         c.deform_n(40)
         assert same(frame_of(c), alone), "graph replay after the mask came back"
         c.set_tuning(graph=0)
-        # override on the left knee with followers below it: rz_fk_ik_sw_follow_kernel
+        # override on the left knee with followers below it: rz_fk_kernel<RzIkParams, RzFollowParams, RzIkSwitchParams>
         ov = np.eye(4)
         ov[:3, 3] = (2.0, 5.0, 1.0)
         ov16 = ov.T.reshape(1, 16).astype(np.float32)

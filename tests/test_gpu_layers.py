@@ -237,7 +237,7 @@ def test_big_pose_ring(rz):
 
 def test_downstream_ik(rz):
     """The leg rig with its IK table: the layered pose on the device against rz_set_pose_local of the float64 layered pose cast to f32, both
-    through rz_fk_ik_kernel. Bar: IK's own, 1e-4 of the skeleton's extent (tests/test_gpu_ik.py)."""
+    through rz_fk_kernel<RzIkParams>. Bar: IK's own, 1e-4 of the skeleton's extent (tests/test_gpu_ik.py)."""
     import ik_ref
     s = ls.leg_scene()
     m = s["mesh"]

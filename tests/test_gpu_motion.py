@@ -220,7 +220,7 @@ def test_second_chunk_of_morphs_on_the_single_character_path(rz, oracle):
 
 def test_downstream_ik(rz):
     """The leg rig with its IK table: the pose blended on the device against rz_set_pose_local of the float64 blend cast to f32, both through
-    rz_fk_ik_kernel. Bar: IK's own, 1e-4 of the skeleton's extent (tests/test_gpu_ik.py)."""
+    rz_fk_kernel<RzIkParams>. Bar: IK's own, 1e-4 of the skeleton's extent (tests/test_gpu_ik.py)."""
     import ik_ref
     s = ms.leg_scene()
     m = s["mesh"]

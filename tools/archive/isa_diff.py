@@ -1,14 +1,17 @@
 """Compare two directories of normalised per-kernel disassembly (tools/archive/isa_dump.sh): for every kernel of the NEW directory, the kernel it
-replaces in the OLD one (rz_deform_kernel<S,U,MODE,NT,NTS,GEO,FAST> was split into rz_deform_dense_kernel<S,U,NT,NTS,GEO,FAST> and
-rz_deform_small_kernel<S,MODE,NTS,GEO,FAST>), identical or not, instruction counts, and the mnemonic histogram differences."""
-import collections, difflib, os, re, sys
+replaces in the OLD one (the hierarchy solve's six hand-written entries of kernels/front.hip became the six instantiations of
+rz_fk_kernel<Stage...>), identical or not, instruction counts, and the mnemonic histogram differences."""
+import collections, difflib, os, sys
 old, new = sys.argv[1], sys.argv[2]
-def old_name(n):
-    m = re.match(r"rz_deform_dense_kernel<(\d+),(\d+),(\w+),(\w+),(\w+),(\w+)>", n)
-    if m: return "rz_deform_kernel<%s,%s,1,%s,%s,%s,%s>" % m.groups()
-    m = re.match(r"rz_deform_small_kernel<(\d+),(\d+),(\w+),(\w+),(\w+)>", n)
-    if m: return "rz_deform_kernel<%s,1,%s,false,%s,%s,%s>" % m.groups()
-    return n
+OLD_NAME = {
+    "rz_fk_kernel<>": "rz_fk_kernel",
+    "rz_fk_kernel<RzIkParams>": "rz_fk_ik_kernel",
+    "rz_fk_kernel<RzFollowParams>": "rz_fk_follow_kernel",
+    "rz_fk_kernel<RzIkParams,RzFollowParams>": "rz_fk_ik_follow_kernel",
+    "rz_fk_kernel<RzIkParams,RzIkSwitchParams>": "rz_fk_ik_sw_kernel",
+    "rz_fk_kernel<RzIkParams,RzFollowParams,RzIkSwitchParams>": "rz_fk_ik_sw_follow_kernel",
+}
+def old_name(n): return OLD_NAME.get(n, n)
 same = diff = 0
 for f in sorted(os.listdir(new)):
     n = f[:-2]

@@ -6,7 +6,7 @@
 OUT=$1; shift
 FL=()
 while [ "$1" != "--" ]; do FL+=("$1"); shift; done; shift
-D=$(cd "$(dirname "$0")/../reze-engine_amd/csrc" && pwd)
+D=$(cd "$(dirname "$0")/../../reze-engine_amd/csrc" && pwd)
 mkdir -p $OUT; T=$(mktemp -d)
 for F in "$@"; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-kernarg-preload-count=16 -I$D "${FL[@]}" --offload-device-only -c "$F" -o $T/k.co || exit 1
@@ -23,7 +23,7 @@ for line in sys.stdin:
     if cur is None: continue
     t = re.sub(r"\s*//.*$", "", line.rstrip())
     t = re.sub(r"^\s+", "", t)
-    if t: cur.append(t)
+    if t and t != "...": cur.append(t)      # ("..." is objdump for the zero fill between two kernels: placement, not code)
 names = list(syms)
 dem = subprocess.check_output(["c++filt"] + names).decode().splitlines()
 for n, d in zip(names, dem):

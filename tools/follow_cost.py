@@ -1,4 +1,4 @@
-"""What rz_override_follow (the FOLLOW stage of the hierarchy solve: rz_fk_follow_kernel instead of rz_fk_kernel) adds to a live frame.
+"""What rz_override_follow (the FOLLOW stage of the hierarchy solve: rz_fk_kernel<RzFollowParams> instead of rz_fk_kernel<>) adds to a live frame.
   python tools/follow_cost.py [rounds]          (writes profiles/follow_cost.txt)
 The loop a live application runs: a new local pose (rz_set_pose_local), rz_physics_step(1) and the frame (rz_deform), on the strands of
 tests/follow_scenes.py's scene (j) — 21 bodies, 18 overridden bones, 5 follower bones per instance — for one character and for a crowd of

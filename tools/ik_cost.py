@@ -1,4 +1,4 @@
-"""What the IK stage (rz_upload_ik, kernels/ik.hip.h: rz_fk_ik_kernel instead of the fused / one-launch hierarchy solve) adds to a
+"""What the IK stage (rz_upload_ik, kernels/ik.hip.h: rz_fk_kernel<RzIkParams> instead of the fused / one-launch hierarchy solve) adds to a
 device-animated frame, and how far the device solve is from the float64 restatement (tests/ik_ref.py).
   python tools/ik_cost.py [rounds] [--parent LIB]
 Shapes: the demo-shaped 28 842-vertex character (sparse morphs, an uploaded local pose) and C4 as a sampled crowd (256 characters, each at

@@ -1,8 +1,8 @@
-"""What the per-instance IK chain switches (rz_set_ik_enabled; rz_fk_ik_sw_kernel instead of rz_fk_ik_kernel) cost and save in a live frame.
+"""What the per-instance IK chain switches (rz_set_ik_enabled; rz_fk_kernel<RzIkParams, RzIkSwitchParams> instead of rz_fk_kernel<RzIkParams>) cost and save in a live frame.
   python tools/ik_switch_cost.py [rounds]          (writes profiles/ik_switch_cost.txt)
 The loop a live application runs: a new local pose (rz_set_pose_local) and the frame (rz_deform), on synth.make_leg_rig (14 bones, four
 chains in two stages, 3000 vertices) for one character and for a crowd of 256, under three masks: all on (the parent commit's kernel: a mask
-of all ones launches rz_fk_ik_kernel), half the instances all off (one character: the two leg chains off, the toe chains on), every
+of all ones launches rz_fk_kernel<RzIkParams>), half the instances all off (one character: the two leg chains off, the toe chains on), every
 instance all off. Every measurement runs in a fresh process (this script starts itself with `--one`), `rounds` (default 5) rounds alternate
 the order of the three masks, the median is printed with every round beside it. One measurement: warm-up frames, then FRAMES frames by the
 host's clock around a drained stream. No bar is set: this is a record of what a skipped chain and a skipped stage save."""
@@ -64,7 +64,7 @@ def main():
         return one(int(sys.argv[2]), int(sys.argv[3]))
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
     lines = ["live frame (rz_set_pose_local + rz_deform) in us (host clock over %d frames around a drained stream, after %d warm-up frames; every"
-             " measurement in a fresh process; median of %d alternated rounds). All on = the parent commit's kernel (rz_fk_ik_kernel)." % (FRAMES, WARM, rounds),
+             " measurement in a fresh process; median of %d alternated rounds). All on = the solve without the switch stage (rz_fk_kernel<RzIkParams>)." % (FRAMES, WARM, rounds),
              "scene    shape         chains stages | all on  half off (bits)  all off (bits) | rounds"]
     for shape, instances in SHAPES:
         t_us, info = {k: [] for k in range(3)}, {}
