@@ -334,7 +334,7 @@ int rz_set_pose_sampled(rz_ctx *ctx, const float *frames);
  *     above 0.9995, sine form otherwise),  t = ta + (tb - ta) * blend;  per vertex morph  w = wa + (wb - wa) * blend  on the effective
  *     weights (own track, then group feeds). clip_a == clip_b is legal: two times of one motion.
  * The result is a device-resident local pose with translations; from there the frame is an rz_set_pose_local frame: bone morphs ->
- * hierarchy -> IK (with a table) -> overrides -> palette -> deform / skin -> the SDEF and QDEF passes. rz_motion_blend_kernel runs ONCE per
+ * hierarchy -> IK (with a table) -> overrides -> palette -> deform / skin -> the SDEF and QDEF passes. rz_motion_kernel runs ONCE per
  * call, in front of the frame, on the stream a copied pose of the same size would have travelled on, into the pose block that copy would
  * have taken; rz_deform_n, graph replays and rz_time_span replay the resident pose. No host synchronisation; one character's state rides
  * in the kernel arguments, a crowd's states go through a slot of the pinned ring.
@@ -364,7 +364,7 @@ int rz_set_pose_blended(rz_ctx *ctx, const rz_motion_state *states);
  *      uploaded without morph masks include every morph); wL = the effective weight (own track, then group feeds):
  *        OVERRIDE   w = w + (wL - w) * weight, at weight == 1 w IS wL;   ADDITIVE   w = w + wL * weight
  *   5. n_layers == 0, or every layer skipped, gives the bits of rz_set_pose_blended(base).
- * The result is written where rz_set_pose_blended writes it (rz_motion_layer_kernel, once per call, same pose block, stream and event);
+ * The result is written where rz_set_pose_blended writes it (rz_motion_kernel with layers, once per call, same pose block, stream and event);
  * every frame behind it is an rz_set_pose_local frame and replays do not sample again. One character's state and layers ride in the
  * kernel arguments (100 bytes), a crowd's I x (20 + 20 n_layers) bytes go through a slot of the pinned ring.
  * rz_upload_motion_masks: n_masks masks, one byte per bone (non-zero = included), and optionally one byte per vertex morph; static data

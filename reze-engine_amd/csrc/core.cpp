@@ -175,13 +175,18 @@ int ensure_pose_buffers(rz_ctx *c)
     return RZ_OK;
 }
 
+void free_keys(RzStatic::RzKeys &k)
+{
+    dfree(k.key_frame); dfree(k.key_rot); dfree(k.key_pos); dfree(k.key_interp); dfree(k.mkey_frame); dfree(k.mkey_weight);
+    dfree(k.feed_off); dfree(k.feed_range); dfree(k.feed_ratio);
+    k.M = 0;
+}
+
 void free_animation(rz_ctx *c)
 {
     drop_graph(c);
-    dfree(c->an_feed_range); dfree(c->an_feed_off);
+    free_keys(c->an);
     c->an_host_range.clear(); c->an_host_mrec.clear();
-    dfree(c->an_key_frame); dfree(c->an_key_pos); dfree(c->an_mkey_frame); dfree(c->an_mkey_weight); dfree(c->an_feed_ratio);
-    dfree(c->an_key_rot); dfree(c->an_key_interp);
     c->has_animation = false;
     c->ik_keys_an = {};                 // rz_upload_ik_keys(RZ_NO_CLIP): the keys of this motion
     if (c->pl.cur.sampled) { c->pl.cur.sampled = false; c->pl.cur.set = false; }
@@ -189,19 +194,19 @@ void free_animation(rz_ctx *c)
 
 void free_motions(rz_ctx *c)
 {
-    if (c->mo_clips) {                    // rz_motion_blend_kernel reads the library on whichever stream the pose travelled on
+    if (c->mo_clips) {                    // rz_motion_kernel reads the library on whichever stream the pose travelled on
         if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }
-    dfree(c->mo_bone_rec); dfree(c->mo_feed_off); dfree(c->mo_feed_range); dfree(c->mo_key_interp);
-    dfree(c->mo_key_frame); dfree(c->mo_key_pos); dfree(c->mo_mkey_frame); dfree(c->mo_mkey_weight); dfree(c->mo_feed_ratio); dfree(c->mo_key_rot);
-    c->mo_clips = 0; c->mo_M = 0;
+    free_keys(c->mo);
+    dfree(c->mo_bone_rec);
+    c->mo_clips = 0;
     c->ik_keys_mo.clear();              // rz_upload_ik_keys(clip): the keys of this library's clips
 }
 
 void free_motion_masks(rz_ctx *c)
 {
-    if (c->mk_count) {                    // rz_motion_layer_kernel reads the masks on whichever stream the pose travelled on
+    if (c->mk_count) {                    // rz_motion_kernel reads the masks on whichever stream the pose travelled on
         if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }

@@ -31,6 +31,7 @@
 
 #include "deform_kernels.h"
 #include "after_table.h"
+#include "motion_table.h"
 #include "physics_table.h"
 #include "pose_ring.h"
 
@@ -155,29 +156,30 @@ struct RzStatic {
     // optional topology for on-device FK
     bool has_topology = false;
     // the hierarchy's static block (kernels/fk.hip.h): [B][4] bone records (topology | bind | the motion's track | ancestors of the first
-    // two doubling rounds) + [an_M][2] vertex-morph records; rebuilt by rebuild_fk_static when the topology or the motion changes
+    // two doubling rounds) + [an.M][2] vertex-morph records; rebuilt by rebuild_fk_static when the topology or the motion changes
     uint4 *fk_rec = nullptr;
     uint2 *fk_anc_more = nullptr;       // [fk_rounds - 2][B] ancestor tables of the doubling rounds beyond the second (depth > 16)
     int fk_rounds = 0;                  // radix-4 doubling rounds = ceil(log4(depth))
     std::vector<uint4> fk_host;         // host copy of the bone records (w2 is filled in from an_host_range)
-    std::vector<uint4> an_host_range, an_host_mrec;     // the motion's per-bone track records / per-morph records (host copies)
-    // device-side motion sampling (rz_upload_animation / rz_set_pose_sampled)
+    // The motion stores: the single motion (rz_upload_animation / rz_set_pose_sampled, sampled inside rz_fk_kernel) and the motion library
+    // (rz_upload_motions / rz_set_pose_blended / rz_set_pose_layered; kernels/motion.hip) are the same arrays — motion_table.h's flattening of
+    // one clip, or of all clips concatenated with absolute indices — independent of each other. Raw pointers, not Scratch: a fork borrows
+    // RzStatic by copying the struct and Scratch is move-only; free_keys (core.cpp) is the one release list.
+    struct RzKeys {
+        float *key_frame = nullptr, *key_pos = nullptr, *mkey_frame = nullptr, *mkey_weight = nullptr, *feed_ratio = nullptr;
+        float4 *key_rot = nullptr;
+        uint4 *key_interp = nullptr;    // null: no clip carries interpolation bytes
+        uint32_t *feed_off = nullptr;   // [clips][M + 1]
+        uint4 *feed_range = nullptr;    // (first key, end, first frame, last frame) per morph feed
+        uint32_t M = 0;                 // vertex-morph count the feeds were built for
+    };
+    RzKeys an;
     bool has_animation = false;
-    uint4 *an_feed_range = nullptr;     // (first key, end, first frame, last frame) per morph feed
-    uint32_t *an_feed_off = nullptr;
-    float *an_key_frame = nullptr, *an_key_pos = nullptr, *an_mkey_frame = nullptr, *an_mkey_weight = nullptr, *an_feed_ratio = nullptr;
-    float4 *an_key_rot = nullptr;
-    uint4 *an_key_interp = nullptr;
-    uint32_t an_M = 0;                  // vertex-morph count the feeds were built for
-    // the motion library (rz_upload_motions / rz_set_pose_blended; kernels/motion.hip): the keys of all clips concatenated, per clip one
-    // 16-byte track record per bone and M + 1 feed offsets. Independent of the single motion above; borrowed by forks.
-    uint32_t mo_clips = 0, mo_M = 0;    // clips resident (0 = no library) / vertex-morph count the feeds were built for
-    uint4 *mo_bone_rec = nullptr;       // [mo_clips][B]
-    uint32_t *mo_feed_off = nullptr;    // [mo_clips][mo_M + 1]
-    uint4 *mo_feed_range = nullptr, *mo_key_interp = nullptr;
-    float *mo_key_frame = nullptr, *mo_key_pos = nullptr, *mo_mkey_frame = nullptr, *mo_mkey_weight = nullptr, *mo_feed_ratio = nullptr;
-    float4 *mo_key_rot = nullptr;
-    // the masks of layered poses (rz_upload_motion_masks / rz_set_pose_layered; kernels/motion_layers.hip): bit sets, one 32-bit word per 32
+    std::vector<uint4> an_host_range, an_host_mrec;     // the motion's per-bone track records / per-morph records (host copies)
+    RzKeys mo;
+    uint32_t mo_clips = 0;              // clips resident (0 = no library)
+    uint4 *mo_bone_rec = nullptr;       // [mo_clips][B] per clip one 16-byte track record per bone
+    // the masks of layered poses (rz_upload_motion_masks / rz_set_pose_layered; kernels/motion.hip): bit sets, one 32-bit word per 32
     // bones / vertex morphs, mk_bone_words / mk_morph_words words per mask. mk_morph_bits null: every mask includes every morph.
     uint32_t mk_count = 0, mk_M = 0;    // masks resident (0 = none) / vertex-morph count the morph masks were built for
     uint32_t *mk_bone_bits = nullptr, *mk_morph_bits = nullptr;
@@ -512,6 +514,8 @@ void set_ring(rz_ctx *c, int slot);
 void point_pose_slot(rz_ctx *c, int k);
 void point_pose_at(rz_ctx *c, float *block);     // the current pose lives in `block` (pose_blk[k] or a block of the big-pose ring)
 int ensure_pose_buffers(rz_ctx *c);
+void free_keys(RzStatic::RzKeys &k);
+RzSampleParams sample_params(const RzStatic::RzKeys &k);      // plan.cpp: the sampler's block with the store's pointers set, everything else zero
 void free_animation(rz_ctx *c);
 void free_motions(rz_ctx *c);
 void free_motion_masks(rz_ctx *c);

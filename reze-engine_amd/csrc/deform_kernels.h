@@ -296,8 +296,9 @@ struct RzQdefParams {
 size_t rz_qdef_lds_bytes(int B);       // dynamic LDS of the pass: the skeleton's dual quaternions, 32 B per bone
 hipError_t rz_launch_qdef(const RzQdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st);
 
-// rz_motion_blend_kernel (kernels/motion.hip): the local pose of every instance from a library of resident motions, in front of the frame
-// (rz_upload_motions / rz_set_pose_blended). A kernel of its own: the frame kernels and rz_fk_kernel see a resident local pose.
+// rz_motion_kernel<P> (kernels/motion.hip): the local pose of every instance from a library of resident motions, in front of the frame. One
+// entry, instantiated for the two parameter blocks below: RzMotionParams, the cross-fade alone (rz_upload_motions / rz_set_pose_blended),
+// and RzLayerParams, the cross-fade with layers on top. A kernel of its own: the frame kernels and rz_fk_kernel see a resident local pose.
 struct RzMotionState {          // = rz_motion_state of the C ABI (pose.cpp asserts the layout)
     uint32_t clip_a; float frame_a;
     uint32_t clip_b; float frame_b;     // clip_b = kRzNoClip: there is no second clip
@@ -310,18 +311,17 @@ struct RzMotionParams {
     const uint4 *bone_rec;          // [n_clips][B] track of each bone in each clip: word 2 of the hierarchy's bone record (first key, end, bits(first
                                     //              frame), bits(last frame)), key indices absolute in the concatenated key arrays
     const uint32_t *feed_off;       // [n_clips][M + 1] per clip and vertex morph: its feeds in the concatenated feed arrays
-    RzSampleParams sample;          // the concatenated keys / morph keys / feeds of all clips (frames, feed_off, morph_w, M unused)
+    RzSampleParams sample;          // the concatenated keys / morph keys / feeds of all clips (frames, morph_w, M unused; feed_off = the array above)
     float4 *local_q;                // [I][B] out: the local-pose part of a pose block ...
     float *local_t;                 // [I][B][3]
     float *morph_w;                 // [I][M]
     int B;
     int M;
 };
-hipError_t rz_launch_motion_blend(const RzMotionParams &p, uint32_t instances, hipStream_t st);
 
-// rz_motion_layer_kernel (kernels/motion_layers.hip): the cross-fade above, then up to kRzMaxLayers layers per instance — one clip each at its
-// own frame with a weight, an optional bone / morph mask and a mode (rz_upload_motion_masks / rz_set_pose_layered). It writes what
-// rz_motion_blend_kernel writes, where it writes it; rz_set_pose_blended keeps launching that kernel.
+// The cross-fade above, then up to kRzMaxLayers layers per instance — one clip each at its own frame with a weight, an optional bone / morph
+// mask and a mode (rz_upload_motion_masks / rz_set_pose_layered). With no live layer it writes what the instantiation without layers
+// writes, bit for bit, where that writes it; rz_set_pose_blended keeps launching the one without.
 constexpr int kRzMaxLayers = 4;
 constexpr uint32_t kRzNoMask = 0xffffffffu;
 struct RzMotionLayer {          // = rz_motion_layer of the C ABI (pose.cpp asserts the layout)
@@ -331,7 +331,7 @@ struct RzMotionLayer {          // = rz_motion_layer of the C ABI (pose.cpp asse
     uint32_t mode;                      // 0 override, 1 additive
 };
 struct RzLayerParams {
-    RzMotionParams m;               // the library, the base states ([I] or state0) and the output, as the blend kernel takes them
+    RzMotionParams m;               // the library, the base states ([I] or state0) and the output, as the instantiation without layers takes them
     const RzMotionLayer *layers;    // [I][n_layers] on the device, or null: one character, the layers ride in the kernel arguments (layers0)
     RzMotionLayer layers0[kRzMaxLayers];
     int n_layers;
@@ -339,7 +339,8 @@ struct RzLayerParams {
     const uint32_t *morph_bits;     // [n_masks][morph_words], or null: every mask includes every morph
     int bone_words, morph_words;
 };
-hipError_t rz_launch_motion_layers(const RzLayerParams &p, uint32_t instances, hipStream_t st);
+hipError_t rz_launch_motion(const RzMotionParams &p, uint32_t instances, hipStream_t st);      // rz_motion_kernel<RzMotionParams>
+hipError_t rz_launch_motion(const RzLayerParams &p, uint32_t instances, hipStream_t st);       // rz_motion_kernel<RzLayerParams>
 
 // rz_physics_kernel (kernels/physics.hip): rigid bodies and joints of every instance advanced by `substeps` fixed steps, one workgroup per
 // instance, in front of the frame (rz_upload_physics / rz_physics_step). It reads the world matrices the hierarchy solve left in memory and

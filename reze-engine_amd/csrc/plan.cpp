@@ -127,7 +127,7 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
         p.fk = fk_params(c); p.fk_on = 1;
         // the specialised variants (fk_solve<true, KIND>): no physics overrides, two bones per thread, one morph per thread;
         // "fuse_fk_plain" = 0 keeps the generic kernel (A/B, tests)
-        const bool plain = c->t_fkplain != 0 && !p.fk.ovr_off && c->B <= 512 && c->M <= 256 && (!c->pl.cur.sampled || c->an_M <= 256);
+        const bool plain = c->t_fkplain != 0 && !p.fk.ovr_off && c->B <= 512 && c->M <= 256 && (!c->pl.cur.sampled || c->an.M <= 256);
         p.fk_kind = plain ? (c->pl.cur.sampled ? 2 : 1) : 0;
         if (c->pl.cur.zc_slot >= 0 && c->pl.cur.zc_local && !c->pl.cur.sampled && (!c->pl.cur.local_resident || !c->pl.cur.mw_resident)) {
             // zero-copy local pose, first frame: workgroup 0 makes it resident (every later frame of this pose reads the device
@@ -536,6 +536,16 @@ RzPrepParams prep_params(const rz_ctx *c)
     return p;
 }
 
+RzSampleParams sample_params(const RzStatic::RzKeys &k)
+{
+    RzSampleParams q;
+    memset(&q, 0, sizeof q);            // padding too: fk_params() hands it to frame_signature()
+    q.key_frame = k.key_frame; q.key_rot = k.key_rot; q.key_pos = k.key_pos; q.key_interp = k.key_interp;
+    q.mkey_frame = k.mkey_frame; q.mkey_weight = k.mkey_weight;
+    q.feed_off = k.feed_off; q.feed_range = k.feed_range; q.feed_ratio = k.feed_ratio;
+    return q;
+}
+
 // overrides = false: the solve of the pose as it is, without the override table (rz_physics_step: bodies follow the SOLVED pose)
 RzFkParams fk_params(const rz_ctx *c, bool overrides)
 {
@@ -551,12 +561,8 @@ RzFkParams fk_params(const rz_ctx *c, bool overrides)
         p.bm_w = src_morph_w(c); p.bm_M = (int)c->M;
     }
     if (c->pl.cur.sampled) {
-        RzSampleParams &q = p.sample;
+        RzSampleParams &q = p.sample = sample_params(c->an);
         q.frames = c->pl.cur.frames_inline ? nullptr : c->pl.an_frames.p; q.frames_inline = c->pl.cur.frames_inline ? 1 : 0; q.frame0 = c->pl.cur.frame0;
-        q.key_frame = c->an_key_frame;
-        q.key_rot = c->an_key_rot; q.key_pos = c->an_key_pos; q.key_interp = c->an_key_interp;
-        q.mkey_frame = c->an_mkey_frame; q.mkey_weight = c->an_mkey_weight;
-        q.feed_off = c->an_feed_off; q.feed_range = c->an_feed_range; q.feed_ratio = c->an_feed_ratio;
         q.morph_w = c->morph_w; q.M = (int)c->M;
     }
     return p;

@@ -631,19 +631,17 @@ int rz_set_pose_local(rz_ctx *c, const float *local_rotations4, const float *loc
                        morph_weights);
 }
 
-static bool finite_f(float x) { return x == x && x - x == 0.0f; }
-
 int rz_set_pose_sampled(rz_ctx *c, const float *frames)
 {
     if (int r = use(c)) return r;
     if (!c->has_animation) return fail(RZ_ERR_INVALID, "rz_upload_animation has not been called");
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
-    if (c->an_M != c->M) return fail(RZ_ERR_INVALID, "the motion's morph feeds were built for %u vertex morphs, the context holds %u", c->an_M, c->M);
+    if (c->an.M != c->M) return fail(RZ_ERR_INVALID, "the motion's morph feeds were built for %u vertex morphs, the context holds %u", c->an.M, c->M);
     if (!frames) return fail(RZ_ERR_INVALID, "null frames");
     // refused before anything of the resident pose is touched (the wording of rz_set_pose_blended): the span guess turns the frame into a
     // key index, which is undefined for a NaN or an infinite frame
     for (uint32_t i = 0; i < c->I; ++i)
-        if (!finite_f(frames[i])) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
+        if (!rzmotion::finite(frames[i])) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
     IkWordsPlan sw;
     if (c->ik_n && c->ik_keys_an.resident) {        // the motion's IK on/off keys: every instance's switches at its frame
         const uint32_t W = ik_sw_words(c);
@@ -675,7 +673,7 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
 }
 
 // A pose blended on the device out of the motion library (kernels/motion.hip). It takes the pose block a COPIED local pose of the same size
-// would take — the other block of pose_blk, or a block of the big-pose ring above 256 KB — and rz_motion_blend_kernel writes it there on the
+// would take — the other block of pose_blk, or a block of the big-pose ring above 256 KB — and rz_motion_kernel writes it there on the
 // stream that copy would have travelled on, followed by the event that copy would have recorded (copy_send). The context is left exactly as
 // after such a copy: a resident local pose with translations. A state that is refused is refused before anything of the resident pose is
 // touched; a device error after that (a staging slot, a block of the ring) leaves the context without a pose, as it does in rz_upload_pose.
@@ -684,11 +682,11 @@ static int check_motion_states(const rz_ctx *c, const RzMotionState *sv)
 {
     for (uint32_t i = 0; i < c->I; ++i) {
         const RzMotionState &s = sv[i];
-        if (!finite_f(s.blend) || s.blend < 0.0f || s.blend > 1.0f) return fail(RZ_ERR_INVALID, "instance %u: blend %g is not in [0, 1]", i, (double)s.blend);
+        if (!rzmotion::finite(s.blend) || s.blend < 0.0f || s.blend > 1.0f) return fail(RZ_ERR_INVALID, "instance %u: blend %g is not in [0, 1]", i, (double)s.blend);
         const bool has_b = s.clip_b != kRzNoClip && s.blend != 0.0f, use_a = !(has_b && s.blend == 1.0f);
         if (s.clip_a >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u: clip_a %u of %u", i, s.clip_a, c->mo_clips);
         if (s.clip_b != kRzNoClip && s.clip_b >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u: clip_b %u of %u", i, s.clip_b, c->mo_clips);
-        if ((use_a && !finite_f(s.frame_a)) || (has_b && !finite_f(s.frame_b))) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
+        if ((use_a && !rzmotion::finite(s.frame_a)) || (has_b && !rzmotion::finite(s.frame_b))) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
     }
     return RZ_OK;
 }
@@ -703,10 +701,10 @@ static int check_motion_layers(const rz_ctx *c, uint32_t n_layers, const RzMotio
         for (uint32_t l = 0; l < n_layers; ++l) {
             const RzMotionLayer &y = lv[(size_t)i * n_layers + l];
             if (y.clip == kRzNoClip || y.weight == 0.0f) continue;
-            if (!finite_f(y.weight) || y.weight < 0.0f || y.weight > 1.0f) return fail(RZ_ERR_INVALID, "instance %u layer %u: weight %g is not in [0, 1]", i, l, (double)y.weight);
+            if (!rzmotion::finite(y.weight) || y.weight < 0.0f || y.weight > 1.0f) return fail(RZ_ERR_INVALID, "instance %u layer %u: weight %g is not in [0, 1]", i, l, (double)y.weight);
             if (y.clip >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u layer %u: clip %u of %u", i, l, y.clip, c->mo_clips);
             if (y.mode > 1u) return fail(RZ_ERR_INVALID, "instance %u layer %u: mode %u is neither RZ_LAYER_OVERRIDE nor RZ_LAYER_ADDITIVE", i, l, y.mode);
-            if (!finite_f(y.frame)) return fail(RZ_ERR_INVALID, "instance %u layer %u: the frame is not finite", i, l);
+            if (!rzmotion::finite(y.frame)) return fail(RZ_ERR_INVALID, "instance %u layer %u: the frame is not finite", i, l);
             if (y.mask != kRzNoMask) {
                 if (y.mask >= c->mk_count) return fail(RZ_ERR_INVALID, "instance %u layer %u: mask %u of %u", i, l, y.mask, c->mk_count);
                 if (c->mk_M != c->M)
@@ -716,15 +714,15 @@ static int check_motion_layers(const rz_ctx *c, uint32_t n_layers, const RzMotio
     return RZ_OK;
 }
 
-// rz_set_pose_blended and rz_set_pose_layered: one path. `layered` picks the kernel (rz_set_pose_blended launches rz_motion_blend_kernel, as
-// ever) and what travels: the states alone into mo_states, or the states with the layers behind them — I x 20 x (1 + n_layers) bytes, one
+// rz_set_pose_blended and rz_set_pose_layered: one path. `layered` picks the instantiation of rz_motion_kernel (rz_set_pose_blended launches the
+// one without layers, as ever) and what travels: the states alone into mo_states, or the states with the layers behind them — I x 20 x (1 + n_layers) bytes, one
 // ring slot, one copy — into mo_layers.
 static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, uint32_t n_layers, const rz_motion_layer *layers)
 {
     if (int r = use(c)) return r;
     if (!c->mo_clips) return fail(RZ_ERR_INVALID, "rz_upload_motions has not been called");
     if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
-    if (c->mo_M != c->M) return fail(RZ_ERR_INVALID, "the library's morph feeds were built for %u vertex morphs, the context holds %u: upload it again", c->mo_M, c->M);
+    if (c->mo.M != c->M) return fail(RZ_ERR_INVALID, "the library's morph feeds were built for %u vertex morphs, the context holds %u: upload it again", c->mo.M, c->M);
     if (!states) return fail(RZ_ERR_INVALID, "null motion states");
     if (n_layers > (uint32_t)kRzMaxLayers) return fail(RZ_ERR_INVALID, "%u layers: at most %d", n_layers, kRzMaxLayers);
     if (n_layers && !layers) return fail(RZ_ERR_INVALID, "null motion layers");
@@ -804,20 +802,16 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
         HIP_TRY(hipMemcpyAsync(pl.mo_states, pl.stage.slot[slot].host, (size_t)c->I * sizeof(RzMotionState), hipMemcpyHostToDevice, us));
         mp.states = pl.mo_states;
     }
-    mp.bone_rec = c->mo_bone_rec; mp.feed_off = c->mo_feed_off;
-    mp.sample.key_frame = c->mo_key_frame; mp.sample.key_rot = c->mo_key_rot; mp.sample.key_pos = c->mo_key_pos; mp.sample.key_interp = c->mo_key_interp;
-    mp.sample.mkey_frame = c->mo_mkey_frame; mp.sample.mkey_weight = c->mo_mkey_weight;
-    mp.sample.feed_range = c->mo_feed_range; mp.sample.feed_ratio = c->mo_feed_ratio;
+    mp.bone_rec = c->mo_bone_rec; mp.feed_off = c->mo.feed_off;
+    mp.sample = sample_params(c->mo);
     mp.local_q = c->local_q; mp.local_t = reinterpret_cast<float *>(c->local_q + nq); mp.morph_w = c->morph_w;
     mp.B = (int)c->B; mp.M = (int)c->M;
     if (layered) {
         lp.n_layers = (int)n_layers;
         lp.bone_bits = c->mk_bone_bits; lp.bone_words = (int)c->mk_bone_words;
         lp.morph_bits = c->mk_M == c->M ? c->mk_morph_bits : nullptr; lp.morph_words = (int)c->mk_morph_words;      // (masks of another morph set: no layer names one)
-        HIP_TRY(rz_launch_motion_layers(lp, c->I, us));
-    } else {
-        HIP_TRY(rz_launch_motion_blend(mp, c->I, us));
     }
+    HIP_TRY(layered ? rz_launch_motion(lp, c->I, us) : rz_launch_motion(mp, c->I, us));
     pl.last_pulled = false; pl.last_rows = false;
     if (slot >= 0)
         if (int r = staged_sent(c, slot, us, piped)) return r;
@@ -849,7 +843,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
         const uint32_t i = instance ? instance[k] : 0;
         if (i >= c->I || bone[k] >= c->B) return fail(RZ_ERR_INVALID, "override %u names instance %u bone %u (have %u x %u)", k, i, bone[k], c->I, c->B);
         for (int e = 0; e < 16; ++e) {
-            if (!finite_f(world16[(size_t)k * 16 + e])) return fail(RZ_ERR_INVALID, "override %u is not finite", k);
+            if (!rzmotion::finite(world16[(size_t)k * 16 + e])) return fail(RZ_ERR_INVALID, "override %u is not finite", k);
         }
         order[k] = k;
     }

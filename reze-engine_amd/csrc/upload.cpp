@@ -510,121 +510,49 @@ int rz_upload_bone_morphs(rz_ctx *c, uint32_t n, const uint32_t *morph, const ui
     return RZ_OK;
 }
 
-// What rz_upload_animation and rz_upload_motions check of one flattened motion, and what they derive from it: bone_track[b] = the track
-// that drives bone b or -1, feed_off[M + 1] / *F = the feeds of the context's vertex morphs (all zero without morph tracks).
-// Keys of tracks that drive nothing of this model (a bone it lacks, a morph track no feed names) are never read by a kernel and are not looked at.
-static bool finite_key(float x) { return x == x && x - x == 0.0f; }
-
-static int check_animation(const rz_ctx *c, const rz_animation *a, std::vector<int> &bone_track, std::vector<uint32_t> &feed_off, uint32_t *F_out)
+// One motion store from motion_table.h's arrays (the caller has released what the store held). Every pointer is allocated, of four
+// elements at least (to_device), but the interpolation bytes: null when no clip carries any.
+static int upload_keys(RzStatic::RzKeys &k, const rzmotion::Flat &f, uint32_t M)
 {
-    if (!a) return fail(RZ_ERR_INVALID, "null animation");
-    if (c->B == 0) return fail(RZ_ERR_INVALID, "upload the skeleton before a motion");
-    const uint32_t n = a->n_bone_tracks, mt = a->n_morph_tracks;
-    if (n && (!a->track_bone || !a->key_off || !a->key_frame || !a->key_rot4 || !a->key_pos3)) return fail(RZ_ERR_INVALID, "null bone-track arrays");
-    if (mt && (!a->mkey_off || !a->mkey_frame || !a->mkey_weight)) return fail(RZ_ERR_INVALID, "null morph-track arrays");
-    if (c->M && mt && (!a->feed_off || (a->feed_off[c->M] && (!a->feed_track || !a->feed_ratio)))) return fail(RZ_ERR_INVALID, "null morph feeds");
-    bone_track.assign(c->B, -1);
-    for (uint32_t t = 0; t < n; ++t) {
-        if (a->key_off[t] > a->key_off[t + 1]) return fail(RZ_ERR_INVALID, "key offsets must be non-decreasing");
-        const int32_t b = a->track_bone[t];
-        if (b < 0 || (uint32_t)b >= c->B) continue;                      // a motion may key bones this model lacks
-        if (bone_track[b] >= 0) return fail(RZ_ERR_INVALID, "bone %d is driven by two tracks", b);
-        for (uint32_t k = a->key_off[t] + 1; k < a->key_off[t + 1]; ++k)
-            // equal frames are legal (real VMD files carry duplicate keys; host/vmd-sampler.js keeps them too): the span search
-            // lands on the last key <= frame and the first key > frame, so a zero-length span is never divided by
-            if (!(a->key_frame[k] >= a->key_frame[k - 1])) return fail(RZ_ERR_INVALID, "track %u: key frames must not descend", t);
-        // every key of a track that drives a bone of this model is finite: a NaN frame passes no comparison of the span search, an
-        // infinite one makes the guessed span's index undefined, and either in a rotation or a position is a NaN pose nothing explains
-        for (uint32_t k = a->key_off[t]; k < a->key_off[t + 1]; ++k) {
-            if (!finite_key(a->key_frame[k])) return fail(RZ_ERR_INVALID, "track %u key %u: the frame is not finite", t, k - a->key_off[t]);
-            for (int d = 0; d < 4; ++d)
-                if (!finite_key(a->key_rot4[(size_t)k * 4 + d])) return fail(RZ_ERR_INVALID, "track %u key %u: the rotation is not finite", t, k - a->key_off[t]);
-            for (int d = 0; d < 3; ++d)
-                if (!finite_key(a->key_pos3[(size_t)k * 3 + d])) return fail(RZ_ERR_INVALID, "track %u key %u: the position is not finite", t, k - a->key_off[t]);
-        }
-        bone_track[b] = (int)t;
-    }
-    for (uint32_t t = 0; t < mt; ++t) {
-        if (a->mkey_off[t] > a->mkey_off[t + 1]) return fail(RZ_ERR_INVALID, "morph key offsets must be non-decreasing");
-        for (uint32_t k = a->mkey_off[t] + 1; k < a->mkey_off[t + 1]; ++k)
-            if (!(a->mkey_frame[k] >= a->mkey_frame[k - 1])) return fail(RZ_ERR_INVALID, "morph track %u: key frames must not descend", t);
-    }
-    feed_off.assign(c->M + 1, 0);
-    uint32_t F = 0;
-    if (c->M && mt) {
-        for (uint32_t m = 0; m <= c->M; ++m) feed_off[m] = a->feed_off[m];
-        F = feed_off[c->M];
-        for (uint32_t m = 0; m < c->M; ++m)
-            if (feed_off[m] > feed_off[m + 1]) return fail(RZ_ERR_INVALID, "feed offsets must be non-decreasing");
-        for (uint32_t f = 0; f < F; ++f)
-            if (a->feed_track[f] < 0 || (uint32_t)a->feed_track[f] >= mt) return fail(RZ_ERR_INVALID, "feed %u names morph track %d of %u", f, a->feed_track[f], mt);
-        // ... and so is every key of a morph track that feeds a vertex morph of this model
-        std::vector<char> seen(mt, 0);
-        for (uint32_t f = 0; f < F; ++f) {
-            const uint32_t t = (uint32_t)a->feed_track[f];
-            if (seen[t]) continue;
-            seen[t] = 1;
-            for (uint32_t k = a->mkey_off[t]; k < a->mkey_off[t + 1]; ++k) {
-                if (!finite_key(a->mkey_frame[k])) return fail(RZ_ERR_INVALID, "morph track %u key %u: the frame is not finite", t, k - a->mkey_off[t]);
-                if (!finite_key(a->mkey_weight[k])) return fail(RZ_ERR_INVALID, "morph track %u key %u: the weight is not finite", t, k - a->mkey_off[t]);
-            }
-        }
-    }
-    *F_out = F;
+    if (int r = to_device(&k.key_frame, f.key_frame.data(), f.key_frame.size())) return r;
+    if (int r = to_device(&k.key_rot, f.key_rot.data(), f.key_rot.size() / 4)) return r;
+    if (int r = to_device(&k.key_pos, f.key_pos.data(), f.key_pos.size())) return r;
+    if (!f.key_interp.empty())
+        if (int r = to_device(&k.key_interp, f.key_interp.data(), f.key_interp.size() / 16)) return r;
+    if (int r = to_device(&k.mkey_frame, f.mkey_frame.data(), f.mkey_frame.size())) return r;
+    if (int r = to_device(&k.mkey_weight, f.mkey_weight.data(), f.mkey_weight.size())) return r;
+    if (int r = to_device(&k.feed_off, f.feed_off.data(), f.feed_off.size())) return r;
+    if (int r = to_device(&k.feed_range, f.feed_range.data(), f.feed_range.size() / 4)) return r;
+    if (int r = to_device(&k.feed_ratio, f.feed_ratio.data(), f.feed_ratio.size())) return r;
+    k.M = M;
     return RZ_OK;
-}
-
-// (first key, one past the last key, bits(first key's frame), bits(last key's frame)) of track t, key indices shifted by `base`
-static uint4 track_record(const uint32_t *off, const float *kf, int t, uint32_t base)
-{
-    uint4 r; r.x = r.y = r.z = r.w = 0;
-    if (t < 0 || off[t + 1] == off[t]) return r;
-    r.x = base + off[t]; r.y = base + off[t + 1];
-    memcpy(&r.z, &kf[off[t]], 4);
-    memcpy(&r.w, &kf[off[t + 1] - 1], 4);
-    return r;
 }
 
 int rz_upload_animation(rz_ctx *c, const rz_animation *a)
 {
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_animation")) return r;
-    std::vector<int> bone_track;
-    std::vector<uint32_t> feed_off;
-    uint32_t F = 0;
-    if (int r = check_animation(c, a, bone_track, feed_off, &F)) return r;
-    const uint32_t n = a->n_bone_tracks, mt = a->n_morph_tracks;
-    const uint32_t K = n ? a->key_off[n] : 0, Km = mt ? a->mkey_off[mt] : 0;
+    rzmotion::Flat f;
+    std::string why;
+    if (!rzmotion::flatten(c->B, c->M, 1, a, nullptr, f, why)) return fail(RZ_ERR_INVALID, "%s", why.c_str());
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_animation(c);
-    // per bone / per morph feed: the key range itself, so the sampler's chain of dependent loads starts one level lower
-    std::vector<uint4> bone_range(c->B), feed_range(F);
-    for (uint32_t b = 0; b < c->B; ++b) bone_range[b] = track_record(a->key_off, a->key_frame, bone_track[b], 0);
-    for (uint32_t f = 0; f < F; ++f) feed_range[f] = track_record(a->mkey_off, a->mkey_frame, a->feed_track[f], 0);
-    if (int r = to_device(&c->an_key_frame, a->key_frame, K)) return r;
-    if (int r = to_device(&c->an_key_rot, a->key_rot4, K)) return r;
-    if (int r = to_device(&c->an_key_pos, a->key_pos3, (size_t)K * 3)) return r;
-    if (a->key_interp16 && K)
-        if (int r = to_device(&c->an_key_interp, a->key_interp16, K)) return r;
-    if (int r = to_device(&c->an_mkey_frame, a->mkey_frame, Km)) return r;
-    if (int r = to_device(&c->an_mkey_weight, a->mkey_weight, Km)) return r;
-    if (int r = to_device(&c->an_feed_off, feed_off.data(), (size_t)c->M + 1)) return r;
-    if (int r = to_device(&c->an_feed_range, feed_range.data(), F)) return r;
-    if (int r = to_device(&c->an_feed_ratio, a->feed_ratio, F)) return r;
-    // per vertex morph: the key range of its FIRST feed and (first feed, end of feeds, bits(its ratio)) — the sampler's one record per morph
-    std::vector<uint4> mrec((size_t)c->M * 2, make_uint4(0u, 0u, 0u, 0u));
-    for (uint32_t m = 0; m < c->M && F; ++m) {
-        const uint32_t f0 = feed_off[m], f1 = feed_off[m + 1];
+    if (int r = upload_keys(c->an, f, c->M)) return r;
+    // host copies for the hierarchy's static block. Per bone: the key range itself, so the sampler's chain of dependent loads starts one
+    // level lower. Per vertex morph: the key range of its FIRST feed and (first feed, end of feeds, bits(its ratio)) — the sampler's one record per morph
+    auto rec = [](const std::vector<uint32_t> &v, size_t k) { return make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]); };
+    c->an_host_range.resize(c->B);
+    for (uint32_t b = 0; b < c->B; ++b) c->an_host_range[b] = rec(f.bone_rec, b);
+    c->an_host_mrec.assign((size_t)c->M * 2, make_uint4(0u, 0u, 0u, 0u));
+    for (uint32_t m = 0; m < c->M; ++m) {
+        const uint32_t f0 = f.feed_off[m], f1 = f.feed_off[m + 1];
         if (f1 > f0) {
             uint32_t rb;
-            memcpy(&rb, &a->feed_ratio[f0], 4);
-            mrec[2 * m] = feed_range[f0];
-            mrec[2 * m + 1] = make_uint4(f0, f1, rb, 0u);
+            memcpy(&rb, &f.feed_ratio[f0], 4);
+            c->an_host_mrec[2 * m] = rec(f.feed_range, f0);
+            c->an_host_mrec[2 * m + 1] = make_uint4(f0, f1, rb, 0u);
         }
     }
-    c->an_host_range = std::move(bone_range);
-    c->an_host_mrec = std::move(mrec);
-    c->an_M = c->M;
     c->has_animation = true;
     return rebuild_fk_static(c);
 }
@@ -639,59 +567,12 @@ int rz_upload_motions(rz_ctx *c, uint32_t n_clips, const rz_animation *clips)
     }
     if (!clips) return fail(RZ_ERR_INVALID, "rz_upload_motions: null clips");
     if (n_clips == 0xffffffffu) return fail(RZ_ERR_INVALID, "rz_upload_motions: too many clips");
-    const uint32_t B = c->B, M = c->M;
-    // every clip is checked before anything is replaced; the keys of all clips are concatenated, the records carry absolute indices
-    std::vector<uint4> bone_rec, feed_range, interp;
-    std::vector<uint32_t> feed_off_all;
-    std::vector<float> key_frame, key_rot, key_pos, mkey_frame, mkey_weight, feed_ratio;
-    bool any_interp = false;
-    for (uint32_t k = 0; k < n_clips; ++k) any_interp = any_interp || (clips[k].key_interp16 != nullptr && clips[k].n_bone_tracks != 0);
-    // a clip without interpolation bytes beside one that has them: the default curve 20 20 107 107, which bezier_y answers with x itself
-    uint4 linear;
-    { const uint8_t d[16] = { 20, 20, 20, 20, 20, 20, 20, 20, 107, 107, 107, 107, 107, 107, 107, 107 }; memcpy(&linear, d, 16); }
-    for (uint32_t k = 0; k < n_clips; ++k) {
-        const rz_animation *a = &clips[k];
-        std::vector<int> bone_track;
-        std::vector<uint32_t> feed_off;
-        uint32_t F = 0;
-        if (int r = check_animation(c, a, bone_track, feed_off, &F)) {
-            const std::string why = last_error();
-            return fail(r, "rz_upload_motions: clip %u: %s", k, why.c_str());
-        }
-        const uint32_t n = a->n_bone_tracks, mt = a->n_morph_tracks;
-        const uint32_t K = n ? a->key_off[n] : 0, Km = mt ? a->mkey_off[mt] : 0;
-        const size_t key_base = key_frame.size(), mkey_base = mkey_frame.size(), feed_base = feed_range.size();
-        if (key_base + K > 0xfffffff0ull || mkey_base + Km > 0xfffffff0ull || feed_base + F > 0xfffffff0ull)
-            return fail(RZ_ERR_INVALID, "rz_upload_motions: the library's keys do not fit 32-bit indices");
-        for (uint32_t b = 0; b < B; ++b) bone_rec.push_back(track_record(a->key_off, a->key_frame, bone_track[b], (uint32_t)key_base));
-        for (uint32_t m = 0; m <= M; ++m) feed_off_all.push_back((uint32_t)feed_base + feed_off[m]);
-        for (uint32_t f = 0; f < F; ++f) {
-            feed_range.push_back(track_record(a->mkey_off, a->mkey_frame, a->feed_track[f], (uint32_t)mkey_base));
-            feed_ratio.push_back(a->feed_ratio[f]);
-        }
-        key_frame.insert(key_frame.end(), a->key_frame, a->key_frame + K);
-        key_rot.insert(key_rot.end(), a->key_rot4, a->key_rot4 + (size_t)K * 4);
-        key_pos.insert(key_pos.end(), a->key_pos3, a->key_pos3 + (size_t)K * 3);
-        if (any_interp) {
-            interp.resize(key_base + K, linear);
-            if (a->key_interp16 && K) memcpy(&interp[key_base], a->key_interp16, (size_t)K * 16);
-        }
-        mkey_frame.insert(mkey_frame.end(), a->mkey_frame, a->mkey_frame + Km);
-        mkey_weight.insert(mkey_weight.end(), a->mkey_weight, a->mkey_weight + Km);
-    }
-    free_motions(c);                    // (drains both streams first: a blend kernel may still be reading the old library)
-    if (int r = to_device(&c->mo_bone_rec, bone_rec.data(), bone_rec.size())) return r;
-    if (int r = to_device(&c->mo_feed_off, feed_off_all.data(), feed_off_all.size())) return r;
-    if (int r = to_device(&c->mo_feed_range, feed_range.data(), feed_range.size())) return r;
-    if (int r = to_device(&c->mo_feed_ratio, feed_ratio.data(), feed_ratio.size())) return r;
-    if (int r = to_device(&c->mo_key_frame, key_frame.data(), key_frame.size())) return r;
-    if (int r = to_device(&c->mo_key_rot, key_rot.data(), key_rot.size() / 4)) return r;
-    if (int r = to_device(&c->mo_key_pos, key_pos.data(), key_pos.size())) return r;
-    if (any_interp)
-        if (int r = to_device(&c->mo_key_interp, interp.data(), interp.size())) return r;
-    if (int r = to_device(&c->mo_mkey_frame, mkey_frame.data(), mkey_frame.size())) return r;
-    if (int r = to_device(&c->mo_mkey_weight, mkey_weight.data(), mkey_weight.size())) return r;
-    c->mo_M = M;
+    rzmotion::Flat f;                   // every clip is checked before anything is replaced
+    std::string why;
+    if (!rzmotion::flatten(c->B, c->M, n_clips, clips, "rz_upload_motions", f, why)) return fail(RZ_ERR_INVALID, "%s", why.c_str());
+    free_motions(c);                    // (drains both streams first: a pose kernel may still be reading the old library)
+    if (int r = to_device(&c->mo_bone_rec, f.bone_rec.data(), f.bone_rec.size() / 4)) return r;
+    if (int r = upload_keys(c->mo, f, c->M)) return r;
     c->mo_clips = n_clips;
     return RZ_OK;
 }

@@ -1,4 +1,4 @@
-"""Layered device poses (rz_upload_motion_masks / rz_set_pose_layered, kernels/motion_layers.hip) against their float64 definition
+"""Layered device poses (rz_upload_motion_masks / rz_set_pose_layered, rz_motion_kernel<RzLayerParams> of kernels/motion.hip) against their float64 definition
 tests/layer_ref.py, and through everything that runs behind a local pose.
 
 Inputs follow one rule (tests/layer_scenes.py; tests/test_layer_cpu.py asserts it on exactly these states): override clips keep every key

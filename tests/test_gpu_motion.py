@@ -1,4 +1,4 @@
-"""The device motion library (rz_upload_motions / rz_set_pose_blended, kernels/motion.hip) against its float64 definition
+"""The device motion library (rz_upload_motions / rz_set_pose_blended, rz_motion_kernel<RzMotionParams> of kernels/motion.hip) against its float64 definition
 tests/motion_ref.py, and through everything that runs behind a local pose.
 
 Inputs follow one rule (tests/test_motion_cpu.py asserts it on exactly these states): every key of a bone, across all clips, lies within a
@@ -338,6 +338,62 @@ def test_forks_and_misuse(rz, scene):
         c.upload_motions(s["clips"])
         c.upload_skeleton(s["mesh"]["inv_bind"])              # a new skeleton drops the library
         assert c.get_tuning("motion_clips") == 0
+
+
+@pytest.mark.parametrize("I", [1, 3])
+def test_both_motion_stores_in_one_context(rz, scene, I):
+    """One context holds the single motion (clip 1) AND the library with masks; sampled, blended and layered poses alternate, a frame after each.
+    Every frame equals, in bits, the frame of a context that holds only the store that pose reads — a parameter block built from the wrong
+    store would not. Then the library is replaced under the sampled pose and the motion under the blended one: neither moves. I = 1: frames
+    and states ride in the kernel arguments; I = 3: in device arrays."""
+    s = scene
+    rng = np.random.default_rng(31)
+    masks = (rng.random((2, ms.B)) < 0.5).astype(np.uint8), (rng.random((2, ms.M)) < 0.5).astype(np.uint8)
+    pack = rz.DeformContext.pack_motion_states
+
+    def pose(c, kind, t):
+        if kind == "sampled":
+            c.set_pose_sampled([3.25 + 2.5 * i + 4.0 * t for i in range(I)])
+            return
+        a, fa, b, fb, bl = zip(*[s["states"][(t + i) % len(s["states"])] for i in range(I)])
+        b = [NO if x is None else x for x in b]
+        if kind == "blended":
+            c.set_pose_blended(a, fa, b, fb, bl)
+        else:
+            c.set_pose_layered(pack(I, a, fa, b, fb, bl),
+                               [[dict(clip=(i + t) % 3, frame=5.5 + i, weight=0.6, mask=i % 2), dict(clip=2, frame=7.25 + t, mask=1 - i % 2, additive=True)] for i in range(I)])
+
+    def frame(c, kind, t):
+        pose(c, kind, t)
+        c.deform()
+        return [snapshot(c, i) for i in range(I)]
+
+    def same(x, y):
+        return all(same_bits(a, b) for a, b in zip(x, y))
+    with make_ctx(rz, s, instances=I) as both, make_ctx(rz, s, instances=I, library=False) as single, make_ctx(rz, s, instances=I) as lib:
+        both.upload_animation(**s["clips"][1])
+        single.upload_animation(**s["clips"][1])
+        both.upload_motion_masks(*masks)
+        lib.upload_motion_masks(*masks)
+        seen = []
+        for t in range(2):
+            for kind in ("sampled", "blended", "layered"):
+                got = frame(both, kind, t)
+                assert same(got, frame(single if kind == "sampled" else lib, kind, t)), (kind, t)
+                seen.append(got)
+        assert not same(seen[0], seen[1]) and not same(seen[1], seen[2]) and not same(seen[0], seen[3])
+        # another library under the sampled pose
+        both.upload_motions(s["clips"][::-1])
+        assert same(frame(both, "sampled", 1), seen[3])
+        lib.upload_motions(s["clips"][::-1])
+        other = frame(both, "blended", 1)
+        assert same(other, frame(lib, "blended", 1)) and not same(other, seen[4])
+        # another motion under the blended pose
+        both.upload_animation(**s["clips"][2])
+        assert same(frame(both, "blended", 1), other)
+        assert same(frame(both, "layered", 1), frame(lib, "layered", 1))
+        single.upload_animation(**s["clips"][2])
+        assert same(frame(both, "sampled", 0), frame(single, "sampled", 0))
 
 
 def test_variants_build_equals_the_product(rz, rzv, scene):

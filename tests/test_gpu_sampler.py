@@ -2,7 +2,7 @@
 held to the float64 sampler on long, uneven key tracks: the scenes of tests/sampler_scenes.py — tracks of 1 to 70 000 keys, bursts, gaps of
 hundreds of frames, runs of equal frames, key indices beyond 65 536, frames beyond 100 000, curves whose x(t) is flat at an end — through
 every kernel that samples: rz_fk_kernel's generic solve, the fused frame's specialised sampled solve, the tail loop of skeletons beyond
-512 bones, the one-launch crowd front, and rz_motion_blend_kernel on a library whose second clip lies behind 80 000 keys of the first.
+512 bones, the one-launch crowd front, and rz_motion_kernel on a library whose second clip lies behind 80 000 keys of the first.
 
 Bars, none of them new: world matrices within 5e-5 x max(1, |ref|.max()) of fk_reference(sample_reference(...)) (the bar of
 test_device_motion_sampling_matches_the_float64_sampler), positions and normals within helpers.POS_TOL / NRM_TOL of the oracle fed the

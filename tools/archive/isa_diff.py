@@ -1,6 +1,7 @@
 """Compare two directories of normalised per-kernel disassembly (tools/archive/isa_dump.sh): for every kernel of the NEW directory, the kernel it
 replaces in the OLD one (the hierarchy solve's six hand-written entries of kernels/front.hip became the six instantiations of
-rz_fk_kernel<Stage...>), identical or not, instruction counts, and the mnemonic histogram differences."""
+rz_fk_kernel<Stage...>; the motion stack's two, of kernels/motion.hip and kernels/motion_layers.hip, the two of rz_motion_kernel<P>),
+identical or not, instruction counts, and the mnemonic histogram differences."""
 import collections, difflib, os, sys
 old, new = sys.argv[1], sys.argv[2]
 OLD_NAME = {
@@ -10,6 +11,8 @@ OLD_NAME = {
     "rz_fk_kernel<RzIkParams,RzFollowParams>": "rz_fk_ik_follow_kernel",
     "rz_fk_kernel<RzIkParams,RzIkSwitchParams>": "rz_fk_ik_sw_kernel",
     "rz_fk_kernel<RzIkParams,RzFollowParams,RzIkSwitchParams>": "rz_fk_ik_sw_follow_kernel",
+    "rz_motion_kernel<RzMotionParams>": "rz_motion_blend_kernel",
+    "rz_motion_kernel<RzLayerParams>": "rz_motion_layer_kernel",
 }
 def old_name(n): return OLD_NAME.get(n, n)
 same = diff = 0

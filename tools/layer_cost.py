@@ -1,5 +1,5 @@
-"""What a layered pose (rz_upload_motion_masks / rz_set_pose_layered, kernels/motion_layers.hip) costs beside a blended one
-(rz_set_pose_blended, kernels/motion.hip) on the same build.
+"""What a layered pose (rz_upload_motion_masks / rz_set_pose_layered) costs beside a blended one (rz_set_pose_blended) on the same build:
+the two instantiations of rz_motion_kernel, kernels/motion.hip.
   python tools/layer_cost.py [rounds] [--out FILE]
 Shapes: the demo-shaped character (28 842 vertices, 349 bones, 60 sparse morphs) and the C4 crowd (256 x 30 000 vertices, 200 bones).
 One measurement, in a FRESH process per shape (this script starts itself again with --child), `rounds` (default 5) alternated rounds, the
