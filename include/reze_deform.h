@@ -767,6 +767,9 @@ int rz_time_span(rz_ctx *a, rz_ctx *b, uint32_t lead, uint32_t frames, double *s
  * last upload did),
  * "qdef_chunks" (0 auto = 1, 1..64: how many 256-vertex chunks of the QDEF table one workgroup of rz_qdef_kernel takes behind one
  * conversion of the skeleton to dual quaternions; same bits),
+ * "sparse_piece" (0 auto, else a multiple of 16 in 16..2048: how many entries of the sparse targets' per-vertex CSR a wave stages in LDS
+ * at a time — a test and diagnosis handle, same bits at every size; a piece the LDS does not hold next to the palette is lowered to what
+ * fits; rz_get_tuning("effective_sparse_piece") gives the piece of the next frame, 0 without resident sparse targets),
  * "overlap" (-1 / 0 off, 1: crowds run their front kernels on the upload stream under
  * the previous frame's skin kernel — measured slower on this runtime, kept for experiments). There is no key that makes a frame
  * emit anything but the deformed mesh: ablation switches exist only in a tools-only build and "dbg" is rejected here.

@@ -238,6 +238,7 @@ struct RzTuning {
     int t_prefetch = -1;                // "pose_prefetch": -1 / 1 on, 0 off
     int t_subsets = -1;                 // "inst_subsets": -1 / 1 = stage only the bones a vertex run names when that is a gain, 0 = always the whole palette
     int t_graph = 0;                    // "graph" tuning key: rz_deform_n replays captured hipGraphs of kGraphFrames frames
+    int t_sppiece = 0;                  // "sparse_piece": 0 = the plan sizes a wave's LDS piece of the sparse CSR, else that many entries (16..2048, a multiple of 16) where they fit
 };
 
 // Rigid-body physics (rz_upload_physics; physics_host.cpp, kernels/physics.hip): static records, per-instance state, and what the next step must

@@ -253,6 +253,7 @@ Plan make_plan(const rz_ctx *c)
             RzDeformParams q;
             memset(&q, 0, sizeof q);
             q.B = (int)c->B; q.M = (int)c->M; q.Mpad = (int)c->Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
+            q.sp_cap = 16;      // (counted for sparse targets only: the buffer must leave room for the smallest piece below, or the frame is refused for a buffer it can do without)
             if (rz_deform_lds_bytes(q, v) > 160 * 1024) pl.out_cap = 0;
         }
     }
@@ -273,6 +274,9 @@ Plan make_plan(const rz_ctx *c)
         const uint32_t want = std::min<uint32_t>(2048u, (256u / (uint32_t)v.S) * std::max<uint32_t>(c->M, 1u));
         pl.sp_cap = avail >= 64 ? std::max<uint32_t>(64u, std::min<uint32_t>(round_up(want, 256), (uint32_t)(avail / 64 * 64)))         // whole 1 KiB bursts (the kernel issues them in groups of four)
                                 : std::max<uint32_t>(16u, (uint32_t)(avail / 16 * 16));
+        // "sparse_piece" (tests, diagnosis): the caller's piece instead of `want`, as it is — no rounding to whole bursts, no share left for a
+        // second workgroup — but never more than the CU's 160 KB hold next to the rest: a request that does not fit is lowered
+        if (c->t_sppiece > 0) pl.sp_cap = std::max<uint32_t>(16u, std::min<uint32_t>((uint32_t)c->t_sppiece, (uint32_t)std::min<size_t>(hard / 16 * 16, 2048)));
     }
     // instanced, morph-free frames: G poses per workgroup share one decode of each vertex, their palettes live in LDS.
     // Where the palettes come from (measured on C4, tools/archive/ablate_c4.py, frame = everything a frame launches):

@@ -22,6 +22,8 @@ const TuneKey kTuneKeys[] = {
     { "geo_lds", &RzTuning::t_geo, [](int &v) { v = v ? 1 : 0; return tools_only(v != 0); }, nullptr, kNo },
     { "nt_store", &RzTuning::t_nts, [](int &v) { v = v < 0 ? -1 : (v ? 1 : 0); return (int)RZ_OK; }, nullptr, kNo },
     { "out_cap", &RzTuning::t_outcap, within<-1, 2048>, "out_cap must be -1 (auto), 0 (off) or 64..2048 vertices per wave", kNo },
+    { "sparse_piece", &RzTuning::t_sppiece, [](int &v) { return need(v == 0 || (v >= 16 && v <= 2048 && v % 16 == 0)); },
+      "sparse_piece must be 0 (auto) or a multiple of 16 in 16..2048 entries of the sparse CSR per wave", kNo },
     { "graph", &RzTuning::t_graph, within<0, 1>, "graph must be 0 or 1", kNo },
     { "inst_loop", &RzTuning::t_instloop, [](int &v) { return v == 9 ? tools_only(true) : need(v >= -1 && v != 1 && v <= 64); },
       "inst_loop must be -1 (auto), 0 (off), 2..8 / 10..64 (poses per workgroup, LDS form) or 9 (register form)", kAlways },
@@ -227,7 +229,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     if (!strncmp(key, "effective_", 10)) {
         // (an unknown key is refused BEFORE the work below: it drains the stream and may rebuild the run lists)
         static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones", "closure_rounds",
-                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds", "morph_storage" };
+                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds", "morph_storage", "sparse_piece" };
         bool ok = false;
         for (const char *k : known) ok = ok || !strcmp(key + 10, k);
         if (!ok) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
@@ -306,6 +308,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "effective_overlap")) *value = want_overlap(c, make_plan(c)) ? 1 : 0;
     else if (!strcmp(key, "effective_inst_block")) *value = make_plan(c).inst_block;
     else if (!strcmp(key, "effective_out_cap")) *value = (int)make_plan(c).out_cap;
+    else if (!strcmp(key, "effective_sparse_piece")) *value = (int)make_plan(c).sp_cap;      // 0 without resident sparse targets (make_plan sizes it for MODE 2 only)
     else if (!strcmp(key, "effective_inst_group")) *value = make_plan(c).inst_group;
     else if (!strcmp(key, "effective_poses_per_wg")) *value = make_plan(c).poses_per_wg;
     else if (!strcmp(key, "effective_grid")) *value = (int)make_plan(c).grid_x;

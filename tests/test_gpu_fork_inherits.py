@@ -8,11 +8,11 @@ pytestmark = pytest.mark.gpu
 # Every settable key with a legal value that is not its default. Written out on purpose: a key that joins the table in csrc/tune.cpp
 # belongs here too. The product refuses the values that select a tools-only kernel variant, so it keeps the only value it accepts there.
 KEYS = dict(morph_split=2, grid_cap=7, nt_store=1, out_cap=64, graph=1, inst_loop=4, pose_prefetch=0, inst_subsets=0, fuse_fk=0,
-            zero_copy=0, fuse_fk_plain=0, pose_pull=0, overlap=1, inst_order=0, inst_block=512, qdef_chunks=3, fast=0)
+            zero_copy=0, fuse_fk_plain=0, pose_pull=0, overlap=1, inst_order=0, inst_block=512, qdef_chunks=3, fast=0, sparse_piece=48)
 PRODUCT_ONLY = dict(unroll=8, geo_lds=0, nontemporal=1)
 VARIANTS_ONLY = dict(unroll=4, geo_lds=1, nontemporal=0)
 DEFAULTS = dict(morph_split=0, grid_cap=0, nt_store=-1, out_cap=-1, graph=0, inst_loop=-1, pose_prefetch=-1, inst_subsets=-1, fuse_fk=-1,
-                zero_copy=-1, fuse_fk_plain=-1, pose_pull=-1, overlap=-1, inst_order=1, inst_block=0, qdef_chunks=0, fast=-1,
+                zero_copy=-1, fuse_fk_plain=-1, pose_pull=-1, overlap=-1, inst_order=1, inst_block=0, qdef_chunks=0, fast=-1, sparse_piece=0,
                 unroll=0, geo_lds=0, nontemporal=1)
 
 
