@@ -770,6 +770,16 @@ int rz_time_span(rz_ctx *a, rz_ctx *b, uint32_t lead, uint32_t frames, double *s
  * "sparse_piece" (0 auto, else a multiple of 16 in 16..2048: how many entries of the sparse targets' per-vertex CSR a wave stages in LDS
  * at a time — a test and diagnosis handle, same bits at every size; a piece the LDS does not hold next to the palette is lowered to what
  * fits; rz_get_tuning("effective_sparse_piece") gives the piece of the next frame, 0 without resident sparse targets),
+ * "inst_morphs" (-1 auto = off, 0, 1: a crowd — rz_set_instances(n > 1) — with SPARSE morph targets takes the crowd skin kernels: a
+ * workgroup decodes each vertex once for its group of "inst_loop" poses and walks the vertex's row of the CSR once per pose, the group's
+ * per-instance morph weights parked in LDS behind its palettes, instead of the single-mesh kernel run once per instance. The same bits as
+ * with the key off, on every instance. It applies where the morph-free crowd kernels apply — no outline hull, no bounding box,
+ * "inst_loop" neither 0 nor 9, a group of at least two poses — and where the group's inst_loop x (morphs + 8, rounded up to 4) x 4 B of
+ * weights fit the LDS beside its palettes [80 KB per workgroup at 256 threads, 156 KB otherwise]; otherwise, and for dense targets,
+ * the frame is the one launched with the key off, never an error. A device-animated crowd solves its hierarchy in the same launch only
+ * while the pose's morph weights are in device memory before the frame [rz_set_pose_local, rz_set_pose_blended, rz_set_pose_layered;
+ * not at 1024 threads]: behind rz_set_pose_sampled rz_fk_kernel stays in front, which writes them.
+ * rz_get_tuning("effective_inst_morphs") is 1 when the next frame walks morph rows in a crowd kernel),
  * "overlap" (-1 / 0 off, 1: crowds run their front kernels on the upload stream under
  * the previous frame's skin kernel — measured slower on this runtime, kept for experiments). There is no key that makes a frame
  * emit anything but the deformed mesh: ablation switches exist only in a tools-only build and "dbg" is rejected here.

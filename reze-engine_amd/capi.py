@@ -1075,9 +1075,13 @@ class DeformContext:
                 fused = g("effective_closure_bones") > 0        # the hierarchy solved in the crowd kernel's front (ABI 5)
             except RzError:
                 fused = False
+            try:
+                morph = "_morph" if g("effective_inst_morphs") else ""     # sparse targets walked in the crowd kernels (kernels/crowd_morph.hip)
+            except RzError:
+                morph = ""
             if fused:
-                return "rz_skin_instances_fk_kernel<%d, %s>" % (g("effective_inst_block"), tf("effective_nt_store"))
-            return "rz_skin_instances_kernel<%d, %s, %s>" % (g("effective_inst_block"), tf("effective_nt_store"), tf("effective_subsets"))
+                return "rz_skin_instances_fk%s_kernel<%d, %s>" % (morph, g("effective_inst_block"), tf("effective_nt_store"))
+            return "rz_skin_instances%s_kernel<%d, %s, %s>" % (morph, g("effective_inst_block"), tf("effective_nt_store"), tf("effective_subsets"))
         mode = g("morph_mode")
         s_ = g("effective_split")
         try:

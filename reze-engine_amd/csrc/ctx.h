@@ -239,6 +239,7 @@ struct RzTuning {
     int t_subsets = -1;                 // "inst_subsets": -1 / 1 = stage only the bones a vertex run names when that is a gain, 0 = always the whole palette
     int t_graph = 0;                    // "graph" tuning key: rz_deform_n replays captured hipGraphs of kGraphFrames frames
     int t_sppiece = 0;                  // "sparse_piece": 0 = the plan sizes a wave's LDS piece of the sparse CSR, else that many entries (16..2048, a multiple of 16) where they fit
+    int t_instmorphs = -1;              // "inst_morphs": 1 = a crowd with sparse morph targets takes the crowd kernels (kernels/crowd_morph.hip), 0 = never, -1 = auto (= off)
 };
 
 // Rigid-body physics (rz_upload_physics; physics_host.cpp, kernels/physics.hip): static records, per-instance state, and what the next step must
@@ -538,10 +539,11 @@ template <typename T> int to_device(T **dst, const void *src, size_t count)
 }
 
 // ---- plan.cpp ----
-struct Plan { RzVariant v; uint32_t grid_x, n_quads, quads_per_wave; bool prep, dma; int inst_group; uint32_t verts_per_wg; int poses_per_wg; uint32_t out_cap; int inst_block; bool fuse_fk; bool subsets; uint32_t sub_bones; uint64_t inst_lds; bool pf; uint32_t sp_cap; bool subfk; };
-// Launch shape of an instanced, morph-free crowd frame (rz_skin_instances_kernel): G poses per workgroup share one decode of each
-// vertex; the grid is (vertex runs, pose groups), `total` workgroups in all.
-struct InstShape { int G, blk, blk_full; bool want_in_kernel; uint32_t per, runs; };
+struct Plan { RzVariant v; uint32_t grid_x, n_quads, quads_per_wave; bool prep, dma; int inst_group; uint32_t verts_per_wg; int poses_per_wg; uint32_t out_cap; int inst_block; bool fuse_fk; bool subsets; uint32_t sub_bones; uint64_t inst_lds; bool pf; uint32_t sp_cap; bool subfk; bool inst_morphs; };
+// Launch shape of an instanced crowd frame without dense morphs (rz_skin_instances_kernel): G poses per workgroup share one decode of each
+// vertex; the grid is (vertex runs, pose groups), `total` workgroups in all. morphs: the context has sparse targets and "inst_morphs" asks
+// for the crowd kernels — the MORPH instantiations, whose LDS holds the group's G x Mpad morph weights behind the palettes.
+struct InstShape { int G, blk, blk_full; bool want_in_kernel; uint32_t per, runs; bool morphs; };
 bool inst_shape(const rz_ctx *c, InstShape *s);
 Plan make_plan(const rz_ctx *c);
 int ensure_run_subsets(rz_ctx *c);

@@ -419,8 +419,10 @@ hipError_t rz_launch_deform_small(const RzDeformParams &p, const RzVariant &v, d
 // register-resident form: 2048 vertices per workgroup decoded once, poses streamed through a 2-deep LDS palette ring
 hipError_t rz_launch_skin_instances_reg(const RzDeformParams &p, int n_inst, int poses_per_wg, uint32_t grid_x, bool nts,
                                         hipStream_t st);
+// morphs (inst_morphs; kernels/crowd_morph.hip): the MORPH instantiations — every pose also walks the rows of the context's sparse CSR
+// (p.sp_ptr / p.sp_entries) with its own weights (p.morph_w [I][M]), which the front stages in LDS behind the palettes
 hipError_t rz_launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                    int block, bool nts, size_t lds_bytes, hipStream_t st);
+                                    int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs = false);
 // Crowd frame with the hierarchy solved in the skin kernel's front (kernels/crowd.hip: rz_skin_instances_fk_kernel): per vertex run the
 // closure of its named bones under "parent of", one 80-byte record per closure slot (plan.cpp: ensure_subfk)
 struct RzSubFk {
@@ -430,10 +432,11 @@ struct RzSubFk {
     uint32_t rounds;            // radix-4 doubling rounds the deepest closure needs (<= 3)
 };
 hipError_t rz_launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                       int block, bool nts, size_t lds_bytes, hipStream_t st);
-size_t rz_skin_instances_fk_lds_bytes(int G, uint32_t closure, uint32_t named);
-// LDS bytes of the instanced skin kernel: G poses of `bones` staged bones (the whole skeleton, or the largest run subset)
-size_t rz_skin_instances_lds_bytes(int G, uint32_t bones, bool dma, bool subsets);
+                                       int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs = false);
+size_t rz_skin_instances_fk_lds_bytes(int G, uint32_t closure, uint32_t named, uint32_t morph_pad = 0);
+// LDS bytes of the instanced skin kernel: G poses of `bones` staged bones (the whole skeleton, or the largest run subset);
+// morph_pad (the MORPH kernels) = Mpad: the group's morph weights behind them, G x Mpad x 4 B
+size_t rz_skin_instances_lds_bytes(int G, uint32_t bones, bool dma, bool subsets, uint32_t morph_pad = 0);
 // per vertex run of `per` vertices: the ascending list of bones its vertices name + the joints rewritten as slots of it
 hipError_t rz_launch_run_subsets(const uint32_t *j01, const uint32_t *j23, uint32_t v_lim, uint32_t per, uint32_t runs, uint32_t B,
                                  uint16_t *list, uint32_t *count, uint32_t *rj01, uint32_t *rj23, hipStream_t st);

@@ -70,12 +70,12 @@ int launch_deform(rz_ctx *c, const Plan &pl)
         return RZ_OK;
     }
     if (pl.inst_group > 0 && pl.subfk) {
-        HIP_TRY(rz_launch_skin_instances_fk(p, subfk_params(c), pl.inst_group, (int)c->I, pl.verts_per_wg, pl.grid_x, pl.inst_block, pl.v.nts, (size_t)pl.inst_lds, c->stream));
+        HIP_TRY(rz_launch_skin_instances_fk(p, subfk_params(c), pl.inst_group, (int)c->I, pl.verts_per_wg, pl.grid_x, pl.inst_block, pl.v.nts, (size_t)pl.inst_lds, c->stream, pl.inst_morphs));
         c->fk_stale = true;                 // neither world matrices nor palettes of this pose are in memory: formed on demand (rz_read_world / rz_read_palette)
         return RZ_OK;
     }
     if (pl.inst_group > 0) {
-        HIP_TRY(rz_launch_skin_instances(p, pl.inst_group, (int)c->I, pl.verts_per_wg, pl.grid_x, pl.inst_block, pl.v.nts, (size_t)pl.inst_lds, c->stream));
+        HIP_TRY(rz_launch_skin_instances(p, pl.inst_group, (int)c->I, pl.verts_per_wg, pl.grid_x, pl.inst_block, pl.v.nts, (size_t)pl.inst_lds, c->stream, pl.inst_morphs));
         if (!pl.dma) c->palette_stale = pl.subsets;    // the whole-palette one-launch frame copies its palettes out, the subset form cannot
         return RZ_OK;
     }

@@ -1,7 +1,37 @@
 // kernels/crowd.hip — instanced skin (BASELINE config C4: many poses of one static mesh) and its plan-time bone-subset pass.
 #include "fk.hip.h"
 
+// MORPH = sparse vertex morphs (the context's per-vertex CSR and per-instance weights, kernels/deform_small.hip MODE 2) for a crowd: the
+// front parks the group's ng x M weights in LDS behind everything else the kernel keeps there (G x Mpad floats), published by the barrier
+// that publishes the palettes; the pose loop walks a vertex's row per pose (crowd_pose_loop.inc.h). MORPH is a constant of the translation
+// unit, not a template parameter: the two kernels below keep their template arguments, hence the symbols every stored profile names, and
+// with MORPH = false they are the parent's instruction streams (profiles/crowd_morph_identity.txt). kernels/crowd_morph.hip compiles this
+// file again with RZ_CROWD_MORPH true; there the same two templates are called rz_skin_instances_morph_kernel<BLOCK, NTS, SUB> and
+// rz_skin_instances_fk_morph_kernel<BLOCK, NTS>.
+#ifndef RZ_CROWD_MORPH
+#define RZ_CROWD_MORPH false
+#endif
+#if RZ_CROWD_MORPH
+#define RZ_CROWD_KERNEL rz_skin_instances_morph_kernel
+#define RZ_CROWD_FK_KERNEL rz_skin_instances_fk_morph_kernel
+#else
+#define RZ_CROWD_KERNEL rz_skin_instances_kernel
+#define RZ_CROWD_FK_KERNEL rz_skin_instances_fk_kernel
+#endif
+
 namespace {
+
+constexpr bool MORPH = RZ_CROWD_MORPH;
+
+// MORPH: the group's morph weights, [ng][M] contiguous in memory, into their LDS block [G][Mpad]
+template <int BLOCK>
+__device__ __forceinline__ void stage_morph_weights(float *s_mw, const float *gw, const int ng, const int M, const int Mpad, const int tid)
+{
+    for (int i = tid; i < ng * M; i += BLOCK) {
+        const int g = i / M;
+        s_mw[g * Mpad + (i - g * M)] = gw[i];
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // instanced skin (MODE 0, I > 1 — BASELINE config C4: many poses of one static mesh).
@@ -29,9 +59,9 @@ namespace {
 // (Tried and measured slower or without effect, then removed again — NOTEBOOK.md R3.1 / R3.4 / R3.9: forcing three workgroups per CU
 // (80 VGPRs spill), a branch-free pose loop with clamped tail lanes, four poses unrolled, raised wave priority around the stores.)
 template <int BLOCK, bool NTS, bool SUB>
-__global__ void __launch_bounds__(BLOCK) rz_skin_instances_kernel(const uint32_t *k_sub_count, const uint16_t *k_sub_list, const float4 *k_src,
-                                                                  const float *k_inv_bind, const int G, const int n_inst, const uint32_t verts_per_wg,
-                                                                  const uint32_t k_grid, const uint32_t k_bf, const uint32_t k_Vp, const RzDeformParams p)
+__global__ void __launch_bounds__(BLOCK) RZ_CROWD_KERNEL(const uint32_t *k_sub_count, const uint16_t *k_sub_list, const float4 *k_src,
+                                                         const float *k_inv_bind, const int G, const int n_inst, const uint32_t verts_per_wg,
+                                                         const uint32_t k_grid, const uint32_t k_bf, const uint32_t k_Vp, const RzDeformParams p)
 {
     // The leading arguments are preloaded into SGPRs at wave start (14 dwords; see rz_deform_kernel): what the FRONT of a workgroup
     // needs — the run's bone list, the matrices it stages (k_src = the poses' world matrices, or their finished palettes behind
@@ -125,11 +155,20 @@ __global__ void __launch_bounds__(BLOCK) rz_skin_instances_kernel(const uint32_t
     uint32_t v = vert_of(v_begin);
     float x = 0, y = 0, z = 0, nx = 0, ny = 0, nz = 0;
     uint32_t j01 = 0, j23 = 0, wq = 0;
+    [[maybe_unused]] uint32_t rb0 = 0, rb1 = 0;         // MORPH: bounds of this lane's vertex's CSR row
+    [[maybe_unused]] float *s_mw = nullptr;             // MORPH: the group's morph weights in LDS, [G][Mpad]
     const uint32_t *jp01 = SUB ? p.rj01 : p.joints01, *jp23 = SUB ? p.rj23 : p.joints23;     // SUB: joints as slots of the run's list
     if (v < v_end) {
         x = p.geom[0 * Vp + v]; y = p.geom[1 * Vp + v]; z = p.geom[2 * Vp + v];
         nx = p.geom[3 * Vp + v]; ny = p.geom[4 * Vp + v]; nz = p.geom[5 * Vp + v];
         j01 = jp01[v]; j23 = jp23[v]; wq = p.weights[v];
+        if constexpr (MORPH) { rb0 = p.sp_ptr[v]; rb1 = p.sp_ptr[v + 1]; }
+    }
+    if constexpr (MORPH) {
+        // the weights sit behind the kernel's other LDS (rz_skin_instances_lds_bytes: staged bones x 48 / 64 / 112 B per pose); nothing
+        // in front of the barrier below reads or writes that region
+        s_mw = reinterpret_cast<float *>(smem + (size_t)G * (SUB ? ns : kB) * (k_dma ? 48 : (SUB ? 112 : 64)));
+        stage_morph_weights<BLOCK>(s_mw, p.morph_w + (size_t)inst0 * p.M, ng, p.M, p.Mpad, tid);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // palettes / world matrices (and the first vertex) have landed
     RZ_STAMP(1);                 // staged matrices have landed
@@ -235,9 +274,9 @@ __global__ void __launch_bounds__(BLOCK) rz_skin_instances_kernel(const uint32_t
 constexpr int kSubFkWords = 5;          // uint4 per closure record
 
 template <int BLOCK, bool NTS>
-__global__ void __launch_bounds__(BLOCK) rz_skin_instances_fk_kernel(const uint32_t *k_cnt, const uint4 *k_rec, const float4 *k_src, const float *k_inv_bind,
-                                                                     const uint32_t k_g, const int n_inst, const uint32_t verts_per_wg, const uint32_t k_grid,
-                                                                     const uint32_t k_bf, const uint32_t k_Vp, const RzDeformParams p)
+__global__ void __launch_bounds__(BLOCK) RZ_CROWD_FK_KERNEL(const uint32_t *k_cnt, const uint4 *k_rec, const float4 *k_src, const float *k_inv_bind,
+                                                            const uint32_t k_g, const int n_inst, const uint32_t verts_per_wg, const uint32_t k_grid,
+                                                            const uint32_t k_bf, const uint32_t k_Vp, const RzDeformParams p)
 {
     constexpr bool SUB = true;
     constexpr int rstride = 3;
@@ -283,11 +322,14 @@ __global__ void __launch_bounds__(BLOCK) rz_skin_instances_fk_kernel(const uint3
     uint32_t v = vert_of(v_begin);
     float x = 0, y = 0, z = 0, nx = 0, ny = 0, nz = 0;
     uint32_t j01 = 0, j23 = 0, wq = 0;
+    [[maybe_unused]] uint32_t rb0 = 0, rb1 = 0;         // MORPH: bounds of this lane's vertex's CSR row
+    [[maybe_unused]] float *s_mw = nullptr;             // MORPH: the group's morph weights in LDS, [G][Mpad]
     const uint32_t *jp01 = p.rj01, *jp23 = p.rj23;
     if (v < v_end) {
         x = p.geom[0 * Vp + v]; y = p.geom[1 * Vp + v]; z = p.geom[2 * Vp + v];
         nx = p.geom[3 * Vp + v]; ny = p.geom[4 * Vp + v]; nz = p.geom[5 * Vp + v];
         j01 = jp01[v]; j23 = jp23[v]; wq = p.weights[v];
+        if constexpr (MORPH) { rb0 = p.sp_ptr[v]; rb1 = p.sp_ptr[v + 1]; }
     }
     const int ns = (int)(k_g >> 18);                   // named bones = palette slots of a run (the longest list's)
     const int lrows = ns * 3;
@@ -358,6 +400,12 @@ __global__ void __launch_bounds__(BLOCK) rz_skin_instances_fk_kernel(const uint3
             d[0] = q0; d[1] = q1; d[2] = q2;
         }
     }
+    if constexpr (MORPH) {
+        // the pose's morph weights are in device memory before this frame (the plan keeps rz_fk_kernel in front of a sampled pose, which
+        // writes them); behind the two matrix buffers and the palettes (rz_skin_instances_fk_lds_bytes)
+        s_mw = reinterpret_cast<float *>(smem + (size_t)G * (2 * (size_t)nc + ns) * 48);
+        stage_morph_weights<BLOCK>(s_mw, p.morph_w + (size_t)inst0 * p.M, ng, p.M, p.Mpad, tid);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the first vertex has landed)
     __syncthreads();
     RZ_STAMP(2);                 // palettes formed and published: the front is over
@@ -366,7 +414,7 @@ __global__ void __launch_bounds__(BLOCK) rz_skin_instances_fk_kernel(const uint3
     RZ_TL_FLUSH(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (BLOCK / 64) + wave);
 }
 
-#ifdef RZ_ALL_VARIANTS
+#if defined(RZ_ALL_VARIANTS) && !RZ_CROWD_MORPH
 // ------------------------------------------------------------------------------------------------
 // instanced skin, register-resident form: a workgroup owns a run of KV*256 vertices and a RANGE of poses.
 // Each lane loads and decodes its KV vertices ONCE into registers (the static mesh is read once per
@@ -474,6 +522,7 @@ __global__ void __launch_bounds__(kBlock) rz_skin_instances_reg_kernel(const RzD
 }
 #endif  // RZ_ALL_VARIANTS
 
+#if !RZ_CROWD_MORPH
 // zero-weight influence still gathers its bone's rows, so it stays the SAME bone: fma(0, row, m) keeps m's bits only while the
 // row is the one the full-palette form would have read), ranks them ascending, writes the list and the joints as slots of it.
 __global__ void __launch_bounds__(kBlock) rz_run_subsets_kernel(const uint32_t *j01, const uint32_t *j23, uint32_t v_lim, uint32_t per,
@@ -519,23 +568,29 @@ __global__ void __launch_bounds__(kBlock) rz_run_subsets_kernel(const uint32_t *
     }
 }
 
+#endif
+
 }  // namespace
 
-size_t rz_skin_instances_lds_bytes(int G, uint32_t bones, bool dma, bool subsets)
+#if !RZ_CROWD_MORPH
+size_t rz_skin_instances_lds_bytes(int G, uint32_t bones, bool dma, bool subsets, uint32_t morph_pad)
 {
     // finished palettes are 48 B per (pose, bone). One-launch frame: the whole-palette form stages the world matrices in
     // the palette region's place (64-byte slots, re-packed in place); the subset form stages them behind it (48 + 64).
+    // morph_pad (MORPH kernels): the group's morph weights behind all that, Mpad floats per pose.
     const size_t per = dma ? 48 : (subsets ? 112 : 64);
-    return (size_t)G * bones * per;
+    return (size_t)G * bones * per + (size_t)G * morph_pad * 4;
 }
+#endif
 
 template <int BLOCK>
 static hipError_t launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
                                         bool nts, size_t lds, hipStream_t st)
 {
     const bool sub = p.sub_list != nullptr;
-    auto k = sub ? (nts ? rz_skin_instances_kernel<BLOCK, true, true> : rz_skin_instances_kernel<BLOCK, false, true>)
-                 : (nts ? rz_skin_instances_kernel<BLOCK, true, false> : rz_skin_instances_kernel<BLOCK, false, false>);
+    auto k = sub ? (nts ? RZ_CROWD_KERNEL<BLOCK, true, true> : RZ_CROWD_KERNEL<BLOCK, false, true>)
+                 : (nts ? RZ_CROWD_KERNEL<BLOCK, true, false> : RZ_CROWD_KERNEL<BLOCK, false, false>);
+    if (RZ_CROWD_MORPH && (!p.sp_ptr || !p.sp_entries || !p.morph_w || p.M <= 0 || p.Mpad < p.M)) return hipErrorInvalidValue;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -549,19 +604,23 @@ static hipError_t launch_skin_instances(const RzDeformParams &p, int G, int n_in
     return hipGetLastError();
 }
 
-size_t rz_skin_instances_fk_lds_bytes(int G, uint32_t closure, uint32_t named) { return (size_t)G * (2 * (size_t)closure + named) * 48; }
+#if !RZ_CROWD_MORPH
+size_t rz_skin_instances_fk_lds_bytes(int G, uint32_t closure, uint32_t named, uint32_t morph_pad) { return (size_t)G * (2 * (size_t)closure + named) * 48 + (size_t)G * morph_pad * 4; }
+#endif
 
 template <int BLOCK>
 static hipError_t launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x, bool nts,
                                            size_t lds, hipStream_t st)
 {
-    auto k = nts ? rz_skin_instances_fk_kernel<BLOCK, true> : rz_skin_instances_fk_kernel<BLOCK, false>;
+    auto k = nts ? RZ_CROWD_FK_KERNEL<BLOCK, true> : RZ_CROWD_FK_KERNEL<BLOCK, false>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     dim3 grid(grid_x, (n_inst + G - 1) / G);
     const bool sampled = p.fk.sample.frames != nullptr;
+    // (MORPH: the front stages the pose's morph weights out of memory; a sampled pose's are written by rz_fk_kernel, which this frame does not have)
+    if (RZ_CROWD_MORPH && (!p.sp_ptr || !p.sp_entries || !p.morph_w || p.M <= 0 || p.Mpad < p.M || sampled)) return hipErrorInvalidValue;
     // what the kernel can take: two 16-bit grid fields, 16 bits of bone count, 12 bits of record stride, 2 bits of rounds, two work items per thread
     if (grid.x > 0xffffu || grid.y > 0xffffu || p.B > 0xffff || f.stride > 0xfffu || f.rounds > 3 || (size_t)G * f.stride > 2 * (size_t)BLOCK || !p.sub_count || !p.rj01)
         return hipErrorInvalidValue;
@@ -573,22 +632,49 @@ static hipError_t launch_skin_instances_fk(const RzDeformParams &p, const RzSubF
     return hipGetLastError();
 }
 
-hipError_t rz_launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                       int block, bool nts, size_t lds_bytes, hipStream_t st)
+#if RZ_CROWD_MORPH
+// the MORPH = true halves, for rz_launch_skin_instances / rz_launch_skin_instances_fk in the other unit
+hipError_t rz_launch_skin_instances_fk_morph_half(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
+                                                  int block, bool nts, size_t lds_bytes, hipStream_t st)
 {
+#else
+hipError_t rz_launch_skin_instances_fk_morph_half(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
+                                                  int block, bool nts, size_t lds_bytes, hipStream_t st);      // kernels/crowd_morph.hip
+hipError_t rz_launch_skin_instances_morph_half(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
+                                               int block, bool nts, size_t lds_bytes, hipStream_t st);
+
+hipError_t rz_launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
+                                       int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs)
+{
+    if (morphs) return rz_launch_skin_instances_fk_morph_half(p, f, G, n_inst, verts_per_wg, grid_x, block, nts, lds_bytes, st);
+#endif
+#if RZ_CROWD_MORPH
+    // (no MORPH instantiation at 1024 threads: 128 VGPRs do not hold the front's two work items beside the row walk without scratch — the
+    // plan keeps rz_fk_kernel in front of such a frame)
+    if (block == 1024) return hipErrorInvalidValue;
+#else
     if (block == 1024) return launch_skin_instances_fk<1024>(p, f, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
+#endif
     if (block == 512) return launch_skin_instances_fk<512>(p, f, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
     return launch_skin_instances_fk<256>(p, f, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
 }
 
-hipError_t rz_launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                    int block, bool nts, size_t lds_bytes, hipStream_t st)
+#if RZ_CROWD_MORPH
+hipError_t rz_launch_skin_instances_morph_half(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
+                                               int block, bool nts, size_t lds_bytes, hipStream_t st)
 {
+#else
+hipError_t rz_launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
+                                    int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs)
+{
+    if (morphs) return rz_launch_skin_instances_morph_half(p, G, n_inst, verts_per_wg, grid_x, block, nts, lds_bytes, st);
+#endif
     if (block == 1024) return launch_skin_instances<1024>(p, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
     if (block == 512) return launch_skin_instances<512>(p, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
     return launch_skin_instances<256>(p, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
 }
 
+#if !RZ_CROWD_MORPH
 hipError_t rz_launch_run_subsets(const uint32_t *j01, const uint32_t *j23, uint32_t v_lim, uint32_t per, uint32_t runs, uint32_t B,
                                  uint16_t *list, uint32_t *count, uint32_t *rj01, uint32_t *rj23, hipStream_t st)
 {
@@ -618,3 +704,4 @@ hipError_t rz_launch_skin_instances_reg(const RzDeformParams &p, int n_inst, int
     return hipErrorInvalidValue;       // the register-resident crowd kernel (measured slower, inst_loop = 9) is a tools-only variant
 #endif
 }
+#endif  // !RZ_CROWD_MORPH

@@ -151,7 +151,9 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
 bool inst_shape(const rz_ctx *c, InstShape *s)
 {
     const bool epilogues = c->edge != nullptr || c->aabb_on;   // only the generic kernel carries the fused consumers
-    if (!(c->morph_mode == 0 && c->I > 1 && c->t_instloop != 0 && c->t_instloop != 9 && !epilogues) || c->B == 0 || c->V == 0) return false;
+    // sparse targets: only when "inst_morphs" asks (auto = off: every such crowd keeps the generic kernel, one launch row per instance)
+    s->morphs = c->morph_mode == 2 && c->t_instmorphs == 1 && c->M > 0 && c->sp_ptr && c->sp_entries;
+    if (!((c->morph_mode == 0 || s->morphs) && c->I > 1 && c->t_instloop != 0 && c->t_instloop != 9 && !epilogues) || c->B == 0 || c->V == 0) return false;
     s->want_in_kernel = c->t_fast != 0 && !c->pl.cur.local;
     // workgroup size. Whole palettes: 512 threads for the one-launch frame (one workgroup of 8 waves per CU shares the 102 KB
     // group), 256 behind rz_prep_kernel / rz_fk_kernel (two workgroups of 80 KB each: measured best in round 2). Bone subsets
@@ -300,21 +302,28 @@ Plan make_plan(const rz_ctx *c)
         // 256-thread skin kernel, and 39.5 us for two 256-thread workgroups of 6 poses).
         const int blk = is.blk;
         const uint32_t lds_budget = (blk == 256 ? 80u : 156u) * 1024u;
+        // Sparse targets ("inst_morphs"): the group's morph weights, G x Mpad floats, sit in LDS behind whatever the form keeps there and
+        // count against the same budgets. A form they do not fit beside is not taken (subset form -> whole palettes with the group the
+        // budget allows -> the generic kernel: the frame launched without the key), never an error.
+        const uint32_t mpad = is.morphs ? c->Mpad : 0u;
         bool sub = c->t_subsets != 0 && c->sub_valid && c->sub_per == is.per && c->sub_runs == is.runs && c->sub_B == c->B &&
                    c->sub_max < c->B && c->sub_max <= (uint32_t)blk;
         if (sub) {
-            const size_t lds = rz_skin_instances_lds_bytes(is.G, c->sub_max, !is.want_in_kernel, true);
+            const size_t lds = rz_skin_instances_lds_bytes(is.G, c->sub_max, !is.want_in_kernel, true, mpad);
             if (lds > lds_budget) sub = false;
             else {
-                pl.subsets = true; pl.sub_bones = c->sub_max; pl.inst_lds = lds;
+                pl.subsets = true; pl.sub_bones = c->sub_max; pl.inst_lds = lds; pl.inst_morphs = is.morphs;
                 pl.inst_group = is.G; pl.inst_block = blk; pl.verts_per_wg = is.per; pl.grid_x = is.runs;
                 pl.prep = !is.want_in_kernel; pl.dma = !is.want_in_kernel;
                 // device-animated poses: the hierarchy solved in the front of the skin kernel — one launch per frame — when the closure
                 // records of these very lists are there, a workgroup's (pose, closure bone) items fit two per thread, and the two matrix
                 // buffers + the palettes fit the LDS budget; else rz_fk_kernel in front, as before
+                // (sparse targets: the front stages the pose's morph weights out of device memory, so they must be there before the frame —
+                // uploaded, blended and layered poses; a sampled pose's are written by rz_fk_kernel, which therefore stays in front. And
+                // not at 1024 threads: the MORPH front has no instantiation there, kernels/crowd.hip.)
                 if (subfk_wanted(c) && c->subfk_valid && c->subfk_sub_gen == c->sub_gen && c->subfk_fk_gen == c->fk_gen &&
-                    (size_t)is.G * c->subfk_stride <= 2 * (size_t)blk) {
-                    const size_t lf = rz_skin_instances_fk_lds_bytes(is.G, c->subfk_stride, c->sub_max);
+                    (size_t)is.G * c->subfk_stride <= 2 * (size_t)blk && !(is.morphs && (c->pl.cur.sampled || blk == 1024))) {
+                    const size_t lf = rz_skin_instances_fk_lds_bytes(is.G, c->subfk_stride, c->sub_max, mpad);
                     if (lf <= lds_budget) { pl.subfk = true; pl.prep = false; pl.dma = false; pl.inst_lds = lf; }
                 }
             }
@@ -323,14 +332,18 @@ Plan make_plan(const rz_ctx *c)
             const int blk_f = is.blk_full;
             const uint32_t budget_f = (blk_f == 256 ? 80u : 156u) * 1024u;
             const bool in_kernel = is.want_in_kernel && c->B <= (uint32_t)blk_f;   // the in-place product gives every bone its own thread
-            const uint32_t g_lds = budget_f / (c->B * (in_kernel ? 64u : 48u));
+            const uint32_t g_lds = budget_f / (c->B * (in_kernel ? 64u : 48u) + mpad * 4u);
             int G = (int)std::min<uint32_t>((uint32_t)is.G, g_lds);
+            // (sparse targets: the group that was asked for, or the generic kernel — a morph-free crowd has no other frame to fall back to
+            // and takes the smaller group; a crowd with targets has the frame it launched before the key existed)
+            if (is.morphs && G != is.G) G = 0;
             if (G >= 2) {
                 uint32_t per = 0, runs = 0;
                 inst_runs(c, G, blk_f, false, &per, &runs);
                 pl.inst_group = G; pl.inst_block = blk_f; pl.verts_per_wg = per; pl.grid_x = runs;
                 pl.prep = !in_kernel; pl.dma = !in_kernel;
-                pl.inst_lds = rz_skin_instances_lds_bytes(G, c->B, !in_kernel, false);
+                pl.inst_lds = rz_skin_instances_lds_bytes(G, c->B, !in_kernel, false, mpad);
+                pl.inst_morphs = is.morphs;
             }
         }
     }

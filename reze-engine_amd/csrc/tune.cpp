@@ -24,6 +24,7 @@ const TuneKey kTuneKeys[] = {
     { "out_cap", &RzTuning::t_outcap, within<-1, 2048>, "out_cap must be -1 (auto), 0 (off) or 64..2048 vertices per wave", kNo },
     { "sparse_piece", &RzTuning::t_sppiece, [](int &v) { return need(v == 0 || (v >= 16 && v <= 2048 && v % 16 == 0)); },
       "sparse_piece must be 0 (auto) or a multiple of 16 in 16..2048 entries of the sparse CSR per wave", kNo },
+    { "inst_morphs", &RzTuning::t_instmorphs, within<-1, 1>, "inst_morphs must be -1 (auto = off), 0 (a crowd with sparse morph targets always runs the generic kernel) or 1 (it takes the crowd kernels where they fit)", kNo },
     { "graph", &RzTuning::t_graph, within<0, 1>, "graph must be 0 or 1", kNo },
     { "inst_loop", &RzTuning::t_instloop, [](int &v) { return v == 9 ? tools_only(true) : need(v >= -1 && v != 1 && v <= 64); },
       "inst_loop must be -1 (auto), 0 (off), 2..8 / 10..64 (poses per workgroup, LDS form) or 9 (register form)", kAlways },
@@ -229,7 +230,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     if (!strncmp(key, "effective_", 10)) {
         // (an unknown key is refused BEFORE the work below: it drains the stream and may rebuild the run lists)
         static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones", "closure_rounds",
-                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds", "morph_storage", "sparse_piece" };
+                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds", "morph_storage", "sparse_piece", "inst_morphs" };
         bool ok = false;
         for (const char *k : known) ok = ok || !strcmp(key + 10, k);
         if (!ok) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
@@ -335,6 +336,7 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "effective_subsets")) *value = make_plan(c).subsets ? 1 : 0;
     else if (!strcmp(key, "effective_subset_bones")) *value = (int)make_plan(c).sub_bones;
     else if (!strcmp(key, "effective_inst_lds")) *value = (int)make_plan(c).inst_lds;
+    else if (!strcmp(key, "effective_inst_morphs")) *value = make_plan(c).inst_morphs ? 1 : 0;     // the frame walks sparse morph rows in a crowd kernel
     else return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
     return RZ_OK;
 }

@@ -96,6 +96,10 @@ class Engine {
     // { deviceFK } send the model's switches with the pose (rz_set_ik_enabled). Off by default: a motion with such keys plays as before.
     this.ikKeys = o.ikKeys === true
     if (this.ikKeys && !this.ik) throw new Error('ikKeys needs new Engine(canvas, { ik: true }): the keys switch chains of the IK solve')
+    // crowdMorphs: a crowd (setInstanceCount) of a model with vertex morphs takes the crowd skin kernels, which walk each vertex's morph
+    // row once per pose of a group (tuning key inst_morphs = 1), instead of the single-mesh kernel run once per instance; set on every
+    // shard behind setInstanceCount and on every fork. The frames are the same bits either way. Off by default.
+    this.crowdMorphs = o.crowdMorphs === true
     this.ikManual = null // setIKEnabled(): [instances][chains], 1 / 0 = held on / off by hand, -1 = left to the motion
     this.ikManualSent = new WeakSet() // the contexts whose mask carries switches set by hand
     this.physicsAccumulator = 0 // seconds of clock advance not yet turned into substeps
@@ -185,6 +189,7 @@ class Engine {
     if (!s.fork) { // made after the launch-shape search, so that it inherits the tuned plan
       s.fork = this.native.fork(s.ctx)
       if (this.followOverrides) this.native.overrideFollow(s.fork, 1) // (rz_fork hands the flag down already: said again, so a fork never depends on when its lender was set)
+      if (this.crowdMorphs) this.native.setTuning(s.fork, 'inst_morphs', 1) // (a fork inherits its lender's tuning: said again for the same reason)
       if (this.overrides) this.native.overrideWorld(s.fork, this.overrides[0], this.overrides[1], this.overrides[2])
     }
     s.flip ^= 1
@@ -868,6 +873,7 @@ class Engine {
     this.dropForks() // a fork takes its instance count from the lender when it is made
     if (n !== this.instances) this.overrides = null // (instance, bone) pairs of the old crowd: rz_set_instances dropped them on the lender too
     this.native.setInstances(this.ctx, n)
+    if (this.crowdMorphs) for (const s of this.shards) this.native.setTuning(s.ctx, 'inst_morphs', 1)
     this.instances = n
     this.tuned = false
   }

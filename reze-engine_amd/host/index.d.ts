@@ -53,6 +53,7 @@ export interface EngineOptions {
   /** With deviceFK: bones below an overridden bone follow it (rz_override_follow, called on every shard and fork behind the topology upload) — W_b = O_a (S_a^-1 S_b) with a the nearest overridden ancestor of b, S the solved pose; for the overrides devicePhysics writes and for those of setBoneWorldOverrides. A strand's tip bone without a body, an ornament on a hair bone, the sub-bone of a skirt plate then ride the physics bone instead of staying with the animation. Not re-evaluated on the followed pose: append transforms, IK chains, following bodies. Off by default; without deviceFK it throws (host FK: call Model.followOverrides(world, bones, matrices) from the { physics } hook). */ followOverrides?: boolean
   /** With deviceFK: the model's PMX after-physics bones (flag 0x1000) are solved again behind the overrides, from the final pose of the bones they read (rz_upload_after_physics, called on every shard behind the topology upload and behind the IK table; forks borrow the list) — a skirt aid that takes half the rotation of a physics bone, a support bone that appends from a sprung body's bone then see the simulated pose. Evaluation order: Model.afterPhysicsOrder() (transform level, then index; it throws on a bone listed before a bone it reads). Off by default; without deviceFK it throws (host FK: call Model.solveAfterPhysics(world, overriddenBones) at the end of the { physics } hook). */ afterPhysics?: boolean
   /** With ik: honour the motion's VMD show / IK keys, which switch single IK chains off and on over time (a motion traced from motion capture switches leg and toe IK off at frame 0). Host path: seekFrame, playAnimation and seekMotions set the model's chain switches (Model.setIKChainEnabled) before the pose solve; a cross-fade takes clip `a`'s switches below blend 0.5 and clip `b`'s from there on, layers never switch. With { deviceFK, deviceSampling } the keys are uploaded behind the motion (rz_upload_ik_keys) and evaluated by the pose calls; host-sampled deviceFK frames send the switches with the pose (rz_set_ik_enabled). The keys' `show` flag is returned by the loader and not used. Off by default: a motion with such keys plays as before; without ik it throws. */ ikKeys?: boolean
+  /** A crowd (setInstanceCount) of a model with vertex morphs takes the crowd skin kernels: each vertex is decoded once for a group of poses and its morph row walked once per pose, instead of the single-mesh kernel run once per instance (tuning key inst_morphs = 1, set on every shard behind setInstanceCount and on every fork). The frames are the same bits either way; whether it is faster depends on the model (profiles/crowd_morph_cost.txt). A group whose morph weights do not fit the LDS beside its palettes, the outline hull and the bounds keep the other kernel. Off by default. */ crowdMorphs?: boolean
 }
 export interface MotionState { a: string; frameA: number; b?: string | null; frameB?: number; blend?: number; layers?: MotionLayer[] }
 /** one layer of a MotionState: motion `motion` at `frame`, applied with `weight` (default 1) where the mask `mask` (Engine.setMotionMask; none: everywhere) includes the bone or morph and the motion keys it — override (slerp / lerp towards it) or `additive` (q * slerp(identity, qL, weight), t + tL * weight, w + wL * weight). At most 4 per state. */

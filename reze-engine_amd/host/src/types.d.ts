@@ -205,7 +205,7 @@ export interface EngineOptions {
   ambient?: number; bloomIntensity?: number; rimLightIntensity?: number; cameraDistance?: number; cameraTarget?: Vec3
   device?: number; devices?: number[]; deviceFK?: boolean; deviceSampling?: boolean; outline?: boolean; bounds?: boolean
   gather?: boolean | 'direct'; morphLayout?: 'sparse' | 'dense'; realtime?: boolean; physics?: PhysicsLike | null
-  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; physicsAligned?: boolean; followOverrides?: boolean; afterPhysics?: boolean; ikKeys?: boolean
+  framesInFlight?: 1 | 2; autotune?: boolean; sdef?: boolean; qdef?: boolean; ik?: boolean; devicePhysics?: boolean; physicsContacts?: boolean | 'boxes' | 'all'; physicsSprings?: boolean; physicsAligned?: boolean; followOverrides?: boolean; afterPhysics?: boolean; ikKeys?: boolean; crowdMorphs?: boolean
 }
 export interface EngineStats { fps: number; frameTime: number; gpuMemory: number; deformMs: number; vertsPerSec: number; hbmGBps: number }
 export interface DeformedMesh { positions: Float32Array; normals: Float32Array }
