@@ -114,10 +114,10 @@ int rz_comm_init(rz_ctx *c, int nranks, int rank, const char id[128], uint32_t v
     if (int r = use(c)) return r;
     if (nranks < 1 || rank < 0 || rank >= nranks || !id) return fail(RZ_ERR_INVALID, "bad communicator arguments");
     if (c->I != 1) return fail(RZ_ERR_UNSUPPORTED, "instancing and vertex sharding are exclusive: a crowd shards along the instance axis (rz_instance_range), with nothing to gather");
-    if (c->V == 0) return fail(RZ_ERR_INVALID, "upload this rank's mesh shard before rz_comm_init");
+    if (c->mesh.V == 0) return fail(RZ_ERR_INVALID, "upload this rank's mesh shard before rz_comm_init");
     uint32_t b = 0, n = 0;
     if (int r = rz_shard_range(v_total, nranks, rank, &b, &n)) return r;
-    if (n != c->V) return fail(RZ_ERR_INVALID, "rank %d holds %u vertices but rz_shard_range assigns %u", rank, c->V, n);
+    if (n != c->mesh.V) return fail(RZ_ERR_INVALID, "rank %d holds %u vertices but rz_shard_range assigns %u", rank, c->mesh.V, n);
     if (int r = rccl_bind()) return r;
     if (c->comm) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     ncclUniqueId u;
@@ -142,10 +142,10 @@ static int comm_buffers(rz_ctx *c, int nranks, int rank, uint32_t v_total)
     if (int r = rz_gather_chunk(v_total, nranks, &c->chunk)) return r;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    dfree(c->g_pos); dfree(c->g_nrm);
+    c->g_pos = {}; c->g_nrm = {};
     const size_t g = (size_t)nranks * c->chunk * 3 * sizeof(float);
-    HIP_TRY(hipMalloc(&c->g_pos, g));
-    HIP_TRY(hipMalloc(&c->g_nrm, g));
+    HIP_TRY(c->g_pos.alloc(g / sizeof(float)));
+    HIP_TRY(c->g_nrm.alloc(g / sizeof(float)));
     return ensure_outputs(c);
 }
 
@@ -160,7 +160,7 @@ int rz_comm_init_all(rz_ctx **ctxs, int n, uint32_t v_total)
         if (c->I != 1) return fail(RZ_ERR_UNSUPPORTED, "instancing and vertex sharding are exclusive: a crowd shards along the instance axis (rz_instance_range), with nothing to gather");
         uint32_t b = 0, cnt = 0;
         if (int e = rz_shard_range(v_total, n, r, &b, &cnt)) return e;
-        if (cnt != c->V) return fail(RZ_ERR_INVALID, "context %d holds %u vertices but rz_shard_range assigns %u", r, c->V, cnt);
+        if (cnt != c->mesh.V) return fail(RZ_ERR_INVALID, "context %d holds %u vertices but rz_shard_range assigns %u", r, c->mesh.V, cnt);
         for (int k = 0; k < r; ++k)
             if (devs[k] == c->device) return fail(RZ_ERR_INVALID, "contexts %d and %d share device %d: RCCL needs one GPU per rank", k, r, c->device);
         devs[r] = c->device;
@@ -201,7 +201,7 @@ static int gather_direct_attach(rz_ctx **ctxs, int n, uint32_t v_total, int root
         if (c->I != 1) return fail(RZ_ERR_UNSUPPORTED, "instancing and vertex sharding are exclusive: a crowd shards along the instance axis (rz_instance_range), with nothing to gather");
         uint32_t b = 0, cnt = 0;
         if (int e = rz_shard_range(v_total, n, r, &b, &cnt)) return e;
-        if (cnt != c->V) return fail(RZ_ERR_INVALID, "context %d holds %u vertices but rz_shard_range assigns %u", r, c->V, cnt);
+        if (cnt != c->mesh.V) return fail(RZ_ERR_INVALID, "context %d holds %u vertices but rz_shard_range assigns %u", r, c->mesh.V, cnt);
         for (int k = 0; k < r; ++k)
             if (ctxs[k] == c) return fail(RZ_ERR_INVALID, "context listed twice");
     }
@@ -214,10 +214,10 @@ static int gather_direct_attach(rz_ctx **ctxs, int n, uint32_t v_total, int root
     if (int r = rz_gather_chunk(v_total, n, &chunk)) return r;
     HIP_TRY(hipSetDevice(rt->device));
     HIP_TRY(hipStreamSynchronize(rt->stream));
-    dfree(rt->g_pos); dfree(rt->g_nrm);
+    rt->g_pos = {}; rt->g_nrm = {};
     const size_t g = (size_t)n * chunk * 3 * sizeof(float);
-    HIP_TRY(hipMalloc(&rt->g_pos, g));
-    HIP_TRY(hipMalloc(&rt->g_nrm, g));
+    HIP_TRY(rt->g_pos.alloc(g / sizeof(float)));
+    HIP_TRY(rt->g_nrm.alloc(g / sizeof(float)));
     // on the root's stream and drained: a plain hipMemset is asynchronous to the host and rides the NULL stream, which the
     // contexts' non-blocking streams do not wait for — it could land on top of the first frame's output
     HIP_TRY(hipMemsetAsync(rt->g_pos, 0, g, rt->stream));

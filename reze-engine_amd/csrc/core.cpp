@@ -75,36 +75,24 @@ int drain(rz_ctx *c)
 int ensure_outputs(rz_ctx *c)
 {
     // one instance: room for a whole all-gather chunk; instances are strided by Vp
-    const size_t need = (c->I == 1) ? std::max<size_t>(c->Vp, c->chunk) * 3 : (size_t)c->I * c->Vp * 3;
+    const size_t need = (c->I == 1) ? std::max<size_t>(c->mesh.Vp, c->chunk) * 3 : (size_t)c->I * c->mesh.Vp * 3;
     if (need == 0) return RZ_OK;
-    if (need > c->out_alloc_floats) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        dfree(c->out_pos);
-        dfree(c->out_nrm);
-        HIP_TRY(hipMalloc(&c->out_pos, need * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->out_nrm, need * sizeof(float)));
+    if (need > c->out_pos.capacity()) {
+        if (int r = grow(c, c->out_pos.to(need), c->out_nrm.to(need))) return r;
         HIP_TRY(hipMemsetAsync(c->out_pos, 0, need * sizeof(float), c->stream));
         HIP_TRY(hipMemsetAsync(c->out_nrm, 0, need * sizeof(float), c->stream));
-        c->out_alloc_floats = need;
     }
-    if (c->edge && need > c->hull_alloc_floats) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        dfree(c->out_hull);
-        HIP_TRY(hipMalloc(&c->out_hull, need * sizeof(float)));
+    if (c->edge && need > c->out_hull.capacity()) {
+        if (int r = grow(c, c->out_hull.to(need))) return r;
         HIP_TRY(hipMemsetAsync(c->out_hull, 0, need * sizeof(float), c->stream));
-        c->hull_alloc_floats = need;
     }
     // Bounding-box keys: a frame accumulates into one slot and re-arms the other FOR THE INSTANCES IT LAUNCHES, so the
     // buffer is armed from scratch whenever the reduction is switched on or the instance count changes (aabb_rearm) —
     // otherwise an instance that sat out some frames would come back onto a slot still holding its old extents.
-    if (c->aabb_on && (c->I > c->aabb_alloc_inst || c->aabb_rearm)) {
+    if (c->aabb_on && ((size_t)c->I * 12 > c->aabb.capacity() || c->aabb_rearm)) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->I > c->aabb_alloc_inst) {
-            dfree(c->aabb);
-            HIP_TRY(hipMalloc(&c->aabb, (size_t)c->I * 12 * sizeof(uint32_t)));
-            c->aabb_alloc_inst = c->I;
-        }
-        std::vector<uint32_t> init((size_t)c->aabb_alloc_inst * 12);
+        if (int r = grow(c, c->aabb.to((size_t)c->I * 12))) return r;
+        std::vector<uint32_t> init(c->aabb.capacity());
         for (size_t i = 0; i < init.size(); ++i) init[i] = (i % 6) < 3 ? 0xffffffffu : 0u;
         HIP_TRY(hipMemcpy(c->aabb, init.data(), init.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         c->aabb_slot = 0;
@@ -122,7 +110,7 @@ void set_ring(rz_ctx *c, int slot)
 // Lay the CURRENT instance / bone / morph counts out over pose slot k and make it the current slot.
 void point_pose_at(rz_ctx *c, float *block)
 {
-    const size_t I = c->I, B = c->B, Mq = std::max<uint32_t>(c->M, 1);
+    const size_t I = c->I, B = c->skel.B, Mq = std::max<uint32_t>(c->morphs.M, 1);
     c->mw_pad = (I * Mq + 3) / 4 * 4;
     c->world = block;
     c->morph_w = block + I * B * 16;
@@ -137,17 +125,17 @@ void point_pose_slot(rz_ctx *c, int k)
 
 int ensure_pose_buffers(rz_ctx *c)
 {
-    if (c->B == 0) return RZ_OK;
-    const uint32_t Mq = std::max<uint32_t>(c->M, 1);
-    if (c->I <= c->pl.alloc_I && c->B <= c->pl.alloc_B && Mq <= c->pl.alloc_M && c->world) return RZ_OK;
+    if (c->skel.B == 0) return RZ_OK;
+    const uint32_t Mq = std::max<uint32_t>(c->morphs.M, 1);
+    if (c->I <= c->pl.alloc_I && c->skel.B <= c->pl.alloc_B && Mq <= c->pl.alloc_M && c->world) return RZ_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->up_stream));
     for (int k = 0; k < 2; ++k) c->pl.pose_blk[k] = {};
     c->pl.big = {};
     c->world = nullptr; c->morph_w = nullptr; c->local_q = nullptr;
-    for (int k = 0; k < 2; ++k) { dfree(c->palette_ring[k]); dfree(c->act_idx_ring[k]); dfree(c->act_w_ring[k]); dfree(c->act_count_ring[k]); c->skin_recorded[k] = false; }
+    for (int k = 0; k < 2; ++k) { c->palette_ring[k] = {}; c->act_idx_ring[k] = {}; c->act_w_ring[k] = {}; c->act_count_ring[k] = {}; c->skin_recorded[k] = false; }
     c->palette = nullptr; c->act_idx = nullptr; c->act_w = nullptr; c->act_count = nullptr;
-    const size_t I = c->I, B = c->B;
+    const size_t I = c->I, B = c->skel.B;
     const size_t Mpad = round_up(Mq + 8, 4);
     const size_t blk_floats = I * B * 16 + ((I * Mq + 3) / 4 * 4) + I * B * 7 + 4;      // + 4: the prefetch helper copies whole 16-byte cells
     for (int k = 0; k < 2; ++k) {
@@ -156,10 +144,10 @@ int ensure_pose_buffers(rz_ctx *c)
     }
     point_pose_slot(c, 0);
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipMalloc(&c->palette_ring[k], I * B * 3 * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c->act_idx_ring[k], I * Mpad * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->act_w_ring[k], I * Mpad * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->act_count_ring[k], I * sizeof(int)));
+        HIP_TRY(c->palette_ring[k].alloc(I * B * 3));
+        HIP_TRY(c->act_idx_ring[k].alloc(I * Mpad));
+        HIP_TRY(c->act_w_ring[k].alloc(I * Mpad));
+        HIP_TRY(c->act_count_ring[k].alloc(I));
         HIP_TRY(hipMemsetAsync(c->palette_ring[k], 0, I * B * 3 * sizeof(float4), c->stream));
         HIP_TRY(hipMemsetAsync(c->act_idx_ring[k], 0, I * Mpad * sizeof(uint32_t), c->stream));
         HIP_TRY(hipMemsetAsync(c->act_w_ring[k], 0, I * Mpad * sizeof(float), c->stream));
@@ -175,17 +163,10 @@ int ensure_pose_buffers(rz_ctx *c)
     return RZ_OK;
 }
 
-void free_keys(RzStatic::RzKeys &k)
-{
-    dfree(k.key_frame); dfree(k.key_rot); dfree(k.key_pos); dfree(k.key_interp); dfree(k.mkey_frame); dfree(k.mkey_weight);
-    dfree(k.feed_off); dfree(k.feed_range); dfree(k.feed_ratio);
-    k.M = 0;
-}
-
 void free_animation(rz_ctx *c)
 {
     drop_graph(c);
-    free_keys(c->an);
+    c->an = {};
     c->an_host_range.clear(); c->an_host_mrec.clear();
     c->has_animation = false;
     c->ik_keys_an = {};                 // rz_upload_ik_keys(RZ_NO_CLIP): the keys of this motion
@@ -194,32 +175,28 @@ void free_animation(rz_ctx *c)
 
 void free_motions(rz_ctx *c)
 {
-    if (c->mo_clips) {                    // rz_motion_kernel reads the library on whichever stream the pose travelled on
+    if (c->lib.clips) {                   // rz_motion_kernel reads the library on whichever stream the pose travelled on
         if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }
-    free_keys(c->mo);
-    dfree(c->mo_bone_rec);
-    c->mo_clips = 0;
+    c->mo = {};
+    c->lib = {};
     c->ik_keys_mo.clear();              // rz_upload_ik_keys(clip): the keys of this library's clips
 }
 
 void free_motion_masks(rz_ctx *c)
 {
-    if (c->mk_count) {                    // rz_motion_kernel reads the masks on whichever stream the pose travelled on
+    if (c->mk.count) {                    // rz_motion_kernel reads the masks on whichever stream the pose travelled on
         if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }
-    dfree(c->mk_bone_bits); dfree(c->mk_morph_bits);
-    c->mk_count = 0; c->mk_M = 0; c->mk_bone_words = 0; c->mk_morph_words = 0;
+    c->mk = {};
 }
 
 void free_bone_morphs(rz_ctx *c)
 {
-    if (!c->bm_off) return;
-    drop_graph(c);
-    dfree(c->bm_off); dfree(c->bm_morph); dfree(c->bm_rot); dfree(c->bm_tr);
-    c->bm_count = 0;
+    if (c->bm.off) drop_graph(c);
+    c->bm = {};
 }
 
 // A launch shape found by rz_autotune belongs to the workload it was timed on.
@@ -233,48 +210,36 @@ void forget_search(rz_ctx *c)
 void free_sdef(rz_ctx *c)
 {
     drop_graph(c);
-    dfree(c->sdef_tab);
-    c->sdef_n = 0;
-    c->sdef_idx_host.clear();
+    c->sdef = {};
 }
 
 void free_qdef(rz_ctx *c)
 {
     drop_graph(c);
-    dfree(c->qdef_tab);
-    c->qdef_n = 0;
-    c->qdef_idx_host.clear();
+    c->qdef = {};
 }
 
 void free_ik(rz_ctx *c)
 {
-    // chain switches name chains of this table: the mask is all on again and every key set goes (a fork holds no table of its own — its
-    // RzStatic is emptied before this runs — and its mask goes with its context)
-    c->ik_dev_pos.clear(); c->ik_keys_an = {}; c->ik_keys_mo.clear(); c->ik_on_path.clear();
+    // chain switches name chains of this table: the mask is all on again and every key set goes
+    c->ik_keys_an = {}; c->ik_keys_mo.clear();
     c->iksw.words.clear(); c->iksw.off = 0;
-    if (!c->ik_n) return;
-    drop_graph(c);
-    dfree(c->ik_chain); dfree(c->ik_path); dfree(c->ik_stage_off); dfree(c->ik_link);
-    c->ik_n = c->ik_stages = 0;
+    if (c->ik.n) drop_graph(c);
+    c->ik = {};
 }
 
 void free_after(rz_ctx *c)
 {
-    c->af_bones.clear();
-    if (!c->af_n) return;
-    drop_graph(c);
-    dfree(c->af_rec); dfree(c->af_level_off); dfree(c->af_index);
-    c->af_n = c->af_levels = 0;
+    if (c->af.n) drop_graph(c);
+    c->af = {};
 }
 
 void free_morphs(rz_ctx *c)
 {
     forget_search(c);
     drop_graph(c);
-    dfree(c->dense); dfree(c->sp_ptr); dfree(c->sp_entries);
-    dfree(c->dense_fold); c->dense_fold_host.clear(); c->morph_storage = 32;
+    c->morphs = {};
     free_bone_morphs(c);                  // their entries name morphs of the old set
-    c->morph_mode = 0; c->M = 0; c->Mpad = 12; c->sp_count = 0;
     retire_pose_tags(c);                  // ... and so does a pose staged ahead of its frame
     c->pl.cur.set = false;                // morph weights belong to the old target set
 }
@@ -340,10 +305,8 @@ int rz_create(int device, rz_ctx **out)
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (se == hipSuccess) se = hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking);
-    for (int k = 0; k < 2 && se == hipSuccess; ++k) {
-        se = hipEventCreateWithFlags(&c->ev_front[k], hipEventDisableTiming);
-        if (se == hipSuccess) se = hipEventCreateWithFlags(&c->ev_skin[k], hipEventDisableTiming);
-    }
+    if (se == hipSuccess) se = c->ev_front.create();
+    if (se == hipSuccess) se = c->ev_skin.create();
     if (se == hipSuccess) se = hipEventCreate(&c->ev0);
     if (se == hipSuccess) se = hipEventCreate(&c->ev1);
     if (se != hipSuccess) {
@@ -364,40 +327,18 @@ int rz_destroy(rz_ctx *c)
 #endif
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
-    if (c->lender) {                      // a fork frees nothing it borrowed: the free_* calls below find an empty RzStatic
-        static_cast<RzStatic &>(*c) = RzStatic{};
+    if (c->lender) {                      // (what a fork borrowed it holds as aliases, which free nothing: dev_buf.h, Lent)
         c->lender->n_forks--;
         c->lender = nullptr;
     }
     drop_direct_gather(c);
     drop_graph(c);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    // RzStatic ...
-    dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->inv_bind); dfree(c->edge);
-    dfree(c->fk_rec); dfree(c->fk_anc_more);
-    free_animation(c); free_motions(c); free_motion_masks(c); free_morphs(c); free_sdef(c); free_qdef(c); free_ik(c); free_after(c);
-    // ... and what the context owns
-    dfree(c->rj01); dfree(c->rj23); dfree(c->sub_list); dfree(c->sub_count);
-    dfree(c->subfk_rec); dfree(c->subfk_count);
-    c->pl = {};                           // the pose transport: blocks, rings, events
-    dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
-    dfree(c->fol_off); dfree(c->fol_ent);
-    c->iksw = {};
-    free_physics(c);
-    for (int k = 0; k < 2; ++k) {
-        dfree(c->palette_ring[k]); dfree(c->act_idx_ring[k]); dfree(c->act_w_ring[k]); dfree(c->act_count_ring[k]);
-        if (c->ev_front[k]) (void)hipEventDestroy(c->ev_front[k]);
-        if (c->ev_skin[k]) (void)hipEventDestroy(c->ev_skin[k]);
-    }
-    dfree(c->out_pos); dfree(c->out_nrm); dfree(c->g_pos); dfree(c->g_nrm);
-#ifdef RZ_ABLATE
-    dfree(c->tl);
-#endif
+    // what was created by hand; every device buffer, pinned slot and ring event has its owner in the context and goes with it
+    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
 #ifdef RZ_ALL_VARIANTS
     if (c->gate_host) { (void)hipHostFree(c->gate_host); c->gate_host = nullptr; }
 #endif
-    dfree(c->out_hull); dfree(c->aabb);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
@@ -412,12 +353,12 @@ int rz_fork(rz_ctx *parent, rz_ctx **out)
     *out = nullptr;
     if (int r = use(parent)) return r;
     if (parent->lender) return fail(RZ_ERR_INVALID, "rz_fork of a fork: fork the context that owns the static data");
-    if (parent->V == 0 || !parent->geom || parent->B == 0 || !parent->inv_bind) return fail(RZ_ERR_INVALID, "rz_fork needs a mesh and a skeleton (rz_upload_mesh, rz_upload_skeleton)");
+    if (parent->mesh.V == 0 || !parent->mesh.geom || parent->skel.B == 0 || !parent->skel.inv_bind) return fail(RZ_ERR_INVALID, "rz_fork needs a mesh and a skeleton (rz_upload_mesh, rz_upload_skeleton)");
     if (parent->comm || parent->gather_root) return fail(RZ_ERR_UNSUPPORTED, "rz_fork of a context that takes part in a gather");
     HIP_TRY(hipStreamSynchronize(parent->stream));        // every static upload of the lender has landed (before anything is created: nothing to undo on failure)
     rz_ctx *c = nullptr;
     if (int r = rz_create(parent->device, &c)) return r;
-    static_cast<RzStatic &>(*c) = *parent;      // borrowed: the lender's pointers, and copies of the host mirrors the plan reads (plan.cpp: ensure_subfk)
+    static_cast<RzStatic &>(*c) = *parent;      // borrowed: aliases of the lender's tables (dev_buf.h: a copy of a Lent frees nothing), and copies of the host mirrors the plan reads (plan.cpp: ensure_subfk)
     static_cast<RzTuning &>(*c) = *parent;      // inherited
     c->I = parent->I; c->aabb_on = parent->aabb_on; c->aabb_rearm = parent->aabb_on; c->tuned_by_search = parent->tuned_by_search;
     c->ovr_follow = parent->ovr_follow;         // rz_override_follow: a flag of the context, inherited here; the override set and its followers are each context's own
@@ -442,7 +383,7 @@ int rz_output_ptrs(rz_ctx *c, void **pos, void **nrm, uint32_t *v_padded)
     if (int r = ensure_outputs(c)) return r;
     if (pos) *pos = c->ext_pos ? c->ext_pos : c->out_pos;
     if (nrm) *nrm = c->ext_nrm ? c->ext_nrm : c->out_nrm;
-    if (v_padded) *v_padded = c->Vp;
+    if (v_padded) *v_padded = c->mesh.Vp;
     return RZ_OK;
 }
 

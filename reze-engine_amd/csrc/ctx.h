@@ -1,12 +1,16 @@
 // ctx.h — what the translation units of libreze_deform.so's host side share: the context (struct rz_ctx), the error / HIP / RCCL
 // plumbing, the frame plan, and the internal entry points of each unit. Nothing here is part of the C ABI (include/reze_deform.h);
 // everything internal lives in namespace rzi with hidden visibility.
-// The context is three parts, and rz_fork follows them: a fork BORROWS RzStatic (a copy of the struct, the lender's pointers), INHERITS RzTuning
-// (by value), and OWNS everything else: streams, palettes, outputs, and two members that are empty in a fresh fork — the per-frame pose
-// transport (RzPoseLink pl: its rings, and where the current pose is) and physics (RzPhysics ph).
+// The context is three parts, and rz_fork follows them: a fork BORROWS RzStatic (a copy of the struct: its tables are Lent<T>, whose copy
+// aliases the lender's pointer and frees nothing), INHERITS RzTuning (by value), and OWNS everything else: streams, palettes, outputs, and
+// two members that are empty in a fresh fork — the per-frame pose transport (RzPoseLink pl: its rings, and where the current pose is) and
+// physics (RzPhysics ph). Every device buffer, pinned slot and ring event is a member with an owner type (dev_buf.h; Pinned and Events
+// below), so rz_destroy releases them by deleting the context; only streams, the events made by hand, the graph, the communicator, the
+// gather links and the gate's pinned word are destroyed explicitly, in the order that matters there.
 //   core.cpp    context life cycle, buffers every unit sizes, error state            rz_create / rz_destroy / rz_fork / rz_sync ...
 //   upload.cpp  static data: mesh, skeleton, topology, morph targets, motion            rz_upload_* / rz_set_instances / rz_shard_range
 //   pose.cpp    per-frame inputs: RzPoseLink's rings and transitions, copies            rz_set_pose* / rz_override_world / rz_read_world
+//   dev_buf.h   the owners of device memory: Scratch, Grown + grow(), Lent (HIP allocator only)    (no exports)
 //   pose_ring.h the reuse proof of the zero-copy and big-pose rings (no HIP)            (no exports)
 //   plan.cpp    launch shapes and the parameter blocks of the kernels                   (no exports)
 //   frame.cpp   launching frames, replay, timing, readbacks                             rz_deform* / rz_time_frames / rz_read*
@@ -34,6 +38,7 @@
 #include "motion_table.h"
 #include "physics_table.h"
 #include "pose_ring.h"
+#include "dev_buf.h"
 
 #pragma GCC visibility push(hidden)
 namespace rzi {
@@ -53,18 +58,6 @@ const char *last_error();
 
 
 inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
-
-// Device memory with one owner. As a local it is upload-time scratch, or a replacement under construction, released on every exit path
-// (HIP_TRY returns early on failure); as a member it is released when its owner is reset or assigned (`owner = {}`).
-template <class T> struct Scratch {
-    T *p = nullptr;
-    Scratch() = default;
-    Scratch(Scratch &&o) noexcept : p(o.p) { o.p = nullptr; }
-    Scratch &operator=(Scratch &&o) noexcept { std::swap(p, o.p); return *this; }       // (o goes out of scope with what this one held)
-    ~Scratch() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
-    operator T *() const { return p; }
-};
 
 // Pinned host memory with one owner, in Scratch's way, and its device address where the device can read it in place.
 struct Pinned {
@@ -142,92 +135,112 @@ struct RzIkKeySet {
     bool resident = false;              // (a set of no keys is resident too: it says "all on")
 };
 
-// Everything rz_upload_* writes and a frame only reads. A new static table goes here and nowhere else: rz_fork copies the struct as a whole and
-// rz_destroy resets a fork's copy as a whole before anything is freed, so a fork neither misses a table nor frees one.
+// Everything rz_upload_* writes and a frame only reads. A new static table goes here and nowhere else: rz_fork copies the struct as a whole,
+// and a copy of a Lent<T> borrows (dev_buf.h), so a fork neither misses a table nor frees one. What one upload writes is one sub-struct:
+// the upload releases it as a whole (`c->ik = {}`: every array with its counts and host mirrors), then builds the new one, and resets it
+// again if that fails part-way — no count is ever non-zero over a null array, and a new member cannot be forgotten.
 struct RzStatic {
-    // static mesh shard
-    uint32_t V = 0, Vp = 0;
-    float *geom = nullptr;              // 6 x Vp
-    uint32_t *j01 = nullptr, *j23 = nullptr, *wq = nullptr;
-
-    // skeleton
-    uint32_t B = 0;
-    float *inv_bind = nullptr;          // B x 16
-    // optional topology for on-device FK
-    bool has_topology = false;
-    // the hierarchy's static block (kernels/fk.hip.h): [B][4] bone records (topology | bind | the motion's track | ancestors of the first
-    // two doubling rounds) + [an.M][2] vertex-morph records; rebuilt by rebuild_fk_static when the topology or the motion changes
-    uint4 *fk_rec = nullptr;
-    uint2 *fk_anc_more = nullptr;       // [fk_rounds - 2][B] ancestor tables of the doubling rounds beyond the second (depth > 16)
-    int fk_rounds = 0;                  // radix-4 doubling rounds = ceil(log4(depth))
-    std::vector<uint4> fk_host;         // host copy of the bone records (w2 is filled in from an_host_range)
+    template <class T> using Lent = rzi::Lent<T>;
+    // static mesh shard (rz_upload_mesh*)
+    struct Mesh {
+        uint32_t V = 0, Vp = 0;
+        Lent<float> geom;               // 6 x Vp
+        Lent<uint32_t> j01, j23, wq;
+    } mesh;
+    // skeleton (rz_upload_skeleton)
+    struct Skeleton {
+        uint32_t B = 0;
+        Lent<float> inv_bind;           // B x 16
+    } skel;
+    // optional topology for on-device FK (rz_upload_skeleton_topology), and the hierarchy's static block (kernels/fk.hip.h): [B][4] bone
+    // records (topology | bind | the motion's track | ancestors of the first two doubling rounds) + [an.M][2] vertex-morph records; `rec`
+    // alone is rebuilt by rebuild_fk_static when the topology or the motion changes
+    struct Hierarchy {
+        bool has_topology = false;
+        Lent<uint4> rec;
+        Lent<uint2> anc_more;           // [rounds - 2][B] ancestor tables of the doubling rounds beyond the second (depth > 16)
+        int rounds = 0;                 // radix-4 doubling rounds = ceil(log4(depth))
+        std::vector<uint4> host;        // host copy of the bone records (w2 is filled in from an_host_range)
+    } fk;
+    uint64_t fk_gen = 0;                // bumped when the hierarchy's static block is rebuilt or goes (never reset: what was built against it compares)
     // The motion stores: the single motion (rz_upload_animation / rz_set_pose_sampled, sampled inside rz_fk_kernel) and the motion library
     // (rz_upload_motions / rz_set_pose_blended / rz_set_pose_layered; kernels/motion.hip) are the same arrays — motion_table.h's flattening of
-    // one clip, or of all clips concatenated with absolute indices — independent of each other. Raw pointers, not Scratch: a fork borrows
-    // RzStatic by copying the struct and Scratch is move-only; free_keys (core.cpp) is the one release list.
+    // one clip, or of all clips concatenated with absolute indices — independent of each other.
     struct RzKeys {
-        float *key_frame = nullptr, *key_pos = nullptr, *mkey_frame = nullptr, *mkey_weight = nullptr, *feed_ratio = nullptr;
-        float4 *key_rot = nullptr;
-        uint4 *key_interp = nullptr;    // null: no clip carries interpolation bytes
-        uint32_t *feed_off = nullptr;   // [clips][M + 1]
-        uint4 *feed_range = nullptr;    // (first key, end, first frame, last frame) per morph feed
+        Lent<float> key_frame, key_pos, mkey_frame, mkey_weight, feed_ratio;
+        Lent<float4> key_rot;
+        Lent<uint4> key_interp;         // null: no clip carries interpolation bytes
+        Lent<uint32_t> feed_off;        // [clips][M + 1]
+        Lent<uint4> feed_range;         // (first key, end, first frame, last frame) per morph feed
         uint32_t M = 0;                 // vertex-morph count the feeds were built for
     };
     RzKeys an;
     bool has_animation = false;
     std::vector<uint4> an_host_range, an_host_mrec;     // the motion's per-bone track records / per-morph records (host copies)
     RzKeys mo;
-    uint32_t mo_clips = 0;              // clips resident (0 = no library)
-    uint4 *mo_bone_rec = nullptr;       // [mo_clips][B] per clip one 16-byte track record per bone
+    struct Library {
+        uint32_t clips = 0;             // clips resident (0 = no library)
+        Lent<uint4> bone_rec;           // [clips][B] per clip one 16-byte track record per bone
+    } lib;
     // the masks of layered poses (rz_upload_motion_masks / rz_set_pose_layered; kernels/motion.hip): bit sets, one 32-bit word per 32
-    // bones / vertex morphs, mk_bone_words / mk_morph_words words per mask. mk_morph_bits null: every mask includes every morph.
-    uint32_t mk_count = 0, mk_M = 0;    // masks resident (0 = none) / vertex-morph count the morph masks were built for
-    uint32_t *mk_bone_bits = nullptr, *mk_morph_bits = nullptr;
-    uint32_t mk_bone_words = 0, mk_morph_words = 0;
+    // bones / vertex morphs, bone_words / morph_words words per mask. morph_bits null: every mask includes every morph.
+    struct Masks {
+        uint32_t count = 0, M = 0;      // masks resident (0 = none) / vertex-morph count the morph masks were built for
+        Lent<uint32_t> bone_bits, morph_bits;
+        uint32_t bone_words = 0, morph_words = 0;
+    } mk;
     // PMX bone morphs (rz_upload_bone_morphs): entries grouped by bone, ascending morph index inside a bone
-    uint32_t *bm_off = nullptr, *bm_morph = nullptr;
-    float4 *bm_rot = nullptr, *bm_tr = nullptr;
-    uint32_t bm_count = 0;
-    // SDEF vertices of this shard (rz_upload_sdef): [10][sdef_n] planes (kernels/sdef.hip); null = every vertex is skinned as the frame kernel skins it
-    uint32_t *sdef_tab = nullptr;
-    uint32_t sdef_n = 0;
-    // QDEF vertices of this shard (rz_upload_qdef): [qdef_n] indices (kernels/qdef.hip); null = every vertex is skinned as the frame kernel skins it
-    uint32_t *qdef_tab = nullptr;
-    uint32_t qdef_n = 0;
-    std::vector<uint32_t> sdef_idx_host, qdef_idx_host;     // the two tables' vertex lists (a vertex may be in one of them only); read by the two uploads only, which a fork is refused
-    // PMX IK chains of this skeleton (rz_upload_ik), grouped into stages (deform_kernels.h: RzIkParams); ik_n = 0: no IK stage, rz_fk_kernel as ever
-    uint4 *ik_chain = nullptr;
-    uint32_t *ik_path = nullptr, *ik_stage_off = nullptr;
-    float4 *ik_link = nullptr;
-    uint32_t ik_n = 0, ik_stages = 0;
-    // chain switches (rz_set_ik_enabled / rz_upload_ik_keys): where chain k of rz_upload_ik's order sits in the device's order, rebuilt
-    // with every table, and the key sets — of the single motion, and one per clip of the library (empty: no clip holds keys). They go
-    // with the table (free_ik), the motion (free_animation) and the library (free_motions). The MASK is pose state: rz_ctx::iksw.
-    std::vector<uint32_t> ik_dev_pos;
-    std::vector<uint8_t> ik_on_path;    // [B] 1 = the bone lies on a chain's path (outermost link ... effector): what rz_upload_after_physics refuses
+    struct BoneMorphs {
+        Lent<uint32_t> off, morph;
+        Lent<float4> rot, tr;
+        uint32_t count = 0;
+    } bm;
+    // SDEF vertices of this shard (rz_upload_sdef): [10][n] planes (kernels/sdef.hip); QDEF vertices (rz_upload_qdef): [n] indices
+    // (kernels/qdef.hip). tab null = every vertex is skinned as the frame kernel skins it. idx_host: the table's vertex list (a vertex may
+    // be in one of the two only); read by the two uploads only, which a fork is refused
+    struct VertexTable {
+        Lent<uint32_t> tab;
+        uint32_t n = 0;
+        std::vector<uint32_t> idx_host;
+    } sdef, qdef;
+    // PMX IK chains of this skeleton (rz_upload_ik), grouped into stages (deform_kernels.h: RzIkParams); n = 0: no IK stage, rz_fk_kernel as ever
+    struct Ik {
+        Lent<uint4> chain;
+        Lent<uint32_t> path, stage_off;
+        Lent<float4> link;
+        uint32_t n = 0, stages = 0;
+        std::vector<uint32_t> dev_pos;  // where chain k of rz_upload_ik's order sits in the device's order (chain switches: rz_set_ik_enabled / rz_upload_ik_keys)
+        std::vector<uint8_t> on_path;   // [B] 1 = the bone lies on a chain's path (outermost link ... effector): what rz_upload_after_physics refuses
+    } ik;
     // PMX after-physics bones (rz_upload_after_physics; after_table.h, kernels/after.hip): the list in evaluation order as uploaded, and
-    // its device tables (deform_kernels.h: RzAfterParams). af_n = 0: no list, no frame launches rz_fk_after_kernel. Static data: a fork
-    // borrows it; a new skeleton or topology clears it (free_after).
-    std::vector<uint32_t> af_bones;
-    uint4 *af_rec = nullptr;
-    int *af_level_off = nullptr, *af_index = nullptr;
-    uint32_t af_n = 0, af_levels = 0;
+    // its device tables (deform_kernels.h: RzAfterParams). n = 0: no list, no frame launches rz_fk_after_kernel. A new skeleton or
+    // topology clears it (free_after).
+    struct After {
+        std::vector<uint32_t> bones;
+        Lent<uint4> rec;
+        Lent<int> level_off, index;
+        uint32_t n = 0, levels = 0;
+    } af;
+    // the key sets of the chain switches — of the single motion, and one per clip of the library (empty: no clip holds keys). They go
+    // with the IK table (free_ik), the motion (free_animation) and the library (free_motions). The MASK is pose state: rz_ctx::iksw.
     RzIkKeySet ik_keys_an;
     std::vector<RzIkKeySet> ik_keys_mo;
-    // morphs
-    int morph_mode = 0;                 // 0 none, 1 dense, 2 sparse
-    uint32_t M = 0, Mpad = 12;
-    float *dense = nullptr;             // M x 3 x Vp: fp32 planes, or (morph_storage 24) 24-bit integers, 3 * Vp bytes a plane
-    // 24-bit dense storage (upload.cpp: rz_upload_morphs_dense; kernels/common.hip.h): per morph s_m * 2^-8, s_m = the power of two its
-    // integers are multiples of — folded into the weights of every active list. Empty / null with fp32 planes.
-    int morph_storage = 32;             // bits per stored delta of the resident dense set: 24 or 32
-    float *dense_fold = nullptr;        // [M] device
-    std::vector<float> dense_fold_host; // [M] host mirror (the one-launch frame's list is compacted on the host)
-    uint32_t *sp_ptr = nullptr;         // Vp + 1
-    float4 *sp_entries = nullptr;
-    uint64_t sp_count = 0;
-    float *edge = nullptr;              // Vp: the fused hull consumer's edge scale
-    uint64_t fk_gen = 0;                // bumped when the hierarchy's static block is rebuilt
+    // morph targets (rz_upload_morphs_dense* / rz_upload_morphs_sparse)
+    struct Morphs {
+        int mode = 0;                   // 0 none, 1 dense, 2 sparse
+        uint32_t M = 0, Mpad = 12;
+        Lent<float> dense_base;         // the allocation behind `dense`
+        float *dense = nullptr;         // M x 3 x Vp: fp32 planes, or (storage 24) 24-bit integers, 3 * Vp bytes a plane. What frames read: dense_base, or (tools-only build) a place RZ_DENSE_OFFSET bytes into it
+        // 24-bit dense storage (upload.cpp: rz_upload_morphs_dense; kernels/common.hip.h): per morph s_m * 2^-8, s_m = the power of two its
+        // integers are multiples of — folded into the weights of every active list. Empty / null with fp32 planes.
+        int storage = 32;               // bits per stored delta of the resident dense set: 24 or 32
+        Lent<float> dense_fold;         // [M] device
+        std::vector<float> dense_fold_host;     // [M] host mirror (the one-launch frame's list is compacted on the host)
+        Lent<uint32_t> sp_ptr;          // Vp + 1
+        Lent<float4> sp_entries;
+        uint64_t sp_count = 0;
+    } morphs;
+    Lent<float> edge;                   // Vp: the fused hull consumer's edge scale (rz_upload_edge_scale)
 };
 
 // The settable tuning keys (tune.cpp: kTuneKeys names each one; 0 / -1 = automatic). A fork starts with its lender's values.
@@ -368,10 +381,9 @@ struct RzPoseLink {
     } cur;
 
     // what device-produced poses are made from: [I] frames (sampled), [I] states or [I] states + [I][n_layers] layers of a crowd (blended / layered)
-    rzi::Scratch<float> an_frames;
-    rzi::Scratch<RzMotionState> mo_states;
-    rzi::Scratch<RzMotionLayer> mo_layers;
-    size_t an_frames_alloc = 0, mo_states_alloc = 0, mo_layers_alloc = 0;
+    rzi::Grown<float> an_frames;
+    rzi::Grown<RzMotionState> mo_states;
+    rzi::Grown<RzMotionLayer> mo_layers;
     hipStream_t mo_states_stream = nullptr;     // the stream that last wrote and read mo_states (and mo_layers)
     // what the most recent copy upload did (rz_get_tuning: pose_pulled / pose_rows): a crowd's pose (more than 256 KB) is PULLED out of the ring
     // slot by rz_pull_pose_kernel on the upload stream instead of copied, world matrices as their upper three rows (pose.cpp: upload_pose_copy)
@@ -388,18 +400,16 @@ struct rz_ctx : RzStatic, RzTuning {
     float4 *local_q = nullptr;          // I x B   (current pose slot)
 
     // physics hand-off for device-solved frames (rz_override_world)
-    int *ovr_off = nullptr, *ovr_bone = nullptr;
-    float *ovr_world = nullptr;
+    rzi::Grown<int> ovr_off, ovr_bone;   // the three grow as a set (plan.cpp: reserve_overrides)
+    rzi::Grown<float> ovr_world;
     uint32_t ovr_count = 0;
-    size_t ovr_alloc = 0, ovr_off_alloc = 0;
     // rz_override_follow: bones below an overridden bone follow it (kernels/fk.hip.h: FOLLOW). A flag of the context (a fork starts with its
     // lender's value); the lists exist only while it is on and are valid whenever ovr_count != 0 — built wherever the override set is
     // built (rz_override_world, the physics table's per-instance buffers, and the flag's own flip while overrides are resident)
     int ovr_follow = 0;
-    int *fol_off = nullptr;             // [I + 1]
-    uint2 *fol_ent = nullptr;           // [fol_count] (follower bone, entry of its nearest overridden ancestor in the override table)
+    rzi::Grown<int> fol_off;            // [I + 1]
+    rzi::Grown<uint2> fol_ent;          // [fol_count] (follower bone, entry of its nearest overridden ancestor in the override table); grows with fol_off as a set (reserve_followers)
     uint32_t fol_count = 0;
-    size_t fol_alloc = 0, fol_off_alloc = 0;
     std::vector<int> ovr_off_host, ovr_bone_host;       // the hand-fed override set as uploaded (rz_override_world), for a later flip of the flag
 
     // The per-instance chain switches the next solve uses: [I][words] in the device's chain order, set = on, padding bits clear; EMPTY =
@@ -409,8 +419,7 @@ struct rz_ctx : RzStatic, RzTuning {
     struct IkSwitch {
         std::vector<uint32_t> words;
         uint32_t off = 0;               // (instance, chain) bits clear
-        rzi::Scratch<uint32_t> dev;
-        size_t dev_alloc = 0;
+        rzi::Grown<uint32_t> dev;
     } iksw;
 
     RzPhysics ph;                       // rigid-body physics; with a table the override table above is physics' own ([I][ph.nd] slots, fixed addresses)
@@ -429,23 +438,20 @@ struct rz_ctx : RzStatic, RzTuning {
     // front kernels of frame f+1 can run on the upload stream while the skin kernel of frame f is still reading slot f:
     // ev_front[s] = slot s is ready (compute stream waits), ev_skin[s] = the skin kernel that read slot s has been enqueued
     // up to here (the front stream waits before overwriting the slot, two frames later). Used by crowds (overlap_on).
-    float4 *palette_ring[2] = {nullptr, nullptr};
-    uint32_t *act_idx_ring[2] = {nullptr, nullptr};
-    float *act_w_ring[2] = {nullptr, nullptr};
-    int *act_count_ring[2] = {nullptr, nullptr};
+    rzi::Scratch<float4> palette_ring[2];
+    rzi::Scratch<uint32_t> act_idx_ring[2];
+    rzi::Scratch<float> act_w_ring[2];
+    rzi::Scratch<int> act_count_ring[2];
     int ring_slot = 0;
-    hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_skin[2] = {nullptr, nullptr};
+    rzi::Events<2> ev_front, ev_skin;
     bool skin_recorded[2] = {false, false};
     bool overlap_on = false;            // the two streams currently follow the overlapped-front protocol
 
     // outputs
-    float *out_pos = nullptr, *out_nrm = nullptr;
-    size_t out_alloc_floats = 0;
+    rzi::Grown<float> out_pos, out_nrm; // the two grow as a set (core.cpp: ensure_outputs)
     // fused consumers
-    float *out_hull = nullptr;          // I x Vp x 3
-    size_t hull_alloc_floats = 0;
-    uint32_t *aabb = nullptr;           // I x 2 x 6 keys
-    size_t aabb_alloc_inst = 0;
+    rzi::Grown<float> out_hull;         // I x Vp x 3
+    rzi::Grown<uint32_t> aabb;          // I x 2 x 6 keys
     bool aabb_on = false;
     int aabb_slot = 0;                  // slot the NEXT frame accumulates into
     bool aabb_rearm = false;            // both slots must be armed again before the next frame
@@ -454,19 +460,17 @@ struct rz_ctx : RzStatic, RzTuning {
     // Bone-subset crowd frames: per vertex run of the CURRENT launch shape, the ascending list of bones the run's
     // vertices name, and the joints rewritten as slots of that list. Derived from the static mesh, rebuilt (one small kernel +
     // one readback of the counts) whenever the shape (vertices per run, runs), the mesh or the skeleton changes.
-    uint32_t *rj01 = nullptr, *rj23 = nullptr;      // [Vp]
-    uint16_t *sub_list = nullptr;                   // [sub_runs][sub_B]
-    uint32_t *sub_count = nullptr;                  // [sub_runs]
-    size_t sub_list_alloc = 0, sub_count_alloc = 0;
+    rzi::Scratch<uint32_t> rj01, rj23;              // [Vp]
+    rzi::Grown<uint16_t> sub_list;                  // [sub_runs][sub_B]
+    rzi::Grown<uint32_t> sub_count;                 // [sub_runs]
     uint32_t sub_per = 0, sub_runs = 0, sub_B = 0, sub_max = 0;
     bool sub_valid = false;
     bool palette_stale = false;         // the last crowd frame formed its palettes in LDS only (subset form): rz_read_palette forms them on demand
     // Crowd frames of device-animated poses with the hierarchy solved in the skin kernel's front (kernels/crowd.hip:
     // rz_skin_instances_fk_kernel): per vertex run the closure of its named bones under "parent of", one 80-byte record per closure
     // slot — derived from the run lists and the hierarchy's static data, rebuilt when either changes (plan.cpp: ensure_subfk)
-    uint4 *subfk_rec = nullptr;
-    uint32_t *subfk_count = nullptr;
-    size_t subfk_rec_alloc = 0, subfk_count_alloc = 0;
+    rzi::Grown<uint4> subfk_rec;
+    rzi::Grown<uint32_t> subfk_count;
     uint32_t subfk_stride = 0, subfk_rounds = 0;
     bool subfk_valid = false;
     uint64_t subfk_sub_gen = 0, subfk_fk_gen = 0;   // what it was built against
@@ -480,7 +484,7 @@ struct rz_ctx : RzStatic, RzTuning {
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     uint32_t v_total = 0, chunk = 0;
-    float *g_pos = nullptr, *g_nrm = nullptr;   // nranks x chunk x 3
+    rzi::Scratch<float> g_pos, g_nrm;           // nranks x chunk x 3
     // peer-direct gather (rz_gather_direct): this context's kernels store straight into the root's gathered buffer
     float *ext_pos = nullptr, *ext_nrm = nullptr;
     rz_ctx *gather_root = nullptr;              // set on every contributor (the root contributes too)
@@ -489,8 +493,7 @@ struct rz_ctx : RzStatic, RzTuning {
     rz_ctx *lender = nullptr;
     int n_forks = 0;
 #ifdef RZ_ABLATE
-    unsigned long long *tl = nullptr;           // tools-only build: per-wave timeline of the last frame (dbg = 100)
-    size_t tl_waves = 0;
+    rzi::Grown<unsigned long long> tl;          // tools-only build: per-wave timeline of the last frame (dbg = 100), 16 words a wave
 #endif
 #ifdef RZ_ALL_VARIANTS
     uint32_t *gate_host = nullptr, *gate_dev = nullptr;     // tools-only build: rz_debug_gate
@@ -504,10 +507,6 @@ namespace rzi {
 // ---- core.cpp ----
 int use(rz_ctx *c);
 int static_unlocked(const rz_ctx *c, const char *what);       // static data shared between a context and its forks cannot be replaced
-template <class T> void dfree(T *&p)
-{
-    if (p) { (void)hipFree(p); p = nullptr; }
-}
 int poll_event(hipEvent_t ev, const char *what);
 void drop_graph(rz_ctx *c);
 int drain(rz_ctx *c);                  // the upload stream, then the compute stream
@@ -516,7 +515,6 @@ void set_ring(rz_ctx *c, int slot);
 void point_pose_slot(rz_ctx *c, int k);
 void point_pose_at(rz_ctx *c, float *block);     // the current pose lives in `block` (pose_blk[k] or a block of the big-pose ring)
 int ensure_pose_buffers(rz_ctx *c);
-void free_keys(RzStatic::RzKeys &k);
 RzSampleParams sample_params(const RzStatic::RzKeys &k);      // plan.cpp: the sampler's block with the store's pointers set, everything else zero
 void free_animation(rz_ctx *c);
 void free_motions(rz_ctx *c);
@@ -530,11 +528,18 @@ void free_qdef(rz_ctx *c);
 void free_ik(rz_ctx *c);
 void free_after(rz_ctx *c);
 void free_physics(rz_ctx *c);          // physics_host.cpp
-template <typename T> int to_device(T **dst, const void *src, size_t count)
+// a table's array from host data, into an EMPTY owner (Lent or Scratch: the table was reset first). A failure leaves the table to its caller, which resets it as a whole
+template <template <class> class Owner, class T> int to_device(Owner<T> &dst, const void *src, size_t count)
 {
-    *dst = nullptr;
-    HIP_TRY(hipMalloc(dst, std::max<size_t>(count, 4) * sizeof(T)));      // (never fewer than four elements: the specialised sampler asks for key 0 unpredicated — three floats of a position)
-    if (count) HIP_TRY(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+    HIP_TRY(dst.alloc(std::max<size_t>(count, 4)));       // (never fewer than four elements: the specialised sampler asks for key 0 unpredicated — three floats of a position)
+    if (count) HIP_TRY(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return RZ_OK;
+}
+// A buffer of the context outgrown, or several that grow as a set (`c->sub_list.to(n), ...`): dev_buf.h's grow with the context's drain —
+// replacements first, then both streams empty, then every array of the set moves at once. Returns RZ_OK with nothing done while all fit.
+template <class... G> int grow(rz_ctx *c, G &&...g)
+{
+    HIP_TRY(grow([c] { const hipError_t e = hipStreamSynchronize(c->up_stream); return e != hipSuccess ? e : hipStreamSynchronize(c->stream); }, std::forward<G>(g)...));
     return RZ_OK;
 }
 
@@ -561,6 +566,7 @@ RzFkStages solve_stages(const rz_ctx *c, bool overrides = true);
 // the follower lists of an override set (off [I + 1], bones ascending inside an instance) from the resident parents: fol_off [I + 1] and per
 // entry (follower bone, index of its nearest overridden ancestor's entry), ascending by bone inside an instance
 void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent);
+int reserve_overrides(rz_ctx *c, size_t entries, size_t offsets);       // grows ovr_off / ovr_bone / ovr_world as a set (drains and drops the graph when it must; the resident set goes)
 int reserve_followers(rz_ctx *c, size_t entries, size_t offsets);       // grows fol_off / fol_ent (drains and drops the graph when it must)
 int upload_followers(rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones);       // build + blocking upload; the caller has drained
 uint64_t algorithmic_bytes(const rz_ctx *c);

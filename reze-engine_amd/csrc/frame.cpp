@@ -7,8 +7,8 @@ namespace rzi {
 
 int check_ready(rz_ctx *c)
 {
-    if (c->V == 0 || !c->geom) return fail(RZ_ERR_INVALID, "no mesh uploaded (rz_upload_mesh)");
-    if (c->B == 0 || !c->inv_bind) return fail(RZ_ERR_INVALID, "no skeleton uploaded (rz_upload_skeleton)");
+    if (c->mesh.V == 0 || !c->mesh.geom) return fail(RZ_ERR_INVALID, "no mesh uploaded (rz_upload_mesh)");
+    if (c->skel.B == 0 || !c->skel.inv_bind) return fail(RZ_ERR_INVALID, "no skeleton uploaded (rz_upload_skeleton)");
     if (!c->pl.cur.set) return fail(RZ_ERR_INVALID, "no pose set (rz_set_pose)");
     return RZ_OK;
 }
@@ -21,13 +21,13 @@ int launch_fk(rz_ctx *c, hipStream_t st, bool overrides)
     const RzFkStages ss = solve_stages(c, overrides);
     const size_t lds = rz_fk_lds_bytes(fp, ss);
     if (lds > 160 * 1024)
-        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve%s on the device: %u bones need %zu B of LDS (%s; the limit is 160 KB)", ss.ik.n_chains ? " with IK" : "", c->B, lds,
+        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve%s on the device: %u bones need %zu B of LDS (%s; the limit is 160 KB)", ss.ik.n_chains ? " with IK" : "", c->skel.B, lds,
                     ss.ik.n_chains ? "156 B per bone + the pose's morph weights: the IK stage keeps the local pose alive beside both matrix buffers" : "108 B per bone + the pose's morph weights");
     HIP_TRY(rz_launch_fk(fp, ss, c->I, st));
     if (ss.af.n) {
         const size_t after_lds = rz_fk_after_lds_bytes(fp, ss.af);
         if (after_lds > 160 * 1024)
-            return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %d entries x 1 B = %zu B of LDS (the limit is 160 KB)", c->B, ss.af.n, after_lds);
+            return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %d entries x 1 B = %zu B of LDS (the limit is 160 KB)", c->skel.B, ss.af.n, after_lds);
         HIP_TRY(rz_launch_fk_after(fp, ss.af, c->I, st));
     }
     c->palette_stale = false; c->fk_stale = false;
@@ -45,7 +45,7 @@ int launch_prep(rz_ctx *c, hipStream_t st)
 // own — but only while the device-animated pose that frame deformed is still the current one. A new pose, skeleton or topology clears the
 // flag where it goes away (upload_pose, rz_set_pose_sampled, rz_upload_skeleton*); this is the second lock on the same door: rz_fk_kernel
 // on a pose block that holds world matrices, or on the records of a replaced skeleton, would overwrite the resident pose.
-bool solve_on_demand(const rz_ctx *c) { return c->fk_stale && c->pl.cur.local && c->has_topology && c->pl.cur.set && c->fk_rec; }
+bool solve_on_demand(const rz_ctx *c) { return c->fk_stale && c->pl.cur.local && c->fk.has_topology && c->pl.cur.set && c->fk.rec; }
 
 // Everything a frame launches in front of the deform kernel: on-device FK (local-rotation poses) and/or the prep
 // kernel. The FK kernel already writes the palette, so prep is only still needed for its morph compaction.
@@ -54,7 +54,7 @@ int launch_front(rz_ctx *c, const Plan &pl, hipStream_t st)
     if (pl.fuse_fk || pl.subfk) return RZ_OK;       // the deform / crowd kernel solves the hierarchy itself
     if (c->pl.cur.local) {
         if (int r = launch_fk(c, st)) return r;
-        if (pl.prep && c->morph_mode == 1)
+        if (pl.prep && c->morphs.mode == 1)
             if (int r = launch_prep(c, st)) return r;
         return RZ_OK;
     }
@@ -95,10 +95,10 @@ int launch_deform(rz_ctx *c, const Plan &pl)
 // into, and the morph weights where the frame read them. S is RzSdefParams or RzQdefParams (the frame fields carry the same names).
 template <typename S> static void pass_frame_fields(const rz_ctx *c, const Plan &pl, S &s)
 {
-    s.geom = c->geom; s.joints01 = c->j01; s.weights = c->wq; s.palette = c->palette;
-    if (c->morph_mode != 0 && c->M > 0) {
-        s.mode = c->morph_mode; s.M = (int)c->M; s.Mpad = (int)c->Mpad;
-        s.dense = c->dense; s.dense_fold = s.mode == 1 ? c->dense_fold : nullptr; s.sp_ptr = c->sp_ptr; s.sp_entries = c->sp_entries;
+    s.geom = c->mesh.geom; s.joints01 = c->mesh.j01; s.weights = c->mesh.wq; s.palette = c->palette;
+    if (c->morphs.mode != 0 && c->morphs.M > 0) {
+        s.mode = c->morphs.mode; s.M = (int)c->morphs.M; s.Mpad = (int)c->morphs.Mpad;
+        s.dense = c->morphs.dense; s.dense_fold = s.mode == 1 ? c->morphs.dense_fold.get() : nullptr; s.sp_ptr = c->morphs.sp_ptr; s.sp_entries = c->morphs.sp_entries;
         // The weights where this frame's kernels leave or read them, never a pose block that a later upload may overwrite before the pass
         // runs (under the overlapped-front protocol the next pose goes down the upload stream behind this frame's front):
         //   dense, one-launch frame: its kernel-argument list (the weights may only sit in a pinned slot)
@@ -118,15 +118,15 @@ template <typename S> static void pass_frame_fields(const rz_ctx *c, const Plan 
     s.out_pos = c->ext_pos ? c->ext_pos : c->out_pos; s.out_nrm = c->ext_nrm ? c->ext_nrm : c->out_nrm;
     if (c->edge) { s.edge = c->edge; s.out_hull = c->out_hull; }
     if (c->aabb_on) { s.aabb = c->aabb; s.aabb_slot = c->aabb_slot; }
-    s.Vp = c->Vp; s.B = (int)c->B;
+    s.Vp = c->mesh.Vp; s.B = (int)c->skel.B;
 }
 
 RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl)
 {
     RzSdefParams s;
     memset(&s, 0, sizeof s);
-    if (!c->sdef_tab || c->sdef_n == 0) return s;
-    s.tab = c->sdef_tab; s.n = c->sdef_n;
+    if (!c->sdef.tab || c->sdef.n == 0) return s;
+    s.tab = c->sdef.tab; s.n = c->sdef.n;
     pass_frame_fields(c, pl, s);
     return s;
 }
@@ -135,8 +135,8 @@ RzQdefParams qdef_params(const rz_ctx *c, const Plan &pl)
 {
     RzQdefParams s;
     memset(&s, 0, sizeof s);
-    if (!c->qdef_tab || c->qdef_n == 0) return s;
-    s.tab = c->qdef_tab; s.n = c->qdef_n; s.joints23 = c->j23;
+    if (!c->qdef.tab || c->qdef.n == 0) return s;
+    s.tab = c->qdef.tab; s.n = c->qdef.n; s.joints23 = c->mesh.j23;
     pass_frame_fields(c, pl, s);
     s.chunks = c->t_qdefchunks > 0 ? c->t_qdefchunks : 1;       // ("qdef_chunks"; the default is the measured one: NOTEBOOK.md, profiles/qdef_cost.txt)
     return s;
@@ -164,7 +164,7 @@ int launch_passes(rz_ctx *c, const RzSdefParams &sp, const RzQdefParams &qp)
 // the deform / skin kernel of a frame and, when the context has an SDEF or a QDEF table, the passes behind it
 static int launch_deform_passes(rz_ctx *c, const Plan &pl)
 {
-    if (!c->sdef_n && !c->qdef_n) return launch_deform(c, pl);
+    if (!c->sdef.n && !c->qdef.n) return launch_deform(c, pl);
     const RzSdefParams sp = sdef_params(c, pl);
     const RzQdefParams qp = qdef_params(c, pl);
     if (int r = launch_deform(c, pl)) return r;
@@ -178,7 +178,7 @@ bool want_overlap(const rz_ctx *c, const Plan &pl)
 {
     // OPT-IN (overlap = 1): measured on MI355X / ROCm 7.2 the two cross-stream hand-offs per frame cost more than the front
     // kernels they hide — C4 39.0 -> 44.8 us with rz_prep_kernel in front, 43.4 -> 62.1 us with rz_fk_kernel
-    return c->t_overlap == 1 && c->I > 1 && c->morph_mode != 2 && !c->t_graph && (pl.prep || c->pl.cur.local) && !pl.subfk;
+    return c->t_overlap == 1 && c->I > 1 && c->morphs.mode != 2 && !c->t_graph && (pl.prep || c->pl.cur.local) && !pl.subfk;
 }
 
 // Switching protocols is rare (instance count, tuning keys): drain both streams so that nothing enqueued under the old
@@ -263,7 +263,7 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     h = fnv(h, &qd, sizeof qd);
     const RzFkStages ss = solve_stages(c);     // whole and unconditionally: a stage that is off is the same zeros in every frame
     h = fnv(h, &ss, sizeof ss);
-    const uint64_t misc[6] = { c->I, c->pl.cur.local, c->pl.cur.local_t, c->pl.cur.sampled, (uint64_t)c->morph_mode, (uint64_t)c->aabb_on };
+    const uint64_t misc[6] = { c->I, c->pl.cur.local, c->pl.cur.local_t, c->pl.cur.sampled, (uint64_t)c->morphs.mode, (uint64_t)c->aabb_on };
     return fnv(h, misc, sizeof misc);
 }
 
@@ -376,10 +376,10 @@ int rz_read(rz_ctx *c, uint32_t instance, uint32_t v0, uint32_t n, float *pos3, 
 {
     if (int r = use(c)) return r;
     if (instance >= c->I) return fail(RZ_ERR_INVALID, "instance %u out of range", instance);
-    if ((uint64_t)v0 + n > c->V) return fail(RZ_ERR_INVALID, "vertex range [%u,%u) exceeds %u", v0, v0 + n, c->V);
+    if ((uint64_t)v0 + n > c->mesh.V) return fail(RZ_ERR_INVALID, "vertex range [%u,%u) exceeds %u", v0, v0 + n, c->mesh.V);
     if (!c->out_pos) return fail(RZ_ERR_INVALID, "nothing deformed yet");
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t off = ((size_t)instance * c->Vp + v0) * 3;
+    const size_t off = ((size_t)instance * c->mesh.Vp + v0) * 3;
     const float *sp = c->ext_pos ? c->ext_pos : c->out_pos, *sn = c->ext_nrm ? c->ext_nrm : c->out_nrm;
     if (pos3 && n) HIP_TRY(hipMemcpy(pos3, sp + off, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (nrm3 && n) HIP_TRY(hipMemcpy(nrm3, sn + off, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
@@ -402,7 +402,7 @@ int rz_read_palette(rz_ctx *c, uint32_t instance, float *rows3x4)
         if (int r = launch_prep(c, c->stream)) return r;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(rows3x4, c->palette + (size_t)instance * c->B * 3, (size_t)c->B * 12 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rows3x4, c->palette + (size_t)instance * c->skel.B * 3, (size_t)c->skel.B * 12 * sizeof(float), hipMemcpyDeviceToHost));
     return RZ_OK;
 }
 
@@ -410,9 +410,9 @@ int rz_read_hull(rz_ctx *c, uint32_t instance, uint32_t v0, uint32_t n, float *p
 {
     if (int r = use(c)) return r;
     if (!c->edge || !c->out_hull) return fail(RZ_ERR_INVALID, "the outline hull is off (rz_upload_edge_scale)");
-    if (instance >= c->I || (uint64_t)v0 + n > c->V || !pos3) return fail(RZ_ERR_INVALID, "bad hull read");
+    if (instance >= c->I || (uint64_t)v0 + n > c->mesh.V || !pos3) return fail(RZ_ERR_INVALID, "bad hull read");
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n) HIP_TRY(hipMemcpy(pos3, c->out_hull + ((size_t)instance * c->Vp + v0) * 3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(pos3, c->out_hull + ((size_t)instance * c->mesh.Vp + v0) * 3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
     return RZ_OK;
 }
 
@@ -476,7 +476,7 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
         out->prep_kernel_ms = ms / frames;
     }
     c->skin_recorded[0] = c->skin_recorded[1] = false;      // both streams are idle: no slot has a reader in flight
-    out->verts_per_frame = (uint64_t)c->V * c->I;
+    out->verts_per_frame = (uint64_t)c->mesh.V * c->I;
     out->algorithmic_bytes_per_frame = algorithmic_bytes(c);
     out->frames = frames;
     return RZ_OK;
@@ -518,8 +518,8 @@ __attribute__((visibility("default"))) int rz_debug_timeline_arm(rz_ctx *c, uint
     const size_t groups = pl.inst_group > 0 ? (c->I + pl.inst_group - 1) / pl.inst_group : c->I;
     const size_t n = ((size_t)pl.grid_x + 1) * groups * wpw;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n > c->tl_waves) { dfree(c->tl); HIP_TRY(hipMalloc(&c->tl, n * 128)); c->tl_waves = n; }
-    HIP_TRY(hipMemset(c->tl, 0, c->tl_waves * 128));
+    if (int r = grow(c, c->tl.to(n * 16))) return r;
+    HIP_TRY(hipMemset(c->tl, 0, c->tl.capacity() * sizeof(unsigned long long)));
     c->t_dbg = 100;
     drop_graph(c);
     if (waves) *waves = (uint32_t)n;
@@ -528,7 +528,7 @@ __attribute__((visibility("default"))) int rz_debug_timeline_arm(rz_ctx *c, uint
 __attribute__((visibility("default"))) int rz_debug_timeline_read(rz_ctx *c, unsigned long long *out, uint32_t waves)
 {
     if (int r = use(c)) return r;
-    if (!c->tl || waves > c->tl_waves || !out) return fail(RZ_ERR_INVALID, "no timeline armed");
+    if (!c->tl || waves > c->tl.capacity() / 16 || !out) return fail(RZ_ERR_INVALID, "no timeline armed");
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, c->tl, (size_t)waves * 128, hipMemcpyDeviceToHost));
     return RZ_OK;

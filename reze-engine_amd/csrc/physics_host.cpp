@@ -32,15 +32,7 @@ static int ensure_instances(rz_ctx *c)
     const size_t I = c->I, nd = ph.nd, n = I * nd;
     HIP_TRY(ph.state.alloc(I * ph.nb * 4));
     HIP_TRY(hipMemset(ph.state, 0, I * ph.nb * 4 * sizeof(float4)));
-    if (n > c->ovr_alloc || I + 1 > c->ovr_off_alloc) {
-        dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
-        c->ovr_alloc = c->ovr_off_alloc = 0;
-        const size_t cap = std::max<size_t>(n, 64);
-        HIP_TRY(hipMalloc(&c->ovr_off, (I + 1) * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->ovr_bone, cap * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->ovr_world, cap * 16 * sizeof(float)));
-        c->ovr_alloc = cap; c->ovr_off_alloc = I + 1;
-    }
+    if (int r = reserve_overrides(c, n, I + 1)) return r;
     std::vector<int> off(I + 1), bones(std::max<size_t>(n, 1));
     for (size_t i = 0; i <= I; ++i) off[i] = (int)(i * nd);
     for (size_t i = 0; i < I; ++i)
@@ -73,7 +65,7 @@ static RzPhysicsParams physics_params(const rz_ctx *c, uint32_t substeps, bool r
     memset(&p, 0, sizeof p);
     p.body = ph.body; p.joint = ph.joint; p.colour_off = ph.colour_off; p.state = ph.state;
     p.world = c->world; p.ovr_world = c->ovr_world;
-    p.nb = (int)ph.nb; p.nj = (int)ph.nj; p.ncol = (int)ph.ncol; p.nd = (int)ph.nd; p.B = (int)c->B;
+    p.nb = (int)ph.nb; p.nj = (int)ph.nj; p.ncol = (int)ph.ncol; p.nd = (int)ph.nd; p.B = (int)c->skel.B;
     p.iterations = ph.iterations; p.substeps = (int)substeps; p.reset = (reset || ph.reset) ? 1 : 0; p.block = ph.block;
     p.h = ph.h; p.gx = ph.g[0]; p.gy = ph.g[1]; p.gz = ph.g[2];
     p.c_shape = k.shape; p.c_follow_off = k.follow_off; p.c_follow_idx = k.follow_idx; p.c_pair = k.pair;
@@ -86,7 +78,7 @@ static RzPhysicsParams physics_params(const rz_ctx *c, uint32_t substeps, bool r
 static int step(rz_ctx *c, uint32_t substeps, bool reset)
 {
     if (!c->pl.cur.set) return fail(RZ_ERR_INVALID, "rz_physics_step: no pose set");
-    if (!c->pl.cur.local || !c->has_topology)
+    if (!c->pl.cur.local || !c->fk.has_topology)
         return fail(RZ_ERR_INVALID, "rz_physics_step acts on device-solved poses (rz_set_pose_local, rz_set_pose_sampled, rz_set_pose_blended): with rz_set_pose the host owns the world matrices");
     if (int r = ensure_instances(c)) return r;
     hipStream_t st = front_stream(c);
@@ -107,15 +99,15 @@ static int step(rz_ctx *c, uint32_t substeps, bool reset)
 // table as the caller gave it. `given` may point into c->ph.kept: it is copied before the old table goes.
 static int install(rz_ctx *c, const rz_physics *given, bool aligned)
 {
-    std::vector<int32_t> parents(c->B);
-    std::vector<float> bind((size_t)c->B * 3);
-    for (uint32_t b = 0; b < c->B; ++b) {
-        parents[b] = (int32_t)c->fk_host[4 * b].x;
-        memcpy(&bind[(size_t)b * 3], &c->fk_host[4 * b + 1], 12);
+    std::vector<int32_t> parents(c->skel.B);
+    std::vector<float> bind((size_t)c->skel.B * 3);
+    for (uint32_t b = 0; b < c->skel.B; ++b) {
+        parents[b] = (int32_t)c->fk.host[4 * b].x;
+        memcpy(&bind[(size_t)b * 3], &c->fk.host[4 * b + 1], 12);
     }
     rzphys::Derived d;
     std::string bad;
-    if (int r = rzphys::derive(given, c->B, parents.data(), bind.data(), aligned, d, bad)) return fail(r, "%s", bad.c_str());
+    if (int r = rzphys::derive(given, c->skel.B, parents.data(), bind.data(), aligned, d, bad)) return fail(r, "%s", bad.c_str());
     const rzphys::Built &o = d.built;
     RzPhysics::Aligned al;
     al.on = aligned ? 1 : 0;
@@ -129,9 +121,9 @@ static int install(rz_ctx *c, const rz_physics *given, bool aligned)
     c->ovr_count = 0;                   // hand-fed overrides end here: the table is physics' own from now on
     // (the old table has gone, as it always had by here: a failed allocation leaves the context without one)
     RzPhysics ph;
-    if (int r = to_device(&ph.body.p, o.body.data(), (size_t)o.nb * 4)) return r;
-    if (int r = to_device(&ph.joint.p, o.joint.data(), (size_t)o.nj * 8)) return r;
-    if (int r = to_device(&ph.colour_off.p, o.colour_off.data(), o.colour_off.size())) return r;
+    if (int r = to_device(ph.body, o.body.data(), (size_t)o.nb * 4)) return r;
+    if (int r = to_device(ph.joint, o.joint.data(), (size_t)o.nj * 8)) return r;
+    if (int r = to_device(ph.colour_off, o.colour_off.data(), o.colour_off.size())) return r;
     ph.nb = (uint32_t)o.nb; ph.nj = (uint32_t)o.nj; ph.ncol = (uint32_t)o.ncol; ph.nd = (uint32_t)o.nd;
     ph.iterations = o.iterations; ph.h = o.h; ph.hd = o.hd;
     for (int k = 0; k < 3; ++k) ph.g[k] = o.g[k];
@@ -158,7 +150,7 @@ int rz_upload_physics(rz_ctx *c, const rz_physics *t)
         free_physics(c);
         return RZ_OK;
     }
-    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+    if (!c->fk.has_topology || c->fk.host.size() != (size_t)c->skel.B * 4)
         return fail(RZ_ERR_INVALID, "rz_upload_physics needs the hierarchy: call rz_upload_skeleton_topology first");
     return install(c, t, false);
 }
@@ -168,7 +160,7 @@ int rz_physics_aligned(rz_ctx *c, uint32_t on)
     if (int r = use(c)) return r;
     if (int r = physics_usable(c, "rz_physics_aligned")) return r;
     if (int r = static_unlocked(c, "rz_physics_aligned")) return r;
-    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+    if (!c->fk.has_topology || c->fk.host.size() != (size_t)c->skel.B * 4)
         return fail(RZ_ERR_INVALID, "rz_physics_aligned needs the hierarchy: call rz_upload_skeleton_topology first");
     const rz_physics t = c->ph.kept.view();
     return install(c, &t, on != 0);
@@ -204,13 +196,13 @@ int rz_physics_contacts(rz_ctx *c, uint32_t on)
     if (o.too_many) return fail(RZ_ERR_UNSUPPORTED, "%s", rzphys::contacts_refusal(o).c_str());
     // the new lists first, in a part of their own: a failed allocation leaves the context as it was
     RzPhysics::Contacts k;
-    if (int r = to_device(&k.shape.p, o.shape.data(), t.n_bodies)) return r;
+    if (int r = to_device(k.shape, o.shape.data(), t.n_bodies)) return r;
     if (mode >= 2)
-        if (int r = to_device(&k.box.p, o.box.data(), t.n_bodies)) return r;
-    if (int r = to_device(&k.follow_off.p, o.follow_off.data(), o.follow_off.size())) return r;
-    if (int r = to_device(&k.follow_idx.p, o.follow_idx.data(), o.follow_idx.size())) return r;
-    if (int r = to_device(&k.pair.p, o.pair.data(), o.pair.size() / 2)) return r;
-    if (int r = to_device(&k.colour_off.p, o.colour_off.data(), o.colour_off.size())) return r;
+        if (int r = to_device(k.box, o.box.data(), t.n_bodies)) return r;
+    if (int r = to_device(k.follow_off, o.follow_off.data(), o.follow_off.size())) return r;
+    if (int r = to_device(k.follow_idx, o.follow_idx.data(), o.follow_idx.size())) return r;
+    if (int r = to_device(k.pair, o.pair.data(), o.pair.size() / 2)) return r;
+    if (int r = to_device(k.colour_off, o.colour_off.data(), o.colour_off.size())) return r;
     k.follow = (uint32_t)o.n_follow; k.pairs = (uint32_t)o.n_pairs; k.ncol = (uint32_t)o.ncol; k.boxes = (uint32_t)o.boxes;
     k.box_pairs = (uint32_t)o.box_pairs; k.box_box = (uint32_t)o.n_box_box;
     k.mode = mode;
@@ -241,7 +233,7 @@ int rz_physics_springs(rz_ctx *c, uint32_t on)
     // the old kernels
     RzPhysics::Springs s;
     if (o.axes)
-        if (int r = to_device(&s.lin.p, o.rec.data(), c->ph.nj)) return r;
+        if (int r = to_device(s.lin, o.rec.data(), c->ph.nj)) return r;
     s.axes = (uint32_t)o.axes;
     s.on = 1;
     if (int r = drain(c)) return r;
@@ -254,7 +246,7 @@ int rz_physics_reset(rz_ctx *c)
 {
     if (int r = use(c)) return r;
     if (int r = physics_usable(c, "rz_physics_reset")) return r;
-    if (!c->pl.cur.set || !c->pl.cur.local || !c->has_topology) {       // nothing to stand the bodies on yet: the next step does it
+    if (!c->pl.cur.set || !c->pl.cur.local || !c->fk.has_topology) {       // nothing to stand the bodies on yet: the next step does it
         c->ph.reset = true;
         c->ovr_count = 0;
         return RZ_OK;

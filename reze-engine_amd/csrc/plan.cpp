@@ -9,7 +9,7 @@ namespace {
 
 int auto_split(const rz_ctx *c)
 {
-    if (c->morph_mode != 1) return 1;
+    if (c->morphs.mode != 1) return 1;
     // S lanes share a quad, so waves = quads * S / 64, and a wave step is 256 / S vertices whose skin phase (and output stores) follow
     // its morph loads. Measured on MI355X, round 6 (tools/plan_sweep.py: 15 mesh sizes x {S} x {whole steps per wave}, round-robin
     // medians, profiles/r6_plan_sweep.txt): the 1 M-vertex mesh streams 3 % faster with two lanes per quad than with one and S = 2 stays
@@ -20,11 +20,11 @@ int auto_split(const rz_ctx *c)
     // The S = 2 / S = 4 boundary sits where S = 4 stops filling three whole 64-vertex steps per wave of the persistent grid (~367 k
     // vertices): between 300 k and 365 k vertices S = 2 left every wave with 1.25-1.5 steps and ran 6-12 % behind S = 4 in every one of
     // 24 fresh processes (tools/fresh_plans.py, profiles/r6_fresh_plans_mid.txt: 313 856 vertices 47.2-47.8 us against 41.1-41.9).
-    const uint64_t quads = (uint64_t)c->Vp / 4 * c->I;
+    const uint64_t quads = (uint64_t)c->mesh.Vp / 4 * c->I;
     int S = 2;
     if (quads * 2 / 64 < 2870) S = 4;
     if (quads * 4 / 64 < 1500) S = 8;
-    while (S > 1 && (uint32_t)S > c->M) S >>= 1;
+    while (S > 1 && (uint32_t)S > c->morphs.M) S >>= 1;
     return S;
 }
 
@@ -68,11 +68,11 @@ void inst_runs(const rz_ctx *c, int G, int blk, bool for_subsets, uint32_t *per,
     const uint32_t groups = (c->I + G - 1) / G;
     const uint32_t total = c->t_grid_cap > 0 ? (uint32_t)c->t_grid_cap : wg_per_cu * (uint32_t)c->n_cu;
     const uint32_t gxi = std::max<uint32_t>(1, total / groups);
-    *per = round_up((c->V + gxi - 1) / gxi, 64);
-    *runs = (c->V + *per - 1) / *per;
+    *per = round_up((c->mesh.V + gxi - 1) / gxi, 64);
+    *runs = (c->mesh.V + *per - 1) / *per;
     if (*runs > 0xffffu) {                  // the crowd kernel takes its launch shape as two 16-bit fields of one preloaded argument
-        *per = round_up((c->V + 0xfffeu) / 0xffffu, 64);
-        *runs = (c->V + *per - 1) / *per;
+        *per = round_up((c->mesh.V + 0xfffeu) / 0xffffu, 64);
+        *runs = (c->mesh.V + *per - 1) / *per;
     }
 }
 
@@ -97,27 +97,27 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
 {
     RzDeformParams p;
     memset(&p, 0, sizeof p);
-    p.geom = c->geom; p.joints01 = c->j01; p.joints23 = c->j23; p.weights = c->wq;
-    p.palette = c->palette; p.world = src_world(c); p.inv_bind = c->inv_bind; p.dense = c->dense; p.dense_fold = c->dense_fold;
+    p.geom = c->mesh.geom; p.joints01 = c->mesh.j01; p.joints23 = c->mesh.j23; p.weights = c->mesh.wq;
+    p.palette = c->palette; p.world = src_world(c); p.inv_bind = c->skel.inv_bind; p.dense = c->morphs.dense; p.dense_fold = c->morphs.dense_fold;
     p.act_idx = c->act_idx; p.act_w = c->act_w; p.act_count = c->act_count; p.morph_w = src_morph_w(c);
     if (pl.v.fast && c->pl.cur.zc_slot >= 0) {            // the one-launch kernel's workgroup 0 makes the pose resident
         if (!c->pl.cur.world_resident && !c->pl.cur.zc_local) p.world_copy = c->world;
         if (!c->pl.cur.mw_resident && pl.v.mode == 2) p.morph_w_copy = c->morph_w;
         if (pl.pf && p.world_copy && c->pl.tag && c->pl.cur.seq) {
             prefetch_params(c, p, 0);
-            p.st_world = c->world; p.st_morph_w = (pl.v.mode == 2 && c->M > 0) ? c->morph_w : nullptr;
+            p.st_world = c->world; p.st_morph_w = (pl.v.mode == 2 && c->morphs.M > 0) ? c->morph_w : nullptr;
         }
     }
-    p.sp_ptr = c->sp_ptr; p.sp_entries = c->sp_entries;
+    p.sp_ptr = c->morphs.sp_ptr; p.sp_entries = c->morphs.sp_entries;
     p.out_pos = c->ext_pos ? c->ext_pos : c->out_pos; p.out_nrm = c->ext_nrm ? c->ext_nrm : c->out_nrm;
-    p.edge = c->edge; p.out_hull = c->out_hull; p.aabb = c->aabb_on ? c->aabb : nullptr; p.aabb_slot = c->aabb_slot;
-    p.n_verts = c->V;
-    p.Vp = c->Vp; p.n_quads = pl.n_quads; p.quads_per_wave = pl.quads_per_wave; p.dma = pl.dma ? 1 : 0;
-    p.B = (int)c->B; p.M = (int)c->M; p.Mpad = (int)c->Mpad;
+    p.edge = c->edge; p.out_hull = c->out_hull; p.aabb = c->aabb_on ? c->aabb.get() : nullptr; p.aabb_slot = c->aabb_slot;
+    p.n_verts = c->mesh.V;
+    p.Vp = c->mesh.Vp; p.n_quads = pl.n_quads; p.quads_per_wave = pl.quads_per_wave; p.dma = pl.dma ? 1 : 0;
+    p.B = (int)c->skel.B; p.M = (int)c->morphs.M; p.Mpad = (int)c->morphs.Mpad;
     p.inst_order = c->t_instorder;
 #ifdef RZ_ABLATE
     p.dbg = c->t_dbg == 100 ? 0 : c->t_dbg;
-    p.tl = c->t_dbg == 100 ? c->tl : nullptr;      // (allocated by rz_debug_timeline_arm)
+    p.tl = c->t_dbg == 100 ? c->tl.get() : nullptr;      // (allocated by rz_debug_timeline_arm)
 #endif
     p.out_cap = pl.out_cap;
     p.sp_cap = pl.sp_cap;
@@ -127,15 +127,15 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
         p.fk = fk_params(c); p.fk_on = 1;
         // the specialised variants (fk_solve<true, KIND>): no physics overrides, two bones per thread, one morph per thread;
         // "fuse_fk_plain" = 0 keeps the generic kernel (A/B, tests)
-        const bool plain = c->t_fkplain != 0 && !p.fk.ovr_off && c->B <= 512 && c->M <= 256 && (!c->pl.cur.sampled || c->an.M <= 256);
+        const bool plain = c->t_fkplain != 0 && !p.fk.ovr_off && c->skel.B <= 512 && c->morphs.M <= 256 && (!c->pl.cur.sampled || c->an.M <= 256);
         p.fk_kind = plain ? (c->pl.cur.sampled ? 2 : 1) : 0;
         if (c->pl.cur.zc_slot >= 0 && c->pl.cur.zc_local && !c->pl.cur.sampled && (!c->pl.cur.local_resident || !c->pl.cur.mw_resident)) {
             // zero-copy local pose, first frame: workgroup 0 makes it resident (every later frame of this pose reads the device
             // block instead of pulling the pose over the host link in every workgroup), and — like the one-launch frame of a
             // world pose — the frame looks for a copy the previous frame's helper staged and carries a helper for the next upload
-            float *blk_t = c->pl.cur.local_t ? reinterpret_cast<float *>(c->local_q + c->B) : nullptr;
+            float *blk_t = c->pl.cur.local_t ? reinterpret_cast<float *>(c->local_q + c->skel.B) : nullptr;
             p.fk.copy_q = c->local_q; p.fk.copy_t = blk_t;
-            if (c->M > 0) p.morph_w_copy = c->morph_w;
+            if (c->morphs.M > 0) p.morph_w_copy = c->morph_w;
             if (pl.pf && c->pl.tag && c->pl.cur.seq) {
                 prefetch_params(c, p, c->morph_w - c->pl.pose_blk[c->pl.pose_slot].p);     // the local range of the other block
                 p.fk.st_expect = c->pl.cur.seq;
@@ -152,8 +152,8 @@ bool inst_shape(const rz_ctx *c, InstShape *s)
 {
     const bool epilogues = c->edge != nullptr || c->aabb_on;   // only the generic kernel carries the fused consumers
     // sparse targets: only when "inst_morphs" asks (auto = off: every such crowd keeps the generic kernel, one launch row per instance)
-    s->morphs = c->morph_mode == 2 && c->t_instmorphs == 1 && c->M > 0 && c->sp_ptr && c->sp_entries;
-    if (!((c->morph_mode == 0 || s->morphs) && c->I > 1 && c->t_instloop != 0 && c->t_instloop != 9 && !epilogues) || c->B == 0 || c->V == 0) return false;
+    s->morphs = c->morphs.mode == 2 && c->t_instmorphs == 1 && c->morphs.M > 0 && c->morphs.sp_ptr && c->morphs.sp_entries;
+    if (!((c->morphs.mode == 0 || s->morphs) && c->I > 1 && c->t_instloop != 0 && c->t_instloop != 9 && !epilogues) || c->skel.B == 0 || c->mesh.V == 0) return false;
     s->want_in_kernel = c->t_fast != 0 && !c->pl.cur.local;
     // workgroup size. Whole palettes: 512 threads for the one-launch frame (one workgroup of 8 waves per CU shares the 102 KB
     // group), 256 behind rz_prep_kernel / rz_fk_kernel (two workgroups of 80 KB each: measured best in round 2). Bone subsets
@@ -175,19 +175,19 @@ Plan make_plan(const rz_ctx *c)
     Plan pl;
     memset(&pl, 0, sizeof pl);          // padding too: frame_signature() hashes the struct
     RzVariant &v = pl.v;
-    v.mode = c->morph_mode;
+    v.mode = c->morphs.mode;
     // Without dense targets S only sets the size of a wave step: S = 4 makes it 64 vertices instead of 256, so a small
     // mesh (one 30 k-vertex character is 118 wave steps at S = 1) reaches four times as many CUs, and a region where
     // every vertex carries dozens of sparse entries (a face) spreads over four times as many waves. 1 or 4 there.
     v.S = (v.mode == 1) ? (c->t_split > 0 ? c->t_split : auto_split(c))
                         : (c->t_split > 0 ? (c->t_split >= 4 ? 4 : 1)
-                                          : ((uint64_t)c->V * c->I <= (v.mode == 2 ? (256u << 10) : (64u << 10)) ? 4 : 1));   // measured: 30 k verts 5.5 -> 4.5 us, 126 k 6.0 -> 6.6
+                                          : ((uint64_t)c->mesh.V * c->I <= (v.mode == 2 ? (256u << 10) : (64u << 10)) ? 4 : 1));   // measured: 30 k verts 5.5 -> 4.5 us, 126 k 6.0 -> 6.6
     v.U = c->t_unroll > 0 ? c->t_unroll : 8;    // 24 loads in flight per lane: best or tied at every size measured
     v.nt = c->t_nt != 0;
     // streaming stores pay once the frame's output no longer fits the L2s (measured: 1 M verts yes, 126 k no)
     // and the morph stream is flowing too; a morph-free instanced frame (184 MB of output, MALL-absorbed) is faster
     // with plain stores: 6.9 vs 5.7 TB/s in tools/membench
-    v.nts = c->t_nts < 0 ? (v.mode == 1 && (uint64_t)c->V * c->I * 24 >= (16u << 20)) : c->t_nts != 0;
+    v.nts = c->t_nts < 0 ? (v.mode == 1 && (uint64_t)c->mesh.V * c->I * 24 >= (16u << 20)) : c->t_nts != 0;
     v.geo = c->t_geo != 0;
     // one-launch frame: single instance, and (dense) the active list fits the kernel arguments
     // Device-animated single character: the hierarchy solve (and the motion sampling) runs as the prologue of every
@@ -198,8 +198,8 @@ Plan make_plan(const rz_ctx *c)
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
     // (the fused kernels' embedded solve carries no stage: any stage of solve_stages — an IK table, resident follower entries, after-physics
     // bones behind overrides — keeps the solve in rz_fk_kernel, whose instantiations do)
-    pl.fuse_fk = solve_stages(c).plain() && c->I == 1 && c->pl.cur.local && c->has_topology && (size_t)c->B * 48 + rz_fk_scratch_bytes((int)c->B) + (size_t)c->M * 12 + 4096 <= 160 * 1024 &&
-                 (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pl.cur.sampled || c->morph_mode != 1)));
+    pl.fuse_fk = solve_stages(c).plain() && c->I == 1 && c->pl.cur.local && c->fk.has_topology && (size_t)c->skel.B * 48 + rz_fk_scratch_bytes((int)c->skel.B) + (size_t)c->morphs.M * 12 + 4096 <= 160 * 1024 &&
+                 (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pl.cur.sampled || c->morphs.mode != 1)));
     const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->pl.cur.ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
     pl.dma = false;
@@ -207,7 +207,7 @@ Plan make_plan(const rz_ctx *c)
     pl.verts_per_wg = 0;
     pl.poses_per_wg = 0;
     pl.out_cap = 0;
-    pl.n_quads = (c->V + 3) / 4;
+    pl.n_quads = (c->mesh.V + 3) / 4;
     pl.quads_per_wave = 8;
     pl.grid_x = 1;
     pl.prep = !v.fast && !pl.fuse_fk;
@@ -231,7 +231,7 @@ Plan make_plan(const rz_ctx *c)
     // (2.25 / 2.5 / 3.25 steps of 128 vertices) the same grid at S = 4 — 64-vertex steps, the ragged last one half the size — was faster in
     // every one of 36 fresh processes: 530-580 k vertices 7-8 %, 596-613 k 3 %, 797-845 k 4 % (profiles/r6_fresh_plans_hi.txt). Its own
     // runs keep the 8-quad grain: rounded up to whole 64-vertex steps on fewer workgroups they were 0.4-4 % slower in 28 processes of 28.
-    if (dense_rules && one_mesh && c->t_split <= 0 && v.S == 2 && c->M >= 4 && per_wave > 32 && per_wave % 32 != 0) {
+    if (dense_rules && one_mesh && c->t_split <= 0 && v.S == 2 && c->morphs.M >= 4 && per_wave > 32 && per_wave % 32 != 0) {
         v.S = 4;
         per_wave = run_per_wave(pl.n_quads, cap_i, v.S, false, true);
     }
@@ -239,7 +239,7 @@ Plan make_plan(const rz_ctx *c)
     // multiple of 32 quads = 384 B, so it starts on a 128-byte line of every plane. Applied AFTER the split is chosen: the heuristic
     // plans above are what they are for fp32 planes (an S = 2 run that survives them is a multiple of 32 already, or a single short
     // step), so this only moves forced shapes (morph_split / grid_cap). S = 4 / 8 read through the cache and keep the 8-quad grain.
-    if (v.mode == 1 && c->morph_storage == 24 && v.S <= 2 && per_wave > 32) per_wave = round_up(per_wave, 32);
+    if (v.mode == 1 && c->morphs.storage == 24 && v.S <= 2 && per_wave > 32) per_wave = round_up(per_wave, 32);
     pl.quads_per_wave = per_wave;
     pl.grid_x = std::max<uint32_t>(1, (pl.n_quads + per_wave * waves_per_wg - 1) / (per_wave * waves_per_wg));
     // LDS write batching. Measured (tools/archive/ablate_c5.py): parking a wave's WHOLE run and writing it once at the end
@@ -254,7 +254,7 @@ Plan make_plan(const rz_ctx *c)
         if (pl.out_cap) {
             RzDeformParams q;
             memset(&q, 0, sizeof q);
-            q.B = (int)c->B; q.M = (int)c->M; q.Mpad = (int)c->Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
+            q.B = (int)c->skel.B; q.M = (int)c->morphs.M; q.Mpad = (int)c->morphs.Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
             q.sp_cap = 16;      // (counted for sparse targets only: the buffer must leave room for the smallest piece below, or the frame is refused for a buffer it can do without)
             if (rz_deform_lds_bytes(q, v) > 160 * 1024) pl.out_cap = 0;
         }
@@ -266,14 +266,14 @@ Plan make_plan(const rz_ctx *c)
     if (v.mode == 2) {
         RzDeformParams q;
         memset(&q, 0, sizeof q);
-        q.B = (int)c->B; q.M = (int)c->M; q.Mpad = (int)c->Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
+        q.B = (int)c->skel.B; q.M = (int)c->morphs.M; q.Mpad = (int)c->morphs.Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
         const size_t base = rz_deform_lds_bytes(q, v);
         const size_t budget = ((uint64_t)pl.grid_x * c->I <= (uint64_t)c->n_cu ? 160u : 80u) * 1024u;
         // (a skeleton near the LDS limit leaves less than the planned share: take what the CU's 160 KB still hold, down to a quarter
         // burst of 16 entries per wave — the piece loop works with any multiple of 16; nothing at all left = "skeleton too large" below)
         const size_t hard = 160u * 1024u > base ? (160u * 1024u - base) / (waves_per_wg * 16) : 0;
         const size_t avail = budget > base + 4096 ? (budget - base - 1024) / (waves_per_wg * 16) : hard;
-        const uint32_t want = std::min<uint32_t>(2048u, (256u / (uint32_t)v.S) * std::max<uint32_t>(c->M, 1u));
+        const uint32_t want = std::min<uint32_t>(2048u, (256u / (uint32_t)v.S) * std::max<uint32_t>(c->morphs.M, 1u));
         pl.sp_cap = avail >= 64 ? std::max<uint32_t>(64u, std::min<uint32_t>(round_up(want, 256), (uint32_t)(avail / 64 * 64)))         // whole 1 KiB bursts (the kernel issues them in groups of four)
                                 : std::max<uint32_t>(16u, (uint32_t)(avail / 16 * 16));
         // "sparse_piece" (tests, diagnosis): the caller's piece instead of `want`, as it is — no rounding to whole bursts, no share left for a
@@ -305,9 +305,9 @@ Plan make_plan(const rz_ctx *c)
         // Sparse targets ("inst_morphs"): the group's morph weights, G x Mpad floats, sit in LDS behind whatever the form keeps there and
         // count against the same budgets. A form they do not fit beside is not taken (subset form -> whole palettes with the group the
         // budget allows -> the generic kernel: the frame launched without the key), never an error.
-        const uint32_t mpad = is.morphs ? c->Mpad : 0u;
-        bool sub = c->t_subsets != 0 && c->sub_valid && c->sub_per == is.per && c->sub_runs == is.runs && c->sub_B == c->B &&
-                   c->sub_max < c->B && c->sub_max <= (uint32_t)blk;
+        const uint32_t mpad = is.morphs ? c->morphs.Mpad : 0u;
+        bool sub = c->t_subsets != 0 && c->sub_valid && c->sub_per == is.per && c->sub_runs == is.runs && c->sub_B == c->skel.B &&
+                   c->sub_max < c->skel.B && c->sub_max <= (uint32_t)blk;
         if (sub) {
             const size_t lds = rz_skin_instances_lds_bytes(is.G, c->sub_max, !is.want_in_kernel, true, mpad);
             if (lds > lds_budget) sub = false;
@@ -331,8 +331,8 @@ Plan make_plan(const rz_ctx *c)
         if (!sub) {
             const int blk_f = is.blk_full;
             const uint32_t budget_f = (blk_f == 256 ? 80u : 156u) * 1024u;
-            const bool in_kernel = is.want_in_kernel && c->B <= (uint32_t)blk_f;   // the in-place product gives every bone its own thread
-            const uint32_t g_lds = budget_f / (c->B * (in_kernel ? 64u : 48u) + mpad * 4u);
+            const bool in_kernel = is.want_in_kernel && c->skel.B <= (uint32_t)blk_f;   // the in-place product gives every bone its own thread
+            const uint32_t g_lds = budget_f / (c->skel.B * (in_kernel ? 64u : 48u) + mpad * 4u);
             int G = (int)std::min<uint32_t>((uint32_t)is.G, g_lds);
             // (sparse targets: the group that was asked for, or the generic kernel — a morph-free crowd has no other frame to fall back to
             // and takes the smaller group; a crowd with targets has the frame it launched before the key existed)
@@ -342,15 +342,15 @@ Plan make_plan(const rz_ctx *c)
                 inst_runs(c, G, blk_f, false, &per, &runs);
                 pl.inst_group = G; pl.inst_block = blk_f; pl.verts_per_wg = per; pl.grid_x = runs;
                 pl.prep = !in_kernel; pl.dma = !in_kernel;
-                pl.inst_lds = rz_skin_instances_lds_bytes(G, c->B, !in_kernel, false, mpad);
+                pl.inst_lds = rz_skin_instances_lds_bytes(G, c->skel.B, !in_kernel, false, mpad);
                 pl.inst_morphs = is.morphs;
             }
         }
     }
     // register-resident instanced form: 2048-vertex runs, pose ranges sized for ~2 WGs per CU
     // (measured slower than the LDS pose-group form on C4 — 37 vs 34 us — so it is opt-in: inst_loop = 9)
-    if (v.mode == 0 && c->I > 1 && c->t_instloop == 9 && c->B * 3 <= 65535u && !epilogues) {
-        const uint32_t runs = (c->V + 2047) / 2048;
+    if (v.mode == 0 && c->I > 1 && c->t_instloop == 9 && c->skel.B * 3 <= 65535u && !epilogues) {
+        const uint32_t runs = (c->mesh.V + 2047) / 2048;
         uint32_t total = c->t_grid_cap > 0 ? (uint32_t)c->t_grid_cap : 2u * (uint32_t)c->n_cu;
         uint32_t ranges = std::max<uint32_t>(1, std::min<uint32_t>(c->I, total / std::max<uint32_t>(1, runs)));
         pl.poses_per_wg = (int)((c->I + ranges - 1) / ranges);
@@ -371,7 +371,7 @@ extern "C" __attribute__((visibility("default"))) int rz_debug_plan_dense(uint32
 {
     if (V == 0 || M == 0 || n_cu <= 0 || !split || !grid || !quads_per_wave) return RZ_ERR_INVALID;
     rz_ctx c;
-    c.n_cu = n_cu; c.V = V; c.Vp = rzi::round_up(V, rzi::kVertPad); c.B = B; c.M = M; c.I = 1; c.morph_mode = 1;
+    c.n_cu = n_cu; c.mesh.V = V; c.mesh.Vp = rzi::round_up(V, rzi::kVertPad); c.skel.B = B; c.morphs.M = M; c.I = 1; c.morphs.mode = 1;
     c.pl.cur.ml.count = M <= (uint32_t)kKargMorphs ? (int)M : -1;
     const rzi::Plan pl = rzi::make_plan(&c);
     *split = pl.v.S; *grid = (int)pl.grid_x; *quads_per_wave = (int)pl.quads_per_wave;
@@ -387,33 +387,24 @@ int ensure_run_subsets(rz_ctx *c)
 {
     InstShape is;
     if (c->t_subsets == 0 || !inst_shape(c, &is)) return RZ_OK;
-    if (c->sub_valid && c->sub_per == is.per && c->sub_runs == is.runs && c->sub_B == c->B) return RZ_OK;
+    if (c->sub_valid && c->sub_per == is.per && c->sub_runs == is.runs && c->sub_B == c->skel.B) return RZ_OK;
     c->sub_valid = false;
     HIP_TRY(hipStreamSynchronize(c->stream));       // a frame in flight may still read the old lists
     drop_graph(c);
-    if (!c->rj01) HIP_TRY(hipMalloc(&c->rj01, (size_t)c->Vp * 4));
-    if (!c->rj23) HIP_TRY(hipMalloc(&c->rj23, (size_t)c->Vp * 4));
-    const size_t need_list = (size_t)is.runs * c->B;
-    if (need_list > c->sub_list_alloc) {
-        dfree(c->sub_list);
-        HIP_TRY(hipMalloc(&c->sub_list, need_list * sizeof(uint16_t)));
-        c->sub_list_alloc = need_list;
-    }
-    if (is.runs > c->sub_count_alloc) {
-        dfree(c->sub_count);
-        HIP_TRY(hipMalloc(&c->sub_count, (size_t)is.runs * sizeof(uint32_t)));
-        c->sub_count_alloc = is.runs;
-    }
-    const uint32_t v_lim = (c->V + 3) / 4 * 4;      // what the skin kernel walks: whole quads
-    HIP_TRY(hipMemsetAsync(c->rj01, 0, (size_t)c->Vp * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(c->rj23, 0, (size_t)c->Vp * 4, c->stream));
-    HIP_TRY(rz_launch_run_subsets(c->j01, c->j23, v_lim, is.per, is.runs, c->B, c->sub_list, c->sub_count, c->rj01, c->rj23, c->stream));
+    if (!c->rj01) HIP_TRY(c->rj01.alloc(c->mesh.Vp));
+    if (!c->rj23) HIP_TRY(c->rj23.alloc(c->mesh.Vp));
+    if (int r = grow(c, c->sub_list.to((size_t)is.runs * c->skel.B))) return r;
+    if (int r = grow(c, c->sub_count.to(is.runs))) return r;
+    const uint32_t v_lim = (c->mesh.V + 3) / 4 * 4;      // what the skin kernel walks: whole quads
+    HIP_TRY(hipMemsetAsync(c->rj01, 0, (size_t)c->mesh.Vp * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->rj23, 0, (size_t)c->mesh.Vp * 4, c->stream));
+    HIP_TRY(rz_launch_run_subsets(c->mesh.j01, c->mesh.j23, v_lim, is.per, is.runs, c->skel.B, c->sub_list, c->sub_count, c->rj01, c->rj23, c->stream));
     std::vector<uint32_t> counts(is.runs);
     HIP_TRY(hipMemcpyAsync(counts.data(), c->sub_count, (size_t)is.runs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     uint32_t mx = 0;
     for (uint32_t n : counts) mx = std::max(mx, n);
-    c->sub_per = is.per; c->sub_runs = is.runs; c->sub_B = c->B; c->sub_max = mx;
+    c->sub_per = is.per; c->sub_runs = is.runs; c->sub_B = c->skel.B; c->sub_max = mx;
     c->sub_valid = true;
     c->sub_gen++;
     return RZ_OK;
@@ -427,8 +418,8 @@ int ensure_run_subsets(rz_ctx *c)
 // after-physics bones is no stage, yet the crowd kernel's front has no override write).
 bool subfk_wanted(const rz_ctx *c)
 {
-    return c->I > 1 && c->pl.cur.local && c->has_topology && c->t_fusefk != 0 && c->t_subsets != 0 && c->sub_valid && c->sub_max < c->B &&
-           !(c->bm_count && c->M) && c->ovr_count == 0 && c->ik_n == 0 && c->fk_host.size() == (size_t)c->B * 4;
+    return c->I > 1 && c->pl.cur.local && c->fk.has_topology && c->t_fusefk != 0 && c->t_subsets != 0 && c->sub_valid && c->sub_max < c->skel.B &&
+           !(c->bm.count && c->morphs.M) && c->ovr_count == 0 && c->ik.n == 0 && c->fk.host.size() == (size_t)c->skel.B * 4;
 }
 
 // The closure records of the current run lists (see ctx.h). Host work + one readback of the lists, only when the lists or the
@@ -439,7 +430,7 @@ int ensure_subfk(rz_ctx *c)
     if (c->subfk_sub_gen == c->sub_gen && c->subfk_fk_gen == c->fk_gen) return RZ_OK;      // built, or found unfit, for exactly these lists and this hierarchy
     c->subfk_valid = false;
     c->subfk_sub_gen = c->sub_gen; c->subfk_fk_gen = c->fk_gen;         // (also remembers a refusal: no retry per frame)
-    const uint32_t runs = c->sub_runs, B = c->B;
+    const uint32_t runs = c->sub_runs, B = c->skel.B;
     std::vector<uint16_t> lists((size_t)runs * B);
     std::vector<uint32_t> counts(runs);
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -447,7 +438,7 @@ int ensure_subfk(rz_ctx *c)
     HIP_TRY(hipMemcpy(lists.data(), c->sub_list, lists.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(counts.data(), c->sub_count, (size_t)runs * sizeof(uint32_t), hipMemcpyDeviceToHost));
     const bool motion = c->has_animation && c->an_host_range.size() == B;
-    auto parent = [&](uint32_t b) { return (int32_t)c->fk_host[4 * (size_t)b].x; };
+    auto parent = [&](uint32_t b) { return (int32_t)c->fk.host[4 * (size_t)b].x; };
     std::vector<std::vector<uint32_t>> closures(runs);
     std::vector<uint32_t> depth(B, 0);
     uint32_t stride = 0, max_depth = 0;
@@ -485,7 +476,7 @@ int ensure_subfk(rz_ctx *c)
         for (uint32_t k = 0; k < cl.size(); ++k) {
             const uint32_t b = cl[k];
             uint4 *w = &rec[((size_t)r * stride + k) * 5];
-            const uint4 t = c->fk_host[4 * (size_t)b], bind = c->fk_host[4 * (size_t)b + 1];
+            const uint4 t = c->fk.host[4 * (size_t)b], bind = c->fk.host[4 * (size_t)b + 1];
             w[0] = make_uint4(b | (pslot[b] << 16), t.y, t.z, t.w);
             w[1] = bind;
             uint32_t a[3][2] = { { 0xffffffffu, 0xffffu }, { 0xffffffffu, 0xffffu }, { 0xffffffffu, 0xffffu } };
@@ -510,16 +501,8 @@ int ensure_subfk(rz_ctx *c)
             w[4] = make_uint4(0u, 0u, 0u, 0u);
         }
     }
-    if (rec.size() > c->subfk_rec_alloc) {
-        dfree(c->subfk_rec);
-        HIP_TRY(hipMalloc(&c->subfk_rec, rec.size() * sizeof(uint4)));
-        c->subfk_rec_alloc = rec.size();
-    }
-    if (runs > c->subfk_count_alloc) {
-        dfree(c->subfk_count);
-        HIP_TRY(hipMalloc(&c->subfk_count, (size_t)runs * sizeof(uint32_t)));
-        c->subfk_count_alloc = runs;
-    }
+    if (int r = grow(c, c->subfk_rec.to(rec.size()))) return r;
+    if (int r = grow(c, c->subfk_count.to(runs))) return r;
     HIP_TRY(hipMemcpy(c->subfk_rec, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->subfk_count, ccount.data(), (size_t)runs * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->subfk_stride = stride; c->subfk_rounds = rounds;
@@ -546,10 +529,10 @@ RzPrepParams prep_params(const rz_ctx *c)
 {
     RzPrepParams p;
     memset(&p, 0, sizeof p);
-    p.world = c->world; p.inv_bind = c->inv_bind; p.palette = c->palette; p.morph_w = c->morph_w;
+    p.world = c->world; p.inv_bind = c->skel.inv_bind; p.palette = c->palette; p.morph_w = c->morph_w;
     p.act_idx = c->act_idx; p.act_w = c->act_w; p.act_count = c->act_count;
-    p.dense_fold = c->morph_mode == 1 ? c->dense_fold : nullptr;
-    p.B = (int)c->B; p.M = (int)c->M; p.Mpad = (int)c->Mpad;
+    p.dense_fold = c->morphs.mode == 1 ? c->morphs.dense_fold.get() : nullptr;
+    p.B = (int)c->skel.B; p.M = (int)c->morphs.M; p.Mpad = (int)c->morphs.Mpad;
     return p;
 }
 
@@ -569,18 +552,18 @@ RzFkParams fk_params(const rz_ctx *c, bool overrides)
     RzFkParams p;
     memset(&p, 0, sizeof p);            // padding too: frame_signature() hashes the struct
     p.local_q = src_local_q(c);
-    p.local_t = c->pl.cur.local_t ? reinterpret_cast<const float *>(p.local_q + (size_t)c->I * c->B) : nullptr;
-    p.bone_rec = c->fk_rec; p.anc_more = c->fk_anc_more; p.inv_bind = c->inv_bind;
-    p.world = c->world; p.palette = c->palette; p.B = (int)c->B; p.n_rounds = c->fk_rounds;
+    p.local_t = c->pl.cur.local_t ? reinterpret_cast<const float *>(p.local_q + (size_t)c->I * c->skel.B) : nullptr;
+    p.bone_rec = c->fk.rec; p.anc_more = c->fk.anc_more; p.inv_bind = c->skel.inv_bind;
+    p.world = c->world; p.palette = c->palette; p.B = (int)c->skel.B; p.n_rounds = c->fk.rounds;
     if (overrides && c->ovr_count) { p.ovr_off = c->ovr_off; p.ovr_bone = c->ovr_bone; p.ovr_world = c->ovr_world; }
-    if (c->bm_count && c->M) {
-        p.bm_off = c->bm_off; p.bm_morph = c->bm_morph; p.bm_rot = c->bm_rot; p.bm_tr = c->bm_tr;
-        p.bm_w = src_morph_w(c); p.bm_M = (int)c->M;
+    if (c->bm.count && c->morphs.M) {
+        p.bm_off = c->bm.off; p.bm_morph = c->bm.morph; p.bm_rot = c->bm.rot; p.bm_tr = c->bm.tr;
+        p.bm_w = src_morph_w(c); p.bm_M = (int)c->morphs.M;
     }
     if (c->pl.cur.sampled) {
         RzSampleParams &q = p.sample = sample_params(c->an);
-        q.frames = c->pl.cur.frames_inline ? nullptr : c->pl.an_frames.p; q.frames_inline = c->pl.cur.frames_inline ? 1 : 0; q.frame0 = c->pl.cur.frame0;
-        q.morph_w = c->morph_w; q.M = (int)c->M;
+        q.frames = c->pl.cur.frames_inline ? nullptr : c->pl.an_frames.get(); q.frames_inline = c->pl.cur.frames_inline ? 1 : 0; q.frame0 = c->pl.cur.frame0;
+        q.morph_w = c->morph_w; q.M = (int)c->morphs.M;
     }
     return p;
 }
@@ -599,14 +582,14 @@ static RzAfterParams after_params(const rz_ctx *c)
 {
     RzAfterParams p;
     memset(&p, 0, sizeof p);
-    if (c->af_n && c->ovr_count) { p.rec = c->af_rec; p.level_off = c->af_level_off; p.index = c->af_index; p.n = (int)c->af_n; p.n_levels = (int)c->af_levels; }
+    if (c->af.n && c->ovr_count) { p.rec = c->af.rec; p.level_off = c->af.level_off; p.index = c->af.index; p.n = (int)c->af.n; p.n_levels = (int)c->af.levels; }
     return p;
 }
 
 void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::vector<int> &bones, std::vector<int> &fol_off, std::vector<uint2> &ent)
 {
     const size_t I = off.empty() ? 0 : off.size() - 1;
-    const int B = (int)c->B;
+    const int B = (int)c->skel.B;
     fol_off.assign(I + 1, 0);
     ent.clear();
     // near[b]: the override entry bone b takes its matrix from — its own when it is overridden, else its nearest overridden ancestor's
@@ -621,7 +604,7 @@ void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::ve
         for (int b = 0; b < B; ++b) {
             chain.clear();
             int cur = b;
-            while (cur >= 0 && near[cur] == kUnknown) { chain.push_back(cur); cur = (int32_t)c->fk_host[4 * (size_t)cur].x; }
+            while (cur >= 0 && near[cur] == kUnknown) { chain.push_back(cur); cur = (int32_t)c->fk.host[4 * (size_t)cur].x; }
             const int found = cur < 0 ? -1 : near[cur];
             for (int x : chain) near[x] = found;
         }
@@ -631,18 +614,25 @@ void build_followers(const rz_ctx *c, const std::vector<int> &off, const std::ve
     fol_off[I] = (int)ent.size();
 }
 
+// The override table's three arrays grow as a set, and only here (rz_override_world and the physics table's per-instance buffers): a
+// resident physics table relies on all three keeping their addresses across steps. Growing drains, so the captured graph and the
+// resident set (whose contents do not move) go with the old arrays.
+int reserve_overrides(rz_ctx *c, size_t entries, size_t offsets)
+{
+    if (entries <= c->ovr_bone.capacity() && offsets <= c->ovr_off.capacity()) return RZ_OK;
+    const size_t cap = std::max<size_t>(entries, 64);
+    if (int r = grow(c, c->ovr_off.to(offsets), c->ovr_bone.to(cap), c->ovr_world.to(cap * 16))) return r;
+    drop_graph(c);
+    c->ovr_count = 0;
+    return RZ_OK;
+}
+
 int reserve_followers(rz_ctx *c, size_t entries, size_t offsets)
 {
-    if (entries <= c->fol_alloc && offsets <= c->fol_off_alloc) return RZ_OK;
-    if (int r = drain(c)) return r;
+    if (entries <= c->fol_ent.capacity() && offsets <= c->fol_off.capacity()) return RZ_OK;
+    if (int r = grow(c, c->fol_ent.to(std::max<size_t>(entries, 64)), c->fol_off.to(std::max(offsets, c->ovr_off.capacity())))) return r;
     drop_graph(c);
-    dfree(c->fol_off); dfree(c->fol_ent);
-    c->fol_alloc = c->fol_off_alloc = 0;
     c->fol_count = 0;
-    const size_t cap = std::max<size_t>(entries, 64), ocap = std::max(offsets, c->ovr_off_alloc);
-    HIP_TRY(hipMalloc(&c->fol_off, ocap * sizeof(int)));
-    HIP_TRY(hipMalloc(&c->fol_ent, cap * sizeof(uint2)));
-    c->fol_alloc = cap; c->fol_off_alloc = ocap;
     return RZ_OK;
 }
 
@@ -663,9 +653,9 @@ static RzIkParams ik_params(const rz_ctx *c)
 {
     RzIkParams p;
     memset(&p, 0, sizeof p);
-    if (!c->ik_n) return p;
-    p.chain = c->ik_chain; p.path = c->ik_path; p.link = c->ik_link; p.stage_off = c->ik_stage_off;
-    p.n_stages = (int)c->ik_stages; p.n_chains = (int)c->ik_n;
+    if (!c->ik.n) return p;
+    p.chain = c->ik.chain; p.path = c->ik.path; p.link = c->ik.link; p.stage_off = c->ik.stage_off;
+    p.n_stages = (int)c->ik.stages; p.n_chains = (int)c->ik.n;
     return p;
 }
 
@@ -675,8 +665,8 @@ static RzIkSwitchParams ik_switch_params(const rz_ctx *c)
     RzIkSwitchParams p;
     memset(&p, 0, sizeof p);
     const rz_ctx::IkSwitch &s = c->iksw;
-    if (!c->ik_n || !s.off || s.words.empty()) return p;
-    p.words = (int)((c->ik_n + 31) / 32);
+    if (!c->ik.n || !s.off || s.words.empty()) return p;
+    p.words = (int)((c->ik.n + 31) / 32);
     if (c->I == 1 && p.words <= kRzIkSwInline) memcpy(p.w0, s.words.data(), (size_t)p.words * sizeof(uint32_t));
     else p.mask = s.dev;
     return p;
@@ -699,10 +689,10 @@ uint64_t algorithmic_bytes(const rz_ctx *c)
 {
     // 36 B read + 24 B written per vertex, 12*M B of dense morph targets per vertex (9*M B in 24-bit storage),
     // world + inverse-bind matrices, morph weights. The static mesh is counted once for instances.
-    const uint64_t V = c->V, I = c->I, B = c->B, M = c->M;
+    const uint64_t V = c->mesh.V, I = c->I, B = c->skel.B, M = c->morphs.M;
     uint64_t bytes = V * 36 + I * (V * 24 + B * 64) + B * 64;
-    if (c->morph_mode == 1) bytes += I * (V * (c->morph_storage == 24 ? 9 : 12) * M + M * 4);
-    if (c->morph_mode == 2) bytes += V * 4 + I * (c->sp_count * 16 + M * 4);
+    if (c->morphs.mode == 1) bytes += I * (V * (c->morphs.storage == 24 ? 9 : 12) * M + M * 4);
+    if (c->morphs.mode == 2) bytes += V * 4 + I * (c->morphs.sp_count * 16 + M * 4);
     return bytes;
 }
 

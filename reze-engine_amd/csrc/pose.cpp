@@ -77,17 +77,6 @@ static int ring_take(rz_ctx *c, rzring::ReuseProof<N> &proof, const Events<2> &e
     return RZ_OK;
 }
 
-// A device array of the transport outgrown: build the replacement, drain, assign.
-template <class T> static int grow(rz_ctx *c, Scratch<T> &a, size_t &have, size_t want)
-{
-    Scratch<T> fresh;
-    HIP_TRY(fresh.alloc(want));
-    if (int r = drain(c)) return r;
-    a = std::move(fresh);
-    have = want;
-    return RZ_OK;
-}
-
 }  // namespace rzi
 
 extern "C" {
@@ -132,7 +121,7 @@ static int staged_sent(rz_ctx *c, int slot, hipStream_t us, bool piped)
 namespace rzi {
 
 // ---- chain switches of the IK stage (rz_set_ik_enabled / rz_upload_ik_keys; tests/ik_switch_ref.py is the definition) ----
-static uint32_t ik_sw_words(const rz_ctx *c) { return (c->ik_n + 31) / 32; }
+static uint32_t ik_sw_words(const rz_ctx *c) { return (c->ik.n + 31) / 32; }
 
 // A change of the mask in two halves, so that a pose call can do everything that may fail BEFORE it touches the resident pose:
 // plan_ik_words allocates, waits and fills the pinned slot; commit_ik_words enqueues the copy and takes the words into the mirror.
@@ -141,7 +130,7 @@ int plan_ik_words(rz_ctx *c, uint32_t I, std::vector<uint32_t> &&w, IkWordsPlan 
     rz_ctx::IkSwitch &s = c->iksw;
     uint64_t on = 0;
     for (uint32_t x : w) on += (uint64_t)__builtin_popcount(x);
-    pl->off = w.empty() ? 0u : (uint32_t)((uint64_t)I * c->ik_n - on);
+    pl->off = w.empty() ? 0u : (uint32_t)((uint64_t)I * c->ik.n - on);
     if (pl->off == 0) w.clear();
     pl->w = std::move(w);
     pl->slot = -1;
@@ -149,8 +138,8 @@ int plan_ik_words(rz_ctx *c, uint32_t I, std::vector<uint32_t> &&w, IkWordsPlan 
     pl->change = pl->w != s.words || pl->inline_words != (c->I == 1 && ik_sw_words(c) <= (uint32_t)kRzIkSwInline);
     if (!pl->change || pl->w.empty() || pl->inline_words) return RZ_OK;
     // a crowd's bits: one pinned slot, one copy on the stream the hierarchy solve runs on, in order with the frames
-    if (pl->w.size() > s.dev_alloc) {
-        if (int r = grow(c, s.dev, s.dev_alloc, std::max<size_t>(pl->w.size(), 64))) return r;
+    if (pl->w.size() > s.dev.capacity()) {
+        if (int r = grow(c, s.dev.to(std::max<size_t>(pl->w.size(), 64)))) return r;
         // (the array moved, drained: until the commit the mirror's words are what a frame must find in it)
         if (s.off && !(c->I == 1 && ik_sw_words(c) <= (uint32_t)kRzIkSwInline))
             HIP_TRY(hipMemcpy(s.dev, s.words.data(), s.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -189,7 +178,7 @@ int plan_ik_resize(rz_ctx *c, uint32_t I, IkWordsPlan *pl)
 {
     pl->change = false;
     if (c->iksw.words.empty() || I == c->I) return RZ_OK;
-    const uint32_t W = ik_sw_words(c), n = c->ik_n;
+    const uint32_t W = ik_sw_words(c), n = c->ik.n;
     std::vector<uint32_t> w((size_t)I * W);
     for (uint32_t i = 0; i < I; ++i)
         for (uint32_t k = 0; k < W; ++k)
@@ -209,7 +198,7 @@ static const uint32_t *ik_state_at(const RzIkKeySet &ks, uint32_t W, float frame
 
 static void ik_row_into(const rz_ctx *c, const uint32_t *row, uint32_t *dst)
 {
-    const uint32_t W = ik_sw_words(c), n = c->ik_n;
+    const uint32_t W = ik_sw_words(c), n = c->ik.n;
     for (uint32_t k = 0; k < W; ++k) dst[k] = row ? row[k] : (k + 1 < W || (n & 31u) == 0 ? 0xffffffffu : (1u << (n & 31u)) - 1u);
 }
 
@@ -288,7 +277,7 @@ static void lay_out_pose(const rz_ctx *c, const PoseParts &pp, char *st)
     char *st_pr = pp.local ? st + pp.mwb : st;
     memcpy(st_pr, pp.primary, pp.pbytes);
     if (pp.sbytes) memcpy(st_pr + pp.pbytes, pp.secondary, pp.sbytes);
-    if (pp.local || c->M > 0) lay_out_weights(pp, pp.local ? st : st + pp.pbytes);
+    if (pp.local || c->morphs.M > 0) lay_out_weights(pp, pp.local ? st : st + pp.pbytes);
 }
 
 // One character: no copy at all. The pose is laid out in a pinned, device-mapped slot; the frame's own kernels read it.
@@ -299,7 +288,7 @@ static void lay_out_pose(const rz_ctx *c, const PoseParts &pp, char *st)
 // caller of rz_map_pose); zc_publish writes the number and makes the slot the current pose.
 static int zc_open(rz_ctx *c, const PoseParts &pp, int *zs)
 {
-    const size_t need = std::max<size_t>(std::max<size_t>((size_t)c->B * 64 + pp.mwb, pp.mwb + (size_t)c->B * 28), 4096);
+    const size_t need = std::max<size_t>(std::max<size_t>((size_t)c->skel.B * 64 + pp.mwb, pp.mwb + (size_t)c->skel.B * 28), 4096);
     if (need > c->pl.zc.bytes) {        // the ring is (re)built when the pose outgrew it
         RzPoseLink::ZeroCopy fresh;
         fresh.bytes = need; fresh.hdr_off = (need + 63) / 64 * 64;
@@ -358,7 +347,7 @@ static int take_pose_block(rz_ctx *c, bool piped)
         return RZ_OK;
     }
     const RzPoseLink &pl = c->pl;
-    const size_t Mq = std::max<uint32_t>(c->M, 1);
+    const size_t Mq = std::max<uint32_t>(c->morphs.M, 1);
     const size_t need = pl.alloc_I * pl.alloc_B * 16 + ((pl.alloc_I * std::max<size_t>(pl.alloc_M, Mq) + 3) / 4 * 4) + pl.alloc_I * pl.alloc_B * 7 + 4;
     if (!pl.big.blk[0] || pl.big.floats < need) {
         RzPoseLink::Big fresh;
@@ -384,7 +373,7 @@ static int take_pose_block(rz_ctx *c, bool piped)
 // caller does): copy_begin takes the slot, the slot is filled, copy_send enqueues everything.
 static int copy_begin(rz_ctx *c, const PoseParts &pp, int *slot)
 {
-    return stage_acquire(c, std::max<size_t>((size_t)c->I * c->B * 64 + pp.mwb, pp.mwb + (size_t)c->I * c->B * 28), slot);
+    return stage_acquire(c, std::max<size_t>((size_t)c->I * c->skel.B * 64 + pp.mwb, pp.mwb + (size_t)c->I * c->skel.B * 28), slot);
 }
 
 // Large poses (instanced crowds: MBs) take the upload stream and a block of the big-pose ring (ctx.h): nothing enqueued so far
@@ -419,7 +408,7 @@ static int copy_send(rz_ctx *c, const PoseParts &pp, int slot, bool pull, bool r
     hipStream_t us = pose_stream(c, piped);
     if (int r = take_pose_block(c, piped)) return r;
     void *dst = pp.local ? static_cast<void *>(c->morph_w) : static_cast<void *>(c->world);
-    const size_t bones = (size_t)c->I * c->B;
+    const size_t bones = (size_t)c->I * c->skel.B;
     if (pull) HIP_TRY(rz_launch_pull_pose(c->pl.stage.slot[slot].dev, dst, rows ? (uint32_t)bones : 0u, rows ? pp.total - pp.pbytes : pp.total, us));
     else HIP_TRY(hipMemcpyAsync(dst, c->pl.stage.slot[slot].host, pp.total, hipMemcpyHostToDevice, us));
     c->pl.last_pulled = pull; c->pl.last_rows = rows;
@@ -432,11 +421,11 @@ static int upload_pose_copy(rz_ctx *c, const PoseParts &pp)
     if (int r = copy_begin(c, pp, &slot)) return r;
     char *st = static_cast<char *>(c->pl.stage.slot[slot].host);
     const bool pull = pose_pullable(c, pp, slot) && (c->t_pull == 1 || (c->t_pull < 0 && !pp.local));
-    const size_t bones = (size_t)c->I * c->B;
+    const size_t bones = (size_t)c->I * c->skel.B;
     bool rows = false;
     if (pull && !pp.local && can_pack_rows()) {
         rows = pack_rows_avx512(static_cast<const float *>(pp.primary), bones, reinterpret_cast<float *>(st));
-        if (rows && c->M > 0) lay_out_weights(pp, st + bones * 48);
+        if (rows && c->morphs.M > 0) lay_out_weights(pp, st + bones * 48);
     }
     if (!rows) lay_out_pose(c, pp, st);     // (a matrix that is not affine: the whole pose as it was handed over)
     return copy_send(c, pp, slot, pull, rows);
@@ -459,9 +448,9 @@ static PoseParts pose_parts(const rz_ctx *c, const void *primary, size_t pbytes,
 {
     PoseParts pp;
     pp.primary = primary; pp.pbytes = pbytes; pp.secondary = secondary; pp.sbytes = sbytes; pp.morph_weights = morph_weights; pp.local = local;
-    pp.mb = (size_t)c->I * c->M * sizeof(float);
-    pp.mwb = ((size_t)c->I * std::max<uint32_t>(c->M, 1) + 3) / 4 * 4 * sizeof(float);
-    pp.total = local ? pp.mwb + pbytes + sbytes : pbytes + (c->M > 0 ? pp.mwb : 0);
+    pp.mb = (size_t)c->I * c->morphs.M * sizeof(float);
+    pp.mwb = ((size_t)c->I * std::max<uint32_t>(c->morphs.M, 1) + 3) / 4 * 4 * sizeof(float);
+    pp.total = local ? pp.mwb + pbytes + sbytes : pbytes + (c->morphs.M > 0 ? pp.mwb : 0);
     return pp;
 }
 
@@ -473,18 +462,18 @@ static void pose_in_place(rz_ctx *c, const float *morph_weights, bool on_device 
 {
     RzMorphList &ml = c->pl.cur.ml;
     memset(&ml, 0, sizeof ml);
-    if (c->M > 0 && morph_weights && c->I == 1) {
+    if (c->morphs.M > 0 && morph_weights && c->I == 1) {
         int n = 0;
-        for (uint32_t m = 0; m < c->M; ++m) {
+        for (uint32_t m = 0; m < c->morphs.M; ++m) {
             const float w = morph_weights[m];
             if (w == 0.0f) continue;
             // (24-bit dense planes: the listed weight carries the morph's scale — exact, a power of two; kernels/common.hip.h)
-            if (n < kKargMorphs) { ml.idx[n] = m; ml.w[n] = c->dense_fold_host.empty() ? w : w * c->dense_fold_host[m]; }
+            if (n < kKargMorphs) { ml.idx[n] = m; ml.w[n] = c->morphs.dense_fold_host.empty() ? w : w * c->morphs.dense_fold_host[m]; }
             ++n;
         }
         ml.count = n <= kKargMorphs ? n : -1;
     }
-    if (on_device && c->M > 0) ml.count = -1;
+    if (on_device && c->morphs.M > 0) ml.count = -1;
     c->pl.cur.I = c->I;
     c->pl.cur.set = true;
 }
@@ -525,10 +514,10 @@ __attribute__((visibility("default"))) int rz_debug_pack_rows(const float *world
 int rz_set_pose(rz_ctx *c, const float *world, const float *morph_weights)
 {
     if (int r = use(c)) return r;
-    if (c->B == 0) return fail(RZ_ERR_INVALID, "no skeleton uploaded");
+    if (c->skel.B == 0) return fail(RZ_ERR_INVALID, "no skeleton uploaded");
     if (!world) return fail(RZ_ERR_INVALID, "null world matrices");
     if (int r = ensure_pose_buffers(c)) return r;
-    return upload_pose(c, world, (size_t)c->I * c->B * 16 * sizeof(float), nullptr, 0, false, morph_weights);
+    return upload_pose(c, world, (size_t)c->I * c->skel.B * 16 * sizeof(float), nullptr, 0, false, morph_weights);
 }
 
 // ---- caller-written poses (ABI 7) ----
@@ -545,11 +534,11 @@ int rz_map_pose(rz_ctx *c, int layout, float **matrices, float **morph_weights)
     if (morph_weights) *morph_weights = nullptr;
     if (!matrices) return fail(RZ_ERR_INVALID, "rz_map_pose: null out pointer");
     if (layout != RZ_POSE_WORLD16 && layout != RZ_POSE_ROWS12) return fail(RZ_ERR_INVALID, "rz_map_pose: layout must be RZ_POSE_WORLD16 or RZ_POSE_ROWS12");
-    if (c->B == 0) return fail(RZ_ERR_INVALID, "no skeleton uploaded");
+    if (c->skel.B == 0) return fail(RZ_ERR_INVALID, "no skeleton uploaded");
     if (int r = ensure_pose_buffers(c)) return r;
     RzPoseLink::Map &map = c->pl.map;
     map.layout = -1;
-    const size_t bones = (size_t)c->I * c->B;
+    const size_t bones = (size_t)c->I * c->skel.B;
     // (the opt-in overlapped-front protocol moves every per-frame input onto the upload stream and decides that per pose KIND at upload
     // time: such a context hands its poses over with rz_set_pose)
     if (c->t_overlap == 1 || c->overlap_on) return fail(RZ_ERR_UNSUPPORTED, "rz_map_pose: not with the overlapped-front protocol (\"overlap\" = 1); hand the pose over with rz_set_pose");
@@ -578,12 +567,12 @@ int rz_map_pose(rz_ctx *c, int layout, float **matrices, float **morph_weights)
         st = static_cast<char *>(c->pl.stage.slot[slot].host);
     }
     const size_t mat_bytes = bones * (layout == RZ_POSE_ROWS12 ? 48 : 64);
-    if (c->M > 0) {
+    if (c->morphs.M > 0) {
         lay_out_weights(pp, st + mat_bytes);        // weights the caller does not write are zero
         if (morph_weights) *morph_weights = reinterpret_cast<float *>(st + mat_bytes);
     }
     *matrices = reinterpret_cast<float *>(st);
-    map.layout = layout; map.I = c->I; map.B = c->B; map.M = c->M; map.ptr = st;
+    map.layout = layout; map.I = c->I; map.B = c->skel.B; map.M = c->morphs.M; map.ptr = st;
     return RZ_OK;
 }
 
@@ -594,10 +583,10 @@ int rz_commit_pose(rz_ctx *c)
     if (map.layout < 0) return fail(RZ_ERR_INVALID, "rz_commit_pose without rz_map_pose (a pose call in between cancels a mapping)");
     const bool rows = map.layout == RZ_POSE_ROWS12;
     map.layout = -1;
-    if (map.I != c->I || map.B != c->B || map.M != c->M) return fail(RZ_ERR_INVALID, "rz_commit_pose: the crowd, skeleton or morph set changed since rz_map_pose");
-    const size_t bones = (size_t)c->I * c->B;
+    if (map.I != c->I || map.B != c->skel.B || map.M != c->morphs.M) return fail(RZ_ERR_INVALID, "rz_commit_pose: the crowd, skeleton or morph set changed since rz_map_pose");
+    const size_t bones = (size_t)c->I * c->skel.B;
     char *st = map.ptr;
-    const float *mw = c->M > 0 ? reinterpret_cast<const float *>(st + bones * (rows ? 48 : 64)) : nullptr;
+    const float *mw = c->morphs.M > 0 ? reinterpret_cast<const float *>(st + bones * (rows ? 48 : 64)) : nullptr;
     const PoseParts pp = pose_parts(c, nullptr, bones * 64, nullptr, 0, false, nullptr);
     // the same decisions as at map time, on the state as it is NOW (a context under the overlapped-front protocol was refused at map time
     // and a world-matrix pose never switches it on by itself) — all of them BEFORE anything is changed: a refused commit leaves the
@@ -623,10 +612,10 @@ int rz_commit_pose(rz_ctx *c)
 int rz_set_pose_local(rz_ctx *c, const float *local_rotations4, const float *local_translations3, const float *morph_weights)
 {
     if (int r = use(c)) return r;
-    if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
+    if (!c->fk.has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
     if (!local_rotations4) return fail(RZ_ERR_INVALID, "null local rotations");
     if (int r = ensure_pose_buffers(c)) return r;
-    const size_t nq = (size_t)c->I * c->B;
+    const size_t nq = (size_t)c->I * c->skel.B;
     return upload_pose(c, local_rotations4, nq * sizeof(float4), local_translations3, local_translations3 ? nq * 3 * sizeof(float) : 0, true,
                        morph_weights);
 }
@@ -635,15 +624,15 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
 {
     if (int r = use(c)) return r;
     if (!c->has_animation) return fail(RZ_ERR_INVALID, "rz_upload_animation has not been called");
-    if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
-    if (c->an.M != c->M) return fail(RZ_ERR_INVALID, "the motion's morph feeds were built for %u vertex morphs, the context holds %u", c->an.M, c->M);
+    if (!c->fk.has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
+    if (c->an.M != c->morphs.M) return fail(RZ_ERR_INVALID, "the motion's morph feeds were built for %u vertex morphs, the context holds %u", c->an.M, c->morphs.M);
     if (!frames) return fail(RZ_ERR_INVALID, "null frames");
     // refused before anything of the resident pose is touched (the wording of rz_set_pose_blended): the span guess turns the frame into a
     // key index, which is undefined for a NaN or an infinite frame
     for (uint32_t i = 0; i < c->I; ++i)
         if (!rzmotion::finite(frames[i])) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
     IkWordsPlan sw;
-    if (c->ik_n && c->ik_keys_an.resident) {        // the motion's IK on/off keys: every instance's switches at its frame
+    if (c->ik.n && c->ik_keys_an.resident) {        // the motion's IK on/off keys: every instance's switches at its frame
         const uint32_t W = ik_sw_words(c);
         std::vector<uint32_t> w((size_t)c->I * W);
         for (uint32_t i = 0; i < c->I; ++i) ik_row_into(c, ik_state_at(c->ik_keys_an, W, frames[i]), &w[(size_t)i * W]);
@@ -651,8 +640,7 @@ int rz_set_pose_sampled(rz_ctx *c, const float *frames)
     }
     if (int r = ensure_pose_buffers(c)) return r;
     RzPoseLink &pl = c->pl;
-    if (c->I > pl.an_frames_alloc)
-        if (int r = grow(c, pl.an_frames, pl.an_frames_alloc, c->I)) return r;
+    if (int r = grow(c, pl.an_frames.to(c->I))) return r;
     if (int r = pose_begins(c, true, true, true)) return r;
     pose_leaves_pinned_slots(c);            // the pose is produced on the device: its frame writes world matrices / weights into the pose block
     pl.cur.frames_inline = rides_in_arguments(c, false);
@@ -684,8 +672,8 @@ static int check_motion_states(const rz_ctx *c, const RzMotionState *sv)
         const RzMotionState &s = sv[i];
         if (!rzmotion::finite(s.blend) || s.blend < 0.0f || s.blend > 1.0f) return fail(RZ_ERR_INVALID, "instance %u: blend %g is not in [0, 1]", i, (double)s.blend);
         const bool has_b = s.clip_b != kRzNoClip && s.blend != 0.0f, use_a = !(has_b && s.blend == 1.0f);
-        if (s.clip_a >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u: clip_a %u of %u", i, s.clip_a, c->mo_clips);
-        if (s.clip_b != kRzNoClip && s.clip_b >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u: clip_b %u of %u", i, s.clip_b, c->mo_clips);
+        if (s.clip_a >= c->lib.clips) return fail(RZ_ERR_INVALID, "instance %u: clip_a %u of %u", i, s.clip_a, c->lib.clips);
+        if (s.clip_b != kRzNoClip && s.clip_b >= c->lib.clips) return fail(RZ_ERR_INVALID, "instance %u: clip_b %u of %u", i, s.clip_b, c->lib.clips);
         if ((use_a && !rzmotion::finite(s.frame_a)) || (has_b && !rzmotion::finite(s.frame_b))) return fail(RZ_ERR_INVALID, "instance %u: a frame that would be sampled is not finite", i);
     }
     return RZ_OK;
@@ -702,13 +690,13 @@ static int check_motion_layers(const rz_ctx *c, uint32_t n_layers, const RzMotio
             const RzMotionLayer &y = lv[(size_t)i * n_layers + l];
             if (y.clip == kRzNoClip || y.weight == 0.0f) continue;
             if (!rzmotion::finite(y.weight) || y.weight < 0.0f || y.weight > 1.0f) return fail(RZ_ERR_INVALID, "instance %u layer %u: weight %g is not in [0, 1]", i, l, (double)y.weight);
-            if (y.clip >= c->mo_clips) return fail(RZ_ERR_INVALID, "instance %u layer %u: clip %u of %u", i, l, y.clip, c->mo_clips);
+            if (y.clip >= c->lib.clips) return fail(RZ_ERR_INVALID, "instance %u layer %u: clip %u of %u", i, l, y.clip, c->lib.clips);
             if (y.mode > 1u) return fail(RZ_ERR_INVALID, "instance %u layer %u: mode %u is neither RZ_LAYER_OVERRIDE nor RZ_LAYER_ADDITIVE", i, l, y.mode);
             if (!rzmotion::finite(y.frame)) return fail(RZ_ERR_INVALID, "instance %u layer %u: the frame is not finite", i, l);
             if (y.mask != kRzNoMask) {
-                if (y.mask >= c->mk_count) return fail(RZ_ERR_INVALID, "instance %u layer %u: mask %u of %u", i, l, y.mask, c->mk_count);
-                if (c->mk_M != c->M)
-                    return fail(RZ_ERR_INVALID, "instance %u layer %u: the masks were built for %u vertex morphs, the context holds %u: upload them again", i, l, c->mk_M, c->M);
+                if (y.mask >= c->mk.count) return fail(RZ_ERR_INVALID, "instance %u layer %u: mask %u of %u", i, l, y.mask, c->mk.count);
+                if (c->mk.M != c->morphs.M)
+                    return fail(RZ_ERR_INVALID, "instance %u layer %u: the masks were built for %u vertex morphs, the context holds %u: upload them again", i, l, c->mk.M, c->morphs.M);
             }
         }
     return RZ_OK;
@@ -720,9 +708,9 @@ static int check_motion_layers(const rz_ctx *c, uint32_t n_layers, const RzMotio
 static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, uint32_t n_layers, const rz_motion_layer *layers)
 {
     if (int r = use(c)) return r;
-    if (!c->mo_clips) return fail(RZ_ERR_INVALID, "rz_upload_motions has not been called");
-    if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
-    if (c->mo.M != c->M) return fail(RZ_ERR_INVALID, "the library's morph feeds were built for %u vertex morphs, the context holds %u: upload it again", c->mo.M, c->M);
+    if (!c->lib.clips) return fail(RZ_ERR_INVALID, "rz_upload_motions has not been called");
+    if (!c->fk.has_topology) return fail(RZ_ERR_INVALID, "rz_upload_skeleton_topology has not been called for this skeleton");
+    if (c->mo.M != c->morphs.M) return fail(RZ_ERR_INVALID, "the library's morph feeds were built for %u vertex morphs, the context holds %u: upload it again", c->mo.M, c->morphs.M);
     if (!states) return fail(RZ_ERR_INVALID, "null motion states");
     if (n_layers > (uint32_t)kRzMaxLayers) return fail(RZ_ERR_INVALID, "%u layers: at most %d", n_layers, kRzMaxLayers);
     if (n_layers && !layers) return fail(RZ_ERR_INVALID, "null motion layers");
@@ -753,7 +741,7 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
         return bad;
     }
     IkWordsPlan sw;
-    if (c->ik_n && !c->ik_keys_mo.empty()) {
+    if (c->ik.n && !c->ik_keys_mo.empty()) {
         // the library's IK on/off keys: clip A's row at frame_a, or from blend 0.5 on clip B's at frame_b (a switch does not cross-fade;
         // layers never switch IK); a chosen clip without keys is all on. Planned here, before the resident pose is touched.
         const uint32_t W = ik_sw_words(c);
@@ -770,16 +758,16 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
     RzPoseLink &pl = c->pl;
     pl.map.layout = -1;                 // a pose handed over whole cancels a mapping that was never committed
     if (int r = pose_begins(c, true, true)) return r;
-    const size_t nq = (size_t)c->I * c->B;
+    const size_t nq = (size_t)c->I * c->skel.B;
     const PoseParts pp = pose_parts(c, nullptr, nq * sizeof(float4), nullptr, nq * 3 * sizeof(float), true, nullptr);
     const bool piped = pose_piped(c, pp);
     hipStream_t us = pose_stream(c, piped);
     const bool inline_state = rides_in_arguments(c, piped);
     if (!inline_state) {
-        if (!layered && c->I > pl.mo_states_alloc)
-            if (int r = grow(c, pl.mo_states, pl.mo_states_alloc, c->I)) return r;
-        if (layered && n_rec > pl.mo_layers_alloc)
-            if (int r = grow(c, pl.mo_layers, pl.mo_layers_alloc, (size_t)c->I * (1 + kRzMaxLayers))) return r;
+        if (!layered)
+            if (int r = grow(c, pl.mo_states.to(c->I))) return r;
+        if (layered && n_rec > pl.mo_layers.capacity())
+            if (int r = grow(c, pl.mo_layers.to((size_t)c->I * (1 + kRzMaxLayers)))) return r;
         if (pl.mo_states_stream && pl.mo_states_stream != us) HIP_TRY(hipStreamSynchronize(pl.mo_states_stream));     // (the protocol changed: rare)
         pl.mo_states_stream = us;
         if (slot < 0) {
@@ -796,20 +784,20 @@ static int library_pose(rz_ctx *c, const rz_motion_state *states, bool layered, 
         memcpy(lp.layers0, one.ly, sizeof one.ly);
     } else if (layered) {
         HIP_TRY(hipMemcpyAsync(pl.mo_layers, pl.stage.slot[slot].host, n_bytes, hipMemcpyHostToDevice, us));
-        mp.states = reinterpret_cast<const RzMotionState *>(pl.mo_layers.p);
+        mp.states = reinterpret_cast<const RzMotionState *>(pl.mo_layers.get());
         lp.layers = pl.mo_layers + c->I;
     } else {
         HIP_TRY(hipMemcpyAsync(pl.mo_states, pl.stage.slot[slot].host, (size_t)c->I * sizeof(RzMotionState), hipMemcpyHostToDevice, us));
         mp.states = pl.mo_states;
     }
-    mp.bone_rec = c->mo_bone_rec; mp.feed_off = c->mo.feed_off;
+    mp.bone_rec = c->lib.bone_rec; mp.feed_off = c->mo.feed_off;
     mp.sample = sample_params(c->mo);
     mp.local_q = c->local_q; mp.local_t = reinterpret_cast<float *>(c->local_q + nq); mp.morph_w = c->morph_w;
-    mp.B = (int)c->B; mp.M = (int)c->M;
+    mp.B = (int)c->skel.B; mp.M = (int)c->morphs.M;
     if (layered) {
         lp.n_layers = (int)n_layers;
-        lp.bone_bits = c->mk_bone_bits; lp.bone_words = (int)c->mk_bone_words;
-        lp.morph_bits = c->mk_M == c->M ? c->mk_morph_bits : nullptr; lp.morph_words = (int)c->mk_morph_words;      // (masks of another morph set: no layer names one)
+        lp.bone_bits = c->mk.bone_bits; lp.bone_words = (int)c->mk.bone_words;
+        lp.morph_bits = c->mk.M == c->morphs.M ? c->mk.morph_bits.get() : nullptr; lp.morph_words = (int)c->mk.morph_words;      // (masks of another morph set: no layer names one)
     }
     HIP_TRY(layered ? rz_launch_motion(lp, c->I, us) : rz_launch_motion(mp, c->I, us));
     pl.last_pulled = false; pl.last_rows = false;
@@ -835,19 +823,19 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
     if (int r = use(c)) return r;
     if (c->ph.nb) return fail(RZ_ERR_INVALID, "rz_override_world while a physics table is resident: rz_physics_step writes the override table (remove the table with rz_upload_physics(ctx, NULL) first)");
     if (n == 0) { c->ovr_count = 0; c->ovr_off_host.clear(); c->ovr_bone_host.clear(); return RZ_OK; }
-    if (!c->has_topology) return fail(RZ_ERR_INVALID, "rz_override_world applies to device-solved poses: call rz_upload_skeleton_topology first");
+    if (!c->fk.has_topology) return fail(RZ_ERR_INVALID, "rz_override_world applies to device-solved poses: call rz_upload_skeleton_topology first");
     if (!bone || !world16) return fail(RZ_ERR_INVALID, "null override arrays");
     // sort by (instance, bone); of several entries for one bone the LAST wins, like successive boneWorldMatrices.set() calls
     std::vector<uint32_t> order(n);
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t i = instance ? instance[k] : 0;
-        if (i >= c->I || bone[k] >= c->B) return fail(RZ_ERR_INVALID, "override %u names instance %u bone %u (have %u x %u)", k, i, bone[k], c->I, c->B);
+        if (i >= c->I || bone[k] >= c->skel.B) return fail(RZ_ERR_INVALID, "override %u names instance %u bone %u (have %u x %u)", k, i, bone[k], c->I, c->skel.B);
         for (int e = 0; e < 16; ++e) {
             if (!rzmotion::finite(world16[(size_t)k * 16 + e])) return fail(RZ_ERR_INVALID, "override %u is not finite", k);
         }
         order[k] = k;
     }
-    auto key = [&](uint32_t k) { return (uint64_t)(instance ? instance[k] : 0) * c->B + bone[k]; };
+    auto key = [&](uint32_t k) { return (uint64_t)(instance ? instance[k] : 0) * c->skel.B + bone[k]; };
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
     std::vector<int> off(c->I + 1, 0), bones;
     std::vector<float> mats;
@@ -860,16 +848,7 @@ int rz_override_world(rz_ctx *c, uint32_t n, const uint32_t *instance, const uin
     }
     for (uint32_t i = 0; i < c->I; ++i) off[i + 1] += off[i];
     const size_t m = bones.size();
-    if (m > c->ovr_alloc || off.size() > c->ovr_off_alloc) {
-        if (int r = drain(c)) return r;
-        drop_graph(c);
-        dfree(c->ovr_off); dfree(c->ovr_bone); dfree(c->ovr_world);
-        c->ovr_alloc = std::max<size_t>(m, 64); c->ovr_off_alloc = off.size();
-        c->ovr_count = 0;
-        HIP_TRY(hipMalloc(&c->ovr_off, c->ovr_off_alloc * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->ovr_bone, c->ovr_alloc * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->ovr_world, c->ovr_alloc * 16 * sizeof(float)));
-    }
+    if (int r = reserve_overrides(c, m, off.size())) return r;
     // rz_override_follow: per-instance sets differ, so the follower lists are rebuilt with every set and travel with it
     std::vector<int> fol_off;
     std::vector<uint2> fol_ent;
@@ -911,7 +890,7 @@ int rz_override_follow(rz_ctx *c, uint32_t on)
 {
     if (int r = use(c)) return r;
     if (on > 1) return fail(RZ_ERR_INVALID, "rz_override_follow: on must be 0 or 1 (got %u)", on);
-    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+    if (!c->fk.has_topology || c->fk.host.size() != (size_t)c->skel.B * 4)
         return fail(RZ_ERR_INVALID, "rz_override_follow needs the hierarchy: call rz_upload_skeleton_topology first");
     if ((int)on == c->ovr_follow) return RZ_OK;
     if (int r = drain(c)) return r;
@@ -939,14 +918,14 @@ int rz_override_follow(rz_ctx *c, uint32_t on)
 int rz_set_ik_enabled(rz_ctx *c, const uint8_t *enabled)
 {
     if (int r = use(c)) return r;
-    if (!c->ik_n) return fail(RZ_ERR_INVALID, "rz_set_ik_enabled: no IK table is resident (rz_upload_ik)");
+    if (!c->ik.n) return fail(RZ_ERR_INVALID, "rz_set_ik_enabled: no IK table is resident (rz_upload_ik)");
     std::vector<uint32_t> w;
     if (enabled) {
-        const uint32_t W = ik_sw_words(c), n = c->ik_n;
+        const uint32_t W = ik_sw_words(c), n = c->ik.n;
         w.assign((size_t)c->I * W, 0u);
         for (uint32_t i = 0; i < c->I; ++i)
             for (uint32_t k = 0; k < n; ++k)
-                if (enabled[(size_t)i * n + k]) { const uint32_t d = c->ik_dev_pos[k]; w[(size_t)i * W + (d >> 5)] |= 1u << (d & 31u); }
+                if (enabled[(size_t)i * n + k]) { const uint32_t d = c->ik.dev_pos[k]; w[(size_t)i * W + (d >> 5)] |= 1u << (d & 31u); }
     }
     return set_ik_words(c, std::move(w));
 }
@@ -954,12 +933,12 @@ int rz_set_ik_enabled(rz_ctx *c, const uint8_t *enabled)
 int rz_read_ik_enabled(rz_ctx *c, uint8_t *out)
 {
     if (int r = use(c)) return r;
-    if (!c->ik_n) return fail(RZ_ERR_INVALID, "rz_read_ik_enabled: no IK table is resident (rz_upload_ik)");
+    if (!c->ik.n) return fail(RZ_ERR_INVALID, "rz_read_ik_enabled: no IK table is resident (rz_upload_ik)");
     if (!out) return fail(RZ_ERR_INVALID, "rz_read_ik_enabled: null out");
-    const uint32_t W = ik_sw_words(c), n = c->ik_n;
+    const uint32_t W = ik_sw_words(c), n = c->ik.n;
     for (uint32_t i = 0; i < c->I; ++i)
         for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t d = c->ik_dev_pos[k];
+            const uint32_t d = c->ik.dev_pos[k];
             out[(size_t)i * n + k] = c->iksw.words.empty() ? 1 : (uint8_t)((c->iksw.words[(size_t)i * W + (d >> 5)] >> (d & 31u)) & 1u);
         }
     return RZ_OK;
@@ -971,14 +950,14 @@ int rz_read_world(rz_ctx *c, uint32_t instance, float *world16)
     if (instance >= c->I || !world16 || !c->world) return fail(RZ_ERR_INVALID, "bad world read");
     const RzPoseLink::Current &p = c->pl.cur;
     if (p.zc_slot >= 0 && !p.zc_local && !p.world_resident) {     // a zero-copy pose no frame has consumed yet: still in its pinned slot
-        memcpy(world16, c->pl.zc.slot[p.zc_slot].host, (size_t)c->B * 16 * sizeof(float));
+        memcpy(world16, c->pl.zc.slot[p.zc_slot].host, (size_t)c->skel.B * 16 * sizeof(float));
         return RZ_OK;
     }
     if (solve_on_demand(c)) {                           // a crowd frame that solved its hierarchy in LDS only: the solve as a kernel of its own, now
         if (int r = launch_fk(c, c->stream)) return r;
     }
     if (int r = drain(c)) return r;        // rz_fk_kernel may have written them on the front stream
-    HIP_TRY(hipMemcpy(world16, c->world + (size_t)instance * c->B * 16, (size_t)c->B * 16 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(world16, c->world + (size_t)instance * c->skel.B * 16, (size_t)c->skel.B * 16 * sizeof(float), hipMemcpyDeviceToHost));
     return RZ_OK;
 }
 

@@ -83,7 +83,7 @@ int rz_autotune_measure(rz_ctx *c, uint32_t frames, rz_tune_entry *table, int ca
         for (int loop : {8, 4, 16})
             for (int capv : {ncu, 2 * ncu, 3 * ncu, 4 * ncu}) add(0, capv, loop);
     } else {
-        const int smax = c->morph_mode == 1 ? (int)std::min<uint32_t>(8, std::max<uint32_t>(1, c->M)) : 4;
+        const int smax = c->morphs.mode == 1 ? (int)std::min<uint32_t>(8, std::max<uint32_t>(1, c->morphs.M)) : 4;
         for (int sp = 1; sp <= smax; sp <<= 1)
             for (int capv : {ncu, 2 * ncu, 4 * ncu}) add(sp, (int)(capv * c->I), 0);
     }
@@ -237,20 +237,20 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
         // what the NEXT frame will launch: a crowd's plan depends on the run lists of its launch shape, so bring them up to
         // date first (as every entry point that launches frames does) instead of describing the whole-palette fallback
         if (int r = use(c)) return r;
-        if (c->V && c->B) {
+        if (c->mesh.V && c->skel.B) {
             if (int r = ensure_run_subsets(c)) return r;
             if (int r = ensure_subfk(c)) return r;
         }
     }
-    if (!strcmp(key, "bones")) *value = (int)c->B;
-    else if (!strcmp(key, "morphs")) *value = (int)c->M;
+    if (!strcmp(key, "bones")) *value = (int)c->skel.B;
+    else if (!strcmp(key, "morphs")) *value = (int)c->morphs.M;
     else if (!strcmp(key, "instances")) *value = (int)c->I;
-    else if (!strcmp(key, "verts")) *value = (int)c->V;
-    else if (!strcmp(key, "sdef_verts")) *value = (int)c->sdef_n;
-    else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef_n;
-    else if (!strcmp(key, "ik_chains")) *value = (int)c->ik_n;
-    else if (!strcmp(key, "motion_clips")) *value = (int)c->mo_clips;
-    else if (!strcmp(key, "motion_masks")) *value = (int)c->mk_count;
+    else if (!strcmp(key, "verts")) *value = (int)c->mesh.V;
+    else if (!strcmp(key, "sdef_verts")) *value = (int)c->sdef.n;
+    else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef.n;
+    else if (!strcmp(key, "ik_chains")) *value = (int)c->ik.n;
+    else if (!strcmp(key, "motion_clips")) *value = (int)c->lib.clips;
+    else if (!strcmp(key, "motion_masks")) *value = (int)c->mk.count;
     else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph.nb;
     else if (!strcmp(key, "physics_joints")) *value = (int)c->ph.nj;
     else if (!strcmp(key, "physics_colours")) *value = (int)c->ph.ncol;
@@ -272,18 +272,18 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "physics_lds")) *value = c->ph.nb ? (int)rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0;
     else if (!strcmp(key, "override_follow")) *value = c->ovr_follow;
     else if (!strcmp(key, "override_followers")) *value = solve_stages(c).fo.off ? (int)c->fol_count : 0;     // entries resident over all instances
-    else if (!strcmp(key, "after_physics")) *value = (int)c->af_n;         // entries resident (rz_upload_after_physics)
-    else if (!strcmp(key, "after_physics_levels")) *value = (int)c->af_levels;
-    else if (!strcmp(key, "ik_stages")) *value = (int)c->ik_stages;
+    else if (!strcmp(key, "after_physics")) *value = (int)c->af.n;         // entries resident (rz_upload_after_physics)
+    else if (!strcmp(key, "after_physics_levels")) *value = (int)c->af.levels;
+    else if (!strcmp(key, "ik_stages")) *value = (int)c->ik.stages;
     else if (!strcmp(key, "ik_switched")) *value = (int)c->iksw.off;       // (instance, chain) bits currently off
     else if (!strcmp(key, "ik_key_sets")) {
         int n = c->ik_keys_an.resident ? 1 : 0;
         for (const RzIkKeySet &s : c->ik_keys_mo) n += s.resident ? 1 : 0;
         *value = n;
     }
-    else if (!strcmp(key, "morph_mode")) *value = c->morph_mode;
-    else if (!strcmp(key, "effective_morph_storage")) *value = c->morph_mode == 1 ? c->morph_storage : 0;
-    else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morph_mode == 1 ? 1 : 0;
+    else if (!strcmp(key, "morph_mode")) *value = c->morphs.mode;
+    else if (!strcmp(key, "effective_morph_storage")) *value = c->morphs.mode == 1 ? c->morphs.storage : 0;
+    else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morphs.mode == 1 ? 1 : 0;
     else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;
     else if (!strcmp(key, "effective_geo")) *value = make_plan(c).v.geo ? 1 : 0;
     else if (!strcmp(key, "effective_prep")) { const Plan pl = make_plan(c); *value = ((pl.prep || c->pl.cur.local) && !pl.fuse_fk && !pl.subfk) ? 1 : 0; }
@@ -328,8 +328,8 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
     else if (!strncmp(key, "addr_", 5)) {
         // diagnostics (tools/archive/placement.py): where the allocator put a buffer — bits [12, 43) of its device address, i.e. the address in
         // 4 KB pages (where a buffer lands relative to the 2 MB large-page frame moves the C5 frame by 3 %: NOTEBOOK.md R5.3)
-        const void *ptr = !strcmp(key, "addr_dense") ? (const void *)c->dense : !strcmp(key, "addr_out") ? (const void *)c->out_pos :
-                          !strcmp(key, "addr_nrm") ? (const void *)c->out_nrm : !strcmp(key, "addr_geom") ? (const void *)c->geom : nullptr;
+        const void *ptr = !strcmp(key, "addr_dense") ? (const void *)c->morphs.dense : !strcmp(key, "addr_out") ? (const void *)c->out_pos :
+                          !strcmp(key, "addr_nrm") ? (const void *)c->out_nrm : !strcmp(key, "addr_geom") ? (const void *)c->mesh.geom : nullptr;
         if (!ptr && strcmp(key, "addr_dense") && strcmp(key, "addr_out") && strcmp(key, "addr_nrm") && strcmp(key, "addr_geom")) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
         *value = (int)(((uintptr_t)ptr >> 12) & 0x7fffffffu);
     }

@@ -9,18 +9,19 @@ namespace rzi {
 // Called when either side changes (the caller has drained the stream); a context without a topology has no block.
 int rebuild_fk_static(rz_ctx *c)
 {
-    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4) return RZ_OK;
-    const bool motion = c->has_animation && c->an_host_range.size() == c->B;
+    if (!c->fk.has_topology || c->fk.host.size() != (size_t)c->skel.B * 4) return RZ_OK;
+    const bool motion = c->has_animation && c->an_host_range.size() == c->skel.B;
     const size_t nm = motion ? c->an_host_mrec.size() / 2 : 0;
-    std::vector<uint4> blk(c->fk_host);
-    blk.resize((size_t)c->B * 4 + nm * 2);
-    for (uint32_t b = 0; b < c->B; ++b) blk[4 * (size_t)b + 2] = motion ? c->an_host_range[b] : make_uint4(0u, 0u, 0u, 0u);
-    for (size_t k = 0; k < nm * 2; ++k) blk[(size_t)c->B * 4 + k] = c->an_host_mrec[k];
+    std::vector<uint4> blk(c->fk.host);
+    blk.resize((size_t)c->skel.B * 4 + nm * 2);
+    for (uint32_t b = 0; b < c->skel.B; ++b) blk[4 * (size_t)b + 2] = motion ? c->an_host_range[b] : make_uint4(0u, 0u, 0u, 0u);
+    for (size_t k = 0; k < nm * 2; ++k) blk[(size_t)c->skel.B * 4 + k] = c->an_host_mrec[k];
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
-    dfree(c->fk_rec);
+    c->fk.rec = {};
     c->fk_gen++;                        // (the closure records of crowd frames carry copies of these: plan.cpp ensure_subfk)
-    return to_device(&c->fk_rec, blk.data(), blk.size());
+    if (int r = to_device(c->fk.rec, blk.data(), blk.size())) { c->fk = {}; return r; }      // (no block, no topology: nothing solves on the device until the next one)
+    return RZ_OK;
 }
 
 }  // namespace rzi
@@ -35,7 +36,7 @@ int upload_skinning(rz_ctx *c, uint32_t V, const uint16_t *joints4, const uint8_
     HIP_TRY(dw.alloc((size_t)V * 4));
     HIP_TRY(hipMemcpy(dj.p, joints4, (size_t)V * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dw.p, weights4, (size_t)V * 4, hipMemcpyHostToDevice));
-    HIP_TRY(rz_launch_pack_skinning(dj.p, dw.p, V, c->j01, c->j23, c->wq, c->stream));
+    HIP_TRY(rz_launch_pack_skinning(dj.p, dw.p, V, c->mesh.j01, c->mesh.j23, c->mesh.wq, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RZ_OK;
 }
@@ -44,23 +45,25 @@ int alloc_mesh(rz_ctx *c, uint32_t V)
 {
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_direct_gather(c);                // shard sizes are about to change: back to private output buffers
-    dfree(c->geom); dfree(c->j01); dfree(c->j23); dfree(c->wq); dfree(c->edge);
-    dfree(c->rj01); dfree(c->rj23); c->sub_valid = false;      // the run lists name this mesh's joints
+    c->mesh = {}; c->edge = {};
+    c->rj01 = {}; c->rj23 = {}; c->sub_valid = false;      // the run lists name this mesh's joints
     free_morphs(c);                       // morph targets are per-vertex: a new mesh invalidates them
     free_sdef(c);                         // ... and so does the SDEF table: its indices name the old mesh's vertices
     free_qdef(c);                         // ... and the QDEF table
-    c->V = V;
-    c->Vp = round_up(V, kVertPad);
-    const size_t Vp = c->Vp;
-    HIP_TRY(hipMalloc(&c->geom, 6 * Vp * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->j01, Vp * 4));
-    HIP_TRY(hipMalloc(&c->j23, Vp * 4));
-    HIP_TRY(hipMalloc(&c->wq, Vp * 4));
+    RzStatic::Mesh m;                     // (takes its place whole: a failure leaves no vertex count over a missing plane)
+    m.V = V;
+    m.Vp = round_up(V, kVertPad);
+    const size_t Vp = m.Vp;
+    HIP_TRY(m.geom.alloc(6 * Vp));
+    HIP_TRY(m.j01.alloc(Vp));
+    HIP_TRY(m.j23.alloc(Vp));
+    HIP_TRY(m.wq.alloc(Vp));
+    c->mesh = std::move(m);
     // padding vertices: zero position/normal, joint 0, weights 0 (takes the (1,0,0,0) branch)
-    HIP_TRY(hipMemsetAsync(c->geom, 0, 6 * Vp * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->j01, 0, Vp * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(c->j23, 0, Vp * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(c->wq, 0, Vp * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->mesh.geom, 0, 6 * Vp * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(c->mesh.j01, 0, Vp * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->mesh.j23, 0, Vp * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->mesh.wq, 0, Vp * 4, c->stream));
     return RZ_OK;
 }
 
@@ -113,9 +116,9 @@ int rz_upload_mesh(rz_ctx *c, uint32_t V, const float *interleaved8, const uint1
     HIP_TRY(scratch.alloc((size_t)V * 8));
     float *tmp = scratch.p;
     HIP_TRY(hipMemcpy(tmp, interleaved8, (size_t)V * 8 * sizeof(float), hipMemcpyHostToDevice));
-    const size_t Vp = c->Vp;
-    HIP_TRY(rz_launch_deinterleave(tmp, 8, 0, V, c->geom, c->geom + Vp, c->geom + 2 * Vp, c->stream));
-    HIP_TRY(rz_launch_deinterleave(tmp, 8, 3, V, c->geom + 3 * Vp, c->geom + 4 * Vp, c->geom + 5 * Vp, c->stream));
+    const size_t Vp = c->mesh.Vp;
+    HIP_TRY(rz_launch_deinterleave(tmp, 8, 0, V, c->mesh.geom, c->mesh.geom + Vp, c->mesh.geom + 2 * Vp, c->stream));
+    HIP_TRY(rz_launch_deinterleave(tmp, 8, 3, V, c->mesh.geom + 3 * Vp, c->mesh.geom + 4 * Vp, c->mesh.geom + 5 * Vp, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int r = upload_skinning(c, V, joints4, weights4)) return r;
     return ensure_outputs(c);
@@ -131,12 +134,12 @@ int rz_upload_mesh_soa(rz_ctx *c, uint32_t V, const float *pos3, const float *nr
     Scratch<float> scratch;
     HIP_TRY(scratch.alloc((size_t)V * 3));
     float *tmp = scratch.p;
-    const size_t Vp = c->Vp;
+    const size_t Vp = c->mesh.Vp;
     HIP_TRY(hipMemcpy(tmp, pos3, (size_t)V * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(rz_launch_deinterleave(tmp, 3, 0, V, c->geom, c->geom + Vp, c->geom + 2 * Vp, c->stream));
+    HIP_TRY(rz_launch_deinterleave(tmp, 3, 0, V, c->mesh.geom, c->mesh.geom + Vp, c->mesh.geom + 2 * Vp, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(tmp, nrm3, (size_t)V * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(rz_launch_deinterleave(tmp, 3, 0, V, c->geom + 3 * Vp, c->geom + 4 * Vp, c->geom + 5 * Vp, c->stream));
+    HIP_TRY(rz_launch_deinterleave(tmp, 3, 0, V, c->mesh.geom + 3 * Vp, c->mesh.geom + 4 * Vp, c->mesh.geom + 5 * Vp, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int r = upload_skinning(c, V, joints4, weights4)) return r;
     return ensure_outputs(c);
@@ -152,17 +155,14 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     drop_graph(c);
     c->ovr_count = 0;
     c->ovr_follow = 0; c->fol_count = 0;        // rz_override_follow goes with the hierarchy it was set for
-    dfree(c->inv_bind);
-    HIP_TRY(hipMalloc(&c->inv_bind, (size_t)B * 16 * sizeof(float)));
-    HIP_TRY(hipMemcpy(c->inv_bind, inverse_bind16, (size_t)B * 16 * sizeof(float), hipMemcpyHostToDevice));
-    c->B = B;
+    c->skel = {};
+    if (int r = to_device(c->skel.inv_bind, inverse_bind16, (size_t)B * 16)) { c->skel = {}; return r; }
+    c->skel.B = B;
     retire_pose_tags(c);                // a pose staged for the old skeleton must never match
     c->sub_valid = false;               // joints are clamped to the bone count when the run lists are built
     c->palette_stale = false;
     c->pl.cur.set = false;
-    c->has_topology = false;            // belongs to the previous skeleton ...
-    dfree(c->fk_rec); dfree(c->fk_anc_more);        // ... and so do its records (sized for the old bone count: nothing may read them for the new one)
-    c->fk_host.clear(); c->fk_rounds = 0; c->fk_gen++;
+    c->fk = {}; c->fk_gen++;            // the topology belongs to the previous skeleton, and so do its records (sized for the old bone count: nothing may read them for the new one)
     c->fk_stale = false; c->subfk_valid = false;
     free_bone_morphs(c);                // ... as do bone morphs (their entries name its bones)
     free_ik(c);                         // ... and the IK table (its chains name its bones)
@@ -226,18 +226,19 @@ int rz_morph_encode24(const float *deltas, uint32_t M, uint32_t V, uint8_t *pack
     return RZ_OK;
 }
 
-static int upload_dense_f32(rz_ctx *c, uint32_t M, const float *deltas)
+// the two forms of a dense set, built into `t` (a local of the upload: it takes the context's place only when it is whole)
+static int upload_dense_f32(rz_ctx *c, RzStatic::Morphs &t, uint32_t M, const float *deltas)
 {
-    const size_t Vp = c->Vp, V = c->V;
+    const size_t Vp = c->mesh.Vp, V = c->mesh.V;
     size_t dense_off = 0;
 #ifdef RZ_ALL_VARIANTS
     // tools-only build: place the morph planes `RZ_DENSE_OFFSET` bytes into a larger allocation (tools/archive/placement.py: how much of the C5
-    // frame's box-to-box spread is WHERE the 768 MB land). The offset is lost on free: hipFree gets the shifted pointer — leak, tools only.
+    // frame's box-to-box spread is WHERE the 768 MB land). The owner keeps the allocation's base; frames read the shifted pointer.
     if (const char *e = getenv("RZ_DENSE_OFFSET")) dense_off = (size_t)strtoull(e, nullptr, 0) / 256 * 256;
 #endif
-    HIP_TRY(hipMalloc(&c->dense, (size_t)M * 3 * Vp * sizeof(float) + dense_off));
-    c->dense += dense_off / sizeof(float);
-    if (Vp != V) HIP_TRY(hipMemsetAsync(c->dense, 0, (size_t)M * 3 * Vp * sizeof(float), c->stream));
+    HIP_TRY(t.dense_base.alloc((size_t)M * 3 * Vp + dense_off / sizeof(float)));
+    t.dense = t.dense_base + dense_off / sizeof(float);
+    if (Vp != V) HIP_TRY(hipMemsetAsync(t.dense, 0, (size_t)M * 3 * Vp * sizeof(float), c->stream));
     // stream the host array through a bounded device staging buffer, re-laying each morph into planes
     const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(M, (64u << 20) / (V * 12)));
     Scratch<float> scratch;
@@ -247,24 +248,25 @@ static int upload_dense_f32(rz_ctx *c, uint32_t M, const float *deltas)
         const uint32_t nb = std::min(batch, M - m0);
         HIP_TRY(hipMemcpy(tmp, deltas + (size_t)m0 * V * 3, (size_t)nb * V * 3 * sizeof(float), hipMemcpyHostToDevice));
         for (uint32_t k = 0; k < nb; ++k) {
-            float *pl = c->dense + (size_t)(m0 + k) * 3 * Vp;
+            float *pl = t.dense + (size_t)(m0 + k) * 3 * Vp;
             HIP_TRY(rz_launch_deinterleave(tmp + (size_t)k * V * 3, 3, 0, (uint32_t)V, pl, pl + Vp, pl + 2 * Vp, c->stream));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->morph_storage = 32;
+    t.storage = 32;
     return RZ_OK;
 }
 
 // 24-bit planes: encoded on the host a batch of morphs at a time (at most 64 MB of packed planes), each batch one copy
-static int upload_dense_q24(rz_ctx *c, uint32_t M, const float *deltas, const std::vector<float> &scales)
+static int upload_dense_q24(rz_ctx *c, RzStatic::Morphs &t, uint32_t M, const float *deltas, const std::vector<float> &scales)
 {
-    const size_t Vp = c->Vp, V = c->V, plane = Vp * 3, per_morph = plane * 3;      // bytes
-    HIP_TRY(hipMalloc(&c->dense, (size_t)M * per_morph));
-    HIP_TRY(hipMalloc(&c->dense_fold, (size_t)M * sizeof(float)));
+    const size_t Vp = c->mesh.Vp, V = c->mesh.V, plane = Vp * 3, per_morph = plane * 3;      // bytes
+    HIP_TRY(t.dense_base.alloc((size_t)M * per_morph / sizeof(float)));       // (Vp is a multiple of 1024: whole floats)
+    t.dense = t.dense_base;
+    HIP_TRY(t.dense_fold.alloc(M));
     const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(M, (64u << 20) / per_morph));
     std::vector<uint32_t> stage((size_t)batch * per_morph / 4, 0u);               // (the pad past V stays zero: every batch writes the same quads)
-    char *dst = reinterpret_cast<char *>(c->dense);
+    char *dst = reinterpret_cast<char *>(t.dense);
     for (uint32_t m0 = 0; m0 < M; m0 += batch) {
         const uint32_t nb = std::min(batch, M - m0);
         for (uint32_t k = 0; k < nb; ++k)
@@ -272,10 +274,10 @@ static int upload_dense_q24(rz_ctx *c, uint32_t M, const float *deltas, const st
                 encode_plane24(deltas + (size_t)(m0 + k) * V * 3, (uint32_t)V, comp, 1.0f / scales[m0 + k], stage.data() + ((size_t)k * 3 + comp) * (plane / 4));
         HIP_TRY(hipMemcpy(dst + (size_t)m0 * per_morph, stage.data(), (size_t)nb * per_morph, hipMemcpyHostToDevice));
     }
-    c->dense_fold_host.resize(M);
-    for (uint32_t m = 0; m < M; ++m) c->dense_fold_host[m] = scales[m] * (1.0f / 256.0f);
-    HIP_TRY(hipMemcpy(c->dense_fold, c->dense_fold_host.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice));
-    c->morph_storage = 24;
+    t.dense_fold_host.resize(M);
+    for (uint32_t m = 0; m < M; ++m) t.dense_fold_host[m] = scales[m] * (1.0f / 256.0f);
+    HIP_TRY(hipMemcpy(t.dense_fold, t.dense_fold_host.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice));
+    t.storage = 24;
     return RZ_OK;
 }
 
@@ -284,18 +286,20 @@ int rz_upload_morphs_dense_ex(rz_ctx *c, uint32_t M, const float *deltas, uint32
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_morphs_dense")) return r;
     if (flags & ~(uint32_t)RZ_MORPH_F32) return fail(RZ_ERR_INVALID, "rz_upload_morphs_dense_ex: unknown flags 0x%x", flags);
-    if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its morph targets");
+    if (c->mesh.V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its morph targets");
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_morphs(c);
     if (M == 0) return ensure_pose_buffers(c);
     if (!deltas) return fail(RZ_ERR_INVALID, "null morph deltas");
     std::vector<float> scales(M);
     bool q24 = !(flags & RZ_MORPH_F32);
-    if (q24) q24 = morph_scales24(M, c->V, deltas, scales.data());
-    if (int r = q24 ? upload_dense_q24(c, M, deltas, scales) : upload_dense_f32(c, M, deltas)) { free_morphs(c); return r; }
-    c->morph_mode = 1;
-    c->M = M;
-    c->Mpad = round_up(M + 8, 4);
+    if (q24) q24 = morph_scales24(M, c->mesh.V, deltas, scales.data());
+    RzStatic::Morphs t;
+    if (int r = q24 ? upload_dense_q24(c, t, M, deltas, scales) : upload_dense_f32(c, t, M, deltas)) return r;
+    t.mode = 1;
+    t.M = M;
+    t.Mpad = round_up(M + 8, 4);
+    c->morphs = std::move(t);
     return ensure_pose_buffers(c);
 }
 
@@ -304,18 +308,18 @@ int rz_upload_morphs_dense(rz_ctx *c, uint32_t M, const float *deltas) { return 
 int rz_read_morph_dense(rz_ctx *c, uint32_t m, float *planes3)
 {
     if (int r = use(c)) return r;
-    if (c->morph_mode != 1 || !c->dense) return fail(RZ_ERR_INVALID, "rz_read_morph_dense: no dense morph targets resident");
-    if (m >= c->M || !planes3) return fail(RZ_ERR_INVALID, "rz_read_morph_dense: morph %u of %u, or null output", m, c->M);
+    if (c->morphs.mode != 1 || !c->morphs.dense) return fail(RZ_ERR_INVALID, "rz_read_morph_dense: no dense morph targets resident");
+    if (m >= c->morphs.M || !planes3) return fail(RZ_ERR_INVALID, "rz_read_morph_dense: morph %u of %u, or null output", m, c->morphs.M);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t Vp = c->Vp, V = c->V;
-    if (c->morph_storage != 24) {
+    const size_t Vp = c->mesh.Vp, V = c->mesh.V;
+    if (c->morphs.storage != 24) {
         for (int comp = 0; comp < 3; ++comp)
-            HIP_TRY(hipMemcpy(planes3 + comp * V, c->dense + ((size_t)m * 3 + comp) * Vp, V * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(planes3 + comp * V, c->morphs.dense + ((size_t)m * 3 + comp) * Vp, V * sizeof(float), hipMemcpyDeviceToHost));
         return RZ_OK;
     }
     std::vector<uint8_t> raw(Vp * 9);
-    HIP_TRY(hipMemcpy(raw.data(), reinterpret_cast<const char *>(c->dense) + (size_t)m * Vp * 9, raw.size(), hipMemcpyDeviceToHost));
-    const float fold = c->dense_fold_host[m];
+    HIP_TRY(hipMemcpy(raw.data(), reinterpret_cast<const char *>(c->morphs.dense) + (size_t)m * Vp * 9, raw.size(), hipMemcpyDeviceToHost));
+    const float fold = c->morphs.dense_fold_host[m];
     for (int comp = 0; comp < 3; ++comp)
         for (size_t v = 0; v < V; ++v) {
             const uint8_t *b = raw.data() + (size_t)comp * Vp * 3 + v * 3;
@@ -329,7 +333,7 @@ int rz_upload_morphs_sparse(rz_ctx *c, uint32_t M, const uint32_t *morph_off, co
 {
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_morphs_sparse")) return r;
-    if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its morph targets");
+    if (c->mesh.V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its morph targets");
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_morphs(c);
     if (M == 0) return ensure_pose_buffers(c);
@@ -340,10 +344,10 @@ int rz_upload_morphs_sparse(rz_ctx *c, uint32_t M, const uint32_t *morph_off, co
         if (morph_off[m] > morph_off[m + 1]) return fail(RZ_ERR_INVALID, "morph offsets must be non-decreasing");
     // transpose morph-major (PMX file order) into a per-vertex CSR; a vertex's entries keep
     // ascending morph order (then file order), which is the oracle's accumulation order
-    const size_t Vp = c->Vp;
+    const size_t Vp = c->mesh.Vp;
     std::vector<uint32_t> ptr(Vp + 1, 0);
     for (uint32_t e = 0; e < E; ++e)
-        if (vert_idx[e] < c->V) ptr[vert_idx[e] + 1]++;
+        if (vert_idx[e] < c->mesh.V) ptr[vert_idx[e] + 1]++;
     for (size_t v = 0; v < Vp; ++v) ptr[v + 1] += ptr[v];
     const uint32_t kept = ptr[Vp];
     std::vector<float4> ent(std::max<uint32_t>(kept, 1));
@@ -351,20 +355,22 @@ int rz_upload_morphs_sparse(rz_ctx *c, uint32_t M, const uint32_t *morph_off, co
     for (uint32_t m = 0; m < M; ++m)
         for (uint32_t e = morph_off[m]; e < morph_off[m + 1]; ++e) {
             const uint32_t v = vert_idx[e];
-            if (v >= c->V) continue;
+            if (v >= c->mesh.V) continue;
             float4 x;
             x.x = delta3[(size_t)e * 3]; x.y = delta3[(size_t)e * 3 + 1]; x.z = delta3[(size_t)e * 3 + 2];
             memcpy(&x.w, &m, 4);
             ent[cur[v]++] = x;
         }
-    HIP_TRY(hipMalloc(&c->sp_ptr, (Vp + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->sp_entries, ent.size() * sizeof(float4)));
-    HIP_TRY(hipMemcpy(c->sp_ptr, ptr.data(), (Vp + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->sp_entries, ent.data(), ent.size() * sizeof(float4), hipMemcpyHostToDevice));
-    c->sp_count = kept;
-    c->morph_mode = 2;
-    c->M = M;
-    c->Mpad = round_up(M + 8, 4);
+    RzStatic::Morphs t;
+    HIP_TRY(t.sp_ptr.alloc(Vp + 1));
+    HIP_TRY(t.sp_entries.alloc(ent.size()));
+    HIP_TRY(hipMemcpy(t.sp_ptr, ptr.data(), (Vp + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.sp_entries, ent.data(), ent.size() * sizeof(float4), hipMemcpyHostToDevice));
+    t.sp_count = kept;
+    t.mode = 2;
+    t.M = M;
+    t.Mpad = round_up(M + 8, 4);
+    c->morphs = std::move(t);
     return ensure_pose_buffers(c);
 }
 
@@ -385,7 +391,7 @@ int rz_set_instances(rz_ctx *c, uint32_t I)
         c->ph.reset = true;               // (a physics table rebuilds its per-instance state and the overrides at its next step)
         // The host-compacted active-morph list is only maintained while I == 1 (upload_pose). Coming back to one instance
         // from a crowd it is stale (zeroed): let the prep kernel compact instance 0's weights, which are still on the device.
-        if (c->M > 0 && c->morph_mode == 1) c->pl.cur.ml.count = -1;
+        if (c->morphs.M > 0 && c->morphs.mode == 1) c->pl.cur.ml.count = -1;
         // A crowd larger than the one the resident pose was uploaded for has no pose for its new members (and a
         // single-character pose may still sit in its pinned slot, which holds exactly one instance): ask for a new one.
         if (I > c->pl.cur.I) c->pl.cur.set = false;
@@ -402,7 +408,7 @@ int rz_upload_skeleton_topology(rz_ctx *c, uint32_t B, const int32_t *parents, c
 {
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_skeleton_topology")) return r;
-    if (B == 0 || B != c->B) return fail(RZ_ERR_INVALID, "topology has %u bones but the uploaded skeleton has %u", B, c->B);
+    if (B == 0 || B != c->skel.B) return fail(RZ_ERR_INVALID, "topology has %u bones but the uploaded skeleton has %u", B, c->skel.B);
     if (!parents || !bind_translation3) return fail(RZ_ERR_INVALID, "null topology arrays");
     // hierarchy levels (parents may come in any order, like the reference's recursive solve; cycles are an error)
     std::vector<int> level(B, -1);
@@ -456,12 +462,14 @@ int rz_upload_skeleton_topology(rz_ctx *c, uint32_t B, const int32_t *parents, c
     c->ovr_count = 0;
     c->ovr_follow = 0; c->fol_count = 0;        // rz_override_follow: the follower lists were built from the old parents
     c->fk_stale = false;                // (a crowd frame solved under the old topology: nothing of it can be formed on demand any more)
-    dfree(c->fk_anc_more);
+    c->fk = {}; c->fk_gen++;
+    RzStatic::Hierarchy t;
     if (!more.empty())
-        if (int r = to_device(&c->fk_anc_more, more.data(), more.size())) return r;
-    c->fk_host = std::move(rec);
-    c->fk_rounds = n_rounds;
-    c->has_topology = true;
+        if (int r = to_device(t.anc_more, more.data(), more.size())) return r;
+    t.host = std::move(rec);
+    t.rounds = n_rounds;
+    t.has_topology = true;
+    c->fk = std::move(t);
     return rebuild_fk_static(c);
 }
 
@@ -474,12 +482,12 @@ int rz_upload_bone_morphs(rz_ctx *c, uint32_t n, const uint32_t *morph, const ui
         free_bone_morphs(c);
         return RZ_OK;
     }
-    if (!c->has_topology) return fail(RZ_ERR_INVALID, "bone morphs act on device-solved poses: call rz_upload_skeleton_topology first");
-    if (c->M == 0) return fail(RZ_ERR_INVALID, "upload the morph set first (rz_upload_morphs_*): bone-morph entries name its morphs");
+    if (!c->fk.has_topology) return fail(RZ_ERR_INVALID, "bone morphs act on device-solved poses: call rz_upload_skeleton_topology first");
+    if (c->morphs.M == 0) return fail(RZ_ERR_INVALID, "upload the morph set first (rz_upload_morphs_*): bone-morph entries name its morphs");
     if (!morph || !bone || !translation3 || !rotation4) return fail(RZ_ERR_INVALID, "null bone-morph arrays");
     for (uint32_t k = 0; k < n; ++k) {
-        if (morph[k] >= c->M) return fail(RZ_ERR_INVALID, "bone-morph entry %u names morph %u of %u", k, morph[k], c->M);
-        if (bone[k] >= c->B) return fail(RZ_ERR_INVALID, "bone-morph entry %u names bone %u of %u", k, bone[k], c->B);
+        if (morph[k] >= c->morphs.M) return fail(RZ_ERR_INVALID, "bone-morph entry %u names morph %u of %u", k, morph[k], c->morphs.M);
+        if (bone[k] >= c->skel.B) return fail(RZ_ERR_INVALID, "bone-morph entry %u names bone %u of %u", k, bone[k], c->skel.B);
         for (int j = 0; j < 7; ++j) {
             const float x = j < 3 ? translation3[(size_t)k * 3 + j] : rotation4[(size_t)k * 4 + j - 3];
             if (!(x == x) || x - x != 0.0f) return fail(RZ_ERR_INVALID, "bone-morph entry %u is not finite", k);
@@ -489,7 +497,7 @@ int rz_upload_bone_morphs(rz_ctx *c, uint32_t n, const uint32_t *morph, const ui
     std::vector<uint32_t> idx(n);
     for (uint32_t k = 0; k < n; ++k) idx[k] = k;
     std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return bone[a] != bone[b] ? bone[a] < bone[b] : morph[a] < morph[b]; });
-    std::vector<uint32_t> off(c->B + 1, 0), mo(n);
+    std::vector<uint32_t> off(c->skel.B + 1, 0), mo(n);
     std::vector<float4> rot(n), tr(n);
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t e = idx[k];
@@ -498,32 +506,34 @@ int rz_upload_bone_morphs(rz_ctx *c, uint32_t n, const uint32_t *morph, const ui
         rot[k] = make_float4(rotation4[(size_t)e * 4], rotation4[(size_t)e * 4 + 1], rotation4[(size_t)e * 4 + 2], rotation4[(size_t)e * 4 + 3]);
         tr[k] = make_float4(translation3[(size_t)e * 3], translation3[(size_t)e * 3 + 1], translation3[(size_t)e * 3 + 2], 0.0f);
     }
-    for (uint32_t b = 0; b < c->B; ++b) off[b + 1] += off[b];
+    for (uint32_t b = 0; b < c->skel.B; ++b) off[b + 1] += off[b];
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_bone_morphs(c);
     drop_graph(c);
-    if (int r = to_device(&c->bm_off, off.data(), off.size())) return r;
-    if (int r = to_device(&c->bm_morph, mo.data(), n)) return r;
-    if (int r = to_device(&c->bm_rot, rot.data(), n)) return r;
-    if (int r = to_device(&c->bm_tr, tr.data(), n)) return r;
-    c->bm_count = n;
+    RzStatic::BoneMorphs t;
+    if (int r = to_device(t.off, off.data(), off.size())) return r;
+    if (int r = to_device(t.morph, mo.data(), n)) return r;
+    if (int r = to_device(t.rot, rot.data(), n)) return r;
+    if (int r = to_device(t.tr, tr.data(), n)) return r;
+    t.count = n;
+    c->bm = std::move(t);
     return RZ_OK;
 }
 
-// One motion store from motion_table.h's arrays (the caller has released what the store held). Every pointer is allocated, of four
+// One motion store from motion_table.h's arrays, into an empty store (a local of the upload). Every pointer is allocated, of four
 // elements at least (to_device), but the interpolation bytes: null when no clip carries any.
 static int upload_keys(RzStatic::RzKeys &k, const rzmotion::Flat &f, uint32_t M)
 {
-    if (int r = to_device(&k.key_frame, f.key_frame.data(), f.key_frame.size())) return r;
-    if (int r = to_device(&k.key_rot, f.key_rot.data(), f.key_rot.size() / 4)) return r;
-    if (int r = to_device(&k.key_pos, f.key_pos.data(), f.key_pos.size())) return r;
+    if (int r = to_device(k.key_frame, f.key_frame.data(), f.key_frame.size())) return r;
+    if (int r = to_device(k.key_rot, f.key_rot.data(), f.key_rot.size() / 4)) return r;
+    if (int r = to_device(k.key_pos, f.key_pos.data(), f.key_pos.size())) return r;
     if (!f.key_interp.empty())
-        if (int r = to_device(&k.key_interp, f.key_interp.data(), f.key_interp.size() / 16)) return r;
-    if (int r = to_device(&k.mkey_frame, f.mkey_frame.data(), f.mkey_frame.size())) return r;
-    if (int r = to_device(&k.mkey_weight, f.mkey_weight.data(), f.mkey_weight.size())) return r;
-    if (int r = to_device(&k.feed_off, f.feed_off.data(), f.feed_off.size())) return r;
-    if (int r = to_device(&k.feed_range, f.feed_range.data(), f.feed_range.size() / 4)) return r;
-    if (int r = to_device(&k.feed_ratio, f.feed_ratio.data(), f.feed_ratio.size())) return r;
+        if (int r = to_device(k.key_interp, f.key_interp.data(), f.key_interp.size() / 16)) return r;
+    if (int r = to_device(k.mkey_frame, f.mkey_frame.data(), f.mkey_frame.size())) return r;
+    if (int r = to_device(k.mkey_weight, f.mkey_weight.data(), f.mkey_weight.size())) return r;
+    if (int r = to_device(k.feed_off, f.feed_off.data(), f.feed_off.size())) return r;
+    if (int r = to_device(k.feed_range, f.feed_range.data(), f.feed_range.size() / 4)) return r;
+    if (int r = to_device(k.feed_ratio, f.feed_ratio.data(), f.feed_ratio.size())) return r;
     k.M = M;
     return RZ_OK;
 }
@@ -534,17 +544,19 @@ int rz_upload_animation(rz_ctx *c, const rz_animation *a)
     if (int r = static_unlocked(c, "rz_upload_animation")) return r;
     rzmotion::Flat f;
     std::string why;
-    if (!rzmotion::flatten(c->B, c->M, 1, a, nullptr, f, why)) return fail(RZ_ERR_INVALID, "%s", why.c_str());
+    if (!rzmotion::flatten(c->skel.B, c->morphs.M, 1, a, nullptr, f, why)) return fail(RZ_ERR_INVALID, "%s", why.c_str());
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_animation(c);
-    if (int r = upload_keys(c->an, f, c->M)) return r;
+    RzStatic::RzKeys keys;
+    if (int r = upload_keys(keys, f, c->morphs.M)) return r;
+    c->an = std::move(keys);
     // host copies for the hierarchy's static block. Per bone: the key range itself, so the sampler's chain of dependent loads starts one
     // level lower. Per vertex morph: the key range of its FIRST feed and (first feed, end of feeds, bits(its ratio)) — the sampler's one record per morph
     auto rec = [](const std::vector<uint32_t> &v, size_t k) { return make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]); };
-    c->an_host_range.resize(c->B);
-    for (uint32_t b = 0; b < c->B; ++b) c->an_host_range[b] = rec(f.bone_rec, b);
-    c->an_host_mrec.assign((size_t)c->M * 2, make_uint4(0u, 0u, 0u, 0u));
-    for (uint32_t m = 0; m < c->M; ++m) {
+    c->an_host_range.resize(c->skel.B);
+    for (uint32_t b = 0; b < c->skel.B; ++b) c->an_host_range[b] = rec(f.bone_rec, b);
+    c->an_host_mrec.assign((size_t)c->morphs.M * 2, make_uint4(0u, 0u, 0u, 0u));
+    for (uint32_t m = 0; m < c->morphs.M; ++m) {
         const uint32_t f0 = f.feed_off[m], f1 = f.feed_off[m + 1];
         if (f1 > f0) {
             uint32_t rb;
@@ -569,11 +581,15 @@ int rz_upload_motions(rz_ctx *c, uint32_t n_clips, const rz_animation *clips)
     if (n_clips == 0xffffffffu) return fail(RZ_ERR_INVALID, "rz_upload_motions: too many clips");
     rzmotion::Flat f;                   // every clip is checked before anything is replaced
     std::string why;
-    if (!rzmotion::flatten(c->B, c->M, n_clips, clips, "rz_upload_motions", f, why)) return fail(RZ_ERR_INVALID, "%s", why.c_str());
+    if (!rzmotion::flatten(c->skel.B, c->morphs.M, n_clips, clips, "rz_upload_motions", f, why)) return fail(RZ_ERR_INVALID, "%s", why.c_str());
     free_motions(c);                    // (drains both streams first: a pose kernel may still be reading the old library)
-    if (int r = to_device(&c->mo_bone_rec, f.bone_rec.data(), f.bone_rec.size() / 4)) return r;
-    if (int r = upload_keys(c->mo, f, c->M)) return r;
-    c->mo_clips = n_clips;
+    RzStatic::Library lib;
+    RzStatic::RzKeys keys;
+    if (int r = to_device(lib.bone_rec, f.bone_rec.data(), f.bone_rec.size() / 4)) return r;
+    if (int r = upload_keys(keys, f, c->morphs.M)) return r;
+    lib.clips = n_clips;
+    c->mo = std::move(keys);
+    c->lib = std::move(lib);
     return RZ_OK;
 }
 
@@ -587,10 +603,10 @@ int rz_upload_motion_masks(rz_ctx *c, uint32_t n_masks, const uint8_t *bone_mask
         free_motion_masks(c);
         return RZ_OK;
     }
-    if (c->B == 0) return fail(RZ_ERR_INVALID, "upload the skeleton before the motion masks");
+    if (c->skel.B == 0) return fail(RZ_ERR_INVALID, "upload the skeleton before the motion masks");
     if (!bone_mask) return fail(RZ_ERR_INVALID, "rz_upload_motion_masks: null bone masks");
     if (n_masks == 0xffffffffu) return fail(RZ_ERR_INVALID, "rz_upload_motion_masks: too many masks");
-    const uint32_t B = c->B, M = c->M, wb = (B + 31) / 32, wm = (M + 31) / 32;
+    const uint32_t B = c->skel.B, M = c->morphs.M, wb = (B + 31) / 32, wm = (M + 31) / 32;
     auto pack = [n_masks](const uint8_t *bytes, uint32_t n, uint32_t words) {
         std::vector<uint32_t> bits((size_t)n_masks * words, 0u);
         for (uint32_t k = 0; k < n_masks; ++k)
@@ -602,13 +618,15 @@ int rz_upload_motion_masks(rz_ctx *c, uint32_t n_masks, const uint8_t *bone_mask
     const bool morphs = morph_mask != nullptr && M > 0;
     const std::vector<uint32_t> morph_bits = morphs ? pack(morph_mask, M, wm) : std::vector<uint32_t>();
     free_motion_masks(c);               // (drains both streams first: a layer kernel may still be reading the old masks)
-    if (int r = to_device(&c->mk_bone_bits, bone_bits.data(), bone_bits.size())) return r;
+    RzStatic::Masks t;
+    if (int r = to_device(t.bone_bits, bone_bits.data(), bone_bits.size())) return r;
     if (morphs)
-        if (int r = to_device(&c->mk_morph_bits, morph_bits.data(), morph_bits.size())) { free_motion_masks(c); return r; }
-    c->mk_bone_words = wb;
-    c->mk_morph_words = morphs ? wm : 0;
-    c->mk_M = M;
-    c->mk_count = n_masks;
+        if (int r = to_device(t.morph_bits, morph_bits.data(), morph_bits.size())) return r;
+    t.bone_words = wb;
+    t.morph_words = morphs ? wm : 0;
+    t.M = M;
+    t.count = n_masks;
+    c->mk = std::move(t);
     return RZ_OK;
 }
 
@@ -618,13 +636,15 @@ int rz_upload_edge_scale(rz_ctx *c, uint32_t V, const float *edge_size)
     if (int r = static_unlocked(c, "rz_upload_edge_scale")) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
-    if (!edge_size) { dfree(c->edge); return RZ_OK; }
-    if (V != c->V || V == 0) return fail(RZ_ERR_INVALID, "edge scale has %u entries but the mesh has %u vertices", V, c->V);
-    dfree(c->edge);
-    HIP_TRY(hipMalloc(&c->edge, (size_t)c->Vp * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(c->edge, 0, (size_t)c->Vp * sizeof(float), c->stream));
+    if (!edge_size) { c->edge = {}; return RZ_OK; }
+    if (V != c->mesh.V || V == 0) return fail(RZ_ERR_INVALID, "edge scale has %u entries but the mesh has %u vertices", V, c->mesh.V);
+    c->edge = {};
+    rzi::Lent<float> edge;
+    HIP_TRY(edge.alloc(c->mesh.Vp));
+    HIP_TRY(hipMemsetAsync(edge, 0, (size_t)c->mesh.Vp * sizeof(float), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->edge, edge_size, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(edge, edge_size, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
+    c->edge = std::move(edge);
     return ensure_outputs(c);
 }
 
@@ -645,13 +665,13 @@ int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float 
     if (int r = static_unlocked(c, "rz_upload_sdef")) return r;
     if (n > 0) {
         if (!vert_idx || !c3 || !r0_3 || !r1_3) return fail(RZ_ERR_INVALID, "rz_upload_sdef: null arrays for %u entries", n);
-        if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its SDEF table");
+        if (c->mesh.V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its SDEF table");
         for (uint32_t k = 0; k < n; ++k) {
-            if (vert_idx[k] >= c->V) return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex index %u (entry %u) is outside the shard's %u vertices", vert_idx[k], k, c->V);
+            if (vert_idx[k] >= c->mesh.V) return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex index %u (entry %u) is outside the shard's %u vertices", vert_idx[k], k, c->mesh.V);
             if (k > 0 && vert_idx[k] <= vert_idx[k - 1])
                 return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex indices must be strictly ascending (entry %u: %u after %u)", k, vert_idx[k], vert_idx[k - 1]);
         }
-        const int64_t both = first_shared(vert_idx, n, c->qdef_idx_host);
+        const int64_t both = first_shared(vert_idx, n, c->qdef.idx_host);
         if (both >= 0) return fail(RZ_ERR_INVALID, "rz_upload_sdef: vertex %lld is in the QDEF table already (a vertex has one weight type)", (long long)both);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -665,9 +685,11 @@ int rz_upload_sdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx, const float 
     for (int a = 0; a < 3; ++a)
         for (int d = 0; d < 3; ++d)
             for (uint32_t k = 0; k < n; ++k) memcpy(&tab[(size_t)(1 + 3 * a + d) * n + k], &src[a][(size_t)k * 3 + d], 4);
-    if (int r = to_device(&c->sdef_tab, tab.data(), tab.size())) return r;
-    c->sdef_n = n;
-    c->sdef_idx_host.assign(vert_idx, vert_idx + n);
+    RzStatic::VertexTable t;
+    if (int r = to_device(t.tab, tab.data(), tab.size())) return r;
+    t.n = n;
+    t.idx_host.assign(vert_idx, vert_idx + n);
+    c->sdef = std::move(t);
     return RZ_OK;
 }
 
@@ -677,22 +699,24 @@ int rz_upload_qdef(rz_ctx *c, uint32_t n, const uint32_t *vert_idx)
     if (int r = static_unlocked(c, "rz_upload_qdef")) return r;
     if (n > 0) {
         if (!vert_idx) return fail(RZ_ERR_INVALID, "rz_upload_qdef: null array for %u entries", n);
-        if (c->V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its QDEF table");
+        if (c->mesh.V == 0) return fail(RZ_ERR_INVALID, "upload the mesh before its QDEF table");
         for (uint32_t k = 0; k < n; ++k) {
-            if (vert_idx[k] >= c->V) return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex index %u (entry %u) is outside the shard's %u vertices", vert_idx[k], k, c->V);
+            if (vert_idx[k] >= c->mesh.V) return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex index %u (entry %u) is outside the shard's %u vertices", vert_idx[k], k, c->mesh.V);
             if (k > 0 && vert_idx[k] <= vert_idx[k - 1])
                 return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex indices must be strictly ascending (entry %u: %u after %u)", k, vert_idx[k], vert_idx[k - 1]);
         }
-        const int64_t both = first_shared(vert_idx, n, c->sdef_idx_host);
+        const int64_t both = first_shared(vert_idx, n, c->sdef.idx_host);
         if (both >= 0) return fail(RZ_ERR_INVALID, "rz_upload_qdef: vertex %lld is in the SDEF table already (a vertex has one weight type)", (long long)both);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
     free_qdef(c);
     if (n == 0) return RZ_OK;
-    if (int r = to_device(&c->qdef_tab, vert_idx, (size_t)n)) return r;
-    c->qdef_n = n;
-    c->qdef_idx_host.assign(vert_idx, vert_idx + n);
+    RzStatic::VertexTable t;
+    if (int r = to_device(t.tab, vert_idx, (size_t)n)) return r;
+    t.n = n;
+    t.idx_host.assign(vert_idx, vert_idx + n);
+    c->qdef = std::move(t);
     return RZ_OK;
 }
 
@@ -706,7 +730,7 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
         free_ik(c);
         return RZ_OK;
     }
-    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4) return fail(RZ_ERR_INVALID, "IK acts on device-solved poses: call rz_upload_skeleton_topology first");
+    if (!c->fk.has_topology || c->fk.host.size() != (size_t)c->skel.B * 4) return fail(RZ_ERR_INVALID, "IK acts on device-solved poses: call rz_upload_skeleton_topology first");
     if (n_chains > 65535) return fail(RZ_ERR_INVALID, "rz_upload_ik: %u chains (at most 65535)", n_chains);
     if (!goal || !effector || !loops || !limit_angle || !link_off) return fail(RZ_ERR_INVALID, "rz_upload_ik: null chain arrays for %u chains", n_chains);
     for (uint32_t k = 0; k < n_chains; ++k)
@@ -714,10 +738,10 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
     if (link_off[0] != 0) return fail(RZ_ERR_INVALID, "rz_upload_ik: link offsets start at %u, not 0", link_off[0]);
     const uint32_t NL = link_off[n_chains];
     if (NL && (!link_bone || !link_limited || !link_min3 || !link_max3)) return fail(RZ_ERR_INVALID, "rz_upload_ik: null link arrays for %u links", NL);
-    const uint32_t B = c->B;
-    auto parent_of = [&](uint32_t b) { return (int32_t)c->fk_host[4 * (size_t)b].x; };
+    const uint32_t B = c->skel.B;
+    auto parent_of = [&](uint32_t b) { return (int32_t)c->fk.host[4 * (size_t)b].x; };
     auto append_of = [&](uint32_t b) -> int32_t {          // the bone whose local rotation b's local matrix reads, or -1 (fk_local_matrix)
-        const uint4 r = c->fk_host[4 * (size_t)b];
+        const uint4 r = c->fk.host[4 * (size_t)b];
         float ratio;
         memcpy(&ratio, &r.z, 4);
         return ((int32_t)r.y >= 0 && fabsf(fminf(1.0f, fmaxf(-1.0f, ratio))) > 1e-6f) ? (int32_t)r.y : -1;
@@ -772,7 +796,7 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
     // the overrides, which undoes the chain (IK chains whose bones are listed are not re-solved after physics). A goal may be listed.
     for (uint32_t k = 0; k < n_chains; ++k)
         for (uint32_t b : path[k])
-            if (std::find(c->af_bones.begin(), c->af_bones.end(), b) != c->af_bones.end())
+            if (std::find(c->af.bones.begin(), c->af.bones.end(), b) != c->af.bones.end())
                 return fail(RZ_ERR_UNSUPPORTED, "rz_upload_ik: bone %u on the path of chain %u is an after-physics bone (rz_upload_after_physics): the stage does not solve IK again", b, k);
     // solve order: ascending IK bone (stable). Stages: a chain comes after every earlier chain whose links move a bone it reads (goal,
     // effector — whose ancestors cover the path —, through parents or an append rotation), and not before an earlier chain that reads a
@@ -836,17 +860,19 @@ int rz_upload_ik(rz_ctx *c, uint32_t n_chains, const uint32_t *goal, const uint3
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_ik(c);
     drop_graph(c);
-    if (int r = to_device(&c->ik_chain, rec.data(), rec.size())) return r;
-    if (int r = to_device(&c->ik_path, pth.data(), pth.size())) return r;
-    if (int r = to_device(&c->ik_link, lnk.data(), lnk.size())) return r;
-    if (int r = to_device(&c->ik_stage_off, soff.data(), soff.size())) return r;
-    c->ik_n = n_chains; c->ik_stages = n_stages;
+    RzStatic::Ik t;                     // (a local: a failure on any array takes the others with it)
+    if (int r = to_device(t.chain, rec.data(), rec.size())) return r;
+    if (int r = to_device(t.path, pth.data(), pth.size())) return r;
+    if (int r = to_device(t.link, lnk.data(), lnk.size())) return r;
+    if (int r = to_device(t.stage_off, soff.data(), soff.size())) return r;
+    t.n = n_chains; t.stages = n_stages;
     // chain switches arrive in this call's chain order and travel in the device's: where each chain went
-    c->ik_on_path.assign(B, 0);
+    t.on_path.assign(B, 0);
     for (uint32_t k = 0; k < n_chains; ++k)
-        for (uint32_t b : path[k]) c->ik_on_path[b] = 1;
-    c->ik_dev_pos.assign(n_chains, 0u);
-    for (uint32_t i = 0; i < n_chains; ++i) c->ik_dev_pos[ord[by_stage[i]]] = i;
+        for (uint32_t b : path[k]) t.on_path[b] = 1;
+    t.dev_pos.assign(n_chains, 0u);
+    for (uint32_t i = 0; i < n_chains; ++i) t.dev_pos[ord[by_stage[i]]] = i;
+    c->ik = std::move(t);
     return RZ_OK;
 }
 
@@ -856,31 +882,33 @@ int rz_upload_after_physics(rz_ctx *c, uint32_t n, const uint32_t *bones)
     if (int r = static_unlocked(c, "rz_upload_after_physics")) return r;
     if (n == 0) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->af_n) c->fk_stale = c->fk_stale || c->ovr_count != 0;       // world matrices in memory carry the stage: rz_read_world solves again
+        if (c->af.n) c->fk_stale = c->fk_stale || c->ovr_count != 0;       // world matrices in memory carry the stage: rz_read_world solves again
         free_after(c);
         return RZ_OK;
     }
-    if (!c->has_topology || c->fk_host.size() != (size_t)c->B * 4)
+    if (!c->fk.has_topology || c->fk.host.size() != (size_t)c->skel.B * 4)
         return fail(RZ_ERR_INVALID, "rz_upload_after_physics acts on device-solved poses: call rz_upload_skeleton_topology first");
     if (!bones) return fail(RZ_ERR_INVALID, "rz_upload_after_physics: null list of %u bones", n);
     rzafter::Table t;
     std::string err;
-    if (rzafter::build(c->B, reinterpret_cast<const uint32_t *>(c->fk_host.data()), n, bones, t, err)) return fail(RZ_ERR_INVALID, "%s", err.c_str());
-    if (c->ik_n)
+    if (rzafter::build(c->skel.B, reinterpret_cast<const uint32_t *>(c->fk.host.data()), n, bones, t, err)) return fail(RZ_ERR_INVALID, "%s", err.c_str());
+    if (c->ik.n)
         for (uint32_t k = 0; k < n; ++k)
-            if (c->ik_on_path[bones[k]])
+            if (c->ik.on_path[bones[k]])
                 return fail(RZ_ERR_UNSUPPORTED, "rz_upload_after_physics: bone %u (entry %u) is a link or the effector of a resident IK chain, or lies on its path: the stage does not solve IK again", bones[k], k);
-    const size_t lds = rzafter::lds_bytes(c->B, n);
+    const size_t lds = rzafter::lds_bytes(c->skel.B, n);
     if (lds > 160 * 1024)
-        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %u entries x 1 B = %zu B of LDS (the limit is 160 KB = %d B)", c->B, n, lds, 160 * 1024);
+        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %u entries x 1 B = %zu B of LDS (the limit is 160 KB = %d B)", c->skel.B, n, lds, 160 * 1024);
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_after(c);
     drop_graph(c);
-    if (int r = to_device(&c->af_rec, t.rec.data(), (size_t)n * 3)) return r;
-    if (int r = to_device(&c->af_level_off, t.level_off.data(), t.level_off.size())) return r;
-    if (int r = to_device(&c->af_index, t.index.data(), t.index.size())) return r;
-    c->af_bones.assign(bones, bones + n);
-    c->af_n = n; c->af_levels = (uint32_t)t.levels;
+    RzStatic::After af;
+    if (int r = to_device(af.rec, t.rec.data(), (size_t)n * 3)) return r;
+    if (int r = to_device(af.level_off, t.level_off.data(), t.level_off.size())) return r;
+    if (int r = to_device(af.index, t.index.data(), t.index.size())) return r;
+    af.bones.assign(bones, bones + n);
+    af.n = n; af.levels = (uint32_t)t.levels;
+    c->af = std::move(af);
     if (c->ovr_count) c->fk_stale = true;       // world matrices and palettes in memory are the frame's without the stage: rz_read_world / rz_read_palette solve again
     return RZ_OK;
 }
@@ -889,9 +917,9 @@ int rz_upload_ik_keys(rz_ctx *c, uint32_t clip, const rz_ik_keys *keys)
 {
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_ik_keys")) return r;
-    if (!c->ik_n) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: no IK table is resident (rz_upload_ik names the chains the keys switch)");
-    if (clip != RZ_NO_CLIP && clip >= c->mo_clips) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: clip %u of %u", clip, c->mo_clips);
-    const uint32_t n = keys ? keys->n_keys : 0, nc = c->ik_n, W = (nc + 31) / 32;
+    if (!c->ik.n) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: no IK table is resident (rz_upload_ik names the chains the keys switch)");
+    if (clip != RZ_NO_CLIP && clip >= c->lib.clips) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: clip %u of %u", clip, c->lib.clips);
+    const uint32_t n = keys ? keys->n_keys : 0, nc = c->ik.n, W = (nc + 31) / 32;
     if (keys && n && (!keys->key_frame || !keys->key_enabled)) return fail(RZ_ERR_INVALID, "rz_upload_ik_keys: null key arrays for %u keys", n);
     for (uint32_t k = 0; k < n; ++k) {
         const float f = keys->key_frame[k];
@@ -905,11 +933,11 @@ int rz_upload_ik_keys(rz_ctx *c, uint32_t clip, const rz_ik_keys *keys)
         set.bits.assign((size_t)n * W, 0u);
         for (uint32_t k = 0; k < n; ++k)
             for (uint32_t ch = 0; ch < nc; ++ch)
-                if (keys->key_enabled[(size_t)k * nc + ch]) { const uint32_t d = c->ik_dev_pos[ch]; set.bits[(size_t)k * W + (d >> 5)] |= 1u << (d & 31u); }
+                if (keys->key_enabled[(size_t)k * nc + ch]) { const uint32_t d = c->ik.dev_pos[ch]; set.bits[(size_t)k * W + (d >> 5)] |= 1u << (d & 31u); }
     }
     // host data of the pose calls alone: no frame in flight reads it, nothing to drain
     if (clip == RZ_NO_CLIP) { c->ik_keys_an = std::move(set); return RZ_OK; }
-    if (c->ik_keys_mo.empty()) { if (!set.resident) return RZ_OK; c->ik_keys_mo.resize(c->mo_clips); }
+    if (c->ik_keys_mo.empty()) { if (!set.resident) return RZ_OK; c->ik_keys_mo.resize(c->lib.clips); }
     c->ik_keys_mo[clip] = std::move(set);
     bool any = false;
     for (const RzIkKeySet &s : c->ik_keys_mo) any = any || s.resident;
