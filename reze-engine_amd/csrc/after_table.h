@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "lds_layout.h"
+
 #pragma GCC visibility push(hidden)
 namespace rzafter {
 
@@ -90,8 +92,8 @@ inline int build(uint32_t B, const uint32_t *bone_rec, uint32_t n, const uint32_
     return 0;
 }
 
-// dynamic LDS of rz_fk_after_kernel: the instance's world rows, 48 B per bone, and one skip byte per entry
-inline size_t lds_bytes(uint32_t B, uint32_t n) { return (size_t)B * 48 + (((size_t)n + 15) & ~(size_t)15); }
+// dynamic LDS of rz_fk_after_kernel: the instance's world rows, 48 B per bone, and one skip byte per entry (lds_layout.h, where the kernel carves it)
+inline size_t lds_bytes(uint32_t B, uint32_t n) { return rzlds::after((int)B, (int)n).total(); }
 
 }  // namespace rzafter
 #pragma GCC visibility pop

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lds_layout.h"
+
 // rz_prep_kernel: palette = rows 0..2 of world * inverseBind (engine/src/engine.ts:926-928) and the
 // ordered list of morphs with a non-zero weight.
 struct RzPrepParams {
@@ -293,7 +295,6 @@ struct RzQdefParams {
     int chunks;                 // 256-vertex chunks of the table one workgroup takes behind one conversion of the skeleton (>= 1)
     int pad_;
 };                              // (no padding: frame_signature() hashes the struct)
-size_t rz_qdef_lds_bytes(int B);       // dynamic LDS of the pass: the skeleton's dual quaternions, 32 B per bone
 hipError_t rz_launch_qdef(const RzQdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st);
 
 // rz_motion_kernel<P> (kernels/motion.hip): the local pose of every instance from a library of resident motions, in front of the frame. One
@@ -386,32 +387,32 @@ struct RzVariant {
     bool fast;   // fused palette + kernarg morph list (single instance)
 };
 
-// LDS the hierarchy solve needs behind the palette rows: per bone 48 B (local rotation | record | bind translation, then the
-// second matrix buffer of the doubling rounds) + 12 B (local translation), 16-byte rounded
-__host__ __device__ inline size_t rz_fk_scratch_bytes(int B) { return ((size_t)B * 60 + 15) & ~(size_t)15; }
-
-// the solve with the IK stage: the pose's morph weights in LDS (bone morphs), rounded so that the matrix buffer behind them is 16-byte aligned
-__host__ __device__ inline size_t rz_fk_mw_bytes(const RzFkParams &p)
+// Every kernel's dynamic LDS is laid out in lds_layout.h (rzlds); what follows maps parameter blocks onto its scalars.
+// the pose's morph weights the solve keeps in LDS for the bone morphs (rzlds::solve: n_weights): none without bone morphs
+__host__ __device__ inline int rz_fk_mw_count(const RzFkParams &p)
 {
     if (!p.bm_off) return 0;
     const int m = p.bm_M > p.sample.M ? p.bm_M : p.sample.M;
-    return ((size_t)(m > 1 ? m : 1) * 4 + 15) & ~(size_t)15;
+    return m > 1 ? m : 1;
+}
+// the generic frame's layout for a variant: the lists are in LDS for sparse targets and for a dense frame behind rz_prep_kernel / the fused
+// solve; a wave step is 256 / S vertices of 3 planes (9 with the rest geometry through LDS); pieces are staged for sparse targets only
+inline rzlds::Frame rz_deform_layout(int B, int M, int Mpad, uint32_t out_cap, uint32_t sp_cap, bool fused, const RzVariant &v)
+{
+    return rzlds::frame(B, (v.mode == 2 || (!v.fast && v.mode == 1)) ? Mpad : 0, v.geo ? 9 : 3, 256 / v.S, out_cap, v.mode == 2 ? sp_cap : 0, fused, M);
 }
 
 hipError_t rz_launch_prep(const RzPrepParams &p, uint32_t instances, hipStream_t st);
 // The hierarchy solve (kernels/front.hip: rz_fk_kernel<Stage...>) with the stages `s` lists: one launcher picks the instantiation, whose
 // kernel arguments carry the blocks of the stages that are on and nothing else.
 hipError_t rz_launch_fk(const RzFkParams &p, const RzFkStages &s, uint32_t instances, hipStream_t st);
-// its dynamic LDS: palette rows + solve scratch + the pose's morph weights; with the IK stage region X of the solve stays alive across
-// the doubling rounds, which get a second matrix buffer of their own: 48 B per bone more
-size_t rz_fk_lds_bytes(const RzFkParams &p, const RzFkStages &s);
+inline size_t rz_fk_lds_bytes(const RzFkParams &p, const RzFkStages &s) { return rzlds::solve(p.B, s.ik.n_chains != 0, rz_fk_mw_count(p)).total(); }      // its dynamic LDS
 // the after-physics stage (s.af) behind the solve, on the same stream (kernels/after.hip: rz_fk_after_kernel): reads the world matrices
 // the solve left in memory and writes the listed bones' world matrices and palette rows again
 hipError_t rz_launch_fk_after(const RzFkParams &p, const RzAfterParams &a, uint32_t instances, hipStream_t st);
-size_t rz_fk_after_lds_bytes(const RzFkParams &p, const RzAfterParams &a);
 hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
                             uint32_t instances, hipStream_t st);
-size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v);
+inline size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v) { return rz_deform_layout(p.B, p.M, p.Mpad, p.out_cap, p.sp_cap, p.fk_on != 0, v).total(); }
 // the two single-mesh frame kernels behind rz_launch_deform (kernels/deform_dense.hip: v.mode == 1; kernels/deform_small.hip: modes 0 / 2)
 hipError_t rz_launch_deform_dense(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st);
 hipError_t rz_launch_deform_small(const RzDeformParams &p, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st);
@@ -433,10 +434,6 @@ struct RzSubFk {
 };
 hipError_t rz_launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
                                        int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs = false);
-size_t rz_skin_instances_fk_lds_bytes(int G, uint32_t closure, uint32_t named, uint32_t morph_pad = 0);
-// LDS bytes of the instanced skin kernel: G poses of `bones` staged bones (the whole skeleton, or the largest run subset);
-// morph_pad (the MORPH kernels) = Mpad: the group's morph weights behind them, G x Mpad x 4 B
-size_t rz_skin_instances_lds_bytes(int G, uint32_t bones, bool dma, bool subsets, uint32_t morph_pad = 0);
 // per vertex run of `per` vertices: the ascending list of bones its vertices name + the joints rewritten as slots of it
 hipError_t rz_launch_run_subsets(const uint32_t *j01, const uint32_t *j23, uint32_t v_lim, uint32_t per, uint32_t runs, uint32_t B,
                                  uint16_t *list, uint32_t *count, uint32_t *rj01, uint32_t *rj23, hipStream_t st);

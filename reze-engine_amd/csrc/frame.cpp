@@ -20,13 +20,13 @@ int launch_fk(rz_ctx *c, hipStream_t st, bool overrides)
     const RzFkParams fp = fk_params(c, overrides);
     const RzFkStages ss = solve_stages(c, overrides);
     const size_t lds = rz_fk_lds_bytes(fp, ss);
-    if (lds > 160 * 1024)
+    if (lds > rzlds::kCuLds)
         return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the hierarchy solve%s on the device: %u bones need %zu B of LDS (%s; the limit is 160 KB)", ss.ik.n_chains ? " with IK" : "", c->skel.B, lds,
                     ss.ik.n_chains ? "156 B per bone + the pose's morph weights: the IK stage keeps the local pose alive beside both matrix buffers" : "108 B per bone + the pose's morph weights");
     HIP_TRY(rz_launch_fk(fp, ss, c->I, st));
     if (ss.af.n) {
-        const size_t after_lds = rz_fk_after_lds_bytes(fp, ss.af);
-        if (after_lds > 160 * 1024)
+        const size_t after_lds = rzafter::lds_bytes(c->skel.B, (uint32_t)ss.af.n);
+        if (after_lds > rzlds::kCuLds)
             return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %d entries x 1 B = %zu B of LDS (the limit is 160 KB)", c->skel.B, ss.af.n, after_lds);
         HIP_TRY(rz_launch_fk_after(fp, ss.af, c->I, st));
     }
@@ -80,7 +80,7 @@ int launch_deform(rz_ctx *c, const Plan &pl)
         return RZ_OK;
     }
     size_t lds = rz_deform_lds_bytes(p, pl.v);
-    if (lds > 160 * 1024) return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the LDS palette (%zu B)", lds);
+    if (lds > rzlds::kCuLds) return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the LDS palette (%zu B)", lds);
     HIP_TRY(rz_launch_deform(p, c->pl.cur.ml, pl.v, pl.grid_x + (p.pf_src ? 1u : 0u), c->I, c->stream));
     c->palette_stale = false;                          // this frame's palette is in memory: written by its front kernels or by workgroup 0
     if (p.world_copy) c->pl.cur.world_resident = true;        // workgroup 0 of that launch left the pose in the device block

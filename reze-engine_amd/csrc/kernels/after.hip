@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(kBlock) rz_fk_after_kernel(const RzFkParams p,
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4 *F = reinterpret_cast<float4 *>(smem);                       // [B][3] world rows 0..2
-    unsigned char *skip = smem + (size_t)p.B * 48;                      // [n] 1 = the entry's bone is overridden in this instance
+    unsigned char *skip = smem + rzlds::after(p.B, a.n).skip_off;                     // [n] 1 = the entry's bone is overridden in this instance
     const int tid = threadIdx.x, inst = blockIdx.x;
     const float4 *lq = p.local_q + (size_t)inst * p.B;
     const float *glt = p.local_t ? p.local_t + (size_t)inst * p.B * 3 : nullptr;
@@ -217,17 +217,12 @@ __global__ void __launch_bounds__(kBlock) rz_fk_after_kernel(const RzFkParams p,
 
 }  // namespace
 
-size_t rz_fk_after_lds_bytes(const RzFkParams &p, const RzAfterParams &a) { return (size_t)p.B * 48 + (((size_t)a.n + 15) & ~(size_t)15); }
-
 hipError_t rz_launch_fk_after(const RzFkParams &p, const RzAfterParams &a, uint32_t instances, hipStream_t st)
 {
-    const size_t lds = rz_fk_after_lds_bytes(p, a);
+    const size_t lds = rzlds::after(p.B, a.n).total();
     // (the host checks the LDS first and says why: launch_fk in frame.cpp; the stage walks the override table and reads the solve's output)
-    if (lds > 160 * 1024 || !a.rec || !a.level_off || !a.index || a.n <= 0 || a.n_levels <= 0 || !p.ovr_off || !p.world || !p.palette) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_fk_after_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (lds > rzlds::kCuLds || !a.rec || !a.level_off || !a.index || a.n <= 0 || a.n_levels <= 0 || !p.ovr_off || !p.world || !p.palette) return hipErrorInvalidValue;
+    if (hipError_t e = rz_opt_in_lds(rz_fk_after_kernel, lds)) return e;
     hipLaunchKernelGGL(rz_fk_after_kernel, dim3(instances), dim3(kBlock), lds, st, p, a);
     return hipGetLastError();
 }

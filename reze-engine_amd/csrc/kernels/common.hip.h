@@ -31,6 +31,15 @@
 namespace {
 
 constexpr int kBlock = 256;
+static_assert(kBlock / 64 == rzlds::kFrameWaves, "lds_layout.h lays the generic frame out for the waves of a kBlock workgroup");
+
+// Dynamic LDS above what a kernel gets unasked (lds_layout.h: kOptIn): the launcher opts its kernel in. Every launcher calls this before
+// it launches; nothing else sets the attribute.
+template <class K> inline hipError_t rz_opt_in_lds(K kernel, size_t lds)
+{
+    if (lds <= rzlds::kOptIn) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
 
 // Ablation switches for profiling experiments exist only in the tools-only build (make ablate ->
 // tools/ablate/libreze_deform_ablate.so, -DRZ_ABLATE). In the shipped library RZ_DBG is the constant 0, the branches

@@ -90,6 +90,7 @@ __global__ void __launch_bounds__(BLOCK) RZ_CROWD_KERNEL(const uint32_t *k_sub_c
     const int ns = SUB ? (int)(k_bf >> 18) : 0;
     const uint16_t *sub = SUB ? k_sub_list + (size_t)wg_run * kB : nullptr;      // (the lists' stride is the bone count)
     const int lrows = SUB ? ns * 3 : rows;          // float4 per pose of the finished LDS palettes
+    // (= smem + rzlds::crowd(G, ns, ...).staged_off; read from the layout it renames registers in the MORPH subset kernels, so the carve stays)
     float4 *stage = pal + (size_t)G * ns * 3;       // SUB, one-launch frame: staged world matrices sit behind the palette region
     if constexpr (SUB) {
         // prep-kernel / device-FK path (dma): the listed bones' finished rows, 3 float4 per bone, straight to their place.
@@ -165,9 +166,9 @@ __global__ void __launch_bounds__(BLOCK) RZ_CROWD_KERNEL(const uint32_t *k_sub_c
         if constexpr (MORPH) { rb0 = p.sp_ptr[v]; rb1 = p.sp_ptr[v + 1]; }
     }
     if constexpr (MORPH) {
-        // the weights sit behind the kernel's other LDS (rz_skin_instances_lds_bytes: staged bones x 48 / 64 / 112 B per pose); nothing
+        // the weights sit behind the kernel's other LDS (rzlds::crowd: staged bones x 48 / 64 / 112 B per pose); nothing
         // in front of the barrier below reads or writes that region
-        s_mw = reinterpret_cast<float *>(smem + (size_t)G * (SUB ? ns : kB) * (k_dma ? 48 : (SUB ? 112 : 64)));
+        s_mw = reinterpret_cast<float *>(smem + rzlds::crowd_poses_bytes(G, SUB ? ns : kB, k_dma, SUB));      // = crowd(...).weights_off
         stage_morph_weights<BLOCK>(s_mw, p.morph_w + (size_t)inst0 * p.M, ng, p.M, p.Mpad, tid);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // palettes / world matrices (and the first vertex) have landed
@@ -296,7 +297,9 @@ __global__ void __launch_bounds__(BLOCK) RZ_CROWD_FK_KERNEL(const uint32_t *k_cn
     // rz_skin_instances_kernel — which takes two dependent scalar loads out of the front)
     const int nc = rec_stride;
     const uint4 *recs = k_rec + (size_t)wg_run * rec_stride * kSubFkWords;
-    float4 *mA = reinterpret_cast<float4 *>(smem), *mB = mA + (size_t)G * nc * 3, *pal = mB + (size_t)G * nc * 3;
+    const int ns = (int)(k_g >> 18);                   // named bones = palette slots of a run (the longest list's)
+    const rzlds::CrowdFront L = rzlds::crowd_front(G, nc, ns, 0);
+    float4 *mA = reinterpret_cast<float4 *>(smem), *mB = mA + L.buffer_rows, *pal = mB + L.buffer_rows;
     // this thread's work items e = tid, tid + BLOCK: (pose g, closure slot c); past the end the LAST item is re-read (unpredicated loads)
     constexpr int NIT = 2;
     const int n_items = ng * nc;
@@ -331,7 +334,6 @@ __global__ void __launch_bounds__(BLOCK) RZ_CROWD_FK_KERNEL(const uint32_t *k_cn
         j01 = jp01[v]; j23 = jp23[v]; wq = p.weights[v];
         if constexpr (MORPH) { rb0 = p.sp_ptr[v]; rb1 = p.sp_ptr[v + 1]; }
     }
-    const int ns = (int)(k_g >> 18);                   // named bones = palette slots of a run (the longest list's)
     const int lrows = ns * 3;
     // ---- the pose of every item: uploaded rotations (+ translations), or the motion sampled at the instance's frame ----
     float4 q[NIT], apq[NIT], ib0[NIT], ib1[NIT], ib2[NIT], ib3[NIT];
@@ -402,8 +404,8 @@ __global__ void __launch_bounds__(BLOCK) RZ_CROWD_FK_KERNEL(const uint32_t *k_cn
     }
     if constexpr (MORPH) {
         // the pose's morph weights are in device memory before this frame (the plan keeps rz_fk_kernel in front of a sampled pose, which
-        // writes them); behind the two matrix buffers and the palettes (rz_skin_instances_fk_lds_bytes)
-        s_mw = reinterpret_cast<float *>(smem + (size_t)G * (2 * (size_t)nc + ns) * 48);
+        // writes them); behind the two matrix buffers and the palettes (rzlds::crowd_front)
+        s_mw = reinterpret_cast<float *>(smem + L.weights_off);
         stage_morph_weights<BLOCK>(s_mw, p.morph_w + (size_t)inst0 * p.M, ng, p.M, p.Mpad, tid);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the first vertex has landed)
@@ -572,17 +574,6 @@ __global__ void __launch_bounds__(kBlock) rz_run_subsets_kernel(const uint32_t *
 
 }  // namespace
 
-#if !RZ_CROWD_MORPH
-size_t rz_skin_instances_lds_bytes(int G, uint32_t bones, bool dma, bool subsets, uint32_t morph_pad)
-{
-    // finished palettes are 48 B per (pose, bone). One-launch frame: the whole-palette form stages the world matrices in
-    // the palette region's place (64-byte slots, re-packed in place); the subset form stages them behind it (48 + 64).
-    // morph_pad (MORPH kernels): the group's morph weights behind all that, Mpad floats per pose.
-    const size_t per = dma ? 48 : (subsets ? 112 : 64);
-    return (size_t)G * bones * per + (size_t)G * morph_pad * 4;
-}
-#endif
-
 template <int BLOCK>
 static hipError_t launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
                                         bool nts, size_t lds, hipStream_t st)
@@ -591,10 +582,7 @@ static hipError_t launch_skin_instances(const RzDeformParams &p, int G, int n_in
     auto k = sub ? (nts ? RZ_CROWD_KERNEL<BLOCK, true, true> : RZ_CROWD_KERNEL<BLOCK, false, true>)
                  : (nts ? RZ_CROWD_KERNEL<BLOCK, true, false> : RZ_CROWD_KERNEL<BLOCK, false, false>);
     if (RZ_CROWD_MORPH && (!p.sp_ptr || !p.sp_entries || !p.morph_w || p.M <= 0 || p.Mpad < p.M)) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
     dim3 grid(grid_x, (n_inst + G - 1) / G);
     if (grid.x > 0xffffu || grid.y > 0xffffu || p.B > 0xffff || (sub && (p.sub_stride != p.B || p.sub_max <= 0 || p.sub_max > 0x3fff))) return hipErrorInvalidValue;      // (k_grid packs both; the lists' stride is the bone count; k_bf carries their padded length in 14 bits)
     // leading arguments = what the front of a workgroup needs, preloaded into SGPRs (see the kernel)
@@ -604,19 +592,12 @@ static hipError_t launch_skin_instances(const RzDeformParams &p, int G, int n_in
     return hipGetLastError();
 }
 
-#if !RZ_CROWD_MORPH
-size_t rz_skin_instances_fk_lds_bytes(int G, uint32_t closure, uint32_t named, uint32_t morph_pad) { return (size_t)G * (2 * (size_t)closure + named) * 48 + (size_t)G * morph_pad * 4; }
-#endif
-
 template <int BLOCK>
 static hipError_t launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x, bool nts,
                                            size_t lds, hipStream_t st)
 {
     auto k = nts ? RZ_CROWD_FK_KERNEL<BLOCK, true> : RZ_CROWD_FK_KERNEL<BLOCK, false>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
     dim3 grid(grid_x, (n_inst + G - 1) / G);
     const bool sampled = p.fk.sample.frames != nullptr;
     // (MORPH: the front stages the pose's morph weights out of memory; a sampled pose's are written by rz_fk_kernel, which this frame does not have)
@@ -690,12 +671,9 @@ hipError_t rz_launch_skin_instances_reg(const RzDeformParams &p, int n_inst, int
 {
 #ifdef RZ_ALL_VARIANTS
     constexpr int KV = 8;
-    const size_t lds = (size_t)2 * p.B * 48;
+    const size_t lds = (size_t)2 * p.B * 48;         // (the 2-deep palette ring: its only spelling, the kernel indexes the ring by slot)
     auto k = nts ? rz_skin_instances_reg_kernel<KV, true> : rz_skin_instances_reg_kernel<KV, false>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
     dim3 grid(grid_x, (n_inst + poses_per_wg - 1) / poses_per_wg);
     hipLaunchKernelGGL(k, grid, dim3(kBlock), lds, st, p, n_inst, poses_per_wg);
     return hipGetLastError();

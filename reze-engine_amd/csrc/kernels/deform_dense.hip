@@ -139,9 +139,10 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
     };
 
     // ---- from here on the kernel reads `p` (scalar loads of the kernel arguments: the loads above are in flight under them) ----
-    uint32_t *s_idx = reinterpret_cast<uint32_t *>(smem + (size_t)p.B * 48);   // Mpad   (LDS_LIST)
-    float *s_w = reinterpret_cast<float *>(s_idx + (LDS_LIST ? p.Mpad : 0));
-    float *scratch_all = s_w + (LDS_LIST ? p.Mpad : 0);                   // 16-B aligned: Mpad % 4 == 0
+    const rzlds::Frame L = rzlds::frame(p.B, LDS_LIST ? p.Mpad : 0, NPL, VW, p.out_cap, 0);       // lds_layout.h: palette | lists | work
+    uint32_t *s_idx = reinterpret_cast<uint32_t *>(smem + L.list_off);         // Mpad   (LDS_LIST)
+    float *s_w = reinterpret_cast<float *>(s_idx + L.pad);
+    float *scratch_all = s_w + L.pad;                                     // 16-B aligned: Mpad % 4 == 0
     const uint64_t st_tagv = spec ? *p.st_tag : 0ull;                   // requested here, compared later (workgroup-uniform)
     int fused_count = 0;
     if (!FAST && (FKV == 1 || FKV == 2 || p.fk_on)) {
@@ -201,7 +202,7 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
 
     // write batching (deform_parts.hip.h: flush_parked)
     const uint32_t cap = p.out_cap;
-    float *ob_pos = scratch_all + (size_t)(kBlock / 64) * NPL * VW + (size_t)wave * cap * 6;
+    float *ob_pos = scratch_all + L.scratch + (size_t)wave * cap * 6;
     float *ob_nrm = ob_pos + (size_t)cap * 3;
     uint32_t ob_fill = 0;               // vertices parked
     size_t ob_v0 = q_begin * 4;         // global vertex index of the first parked vertex
@@ -417,10 +418,7 @@ static hipError_t launch_one(const RzDeformParams &p, const RzMorphList &ml, dim
     }
     auto k = rz_deform_dense_kernel<S, U, NT, NTS, GEO, FAST, FKV, Q24>;
     if (p.B > 0xffff) return hipErrorInvalidValue;      // k_bf carries the bone count in 16 bits (the 48 B per bone LDS palette keeps it far below today)
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
     // the leading arguments (kernel-argument preload: deform_parts.hip.h) repeat fields of `p`; k_world is the pose the kernel asks for
     // FIRST — the copy a helper may have staged when the frame looks for one, else p.world
     // (!FAST: the hierarchy's static block and the motion's morph count ride in the two matrix slots, deform_parts.hip.h)

@@ -161,7 +161,7 @@ __device__ __forceinline__ float *fused_hierarchy_prologue(const RzFkParams &fk,
 {
     const int tid = threadIdx.x;
     unsigned char *fscr = reinterpret_cast<unsigned char *>(work);
-    float *lds_mw = reinterpret_cast<float *>(fscr + rz_fk_scratch_bytes(fk.B));
+    float *lds_mw = reinterpret_cast<float *>(fscr + rzlds::solve_scratch(fk.B));
     const bool sampled = KIND == 2 || (KIND == 0 && (fk.sample.frames != nullptr || fk.sample.frames_inline));
     const bool fspec = KIND != 2 && st_tag != nullptr;
     const uint64_t ftag = fspec ? *st_tag : 0ull;

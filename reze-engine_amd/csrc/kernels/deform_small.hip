@@ -160,9 +160,10 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_small_kernel(const float 
     if (PRE && q_begin < q_end) issue(q_begin);
 
     // ---- from here on the kernel reads `p` (scalar loads of the kernel arguments: the loads above are in flight under them) ----
-    uint32_t *s_idx = reinterpret_cast<uint32_t *>(smem + (size_t)p.B * 48);   // Mpad   (LDS_LIST)
-    float *s_w = reinterpret_cast<float *>(s_idx + (LDS_LIST ? p.Mpad : 0));
-    float *scratch_all = s_w + (LDS_LIST ? p.Mpad : 0);                   // 16-B aligned: Mpad % 4 == 0
+    const rzlds::Frame L = rzlds::frame(p.B, LDS_LIST ? p.Mpad : 0, NPL, VW, p.out_cap, p.sp_cap);       // lds_layout.h: palette | lists | work
+    uint32_t *s_idx = reinterpret_cast<uint32_t *>(smem + L.list_off);         // Mpad   (LDS_LIST)
+    float *s_w = reinterpret_cast<float *>(s_idx + L.pad);
+    float *scratch_all = s_w + L.pad;                                     // 16-B aligned: Mpad % 4 == 0
     const uint64_t st_tagv = spec ? *p.st_tag : 0ull;                   // requested here, compared later (workgroup-uniform)
     const bool staged_now = MODE == 2 && spec && st_tagv == p.st_expect;
     const float *morph_w_in = (staged_now && p.st_morph_w) ? p.st_morph_w : p.morph_w;
@@ -250,9 +251,9 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_small_kernel(const float 
 
     // write batching (deform_parts.hip.h: flush_parked)
     const uint32_t cap = p.out_cap;
-    float *ob_pos = scratch_all + (size_t)(kBlock / 64) * NPL * VW + (size_t)wave * cap * 6;
+    float *ob_pos = scratch_all + L.scratch + (size_t)wave * cap * 6;
     float *ob_nrm = ob_pos + (size_t)cap * 3;
-    float *sp_all = scratch_all + (size_t)(kBlock / 64) * NPL * VW + (size_t)(kBlock / 64) * cap * 6;      // MODE 2: 4 x sp_cap staged CSR entries (16-byte aligned: every term is a multiple of 4 floats)
+    float *sp_all = scratch_all + L.scratch + L.parked;      // MODE 2: 4 x sp_cap staged CSR entries (16-byte aligned: every term is a multiple of 4 floats)
     uint32_t ob_fill = 0;               // vertices parked
     size_t ob_v0 = q_begin * 4;         // global vertex index of the first parked vertex
     auto flush_out = [&]() {
@@ -437,10 +438,7 @@ static hipError_t launch_one(const RzDeformParams &p, dim3 grid, size_t lds, hip
     }
     auto k = rz_deform_small_kernel<S, MODE, NTS, GEO, FAST, FKV>;
     if (p.B > 0xffff) return hipErrorInvalidValue;      // k_bf carries the bone count in 16 bits
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
     // (!FAST: the hierarchy's static block and the motion's morph count ride in the two matrix slots, deform_parts.hip.h)
     const float *k_world = FAST ? (p.st_tag ? p.st_world : p.world) : (p.fk_on ? reinterpret_cast<const float *>(p.fk.bone_rec) : nullptr);
     const float *k_inv_bind = FAST ? p.inv_bind : reinterpret_cast<const float *>((uintptr_t)(p.fk_on ? p.fk.sample.M : 0));

@@ -400,7 +400,7 @@ __device__ __forceinline__ void fk_palette_rows(const float4 w0, const float4 w1
 // a 12-level tree (4 radix-2 rounds of ~0.38 us each in round 4, six barrier-separated levels before that) — each ONE LDS latency,
 // three products and a barrier. The products are associated differently from the reference's parent-first recursion: same f32
 // error class, ~1e-7 per product (tests/test_gpu_round4.py: test_pointer_doubling_hierarchy_solve, against float64).
-// LDS behind `scr`: rz_fk_scratch_bytes(B) = B x (48 + 12) bytes. Ends with a barrier.
+// LDS behind `scr`: rzlds::solve_scratch(B) (lds_layout.h) = B x (48 + 12) bytes. Ends with a barrier.
 // KIND specialises the body at compile time for the two common single-character poses (the deform kernels' fused frame, round 5): the
 // generic form carries every feature behind workgroup-uniform branches — 47 KB of code in front of a 10 KB deform kernel, of which a frame
 // executes every instruction once. KIND 1 = an uploaded pose, KIND 2 = a sampled pose, both PLAIN: no physics overrides,

@@ -60,10 +60,12 @@ __global__ void __launch_bounds__(kBlock) rz_fk_kernel(const uint4 *k_rec, const
                    SW = (std::is_same<Stage, RzIkSwitchParams>::value || ...);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FkEarly early = fk_issue_static(k_rec, (int)k_B, (int)k_M, (int)threadIdx.x);
-    unsigned char *scr = smem + (size_t)p.B * 48;
-    unsigned char *mw = scr + rz_fk_scratch_bytes(p.B);
+    // (rzlds::solve's first two regions by the scalars it is built from: read out of the struct, the same sizes moved an instruction of every instantiation)
+    unsigned char *scr = smem + rzlds::palette_bytes(p.B);
+    unsigned char *mw = scr + rzlds::solve_scratch(p.B);
+    const rzlds::Solve L = rzlds::solve(p.B, IK, rz_fk_mw_count(p));
     fk_solve<false, 0, IK, FOLLOW, SW>(p, early, (int)blockIdx.x, reinterpret_cast<float4 *>(smem), scr, reinterpret_cast<float *>(mw), true, 0ull, nullptr,
-                                       fk_stage_arg<RzIkParams>(stage...), IK ? reinterpret_cast<float4 *>(mw + rz_fk_mw_bytes(p)) : nullptr,
+                                       fk_stage_arg<RzIkParams>(stage...), IK ? reinterpret_cast<float4 *>(mw + L.weights) : nullptr,
                                        fk_stage_arg<RzFollowParams>(stage...), fk_stage_arg<RzIkSwitchParams>(stage...));
 }
 
@@ -174,22 +176,9 @@ hipError_t rz_launch_prep(const RzPrepParams &p, uint32_t instances, hipStream_t
     return hipGetLastError();
 }
 
-// Dynamic LDS of the solve. Without IK: palette rows + solve scratch + the pose's morph weights as they are. With IK region X of the solve
-// stays alive across the doubling rounds, which get a second matrix buffer of their own, 48 B per bone more, behind the ROUNDED weights.
-size_t rz_fk_lds_bytes(const RzFkParams &p, const RzFkStages &s)
-{
-    size_t lds = (size_t)p.B * 48 + rz_fk_scratch_bytes(p.B);
-    if (s.ik.n_chains) return lds + rz_fk_mw_bytes(p) + (size_t)p.B * 48;
-    if (p.bm_off) lds += (size_t)std::max(std::max(p.bm_M, p.sample.M), 1) * 4;      // the pose's morph weights, for the bone morphs
-    return lds;
-}
-
 template <class... Stage> static hipError_t fk_launch(const RzFkParams &p, size_t lds, uint32_t instances, hipStream_t st, const Stage &...stage)
 {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_fk_kernel<Stage...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(rz_fk_kernel<Stage...>, lds)) return e;
     hipLaunchKernelGGL(rz_fk_kernel<Stage...>, dim3(instances), dim3(kBlock), lds, st, p.bone_rec, (uint32_t)p.B, (uint32_t)p.sample.M, p, stage...);
     return hipGetLastError();
 }
@@ -200,7 +189,7 @@ hipError_t rz_launch_fk(const RzFkParams &p, const RzFkStages &s, uint32_t insta
 {
     const bool ik = s.ik.n_chains != 0, fo = s.fo.off != nullptr, sw = s.sw.words != 0;
     const size_t lds = rz_fk_lds_bytes(p, s);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;      // (the host checks first and says why: launch_fk in frame.cpp)
+    if (lds > rzlds::kCuLds) return hipErrorInvalidValue;      // (the host checks first and says why: launch_fk in frame.cpp)
     if (ik && (!s.ik.chain || s.ik.n_stages <= 0)) return hipErrorInvalidValue;
     // switches belong to an IK table; words in the arguments serve one instance only
     if (sw && (!ik || s.sw.words != (s.ik.n_chains + 31) / 32 || (!s.sw.mask && (instances != 1 || s.sw.words > kRzIkSwInline)))) return hipErrorInvalidValue;
@@ -246,16 +235,6 @@ hipError_t rz_launch_pack_skinning(const uint16_t *joints4, const uint8_t *weigh
     hipLaunchKernelGGL(rz_pack_skinning_kernel, dim3((n + 255) / 256), dim3(256), 0, st, joints4, weights4, n,
                        j01, j23, wq);
     return hipGetLastError();
-}
-
-size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v)
-{
-    const size_t vw = 256 / v.S;   // vertices per wave per tile
-    size_t scratch = (size_t)(kBlock / 64) * (v.geo ? 9 : 3) * vw * 4;
-    const size_t list = (v.mode == 2 || (!v.fast && v.mode == 1)) ? (size_t)p.Mpad * 8 : 0;
-    size_t work = scratch + (size_t)(kBlock / 64) * p.out_cap * 24 + (v.mode == 2 ? (size_t)(kBlock / 64) * p.sp_cap * 16 : 0);     // sparse: staged CSR pieces
-    if (p.fk_on) work = std::max(work, rz_fk_scratch_bytes(p.B) + (size_t)std::max(p.M, 1) * 4 + 16);   // the fused solve's scratch aliases it
-    return (size_t)p.B * 48 + list + work;
 }
 
 uint32_t rz_quads_per_tile(int S) { return (kBlock / 64) * (64 / S); }

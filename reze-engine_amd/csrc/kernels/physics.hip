@@ -750,10 +750,7 @@ template <int BLOCK, bool OWN, int CONTACT, bool LSPRING, bool ALIGN>
 hipError_t launch(const RzPhysicsParams &p, uint32_t instances, size_t lds, hipStream_t st)
 {
     auto k = rz_physics_kernel<BLOCK, OWN, CONTACT, LSPRING, ALIGN>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
     hipLaunchKernelGGL(k, dim3(instances), dim3(BLOCK), lds, st, p);
     return hipGetLastError();
 }

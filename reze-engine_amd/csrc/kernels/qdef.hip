@@ -148,17 +148,12 @@ __global__ void __launch_bounds__(kBlock) rz_qdef_kernel(const RzQdefParams p, c
 
 }  // namespace
 
-size_t rz_qdef_lds_bytes(int B) { return (size_t)B * 2 * sizeof(float4); }
-
 hipError_t rz_launch_qdef(const RzQdefParams &p, const RzMorphList &ml, uint32_t instances, hipStream_t st)
 {
     if (p.n == 0 || instances == 0) return hipSuccess;
     if (p.chunks < 1 || p.B < 1) return hipErrorInvalidValue;
-    const size_t lds = rz_qdef_lds_bytes(p.B);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rz_qdef_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    const size_t lds = rzlds::qdef(p.B).total();
+    if (hipError_t e = rz_opt_in_lds(rz_qdef_kernel, lds)) return e;
     const uint32_t per = (uint32_t)p.chunks * kBlock;
     hipLaunchKernelGGL(rz_qdef_kernel, dim3((p.n + per - 1) / per, instances), dim3(kBlock), lds, st, p, ml);
     return hipGetLastError();

@@ -6,6 +6,7 @@
 // once, as physics_ref.prepare does.
 #pragma once
 #include "../../include/reze_deform.h"
+#include "lds_layout.h"
 
 #include <algorithm>
 #include <cmath>
@@ -278,7 +279,7 @@ private:
 
 // ---- the solver's LDS, and the linear springs (rz_physics_springs; tests/spring_ref.py) ----
 
-constexpr size_t kLdsLimit = 160 * 1024;   // what one workgroup of rz_physics_kernel may take: the only spelling of it
+constexpr size_t kLdsLimit = rzlds::kCuLds;    // what one workgroup of rz_physics_kernel may take: the CU's LDS, as for every kernel (lds_layout.h)
 // lanes per workgroup, chosen at upload: 64 when the bodies and the widest colour fit one wave, else 256 (unmeasured: DESIGN.md 9.7)
 inline int block_for(int n_bodies, int widest) { return n_bodies <= 64 && widest <= 64 ? 64 : 256; }
 // LDS of one workgroup: 96 B per body; once the joints outnumber the lanes their multipliers live there too, 12 B per joint, 24 B with the

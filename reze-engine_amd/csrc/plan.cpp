@@ -198,7 +198,7 @@ Plan make_plan(const rz_ctx *c)
     // Automatic mode follows that; "fuse_fk" = 0 / 1 forces it.
     // (the fused kernels' embedded solve carries no stage: any stage of solve_stages — an IK table, resident follower entries, after-physics
     // bones behind overrides — keeps the solve in rz_fk_kernel, whose instantiations do)
-    pl.fuse_fk = solve_stages(c).plain() && c->I == 1 && c->pl.cur.local && c->fk.has_topology && (size_t)c->skel.B * 48 + rz_fk_scratch_bytes((int)c->skel.B) + (size_t)c->morphs.M * 12 + 4096 <= 160 * 1024 &&
+    pl.fuse_fk = solve_stages(c).plain() && c->I == 1 && c->pl.cur.local && c->fk.has_topology && rzlds::fused_fit_bytes((int)c->skel.B, c->morphs.M) <= rzlds::kCuLds &&
                  (c->t_fusefk == 1 || (c->t_fusefk < 0 && (c->pl.cur.sampled || c->morphs.mode != 1)));
     const bool can_fast = c->I == 1 && !pl.fuse_fk && (v.mode != 1 || c->pl.cur.ml.count >= 0);
     v.fast = can_fast && c->t_fast != 0;
@@ -242,6 +242,10 @@ Plan make_plan(const rz_ctx *c)
     if (v.mode == 1 && c->morphs.storage == 24 && v.S <= 2 && per_wave > 32) per_wave = round_up(per_wave, 32);
     pl.quads_per_wave = per_wave;
     pl.grid_x = std::max<uint32_t>(1, (pl.n_quads + per_wave * waves_per_wg - 1) / (per_wave * waves_per_wg));
+    // the single-mesh frame's LDS with this write-batching buffer and this sparse piece (lds_layout.h, through the variant chosen above)
+    auto frame_lds = [&](uint32_t out_cap, uint32_t sp_cap) {
+        return rz_deform_layout((int)c->skel.B, (int)c->morphs.M, (int)c->morphs.Mpad, out_cap, sp_cap, pl.fuse_fk, v).total();
+    };
     // LDS write batching. Measured (tools/archive/ablate_c5.py): parking a wave's WHOLE run and writing it once at the end
     // takes C5 from 127.6 to 124.5 us (the stores leave the read stream alone until the kernel's tail); flushing every
     // step gains nothing. So automatic mode turns it on exactly when the run fits the buffer (<= 640 vertices per wave).
@@ -251,28 +255,20 @@ Plan make_plan(const rz_ctx *c)
         if (c->t_outcap > 0) pl.out_cap = std::max(std::min<uint32_t>(round_up((uint32_t)c->t_outcap, 64), 640), step);
         else if (c->t_outcap < 0 && run <= 640) pl.out_cap = std::max(run, step);
         // a skeleton near the LDS limit (3 242 bones = 152 KB of palette) leaves no room for the write-batching buffer: do without
-        if (pl.out_cap) {
-            RzDeformParams q;
-            memset(&q, 0, sizeof q);
-            q.B = (int)c->skel.B; q.M = (int)c->morphs.M; q.Mpad = (int)c->morphs.Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
-            q.sp_cap = 16;      // (counted for sparse targets only: the buffer must leave room for the smallest piece below, or the frame is refused for a buffer it can do without)
-            if (rz_deform_lds_bytes(q, v) > 160 * 1024) pl.out_cap = 0;
-        }
+        // (with the smallest piece, which the layout counts for sparse targets only: the buffer must leave room for it, or the frame is refused for a buffer it can do without)
+        if (pl.out_cap && frame_lds(pl.out_cap, rzlds::kMinPiece) > rzlds::kCuLds) pl.out_cap = 0;
     }
     // Sparse targets: every wave stages its step's piece of the CSR in LDS (deform_kernels.hip, MODE 2). The buffer takes what the
     // launch leaves of the LDS — a frame of at most one workgroup per CU (a single character: the demo model is 113 workgroups)
     // has the CU's 160 KB to itself, larger frames plan for two workgroups per CU — up to a whole step of M-entry rows or 2 048
     // entries (32 KB per wave); longer ranges go through it in pieces.
     if (v.mode == 2) {
-        RzDeformParams q;
-        memset(&q, 0, sizeof q);
-        q.B = (int)c->skel.B; q.M = (int)c->morphs.M; q.Mpad = (int)c->morphs.Mpad; q.out_cap = pl.out_cap; q.fk_on = pl.fuse_fk ? 1 : 0;
-        const size_t base = rz_deform_lds_bytes(q, v);
-        const size_t budget = ((uint64_t)pl.grid_x * c->I <= (uint64_t)c->n_cu ? 160u : 80u) * 1024u;
+        const size_t base = frame_lds(pl.out_cap, 0);
+        const size_t budget = (uint64_t)pl.grid_x * c->I <= (uint64_t)c->n_cu ? rzlds::kCuLds : rzlds::kHalfCu;
         // (a skeleton near the LDS limit leaves less than the planned share: take what the CU's 160 KB still hold, down to a quarter
         // burst of 16 entries per wave — the piece loop works with any multiple of 16; nothing at all left = "skeleton too large" below)
-        const size_t hard = 160u * 1024u > base ? (160u * 1024u - base) / (waves_per_wg * 16) : 0;
-        const size_t avail = budget > base + 4096 ? (budget - base - 1024) / (waves_per_wg * 16) : hard;
+        const size_t hard = rzlds::kCuLds > base ? (rzlds::kCuLds - base) / (waves_per_wg * 16) : 0;
+        const size_t avail = budget > base + rzlds::kPieceRoom ? (budget - base - rzlds::kPieceSlack) / (waves_per_wg * 16) : hard;
         const uint32_t want = std::min<uint32_t>(2048u, (256u / (uint32_t)v.S) * std::max<uint32_t>(c->morphs.M, 1u));
         pl.sp_cap = avail >= 64 ? std::max<uint32_t>(64u, std::min<uint32_t>(round_up(want, 256), (uint32_t)(avail / 64 * 64)))         // whole 1 KiB bursts (the kernel issues them in groups of four)
                                 : std::max<uint32_t>(16u, (uint32_t)(avail / 16 * 16));
@@ -301,7 +297,8 @@ Plan make_plan(const rz_ctx *c)
         // 102 KB, one 512-thread workgroup per CU (measured 35.5 us on C4 against 39.0 us for prep kernel + launch boundary +
         // 256-thread skin kernel, and 39.5 us for two 256-thread workgroups of 6 poses).
         const int blk = is.blk;
-        const uint32_t lds_budget = (blk == 256 ? 80u : 156u) * 1024u;
+        auto crowd_budget = [](int block) { return block == 256 ? rzlds::kHalfCu : rzlds::kCrowdLarge; };    // two 256-thread workgroups per CU, or one large one
+        const size_t lds_budget = crowd_budget(blk);
         // Sparse targets ("inst_morphs"): the group's morph weights, G x Mpad floats, sit in LDS behind whatever the form keeps there and
         // count against the same budgets. A form they do not fit beside is not taken (subset form -> whole palettes with the group the
         // budget allows -> the generic kernel: the frame launched without the key), never an error.
@@ -309,7 +306,7 @@ Plan make_plan(const rz_ctx *c)
         bool sub = c->t_subsets != 0 && c->sub_valid && c->sub_per == is.per && c->sub_runs == is.runs && c->sub_B == c->skel.B &&
                    c->sub_max < c->skel.B && c->sub_max <= (uint32_t)blk;
         if (sub) {
-            const size_t lds = rz_skin_instances_lds_bytes(is.G, c->sub_max, !is.want_in_kernel, true, mpad);
+            const size_t lds = rzlds::crowd(is.G, (int)c->sub_max, !is.want_in_kernel, true, mpad).total();
             if (lds > lds_budget) sub = false;
             else {
                 pl.subsets = true; pl.sub_bones = c->sub_max; pl.inst_lds = lds; pl.inst_morphs = is.morphs;
@@ -323,16 +320,15 @@ Plan make_plan(const rz_ctx *c)
                 // not at 1024 threads: the MORPH front has no instantiation there, kernels/crowd.hip.)
                 if (subfk_wanted(c) && c->subfk_valid && c->subfk_sub_gen == c->sub_gen && c->subfk_fk_gen == c->fk_gen &&
                     (size_t)is.G * c->subfk_stride <= 2 * (size_t)blk && !(is.morphs && (c->pl.cur.sampled || blk == 1024))) {
-                    const size_t lf = rz_skin_instances_fk_lds_bytes(is.G, c->subfk_stride, c->sub_max, mpad);
+                    const size_t lf = rzlds::crowd_front(is.G, (int)c->subfk_stride, (int)c->sub_max, mpad).total();
                     if (lf <= lds_budget) { pl.subfk = true; pl.prep = false; pl.dma = false; pl.inst_lds = lf; }
                 }
             }
         }
         if (!sub) {
             const int blk_f = is.blk_full;
-            const uint32_t budget_f = (blk_f == 256 ? 80u : 156u) * 1024u;
             const bool in_kernel = is.want_in_kernel && c->skel.B <= (uint32_t)blk_f;   // the in-place product gives every bone its own thread
-            const uint32_t g_lds = budget_f / (c->skel.B * (in_kernel ? 64u : 48u) + mpad * 4u);
+            const uint32_t g_lds = (uint32_t)(crowd_budget(blk_f) / rzlds::crowd(1, (int)c->skel.B, !in_kernel, false, mpad).total());      // poses the budget holds
             int G = (int)std::min<uint32_t>((uint32_t)is.G, g_lds);
             // (sparse targets: the group that was asked for, or the generic kernel — a morph-free crowd has no other frame to fall back to
             // and takes the smaller group; a crowd with targets has the frame it launched before the key existed)
@@ -342,7 +338,7 @@ Plan make_plan(const rz_ctx *c)
                 inst_runs(c, G, blk_f, false, &per, &runs);
                 pl.inst_group = G; pl.inst_block = blk_f; pl.verts_per_wg = per; pl.grid_x = runs;
                 pl.prep = !in_kernel; pl.dma = !in_kernel;
-                pl.inst_lds = rz_skin_instances_lds_bytes(G, c->skel.B, !in_kernel, false, mpad);
+                pl.inst_lds = rzlds::crowd(G, (int)c->skel.B, !in_kernel, false, mpad).total();
                 pl.inst_morphs = is.morphs;
             }
         }

@@ -150,7 +150,7 @@ int rz_upload_skeleton(rz_ctx *c, uint32_t B, const float *inverse_bind16)
     if (int r = use(c)) return r;
     if (int r = static_unlocked(c, "rz_upload_skeleton")) return r;
     if (B == 0 || !inverse_bind16) return fail(RZ_ERR_INVALID, "rz_upload_skeleton: model has no bones");
-    if ((size_t)B * 48 + 8192 > 160 * 1024) return fail(RZ_ERR_UNSUPPORTED, "more than %d bones do not fit the LDS palette", (160 * 1024 - 8192) / 48);
+    if ((size_t)B * 48 + rzlds::kSkeletonReserve > rzlds::kCuLds) return fail(RZ_ERR_UNSUPPORTED, "more than %d bones do not fit the LDS palette", (int)((rzlds::kCuLds - rzlds::kSkeletonReserve) / 48));
     HIP_TRY(hipStreamSynchronize(c->stream));
     drop_graph(c);
     c->ovr_count = 0;
@@ -897,8 +897,8 @@ int rz_upload_after_physics(rz_ctx *c, uint32_t n, const uint32_t *bones)
             if (c->ik.on_path[bones[k]])
                 return fail(RZ_ERR_UNSUPPORTED, "rz_upload_after_physics: bone %u (entry %u) is a link or the effector of a resident IK chain, or lies on its path: the stage does not solve IK again", bones[k], k);
     const size_t lds = rzafter::lds_bytes(c->skel.B, n);
-    if (lds > 160 * 1024)
-        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %u entries x 1 B = %zu B of LDS (the limit is 160 KB = %d B)", c->skel.B, n, lds, 160 * 1024);
+    if (lds > rzlds::kCuLds)
+        return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the after-physics stage on the device: %u bones x 48 B + %u entries x 1 B = %zu B of LDS (the limit is 160 KB = %d B)", c->skel.B, n, lds, (int)rzlds::kCuLds);
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_after(c);
     drop_graph(c);

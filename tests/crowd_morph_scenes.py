@@ -40,7 +40,7 @@ def mpad(M):
 
 
 def lds_bytes(G_, bones, per_bone, M):
-    """rz_skin_instances_lds_bytes with the weight block: G poses x (staged bones x 48 / 64 / 112 B + Mpad x 4 B)"""
+    """rzlds::crowd (csrc/lds_layout.h) with the weight block, restated: G poses x (staged bones x 48 / 64 / 112 B + Mpad x 4 B)"""
     return G_ * bones * per_bone + G_ * mpad(M) * 4
 
 

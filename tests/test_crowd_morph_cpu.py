@@ -2,7 +2,7 @@
 tests/test_gpu_crowd_morphs.py then finds on the device is about the kernels, not about a scene that is not what it says.
 
 The plan arithmetic restated here is plan.cpp's (inst_runs, make_plan's LDS admission) and kernels/crowd.hip's
-(rz_skin_instances_lds_bytes / rz_skin_instances_fk_lds_bytes with the weight block of G x Mpad x 4 B)."""
+(csrc/lds_layout.h: rzlds::crowd / rzlds::crowd_front with the weight block of G x Mpad x 4 B)."""
 import json
 import os
 import shutil
