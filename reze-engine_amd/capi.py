@@ -388,6 +388,29 @@ def gather_direct(contexts, v_total, root=0):
         c.v_total = int(v_total)
 
 
+KERNEL_NAME_KEYS = ("morph_mode", "effective_split", "effective_unroll", "effective_nt", "effective_nt_store", "effective_geo", "effective_fast", "effective_variant",
+                    "effective_inst_group", "effective_inst_block", "effective_subsets", "effective_fuse_fk", "effective_inst_morphs", "effective_poses_per_wg")
+
+
+def kernel_name_of(keys):
+    """The frame kernel's name from the values of KERNEL_NAME_KEYS (rz_get_tuning; the library reads them off its one kernel record,
+    csrc/frame_kernel.h), spelled like the demangled symbol — except that the dense kernel's eighth template argument (Q24: 24-bit morph
+    planes) is OMITTED. It stays omitted: stored profiles (profiles/pmc_traffic.json) and bench lines are keyed on this string as it is."""
+    tf = lambda k: "true" if keys[k] else "false"  # noqa: E731
+    if keys["effective_poses_per_wg"] > 0:
+        return "rz_skin_instances_reg_kernel<8, %s>" % tf("effective_nt_store")
+    if keys["effective_inst_group"] > 0:
+        morph = "_morph" if keys["effective_inst_morphs"] else ""     # sparse targets walked in the crowd kernels (kernels/crowd_morph.hip)
+        if keys["effective_fuse_fk"]:                                 # the hierarchy solved in the crowd kernel's front
+            return "rz_skin_instances_fk%s_kernel<%d, %s>" % (morph, keys["effective_inst_block"], tf("effective_nt_store"))
+        return "rz_skin_instances%s_kernel<%d, %s, %s>" % (morph, keys["effective_inst_block"], tf("effective_nt_store"), tf("effective_subsets"))
+    mode, s_ = keys["morph_mode"], keys["effective_split"]
+    if mode == 1:
+        return "rz_deform_dense_kernel<%d, %d, %s, %s, %s, %s, %d>" % (s_, 8 if keys["effective_unroll"] >= 8 else 4, tf("effective_nt"), tf("effective_nt_store"),
+                                                                       tf("effective_geo"), tf("effective_fast"), keys["effective_variant"])
+    return "rz_deform_small_kernel<%d, %d, %s, %s, %s, %d>" % (4 if s_ >= 4 else 1, mode, tf("effective_nt_store"), tf("effective_geo"), tf("effective_fast"), keys["effective_variant"])
+
+
 class DeformContext:
     """One GPU's deformation context (rz_ctx)."""
 
@@ -1065,33 +1088,8 @@ class DeformContext:
         return {"comm_count": n.value, "comm_user_rank": u.value}
 
     def kernel_name(self):
-        """The dominant kernel the CURRENT plan launches, spelled like rocprofv3's kernel trace spells it."""
-        g = self.get_tuning
-        tf = lambda k: "true" if g(k) else "false"  # noqa: E731
-        if g("effective_poses_per_wg") > 0:
-            return "rz_skin_instances_reg_kernel<8, %s>" % tf("effective_nt_store")
-        if g("effective_inst_group") > 0:
-            try:
-                fused = g("effective_closure_bones") > 0        # the hierarchy solved in the crowd kernel's front (ABI 5)
-            except RzError:
-                fused = False
-            try:
-                morph = "_morph" if g("effective_inst_morphs") else ""     # sparse targets walked in the crowd kernels (kernels/crowd_morph.hip)
-            except RzError:
-                morph = ""
-            if fused:
-                return "rz_skin_instances_fk%s_kernel<%d, %s>" % (morph, g("effective_inst_block"), tf("effective_nt_store"))
-            return "rz_skin_instances%s_kernel<%d, %s, %s>" % (morph, g("effective_inst_block"), tf("effective_nt_store"), tf("effective_subsets"))
-        mode = g("morph_mode")
-        s_ = g("effective_split")
-        try:
-            var = ", %d" % g("effective_variant")       # (ABI 6: the kernel variant without the fused consumers / with the specialised solve)
-        except RzError:
-            var = ""
-        if mode == 1:
-            return "rz_deform_dense_kernel<%d, %d, %s, %s, %s, %s%s>" % (s_, 8 if g("effective_unroll") >= 8 else 4, tf("effective_nt"), tf("effective_nt_store"),
-                                                                         tf("effective_geo"), tf("effective_fast"), var)
-        return "rz_deform_small_kernel<%d, %d, %s, %s, %s%s>" % (4 if s_ >= 4 else 1, mode, tf("effective_nt_store"), tf("effective_geo"), tf("effective_fast"), var)
+        """The dominant kernel the CURRENT plan launches: kernel_name_of() over the tuning keys it reads."""
+        return kernel_name_of({k: self.get_tuning(k) for k in KERNEL_NAME_KEYS})
 
     def time_frames(self, frames):
         t = RzTiming()

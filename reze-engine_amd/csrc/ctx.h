@@ -556,6 +556,8 @@ int ensure_subfk(rz_ctx *c);
 RzSubFk subfk_params(const rz_ctx *c);
 int frame_plan(rz_ctx *c, Plan *pl);
 RzDeformParams deform_params(const rz_ctx *c, const Plan &pl);
+// Which kernel that frame launches (frame_kernel.h), the one owner of that decision: launch_deform, frame_signature and rz_get_tuning's effective_* keys read it.
+RzFrameKernel frame_kernel(const Plan &pl, const RzDeformParams &p);
 RzPrepParams prep_params(const rz_ctx *c);
 RzFkParams fk_params(const rz_ctx *c, bool overrides = true);      // overrides = false: without the override table (rz_physics_step's solve)
 // Which stages the next hierarchy solve runs (deform_kernels.h: RzFkStages), the one owner of that decision: IK while a table is resident,
@@ -593,10 +595,12 @@ int check_ready(rz_ctx *c);
 int launch_fk(rz_ctx *c, hipStream_t st, bool overrides = true);       // the solve + the after launch solve_stages(c, overrides) lists
 bool solve_on_demand(const rz_ctx *c);
 int launch_prep(rz_ctx *c, hipStream_t st);
+bool has_front(const rz_ctx *c, const Plan &pl);       // does a frame of this plan launch kernels in front of its deform / skin kernel?
 int launch_front(rz_ctx *c, const Plan &pl, hipStream_t st);
 int launch_deform(rz_ctx *c, const Plan &pl);
 bool want_overlap(const rz_ctx *c, const Plan &pl);
 int set_overlap(rz_ctx *c, bool on);
+int begin_frames(rz_ctx *c, Plan *pl);      // use -> check_ready -> ensure_outputs -> frame_plan -> set_overlap(want_overlap)
 int run_frame(rz_ctx *c, const Plan &pl);
 RzSdefParams sdef_params(const rz_ctx *c, const Plan &pl);
 RzQdefParams qdef_params(const rz_ctx *c, const Plan &pl);

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "frame_kernel.h"
 #include "lds_layout.h"
 
 // rz_prep_kernel: palette = rows 0..2 of world * inverseBind (engine/src/engine.ts:926-928) and the
@@ -376,17 +377,6 @@ struct RzPhysicsParams {
 // (its LDS: physics_table.h, rzphys::lds_bytes and kLdsLimit)
 hipError_t rz_launch_physics(const RzPhysicsParams &p, uint32_t instances, hipStream_t st, bool aligned = false);   // aligned: the ALIGN instantiations (rz_physics_aligned)
 
-// Compile-time variant selection of the single-mesh frame kernels (kernels/deform_dense.hip, kernels/deform_small.hip).
-struct RzVariant {
-    int mode;    // 0 none, 1 dense, 2 sparse
-    int S;       // morph split 1,2,4,8 (mode 1 only)
-    int U;       // 4 or 8
-    bool nt;     // nontemporal morph loads
-    bool nts;    // nontemporal output stores
-    bool geo;    // rest geometry through LDS
-    bool fast;   // fused palette + kernarg morph list (single instance)
-};
-
 // Every kernel's dynamic LDS is laid out in lds_layout.h (rzlds); what follows maps parameter blocks onto its scalars.
 // the pose's morph weights the solve keeps in LDS for the bone morphs (rzlds::solve: n_weights): none without bone morphs
 __host__ __device__ inline int rz_fk_mw_count(const RzFkParams &p)
@@ -410,20 +400,7 @@ inline size_t rz_fk_lds_bytes(const RzFkParams &p, const RzFkStages &s) { return
 // the after-physics stage (s.af) behind the solve, on the same stream (kernels/after.hip: rz_fk_after_kernel): reads the world matrices
 // the solve left in memory and writes the listed bones' world matrices and palette rows again
 hipError_t rz_launch_fk_after(const RzFkParams &p, const RzAfterParams &a, uint32_t instances, hipStream_t st);
-hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
-                            uint32_t instances, hipStream_t st);
 inline size_t rz_deform_lds_bytes(const RzDeformParams &p, const RzVariant &v) { return rz_deform_layout(p.B, p.M, p.Mpad, p.out_cap, p.sp_cap, p.fk_on != 0, v).total(); }
-// the two single-mesh frame kernels behind rz_launch_deform (kernels/deform_dense.hip: v.mode == 1; kernels/deform_small.hip: modes 0 / 2)
-hipError_t rz_launch_deform_dense(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st);
-hipError_t rz_launch_deform_small(const RzDeformParams &p, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st);
-// instanced skin (no morphs): G poses per workgroup share one decode of each vertex
-// register-resident form: 2048 vertices per workgroup decoded once, poses streamed through a 2-deep LDS palette ring
-hipError_t rz_launch_skin_instances_reg(const RzDeformParams &p, int n_inst, int poses_per_wg, uint32_t grid_x, bool nts,
-                                        hipStream_t st);
-// morphs (inst_morphs; kernels/crowd_morph.hip): the MORPH instantiations — every pose also walks the rows of the context's sparse CSR
-// (p.sp_ptr / p.sp_entries) with its own weights (p.morph_w [I][M]), which the front stages in LDS behind the palettes
-hipError_t rz_launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                    int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs = false);
 // Crowd frame with the hierarchy solved in the skin kernel's front (kernels/crowd.hip: rz_skin_instances_fk_kernel): per vertex run the
 // closure of its named bones under "parent of", one 80-byte record per closure slot (plan.cpp: ensure_subfk)
 struct RzSubFk {
@@ -432,8 +409,17 @@ struct RzSubFk {
     uint32_t stride;            // closure slots of the largest run
     uint32_t rounds;            // radix-4 doubling rounds the deepest closure needs (<= 3)
 };
-hipError_t rz_launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                       int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs = false);
+// The launch shape of a frame's kernel: grid (grid_x, n_inst) for one mesh; for a crowd grid_x vertex runs of verts_per_wg vertices by
+// ceil(n_inst / G) groups (the register form: ranges) of G poses. lds = the dynamic LDS of the launch.
+struct RzLaunchShape { int G, n_inst; uint32_t verts_per_wg, grid_x; size_t lds; };
+// The frame's kernel (frame_kernel.h), ONE entry: the kernel file of k's family picks the instantiation k names and launches it, or refuses
+// (hipErrorInvalidValue) a record this build does not carry. ml: the one-launch dense frame's list; f: the crowd fk front's records.
+hipError_t rz_launch_frame(const RzFrameKernel &k, const RzDeformParams &p, const RzMorphList &ml, const RzSubFk &f, const RzLaunchShape &s, hipStream_t st);
+// behind it; the MORPH half of crowd.hip (crowd_morph.hip) also walks the context's sparse CSR per pose, weights p.morph_w [I][M] staged in LDS
+hipError_t rz_launch_deform_dense(const RzFrameKernel &k, const RzDeformParams &p, const RzMorphList &ml, const RzLaunchShape &s, hipStream_t st);
+hipError_t rz_launch_deform_small(const RzFrameKernel &k, const RzDeformParams &p, const RzLaunchShape &s, hipStream_t st);
+hipError_t rz_launch_crowd(const RzFrameKernel &k, const RzDeformParams &p, const RzSubFk &f, const RzLaunchShape &s, hipStream_t st);
+hipError_t rz_launch_crowd_morph(const RzFrameKernel &k, const RzDeformParams &p, const RzSubFk &f, const RzLaunchShape &s, hipStream_t st);
 // per vertex run of `per` vertices: the ascending list of bones its vertices name + the joints rewritten as slots of it
 hipError_t rz_launch_run_subsets(const uint32_t *j01, const uint32_t *j23, uint32_t v_lim, uint32_t per, uint32_t runs, uint32_t B,
                                  uint16_t *list, uint32_t *count, uint32_t *rj01, uint32_t *rj23, hipStream_t st);

@@ -49,39 +49,37 @@ bool solve_on_demand(const rz_ctx *c) { return c->fk_stale && c->pl.cur.local &&
 
 // Everything a frame launches in front of the deform kernel: on-device FK (local-rotation poses) and/or the prep
 // kernel. The FK kernel already writes the palette, so prep is only still needed for its morph compaction.
+// (a frame whose deform / crowd kernel solves the hierarchy itself has none: pl.fuse_fk, pl.subfk — RzFrameKernel::solve)
+bool has_front(const rz_ctx *c, const Plan &pl) { return (pl.prep || c->pl.cur.local) && !pl.fuse_fk && !pl.subfk; }
+
 int launch_front(rz_ctx *c, const Plan &pl, hipStream_t st)
 {
-    if (pl.fuse_fk || pl.subfk) return RZ_OK;       // the deform / crowd kernel solves the hierarchy itself
+    if (!has_front(c, pl)) return RZ_OK;
     if (c->pl.cur.local) {
         if (int r = launch_fk(c, st)) return r;
         if (pl.prep && c->morphs.mode == 1)
             if (int r = launch_prep(c, st)) return r;
         return RZ_OK;
     }
-    if (pl.prep) return launch_prep(c, st);
-    return RZ_OK;
+    return launch_prep(c, st);
 }
 
+// The frame's kernel: frame_kernel (plan.cpp) names the instantiation, rz_launch_frame launches it; then what that family's frame leaves in memory.
 int launch_deform(rz_ctx *c, const Plan &pl)
 {
-    RzDeformParams p = deform_params(c, pl);
-    if (pl.poses_per_wg > 0) {
-        HIP_TRY(rz_launch_skin_instances_reg(p, (int)c->I, pl.poses_per_wg, pl.grid_x, pl.v.nts, c->stream));
-        return RZ_OK;
+    const RzDeformParams p = deform_params(c, pl);
+    const RzFrameKernel k = frame_kernel(pl, p);
+    const bool one_mesh = k.family == kRzSmall || k.family == kRzDense;
+    RzLaunchShape s = { k.family == kRzCrowdReg ? k.poses_per_wg : k.group, (int)c->I, pl.verts_per_wg, pl.grid_x, (size_t)pl.inst_lds };
+    if (one_mesh) {
+        s.grid_x += p.pf_src ? 1u : 0u;
+        s.lds = rz_deform_lds_bytes(p, pl.v);
+        if (s.lds > rzlds::kCuLds) return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the LDS palette (%zu B)", s.lds);
     }
-    if (pl.inst_group > 0 && pl.subfk) {
-        HIP_TRY(rz_launch_skin_instances_fk(p, subfk_params(c), pl.inst_group, (int)c->I, pl.verts_per_wg, pl.grid_x, pl.inst_block, pl.v.nts, (size_t)pl.inst_lds, c->stream, pl.inst_morphs));
-        c->fk_stale = true;                 // neither world matrices nor palettes of this pose are in memory: formed on demand (rz_read_world / rz_read_palette)
-        return RZ_OK;
-    }
-    if (pl.inst_group > 0) {
-        HIP_TRY(rz_launch_skin_instances(p, pl.inst_group, (int)c->I, pl.verts_per_wg, pl.grid_x, pl.inst_block, pl.v.nts, (size_t)pl.inst_lds, c->stream, pl.inst_morphs));
-        if (!pl.dma) c->palette_stale = pl.subsets;    // the whole-palette one-launch frame copies its palettes out, the subset form cannot
-        return RZ_OK;
-    }
-    size_t lds = rz_deform_lds_bytes(p, pl.v);
-    if (lds > rzlds::kCuLds) return fail(RZ_ERR_UNSUPPORTED, "skeleton too large for the LDS palette (%zu B)", lds);
-    HIP_TRY(rz_launch_deform(p, c->pl.cur.ml, pl.v, pl.grid_x + (p.pf_src ? 1u : 0u), c->I, c->stream));
+    HIP_TRY(rz_launch_frame(k, p, c->pl.cur.ml, subfk_params(c), s, c->stream));
+    if (k.family == kRzCrowdFk) c->fk_stale = true;     // neither world matrices nor palettes of this pose are in memory: formed on demand (rz_read_world / rz_read_palette)
+    if (k.family == kRzCrowd && !pl.dma) c->palette_stale = pl.subsets;     // the whole-palette one-launch frame copies its palettes out, the subset form cannot
+    if (!one_mesh) return RZ_OK;
     c->palette_stale = false;                          // this frame's palette is in memory: written by its front kernels or by workgroup 0
     if (p.world_copy) c->pl.cur.world_resident = true;        // workgroup 0 of that launch left the pose in the device block
     if (p.morph_w_copy) c->pl.cur.mw_resident = true;
@@ -178,7 +176,7 @@ bool want_overlap(const rz_ctx *c, const Plan &pl)
 {
     // OPT-IN (overlap = 1): measured on MI355X / ROCm 7.2 the two cross-stream hand-offs per frame cost more than the front
     // kernels they hide — C4 39.0 -> 44.8 us with rz_prep_kernel in front, 43.4 -> 62.1 us with rz_fk_kernel
-    return c->t_overlap == 1 && c->I > 1 && c->morphs.mode != 2 && !c->t_graph && (pl.prep || c->pl.cur.local) && !pl.subfk;
+    return c->t_overlap == 1 && c->I > 1 && c->morphs.mode != 2 && !c->t_graph && has_front(c, pl);
 }
 
 // Switching protocols is rare (instance count, tuning keys): drain both streams so that nothing enqueued under the old
@@ -217,18 +215,24 @@ int run_frame(rz_ctx *c, const Plan &pl)
 // the stream per-frame inputs travel on and front kernels run on
 hipStream_t front_stream(const rz_ctx *c) { return c->overlap_on ? c->up_stream : c->stream; }
 
+// What every entry that launches frames does first, behind its own argument checks; leaves the next frame's plan and its stream protocol.
+int begin_frames(rz_ctx *c, Plan *pl)
+{
+    if (int r = use(c)) return r;
+    if (int r = check_ready(c)) return r;
+    if (int r = ensure_outputs(c)) return r;
+    if (int r = frame_plan(c, pl)) return r;
+    return set_overlap(c, want_overlap(c, *pl));
+}
+
 }  // namespace rzi
 
 extern "C" {
 
 int rz_deform(rz_ctx *c)
 {
-    if (int r = use(c)) return r;
-    if (int r = check_ready(c)) return r;
-    if (int r = ensure_outputs(c)) return r;
     Plan pl;
-    if (int r = frame_plan(c, &pl)) return r;
-    if (int r = set_overlap(c, want_overlap(c, pl))) return r;
+    if (int r = begin_frames(c, &pl)) return r;
     return run_frame(c, pl);
 }
 
@@ -249,6 +253,8 @@ static uint64_t frame_signature(rz_ctx *c, const Plan &pl)
     uint64_t h = 1469598103934665603ull;
     const RzDeformParams dp = deform_params(c, pl);
     h = fnv(h, &dp, sizeof dp);
+    const RzFrameKernel fk = frame_kernel(pl, dp);      // which kernel those launches are
+    h = fnv(h, &fk, sizeof fk);
     h = fnv(h, &c->pl.cur.ml, sizeof c->pl.cur.ml);
     h = fnv(h, &pl, sizeof pl);
     const RzPrepParams pp = prep_params(c);
@@ -271,12 +277,8 @@ constexpr uint32_t kGraphFrames = 16;   // even: the bounding-box slot parity is
 
 int rz_deform_n(rz_ctx *c, uint32_t frames)
 {
-    if (int r = use(c)) return r;
-    if (int r = check_ready(c)) return r;
-    if (int r = ensure_outputs(c)) return r;
     Plan pl;
-    if (int r = frame_plan(c, &pl)) return r;
-    if (int r = set_overlap(c, want_overlap(c, pl))) return r;      // never on while the graph key is set
+    if (int r = begin_frames(c, &pl)) return r;      // (the overlapped protocol is never on while the graph key is set)
     uint32_t f = 0;
     if (c->t_graph && frames >= 2 * kGraphFrames) {
         // Launch-bound replay (a 30 k-vertex frame is 3-6 us of GPU time per ~3 us of launch work on the host): capture
@@ -320,13 +322,8 @@ int rz_deform_pair(rz_ctx *a, rz_ctx *b, uint32_t frames)
     if (a->device != b->device) return fail(RZ_ERR_INVALID, "rz_deform_pair: the contexts live on devices %d and %d", a->device, b->device);
     rz_ctx *cs[2] = { a, b };
     Plan pl[2];
-    for (int k = 0; k < 2; ++k) {
-        if (int r = use(cs[k])) return r;
-        if (int r = check_ready(cs[k])) return r;
-        if (int r = ensure_outputs(cs[k])) return r;
-        if (int r = frame_plan(cs[k], &pl[k])) return r;
-        if (int r = set_overlap(cs[k], want_overlap(cs[k], pl[k]))) return r;
-    }
+    for (int k = 0; k < 2; ++k)
+        if (int r = begin_frames(cs[k], &pl[k])) return r;
     for (uint32_t f = 0; f < frames; ++f)
         if (int r = run_frame(cs[f & 1], pl[f & 1])) return r;
     return RZ_OK;
@@ -436,11 +433,8 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
 {
     if (int r = use(c)) return r;
     if (!out || frames == 0) return fail(RZ_ERR_INVALID, "rz_time_frames: bad arguments");
-    if (int r = check_ready(c)) return r;
-    if (int r = ensure_outputs(c)) return r;
     Plan pl;
-    if (int r = frame_plan(c, &pl)) return r;
-    if (int r = set_overlap(c, want_overlap(c, pl))) return r;
+    if (int r = begin_frames(c, &pl)) return r;
     memset(out, 0, sizeof *out);
     float ms = 0.f;
     // whole frames (front kernels when the plan has any + the deform / skin kernel), back to back exactly as rz_deform
@@ -465,7 +459,7 @@ int rz_time_frames(rz_ctx *c, uint32_t frames, rz_timing *out)
     out->deform_kernel_ms = ms / frames;
     // the front kernels alone (only part of the frame when the plan is not the one-launch FAST form); everything has
     // drained at this point, so they may run on the context's stream whatever the protocol
-    if ((pl.prep || c->pl.cur.local) && !pl.fuse_fk && !pl.subfk) {
+    if (has_front(c, pl)) {
         HIP_TRY(hipStreamSynchronize(c->up_stream));
         HIP_TRY(hipEventRecord(c->ev0, c->stream));
         for (uint32_t f = 0; f < frames; ++f)

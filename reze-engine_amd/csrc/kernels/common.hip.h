@@ -30,6 +30,11 @@
 
 namespace {
 
+#ifdef RZ_ALL_VARIANTS
+constexpr bool kAllVariants = true;      // the tools-only build (`make variants`): every frame kernel RzFrameKernel::carried(true) admits
+#else
+constexpr bool kAllVariants = false;
+#endif
 constexpr int kBlock = 256;
 static_assert(kBlock / 64 == rzlds::kFrameWaves, "lds_layout.h lays the generic frame out for the waves of a kBlock workgroup");
 

@@ -7,14 +7,16 @@
 // unit, not a template parameter: the two kernels below keep their template arguments, hence the symbols every stored profile names, and
 // with MORPH = false they are the parent's instruction streams (profiles/crowd_morph_identity.txt). kernels/crowd_morph.hip compiles this
 // file again with RZ_CROWD_MORPH true; there the same two templates are called rz_skin_instances_morph_kernel<BLOCK, NTS, SUB> and
-// rz_skin_instances_fk_morph_kernel<BLOCK, NTS>.
+// rz_skin_instances_fk_morph_kernel<BLOCK, NTS>. Either compilation exports ONE launcher for its half, RZ_CROWD_LAUNCH at the end of the file.
 #ifndef RZ_CROWD_MORPH
 #define RZ_CROWD_MORPH false
 #endif
 #if RZ_CROWD_MORPH
 #define RZ_CROWD_KERNEL rz_skin_instances_morph_kernel
 #define RZ_CROWD_FK_KERNEL rz_skin_instances_fk_morph_kernel
+#define RZ_CROWD_LAUNCH rz_launch_crowd_morph
 #else
+#define RZ_CROWD_LAUNCH rz_launch_crowd
 #define RZ_CROWD_KERNEL rz_skin_instances_kernel
 #define RZ_CROWD_FK_KERNEL rz_skin_instances_fk_kernel
 #endif
@@ -574,85 +576,85 @@ __global__ void __launch_bounds__(kBlock) rz_run_subsets_kernel(const uint32_t *
 
 }  // namespace
 
-template <int BLOCK>
-static hipError_t launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                        bool nts, size_t lds, hipStream_t st)
+// the instantiations `k` names (frame_kernel.h), or null: every one this compilation carries is named here and nowhere else
+using CrowdFn = decltype(&RZ_CROWD_KERNEL<256, false, false>);
+using CrowdFkFn = decltype(&RZ_CROWD_FK_KERNEL<256, false>);
+static CrowdFn crowd_kernel(const RzFrameKernel &k)
 {
-    const bool sub = p.sub_list != nullptr;
-    auto k = sub ? (nts ? RZ_CROWD_KERNEL<BLOCK, true, true> : RZ_CROWD_KERNEL<BLOCK, false, true>)
-                 : (nts ? RZ_CROWD_KERNEL<BLOCK, true, false> : RZ_CROWD_KERNEL<BLOCK, false, false>);
+    constexpr CrowdFn none = nullptr;
+    return rz_pick<int, 256, 512, 1024>(k.block, none, [&](auto BLOCK) {
+    return rz_pick<bool, false, true>(k.nts, none, [&](auto NTS) {
+    return rz_pick<bool, false, true>(k.sub, none, [&](auto SUB) -> CrowdFn { return RZ_CROWD_KERNEL<RZ_V(BLOCK), RZ_V(NTS), RZ_V(SUB)>; }); }); });
+}
+static CrowdFkFn crowd_fk_kernel(const RzFrameKernel &k)
+{
+    constexpr CrowdFkFn none = nullptr;
+    return rz_pick<int, 256, 512, 1024>(k.block, none, [&](auto BLOCK) {
+    return rz_pick<bool, false, true>(k.nts, none, [&](auto NTS) -> CrowdFkFn {
+        if constexpr (!(MORPH && RZ_V(BLOCK) == 1024)) return RZ_CROWD_FK_KERNEL<RZ_V(BLOCK), RZ_V(NTS)>;      // (no MORPH front at 1024 threads: RzFrameKernel::carried)
+        else return none;
+    }); });
+}
+
+static hipError_t launch_crowd(const RzFrameKernel &k, const RzDeformParams &p, const RzLaunchShape &s, hipStream_t st)
+{
+    const CrowdFn fn = crowd_kernel(k);
+    if (!fn) return hipErrorInvalidValue;
     if (RZ_CROWD_MORPH && (!p.sp_ptr || !p.sp_entries || !p.morph_w || p.M <= 0 || p.Mpad < p.M)) return hipErrorInvalidValue;
-    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
-    dim3 grid(grid_x, (n_inst + G - 1) / G);
-    if (grid.x > 0xffffu || grid.y > 0xffffu || p.B > 0xffff || (sub && (p.sub_stride != p.B || p.sub_max <= 0 || p.sub_max > 0x3fff))) return hipErrorInvalidValue;      // (k_grid packs both; the lists' stride is the bone count; k_bf carries their padded length in 14 bits)
+    if (hipError_t e = rz_opt_in_lds(fn, s.lds)) return e;
+    dim3 grid(s.grid_x, (s.n_inst + s.G - 1) / s.G);
+    if (grid.x > 0xffffu || grid.y > 0xffffu || p.B > 0xffff || (k.sub && (!p.sub_list || p.sub_stride != p.B || p.sub_max <= 0 || p.sub_max > 0x3fff))) return hipErrorInvalidValue;      // (k_grid packs both; the lists' stride is the bone count; k_bf carries their padded length in 14 bits)
     // leading arguments = what the front of a workgroup needs, preloaded into SGPRs (see the kernel)
     const float4 *k_src = p.dma ? p.palette : reinterpret_cast<const float4 *>(p.world);
-    const uint32_t k_grid = grid.x | (grid.y << 16), k_bf = (uint32_t)p.B | (p.inst_order ? 1u << 16 : 0u) | (p.dma ? 1u << 17 : 0u) | (sub ? (uint32_t)p.sub_max << 18 : 0u);
-    hipLaunchKernelGGL(k, grid, dim3(BLOCK), lds, st, p.sub_count, p.sub_list, k_src, p.inv_bind, G, n_inst, verts_per_wg, k_grid, k_bf, p.Vp, p);
+    const uint32_t k_grid = grid.x | (grid.y << 16), k_bf = (uint32_t)p.B | (p.inst_order ? 1u << 16 : 0u) | (p.dma ? 1u << 17 : 0u) | (k.sub ? (uint32_t)p.sub_max << 18 : 0u);
+    hipLaunchKernelGGL(fn, grid, dim3(k.block), s.lds, st, p.sub_count, p.sub_list, k_src, p.inv_bind, s.G, s.n_inst, s.verts_per_wg, k_grid, k_bf, p.Vp, p);
     return hipGetLastError();
 }
 
-template <int BLOCK>
-static hipError_t launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x, bool nts,
-                                           size_t lds, hipStream_t st)
+static hipError_t launch_crowd_fk(const RzFrameKernel &k, const RzDeformParams &p, const RzSubFk &f, const RzLaunchShape &s, hipStream_t st)
 {
-    auto k = nts ? RZ_CROWD_FK_KERNEL<BLOCK, true> : RZ_CROWD_FK_KERNEL<BLOCK, false>;
-    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
-    dim3 grid(grid_x, (n_inst + G - 1) / G);
+    const CrowdFkFn fn = crowd_fk_kernel(k);
+    if (!fn) return hipErrorInvalidValue;
+    if (hipError_t e = rz_opt_in_lds(fn, s.lds)) return e;
+    dim3 grid(s.grid_x, (s.n_inst + s.G - 1) / s.G);
     const bool sampled = p.fk.sample.frames != nullptr;
     // (MORPH: the front stages the pose's morph weights out of memory; a sampled pose's are written by rz_fk_kernel, which this frame does not have)
     if (RZ_CROWD_MORPH && (!p.sp_ptr || !p.sp_entries || !p.morph_w || p.M <= 0 || p.Mpad < p.M || sampled)) return hipErrorInvalidValue;
     // what the kernel can take: two 16-bit grid fields, 16 bits of bone count, 12 bits of record stride, 2 bits of rounds, two work items per thread
-    if (grid.x > 0xffffu || grid.y > 0xffffu || p.B > 0xffff || f.stride > 0xfffu || f.rounds > 3 || (size_t)G * f.stride > 2 * (size_t)BLOCK || !p.sub_count || !p.rj01)
+    if (grid.x > 0xffffu || grid.y > 0xffffu || p.B > 0xffff || f.stride > 0xfffu || f.rounds > 3 || (size_t)s.G * f.stride > 2 * (size_t)k.block || !p.sub_count || !p.rj01)
         return hipErrorInvalidValue;
     const float4 *k_src = sampled ? reinterpret_cast<const float4 *>(p.fk.sample.frames) : p.fk.local_q;
     if (p.sub_max <= 0 || p.sub_max > 0x3fff) return hipErrorInvalidValue;
-    const uint32_t k_g = (uint32_t)G | (sampled ? 1u << 16 : 0u) | (p.fk.local_t ? 1u << 17 : 0u) | ((uint32_t)p.sub_max << 18);
+    const uint32_t k_g = (uint32_t)s.G | (sampled ? 1u << 16 : 0u) | (p.fk.local_t ? 1u << 17 : 0u) | ((uint32_t)p.sub_max << 18);
     const uint32_t k_grid = grid.x | (grid.y << 16), k_bf = (uint32_t)p.B | (p.inst_order ? 1u << 16 : 0u) | (f.rounds << 18) | (f.stride << 20);
-    hipLaunchKernelGGL(k, grid, dim3(BLOCK), lds, st, f.count, f.rec, k_src, p.inv_bind, k_g, n_inst, verts_per_wg, k_grid, k_bf, p.Vp, p);
+    hipLaunchKernelGGL(fn, grid, dim3(k.block), s.lds, st, f.count, f.rec, k_src, p.inv_bind, k_g, s.n_inst, s.verts_per_wg, k_grid, k_bf, p.Vp, p);
     return hipGetLastError();
 }
-
-#if RZ_CROWD_MORPH
-// the MORPH = true halves, for rz_launch_skin_instances / rz_launch_skin_instances_fk in the other unit
-hipError_t rz_launch_skin_instances_fk_morph_half(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                                  int block, bool nts, size_t lds_bytes, hipStream_t st)
+#if defined(RZ_ALL_VARIANTS) && !RZ_CROWD_MORPH
+// the register-resident form (measured slower, inst_loop = 9: a tools-only variant); s.G = poses per workgroup
+static hipError_t launch_crowd_reg(const RzFrameKernel &k, const RzDeformParams &p, const RzLaunchShape &s, hipStream_t st)
 {
-#else
-hipError_t rz_launch_skin_instances_fk_morph_half(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                                  int block, bool nts, size_t lds_bytes, hipStream_t st);      // kernels/crowd_morph.hip
-hipError_t rz_launch_skin_instances_morph_half(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                               int block, bool nts, size_t lds_bytes, hipStream_t st);
-
-hipError_t rz_launch_skin_instances_fk(const RzDeformParams &p, const RzSubFk &f, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                       int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs)
-{
-    if (morphs) return rz_launch_skin_instances_fk_morph_half(p, f, G, n_inst, verts_per_wg, grid_x, block, nts, lds_bytes, st);
-#endif
-#if RZ_CROWD_MORPH
-    // (no MORPH instantiation at 1024 threads: 128 VGPRs do not hold the front's two work items beside the row walk without scratch — the
-    // plan keeps rz_fk_kernel in front of such a frame)
-    if (block == 1024) return hipErrorInvalidValue;
-#else
-    if (block == 1024) return launch_skin_instances_fk<1024>(p, f, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
-#endif
-    if (block == 512) return launch_skin_instances_fk<512>(p, f, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
-    return launch_skin_instances_fk<256>(p, f, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
+    if (k.kv != 8 || s.G <= 0) return hipErrorInvalidValue;
+    const size_t lds = (size_t)2 * p.B * 48;         // (the 2-deep palette ring: its only spelling, the kernel indexes the ring by slot)
+    auto fn = k.nts ? rz_skin_instances_reg_kernel<8, true> : rz_skin_instances_reg_kernel<8, false>;
+    if (hipError_t e = rz_opt_in_lds(fn, lds)) return e;
+    dim3 grid(s.grid_x, (s.n_inst + s.G - 1) / s.G);
+    hipLaunchKernelGGL(fn, grid, dim3(kBlock), lds, st, p, s.n_inst, s.G);
+    return hipGetLastError();
 }
-
-#if RZ_CROWD_MORPH
-hipError_t rz_launch_skin_instances_morph_half(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                               int block, bool nts, size_t lds_bytes, hipStream_t st)
-{
-#else
-hipError_t rz_launch_skin_instances(const RzDeformParams &p, int G, int n_inst, uint32_t verts_per_wg, uint32_t grid_x,
-                                    int block, bool nts, size_t lds_bytes, hipStream_t st, bool morphs)
-{
-    if (morphs) return rz_launch_skin_instances_morph_half(p, G, n_inst, verts_per_wg, grid_x, block, nts, lds_bytes, st);
 #endif
-    if (block == 1024) return launch_skin_instances<1024>(p, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
-    if (block == 512) return launch_skin_instances<512>(p, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
-    return launch_skin_instances<256>(p, G, n_inst, verts_per_wg, grid_x, nts, lds_bytes, st);
+// This compilation's half of the crowd families: a record of the other half, or one this build does not carry, is refused here.
+hipError_t RZ_CROWD_LAUNCH(const RzFrameKernel &k, const RzDeformParams &p, const RzSubFk &f, const RzLaunchShape &s, hipStream_t st)
+{
+    if (k.morph != MORPH || !k.carried(kAllVariants)) return hipErrorInvalidValue;
+    switch (k.family) {
+    case kRzCrowd: return launch_crowd(k, p, s, st);
+    case kRzCrowdFk: return launch_crowd_fk(k, p, f, s, st);
+#if defined(RZ_ALL_VARIANTS) && !RZ_CROWD_MORPH
+    case kRzCrowdReg: return launch_crowd_reg(k, p, s, st);
+#endif
+    default: return hipErrorInvalidValue;
+    }
 }
 
 #if !RZ_CROWD_MORPH
@@ -665,21 +667,4 @@ hipError_t rz_launch_run_subsets(const uint32_t *j01, const uint32_t *j23, uint3
     hipLaunchKernelGGL(rz_run_subsets_kernel, dim3(runs), dim3(kBlock), lds, st, j01, j23, v_lim, per, B, list, count, rj01, rj23);
     return hipGetLastError();
 }
-
-hipError_t rz_launch_skin_instances_reg(const RzDeformParams &p, int n_inst, int poses_per_wg, uint32_t grid_x, bool nts,
-                                        hipStream_t st)
-{
-#ifdef RZ_ALL_VARIANTS
-    constexpr int KV = 8;
-    const size_t lds = (size_t)2 * p.B * 48;         // (the 2-deep palette ring: its only spelling, the kernel indexes the ring by slot)
-    auto k = nts ? rz_skin_instances_reg_kernel<KV, true> : rz_skin_instances_reg_kernel<KV, false>;
-    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
-    dim3 grid(grid_x, (n_inst + poses_per_wg - 1) / poses_per_wg);
-    hipLaunchKernelGGL(k, grid, dim3(kBlock), lds, st, p, n_inst, poses_per_wg);
-    return hipGetLastError();
-#else
-    (void)p; (void)n_inst; (void)poses_per_wg; (void)grid_x; (void)nts; (void)st;
-    return hipErrorInvalidValue;       // the register-resident crowd kernel (measured slower, inst_loop = 9) is a tools-only variant
 #endif
-}
-#endif  // !RZ_CROWD_MORPH

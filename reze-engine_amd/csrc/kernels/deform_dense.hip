@@ -387,86 +387,30 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_dense_kernel(const float 
 
 }  // namespace
 
-// ---- launch: which instantiations the library carries ----
-// The PRODUCT instantiates what a plan can select by default or through rz_autotune: rest geometry by 4-byte loads (GEO = false),
-// nontemporal morph loads (NT = true), 8 morphs in flight (U = 8) — 16 kernels. The variants measured slower everywhere (GEO = true,
-// NT = false, U = 4: profiles/archive/r1_*sweep*) live in the tools-only build (-DRZ_ALL_VARIANTS, `make variants`), where the parity tests
-// still cover every one of them; in the product rz_set_tuning refuses the keys that would select them.
-#ifdef RZ_ALL_VARIANTS
-constexpr bool kAllVariants = true;
-#else
-constexpr bool kAllVariants = false;
-#endif
-
-template <int S, int U, bool NT, bool NTS, bool GEO, bool FAST, int FKV = 0, bool Q24 = false>
-static hipError_t launch_one(const RzDeformParams &p, const RzMorphList &ml, dim3 grid, size_t lds, hipStream_t st)
-{
-    // FKV — which variant of the kernel (the shapes a plan selects only): 0 = everything compiled in (the fused consumers: outline hull,
-    // bounding box); 3 = without them; 1 / 2 = without them AND the hierarchy solve specialised for a plain uploaded / sampled pose
-    // 24-bit morph planes (a property of the resident targets, not of the plan): the same variant, reading them
-    if constexpr (!Q24) {
-        if (p.dense_fold) return launch_one<S, U, NT, NTS, GEO, FAST, FKV, true>(p, ml, grid, lds, st);
-    }
-    if constexpr (!GEO && NT && U == 8 && FKV == 0) {
-        if (!p.edge && !p.aabb) {
-            if constexpr (!FAST) {
-                if (p.fk_on && p.fk_kind == 1) return launch_one<S, U, NT, NTS, GEO, FAST, 1, Q24>(p, ml, grid, lds, st);
-                if (p.fk_on && p.fk_kind == 2) return launch_one<S, U, NT, NTS, GEO, FAST, 2, Q24>(p, ml, grid, lds, st);
-            }
-            return launch_one<S, U, NT, NTS, GEO, FAST, 3, Q24>(p, ml, grid, lds, st);
-        }
-    }
-    auto k = rz_deform_dense_kernel<S, U, NT, NTS, GEO, FAST, FKV, Q24>;
-    if (p.B > 0xffff) return hipErrorInvalidValue;      // k_bf carries the bone count in 16 bits (the 48 B per bone LDS palette keeps it far below today)
-    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
-    // the leading arguments (kernel-argument preload: deform_parts.hip.h) repeat fields of `p`; k_world is the pose the kernel asks for
-    // FIRST — the copy a helper may have staged when the frame looks for one, else p.world
-    // (!FAST: the hierarchy's static block and the motion's morph count ride in the two matrix slots, deform_parts.hip.h)
-    const float *k_world = FAST ? (p.st_tag ? p.st_world : p.world) : (p.fk_on ? reinterpret_cast<const float *>(p.fk.bone_rec) : nullptr);
-    const float *k_inv_bind = FAST ? p.inv_bind : reinterpret_cast<const float *>((uintptr_t)(p.fk_on ? p.fk.sample.M : 0));
-    hipLaunchKernelGGL(k, grid, dim3(kBlock), lds, st, p.geom, k_world, k_inv_bind, rz_deform_k_bf(p, grid.x), p.Vp, p.n_quads, p.quads_per_wave, p.joints01, p.joints23, p.weights, p, ml);
-    return hipGetLastError();
-}
-
-template <int S, int U, bool NT, bool NTS>
-static hipError_t launch_gf(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st)
-{
-    if constexpr (kAllVariants) {
-        if (v.geo) return v.fast ? launch_one<S, U, NT, NTS, true, true>(p, ml, grid, lds, st)
-                                 : launch_one<S, U, NT, NTS, true, false>(p, ml, grid, lds, st);
-    } else if (v.geo) return hipErrorInvalidValue;
-    return v.fast ? launch_one<S, U, NT, NTS, false, true>(p, ml, grid, lds, st)
-                  : launch_one<S, U, NT, NTS, false, false>(p, ml, grid, lds, st);
-}
-
-template <int S, int U>
-static hipError_t launch_nt(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st)
-{
-    if (v.nt || !kAllVariants) {
-        if (!v.nt) return hipErrorInvalidValue;
-        return v.nts ? launch_gf<S, U, true, true>(p, ml, v, grid, lds, st) : launch_gf<S, U, true, false>(p, ml, v, grid, lds, st);
-    }
-    if constexpr (kAllVariants)
-        return v.nts ? launch_gf<S, U, false, true>(p, ml, v, grid, lds, st) : launch_gf<S, U, false, false>(p, ml, v, grid, lds, st);
-    return hipErrorInvalidValue;
-}
-
-template <int S>
-static hipError_t launch_split(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st)
-{
-    if (v.U >= 8) return launch_nt<S, 8>(p, ml, v, grid, lds, st);
-    if constexpr (kAllVariants) return launch_nt<S, 4>(p, ml, v, grid, lds, st);
-    return hipErrorInvalidValue;
-}
-
 bool rz_has_all_variants() { return kAllVariants; }
 
-hipError_t rz_launch_deform_dense(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st)
+// ---- launch: the instantiation `k` names (frame_kernel.h), or null. Every one a build carries is named here and nowhere else: the
+// PRODUCT what a plan can select by default or through rz_autotune, the tools-only build (`make variants`) also the variants measured
+// slower everywhere (GEO, !NT, U = 4: profiles/archive/r1_*sweep*); which is which, RzFrameKernel::carried() says ----
+using DenseFn = decltype(&rz_deform_dense_kernel<1, 8, true, false, false, false, 0, false>);
+static DenseFn dense_kernel(const RzFrameKernel &k)
 {
-    switch (v.S) {
-    case 2: return launch_split<2>(p, ml, v, grid, lds, st);
-    case 4: return launch_split<4>(p, ml, v, grid, lds, st);
-    case 8: return launch_split<8>(p, ml, v, grid, lds, st);
-    default: return launch_split<1>(p, ml, v, grid, lds, st);
-    }
+    constexpr DenseFn none = nullptr;
+    return rz_pick<int, 1, 2, 4, 8>(k.S, none, [&](auto S) {
+    return rz_pick<int, 4, 8>(k.U, none, [&](auto U) {
+    return rz_pick<bool, false, true>(k.nt, none, [&](auto NT) {
+    return rz_pick<bool, false, true>(k.nts, none, [&](auto NTS) {
+    return rz_pick<bool, false, true>(k.geo, none, [&](auto GEO) {
+    return rz_pick<bool, false, true>(k.fast, none, [&](auto FAST) {
+    return rz_pick<int, 0, 1, 2, 3>(k.fkv, none, [&](auto FKV) {
+    return rz_pick<bool, false, true>(k.q24, none, [&](auto Q24) -> DenseFn {
+        if constexpr (RzFrameKernel{ kRzDense, RZ_V(S), RZ_V(U), 1, RZ_V(FKV), 0, 0, 0, 0, RZ_V(NT), RZ_V(NTS), RZ_V(GEO), RZ_V(FAST), RZ_V(Q24) }.carried(kAllVariants))
+            return rz_deform_dense_kernel<RZ_V(S), RZ_V(U), RZ_V(NT), RZ_V(NTS), RZ_V(GEO), RZ_V(FAST), RZ_V(FKV), RZ_V(Q24)>;
+        else return none;
+    }); }); }); }); }); }); }); });
+}
+
+hipError_t rz_launch_deform_dense(const RzFrameKernel &k, const RzDeformParams &p, const RzMorphList &ml, const RzLaunchShape &s, hipStream_t st)
+{
+    return launch_one_mesh(k.carried(kAllVariants) ? dense_kernel(k) : nullptr, k, p, s, st, ml);
 }

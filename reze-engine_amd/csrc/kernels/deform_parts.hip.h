@@ -186,4 +186,18 @@ inline uint32_t rz_deform_k_bf(const RzDeformParams &p, const uint32_t grid_x)
     return (uint32_t)p.B | (p.pf_src ? 1u << 16 : 0u) | (p.st_tag ? 1u << 17 : 0u) | (p.world_copy ? 1u << 18 : 0u) | (workers < 8192u ? workers << 19 : 0u);
 }
 
+// The launch of a one-mesh frame kernel (`fn`: the instantiation the record names, null when this build does not carry it; tail: the dense kernel's
+// RzMorphList). The leading arguments (top of the file) repeat fields of `p`; k_world is the pose the kernel asks for FIRST — the copy a helper may
+// have staged when the frame looks for one, else p.world (!FAST: the hierarchy's static block and the motion's morph count ride in the two matrix slots).
+template <class Fn, class... Tail>
+inline hipError_t launch_one_mesh(Fn fn, const RzFrameKernel &k, const RzDeformParams &p, const RzLaunchShape &s, hipStream_t st, const Tail &...tail)
+{
+    if (!fn || p.B > 0xffff) return hipErrorInvalidValue;      // k_bf carries the bone count in 16 bits (the 48 B per bone LDS palette keeps it far below today)
+    if (hipError_t e = rz_opt_in_lds(fn, s.lds)) return e;
+    const float *k_world = k.fast ? (p.st_tag ? p.st_world : p.world) : (p.fk_on ? reinterpret_cast<const float *>(p.fk.bone_rec) : nullptr);
+    const float *k_inv_bind = k.fast ? p.inv_bind : reinterpret_cast<const float *>((uintptr_t)(p.fk_on ? p.fk.sample.M : 0));
+    hipLaunchKernelGGL(fn, dim3(s.grid_x, s.n_inst), dim3(kBlock), s.lds, st, p.geom, k_world, k_inv_bind, rz_deform_k_bf(p, s.grid_x), p.Vp, p.n_quads, p.quads_per_wave, p.joints01, p.joints23, p.weights, p, tail...);
+    return hipGetLastError();
+}
+
 }  // namespace

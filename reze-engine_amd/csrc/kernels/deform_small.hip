@@ -416,52 +416,24 @@ __global__ void __launch_bounds__(kBlock, 2) rz_deform_small_kernel(const float 
 
 }  // namespace
 
-#ifdef RZ_ALL_VARIANTS
-constexpr bool kAllVariants = true;
-#else
-constexpr bool kAllVariants = false;
-#endif
-
-template <int S, int MODE, bool NTS, bool GEO, bool FAST, int FKV = 0>
-static hipError_t launch_one(const RzDeformParams &p, dim3 grid, size_t lds, hipStream_t st)
+// the instantiation `k` names (frame_kernel.h), or null: every one this build carries is named here and nowhere else
+using SmallFn = decltype(&rz_deform_small_kernel<1, 0, false, false, false, 0>);
+static SmallFn small_kernel(const RzFrameKernel &k)
 {
-    // FKV — which variant of the kernel: 0 = everything compiled in (the fused consumers: outline hull, bounding box); 3 = without them;
-    // 1 / 2 = without them AND the hierarchy solve specialised for a plain uploaded / sampled pose (fk_solve<true, KIND>)
-    if constexpr (!GEO && FKV == 0) {
-        if (!p.edge && !p.aabb) {
-            if constexpr (!FAST) {
-                if (p.fk_on && p.fk_kind == 1) return launch_one<S, MODE, NTS, GEO, FAST, 1>(p, grid, lds, st);
-                if (p.fk_on && p.fk_kind == 2) return launch_one<S, MODE, NTS, GEO, FAST, 2>(p, grid, lds, st);
-            }
-            return launch_one<S, MODE, NTS, GEO, FAST, 3>(p, grid, lds, st);
-        }
-    }
-    auto k = rz_deform_small_kernel<S, MODE, NTS, GEO, FAST, FKV>;
-    if (p.B > 0xffff) return hipErrorInvalidValue;      // k_bf carries the bone count in 16 bits
-    if (hipError_t e = rz_opt_in_lds(k, lds)) return e;
-    // (!FAST: the hierarchy's static block and the motion's morph count ride in the two matrix slots, deform_parts.hip.h)
-    const float *k_world = FAST ? (p.st_tag ? p.st_world : p.world) : (p.fk_on ? reinterpret_cast<const float *>(p.fk.bone_rec) : nullptr);
-    const float *k_inv_bind = FAST ? p.inv_bind : reinterpret_cast<const float *>((uintptr_t)(p.fk_on ? p.fk.sample.M : 0));
-    hipLaunchKernelGGL(k, grid, dim3(kBlock), lds, st, p.geom, k_world, k_inv_bind, rz_deform_k_bf(p, grid.x), p.Vp, p.n_quads, p.quads_per_wave, p.joints01, p.joints23, p.weights, p);
-    return hipGetLastError();
+    constexpr SmallFn none = nullptr;
+    return rz_pick<int, 1, 4>(k.S, none, [&](auto S) {
+    return rz_pick<int, 0, 2>(k.mode, none, [&](auto MODE) {
+    return rz_pick<bool, false, true>(k.nts, none, [&](auto NTS) {
+    return rz_pick<bool, false, true>(k.geo, none, [&](auto GEO) {
+    return rz_pick<bool, false, true>(k.fast, none, [&](auto FAST) {
+    return rz_pick<int, 0, 1, 2, 3>(k.fkv, none, [&](auto FKV) -> SmallFn {
+        if constexpr (RzFrameKernel{ kRzSmall, RZ_V(S), 8, RZ_V(MODE), RZ_V(FKV), 0, 0, 0, 0, true, RZ_V(NTS), RZ_V(GEO), RZ_V(FAST) }.carried(kAllVariants))
+            return rz_deform_small_kernel<RZ_V(S), RZ_V(MODE), RZ_V(NTS), RZ_V(GEO), RZ_V(FAST), RZ_V(FKV)>;
+        else return none;
+    }); }); }); }); }); });
 }
 
-template <int S, int MODE>
-static hipError_t launch_mode(const RzDeformParams &p, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st)
+hipError_t rz_launch_deform_small(const RzFrameKernel &k, const RzDeformParams &p, const RzLaunchShape &s, hipStream_t st)
 {
-    if (v.geo) {
-        if constexpr (kAllVariants) {
-            if (v.nts) return v.fast ? launch_one<S, MODE, true, true, true>(p, grid, lds, st) : launch_one<S, MODE, true, true, false>(p, grid, lds, st);
-            return v.fast ? launch_one<S, MODE, false, true, true>(p, grid, lds, st) : launch_one<S, MODE, false, true, false>(p, grid, lds, st);
-        }
-        return hipErrorInvalidValue;      // rest geometry through LDS is a tools-only variant
-    }
-    if (v.nts) return v.fast ? launch_one<S, MODE, true, false, true>(p, grid, lds, st) : launch_one<S, MODE, true, false, false>(p, grid, lds, st);
-    return v.fast ? launch_one<S, MODE, false, false, true>(p, grid, lds, st) : launch_one<S, MODE, false, false, false>(p, grid, lds, st);
-}
-
-hipError_t rz_launch_deform_small(const RzDeformParams &p, const RzVariant &v, dim3 grid, size_t lds, hipStream_t st)
-{
-    if (v.mode == 0) return v.S == 4 ? launch_mode<4, 0>(p, v, grid, lds, st) : launch_mode<1, 0>(p, v, grid, lds, st);
-    return v.S == 4 ? launch_mode<4, 2>(p, v, grid, lds, st) : launch_mode<1, 2>(p, v, grid, lds, st);
+    return launch_one_mesh(k.carried(kAllVariants) ? small_kernel(k) : nullptr, k, p, s, st);
 }

@@ -239,12 +239,13 @@ hipError_t rz_launch_pack_skinning(const uint16_t *joints4, const uint8_t *weigh
 
 uint32_t rz_quads_per_tile(int S) { return (kBlock / 64) * (64 / S); }
 
-// One mesh, one launch: the dense morph stream (deform_dense.hip) or the latency-bound frame without one (deform_small.hip)
-hipError_t rz_launch_deform(const RzDeformParams &p, const RzMorphList &ml, const RzVariant &v, uint32_t grid_x,
-                            uint32_t instances, hipStream_t st)
+// The frame's kernel, to the file of its family: the dense morph stream (deform_dense.hip), the latency-bound frame without one
+// (deform_small.hip), a crowd's pose groups (crowd.hip, and crowd_morph.hip for its MORPH half)
+hipError_t rz_launch_frame(const RzFrameKernel &k, const RzDeformParams &p, const RzMorphList &ml, const RzSubFk &f, const RzLaunchShape &s, hipStream_t st)
 {
-    const size_t lds = rz_deform_lds_bytes(p, v);
-    dim3 grid(grid_x, instances);
-    if (v.mode == 1) return rz_launch_deform_dense(p, ml, v, grid, lds, st);
-    return rz_launch_deform_small(p, v, grid, lds, st);
+    switch (k.family) {
+    case kRzDense: return rz_launch_deform_dense(k, p, ml, s, st);
+    case kRzSmall: return rz_launch_deform_small(k, p, s, st);
+    default: return k.morph ? rz_launch_crowd_morph(k, p, f, s, st) : rz_launch_crowd(k, p, f, s, st);
+    }
 }

@@ -146,6 +146,12 @@ RzDeformParams deform_params(const rz_ctx *c, const Plan &pl)
     return p;
 }
 
+// The single statement of which kernel a frame launches (ctx.h): rz_frame_kernel over the plan and three facts of its parameter block
+RzFrameKernel frame_kernel(const Plan &pl, const RzDeformParams &p)
+{
+    return rz_frame_kernel({ pl.v, p.edge || p.aabb, p.fk_on != 0, p.fk_kind, p.dense_fold != nullptr, pl.inst_group, pl.inst_block, pl.subsets, pl.subfk, pl.inst_morphs, pl.poses_per_wg });
+}
+
 // The shape the caller ASKS for (inst_loop / inst_block / grid_cap or the defaults), before LDS limits the group size; when
 // bone subsets are allowed it is the shape of the SUBSET form (the whole-palette fallback sizes its own grid).
 bool inst_shape(const rz_ctx *c, InstShape *s)

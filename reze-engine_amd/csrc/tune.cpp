@@ -11,22 +11,25 @@ namespace {
 // kAlways clears it even when the value is then refused as invalid: deliberate, kept for compatibility, not an accident. kAccepted: only with the store.
 enum { kNo, kAlways, kAccepted };
 struct TuneKey { const char *name; int RzTuning::*field; int (*check)(int &v); const char *refusal; int shape; };
-int tools_only(bool selected) { return selected && !rz_has_all_variants() ? RZ_ERR_UNSUPPORTED : RZ_OK; }
+// (the records a key selects: the dense frame with that unroll, those morph loads and that rest-geometry path; the register crowd form)
+int tools_only(const RzFrameKernel &k) { return k.carried(rz_has_all_variants()) ? RZ_OK : RZ_ERR_UNSUPPORTED; }
+constexpr RzFrameKernel dense(int U, bool nt, bool geo) { return RzFrameKernel{ kRzDense, 1, U, 1, 0, 0, 0, 0, 0, nt, false, geo }; }
+constexpr RzFrameKernel kRegForm = { kRzCrowdReg };
 int need(bool ok) { return ok ? RZ_OK : RZ_ERR_INVALID; }
 template <int lo, int hi> int within(int &v) { return need(v >= lo && v <= hi); }
 const TuneKey kTuneKeys[] = {
     { "morph_split", &RzTuning::t_split, [](int &v) { return need(v == 0 || v == 1 || v == 2 || v == 4 || v == 8); }, "morph_split must be 0 (auto),1,2,4,8", kAlways },
-    { "unroll", &RzTuning::t_unroll, [](int &v) { return v == 4 ? tools_only(true) : need(v == 0 || v == 8); }, "unroll must be 0 (auto), 4 or 8", kNo },
+    { "unroll", &RzTuning::t_unroll, [](int &v) { return v == 4 ? tools_only(dense(4, true, false)) : need(v == 0 || v == 8); }, "unroll must be 0 (auto), 4 or 8", kNo },
     { "grid_cap", &RzTuning::t_grid_cap, [](int &v) { return need(v >= 0); }, "grid_cap must be >= 0", kAlways },
-    { "nontemporal", &RzTuning::t_nt, [](int &v) { v = v ? 1 : 0; return tools_only(v == 0); }, nullptr, kNo },
-    { "geo_lds", &RzTuning::t_geo, [](int &v) { v = v ? 1 : 0; return tools_only(v != 0); }, nullptr, kNo },
+    { "nontemporal", &RzTuning::t_nt, [](int &v) { v = v ? 1 : 0; return tools_only(dense(8, v != 0, false)); }, nullptr, kNo },
+    { "geo_lds", &RzTuning::t_geo, [](int &v) { v = v ? 1 : 0; return tools_only(dense(8, true, v != 0)); }, nullptr, kNo },
     { "nt_store", &RzTuning::t_nts, [](int &v) { v = v < 0 ? -1 : (v ? 1 : 0); return (int)RZ_OK; }, nullptr, kNo },
     { "out_cap", &RzTuning::t_outcap, within<-1, 2048>, "out_cap must be -1 (auto), 0 (off) or 64..2048 vertices per wave", kNo },
     { "sparse_piece", &RzTuning::t_sppiece, [](int &v) { return need(v == 0 || (v >= 16 && v <= 2048 && v % 16 == 0)); },
       "sparse_piece must be 0 (auto) or a multiple of 16 in 16..2048 entries of the sparse CSR per wave", kNo },
     { "inst_morphs", &RzTuning::t_instmorphs, within<-1, 1>, "inst_morphs must be -1 (auto = off), 0 (a crowd with sparse morph targets always runs the generic kernel) or 1 (it takes the crowd kernels where they fit)", kNo },
     { "graph", &RzTuning::t_graph, within<0, 1>, "graph must be 0 or 1", kNo },
-    { "inst_loop", &RzTuning::t_instloop, [](int &v) { return v == 9 ? tools_only(true) : need(v >= -1 && v != 1 && v <= 64); },
+    { "inst_loop", &RzTuning::t_instloop, [](int &v) { return v == 9 ? tools_only(kRegForm) : need(v >= -1 && v != 1 && v <= 64); },
       "inst_loop must be -1 (auto), 0 (off), 2..8 / 10..64 (poses per workgroup, LDS form) or 9 (register form)", kAlways },
     { "pose_prefetch", &RzTuning::t_prefetch, within<-1, 1>, "pose_prefetch must be -1 (auto = on), 0 (a zero-copy frame never stages the next pose) or 1", kNo },
     { "inst_subsets", &RzTuning::t_subsets, within<-1, 1>, "inst_subsets must be -1 (auto = on), 0 (crowd frames always stage the whole palette) or 1", kNo },
@@ -111,8 +114,7 @@ int rz_autotune_measure(rz_ctx *c, uint32_t frames, rz_tune_entry *table, int ca
         // plan for ~0.25 s first, untimed
         c->t_split = cands[0].morph_split; c->t_grid_cap = cands[0].grid_cap; c->t_instloop = instanced ? cands[0].inst_loop : keep_loop;
         Plan warm;
-        rc = frame_plan(c, &warm);      // (a crowd's run lists belong to ONE launch shape: bring them back to entry 0's)
-        if (rc == RZ_OK) rc = set_overlap(c, want_overlap(c, warm));
+        rc = begin_frames(c, &warm);    // (a crowd's run lists belong to ONE launch shape: bring them back to entry 0's)
         const auto t0 = std::chrono::steady_clock::now();
         while (rc == RZ_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(250)) {
             for (uint32_t f = 0; f < 64 && rc == RZ_OK; ++f) rc = run_frame(c, warm);
@@ -124,8 +126,7 @@ int rz_autotune_measure(rz_ctx *c, uint32_t frames, rz_tune_entry *table, int ca
             if (cands[i].same_as >= 0) continue;
             c->t_split = cands[i].morph_split; c->t_grid_cap = cands[i].grid_cap; c->t_instloop = instanced ? cands[i].inst_loop : keep_loop;
             Plan pl;
-            if ((rc = frame_plan(c, &pl)) != RZ_OK) break;       // crowd shapes alternate: the run lists follow (a rebuild, untimed)
-            if ((rc = set_overlap(c, want_overlap(c, pl))) != RZ_OK) break;
+            if ((rc = begin_frames(c, &pl)) != RZ_OK) break;     // crowd shapes alternate: the run lists follow (a rebuild, untimed)
             const uint32_t nf = round < 0 ? 8 : frames;
             for (uint32_t f = 0; f < 4 && rc == RZ_OK; ++f) rc = run_frame(c, pl);
             if (rc != RZ_OK) break;
@@ -178,7 +179,7 @@ int rz_autotune_apply(rz_ctx *c, const rz_tune_entry *e)
     const int sp = e->morph_split;
     if (sp != 0 && sp != 1 && sp != 2 && sp != 4 && sp != 8) return fail(RZ_ERR_INVALID, "rz_autotune_apply: morph_split %d", sp);
     if (e->grid_cap < 0 || e->inst_loop < -1 || e->inst_loop == 1 || e->inst_loop > 64) return fail(RZ_ERR_INVALID, "rz_autotune_apply: bad entry");
-    if (e->inst_loop == 9 && !rz_has_all_variants())
+    if (e->inst_loop == 9 && tools_only(kRegForm))
         return fail(RZ_ERR_UNSUPPORTED, "rz_autotune_apply: inst_loop = 9 selects the register-resident crowd kernel, which the product library does not carry");
     // a caller who switched the crowd kernel off (inst_loop = 0) or chose the register form (9) keeps that choice: the entry's
     // pose-group size only applies where the search itself would have used one
@@ -223,17 +224,95 @@ int rz_set_tuning(rz_ctx *c, const char *key, int value)
     return RZ_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The read keys: name, whether the key describes the NEXT frame, and a getter. For a key of the next frame rz_get_tuning resolves that
+// frame ONCE — plan, parameter block and the kernel record (frame_kernel.h) — and the getter reads it; which kernel that frame launches
+// is read from the record alone. A key that is not in the table (or among the settable ones) is unknown, and refused before any work.
+struct Next { Plan pl; RzDeformParams dp; RzFrameKernel k; };
+struct ReadKey { const char *name; bool next; int (*get)(rz_ctx *c, const Next &n, int *value); };
+#define RZ_GET(expr) [](rz_ctx *c, const Next &n, int *value) -> int { (void)c; (void)n; *value = (int)(expr); return RZ_OK; }
+// diagnostics (tools/archive/placement.py): where the allocator put a buffer — bits [12, 43) of its device address, i.e. the address in
+// 4 KB pages (where a buffer lands relative to the 2 MB large-page frame moves the C5 frame by 3 %: NOTEBOOK.md R5.3)
+int page_of(const void *ptr) { return (int)(((uintptr_t)ptr >> 12) & 0x7fffffffu); }
+const ReadKey kReadKeys[] = {
+    { "bones", false, RZ_GET(c->skel.B) }, { "morphs", false, RZ_GET(c->morphs.M) }, { "instances", false, RZ_GET(c->I) }, { "verts", false, RZ_GET(c->mesh.V) },
+    { "sdef_verts", false, RZ_GET(c->sdef.n) }, { "qdef_verts", false, RZ_GET(c->qdef.n) }, { "ik_chains", false, RZ_GET(c->ik.n) },
+    { "motion_clips", false, RZ_GET(c->lib.clips) }, { "motion_masks", false, RZ_GET(c->mk.count) }, { "morph_mode", false, RZ_GET(c->morphs.mode) },
+    { "physics_bodies", false, RZ_GET(c->ph.nb) }, { "physics_joints", false, RZ_GET(c->ph.nj) }, { "physics_colours", false, RZ_GET(c->ph.ncol) },
+    // the form rz_launch_physics takes for the resident table (kernels/physics.hip): lanes per workgroup, joints kept in registers (1) or
+    // strided over a colour (0), dynamic LDS per workgroup; all 0 without a table
+    { "physics_block", false, RZ_GET(c->ph.nb ? c->ph.block : 0) }, { "physics_own", false, RZ_GET((c->ph.nb && (int)c->ph.nj <= c->ph.block) ? 1 : 0) },
+    { "physics_lds", false, RZ_GET(c->ph.nb ? rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0) },
+    { "physics_contacts", false, RZ_GET(c->ph.contacts.mode) }, { "physics_contact_follow", false, RZ_GET(c->ph.contacts.follow) },
+    { "physics_contact_pairs", false, RZ_GET(c->ph.contacts.pairs) }, { "physics_contact_colours", false, RZ_GET(c->ph.contacts.ncol) },
+    { "physics_contact_boxes", false, RZ_GET(c->ph.contacts.boxes) }, { "physics_contact_box_pairs", false, RZ_GET(c->ph.contacts.box_pairs) },
+    { "physics_contact_box_box", false, RZ_GET(c->ph.contacts.box_box) },
+    { "physics_springs", false, RZ_GET(c->ph.springs.on) }, { "physics_spring_axes", false, RZ_GET(c->ph.springs.axes) },
+    { "physics_aligned", false, RZ_GET(c->ph.aligned.on) }, { "physics_aligned_bodies", false, RZ_GET(c->ph.aligned.n) },
+    { "override_follow", false, RZ_GET(c->ovr_follow) },
+    { "override_followers", false, RZ_GET(solve_stages(c).fo.off ? c->fol_count : 0) },     // entries resident over all instances
+    { "after_physics", false, RZ_GET(c->af.n) }, { "after_physics_levels", false, RZ_GET(c->af.levels) },       // entries resident (rz_upload_after_physics), their levels
+    { "ik_stages", false, RZ_GET(c->ik.stages) }, { "ik_switched", false, RZ_GET(c->iksw.off) },       // ik_switched: (instance, chain) bits currently off
+    { "ik_key_sets", false, [](rz_ctx *c, const Next &, int *value) -> int {
+          int n = c->ik_keys_an.resident ? 1 : 0;
+          for (const RzIkKeySet &s : c->ik_keys_mo) n += s.resident ? 1 : 0;
+          *value = n;
+          return RZ_OK;
+      } },
+    { "pose_pulled", false, RZ_GET(c->pl.last_pulled ? 1 : 0) },      // the most recent copied pose came down by rz_pull_pose_kernel ...
+    { "pose_rows", false, RZ_GET(c->pl.last_rows ? 1 : 0) },          // ... its world matrices as three rows per bone
+    { "pose_resident", false, RZ_GET(c->pl.cur.resident() ? 1 : 0) }, { "all_variants", false, RZ_GET(rz_has_all_variants() ? 1 : 0) },
+    { "pose_staged", false, [](rz_ctx *c, const Next &, int *value) -> int {
+          // did the helper of an earlier frame stage the CURRENT pose in device memory? (synchronises; for tests and tools)
+          *value = 0;
+          if (c->pl.tag && c->pl.cur.seq) {
+              uint64_t tags[2] = {0, 0};
+              HIP_TRY(hipSetDevice(c->device));
+              HIP_TRY(hipStreamSynchronize(c->stream));
+              HIP_TRY(hipMemcpy(tags, c->pl.tag, sizeof tags, hipMemcpyDeviceToHost));
+              *value = tags[c->pl.pose_slot] == c->pl.cur.seq ? 1 : 0;
+          }
+          return RZ_OK;
+      } },
+    { "addr_dense", false, RZ_GET(page_of(c->morphs.dense)) }, { "addr_out", false, RZ_GET(page_of(c->out_pos)) },
+    { "addr_nrm", false, RZ_GET(page_of(c->out_nrm)) }, { "addr_geom", false, RZ_GET(page_of(c->mesh.geom)) },
+    // ---- the next frame's kernel: the record ----
+    { "effective_variant", true, RZ_GET(n.k.fkv) },      // the single-mesh frame kernel's last template argument (the FKV rule: rz_frame_kernel)
+    { "effective_nt", true, RZ_GET(n.k.nt && n.k.mode == 1 ? 1 : 0) }, { "effective_nt_store", true, RZ_GET(n.k.nts ? 1 : 0) },
+    { "effective_geo", true, RZ_GET(n.k.geo ? 1 : 0) }, { "effective_fast", true, RZ_GET(n.k.fast ? 1 : 0) },
+    { "effective_split", true, RZ_GET(n.k.S) }, { "effective_unroll", true, RZ_GET(n.k.U) },
+    // (block / sub / morph are zero outside the pose-group families; so are the Plan's fields: make_plan fills them in its crowd branch only,
+    // which the register form's inst_loop = 9 never enters)
+    { "effective_inst_block", true, RZ_GET(n.k.block) }, { "effective_subsets", true, RZ_GET(n.k.sub ? 1 : 0) },
+    { "effective_inst_morphs", true, RZ_GET(n.k.morph ? 1 : 0) },     // the frame walks sparse morph rows in a crowd kernel
+    { "effective_fuse_fk", true, RZ_GET(n.k.solve ? 1 : 0) },
+    { "effective_poses_per_wg", true, RZ_GET(n.k.poses_per_wg) }, { "effective_inst_group", true, RZ_GET(n.k.group) },
+    // ---- the next frame's launch shape, parameter block and front ----
+    { "effective_fk_kind", true, RZ_GET(n.dp.fk_kind) }, { "effective_morph_storage", true, RZ_GET(c->morphs.mode == 1 ? c->morphs.storage : 0) },
+    { "effective_prep", true, RZ_GET(has_front(c, n.pl) ? 1 : 0) }, { "effective_overlap", true, RZ_GET(want_overlap(c, n.pl) ? 1 : 0) },
+    { "effective_closure_bones", true, RZ_GET(n.pl.subfk ? c->subfk_stride : 0) },
+    { "effective_closure_rounds", true, RZ_GET(n.pl.subfk ? c->subfk_rounds : 0) },      // radix-4 doubling rounds of that front (0 .. 3)
+    { "effective_out_cap", true, RZ_GET(n.pl.out_cap) }, { "effective_grid", true, RZ_GET(n.pl.grid_x) },
+    { "effective_sparse_piece", true, RZ_GET(n.pl.sp_cap) },      // 0 without resident sparse targets (make_plan sizes it for MODE 2 only)
+    { "effective_subset_bones", true, RZ_GET(n.pl.sub_bones) }, { "effective_inst_lds", true, RZ_GET(n.pl.inst_lds) },
+};
+#undef RZ_GET
+}  // namespace
+
+extern "C" {
+
 int rz_get_tuning(rz_ctx *c, const char *key, int *value)
 {
     if (!c || !key || !value) return fail(RZ_ERR_INVALID, "null argument");
     if (const TuneKey *k = find_key(key)) { *value = c->*k->field; return RZ_OK; }
-    if (!strncmp(key, "effective_", 10)) {
-        // (an unknown key is refused BEFORE the work below: it drains the stream and may rebuild the run lists)
-        static const char *const known[] = { "nt", "nt_store", "geo", "prep", "split", "unroll", "fast", "variant", "fk_kind", "fuse_fk", "closure_bones", "closure_rounds",
-                                             "overlap", "inst_block", "out_cap", "inst_group", "poses_per_wg", "grid", "subsets", "subset_bones", "inst_lds", "morph_storage", "sparse_piece", "inst_morphs" };
-        bool ok = false;
-        for (const char *k : known) ok = ok || !strcmp(key + 10, k);
-        if (!ok) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
+    const ReadKey *row = nullptr;
+    for (const ReadKey &k : kReadKeys)
+        if (!strcmp(key, k.name)) row = &k;
+    if (!row) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
+    Next n;     // resolved for a key of the next frame only; the other getters do not read it
+    if (row->next) {
         // what the NEXT frame will launch: a crowd's plan depends on the run lists of its launch shape, so bring them up to
         // date first (as every entry point that launches frames does) instead of describing the whole-palette fallback
         if (int r = use(c)) return r;
@@ -241,104 +320,11 @@ int rz_get_tuning(rz_ctx *c, const char *key, int *value)
             if (int r = ensure_run_subsets(c)) return r;
             if (int r = ensure_subfk(c)) return r;
         }
+        n.pl = make_plan(c);
+        n.dp = deform_params(c, n.pl);
+        n.k = frame_kernel(n.pl, n.dp);
     }
-    if (!strcmp(key, "bones")) *value = (int)c->skel.B;
-    else if (!strcmp(key, "morphs")) *value = (int)c->morphs.M;
-    else if (!strcmp(key, "instances")) *value = (int)c->I;
-    else if (!strcmp(key, "verts")) *value = (int)c->mesh.V;
-    else if (!strcmp(key, "sdef_verts")) *value = (int)c->sdef.n;
-    else if (!strcmp(key, "qdef_verts")) *value = (int)c->qdef.n;
-    else if (!strcmp(key, "ik_chains")) *value = (int)c->ik.n;
-    else if (!strcmp(key, "motion_clips")) *value = (int)c->lib.clips;
-    else if (!strcmp(key, "motion_masks")) *value = (int)c->mk.count;
-    else if (!strcmp(key, "physics_bodies")) *value = (int)c->ph.nb;
-    else if (!strcmp(key, "physics_joints")) *value = (int)c->ph.nj;
-    else if (!strcmp(key, "physics_colours")) *value = (int)c->ph.ncol;
-    // the form rz_launch_physics takes for the resident table (kernels/physics.hip): lanes per workgroup, joints kept in registers (1) or
-    // strided over a colour (0), dynamic LDS per workgroup; all 0 without a table
-    else if (!strcmp(key, "physics_block")) *value = c->ph.nb ? c->ph.block : 0;
-    else if (!strcmp(key, "physics_own")) *value = (c->ph.nb && (int)c->ph.nj <= c->ph.block) ? 1 : 0;
-    else if (!strcmp(key, "physics_contacts")) *value = c->ph.contacts.mode;
-    else if (!strcmp(key, "physics_contact_follow")) *value = (int)c->ph.contacts.follow;
-    else if (!strcmp(key, "physics_contact_pairs")) *value = (int)c->ph.contacts.pairs;
-    else if (!strcmp(key, "physics_contact_colours")) *value = (int)c->ph.contacts.ncol;
-    else if (!strcmp(key, "physics_contact_boxes")) *value = (int)c->ph.contacts.boxes;
-    else if (!strcmp(key, "physics_contact_box_pairs")) *value = (int)c->ph.contacts.box_pairs;
-    else if (!strcmp(key, "physics_contact_box_box")) *value = (int)c->ph.contacts.box_box;
-    else if (!strcmp(key, "physics_springs")) *value = c->ph.springs.on;
-    else if (!strcmp(key, "physics_spring_axes")) *value = (int)c->ph.springs.axes;
-    else if (!strcmp(key, "physics_aligned")) *value = c->ph.aligned.on;
-    else if (!strcmp(key, "physics_aligned_bodies")) *value = (int)c->ph.aligned.n;
-    else if (!strcmp(key, "physics_lds")) *value = c->ph.nb ? (int)rzphys::lds_bytes((int)c->ph.nb, (int)c->ph.nj, c->ph.block, c->ph.springs.lin.p != nullptr) : 0;
-    else if (!strcmp(key, "override_follow")) *value = c->ovr_follow;
-    else if (!strcmp(key, "override_followers")) *value = solve_stages(c).fo.off ? (int)c->fol_count : 0;     // entries resident over all instances
-    else if (!strcmp(key, "after_physics")) *value = (int)c->af.n;         // entries resident (rz_upload_after_physics)
-    else if (!strcmp(key, "after_physics_levels")) *value = (int)c->af.levels;
-    else if (!strcmp(key, "ik_stages")) *value = (int)c->ik.stages;
-    else if (!strcmp(key, "ik_switched")) *value = (int)c->iksw.off;       // (instance, chain) bits currently off
-    else if (!strcmp(key, "ik_key_sets")) {
-        int n = c->ik_keys_an.resident ? 1 : 0;
-        for (const RzIkKeySet &s : c->ik_keys_mo) n += s.resident ? 1 : 0;
-        *value = n;
-    }
-    else if (!strcmp(key, "morph_mode")) *value = c->morphs.mode;
-    else if (!strcmp(key, "effective_morph_storage")) *value = c->morphs.mode == 1 ? c->morphs.storage : 0;
-    else if (!strcmp(key, "effective_nt")) *value = make_plan(c).v.nt && c->morphs.mode == 1 ? 1 : 0;
-    else if (!strcmp(key, "effective_nt_store")) *value = make_plan(c).v.nts ? 1 : 0;
-    else if (!strcmp(key, "effective_geo")) *value = make_plan(c).v.geo ? 1 : 0;
-    else if (!strcmp(key, "effective_prep")) { const Plan pl = make_plan(c); *value = ((pl.prep || c->pl.cur.local) && !pl.fuse_fk && !pl.subfk) ? 1 : 0; }
-    else if (!strcmp(key, "effective_split")) *value = make_plan(c).v.S;
-    else if (!strcmp(key, "effective_unroll")) *value = make_plan(c).v.U;
-    else if (!strcmp(key, "effective_fast")) *value = make_plan(c).v.fast ? 1 : 0;
-    else if (!strcmp(key, "effective_variant")) {
-        // the last template argument of the single-mesh frame kernel the next frame launches (kernels/deform_small.hip / deform_dense.hip:
-        // launch_one): 0 everything compiled in, 3 without the fused consumers, 1 / 2 without them and with the specialised solve
-        Plan pl;
-        if (int r = frame_plan(c, &pl)) return r;
-        const RzDeformParams dp = deform_params(c, pl);
-        const bool shapes = !pl.v.geo && (pl.v.mode != 1 || (pl.v.nt && pl.v.U == 8));
-        *value = (!shapes || dp.edge || dp.aabb) ? 0 : ((!pl.v.fast && dp.fk_on && (dp.fk_kind == 1 || dp.fk_kind == 2)) ? dp.fk_kind : 3);
-    }
-    else if (!strcmp(key, "effective_fk_kind")) { Plan pl; if (int r = frame_plan(c, &pl)) return r; *value = deform_params(c, pl).fk_kind; }
-    else if (!strcmp(key, "pose_pulled")) *value = c->pl.last_pulled ? 1 : 0;      // the most recent copied pose came down by rz_pull_pose_kernel ...
-    else if (!strcmp(key, "pose_rows")) *value = c->pl.last_rows ? 1 : 0;          // ... its world matrices as three rows per bone
-    else if (!strcmp(key, "effective_fuse_fk")) { const Plan pl = make_plan(c); *value = (pl.fuse_fk || pl.subfk) ? 1 : 0; }
-    else if (!strcmp(key, "effective_closure_bones")) *value = make_plan(c).subfk ? (int)c->subfk_stride : 0;
-    else if (!strcmp(key, "effective_closure_rounds")) *value = make_plan(c).subfk ? (int)c->subfk_rounds : 0;      // radix-4 doubling rounds of that front (0 .. 3)
-    else if (!strcmp(key, "pose_resident")) *value = c->pl.cur.resident() ? 1 : 0;
-    else if (!strcmp(key, "effective_overlap")) *value = want_overlap(c, make_plan(c)) ? 1 : 0;
-    else if (!strcmp(key, "effective_inst_block")) *value = make_plan(c).inst_block;
-    else if (!strcmp(key, "effective_out_cap")) *value = (int)make_plan(c).out_cap;
-    else if (!strcmp(key, "effective_sparse_piece")) *value = (int)make_plan(c).sp_cap;      // 0 without resident sparse targets (make_plan sizes it for MODE 2 only)
-    else if (!strcmp(key, "effective_inst_group")) *value = make_plan(c).inst_group;
-    else if (!strcmp(key, "effective_poses_per_wg")) *value = make_plan(c).poses_per_wg;
-    else if (!strcmp(key, "effective_grid")) *value = (int)make_plan(c).grid_x;
-    else if (!strcmp(key, "all_variants")) *value = rz_has_all_variants() ? 1 : 0;
-    else if (!strcmp(key, "pose_staged")) {
-        // did the helper of an earlier frame stage the CURRENT pose in device memory? (synchronises; for tests and tools)
-        *value = 0;
-        if (c->pl.tag && c->pl.cur.seq) {
-            uint64_t tags[2] = {0, 0};
-            HIP_TRY(hipSetDevice(c->device));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipMemcpy(tags, c->pl.tag, sizeof tags, hipMemcpyDeviceToHost));
-            *value = tags[c->pl.pose_slot] == c->pl.cur.seq ? 1 : 0;
-        }
-    }
-    else if (!strncmp(key, "addr_", 5)) {
-        // diagnostics (tools/archive/placement.py): where the allocator put a buffer — bits [12, 43) of its device address, i.e. the address in
-        // 4 KB pages (where a buffer lands relative to the 2 MB large-page frame moves the C5 frame by 3 %: NOTEBOOK.md R5.3)
-        const void *ptr = !strcmp(key, "addr_dense") ? (const void *)c->morphs.dense : !strcmp(key, "addr_out") ? (const void *)c->out_pos :
-                          !strcmp(key, "addr_nrm") ? (const void *)c->out_nrm : !strcmp(key, "addr_geom") ? (const void *)c->mesh.geom : nullptr;
-        if (!ptr && strcmp(key, "addr_dense") && strcmp(key, "addr_out") && strcmp(key, "addr_nrm") && strcmp(key, "addr_geom")) return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
-        *value = (int)(((uintptr_t)ptr >> 12) & 0x7fffffffu);
-    }
-    else if (!strcmp(key, "effective_subsets")) *value = make_plan(c).subsets ? 1 : 0;
-    else if (!strcmp(key, "effective_subset_bones")) *value = (int)make_plan(c).sub_bones;
-    else if (!strcmp(key, "effective_inst_lds")) *value = (int)make_plan(c).inst_lds;
-    else if (!strcmp(key, "effective_inst_morphs")) *value = make_plan(c).inst_morphs ? 1 : 0;     // the frame walks sparse morph rows in a crowd kernel
-    else return fail(RZ_ERR_INVALID, "unknown tuning key '%s'", key);
-    return RZ_OK;
+    return row->get(c, n, value);
 }
 
 }  // extern "C"

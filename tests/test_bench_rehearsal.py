@@ -97,7 +97,7 @@ STUB = textwrap.dedent('''
             _log("time_frames", frames)
             ms = self._frame_s() * 1e3
             return dict(frame_ms=ms, deform_kernel_ms=ms * 0.98, prep_kernel_ms=0.0, verts_per_frame=self.V, algorithmic_bytes_per_frame=self.V * 828, frames=frames)
-        def kernel_name(self): return "rz_deform_dense_kernel<4, 8, true, false, false, true>"
+        def kernel_name(self): return "rz_deform_dense_kernel<4, 8, true, false, false, true, 3>"
         def comm_init(self, nranks, rank, uid, v_total):
             _log("comm_init")
             if MODE == "fail": raise capi.RzError(-4, "ncclCommInitRank failed: unhandled system error (stand-in)")
